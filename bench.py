@@ -9,6 +9,11 @@ One "step" = one full ``generate_diffusion_cond`` call on this rank's prompts: c
 N > 1 one RCCL all-gather of the int16 audio.  Prompts are sharded rank-strided (reference generate.py:119-120),
 one full model replica per GPU, no collective on the data path except that final gather -> weak scaling.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (``ms_per_step`` = wall milliseconds of one timed step).
+``--dump-outputs DIR`` writes what the last timed step returned (the int16 audio, as float32 .npy) for output-for-output comparisons of
+two builds: the weights, prompts and seeds depend only on the arguments.  ``--full`` adds what takes runs of its own: the FFN-in
+GEMM's roofline figures (a HIP-event profiled pass after the timed steps) and, at one GPU, the CPU baseline.
 """
 import argparse
 import ctypes
@@ -131,6 +136,37 @@ def cpu_baseline(sd):
                       f"43 frames ({t_dec:.2f} s) x(1024/43), extrapolated"}
 
 
+def roofline(args, tot_ms, launches, m, n, k):
+    """--full: the FFN-in GEMM's figures from the profiled pass (total HIP-event milliseconds over `launches` launches of M x N x K)"""
+    avg_ms = tot_ms / max(launches, 1)
+    flops = 2.0 * m * n * k          # algorithmic FLOPs of one launch (SURVEY 8d: ff_in 38.69 GFLOP/seq/layer)
+    achieved = flops / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+    # HBM traffic of the dominant kernel cannot be measured inside a timed run (PMC passes serialise the kernels): it is the
+    # figure of the latest committed rocprofv3 --pmc pass of this same command (FETCH_SIZE x2 + WRITE_SIZE, separate passes)
+    traffic, traffic_source = None, None
+    import glob
+    for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_ffn_traffic.json")), reverse=True):          # newest round first
+        tname = os.path.basename(tpath)
+        if os.path.exists(tpath) and args.batch == 1 and args.dtype in ("bf16", "fp16") and args.workload == "sa_open":
+            traffic = json.load(open(tpath)).get("hbm_bytes_per_launch")
+            traffic_source = f"profiles/{tname} (rocprofv3 --pmc passes of this command, not measured in this run)"
+            break
+    mfma_peak = FP8_MFMA_PEAK_TFLOPS if args.dtype.startswith("fp8") else BF16_MFMA_PEAK_TFLOPS          # fp16 and bf16 MFMAs: the same dense peak
+    # The dense peak is quoted at 2.4 GHz; under the 1400 W cap this launch runs at the EFFECTIVE clock of the latest committed GRBM_GUI_ACTIVE pass
+    # (profiles/rNN_clock.json: a counter pass serialises the kernels, so it cannot be taken inside a timed run): the fraction is reported at both
+    eff_clock, clock_source = None, None
+    for cpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_clock.json")), reverse=True):
+        cj = json.load(open(cpath))
+        if args.workload == "sa_open" and args.dtype in ("bf16", "fp16") and str(args.batch) in cj.get("ffn_in_effective_clock_ghz", {}):
+            eff_clock = cj["ffn_in_effective_clock_ghz"][str(args.batch)] / cj.get("peak_clock_ghz", 2.4)
+            clock_source = f"profiles/{os.path.basename(cpath)} (effective clock {cj['ffn_in_effective_clock_ghz'][str(args.batch)]} GHz of {cj.get('peak_clock_ghz', 2.4)}; not measured in this run)"
+        break
+    return {"bound": "mfma", "kernel": f"FFN-in SwiGLU GEMM M={m} N={n} K={k} ({args.dtype} MFMA, fp32 acc)", "achieved": achieved,
+            "peak": mfma_peak, "unit": "TFLOP/s", "frac": achieved / mfma_peak,
+            "frac_at_effective_clock": (achieved / (mfma_peak * eff_clock)) if eff_clock else None, "effective_clock_source": clock_source, "traffic": traffic,
+            "traffic_source": traffic_source, "avg_launch_us": avg_ms * 1e3, "launches_timed": launches}
+
+
 # ---- the multi-rank logic, in functions of its own so that the CPU test (tests/test_bench_ranks.py, gloo, world size 2) runs exactly
 # what an 8-GPU launch runs, with the generation stubbed out
 def shard_prompts(world, rank, batch):
@@ -163,6 +199,27 @@ def stub_generation(prompt_ids, seed, dev):
     return torch.stack(rows).to(dev)
 
 
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32, so that two builds can be compared output for output.  Past DUMP_BYTES
+    in all, an array keeps a share of its elements at fixed indices (seeded: the same on every run), written flat, with the flat indices
+    in DIR/<name>_index.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.numel() for a in arrays.values()) * 4
+    for name, a in arrays.items():
+        a = a.detach().cpu().to(torch.float32)
+        if total > DUMP_BYTES:
+            keep = a.numel() * ((DUMP_BYTES - 4096) // 3) // total          # 4 bytes of value + 8 of index per element kept
+            g = torch.Generator().manual_seed(20241016)
+            idx = torch.unique(torch.randint(a.numel(), (keep,), generator=g))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.to(torch.float64).numpy())
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -170,7 +227,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=None,
                     help="prompts per GPU; default 1 at --gpus 1 (BASELINE config 2) and 8 at --gpus > 1 (config 3: 64 prompts on 8 GPUs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the FFN-in GEMM's roofline figures (a HIP-event "
+                         "profiled pass of --steps generations) and, at one GPU, the CPU baseline (the oracle on the host cores)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's int16 audio) to DIR/audio.npy as float32; a fixed, seeded "
+                         f"sample of it (DIR/audio.npy + DIR/audio_index.npy) if it exceeds {DUMP_BYTES // 10**6} MB")
     ap.add_argument("--dtype", choices=("bf16", "fp16", "fp8", "fp8-all"), default="fp16",
                     help="GEMM / attention / codec operand type: fp16 (default: the reference's own GPU arithmetic and the build that meets the "
                          "1e-3 target against its fp32 outputs), bf16 (the same kernels on the bf16 MFMAs: 3-4 %% faster, 8x the operand "
@@ -239,6 +302,8 @@ def main():
         elapsed = timed_steps(step, args.steps, use_dist, lambda: None, dev)
         if rank == 0:
             audio = last["audio"]
+            if args.dump_outputs:                          # what the real step returns on rank 0: its own prompts of the gathered batch
+                dump_outputs(args.dump_outputs, {"audio": audio[rank::world] if world > 1 else audio})
             print(json.dumps({"stub": True, "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
                               "rccl_ranks": world if use_dist else 0, "gathered_shape": list(audio.shape),
                               "gathered_first_samples": [int(v) for v in audio[:, 0, 0]], "prompt_ids_rank0": prompt_ids}), flush=True)
@@ -271,7 +336,8 @@ def main():
         g = torch.Generator(device="cpu").manual_seed(11)
         WORKLOAD["init_audio"] = (torch.rand(2, SAMPLE_SIZE, generator=g) - 0.5).to(dev)
         args.no_cpu_baseline = True
-    if rank != 0 or args.no_cpu_baseline:
+    cpu_base = args.full and world == 1 and not args.no_cpu_baseline
+    if rank != 0 or not cpu_base:
         sd = None
     # rank-strided prompt sharding, as the reference's generate.py:119-120
     prompt_ids = shard_prompts(world, rank, args.batch)
@@ -288,42 +354,30 @@ def main():
     lib = _hip.lib()
     for i in range(args.warmup):
         one_generation(model, cond, 1000 + i, dev, world)
-    dit._ensure_plan()                              # --warmup 0: the plan is otherwise built lazily by the first generation
-    _hip.check(lib.sat_dit_profile(dit._plan, 1))
-    elapsed = timed_steps(lambda seed: one_generation(model, cond, seed, dev, world), args.steps, use_dist, torch.cuda.synchronize, dev)
+    last = {}
 
-    # dominant kernel: FFN-in SwiGLU GEMM, timed live with HIP events on the launch stream (one layer per forward)
-    tot = ctypes.c_double()
-    cnt = ctypes.c_int32()
-    m, n, k = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-    _hip.check(lib.sat_dit_profile_read(dit._plan, ctypes.byref(tot), ctypes.byref(cnt), ctypes.byref(m), ctypes.byref(n), ctypes.byref(k)))
-    _hip.check(lib.sat_dit_profile(dit._plan, 0))
+    def step(seed):
+        last["audio"] = one_generation(model, cond, seed, dev, world)
+
+    elapsed = timed_steps(step, args.steps, use_dist, torch.cuda.synchronize, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+
+    if args.full:
+        # dominant kernel: FFN-in SwiGLU GEMM, timed live with HIP events on the launch stream (one layer per forward), in a pass of
+        # --steps generations of its own after the headline's timed steps (the events stay out of the headline)
+        dit._ensure_plan()                              # --warmup 0: the plan is otherwise built lazily by the first generation
+        _hip.check(lib.sat_dit_profile(dit._plan, 1))
+        for i in range(args.steps):
+            one_generation(model, cond, 3000 + i, dev, world)
+        tot = ctypes.c_double()
+        cnt = ctypes.c_int32()
+        m, n, k = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _hip.check(lib.sat_dit_profile_read(dit._plan, ctypes.byref(tot), ctypes.byref(cnt), ctypes.byref(m), ctypes.byref(n), ctypes.byref(k)))
+        _hip.check(lib.sat_dit_profile(dit._plan, 0))
 
     if rank == 0:
         audio_seconds = world * args.batch * (SAMPLE_SIZE / SAMPLE_RATE) * args.steps
-        avg_ms = tot.value / max(cnt.value, 1)
-        flops = 2.0 * m.value * n.value * k.value          # algorithmic FLOPs of one launch (ff_in 38.69 GFLOP/seq/layer)
-        achieved = flops / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-        # HBM traffic of the dominant kernel cannot be measured inside a timed run (PMC passes serialise the kernels): it is the
-        # figure of the latest committed rocprofv3 --pmc pass of this same command (FETCH_SIZE x2 + WRITE_SIZE, separate passes)
-        traffic, traffic_source = None, None
-        import glob
-        for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_ffn_traffic.json")), reverse=True):          # newest round first
-            tname = os.path.basename(tpath)
-            if os.path.exists(tpath) and args.batch == 1 and args.dtype in ("bf16", "fp16") and args.workload == "sa_open":
-                traffic = json.load(open(tpath)).get("hbm_bytes_per_launch")
-                traffic_source = f"profiles/{tname} (rocprofv3 --pmc passes of this command, not measured in this run)"
-                break
-        mfma_peak = FP8_MFMA_PEAK_TFLOPS if args.dtype.startswith("fp8") else BF16_MFMA_PEAK_TFLOPS          # fp16 and bf16 MFMAs: the same dense peak
-        # The dense peak is quoted at 2.4 GHz; under the 1400 W cap this launch runs at the EFFECTIVE clock of the latest committed GRBM_GUI_ACTIVE pass
-        # (profiles/rNN_clock.json: a counter pass serialises the kernels, so it cannot be taken inside a timed run): the fraction is reported at both
-        eff_clock, clock_source = None, None
-        for cpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_clock.json")), reverse=True):
-            cj = json.load(open(cpath))
-            if args.workload == "sa_open" and args.dtype in ("bf16", "fp16") and str(args.batch) in cj.get("ffn_in_effective_clock_ghz", {}):
-                eff_clock = cj["ffn_in_effective_clock_ghz"][str(args.batch)] / cj.get("peak_clock_ghz", 2.4)
-                clock_source = f"profiles/{os.path.basename(cpath)} (effective clock {cj['ffn_in_effective_clock_ghz'][str(args.batch)]} GHz of {cj.get('peak_clock_ghz', 2.4)}; not measured in this run)"
-            break
         line = {
             "metric": "audio-seconds/sec @44.1kHz stereo, 100-step DPM++, SA-Open-1.0 shape" if args.workload == "sa_open" else
                       "audio-seconds/sec @44.1kHz stereo, 100-step DPM++, SA-2.0 shape audio-to-audio (encode + sample + decode)",
@@ -345,13 +399,10 @@ def main():
                                    ("Stable Audio 2.0 shape (24 layers, D=1536, S=6145, CFG 7) audio-to-audio: Oobleck encode of 285.3 s init audio + "
                                     f"100 DPM-Solver++(3M) SDE steps from sigma 7 + decode, {args.batch} prompt(s)/GPU"), "prompts_per_gpu": args.batch,
                        "codec_dtype": codec_dtype, "sampler_steps": DIT_STEPS, "cfg_scale": CFG_SCALE, "layernorm": args.layernorm, "cross_attention": args.cross_attention, "sample_size": SAMPLE_SIZE, "parallelism": f"dp{world} (rank-strided prompts, one all-gather)"},
-            "roofline": {"bound": "mfma", "kernel": f"FFN-in SwiGLU GEMM M={m.value} N={n.value} K={k.value} ({args.dtype} MFMA, fp32 acc)", "achieved": achieved,
-                         "peak": mfma_peak, "unit": "TFLOP/s", "frac": achieved / mfma_peak,
-                         "frac_at_effective_clock": (achieved / (mfma_peak * eff_clock)) if eff_clock else None, "effective_clock_source": clock_source, "traffic": traffic,
-                         "traffic_source": traffic_source, "avg_launch_us": avg_ms * 1e3, "launches_timed": cnt.value},
+            **({"roofline": roofline(args, tot.value, cnt.value, m.value, n.value, k.value)} if args.full else {}),
             "rccl_ranks": world if use_dist else 0,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_base:
             line["cpu_baseline"] = cpu_baseline(sd)
         print(json.dumps(line), flush=True)
     if use_dist:

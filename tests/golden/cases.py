@@ -105,8 +105,70 @@ def vae_kwargs(v, decoder):
     return dict(in_channels=2, channels=v["channels"], c_mults=v["c_mults"], strides=v["strides"], latent_dim=128, use_snake=True)
 
 
+# No committed file may exceed 1 MiB.  A fixture larger than that is stored as name.part0.npz, name.part1.npz, ... (save()); an array
+# too large for one part is cut along its last axis into "key@0", "key@1", ... and load() joins the pieces again, bit for bit.
+PART_BYTES = 960 * 1024          # raw bytes per file: float32 noise barely compresses, so this bounds the file size as well
+
+
+def _paths(name):
+    single = os.path.join(GOLDEN_DIR, name + ".npz")
+    if os.path.exists(single):
+        return [single]
+    parts = []
+    while os.path.exists(os.path.join(GOLDEN_DIR, f"{name}.part{len(parts)}.npz")):
+        parts.append(os.path.join(GOLDEN_DIR, f"{name}.part{len(parts)}.npz"))
+    return parts
+
+
+def exists(name):
+    return bool(_paths(name))
+
+
 def load(name):
     import numpy as np
-    path = os.path.join(GOLDEN_DIR, name + ".npz")
-    with np.load(path) as z:
-        return {k: torch.from_numpy(z[k]) for k in z.files}
+    paths = _paths(name)
+    if not paths:
+        raise FileNotFoundError(os.path.join(GOLDEN_DIR, name + ".npz"))
+    arrays = {}
+    for path in paths:
+        with np.load(path) as z:
+            arrays.update({k: z[k] for k in z.files})
+    out = {}
+    for k, a in arrays.items():
+        base, cut, j = k.rpartition("@")
+        if not cut:
+            out[k] = torch.from_numpy(a)
+        elif j == "0":
+            pieces = []
+            while f"{base}@{len(pieces)}" in arrays:
+                pieces.append(arrays[f"{base}@{len(pieces)}"])
+            out[base] = torch.from_numpy(np.concatenate(pieces, axis=-1))
+    return out
+
+
+def save(name, arrays):
+    """Writes {key: numpy array} as name.npz, or as parts of at most PART_BYTES each; returns the paths written."""
+    import numpy as np
+    for stale in _paths(name):
+        os.remove(stale)
+    pieces = []
+    for k, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes <= PART_BYTES:
+            pieces.append((k, a))
+            continue
+        cols = PART_BYTES // (a.nbytes // a.shape[-1])
+        assert cols >= 1, f"{name}/{k}: one last-axis column of {a.shape} holds more than {PART_BYTES} bytes"
+        pieces += [(f"{k}@{j}", a[..., s:s + cols]) for j, s in enumerate(range(0, a.shape[-1], cols))]
+    groups, size = [[]], 0
+    for k, a in pieces:
+        if groups[-1] and size + a.nbytes > PART_BYTES:
+            groups.append([])
+            size = 0
+        groups[-1].append((k, a))
+        size += a.nbytes
+    paths = ([os.path.join(GOLDEN_DIR, name + ".npz")] if len(groups) == 1 else
+             [os.path.join(GOLDEN_DIR, f"{name}.part{i}.npz") for i in range(len(groups))])
+    for path, group in zip(paths, groups):
+        np.savez_compressed(path, **dict(group))
+    return paths

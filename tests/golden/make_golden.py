@@ -31,9 +31,9 @@ rgen = R.ref("inference.generation")
 
 
 def save(name, **arrays):
-    path = os.path.join(cases.GOLDEN_DIR, name + ".npz")
-    np.savez_compressed(path, **{k: v.detach().cpu().numpy() for k, v in arrays.items()})
-    print(f"wrote {path}: {os.path.getsize(path)/1024:.0f} KiB  " + ", ".join(f"{k}{tuple(v.shape)}" for k, v in arrays.items()))
+    paths = cases.save(name, {k: v.detach().cpu().numpy() for k, v in arrays.items()})
+    print(f"wrote {', '.join(paths)}: {sum(os.path.getsize(p) for p in paths)/1024:.0f} KiB  " +
+          ", ".join(f"{k}{tuple(v.shape)}" for k, v in arrays.items()))
 
 
 def load_synth(module, seed):

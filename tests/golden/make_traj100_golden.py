@@ -43,7 +43,8 @@ def main():
     del dit
     c, g, noise, step_noise = cases.traj100_inputs(variant)
     sig = osamp.get_sigmas_polyexponential(T100["steps"], T100["sigma_min"], T100["sigma_max"], 1.0)
-    path = os.path.join(cases.GOLDEN_DIR, "traj100_full.npz" if variant == 0 else f"traj100_full_v{variant}.npz")
+    fixture = "traj100_full" if variant == 0 else f"traj100_full_v{variant}"
+    path = os.path.join(cases.GOLDEN_DIR, fixture + ".npz")
     out = {}
     t0 = time.time()
 
@@ -61,9 +62,9 @@ def main():
     print(f"trajectory: {time.time() - t0:.0f} s, final std {x.std():.4f}", flush=True)
     del sd
     if variant != 0:
-        np.savez_compressed(path, **out)
+        paths = cases.save(fixture, out)
         os.remove(path + ".partial.npz")
-        print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+        print("wrote", ", ".join(paths), sum(os.path.getsize(p) for p in paths) // 1024, "KiB")
         return
     with _init.skip_init():
         dec = OobleckDecoder(**cases.vae_kwargs(cases.FULL_VAE, True))
@@ -73,9 +74,9 @@ def main():
     print(f"decode: audio {tuple(audio.shape)} std {audio.std():.4f}  {time.time() - t0:.0f} s", flush=True)
     for name, s0 in T100["audio_windows"].items():
         out[f"audio_{name}"] = audio[:, :, s0:s0 + T100["audio_window_len"]].numpy().astype(np.float32)
-    np.savez_compressed(path, **out)
+    paths = cases.save(fixture, out)
     os.remove(path + ".partial.npz")
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+    print("wrote", ", ".join(paths), sum(os.path.getsize(p) for p in paths) // 1024, "KiB")
 
 
 if __name__ == "__main__":

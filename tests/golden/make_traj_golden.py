@@ -39,10 +39,9 @@ def main():
     out = {}
     hooks = (("fp32", None), ("bf16", odit.LnFoldRounding()), ("fp8", odit.Fp8Rounding()), ("fp8all", odit.Fp8Rounding(odit.FP8_FAMILIES)),
              ("fp16", odit.LnFoldRoundingF16()))
-    path = os.path.join(cases.GOLDEN_DIR, "traj_full.npz")
     only = sys.argv[1:]                 # e.g. `make_traj_golden.py fp16`: add these runs to the existing file, leave the others as they are
     if only:
-        out.update({k: v for k, v in np.load(path).items()})
+        out.update({k: v.numpy() for k, v in cases.load("traj_full").items()})
         hooks = tuple(h for h in hooks if h[0] in only)
     for tag, rnd in hooks:
         t0 = time.time()
@@ -58,8 +57,8 @@ def main():
         for i in SNAP:
             out[f"{tag}_step{i}"] = snaps[i].numpy().astype(np.float32)
         print(f"{tag}: {time.time() - t0:.0f} s, final std {x.std():.4f}", flush=True)
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+    paths = cases.save("traj_full", out)
+    print("wrote", ", ".join(paths), sum(os.path.getsize(p) for p in paths) // 1024, "KiB")
     for i in SNAP:
         a = torch.from_numpy(out[f"fp32_step{i}"])
         print(f"step {i}: " + "   ".join(f"{t}-matched vs fp32 {((torch.from_numpy(out[f'{t}_step{i}']) - a).norm() / a.norm()).item():.3e}"

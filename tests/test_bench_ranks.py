@@ -72,3 +72,51 @@ def test_bench_rejects_mismatched_world():
     env = dict(os.environ, SAT_BENCH_STUB="1", WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "4"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_stub(tmp_path):
+    """--dump-outputs writes what the last timed step returned, as float32, identical from run to run with the same arguments"""
+    import numpy as np
+    got = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        line = _run(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "3", "--dump-outputs", str(out)], {"SAT_BENCH_STUB": "1"})
+        assert line["steps"] == 2
+        a = np.load(out / "audio.npy")
+        assert a.dtype == np.float32 and a.shape == (3, 2, 64)
+        got.append(a)
+    seed = 2000 + 2 - 1                                                  # the last timed step
+    assert [int(v) for v in got[0][:, 0, 0]] == [(pid * 131 + seed) % 30000 for pid in range(3)]
+    assert np.array_equal(got[0], got[1])
+
+
+def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
+    """past the size budget: a fixed, seeded sample of the elements and their flat indices, within the budget, the same on every call"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 60000)
+    a = torch.arange(3 * 2 * 5000, dtype=torch.int16).reshape(3, 2, 5000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"audio": a})
+    files = {d: (np.load(tmp_path / d / "audio.npy"), np.load(tmp_path / d / "audio_index.npy")) for d in ("a", "b")}
+    vals, idx = files["a"]
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and len(vals) == len(idx) > 0
+    assert np.array_equal(vals, a.reshape(-1).float().numpy()[idx.astype(np.int64)])
+    assert np.array_equal(vals, files["b"][0]) and np.array_equal(idx, files["b"][1])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in ("audio.npy", "audio_index.npy")) <= 60000
+
+
+def test_bench_dump_outputs_world2_rank0_shard(tmp_path):
+    """at N > 1 the dump holds what the timed step returns on rank 0: its own prompts (rank-strided) of the gathered batch"""
+    import numpy as np
+    world, batch, steps = 2, 3, 2
+    line = _run(["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port",
+                 str(_free_port()), "bench.py", "--gpus", str(world), "--steps", str(steps), "--warmup", "0", "--batch", str(batch),
+                 "--dump-outputs", str(tmp_path)], {"SAT_BENCH_STUB": "1"})
+    assert line["gathered_shape"] == [world * batch, 2, 64]
+    a = np.load(tmp_path / "audio.npy")
+    assert a.dtype == np.float32 and a.shape == (batch, 2, 64)
+    seed = 2000 + steps - 1
+    assert [int(v) for v in a[:, 0, 0]] == [(pid * 131 + seed) % 30000 for pid in (0, 2, 4)]

@@ -708,9 +708,8 @@ def test_full_size_dit_vs_reference_golden(dev, full_dit, t_len, gemm_dtype):
     the reference itself).  fp16 operands (round 4; the reference's own GPU arithmetic): north_star's 1e-3."""
     import cases
     import os
-    path = os.path.join(cases.GOLDEN_DIR, f"dit_full_T{t_len}.npz")
-    if not os.path.exists(path):
-        pytest.skip(f"{os.path.basename(path)} not generated")
+    if not cases.exists(f"dit_full_T{t_len}"):
+        pytest.skip(f"dit_full_T{t_len}.npz not generated")
     want = cases.load(f"dit_full_T{t_len}")["out"]
     x, t, c, g = cases.dit_inputs(1, t_len, 768, 1536, 1)
     full_dit.set_gemm_dtype(gemm_dtype)
@@ -793,8 +792,7 @@ def test_full_size_trajectory(dev, full_dit, gemm_dtype):
     import os
     if os.environ.get("SAT_SKIP_SLOW") == "1":
         pytest.skip("SAT_SKIP_SLOW=1")
-    path = os.path.join(cases.GOLDEN_DIR, "traj_full.npz")
-    if not os.path.exists(path):
+    if not cases.exists("traj_full"):
         pytest.skip("traj_full.npz not generated")
     from stable_audio_tools.inference.sampling import sample_k
     from stable_audio_tools.models.diffusion import DiTWrapper
@@ -1011,7 +1009,7 @@ def test_fp32x_mode_vs_reference_golden(dev, full_dit, small_dit):
         e7 = assert_close("fp32x full-size DiT T=1024 CFG 7 vs reference", got, gold["cfg7"], 1e-3)
         import os
         e6 = float("nan")
-        if os.path.exists(os.path.join(cases.GOLDEN_DIR, "dit_full_T6144.npz")):
+        if cases.exists("dit_full_T6144"):
             x, t, c, g = cases.dit_inputs(1, 6144, 768, 1536, 1)
             got = full_dit(x.to(dev), t.to(dev), cross_attn_cond=c.to(dev), global_embed=g.to(dev), cfg_scale=1.0)
             e6 = assert_close("fp32x full-size DiT T=6144 vs reference", got, cases.load("dit_full_T6144")["out"], 1e-3)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One parametrised GPU-box session (run through gpurun from the repo root):   tools/gpu_session.sh <stage> [args...]
 #   pytest [-k expr]        the -m gpu parity suite                          -> gpurun_out/${TAG}_pytest.log
-#   bench [bench.py args]   one bench line                                   -> gpurun_out/${TAG}_bench.json
+#   bench [bench.py args]   one bench.py --full line (roofline + CPU baseline), on stdout
 #   stats [bench.py args]   rocprofv3 --kernel-trace --stats of bench.py     -> gpurun_out/${TAG}_kernel_stats.csv + _summary.md
 #   pmc                     FETCH_SIZE / WRITE_SIZE / SQ counter passes of tools/gpu_probe.py full (separate passes, no traces)
 #   probe <sections...>     tools/ph8_probe.py sections with the experiments build
@@ -25,7 +25,7 @@ case $stage in
       echo "pytest[$fmt] rc=$?" >> gpurun_out/${TAG}_pytest_$fmt.log; tail -3 gpurun_out/${TAG}_pytest_$fmt.log
     done ;;
   bench)
-    timeout 900 python bench.py "$@" > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; cut -c1-400 gpurun_out/${TAG}_bench.json ;;
+    timeout 900 python bench.py --full "$@" ;;
   stats)
     cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_$TAG
     timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@" > $R/gpurun_out/${TAG}_stats_bench.json 2> $R/gpurun_out/${TAG}_stats.err
