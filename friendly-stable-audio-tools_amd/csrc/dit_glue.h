@@ -9,6 +9,10 @@ int glue_fold_in(const float* Win, const float* Wpre, float* Weff, int D, int C,
 int glue_fold_out(const float* Wout, const float* Wpost, float* Weff, int D, int C, hipStream_t s);
 int glue_input_proj(const float* x, const float* Weff, float* X, int Bf, int xB, int C, int T, int S, int D, float xscale,
                     hipStream_t s);
+// the same launch for a model with input-concat / prepend conditioning: + W_c concat (nearest-resized from Tc frames, unscaled) and the
+// P prepared prepend rows copied to X[b, 0..P-1]; S = P + 1 + T
+int glue_input_proj_extra(const float* x, const float* Weff, float* X, int Bf, int xB, int C, int T, int S, int D, float xscale,
+                          const float* concat, int Cc, int Tc, const float* prep, int P, hipStream_t s);
 int glue_output_proj(const float* X, const float* Weff, float* out, int Bf, int C, int T, int S, int D, hipStream_t s);
 int glue_cfg_denoise(const float* mo, const float* x, float* den, int B, int C, int T, int use_cfg, float cfg_scale,
                      float scale_phi, float c_out, float c_skip, hipStream_t s);

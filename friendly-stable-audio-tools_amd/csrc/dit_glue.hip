@@ -107,12 +107,33 @@ __global__ __launch_bounds__(256) void adaln_finish_kernel(float* __restrict__ s
 // time steps are the SAME for every lane, so they are read through wave-uniform addresses -- scalar loads into SGPRs, consumed as
 // the scalar operand of v_fmac: no LDS traffic at all (a first version broadcast them from LDS and was bound by the LDS pipe: one
 // 16-byte broadcast read per 4 FMAs is twice what four SIMDs can be fed).  Stores are row-contiguous (1 KiB per wave).
+//
+// EXTRA (models with input-concat / prepend conditioning; the plain models run EXTRA = false, the code above unchanged):
+//  - the Cc concat channels follow the C latent channels in WeffT (project_in o (I + preprocess_conv) over cat([x, c]), dit.py:173,197)
+//    and are added unscaled: X = xscale * (W_x x) + W_c c (k-diffusion's VDenoiser scales x only; c travels in the kwargs).  c is
+//    [Bf][Cc][Tc], read at the nearest-neighbour source frame of F.interpolate(mode='nearest') (dit.py:170):
+//    src = min(floor(t * scale), Tc - 1) with the fp32 scale = (float)Tc / T;
+//  - workgroups with blockIdx.x >= cdiv(T, IP_TT) copy the P prepared prepend rows prep[b][p][:] to X[b, p, :] (dit.py:185-195).
 constexpr int IP_TT = 8;       // measured at T = 1024: 32 -> 19.6 us, 16 -> 15.3, 8 -> 12.5, 4 -> 18.0
+template <bool EXTRA>
 __global__ __launch_bounds__(256) void input_proj_kernel(const float* __restrict__ x, const float* __restrict__ WeffT,
-                                                         float* __restrict__ X, int xB, int C, int T, int S, int D, float xscale) {
+                                                         float* __restrict__ X, int xB, int C, int T, int S, int D, float xscale,
+                                                         const float* __restrict__ cc, int Cc, int Tc, float cscale,
+                                                         const float* __restrict__ prep, int P) {
     const int b = blockIdx.z;
-    const int t0 = blockIdx.x * IP_TT;
     const int n = blockIdx.y * 256 + threadIdx.x;
+    if constexpr (EXTRA) {
+        const int nt = (T + IP_TT - 1) / IP_TT;
+        if ((int)blockIdx.x >= nt) {        // prepend rows
+            const int p0 = (blockIdx.x - nt) * IP_TT;
+            if (n >= D) return;
+#pragma unroll
+            for (int pp = 0; pp < IP_TT; ++pp)
+                if (p0 + pp < P) X[((size_t)b * S + p0 + pp) * D + n] = prep[((size_t)b * P + p0 + pp) * D + n];
+            return;
+        }
+    }
+    const int t0 = blockIdx.x * IP_TT;
     const float* __restrict__ xb = x + (size_t)(b % xB) * C * T + t0;      // wave-uniform
     if (n >= D) return;
     float acc[IP_TT];
@@ -133,6 +154,39 @@ __global__ __launch_bounds__(256) void input_proj_kernel(const float* __restrict
 #pragma unroll
             for (int tt = 0; tt < IP_TT; ++tt) acc[tt] += w * (t0 + tt < T ? xr[tt] : 0.f);
         }
+    }
+    if constexpr (EXTRA) {
+        float accc[IP_TT];
+        int src[IP_TT];
+#pragma unroll
+        for (int tt = 0; tt < IP_TT; ++tt) {
+            accc[tt] = 0.f;
+            const int t = t0 + tt < T ? t0 + tt : T - 1;
+            const int si = Tc == T ? t : (int)floorf((float)t * cscale);
+            src[tt] = si < Tc - 1 ? si : Tc - 1;
+        }
+        const float* __restrict__ cb = cc + (size_t)b * Cc * Tc;       // wave-uniform
+        if (Tc == T && t0 + IP_TT <= T) {     // no resize (the inpainting case): the contiguous reads of the latent loop
+            const float* __restrict__ cbt = cb + t0;
+#pragma unroll 4
+            for (int c = 0; c < Cc; ++c) {
+                const float w = WeffT[(size_t)(C + c) * D + n];
+                const float* __restrict__ cr = cbt + (size_t)c * Tc;
+#pragma unroll
+                for (int tt = 0; tt < IP_TT; ++tt) accc[tt] += w * cr[tt];
+            }
+        } else {
+            for (int c = 0; c < Cc; ++c) {
+                const float w = WeffT[(size_t)(C + c) * D + n];
+                const float* __restrict__ cr = cb + (size_t)c * Tc;
+#pragma unroll
+                for (int tt = 0; tt < IP_TT; ++tt) accc[tt] += w * cr[src[tt]];
+            }
+        }
+#pragma unroll
+        for (int tt = 0; tt < IP_TT; ++tt)
+            if (t0 + tt < T) X[((size_t)b * S + (S - T) + t0 + tt) * D + n] = acc[tt] * xscale + accc[tt];
+        return;
     }
 #pragma unroll
     for (int tt = 0; tt < IP_TT; ++tt)
@@ -383,7 +437,21 @@ int glue_fold_out(const float* Wout, const float* Wpost, float* Weff, int D, int
 int glue_input_proj(const float* x, const float* Weff, float* X, int Bf, int xB, int C, int T, int S, int D, float xscale,
                     hipStream_t s) {
     SAT_CHECK_ARG(C <= 64, SAT_E_UNSUPPORTED, "input_proj: io_channels %d > 64", C);
-    hipLaunchKernelGGL(input_proj_kernel, dim3(cdiv(T, IP_TT), cdiv(D, 256), Bf), dim3(256), 0, s, x, Weff, X, xB, C, T, S, D, xscale);
+    hipLaunchKernelGGL(input_proj_kernel<false>, dim3(cdiv(T, IP_TT), cdiv(D, 256), Bf), dim3(256), 0, s, x, Weff, X, xB, C, T, S, D, xscale,
+                       nullptr, 0, 1, 1.0f, nullptr, 0);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int glue_input_proj_extra(const float* x, const float* Weff, float* X, int Bf, int xB, int C, int T, int S, int D, float xscale,
+                          const float* concat, int Cc, int Tc, const float* prep, int P, hipStream_t s) {
+    SAT_CHECK_ARG(C <= 64, SAT_E_UNSUPPORTED, "input_proj: io_channels %d > 64", C);
+    SAT_CHECK_ARG(P >= 0 && (S == P + 1 + T || (P == 0 && S == T)) && (P == 0 || prep) && (Cc == 0 || (concat && Tc > 0)), SAT_E_INVALID,
+                  "input_proj: bad extra conditioning (S %d, P %d, T %d, Cc %d, Tc %d)", S, P, T, Cc, Tc);
+    if (!concat) Cc = 0;
+    const float cscale = Cc ? (float)Tc / (float)T : 1.0f;     // F.interpolate's fp32 scale (input size / output size)
+    hipLaunchKernelGGL(input_proj_kernel<true>, dim3(cdiv(T, IP_TT) + cdiv(P, IP_TT), cdiv(D, 256), Bf), dim3(256), 0, s, x, Weff, X, xB, C,
+                       T, S, D, xscale, concat, Cc, Cc ? Tc : 1, cscale, prep, P);
     SAT_LAUNCH_CHECK();
     return 0;
 }

@@ -117,6 +117,9 @@ struct sat_dit_plan {
     // gemm_dtype == 1: which GEMM families take e4m3 operands (sat_dit_cfg.fp8_families; SAT_FP8_* bits); 0 in every other mode
     bool f8_qkv = false, f8_cq = false, f8_ff1 = false, f8_ff2 = false, f8_o = false;
     float* ssg_w = nullptr;         // adaLN: [depth * 6D, D] stacked to_scale_shift_gate weights
+    // input-concat / prepend conditioning (sat_dit_plan_set_extra_conditioning): win_eff then spans io_channels + concat_dim input channels
+    int concat_dim = 0, prepend_dim = 0, max_prep = 0;
+    float *pe0_w = nullptr, *pe2_w = nullptr;      // to_prepend_embed.0 / .2 (dit.py:160-165)
     // per-generation context (sat_dit_prepare_context)
     char* ctx_buf = nullptr;
     size_t ctx_cap = 0;
@@ -128,6 +131,17 @@ struct sat_dit_plan {
     op_t* vct = nullptr;          // [depth][bf, kvh, 64, lcpad]
     float* kc32 = nullptr;          // fp32 verification mode: [depth][bf, kvh, lc, 64]
     float* vc32 = nullptr;
+    // per-generation extra conditioning (sat_dit_prepare_extra_conditioning); reset by every sat_dit_prepare_context
+    char* ext_buf = nullptr;
+    size_t ext_cap = 0;
+    bool ext_ready = false;
+    const float* ext_concat = nullptr;   // [ctx_bf, concat_dim, ext_concat_len] (a copy in ext_buf)
+    int ext_concat_len = 0;
+    float* ext_prep = nullptr;           // [ctx_bf, ctx_prep, D] to_prepend_embed(prepend_cond)
+    int ctx_prep = 0;                    // P: prepend tokens of the prepared generation
+    // sat_dit_workspace_bytes of a plan with prepend conditioning maximises over P = 0..max_prep: the last (bf, t_len) asked is cached
+    mutable int wsq_bf = -1, wsq_t = -1;
+    mutable size_t wsq_bytes = 0;
     // optional HIP-event timing of the FFN-in (SwiGLU) GEMM of one layer per forward (sat_dit_profile)
     bool prof_on = false;
     int prof_n = 0;
@@ -139,6 +153,10 @@ struct sat_dit_plan {
 static const int kProfMaxPairs = 4096;
 
 namespace {
+
+// Rows of one sequence in the residual stream: [P prepend tokens | global token | T latent frames] (dit.py:185-197), no global
+// token under adaLN (P is 0 there: sat_dit_plan_set_extra_conditioning rejects adaLN + prepend)
+int seq_len(const sat_dit_plan* p, int T, int P) { return P + T + (p->cfg.adaln ? 0 : 1); }
 
 int get_tensor(sat_dit_plan* p, const std::string& name, int64_t numel, const float** out) {
     auto it = p->tensors.find(name);
@@ -207,19 +225,24 @@ int build(sat_dit_plan* p, Arena& ar, hipStream_t s) {
         SAT_TRY(copy_f32(p, ar, "to_global_embed.0.weight", (int64_t)D * Dg, &p->ge0_w, s));
         SAT_TRY(copy_f32(p, ar, "to_global_embed.2.weight", (int64_t)D * D, &p->ge2_w, s));
     }
+    if (p->prepend_dim > 0) {
+        SAT_TRY(copy_f32(p, ar, "to_prepend_embed.0.weight", (int64_t)D * p->prepend_dim, &p->pe0_w, s));
+        SAT_TRY(copy_f32(p, ar, "to_prepend_embed.2.weight", (int64_t)D * D, &p->pe2_w, s));
+    }
     SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 16, &p->inv_freq, s));
-    p->win_eff = (float*)ar.take((size_t)D * C * 4);
+    const int Ci = C + p->concat_dim;       // preprocess_conv / project_in see cat([x, input_concat_cond]) (dit.py:38,130,173)
+    p->win_eff = (float*)ar.take((size_t)D * Ci * 4);
     p->wout_eff = (float*)ar.take((size_t)D * C * 4);
-    const int smax = c.max_seq_len + 1;
+    const int smax = seq_len(p, c.max_seq_len, p->max_prep);
     p->rope_cos = (float*)ar.take((size_t)smax * 16 * 4);
     p->rope_sin = (float*)ar.take((size_t)smax * 16 * 4);
     if (!ar.dry) {
         const float *win, *wpre, *wout, *wpost;
-        SAT_TRY(get_tensor(p, "transformer.project_in.weight", (int64_t)D * C, &win));
-        SAT_TRY(get_tensor(p, "preprocess_conv.weight", (int64_t)C * C, &wpre));
+        SAT_TRY(get_tensor(p, "transformer.project_in.weight", (int64_t)D * Ci, &win));
+        SAT_TRY(get_tensor(p, "preprocess_conv.weight", (int64_t)Ci * Ci, &wpre));
         SAT_TRY(get_tensor(p, "transformer.project_out.weight", (int64_t)D * C, &wout));
         SAT_TRY(get_tensor(p, "postprocess_conv.weight", (int64_t)C * C, &wpost));
-        SAT_TRY(glue_fold_in(win, wpre, p->win_eff, D, C, s));
+        SAT_TRY(glue_fold_in(win, wpre, p->win_eff, D, Ci, s));
         SAT_TRY(glue_fold_out(wout, wpost, p->wout_eff, D, C, s));
         SAT_TRY(sat_launch_rope_table(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
     }
@@ -304,10 +327,10 @@ struct Workspace {
     size_t total;
 };
 
-Workspace carve(const sat_dit_plan* p, int bf, int T, char* base) {
+Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     const sat_dit_cfg& c = p->cfg;
     const int D = c.embed_dim, H = c.num_heads;
-    const int S = T + (c.adaln ? 0 : 1);
+    const int S = seq_len(p, T, P);
     const size_t M = (size_t)bf * S;
     const int Spad = (int)round_up(S + 3, 128);
     Workspace w;
@@ -371,22 +394,25 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     const bool cross = c.cond_token_dim > 0;
     SAT_CHECK_ARG(p->ctx_bf == bf, SAT_E_STATE, "dit forward: context prepared for %d sequences, forward called with %d",
                   p->ctx_bf, bf);
-    Workspace w = carve(p, bf, T, (char*)ws);
+    SAT_CHECK_ARG(p->concat_dim == 0 || p->ext_ready, SAT_E_STATE,
+                  "dit forward: the model has input_concat_dim %d: sat_dit_prepare_extra_conditioning must follow sat_dit_prepare_context", p->concat_dim);
+    const int P = p->ctx_prep;
+    Workspace w = carve(p, bf, T, P, (char*)ws);
     SAT_CHECK_ARG(ws_bytes >= w.total, SAT_E_WORKSPACE, "dit forward: workspace %zu < required %zu", ws_bytes, w.total);
     const int D = c.embed_dim, H = c.num_heads, C = c.io_channels;
     const bool adaln = c.adaln != 0, f32 = c.gemm_dtype == 2;
     const int f16 = p->f16;
-    const int S = T + (adaln ? 0 : 1), M = bf * S, Spad = (int)round_up(S + 3, 128);
+    const int S = seq_len(p, T, P), M = bf * S, Spad = (int)round_up(S + 3, 128);
     const int ssg_ld = c.depth * 6 * D;      // per-sequence stride of the adaLN modulation vectors
 
     // pads of q/k/vt must be finite (zero): one memset per forward
     if (!f32) SAT_HIP(hipMemsetAsync(w.Q, 0, 3 * (size_t)round_up((int64_t)w.qkv_bytes, 256), s));
 
-    // timestep embedding (dit.py:176) + global embed (dit.py:179-182) -> prepend token rows X[b,0,:]
+    // timestep embedding (dit.py:176) + global embed (dit.py:179-182) -> global token rows X[b,P,:] (behind the P prepend tokens)
     SAT_TRY(glue_fourier(t_dev, t_const, p->ts_w, w.ff, bf, 128, s));
     SAT_TRY(glue_small_linear(w.ff, 256, p->te0_w, p->te0_b, nullptr, 0, w.h1, D, bf, D, 256, 1, 0, s));
     if (!adaln) {
-        SAT_TRY(glue_small_linear(w.h1, D, p->te2_w, p->te2_b, p->has_global ? p->ge : nullptr, D, w.X, S * D, bf, D, D, 0, 0, s));
+        SAT_TRY(glue_small_linear(w.h1, D, p->te2_w, p->te2_b, p->has_global ? p->ge : nullptr, D, w.X + (size_t)P * D, S * D, bf, D, D, 0, 0, s));
     } else {
         // dit.py:205-206: the summed embedding conditions every block instead of being prepended; transformer.py:667:
         // (scale, shift, gate) x (self, ff) = Linear(SiLU(global)) for all layers in one launch
@@ -394,8 +420,13 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
         SAT_TRY(glue_small_linear(w.gsum, D, p->ssg_w, nullptr, nullptr, 0, w.ssg, ssg_ld, bf, ssg_ld, D, 0, 0, s));
         SAT_TRY(glue_adaln_finish(w.ssg, (int64_t)bf * ssg_ld, D, s));
     }
-    // preprocess_conv + residual + project_in (dit.py:197-199, transformer.py:778)
-    SAT_TRY(glue_input_proj(x, p->win_eff, w.X, bf, xB, C, T, S, D, xscale, s));
+    // preprocess_conv + residual + project_in (dit.py:197-199, transformer.py:778); with extra conditioning the same launch adds the
+    // concat channels (dit.py:167-173, unscaled by c_in) and copies the prepared prepend rows X[b, 0..P-1, :]
+    if (p->ext_ready)
+        SAT_TRY(glue_input_proj_extra(x, p->win_eff, w.X, bf, xB, C, T, S, D, xscale, p->ext_concat, p->concat_dim, p->ext_concat_len,
+                                      p->ext_prep, P, s));
+    else
+        SAT_TRY(glue_input_proj(x, p->win_eff, w.X, bf, xB, C, T, S, D, xscale, s));
 
     if (p->dbg) SAT_HIP(hipMemsetAsync(p->dbg, 0, (size_t)c.depth * 3 * 4 * sizeof(float), s));
     GemmArgs g{};
@@ -606,6 +637,7 @@ extern "C" void sat_dit_plan_destroy(sat_dit_plan* p) {
     if (!p) return;
     if (p->arena) (void)hipFree(p->arena);
     if (p->ctx_buf) (void)hipFree(p->ctx_buf);
+    if (p->ext_buf) (void)hipFree(p->ext_buf);
     if (p->dbg) (void)hipFree(p->dbg);
     for (hipEvent_t e : p->prof_ev) (void)hipEventDestroy(e);
     delete p;
@@ -632,6 +664,7 @@ extern "C" int sat_dit_plan_finalize(sat_dit_plan* p, sat_stream_t stream) {
         p->arena = nullptr;
     }
     p->finalized = false;
+    p->wsq_bf = p->wsq_t = -1;
     Arena dry;
     SAT_TRY(build(p, dry, s));
     SAT_HIP(hipMalloc((void**)&p->arena, dry.off));
@@ -648,7 +681,21 @@ extern "C" int sat_dit_plan_finalize(sat_dit_plan* p, sat_stream_t stream) {
 extern "C" int sat_dit_workspace_bytes(const sat_dit_plan* p, int32_t bf, int32_t t_len, size_t* out_bytes) {
     SAT_CHECK_ARG(p && out_bytes && bf > 0 && t_len > 0, SAT_E_INVALID, "dit_workspace_bytes: bad argument");
     SAT_CHECK_ARG(p->finalized, SAT_E_STATE, "dit_workspace_bytes: plan not finalized");
-    *out_bytes = carve(p, bf, t_len, nullptr).total;
+    // enough for any prepend length up to max_prepend_len (the layout is not monotonic in P: the FF-out K-split slab depends on M).
+    // Host arithmetic only, once per (bf, t_len): the hot calls check carve() of the prepared P instead.
+    if (p->max_prep == 0) {
+        *out_bytes = carve(p, bf, t_len, 0, nullptr).total;
+        return 0;
+    }
+    if (p->wsq_bf != bf || p->wsq_t != t_len) {
+        size_t need = 0;
+        for (int P = 0; P <= p->max_prep; ++P) {
+            const size_t b = carve(p, bf, t_len, P, nullptr).total;
+            need = b > need ? b : need;
+        }
+        p->wsq_bf = bf; p->wsq_t = t_len; p->wsq_bytes = need;
+    }
+    *out_bytes = p->wsq_bytes;
     return 0;
 }
 
@@ -733,6 +780,11 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
     }
     p->ctx_bf = bf;
     p->ctx_null_from = -1;
+    p->ext_ready = false;           // the extra conditioning belongs to the previous generation
+    p->ext_concat = nullptr;
+    p->ext_concat_len = 0;
+    p->ext_prep = nullptr;
+    p->ctx_prep = 0;
     p->ctx_lc = cross ? lc : 0;
     p->ctx_lcpad = lcpad;
     return 0;
@@ -743,6 +795,76 @@ extern "C" int sat_dit_set_null_context_from(sat_dit_plan* p, int32_t first_null
     SAT_CHECK_ARG(first_null_seq >= -1 && first_null_seq <= p->ctx_bf, SAT_E_INVALID, "dit_set_null_context_from: %d not in [-1, %d]",
                   first_null_seq, p->ctx_bf);
     p->ctx_null_from = first_null_seq;
+    return 0;
+}
+
+extern "C" int sat_dit_plan_set_extra_conditioning(sat_dit_plan* p, int32_t input_concat_dim, int32_t prepend_cond_dim, int32_t max_prepend_len) {
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "dit_plan_set_extra_conditioning: null plan");
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_extra_conditioning: plan already finalized (call it between create and finalize)");
+    SAT_CHECK_ARG(input_concat_dim >= 0 && prepend_cond_dim >= 0 && max_prepend_len >= 0, SAT_E_INVALID,
+                  "dit_plan_set_extra_conditioning: negative argument (%d, %d, %d)", input_concat_dim, prepend_cond_dim, max_prepend_len);
+    SAT_CHECK_ARG((prepend_cond_dim > 0) == (max_prepend_len > 0), SAT_E_INVALID,
+                  "dit_plan_set_extra_conditioning: max_prepend_len %d with prepend_cond_dim %d (both positive or both 0)", max_prepend_len,
+                  prepend_cond_dim);
+    // adaLN + prepend_cond: the reference sets prepend_length only in the "prepend" branch (models/dit.py:158,185-195) and so returns
+    // P + T frames (:219); there is no working behaviour to reproduce
+    SAT_CHECK_ARG(!(p->cfg.adaln && prepend_cond_dim > 0), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_extra_conditioning: prepend_cond with global_cond_type 'adaLN' (the reference drops the wrong rows there)");
+    SAT_CHECK_ARG(prepend_cond_dim % 4 == 0, SAT_E_UNSUPPORTED, "dit_plan_set_extra_conditioning: prepend_cond_dim %d must be a multiple of 4",
+                  prepend_cond_dim);
+    SAT_CHECK_ARG(p->cfg.io_channels + input_concat_dim <= 256, SAT_E_UNSUPPORTED,
+                  "dit_plan_set_extra_conditioning: io_channels + input_concat_dim = %d exceeds 256", p->cfg.io_channels + input_concat_dim);
+    SAT_CHECK_ARG((int64_t)p->cfg.max_seq_len + 1 + max_prepend_len <= (1 << 20), SAT_E_INVALID,
+                  "dit_plan_set_extra_conditioning: max_prepend_len %d too large", max_prepend_len);
+    p->concat_dim = input_concat_dim;
+    p->prepend_dim = prepend_cond_dim;
+    p->max_prep = max_prepend_len;
+    return 0;
+}
+
+extern "C" int sat_dit_prepare_extra_conditioning(sat_dit_plan* p, const float* concat, int32_t concat_len, const float* prepend,
+                                                  int32_t prepend_len, int32_t bf, sat_stream_t stream) {
+    SAT_CHECK_ARG(p && p->finalized, SAT_E_STATE, "dit_prepare_extra_conditioning: plan not finalized");
+    SAT_CHECK_ARG(p->ctx_bf > 0 && p->ctx_bf == bf, SAT_E_STATE,
+                  "dit_prepare_extra_conditioning: context prepared for %d sequences, called with %d (sat_dit_prepare_context first)", p->ctx_bf, bf);
+    hipStream_t s = (hipStream_t)stream;
+    const int D = p->cfg.embed_dim, Cc = p->concat_dim;
+    SAT_CHECK_ARG(!concat || Cc > 0, SAT_E_INVALID, "dit_prepare_extra_conditioning: the model has no input_concat_dim");
+    SAT_CHECK_ARG(Cc == 0 || (concat && concat_len > 0), SAT_E_INVALID,
+                  "dit_prepare_extra_conditioning: the model has input_concat_dim %d and needs input_concat_cond (concat_len > 0)", Cc);
+    SAT_CHECK_ARG(!prepend || p->prepend_dim > 0, SAT_E_INVALID, "dit_prepare_extra_conditioning: the model has no prepend_cond_dim");
+    SAT_CHECK_ARG(prepend ? (prepend_len > 0 && prepend_len <= p->max_prep) : prepend_len == 0, SAT_E_INVALID,
+                  "dit_prepare_extra_conditioning: prepend_len %d not in 1..max_prepend_len %d", prepend_len, p->max_prep);
+    const size_t n_cat = Cc ? (size_t)bf * Cc * concat_len : 0;
+    const size_t n_prep = prepend ? (size_t)bf * prepend_len * D : 0;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        size_t o = off;
+        off += (size_t)round_up((int64_t)bytes, 256);
+        return o;
+    };
+    const size_t o_cat = take(n_cat * 4), o_h = take(n_prep * 4), o_prep = take(n_prep * 4);
+    if (off > p->ext_cap) {
+        SAT_HIP(hipStreamSynchronize(s));
+        if (p->ext_buf) SAT_HIP(hipFree(p->ext_buf));
+        p->ext_buf = nullptr;
+        p->ext_cap = 0;
+        SAT_HIP(hipMalloc((void**)&p->ext_buf, off));
+        p->ext_cap = off;
+    }
+    p->ext_ready = false;
+    if (Cc) SAT_HIP(hipMemcpyAsync(p->ext_buf + o_cat, concat, n_cat * 4, hipMemcpyDeviceToDevice, s));
+    if (prepend) {   // dit.py:160-165: Linear(prepend_cond_dim, D, bias=False), SiLU, Linear(D, D, bias=False)
+        const int R = bf * prepend_len;
+        float* h = (float*)(p->ext_buf + o_h);
+        SAT_TRY(glue_small_linear(prepend, p->prepend_dim, p->pe0_w, nullptr, nullptr, 0, h, D, R, D, p->prepend_dim, 1, 0, s));
+        SAT_TRY(glue_small_linear(h, D, p->pe2_w, nullptr, nullptr, 0, p->ext_buf + o_prep, D, R, D, D, 0, 0, s));
+    }
+    p->ext_concat = Cc ? (const float*)(p->ext_buf + o_cat) : nullptr;
+    p->ext_concat_len = Cc ? concat_len : 0;
+    p->ext_prep = prepend ? (float*)(p->ext_buf + o_prep) : nullptr;
+    p->ctx_prep = prepend ? prepend_len : 0;
+    p->ext_ready = Cc > 0 || prepend;       // neither: the plain path (P = 0), as after sat_dit_prepare_context
     return 0;
 }
 
@@ -757,8 +879,8 @@ extern "C" int sat_dit_denoise_cfg(sat_dit_plan* p, const float* x_dev, float si
     SAT_CHECK_ARG(p && p->finalized, SAT_E_STATE, "dit_denoise_cfg: plan not finalized");
     SAT_CHECK_ARG(x_dev && denoised_dev && b > 0 && t_len > 0 && ws, SAT_E_INVALID, "dit_denoise_cfg: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    // models/dit.py:270: CFG only when cfg_scale != 1 and there is cross-attention conditioning
-    const int use_cfg = (cfg_scale != 1.0f && p->cfg.cond_token_dim > 0) ? 1 : 0;
+    // models/dit.py:270: CFG only when cfg_scale != 1 and there is cross-attention or prepend conditioning
+    const int use_cfg = (cfg_scale != 1.0f && (p->cfg.cond_token_dim > 0 || p->ctx_prep > 0)) ? 1 : 0;
     const int bf = use_cfg ? 2 * b : b;
     // k_diffusion.external.VDenoiser, sigma_data = 1
     const double sg = (double)sigma;
@@ -766,10 +888,8 @@ extern "C" int sat_dit_denoise_cfg(sat_dit_plan* p, const float* x_dev, float si
     const float c_out = (float)(-sg / sqrt(sg * sg + 1.0));
     const float c_in = (float)(1.0 / sqrt(sg * sg + 1.0));
     const float t = (float)(atan(sg) / M_PI * 2.0);
-    size_t need = 0;
-    SAT_TRY(sat_dit_workspace_bytes(p, bf, t_len, &need));
-    SAT_CHECK_ARG(ws_bytes >= need, SAT_E_WORKSPACE, "dit_denoise_cfg: workspace %zu < required %zu", ws_bytes, need);
-    Workspace w = carve(p, bf, t_len, (char*)ws);
+    Workspace w = carve(p, bf, t_len, p->ctx_prep, (char*)ws);      // the layout of the prepared prepend length P
+    SAT_CHECK_ARG(ws_bytes >= w.total, SAT_E_WORKSPACE, "dit_denoise_cfg: workspace %zu < required %zu", ws_bytes, w.total);
     SAT_TRY(run_forward(p, x_dev, b, c_in, nullptr, t, w.mo, bf, t_len, ws, ws_bytes, s));
     return glue_cfg_denoise(w.mo, x_dev, denoised_dev, b, p->cfg.io_channels, t_len, use_cfg, cfg_scale, scale_phi, c_out, c_skip, s);
 }

@@ -354,8 +354,6 @@ def sample_k(model_fn, noise, init_data=None, mask=None, steps=100, sampler_type
         raise NotImplementedError("cond_fn (gradient guidance through the denoiser) is outside the supported hot path")
     if mask is not None and init_data is None:
         mask = None                                                     # sampling.py:166-201: a mask without init data is ignored
-    if input_concat_cond is not None or prepend_cond is not None:
-        raise NotImplementedError("input_concat_cond / prepend_cond are outside the supported hot path")
     if not isinstance(model_fn, DiTWrapper):
         raise NotImplementedError("sample_k drives the HIP DiT (DiTWrapper) only; there is no eager/CPU denoiser path")
     assert batch_cfg, "batch_cfg must be True for DiTWrapper"
@@ -379,7 +377,10 @@ def sample_k(model_fn, noise, init_data=None, mask=None, steps=100, sampler_type
     else:
         x = noise                                                       # SAMPLING
 
-    dit.prepare_generation(cross_attn_cond, global_cond, cfg_scale, negative_cross_attn_cond, negative_cross_attn_mask)
+    # negative_input_concat_cond / prepend_cond_mask are accepted and ignored, as DiTWrapper does (reference diffusion.py:497-525,
+    # transformer.py:787-802)
+    dit.prepare_generation(cross_attn_cond, global_cond, cfg_scale, negative_cross_attn_cond, negative_cross_attn_mask,
+                           input_concat_cond=input_concat_cond, prepend_cond=prepend_cond)
 
     def after_denoise(i, x, sigma, denoised):
         if mask is not None:

@@ -90,7 +90,8 @@ class ConditionedDiffusionModelWrapper(nn.Module):
             if global_cond.dim() == 3:
                 global_cond = global_cond.squeeze(1)
         if self.input_concat_ids:
-            concat = torch.cat([t for t, _ in pairs(self.input_concat_ids)], dim=1)
+            # entries may be one-element lists ([tensor], reference training/diffusion.py:754): only [0] is read (:172)
+            concat = torch.cat([conditioning_tensors[i][0] for i in self.input_concat_ids], dim=1)
         if self.prepend_cond_ids:
             prepend = torch.cat([t for t, _ in pairs(self.prepend_cond_ids)], dim=1)
             prepend_mask = torch.cat([m for _, m in pairs(self.prepend_cond_ids)], dim=1)

@@ -35,8 +35,14 @@ class DiffusionTransformer(nn.Module):
             raise NotImplementedError("only transformer_type='continuous_transformer' is implemented (the shipped DiT configs)")
         if global_cond_type not in ("prepend", "adaLN"):
             raise ValueError(f"Unknown global_cond_type: {global_cond_type}")
-        if patch_size != 1 or input_concat_dim != 0 or prepend_cond_dim != 0:
-            raise NotImplementedError("patch_size>1 / input_concat / prepend_cond are outside the supported hot path")
+        if patch_size != 1:
+            raise NotImplementedError("patch_size>1 is outside the supported hot path")
+        if prepend_cond_dim > 0 and global_cond_type == "adaLN":
+            # the reference sets prepend_length only in the "prepend" branch (dit.py:158,185-195) and so returns P + T frames (:219)
+            raise NotImplementedError("prepend_cond_dim with global_cond_type='adaLN' has no working reference behaviour (reference dit.py:158,"
+                                      "185-195,219 return prepend_len + T frames); use global_cond_type='prepend'")
+        if input_concat_dim < 0 or prepend_cond_dim < 0:
+            raise ValueError("input_concat_dim / prepend_cond_dim must be >= 0")
         if not project_global_cond and global_cond_dim > 0:
             raise NotImplementedError("project_global_cond=False is not supported")
         self.patch_size = patch_size
@@ -47,6 +53,8 @@ class DiffusionTransformer(nn.Module):
         self.cond_token_dim = cond_token_dim
         self.global_cond_dim = global_cond_dim
         self.input_concat_dim = input_concat_dim
+        self.prepend_cond_dim = prepend_cond_dim
+        self.max_prepend_len = 64 if prepend_cond_dim > 0 else 0     # grows (plan rebuild) when a generation brings more tokens
         self.max_seq_len = max_seq_len
         self.transformer_type = transformer_type
         self.global_cond_type = global_cond_type
@@ -63,17 +71,23 @@ class DiffusionTransformer(nn.Module):
         if global_cond_dim > 0:
             self.to_global_embed = nn.Sequential(_init.linear(global_cond_dim, embed_dim, bias=False), nn.SiLU(),
                                                  _init.linear(embed_dim, embed_dim, bias=False))
+        if prepend_cond_dim > 0:      # dit.py:160-165
+            self.to_prepend_embed = nn.Sequential(_init.linear(prepend_cond_dim, embed_dim, bias=False), nn.SiLU(),
+                                                  _init.linear(embed_dim, embed_dim, bias=False))
+        dim_in = io_channels + input_concat_dim      # dit.py:38: the input projection sees cat([x, input_concat_cond])
         self.transformer = ContinuousTransformer(dim=embed_dim, depth=depth, dim_heads=embed_dim // num_heads,
-                                                 dim_in=io_channels, dim_out=io_channels, cross_attend=cond_token_dim > 0,
+                                                 dim_in=dim_in, dim_out=io_channels, cross_attend=cond_token_dim > 0,
                                                  cond_token_dim=cond_embed_dim,
                                                  global_cond_dim=embed_dim if global_cond_type == "adaLN" else None, **kwargs)
-        self.preprocess_conv = _init.conv1d(io_channels, io_channels, 1, bias=False, zero=True)
+        self.preprocess_conv = _init.conv1d(dim_in, dim_in, 1, bias=False, zero=True)
         self.postprocess_conv = _init.conv1d(io_channels, io_channels, 1, bias=False, zero=True)
 
         self._plan = None
         self._plan_version = None
         self._ws = None
         self._ctx_key = None
+        self._ext_key = None
+        self._gen_prepend = False
         self.gemm_dtype = _config.default_gemm_dtype()
         self.layernorm_fusion = True
         self.cross_attention_fusion = True
@@ -168,6 +182,11 @@ class DiffusionTransformer(nn.Module):
                              1 if self.layernorm_fusion else 0, 0 if self.cross_attention_fusion else 1, self.tile_policy)
         plan = ctypes.c_void_p()
         _hip.check(lib.sat_dit_plan_create_sized(ctypes.byref(cfg), ctypes.sizeof(cfg), ctypes.byref(plan)))
+        if self.input_concat_dim > 0 or self.prepend_cond_dim > 0:
+            rc = lib.sat_dit_plan_set_extra_conditioning(plan, self.input_concat_dim, self.prepend_cond_dim, self.max_prepend_len)
+            if rc != 0:
+                lib.sat_dit_plan_destroy(plan)
+                _hip.check(rc)
         keep = []
         for name, t in self.state_dict().items():
             t32 = t.detach().to(torch.float32).contiguous()
@@ -178,6 +197,7 @@ class DiffusionTransformer(nn.Module):
         self._plan = plan
         self._plan_version = ver
         self._ctx_key = None
+        self._ext_key = None
         return plan
 
     def _workspace(self, bf, t_len):
@@ -197,6 +217,7 @@ class DiffusionTransformer(nn.Module):
         key = key + (null_from,)
         if key == self._ctx_key:
             return
+        self._ext_key = None          # sat_dit_prepare_context discards the extra conditioning of the previous generation
         c = None if cross_attn_cond is None else cross_attn_cond.detach().float().contiguous()
         g = None if global_embed is None else global_embed.detach().float().contiguous()
         bf = c.shape[0] if c is not None else (g.shape[0] if g is not None else 0)
@@ -207,6 +228,7 @@ class DiffusionTransformer(nn.Module):
         if null_from >= 0 and c is not None:
             _hip.check(_hip.lib().sat_dit_set_null_context_from(plan, int(null_from)))
         self._ctx_key = key
+        self._ctx_nseq = bf
         self._ctx_keep = (cross_attn_cond, global_embed)
 
     def prepare_context_bf(self, bf):
@@ -214,11 +236,49 @@ class DiffusionTransformer(nn.Module):
         plan = self._ensure_plan()
         _hip.check(_hip.lib().sat_dit_prepare_context(plan, None, bf, 0, None, _hip.stream()))
         self._ctx_key = ("bf", bf)
+        self._ctx_nseq = bf
+        self._ext_key = None
+
+    def _reserve_prepend(self, prepend_cond):
+        """Grow the plan's max_prepend_len (a plan rebuild) when ``prepend_cond`` brings more tokens than it was built for."""
+        if prepend_cond is None:
+            return
+        if self.prepend_cond_dim == 0:
+            raise ValueError("prepend_cond given to a DiT without prepend_cond_dim")
+        if prepend_cond.shape[-1] != self.prepend_cond_dim:
+            raise ValueError(f"prepend_cond has {prepend_cond.shape[-1]} channels, model expects {self.prepend_cond_dim}")
+        if prepend_cond.shape[1] > self.max_prepend_len:
+            self.max_prepend_len = -(-prepend_cond.shape[1] // 64) * 64
+            self._plan_version = None
+
+    def prepare_extra(self, input_concat_cond, prepend_cond, bf):
+        """Per-generation input-concat signal [bf, input_concat_dim, Tc] and prepend tokens [bf, P, prepend_cond_dim] (dit.py:160-173),
+        both already CFG-doubled; after ``prepare_context`` for the same ``bf``."""
+        if input_concat_cond is None and prepend_cond is None:
+            if self.input_concat_dim > 0:
+                raise ValueError(f"this DiT has input_concat_dim {self.input_concat_dim}: input_concat_cond is required")
+            if self.prepend_cond_dim == 0:
+                return
+        # (the absence of prepend tokens is part of the key: a cached context must not keep those of an earlier call)
+        key = tuple((t.data_ptr(), t._version, tuple(t.shape)) if t is not None else None for t in (input_concat_cond, prepend_cond)) + (bf,)
+        if key == self._ext_key:
+            return
+        c = None if input_concat_cond is None else input_concat_cond.detach().float().contiguous()
+        pc = None if prepend_cond is None else prepend_cond.detach().float().contiguous()
+        if c is not None and (c.dim() != 3 or c.shape[0] != bf or c.shape[1] != self.input_concat_dim):
+            raise ValueError(f"input_concat_cond of shape {tuple(c.shape)}, model expects [{bf}, {self.input_concat_dim}, T]")
+        if pc is not None and (pc.dim() != 3 or pc.shape[0] != bf):
+            raise ValueError(f"prepend_cond of shape {tuple(pc.shape)}, model expects [{bf}, P, {self.prepend_cond_dim}]")
+        _hip.check(_hip.lib().sat_dit_prepare_extra_conditioning(self._plan, _hip.ptr(c), 0 if c is None else c.shape[2], _hip.ptr(pc),
+                                                                   0 if pc is None else pc.shape[1], bf, _hip.stream()))
+        self._ext_key = key
+        self._ext_keep = (input_concat_cond, prepend_cond, c, pc)
 
     # ------------------------------------------------------------------ reference-semantics forward
     @torch.no_grad()
-    def _forward(self, x, t, cross_attn_cond=None, global_embed=None, null_from=-1, **ignored):
+    def _forward(self, x, t, cross_attn_cond=None, global_embed=None, null_from=-1, input_concat_cond=None, prepend_cond=None, **ignored):
         """dit.py:135-226 on the given batch (no CFG logic)."""
+        self._reserve_prepend(prepend_cond)
         self._ensure_plan()
         x = x.detach().float().contiguous()
         t = t.detach().float().contiguous()
@@ -227,6 +287,7 @@ class DiffusionTransformer(nn.Module):
             self.prepare_context_bf(bf)
         else:
             self.prepare_context(cross_attn_cond, global_embed, null_from)
+        self.prepare_extra(input_concat_cond, prepend_cond, bf)
         ws = self._workspace(bf, t_len)
         out = torch.empty_like(x)
         _hip.check(_hip.lib().sat_dit_forward(self._plan, _hip.ptr(x), _hip.ptr(t), _hip.ptr(out), bf, t_len, _hip.ptr(ws),
@@ -239,55 +300,70 @@ class DiffusionTransformer(nn.Module):
                 prepend_cond_mask=None, cfg_scale=1.0, cfg_dropout_prob=0.0, causal=False, scale_phi=0.0, mask=None,
                 return_info=False, **kwargs):
         assert not causal, "Causal mode is not supported for DiffusionTransformer"
-        if input_concat_cond is not None or prepend_cond is not None or return_info:
-            raise NotImplementedError("input_concat_cond / prepend_cond / return_info are outside the supported hot path")
-        # masks are discarded exactly as the reference does at inference (dit.py:250-252)
-        if cfg_scale != 1.0 and cross_attn_cond is not None:
+        if return_info:
+            raise NotImplementedError("return_info is outside the supported hot path")
+        # masks are discarded exactly as the reference does at inference (dit.py:250-252); prepend_cond_mask never reaches
+        # the layers there either (transformer.py:787-802)
+        if cfg_scale != 1.0 and (cross_attn_cond is not None or prepend_cond is not None):
             b = x.shape[0]
-            bc, bg = self._cfg_batch(cross_attn_cond, global_embed, negative_cross_attn_cond, negative_cross_attn_mask)
+            bc, bg, bcat, bpre = self._cfg_batch(cross_attn_cond, global_embed, negative_cross_attn_cond, negative_cross_attn_mask,
+                                                 input_concat_cond, prepend_cond)
             out = self._forward(torch.cat([x, x], dim=0), torch.cat([t, t], dim=0), bc, bg,
-                                null_from=b if negative_cross_attn_cond is None else -1)
+                                null_from=b if (cross_attn_cond is not None and negative_cross_attn_cond is None) else -1,
+                                input_concat_cond=bcat, prepend_cond=bpre)
             res = torch.empty_like(out[:b])
             # CFG combine (+ optional std rescale), dit.py:336-345, as a HIP kernel: denoise form with c_out=1, c_skip=0
             _hip.check(_hip.lib().sat_cfg_combine(_hip.ptr(out), _hip.ptr(res), b, out.shape[1], out.shape[2], float(cfg_scale),
                                                   float(scale_phi), _hip.stream()))
             return res
-        return self._forward(x, t, cross_attn_cond, global_embed)
+        return self._forward(x, t, cross_attn_cond, global_embed, input_concat_cond=input_concat_cond, prepend_cond=prepend_cond)
 
     @staticmethod
-    def _cfg_batch(cross_attn_cond, global_embed, negative_cross_attn_cond=None, negative_cross_attn_mask=None):
-        """cat([cond, null]) / cat([global, global]) (dit.py:273-300)."""
-        null = torch.zeros_like(cross_attn_cond)
-        if negative_cross_attn_cond is not None:
-            if negative_cross_attn_mask is not None:
-                m = negative_cross_attn_mask.to(torch.bool).unsqueeze(2)
-                negative_cross_attn_cond = torch.where(m, negative_cross_attn_cond, null)
-            null = negative_cross_attn_cond
-        bc = torch.cat([cross_attn_cond, null], dim=0)
+    def _cfg_batch(cross_attn_cond, global_embed, negative_cross_attn_cond=None, negative_cross_attn_mask=None, input_concat_cond=None,
+                   prepend_cond=None):
+        """cat([cond, null]) / cat([global, global]) / cat([concat, concat]) / cat([prepend, 0]) (dit.py:273-315)."""
+        bc = None
+        if cross_attn_cond is not None:
+            null = torch.zeros_like(cross_attn_cond)
+            if negative_cross_attn_cond is not None:
+                if negative_cross_attn_mask is not None:
+                    m = negative_cross_attn_mask.to(torch.bool).unsqueeze(2)
+                    negative_cross_attn_cond = torch.where(m, negative_cross_attn_cond, null)
+                null = negative_cross_attn_cond
+            bc = torch.cat([cross_attn_cond, null], dim=0)
         bg = None if global_embed is None else torch.cat([global_embed, global_embed], dim=0)
-        return bc, bg
+        bcat = None if input_concat_cond is None else torch.cat([input_concat_cond, input_concat_cond], dim=0)
+        bpre = None if prepend_cond is None else torch.cat([prepend_cond, torch.zeros_like(prepend_cond)], dim=0)
+        return bc, bg, bcat, bpre
 
     # ------------------------------------------------------------------ fused sampler-step path
     @torch.no_grad()
     def prepare_generation(self, cross_attn_cond, global_embed, cfg_scale, negative_cross_attn_cond=None,
-                           negative_cross_attn_mask=None):
+                           negative_cross_attn_mask=None, input_concat_cond=None, prepend_cond=None):
         """Once per ``generate_diffusion_cond`` call: everything that is constant over the steps."""
+        self._reserve_prepend(prepend_cond)
         self._ensure_plan()
-        use_cfg = cfg_scale != 1.0 and cross_attn_cond is not None
+        use_cfg = cfg_scale != 1.0 and (cross_attn_cond is not None or prepend_cond is not None)
         if use_cfg:
-            bc, bg = self._cfg_batch(cross_attn_cond, global_embed, negative_cross_attn_cond, negative_cross_attn_mask)
+            bc, bg, bcat, bpre = self._cfg_batch(cross_attn_cond, global_embed, negative_cross_attn_cond, negative_cross_attn_mask,
+                                                 input_concat_cond, prepend_cond)
         else:
-            bc, bg = cross_attn_cond, global_embed
-        if bc is None and bg is None:
+            bc, bg, bcat, bpre = cross_attn_cond, global_embed, input_concat_cond, prepend_cond
+        if bc is None and bg is None and bcat is None and bpre is None:
             raise ValueError("prepare_generation needs conditioning tensors")
-        null_from = cross_attn_cond.shape[0] if (use_cfg and negative_cross_attn_cond is None) else -1
-        self.prepare_context(bc, bg, null_from)
+        if bc is None and bg is None:
+            self.prepare_context_bf((bcat if bcat is not None else bpre).shape[0])
+        else:
+            null_from = cross_attn_cond.shape[0] if (use_cfg and cross_attn_cond is not None and negative_cross_attn_cond is None) else -1
+            self.prepare_context(bc, bg, null_from)
+        self.prepare_extra(bcat, bpre, self._ctx_nseq)
+        self._gen_prepend = prepend_cond is not None
 
     @torch.no_grad()
     def denoise(self, x, sigma: float, cfg_scale: float = 1.0, scale_phi: float = 0.0, out=None):
         """k-diffusion VDenoiser(DiT with batched CFG)(x, sigma) -- ``sat_dit_denoise_cfg``."""
         b, _, t_len = x.shape
-        use_cfg = cfg_scale != 1.0 and self.cond_token_dim > 0
+        use_cfg = cfg_scale != 1.0 and (self.cond_token_dim > 0 or self._gen_prepend)
         ws = self._workspace(2 * b if use_cfg else b, t_len)
         if out is None:
             out = torch.empty_like(x)

@@ -53,9 +53,12 @@ const char* sat_last_error(void);
  * DiT denoiser.  Replaces models/dit.py:135-364 (DiffusionTransformer._forward/.forward),
  * models/transformer.py:99-809 (ContinuousTransformer, TransformerBlock, Attention,
  * FeedForward, LayerNorm, RotaryEmbedding), models/diffusion.py:482-529 (DiTWrapper).
- * Supported set: transformer_type "continuous_transformer", global_cond_type "prepend",
- * dim_heads 64, patch_size 1, no input_concat / prepend_cond, non-causal, no masks
- * (the reference discards them at inference: models/dit.py:250-252).
+ * Supported set: transformer_type "continuous_transformer", global_cond_type "prepend"
+ * or "adaLN", dim_heads 64, patch_size 1, non-causal, no masks (the reference discards
+ * them at inference: models/dit.py:250-252; prepend_cond_mask never reaches the layers,
+ * models/transformer.py:787-802).  Input-concat and prepend conditioning (dit.py:160-197)
+ * through sat_dit_plan_set_extra_conditioning / sat_dit_prepare_extra_conditioning; prepend
+ * conditioning with "adaLN" is rejected (the reference returns P + T frames there).
  * ---------------------------------------------------------------------------------- */
 typedef struct sat_dit_plan sat_dit_plan;
 
@@ -140,13 +143,26 @@ void sat_dit_plan_destroy(sat_dit_plan* plan);
  * tree).  The pointer is only read inside sat_dit_plan_finalize. */
 int sat_dit_plan_set_tensor(sat_dit_plan* plan, const char* name, const float* data_dev, int64_t numel);
 
+/* Input-concat / prepend conditioning (models/dit.py:38,160-173,185-197), between create and finalize; a plan never given
+ * this call has neither (input_concat_dim = prepend_cond_dim = 0).  input_concat_dim (config "input_concat_dim", e.g. 65
+ * for "diffusion_cond_inpaint"): preprocess_conv is (io + Cc) x (io + Cc) and project_in [D, io + Cc]; prepend_cond_dim:
+ * the tensors "to_prepend_embed.0.weight" / ".2.weight" are required; max_prepend_len: the most prepend tokens any
+ * generation will bring (the RoPE table and sat_dit_workspace_bytes grow by it).  prepend_cond_dim and max_prepend_len
+ * are both positive or both 0.  SAT_E_STATE after finalize, SAT_E_INVALID for negative values.  SAT_E_UNSUPPORTED for
+ * prepend conditioning on an "adaLN" plan, and for two limits of this build that the reference does not have:
+ * prepend_cond_dim must be a multiple of 4 (the prepend MLP's vector loads), and io_channels + input_concat_dim must be
+ * at most 256. */
+int sat_dit_plan_set_extra_conditioning(sat_dit_plan* plan, int32_t input_concat_dim, int32_t prepend_cond_dim,
+                                        int32_t max_prepend_len);
+
 /* Checks that every required tensor was set, converts GEMM weights to bf16 (SwiGLU rows
  * interleaved), folds the 1x1 pre/post convs into the in/out projections, builds the RoPE
  * table.  Replaces nn.Module.load_state_dict for the DiT. */
 int sat_dit_plan_finalize(sat_dit_plan* plan, sat_stream_t stream);
 
 /* Bytes of caller workspace needed by sat_dit_forward / sat_dit_denoise_cfg for `bf`
- * sequences (bf = 2*B with CFG) of latent length `t_len`. */
+ * sequences (bf = 2*B with CFG) of latent length `t_len`, for any prepend length up to the
+ * plan's max_prepend_len. */
 int sat_dit_workspace_bytes(const sat_dit_plan* plan, int32_t bf, int32_t t_len, size_t* out_bytes);
 
 /* Per-generation constants (models/dit.py:150,154 to_cond_embed / to_global_embed and the
@@ -162,6 +178,17 @@ int sat_dit_prepare_context(sat_dit_plan* plan, const float* cross_attn_cond_dev
  * after every sat_dit_prepare_context). */
 int sat_dit_set_null_context_from(sat_dit_plan* plan, int32_t first_null_seq);
 
+/* Per-generation extra conditioning, after sat_dit_prepare_context for the same bf (which discards that of the previous
+ * generation); not part of the per-step work.  input_concat_dev [bf, input_concat_dim, concat_len] (both CFG halves carry
+ * the same signal, models/dit.py:281-284) is copied and resized to each forward's t_len on the fly (F.interpolate
+ * 'nearest', dit.py:170); it enters unscaled by the VDenoiser's c_in.  prepend_dev [bf, prepend_len, prepend_cond_dim]
+ * (zeros for the unconditional half, dit.py:310-315) goes through to_prepend_embed here; 1 <= prepend_len <=
+ * max_prepend_len, or NULL / 0.  Both NULL: no extra conditioning for this generation (the plain path).  Required (SAT_E_STATE at forward) when the model has input_concat_dim > 0.  With
+ * prepend tokens the sequence is [P prepend | global token | T frames] and sat_dit_denoise_cfg applies CFG even without
+ * cross-attention (dit.py:270). */
+int sat_dit_prepare_extra_conditioning(sat_dit_plan* plan, const float* input_concat_dev, int32_t concat_len,
+                                       const float* prepend_dev, int32_t prepend_len, int32_t bf, sat_stream_t stream);
+
 /* DiffusionTransformer._forward (models/dit.py:135-226) on bf sequences:
  * x_dev [bf, io_channels, t_len], t_dev [bf] (timestep in [0,1]) -> out_dev [bf, io_channels, t_len]. */
 int sat_dit_forward(sat_dit_plan* plan, const float* x_dev, const float* t_dev, float* out_dev,
@@ -171,7 +198,8 @@ int sat_dit_forward(sat_dit_plan* plan, const float* x_dev, const float* t_dev, 
  * called at inference/sampling.py:159 around DiTWrapper.forward; CFG models/dit.py:270-349):
  *   denoised = cfg(DiT(x*c_in, t(sigma))) * c_out + x * c_skip
  * x_dev, denoised_dev [b, io_channels, t_len]; the context prepared must hold bf = 2*b
- * sequences (cond half first, uncond half second) when cfg_scale != 1, else bf = b.
+ * sequences (cond half first, uncond half second) when cfg_scale != 1 and the model has
+ * cross-attention or prepend tokens were prepared, else bf = b.
  * scale_phi: CFG rescale (models/dit.py:342-345); 0 = off. */
 int sat_dit_denoise_cfg(sat_dit_plan* plan, const float* x_dev, float sigma, float cfg_scale, float scale_phi,
                         float* denoised_dev, int32_t b, int32_t t_len,
