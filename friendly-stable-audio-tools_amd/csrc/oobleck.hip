@@ -45,12 +45,35 @@ struct ConvArgs {
     long long out_limit;
     float* out_cf;           // channel-first fp32 output [B][cf_channels][M] (final convs) or null
     int cf_channels;
-    const op_t* zero_page; // >= 128 B of zeros: LDS-DMA source of the rows that fall into the conv padding
+    const op_t* zero_page; // >= one K-tile row (ROW_B <= 256 B) of zeros: LDS-DMA source of the rows that fall into the conv padding
 };
 
 __device__ __forceinline__ float snake_f(float v, float a, float ib) {
+#if SAT_OP_IS_F32
+    float s = sinf(v * a);      // reference-precision build: the error of __sinf grows with |v * a| and would dominate
+#else
     float s = __sinf(v * a);
+#endif
     return v + ib * (s * s);
+}
+
+// LDS rows of one 64-channel K-tile: 128 B (16-bit builds: eight 16-byte chunks, lds_tile_off) or 256 B (fp32 build: sixteen
+// chunks).  The fp32 swizzle XORs the chunk with row & 15, so each 16-lane group of a fragment read (16 consecutive rows, one
+// logical chunk) covers the 16 slots of a 256-byte bank row; LDS-DMA destinations stay linear, the swizzle picks the sources.
+constexpr int ROW_B = 64 * (int)sizeof(op_t);
+constexpr int ROW_CH = ROW_B / 16;              // 16-byte chunks per row
+constexpr int CH_EL = 16 / (int)sizeof(op_t);   // elements per chunk
+__device__ __forceinline__ int chunk_swz(int row) { return SAT_OP_IS_F32 ? (row & 15) : ((row >> 1) & 7); }
+__device__ __forceinline__ int conv_tile_off(int row, int chunk) { return row * ROW_B + ((chunk ^ chunk_swz(row)) << 4); }
+
+// 8 consecutive channels of one row: one 16-byte store of packed 16-bit values, or two 16-byte stores in the fp32 build
+__device__ __forceinline__ void store_op8(op_t* p, const float (&x)[8]) {
+#if SAT_OP_IS_F32
+    *reinterpret_cast<f32x4*>(p) = f32x4{x[0], x[1], x[2], x[3]};
+    *reinterpret_cast<f32x4*>(p + 4) = f32x4{x[4], x[5], x[6], x[7]};
+#else
+    *reinterpret_cast<u32x4*>(p) = u32x4{pack_op2(x[0], x[1]), pack_op2(x[2], x[3]), pack_op2(x[4], x[5]), pack_op2(x[6], x[7])};
+#endif
 }
 
 // Epilogue on TRANSPOSED accumulators (the main loop issues its MFMAs with the weight fragment as the A operand, see
@@ -109,8 +132,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& g, f32x16 (&acc)[M
 #pragma unroll
                     for (int e = 0; e < 8; ++e) x[e] += op_to_f32(rv[e]);
                 }
-                if (oraw && ok)
-                    *reinterpret_cast<u32x4*>(oraw + flat) = u32x4{pack_op2(x[0], x[1]), pack_op2(x[2], x[3]), pack_op2(x[4], x[5]), pack_op2(x[6], x[7])};
+                if (oraw && ok) store_op8(oraw + flat, x);
                 if (osnk) {
                     const f32x4 a0 = *reinterpret_cast<const f32x4*>(g.sn_a + co), a1 = *reinterpret_cast<const f32x4*>(g.sn_a + co + 4);
                     const f32x4 i0 = *reinterpret_cast<const f32x4*>(g.sn_ib + co), i1 = *reinterpret_cast<const f32x4*>(g.sn_ib + co + 4);
@@ -120,8 +142,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& g, f32x16 (&acc)[M
                         y[e] = snake_f(x[e], a0[e], i0[e]);
                         y[4 + e] = snake_f(x[4 + e], a1[e], i1[e]);
                     }
-                    if (ok)
-                        *reinterpret_cast<u32x4*>(osnk + flat) = u32x4{pack_op2(y[0], y[1]), pack_op2(y[2], y[3]), pack_op2(y[4], y[5]), pack_op2(y[6], y[7])};
+                    if (ok) store_op8(osnk + flat, y);
                 }
             }
         }
@@ -140,10 +161,10 @@ __device__ __forceinline__ void conv_main_loop(const ConvArgs& g, char* smem, co
     static_assert(TN == 64, "wave tile is TM x 64");
     constexpr int MI = TM / 32;
     constexpr int NI = 2;
-    constexpr int A_CH = BM * 8 / NT;
-    constexpr int B_CH = BN * 8 / NT;
+    constexpr int A_CH = BM * ROW_CH / NT;
+    constexpr int B_CH = BN * ROW_CH / NT;
     constexpr int LPT = A_CH + B_CH;
-    constexpr int STAGE_BYTES = (BM + BN) * 128;
+    constexpr int STAGE_BYTES = (BM + BN) * ROW_B;
     constexpr int D = NS - 1;
     static_assert(A_CH >= 1 && B_CH >= 1 && (D > 0) && (D - 1) * LPT < 64, "bad pipeline geometry");
 
@@ -162,16 +183,16 @@ __device__ __forceinline__ void conv_main_loop(const ConvArgs& g, char* smem, co
 #pragma unroll
     for (int i = 0; i < A_CH; ++i) {
         int q = i * NT + tid;
-        int row = q >> 3, pos = q & 7;
+        int row = q / ROW_CH, pos = q % ROW_CH;
         a_m[i] = (m0 + row) * g.stride;
-        a_coff[i] = (pos ^ ((row >> 1) & 7)) * 8;
+        a_coff[i] = (pos ^ chunk_swz(row)) * CH_EL;
     }
     int b_off[B_CH];
 #pragma unroll
     for (int i = 0; i < B_CH; ++i) {
         int q = i * NT + tid;
-        int row = q >> 3, pos = q & 7;
-        b_off[i] = row * Cin + (pos ^ ((row >> 1) & 7)) * 8;
+        int row = q / ROW_CH, pos = q % ROW_CH;
+        b_off[i] = row * Cin + (pos ^ chunk_swz(row)) * CH_EL;
     }
 
     auto stage_in = [&](int kt, int stage) {
@@ -179,7 +200,7 @@ __device__ __forceinline__ void conv_main_loop(const ConvArgs& g, char* smem, co
         const int ci0 = (kt - tap * cpt) << 6;
         const int off = g.off0 + tap * g.doff;
         char* sa = smem + stage * STAGE_BYTES;
-        char* sb = sa + BM * 128;
+        char* sb = sa + BM * ROW_B;
 #pragma unroll
         for (int i = 0; i < A_CH; ++i) {
             const int r = a_m[i] + off;
@@ -193,9 +214,38 @@ __device__ __forceinline__ void conv_main_loop(const ConvArgs& g, char* smem, co
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wt + b_off[i]),
                                              (__attribute__((address_space(3))) void*)(sb + (i * NT + wave * 64) * 16), 16, 0, 0);
     };
+#if SAT_OP_IS_F32
+    // fp32 build, v_mfma_f32_32x32x2_f32 (K = 2): lane half h takes channels 32 h + 4 ks + e of its row (one 16-byte chunk per
+    // fragment and ks, four MFMAs per chunk).  A and B use the same channel order, so the sum runs over the 64 channels exactly once.
     auto compute = [&](int stage) {
         const char* sa = smem + stage * STAGE_BYTES;
-        const char* sb = sa + BM * 128;
+        const char* sb = sa + BM * ROW_B;
+        f32x4 af[2][MI], bfr[2][NI];
+        auto frag = [&](int ks, int buf) {
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+                af[buf][i] = *reinterpret_cast<const f32x4*>(sa + conv_tile_off(wm * TM + i * 32 + l31, half * 8 + ks));
+#pragma unroll
+            for (int j = 0; j < NI; ++j)
+                bfr[buf][j] = *reinterpret_cast<const f32x4*>(sb + conv_tile_off(wn * TN + j * 32 + l31, half * 8 + ks));
+        };
+        frag(0, 0);
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            if (ks + 1 < 8) frag(ks + 1, (ks + 1) & 1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < MI; ++i)
+#pragma unroll
+                    for (int j = 0; j < NI; ++j)      // C^T: lane = output row
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bfr[ks & 1][j][e], af[ks & 1][i][e], acc[i][j], 0, 0, 0);
+        }
+    };
+#else
+    auto compute = [&](int stage) {
+        const char* sa = smem + stage * STAGE_BYTES;
+        const char* sb = sa + BM * ROW_B;
         opx8 af[2][MI], bfr[2][NI];
         auto frag = [&](int ks, int buf) {
 #pragma unroll
@@ -229,6 +279,7 @@ __device__ __forceinline__ void conv_main_loop(const ConvArgs& g, char* smem, co
             }
         }
     };
+#endif
 
 #pragma unroll
     for (int s = 0; s < D; ++s) stage_in(s, s);       // nk >= D guaranteed by the launcher
@@ -284,6 +335,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_pipe_kernel(ConvArgs g) {
 // ordinary one (bias, raw residual, raw and / or Snake'd output).  Against two launches this removes one write and one read of the
 // activation (537 MB each at the top decoder level), the <= 4-K-tile kernel whose time was all prologue and epilogue, and a launch.
 // ---------------------------------------------------------------------------------------------
+#if !SAT_OP_IS_F32
 struct RuArgs {
     ConvArgs c7;     // in = snake1(x); bias / sn_a / sn_ib: those of the k = 7 convolution and of the Snake behind it
     ConvArgs c1;     // W / bias of the 1 x 1 convolution, res = raw x, out_raw / out_snk (+ the next layer's Snake)
@@ -395,6 +447,7 @@ __global__ __launch_bounds__(WM * WN * 64) void ru_fused_kernel(RuArgs ga) {
     }
     conv_epilogue<MI>(g1, acc, m0 + wm * TM, wn * TN, b, half, l31);
 }
+#endif  // !SAT_OP_IS_F32
 
 // z [B][C][T] fp32 (channel-first) -> [B][T][C] bf16
 __global__ __launch_bounds__(256) void cf_to_cl_kernel(const float* __restrict__ x, op_t* __restrict__ y, int C, int T) {
@@ -506,7 +559,7 @@ __global__ void snake_params_kernel(const float* __restrict__ alpha, const float
 
 template <int BM, int BN, int WM, int WN, int NS>
 int launch_conv_cfg(const ConvArgs& a, int B, hipStream_t s) {
-    constexpr int LDS = NS * (BM + BN) * 128;
+    constexpr int LDS = NS * (BM + BN) * ROW_B;
     auto kern = conv_pipe_kernel<BM, BN, WM, WN, NS>;
     SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS));
     hipLaunchKernelGGL(kern, dim3(cdiv(a.M, BM) * (a.N / BN), B), dim3(WM * WN * 64), LDS, s, a);
@@ -519,12 +572,20 @@ int launch_conv(const ConvArgs& a, int B, hipStream_t s) {
     SAT_CHECK_ARG(a.N % 64 == 0, SAT_E_UNSUPPORTED, "conv: N=%d must be a multiple of 64", a.N);
     SAT_CHECK_ARG(a.zero_page != nullptr, SAT_E_STATE, "conv: zero page missing");
     const int nk = a.taps * (a.Cin / 64);
+#if SAT_OP_IS_F32
+    // fp32: 256-byte rows double every stage, and at 1/16 of the 16-bit MFMA rate one K-tile of compute (1024 cycles per wave and
+    // 32 x 64 block) hides a whole tile of loads: a 2-stage ring, 8 waves of 32 x 64 on 128 x 128 (128 KiB), 4 on 128 x 64 (96 KiB)
+    (void)nk;
+    if (a.N % 128 == 0) return launch_conv_cfg<128, 128, 4, 2, 2>(a, B, s);
+    return launch_conv_cfg<128, 64, 4, 1, 2>(a, B, s);
+#else
     if (a.N % 128 == 0) {
         if (nk >= 3) return launch_conv_cfg<128, 128, 4, 2, 3>(a, B, s);
         return launch_conv_cfg<128, 128, 4, 2, 2>(a, B, s);
     }
     if (nk >= 3) return launch_conv_cfg<256, 64, 8, 1, 3>(a, B, s);
     return launch_conv_cfg<256, 64, 8, 1, 2>(a, B, s);
+#endif
 }
 
 struct Snake {
@@ -615,7 +676,7 @@ int make_conv(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, 
     cw->Cin = Cin; cw->Cout = Cout; cw->taps = k; cw->N = Npad; cw->zero = p->zero_page;
     float* scale = (float*)ar.take((size_t)Cout * 4);
     if (w_f32) *w_f32 = (float*)ar.take((size_t)Cout * Cin * k * 4);
-    else cw->W = (op_t*)ar.take((size_t)k * Npad * Cin * 2);
+    else cw->W = (op_t*)ar.take((size_t)k * Npad * Cin * sizeof(op_t));
     cw->bias = has_bias ? (float*)ar.take((size_t)Cout * 4) : nullptr;
     if (ar.dry) return 0;
     const float *g, *v, *bsrc;
@@ -641,7 +702,7 @@ int make_conv(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, 
 int make_convT(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
     cw->Cin = Cin; cw->Cout = Cout; cw->taps = 2; cw->N = stride * Cout; cw->zero = p->zero_page;
     float* scale = (float*)ar.take((size_t)Cin * 4);
-    cw->W = (op_t*)ar.take((size_t)2 * cw->N * Cin * 2);
+    cw->W = (op_t*)ar.take((size_t)2 * cw->N * Cin * sizeof(op_t));
     cw->bias = (float*)ar.take((size_t)Cout * 4);
     if (ar.dry) return 0;
     const float *g, *v, *bsrc;
@@ -730,7 +791,7 @@ Bufs carve(const OobPlan* p, int B, int T, char* base) {
             mx = std::max(mx, len * b.cout);
         }
     }
-    size_t per = (size_t)round_up((int64_t)(mx * B * 2), 256);
+    size_t per = (size_t)round_up((int64_t)(mx * B * sizeof(op_t)), 256);
     Bufs o;
     o.R = (op_t*)(base ? base : nullptr);
     o.S0 = (op_t*)(base ? base + per : nullptr);
@@ -749,6 +810,7 @@ ConvArgs base_args(const ConvW& w, const op_t* in, int Tin, int M) {
     return a;
 }
 
+#if !SAT_OP_IS_F32
 template <int BN, int WM, int WN, int NS>
 int launch_ru_fused(const RuArgs& a, int B, hipStream_t s) {
     constexpr int LDS = NS * (128 + BN) * 128;
@@ -758,6 +820,7 @@ int launch_ru_fused(const RuArgs& a, int B, hipStream_t s) {
     SAT_LAUNCH_CHECK();
     return 0;
 }
+#endif
 
 // one ResidualUnit (autoencoders.py:45-68): in S (snaked x) + R (raw x) -> R (raw x') and/or Sout (snake_next(x'))
 int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const op_t* S, op_t* Y, op_t* Sout,
@@ -770,6 +833,7 @@ int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const
     c.res = R;
     c.out_raw = need_raw ? R : nullptr;   // in place: each thread reads then writes its own elements
     c.out_snk = Sout; c.sn_a = next.a; c.sn_ib = next.ib;
+#if !SAT_OP_IS_F32      // (fp32 build: the 128 x C intermediate would not fit next to the weight ring; two launches through Y)
     if (!g_ru_unfused && (C == 128 || C == 256)) {      // the whole unit in one launch, the intermediate never leaves LDS
         RuArgs f{a, c};
         f.c7.out_snk = nullptr;
@@ -778,6 +842,7 @@ int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const
         if (C == 128) return launch_ru_fused<128, 4, 2, 2>(f, B, s);
         return launch_ru_fused<256, 2, 4, 3>(f, B, s);
     }
+#endif
     SAT_TRY(launch_conv(a, B, s));
     SAT_TRY(launch_conv(c, B, s));
     return 0;
@@ -940,51 +1005,68 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
 
 }  // namespace SAT_OPNS
 
-#ifndef SAT_OPERAND_F16
-// ---- C ABI (bf16 build only): the plan's operand format (sat_oobleck_cfg.gemm_dtype, first member of both builds' plan) picks the build
-namespace f16 {
-struct OobPlan;
-int oob_plan_create(const sat_oobleck_cfg* cfg, OobPlan** out_plan);
-void oob_plan_destroy(OobPlan* p);
-int oob_plan_set_tensor(OobPlan* p, const char* name, const float* data_dev, int64_t numel);
-int oob_plan_finalize(OobPlan* p, sat_stream_t stream);
-int oob_workspace_bytes(const OobPlan* p, int32_t b, int32_t t_len, size_t* out_bytes);
-int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, void* ws, size_t ws_bytes, sat_stream_t stream);
-int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T, void* ws, size_t ws_bytes, sat_stream_t stream);
-}  // namespace f16
-static inline bool oob_f16(const void* p) { return p && static_cast<const sat_oobleck_cfg*>(p)->gemm_dtype == SAT_GEMM_FP16; }
+#if !defined(SAT_OPERAND_F16) && !defined(SAT_OPERAND_F32)
+// ---- C ABI (bf16 build only): the plan's operand format (sat_oobleck_cfg.gemm_dtype, first member of every build's plan) picks the build
+#define SAT_OOB_DECLARE(NS)                                                                                                       \
+    namespace NS {                                                                                                                \
+    struct OobPlan;                                                                                                               \
+    int oob_plan_create(const sat_oobleck_cfg* cfg, OobPlan** out_plan);                                                          \
+    void oob_plan_destroy(OobPlan* p);                                                                                            \
+    int oob_plan_set_tensor(OobPlan* p, const char* name, const float* data_dev, int64_t numel);                                  \
+    int oob_plan_finalize(OobPlan* p, sat_stream_t stream);                                                                       \
+    int oob_workspace_bytes(const OobPlan* p, int32_t b, int32_t t_len, size_t* out_bytes);                                       \
+    int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, void* ws, size_t ws_bytes, sat_stream_t stream); \
+    int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T, void* ws, size_t ws_bytes, sat_stream_t stream); \
+    }
+SAT_OOB_DECLARE(f16)
+SAT_OOB_DECLARE(f32)
+#undef SAT_OOB_DECLARE
+static inline int32_t oob_dtype(const void* p) { return static_cast<const sat_oobleck_cfg*>(p)->gemm_dtype; }
+// one call into the build that owns plan p (the same function name in namespaces bf16 / f16 / f32)
+#define SAT_OOB_CALL(p, fn, ...)                                                                                                  \
+    (oob_dtype(p) == SAT_GEMM_FP16    ? f16::fn(reinterpret_cast<f16::OobPlan*>(const_cast<sat_oobleck_plan*>(p)), __VA_ARGS__)   \
+     : oob_dtype(p) == SAT_GEMM_FP32X ? f32::fn(reinterpret_cast<f32::OobPlan*>(const_cast<sat_oobleck_plan*>(p)), __VA_ARGS__)   \
+                                      : bf16::fn(reinterpret_cast<bf16::OobPlan*>(const_cast<sat_oobleck_plan*>(p)), __VA_ARGS__))
 
 extern "C" int sat_oobleck_plan_create(const sat_oobleck_cfg* cfg, sat_oobleck_plan** out_plan) {
     SAT_CHECK_ARG(cfg && out_plan, SAT_E_INVALID, "oobleck_plan_create: null argument");
-    SAT_CHECK_ARG(cfg->gemm_dtype == SAT_GEMM_BF16 || cfg->gemm_dtype == SAT_GEMM_FP16, SAT_E_UNSUPPORTED,
-                  "oobleck_plan_create: gemm_dtype must be 0 (bf16) or 3 (fp16)");
-    return cfg->gemm_dtype == SAT_GEMM_FP16 ? f16::oob_plan_create(cfg, reinterpret_cast<f16::OobPlan**>(out_plan))
-                                            : bf16::oob_plan_create(cfg, reinterpret_cast<bf16::OobPlan**>(out_plan));
+    SAT_CHECK_ARG(cfg->gemm_dtype == SAT_GEMM_BF16 || cfg->gemm_dtype == SAT_GEMM_FP16 || cfg->gemm_dtype == SAT_GEMM_FP32X,
+                  SAT_E_UNSUPPORTED, "oobleck_plan_create: gemm_dtype must be 0 (bf16), 3 (fp16) or 2 (fp32)");
+    switch (cfg->gemm_dtype) {
+        case SAT_GEMM_FP16: return f16::oob_plan_create(cfg, reinterpret_cast<f16::OobPlan**>(out_plan));
+        case SAT_GEMM_FP32X: return f32::oob_plan_create(cfg, reinterpret_cast<f32::OobPlan**>(out_plan));
+        default: return bf16::oob_plan_create(cfg, reinterpret_cast<bf16::OobPlan**>(out_plan));
+    }
 }
 extern "C" void sat_oobleck_plan_destroy(sat_oobleck_plan* p) {
-    if (oob_f16(p)) f16::oob_plan_destroy(reinterpret_cast<f16::OobPlan*>(p));
-    else bf16::oob_plan_destroy(reinterpret_cast<bf16::OobPlan*>(p));
+    if (!p) return;
+    switch (oob_dtype(p)) {
+        case SAT_GEMM_FP16: f16::oob_plan_destroy(reinterpret_cast<f16::OobPlan*>(p)); break;
+        case SAT_GEMM_FP32X: f32::oob_plan_destroy(reinterpret_cast<f32::OobPlan*>(p)); break;
+        default: bf16::oob_plan_destroy(reinterpret_cast<bf16::OobPlan*>(p));
+    }
 }
 extern "C" int sat_oobleck_plan_set_tensor(sat_oobleck_plan* p, const char* name, const float* data_dev, int64_t numel) {
-    return oob_f16(p) ? f16::oob_plan_set_tensor(reinterpret_cast<f16::OobPlan*>(p), name, data_dev, numel)
-                      : bf16::oob_plan_set_tensor(reinterpret_cast<bf16::OobPlan*>(p), name, data_dev, numel);
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_set_tensor: null plan");
+    return SAT_OOB_CALL(p, oob_plan_set_tensor, name, data_dev, numel);
 }
 extern "C" int sat_oobleck_plan_finalize(sat_oobleck_plan* p, sat_stream_t stream) {
-    return oob_f16(p) ? f16::oob_plan_finalize(reinterpret_cast<f16::OobPlan*>(p), stream)
-                      : bf16::oob_plan_finalize(reinterpret_cast<bf16::OobPlan*>(p), stream);
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_finalize: null plan");
+    return SAT_OOB_CALL(p, oob_plan_finalize, stream);
 }
 extern "C" int sat_oobleck_workspace_bytes(const sat_oobleck_plan* p, int32_t b, int32_t t_len, size_t* out_bytes) {
-    return oob_f16(p) ? f16::oob_workspace_bytes(reinterpret_cast<const f16::OobPlan*>(p), b, t_len, out_bytes)
-                      : bf16::oob_workspace_bytes(reinterpret_cast<const bf16::OobPlan*>(p), b, t_len, out_bytes);
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_workspace_bytes: null plan");
+    return SAT_OOB_CALL(p, oob_workspace_bytes, b, t_len, out_bytes);
 }
 extern "C" int sat_oobleck_decode(sat_oobleck_plan* p, const float* z_dev, float* audio_dev, int32_t b, int32_t t_len, void* ws, size_t ws_bytes,
                                   sat_stream_t stream) {
-    return oob_f16(p) ? f16::oob_decode(reinterpret_cast<f16::OobPlan*>(p), z_dev, audio_dev, b, t_len, ws, ws_bytes, stream)
-                      : bf16::oob_decode(reinterpret_cast<bf16::OobPlan*>(p), z_dev, audio_dev, b, t_len, ws, ws_bytes, stream);
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_decode: null plan");
+    return SAT_OOB_CALL(p, oob_decode, z_dev, audio_dev, b, t_len, ws, ws_bytes, stream);
 }
 extern "C" int sat_oobleck_encode(sat_oobleck_plan* p, const float* audio_dev, float* out_dev, int32_t b, int32_t t_len, void* ws, size_t ws_bytes,
                                   sat_stream_t stream) {
-    return oob_f16(p) ? f16::oob_encode(reinterpret_cast<f16::OobPlan*>(p), audio_dev, out_dev, b, t_len, ws, ws_bytes, stream)
-                      : bf16::oob_encode(reinterpret_cast<bf16::OobPlan*>(p), audio_dev, out_dev, b, t_len, ws, ws_bytes, stream);
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_encode: null plan");
+    return SAT_OOB_CALL(p, oob_encode, audio_dev, out_dev, b, t_len, ws, ws_bytes, stream);
 }
+#undef SAT_OOB_CALL
 #endif

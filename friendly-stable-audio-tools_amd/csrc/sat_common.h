@@ -23,14 +23,26 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // (dit_plan.hip, layernorm.hip, ...) see op_t = bf16 and treat operand buffers as opaque 16-bit storage.
 // fp16 range policy: conversions SATURATE at +-65504 (MODE.FP16_OVFL, set by sat_f16_saturate() at the top of every kernel of the
 // fp16 build) instead of producing infinities; inf / NaN inputs still propagate.
+// A third operand format exists for oobleck.hip only: -DSAT_OPERAND_F32, op_t = float (namespace f32), the convolutions on the
+// exact f32-input MFMA (the reference's model_half=False codec).  The 16-bit helpers below (mfma_32x32x16, pack_op2, ...) are not
+// defined in that build.
 #ifdef SAT_OPERAND_F16
 typedef _Float16 op_t;
 #define SAT_OPNS f16
 #define SAT_OP_IS_F16 1
+#elif defined(SAT_OPERAND_F32)
+typedef float op_t;
+#define SAT_OPNS f32
+#define SAT_OP_IS_F16 0
 #else
 typedef __bf16 op_t;
 #define SAT_OPNS bf16
 #define SAT_OP_IS_F16 0
+#endif
+#ifdef SAT_OPERAND_F32
+#define SAT_OP_IS_F32 1
+#else
+#define SAT_OP_IS_F32 0
 #endif
 typedef op_t opx8 __attribute__((ext_vector_type(8)));
 typedef op_t opx4 __attribute__((ext_vector_type(4)));
@@ -104,6 +116,7 @@ __device__ __forceinline__ void sat_saturate_for() {
     if constexpr (__is_same(OT, _Float16)) sat_f16_saturate_on();
 }
 
+#if !SAT_OP_IS_F32
 // the two dense 16-bit MFMAs of gfx950 on the operand type of this build (same rate for bf16 and fp16)
 __device__ __forceinline__ f32x16 mfma_32x32x16(opx8 a, opx8 b, f32x16 c) {
 #ifdef SAT_OPERAND_F16
@@ -119,6 +132,7 @@ __device__ __forceinline__ f32x4 mfma_16x16x32(opx8 a, opx8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 #endif
 }
+#endif
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 
@@ -199,12 +213,14 @@ __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
     v[1] = f32_to_bf16(b);
     return __builtin_bit_cast(unsigned, v);
 }
+#if !SAT_OP_IS_F32
 __device__ __forceinline__ unsigned pack_op2(float a, float b) {
     opx2 v;
     v[0] = f32_to_op(a);
     v[1] = f32_to_op(b);
     return __builtin_bit_cast(unsigned, v);
 }
+#endif
 // the same exchange on the fp32 values of a whole block: afterwards v[0..7] are channels c0 .. c0+7 and v[8..15] channels
 // c0+16 .. c0+23 of the lane's row, c0 = 8 * half (16-byte residual reads, 16-byte bf16 stores after packing)
 __device__ __forceinline__ void gather_channel_runs(const f32x16& a, float (&v)[16]) {

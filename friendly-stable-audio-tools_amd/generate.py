@@ -51,6 +51,9 @@ def get_args():
                    help="build extension: operand format of the transformer GEMMs / attention (and, for fp16 / bf16, the codec).  Default: the "
                         "package default (fp16, the reference's own GPU arithmetic); bf16 = 3-4 %% faster, 8x the operand rounding; fp8 = OCP e4m3 "
                         "/ MXFP8 operands for the block GEMMs (BASELINE config 5)")
+    p.add_argument("--codec-dtype", choices=["fp16", "bf16", "fp32"], default=None,
+                   help="build extension: operand format of the VAE decoder, overriding the rule that ties it to --gemm-dtype.  fp32 = the "
+                        "reference's full-precision decode (model_half=False) on the exact f32 MFMA, no fp16 range limit, slower")
     return p.parse_args()
 
 
@@ -137,6 +140,8 @@ def main():
         model.model.model.set_gemm_dtype(args.gemm_dtype)
         if model.pretransform is not None:          # the codec follows by ONE rule (same in bench.py): fp16 with fp16, bf16 with bf16 and the e4m3 modes
             model.pretransform.model.set_gemm_dtype(_config.codec_gemm_dtype(args.gemm_dtype))
+    if args.codec_dtype is not None and model.pretransform is not None:
+        model.pretransform.model.set_gemm_dtype(args.codec_dtype)
     cond_dim = model_config["model"]["conditioning"]["cond_dim"]
     if model.conditioner is not None:
         model.conditioner.set_device(str(device))      # what generate_diffusion_cond does first (generation.py:125); needed by encoders here

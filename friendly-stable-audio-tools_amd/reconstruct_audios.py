@@ -27,6 +27,9 @@ def get_args():
     p.add_argument("--frame-duration", type=float, default=1.0)
     p.add_argument("--overlap-rate", type=float, default=0.01)
     p.add_argument("--batch-size", type=int, default=20)
+    p.add_argument("--codec-dtype", choices=["fp16", "bf16", "fp32"], default=None,
+                   help="build extension: operand format of the encoder / decoder kernels.  Default: the package default (fp16); fp32 = the "
+                        "reference's full-precision codec on the exact f32 MFMA")
     return p.parse_args()
 
 
@@ -48,6 +51,8 @@ def main():
         from stable_audio_tools import synthetic
         model.load_state_dict(synthetic.synth_state_dict(model.state_dict(), args.synthetic_weights))
     model = model.to(device).eval()
+    if args.codec_dtype is not None:
+        model.set_gemm_dtype(args.codec_dtype)
     sr, ratio = model.sample_rate, model.downsampling_ratio
     chunk_size = int((args.frame_duration * sr) / ratio)                              # reconstruct_audios.py:86-87
     overlap = max(int((args.frame_duration * sr * args.overlap_rate) / ratio), 1)

@@ -93,6 +93,10 @@ class DecoderBlock(nn.Module):
             ResidualUnit(out_channels, out_channels, 9, use_snake=use_snake))
 
 
+# operand format -> sat_oobleck_cfg.gemm_dtype (include/sat_hip.h: SAT_GEMM_BF16, SAT_GEMM_FP16, SAT_GEMM_FP32X)
+_CODEC_GEMM_DTYPES = {"bf16": 0, "fp16": 3, "fp32": 2}
+
+
 class _OobleckHip(nn.Module):
     """Shared plan handling of encoder and decoder."""
     _is_decoder = False
@@ -104,11 +108,13 @@ class _OobleckHip(nn.Module):
         self._ws = None
 
     def set_gemm_dtype(self, dtype: str):
-        """Build extension: 16-bit format of the activations and weights inside the convolution kernels -- "fp16" (the package default,
+        """Build extension: format of the activations and weights inside the convolution kernels -- "fp16" (the package default,
         stable_audio_tools/_config.py: IEEE fp16 on the fp16 build of the kernels, what the reference's ``model_half`` runs,
-        ``models/pretransforms.py:39-59``) or "bf16" (8x the rounding error, a few per cent faster).  Parameters stay fp32 in the module; rebuilds the plan on next use."""
-        if dtype not in ("bf16", "fp16"):
-            raise ValueError("the codec kernels take 'bf16' or 'fp16' operands")
+        ``models/pretransforms.py:39-59``), "bf16" (8x the rounding error, a few per cent faster) or "fp32" (fp32 operands on the exact
+        f32-input MFMA: the reference's full-precision codec, ``model_half=False``; no fp16 range limit, several times slower).
+        Parameters stay fp32 in the module; rebuilds the plan on next use."""
+        if dtype not in _CODEC_GEMM_DTYPES:
+            raise ValueError("the codec kernels take 'bf16', 'fp16' or 'fp32' operands")
         if dtype != self.gemm_dtype:
             self.gemm_dtype = dtype
             self._plan_version = None
@@ -141,7 +147,7 @@ class _OobleckHip(nn.Module):
         for i, (c, s) in enumerate(zip(self.c_mults, self.strides)):
             cfg.c_mults[i] = c
             cfg.strides[i] = s
-        cfg.gemm_dtype = 3 if self.gemm_dtype == "fp16" else 0          # SAT_GEMM_FP16 / SAT_GEMM_BF16 (include/sat_hip.h)
+        cfg.gemm_dtype = _CODEC_GEMM_DTYPES[self.gemm_dtype]
         plan = ctypes.c_void_p()
         _hip.check(lib.sat_oobleck_plan_create(ctypes.byref(cfg), ctypes.byref(plan)))
         keep = []
@@ -255,7 +261,7 @@ class AudioAutoencoder(nn.Module):
         self.is_discrete = self.bottleneck and self.bottleneck.is_discrete
 
     def set_gemm_dtype(self, dtype: str):
-        """"bf16" | "fp16" for the encoder and decoder kernels (see ``_OobleckHip.set_gemm_dtype``)."""
+        """"bf16" | "fp16" | "fp32" for the encoder and decoder kernels (see ``_OobleckHip.set_gemm_dtype``)."""
         for part in (self.encoder, self.decoder):
             if isinstance(part, _OobleckHip):
                 part.set_gemm_dtype(dtype)

@@ -293,7 +293,10 @@ typedef struct sat_oobleck_cfg {
     int32_t strides[8];        /* e.g. {2,4,4,8,8} */
     int32_t gemm_dtype;        /* SAT_GEMM_BF16 (0): bf16 activations / weights in the convolutions; SAT_GEMM_FP16 (3): IEEE fp16 (the
                                   reference's `model_half`, models/pretransforms.py:39-59: encoder / decoder in half precision) -- the
-                                  fp16 build of the same kernels, same MFMA rate, saturating conversions; fp32 accumulation either way */
+                                  fp16 build of the same kernels, same MFMA rate, saturating conversions; fp32 accumulation either way;
+                                  SAT_GEMM_FP32X (2): fp32 activations / weights on the exact f32-input MFMA (the reference's
+                                  `model_half=False` codec: no operand rounding, no fp16 range limit, 2x the workspace, 1/16 of the
+                                  16-bit MFMA rate).  SAT_GEMM_FP8 is rejected (SAT_E_UNSUPPORTED). */
 } sat_oobleck_cfg;
 
 int sat_oobleck_plan_create(const sat_oobleck_cfg* cfg, sat_oobleck_plan** out_plan);

@@ -1,5 +1,7 @@
 """Developer probe: full-size Oobleck decode (1024 latent frames) and encode (the same audio back) alone, for rocprofv3 / A-B runs
-of the codec kernels (SAT_HIP_EXP=1 SAT_OOBLECK_UNFUSED=1: experiments build, two launches per ResidualUnit).  Not part of the product or the tests."""
+of the codec kernels (SAT_HIP_EXP=1 SAT_OOBLECK_UNFUSED=1: experiments build, two launches per ResidualUnit).  Not part of the product or the tests.
+Usage: python tools/codec_only.py [fp16|bf16|fp32]   (operand format of the codec kernels; default: the package default)."""
+import ctypes
 import os
 import sys
 import time
@@ -21,6 +23,9 @@ with _init.skip_init():
     vae = S.create_model_from_config(MC.stable_audio_vae())
 vae.load_state_dict(synthetic.synth_state_dict(vae.state_dict(), 3))
 vae = vae.to(dev).eval()
+if len(sys.argv) > 1:
+    vae.set_gemm_dtype(sys.argv[1])
+print(f"codec operands: {vae.decoder.gemm_dtype}", flush=True)
 z = torch.randn(1, 64, int(os.environ.get("FRAMES", "1024")), device=dev)
 
 
@@ -38,3 +43,9 @@ ms, audio = timeit(lambda: vae.decode(z), 5)
 print(f"decode {z.shape[-1]} frames: {ms:.2f} ms", flush=True)
 ms, lat = timeit(lambda: vae.encode(audio), 5)
 print(f"encode {audio.shape[-1]} samples: {ms:.2f} ms", flush=True)
+ws = {}
+for name, part in (("decode", vae.decoder), ("encode", vae.encoder)):
+    need = ctypes.c_size_t()
+    _hip.check(_hip.lib().sat_oobleck_workspace_bytes(part._plan, 1, z.shape[-1], ctypes.byref(need)))
+    ws[name] = need.value
+print(f"workspace: decode {ws['decode'] / 2**30:.2f} GiB, encode {ws['encode'] / 2**30:.2f} GiB", flush=True)
