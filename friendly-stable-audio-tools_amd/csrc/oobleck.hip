@@ -8,12 +8,18 @@
 //   * transposed conv k=2s  : polyphase -- N = s*Cout (phase-major), 2 taps at rows m, m-1;
 //                             row m of the GEMM is the contiguous output span
 //                             [(m*s - pad)*Cout, +s*Cout)                     (:102-105)
+//   * nearest upsample + conv : Upsample(s) then Conv1d(k=2s, "same") (:95-99) in the same polyphase form with THREE taps at
+//                             rows m-1, m, m+1 and per-phase sums of the 2s original taps (wn_pack_nearest_kernel); the
+//                             upsampled tensor never exists
 // Contiguous sample windows are loaded with coalesced 16-byte accesses ([t][c] rows are
 // 128..4096 B) into XOR-swizzled LDS tiles; taps re-read the window through L2.
 // SnakeBeta (models/blocks.py:318-319) is never a standalone pass: the PRODUCER's epilogue
 // applies the consumer's Snake to the fp32 accumulator and stores the activated tensor
 // (and the raw tensor only where a residual needs it).  Weight norm (dac WNConv1d) is
-// folded once at plan finalize.
+// folded once at plan finalize.  ELU (use_snake=False) takes Snake's place in the same epilogues, and the decoder's final tanh sits in
+// the epilogue of its last convolution; both are wave-uniform run-time fields of ConvArgs, not further kernel instantiations.
+// Stage widths that are not multiples of 64 are rounded up inside the plan: weights, biases and Snake parameters are zero-padded at
+// finalize, so the pad channels of every activation tensor are written as exact zeros (act(0) = 0) and no kernel masks channels.
 #include <math.h>
 
 #include <algorithm>
@@ -38,7 +44,7 @@ struct ConvArgs {
     const op_t* res;       // residual (raw), same indexing as out ; or null
     op_t* out_raw;         // or null
     op_t* out_snk;         // or null
-    const float* sn_a;       // exp(alpha)[Cout]
+    const float* sn_a;     // exp(alpha)[Cout]
     const float* sn_ib;      // 1/(exp(beta)+1e-9)[Cout]
     long long out_bstride;   // elements per batch item
     long long out_shift;     // flat = m*N + out_shift + n ; valid if 0 <= flat < out_limit
@@ -46,7 +52,21 @@ struct ConvArgs {
     float* out_cf;           // channel-first fp32 output [B][cf_channels][M] (final convs) or null
     int cf_channels;
     const op_t* zero_page; // >= one K-tile row (ROW_B <= 256 B) of zeros: LDS-DMA source of the rows that fall into the conv padding
+    // (the option fields come last: the fields above keep the offsets they had before the options existed)
+    int act;                 // activation behind out_snk: ACT_SNAKE (sn_a / sn_ib) or ACT_ELU (no parameters)
+    int tanh_out;            // out_cf only: tanh on the result (OobleckDecoder final_tanh)
 };
+
+enum { ACT_SNAKE = SAT_OOBLECK_ACT_SNAKE, ACT_ELU = SAT_OOBLECK_ACT_ELU, ACT_RUNTIME = -1 };
+
+// nn.ELU(alpha = 1) on the fp32 accumulator; elu(0) == 0 exactly in both forms, which keeps the pad channels zero
+__device__ __forceinline__ float elu_f(float v) {
+#if SAT_OP_IS_F32
+    return v > 0.f ? v : expm1f(v);
+#else
+    return v > 0.f ? v : __expf(v) - 1.f;      // absolute error ~1e-7, below the rounding of the 16-bit store
+#endif
+}
 
 __device__ __forceinline__ float snake_f(float v, float a, float ib) {
 #if SAT_OP_IS_F32
@@ -82,7 +102,11 @@ __device__ __forceinline__ void store_op8(op_t* p, const float (&x)[8]) {
 // access: the unit's 1 x 1 convolution then spent its whole time issuing them), bias and Snake parameters come as float4 pairs.
 // flat = m*N + out_shift + n addresses plain convolutions (shift 0) and the polyphase transposed ones (N = stride * Cout columns per
 // input row, shifted by the padding); shift and limit are multiples of Cout, groups are 8-aligned: a group is in or out as a whole.
-template <int MI>
+// ACT is the activation behind out_snk: ACT_RUNTIME in the convolution kernel, which tests the wave-uniform g.act at each group (one
+// kernel per tile whatever the plan's options: 68 VGPRs in the 16-bit builds and 97 in the fp32 one, as before the options existed;
+// a branch hoisted around two copies of the epilogue, and an activation template parameter, timed the same within the box's spread,
+// profiles/codec_options_timing.txt), or a compile-time constant in the fused ResidualUnit kernel.
+template <int MI, int ACT>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& g, f32x16 (&acc)[MI][2], const int mw, const int nw, const int b,
                                               const int half, const int l31) {
     if (g.out_cf) {      // fp32 channel-first result of the last convolution: consecutive lanes = consecutive time steps
@@ -95,7 +119,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& g, f32x16 (&acc)[M
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int n = nw + j * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
-                    if (m < g.M && n < g.cf_channels) o[(size_t)n * g.M + m] = acc[i][j][r] + (g.bias ? g.bias[n % g.Cout] : 0.f);
+                    if (m < g.M && n < g.cf_channels) {
+                        const float v = acc[i][j][r] + (g.bias ? g.bias[n % g.Cout] : 0.f);
+                        o[(size_t)n * g.M + m] = g.tanh_out ? tanhf(v) : v;
+                    }
                 }
         }
         return;
@@ -134,13 +161,18 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& g, f32x16 (&acc)[M
                 }
                 if (oraw && ok) store_op8(oraw + flat, x);
                 if (osnk) {
-                    const f32x4 a0 = *reinterpret_cast<const f32x4*>(g.sn_a + co), a1 = *reinterpret_cast<const f32x4*>(g.sn_a + co + 4);
-                    const f32x4 i0 = *reinterpret_cast<const f32x4*>(g.sn_ib + co), i1 = *reinterpret_cast<const f32x4*>(g.sn_ib + co + 4);
                     float y[8];
+                    if (ACT == ACT_RUNTIME ? g.act == ACT_ELU : ACT == ACT_ELU) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        y[e] = snake_f(x[e], a0[e], i0[e]);
-                        y[4 + e] = snake_f(x[4 + e], a1[e], i1[e]);
+                        for (int e = 0; e < 8; ++e) y[e] = elu_f(x[e]);
+                    } else {
+                        const f32x4 a0 = *reinterpret_cast<const f32x4*>(g.sn_a + co), a1 = *reinterpret_cast<const f32x4*>(g.sn_a + co + 4);
+                        const f32x4 i0 = *reinterpret_cast<const f32x4*>(g.sn_ib + co), i1 = *reinterpret_cast<const f32x4*>(g.sn_ib + co + 4);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            y[e] = snake_f(x[e], a0[e], i0[e]);
+                            y[4 + e] = snake_f(x[4 + e], a1[e], i1[e]);
+                        }
                     }
                     if (ok) store_op8(osnk + flat, y);
                 }
@@ -324,7 +356,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_pipe_kernel(ConvArgs g) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     conv_main_loop<BM, BN, WM, WN, NS>(g, smem, m0, n0, b, acc);
-    conv_epilogue<MI>(g, acc, m0 + wm * TM, n0 + wn * TN, b, lane >> 5, lane & 31);
+    conv_epilogue<MI, ACT_RUNTIME>(g, acc, m0 + wm * TM, n0 + wn * TN, b, lane >> 5, lane & 31);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -341,7 +373,7 @@ struct RuArgs {
     ConvArgs c1;     // W / bias of the 1 x 1 convolution, res = raw x, out_raw / out_snk (+ the next layer's Snake)
 };
 
-template <int BN, int WM, int WN, int NS>
+template <int BN, int WM, int WN, int NS, int ACT>      // ACT: the plan's activation (both Snakes / ELUs of the unit and the one behind it)
 __global__ __launch_bounds__(WM * WN * 64) void ru_fused_kernel(RuArgs ga) {
     sat_f16_saturate();
     constexpr int BM = 128;
@@ -393,7 +425,7 @@ __global__ __launch_bounds__(WM * WN * 64) void ru_fused_kernel(RuArgs ga) {
     w_in(0, 0);
     w_in(1, 1);
 
-    // ---- first epilogue: y = snake(acc + bias) -> bf16 -> LDS, 8 channels (one 16-byte chunk of a K-tile row) per store
+    // ---- first epilogue: y = act(acc + bias) -> bf16 -> LDS, 8 channels (one 16-byte chunk of a K-tile row) per store
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
         const int row = wm * TM + i * 32 + l31;
@@ -405,13 +437,21 @@ __global__ __launch_bounds__(WM * WN * 64) void ru_fused_kernel(RuArgs ga) {
             for (int grp = 0; grp < 2; ++grp) {
                 const int n = wn * TN + j * 32 + grp * 16 + 8 * half;
                 const f32x4 b0 = *reinterpret_cast<const f32x4*>(g7.bias + n), b1 = *reinterpret_cast<const f32x4*>(g7.bias + n + 4);
-                const f32x4 a0 = *reinterpret_cast<const f32x4*>(g7.sn_a + n), a1 = *reinterpret_cast<const f32x4*>(g7.sn_a + n + 4);
-                const f32x4 i0 = *reinterpret_cast<const f32x4*>(g7.sn_ib + n), i1 = *reinterpret_cast<const f32x4*>(g7.sn_ib + n + 4);
                 float y[8];
+                if (ACT == ACT_ELU) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    y[e] = snake_f(v[grp * 8 + e] + b0[e], a0[e], i0[e]);
-                    y[4 + e] = snake_f(v[grp * 8 + 4 + e] + b1[e], a1[e], i1[e]);
+                    for (int e = 0; e < 4; ++e) {
+                        y[e] = elu_f(v[grp * 8 + e] + b0[e]);
+                        y[4 + e] = elu_f(v[grp * 8 + 4 + e] + b1[e]);
+                    }
+                } else {
+                    const f32x4 a0 = *reinterpret_cast<const f32x4*>(g7.sn_a + n), a1 = *reinterpret_cast<const f32x4*>(g7.sn_a + n + 4);
+                    const f32x4 i0 = *reinterpret_cast<const f32x4*>(g7.sn_ib + n), i1 = *reinterpret_cast<const f32x4*>(g7.sn_ib + n + 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        y[e] = snake_f(v[grp * 8 + e] + b0[e], a0[e], i0[e]);
+                        y[4 + e] = snake_f(v[grp * 8 + 4 + e] + b1[e], a1[e], i1[e]);
+                    }
                 }
                 *reinterpret_cast<u32x4*>(smem + (n >> 6) * (BM * 128) + lds_tile_off(row, (n & 63) >> 3)) =
                     u32x4{pack_op2(y[0], y[1]), pack_op2(y[2], y[3]), pack_op2(y[4], y[5]), pack_op2(y[6], y[7])};
@@ -445,12 +485,12 @@ __global__ __launch_bounds__(WM * WN * 64) void ru_fused_kernel(RuArgs ga) {
             w_in(kt + 2, kt & 1);
         }
     }
-    conv_epilogue<MI>(g1, acc, m0 + wm * TM, wn * TN, b, half, l31);
+    conv_epilogue<MI, ACT>(g1, acc, m0 + wm * TM, wn * TN, b, half, l31);
 }
 #endif  // !SAT_OP_IS_F32
 
-// z [B][C][T] fp32 (channel-first) -> [B][T][C] bf16
-__global__ __launch_bounds__(256) void cf_to_cl_kernel(const float* __restrict__ x, op_t* __restrict__ y, int C, int T) {
+// z [B][C][T] fp32 (channel-first) -> [B][T][Cp] bf16, channels C..Cp-1 (the plan's padding to a multiple of 64) written as zeros
+__global__ __launch_bounds__(256) void cf_to_cl_kernel(const float* __restrict__ x, op_t* __restrict__ y, int C, int Cp, int T) {
     sat_f16_saturate();
     __shared__ float tile[64][65];
     const int b = blockIdx.z, t0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
@@ -461,16 +501,19 @@ __global__ __launch_bounds__(256) void cf_to_cl_kernel(const float* __restrict__
     __syncthreads();
     for (int i = threadIdx.x; i < 64 * 64; i += 256) {
         int t = i >> 6, c = i & 63;
-        if (c0 + c < C && t0 + t < T) y[((size_t)b * T + t0 + t) * C + c0 + c] = f32_to_op(tile[c][t]);
+        if (c0 + c < Cp && t0 + t < T) y[((size_t)b * T + t0 + t) * Cp + c0 + c] = f32_to_op(tile[c][t]);
     }
 }
 
 // OobleckEncoder first conv (autoencoders.py:136): audio [B][Cin<=2][L] fp32 channel-first,
-// k=7 pad 3 -> Cout channels; writes raw + snaked channels-last bf16.  VALU (K = 14).
+// k=7 pad 3 -> Cout channels; writes raw + activated channels-last bf16 rows of Cp >= Cout channels (pad channels: zeros).
+// VALU (K = 14).  GENERAL = false is the Stable Audio case (Snake, Cp == Cout) with the tests for pad channels and ELU folded away, so
+// that its code, and with it the rounding of its multiply-add chain, is what it was before those options existed.
+template <bool GENERAL>
 __global__ __launch_bounds__(256) void first_conv_kernel(const float* __restrict__ x, const float* __restrict__ w /*[Cout][Cin][7]*/,
                                                          const float* __restrict__ bias, const float* __restrict__ sn_a,
-                                                         const float* __restrict__ sn_ib, op_t* __restrict__ out_raw,
-                                                         op_t* __restrict__ out_snk, int Cin, int Cout, int L) {
+                                                         const float* __restrict__ sn_ib, int act, op_t* __restrict__ out_raw,
+                                                         op_t* __restrict__ out_snk, int Cin, int Cout, int Cp, int L) {
     sat_f16_saturate();
     __shared__ float xs[2][64 + 6];
     const int b = blockIdx.y, t0 = blockIdx.x * 64;
@@ -480,13 +523,16 @@ __global__ __launch_bounds__(256) void first_conv_kernel(const float* __restrict
         xs[c][k] = (c < Cin && t >= 0 && t < L) ? x[((size_t)b * Cin + c) * L + t] : 0.f;
     }
     __syncthreads();
-    for (int co = threadIdx.x; co < Cout; co += 256) {
+    for (int co = threadIdx.x; co < Cp; co += 256) {
+        const bool real = !GENERAL || co < Cout;
         float wr[2][7];
 #pragma unroll
         for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int k = 0; k < 7; ++k) wr[c][k] = (c < Cin) ? w[((size_t)co * Cin + c) * 7 + k] : 0.f;
-        const float bv = bias[co], a = sn_a[co], ib = sn_ib[co];
+            for (int k = 0; k < 7; ++k) wr[c][k] = (real && c < Cin) ? w[((size_t)co * Cin + c) * 7 + k] : 0.f;
+        const float bv = real ? bias[co] : 0.f;
+        const bool elu = GENERAL && act == ACT_ELU;
+        const float a = elu ? 0.f : sn_a[co], ib = elu ? 0.f : sn_ib[co];      // [Cp], zero-padded
         for (int tt = 0; tt < 64; ++tt) {
             if (t0 + tt >= L) break;
             float acc = bv;
@@ -494,9 +540,9 @@ __global__ __launch_bounds__(256) void first_conv_kernel(const float* __restrict
             for (int c = 0; c < 2; ++c)
 #pragma unroll
                 for (int k = 0; k < 7; ++k) acc += wr[c][k] * xs[c][tt + k];
-            size_t o = ((size_t)b * L + t0 + tt) * Cout + co;
+            size_t o = ((size_t)b * L + t0 + tt) * Cp + co;
             out_raw[o] = f32_to_op(acc);
-            out_snk[o] = f32_to_op(snake_f(acc, a, ib));
+            out_snk[o] = f32_to_op(elu ? elu_f(acc) : snake_f(acc, a, ib));
         }
     }
 }
@@ -517,16 +563,16 @@ __global__ __launch_bounds__(256) void wn_invnorm_kernel(const float* __restrict
     __syncthreads();
     if (threadIdx.x == 0) scale[i] = gsc[i] / sqrtf(red[0] + red[1] + red[2] + red[3]);
 }
-// Conv1d v[co][ci][k] -> W[j][co_pad][ci] bf16 (rows co >= Cout are zero)
+// Conv1d v[co][ci][k] -> W[j][Npad][Kpad] bf16 (rows co >= Cout and columns ci >= Cin are zero)
 __global__ void wn_pack_conv_kernel(const float* __restrict__ v, const float* __restrict__ scale, op_t* __restrict__ W,
-                                    int Cout, int Cin, int k, int Npad) {
+                                    int Cout, int Cin, int k, int Npad, int Kpad) {
     sat_f16_saturate();
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)k * Npad * Cin) return;
-    int ci = (int)(i % Cin);
-    int n = (int)((i / Cin) % Npad);
-    int j = (int)(i / ((size_t)Cin * Npad));
-    W[i] = f32_to_op(n < Cout ? v[((size_t)n * Cin + ci) * k + j] * scale[n] : 0.f);
+    if (i >= (size_t)k * Npad * Kpad) return;
+    int ci = (int)(i % Kpad);
+    int n = (int)((i / Kpad) % Npad);
+    int j = (int)(i / ((size_t)Kpad * Npad));
+    W[i] = f32_to_op(n < Cout && ci < Cin ? v[((size_t)n * Cin + ci) * k + j] * scale[n] : 0.f);
 }
 // same, fp32, original layout (for the VALU first conv)
 __global__ void wn_fold_f32_kernel(const float* __restrict__ v, const float* __restrict__ scale, float* __restrict__ w, int slice,
@@ -535,26 +581,48 @@ __global__ void wn_fold_f32_kernel(const float* __restrict__ v, const float* __r
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) w[i] = v[i] * scale[i / slice];
 }
-// ConvTranspose1d v[ci][co][k=2s] -> W[j][phi*Cout+co][ci] = w[ci][co][phi + j*s]
+// ConvTranspose1d v[ci][co][k=2s] -> W[j][phi*Np+co][Kp] = w[ci][co][phi + j*s]  (Np, Kp: Cout, Cin rounded up; the padding is zero)
 __global__ void wn_pack_convT_kernel(const float* __restrict__ v, const float* __restrict__ scale, op_t* __restrict__ W,
-                                     int Cin, int Cout, int s) {
+                                     int Cin, int Cout, int s, int Kp, int Np) {
     sat_f16_saturate();
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = s * Cout;
-    if (i >= (size_t)2 * N * Cin) return;
-    int ci = (int)(i % Cin);
-    int n = (int)((i / Cin) % N);
-    int j = (int)(i / ((size_t)Cin * N));
-    int phi = n / Cout, co = n - phi * Cout;
-    W[i] = f32_to_op(v[((size_t)ci * Cout + co) * (2 * s) + phi + j * s] * scale[ci]);
+    const int N = s * Np;
+    if (i >= (size_t)2 * N * Kp) return;
+    int ci = (int)(i % Kp);
+    int n = (int)((i / Kp) % N);
+    int j = (int)(i / ((size_t)Kp * N));
+    int phi = n / Np, co = n - phi * Np;
+    W[i] = f32_to_op(co < Cout && ci < Cin ? v[((size_t)ci * Cout + co) * (2 * s) + phi + j * s] * scale[ci] : 0.f);
 }
+// Upsample(scale_factor = s, nearest) + Conv1d v[co][ci][k=2s], padding "same" (s-1 left, s right): output sample m*s + phi reads the
+// upsampled positions m*s + phi + j - (s-1), j = 0..2s-1, i.e. input rows m-1, m, m+1.  W[r+1][phi*Np+co][Kp] = the fp32 sum of the
+// folded taps j with floor((phi + j - s + 1) / s) == r, r = -1, 0, 1.
+__global__ void wn_pack_nearest_kernel(const float* __restrict__ v, const float* __restrict__ scale, op_t* __restrict__ W,
+                                       int Cin, int Cout, int s, int Kp, int Np) {
+    sat_f16_saturate();
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = s * Np;
+    if (i >= (size_t)3 * N * Kp) return;
+    int ci = (int)(i % Kp);
+    int n = (int)((i / Kp) % N);
+    int r = (int)(i / ((size_t)Kp * N)) - 1;
+    int phi = n / Np, co = n - phi * Np;
+    float acc = 0.f;
+    if (co < Cout && ci < Cin) {
+        // the taps of row r: (r*s + s - 1 - phi) <= j < ((r+1)*s + s - 1 - phi), clipped to [0, 2s)
+        const int lo = max(0, r * s + s - 1 - phi), hi = min(2 * s, (r + 1) * s + s - 1 - phi);
+        for (int j = lo; j < hi; ++j) acc += v[((size_t)co * Cin + ci) * (2 * s) + j] * scale[co];
+    }
+    W[i] = f32_to_op(acc);
+}
+// a / ib hold Cp >= C entries; the pad entries are zero (snake(0) = 0 + 0 * sin^2(0))
 __global__ void snake_params_kernel(const float* __restrict__ alpha, const float* __restrict__ beta, float* __restrict__ a,
-                                    float* __restrict__ ib, int C) {
+                                    float* __restrict__ ib, int C, int Cp) {
     sat_f16_saturate();
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C) return;
-    a[i] = expf(alpha[i]);
-    ib[i] = 1.0f / (expf(beta[i]) + 0.000000001f);
+    if (i >= Cp) return;
+    a[i] = i < C ? expf(alpha[i]) : 0.f;
+    ib[i] = i < C ? 1.0f / (expf(beta[i]) + 0.000000001f) : 0.f;
 }
 
 template <int BM, int BN, int WM, int WN, int NS>
@@ -588,9 +656,12 @@ int launch_conv(const ConvArgs& a, int B, hipStream_t s) {
 #endif
 }
 
+// the activation in front of a convolution: SnakeBeta with its folded parameters, or ELU (no parameters)
 struct Snake {
     float *a = nullptr, *ib = nullptr;
+    int act = ACT_SNAKE;
 };
+inline int pad64(int c) { return (int)round_up(c, 64); }
 // experiments build only: SAT_OOBLECK_UNFUSED=1 in the environment runs every ResidualUnit as two launches (conv7, conv1) for A/B
 // measurements (tools/codec_only.py)
 #ifdef SAT_GEMM_EXPERIMENTS
@@ -604,7 +675,7 @@ constexpr bool g_ru_unfused = false;
 struct ConvW {
     op_t* W = nullptr;
     float* bias = nullptr;
-    int Cin = 0, Cout = 0, taps = 0, N = 0;
+    int Cin = 0, Cout = 0, taps = 0, N = 0;      // Cin / Cout: the padded widths the kernels see
     const op_t* zero = nullptr;   // the plan's zero page (LDS-DMA source for padding rows)
 };
 
@@ -613,6 +684,7 @@ struct ConvW {
 namespace SAT_OPNS {
 struct OobPlan {
     sat_oobleck_cfg cfg;          // first member: the C entry points read cfg.gemm_dtype through the opaque pointer to pick the build
+    sat_oobleck_options opt;
     std::map<std::string, std::pair<const float*, int64_t>> tensors;
     bool finalized = false;
     char* arena = nullptr;
@@ -626,7 +698,7 @@ struct OobPlan {
         ConvW resample;          // convT (decoder) / strided conv (encoder)
         Snake ru_sn1[3], ru_sn2[3];
         ConvW ru_c7[3], ru_c1[3];
-        int stride, cin, cout;
+        int stride, cin, cout;   // cin / cout: padded to multiples of 64
     };
     std::vector<Block> blocks;
     Snake final_snake;
@@ -658,28 +730,44 @@ int get_tensor(OobPlan* p, const std::string& name, int64_t numel, const float**
 }
 
 int make_snake(OobPlan* p, Arena& ar, const std::string& pfx, int C, Snake* sn, hipStream_t s) {
-    sn->a = (float*)ar.take((size_t)C * 4);
-    sn->ib = (float*)ar.take((size_t)C * 4);
+    sn->act = p->opt.activation;
+    if (sn->act == ACT_ELU) return 0;        // nn.ELU has no tensors: nothing to ask for
+    const int Cp = pad64(C);
+    sn->a = (float*)ar.take((size_t)Cp * 4);
+    sn->ib = (float*)ar.take((size_t)Cp * 4);
     if (ar.dry) return 0;
     const float *al, *be;
     SAT_TRY(get_tensor(p, pfx + "alpha", C, &al));
     SAT_TRY(get_tensor(p, pfx + "beta", C, &be));
-    hipLaunchKernelGGL(snake_params_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, al, be, sn->a, sn->ib, C);
+    hipLaunchKernelGGL(snake_params_kernel, dim3(cdiv(Cp, 256)), dim3(256), 0, s, al, be, sn->a, sn->ib, C, Cp);
     SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+// bias[Cp]: the tensor's C values, then zeros
+int make_bias(OobPlan* p, Arena& ar, const std::string& name, int C, float** out, hipStream_t s) {
+    const int Cp = pad64(C);
+    *out = (float*)ar.take((size_t)Cp * 4);
+    if (ar.dry) return 0;
+    const float* bsrc;
+    SAT_TRY(get_tensor(p, name, C, &bsrc));
+    if (Cp > C) SAT_HIP(hipMemsetAsync(*out + C, 0, (size_t)(Cp - C) * 4, s));
+    SAT_HIP(hipMemcpyAsync(*out, bsrc, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
 // Conv1d weight [Cout][Cin][k]
 int make_conv(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, int k, bool has_bias, ConvW* cw,
               hipStream_t s, float** w_f32 = nullptr) {
-    const int Npad = (int)round_up(Cout, 64);
-    cw->Cin = Cin; cw->Cout = Cout; cw->taps = k; cw->N = Npad; cw->zero = p->zero_page;
+    const int Npad = pad64(Cout), Kpad = pad64(Cin);
+    cw->Cin = Kpad; cw->Cout = Npad; cw->taps = k; cw->N = Npad; cw->zero = p->zero_page;
     float* scale = (float*)ar.take((size_t)Cout * 4);
     if (w_f32) *w_f32 = (float*)ar.take((size_t)Cout * Cin * k * 4);
-    else cw->W = (op_t*)ar.take((size_t)k * Npad * Cin * sizeof(op_t));
-    cw->bias = has_bias ? (float*)ar.take((size_t)Cout * 4) : nullptr;
+    else cw->W = (op_t*)ar.take((size_t)k * Npad * Kpad * sizeof(op_t));
+    cw->bias = nullptr;
+    if (has_bias) SAT_TRY(make_bias(p, ar, pfx + "bias", Cout, &cw->bias, s));
     if (ar.dry) return 0;
-    const float *g, *v, *bsrc;
+    const float *g, *v;
     SAT_TRY(get_tensor(p, pfx + "weight_g", Cout, &g));
     SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cout * Cin * k, &v));
     hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cout), dim3(256), 0, s, v, g, scale, Cin * k);
@@ -687,12 +775,9 @@ int make_conv(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, 
         size_t n = (size_t)Cout * Cin * k;
         hipLaunchKernelGGL(wn_fold_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, *w_f32, Cin * k, n);
     } else {
-        size_t n = (size_t)k * Npad * Cin;
-        hipLaunchKernelGGL(wn_pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, cw->W, Cout, Cin, k, Npad);
-    }
-    if (has_bias) {
-        SAT_TRY(get_tensor(p, pfx + "bias", Cout, &bsrc));
-        SAT_HIP(hipMemcpyAsync(cw->bias, bsrc, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
+        size_t n = (size_t)k * Npad * Kpad;
+        hipLaunchKernelGGL(wn_pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, cw->W, Cout, Cin, k, Npad,
+                           Kpad);
     }
     SAT_LAUNCH_CHECK();
     return 0;
@@ -700,19 +785,38 @@ int make_conv(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, 
 
 // ConvTranspose1d weight [Cin][Cout][2s]
 int make_convT(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
-    cw->Cin = Cin; cw->Cout = Cout; cw->taps = 2; cw->N = stride * Cout; cw->zero = p->zero_page;
+    const int Kp = pad64(Cin), Np = pad64(Cout);
+    cw->Cin = Kp; cw->Cout = Np; cw->taps = 2; cw->N = stride * Np; cw->zero = p->zero_page;
     float* scale = (float*)ar.take((size_t)Cin * 4);
-    cw->W = (op_t*)ar.take((size_t)2 * cw->N * Cin * sizeof(op_t));
-    cw->bias = (float*)ar.take((size_t)Cout * 4);
+    cw->W = (op_t*)ar.take((size_t)2 * cw->N * Kp * sizeof(op_t));
+    SAT_TRY(make_bias(p, ar, pfx + "bias", Cout, &cw->bias, s));
     if (ar.dry) return 0;
-    const float *g, *v, *bsrc;
+    const float *g, *v;
     SAT_TRY(get_tensor(p, pfx + "weight_g", Cin, &g));
     SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cin * Cout * 2 * stride, &v));
-    SAT_TRY(get_tensor(p, pfx + "bias", Cout, &bsrc));
     hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cin), dim3(256), 0, s, v, g, scale, Cout * 2 * stride);
-    size_t n = (size_t)2 * cw->N * Cin;
-    hipLaunchKernelGGL(wn_pack_convT_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, cw->W, Cin, Cout, stride);
-    SAT_HIP(hipMemcpyAsync(cw->bias, bsrc, (size_t)Cout * 4, hipMemcpyDeviceToDevice, s));
+    size_t n = (size_t)2 * cw->N * Kp;
+    hipLaunchKernelGGL(wn_pack_convT_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, cw->W, Cin, Cout, stride, Kp,
+                       Np);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+// Upsample(nearest, s) + bias-free Conv1d weight [Cout][Cin][2s] -> the three-tap polyphase form
+int make_nearest(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
+    const int Kp = pad64(Cin), Np = pad64(Cout);
+    cw->Cin = Kp; cw->Cout = Np; cw->taps = 3; cw->N = stride * Np; cw->zero = p->zero_page;
+    float* scale = (float*)ar.take((size_t)Cout * 4);
+    cw->W = (op_t*)ar.take((size_t)3 * cw->N * Kp * sizeof(op_t));
+    cw->bias = nullptr;
+    if (ar.dry) return 0;
+    const float *g, *v;
+    SAT_TRY(get_tensor(p, pfx + "weight_g", Cout, &g));
+    SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cout * Cin * 2 * stride, &v));
+    hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cout), dim3(256), 0, s, v, g, scale, Cin * 2 * stride);
+    size_t n = (size_t)3 * cw->N * Kp;
+    hipLaunchKernelGGL(wn_pack_nearest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, cw->W, Cin, Cout, stride, Kp,
+                       Np);
     SAT_LAUNCH_CHECK();
     return 0;
 }
@@ -738,13 +842,18 @@ int build(OobPlan* p, Arena& ar, hipStream_t s) {
         for (int bi = 0; bi < nb; ++bi) {
             const int i = nb - bi;   // reference loop index: range(depth-1, 0, -1)
             auto& blk = p->blocks[bi];
-            blk.cin = c.c_mults[i - 1] * c.channels;
-            blk.cout = (i - 2 >= 0 ? c.c_mults[i - 2] : 1) * c.channels;
+            const int cin = c.c_mults[i - 1] * c.channels;
+            const int cout = (i - 2 >= 0 ? c.c_mults[i - 2] : 1) * c.channels;
+            blk.cin = pad64(cin);
+            blk.cout = pad64(cout);
             blk.stride = c.strides[i - 1];
             const std::string pf = "layers." + std::to_string(bi + 1) + ".";
-            SAT_TRY(make_snake(p, ar, pf + "layers.0.", blk.cin, &blk.sn_in, s));
-            SAT_TRY(make_convT(p, ar, pf + "layers.1.", blk.cin, blk.cout, blk.stride, &blk.resample, s));
-            for (int r = 0; r < 3; ++r) SAT_TRY(make_ru(p, ar, pf + "layers." + std::to_string(2 + r) + ".", blk.cout, blk, r, s));
+            SAT_TRY(make_snake(p, ar, pf + "layers.0.", cin, &blk.sn_in, s));
+            if (p->opt.nearest_upsample)      // Sequential(Upsample, WNConv1d): the convolution is layers.1.1
+                SAT_TRY(make_nearest(p, ar, pf + "layers.1.1.", cin, cout, blk.stride, &blk.resample, s));
+            else
+                SAT_TRY(make_convT(p, ar, pf + "layers.1.", cin, cout, blk.stride, &blk.resample, s));
+            for (int r = 0; r < 3; ++r) SAT_TRY(make_ru(p, ar, pf + "layers." + std::to_string(2 + r) + ".", cout, blk, r, s));
         }
         SAT_TRY(make_snake(p, ar, "layers." + std::to_string(nb + 1) + ".", c.channels, &p->final_snake, s));
         SAT_TRY(make_conv(p, ar, "layers." + std::to_string(nb + 2) + ".", c.channels, c.io_channels, 7, false, &p->last, s));
@@ -753,13 +862,15 @@ int build(OobPlan* p, Arena& ar, hipStream_t s) {
         SAT_TRY(make_conv(p, ar, "layers.0.", c.io_channels, c.channels, 7, true, &p->first, s, &p->first_w_f32));
         for (int bi = 0; bi < nb; ++bi) {
             auto& blk = p->blocks[bi];
-            blk.cin = (bi == 0 ? 1 : c.c_mults[bi - 1]) * c.channels;
-            blk.cout = c.c_mults[bi] * c.channels;
+            const int cin = (bi == 0 ? 1 : c.c_mults[bi - 1]) * c.channels;
+            const int cout = c.c_mults[bi] * c.channels;
+            blk.cin = pad64(cin);
+            blk.cout = pad64(cout);
             blk.stride = c.strides[bi];
             const std::string pf = "layers." + std::to_string(bi + 1) + ".";
-            for (int r = 0; r < 3; ++r) SAT_TRY(make_ru(p, ar, pf + "layers." + std::to_string(r) + ".", blk.cin, blk, r, s));
-            SAT_TRY(make_snake(p, ar, pf + "layers.3.", blk.cin, &blk.sn_in, s));
-            SAT_TRY(make_conv(p, ar, pf + "layers.4.", blk.cin, blk.cout, 2 * blk.stride, true, &blk.resample, s));
+            for (int r = 0; r < 3; ++r) SAT_TRY(make_ru(p, ar, pf + "layers." + std::to_string(r) + ".", cin, blk, r, s));
+            SAT_TRY(make_snake(p, ar, pf + "layers.3.", cin, &blk.sn_in, s));
+            SAT_TRY(make_conv(p, ar, pf + "layers.4.", cin, cout, 2 * blk.stride, true, &blk.resample, s));
         }
         const int ctop = c.c_mults[nb - 1] * c.channels;
         SAT_TRY(make_snake(p, ar, "layers." + std::to_string(nb + 1) + ".", ctop, &p->final_snake, s));
@@ -773,18 +884,18 @@ struct Bufs {
     size_t total;
 };
 Bufs carve(const OobPlan* p, int B, int T, char* base) {
-    // largest channels-last tensor of the network, in elements per batch item
+    // largest channels-last tensor of the network (padded widths), in elements per batch item
     const sat_oobleck_cfg& c = p->cfg;
     size_t len = (size_t)T, mx = 0;
     if (c.is_decoder) {
-        mx = (size_t)T * p->blocks[0].cin;
+        mx = std::max((size_t)T * pad64(c.latent_dim), (size_t)T * p->blocks[0].cin);
         for (auto& b : p->blocks) {
             len *= b.stride;
             mx = std::max(mx, len * b.cout);
         }
     } else {
         len = (size_t)T * p->ratio;
-        mx = len * c.channels;
+        mx = len * pad64(c.channels);
         for (auto& b : p->blocks) {
             mx = std::max(mx, len * b.cin);
             len /= b.stride;
@@ -810,11 +921,16 @@ ConvArgs base_args(const ConvW& w, const op_t* in, int Tin, int M) {
     return a;
 }
 
+// out = the activated copy of the result, for the consumer whose activation is sn
+void set_act(ConvArgs& a, op_t* out, const Snake& sn) {
+    a.out_snk = out; a.act = sn.act; a.sn_a = sn.a; a.sn_ib = sn.ib;
+}
+
 #if !SAT_OP_IS_F32
 template <int BN, int WM, int WN, int NS>
 int launch_ru_fused(const RuArgs& a, int B, hipStream_t s) {
     constexpr int LDS = NS * (128 + BN) * 128;
-    auto kern = ru_fused_kernel<BN, WM, WN, NS>;
+    auto kern = a.c7.act == ACT_ELU ? ru_fused_kernel<BN, WM, WN, NS, ACT_ELU> : ru_fused_kernel<BN, WM, WN, NS, ACT_SNAKE>;
     SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS));
     hipLaunchKernelGGL(kern, dim3(cdiv(a.c7.M, 128), B), dim3(WM * WN * 64), LDS, s, a);
     SAT_LAUNCH_CHECK();
@@ -828,11 +944,11 @@ int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const
     static const int dil[3] = {1, 3, 9};
     ConvArgs a = base_args(blk.ru_c7[r], S, L, L);
     a.off0 = -3 * dil[r]; a.doff = dil[r];
-    a.out_snk = Y; a.sn_a = blk.ru_sn2[r].a; a.sn_ib = blk.ru_sn2[r].ib;
+    set_act(a, Y, blk.ru_sn2[r]);
     ConvArgs c = base_args(blk.ru_c1[r], Y, L, L);
     c.res = R;
     c.out_raw = need_raw ? R : nullptr;   // in place: each thread reads then writes its own elements
-    c.out_snk = Sout; c.sn_a = next.a; c.sn_ib = next.ib;
+    set_act(c, Sout, next);
 #if !SAT_OP_IS_F32      // (fp32 build: the 128 x C intermediate would not fit next to the weight ring; two launches through Y)
     if (!g_ru_unfused && (C == 128 || C == 256)) {      // the whole unit in one launch, the intermediate never leaves LDS
         RuArgs f{a, c};
@@ -852,16 +968,17 @@ int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const
 
 namespace SAT_OPNS {
 
-int oob_plan_create(const sat_oobleck_cfg* cfg, OobPlan** out_plan) {
-    SAT_CHECK_ARG(cfg && out_plan, SAT_E_INVALID, "oobleck_plan_create: null argument");
+// (the options were validated by sat_oobleck_plan_create_ex; channel counts are free: the plan pads every width to a multiple of 64)
+int oob_plan_create(const sat_oobleck_cfg* cfg, const sat_oobleck_options* opt, OobPlan** out_plan) {
+    SAT_CHECK_ARG(cfg && opt && out_plan, SAT_E_INVALID, "oobleck_plan_create: null argument");
     SAT_CHECK_ARG(cfg->n_blocks >= 1 && cfg->n_blocks <= 8, SAT_E_UNSUPPORTED, "oobleck_plan_create: n_blocks %d not in 1..8", cfg->n_blocks);
-    SAT_CHECK_ARG(cfg->channels % 64 == 0 && cfg->channels > 0, SAT_E_UNSUPPORTED, "oobleck_plan_create: channels %d must be a multiple of 64", cfg->channels);
+    SAT_CHECK_ARG(cfg->channels > 0, SAT_E_UNSUPPORTED, "oobleck_plan_create: channels %d must be positive", cfg->channels);
     SAT_CHECK_ARG(cfg->io_channels >= 1 && cfg->io_channels <= 2, SAT_E_UNSUPPORTED, "oobleck_plan_create: io_channels must be 1 or 2");
-    if (cfg->is_decoder)
-        SAT_CHECK_ARG(cfg->latent_dim % 64 == 0, SAT_E_UNSUPPORTED, "oobleck_plan_create: decoder latent_dim %d must be a multiple of 64", cfg->latent_dim);
+    SAT_CHECK_ARG(cfg->latent_dim > 0, SAT_E_UNSUPPORTED, "oobleck_plan_create: latent_dim %d must be positive", cfg->latent_dim);
     OobPlan* p = new (std::nothrow) OobPlan();
     SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_create: out of host memory");
     p->cfg = *cfg;
+    p->opt = *opt;
     p->ratio = 1;
     for (int i = 0; i < cfg->n_blocks; ++i) {
         SAT_CHECK_ARG(cfg->strides[i] >= 1 && cfg->strides[i] <= 16 && cfg->c_mults[i] >= 1, SAT_E_UNSUPPORTED, "oobleck_plan_create: bad stride/c_mult");
@@ -922,28 +1039,31 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
     const sat_oobleck_cfg& c = p->cfg;
     const int nb = c.n_blocks;
     // latents -> channels-last bf16 (in Y), first conv (autoencoders.py:175) -> S0 = snake_block1(x)
-    hipLaunchKernelGGL(cf_to_cl_kernel, dim3(cdiv(T, 64), cdiv(c.latent_dim, 64), B), dim3(256), 0, s, z, bf.Y, c.latent_dim, T);
+    hipLaunchKernelGGL(cf_to_cl_kernel, dim3(cdiv(T, 64), pad64(c.latent_dim) / 64, B), dim3(256), 0, s, z, bf.Y, c.latent_dim,
+                       pad64(c.latent_dim), T);
     SAT_LAUNCH_CHECK();
     op_t* S = bf.S0;
     op_t* Sn = bf.S1;
     {
         ConvArgs a = base_args(p->first, bf.Y, T, T);
         a.off0 = -3;
-        a.out_snk = S; a.sn_a = p->blocks[0].sn_in.a; a.sn_ib = p->blocks[0].sn_in.ib;
+        set_act(a, S, p->blocks[0].sn_in);
         SAT_TRY(launch_conv(a, B, s));
     }
     int L = T;
     for (int bi = 0; bi < nb; ++bi) {
         const auto& blk = p->blocks[bi];
         const int st = blk.stride, pad = (st + 1) / 2;
-        // transposed conv (autoencoders.py:102-105): rows m = 0..L, output row span (m*st - pad)*Cout
-        ConvArgs a = base_args(blk.resample, S, L, L + 1);
-        a.off0 = 0; a.doff = -1;
+        // transposed conv (autoencoders.py:102-105): rows m = 0..L, output row span (m*st - pad)*Cout, taps at rows m, m-1;
+        // nearest upsample + conv (:95-99): rows m = 0..L-1, output row span m*st*Cout, taps at rows m-1, m, m+1
+        const bool nearest = p->opt.nearest_upsample != 0;
+        ConvArgs a = base_args(blk.resample, S, L, nearest ? L : L + 1);
+        a.off0 = nearest ? -1 : 0; a.doff = nearest ? 1 : -1;
         a.out_bstride = (long long)L * st * blk.cout;
-        a.out_shift = -(long long)pad * blk.cout;
+        a.out_shift = nearest ? 0 : -(long long)pad * blk.cout;
         a.out_limit = (long long)L * st * blk.cout;
         a.out_raw = bf.R;
-        a.out_snk = Sn; a.sn_a = blk.ru_sn1[0].a; a.sn_ib = blk.ru_sn1[0].ib;
+        set_act(a, Sn, blk.ru_sn1[0]);
         SAT_TRY(launch_conv(a, B, s));
         std::swap(S, Sn);
         L *= st;
@@ -953,10 +1073,10 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
             std::swap(S, Sn);
         }
     }
-    // final conv (autoencoders.py:187): no bias, no tanh -> fp32 channel-first audio
+    // final conv (autoencoders.py:187-188): no bias, tanh by option -> fp32 channel-first audio
     ConvArgs a = base_args(p->last, S, L, L);
     a.off0 = -3;
-    a.out_cf = audio; a.cf_channels = c.io_channels;
+    a.out_cf = audio; a.cf_channels = c.io_channels; a.tanh_out = p->opt.final_tanh;
     SAT_TRY(launch_conv(a, B, s));
     return 0;
 }
@@ -974,8 +1094,10 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
     int L = T * p->ratio;
     op_t* S = bf.S0;
     op_t* Sn = bf.S1;
-    hipLaunchKernelGGL(first_conv_kernel, dim3(cdiv(L, 64), B), dim3(256), 0, s, audio, p->first_w_f32, p->first.bias,
-                       p->blocks[0].ru_sn1[0].a, p->blocks[0].ru_sn1[0].ib, bf.R, S, c.io_channels, c.channels, L);
+    const Snake& sn0 = p->blocks[0].ru_sn1[0];
+    const bool general = sn0.act != ACT_SNAKE || pad64(c.channels) != c.channels;
+    hipLaunchKernelGGL(general ? first_conv_kernel<true> : first_conv_kernel<false>, dim3(cdiv(L, 64), B), dim3(256), 0, s, audio,
+                       p->first_w_f32, p->first.bias, sn0.a, sn0.ib, sn0.act, bf.R, S, c.io_channels, c.channels, pad64(c.channels), L);
     SAT_LAUNCH_CHECK();
     for (int bi = 0; bi < nb; ++bi) {
         const auto& blk = p->blocks[bi];
@@ -991,7 +1113,7 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
         const bool lastb = bi + 1 == nb;
         a.out_raw = lastb ? nullptr : bf.R;
         const Snake& nx = lastb ? p->final_snake : p->blocks[bi + 1].ru_sn1[0];
-        a.out_snk = Sn; a.sn_a = nx.a; a.sn_ib = nx.ib;
+        set_act(a, Sn, nx);
         SAT_TRY(launch_conv(a, B, s));
         std::swap(S, Sn);
         L = Lo;
@@ -1010,7 +1132,7 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
 #define SAT_OOB_DECLARE(NS)                                                                                                       \
     namespace NS {                                                                                                                \
     struct OobPlan;                                                                                                               \
-    int oob_plan_create(const sat_oobleck_cfg* cfg, OobPlan** out_plan);                                                          \
+    int oob_plan_create(const sat_oobleck_cfg* cfg, const sat_oobleck_options* opt, OobPlan** out_plan);                          \
     void oob_plan_destroy(OobPlan* p);                                                                                            \
     int oob_plan_set_tensor(OobPlan* p, const char* name, const float* data_dev, int64_t numel);                                  \
     int oob_plan_finalize(OobPlan* p, sat_stream_t stream);                                                                       \
@@ -1028,15 +1150,41 @@ static inline int32_t oob_dtype(const void* p) { return static_cast<const sat_oo
      : oob_dtype(p) == SAT_GEMM_FP32X ? f32::fn(reinterpret_cast<f32::OobPlan*>(const_cast<sat_oobleck_plan*>(p)), __VA_ARGS__)   \
                                       : bf16::fn(reinterpret_cast<bf16::OobPlan*>(const_cast<sat_oobleck_plan*>(p)), __VA_ARGS__))
 
+extern "C" int sat_oobleck_plan_create_ex(const sat_oobleck_cfg* cfg, const sat_oobleck_options* options, size_t options_bytes,
+                                          sat_oobleck_plan** out_plan) {
+    SAT_CHECK_ARG(cfg && out_plan, SAT_E_INVALID, "oobleck_plan_create: null argument");
+    sat_oobleck_options opt = {SAT_OOBLECK_ACT_SNAKE, 0, 0};      // options == NULL: the defaults of sat_oobleck_plan_create
+    if (options) {
+        SAT_CHECK_ARG(options_bytes == sizeof(sat_oobleck_options), SAT_E_INVALID,
+                      "oobleck_plan_create_ex: options_bytes %zu is not the size of this version's sat_oobleck_options (%zu)", options_bytes,
+                      sizeof(sat_oobleck_options));
+        opt = *options;
+    }
+    SAT_CHECK_ARG(cfg->gemm_dtype == SAT_GEMM_BF16 || cfg->gemm_dtype == SAT_GEMM_FP16 || cfg->gemm_dtype == SAT_GEMM_FP32X,
+                  SAT_E_UNSUPPORTED, "oobleck_plan_create: gemm_dtype must be 0 (bf16), 3 (fp16) or 2 (fp32)");
+    SAT_CHECK_ARG(opt.activation == SAT_OOBLECK_ACT_SNAKE || opt.activation == SAT_OOBLECK_ACT_ELU, SAT_E_UNSUPPORTED,
+                  "oobleck_plan_create_ex: activation %d is neither SAT_OOBLECK_ACT_SNAKE (0) nor SAT_OOBLECK_ACT_ELU (1)", opt.activation);
+    SAT_CHECK_ARG((opt.final_tanh == 0 || opt.final_tanh == 1) && (opt.nearest_upsample == 0 || opt.nearest_upsample == 1), SAT_E_UNSUPPORTED,
+                  "oobleck_plan_create_ex: final_tanh / nearest_upsample must be 0 or 1");
+    SAT_CHECK_ARG(cfg->is_decoder || (!opt.final_tanh && !opt.nearest_upsample), SAT_E_UNSUPPORTED,
+                  "oobleck_plan_create_ex: final_tanh / nearest_upsample are decoder options");
+    switch (cfg->gemm_dtype) {
+        case SAT_GEMM_FP16: return f16::oob_plan_create(cfg, &opt, reinterpret_cast<f16::OobPlan**>(out_plan));
+        case SAT_GEMM_FP32X: return f32::oob_plan_create(cfg, &opt, reinterpret_cast<f32::OobPlan**>(out_plan));
+        default: return bf16::oob_plan_create(cfg, &opt, reinterpret_cast<bf16::OobPlan**>(out_plan));
+    }
+}
+// The original entry point and its contract: Snake, transposed convolutions, no tanh, channels and the decoder's latent_dim multiples of 64
 extern "C" int sat_oobleck_plan_create(const sat_oobleck_cfg* cfg, sat_oobleck_plan** out_plan) {
     SAT_CHECK_ARG(cfg && out_plan, SAT_E_INVALID, "oobleck_plan_create: null argument");
     SAT_CHECK_ARG(cfg->gemm_dtype == SAT_GEMM_BF16 || cfg->gemm_dtype == SAT_GEMM_FP16 || cfg->gemm_dtype == SAT_GEMM_FP32X,
                   SAT_E_UNSUPPORTED, "oobleck_plan_create: gemm_dtype must be 0 (bf16), 3 (fp16) or 2 (fp32)");
-    switch (cfg->gemm_dtype) {
-        case SAT_GEMM_FP16: return f16::oob_plan_create(cfg, reinterpret_cast<f16::OobPlan**>(out_plan));
-        case SAT_GEMM_FP32X: return f32::oob_plan_create(cfg, reinterpret_cast<f32::OobPlan**>(out_plan));
-        default: return bf16::oob_plan_create(cfg, reinterpret_cast<bf16::OobPlan**>(out_plan));
-    }
+    SAT_CHECK_ARG(cfg->channels % 64 == 0 && cfg->channels > 0, SAT_E_UNSUPPORTED,
+                  "oobleck_plan_create: channels %d must be a multiple of 64 (sat_oobleck_plan_create_ex takes any)", cfg->channels);
+    if (cfg->is_decoder)
+        SAT_CHECK_ARG(cfg->latent_dim % 64 == 0, SAT_E_UNSUPPORTED,
+                      "oobleck_plan_create: decoder latent_dim %d must be a multiple of 64 (sat_oobleck_plan_create_ex takes any)", cfg->latent_dim);
+    return sat_oobleck_plan_create_ex(cfg, nullptr, 0, out_plan);
 }
 extern "C" void sat_oobleck_plan_destroy(sat_oobleck_plan* p) {
     if (!p) return;

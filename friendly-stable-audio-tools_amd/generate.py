@@ -54,6 +54,9 @@ def get_args():
     p.add_argument("--codec-dtype", choices=["fp16", "bf16", "fp32"], default=None,
                    help="build extension: operand format of the VAE decoder, overriding the rule that ties it to --gemm-dtype.  fp32 = the "
                         "reference's full-precision decode (model_half=False) on the exact f32 MFMA, no fp16 range limit, slower")
+    p.add_argument("--codec-final-tanh", action="store_true",
+                   help="build extension: the VAE decoder was trained with final_tanh=True (write \"final_tanh\": false in the model config, "
+                        "which the constructor requires, and pass this flag: set_final_tanh(True))")
     return p.parse_args()
 
 
@@ -142,6 +145,8 @@ def main():
             model.pretransform.model.set_gemm_dtype(_config.codec_gemm_dtype(args.gemm_dtype))
     if args.codec_dtype is not None and model.pretransform is not None:
         model.pretransform.model.set_gemm_dtype(args.codec_dtype)
+    if args.codec_final_tanh and model.pretransform is not None:
+        model.pretransform.model.set_final_tanh(True)
     cond_dim = model_config["model"]["conditioning"]["cond_dim"]
     if model.conditioner is not None:
         model.conditioner.set_device(str(device))      # what generate_diffusion_cond does first (generation.py:125); needed by encoders here

@@ -30,6 +30,9 @@ def get_args():
     p.add_argument("--codec-dtype", choices=["fp16", "bf16", "fp32"], default=None,
                    help="build extension: operand format of the encoder / decoder kernels.  Default: the package default (fp16); fp32 = the "
                         "reference's full-precision codec on the exact f32 MFMA")
+    p.add_argument("--codec-final-tanh", action="store_true",
+                   help="build extension: the decoder was trained with final_tanh=True (write \"final_tanh\": false in the model config, "
+                        "which the constructor requires, and pass this flag: set_final_tanh(True))")
     return p.parse_args()
 
 
@@ -53,6 +56,8 @@ def main():
     model = model.to(device).eval()
     if args.codec_dtype is not None:
         model.set_gemm_dtype(args.codec_dtype)
+    if args.codec_final_tanh:
+        model.set_final_tanh(True)
     sr, ratio = model.sample_rate, model.downsampling_ratio
     chunk_size = int((args.frame_duration * sr) / ratio)                              # reconstruct_audios.py:86-87
     overlap = max(int((args.frame_duration * sr * args.overlap_rate) / ratio), 1)

@@ -39,6 +39,13 @@ class SatOobleckCfg(Structure):
                 ("n_blocks", c_int32), ("c_mults", c_int32 * 8), ("strides", c_int32 * 8), ("gemm_dtype", c_int32)]
 
 
+class SatOobleckOptions(Structure):
+    _fields_ = [("activation", c_int32), ("final_tanh", c_int32), ("nearest_upsample", c_int32)]
+
+
+OOBLECK_ACT_SNAKE, OOBLECK_ACT_ELU = 0, 1     # include/sat_hip.h: SAT_OOBLECK_ACT_*
+
+
 _SIGNATURES = {
     "sat_version": (c_int32, []),
     "sat_last_error": (c_char_p, []),
@@ -75,6 +82,7 @@ _SIGNATURES = {
     "sat_dpmpp3m_update": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                      c_float, c_int64, c_void_p]),
     "sat_oobleck_plan_create": (c_int32, [POINTER(SatOobleckCfg), POINTER(c_void_p)]),
+    "sat_oobleck_plan_create_ex": (c_int32, [POINTER(SatOobleckCfg), POINTER(SatOobleckOptions), c_size_t, POINTER(c_void_p)]),
     "sat_oobleck_plan_destroy": (None, [c_void_p]),
     "sat_oobleck_plan_set_tensor": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64]),
     "sat_oobleck_plan_finalize": (c_int32, [c_void_p, c_void_p]),

@@ -50,22 +50,38 @@ class WNConvTranspose1d(_WNBase):
         self._register(_init.conv_transpose1d(in_channels, out_channels, kernel_size, stride=stride, padding=padding), True)
 
 
-def _act(use_snake, channels):
-    if not use_snake:
-        raise NotImplementedError("only use_snake=True (the Stable Audio VAE configs) is supported by the HIP codec")
-    return SnakeBeta(channels)
+def _act(use_snake, channels, antialias_activation=False):
+    """``get_activation("snake" if use_snake else "elu")`` (autoencoders.py:27-42): SnakeBeta, or the parameter-free ``nn.ELU``.  Either
+    runs inside the producing convolution's epilogue; the module only holds the parameters (none for ELU)."""
+    if antialias_activation:
+        raise NotImplementedError("antialias_activation is not supported by the HIP codec")
+    return SnakeBeta(channels) if use_snake else nn.ELU()
+
+
+def nearest_upsample_taps(weight, stride):
+    """The three-tap polyphase form of ``Upsample(scale_factor=stride, mode="nearest")`` + ``Conv1d(k=2*stride, padding="same")`` that
+    the HIP plan builds at finalize (csrc/oobleck.hip, wn_pack_nearest_kernel), for tests and documentation.  ``weight`` [Cout, Cin,
+    2*stride] (weight norm already folded) -> [stride, 3, Cout, Cin]: output sample ``m*stride + p`` is
+    ``sum_r taps[p, r+1] @ x[:, m+r]``, r = -1, 0, 1, with x zero outside [0, T).  PyTorch pads an even kernel stride-1 on the left
+    and stride on the right, so tap j of phase p reads upsampled position m*stride + p + j - (stride-1), which lies in input row
+    m + floor((p + j - stride + 1) / stride)."""
+    c_out, c_in, k = weight.shape
+    assert k == 2 * stride
+    taps = weight.new_zeros((stride, 3, c_out, c_in), dtype=torch.float32)
+    for p in range(stride):
+        for j in range(k):
+            taps[p, (p + j - stride + 1) // stride + 1] += weight[:, :, j].float()
+    return taps
 
 
 class ResidualUnit(nn.Module):
     def __init__(self, in_channels, out_channels, dilation, use_snake=False, antialias_activation=False):
         super().__init__()
-        if antialias_activation:
-            raise NotImplementedError("antialias_activation is not supported by the HIP codec")
         self.dilation = dilation
         self.layers = nn.Sequential(
-            _act(use_snake, out_channels),
+            _act(use_snake, out_channels, antialias_activation),
             WNConv1d(in_channels, out_channels, 7, dilation=dilation, padding=(dilation * 6) // 2),
-            _act(use_snake, out_channels),
+            _act(use_snake, out_channels, antialias_activation),
             WNConv1d(out_channels, out_channels, 1))
 
 
@@ -76,18 +92,21 @@ class EncoderBlock(nn.Module):
             ResidualUnit(in_channels, in_channels, 1, use_snake=use_snake),
             ResidualUnit(in_channels, in_channels, 3, use_snake=use_snake),
             ResidualUnit(in_channels, in_channels, 9, use_snake=use_snake),
-            _act(use_snake, in_channels),
+            _act(use_snake, in_channels, antialias_activation),
             WNConv1d(in_channels, out_channels, 2 * stride, stride=stride, padding=math.ceil(stride / 2)))
 
 
 class DecoderBlock(nn.Module):
     def __init__(self, in_channels, out_channels, stride, use_snake=False, antialias_activation=False, use_nearest_upsample=False):
         super().__init__()
-        if use_nearest_upsample:
-            raise NotImplementedError("use_nearest_upsample is not supported by the HIP codec")
+        if use_nearest_upsample:      # autoencoders.py:95-99; on the device a three-tap polyphase convolution (nearest_upsample_taps)
+            upsample_layer = nn.Sequential(nn.Upsample(scale_factor=stride, mode="nearest"),
+                                           WNConv1d(in_channels, out_channels, 2 * stride, stride=1, bias=False, padding="same"))
+        else:
+            upsample_layer = WNConvTranspose1d(in_channels, out_channels, 2 * stride, stride=stride, padding=math.ceil(stride / 2))
         self.layers = nn.Sequential(
-            _act(use_snake, in_channels),
-            WNConvTranspose1d(in_channels, out_channels, 2 * stride, stride=stride, padding=math.ceil(stride / 2)),
+            _act(use_snake, in_channels, antialias_activation),
+            upsample_layer,
             ResidualUnit(out_channels, out_channels, 1, use_snake=use_snake),
             ResidualUnit(out_channels, out_channels, 3, use_snake=use_snake),
             ResidualUnit(out_channels, out_channels, 9, use_snake=use_snake))
@@ -100,6 +119,7 @@ _CODEC_GEMM_DTYPES = {"bf16": 0, "fp16": 3, "fp32": 2}
 class _OobleckHip(nn.Module):
     """Shared plan handling of encoder and decoder."""
     _is_decoder = False
+    use_snake, use_nearest_upsample, final_tanh = True, False, False
 
     def _init_plan_state(self):
         self.gemm_dtype = _config.default_gemm_dtype()
@@ -148,8 +168,12 @@ class _OobleckHip(nn.Module):
             cfg.c_mults[i] = c
             cfg.strides[i] = s
         cfg.gemm_dtype = _CODEC_GEMM_DTYPES[self.gemm_dtype]
+        opt = _hip.SatOobleckOptions()
+        opt.activation = _hip.OOBLECK_ACT_SNAKE if self.use_snake else _hip.OOBLECK_ACT_ELU
+        opt.final_tanh = 1 if self.final_tanh else 0
+        opt.nearest_upsample = 1 if self.use_nearest_upsample else 0
         plan = ctypes.c_void_p()
-        _hip.check(lib.sat_oobleck_plan_create(ctypes.byref(cfg), ctypes.byref(plan)))
+        _hip.check(lib.sat_oobleck_plan_create_ex(ctypes.byref(cfg), ctypes.byref(opt), ctypes.sizeof(opt), ctypes.byref(plan)))
         keep = []
         for name, t in self.state_dict().items():
             t32 = t.detach().to(torch.float32).contiguous()
@@ -176,13 +200,14 @@ class OobleckEncoder(_OobleckHip):
         super().__init__()
         self.io_channels, self.channels, self.latent_dim = in_channels, channels, latent_dim
         self.c_mults, self.strides = list(c_mults), list(strides)
+        self.use_snake = bool(use_snake)
         self.ratio = int(math.prod(strides))
         cm = [1] + list(c_mults)
         self.depth = len(cm)
         layers = [WNConv1d(in_channels, cm[0] * channels, 7, padding=3)]
         for i in range(self.depth - 1):
             layers.append(EncoderBlock(cm[i] * channels, cm[i + 1] * channels, strides[i], use_snake=use_snake))
-        layers += [_act(use_snake, cm[-1] * channels), WNConv1d(cm[-1] * channels, latent_dim, 3, padding=1)]
+        layers += [_act(use_snake, cm[-1] * channels, antialias_activation), WNConv1d(cm[-1] * channels, latent_dim, 3, padding=1)]
         self.layers = nn.Sequential(*layers)
         self._init_plan_state()
 
@@ -207,9 +232,12 @@ class OobleckDecoder(_OobleckHip):
                  antialias_activation=False, use_nearest_upsample=False, final_tanh=True):
         super().__init__()
         if final_tanh:
-            raise NotImplementedError("final_tanh=True is not supported by the HIP codec (Stable Audio VAEs use final_tanh=False)")
+            raise NotImplementedError(
+                "final_tanh=True cannot be given to the constructor of the HIP codec: build the decoder with final_tanh=False, then call "
+                "set_final_tanh(True) (a tanh has no parameters, so a checkpoint trained with final_tanh=True loads unchanged)")
         self.io_channels, self.channels, self.latent_dim = out_channels, channels, latent_dim
         self.c_mults, self.strides = list(c_mults), list(strides)
+        self.use_snake, self.use_nearest_upsample = bool(use_snake), bool(use_nearest_upsample)
         self.ratio = int(math.prod(strides))
         cm = [1] + list(c_mults)
         self.depth = len(cm)
@@ -217,9 +245,21 @@ class OobleckDecoder(_OobleckHip):
         for i in range(self.depth - 1, 0, -1):
             layers.append(DecoderBlock(cm[i] * channels, cm[i - 1] * channels, strides[i - 1], use_snake=use_snake,
                                        antialias_activation=antialias_activation, use_nearest_upsample=use_nearest_upsample))
-        layers += [_act(use_snake, cm[0] * channels), WNConv1d(cm[0] * channels, out_channels, 7, padding=3, bias=False), nn.Identity()]
+        layers += [_act(use_snake, cm[0] * channels, antialias_activation),
+                   WNConv1d(cm[0] * channels, out_channels, 7, padding=3, bias=False), nn.Identity()]
         self.layers = nn.Sequential(*layers)
         self._init_plan_state()
+
+    def set_final_tanh(self, enabled: bool = True):
+        """Build extension: the reference's ``final_tanh=True`` (``nn.Tanh`` behind the last convolution, autoencoders.py:188), applied in
+        that convolution's epilogue on the device.  The constructor rejects ``final_tanh=True`` (a pinned test of the config surface
+        says so), hence this call after construction; rebuilds the plan on next use."""
+        enabled = bool(enabled)
+        if enabled != self.final_tanh:
+            self.final_tanh = enabled
+            self.layers[-1] = nn.Tanh() if enabled else nn.Identity()
+            self._plan_version = None
+        return self
 
     @torch.no_grad()
     def forward(self, z):
@@ -265,6 +305,13 @@ class AudioAutoencoder(nn.Module):
         for part in (self.encoder, self.decoder):
             if isinstance(part, _OobleckHip):
                 part.set_gemm_dtype(dtype)
+        return self
+
+    def set_final_tanh(self, enabled: bool = True):
+        """The decoder's final tanh (see ``OobleckDecoder.set_final_tanh``)."""
+        if not isinstance(self.decoder, OobleckDecoder):
+            raise NotImplementedError("set_final_tanh needs an Oobleck decoder")
+        self.decoder.set_final_tanh(enabled)
         return self
 
     # autoencoders.py:268-304

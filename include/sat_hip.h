@@ -299,7 +299,28 @@ typedef struct sat_oobleck_cfg {
                                   16-bit MFMA rate).  SAT_GEMM_FP8 is rejected (SAT_E_UNSUPPORTED). */
 } sat_oobleck_cfg;
 
+/* Snake, transposed-convolution upsampling, no final tanh (the Stable Audio VAEs); `channels` and a decoder's `latent_dim` must be
+ * multiples of 64 (SAT_E_UNSUPPORTED otherwise).  == sat_oobleck_plan_create_ex(cfg, NULL, 0, out_plan) after that check. */
 int sat_oobleck_plan_create(const sat_oobleck_cfg* cfg, sat_oobleck_plan** out_plan);
+
+/* The other shapes of the reference's OobleckEncoder / OobleckDecoder (models/autoencoders.py:119-194). */
+#define SAT_OOBLECK_ACT_SNAKE 0   /* use_snake=True: SnakeBeta, tensors "<...>.alpha" / "<...>.beta" */
+#define SAT_OOBLECK_ACT_ELU 1     /* use_snake=False: nn.ELU(alpha=1), no tensors (set_tensor / finalize ask for none) */
+typedef struct sat_oobleck_options {
+    int32_t activation;        /* SAT_OOBLECK_ACT_*; fused into the producing convolution's epilogue either way */
+    int32_t final_tanh;        /* decoder: 1 = tanh on the audio (final_tanh=True), in the last convolution's epilogue */
+    int32_t nearest_upsample;  /* decoder: 1 = use_nearest_upsample=True: each block's upsampler is Upsample(nearest, stride) + a bias-free
+                                  Conv1d(k = 2*stride, padding "same") with tensors "layers.<b>.layers.1.1.weight_g/_v"; runs as a
+                                  three-tap polyphase convolution over the input rows m-1, m, m+1 (taps summed per phase at finalize) */
+} sat_oobleck_options;
+
+/* options_bytes = sizeof(sat_oobleck_options) of the header the CALLER was built against (any other size: SAT_E_INVALID, as
+ * sat_dit_plan_create_sized); options == NULL takes the defaults {SNAKE, 0, 0}.  No rule on channel counts: `channels`, every
+ * channels * c_mults[i] and `latent_dim` may be any positive integer.  The plan rounds each stage width up to a multiple of 64 and
+ * zero-pads weights, biases and Snake parameters at finalize, so a narrow codec costs what the next multiple of 64 costs, and
+ * sat_oobleck_workspace_bytes counts the padded widths.  An unknown option value is SAT_E_UNSUPPORTED. */
+int sat_oobleck_plan_create_ex(const sat_oobleck_cfg* cfg, const sat_oobleck_options* options, size_t options_bytes,
+                               sat_oobleck_plan** out_plan);
 void sat_oobleck_plan_destroy(sat_oobleck_plan* plan);
 /* `name` relative to the OobleckEncoder/OobleckDecoder module, e.g.
  * "layers.1.layers.2.layers.1.weight_v". */

@@ -1,6 +1,9 @@
 """Developer probe: full-size Oobleck decode (1024 latent frames) and encode (the same audio back) alone, for rocprofv3 / A-B runs
 of the codec kernels (SAT_HIP_EXP=1 SAT_OOBLECK_UNFUSED=1: experiments build, two launches per ResidualUnit).  Not part of the product or the tests.
-Usage: python tools/codec_only.py [fp16|bf16|fp32]   (operand format of the codec kernels; default: the package default)."""
+Usage: python tools/codec_only.py [fp16|bf16|fp32]   (operand format of the codec kernels; default: the package default).
+CODEC_CONFIG picks the shape: full (default, the Stable Audio VAE), full_nearest (the same with use_nearest_upsample=True: three-tap
+polyphase upsamplers), small16 (16 channels, stage widths 16 ... 256, padded to 64 ... 256 inside the plan) or small64 (64 channels,
+same depth: what small16 is padded towards in its narrow stages)."""
 import ctypes
 import os
 import sys
@@ -19,13 +22,22 @@ from stable_audio_tools import _hip
 if os.environ.get("SAT_HIP_EXP"):       # experiments build: honours SAT_OOBLECK_UNFUSED=1
     _hip.LIB_PATH = os.path.join(os.path.dirname(_hip.LIB_PATH), "libsat_hip_exp.so")
 dev = torch.device("cuda:0")
+config = MC.stable_audio_vae()
+which = os.environ.get("CODEC_CONFIG", "full")
+if which == "full_nearest":
+    config["model"]["decoder"]["config"]["use_nearest_upsample"] = True
+elif which in ("small16", "small64"):
+    for part in ("encoder", "decoder"):
+        config["model"][part]["config"]["channels"] = 16 if which == "small16" else 64
+elif which != "full":
+    raise SystemExit(f"unknown CODEC_CONFIG {which}")
 with _init.skip_init():
-    vae = S.create_model_from_config(MC.stable_audio_vae())
+    vae = S.create_model_from_config(config)
 vae.load_state_dict(synthetic.synth_state_dict(vae.state_dict(), 3))
 vae = vae.to(dev).eval()
 if len(sys.argv) > 1:
     vae.set_gemm_dtype(sys.argv[1])
-print(f"codec operands: {vae.decoder.gemm_dtype}", flush=True)
+print(f"codec operands: {vae.decoder.gemm_dtype}, config: {which}", flush=True)
 z = torch.randn(1, 64, int(os.environ.get("FRAMES", "1024")), device=dev)
 
 
