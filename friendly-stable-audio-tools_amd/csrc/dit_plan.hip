@@ -1003,8 +1003,8 @@ extern "C" int sat_gemm_f32_workspace_bytes(int32_t m, int32_t n, int32_t k, int
     SAT_CHECK_ARG(out_bytes && m > 0 && n > 0 && k > 0, SAT_E_INVALID, "gemm_f32_workspace_bytes: bad argument");
     const int cus = sat_device_cus();
     SAT_CHECK_ARG(cus > 0, SAT_E_INVALID, "gemm_f32_workspace_bytes: no device");
-    // forced K-split (variant bit 16, tests / measurements): one slab per workgroup; otherwise what the automatic schedule would use
-    *out_bytes = (variant & 0x10000) ? (size_t)cus * 65536 * sizeof(float) : sat_gemm_ph8_slab_bytes(EPI_F32, m, n, k);
+    // forced K-split (tests / measurements): one slab per workgroup; otherwise what the automatic schedule would use
+    *out_bytes = sat_variant_has(variant, SAT_VARIANT_SPLIT_FORCE) ? (size_t)cus * 65536 * sizeof(float) : sat_gemm_ph8_slab_bytes(EPI_F32, m, n, k);
     return 0;
 }
 
@@ -1012,14 +1012,14 @@ static int gemm_swiglu_bf16_impl(int f16, const void* a, const float* w_f32, con
                                     void* h, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
     SAT_CHECK_ARG(w_f32 && wpack && bpack && h, SAT_E_INVALID, "gemm_swiglu: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (!(variant & 0x4000)) {     // bit 14: wpack / bpack already hold the packed operands of a previous call (benchmarks)
+    if (!sat_variant_has(variant, SAT_VARIANT_PACKED)) {     // wpack / bpack already hold the packed operands of a previous call (benchmarks)
         SAT_TRY(sat_launch_pack_rows_bf16(w_f32, (op_t*)wpack, n, k, 1, s, f16));
         if (bias_f32) SAT_TRY(sat_launch_pack_bias(bias_f32, bpack, n, 1, s));
     }
     GemmArgs g{};
     g.f16 = f16;
     g.A = (const op_t*)a; g.W = (const op_t*)wpack; g.bias = bias_f32 ? bpack : nullptr; g.M = m; g.N = n; g.K = k;
-    g.H = (op_t*)h; g.variant = variant;
+    g.H = (op_t*)h; g.variant = variant & ~SAT_VARIANT_PACKED;
     return sat_launch_gemm(EPI_SWIGLU, g, s);
 }
 extern "C" int sat_gemm_swiglu_bf16(const void* a, const float* w_f32, const float* bias_f32, void* wpack, float* bpack,
@@ -1148,11 +1148,11 @@ static int gemm_swiglu_ln_bf16_impl(int f16, const void* xb, const float* ln_par
                                        int32_t variant, sat_stream_t stream) {
     SAT_CHECK_ARG(xb && ln_part && w_f32 && gamma && beta && wpack && c12 && h, SAT_E_INVALID, "gemm_swiglu_ln: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (!(variant & 0x4000))       // bit 14: wpack / c12 already hold the packed operands of a previous call (benchmarks)
+    if (!sat_variant_has(variant, SAT_VARIANT_PACKED))       // wpack / c12 already hold the packed operands of a previous call (benchmarks)
         SAT_TRY(sat_launch_pack_rows_ln(w_f32, gamma, beta, bias_f32, (op_t*)wpack, c12, c12 + n, n, k, 1, s, f16));
     GemmArgs g{};
     g.f16 = f16;
-    g.A = (const op_t*)xb; g.W = (const op_t*)wpack; g.M = m; g.N = n; g.K = k; g.H = (op_t*)h; g.variant = variant & ~0x4000;
+    g.A = (const op_t*)xb; g.W = (const op_t*)wpack; g.M = m; g.N = n; g.K = k; g.H = (op_t*)h; g.variant = variant & ~SAT_VARIANT_PACKED;
     g.ln_part = ln_part; g.ln_c1 = c12; g.ln_c2 = c12 + n; g.ln_eps = 1e-5f;
     return sat_launch_gemm(EPI_SWIGLU, g, s);
 }
@@ -1178,7 +1178,7 @@ static int qkv_rope_ln_bf16_impl(int f16, const void* xb, const float* ln_part, 
     const size_t bytes = (size_t)b * H * s_pad * 64 * 2;
     float* cs = rope_scratch;
     float* sn = rope_scratch + (size_t)s_len * 16;
-    if (!(variant & 0x4000)) {     // bit 14: pads, tables and packed operands are those of a previous call (benchmarks)
+    if (!sat_variant_has(variant, SAT_VARIANT_PACKED)) {     // pads, tables and packed operands are those of a previous call (benchmarks)
         SAT_HIP(hipMemsetAsync(q, 0, bytes, s));
         SAT_HIP(hipMemsetAsync(k, 0, bytes, s));
         SAT_HIP(hipMemsetAsync(vt, 0, bytes, s));
@@ -1187,7 +1187,7 @@ static int qkv_rope_ln_bf16_impl(int f16, const void* xb, const float* ln_part, 
     }
     GemmArgs g{};
     g.f16 = f16;
-    g.A = (const op_t*)xb; g.W = (const op_t*)wpack; g.M = b * s_len; g.N = 3 * d; g.K = d; g.variant = variant & ~0x4000;
+    g.A = (const op_t*)xb; g.W = (const op_t*)wpack; g.M = b * s_len; g.N = 3 * d; g.K = d; g.variant = variant & ~SAT_VARIANT_PACKED;
     g.heads.out[0] = (op_t*)q; g.heads.out[1] = (op_t*)k; g.heads.out[2] = (op_t*)vt;
     g.heads.kind[0] = 2; g.heads.kind[1] = 2 | 4; g.heads.kind[2] = 1 | 4;
     g.heads.parts = 3; g.heads.heads = H; g.heads.S = s_len; g.heads.Spad = s_pad;
@@ -1219,9 +1219,9 @@ extern "C" int sat_gemm_fp8_f32(const void* a8, const float* a_scale, const void
                                 float* c, int32_t m, int32_t n, int32_t k, int32_t accumulate, int32_t variant, sat_stream_t stream) {
     SAT_CHECK_ARG(a8 && w8 && a_scale && w_scale && c, SAT_E_INVALID, "gemm_fp8: null pointer");
     GemmArgs g{};
-    g.A = (const op_t*)a8; g.W = (const op_t*)w8; g.bias = bias; g.M = m; g.N = n; g.K = k; g.variant = variant & ~256;
+    g.A = (const op_t*)a8; g.W = (const op_t*)w8; g.bias = bias; g.M = m; g.N = n; g.K = k; g.variant = variant & ~SAT_VARIANT_FP8_PLAIN;
     g.C = c; g.ldc = n; g.accumulate = accumulate; g.a_scale = a_scale; g.w_scale = w_scale;
-    g.fp8 = (variant & 256) ? 1 : 2;      // bit 8 of variant: the plain 32x32x16 fp8 MFMA instead of the 2x-rate scaled 32x32x64
+    g.fp8 = sat_variant_has(variant, SAT_VARIANT_FP8_PLAIN) ? 1 : 2;      // the plain 32x32x16 fp8 MFMA instead of the 2x-rate scaled 32x32x64
     return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
 }
 
@@ -1234,7 +1234,7 @@ extern "C" int sat_gemm_mxfp8_f32(const void* a8, const void* a_scales, const vo
     SAT_CHECK_ARG(a8 && w8 && a_scales && w_scale && c, SAT_E_INVALID, "gemm_mxfp8: null pointer");
     SAT_CHECK_ARG(((uintptr_t)a_scales & 3) == 0, SAT_E_INVALID, "gemm_mxfp8: the scale array must be 4-byte aligned");
     GemmArgs g{};
-    g.A = (const op_t*)a8; g.W = (const op_t*)w8; g.bias = bias; g.M = m; g.N = n; g.K = k; g.variant = variant & 0xff;
+    g.A = (const op_t*)a8; g.W = (const op_t*)w8; g.bias = bias; g.M = m; g.N = n; g.K = k; g.variant = sat_variant_tile(variant);
     g.C = c; g.ldc = n; g.accumulate = accumulate; g.a_bscale = (const unsigned*)a_scales; g.w_scale = w_scale; g.fp8 = 3;
     return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
 }

@@ -877,7 +877,7 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     if constexpr (PRE_RESID) {
         // (exactly the condition under which the staged epilogue runs, see the end of the kernel)
 #ifdef SAT_GEMM_EXPERIMENTS
-        const bool staged = !(!MXA && !(g.variant & 0x1000) && (g.variant & 0x2000)) && !(g.variant & 0x8000);
+        const bool staged = !(!MXA && !(g.variant & SAT_VARIANT_EPI_UNSWAPPED) && (g.variant & SAT_VARIANT_EPI_F32_TR)) && !(g.variant & SAT_VARIANT_EPI_F32_DIRECT);
 #else
         const bool staged = true;
 #endif
@@ -1215,11 +1215,11 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     // The shipped build fixes the orientation at compile time wherever it can (ORI 0: un-swapped only -- fp32 output, MXFP8 A
     // operand; 1: transposed only -- SwiGLU; 2: per workgroup -- heads: q / k transposed, V^T un-swapped): one main loop instead of
     // two keeps the 128-VGPR kernels (16 waves, e4m3 fragments) out of scratch.  The experiments build keeps both behind variant
-    // bits 12 (force un-swapped), 13 (transposed fp32 epilogue) and 15 (direct dword fp32 epilogue) for A/B measurements.
+    // bits (SAT_VARIANT_EPI_*: force un-swapped, transposed fp32 epilogue, direct dword fp32 epilogue) for A/B measurements.
 #ifdef SAT_GEMM_EXPERIMENTS
     constexpr int ORI = MXA ? 0 : 2;
-    bool tr = !MXA && !(g.variant & 0x1000) && (EPI != EPI_F32 || (g.variant & 0x2000));
-    const bool direct_f32 = (g.variant & 0x8000) != 0;
+    bool tr = !MXA && !(g.variant & SAT_VARIANT_EPI_UNSWAPPED) && (EPI != EPI_F32 || (g.variant & SAT_VARIANT_EPI_F32_TR));
+    const bool direct_f32 = (g.variant & SAT_VARIANT_EPI_F32_DIRECT) != 0;
 #else
     constexpr int ORI = (MXA || EPI == EPI_F32) ? 0 : (EPI == EPI_SWIGLU ? 1 : 2);
     bool tr = ORI != 0;
@@ -1472,18 +1472,6 @@ int launch_cfg(const GemmArgs& a, hipStream_t stream) {
     return 0;
 }
 
-// Shipped tile configurations (variant ids as in round 1; everything else was an experiment and lives behind
-// -DSAT_GEMM_EXPERIMENTS, see profiles/r01_gemm_variants*.txt for what they measured):
-//    1  128x128, 4 waves, register-staged double buffer   (reference tile; tiny per-generation GEMMs: cross-attention to_kv)
-//    5  128x128, 4 waves, LDS-DMA double buffer            (K < 192: too short for a 3-stage ring)
-//   15  128x128x64, 8 waves, 3-stage LDS-DMA ring          (to_out at 1 prompt)
-//   44  the same with a 4-stage ring, fp32 output only     (FF-out at 1 prompt: K = 6144)
-//   16  128x64x64,  4 waves, 3-stage ring                  (cross-attention projections, M = 1025)
-//   22  256x256x64, 16 waves, 2-stage ring                 (FF-in at 1 prompt; every GEMM from 4 prompts on.  The 4-stage BK = 32
-//       variant with cross-tile fragment prefetch and grouped raster of round 1 measured within 2 % of it at 8 prompts after the
-//       epilogue rewrite -- profiles/r02_b8_tiles.txt -- and was removed)
-//   30  256x192x64, 12 waves, 2-stage ring                 (to_qkv at 1 prompt)
-// fp8 (e4m3) operands: 15 / 16 / 22 / 30 in three flavours (plain fp8 MFMA, 2x-rate block-scaled MFMA, MXFP8 A operand).
 // experiments build: SAT_GEMM_NO_DEEP=1 keeps the 3-stage ring for FF-out (A/B measurements)
 inline bool deep_ring_off() {
 #ifdef SAT_GEMM_EXPERIMENTS
@@ -1497,136 +1485,81 @@ inline bool deep_ring_off() {
 #endif
 }
 
-template <int EPI>
-int launch_epi(const GemmArgs& a, hipStream_t stream) {
-    int v = a.variant & 0xff;
-    if constexpr (EPI == EPI_HEADS) {
-        if (a.heads.xa_k) {       // fused cross-attention: built into the 128 x 64 tile only (the caller asks for it where that tile is the choice)
-            SAT_CHECK_ARG(!a.fp8 && a.K >= 192, SAT_E_UNSUPPORTED, "gemm: fused cross-attention needs bf16 operands and K >= 192");
-            return launch_pipe<128, 64, 64, 4, 1, 3, EPI>(a, stream);
-        }
+// tile id (the table in gemm_tiles.h) -> the template instantiation; F8 = e4m3 flavour of the operands (0: 16-bit)
+template <int ID, int EPI, int F8>
+int launch_tile(const GemmArgs& a, hipStream_t stream) {
+    constexpr SatTile t = sat_tile_geom(ID);
+    static_assert(!t.f32_only || EPI == EPI_F32, "tile built for the fp32-output epilogue only");
+    if constexpr (t.family == SAT_GEMM_PIPE) return launch_pipe<t.bm, t.bn, t.bk, t.wm, t.wn, t.ns, EPI, F8, t.kg, t.dil && F8 == 0>(a, stream);
+    else return launch_cfg<t.bm, t.bn, t.wm, t.wn, EPI, t.family == SAT_GEMM_DMA2>(a, stream);
+}
+
+// The ring tiles that are BUILT for (epilogue, operand flavour): sat_gemm_route hands out no others.
+template <int EPI, int F8>
+int launch_epi(int tile, const GemmArgs& a, hipStream_t stream) {
+#define SAT_TILE_CASE(id) \
+    case id: return launch_tile<id, EPI, F8>(a, stream);
+    switch (tile) {
+        SAT_TILE_CASE(SAT_TILE_128)
+        SAT_TILE_CASE(SAT_TILE_128x64)
+        SAT_TILE_CASE(SAT_TILE_256)
+        SAT_TILE_CASE(SAT_TILE_256x192)
     }
-    // fill of the last round of the device's CUs (256 on MI355X) x measured in-kernel rate of the tile, relative to the 256x256 tile
-    const long cus = std::max(1, sat_device_cus());
-    auto score = [&](int bm, int bn, double rate) {
-        if (a.N % bn) return 0.0;
-        long t = (long)cdiv(a.M, bm) * (a.N / bn);
-        return rate * (double)t / (double)(((t + cus - 1) / cus) * cus);
-    };
-#ifndef SAT_OPERAND_F16          // e4m3 operands ride in the bf16 build (sat_launch_gemm rejects f16 && fp8): the fp16 build does not instantiate them
-    if (a.fp8) {
-        if (v == 0) {
-            const double s256 = score(256, 256, 1.0), s192 = score(256, 192, 0.95), s128 = score(128, 128, 0.7), s64 = score(128, 64, 0.6);
-            const double best = s256 > s192 ? (s256 > s128 ? s256 : s128) : (s192 > s128 ? s192 : s128);
-            v = (s64 > best) ? 16 : (best == s256) ? 22 : (best == s192) ? 30 : 15;
-            if (a.K < 384 && (v == 15 || v == 16)) v = 22;     // the 3-stage tiles need K >= 384 bytes
-        }
-        if (a.fp8 == 3) {      // MXFP8 A operand (hardware block scales), fp32 output only: FF-out, to_out
-            if constexpr (EPI == EPI_F32) {
-                switch (v) {
-                    case 15: return launch_pipe<128, 128, 64, 4, 2, 3, EPI, 3>(a, stream);
-                    case 16: return launch_pipe<128, 64, 64, 4, 1, 3, EPI, 3>(a, stream);
-                    case 22: return launch_pipe<256, 256, 64, 4, 4, 2, EPI, 3>(a, stream);
-                    case 30: return launch_pipe<256, 192, 64, 4, 3, 2, EPI, 3>(a, stream);
-                }
-            }
-        } else if (a.fp8 == 2) {      // block-scaled MFMA with unit scales: 2x the MFMA rate
-            const int fv = a.variant & 0xff;
-            if ((fv == 80 || (fv == 0 && v == 22 && sat_wide_tile_of(a.variant) >= 80)) && sat_gemm_ph8_supports(EPI, a)) return sat_launch_gemm_ph8(EPI, a, stream);
-            switch (v) {
-                case 15: return launch_pipe<128, 128, 64, 4, 2, 3, EPI, 2>(a, stream);
-                case 16: return launch_pipe<128, 64, 64, 4, 1, 3, EPI, 2>(a, stream);
-                case 22: return launch_pipe<256, 256, 64, 4, 4, 2, EPI, 2>(a, stream);
-                case 30: return launch_pipe<256, 192, 64, 4, 3, 2, EPI, 2>(a, stream);
-            }
-        } else {
-            switch (v) {
-                case 15: return launch_pipe<128, 128, 64, 4, 2, 3, EPI, 1>(a, stream);
-                case 16: return launch_pipe<128, 64, 64, 4, 1, 3, EPI, 1>(a, stream);
-                case 22: return launch_pipe<256, 256, 64, 4, 4, 2, EPI, 1>(a, stream);
-                case 30: return launch_pipe<256, 192, 64, 4, 3, 2, EPI, 1>(a, stream);
-            }
-        }
-        sat_set_error("gemm(fp8): variant %d has no e4m3 build (15, 16, 22, 30)", v);
-        return SAT_E_INVALID;
-    }
-#endif
-    if (v == 0) {
-        // At 1 prompt (M = 2050) this gives FF-in 256x256 (432 workgroups, 2 rounds), to_qkv 256x192 (216 instead of 162
-        // workgroups), to_out / FF-out 128x128 (204) and the cross-attention projections (M = 1025) 128x64 (216); from 4 prompts on
-        // everything takes the 256x256 tile.
-        if (a.K >= 192) {
-            // The 256 x 256 tile is the 8-phase kernel where it applies; its rate relative to the 16-wave tile, measured at 8 prompts
-            // (profiles/r03_ph8_streamk.txt): SwiGLU 1.26, heads 1.07, fp32 output with a long reduction 1.02 -- and with the K-split of the
-            // remainder round (sat_gemm_ph8_splits) the last round costs ~0.35 of a round instead of 1.
-            double s256 = score(256, 256, 1.0);
-            if (sat_wide_tile_of(a.variant) >= 80 && sat_gemm_ph8_supports(EPI, a)) {
-                const double rate = EPI == EPI_SWIGLU ? 1.26 : EPI == EPI_HEADS ? 1.07 : 1.02;
-                const long t = (long)cdiv(a.M, 256) * (a.N / 256);
-                const double rounds = sat_gemm_ph8_splits(EPI, a) ? (double)(t / cus) + 0.35 : (double)((t + cus - 1) / cus);
-                s256 = rate * (double)t / (rounds * (double)cus);
-            }
-            const double s192 = score(256, 192, 0.95), s128 = score(128, 128, 0.7), s64 = score(128, 64, 0.6);
-            const double best = s256 > s192 ? (s256 > s128 ? s256 : s128) : (s192 > s128 ? s192 : s128);
-            if (best == 0.0 && s64 == 0.0) v = 15;      // N is not a tile multiple: let the launcher report it
-            else if (s64 > best) v = 16;
-            else if (best == s256) v = 22;
-            else if (best == s192) v = 30;
-            else v = 15;
-            // long reductions (FF-out: 96 K-tiles) gain 4 % from a fourth ring stage (prefetch distance 3); K = 1536 does not care
-            if (v == 15 && EPI == EPI_F32 && a.K >= 4096 && !deep_ring_off()) v = 44;
-            // one round of 128 x 128 tiles (to_out / FF-out at one prompt: 204 workgroups on 256 CUs): the two-K-group build puts 8 waves of
-            // 64 x 64 on every CU instead of 8 waves of 32 x 64 -- FF-out 56.5 us against 60.7, to_out 20.6 against 21.4 (tools/ph8_probe.py narrow)
-            if ((v == 15 || v == 44) && EPI == EPI_F32 && !a.fp8 && a.K % 128 == 0 && a.K >= 256 && (long)cdiv(a.M, 128) * (a.N / 128) <= cus &&
-                !(a.variant & 0x800000) && sat_wide_tile_of(a.variant) != 82)
-                v = 49;
-        } else {
-            v = 5;
-        }
-    }
-    // the 256x256 tile is the 8-wave / 8-phase kernel of gemm_ph8.hip wherever it applies (bf16 operands, K % 128 == 0);
-    // tile policy 22 (sat_dit_cfg.tile_policy) brings the 16-wave 2-stage tile back for A/B measurements
-    if (v == 22 && !(a.variant & 0xff) && sat_wide_tile_of(a.variant) >= 80 && sat_gemm_ph8_supports(EPI, a)) return sat_launch_gemm_ph8(EPI, a, stream);
-    switch (v) {
-        case 1: return launch_cfg<128, 128, 2, 2, EPI>(a, stream);
-        case 5: return launch_cfg<128, 128, 2, 2, EPI, true>(a, stream);
-        case 15: return launch_pipe<128, 128, 64, 4, 2, 3, EPI>(a, stream);
-        case 44:
-            if constexpr (EPI == EPI_F32) return launch_pipe<128, 128, 64, 4, 2, 4, EPI>(a, stream);
-            break;
-        case 16: return launch_pipe<128, 64, 64, 4, 1, 3, EPI, 0, 1, true>(a, stream);      // four waves = one per SIMD: LDS-DMA pieces in the MFMA stream (15.1 vs 16.2 us, cross to_out)
-        case 49:           // 128 x 128 on two K-groups of 2 x 2 waves (64 x 64 each), 2 x 64 k per stage, 2 stages
-            if constexpr (EPI == EPI_F32) return launch_pipe<128, 128, 64, 2, 2, 2, EPI, 0, 2>(a, stream);
-            break;
-        case 22: return launch_pipe<256, 256, 64, 4, 4, 2, EPI>(a, stream);
-        case 30: return launch_pipe<256, 192, 64, 4, 3, 2, EPI>(a, stream);
+    if constexpr (F8 == 0) {
+        switch (tile) {
+            SAT_TILE_CASE(SAT_TILE_REF_128)
+            SAT_TILE_CASE(SAT_TILE_DMA_128)
 #ifdef SAT_GEMM_EXPERIMENTS
-        case 55: return launch_pipe<128, 128, 64, 4, 2, 3, EPI, 0, 1, true>(a, stream);      // tiles 15 / 16 / 30 / 44 with the LDS-DMA pieces in the MFMA stream (A/B)
-        case 56: return launch_pipe<128, 64, 64, 4, 1, 3, EPI>(a, stream);                   // tile 16 with its pieces in front of the loop body (A/B)
-        case 60: return launch_pipe<256, 192, 64, 4, 3, 2, EPI, 0, 1, true>(a, stream);
-        case 54:
-            if constexpr (EPI == EPI_F32) return launch_pipe<128, 128, 64, 4, 2, 4, EPI, 0, 1, true>(a, stream);
-            break;
-        case 2: return launch_cfg<256, 128, 4, 2, EPI>(a, stream);
-        case 3: return launch_cfg<256, 256, 2, 4, EPI>(a, stream);
-        case 7: return launch_cfg<256, 256, 2, 4, EPI, true>(a, stream);
-        case 10: return launch_pipe<128, 128, 64, 2, 2, 3, EPI>(a, stream);
-        case 12: return launch_pipe<256, 128, 64, 4, 2, 3, EPI>(a, stream);
-        case 13: return launch_pipe<256, 256, 32, 2, 4, 3, EPI>(a, stream);
-        case 39: return launch_pipe<128, 128, 128, 4, 2, 2, EPI>(a, stream);       // 256-B rows: half the barriers per k
-        case 48: return launch_pipe<128, 128, 128, 2, 2, 2, EPI>(a, stream);       // the same on 4 waves of 64x64 (the vendor library's pick for FF-out at one prompt)
-        case 41: return launch_pipe<256, 128, 32, 4, 2, 3, EPI>(a, stream);        // 72 KiB, <= 128 VGPRs: two workgroups per CU
-        case 45:                                                                    //                               distance 4 (160 KiB)
-            if constexpr (EPI == EPI_F32) return launch_pipe<128, 128, 64, 4, 2, 5, EPI>(a, stream);
-            break;
-        case 46: return launch_pipe<128, 64, 64, 4, 1, 5, EPI>(a, stream);         // tile 16 with prefetch distance 4
-        case 47: return launch_pipe<128, 64, 64, 4, 1, 6, EPI>(a, stream);         //                               distance 5 (144 KiB)
-        case 42: return launch_pipe<128, 128, 64, 2, 2, 4, EPI>(a, stream);        // 4 waves of 64x64 (half the LDS reads per MFMA of tile 15), 4 stages
-        case 43: return launch_pipe<128, 128, 64, 2, 2, 2, EPI>(a, stream);        // same, 2 stages = 64 KiB: two workgroups per CU
+            SAT_TILE_CASE(SAT_TILE_X_128_DIL)
+            SAT_TILE_CASE(SAT_TILE_X_128x64_FRONT)
+            SAT_TILE_CASE(SAT_TILE_X_256x192_DIL)
+            SAT_TILE_CASE(SAT_TILE_X_REG_256x128)
+            SAT_TILE_CASE(SAT_TILE_X_REG_256)
+            SAT_TILE_CASE(SAT_TILE_X_DMA_256)
+            SAT_TILE_CASE(SAT_TILE_X_128_4W)
+            SAT_TILE_CASE(SAT_TILE_X_256x128)
+            SAT_TILE_CASE(SAT_TILE_X_256_BK32)
+            SAT_TILE_CASE(SAT_TILE_X_128_BK128)
+            SAT_TILE_CASE(SAT_TILE_X_128_BK128_4W)
+            SAT_TILE_CASE(SAT_TILE_X_256x128_BK32)
+            SAT_TILE_CASE(SAT_TILE_X_128x64_DEEP5)
+            SAT_TILE_CASE(SAT_TILE_X_128x64_DEEP6)
+            SAT_TILE_CASE(SAT_TILE_X_128_4W_DEEP)
+            SAT_TILE_CASE(SAT_TILE_X_128_4W_2ST)
 #endif
-        default: break;
+        }
+        if constexpr (EPI == EPI_F32) {
+            switch (tile) {
+                SAT_TILE_CASE(SAT_TILE_128_DEEP)
+                SAT_TILE_CASE(SAT_TILE_128_KGROUP)
+#ifdef SAT_GEMM_EXPERIMENTS
+                SAT_TILE_CASE(SAT_TILE_X_128_DEEP_DIL)
+                SAT_TILE_CASE(SAT_TILE_X_128_DEEP5)
+#endif
+            }
+        }
+        if constexpr (EPI == EPI_HEADS) {
+            switch (tile) { SAT_TILE_CASE(SAT_TILE_128x64_XATTN) }
+        }
     }
-    sat_set_error("gemm: unknown variant %d (or not built for this epilogue)", v);
+#undef SAT_TILE_CASE
+    sat_set_error("gemm: tile %d is not built for epilogue %d, operand flavour %d", tile, EPI, F8);
+    return SAT_E_INVALID;
+}
+
+template <int EPI>
+int launch_flavour(const GemmRoute& r, const GemmArgs& a, hipStream_t stream) {
+    switch (r.e4m3) {
+        case 0: return launch_epi<EPI, 0>(r.tile, a, stream);
+#ifndef SAT_OPERAND_F16          // e4m3 operands ride in the bf16 build (sat_launch_gemm rejects f16 && fp8): the fp16 build does not instantiate them
+        case 1: return launch_epi<EPI, 1>(r.tile, a, stream);
+        case 2: return launch_epi<EPI, 2>(r.tile, a, stream);      // block-scaled MFMA with unit scales: 2x the MFMA rate
+        case 3:                                                      // MXFP8 A operand (hardware block scales), fp32 output only: FF-out, to_out
+            if constexpr (EPI == EPI_F32) return launch_epi<EPI, 3>(r.tile, a, stream);
+            break;
+#endif
+    }
+    sat_set_error("gemm: no e4m3 flavour %d of epilogue %d in this build", r.e4m3, EPI);
     return SAT_E_INVALID;
 }
 
@@ -1658,13 +1591,28 @@ int SAT_OPNS::sat_launch_gemm(int epi, const GemmArgs& a, hipStream_t stream) {
                                  (((uintptr_t)a.ln_part | (uintptr_t)a.ln_c1 | (uintptr_t)a.ln_c2) & 15) == 0),
                   SAT_E_INVALID, "gemm: LayerNorm fold needs ln_c1 / ln_c2 / ln_eps, no separate bias (it is part of ln_c2), 16-byte aligned vectors");
     SAT_CHECK_ARG((((uintptr_t)a.xb | (uintptr_t)a.ln_part_out) & 15) == 0, SAT_E_INVALID, "gemm: xb / ln_part_out must be 16-byte aligned");
-    if ((a.variant & 0xfff) % 100 == 80 || (a.variant & 0xfff) % 100 == 81) return sat_launch_gemm_ph8(epi, a, stream);      // 256x256x64, 8 waves, 8-phase schedule (gemm_ph8.hip)
-    switch (epi) {
-        case EPI_F32:
-        case EPI_RESID: return launch_epi<EPI_F32>(a, stream);
-        case EPI_SWIGLU: return launch_epi<EPI_SWIGLU>(a, stream);
-        case EPI_HEADS: return launch_epi<EPI_HEADS>(a, stream);
+    // what runs is decided by sat_gemm_route (gemm_tiles.h) from these integers and flags alone
+    const int cus = sat_device_cus();
+    GemmShape s{};
+    s.M = a.M; s.N = a.N; s.K = a.K; s.variant = a.variant; s.fp8 = a.fp8;
+    s.h8 = a.H8 != nullptr; s.ln_part = a.ln_part != nullptr; s.gate = a.gate != nullptr;
+    s.heads = a.heads.heads; s.xattn = a.heads.xa_k != nullptr;
+    s.slab_ok = cus > 0 && a.slab && a.slab_bytes >= (size_t)cus * 65536 * sizeof(float);
+    s.e4m3_built = !SAT_OP_IS_F16;
+    s.no_deep_ring = deep_ring_off();
+    const GemmRoute r = sat_gemm_route(epi, s, cus);
+    switch (r.msg) {
+        case SAT_ROUTE_OK: break;
+        case SAT_ROUTE_UNKNOWN_EPI: sat_set_error("gemm: unknown epilogue %d", epi); return SAT_E_INVALID;
+        case SAT_ROUTE_XATTN_OPERANDS: sat_set_error("gemm: fused cross-attention needs bf16 operands and K >= 192"); return SAT_E_UNSUPPORTED;
+        case SAT_ROUTE_NO_E4M3_TILE: sat_set_error("gemm(fp8): variant %d has no e4m3 build (15, 16, 22, 30)", r.tile); return SAT_E_INVALID;
+        case SAT_ROUTE_PH8_NOT_BUILT: sat_set_error("gemm(8-phase): epilogue %d / ablation %d not built", epi, r.tile); return SAT_E_UNSUPPORTED;
+        default: sat_set_error("gemm: unknown variant %d (or not built for this epilogue)", r.tile); return SAT_E_INVALID;
     }
-    sat_set_error("gemm: unknown epilogue %d", epi);
-    return SAT_E_INVALID;
+    if (r.family == SAT_GEMM_PH8) return sat_launch_gemm_ph8(epi, r.ph8, a, stream);
+    switch (epi) {
+        case EPI_SWIGLU: return launch_flavour<EPI_SWIGLU>(r, a, stream);
+        case EPI_HEADS: return launch_flavour<EPI_HEADS>(r, a, stream);
+        default: return launch_flavour<EPI_F32>(r, a, stream);          // EPI_F32, EPI_RESID
+    }
 }

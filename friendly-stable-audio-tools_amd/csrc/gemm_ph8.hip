@@ -27,12 +27,12 @@
 //   (profiles/r03_ph8_two_phases.txt).  It is kept as `main_loop` for A/B, variant bit 18, experiments build.)
 //   Measured in the loop: 1.36 us per K-tile on 256 CUs = 1575 TFLOP/s (profiles/r03_ph8_ksweep_fixed_overhead.txt).
 //
-// Schedule (PERSISTENT workgroups, one per CU; Ph8Sched).  With one 136-KiB workgroup per CU nothing overlaps a tile's prologue and
+// Schedule (PERSISTENT workgroups, one per CU; Ph8Sched and its functions are ph8_sched.h, plain C++ that the CPU tests walk).  With one 136-KiB workgroup per CU nothing overlaps a tile's prologue and
 // epilogue, and a launch of T tiles costs ceil(T / 256) rounds: measured 8-10 us of a 42-52 us tile
 // (profiles/r03_ph8_workgroup_timeline.txt) and, at one prompt, 2 rounds for 1.5 rounds of work.  So:
 //   * workgroup i walks `dp_rounds` whole tiles (logical tile s G + i in round s: the same neighbourhood per round as hardware
 //     dispatch order, XCD-aware), then its share of the REMAINDER round: whole tiles (contiguous shares), or -- fp32 output with a long
-//     reduction behind a whole round, sat_gemm_ph8_splits -- ONE K-range of a remainder tile: every remainder tile is cut along K into
+//     reduction behind a whole round, ph8_auto_split -- ONE K-range of a remainder tile: every remainder tile is cut along K into
 //     equal parts, one workgroup per part, parts in proportion to cost (row tiles with <= 64 valid rows -- the 2 leftover rows of
 //     M = 2 x 1025 -- count half);
 //   * a partial K-range stores its raw accumulators to the workgroup's slab (lane-for-lane the register image, 1-KiB coalesced
@@ -122,94 +122,12 @@ __device__ __forceinline__ int chan_of(int ni, int nf, int i) {
     else return ni == 0 ? nf * 16 + i : 32 + q * 8 + nf * 4 + r;
 }
 
-struct Ph8Sched {          // host-computed per launch (ph8_schedule), passed by value
-    int G;                  // workgroups (== gridDim.x)
-    int tiles_n;
-    int tiles_m_full;       // row tiles of the "full" logical tile space
-    int light;              // 1: one more row of tiles with <= 64 valid rows ("light": about half the time of a full tile: the W panel still streams)
-    int light_first;        // work order: light tiles before the full ones (K-split schedules with whole rounds) instead of behind them
-    int dp_rounds;          // whole tiles per workgroup
-    int nkp;                // K-pair units (128 k) per tile
-    int sk_tiles;           // tiles of the remainder space (the full tiles left over by the whole rounds, and the light tiles)
-    int rem0;               // work-order position of the first remainder tile (remainder tile j = position rem0 + j)
-    int split;              // 0: remainder tiles stay whole; 1: every remainder tile is cut along K, one workgroup per part
-    int sk_q, sk_r;         // split 0: workgroup i takes sk_q (+ 1 if i < sk_r) consecutive remainder tiles
-    int cls_n[3], cls_p[3]; // split 1: three consecutive classes of remainder tiles, cls_n[c] tiles of cls_p[c] parts each
-    float* sk_slab;         // split 1: [G][65536] raw accumulator images (caller's workspace)
-};
-
-// units [b, e) of the remainder space (unit = 128 k of one tile, tile j = units [j nkp, (j + 1) nkp)) that workgroup i works on
-__host__ __device__ __forceinline__ void ph8_wg_units(const Ph8Sched& sc, int i, int& b, int& e) {
-    if (!sc.split) {
-        const int lo = i < sc.sk_r ? i : sc.sk_r, hi = i + 1 < sc.sk_r ? i + 1 : sc.sk_r;
-        b = (i * sc.sk_q + lo) * sc.nkp;
-        e = ((i + 1) * sc.sk_q + hi) * sc.nkp;
-        return;
-    }
-    int w0 = 0, j0 = 0;
-    b = e = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int n = sc.cls_n[c], p = sc.cls_p[c];
-        if (i >= w0 && i < w0 + n * p) {
-            const int j = j0 + (i - w0) / p, k = (i - w0) % p;
-            b = j * sc.nkp + sc.nkp * k / p;
-            e = j * sc.nkp + sc.nkp * (k + 1) / p;
-        }
-        w0 += n * p;
-        j0 += n;
-    }
-}
-// split 1: the workgroups first .. first + parts - 1 that hold remainder tile j's K-ranges
-__host__ __device__ __forceinline__ void ph8_tile_parts(const Ph8Sched& sc, int j, int& first, int& parts) {
-    int w0 = 0, j0 = 0;
-    first = 0;
-    parts = 1;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int n = sc.cls_n[c], p = sc.cls_p[c];
-        if (j >= j0 && j < j0 + n) {
-            first = w0 + (j - j0) * p;
-            parts = p;
-        }
-        w0 += n * p;
-        j0 += n;
-    }
-}
-
 struct Seg {                // one K-range of one tile
     int m0, n0;
     int kt0, nk;            // first K-tile, K-tiles (even)
     bool whole;             // the K-range covers the tile: plain epilogue
     bool tr;                // accumulator orientation (transposed unless a V^T destination)
 };
-
-
-// position in the work order -> tile.  Work order: the full tiles (short M: m fastest, the W panel of a column tile stays in one
-// XCD's L2; long M: bands of 8 row tiles, n-major inside a band -- 8 A panels + the W panels in flight) with the light row behind
-// them, or (light_first) in front of them.
-__device__ __forceinline__ void ph8_tile_of(const Ph8Sched& sc, int id, int& tm, int& tn) {
-    const int nl = sc.light ? sc.tiles_n : 0;
-    const int lid = sc.light_first ? id : id - sc.tiles_m_full * sc.tiles_n;
-    if (lid >= 0 && lid < nl) {
-        tm = sc.tiles_m_full;
-        tn = lid;
-        return;
-    }
-    const int L = sc.light_first ? id - nl : id;
-    const int tiles_m = sc.tiles_m_full, tiles_n = sc.tiles_n;
-    if (tiles_m <= 12) {
-        tn = L / tiles_m;
-        tm = L - tn * tiles_m;
-    } else {
-        const int band_sz = 8 * tiles_n;
-        const int band = L / band_sz;
-        const int rem = L - band * band_sz;
-        const int gm = min(8, tiles_m - band * 8);
-        tn = rem / gm;
-        tm = band * 8 + (rem - tn * gm);
-    }
-}
 
 // fp32 output / residual update of ONE token row piece (transformer.py:692-700), adaLN gate (:674, 688), and the producer side of the
 // LayerNorm fold: 16-bit image of the updated row + (sum, sum of squares) of the ROUNDED values over the wave's 64-column block.
@@ -333,7 +251,8 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
     const int M = g.M, N = g.N, K = g.K;
     const int wgi = xcd_remap(blockIdx.x, sc.G);          // consecutive logical workgroups share an XCD (and so the tiles they split)
 
-    // ---- the walk over this workgroup's K-ranges
+    // ---- the walk over this workgroup's K-ranges (restated for the CPU in tests/host/gemm_host_dump.cpp, which checks that the walks
+    // of all workgroups cover every tile's K exactly once: change both together)
     auto tile_of = [&](int id, int& tm, int& tn) { ph8_tile_of(sc, id, tm, tn); };
     int dp_s = 0;
     int sk_b = 0, sk_e = 0;
@@ -1195,89 +1114,32 @@ __global__ __launch_bounds__(512) void ph8_reduce_f32_kernel(GemmArgs g, Ph8Sche
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// host side: the persistent schedule of a shape -- a few integers in closed form, rebuilt per launch (no state, no allocation)
+// host side: the persistent schedule of a shape is ph8_schedule_ints (ph8_sched.h) -- a few integers in closed form, rebuilt per
+// launch (no state, no allocation); what needs the device or the caller's pointers is here
 // ---------------------------------------------------------------------------------------------------------------------------------
 int ph8_cus(int& out) {
     out = sat_device_cus();
     return out > 0 ? 0 : SAT_E_INVALID;
 }
 
-// Measured policy (profiles/r03_ph8_streamk.txt): split only fp32-output GEMMs with a long reduction (K >= 4096: FF-out) behind at
-// least one whole round, and only when every remainder tile gets >= 2 parts (otherwise the whole tiles set the makespan and the slab
-// traffic -- 256 KiB per part written and read back at HBM speed, everybody at the same time -- is pure loss): SA-2.0 FF-out -25 %.
-// 8 prompts (134 remainder tiles on 256 CUs) and every K = 1536 GEMM stay whole; below one whole round the 128 x 128 tiles of
-// gemm_bf16.hip are faster (FF-out at 1 prompt: 60 us against 67).
-bool ph8_auto_split(const GemmArgs& a, bool epi_f32, int cus) {
-    const long t_all = (long)cdiv(a.M, 256) * (a.N / 256);
-    const long rem = t_all % cus;
-    return epi_f32 && a.K >= 4096 && t_all > cus && rem > 0 && 2 * rem <= cus;
-}
-
-// split: 0 = the remainder round's tiles stay whole (contiguous shares, light tiles last), 1 = every remainder tile is cut along K
-// (needs GemmArgs::slab), -1 = the measured policy above
-int ph8_schedule(const GemmArgs& a, int split, bool epi_f32, int bm, int bn, int wgs_per_cu, Ph8Sched& out) {
+int ph8_schedule(const GemmArgs& a, bool epi_f32, int bm, int bn, int wgs_per_cu, Ph8Sched& s) {
     int cus = 0;
     SAT_TRY(ph8_cus(cus));
     // the automatic policy only splits when the caller's slab holds one accumulator image per workgroup -- the same condition the tile score
-    // assumes (sat_gemm_ph8_splits); an undersized workspace runs the unsplit schedule.  A FORCED split (variant bit 16) keeps the hard error.
+    // assumes (GemmShape::slab_ok); an undersized workspace runs the unsplit schedule.  A FORCED split keeps the hard error.
+    const int split = sat_variant_split(a.variant);
     const bool have_slab = a.slab != nullptr && (split >= 0 || a.slab_bytes >= (size_t)cus * 65536 * sizeof(float));
-    if (split < 0) split = (bm == 256 && epi_f32 && have_slab && ph8_auto_split(a, epi_f32, cus)) ? 1 : 0;
-    if (bm != 256 || !epi_f32) split = 0;          // the K-split machinery (slabs, reduce kernel) is built for the 256 x 256 fp32-output tile
-    Ph8Sched s{};
-    const int tiles_m = cdiv(a.M, bm), tail = a.M % bm;
-    s.tiles_n = a.N / bn;
-    s.light = (tail != 0 && tail <= bm / 4 && tiles_m > 1) ? 1 : 0;          // only the first quadrant of the first wave row has rows
-    s.tiles_m_full = tiles_m - s.light;
-    s.nkp = a.K / 128;
-    const long t_full = (long)s.tiles_m_full * s.tiles_n, t_light = s.light ? s.tiles_n : 0;
-    const long t_all = t_full + t_light;
-    s.G = (int)std::min<long>((long)cus * wgs_per_cu, split ? t_all * s.nkp : t_all);
-    // Balanced rounds: a launch of more than one and at most two rounds runs on FEWER workgroups, every one with two tiles (390 tiles:
-    // 2 x 195 instead of 256 + 134; FF-in at one prompt: 2 x 216, which is also what the vendor library's stream-K launches for this
-    // shape).  The chip is power-limited under MFMA load -- a tile runs faster when fewer CUs are active -- so the idle CUs cost
-    // less than a half-empty second round: FF-out at 8 prompts 336 -> 311 us, FF-in at one prompt 85.4 -> 82.6 us.  With many rounds it
-    // loses (FF-in at 8 prompts, 12.2 rounds: 479 -> 488 us): profiles/r04_ph8_balanced_rounds.txt.  Variant bit 21 switches it off (A/B).
-    if (!split && !(a.variant & 0x200000) && t_all > s.G && t_all <= 2L * s.G) s.G = (int)((t_all + 1) / 2);
-#ifdef SAT_GEMM_EXPERIMENTS
-    if (!split && (a.variant & 0x400000) && t_all > s.G) {          // bit 22 (A/B): balanced rounds at any round count
-        const long rounds = (t_all + s.G - 1) / s.G;
-        s.G = (int)((t_all + rounds - 1) / rounds);
-    }
-#endif
-    s.dp_rounds = (int)((split ? t_all : t_full) / s.G);
-    // K-split with at least one whole round: the light tiles go FIRST (they idle their workgroup for half of round 0 -- a handful of
-    // them) so that the remainder round holds full tiles only and splits evenly
-    s.light_first = (split && s.dp_rounds >= 1 && t_light) ? 1 : 0;
-    s.rem0 = (int)((long)s.dp_rounds * s.G);
-    s.sk_tiles = (int)(t_all - s.rem0);
-    s.split = (split && s.sk_tiles) ? 1 : 0;
-    if (s.sk_tiles && !s.split) {
-        s.sk_q = s.sk_tiles / s.G;
-        s.sk_r = s.sk_tiles % s.G;
-    } else if (s.sk_tiles) {
-        // remainder tiles in work order: full ones (cost 2), then -- unless they went first -- the light ones (cost 1).  Parts per tile in
-        // proportion to cost, at most min(nkp, 8); leftover workgroups give the first full tiles one more part: three classes.
-        const int n_light = s.light_first ? 0 : (int)std::min<long>(t_light, s.sk_tiles);
-        const int n_full = s.sk_tiles - n_light;
-        const long cost2 = 2L * n_full + n_light;
-        const int cap = std::min(s.nkp, 8);
-        const int pf = (int)std::max<long>(1, std::min<long>(cap, (long)s.G * 2 / cost2));
-        const int pl = (int)std::max<long>(1, std::min<long>(cap, (long)s.G * 1 / cost2));
-        long used = (long)n_full * pf + (long)n_light * pl;
-        int extra = 0;
-        if (pf < cap && used < s.G) extra = (int)std::min<long>(n_full, s.G - used);
-        used += extra;
-        SAT_CHECK_ARG(used <= s.G, SAT_E_INVALID, "gemm(8-phase): the K-split needs %ld workgroups, has %d", used, s.G);
-        s.cls_n[0] = extra; s.cls_p[0] = pf + 1;
-        s.cls_n[1] = n_full - extra; s.cls_p[1] = pf;
-        s.cls_n[2] = n_light; s.cls_p[2] = pl;
+    const int balance = (sat_variant_has(a.variant, SAT_VARIANT_BALANCE_OFF) ? PH8_BALANCE_OFF : 0) |
+                        (SAT_GEMM_EXP && sat_variant_has(a.variant, SAT_VARIANT_BALANCE_ANY) ? PH8_BALANCE_ANY : 0);
+    const long used = ph8_schedule_ints(a.M, a.N, a.K, split, epi_f32, bm, bn, wgs_per_cu, cus, have_slab, balance, s);
+    SAT_CHECK_ARG(used == 0, SAT_E_INVALID, "gemm(8-phase): the K-split needs %ld workgroups, has %d", used, s.G);
+    if (s.split) {
         const size_t need = (size_t)s.G * 65536 * sizeof(float);
         SAT_CHECK_ARG(a.slab && a.slab_bytes >= need, SAT_E_WORKSPACE, "gemm(8-phase): the K-split of the remainder round needs %zu bytes of slab workspace, got %zu",
                       need, a.slab ? a.slab_bytes : (size_t)0);
         SAT_CHECK_ARG(((uintptr_t)a.slab & 15) == 0, SAT_E_INVALID, "gemm(8-phase): the slab workspace must be 16-byte aligned");
         s.sk_slab = a.slab;
     }
-    out = s;
     return 0;
 }
 
@@ -1319,9 +1181,7 @@ int launch_ph8(const GemmArgs& a0, hipStream_t stream) {
         SAT_CHECK_ARG(!a.heads.xa_k, SAT_E_UNSUPPORTED, "gemm(8-phase): the fused cross-attention epilogue lives in the 128 x 64 tile");
     }
     Ph8Sched sc;
-    // bits 16 / 17 of the variant force / forbid the K-split of the remainder round (measurements, tests)
-    const int split = (a.variant & 0x10000) ? 1 : (a.variant & 0x20000) ? 0 : -1;
-    SAT_TRY(ph8_schedule(a, split, EPI == EPI_F32, BM, BN, BM == 256 ? 1 : 2, sc));
+    SAT_TRY(ph8_schedule(a, EPI == EPI_F32, BM, BN, BM == 256 ? 1 : 2, sc));
     SAT_CHECK_ARG(GATED == (a0.gate != nullptr), SAT_E_INVALID, "gemm(8-phase): gated / plain build mismatch");
     auto kern = gemm_ph8_kernel<EPI, DBG, PH2, PH2V, WN, MFQ, FP8, GATED>;
     SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS));
@@ -1339,21 +1199,50 @@ int launch_ph8(const GemmArgs& a0, hipStream_t stream) {
     return 0;
 }
 
-}  // namespace
-
-// whether the launcher's automatic choice of the 256 x 256 tile should land here (a forced variant 80 always does)
-bool SAT_OPNS::sat_gemm_ph8_supports(int epi, const GemmArgs& a) {
-    if (a.N % 256 || a.K % 128 || (uint64_t)a.M * (uint64_t)a.K * 2u >= (1ull << 31)) return false;
-    if (a.fp8 || a.H8) {      // e4m3: the LayerNorm-fed GEMMs (to_qkv, cross to_q, FF-in) with per-token scales
-        if (a.fp8 != 2 || a.K % 256 || a.ln_part || !(epi == EPI_SWIGLU || epi == EPI_HEADS) || (a.H8 && epi != EPI_SWIGLU)) return false;
-    }
-    // fp32-output GEMMs with a short reduction (to_out, cross to_out: K = 1536) spend a third of their time in the residual
-    // read-modify-write at HBM speed; persistent workgroups run those epilogues in lockstep, the 16-wave tile's independent workgroups
-    // drift apart and overlap them with other tiles' main loops: measured 111 us against 122 at 8 prompts (profiles/r03_ph8_streamk.txt)
-    if ((epi == EPI_F32 || epi == EPI_RESID) && a.K < 4096 && sat_wide_tile_of(a.variant) != 81) return false;          // (81: sat_dit_cfg.tile_policy, A/B)
-    if (epi == EPI_HEADS) return (a.heads.heads * 64) % 256 == 0;
-    return true;
+template <int EPI, int BUILD>
+int launch_ph8_build(const GemmArgs& a, hipStream_t stream) {
+    constexpr SatPh8Params p = sat_ph8_params(BUILD);
+    return launch_ph8<EPI, p.dbg, p.ph2, p.ph2v, p.wn, p.mfq, p.fp8, p.gated>(a, stream);
 }
+
+// the builds that exist for one epilogue (sat_ph8_route, gemm_tiles.h, hands out no others)
+template <int EPI>
+int launch_ph8_epi(int build, const GemmArgs& a, hipStream_t stream) {
+    switch (build) {
+        case SAT_PH8_PLAIN: return launch_ph8_build<EPI, SAT_PH8_PLAIN>(a, stream);
+        case SAT_PH8_GATED:
+            if constexpr (EPI == EPI_F32) return launch_ph8_build<EPI, SAT_PH8_GATED>(a, stream);
+            break;
+#ifndef SAT_OPERAND_F16          // (e4m3 operands ride in the bf16 build: sat_launch_gemm rejects f16 && fp8)
+        case SAT_PH8_E4M3:
+            if constexpr (EPI != EPI_F32) return launch_ph8_build<EPI, SAT_PH8_E4M3>(a, stream);
+            break;
+#endif
+#ifdef SAT_GEMM_EXPERIMENTS
+        case SAT_PH8_FOUR_PHASE:
+            if constexpr (EPI != EPI_HEADS) return launch_ph8_build<EPI, SAT_PH8_FOUR_PHASE>(a, stream);
+            break;
+        case SAT_PH8_WHI_EARLY:
+            if constexpr (EPI != EPI_HEADS) return launch_ph8_build<EPI, SAT_PH8_WHI_EARLY>(a, stream);
+            break;
+        case SAT_PH8_ABLATION_1:
+            if constexpr (EPI == EPI_F32) return launch_ph8_build<EPI, SAT_PH8_ABLATION_1>(a, stream);
+            break;
+        case SAT_PH8_ABLATION_2:
+            if constexpr (EPI == EPI_F32) return launch_ph8_build<EPI, SAT_PH8_ABLATION_2>(a, stream);
+            break;
+        case SAT_PH8_ABLATION_3:
+            if constexpr (EPI == EPI_F32) return launch_ph8_build<EPI, SAT_PH8_ABLATION_3>(a, stream);
+            break;
+        case SAT_PH8_TIMESTAMPS: return launch_ph8_build<EPI, SAT_PH8_TIMESTAMPS>(a, stream);
+        case SAT_PH8_GEOM_128: return launch_ph8_build<EPI, SAT_PH8_GEOM_128>(a, stream);
+#endif
+    }
+    sat_set_error("gemm(8-phase): build %d does not exist for epilogue %d", build, EPI);
+    return SAT_E_UNSUPPORTED;
+}
+
+}  // namespace
 
 #if defined(SAT_GEMM_EXPERIMENTS) && !defined(SAT_OPERAND_F16)
 extern "C" __attribute__((visibility("default"))) int sat_gemm_ph8_timestamps(unsigned long long* out_host) {
@@ -1364,80 +1253,23 @@ extern "C" __attribute__((visibility("default"))) int sat_gemm_ph8_timestamps(un
 }
 #endif
 
-bool SAT_OPNS::sat_gemm_ph8_splits(int epi, const GemmArgs& a) {
-    int cus = 0;
-    if (ph8_cus(cus) != 0 || !a.slab || a.slab_bytes < (size_t)cus * 65536 * sizeof(float)) return false;
-    return ph8_auto_split(a, epi == EPI_F32 || epi == EPI_RESID, cus);
-}
-
 // bytes of slab workspace (GemmArgs::slab) with which the launcher's automatic schedule splits the remainder round of this shape
 // along K; 0 = it would not split (callers size their workspace with this: sat_dit_workspace_bytes)
 size_t SAT_OPNS::sat_gemm_ph8_slab_bytes(int epi, int M, int N, int K) {
     int cus = 0;
     if (ph8_cus(cus) != 0) return 0;
-    GemmArgs a{};
-    a.M = M; a.N = N; a.K = K;
-    if (N % 256 || K % 128 || !ph8_auto_split(a, epi == EPI_F32 || epi == EPI_RESID, cus)) return 0;
+    if (N % 256 || K % 128 || !ph8_auto_split(M, N, K, epi == EPI_F32 || epi == EPI_RESID, cus)) return 0;
     return (size_t)cus * 65536 * sizeof(float);
 }
 
-int SAT_OPNS::sat_launch_gemm_ph8(int epi, const GemmArgs& a, hipStream_t stream) {
-    const int dbg = (a.variant & 0xfff) / 100;
-#ifdef SAT_GEMM_EXPERIMENTS
-    // The 128 x 128 geometry (4 waves, two workgroups per CU), experiments build only: measured SLOWER than the 16-wave-family tiles at
-    // every one-prompt shape (FF-out 69.5 us vs 62.3, to_out 26.8 vs 22.4, cross 25.0 vs 16.2, QKV 68 vs 51;
-    // profiles/r03_ph8_128x128_geometry_negative.txt) -- 16 MFMAs between barriers and half the operand reuse per LDS byte.
-    if ((a.variant & 0xfff) % 100 == 81) {
-        switch (epi) {
-            case EPI_F32:
-            case EPI_RESID: return launch_ph8<EPI_F32, 0, true, 1, 2, 2>(a, stream);
-            case EPI_SWIGLU: return launch_ph8<EPI_SWIGLU, 0, true, 1, 2, 2>(a, stream);
-            case EPI_HEADS: return launch_ph8<EPI_HEADS, 0, true, 1, 2, 2>(a, stream);
-        }
-    }
-#endif
+// build: SatPh8Build, as sat_gemm_route chose it
+int SAT_OPNS::sat_launch_gemm_ph8(int epi, int build, const GemmArgs& a, hipStream_t stream) {
     switch (epi) {
         case EPI_F32:
-        case EPI_RESID:
-            switch (dbg) {
-                case 0:
-#ifdef SAT_GEMM_EXPERIMENTS
-                    if (a.variant & 0x40000) return launch_ph8<EPI_F32, 0, false>(a, stream);          // bit 18: the four-phase loop (A/B)
-                    if (a.variant & 0x80000) return launch_ph8<EPI_F32, 0, true, 2>(a, stream);        // bit 19: W-hi issued one phase earlier
-#endif
-                    if (a.gate) return launch_ph8<EPI_F32, 0, true, 1, 4, 4, 0, true>(a, stream);          // adaLN
-                    return launch_ph8<EPI_F32>(a, stream);
-#ifdef SAT_GEMM_EXPERIMENTS
-                case 1: return launch_ph8<EPI_F32, 1, false>(a, stream);
-                case 2: return launch_ph8<EPI_F32, 2, false>(a, stream);
-                case 3: return launch_ph8<EPI_F32, 3, false>(a, stream);
-                case 9: return launch_ph8<EPI_F32, 9>(a, stream);
-#endif
-            }
-            break;
-        case EPI_SWIGLU:
-#ifdef SAT_GEMM_EXPERIMENTS
-            if (dbg == 0 && (a.variant & 0x40000)) return launch_ph8<EPI_SWIGLU, 0, false>(a, stream);
-            if (dbg == 0 && (a.variant & 0x80000)) return launch_ph8<EPI_SWIGLU, 0, true, 2>(a, stream);
-#endif
-#ifndef SAT_OPERAND_F16          // (e4m3 operands ride in the bf16 build: sat_launch_gemm rejects f16 && fp8)
-            if (dbg == 0 && a.fp8) return launch_ph8<EPI_SWIGLU, 0, true, 1, 4, 4, 2>(a, stream);
-#endif
-            if (dbg == 0) return launch_ph8<EPI_SWIGLU>(a, stream);
-#ifdef SAT_GEMM_EXPERIMENTS
-            if (dbg == 9) return launch_ph8<EPI_SWIGLU, 9>(a, stream);
-#endif
-            break;
-        case EPI_HEADS:
-#ifndef SAT_OPERAND_F16
-            if (dbg == 0 && a.fp8) return launch_ph8<EPI_HEADS, 0, true, 1, 4, 4, 2>(a, stream);
-#endif
-            if (dbg == 0) return launch_ph8<EPI_HEADS>(a, stream);
-#ifdef SAT_GEMM_EXPERIMENTS
-            if (dbg == 9) return launch_ph8<EPI_HEADS, 9>(a, stream);
-#endif
-            break;
+        case EPI_RESID: return launch_ph8_epi<EPI_F32>(build, a, stream);
+        case EPI_SWIGLU: return launch_ph8_epi<EPI_SWIGLU>(build, a, stream);
+        case EPI_HEADS: return launch_ph8_epi<EPI_HEADS>(build, a, stream);
     }
-    sat_set_error("gemm(8-phase): epilogue %d / ablation %d not built", epi, dbg);
+    sat_set_error("gemm(8-phase): unknown epilogue %d", epi);
     return SAT_E_UNSUPPORTED;
 }

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/sat_hip.h"
+#include "gemm_tiles.h"          // host-only integer logic: cdiv / round_up, the GemmArgs::variant fields, tiles and their choice, xcd_remap (ph8_sched.h)
 
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -90,9 +91,6 @@ void sat_set_error(const char* fmt, ...);
 // per process (a second GPU in the same process would otherwise launch with the 64 KiB default and fail).  Thread-safe.
 int sat_ensure_dynamic_lds(const void* kernel, int bytes);
 int sat_device_cus();          // compute units of the current device (cached per device; 0 + sat_last_error on failure)
-
-static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // ---------------------------------------------------------------------------------------
 // device helpers
@@ -235,17 +233,6 @@ __device__ __forceinline__ void gather_channel_runs(const f32x16& a, float (&v)[
         }
 }
 
-// XCD-aware bijective remap of a linear workgroup id (guide T1): consecutive logical ids
-// land on the same XCD (hardware places block b on XCD b % 8), so neighbouring tiles share
-// one L2.  Speed only -- never correctness.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int NX = 8;
-    int xcd = bid % NX, idx = bid / NX;
-    int q = nwg / NX, r = nwg % NX;
-    int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + idx;
-}
-
 // LDS tile layout used by the MFMA kernels: rows of 64 bf16 (128 B = eight 16-B chunks);
 // chunk c of row r lives at chunk (c ^ ((r >> 1) & 7)).  With this XOR every 16-lane group
 // of a ds_read_b128 fragment read (16 distinct rows, same logical chunk) covers all 16
@@ -270,9 +257,8 @@ __device__ __forceinline__ void wait_vmcnt() {
 }
 
 // ---------------------------------------------------------------------------------------
-// internal launchers shared between translation units
+// internal launchers shared between translation units (EPI_F32 / EPI_RESID / EPI_SWIGLU / EPI_HEADS: gemm_tiles.h)
 // ---------------------------------------------------------------------------------------
-enum { EPI_F32 = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_HEADS = 3 };
 
 namespace SAT_OPNS {
 
@@ -305,7 +291,7 @@ struct GemmArgs {
     const op_t* W;     // [N,K]
     const float* bias;   // [N] or nullptr
     int M, N, K;
-    int variant;
+    int variant;         // forced tile, 8-phase switches, tile policy: the table in gemm_tiles.h
     // EPI_F32 / EPI_RESID
     float* C;            // [M,ldc]
     int ldc;
@@ -347,10 +333,8 @@ struct GemmArgs {
 
 // bf16 build: checks a.f16 and forwards fp16 work to sat_launch_gemm_f16 (the fp16 build of the same file)
 int sat_launch_gemm(int epi, const GemmArgs& a, hipStream_t stream);
-bool sat_gemm_ph8_supports(int epi, const GemmArgs& a);
-bool sat_gemm_ph8_splits(int epi, const GemmArgs& a);       // the automatic schedule would split the remainder round along K
-size_t sat_gemm_ph8_slab_bytes(int epi, int M, int N, int K);      // slab workspace that makes it do so (0: never for this shape)
-int sat_launch_gemm_ph8(int epi, const GemmArgs& a, hipStream_t stream);     // gemm_ph8.hip: the 8-wave / 8-phase 256x256 tile
+size_t sat_gemm_ph8_slab_bytes(int epi, int M, int N, int K);      // slab workspace with which the automatic schedule splits the remainder round along K (0: never for this shape)
+int sat_launch_gemm_ph8(int epi, int build, const GemmArgs& a, hipStream_t stream);     // gemm_ph8.hip: the 8-wave / 8-phase 256x256 tile, build = SatPh8Build
 // out_scales != nullptr: MXFP8 output (e4m3 bytes at `out`, E8M0 per 32 channels at out_scales [b*sq][h*2]) instead of bf16
 // q_scale: what the kernel still has to multiply in -- SAT_ATTN_QSCALE = 1/sqrt(64) * log2(e) for a plain Q, 1.0f for a Q the
 // producer already wrote pre-scaled (HeadsEpi kind bit 3): only then the single-KV-group kernel carries its softmax reference
@@ -367,16 +351,6 @@ using namespace SAT_OPNS;
 int sat_launch_gemm_f16(int epi, const void* gemm_args, hipStream_t stream);
 int sat_launch_attention_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int sq, int sk, int sq_pad,
                              int sk_pad, hipStream_t s, unsigned char* out_scales, float q_scale);
-// Tile policy of a launch: bits 24-26 of GemmArgs::variant (sat_dit_cfg.tile_policy puts them there for every GEMM of a plan; the
-// unit-level entry points leave them 0).  0 = the default (80); the others are A/B measurement switches:
-//   22: the 16-wave 2-stage 256 x 256 tile of rounds 1-2 instead of the 8-phase kernel
-//   81: the 8-phase kernel also for the fp32-output GEMMs with K < 4096        82: no two-K-group 128 x 128 tile
-#define SAT_TILE_POLICY_SHIFT 24
-static inline int sat_tile_policy_bits(int policy) { return (policy == 22 ? 1 : policy == 81 ? 2 : policy == 82 ? 3 : 0) << SAT_TILE_POLICY_SHIFT; }
-static inline int sat_wide_tile_of(int variant) {
-    const int p = (variant >> SAT_TILE_POLICY_SHIFT) & 7;
-    return p == 1 ? 22 : p == 2 ? 81 : p == 3 ? 82 : 80;
-}
 
 // f16 (last argument of the launchers below): the 16-bit output is IEEE fp16 (saturating) instead of bf16
 int sat_launch_layernorm(const float* x, const float* gamma, const float* beta, op_t* y, int m, int d, hipStream_t s, int f16 = 0);

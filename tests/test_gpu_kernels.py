@@ -50,10 +50,9 @@ def test_cast_bf16(dev, fmt):
     assert torch.equal(y.cpu(), x.clamp(-65504.0, 65504.0).to(fmt.dtype) if fmt.f16 else x.to(fmt.dtype))
 
 
-# the shipped tile configurations (gemm_bf16.hip: launch_epi); 0 = the launcher's own choice
-# 80: the 256x256 tile on 8 waves with the 8-phase schedule (gemm_ph8.hip) -- what variant 0 picks whenever it picks that tile
-# 80 | 0x10000 (fp32 output only): the same with the remainder round split along K -- slabs in caller-supplied workspace + ph8_reduce_f32_kernel --
-# forced here, the launcher only splits long reductions behind a whole round; goes through the *_ws entry points
+# the shipped tile configurations (ids and variant bits: the tables in csrc/gemm_tiles.h); 0 = the launcher's own choice
+# 80 | 0x10000 (SAT_VARIANT_SPLIT_FORCE, fp32 output only): the 8-phase kernel with the remainder round split along K, forced here -- the
+# launcher only splits long reductions behind a whole round; goes through the *_ws entry points
 GEMM_VARIANTS = [1, 5, 15, 16, 22, 30, 80]
 SPLIT = 80 | 0x10000
 # 44: tile 15 with a 4-stage ring (fp32 output, long K); 49: the 128 x 128 tile on two K-groups of 64 x 64 waves (what variant 0 picks for
