@@ -117,7 +117,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 // LayerNorm -> fp32 (one wave per row, any d % 4 == 0; optional adaLN modulation)
 __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ y, int m, int d,
-                                                            const float* __restrict__ sc, const float* __restrict__ sh, int rps, int ld) {
+                                                            const float* __restrict__ sc, const float* __restrict__ sh, int rps, int ld,
+                                                            float eps) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= m) return;
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
         const float a = xr[i] - mean;
         q += a * a;
     }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + eps);
     const float* scr = sc ? sc + (size_t)(row / rps) * ld : nullptr;
     const float* shr = sc ? sh + (size_t)(row / rps) * ld : nullptr;
     for (int i = lane; i < d; i += 64) {
@@ -253,9 +254,9 @@ int sat_launch_gemm_f32(const float* A, const float* W, const float* bias, float
 }
 
 int sat_launch_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int m, int d, const float* sc,
-                             const float* sh, int rps, int ld, hipStream_t s) {
+                             const float* sh, int rps, int ld, hipStream_t s, float eps) {
     SAT_CHECK_ARG(x && gamma && y && m > 0 && d > 0, SAT_E_INVALID, "layernorm_f32: bad args");
-    hipLaunchKernelGGL(layernorm_f32_kernel, dim3(cdiv(m, 4)), dim3(256), 0, s, x, gamma, beta, y, m, d, sc, sh, rps > 0 ? rps : 1, ld);
+    hipLaunchKernelGGL(layernorm_f32_kernel, dim3(cdiv(m, 4)), dim3(256), 0, s, x, gamma, beta, y, m, d, sc, sh, rps > 0 ? rps : 1, ld, eps);
     SAT_LAUNCH_CHECK();
     return 0;
 }

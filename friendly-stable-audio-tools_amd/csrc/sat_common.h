@@ -367,7 +367,7 @@ int sat_launch_quant_mx_rows(const float* x, void* out8, void* scales_e8m0, int 
 int sat_launch_gemm_f32(const float* A, const float* W, const float* bias, float* C, int M, int N, int K, int ldc, int accumulate,
                         const float* gate, int gate_rows, int gate_ld, hipStream_t s);
 int sat_launch_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int m, int d, const float* sc,
-                             const float* sh, int rps, int ld, hipStream_t s);
+                             const float* sh, int rps, int ld, hipStream_t s, float eps = 1e-5f);
 int sat_launch_split_heads_f32(const float* src, float* d0, float* d1, float* d2, int M, int S, int parts, int H, int rope_mask,
                                const float* rope_cos, const float* rope_sin, hipStream_t s);
 int sat_launch_swiglu_f32(const float* hg, float* h, int64_t M, int inner, hipStream_t s);

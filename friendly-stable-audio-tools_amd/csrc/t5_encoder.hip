@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "enc_attention.h"
 #include "sat_common.h"
 
 namespace {
@@ -59,62 +60,6 @@ __global__ void t5_position_bias_kernel(const float* __restrict__ relb, const in
     if (i >= H * n) return;
     const int h = i / n, d = i - h * n;
     pb[i] = relb[(size_t)bucket[d] * H + h];
-}
-
-// One wave per (query, head, sequence).  qkv [B*L][3*inner] (q | k | v), out [B*L][inner].  Keys beyond the attention mask get
-// finfo.min added, exactly as the reference model does (so an all-padding row degenerates to the same uniform average).
-constexpr int T5_MAX_KEYS_PER_LANE = 8;      // L <= 512
-__global__ __launch_bounds__(64) void t5_attention_kernel(const float* __restrict__ qkv, const float* __restrict__ pb, const int* __restrict__ mask,
-                                                          float* __restrict__ out, int L, int H, int dkv) {
-    extern __shared__ float t5_sm[];          // q [dkv] then p [L]
-    float* sq = t5_sm;
-    float* sp = t5_sm + dkv;
-    const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int lane = threadIdx.x;
-    const int inner = H * dkv, ld = 3 * inner;
-    const float* base = qkv + (size_t)b * L * ld;
-    for (int d = lane; d < dkv; d += 64) sq[d] = base[(size_t)i * ld + h * dkv + d];
-    __syncthreads();
-    float sc[T5_MAX_KEYS_PER_LANE];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < T5_MAX_KEYS_PER_LANE; ++u) {
-        const int j = lane + u * 64;
-        sc[u] = -INFINITY;
-        if (j < L) {
-            const float4* kr = reinterpret_cast<const float4*>(base + (size_t)j * ld + inner + h * dkv);
-            float s = 0.f;
-            for (int d4 = 0; d4 < dkv / 4; ++d4) {
-                const float4 kv = kr[d4];
-                const float4 qv = reinterpret_cast<const float4*>(sq)[d4];
-                s += (qv.x * kv.x + qv.y * kv.y) + (qv.z * kv.z + qv.w * kv.w);
-            }
-            s += pb[(size_t)h * (2 * L - 1) + (j - i + L - 1)];
-            if (!mask[(size_t)b * L + j]) s += -3.4028234663852886e38f;
-            sc[u] = s;
-            mx = fmaxf(mx, s);
-        }
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int u = 0; u < T5_MAX_KEYS_PER_LANE; ++u) {
-        const int j = lane + u * 64;
-        if (j < L) {
-            const float p = expf(sc[u] - mx);
-            sp[j] = p;
-            sum += p;
-        }
-    }
-    sum = wave_sum(sum);
-    __syncthreads();
-    const float inv = 1.0f / sum;
-    for (int d = lane; d < dkv; d += 64) {
-        const float* vc = base + 2 * inner + h * dkv + d;
-        float o = 0.f;
-        for (int j = 0; j < L; ++j) o += sp[j] * vc[(size_t)j * ld];
-        out[((size_t)b * L + i) * inner + h * dkv + d] = o * inv;
-    }
 }
 
 // relu in place on [rows][F]  |  gated: h[r][c] = gelu_new(g[r][c]) * g[r][F + c] from the stacked wi_0 | wi_1 output [rows][2F]
@@ -319,7 +264,7 @@ extern "C" int sat_t5_encode(sat_t5_plan* p, const int32_t* input_ids_dev, const
                              int32_t l, int32_t mask_output, void* ws, size_t ws_bytes, sat_stream_t stream) {
     SAT_CHECK_ARG(p && p->finalized, SAT_E_STATE, "t5_encode: plan not finalized");
     SAT_CHECK_ARG(input_ids_dev && attention_mask_dev && out_dev && ws && b > 0 && l > 0, SAT_E_INVALID, "t5_encode: bad arguments");
-    SAT_CHECK_ARG(l <= 64 * T5_MAX_KEYS_PER_LANE, SAT_E_UNSUPPORTED, "t5_encode: sequence length %d > %d", l, 64 * T5_MAX_KEYS_PER_LANE);
+    SAT_CHECK_ARG(l <= 64 * ENC_MAX_KEYS_PER_LANE, SAT_E_UNSUPPORTED, "t5_encode: sequence length %d > %d", l, 64 * ENC_MAX_KEYS_PER_LANE);
     SAT_CHECK_ARG(((uintptr_t)ws & 255) == 0, SAT_E_INVALID, "t5_encode: workspace must be 256-byte aligned");
     const sat_t5_cfg& c = p->cfg;
     hipStream_t s = (hipStream_t)stream;
@@ -345,7 +290,8 @@ extern "C" int sat_t5_encode(sat_t5_plan* p, const int32_t* input_ids_dev, const
         hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, w.hid, L.ln1, w.nrm, M, D, c.eps);
         SAT_LAUNCH_CHECK();
         SAT_TRY(sat_launch_gemm_f32(w.nrm, L.wqkv, nullptr, w.qkv, M, 3 * I, D, 3 * I, 0, nullptr, 1, 0, s));
-        hipLaunchKernelGGL(t5_attention_kernel, dim3(l, H, b), dim3(64), att_lds, s, w.qkv, w.pb, attention_mask_dev, w.att, l, H, c.d_kv);
+        // T5Attention: no 1/sqrt(d) scale, bucketed relative-position bias
+        hipLaunchKernelGGL(enc_attention_kernel, dim3(l, H, b), dim3(64), att_lds, s, w.qkv, w.pb, attention_mask_dev, w.att, l, H, c.d_kv, 1.0f);
         SAT_LAUNCH_CHECK();
         SAT_TRY(sat_launch_gemm_f32(w.att, L.wo, nullptr, w.hid, M, D, I, D, 1, nullptr, 1, 0, s));
         hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, w.hid, L.ln2, w.nrm, M, D, c.eps);

@@ -4,9 +4,11 @@
 Same flags as the reference plus what an offline MI355X box needs:
   --model-config / --ckpt-path   instead of the Hugging Face download of --model-name
   --synthetic-weights SEED       random-init weights of the configured architecture (benchmarks)
-  --text-embeds FILE | random    T5/CLAP encoders are out of scope for this build: the "prompt" entry of the conditioning comes
-                                 from a file of precomputed embeddings; "random" (seed-from-text Gaussian [128, cond_dim]) is
-                                 accepted only with --synthetic-weights, never with a real checkpoint
+  --clap-ckpt PATH               the laion_clap checkpoint of a "clap_text" conditioner (Stable Audio 2.0), replacing the config's
+                                 relative clap_ckpt_path: with it the "prompt" is taken as TEXT and encoded on the device
+  --text-embeds FILE | random    for a "prompt" no registered conditioner serves (no T5 in the local Hugging Face cache, no CLAP
+                                 checkpoint): the entry comes from a file of precomputed embeddings; "random" (seed-from-text
+                                 Gaussian [128, cond_dim]) is accepted only with --synthetic-weights, never with a real checkpoint
 Launch with ``python -m torch.distributed.run --nproc-per-node N generate.py ...`` for N GPUs: one process per GPU,
 full replica each, prompts ``items[rank::world]``, every rank writes its own files (as the reference does).
 """
@@ -37,9 +39,13 @@ def get_args():
     p.add_argument("--ckpt-path", type=str, default=None)
     p.add_argument("--synthetic-weights", type=int, default=None, metavar="SEED")
     p.add_argument("--text-embeds", type=str, default=None,
-                   help="source of the text-encoder ('prompt') conditioning, which this build does not compute: a .pt / .safetensors file "
-                        "mapping each prompt string (or condition path) to a precomputed [tokens, cond_dim] embedding, or 'random' = "
+                   help="source of the text-encoder ('prompt') conditioning when no registered conditioner computes it (see --clap-ckpt): "
+                        "a .pt / .safetensors file mapping each prompt string (or condition path) to a precomputed [tokens, cond_dim] embedding, or 'random' = "
                         "seed-from-text Gaussian embeddings (benchmarks; only with --synthetic-weights)")
+    p.add_argument("--clap-ckpt", type=str, default=None, metavar="PATH",
+                   help="laion_clap checkpoint for the model config's 'clap_text' conditioner (overrides its clap_ckpt_path): the RoBERTa "
+                        "text branch then runs on the device and 'prompt' is read as text.  Needs the roberta-base tokenizer in the local "
+                        "Hugging Face cache")
     p.add_argument("--sampler-type", type=str, default="dpmpp-3m-sde")
     p.add_argument("--sample-steps", type=int, default=100)
     p.add_argument("--cfg-scale", type=float, default=7.0)
@@ -94,8 +100,9 @@ def text_embed_source(args, cond_dim):
                              "--synthetic-weights.  With real weights pass --text-embeds FILE (precomputed text-encoder outputs).")
         return lambda path, cond: text_embedding(str(cond["prompt"]), cond_dim)
     if src is None:
-        raise SystemExit("this build has no text encoder (T5 / CLAP need a download): pass --text-embeds FILE with the precomputed "
-                         "embedding of every prompt, or --synthetic-weights SEED for a random-weights benchmark run")
+        raise SystemExit("no text encoder is registered for 'prompt' (T5 weights are not in the local Hugging Face cache, no CLAP "
+                         "checkpoint was given with --clap-ckpt): pass --text-embeds FILE with the precomputed embedding of every "
+                         "prompt, or --synthetic-weights SEED for a random-weights benchmark run")
     if src.endswith(".safetensors"):
         from safetensors.torch import load_file
         table = load_file(src)
@@ -127,9 +134,15 @@ def main():
         model, model_config = get_pretrained_model(args.model_name)
     else:
         model_config = json.load(open(args.model_config)) if args.model_config else model_configs.stable_audio_open_1_0()
-        if args.model_config:     # text encoders are supplied as embeddings
+        if args.model_config:     # text encoders are supplied as embeddings, except a clap_text entry given its checkpoint
             cc = model_config["model"]["conditioning"]["configs"]
-            model_config["model"]["conditioning"]["configs"] = [c for c in cc if c["type"] in ("number", "int")]
+            if args.clap_ckpt and not os.path.exists(args.clap_ckpt):
+                raise SystemExit(f"--clap-ckpt: no file at {args.clap_ckpt}")
+            for c in cc:
+                if c["type"] == "clap_text" and args.clap_ckpt:
+                    c["config"]["clap_ckpt_path"] = args.clap_ckpt
+            keep = lambda c: c["type"] in ("number", "int") or (c["type"] == "clap_text" and args.clap_ckpt)
+            model_config["model"]["conditioning"]["configs"] = [c for c in cc if keep(c)]
         model = create_model_from_config(model_config)
         if args.ckpt_path:
             copy_state_dict(model, load_ckpt_state_dict(args.ckpt_path))
@@ -155,7 +168,7 @@ def main():
     missing = [k for k in model.cross_attn_cond_ids if k not in have]
     if any(k != "prompt" for k in missing):
         raise SystemExit(f"generate.py: the model consumes cross-attention conditioning {missing} that no registered conditioner produces; "
-                         f"--text-embeds only supplies the 'prompt' id (other encoders, e.g. CLAP, are outside this build)")
+                         f"--text-embeds only supplies the 'prompt' id (other encoders, e.g. CLAP audio, are outside this build)")
     needs_text = bool(missing)
     embed_of = text_embed_source(args, cond_dim) if needs_text else None
 

@@ -34,6 +34,12 @@ class SatT5Cfg(Structure):
                 ("proj_dim", c_int32), ("eps", c_float)]
 
 
+class SatRobertaCfg(Structure):
+    _fields_ = [("vocab_size", c_int32), ("hidden_size", c_int32), ("num_layers", c_int32), ("run_layers", c_int32),
+                ("num_heads", c_int32), ("intermediate_size", c_int32), ("max_positions", c_int32), ("pad_id", c_int32),
+                ("proj_dim", c_int32), ("eps", c_float)]
+
+
 class SatOobleckCfg(Structure):
     _fields_ = [("is_decoder", c_int32), ("io_channels", c_int32), ("channels", c_int32), ("latent_dim", c_int32),
                 ("n_blocks", c_int32), ("c_mults", c_int32 * 8), ("strides", c_int32 * 8), ("gemm_dtype", c_int32)]
@@ -122,6 +128,12 @@ _SIGNATURES = {
     "sat_t5_workspace_bytes": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
     "sat_t5_encode": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_t5_relative_buckets": (c_int32, [c_int32, c_int32, c_int32, c_void_p]),
+    "sat_roberta_plan_create": (c_int32, [c_void_p, c_void_p]),
+    "sat_roberta_plan_destroy": (None, [c_void_p]),
+    "sat_roberta_plan_set_tensor": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64]),
+    "sat_roberta_plan_finalize": (c_int32, [c_void_p, c_void_p]),
+    "sat_roberta_workspace_bytes": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
+    "sat_roberta_encode": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_snake_beta": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "sat_overlap_add": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "sat_number_embed": (c_int32, [c_void_p, c_int32, c_float, c_float, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),

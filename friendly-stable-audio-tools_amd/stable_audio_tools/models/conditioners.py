@@ -8,11 +8,15 @@ Counterparts of ``Conditioner`` / ``NumberConditioner`` / ``MultiConditioner`` /
 launch per call); like the rest of the package it has no CPU path.  ``T5Conditioner`` (conditioners.py:261-346) runs the T5 encoder
 stack on the C ABI as well (``sat_t5_*``, csrc/t5_encoder.hip); its weights and tokenizer are not part of a stable-audio checkpoint
 -- the reference downloads them -- so it is registered only when they are in the local Hugging Face cache (or handed over with
-``load_encoder``).  The other encoder-backed types (CLAP, phonemes, ...) and a T5 without weights are recorded in
+``load_encoder``).  ``CLAPTextConditioner`` (conditioners.py:105-193) with ``use_text_features=True`` is a RoBERTa encoder and runs
+on the C ABI too (``sat_roberta_*``, csrc/roberta_encoder.hip); it is registered when the file at ``clap_ckpt_path`` exists.  The other
+encoder-backed types (the pooled CLAP embedding, CLAP audio, phonemes, ...) and a text encoder without weights are recorded in
 ``MultiConditioner.external_ids``: the caller supplies those entries through ``conditioning_tensors=`` -- the "random T5 embeds"
 configuration of BASELINE.json.
 """
 import ctypes
+import os
+import re
 import typing as tp
 
 import torch
@@ -20,7 +24,7 @@ from torch import nn
 
 from .. import _hip
 
-# conditioner types whose tensors must come from outside (encoders this build does not ship)
+# conditioner types whose tensors must come from outside (encoders this build does not ship; "clap_text" without its checkpoint file)
 _EXTERNAL_TYPES = ("clap_text", "clap_audio", "phoneme", "lut", "pretransform", "int")
 
 
@@ -233,6 +237,240 @@ class T5Conditioner(Conditioner):
         return self.encode_ids(encoded["input_ids"], encoded["attention_mask"])
 
 
+class RobertaEncoderPlan:
+    """A finalized ``sat_roberta_plan`` on one device: ``hidden_states[run_layers]`` of a Hugging Face ``RobertaModel`` (+ an optional
+    ``proj_out``) for tokenised prompts.  ``state_dict`` holds ``RobertaModel.state_dict()`` keys; only the embeddings and the first
+    ``run_layers`` layers are uploaded."""
+
+    def __init__(self, state_dict: tp.Dict[str, torch.Tensor], shape: tp.Dict[str, tp.Any], run_layers: int, device: tp.Any,
+                 proj: tp.Optional[tp.Tuple[torch.Tensor, torch.Tensor]] = None):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _hip.SatError("the RoBERTa encoder must be on a HIP device (set_device('cuda')); there is no CPU path")
+        lib = _hip.lib()
+        self.out_dim = proj[0].shape[0] if proj is not None else shape["hidden_size"]
+        cfg = _hip.SatRobertaCfg(shape["vocab_size"], shape["hidden_size"], shape["num_layers"], run_layers, shape["num_heads"],
+                                 shape["intermediate_size"], shape["max_positions"], shape["pad_id"],
+                                 self.out_dim if proj is not None else 0, float(shape["eps"]))
+        plan = ctypes.c_void_p()
+        _hip.check(lib.sat_roberta_plan_create(ctypes.byref(cfg), ctypes.byref(plan)))
+        self.handle, self.device, self._ws = plan, dev, None
+        wanted = lambda k: k.startswith("embeddings.") or int(k.split(".")[2]) < run_layers
+        tensors = {k: v for k, v in state_dict.items() if wanted(k)}
+        if proj is not None:
+            tensors["proj_out.weight"], tensors["proj_out.bias"] = proj[0].detach(), proj[1].detach()
+        keep = []
+        try:
+            for name, t in tensors.items():
+                td = t.to(dev, torch.float32).contiguous()
+                keep.append(td)
+                _hip.check(lib.sat_roberta_plan_set_tensor(plan, name.encode(), _hip.ptr(td), td.numel()))
+            _hip.check(lib.sat_roberta_plan_finalize(plan, _hip.stream()))
+        except Exception:
+            self.close()
+            raise
+        torch.cuda.current_stream().synchronize()      # the plan copied from `keep`
+
+    def close(self):
+        if self.handle is not None:
+            _hip.lib().sat_roberta_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @torch.no_grad()
+    def encode(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+        """``[B, L]`` ids and mask -> ``[B, L, out_dim]`` fp32 (padded rows are computed, not zeroed)."""
+        dev = self.device
+        ids = input_ids.to(dev, torch.int32).contiguous()
+        mask = attention_mask.to(dev, torch.int32).contiguous()
+        b, l = ids.shape
+        lib = _hip.lib()
+        need = ctypes.c_size_t()
+        _hip.check(lib.sat_roberta_workspace_bytes(self.handle, b, l, ctypes.byref(need)))
+        if self._ws is None or self._ws.numel() < need.value:
+            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        out = torch.empty((b, l, self.out_dim), dtype=torch.float32, device=dev)
+        _hip.check(lib.sat_roberta_encode(self.handle, _hip.ptr(ids), _hip.ptr(mask), _hip.ptr(out), b, l, _hip.ptr(self._ws),
+                                          self._ws.numel(), _hip.stream()))
+        return out
+
+
+_ROBERTA_PREFIXES = ("", "text_branch.", "module.text_branch.")
+_ROBERTA_SKIP = ("embeddings.position_ids", "embeddings.token_type_ids")
+
+
+def roberta_encoder_tensors(state_dict: tp.Dict[str, torch.Tensor], config: tp.Any = None):
+    """Picks the RoBERTa encoder out of ``state_dict`` -- ``RobertaModel`` keys, bare or behind ``text_branch.`` /
+    ``module.text_branch.`` (a laion_clap checkpoint) -- and reads its sizes from the tensor shapes.  Everything else (audio branch,
+    projections, ``logit_scale_*``, ``embeddings.position_ids``, ``pooler.*``) is ignored.  Returns (tensors on the host in fp32, shape dict).
+    ``config`` (``RobertaConfig`` attributes) supplies what shapes cannot: heads (default hidden // 64), pad id (1), eps (1e-5)."""
+    prefix = next((p for p in _ROBERTA_PREFIXES if p + "embeddings.word_embeddings.weight" in state_dict), None)
+    if prefix is None:
+        raise ValueError("no RoBERTa encoder in the state dict: 'embeddings.word_embeddings.weight' not found bare, behind "
+                         "'text_branch.' or behind 'module.text_branch.'")
+    sd = {}
+    for k, v in state_dict.items():
+        if not k.startswith(prefix):
+            continue
+        k = k[len(prefix):]
+        if (k.startswith("embeddings.") and k not in _ROBERTA_SKIP) or re.match(r"encoder\.layer\.\d+\.", k):
+            sd[k] = v.detach().to("cpu", torch.float32)
+    vocab, hidden = sd["embeddings.word_embeddings.weight"].shape
+    layers = 1 + max((int(k.split(".")[2]) for k in sd if k.startswith("encoder.layer.")), default=-1)
+    if layers < 1:
+        raise ValueError("the RoBERTa state dict has no 'encoder.layer.N.' tensors")
+    inter = sd["encoder.layer.0.intermediate.dense.weight"].shape[0]
+    shape = {"vocab_size": vocab, "hidden_size": hidden, "num_layers": layers, "intermediate_size": inter,
+             "max_positions": sd["embeddings.position_embeddings.weight"].shape[0],
+             "num_heads": getattr(config, "num_attention_heads", None) or hidden // 64,
+             "pad_id": 1 if getattr(config, "pad_token_id", None) is None else config.pad_token_id,
+             "eps": getattr(config, "layer_norm_eps", None) or 1e-5}
+    want = {"embeddings.word_embeddings.weight": (vocab, hidden), "embeddings.position_embeddings.weight": (shape["max_positions"], hidden),
+            "embeddings.LayerNorm.weight": (hidden,), "embeddings.LayerNorm.bias": (hidden,)}
+    for n in range(layers):
+        pf = f"encoder.layer.{n}."
+        for lin, (o, i) in {"attention.self.query": (hidden, hidden), "attention.self.key": (hidden, hidden),
+                            "attention.self.value": (hidden, hidden), "attention.output.dense": (hidden, hidden),
+                            "intermediate.dense": (inter, hidden), "output.dense": (hidden, inter)}.items():
+            want[pf + lin + ".weight"], want[pf + lin + ".bias"] = (o, i), (o,)
+        for ln in ("attention.output.LayerNorm", "output.LayerNorm"):
+            want[pf + ln + ".weight"] = want[pf + ln + ".bias"] = (hidden,)
+    for k, shp in want.items():
+        if k not in sd:
+            raise ValueError(f"RoBERTa state dict: '{prefix}{k}' is missing")
+        if tuple(sd[k].shape) != shp:
+            raise ValueError(f"RoBERTa state dict: '{prefix}{k}' has shape {tuple(sd[k].shape)}, expected {shp}")
+    tt = sd.get("embeddings.token_type_embeddings.weight")
+    if tt is None or tt.ndim != 2 or tt.shape[1] != hidden:
+        raise ValueError(f"RoBERTa state dict: '{prefix}embeddings.token_type_embeddings.weight' must be [type_vocab_size, {hidden}]")
+    return sd, shape
+
+
+class CLAPTextConditioner(Conditioner):
+    """Prompts -> ``[B, 77, output_dim]`` per-token features of CLAP's text branch and the tokenizer's attention mask
+    (conditioners.py:105-193 with ``use_text_features=True``): tokenizer -> RoBERTa ``hidden_states[feature_layer_ix]`` -> ``proj_out``.
+    The encoder (``laion_clap``'s ``text_branch``, a ``transformers.RobertaModel``, under fp16 autocast in the reference) runs in fp32
+    on ``sat_roberta_encode``, which evaluates only the layers below ``feature_layer_ix`` and applies ``proj_out`` in the same call.
+    Padded rows are returned as computed, not zeroed, as in the reference.  As in the reference the encoder weights live outside
+    the module's state dict, which holds ``proj_out.*`` only.
+
+    The weights come from ``load_encoder`` or, lazily at the first call, from the laion_clap checkpoint at ``clap_ckpt_path``
+    (``torch.load`` -> ``["state_dict"]`` -> ``module.text_branch.*``, what laion_clap's ``load_state_dict`` does in
+    conditioners.py:131-141).  That loading path is written against the reference's usage and has NOT been run on a real
+    ``music_audioset_epoch_15_esc_90.14.pt``: none is available offline; the tests use a synthetic file of the same layout.
+
+    Refused: ``finetune=True`` (training) and ``use_text_features=False`` (the pooled 512-d embedding goes through laion_clap's
+    ``text_projection`` and normalisation, which this build cannot pin against anything; such an entry stays an external id).
+    ``audio_model_type`` / ``enable_fusion`` describe the audio branch, which the text conditioner deletes: accepted and unused."""
+
+    MAX_LENGTH = 77                # laion_clap's tokenizer call (hook.py: max_length=77)
+    TOKENIZER_NAME = "roberta-base"
+
+    def __init__(self, output_dim: int, clap_ckpt_path: str, use_text_features: bool = False, feature_layer_ix: int = -1,
+                 audio_model_type: str = "HTSAT-base", enable_fusion: bool = True, project_out: bool = False, finetune: bool = False):
+        if finetune:
+            raise NotImplementedError("CLAPTextConditioner: the HIP encoder is inference-only (finetune=True is a training option)")
+        if not use_text_features:
+            raise NotImplementedError("CLAPTextConditioner: use_text_features=False (the pooled, projected and normalised 512-d CLAP "
+                                      "embedding) is not computed by this build; pass that embedding through conditioning_tensors=")
+        super().__init__(768 if use_text_features else 512, output_dim, project_out=project_out)
+        self.clap_ckpt_path, self.use_text_features, self.feature_layer_ix = clap_ckpt_path, use_text_features, feature_layer_ix
+        self.finetune = finetune
+        self.tokenizer = None
+        self.__dict__["_enc"] = None          # (RobertaEncoderPlan, params_version of proj_out) -- not a submodule, not in state_dict
+        self.__dict__["_enc_src"] = None      # (state dict on the host, shape dict) kept to rebuild the plan after .to(device) / a weight load
+        self._device = "cpu"
+
+    # ---------------------------------------------------------------- encoder weights
+    def load_encoder(self, state_dict: tp.Dict[str, torch.Tensor], config: tp.Any = None, tokenizer: tp.Any = None) -> "CLAPTextConditioner":
+        """Hand over the text branch: ``state_dict`` with ``RobertaModel.state_dict()`` keys, bare or behind ``text_branch.`` /
+        ``module.text_branch.`` (unrelated keys are ignored); sizes are read from the shapes, ``config`` (optional, ``RobertaConfig``
+        attributes) gives heads / pad id / eps; ``tokenizer`` is a callable with the ``transformers`` tokenizer interface."""
+        sd, shape = roberta_encoder_tensors(state_dict, config)
+        if shape["hidden_size"] != self.dim:
+            raise ValueError(f"RoBERTa hidden size {shape['hidden_size']} != {self.dim}, the feature width of CLAPTextConditioner")
+        n = self.feature_layer_ix if self.feature_layer_ix >= 0 else shape["num_layers"] + 1 + self.feature_layer_ix
+        if not 0 <= n <= shape["num_layers"]:
+            raise ValueError(f"feature_layer_ix {self.feature_layer_ix} is outside the {shape['num_layers'] + 1} hidden states of the encoder")
+        self.__dict__["_enc_src"] = (sd, shape, n)
+        self._drop_plan()
+        if tokenizer is not None:
+            self.tokenizer = tokenizer
+        return self
+
+    def _load_from_ckpt(self):
+        if not (self.clap_ckpt_path and os.path.exists(self.clap_ckpt_path)):
+            raise _hip.SatError(f"CLAPTextConditioner: no CLAP checkpoint at '{self.clap_ckpt_path}'; call load_encoder(state_dict, ...) "
+                                "or pass the embeddings through conditioning_tensors=")
+        ckpt = torch.load(self.clap_ckpt_path, map_location="cpu", weights_only=True)
+        if isinstance(ckpt, dict) and "state_dict" in ckpt:
+            ckpt = ckpt["state_dict"]
+        # laion_clap strips a leading "module." (DataParallel); load_encoder accepts the key with or without it
+        self.load_encoder(ckpt)
+
+    def _load_tokenizer(self):
+        try:
+            from transformers import AutoTokenizer
+            self.tokenizer = AutoTokenizer.from_pretrained(self.TOKENIZER_NAME, local_files_only=True)
+        except Exception as e:
+            raise _hip.SatError(f"CLAPTextConditioner: the '{self.TOKENIZER_NAME}' tokenizer is not in the local Hugging Face cache "
+                                f"({type(e).__name__}) and nothing is downloaded; hand one over with load_encoder(..., tokenizer=)") from e
+
+    def _drop_plan(self):
+        enc = self.__dict__.get("_enc")
+        if enc is not None:
+            enc[0].close()
+        self.__dict__["_enc"] = None
+
+    def __del__(self):
+        try:
+            self._drop_plan()
+        except Exception:
+            pass
+
+    def _plan(self) -> RobertaEncoderPlan:
+        from . import _init
+        dev = torch.device(self._device)
+        if dev.type != "cuda":
+            raise _hip.SatError("CLAPTextConditioner must be on a HIP device (set_device('cuda')); there is no CPU path")
+        ver = _init.params_version(self)
+        enc = self.__dict__["_enc"]
+        if enc is not None and enc[0].device == dev and enc[1] == ver:
+            return enc[0]
+        self._drop_plan()
+        if self.__dict__["_enc_src"] is None:
+            self._load_from_ckpt()
+        sd, shape, n = self.__dict__["_enc_src"]
+        proj = (self.proj_out.weight, self.proj_out.bias) if isinstance(self.proj_out, nn.Linear) else None
+        plan = RobertaEncoderPlan(sd, shape, n, dev, proj)
+        self.__dict__["_enc"] = (plan, ver)
+        return plan
+
+    # ---------------------------------------------------------------- Conditioner interface
+    def set_device(self, device):
+        self.to(device)
+        self._device = str(device)
+
+    @torch.no_grad()
+    def encode_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> tp.List[torch.Tensor]:
+        """Tokenised prompts ``[B, L]`` -> [``[B, L, output_dim]`` fp32, the attention mask on the device with the dtype it came in]."""
+        plan = self._plan()
+        return [plan.encode(input_ids, attention_mask), attention_mask.to(plan.device)]
+
+    def forward(self, texts: tp.List[str]) -> tp.List[torch.Tensor]:
+        """The reference encodes ``[texts[0], ""]`` for a single prompt and drops the second row (a laion_clap work-around,
+        conditioners.py:175-178); sequences are independent here, so the one prompt is encoded alone with the same result."""
+        if self.tokenizer is None:
+            self._load_tokenizer()
+        encoded = self.tokenizer(list(texts), padding="max_length", truncation=True, max_length=self.MAX_LENGTH, return_tensors="pt")
+        return self.encode_ids(encoded["input_ids"], encoded["attention_mask"])
+
+
 class MultiConditioner(nn.Module):
     """Applies each conditioner to its entry of the per-item metadata dicts (conditioners.py:506-549)."""
 
@@ -265,8 +503,9 @@ class MultiConditioner(nn.Module):
 
 
 def create_multi_conditioner_from_conditioning_config(config: tp.Dict[str, tp.Any]) -> MultiConditioner:
-    """conditioners.py:552-599 for the conditioner types this build evaluates: "number", and "t5" when its weights are in the
-    local Hugging Face cache; the other encoder-backed types are listed in ``external_ids`` instead of being instantiated."""
+    """conditioners.py:552-599 for the conditioner types this build evaluates: "number", "t5" when its weights are in the local
+    Hugging Face cache, and "clap_text" when it asks for text features and the file at ``clap_ckpt_path`` exists; the other
+    encoder-backed types are listed in ``external_ids`` instead of being instantiated."""
     built, external = {}, []
     for entry in config["configs"]:
         kind = entry["type"]
@@ -274,6 +513,9 @@ def create_multi_conditioner_from_conditioning_config(config: tp.Dict[str, tp.An
             built[entry["id"]] = NumberConditioner(**{"output_dim": config["cond_dim"], **entry["config"]})
         elif kind == "t5" and T5Conditioner.cached_locally(entry["config"].get("t5_model_name", "t5-base")):
             built[entry["id"]] = T5Conditioner(**{"output_dim": config["cond_dim"], **entry["config"]})
+        elif (kind == "clap_text" and entry["config"].get("use_text_features", False) and not entry["config"].get("finetune", False)
+              and os.path.exists(entry["config"].get("clap_ckpt_path") or "")):
+            built[entry["id"]] = CLAPTextConditioner(**{"output_dim": config["cond_dim"], **entry["config"]})
         elif kind == "t5" or kind in _EXTERNAL_TYPES:
             external.append(entry["id"])
         else:

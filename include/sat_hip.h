@@ -510,6 +510,45 @@ int sat_t5_encode(sat_t5_plan* plan, const int32_t* input_ids_dev, const int32_t
  * [-(l-1), l-1] -> out_host[2l - 1] */
 int sat_t5_relative_buckets(int32_t l, int32_t num_buckets, int32_t max_distance, int32_t* out_host);
 
+/* ------------------------------------------------------------------------------------
+ * RoBERTa encoder stack: the text branch of CLAP, front-end of the "clap_text" conditioner.  Replaces the
+ * text_branch(input_ids, attention_mask, output_hidden_states=True)["hidden_states"][feature_layer_ix] call of
+ * CLAPTextConditioner.get_clap_features (models/conditioners.py:162-171) and the proj_out after it (:182).  The algorithm is
+ * transformers' modeling_roberta.py (BERT post-LayerNorm, absolute positions counted from the input ids, scaled attention with a
+ * key mask, exact erf GELU); fp32 throughout (the reference runs it under fp16 autocast).
+ * Tensors are named as in RobertaModel.state_dict(): "embeddings.{word,position,token_type}_embeddings.weight" (of the token-type
+ * table only row 0 is used), "embeddings.LayerNorm.{weight,bias}", and per layer N < run_layers
+ * "encoder.layer.N.attention.self.{query,key,value}.{weight,bias}", "encoder.layer.N.attention.output.{dense,LayerNorm}.{weight,bias}",
+ * "encoder.layer.N.intermediate.dense.{weight,bias}", "encoder.layer.N.output.{dense,LayerNorm}.{weight,bias}".  Layers from
+ * run_layers on and the pooler are never read.
+ * ---------------------------------------------------------------------------------- */
+typedef struct sat_roberta_plan sat_roberta_plan;
+typedef struct sat_roberta_cfg {
+    int32_t vocab_size;         /* RobertaConfig.vocab_size (50265) */
+    int32_t hidden_size;        /* 768 for roberta-base */
+    int32_t num_layers;         /* num_hidden_layers of the checkpoint (12) */
+    int32_t run_layers;         /* layers evaluated: the output is hidden_states[run_layers], 0 = the embeddings, num_layers = the last
+                                   hidden state; feature_layer_ix = -2 of roberta-base is 11 */
+    int32_t num_heads;          /* 12; head dim = hidden_size / num_heads */
+    int32_t intermediate_size;  /* 3072 */
+    int32_t max_positions;      /* max_position_embeddings (514): rows of the position table */
+    int32_t pad_id;             /* pad_token_id (1): positions are pad_id + 1, pad_id + 2, ... at non-pad tokens and pad_id at pad tokens */
+    int32_t proj_dim;           /* > 0: Conditioner.proj_out = Linear(hidden_size, proj_dim) (conditioners.py:23) applied to the output,
+                                   tensors "proj_out.weight" [proj_dim, hidden_size] / "proj_out.bias"; 0: identity */
+    float eps;                  /* layer_norm_eps (1e-5) */
+} sat_roberta_cfg;
+int sat_roberta_plan_create(const sat_roberta_cfg* cfg, sat_roberta_plan** out_plan);
+void sat_roberta_plan_destroy(sat_roberta_plan* plan);
+int sat_roberta_plan_set_tensor(sat_roberta_plan* plan, const char* name, const float* data_dev, int64_t numel);
+int sat_roberta_plan_finalize(sat_roberta_plan* plan, sat_stream_t stream);
+/* l <= max_positions - pad_id - 1 (the position table) and l <= 512, else SAT_E_UNSUPPORTED; needs no finalized plan */
+int sat_roberta_workspace_bytes(const sat_roberta_plan* plan, int32_t b, int32_t l, size_t* out_bytes);
+/* input_ids_dev / attention_mask_dev [b, l] int32 (tokenizer output) -> out_dev [b, l, proj_dim or hidden_size] fp32
+ * = proj_out(hidden_states[run_layers]).  Keys with attention_mask == 0 are excluded; padded rows are computed and NOT zeroed, as in
+ * the reference.  Allocates nothing and does not synchronise. */
+int sat_roberta_encode(sat_roberta_plan* plan, const int32_t* input_ids_dev, const int32_t* attention_mask_dev, float* out_dev,
+                       int32_t b, int32_t l, void* workspace_dev, size_t workspace_bytes, sat_stream_t stream);
+
 /* SnakeBeta (models/blocks.py:318-319): y = x + sin^2(x*exp(alpha_c)) / (exp(beta_c)+1e-9); x,y [b,c,t] fp32 */
 int sat_snake_beta(const float* x_dev, const float* alpha_dev, const float* beta_dev, float* y_dev,
                    int32_t b, int32_t c, int32_t t, sat_stream_t stream);
