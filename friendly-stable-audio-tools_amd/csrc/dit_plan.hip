@@ -3,87 +3,18 @@
 // fixed sequence of HIP kernel launches on the caller's stream.  Host-side C++ only; the
 // arithmetic lives in gemm_bf16.hip / attention.hip / layernorm.hip / dit_glue.hip.
 #include <math.h>
-#include <stdarg.h>
 #include <stddef.h>
 #include <string.h>
 
-#include <atomic>
-#include <map>
-#include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
 #include "dit_glue.h"
 #include "sat_common.h"
-
-// ------------------------------------------------------------------------------ errors
-static thread_local std::string g_last_error;
-void sat_set_error(const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-}
-extern "C" const char* sat_last_error(void) { return g_last_error.c_str(); }
-
-int sat_ensure_dynamic_lds(const void* kernel, int bytes) {
-    // Launch-path cost: one thread-local table probe (no lock, no allocation) once a (kernel, device) pair has been seen by this
-    // thread; the mutex-protected set is only consulted on a thread's first launch of a kernel on a device.
-    struct Seen { const void* k; int dev; };
-    static thread_local Seen seen[64];
-    static thread_local int n_seen = 0;
-    int dev = 0;
-    SAT_HIP(hipGetDevice(&dev));
-    for (int i = 0; i < n_seen; ++i)
-        if (seen[i].k == kernel && seen[i].dev == dev) return 0;
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> done;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!done.count({kernel, dev})) {
-            SAT_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-            done.insert({kernel, dev});
-        }
-    }
-    if (n_seen < 64) seen[n_seen++] = Seen{kernel, dev};
-    return 0;
-}
-// compute units of the current device: one attribute query per device and process (no allocation, no synchronisation); 0 on failure
-int sat_device_cus() {
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        sat_set_error("hipGetDevice failed");
-        return 0;
-    }
-    int c = (dev >= 0 && dev < 64) ? cache[dev].load(std::memory_order_relaxed) : 0;
-    if (!c) {
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0) {
-            sat_set_error("hipDeviceGetAttribute(MultiprocessorCount) failed");
-            return 0;
-        }
-        if (dev >= 0 && dev < 64) cache[dev].store(c, std::memory_order_relaxed);
-    }
-    return c;
-}
-extern "C" int sat_version(void) { return 6; }
+#include "plan_core.h"
 
 // ------------------------------------------------------------------------------ plan
 namespace {
-
-struct Arena {
-    char* base = nullptr;
-    size_t off = 0;
-    bool dry = true;
-    void* take(size_t bytes) {
-        size_t o = off;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return dry ? nullptr : base + o;
-    }
-};
 
 struct LayerW {
     float *pre_g, *pre_b, *cross_g, *cross_b, *ff_g, *ff_b;
@@ -99,11 +30,11 @@ struct LayerW {
 
 struct sat_dit_plan {
     sat_dit_cfg cfg;
-    std::map<std::string, std::pair<const float*, int64_t>> tensors;
+    TensorTable tensors;
     bool finalized = false;
     int inner = 0;          // FF inner dim
     int kvh_cross = 0;
-    char* arena = nullptr;
+    DevBuf arena;
     std::vector<LayerW> layers;
     float *ts_w, *te0_w, *te0_b, *te2_w, *te2_b;
     float *ce0_w, *ce2_w, *ge0_w, *ge2_w;
@@ -121,8 +52,7 @@ struct sat_dit_plan {
     int concat_dim = 0, prepend_dim = 0, max_prep = 0;
     float *pe0_w = nullptr, *pe2_w = nullptr;      // to_prepend_embed.0 / .2 (dit.py:160-165)
     // per-generation context (sat_dit_prepare_context)
-    char* ctx_buf = nullptr;
-    size_t ctx_cap = 0;
+    DevBuf ctx_buf;
     int ctx_bf = 0, ctx_lc = 0, ctx_lcpad = 0;
     bool has_global = false;
     int ctx_null_from = -1;         // sequences >= this index have an all-zero context (sat_dit_set_null_context_from)
@@ -132,8 +62,7 @@ struct sat_dit_plan {
     float* kc32 = nullptr;          // fp32 verification mode: [depth][bf, kvh, lc, 64]
     float* vc32 = nullptr;
     // per-generation extra conditioning (sat_dit_prepare_extra_conditioning); reset by every sat_dit_prepare_context
-    char* ext_buf = nullptr;
-    size_t ext_cap = 0;
+    DevBuf ext_buf;
     bool ext_ready = false;
     const float* ext_concat = nullptr;   // [ctx_bf, concat_dim, ext_concat_len] (a copy in ext_buf)
     int ext_concat_len = 0;
@@ -148,6 +77,7 @@ struct sat_dit_plan {
     std::vector<hipEvent_t> prof_ev;   // pairs
     long long prof_m = 0, prof_nn = 0, prof_k = 0;
     // optional diagnostics of the residual stream (sat_dit_debug): [depth][3 updates][4] floats, overwritten by every forward while enabled
+    DevBuf dbg_buf;
     float* dbg = nullptr;
 };
 static const int kProfMaxPairs = 4096;
@@ -158,39 +88,28 @@ namespace {
 // token under adaLN (P is 0 there: sat_dit_plan_set_extra_conditioning rejects adaLN + prepend)
 int seq_len(const sat_dit_plan* p, int T, int P) { return P + T + (p->cfg.adaln ? 0 : 1); }
 
-int get_tensor(sat_dit_plan* p, const std::string& name, int64_t numel, const float** out) {
-    auto it = p->tensors.find(name);
-    SAT_CHECK_ARG(it != p->tensors.end(), SAT_E_MISSING, "dit plan: tensor '%s' was never set", name.c_str());
-    SAT_CHECK_ARG(numel < 0 || it->second.second == numel, SAT_E_INVALID, "dit plan: tensor '%s' has %lld elements, expected %lld",
-                  name.c_str(), (long long)it->second.second, (long long)numel);
-    *out = it->second.first;
-    return 0;
-}
+int get_tensor(sat_dit_plan* p, const std::string& name, int64_t numel, const float** out) { return p->tensors.get("dit", name, numel, out); }
 
-int copy_f32(sat_dit_plan* p, Arena& ar, const std::string& name, int64_t numel, float** dst, hipStream_t s) {
+int copy_f32(sat_dit_plan* p, Bump& ar, const std::string& name, int64_t numel, float** dst, hipStream_t s) {
     *dst = (float*)ar.take(numel * 4);
-    if (ar.dry) return 0;
-    const float* src;
-    SAT_TRY(get_tensor(p, name, numel, &src));
-    SAT_HIP(hipMemcpyAsync(*dst, src, numel * 4, hipMemcpyDeviceToDevice, s));
-    return 0;
+    return ar.dry() ? 0 : p->tensors.copy("dit", name, numel, *dst, s);
 }
 
-int pack_w(sat_dit_plan* p, Arena& ar, const std::string& name, int n, int k, int interleave, op_t** dst, hipStream_t s) {
+int pack_w(sat_dit_plan* p, Bump& ar, const std::string& name, int n, int k, int interleave, op_t** dst, hipStream_t s) {
     *dst = (op_t*)ar.take((size_t)n * k * 2);
-    if (ar.dry) return 0;
+    if (ar.dry()) return 0;
     const float* src;
     SAT_TRY(get_tensor(p, name, (int64_t)n * k, &src));
     return sat_launch_pack_rows_bf16(src, *dst, n, k, interleave, s, p->f16);
 }
 
 // LayerNorm fold: bf16(gamma (.) W) + the two correction vectors of GemmArgs::ln_c1 / ln_c2 (bias folded into c2)
-int pack_w_ln(sat_dit_plan* p, Arena& ar, const std::string& name, const float* gamma, const float* beta, const std::string& bias_name, int n,
+int pack_w_ln(sat_dit_plan* p, Bump& ar, const std::string& name, const float* gamma, const float* beta, const std::string& bias_name, int n,
               int k, int interleave, op_t** dst, float** c1, float** c2, hipStream_t s) {
     *dst = (op_t*)ar.take((size_t)n * k * 2);
     *c1 = (float*)ar.take((size_t)n * 4);
     *c2 = (float*)ar.take((size_t)n * 4);
-    if (ar.dry) return 0;
+    if (ar.dry()) return 0;
     const float *src, *bias = nullptr;
     SAT_TRY(get_tensor(p, name, (int64_t)n * k, &src));
     if (!bias_name.empty()) SAT_TRY(get_tensor(p, bias_name, n, &bias));
@@ -198,17 +117,17 @@ int pack_w_ln(sat_dit_plan* p, Arena& ar, const std::string& name, const float* 
 }
 
 // gemm_dtype: e4m3 bytes + one scale per output channel instead of bf16
-int pack_w8(sat_dit_plan* p, Arena& ar, const std::string& name, int n, int k, int interleave, op_t** dst, float** scale,
+int pack_w8(sat_dit_plan* p, Bump& ar, const std::string& name, int n, int k, int interleave, op_t** dst, float** scale,
             hipStream_t s) {
     *dst = (op_t*)ar.take((size_t)n * k);
     *scale = (float*)ar.take((size_t)n * 4);
-    if (ar.dry) return 0;
+    if (ar.dry()) return 0;
     const float* src;
     SAT_TRY(get_tensor(p, name, (int64_t)n * k, &src));
     return sat_launch_quant_rows_fp8(src, *dst, *scale, n, k, interleave, s);
 }
 
-int build(sat_dit_plan* p, Arena& ar, hipStream_t s) {
+int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
     const sat_dit_cfg& c = p->cfg;
     const int D = c.embed_dim, C = c.io_channels, Dc = c.cond_embed_dim, Dct = c.cond_token_dim, Dg = c.global_cond_dim;
     const int inner = p->inner;
@@ -236,7 +155,7 @@ int build(sat_dit_plan* p, Arena& ar, hipStream_t s) {
     const int smax = seq_len(p, c.max_seq_len, p->max_prep);
     p->rope_cos = (float*)ar.take((size_t)smax * 16 * 4);
     p->rope_sin = (float*)ar.take((size_t)smax * 16 * 4);
-    if (!ar.dry) {
+    if (!ar.dry()) {
         const float *win, *wpre, *wout, *wpost;
         SAT_TRY(get_tensor(p, "transformer.project_in.weight", (int64_t)D * Ci, &win));
         SAT_TRY(get_tensor(p, "preprocess_conv.weight", (int64_t)Ci * Ci, &wpre));
@@ -251,10 +170,8 @@ int build(sat_dit_plan* p, Arena& ar, hipStream_t s) {
     for (int l = 0; l < c.depth; ++l) {
         LayerW& L = p->layers[l];
         const std::string pf = "transformer.layers." + std::to_string(l) + ".";
-        if (c.adaln && !ar.dry) {   // transformer.py:651-655: Sequential(SiLU, Linear(D, 6D, bias=False)) -> key "...1.weight"
-            const float* wsrc;
-            SAT_TRY(get_tensor(p, pf + "to_scale_shift_gate.1.weight", (int64_t)6 * D * D, &wsrc));
-            SAT_HIP(hipMemcpyAsync(p->ssg_w + (size_t)l * 6 * D * D, wsrc, (size_t)6 * D * D * 4, hipMemcpyDeviceToDevice, s));
+        if (c.adaln && !ar.dry()) {   // transformer.py:651-655: Sequential(SiLU, Linear(D, 6D, bias=False)) -> key "...1.weight"
+            SAT_TRY(p->tensors.copy("dit", pf + "to_scale_shift_gate.1.weight", (int64_t)6 * D * D, p->ssg_w + (size_t)l * 6 * D * D, s));
         }
         SAT_TRY(copy_f32(p, ar, pf + "pre_norm.gamma", D, &L.pre_g, s));
         SAT_TRY(copy_f32(p, ar, pf + "pre_norm.beta", D, &L.pre_b, s));
@@ -299,7 +216,7 @@ int build(sat_dit_plan* p, Arena& ar, hipStream_t s) {
                                        &L.c2_ff1, s));
         else SAT_TRY(pack_w(p, ar, pf + "ff.ff.0.proj.weight", 2 * inner, D, 1, &L.w_ff1, s));
         L.b_ff1 = (float*)ar.take((size_t)2 * inner * 4);
-        if (!ar.dry) {
+        if (!ar.dry()) {
             const float* b1;
             SAT_TRY(get_tensor(p, pf + "ff.ff.0.proj.bias", 2 * inner, &b1));
             SAT_TRY(sat_launch_pack_bias(b1, L.b_ff1, 2 * inner, 1, s));
@@ -334,53 +251,48 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     const size_t M = (size_t)bf * S;
     const int Spad = (int)round_up(S + 3, 128);
     Workspace w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* ptr = base ? base + off : nullptr;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return ptr;
-    };
-    w.X = (float*)take(M * D * 4);
+    Bump ws{base};
+    w.X = (float*)ws.take(M * D * 4);
     if (c.gemm_dtype == 2) {      // fp32 verification mode: every intermediate is fp32, q / k / v un-padded [bf, H, S, 64]
-        w.A = (op_t*)take(M * D * 4);
-        w.AO = (op_t*)take(M * D * 4);
+        w.A = (op_t*)ws.take(M * D * 4);
+        w.AO = (op_t*)ws.take(M * D * 4);
         w.qkv_bytes = M * D * 4;
-        w.Q = (op_t*)take(w.qkv_bytes);
-        w.K = (op_t*)take(w.qkv_bytes);
-        w.Vt = (op_t*)take(w.qkv_bytes);
-        w.Hh = (op_t*)take(M * (size_t)p->inner * 4);
-        w.f32_wide = (float*)take(M * (size_t)(2 * p->inner > 3 * D ? 2 * p->inner : 3 * D) * 4);     // [M, 3D] qkv / [M, 2 inner] FF-in
-        w.ff = (float*)take((size_t)bf * 256 * 4);
-        w.h1 = (float*)take((size_t)bf * D * 4);
-        w.mo = (float*)take((size_t)bf * c.io_channels * T * 4);
+        w.Q = (op_t*)ws.take(w.qkv_bytes);
+        w.K = (op_t*)ws.take(w.qkv_bytes);
+        w.Vt = (op_t*)ws.take(w.qkv_bytes);
+        w.Hh = (op_t*)ws.take(M * (size_t)p->inner * 4);
+        w.f32_wide = (float*)ws.take(M * (size_t)(2 * p->inner > 3 * D ? 2 * p->inner : 3 * D) * 4);     // [M, 3D] qkv / [M, 2 inner] FF-in
+        w.ff = (float*)ws.take((size_t)bf * 256 * 4);
+        w.h1 = (float*)ws.take((size_t)bf * D * 4);
+        w.mo = (float*)ws.take((size_t)bf * c.io_channels * T * 4);
         w.As = nullptr; w.Hs = nullptr; w.AOs = nullptr;
-        w.gsum = c.adaln ? (float*)take((size_t)bf * D * 4) : nullptr;
-        w.ssg = c.adaln ? (float*)take((size_t)bf * c.depth * 6 * D * 4) : nullptr;
-        w.total = off;
+        w.gsum = c.adaln ? (float*)ws.take((size_t)bf * D * 4) : nullptr;
+        w.ssg = c.adaln ? (float*)ws.take((size_t)bf * c.depth * 6 * D * 4) : nullptr;
+        w.total = ws.off;
         return w;
     }
-    w.A = (op_t*)take(M * D * 2);
-    w.AO = (op_t*)take(M * D * 2);
+    w.A = (op_t*)ws.take(M * D * 2);
+    w.AO = (op_t*)ws.take(M * D * 2);
     w.qkv_bytes = (size_t)bf * H * Spad * 64 * 2;
     // Q, K, Vt contiguous so that one memset clears all pads
-    w.Q = (op_t*)take(w.qkv_bytes);
-    w.K = (op_t*)take(w.qkv_bytes);
-    w.Vt = (op_t*)take(w.qkv_bytes);
-    w.Hh = (op_t*)take(M * (size_t)p->inner * 2);
-    w.ff = (float*)take((size_t)bf * 256 * 4);
-    w.h1 = (float*)take((size_t)bf * D * 4);
-    w.mo = (float*)take((size_t)bf * c.io_channels * T * 4);
-    w.As = c.gemm_dtype == 1 ? (float*)take(M * 4) : nullptr;
-    w.Hs = c.gemm_dtype == 1 ? (unsigned char*)take(M * (size_t)(p->inner / 32)) : nullptr;
-    w.AOs = c.gemm_dtype == 1 ? (unsigned char*)take(M * (size_t)(D / 32)) : nullptr;
-    w.gsum = c.adaln ? (float*)take((size_t)bf * D * 4) : nullptr;
-    w.ssg = c.adaln ? (float*)take((size_t)bf * c.depth * 6 * D * 4) : nullptr;
-    w.ln_part = p->ln_fold ? (float*)take(M * (size_t)(D / 64) * 2 * 4) : nullptr;
+    w.Q = (op_t*)ws.take(w.qkv_bytes);
+    w.K = (op_t*)ws.take(w.qkv_bytes);
+    w.Vt = (op_t*)ws.take(w.qkv_bytes);
+    w.Hh = (op_t*)ws.take(M * (size_t)p->inner * 2);
+    w.ff = (float*)ws.take((size_t)bf * 256 * 4);
+    w.h1 = (float*)ws.take((size_t)bf * D * 4);
+    w.mo = (float*)ws.take((size_t)bf * c.io_channels * T * 4);
+    w.As = c.gemm_dtype == 1 ? (float*)ws.take(M * 4) : nullptr;
+    w.Hs = c.gemm_dtype == 1 ? (unsigned char*)ws.take(M * (size_t)(p->inner / 32)) : nullptr;
+    w.AOs = c.gemm_dtype == 1 ? (unsigned char*)ws.take(M * (size_t)(D / 32)) : nullptr;
+    w.gsum = c.adaln ? (float*)ws.take((size_t)bf * D * 4) : nullptr;
+    w.ssg = c.adaln ? (float*)ws.take((size_t)bf * c.depth * 6 * D * 4) : nullptr;
+    w.ln_part = p->ln_fold ? (float*)ws.take(M * (size_t)(D / 64) * 2 * 4) : nullptr;
     // FF-out (K = inner) is the one fp32-output GEMM with a reduction long enough for the 8-phase kernel's K-split of the remainder
     // round (SA-2.0 shape): its slabs live here, per workspace = per caller and stream
     w.slab_bytes = (c.gemm_dtype == 0 || c.gemm_dtype == 3) ? sat_gemm_ph8_slab_bytes(EPI_RESID, (int)M, D, p->inner) : 0;
-    w.slab = w.slab_bytes ? (float*)take(w.slab_bytes) : nullptr;
-    w.total = off;
+    w.slab = w.slab_bytes ? (float*)ws.take(w.slab_bytes) : nullptr;
+    w.total = ws.off;
     return w;
 }
 
@@ -635,47 +547,27 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
 
 extern "C" void sat_dit_plan_destroy(sat_dit_plan* p) {
     if (!p) return;
-    if (p->arena) (void)hipFree(p->arena);
-    if (p->ctx_buf) (void)hipFree(p->ctx_buf);
-    if (p->ext_buf) (void)hipFree(p->ext_buf);
-    if (p->dbg) (void)hipFree(p->dbg);
     for (hipEvent_t e : p->prof_ev) (void)hipEventDestroy(e);
     delete p;
 }
 
 extern "C" int sat_dit_plan_set_tensor(sat_dit_plan* p, const char* name, const float* data_dev, int64_t numel) {
-    SAT_CHECK_ARG(p && name && data_dev && numel > 0, SAT_E_INVALID, "dit_plan_set_tensor: bad argument");
-    p->tensors[name] = {data_dev, numel};
-    return 0;
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "dit_plan_set_tensor: bad argument");
+    return p->tensors.set("dit", name, data_dev, numel);
 }
 
 extern "C" int sat_dit_plan_finalize(sat_dit_plan* p, sat_stream_t stream) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "dit_plan_finalize: null plan");
     hipStream_t s = (hipStream_t)stream;
     const int D = p->cfg.embed_dim;
-    auto it = p->tensors.find("transformer.layers.0.ff.ff.0.proj.weight");
-    SAT_CHECK_ARG(it != p->tensors.end(), SAT_E_MISSING, "dit plan: tensor 'transformer.layers.0.ff.ff.0.proj.weight' was never set");
+    auto it = p->tensors.m.find("transformer.layers.0.ff.ff.0.proj.weight");
+    SAT_CHECK_ARG(it != p->tensors.m.end(), SAT_E_MISSING, "dit plan: tensor 'transformer.layers.0.ff.ff.0.proj.weight' was never set");
     SAT_CHECK_ARG(it->second.second % (2 * (int64_t)D) == 0, SAT_E_INVALID, "dit plan: FF weight size not divisible by 2*embed_dim");
     p->inner = (int)(it->second.second / (2 * (int64_t)D));
     SAT_CHECK_ARG(p->inner % 64 == 0, SAT_E_UNSUPPORTED, "dit plan: FF inner dim %d must be a multiple of 64", p->inner);
     SAT_CHECK_ARG(p->cfg.gemm_dtype != 1 || p->inner % 128 == 0, SAT_E_UNSUPPORTED, "dit plan: gemm_dtype needs an FF inner dim that is a multiple of 128");
-    if (p->arena) {
-        (void)hipFree(p->arena);
-        p->arena = nullptr;
-    }
-    p->finalized = false;
     p->wsq_bf = p->wsq_t = -1;
-    Arena dry;
-    SAT_TRY(build(p, dry, s));
-    SAT_HIP(hipMalloc((void**)&p->arena, dry.off));
-    Arena real;
-    real.base = p->arena;
-    real.dry = false;
-    SAT_TRY(build(p, real, s));
-    SAT_HIP(hipStreamSynchronize(s));   // the caller may free its fp32 tensors once this returns
-    p->tensors.clear();
-    p->finalized = true;
-    return 0;
+    return plan_finalize(p, s, [&](Bump& ar) { return build(p, ar, s); });
 }
 
 extern "C" int sat_dit_workspace_bytes(const sat_dit_plan* p, int32_t bf, int32_t t_len, size_t* out_bytes) {
@@ -712,45 +604,34 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
     const int lcpad = cross ? (int)round_up(lc + 3, 64) : 0;
     const int R = bf * lc;
     // layout of the context buffer
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return o;
-    };
-    const size_t o_ge = take((size_t)bf * D * 4);
-    const size_t o_gh = take((size_t)bf * D * 4);
-    const size_t o_ch = cross ? take((size_t)R * Dc * 4) : 0;
-    const size_t o_ce = cross ? take((size_t)R * Dc * 2) : 0;
+    Bump lay;
+    const size_t o_ge = lay.take_off((size_t)bf * D * 4);
+    const size_t o_gh = lay.take_off((size_t)bf * D * 4);
+    const size_t o_ch = cross ? lay.take_off((size_t)R * Dc * 4) : 0;
+    const size_t o_ce = cross ? lay.take_off((size_t)R * Dc * 2) : 0;
     const bool f32 = c.gemm_dtype == 2;
     const size_t kv_elems = cross ? (size_t)c.depth * bf * p->kvh_cross * (f32 ? lc : lcpad) * 64 : 0;
-    const size_t o_kc = take(kv_elems * (f32 ? 4 : 2));
-    const size_t o_vc = take(kv_elems * (f32 ? 4 : 2));
-    const size_t o_kv32 = (cross && f32) ? take((size_t)R * 2 * Dc * 4) : 0;
-    const size_t o_ce32 = (cross && f32) ? take((size_t)R * Dc * 4) : 0;
-    if (off > p->ctx_cap) {
-        SAT_HIP(hipStreamSynchronize(s));
-        if (p->ctx_buf) SAT_HIP(hipFree(p->ctx_buf));
-        p->ctx_buf = nullptr;
-        p->ctx_cap = 0;
-        SAT_HIP(hipMalloc((void**)&p->ctx_buf, off));
-        p->ctx_cap = off;
-    }
-    p->ge = (float*)(p->ctx_buf + o_ge);
-    float* gh = (float*)(p->ctx_buf + o_gh);
-    p->kc = (op_t*)(p->ctx_buf + o_kc);
-    p->vct = (op_t*)(p->ctx_buf + o_vc);
+    const size_t o_kc = lay.take_off(kv_elems * (f32 ? 4 : 2));
+    const size_t o_vc = lay.take_off(kv_elems * (f32 ? 4 : 2));
+    const size_t o_kv32 = (cross && f32) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;
+    const size_t o_ce32 = (cross && f32) ? lay.take_off((size_t)R * Dc * 4) : 0;
+    if (lay.off > p->ctx_buf.cap) SAT_HIP(hipStreamSynchronize(s));      // launches of the previous generation may still read the old buffer
+    SAT_TRY(p->ctx_buf.reserve(lay.off));
+    p->ge = (float*)(p->ctx_buf.ptr + o_ge);
+    float* gh = (float*)(p->ctx_buf.ptr + o_gh);
+    p->kc = (op_t*)(p->ctx_buf.ptr + o_kc);
+    p->vct = (op_t*)(p->ctx_buf.ptr + o_vc);
     p->has_global = global_cond != nullptr;
     if (global_cond) {   // dit.py:154
         SAT_TRY(glue_small_linear(global_cond, Dg, p->ge0_w, nullptr, nullptr, 0, gh, D, bf, D, Dg, 1, 0, s));
         SAT_TRY(glue_small_linear(gh, D, p->ge2_w, nullptr, nullptr, 0, p->ge, D, bf, D, D, 0, 0, s));
     }
     if (cross && f32) {   // fp32 verification mode: fp32 context embedding, fp32 K / V [bf, kvh, lc, 64] per layer
-        float* ch = (float*)(p->ctx_buf + o_ch);
-        float* ce32 = (float*)(p->ctx_buf + o_ce32);
-        float* kv32 = (float*)(p->ctx_buf + o_kv32);
-        p->kc32 = (float*)(p->ctx_buf + o_kc);
-        p->vc32 = (float*)(p->ctx_buf + o_vc);
+        float* ch = (float*)(p->ctx_buf.ptr + o_ch);
+        float* ce32 = (float*)(p->ctx_buf.ptr + o_ce32);
+        float* kv32 = (float*)(p->ctx_buf.ptr + o_kv32);
+        p->kc32 = (float*)(p->ctx_buf.ptr + o_kc);
+        p->vc32 = (float*)(p->ctx_buf.ptr + o_vc);
         SAT_TRY(glue_small_linear(cond, Dct, p->ce0_w, nullptr, nullptr, 0, ch, Dc, R, Dc, Dct, 1, 0, s));
         SAT_TRY(glue_small_linear(ch, Dc, p->ce2_w, nullptr, nullptr, 0, ce32, Dc, R, Dc, Dc, 0, 0, s));
         const size_t per_layer = (size_t)bf * p->kvh_cross * lc * 64;
@@ -760,8 +641,8 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
                                                nullptr, s));
         }
     } else if (cross) {   // dit.py:150 then per-layer to_kv (transformer.py:420-427)
-        float* ch = (float*)(p->ctx_buf + o_ch);
-        op_t* ce = (op_t*)(p->ctx_buf + o_ce);
+        float* ch = (float*)(p->ctx_buf.ptr + o_ch);
+        op_t* ce = (op_t*)(p->ctx_buf.ptr + o_ce);
         SAT_TRY(glue_small_linear(cond, Dct, p->ce0_w, nullptr, nullptr, 0, ch, Dc, R, Dc, Dct, 1, 0, s));
         SAT_TRY(glue_small_linear(ch, Dc, p->ce2_w, nullptr, nullptr, 0, ce, Dc, R, Dc, Dc, 0, p->f16 ? 2 : 1, s));
         SAT_HIP(hipMemsetAsync(p->kc, 0, kv_elems * 2, s));
@@ -837,32 +718,21 @@ extern "C" int sat_dit_prepare_extra_conditioning(sat_dit_plan* p, const float* 
                   "dit_prepare_extra_conditioning: prepend_len %d not in 1..max_prepend_len %d", prepend_len, p->max_prep);
     const size_t n_cat = Cc ? (size_t)bf * Cc * concat_len : 0;
     const size_t n_prep = prepend ? (size_t)bf * prepend_len * D : 0;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return o;
-    };
-    const size_t o_cat = take(n_cat * 4), o_h = take(n_prep * 4), o_prep = take(n_prep * 4);
-    if (off > p->ext_cap) {
-        SAT_HIP(hipStreamSynchronize(s));
-        if (p->ext_buf) SAT_HIP(hipFree(p->ext_buf));
-        p->ext_buf = nullptr;
-        p->ext_cap = 0;
-        SAT_HIP(hipMalloc((void**)&p->ext_buf, off));
-        p->ext_cap = off;
-    }
+    Bump lay;
+    const size_t o_cat = lay.take_off(n_cat * 4), o_h = lay.take_off(n_prep * 4), o_prep = lay.take_off(n_prep * 4);
+    if (lay.off > p->ext_buf.cap) SAT_HIP(hipStreamSynchronize(s));
+    SAT_TRY(p->ext_buf.reserve(lay.off));
     p->ext_ready = false;
-    if (Cc) SAT_HIP(hipMemcpyAsync(p->ext_buf + o_cat, concat, n_cat * 4, hipMemcpyDeviceToDevice, s));
+    if (Cc) SAT_HIP(hipMemcpyAsync(p->ext_buf.ptr + o_cat, concat, n_cat * 4, hipMemcpyDeviceToDevice, s));
     if (prepend) {   // dit.py:160-165: Linear(prepend_cond_dim, D, bias=False), SiLU, Linear(D, D, bias=False)
         const int R = bf * prepend_len;
-        float* h = (float*)(p->ext_buf + o_h);
+        float* h = (float*)(p->ext_buf.ptr + o_h);
         SAT_TRY(glue_small_linear(prepend, p->prepend_dim, p->pe0_w, nullptr, nullptr, 0, h, D, R, D, p->prepend_dim, 1, 0, s));
-        SAT_TRY(glue_small_linear(h, D, p->pe2_w, nullptr, nullptr, 0, p->ext_buf + o_prep, D, R, D, D, 0, 0, s));
+        SAT_TRY(glue_small_linear(h, D, p->pe2_w, nullptr, nullptr, 0, p->ext_buf.ptr + o_prep, D, R, D, D, 0, 0, s));
     }
-    p->ext_concat = Cc ? (const float*)(p->ext_buf + o_cat) : nullptr;
+    p->ext_concat = Cc ? (const float*)(p->ext_buf.ptr + o_cat) : nullptr;
     p->ext_concat_len = Cc ? concat_len : 0;
-    p->ext_prep = prepend ? (float*)(p->ext_buf + o_prep) : nullptr;
+    p->ext_prep = prepend ? (float*)(p->ext_buf.ptr + o_prep) : nullptr;
     p->ctx_prep = prepend ? prepend_len : 0;
     p->ext_ready = Cc > 0 || prepend;       // neither: the plain path (P = 0), as after sat_dit_prepare_context
     return 0;
@@ -922,11 +792,12 @@ extern "C" int sat_dit_debug(sat_dit_plan* p, int32_t enable) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "dit_debug: null plan");
     if (enable && !p->dbg) {
         SAT_CHECK_ARG(p->cfg.gemm_dtype != 2, SAT_E_UNSUPPORTED, "dit_debug: the fp32 verification mode keeps no 16-bit image of the residual stream");
-        SAT_HIP(hipMalloc((void**)&p->dbg, (size_t)p->cfg.depth * 3 * 4 * sizeof(float)));
+        SAT_TRY(p->dbg_buf.reserve((size_t)p->cfg.depth * 3 * 4 * sizeof(float)));
+        p->dbg = (float*)p->dbg_buf.ptr;
         SAT_HIP(hipMemset(p->dbg, 0, (size_t)p->cfg.depth * 3 * 4 * sizeof(float)));
     } else if (!enable && p->dbg) {
         SAT_HIP(hipDeviceSynchronize());
-        SAT_HIP(hipFree(p->dbg));
+        p->dbg_buf.release();
         p->dbg = nullptr;
     }
     return 0;
@@ -947,294 +818,4 @@ extern "C" int sat_cfg_combine(const float* model_out_dev, float* out_dev, int32
     SAT_CHECK_ARG(model_out_dev && out_dev && b > 0 && c > 1 && t > 0, SAT_E_INVALID, "cfg_combine: bad arguments");
     // denoise form with c_out = 1, c_skip = 0 (x is not read when c_skip == 0, but must be a valid pointer)
     return glue_cfg_denoise(model_out_dev, model_out_dev, out_dev, b, c, t, 1, cfg_scale, scale_phi, 1.0f, 0.0f, (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------------ unit-level entry points
-static int layernorm_bf16_impl(int f16, const float* x, const float* gamma, const float* beta, void* y, int32_t m, int32_t d,
-                                  sat_stream_t stream) {
-    return sat_launch_layernorm(x, gamma, beta, (op_t*)y, m, d, (hipStream_t)stream, f16);
-}
-extern "C" int sat_layernorm_bf16(const float* x, const float* gamma, const float* beta, void* y, int32_t m, int32_t d,
-                                  sat_stream_t stream) {
-    return layernorm_bf16_impl(0, x, gamma, beta, y, m, d, stream);
-}
-extern "C" int sat_layernorm_f16(const float* x, const float* gamma, const float* beta, void* y, int32_t m, int32_t d,
-                                  sat_stream_t stream) {
-    return layernorm_bf16_impl(1, x, gamma, beta, y, m, d, stream);
-}
-
-static int cast_bf16_impl(int f16, const float* x, void* y, int64_t n, sat_stream_t stream) {
-    return sat_launch_cast_bf16(x, (op_t*)y, n, (hipStream_t)stream, f16);
-}
-extern "C" int sat_cast_bf16(const float* x, void* y, int64_t n, sat_stream_t stream) {
-    return cast_bf16_impl(0, x, y, n, stream);
-}
-extern "C" int sat_cast_f16(const float* x, void* y, int64_t n, sat_stream_t stream) {
-    return cast_bf16_impl(1, x, y, n, stream);
-}
-
-static int gemm_bf16_f32_impl(int f16, const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
-                              int32_t accumulate, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
-    SAT_CHECK_ARG(c, SAT_E_INVALID, "gemm: null output");
-    GemmArgs g{};
-    g.f16 = f16;
-    g.A = (const op_t*)a; g.W = (const op_t*)w; g.bias = bias; g.M = m; g.N = n; g.K = k;
-    g.C = c; g.ldc = n; g.accumulate = accumulate; g.variant = variant;
-    g.slab = (float*)ws; g.slab_bytes = ws ? ws_bytes : 0;
-    return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
-}
-extern "C" int sat_gemm_bf16_f32(const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
-                                 int32_t accumulate, int32_t variant, sat_stream_t stream) {
-    return gemm_bf16_f32_impl(0, a, w, bias, c, m, n, k, accumulate, variant, nullptr, 0, stream);
-}
-extern "C" int sat_gemm_f16_f32(const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
-                                int32_t accumulate, int32_t variant, sat_stream_t stream) {
-    return gemm_bf16_f32_impl(1, a, w, bias, c, m, n, k, accumulate, variant, nullptr, 0, stream);
-}
-extern "C" int sat_gemm_bf16_f32_ws(const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
-                                    int32_t accumulate, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
-    return gemm_bf16_f32_impl(0, a, w, bias, c, m, n, k, accumulate, variant, ws, ws_bytes, stream);
-}
-extern "C" int sat_gemm_f16_f32_ws(const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
-                                   int32_t accumulate, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
-    return gemm_bf16_f32_impl(1, a, w, bias, c, m, n, k, accumulate, variant, ws, ws_bytes, stream);
-}
-extern "C" int sat_gemm_f32_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t variant, size_t* out_bytes) {
-    SAT_CHECK_ARG(out_bytes && m > 0 && n > 0 && k > 0, SAT_E_INVALID, "gemm_f32_workspace_bytes: bad argument");
-    const int cus = sat_device_cus();
-    SAT_CHECK_ARG(cus > 0, SAT_E_INVALID, "gemm_f32_workspace_bytes: no device");
-    // forced K-split (tests / measurements): one slab per workgroup; otherwise what the automatic schedule would use
-    *out_bytes = sat_variant_has(variant, SAT_VARIANT_SPLIT_FORCE) ? (size_t)cus * 65536 * sizeof(float) : sat_gemm_ph8_slab_bytes(EPI_F32, m, n, k);
-    return 0;
-}
-
-static int gemm_swiglu_bf16_impl(int f16, const void* a, const float* w_f32, const float* bias_f32, void* wpack, float* bpack,
-                                    void* h, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
-    SAT_CHECK_ARG(w_f32 && wpack && bpack && h, SAT_E_INVALID, "gemm_swiglu: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (!sat_variant_has(variant, SAT_VARIANT_PACKED)) {     // wpack / bpack already hold the packed operands of a previous call (benchmarks)
-        SAT_TRY(sat_launch_pack_rows_bf16(w_f32, (op_t*)wpack, n, k, 1, s, f16));
-        if (bias_f32) SAT_TRY(sat_launch_pack_bias(bias_f32, bpack, n, 1, s));
-    }
-    GemmArgs g{};
-    g.f16 = f16;
-    g.A = (const op_t*)a; g.W = (const op_t*)wpack; g.bias = bias_f32 ? bpack : nullptr; g.M = m; g.N = n; g.K = k;
-    g.H = (op_t*)h; g.variant = variant & ~SAT_VARIANT_PACKED;
-    return sat_launch_gemm(EPI_SWIGLU, g, s);
-}
-extern "C" int sat_gemm_swiglu_bf16(const void* a, const float* w_f32, const float* bias_f32, void* wpack, float* bpack,
-                                    void* h, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
-    return gemm_swiglu_bf16_impl(0, a, w_f32, bias_f32, wpack, bpack, h, m, n, k, variant, stream);
-}
-extern "C" int sat_gemm_swiglu_f16(const void* a, const float* w_f32, const float* bias_f32, void* wpack, float* bpack,
-                                    void* h, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
-    return gemm_swiglu_bf16_impl(1, a, w_f32, bias_f32, wpack, bpack, h, m, n, k, variant, stream);
-}
-
-static int attention_bf16_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
-                                  int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return sat_launch_attention((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, sq, sk, sq_pad,
-                                sk_pad, (hipStream_t)stream, nullptr, SAT_ATTN_QSCALE, f16);
-}
-extern "C" int sat_attention_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
-                                  int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return attention_bf16_impl(0, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
-}
-extern "C" int sat_attention_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
-                                  int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return attention_bf16_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
-}
-
-// to_q projection + cross-attention in ONE launch (what the plan runs per layer at one prompt): out [b*s, d] = attention(a wq^T, k, v)
-static int cross_attention_fused_bf16_impl(int f16, const void* a, const void* wq, const void* k, const void* vt, void* out, int32_t b, int32_t s_len,
-                                              int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream) {
-    SAT_CHECK_ARG(a && wq && k && vt && out && b > 0 && s_len > 0 && d > 0 && d % 128 == 0 && kvh > 0, SAT_E_INVALID, "cross_attention_fused: bad argument");
-    GemmArgs g{};
-    g.f16 = f16;
-    g.A = (const op_t*)a; g.W = (const op_t*)wq; g.M = b * s_len; g.N = d; g.K = d;
-    g.heads.kind[0] = 8; g.heads.qscale = SAT_ATTN_QSCALE; g.heads.parts = 1; g.heads.heads = d / 64; g.heads.S = s_len; g.heads.Spad = s_len;
-    g.heads.xa_k = (const op_t*)k; g.heads.xa_vt = (const op_t*)vt; g.heads.xa_out = (op_t*)out;
-    g.heads.xa_kvh = kvh; g.heads.xa_sk = sk; g.heads.xa_sk_pad = sk_pad;
-    return sat_launch_gemm(EPI_HEADS, g, (hipStream_t)stream);
-}
-extern "C" int sat_cross_attention_fused_bf16(const void* a, const void* wq, const void* k, const void* vt, void* out, int32_t b, int32_t s_len,
-                                              int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream) {
-    return cross_attention_fused_bf16_impl(0, a, wq, k, vt, out, b, s_len, d, kvh, sk, sk_pad, stream);
-}
-extern "C" int sat_cross_attention_fused_f16(const void* a, const void* wq, const void* k, const void* vt, void* out, int32_t b, int32_t s_len,
-                                              int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream) {
-    return cross_attention_fused_bf16_impl(1, a, wq, k, vt, out, b, s_len, d, kvh, sk, sk_pad, stream);
-}
-
-// The layout the DiT plan runs: Q pre-scaled by 1/sqrt(64) * log2(e) by its producer (the QKV / to_q GEMM epilogue)
-static int attention_prescaled_bf16_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
-                                            int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return sat_launch_attention((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, sq, sk, sq_pad,
-                                sk_pad, (hipStream_t)stream, nullptr, 1.0f, f16);
-}
-extern "C" int sat_attention_prescaled_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
-                                            int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return attention_prescaled_bf16_impl(0, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
-}
-extern "C" int sat_attention_prescaled_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
-                                            int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return attention_prescaled_bf16_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
-}
-
-static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
-                                 float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
-                                 sat_stream_t stream) {
-    SAT_CHECK_ARG(a && w && inv_freq && q && k && vt && rope_scratch, SAT_E_INVALID, "qkv_rope: null pointer");
-    SAT_CHECK_ARG(d % 64 == 0 && s_pad >= s_len + 3 && s_pad % 128 == 0, SAT_E_INVALID, "qkv_rope: bad dims (s_pad >= s + 3, %% 128)");
-    hipStream_t s = (hipStream_t)stream;
-    const int H = d / 64;
-    const size_t bytes = (size_t)b * H * s_pad * 64 * 2;
-    SAT_HIP(hipMemsetAsync(q, 0, bytes, s));
-    SAT_HIP(hipMemsetAsync(k, 0, bytes, s));
-    SAT_HIP(hipMemsetAsync(vt, 0, bytes, s));
-    float* cs = rope_scratch;
-    float* sn = rope_scratch + (size_t)s_len * 16;
-    SAT_TRY(sat_launch_rope_table(inv_freq, cs, sn, s_len, s));
-    GemmArgs g{};
-    g.f16 = f16;
-    g.A = (const op_t*)a; g.W = (const op_t*)w; g.M = b * s_len; g.N = 3 * d; g.K = d; g.variant = variant;
-    g.heads.out[0] = (op_t*)q; g.heads.out[1] = (op_t*)k; g.heads.out[2] = (op_t*)vt;
-    g.heads.kind[0] = 2; g.heads.kind[1] = 2 | 4; g.heads.kind[2] = 1 | 4;
-    g.heads.parts = 3; g.heads.heads = H; g.heads.S = s_len; g.heads.Spad = s_pad;
-    g.heads.rope_cos = cs; g.heads.rope_sin = sn;
-    return sat_launch_gemm(EPI_HEADS, g, s);
-}
-extern "C" int sat_qkv_rope_bf16(const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
-                                 float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
-                                 sat_stream_t stream) {
-    return qkv_rope_bf16_impl(0, a, w, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream);
-}
-extern "C" int sat_qkv_rope_f16(const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
-                                 float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
-                                 sat_stream_t stream) {
-    return qkv_rope_bf16_impl(1, a, w, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream);
-}
-
-// ---- LayerNorm folded into the neighbouring GEMMs (sat_dit_cfg.ln_fold), one entry per role
-static int gemm_resid_ln_bf16_impl(int f16, const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
-                                   int32_t n, int32_t k, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
-    SAT_CHECK_ARG(c && xb && ln_part, SAT_E_INVALID, "gemm_resid_ln: null output");
-    GemmArgs g{};
-    g.f16 = f16;
-    g.A = (const op_t*)a; g.W = (const op_t*)w; g.bias = bias; g.M = m; g.N = n; g.K = k;
-    g.C = c; g.ldc = n; g.accumulate = 1; g.variant = variant; g.xb = (op_t*)xb; g.ln_part_out = ln_part;
-    g.slab = (float*)ws; g.slab_bytes = ws ? ws_bytes : 0;
-    return sat_launch_gemm(EPI_RESID, g, (hipStream_t)stream);
-}
-extern "C" int sat_gemm_resid_ln_bf16(const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
-                                      int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
-    return gemm_resid_ln_bf16_impl(0, a, w, bias, c, xb, ln_part, m, n, k, variant, nullptr, 0, stream);
-}
-extern "C" int sat_gemm_resid_ln_f16(const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
-                                     int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
-    return gemm_resid_ln_bf16_impl(1, a, w, bias, c, xb, ln_part, m, n, k, variant, nullptr, 0, stream);
-}
-extern "C" int sat_gemm_resid_ln_bf16_ws(const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
-                                         int32_t n, int32_t k, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
-    return gemm_resid_ln_bf16_impl(0, a, w, bias, c, xb, ln_part, m, n, k, variant, ws, ws_bytes, stream);
-}
-extern "C" int sat_gemm_resid_ln_f16_ws(const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
-                                        int32_t n, int32_t k, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
-    return gemm_resid_ln_bf16_impl(1, a, w, bias, c, xb, ln_part, m, n, k, variant, ws, ws_bytes, stream);
-}
-
-static int gemm_swiglu_ln_bf16_impl(int f16, const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
-                                       const float* bias_f32, void* wpack, float* c12, void* h, int32_t m, int32_t n, int32_t k,
-                                       int32_t variant, sat_stream_t stream) {
-    SAT_CHECK_ARG(xb && ln_part && w_f32 && gamma && beta && wpack && c12 && h, SAT_E_INVALID, "gemm_swiglu_ln: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (!sat_variant_has(variant, SAT_VARIANT_PACKED))       // wpack / c12 already hold the packed operands of a previous call (benchmarks)
-        SAT_TRY(sat_launch_pack_rows_ln(w_f32, gamma, beta, bias_f32, (op_t*)wpack, c12, c12 + n, n, k, 1, s, f16));
-    GemmArgs g{};
-    g.f16 = f16;
-    g.A = (const op_t*)xb; g.W = (const op_t*)wpack; g.M = m; g.N = n; g.K = k; g.H = (op_t*)h; g.variant = variant & ~SAT_VARIANT_PACKED;
-    g.ln_part = ln_part; g.ln_c1 = c12; g.ln_c2 = c12 + n; g.ln_eps = 1e-5f;
-    return sat_launch_gemm(EPI_SWIGLU, g, s);
-}
-extern "C" int sat_gemm_swiglu_ln_bf16(const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
-                                       const float* bias_f32, void* wpack, float* c12, void* h, int32_t m, int32_t n, int32_t k,
-                                       int32_t variant, sat_stream_t stream) {
-    return gemm_swiglu_ln_bf16_impl(0, xb, ln_part, w_f32, gamma, beta, bias_f32, wpack, c12, h, m, n, k, variant, stream);
-}
-extern "C" int sat_gemm_swiglu_ln_f16(const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
-                                       const float* bias_f32, void* wpack, float* c12, void* h, int32_t m, int32_t n, int32_t k,
-                                       int32_t variant, sat_stream_t stream) {
-    return gemm_swiglu_ln_bf16_impl(1, xb, ln_part, w_f32, gamma, beta, bias_f32, wpack, c12, h, m, n, k, variant, stream);
-}
-
-static int qkv_rope_ln_bf16_impl(int f16, const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
-                                    void* wpack, float* c12, const float* inv_freq, void* q, void* k, void* vt, float* rope_scratch,
-                                    int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream) {
-    SAT_CHECK_ARG(xb && ln_part && w_f32 && gamma && beta && wpack && c12 && inv_freq && q && k && vt && rope_scratch, SAT_E_INVALID,
-                  "qkv_rope_ln: null pointer");
-    SAT_CHECK_ARG(d % 64 == 0 && s_pad >= s_len + 3 && s_pad % 128 == 0, SAT_E_INVALID, "qkv_rope_ln: bad dims (s_pad >= s + 3, %% 128)");
-    hipStream_t s = (hipStream_t)stream;
-    const int H = d / 64;
-    const size_t bytes = (size_t)b * H * s_pad * 64 * 2;
-    float* cs = rope_scratch;
-    float* sn = rope_scratch + (size_t)s_len * 16;
-    if (!sat_variant_has(variant, SAT_VARIANT_PACKED)) {     // pads, tables and packed operands are those of a previous call (benchmarks)
-        SAT_HIP(hipMemsetAsync(q, 0, bytes, s));
-        SAT_HIP(hipMemsetAsync(k, 0, bytes, s));
-        SAT_HIP(hipMemsetAsync(vt, 0, bytes, s));
-        SAT_TRY(sat_launch_rope_table(inv_freq, cs, sn, s_len, s));
-        SAT_TRY(sat_launch_pack_rows_ln(w_f32, gamma, beta, nullptr, (op_t*)wpack, c12, c12 + 3 * d, 3 * d, d, 0, s, f16));
-    }
-    GemmArgs g{};
-    g.f16 = f16;
-    g.A = (const op_t*)xb; g.W = (const op_t*)wpack; g.M = b * s_len; g.N = 3 * d; g.K = d; g.variant = variant & ~SAT_VARIANT_PACKED;
-    g.heads.out[0] = (op_t*)q; g.heads.out[1] = (op_t*)k; g.heads.out[2] = (op_t*)vt;
-    g.heads.kind[0] = 2; g.heads.kind[1] = 2 | 4; g.heads.kind[2] = 1 | 4;
-    g.heads.parts = 3; g.heads.heads = H; g.heads.S = s_len; g.heads.Spad = s_pad;
-    g.heads.rope_cos = cs; g.heads.rope_sin = sn;
-    g.ln_part = ln_part; g.ln_c1 = c12; g.ln_c2 = c12 + 3 * d; g.ln_eps = 1e-5f;
-    return sat_launch_gemm(EPI_HEADS, g, s);
-}
-extern "C" int sat_qkv_rope_ln_bf16(const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
-                                    void* wpack, float* c12, const float* inv_freq, void* q, void* k, void* vt, float* rope_scratch,
-                                    int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream) {
-    return qkv_rope_ln_bf16_impl(0, xb, ln_part, w_f32, gamma, beta, wpack, c12, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream);
-}
-extern "C" int sat_qkv_rope_ln_f16(const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
-                                    void* wpack, float* c12, const float* inv_freq, void* q, void* k, void* vt, float* rope_scratch,
-                                    int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream) {
-    return qkv_rope_ln_bf16_impl(1, xb, ln_part, w_f32, gamma, beta, wpack, c12, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream);
-}
-
-extern "C" int sat_quant_rows_fp8(const float* x, void* out8, float* row_scale, int32_t rows, int32_t k, sat_stream_t stream) {
-    return sat_launch_quant_rows_fp8(x, out8, row_scale, rows, k, 0, (hipStream_t)stream);
-}
-
-extern "C" int sat_layernorm_fp8(const float* x, const float* gamma, const float* beta, void* y8, float* row_scale, int32_t m,
-                                 int32_t d, sat_stream_t stream) {
-    return sat_launch_layernorm_fp8(x, gamma, beta, y8, row_scale, m, d, nullptr, nullptr, 1, 0, (hipStream_t)stream);
-}
-
-extern "C" int sat_gemm_fp8_f32(const void* a8, const float* a_scale, const void* w8, const float* w_scale, const float* bias,
-                                float* c, int32_t m, int32_t n, int32_t k, int32_t accumulate, int32_t variant, sat_stream_t stream) {
-    SAT_CHECK_ARG(a8 && w8 && a_scale && w_scale && c, SAT_E_INVALID, "gemm_fp8: null pointer");
-    GemmArgs g{};
-    g.A = (const op_t*)a8; g.W = (const op_t*)w8; g.bias = bias; g.M = m; g.N = n; g.K = k; g.variant = variant & ~SAT_VARIANT_FP8_PLAIN;
-    g.C = c; g.ldc = n; g.accumulate = accumulate; g.a_scale = a_scale; g.w_scale = w_scale;
-    g.fp8 = sat_variant_has(variant, SAT_VARIANT_FP8_PLAIN) ? 1 : 2;      // the plain 32x32x16 fp8 MFMA instead of the 2x-rate scaled 32x32x64
-    return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
-}
-
-extern "C" int sat_quant_mx_rows_fp8(const float* x, void* out8, void* scales, int32_t rows, int32_t k, sat_stream_t stream) {
-    return sat_launch_quant_mx_rows(x, out8, scales, rows, k, (hipStream_t)stream);
-}
-
-extern "C" int sat_gemm_mxfp8_f32(const void* a8, const void* a_scales, const void* w8, const float* w_scale, const float* bias,
-                                  float* c, int32_t m, int32_t n, int32_t k, int32_t accumulate, int32_t variant, sat_stream_t stream) {
-    SAT_CHECK_ARG(a8 && w8 && a_scales && w_scale && c, SAT_E_INVALID, "gemm_mxfp8: null pointer");
-    SAT_CHECK_ARG(((uintptr_t)a_scales & 3) == 0, SAT_E_INVALID, "gemm_mxfp8: the scale array must be 4-byte aligned");
-    GemmArgs g{};
-    g.A = (const op_t*)a8; g.W = (const op_t*)w8; g.bias = bias; g.M = m; g.N = n; g.K = k; g.variant = sat_variant_tile(variant);
-    g.C = c; g.ldc = n; g.accumulate = accumulate; g.a_bscale = (const unsigned*)a_scales; g.w_scale = w_scale; g.fp8 = 3;
-    return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
 }

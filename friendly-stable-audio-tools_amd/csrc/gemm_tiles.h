@@ -17,12 +17,12 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 //   bits  0-11  SAT_VARIANT_CODE        read as a decimal number: code % 100 = 80 / 81 forces the 8-phase kernel (81 exp: its
 //                                       128 x 128 geometry), code / 100 = its ablation mode (1-3, 9: exp)   sat_gemm_route
 //   bit   8     SAT_VARIANT_FP8_PLAIN   sat_gemm_fp8_f32 only, stripped there: plain fp8 MFMA (GemmArgs::fp8 = 1) instead of the
-//                                       2x-rate block-scaled one (2)                                      dit_plan.hip
+//                                       2x-rate block-scaled one (2)                                      unit_entry.hip
 //   bit  12     SAT_VARIANT_EPI_UNSWAPPED   exp: force the un-swapped accumulator orientation             gemm_pipe_kernel
 //   bit  13     SAT_VARIANT_EPI_F32_TR      exp: transposed fp32 epilogue                                 gemm_pipe_kernel
 //   bit  15     SAT_VARIANT_EPI_F32_DIRECT  exp: direct dword fp32 epilogue                               gemm_pipe_kernel
 //   bit  14     SAT_VARIANT_PACKED      unit-level SwiGLU / LayerNorm-fold entry points only, stripped there: the packed operands
-//                                       are those of a previous call (benchmarks)                         dit_plan.hip
+//                                       are those of a previous call (benchmarks)                         unit_entry.hip
 //   bit  16     SAT_VARIANT_SPLIT_FORCE     8-phase: cut the remainder round along K whatever the policy says (tests)
 //   bit  17     SAT_VARIANT_SPLIT_OFF       8-phase: never                                                launch_ph8, sat_gemm_f32_workspace_bytes
 //   bit  18     SAT_VARIANT_PH8_FOUR_PHASE  exp: the four-phase main loop                                 sat_gemm_route

@@ -23,13 +23,13 @@
 #include <math.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <vector>
 
 #include <stdlib.h>
 
 #include "sat_common.h"
+#include "plan_core.h"
 
 namespace {
 
@@ -685,9 +685,9 @@ namespace SAT_OPNS {
 struct OobPlan {
     sat_oobleck_cfg cfg;          // first member: the C entry points read cfg.gemm_dtype through the opaque pointer to pick the build
     sat_oobleck_options opt;
-    std::map<std::string, std::pair<const float*, int64_t>> tensors;
+    TensorTable tensors;
     bool finalized = false;
-    char* arena = nullptr;
+    DevBuf arena;
     int ratio = 1;
     std::vector<int> chans;   // channels after each stage, decoder order or encoder order
     // decoder / encoder share the block structure
@@ -709,33 +709,15 @@ using SAT_OPNS::OobPlan;
 
 namespace {
 
-struct Arena {
-    char* base = nullptr;
-    size_t off = 0;
-    bool dry = true;
-    void* take(size_t bytes) {
-        size_t o = off;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return dry ? nullptr : base + o;
-    }
-};
+int get_tensor(OobPlan* p, const std::string& name, int64_t numel, const float** out) { return p->tensors.get("oobleck", name, numel, out); }
 
-int get_tensor(OobPlan* p, const std::string& name, int64_t numel, const float** out) {
-    auto it = p->tensors.find(name);
-    SAT_CHECK_ARG(it != p->tensors.end(), SAT_E_MISSING, "oobleck plan: tensor '%s' was never set", name.c_str());
-    SAT_CHECK_ARG(it->second.second == numel, SAT_E_INVALID, "oobleck plan: tensor '%s' has %lld elements, expected %lld", name.c_str(),
-                  (long long)it->second.second, (long long)numel);
-    *out = it->second.first;
-    return 0;
-}
-
-int make_snake(OobPlan* p, Arena& ar, const std::string& pfx, int C, Snake* sn, hipStream_t s) {
+int make_snake(OobPlan* p, Bump& ar, const std::string& pfx, int C, Snake* sn, hipStream_t s) {
     sn->act = p->opt.activation;
     if (sn->act == ACT_ELU) return 0;        // nn.ELU has no tensors: nothing to ask for
     const int Cp = pad64(C);
     sn->a = (float*)ar.take((size_t)Cp * 4);
     sn->ib = (float*)ar.take((size_t)Cp * 4);
-    if (ar.dry) return 0;
+    if (ar.dry()) return 0;
     const float *al, *be;
     SAT_TRY(get_tensor(p, pfx + "alpha", C, &al));
     SAT_TRY(get_tensor(p, pfx + "beta", C, &be));
@@ -745,19 +727,16 @@ int make_snake(OobPlan* p, Arena& ar, const std::string& pfx, int C, Snake* sn, 
 }
 
 // bias[Cp]: the tensor's C values, then zeros
-int make_bias(OobPlan* p, Arena& ar, const std::string& name, int C, float** out, hipStream_t s) {
+int make_bias(OobPlan* p, Bump& ar, const std::string& name, int C, float** out, hipStream_t s) {
     const int Cp = pad64(C);
     *out = (float*)ar.take((size_t)Cp * 4);
-    if (ar.dry) return 0;
-    const float* bsrc;
-    SAT_TRY(get_tensor(p, name, C, &bsrc));
+    if (ar.dry()) return 0;
     if (Cp > C) SAT_HIP(hipMemsetAsync(*out + C, 0, (size_t)(Cp - C) * 4, s));
-    SAT_HIP(hipMemcpyAsync(*out, bsrc, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-    return 0;
+    return p->tensors.copy("oobleck", name, C, *out, s);
 }
 
 // Conv1d weight [Cout][Cin][k]
-int make_conv(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, int k, bool has_bias, ConvW* cw,
+int make_conv(OobPlan* p, Bump& ar, const std::string& pfx, int Cin, int Cout, int k, bool has_bias, ConvW* cw,
               hipStream_t s, float** w_f32 = nullptr) {
     const int Npad = pad64(Cout), Kpad = pad64(Cin);
     cw->Cin = Kpad; cw->Cout = Npad; cw->taps = k; cw->N = Npad; cw->zero = p->zero_page;
@@ -766,7 +745,7 @@ int make_conv(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, 
     else cw->W = (op_t*)ar.take((size_t)k * Npad * Kpad * sizeof(op_t));
     cw->bias = nullptr;
     if (has_bias) SAT_TRY(make_bias(p, ar, pfx + "bias", Cout, &cw->bias, s));
-    if (ar.dry) return 0;
+    if (ar.dry()) return 0;
     const float *g, *v;
     SAT_TRY(get_tensor(p, pfx + "weight_g", Cout, &g));
     SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cout * Cin * k, &v));
@@ -784,13 +763,13 @@ int make_conv(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, 
 }
 
 // ConvTranspose1d weight [Cin][Cout][2s]
-int make_convT(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
+int make_convT(OobPlan* p, Bump& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
     const int Kp = pad64(Cin), Np = pad64(Cout);
     cw->Cin = Kp; cw->Cout = Np; cw->taps = 2; cw->N = stride * Np; cw->zero = p->zero_page;
     float* scale = (float*)ar.take((size_t)Cin * 4);
     cw->W = (op_t*)ar.take((size_t)2 * cw->N * Kp * sizeof(op_t));
     SAT_TRY(make_bias(p, ar, pfx + "bias", Cout, &cw->bias, s));
-    if (ar.dry) return 0;
+    if (ar.dry()) return 0;
     const float *g, *v;
     SAT_TRY(get_tensor(p, pfx + "weight_g", Cin, &g));
     SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cin * Cout * 2 * stride, &v));
@@ -803,13 +782,13 @@ int make_convT(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout,
 }
 
 // Upsample(nearest, s) + bias-free Conv1d weight [Cout][Cin][2s] -> the three-tap polyphase form
-int make_nearest(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
+int make_nearest(OobPlan* p, Bump& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
     const int Kp = pad64(Cin), Np = pad64(Cout);
     cw->Cin = Kp; cw->Cout = Np; cw->taps = 3; cw->N = stride * Np; cw->zero = p->zero_page;
     float* scale = (float*)ar.take((size_t)Cout * 4);
     cw->W = (op_t*)ar.take((size_t)3 * cw->N * Kp * sizeof(op_t));
     cw->bias = nullptr;
-    if (ar.dry) return 0;
+    if (ar.dry()) return 0;
     const float *g, *v;
     SAT_TRY(get_tensor(p, pfx + "weight_g", Cout, &g));
     SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cout * Cin * 2 * stride, &v));
@@ -821,7 +800,7 @@ int make_nearest(OobPlan* p, Arena& ar, const std::string& pfx, int Cin, int Cou
     return 0;
 }
 
-int make_ru(OobPlan* p, Arena& ar, const std::string& pfx, int C, OobPlan::Block& blk, int r, hipStream_t s) {
+int make_ru(OobPlan* p, Bump& ar, const std::string& pfx, int C, OobPlan::Block& blk, int r, hipStream_t s) {
     SAT_TRY(make_snake(p, ar, pfx + "layers.0.", C, &blk.ru_sn1[r], s));
     SAT_TRY(make_conv(p, ar, pfx + "layers.1.", C, C, 7, true, &blk.ru_c7[r], s));
     SAT_TRY(make_snake(p, ar, pfx + "layers.2.", C, &blk.ru_sn2[r], s));
@@ -829,12 +808,12 @@ int make_ru(OobPlan* p, Arena& ar, const std::string& pfx, int C, OobPlan::Block
     return 0;
 }
 
-int build(OobPlan* p, Arena& ar, hipStream_t s) {
+int build(OobPlan* p, Bump& ar, hipStream_t s) {
     const sat_oobleck_cfg& c = p->cfg;
     const int nb = c.n_blocks;
     p->blocks.resize(nb);
     p->zero_page = (op_t*)ar.take(256);
-    if (!ar.dry) SAT_HIP(hipMemsetAsync(p->zero_page, 0, 256, s));
+    if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->zero_page, 0, 256, s));
     if (c.is_decoder) {
         // autoencoders.py:174-191: channel list c_mults=[1]+c_mults ; blocks from deepest to shallowest
         const int ctop = c.c_mults[nb - 1] * c.channels;
@@ -988,37 +967,17 @@ int oob_plan_create(const sat_oobleck_cfg* cfg, const sat_oobleck_options* opt, 
     return 0;
 }
 
-void oob_plan_destroy(OobPlan* p) {
-    if (!p) return;
-    if (p->arena) (void)hipFree(p->arena);
-    delete p;
-}
+void oob_plan_destroy(OobPlan* p) { delete p; }
 
 int oob_plan_set_tensor(OobPlan* p, const char* name, const float* data_dev, int64_t numel) {
-    SAT_CHECK_ARG(p && name && data_dev && numel > 0, SAT_E_INVALID, "oobleck_plan_set_tensor: bad argument");
-    p->tensors[name] = {data_dev, numel};
-    return 0;
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_set_tensor: bad argument");
+    return p->tensors.set("oobleck", name, data_dev, numel);
 }
 
 int oob_plan_finalize(OobPlan* p, sat_stream_t stream) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_finalize: null plan");
     hipStream_t s = (hipStream_t)stream;
-    if (p->arena) {
-        (void)hipFree(p->arena);
-        p->arena = nullptr;
-    }
-    p->finalized = false;
-    Arena dry;
-    SAT_TRY(build(p, dry, s));
-    SAT_HIP(hipMalloc((void**)&p->arena, dry.off));
-    Arena real;
-    real.base = p->arena;
-    real.dry = false;
-    SAT_TRY(build(p, real, s));
-    SAT_HIP(hipStreamSynchronize(s));
-    p->tensors.clear();
-    p->finalized = true;
-    return 0;
+    return plan_finalize(p, s, [&](Bump& ar) { return build(p, ar, s); });
 }
 
 int oob_workspace_bytes(const OobPlan* p, int32_t b, int32_t t_len, size_t* out_bytes) {

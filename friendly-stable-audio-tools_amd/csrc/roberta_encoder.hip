@@ -17,12 +17,12 @@
 // the reference runs the encoder under fp16 autocast; fp32 is the more accurate of the two and needs no second set of kernels.
 #include <math.h>
 
-#include <map>
 #include <string>
 #include <vector>
 
 #include "enc_attention.h"
 #include "sat_common.h"
+#include "plan_core.h"
 
 namespace {
 
@@ -81,9 +81,9 @@ struct RobertaLayer {
 
 struct sat_roberta_plan {
     sat_roberta_cfg cfg;
-    std::map<std::string, std::pair<const float*, int64_t>> tensors;
+    TensorTable tensors;
     bool finalized = false;
-    char* arena = nullptr;
+    DevBuf arena;
     float *word = nullptr, *posw = nullptr, *type0 = nullptr, *emb_g = nullptr, *emb_b = nullptr;
     float *proj_w = nullptr, *proj_b = nullptr;       // Conditioner.proj_out (conditioners.py:23) when cfg.proj_dim > 0
     std::vector<RobertaLayer> layers;                 // cfg.run_layers of them
@@ -112,16 +112,11 @@ extern "C" int sat_roberta_plan_create(const sat_roberta_cfg* cfg, sat_roberta_p
     return 0;
 }
 
-extern "C" void sat_roberta_plan_destroy(sat_roberta_plan* p) {
-    if (!p) return;
-    if (p->arena) (void)hipFree(p->arena);
-    delete p;
-}
+extern "C" void sat_roberta_plan_destroy(sat_roberta_plan* p) { delete p; }
 
 extern "C" int sat_roberta_plan_set_tensor(sat_roberta_plan* p, const char* name, const float* data_dev, int64_t numel) {
-    SAT_CHECK_ARG(p && name && data_dev && numel > 0, SAT_E_INVALID, "roberta_plan_set_tensor: bad argument");
-    p->tensors[name] = {data_dev, numel};
-    return 0;
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "roberta_plan_set_tensor: bad argument");
+    return p->tensors.set("roberta", name, data_dev, numel);
 }
 
 namespace {
@@ -132,37 +127,22 @@ int roberta_max_len(const sat_roberta_cfg& c) {
     return by_table < by_kernel ? by_table : by_kernel;
 }
 
-int roberta_get(sat_roberta_plan* p, const std::string& name, int64_t numel, bool first_rows, const float** out) {
-    auto it = p->tensors.find(name);
-    SAT_CHECK_ARG(it != p->tensors.end(), SAT_E_MISSING, "roberta plan: tensor '%s' was never set", name.c_str());
-    const int64_t have = it->second.second;
-    SAT_CHECK_ARG(first_rows ? (have >= numel && have % numel == 0) : have == numel, SAT_E_INVALID,
-                  "roberta plan: tensor '%s' has %lld elements, expected %lld", name.c_str(), (long long)have, (long long)numel);
-    *out = it->second.first;
-    return 0;
-}
-
-// two passes over the same code: sizes first (base == nullptr), then copies
-int roberta_build(sat_roberta_plan* p, char* base, size_t* total, hipStream_t s) {
+// two passes over the same code (plan_finalize): sizes first (ar.dry()), then copies
+int roberta_build(sat_roberta_plan* p, Bump& ar, hipStream_t s) {
     const sat_roberta_cfg& c = p->cfg;
     const int64_t D = c.hidden_size, F = c.intermediate_size;
-    size_t off = 0;
-    auto place = [&](const std::string& name, int64_t numel, float** dst, int64_t dst_off_elems = 0, bool advance = true,
-                     bool first_rows = false) -> int {
-        float* d = base ? reinterpret_cast<float*>(base + off) : nullptr;
-        if (dst) *dst = d;
-        if (base) {
-            const float* src;
-            SAT_TRY(roberta_get(p, name, numel, first_rows, &src));
-            SAT_HIP(hipMemcpyAsync(d + dst_off_elems, src, numel * 4, hipMemcpyDeviceToDevice, s));
-        }
-        if (advance) off += (size_t)round_up((numel + dst_off_elems) * 4, 256);
-        return 0;
+    // the named tensor as part `part` of a buffer of equal parts stacked behind each other
+    auto fill = [&](const std::string& name, int64_t numel, float* dst, int part = 0, bool first_rows = false) -> int {
+        return ar.dry() ? 0 : p->tensors.copy("roberta", name, numel, dst + part * numel, s, first_rows);
+    };
+    auto place = [&](const std::string& name, int64_t numel, float** dst, bool first_rows = false) -> int {
+        *dst = (float*)ar.take((size_t)numel * 4);
+        return fill(name, numel, *dst, 0, first_rows);
     };
     SAT_TRY(place("embeddings.word_embeddings.weight", (int64_t)c.vocab_size * D, &p->word));
     SAT_TRY(place("embeddings.position_embeddings.weight", (int64_t)c.max_positions * D, &p->posw));
     // [type_vocab_size, D]; the encoder is called without token_type_ids, i.e. with zeros: row 0 only
-    SAT_TRY(place("embeddings.token_type_embeddings.weight", D, &p->type0, 0, true, true));
+    SAT_TRY(place("embeddings.token_type_embeddings.weight", D, &p->type0, true));
     SAT_TRY(place("embeddings.LayerNorm.weight", D, &p->emb_g));
     SAT_TRY(place("embeddings.LayerNorm.bias", D, &p->emb_b));
     if (c.proj_dim > 0) {
@@ -174,12 +154,13 @@ int roberta_build(sat_roberta_plan* p, char* base, size_t* total, hipStream_t s)
         RobertaLayer& L = p->layers[l];
         const std::string pf = "encoder.layer." + std::to_string(l) + ".";
         // query | key | value stacked into one [3D, D] weight and one [3D] bias: one GEMM
-        SAT_TRY(place(pf + "attention.self.query.weight", D * D, &L.wqkv, 0, false));
-        SAT_TRY(place(pf + "attention.self.key.weight", D * D, nullptr, D * D, false));
-        SAT_TRY(place(pf + "attention.self.value.weight", D * D, nullptr, 2 * D * D, true));
-        SAT_TRY(place(pf + "attention.self.query.bias", D, &L.bqkv, 0, false));
-        SAT_TRY(place(pf + "attention.self.key.bias", D, nullptr, D, false));
-        SAT_TRY(place(pf + "attention.self.value.bias", D, nullptr, 2 * D, true));
+        L.wqkv = (float*)ar.take((size_t)(3 * D * D) * 4);
+        L.bqkv = (float*)ar.take((size_t)(3 * D) * 4);
+        const char* qkv[3] = {"query", "key", "value"};
+        for (int i = 0; i < 3; ++i) {
+            SAT_TRY(fill(pf + "attention.self." + qkv[i] + ".weight", D * D, L.wqkv, i));
+            SAT_TRY(fill(pf + "attention.self." + qkv[i] + ".bias", D, L.bqkv, i));
+        }
         SAT_TRY(place(pf + "attention.output.dense.weight", D * D, &L.wo));
         SAT_TRY(place(pf + "attention.output.dense.bias", D, &L.bo));
         SAT_TRY(place(pf + "attention.output.LayerNorm.weight", D, &L.ln1g));
@@ -191,7 +172,6 @@ int roberta_build(sat_roberta_plan* p, char* base, size_t* total, hipStream_t s)
         SAT_TRY(place(pf + "output.LayerNorm.weight", D, &L.ln2g));
         SAT_TRY(place(pf + "output.LayerNorm.bias", D, &L.ln2b));
     }
-    *total = off;
     return 0;
 }
 
@@ -203,19 +183,14 @@ struct RobertaWs {
 RobertaWs roberta_carve(const sat_roberta_plan* p, int b, int l, char* base) {
     const sat_roberta_cfg& c = p->cfg;
     const size_t M = (size_t)b * l, D = c.hidden_size, F = c.intermediate_size;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = base ? base + off : nullptr;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return q;
-    };
+    Bump ws{base};
     RobertaWs w;
-    w.ha = (float*)take(M * D * 4);
-    w.hb = (float*)take(M * D * 4);
-    w.qkv = (float*)take(M * 3 * D * 4);
-    w.att = (float*)take(M * D * 4);
-    w.ff = (float*)take(M * F * 4);
-    w.total = off;
+    w.ha = (float*)ws.take(M * D * 4);
+    w.hb = (float*)ws.take(M * D * 4);
+    w.qkv = (float*)ws.take(M * 3 * D * 4);
+    w.att = (float*)ws.take(M * D * 4);
+    w.ff = (float*)ws.take(M * F * 4);
+    w.total = ws.off;
     return w;
 }
 
@@ -224,16 +199,7 @@ RobertaWs roberta_carve(const sat_roberta_plan* p, int b, int l, char* base) {
 extern "C" int sat_roberta_plan_finalize(sat_roberta_plan* p, sat_stream_t stream) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "roberta_plan_finalize: null plan");
     hipStream_t s = (hipStream_t)stream;
-    p->finalized = false;
-    size_t total = 0;
-    SAT_TRY(roberta_build(p, nullptr, &total, s));
-    if (p->arena) (void)hipFree(p->arena);
-    p->arena = nullptr;
-    SAT_HIP(hipMalloc((void**)&p->arena, total));
-    SAT_TRY(roberta_build(p, p->arena, &total, s));
-    p->tensors.clear();      // the caller's pointers are not kept
-    p->finalized = true;
-    return 0;
+    return plan_finalize(p, s, [&](Bump& ar) { return roberta_build(p, ar, s); });
 }
 
 extern "C" int sat_roberta_workspace_bytes(const sat_roberta_plan* p, int32_t b, int32_t l, size_t* out_bytes) {

@@ -18,6 +18,7 @@
 
 #include "enc_attention.h"
 #include "sat_common.h"
+#include "plan_core.h"
 
 namespace {
 
@@ -91,9 +92,9 @@ struct T5Layer {
 
 struct sat_t5_plan {
     sat_t5_cfg cfg;
-    std::map<std::string, std::pair<const float*, int64_t>> tensors;
+    TensorTable tensors;
     bool finalized = false;
-    char* arena = nullptr;
+    DevBuf arena;
     float *emb = nullptr, *relb = nullptr, *final_ln = nullptr;
     float *proj_w = nullptr, *proj_b = nullptr;       // Conditioner.proj_out (conditioners.py:23) when cfg.proj_dim > 0
     std::vector<T5Layer> layers;
@@ -138,47 +139,29 @@ extern "C" int sat_t5_plan_create(const sat_t5_cfg* cfg, sat_t5_plan** out_plan)
     return 0;
 }
 
-extern "C" void sat_t5_plan_destroy(sat_t5_plan* p) {
-    if (!p) return;
-    if (p->arena) (void)hipFree(p->arena);
-    delete p;
-}
+extern "C" void sat_t5_plan_destroy(sat_t5_plan* p) { delete p; }
 
 extern "C" int sat_t5_plan_set_tensor(sat_t5_plan* p, const char* name, const float* data_dev, int64_t numel) {
-    SAT_CHECK_ARG(p && name && data_dev && numel > 0, SAT_E_INVALID, "t5_plan_set_tensor: bad argument");
-    p->tensors[name] = {data_dev, numel};
-    return 0;
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "t5_plan_set_tensor: bad argument");
+    return p->tensors.set("t5", name, data_dev, numel);
 }
 
 namespace {
 
-int t5_get(sat_t5_plan* p, const std::string& name, int64_t numel, const float** out) {
-    auto it = p->tensors.find(name);
-    SAT_CHECK_ARG(it != p->tensors.end(), SAT_E_MISSING, "t5 plan: tensor '%s' was never set", name.c_str());
-    SAT_CHECK_ARG(it->second.second == numel, SAT_E_INVALID, "t5 plan: tensor '%s' has %lld elements, expected %lld", name.c_str(),
-                  (long long)it->second.second, (long long)numel);
-    *out = it->second.first;
-    return 0;
-}
-
-// two passes over the same code: sizes first (base == nullptr), then copies
-int t5_build(sat_t5_plan* p, char* base, size_t* total, hipStream_t s) {
+// two passes over the same code (plan_finalize): sizes first (ar.dry()), then copies
+int t5_build(sat_t5_plan* p, Bump& ar, hipStream_t s) {
     const sat_t5_cfg& c = p->cfg;
     const int64_t D = c.d_model, I = (int64_t)c.num_heads * c.d_kv, F = c.d_ff;
-    size_t off = 0;
-    auto place = [&](const std::string& name, int64_t numel, float** dst, int64_t dst_off_elems = 0, bool advance = true) -> int {
-        float* d = base ? reinterpret_cast<float*>(base + off) : nullptr;
-        if (dst) *dst = d;
-        if (base) {
-            const float* src;
-            SAT_TRY(t5_get(p, name, numel, &src));
-            SAT_HIP(hipMemcpyAsync(d + dst_off_elems, src, numel * 4, hipMemcpyDeviceToDevice, s));
-        }
-        if (advance) off += (size_t)round_up((numel + dst_off_elems) * 4, 256);
-        return 0;
+    // the named tensor as part `part` of a buffer of equal parts stacked behind each other
+    auto fill = [&](const std::string& name, int64_t numel, float* dst, int part = 0) -> int {
+        return ar.dry() ? 0 : p->tensors.copy("t5", name, numel, dst + part * numel, s);
+    };
+    auto place = [&](const std::string& name, int64_t numel, float** dst) -> int {
+        *dst = (float*)ar.take((size_t)numel * 4);
+        return fill(name, numel, *dst);
     };
     // "shared.weight" and "encoder.embed_tokens.weight" are the same tensor in a T5 checkpoint; accept either
-    const bool has_shared = p->tensors.count("shared.weight") != 0;
+    const bool has_shared = p->tensors.has("shared.weight");
     SAT_TRY(place(has_shared ? "shared.weight" : "encoder.embed_tokens.weight", (int64_t)c.vocab_size * D, &p->emb));
     SAT_TRY(place("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (int64_t)c.rel_buckets * c.num_heads, &p->relb));
     SAT_TRY(place("encoder.final_layer_norm.weight", D, &p->final_ln));
@@ -192,20 +175,21 @@ int t5_build(sat_t5_plan* p, char* base, size_t* total, hipStream_t s) {
         const std::string pf = "encoder.block." + std::to_string(l) + ".layer.";
         SAT_TRY(place(pf + "0.layer_norm.weight", D, &L.ln1));
         // q | k | v stacked into one [3I, D] weight: one GEMM
-        SAT_TRY(place(pf + "0.SelfAttention.q.weight", I * D, &L.wqkv, 0, false));
-        SAT_TRY(place(pf + "0.SelfAttention.k.weight", I * D, nullptr, I * D, false));
-        SAT_TRY(place(pf + "0.SelfAttention.v.weight", I * D, nullptr, 2 * I * D, true));
+        L.wqkv = (float*)ar.take((size_t)(3 * I * D) * 4);
+        SAT_TRY(fill(pf + "0.SelfAttention.q.weight", I * D, L.wqkv, 0));
+        SAT_TRY(fill(pf + "0.SelfAttention.k.weight", I * D, L.wqkv, 1));
+        SAT_TRY(fill(pf + "0.SelfAttention.v.weight", I * D, L.wqkv, 2));
         SAT_TRY(place(pf + "0.SelfAttention.o.weight", D * I, &L.wo));
         SAT_TRY(place(pf + "1.layer_norm.weight", D, &L.ln2));
         if (c.gated_gelu) {
-            SAT_TRY(place(pf + "1.DenseReluDense.wi_0.weight", F * D, &L.wi, 0, false));
-            SAT_TRY(place(pf + "1.DenseReluDense.wi_1.weight", F * D, nullptr, F * D, true));
+            L.wi = (float*)ar.take((size_t)(2 * F * D) * 4);
+            SAT_TRY(fill(pf + "1.DenseReluDense.wi_0.weight", F * D, L.wi, 0));
+            SAT_TRY(fill(pf + "1.DenseReluDense.wi_1.weight", F * D, L.wi, 1));
         } else {
             SAT_TRY(place(pf + "1.DenseReluDense.wi.weight", F * D, &L.wi));
         }
         SAT_TRY(place(pf + "1.DenseReluDense.wo.weight", D * F, &L.wo2));
     }
-    *total = off;
     return 0;
 }
 
@@ -218,22 +202,17 @@ struct T5Ws {
 T5Ws t5_carve(const sat_t5_plan* p, int b, int l, char* base) {
     const sat_t5_cfg& c = p->cfg;
     const size_t M = (size_t)b * l, D = c.d_model, I = (size_t)c.num_heads * c.d_kv, F = c.d_ff;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* q = base ? base + off : nullptr;
-        off += (size_t)round_up((int64_t)bytes, 256);
-        return q;
-    };
+    Bump ws{base};
     T5Ws w;
-    w.hid = (float*)take(M * D * 4);
-    w.nrm = (float*)take(M * D * 4);
-    w.qkv = (float*)take(M * 3 * I * 4);
-    w.att = (float*)take(M * I * 4);
-    w.ff = (float*)take(M * F * (c.gated_gelu ? 2 : 1) * 4);
-    w.ffh = c.gated_gelu ? (float*)take(M * F * 4) : w.ff;
-    w.pb = (float*)take((size_t)c.num_heads * (2 * l - 1) * 4);
-    w.bucket = (int*)take((size_t)(2 * l - 1) * 4);
-    w.total = off;
+    w.hid = (float*)ws.take(M * D * 4);
+    w.nrm = (float*)ws.take(M * D * 4);
+    w.qkv = (float*)ws.take(M * 3 * I * 4);
+    w.att = (float*)ws.take(M * I * 4);
+    w.ff = (float*)ws.take(M * F * (c.gated_gelu ? 2 : 1) * 4);
+    w.ffh = c.gated_gelu ? (float*)ws.take(M * F * 4) : w.ff;
+    w.pb = (float*)ws.take((size_t)c.num_heads * (2 * l - 1) * 4);
+    w.bucket = (int*)ws.take((size_t)(2 * l - 1) * 4);
+    w.total = ws.off;
     return w;
 }
 
@@ -242,16 +221,7 @@ T5Ws t5_carve(const sat_t5_plan* p, int b, int l, char* base) {
 extern "C" int sat_t5_plan_finalize(sat_t5_plan* p, sat_stream_t stream) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "t5_plan_finalize: null plan");
     hipStream_t s = (hipStream_t)stream;
-    p->finalized = false;
-    size_t total = 0;
-    SAT_TRY(t5_build(p, nullptr, &total, s));
-    if (p->arena) (void)hipFree(p->arena);
-    p->arena = nullptr;
-    SAT_HIP(hipMalloc((void**)&p->arena, total));
-    SAT_TRY(t5_build(p, p->arena, &total, s));
-    p->tensors.clear();      // the caller's pointers are not kept
-    p->finalized = true;
-    return 0;
+    return plan_finalize(p, s, [&](Bump& ar) { return t5_build(p, ar, s); });
 }
 
 extern "C" int sat_t5_workspace_bytes(const sat_t5_plan* p, int32_t b, int32_t l, size_t* out_bytes) {

@@ -1,0 +1,293 @@
+// Unit-level C entry points (include/sat_hip.h): one kernel launcher each, for tests, probes and callers that drive single
+// operations; the bf16 / fp16 pairs share an _impl.  Host code only; no kernel, nothing of the DiT plan.
+#include "sat_common.h"
+
+// ------------------------------------------------------------------------------ unit-level entry points
+static int layernorm_bf16_impl(int f16, const float* x, const float* gamma, const float* beta, void* y, int32_t m, int32_t d,
+                                  sat_stream_t stream) {
+    return sat_launch_layernorm(x, gamma, beta, (op_t*)y, m, d, (hipStream_t)stream, f16);
+}
+extern "C" int sat_layernorm_bf16(const float* x, const float* gamma, const float* beta, void* y, int32_t m, int32_t d,
+                                  sat_stream_t stream) {
+    return layernorm_bf16_impl(0, x, gamma, beta, y, m, d, stream);
+}
+extern "C" int sat_layernorm_f16(const float* x, const float* gamma, const float* beta, void* y, int32_t m, int32_t d,
+                                  sat_stream_t stream) {
+    return layernorm_bf16_impl(1, x, gamma, beta, y, m, d, stream);
+}
+
+static int cast_bf16_impl(int f16, const float* x, void* y, int64_t n, sat_stream_t stream) {
+    return sat_launch_cast_bf16(x, (op_t*)y, n, (hipStream_t)stream, f16);
+}
+extern "C" int sat_cast_bf16(const float* x, void* y, int64_t n, sat_stream_t stream) {
+    return cast_bf16_impl(0, x, y, n, stream);
+}
+extern "C" int sat_cast_f16(const float* x, void* y, int64_t n, sat_stream_t stream) {
+    return cast_bf16_impl(1, x, y, n, stream);
+}
+
+static int gemm_bf16_f32_impl(int f16, const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
+                              int32_t accumulate, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
+    SAT_CHECK_ARG(c, SAT_E_INVALID, "gemm: null output");
+    GemmArgs g{};
+    g.f16 = f16;
+    g.A = (const op_t*)a; g.W = (const op_t*)w; g.bias = bias; g.M = m; g.N = n; g.K = k;
+    g.C = c; g.ldc = n; g.accumulate = accumulate; g.variant = variant;
+    g.slab = (float*)ws; g.slab_bytes = ws ? ws_bytes : 0;
+    return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
+}
+extern "C" int sat_gemm_bf16_f32(const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
+                                 int32_t accumulate, int32_t variant, sat_stream_t stream) {
+    return gemm_bf16_f32_impl(0, a, w, bias, c, m, n, k, accumulate, variant, nullptr, 0, stream);
+}
+extern "C" int sat_gemm_f16_f32(const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
+                                int32_t accumulate, int32_t variant, sat_stream_t stream) {
+    return gemm_bf16_f32_impl(1, a, w, bias, c, m, n, k, accumulate, variant, nullptr, 0, stream);
+}
+extern "C" int sat_gemm_bf16_f32_ws(const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
+                                    int32_t accumulate, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
+    return gemm_bf16_f32_impl(0, a, w, bias, c, m, n, k, accumulate, variant, ws, ws_bytes, stream);
+}
+extern "C" int sat_gemm_f16_f32_ws(const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
+                                   int32_t accumulate, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
+    return gemm_bf16_f32_impl(1, a, w, bias, c, m, n, k, accumulate, variant, ws, ws_bytes, stream);
+}
+extern "C" int sat_gemm_f32_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t variant, size_t* out_bytes) {
+    SAT_CHECK_ARG(out_bytes && m > 0 && n > 0 && k > 0, SAT_E_INVALID, "gemm_f32_workspace_bytes: bad argument");
+    const int cus = sat_device_cus();
+    SAT_CHECK_ARG(cus > 0, SAT_E_INVALID, "gemm_f32_workspace_bytes: no device");
+    // forced K-split (tests / measurements): one slab per workgroup; otherwise what the automatic schedule would use
+    *out_bytes = sat_variant_has(variant, SAT_VARIANT_SPLIT_FORCE) ? (size_t)cus * 65536 * sizeof(float) : sat_gemm_ph8_slab_bytes(EPI_F32, m, n, k);
+    return 0;
+}
+
+static int gemm_swiglu_bf16_impl(int f16, const void* a, const float* w_f32, const float* bias_f32, void* wpack, float* bpack,
+                                    void* h, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
+    SAT_CHECK_ARG(w_f32 && wpack && bpack && h, SAT_E_INVALID, "gemm_swiglu: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (!sat_variant_has(variant, SAT_VARIANT_PACKED)) {     // wpack / bpack already hold the packed operands of a previous call (benchmarks)
+        SAT_TRY(sat_launch_pack_rows_bf16(w_f32, (op_t*)wpack, n, k, 1, s, f16));
+        if (bias_f32) SAT_TRY(sat_launch_pack_bias(bias_f32, bpack, n, 1, s));
+    }
+    GemmArgs g{};
+    g.f16 = f16;
+    g.A = (const op_t*)a; g.W = (const op_t*)wpack; g.bias = bias_f32 ? bpack : nullptr; g.M = m; g.N = n; g.K = k;
+    g.H = (op_t*)h; g.variant = variant & ~SAT_VARIANT_PACKED;
+    return sat_launch_gemm(EPI_SWIGLU, g, s);
+}
+extern "C" int sat_gemm_swiglu_bf16(const void* a, const float* w_f32, const float* bias_f32, void* wpack, float* bpack,
+                                    void* h, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
+    return gemm_swiglu_bf16_impl(0, a, w_f32, bias_f32, wpack, bpack, h, m, n, k, variant, stream);
+}
+extern "C" int sat_gemm_swiglu_f16(const void* a, const float* w_f32, const float* bias_f32, void* wpack, float* bpack,
+                                    void* h, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
+    return gemm_swiglu_bf16_impl(1, a, w_f32, bias_f32, wpack, bpack, h, m, n, k, variant, stream);
+}
+
+static int attention_bf16_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
+                                  int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return sat_launch_attention((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, sq, sk, sq_pad,
+                                sk_pad, (hipStream_t)stream, nullptr, SAT_ATTN_QSCALE, f16);
+}
+extern "C" int sat_attention_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
+                                  int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_bf16_impl(0, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
+}
+extern "C" int sat_attention_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
+                                  int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_bf16_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
+}
+
+// to_q projection + cross-attention in ONE launch (what the plan runs per layer at one prompt): out [b*s, d] = attention(a wq^T, k, v)
+static int cross_attention_fused_bf16_impl(int f16, const void* a, const void* wq, const void* k, const void* vt, void* out, int32_t b, int32_t s_len,
+                                              int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream) {
+    SAT_CHECK_ARG(a && wq && k && vt && out && b > 0 && s_len > 0 && d > 0 && d % 128 == 0 && kvh > 0, SAT_E_INVALID, "cross_attention_fused: bad argument");
+    GemmArgs g{};
+    g.f16 = f16;
+    g.A = (const op_t*)a; g.W = (const op_t*)wq; g.M = b * s_len; g.N = d; g.K = d;
+    g.heads.kind[0] = 8; g.heads.qscale = SAT_ATTN_QSCALE; g.heads.parts = 1; g.heads.heads = d / 64; g.heads.S = s_len; g.heads.Spad = s_len;
+    g.heads.xa_k = (const op_t*)k; g.heads.xa_vt = (const op_t*)vt; g.heads.xa_out = (op_t*)out;
+    g.heads.xa_kvh = kvh; g.heads.xa_sk = sk; g.heads.xa_sk_pad = sk_pad;
+    return sat_launch_gemm(EPI_HEADS, g, (hipStream_t)stream);
+}
+extern "C" int sat_cross_attention_fused_bf16(const void* a, const void* wq, const void* k, const void* vt, void* out, int32_t b, int32_t s_len,
+                                              int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream) {
+    return cross_attention_fused_bf16_impl(0, a, wq, k, vt, out, b, s_len, d, kvh, sk, sk_pad, stream);
+}
+extern "C" int sat_cross_attention_fused_f16(const void* a, const void* wq, const void* k, const void* vt, void* out, int32_t b, int32_t s_len,
+                                              int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream) {
+    return cross_attention_fused_bf16_impl(1, a, wq, k, vt, out, b, s_len, d, kvh, sk, sk_pad, stream);
+}
+
+// The layout the DiT plan runs: Q pre-scaled by 1/sqrt(64) * log2(e) by its producer (the QKV / to_q GEMM epilogue)
+static int attention_prescaled_bf16_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
+                                            int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return sat_launch_attention((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, sq, sk, sq_pad,
+                                sk_pad, (hipStream_t)stream, nullptr, 1.0f, f16);
+}
+extern "C" int sat_attention_prescaled_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
+                                            int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_prescaled_bf16_impl(0, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
+}
+extern "C" int sat_attention_prescaled_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
+                                            int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_prescaled_bf16_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
+}
+
+static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
+                                 float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
+                                 sat_stream_t stream) {
+    SAT_CHECK_ARG(a && w && inv_freq && q && k && vt && rope_scratch, SAT_E_INVALID, "qkv_rope: null pointer");
+    SAT_CHECK_ARG(d % 64 == 0 && s_pad >= s_len + 3 && s_pad % 128 == 0, SAT_E_INVALID, "qkv_rope: bad dims (s_pad >= s + 3, %% 128)");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = d / 64;
+    const size_t bytes = (size_t)b * H * s_pad * 64 * 2;
+    SAT_HIP(hipMemsetAsync(q, 0, bytes, s));
+    SAT_HIP(hipMemsetAsync(k, 0, bytes, s));
+    SAT_HIP(hipMemsetAsync(vt, 0, bytes, s));
+    float* cs = rope_scratch;
+    float* sn = rope_scratch + (size_t)s_len * 16;
+    SAT_TRY(sat_launch_rope_table(inv_freq, cs, sn, s_len, s));
+    GemmArgs g{};
+    g.f16 = f16;
+    g.A = (const op_t*)a; g.W = (const op_t*)w; g.M = b * s_len; g.N = 3 * d; g.K = d; g.variant = variant;
+    g.heads.out[0] = (op_t*)q; g.heads.out[1] = (op_t*)k; g.heads.out[2] = (op_t*)vt;
+    g.heads.kind[0] = 2; g.heads.kind[1] = 2 | 4; g.heads.kind[2] = 1 | 4;
+    g.heads.parts = 3; g.heads.heads = H; g.heads.S = s_len; g.heads.Spad = s_pad;
+    g.heads.rope_cos = cs; g.heads.rope_sin = sn;
+    return sat_launch_gemm(EPI_HEADS, g, s);
+}
+extern "C" int sat_qkv_rope_bf16(const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
+                                 float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
+                                 sat_stream_t stream) {
+    return qkv_rope_bf16_impl(0, a, w, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream);
+}
+extern "C" int sat_qkv_rope_f16(const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
+                                 float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
+                                 sat_stream_t stream) {
+    return qkv_rope_bf16_impl(1, a, w, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream);
+}
+
+// ---- LayerNorm folded into the neighbouring GEMMs (sat_dit_cfg.ln_fold), one entry per role
+static int gemm_resid_ln_bf16_impl(int f16, const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
+                                   int32_t n, int32_t k, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
+    SAT_CHECK_ARG(c && xb && ln_part, SAT_E_INVALID, "gemm_resid_ln: null output");
+    GemmArgs g{};
+    g.f16 = f16;
+    g.A = (const op_t*)a; g.W = (const op_t*)w; g.bias = bias; g.M = m; g.N = n; g.K = k;
+    g.C = c; g.ldc = n; g.accumulate = 1; g.variant = variant; g.xb = (op_t*)xb; g.ln_part_out = ln_part;
+    g.slab = (float*)ws; g.slab_bytes = ws ? ws_bytes : 0;
+    return sat_launch_gemm(EPI_RESID, g, (hipStream_t)stream);
+}
+extern "C" int sat_gemm_resid_ln_bf16(const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
+                                      int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
+    return gemm_resid_ln_bf16_impl(0, a, w, bias, c, xb, ln_part, m, n, k, variant, nullptr, 0, stream);
+}
+extern "C" int sat_gemm_resid_ln_f16(const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
+                                     int32_t n, int32_t k, int32_t variant, sat_stream_t stream) {
+    return gemm_resid_ln_bf16_impl(1, a, w, bias, c, xb, ln_part, m, n, k, variant, nullptr, 0, stream);
+}
+extern "C" int sat_gemm_resid_ln_bf16_ws(const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
+                                         int32_t n, int32_t k, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
+    return gemm_resid_ln_bf16_impl(0, a, w, bias, c, xb, ln_part, m, n, k, variant, ws, ws_bytes, stream);
+}
+extern "C" int sat_gemm_resid_ln_f16_ws(const void* a, const void* w, const float* bias, float* c, void* xb, float* ln_part, int32_t m,
+                                        int32_t n, int32_t k, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
+    return gemm_resid_ln_bf16_impl(1, a, w, bias, c, xb, ln_part, m, n, k, variant, ws, ws_bytes, stream);
+}
+
+static int gemm_swiglu_ln_bf16_impl(int f16, const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
+                                       const float* bias_f32, void* wpack, float* c12, void* h, int32_t m, int32_t n, int32_t k,
+                                       int32_t variant, sat_stream_t stream) {
+    SAT_CHECK_ARG(xb && ln_part && w_f32 && gamma && beta && wpack && c12 && h, SAT_E_INVALID, "gemm_swiglu_ln: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (!sat_variant_has(variant, SAT_VARIANT_PACKED))       // wpack / c12 already hold the packed operands of a previous call (benchmarks)
+        SAT_TRY(sat_launch_pack_rows_ln(w_f32, gamma, beta, bias_f32, (op_t*)wpack, c12, c12 + n, n, k, 1, s, f16));
+    GemmArgs g{};
+    g.f16 = f16;
+    g.A = (const op_t*)xb; g.W = (const op_t*)wpack; g.M = m; g.N = n; g.K = k; g.H = (op_t*)h; g.variant = variant & ~SAT_VARIANT_PACKED;
+    g.ln_part = ln_part; g.ln_c1 = c12; g.ln_c2 = c12 + n; g.ln_eps = 1e-5f;
+    return sat_launch_gemm(EPI_SWIGLU, g, s);
+}
+extern "C" int sat_gemm_swiglu_ln_bf16(const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
+                                       const float* bias_f32, void* wpack, float* c12, void* h, int32_t m, int32_t n, int32_t k,
+                                       int32_t variant, sat_stream_t stream) {
+    return gemm_swiglu_ln_bf16_impl(0, xb, ln_part, w_f32, gamma, beta, bias_f32, wpack, c12, h, m, n, k, variant, stream);
+}
+extern "C" int sat_gemm_swiglu_ln_f16(const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
+                                       const float* bias_f32, void* wpack, float* c12, void* h, int32_t m, int32_t n, int32_t k,
+                                       int32_t variant, sat_stream_t stream) {
+    return gemm_swiglu_ln_bf16_impl(1, xb, ln_part, w_f32, gamma, beta, bias_f32, wpack, c12, h, m, n, k, variant, stream);
+}
+
+static int qkv_rope_ln_bf16_impl(int f16, const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
+                                    void* wpack, float* c12, const float* inv_freq, void* q, void* k, void* vt, float* rope_scratch,
+                                    int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream) {
+    SAT_CHECK_ARG(xb && ln_part && w_f32 && gamma && beta && wpack && c12 && inv_freq && q && k && vt && rope_scratch, SAT_E_INVALID,
+                  "qkv_rope_ln: null pointer");
+    SAT_CHECK_ARG(d % 64 == 0 && s_pad >= s_len + 3 && s_pad % 128 == 0, SAT_E_INVALID, "qkv_rope_ln: bad dims (s_pad >= s + 3, %% 128)");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = d / 64;
+    const size_t bytes = (size_t)b * H * s_pad * 64 * 2;
+    float* cs = rope_scratch;
+    float* sn = rope_scratch + (size_t)s_len * 16;
+    if (!sat_variant_has(variant, SAT_VARIANT_PACKED)) {     // pads, tables and packed operands are those of a previous call (benchmarks)
+        SAT_HIP(hipMemsetAsync(q, 0, bytes, s));
+        SAT_HIP(hipMemsetAsync(k, 0, bytes, s));
+        SAT_HIP(hipMemsetAsync(vt, 0, bytes, s));
+        SAT_TRY(sat_launch_rope_table(inv_freq, cs, sn, s_len, s));
+        SAT_TRY(sat_launch_pack_rows_ln(w_f32, gamma, beta, nullptr, (op_t*)wpack, c12, c12 + 3 * d, 3 * d, d, 0, s, f16));
+    }
+    GemmArgs g{};
+    g.f16 = f16;
+    g.A = (const op_t*)xb; g.W = (const op_t*)wpack; g.M = b * s_len; g.N = 3 * d; g.K = d; g.variant = variant & ~SAT_VARIANT_PACKED;
+    g.heads.out[0] = (op_t*)q; g.heads.out[1] = (op_t*)k; g.heads.out[2] = (op_t*)vt;
+    g.heads.kind[0] = 2; g.heads.kind[1] = 2 | 4; g.heads.kind[2] = 1 | 4;
+    g.heads.parts = 3; g.heads.heads = H; g.heads.S = s_len; g.heads.Spad = s_pad;
+    g.heads.rope_cos = cs; g.heads.rope_sin = sn;
+    g.ln_part = ln_part; g.ln_c1 = c12; g.ln_c2 = c12 + 3 * d; g.ln_eps = 1e-5f;
+    return sat_launch_gemm(EPI_HEADS, g, s);
+}
+extern "C" int sat_qkv_rope_ln_bf16(const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
+                                    void* wpack, float* c12, const float* inv_freq, void* q, void* k, void* vt, float* rope_scratch,
+                                    int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream) {
+    return qkv_rope_ln_bf16_impl(0, xb, ln_part, w_f32, gamma, beta, wpack, c12, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream);
+}
+extern "C" int sat_qkv_rope_ln_f16(const void* xb, const float* ln_part, const float* w_f32, const float* gamma, const float* beta,
+                                    void* wpack, float* c12, const float* inv_freq, void* q, void* k, void* vt, float* rope_scratch,
+                                    int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream) {
+    return qkv_rope_ln_bf16_impl(1, xb, ln_part, w_f32, gamma, beta, wpack, c12, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream);
+}
+
+extern "C" int sat_quant_rows_fp8(const float* x, void* out8, float* row_scale, int32_t rows, int32_t k, sat_stream_t stream) {
+    return sat_launch_quant_rows_fp8(x, out8, row_scale, rows, k, 0, (hipStream_t)stream);
+}
+
+extern "C" int sat_layernorm_fp8(const float* x, const float* gamma, const float* beta, void* y8, float* row_scale, int32_t m,
+                                 int32_t d, sat_stream_t stream) {
+    return sat_launch_layernorm_fp8(x, gamma, beta, y8, row_scale, m, d, nullptr, nullptr, 1, 0, (hipStream_t)stream);
+}
+
+extern "C" int sat_gemm_fp8_f32(const void* a8, const float* a_scale, const void* w8, const float* w_scale, const float* bias,
+                                float* c, int32_t m, int32_t n, int32_t k, int32_t accumulate, int32_t variant, sat_stream_t stream) {
+    SAT_CHECK_ARG(a8 && w8 && a_scale && w_scale && c, SAT_E_INVALID, "gemm_fp8: null pointer");
+    GemmArgs g{};
+    g.A = (const op_t*)a8; g.W = (const op_t*)w8; g.bias = bias; g.M = m; g.N = n; g.K = k; g.variant = variant & ~SAT_VARIANT_FP8_PLAIN;
+    g.C = c; g.ldc = n; g.accumulate = accumulate; g.a_scale = a_scale; g.w_scale = w_scale;
+    g.fp8 = sat_variant_has(variant, SAT_VARIANT_FP8_PLAIN) ? 1 : 2;      // the plain 32x32x16 fp8 MFMA instead of the 2x-rate scaled 32x32x64
+    return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
+}
+
+extern "C" int sat_quant_mx_rows_fp8(const float* x, void* out8, void* scales, int32_t rows, int32_t k, sat_stream_t stream) {
+    return sat_launch_quant_mx_rows(x, out8, scales, rows, k, (hipStream_t)stream);
+}
+
+extern "C" int sat_gemm_mxfp8_f32(const void* a8, const void* a_scales, const void* w8, const float* w_scale, const float* bias,
+                                  float* c, int32_t m, int32_t n, int32_t k, int32_t accumulate, int32_t variant, sat_stream_t stream) {
+    SAT_CHECK_ARG(a8 && w8 && a_scales && w_scale && c, SAT_E_INVALID, "gemm_mxfp8: null pointer");
+    SAT_CHECK_ARG(((uintptr_t)a_scales & 3) == 0, SAT_E_INVALID, "gemm_mxfp8: the scale array must be 4-byte aligned");
+    GemmArgs g{};
+    g.A = (const op_t*)a8; g.W = (const op_t*)w8; g.bias = bias; g.M = m; g.N = n; g.K = k; g.variant = sat_variant_tile(variant);
+    g.C = c; g.ldc = n; g.accumulate = accumulate; g.a_bscale = (const unsigned*)a_scales; g.w_scale = w_scale; g.fp8 = 3;
+    return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
+}

@@ -188,3 +188,52 @@ def ptr(t):
 
 def stream():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ---------------------------------------------------------------------- plan lifecycle, shared by the DiT, the codec and the text encoders
+def destroy_plan(kind, handle):
+    """``sat_<kind>_plan_destroy``; nothing to do for ``None``."""
+    if handle is not None:
+        getattr(lib(), f"sat_{kind}_plan_destroy")(handle)
+
+
+def new_handle(create_fn, *args):
+    """The opaque handle a ``*_create(*args, &handle)`` entry point returns."""
+    handle = c_void_p()
+    check(create_fn(*args, ctypes.byref(handle)))
+    return handle
+
+
+def build_plan(kind, create, tensors, device, configure=None):
+    """create -> configure -> set_tensor for every entry of ``tensors`` (name -> tensor, uploaded as contiguous fp32 on ``device``)
+    -> finalize, for ``kind`` in "dit" / "oobleck" / "t5" / "roberta".  ``create()`` returns the new handle.  Finalize has read and
+    synchronised every pointer when it returns, so the uploads live only that long.  Any failure destroys the plan and re-raises."""
+    handle = create()
+    try:
+        if configure is not None:
+            configure(handle)
+        set_tensor = getattr(lib(), f"sat_{kind}_plan_set_tensor")
+        keep = [t.detach().to(device, torch.float32).contiguous() for t in tensors.values()]
+        for name, t in zip(tensors, keep):
+            check(set_tensor(handle, name.encode(), ptr(t), t.numel()))
+        check(getattr(lib(), f"sat_{kind}_plan_finalize")(handle, stream()))
+    except BaseException:
+        destroy_plan(kind, handle)
+        raise
+    return handle
+
+
+def same_device(a, b):
+    """``torch.device`` equality with ``cuda`` meaning the current device (``cuda`` != ``cuda:0`` for torch)."""
+    index = lambda d: torch.cuda.current_device() if d.type == "cuda" and d.index is None else d.index
+    a, b = torch.device(a), torch.device(b)
+    return a.type == b.type and index(a) == index(b)
+
+
+def plan_workspace(kind, handle, cached, device, *dims):
+    """The grow-only uint8 workspace of ``sat_<kind>_workspace_bytes(handle, *dims)``: ``cached`` when it is large enough and on ``device``."""
+    need = c_size_t()
+    check(getattr(lib(), f"sat_{kind}_workspace_bytes")(handle, *dims, ctypes.byref(need)))
+    if cached is not None and cached.numel() >= need.value and same_device(cached.device, device):
+        return cached
+    return torch.empty(need.value, dtype=torch.uint8, device=device)

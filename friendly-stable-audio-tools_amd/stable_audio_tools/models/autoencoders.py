@@ -142,8 +142,7 @@ class _OobleckHip(nn.Module):
 
     def __del__(self):
         try:
-            if self._plan is not None:
-                _hip.lib().sat_oobleck_plan_destroy(self._plan)
+            _hip.destroy_plan("oobleck", self._plan)
         except Exception:
             pass
 
@@ -155,9 +154,8 @@ class _OobleckHip(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise _hip.SatError("Oobleck modules must be on a HIP device (model.to('cuda')); there is no CPU path")
-        if self._plan is not None:
-            lib.sat_oobleck_plan_destroy(self._plan)
-            self._plan = None
+        _hip.destroy_plan("oobleck", self._plan)
+        self._plan = None
         cfg = _hip.SatOobleckCfg()
         cfg.is_decoder = 1 if self._is_decoder else 0
         cfg.io_channels = self.io_channels
@@ -172,25 +170,12 @@ class _OobleckHip(nn.Module):
         opt.activation = _hip.OOBLECK_ACT_SNAKE if self.use_snake else _hip.OOBLECK_ACT_ELU
         opt.final_tanh = 1 if self.final_tanh else 0
         opt.nearest_upsample = 1 if self.use_nearest_upsample else 0
-        plan = ctypes.c_void_p()
-        _hip.check(lib.sat_oobleck_plan_create_ex(ctypes.byref(cfg), ctypes.byref(opt), ctypes.sizeof(opt), ctypes.byref(plan)))
-        keep = []
-        for name, t in self.state_dict().items():
-            t32 = t.detach().to(torch.float32).contiguous()
-            keep.append(t32)
-            _hip.check(lib.sat_oobleck_plan_set_tensor(plan, name.encode(), _hip.ptr(t32), t32.numel()))
-        _hip.check(lib.sat_oobleck_plan_finalize(plan, _hip.stream()))
-        del keep
-        self._plan, self._plan_version = plan, ver
-        return plan
+        create = lambda: _hip.new_handle(lib.sat_oobleck_plan_create_ex, ctypes.byref(cfg), ctypes.byref(opt), ctypes.sizeof(opt))
+        self._plan, self._plan_version = _hip.build_plan("oobleck", create, self.state_dict(), dev), ver
+        return self._plan
 
     def _workspace(self, b, t_len):
-        need = ctypes.c_size_t()
-        _hip.check(_hip.lib().sat_oobleck_workspace_bytes(self._plan, b, t_len, ctypes.byref(need)))
-        dev = next(self.parameters()).device
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != dev:
-            self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        self._ws = _hip.plan_workspace("oobleck", self._plan, self._ws, next(self.parameters()).device, b, t_len)
         return self._ws
 
 

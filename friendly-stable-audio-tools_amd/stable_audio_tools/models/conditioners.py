@@ -156,8 +156,7 @@ class T5Conditioner(Conditioner):
 
     def _drop_plan(self):
         enc = self.__dict__.get("_enc")
-        if enc is not None:
-            _hip.lib().sat_t5_plan_destroy(enc[0])
+        _hip.destroy_plan("t5", enc and enc[0])
         self.__dict__["_enc"] = None
 
     def __del__(self):
@@ -185,22 +184,10 @@ class T5Conditioner(Conditioner):
                             config.relative_attention_num_buckets, getattr(config, "relative_attention_max_distance", 128),
                             1 if getattr(config, "feed_forward_proj", "relu") == "gated-gelu" else 0,
                             self.output_dim if has_proj else 0, float(config.layer_norm_epsilon))
-        plan = ctypes.c_void_p()
-        _hip.check(lib.sat_t5_plan_create(ctypes.byref(cfg), ctypes.byref(plan)))
-        keep = []
         tensors = dict(sd)
         if has_proj:
-            tensors["proj_out.weight"], tensors["proj_out.bias"] = self.proj_out.weight.detach(), self.proj_out.bias.detach()
-        try:
-            for name, t in tensors.items():
-                td = t.to(dev, torch.float32).contiguous()
-                keep.append(td)
-                _hip.check(lib.sat_t5_plan_set_tensor(plan, name.encode(), _hip.ptr(td), td.numel()))
-            _hip.check(lib.sat_t5_plan_finalize(plan, _hip.stream()))
-        except Exception:
-            lib.sat_t5_plan_destroy(plan)
-            raise
-        torch.cuda.current_stream().synchronize()      # the plan copied from `keep`
+            tensors["proj_out.weight"], tensors["proj_out.bias"] = self.proj_out.weight, self.proj_out.bias
+        plan = _hip.build_plan("t5", lambda: _hip.new_handle(lib.sat_t5_plan_create, ctypes.byref(cfg)), tensors, dev)
         self.__dict__["_enc"] = (plan, dev, ver)
         return plan
 
@@ -217,17 +204,9 @@ class T5Conditioner(Conditioner):
         ids = input_ids.to(dev, torch.int32).contiguous()
         mask = attention_mask.to(dev, torch.int32).contiguous()
         b, l = ids.shape
-        lib = _hip.lib()
-        need = ctypes.c_size_t()
-        _hip.check(lib.sat_t5_workspace_bytes(plan, b, l, ctypes.byref(need)))
-        ws = self.__dict__["_ws"]
-        if dev.index is None:                      # torch.device("cuda") != tensor.device ("cuda:0"): compare resolved devices
-            dev = torch.device(dev.type, torch.cuda.current_device())
-        if ws is None or ws.numel() < need.value or ws.device != dev:
-            ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-            self.__dict__["_ws"] = ws
+        ws = self.__dict__["_ws"] = _hip.plan_workspace("t5", plan, self.__dict__["_ws"], dev, b, l)
         out = torch.empty((b, l, self.output_dim), dtype=torch.float32, device=dev)
-        _hip.check(lib.sat_t5_encode(plan, _hip.ptr(ids), _hip.ptr(mask), _hip.ptr(out), b, l, 1, _hip.ptr(ws), ws.numel(), _hip.stream()))
+        _hip.check(_hip.lib().sat_t5_encode(plan, _hip.ptr(ids), _hip.ptr(mask), _hip.ptr(out), b, l, 1, _hip.ptr(ws), ws.numel(), _hip.stream()))
         return out, mask.to(torch.bool)
 
     def forward(self, texts: tp.List[str]) -> tp.Tuple[torch.Tensor, torch.Tensor]:
@@ -252,29 +231,16 @@ class RobertaEncoderPlan:
         cfg = _hip.SatRobertaCfg(shape["vocab_size"], shape["hidden_size"], shape["num_layers"], run_layers, shape["num_heads"],
                                  shape["intermediate_size"], shape["max_positions"], shape["pad_id"],
                                  self.out_dim if proj is not None else 0, float(shape["eps"]))
-        plan = ctypes.c_void_p()
-        _hip.check(lib.sat_roberta_plan_create(ctypes.byref(cfg), ctypes.byref(plan)))
-        self.handle, self.device, self._ws = plan, dev, None
+        self.handle, self.device, self._ws = None, dev, None
         wanted = lambda k: k.startswith("embeddings.") or int(k.split(".")[2]) < run_layers
         tensors = {k: v for k, v in state_dict.items() if wanted(k)}
         if proj is not None:
-            tensors["proj_out.weight"], tensors["proj_out.bias"] = proj[0].detach(), proj[1].detach()
-        keep = []
-        try:
-            for name, t in tensors.items():
-                td = t.to(dev, torch.float32).contiguous()
-                keep.append(td)
-                _hip.check(lib.sat_roberta_plan_set_tensor(plan, name.encode(), _hip.ptr(td), td.numel()))
-            _hip.check(lib.sat_roberta_plan_finalize(plan, _hip.stream()))
-        except Exception:
-            self.close()
-            raise
-        torch.cuda.current_stream().synchronize()      # the plan copied from `keep`
+            tensors["proj_out.weight"], tensors["proj_out.bias"] = proj
+        self.handle = _hip.build_plan("roberta", lambda: _hip.new_handle(lib.sat_roberta_plan_create, ctypes.byref(cfg)), tensors, dev)
 
     def close(self):
-        if self.handle is not None:
-            _hip.lib().sat_roberta_plan_destroy(self.handle)
-            self.handle = None
+        _hip.destroy_plan("roberta", self.handle)
+        self.handle = None
 
     def __del__(self):
         try:
@@ -289,13 +255,9 @@ class RobertaEncoderPlan:
         ids = input_ids.to(dev, torch.int32).contiguous()
         mask = attention_mask.to(dev, torch.int32).contiguous()
         b, l = ids.shape
-        lib = _hip.lib()
-        need = ctypes.c_size_t()
-        _hip.check(lib.sat_roberta_workspace_bytes(self.handle, b, l, ctypes.byref(need)))
-        if self._ws is None or self._ws.numel() < need.value:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        self._ws = _hip.plan_workspace("roberta", self.handle, self._ws, dev, b, l)
         out = torch.empty((b, l, self.out_dim), dtype=torch.float32, device=dev)
-        _hip.check(lib.sat_roberta_encode(self.handle, _hip.ptr(ids), _hip.ptr(mask), _hip.ptr(out), b, l, _hip.ptr(self._ws),
+        _hip.check(_hip.lib().sat_roberta_encode(self.handle, _hip.ptr(ids), _hip.ptr(mask), _hip.ptr(out), b, l, _hip.ptr(self._ws),
                                           self._ws.numel(), _hip.stream()))
         return out
 

@@ -160,8 +160,7 @@ class DiffusionTransformer(nn.Module):
     # ------------------------------------------------------------------ plan management
     def __del__(self):
         try:
-            if self._plan is not None:
-                _hip.lib().sat_dit_plan_destroy(self._plan)
+            _hip.destroy_plan("dit", self._plan)
         except Exception:
             pass
 
@@ -173,38 +172,26 @@ class DiffusionTransformer(nn.Module):
         dev = self.timestep_features.weight.device
         if dev.type != "cuda":
             raise _hip.SatError("DiffusionTransformer must be on a HIP device (model.to('cuda')); there is no CPU path")
-        if self._plan is not None:
-            lib.sat_dit_plan_destroy(self._plan)
-            self._plan = None
+        _hip.destroy_plan("dit", self._plan)
+        self._plan = None
         cfg = _hip.SatDitCfg(self.io_channels, self.embed_dim, self.depth, self.num_heads, self.cond_token_dim,
                              self.cond_embed_dim, self.global_cond_dim, self.max_seq_len,
                              1 if self.global_cond_type == "adaLN" else 0, GEMM_DTYPES[self.gemm_dtype], FP8_FAMILIES.get(self.gemm_dtype, 0),
                              1 if self.layernorm_fusion else 0, 0 if self.cross_attention_fusion else 1, self.tile_policy)
-        plan = ctypes.c_void_p()
-        _hip.check(lib.sat_dit_plan_create_sized(ctypes.byref(cfg), ctypes.sizeof(cfg), ctypes.byref(plan)))
-        if self.input_concat_dim > 0 or self.prepend_cond_dim > 0:
-            rc = lib.sat_dit_plan_set_extra_conditioning(plan, self.input_concat_dim, self.prepend_cond_dim, self.max_prepend_len)
-            if rc != 0:
-                lib.sat_dit_plan_destroy(plan)
-                _hip.check(rc)
-        keep = []
-        for name, t in self.state_dict().items():
-            t32 = t.detach().to(torch.float32).contiguous()
-            keep.append(t32)
-            _hip.check(lib.sat_dit_plan_set_tensor(plan, name.encode(), _hip.ptr(t32), t32.numel()))
-        _hip.check(lib.sat_dit_plan_finalize(plan, _hip.stream()))
-        del keep
-        self._plan = plan
+
+        def configure(plan):
+            if self.input_concat_dim > 0 or self.prepend_cond_dim > 0:
+                _hip.check(lib.sat_dit_plan_set_extra_conditioning(plan, self.input_concat_dim, self.prepend_cond_dim, self.max_prepend_len))
+
+        create = lambda: _hip.new_handle(lib.sat_dit_plan_create_sized, ctypes.byref(cfg), ctypes.sizeof(cfg))
+        plan = self._plan = _hip.build_plan("dit", create, self.state_dict(), dev, configure)
         self._plan_version = ver
         self._ctx_key = None
         self._ext_key = None
         return plan
 
     def _workspace(self, bf, t_len):
-        need = ctypes.c_size_t()
-        _hip.check(_hip.lib().sat_dit_workspace_bytes(self._plan, bf, t_len, ctypes.byref(need)))
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != self.timestep_features.weight.device:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.timestep_features.weight.device)
+        self._ws = _hip.plan_workspace("dit", self._plan, self._ws, self.timestep_features.weight.device, bf, t_len)
         return self._ws
 
     def prepare_context(self, cross_attn_cond, global_embed, null_from=-1):

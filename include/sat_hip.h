@@ -140,7 +140,14 @@ void sat_dit_plan_destroy(sat_dit_plan* plan);
 /* Hand one fp32 tensor of the reference state dict to the plan.  `name` is the key
  * RELATIVE to the DiffusionTransformer module ("model.model." stripped), e.g.
  * "transformer.layers.3.ff.ff.0.proj.weight" (models/dit.py, models/transformer.py module
- * tree).  The pointer is only read inside sat_dit_plan_finalize. */
+ * tree).
+ *
+ * Lifetime rule of all four plan kinds (sat_dit_*, sat_oobleck_*, sat_t5_*, sat_roberta_*): *_plan_set_tensor only records
+ * the pointer (setting a name again replaces it); the memory is read inside *_plan_finalize and nowhere else.
+ * *_plan_finalize copies / re-packs everything into device memory the plan owns and synchronises `stream` before it
+ * returns: after a successful finalize the caller may free or overwrite its fp32 tensors at once.  A finalize that fails
+ * (SAT_E_MISSING, SAT_E_INVALID, a HIP error) leaves the plan unfinalized with its table intact: set what was missing and
+ * finalize again, or destroy the plan. */
 int sat_dit_plan_set_tensor(sat_dit_plan* plan, const char* name, const float* data_dev, int64_t numel);
 
 /* Input-concat / prepend conditioning (models/dit.py:38,160-173,185-197), between create and finalize; a plan never given
@@ -323,7 +330,7 @@ int sat_oobleck_plan_create_ex(const sat_oobleck_cfg* cfg, const sat_oobleck_opt
                                sat_oobleck_plan** out_plan);
 void sat_oobleck_plan_destroy(sat_oobleck_plan* plan);
 /* `name` relative to the OobleckEncoder/OobleckDecoder module, e.g.
- * "layers.1.layers.2.layers.1.weight_v". */
+ * "layers.1.layers.2.layers.1.weight_v".  Pointer lifetime and the synchronising finalize: see sat_dit_plan_set_tensor. */
 int sat_oobleck_plan_set_tensor(sat_oobleck_plan* plan, const char* name, const float* data_dev, int64_t numel);
 int sat_oobleck_plan_finalize(sat_oobleck_plan* plan, sat_stream_t stream);
 /* latent length `t_len` for both directions (audio length = t_len * prod(strides)). */
@@ -498,6 +505,7 @@ typedef struct sat_t5_cfg {
 } sat_t5_cfg;
 int sat_t5_plan_create(const sat_t5_cfg* cfg, sat_t5_plan** out_plan);
 void sat_t5_plan_destroy(sat_t5_plan* plan);
+/* (pointer lifetime and the synchronising finalize: see sat_dit_plan_set_tensor) */
 int sat_t5_plan_set_tensor(sat_t5_plan* plan, const char* name, const float* data_dev, int64_t numel);
 int sat_t5_plan_finalize(sat_t5_plan* plan, sat_stream_t stream);
 int sat_t5_workspace_bytes(const sat_t5_plan* plan, int32_t b, int32_t l, size_t* out_bytes);
@@ -539,6 +547,7 @@ typedef struct sat_roberta_cfg {
 } sat_roberta_cfg;
 int sat_roberta_plan_create(const sat_roberta_cfg* cfg, sat_roberta_plan** out_plan);
 void sat_roberta_plan_destroy(sat_roberta_plan* plan);
+/* (pointer lifetime and the synchronising finalize: see sat_dit_plan_set_tensor) */
 int sat_roberta_plan_set_tensor(sat_roberta_plan* plan, const char* name, const float* data_dev, int64_t numel);
 int sat_roberta_plan_finalize(sat_roberta_plan* plan, sat_stream_t stream);
 /* l <= max_positions - pad_id - 1 (the position table) and l <= 512, else SAT_E_UNSUPPORTED; needs no finalized plan */
