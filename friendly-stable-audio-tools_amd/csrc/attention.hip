@@ -51,7 +51,7 @@ __device__ __forceinline__ void swap_halves(unsigned& lo_run, unsigned& hi_run) 
 // still fills the chip)
 // MODE: the softmax recurrence of attn_core.h -- 1 (default): standing reference, the row sum is the overflow check; 2: the same with
 // the reference carried through the matrix pipe, for a Q its producer wrote pre-scaled (scale_log2 == 1; anything else is multiplied
-// into Q here and rounded to bf16 a second time: experiments); 0: the textbook recurrence (experiments build).
+// into Q here and rounded to bf16 a second time: experiments).
 template <bool MX8, int DBG = 0, int NGRP = 2, int MODE = 1>
 __global__ __launch_bounds__(512, 2) void attention_kernel(const op_t* __restrict__ q, const op_t* __restrict__ k,
                                                            const op_t* __restrict__ vt, op_t* __restrict__ out,
@@ -344,17 +344,15 @@ int SAT_OPNS::sat_launch_attention(const op_t* q, const op_t* k, const op_t* vt,
     }
 #endif
 #ifdef SAT_GEMM_EXPERIMENTS
-    if (const char* eo = getenv("SAT_ATTN_MODE"); eo && !out_scales) {          // A/B of the softmax recurrences (tools/attn_opt_probe.py)
+    if (const char* eo = getenv("SAT_ATTN_MODE"); eo && !out_scales) {          // forced MODE 1 / 2 (tools/attn_opt_probe.py)
         auto launch = [&](auto kern, dim3 g, int lds) {
             (void)sat_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
             hipLaunchKernelGGL(kern, g, dim3(512), lds, s, q, k, vt, out, out_scales, h, kvh, sq, sk, sq_pad, sk_pad, scale_log2);
         };
         const dim3 g1(cdiv(sq, 256), h, b);
         switch (atoi(eo) + (one_group ? 100 : 0)) {
-            case 0: launch(attention_kernel<false, 0, 2, 0>, grid, ATT_LDS); return 0;
             case 1: launch(attention_kernel<false, 0, 2, 1>, grid, ATT_LDS); return 0;
             case 2: launch(attention_kernel<false, 0, 2, 2>, grid, ATT_LDS); return 0;
-            case 100: launch(attention_kernel<false, 0, 1, 0>, g1, 3 * STAGE_BYTES); return 0;
             case 101: launch(attention_kernel<false, 0, 1, 1>, g1, 3 * STAGE_BYTES); return 0;
             case 102: launch(attention_kernel<false, 0, 1, 2>, g1, 3 * STAGE_BYTES); return 0;
         }

@@ -16,7 +16,6 @@
 //   MODE 2 (Q pre-scaled by scale_log2 by its producer): the reference rides in the matrix pipe -- a fifth K-step
 //           [1, 0, ...] x [-m_ref, 0, ...] makes the accumulator come out as log2-domain score minus reference, p = exp2(acc): the 16
 //           v_fma_f32 disappear from the VALU stream, the matrix pipe has the slack.  m_ref is kept representable in the operand type (bf16 / fp16).
-//   MODE 0: the textbook recurrence (experiments build, A/B).
 #pragma once
 #include "sat_common.h"
 
@@ -107,28 +106,6 @@ __device__ __forceinline__ void tile(State<MODE>& st, const opx8 (&qf)[4], const
 #pragma unroll
             for (int r = 0; r < 16; ++r) pb[r >> 3][r & 7] = f32_to_op(sacc[r]);
             st.l_run += sacc[0];
-        } else if constexpr (MODE == 0) {
-            float mloc = sacc[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, sacc[r]);
-            mloc = half_max(mloc);
-            const float m_new = fmaxf(st.m_run, mloc * scale_log2);
-            const float alpha = __builtin_amdgcn_exp2f(st.m_run - m_new);
-            st.m_run = m_new;
-            float psum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(sacc[r], scale_log2, -m_new));
-                psum += p;
-                pb[r >> 3][r & 7] = f32_to_op(p);
-            }
-            st.l_run = st.l_run * alpha + psum;
-            if (!__all(alpha == 1.0f)) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) st.oacc[i][r] *= alpha;
-            }
         } else {
             // fast path: exponentials against the standing reference (MODE 2: already subtracted by the matrix pipe)
             float psum = 0.f;

@@ -212,13 +212,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[M
 // (W fragment as the A operand, activation fragment as the B operand), so a 32x32 block holds C^T: lane l31 owns TOKEN row
 // m = mw + i*32 + l31, and its 16 registers are output channels n = nw + j*32 + 8*(r>>2) + 4*half + (r&3) -- four runs of
 // four consecutive channels.  Everything a token needs is then lane-local:
-//   * fp32 output / residual: 16-byte loads and stores (4 per 32x32 block instead of 16 dword accesses);
 //   * bf16 / e4m3 output: two runs are exchanged between the wave halves with v_permlane32_swap (lane l takes the partner's
 //     low run, lane l+32 the high runs), so every lane writes 8 consecutive channels = one 16-byte (8-byte for e4m3) store
 //     instead of sixteen 2-byte stores -- the epilogue is store-issue bound (guide T21), not bandwidth bound;
 //   * RoPE: the rotation partner d^16 is register r^8 of the same lane, no cross-lane traffic, cos/sin are two 16-byte loads;
 //   * SwiGLU / MXFP8 block maximum: value and gate, resp. the 32 channels of a block, sit in one lane pair.
-// V^T (token-contiguous destination) keeps the un-swapped orientation and the epilogue above.
+// V^T (token-contiguous destination) and fp32 output keep the un-swapped orientation: the epilogue above, resp. the staged one below.
 // ---------------------------------------------------------------------------------------------
 // ROPE_PRE: the rotation table rows of all MI row blocks are fetched up front (not in the 128-register budget of the 16-wave tile)
 template <int EPI, int MI, int NI, bool LNC = false, bool ROPE_PRE = true>
@@ -227,33 +226,8 @@ __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& g, f32x16 (&acc)
                                                 const float* lc2 = nullptr, unsigned (*qfrag)[8] = nullptr) {
     const int M = g.M, N = g.N;
     (void)N;
-    if constexpr (EPI == EPI_F32) {
-        const bool accum = g.accumulate != 0;
-        const int c0 = nw + 4 * half;                  // first channel of this lane's run 0
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-            const int m = mw + i * 32 + l31;
-            const int mc = m < M ? m : M - 1;
-            float* __restrict__ crow = g.C + (size_t)mc * g.ldc + c0;
-            f32x4 old[NI][4];
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    old[j][q] = accum ? *reinterpret_cast<const f32x4*>(crow + j * 32 + q * 8) : f32x4{0.f, 0.f, 0.f, 0.f};
-            const float* grow = g.gate ? g.gate + (size_t)(mc / g.gate_rows) * g.gate_ld + c0 : nullptr;
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                    if (g.bias) v += *reinterpret_cast<const f32x4*>(g.bias + c0 + j * 32 + q * 8);
-                    if (grow) v *= *reinterpret_cast<const f32x4*>(grow + j * 32 + q * 8);      // adaLN gate (transformer.py:674, 688)
-                    v += old[j][q];
-                    if (m < M) *reinterpret_cast<f32x4*>(crow + j * 32 + q * 8) = v;
-                }
-        }
-    } else if constexpr (EPI == EPI_SWIGLU) {
+    static_assert(EPI == EPI_SWIGLU || EPI == EPI_HEADS, "fp32 output is never transposed");
+    if constexpr (EPI == EPI_SWIGLU) {
         static_assert(NI == 2, "value block + gate block");
         const int ldh = N >> 1;
         const int hc0 = nw >> 1;                       // first hidden column of this wave's 32
@@ -771,7 +745,7 @@ __device__ __forceinline__ int lds_off_bk(int row, int chunk) {
 // ~16 clocks whoever issues it, and with a two-stage ring the issue of tile k + 1 can only start at boundary k and has to land by boundary k + 1 -- sixteen
 // pieces in a row per producer wave stretch that chain, eight per wave in parallel with the MFMAs do not.  The ablation without any DMA runs 36.9 us.)
 // DIL ("DMA in loop", bf16 / fp16 operands): the iteration's LDS-DMA pieces are issued inside compute(), behind the MFMAs of the first k-steps, instead of
-// in front of it -- always on with K-groups; a per-tile choice otherwise (measured, see launch_epi)
+// in front of it -- always on with K-groups; a per-tile choice otherwise (SatTile::dil, gemm_tiles.h)
 template <int BM, int BN, int BK, int WM, int WN, int NS, int EPI, int FP8 = 0, int KG = 1, bool DIL = false>
 __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g) {
     sat_f16_saturate();
@@ -780,8 +754,8 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     constexpr int NT = KG * WM * WN * 64;
     constexpr int TM = BM / WM;
     constexpr int TN = BN / WN;
-    // the fused epilogues need a whole head / a value-gate pair per wave (64 columns); plain fp32 output takes any 32-multiple
-    static_assert(TN % 32 == 0 && (TN == 64 || EPI == EPI_F32), "wave tile is TM x 64 (TM x 32k for EPI_F32)");
+    // the fused epilogues need a whole head / a value-gate pair per wave, the staged fp32 epilogue a 64-column block
+    static_assert(TN == 64, "wave tile is TM x 64");
     constexpr int MI = TM / 32;
     constexpr int NI = TN / 32;
     constexpr int CPR = BK / 8;                    // 16-B chunks per row
@@ -875,13 +849,7 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     const bool epi_rows_valid = KG == 2 ? epi_m < M : wave_rows_valid;
     [[maybe_unused]] f32x4 resid[PRE_RESID ? 8 : 1];
     if constexpr (PRE_RESID) {
-        // (exactly the condition under which the staged epilogue runs, see the end of the kernel)
-#ifdef SAT_GEMM_EXPERIMENTS
-        const bool staged = !(!MXA && !(g.variant & SAT_VARIANT_EPI_UNSWAPPED) && (g.variant & SAT_VARIANT_EPI_F32_TR)) && !(g.variant & SAT_VARIANT_EPI_F32_DIRECT);
-#else
-        const bool staged = true;
-#endif
-        const bool want = g.accumulate != 0 && epi_rows_valid && staged;
+        const bool want = g.accumulate != 0 && epi_rows_valid;
 #pragma unroll
         for (int ps = 0; ps < 8; ++ps) {
             const int m = epi_m + ps * 4 + (lane >> 4);
@@ -1212,19 +1180,13 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     // Measured (profiles/r02_epilogue_ab.txt): bf16 outputs gain 3-4 % (SwiGLU) / 13 % (heads) from the transposed orientation, the
     // fp32 residual epilogue LOSES 6-10 % at 8 prompts (a lane-per-token store instruction touches 32 cache lines; in the legacy
     // orientation every store instruction writes two full 128-byte lines) -> fp32 output stays un-swapped.
-    // The shipped build fixes the orientation at compile time wherever it can (ORI 0: un-swapped only -- fp32 output, MXFP8 A
-    // operand; 1: transposed only -- SwiGLU; 2: per workgroup -- heads: q / k transposed, V^T un-swapped): one main loop instead of
-    // two keeps the 128-VGPR kernels (16 waves, e4m3 fragments) out of scratch.  The experiments build keeps both behind variant
-    // bits (SAT_VARIANT_EPI_*: force un-swapped, transposed fp32 epilogue, direct dword fp32 epilogue) for A/B measurements.
-#ifdef SAT_GEMM_EXPERIMENTS
-    constexpr int ORI = MXA ? 0 : 2;
-    bool tr = !MXA && !(g.variant & SAT_VARIANT_EPI_UNSWAPPED) && (EPI != EPI_F32 || (g.variant & SAT_VARIANT_EPI_F32_TR));
-    const bool direct_f32 = (g.variant & SAT_VARIANT_EPI_F32_DIRECT) != 0;
-#else
+    // fp32 output therefore always takes the LDS-staged epilogue: to_out at one prompt 21.5 us staged / 22.8 direct dword stores / 23.1 transposed,
+    // at 8 prompts 101 / 106 / 119 (profiles/r02_f32_epilogue_and_tile_quantisation.txt).
+    // The orientation is fixed at compile time wherever it can be (ORI 0: un-swapped only -- fp32 output, MXFP8 A operand;
+    // 1: transposed only -- SwiGLU; 2: per workgroup -- heads: q / k transposed, V^T un-swapped): one main loop instead of two keeps
+    // the 128-VGPR kernels (16 waves, e4m3 fragments) out of scratch.
     constexpr int ORI = (MXA || EPI == EPI_F32) ? 0 : (EPI == EPI_SWIGLU ? 1 : 2);
     bool tr = ORI != 0;
-    constexpr bool direct_f32 = false;
-#endif
     if constexpr (EPI == EPI_HEADS) {
         const int hp = g.heads.heads * 64;
         tr = tr && !(g.heads.kind[(n0 + wn * TN) / hp] & 1);
@@ -1395,25 +1357,17 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
             gemm_epilogue_f32_staged<1, true>(g, fin, reinterpret_cast<float*>(smem + NW * 8192) + wave * 2048, epi_m, n0 + wn * TN, lane, resid);
         return;
     }
-    if constexpr (EPI == EPI_F32 && NI == 2) {
-        if (!tr && !direct_f32) {
-            __builtin_amdgcn_s_barrier();       // every wave is done reading the ring: it becomes the staging area
-            if (wave_rows_valid) {
-                if constexpr (PRE_RESID)
-                    gemm_epilogue_f32_staged<MI, true>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane, resid);
-                else
-                    gemm_epilogue_f32_staged<MI>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane);
-            }
-            return;
+    if constexpr (EPI == EPI_F32) {
+        __builtin_amdgcn_s_barrier();       // every wave is done reading the ring: it becomes the staging area
+        if (wave_rows_valid) {
+            if constexpr (PRE_RESID)
+                gemm_epilogue_f32_staged<MI, true>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane, resid);
+            else
+                gemm_epilogue_f32_staged<MI>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane);
         }
-    }
-    if (wave_rows_valid) {
-        if constexpr (NI == 2 || EPI == EPI_F32) {
-            if (tr) gemm_epilogue_t<EPI, MI, NI, LN_CONS, (NT < 1024)>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
-            else gemm_epilogue<EPI, MI, NI, LN_CONS>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
-        } else {
-            gemm_epilogue<EPI, MI, NI>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31);
-        }
+    } else if (wave_rows_valid) {
+        if (tr) gemm_epilogue_t<EPI, MI, NI, LN_CONS, (NT < 1024)>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
+        else gemm_epilogue<EPI, MI, NI, LN_CONS>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
     }
 }
 
@@ -1472,19 +1426,6 @@ int launch_cfg(const GemmArgs& a, hipStream_t stream) {
     return 0;
 }
 
-// experiments build: SAT_GEMM_NO_DEEP=1 keeps the 3-stage ring for FF-out (A/B measurements)
-inline bool deep_ring_off() {
-#ifdef SAT_GEMM_EXPERIMENTS
-    static const bool off = [] {
-        const char* e = getenv("SAT_GEMM_NO_DEEP");
-        return e && e[0] == '1';
-    }();
-    return off;
-#else
-    return false;
-#endif
-}
-
 // tile id (the table in gemm_tiles.h) -> the template instantiation; F8 = e4m3 flavour of the operands (0: 16-bit)
 template <int ID, int EPI, int F8>
 int launch_tile(const GemmArgs& a, hipStream_t stream) {
@@ -1509,33 +1450,11 @@ int launch_epi(int tile, const GemmArgs& a, hipStream_t stream) {
         switch (tile) {
             SAT_TILE_CASE(SAT_TILE_REF_128)
             SAT_TILE_CASE(SAT_TILE_DMA_128)
-#ifdef SAT_GEMM_EXPERIMENTS
-            SAT_TILE_CASE(SAT_TILE_X_128_DIL)
-            SAT_TILE_CASE(SAT_TILE_X_128x64_FRONT)
-            SAT_TILE_CASE(SAT_TILE_X_256x192_DIL)
-            SAT_TILE_CASE(SAT_TILE_X_REG_256x128)
-            SAT_TILE_CASE(SAT_TILE_X_REG_256)
-            SAT_TILE_CASE(SAT_TILE_X_DMA_256)
-            SAT_TILE_CASE(SAT_TILE_X_128_4W)
-            SAT_TILE_CASE(SAT_TILE_X_256x128)
-            SAT_TILE_CASE(SAT_TILE_X_256_BK32)
-            SAT_TILE_CASE(SAT_TILE_X_128_BK128)
-            SAT_TILE_CASE(SAT_TILE_X_128_BK128_4W)
-            SAT_TILE_CASE(SAT_TILE_X_256x128_BK32)
-            SAT_TILE_CASE(SAT_TILE_X_128x64_DEEP5)
-            SAT_TILE_CASE(SAT_TILE_X_128x64_DEEP6)
-            SAT_TILE_CASE(SAT_TILE_X_128_4W_DEEP)
-            SAT_TILE_CASE(SAT_TILE_X_128_4W_2ST)
-#endif
         }
         if constexpr (EPI == EPI_F32) {
             switch (tile) {
                 SAT_TILE_CASE(SAT_TILE_128_DEEP)
                 SAT_TILE_CASE(SAT_TILE_128_KGROUP)
-#ifdef SAT_GEMM_EXPERIMENTS
-                SAT_TILE_CASE(SAT_TILE_X_128_DEEP_DIL)
-                SAT_TILE_CASE(SAT_TILE_X_128_DEEP5)
-#endif
             }
         }
         if constexpr (EPI == EPI_HEADS) {
@@ -1599,7 +1518,6 @@ int SAT_OPNS::sat_launch_gemm(int epi, const GemmArgs& a, hipStream_t stream) {
     s.heads = a.heads.heads; s.xattn = a.heads.xa_k != nullptr;
     s.slab_ok = cus > 0 && a.slab && a.slab_bytes >= (size_t)cus * 65536 * sizeof(float);
     s.e4m3_built = !SAT_OP_IS_F16;
-    s.no_deep_ring = deep_ring_off();
     const GemmRoute r = sat_gemm_route(epi, s, cus);
     switch (r.msg) {
         case SAT_ROUTE_OK: break;

@@ -23,8 +23,7 @@
 //     slot may be restaged by the partner wave row in the very next interval: W-lo / A-lo / W-hi of tile t (read in phase A) are
 //     rewritten from phase B on, A-hi from phase A of tile t + 1.
 //   (The first version of this kernel ran FOUR phases of 16 MFMAs, 8 barriers per K-tile, half-tiles issued seven ahead, one
-//   vmcnt(6) per K-tile -- the schedule of the in-image guide; two phases measured +5..7 % on the SwiGLU GEMM, +3 % on fp32 output
-//   (profiles/r03_ph8_two_phases.txt).  It is kept as `main_loop` for A/B, variant bit 18, experiments build.)
+//   vmcnt(6) per K-tile; two phases measured +5..7 % on the SwiGLU GEMM, +3 % on fp32 output (profiles/r03_ph8_two_phases.txt).)
 //   Measured in the loop: 1.36 us per K-tile on 256 CUs = 1575 TFLOP/s (profiles/r03_ph8_ksweep_fixed_overhead.txt).
 //
 // Schedule (PERSISTENT workgroups, one per CU; Ph8Sched and its functions are ph8_sched.h, plain C++ that the CPU tests walk).  With one 136-KiB workgroup per CU nothing overlaps a tile's prologue and
@@ -44,7 +43,7 @@
 //     r03_ph8_ffout_streamk_negative.txt -- and are gone from the source.)
 //   * the whole schedule is a handful of integers computed on the host per launch in closed form and passed by value: no device
 //     tables, no cache, no lock;
-//   * the LDS-DMA prologue of the next K-range (7 half-tiles) is issued BEFORE the epilogue of the current one -- the ring is
+//   * the LDS-DMA prologue of the next K-range (6 half-tiles) is issued BEFORE the epilogue of the current one -- the ring is
 //     free after the last barrier of the main loop and the DMA needs no registers -- so its latency hides behind the epilogue.
 //
 // Epilogues run on TRANSPOSED accumulators (W fragment = MFMA A operand): lane l owns token row (l & 15) of a 16 x 16 block and
@@ -210,16 +209,13 @@ __device__ __forceinline__ void ph8_epi_f32_row(const Ph8F32Epi& e, f32x4_t (&v)
     }
 }
 
-// DBG (tools/ph8_probe.py ablations, wrong results): 1 no LDS-DMA in the loop, 2 no ds_read (fragments stay), 3 no MFMA
 // Measured and dropped (profiles/r03_ph8_schedule_options.txt): without the explicit lgkmcnt(0) behind the barrier, without s_setprio,
 // with a static priority for waves 4-7 -- all within 1 %; LDS-DMA issued at the head of the MFMA section instead of the load
 // section -- 5 % slower.
 // DBG 9 (experiments build): per workgroup and K-range the 100 MHz timestamps (range start, main loop done, fix-up done, epilogue
 // done) + (whole, K-tiles, last arriver) -> tools/ph8_probe.py timeline
-// Tile geometry: 2 wave rows x WN wave columns, a wave = 2 quadrant rows of MFQ 16-row blocks x 64 columns.
-//   WN = 4, MFQ = 4: 256 x 256, 8 waves, 136 KiB of LDS, one workgroup per CU   (the tile everything above describes)
-//   WN = 2, MFQ = 2: 128 x 128, 4 waves,  68 KiB of LDS, two workgroups per CU  (experiment for the narrow one-prompt GEMMs: slower than
-//                    the 16-wave-family tiles everywhere, see sat_launch_gemm_ph8; compiled in the experiments build only)
+// Tile geometry: 2 wave rows x WN = 4 wave columns, a wave = 2 quadrant rows of MFQ = 4 16-row blocks x 64 columns: 256 x 256,
+// 8 waves, 136 KiB of LDS, one workgroup per CU.
 // FP8 = 2 (BASELINE config 5, the LayerNorm-fed GEMMs: to_qkv, cross to_q, FF-in): A and W hold e4m3 bytes; the launcher hands the kernel
 // K / 2 "16-bit columns", so DMA, LDS image and swizzle are byte-for-byte those of the bf16 kernel -- a 128-byte LDS row now carries 128 k.
 // One v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales, twice the bf16 MFMA rate) consumes a whole row of the K-tile: a lane's 32
@@ -228,9 +224,10 @@ __device__ __forceinline__ void ph8_epi_f32_row(const Ph8F32Epi& e, f32x4_t (&v)
 // GATED (fp32 output only): the adaLN build of the residual epilogue -- (acc + bias) * gate[sequence] before the add
 // (transformer.py:674, 688).  A kernel of its own: a second copy of the straight-line epilogue inside one kernel made the register
 // allocator spill, a uniform branch inside it hides the vmcnt bookkeeping.
-template <int EPI, int DBG = 0, bool PH2 = true, int PH2V = 1, int WN = 4, int MFQ = 4, int FP8 = 0, bool GATED = false>
-__global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, unsigned long long* ts = nullptr) {
+template <int EPI, int DBG = 0, int FP8 = 0, bool GATED = false>
+__global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, unsigned long long* ts = nullptr) {
     sat_f16_saturate();
+    constexpr int WN = 4, MFQ = 4;
     constexpr int NW = 2 * WN, NT = NW * 64;
     constexpr int QR = MFQ * 16;                 // rows of one quadrant of a wave
     constexpr int WR = 2 * QR;                   // rows of a wave
@@ -369,100 +366,10 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
     };
 
     // SWAP: W fragment as the MFMA A operand -> a 16 x 16 block holds C^T (lane = token l15, registers = channels 4 q4 + r).
-    // K-tiles kt0 .. kt0 + nk - 1 (nk even); on entry half-tiles 0..6 of the range are in flight or landed and tile kt0 is visible.
+    // K-tiles kt0 .. kt0 + nk - 1 (nk even); on entry half-tiles 0..5 of the range are in flight or landed and tile kt0 is visible.
     // Quadrant mi of a wave is skipped when its 64 rows lie beyond M (M-tail tiles: the wave keeps staging and joining barriers).
+    // One K-tile = phases A and B of the header comment.
     auto main_loop = [&](auto swap_c, const int kt0, const int nk, const bool q_valid0, const bool q_valid1) {
-        constexpr bool SWAP = decltype(swap_c)::value;
-        auto mfma_quadrant = [&](int mi, int ni, opx8 (&fw)[2][2]) {
-            if constexpr (DBG == 3) return;
-            if (!(mi ? q_valid1 : q_valid0)) return;
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int f = 0; f < MFQ; ++f)
-#pragma unroll
-                    for (int n = 0; n < 2; ++n)
-                        acc[mi * MFQ + f][ni * 2 + n] = SWAP ? mfma_16x16x32(fw[n][ks], fa[f][ks], acc[mi * MFQ + f][ni * 2 + n])
-                                                             : mfma_16x16x32(fa[f][ks], fw[n][ks], acc[mi * MFQ + f][ni * 2 + n]);
-            __builtin_amdgcn_s_setprio(0);
-        };
-        // One K-tile = four phases.  BUF is the LDS buffer of tile t; tile t + 2 restages the same buffer.
-        // ISSUE: 4 = issue all four half-tiles (steady state), 1 = only phase 0's (the range's tile nk - 2), 0 = none (tile nk - 1)
-        auto k_tile = [&](auto buf_c, auto issue_c, auto wait_c, int t) {
-            constexpr int BUF = decltype(buf_c)::value;
-            constexpr int ISSUE = (DBG == 1) ? 0 : decltype(issue_c)::value;
-            constexpr int WAIT = decltype(wait_c)::value;          // vmcnt at phase 3: 6 steady, 0 for tile nk - 2, -1 none
-            // ---- phase 0
-            if constexpr (DBG != 2) {
-                read_w(BUF, 0, fwl);
-                __builtin_amdgcn_sched_barrier(0);
-                read_a(BUF, 0);
-            }
-            if constexpr (ISSUE >= 1) issue(3, BUF ^ 1, t + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (DBG != 2) wait_lgkmcnt<8>();              // the W-lo reads (issued first) have returned: slot 0 may be restaged in phase 1
-            __builtin_amdgcn_s_barrier();
-            wait_lgkmcnt<0>();
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_quadrant(0, 0, fwl);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            // ---- phase 1
-            if constexpr (DBG != 2) read_w(BUF, 1, fwh);
-            if constexpr (ISSUE >= 4) issue(0, BUF, t + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            wait_lgkmcnt<0>();
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_quadrant(0, 1, fwh);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            // ---- phase 2
-            if constexpr (DBG != 2) read_a(BUF, 1);
-            if constexpr (ISSUE >= 4) issue(1, BUF, t + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            wait_lgkmcnt<0>();
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_quadrant(1, 1, fwh);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            // ---- phase 3
-            if constexpr (ISSUE >= 4) issue(2, BUF, t + 2);
-            // K-tile t + 1 has landed (this wave's pieces; the barrier covers the others'); it is first read in the next phase
-            if constexpr (WAIT >= 0 && DBG != 1) wait_vmcnt<WAIT>();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_quadrant(1, 0, fwl);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-        };
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        using I4 = std::integral_constant<int, 4>;
-        using I6 = std::integral_constant<int, 6>;
-        using IM = std::integral_constant<int, -1>;
-        if (wr == 1) __builtin_amdgcn_s_barrier();          // stagger: wave row 1 runs one barrier behind wave row 0
-        const int kt_last = kt0 + nk - 2;
-        for (int t = kt0; t < kt_last; t += 2) {
-            k_tile(I0{}, I4{}, I6{}, t);
-            k_tile(I1{}, I4{}, I6{}, t + 1);
-        }
-        k_tile(I0{}, I1{}, I0{}, kt_last);
-        k_tile(I1{}, I0{}, IM{}, kt_last + 1);
-        if (wr == 0) __builtin_amdgcn_s_barrier();          // re-align the two wave rows: every wave is done with the ring
-    };
-
-    // PH2 (experiment): the same K-tile in TWO phases of 32 MFMAs -- 4 barriers per K-tile instead of 8.
-    //   phase A: read W-lo, W-hi (4 + 4) and A-lo (8); issue W-hi, A-hi of tile t + 1; vmcnt(8): A-hi of tile t has landed
-    //            -> A-lo x W-lo, A-lo x W-hi
-    //   phase B: read A-hi (8); issue W-lo, A-lo of tile t + 2; vmcnt(6): W-lo, A-lo, W-hi of tile t + 1 have landed
-    //            -> A-hi x W-hi, A-hi x W-lo
-    // every load section retires its ds_reads BEFORE its barrier, so a slot may be restaged by the partner wave row in the very next
-    // interval; a landed half-tile is first read one barrier after the wait that covers it.
-    auto main_loop2 = [&](auto swap_c, const int kt0, const int nk, const bool q_valid0, const bool q_valid1) {
         constexpr bool SWAP = decltype(swap_c)::value;
         auto mfma_half = [&](int mi, int ni_first) {
             if (!(mi ? q_valid1 : q_valid0)) return;
@@ -499,10 +406,7 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
             __builtin_amdgcn_s_setprio(0);
         };
         // MODE 0: steady state (tiles t + 1 and t + 2 exist); 1: tile t + 1 is the range's last; 2: tile t is the last
-        // EARLY_WHI: W-hi of tile t + 2 is issued in phase B of tile t together with W-lo and A-lo (its slot is free since phase A)
-        // instead of phase A of tile t + 1: one phase more of flight time, and the DMA issues balance the ds_reads (A: 16 + 2, B: 8 + 6)
-        constexpr bool EARLY_WHI = (PH2V == 2);
-        auto k_tile2 = [&](auto buf_c, auto mode_c, int t) {
+        auto k_tile = [&](auto buf_c, auto mode_c, int t) {
             constexpr int BUF = decltype(buf_c)::value;
             constexpr int MODE = decltype(mode_c)::value;
             // ---- phase A
@@ -516,7 +420,7 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
                 read_a(BUF, 0);
             }
             if constexpr (MODE <= 1) {
-                if constexpr (!EARLY_WHI) issue(2, BUF ^ 1, t + 1);
+                issue(2, BUF ^ 1, t + 1);
                 issue(3, BUF ^ 1, t + 1);
                 wait_vmcnt<8>();
             } else {
@@ -535,8 +439,7 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
             if constexpr (MODE == 0) {
                 issue(0, BUF, t + 2);
                 issue(1, BUF, t + 2);
-                if constexpr (EARLY_WHI) issue(2, BUF, t + 2);
-                wait_vmcnt<EARLY_WHI ? 8 : 6>();
+                wait_vmcnt<6>();
             } else if constexpr (MODE == 1) {
                 wait_vmcnt<2>();
             }
@@ -554,11 +457,11 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
         if (wr == 1) __builtin_amdgcn_s_barrier();
         const int kt_last = kt0 + nk - 2;
         for (int t = kt0; t < kt_last; t += 2) {
-            k_tile2(I0{}, I0{}, t);
-            k_tile2(I1{}, I0{}, t + 1);
+            k_tile(I0{}, I0{}, t);
+            k_tile(I1{}, I0{}, t + 1);
         }
-        k_tile2(I0{}, I1{}, kt_last);
-        k_tile2(I1{}, I2{}, kt_last + 1);
+        k_tile(I0{}, I1{}, kt_last);
+        k_tile(I1{}, I2{}, kt_last + 1);
         if (wr == 0) __builtin_amdgcn_s_barrier();
     };
 
@@ -590,9 +493,9 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
         float a_sc;
     };
     constexpr bool LN_DEFER = LN_CONS && EPI == EPI_SWIGLU;
-    // Half-tiles of a range's DMA prologue: all four of its first K-tile + PRO_T1 of the second.  ONE constant drives the issue loop below and the
+    // Half-tiles of a range's DMA prologue: all four of its first K-tile + PRO_T1 (W-lo, A-lo) of the second.  ONE constant drives the issue loop below and the
     // counted waits that let exactly these stay in flight (PRO_DMA; ADVICE r5: the two used to spell the expression out separately)
-    constexpr int PRO_T1 = (PH2 && PH2V != 2) ? 2 : 3;
+    constexpr int PRO_T1 = 2;
     auto prepare_issue = [&](const Seg& s, [[maybe_unused]] LnPre& st) {
         int tid = tid_;
         asm volatile("" : "+v"(tid));            // (keeps this block's address arithmetic inside the persistent loop, see the epilogue)
@@ -687,7 +590,7 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
         }          // (published by the barriers of the first main loop)
     }
     constexpr int PRO_DMA = 2 * (4 + PRO_T1);          // LDS-DMA instructions per wave of a range's prologue (issue(): two per half-tile)
-    static_assert(PRO_DMA == 12 || PRO_DMA == 14, "prologue = 6 or 7 half-tiles");
+    static_assert(PRO_DMA == 12, "prologue = 6 half-tiles");
     [[maybe_unused]] auto rope_load = [&](f32x4_t& cs, f32x4_t& sn, int row, int q4) {
         const unsigned voff = (unsigned)(row * 16 + 4 * q4) * 4u;
         asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(cs) : "v"(voff), "s"(g.heads.rope_cos) : "memory");
@@ -977,7 +880,7 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
     // and no other vector-memory operation: that is the number the counted wait at the top of the next range adds to its 6.  A store made
     // conditional again, or a second one per block, has to change this line (a build with vmcnt(0) there must give bit-identical results)
     constexpr int SWIGLU_STORES_PER_BLOCK = 1;
-    constexpr int EPI_STORES = (EPI == EPI_SWIGLU && FP8 == 0 && (DBG == 0 || DBG == 9) && PH2 && PH2V == 1) ? MB * SWIGLU_STORES_PER_BLOCK : -1;
+    constexpr int EPI_STORES = (EPI == EPI_SWIGLU && FP8 == 0) ? MB * SWIGLU_STORES_PER_BLOCK : -1;
     static_assert(EPI_STORES < 0 || 6 + EPI_STORES <= 63, "vmcnt is a 6-bit counter");
     [[maybe_unused]] bool stores_behind = false;
     LnPre lnpre;
@@ -1024,22 +927,12 @@ __global__ __launch_bounds__(2 * WN * 64) void gemm_ph8_kernel(GemmArgs g, Ph8Sc
         }
         wait_lgkmcnt<0>();
         __builtin_amdgcn_s_barrier();
-        if constexpr (DBG == 2) {       // ablation: fragments are read once
-            read_w(0, 0, fwl);
-            read_w(0, 1, fwh);
-            read_a(0, 0);
-        }
         [[maybe_unused]] unsigned long long t0 = 0, t1 = 0, t2 = 0;
         if constexpr (DBG == 9) t0 = __builtin_amdgcn_s_memrealtime();
         const int mq = cur.m0 + wr * WR;
         const bool rows_valid = mq < M;
-        if constexpr (PH2) {
-            if (cur.tr) main_loop2(std::true_type{}, cur.kt0, cur.nk, rows_valid, mq + QR < M);
-            else main_loop2(std::false_type{}, cur.kt0, cur.nk, rows_valid, mq + QR < M);
-        } else {
-            if (cur.tr) main_loop(std::true_type{}, cur.kt0, cur.nk, rows_valid, mq + QR < M);
-            else main_loop(std::false_type{}, cur.kt0, cur.nk, rows_valid, mq + QR < M);
-        }
+        if (cur.tr) main_loop(std::true_type{}, cur.kt0, cur.nk, rows_valid, mq + QR < M);
+        else main_loop(std::false_type{}, cur.kt0, cur.nk, rows_valid, mq + QR < M);
         if constexpr (DBG == 9) t1 = __builtin_amdgcn_s_memrealtime();
         const bool more = next_seg(nxt);
         [[maybe_unused]] RopePre rp;
@@ -1129,8 +1022,7 @@ int ph8_schedule(const GemmArgs& a, bool epi_f32, int bm, int bn, int wgs_per_cu
     // assumes (GemmShape::slab_ok); an undersized workspace runs the unsplit schedule.  A FORCED split keeps the hard error.
     const int split = sat_variant_split(a.variant);
     const bool have_slab = a.slab != nullptr && (split >= 0 || a.slab_bytes >= (size_t)cus * 65536 * sizeof(float));
-    const int balance = (sat_variant_has(a.variant, SAT_VARIANT_BALANCE_OFF) ? PH8_BALANCE_OFF : 0) |
-                        (SAT_GEMM_EXP && sat_variant_has(a.variant, SAT_VARIANT_BALANCE_ANY) ? PH8_BALANCE_ANY : 0);
+    const int balance = sat_variant_has(a.variant, SAT_VARIANT_BALANCE_OFF) ? PH8_BALANCE_OFF : PH8_BALANCE_TWO_ROUNDS;
     const long used = ph8_schedule_ints(a.M, a.N, a.K, split, epi_f32, bm, bn, wgs_per_cu, cus, have_slab, balance, s);
     SAT_CHECK_ARG(used == 0, SAT_E_INVALID, "gemm(8-phase): the K-split needs %ld workgroups, has %d", used, s.G);
     if (s.split) {
@@ -1147,7 +1039,7 @@ int ph8_schedule(const GemmArgs& a, bool epi_f32, int bm, int bn, int wgs_per_cu
 unsigned long long* g_ts_buf = nullptr;
 #endif
 
-template <int EPI, int DBG = 0, bool PH2 = true, int PH2V = 1, int WN = 4, int MFQ = 4, int FP8 = 0, bool GATED = false>
+template <int EPI, int DBG = 0, int FP8 = 0, bool GATED = false>
 int launch_ph8(const GemmArgs& a0, hipStream_t stream) {
     GemmArgs a = a0;
     if constexpr (FP8 != 0) {
@@ -1160,7 +1052,7 @@ int launch_ph8(const GemmArgs& a0, hipStream_t stream) {
     } else {
         SAT_CHECK_ARG(!a.fp8 && !a.H8, SAT_E_UNSUPPORTED, "gemm(8-phase): built for bf16 operands");
     }
-    constexpr int BM = 64 * MFQ, BN = 64 * WN, NT = 2 * WN * 64;
+    constexpr int BM = 256, BN = 256, NT = 512;
     constexpr int LDS = 2 * 2 * (BM / 2 + BN / 2) * 128 + 2 * (BM + BN) * 8 + (EPI == EPI_HEADS ? 128 : 0);          // ring + 2 x ((mean, rstd) per row + (c1, c2) per column) + rotation constants
     SAT_CHECK_ARG(a.N % BN == 0, SAT_E_UNSUPPORTED, "gemm(8-phase): N=%d not a multiple of %d", a.N, BN);
     SAT_CHECK_ARG(a.K % 128 == 0, SAT_E_UNSUPPORTED, "gemm(8-phase): K=%d must be a multiple of 128", a.K);
@@ -1181,9 +1073,9 @@ int launch_ph8(const GemmArgs& a0, hipStream_t stream) {
         SAT_CHECK_ARG(!a.heads.xa_k, SAT_E_UNSUPPORTED, "gemm(8-phase): the fused cross-attention epilogue lives in the 128 x 64 tile");
     }
     Ph8Sched sc;
-    SAT_TRY(ph8_schedule(a, EPI == EPI_F32, BM, BN, BM == 256 ? 1 : 2, sc));
+    SAT_TRY(ph8_schedule(a, EPI == EPI_F32, BM, BN, 1, sc));
     SAT_CHECK_ARG(GATED == (a0.gate != nullptr), SAT_E_INVALID, "gemm(8-phase): gated / plain build mismatch");
-    auto kern = gemm_ph8_kernel<EPI, DBG, PH2, PH2V, WN, MFQ, FP8, GATED>;
+    auto kern = gemm_ph8_kernel<EPI, DBG, FP8, GATED>;
     SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS));
     unsigned long long* ts = nullptr;
 #ifdef SAT_GEMM_EXPERIMENTS
@@ -1202,7 +1094,7 @@ int launch_ph8(const GemmArgs& a0, hipStream_t stream) {
 template <int EPI, int BUILD>
 int launch_ph8_build(const GemmArgs& a, hipStream_t stream) {
     constexpr SatPh8Params p = sat_ph8_params(BUILD);
-    return launch_ph8<EPI, p.dbg, p.ph2, p.ph2v, p.wn, p.mfq, p.fp8, p.gated>(a, stream);
+    return launch_ph8<EPI, p.dbg, p.fp8, p.gated>(a, stream);
 }
 
 // the builds that exist for one epilogue (sat_ph8_route, gemm_tiles.h, hands out no others)
@@ -1219,23 +1111,7 @@ int launch_ph8_epi(int build, const GemmArgs& a, hipStream_t stream) {
             break;
 #endif
 #ifdef SAT_GEMM_EXPERIMENTS
-        case SAT_PH8_FOUR_PHASE:
-            if constexpr (EPI != EPI_HEADS) return launch_ph8_build<EPI, SAT_PH8_FOUR_PHASE>(a, stream);
-            break;
-        case SAT_PH8_WHI_EARLY:
-            if constexpr (EPI != EPI_HEADS) return launch_ph8_build<EPI, SAT_PH8_WHI_EARLY>(a, stream);
-            break;
-        case SAT_PH8_ABLATION_1:
-            if constexpr (EPI == EPI_F32) return launch_ph8_build<EPI, SAT_PH8_ABLATION_1>(a, stream);
-            break;
-        case SAT_PH8_ABLATION_2:
-            if constexpr (EPI == EPI_F32) return launch_ph8_build<EPI, SAT_PH8_ABLATION_2>(a, stream);
-            break;
-        case SAT_PH8_ABLATION_3:
-            if constexpr (EPI == EPI_F32) return launch_ph8_build<EPI, SAT_PH8_ABLATION_3>(a, stream);
-            break;
         case SAT_PH8_TIMESTAMPS: return launch_ph8_build<EPI, SAT_PH8_TIMESTAMPS>(a, stream);
-        case SAT_PH8_GEOM_128: return launch_ph8_build<EPI, SAT_PH8_GEOM_128>(a, stream);
 #endif
     }
     sat_set_error("gemm(8-phase): build %d does not exist for epilogue %d", build, EPI);

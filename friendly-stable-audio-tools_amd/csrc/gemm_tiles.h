@@ -13,22 +13,17 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // ---------------------------------------------------------------------------------------------------------------------------------
 // GemmArgs::variant (and the `variant` argument of the unit-level C ABI: sat_gemm_bf16_f32 and friends).  The layout is ABI: tests
 // and tools/*.py pass these numbers.  "exp" = read in the experiments build only (make -C csrc exp), ignored by the shipped one.
+// Bits 12, 13, 15, 18, 19, 22 are unassigned and not read (retired variants: profiles/HISTORY.md names them, so they are not reused).
 //   bits  0-7   SAT_VARIANT_TILE        forced tile id, 0 = let sat_gemm_route choose                    sat_gemm_route
-//   bits  0-11  SAT_VARIANT_CODE        read as a decimal number: code % 100 = 80 / 81 forces the 8-phase kernel (81 exp: its
-//                                       128 x 128 geometry), code / 100 = its ablation mode (1-3, 9: exp)   sat_gemm_route
+//   bits  0-11  SAT_VARIANT_CODE        read as a decimal number: code % 100 = 80 / 81 forces the 8-phase kernel (81 was its retired
+//                                       128 x 128 geometry and runs 80), code / 100 = 9: its timestamp build (exp)   sat_gemm_route
 //   bit   8     SAT_VARIANT_FP8_PLAIN   sat_gemm_fp8_f32 only, stripped there: plain fp8 MFMA (GemmArgs::fp8 = 1) instead of the
 //                                       2x-rate block-scaled one (2)                                      unit_entry.hip
-//   bit  12     SAT_VARIANT_EPI_UNSWAPPED   exp: force the un-swapped accumulator orientation             gemm_pipe_kernel
-//   bit  13     SAT_VARIANT_EPI_F32_TR      exp: transposed fp32 epilogue                                 gemm_pipe_kernel
-//   bit  15     SAT_VARIANT_EPI_F32_DIRECT  exp: direct dword fp32 epilogue                               gemm_pipe_kernel
 //   bit  14     SAT_VARIANT_PACKED      unit-level SwiGLU / LayerNorm-fold entry points only, stripped there: the packed operands
 //                                       are those of a previous call (benchmarks)                         unit_entry.hip
 //   bit  16     SAT_VARIANT_SPLIT_FORCE     8-phase: cut the remainder round along K whatever the policy says (tests)
 //   bit  17     SAT_VARIANT_SPLIT_OFF       8-phase: never                                                launch_ph8, sat_gemm_f32_workspace_bytes
-//   bit  18     SAT_VARIANT_PH8_FOUR_PHASE  exp: the four-phase main loop                                 sat_gemm_route
-//   bit  19     SAT_VARIANT_PH8_WHI_EARLY   exp: W-hi issued one phase earlier                            sat_gemm_route
 //   bit  21     SAT_VARIANT_BALANCE_OFF     8-phase: no balanced rounds (A/B)                             launch_ph8
-//   bit  22     SAT_VARIANT_BALANCE_ANY     exp: balanced rounds at any round count                       launch_ph8
 //   bit  23     SAT_VARIANT_NO_KGROUP   never the two-K-group 128 x 128 tile (49)                         sat_gemm_route
 //   bits 24-26  tile policy (sat_tile_policy_bits / sat_wide_tile_of): sat_dit_cfg.tile_policy puts them there for every GEMM of a
 //               plan; the unit-level entry points leave them 0                                            sat_gemm_route
@@ -37,16 +32,10 @@ enum {
     SAT_VARIANT_TILE = 0xff,
     SAT_VARIANT_CODE = 0xfff,
     SAT_VARIANT_FP8_PLAIN = 0x100,
-    SAT_VARIANT_EPI_UNSWAPPED = 0x1000,
-    SAT_VARIANT_EPI_F32_TR = 0x2000,
     SAT_VARIANT_PACKED = 0x4000,
-    SAT_VARIANT_EPI_F32_DIRECT = 0x8000,
     SAT_VARIANT_SPLIT_FORCE = 0x10000,
     SAT_VARIANT_SPLIT_OFF = 0x20000,
-    SAT_VARIANT_PH8_FOUR_PHASE = 0x40000,
-    SAT_VARIANT_PH8_WHI_EARLY = 0x80000,
     SAT_VARIANT_BALANCE_OFF = 0x200000,
-    SAT_VARIANT_BALANCE_ANY = 0x400000,
     SAT_VARIANT_NO_KGROUP = 0x800000,
 };
 static inline int sat_variant_tile(int variant) { return variant & SAT_VARIANT_TILE; }
@@ -67,8 +56,8 @@ static inline int sat_wide_tile_of(int variant) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// Tiles.  The ids are the numbers of round 1 and part of the ABI; everything that is not listed as shipped was an experiment and
-// lives behind -DSAT_GEMM_EXPERIMENTS (profiles/r01_gemm_variants*.txt has what they measured).
+// Tiles.  The ids are the numbers of round 1 and part of the ABI.  Reserved, never to be reused (retired experiments that the files
+// under profiles/ name by number): 2, 3, 7, 10, 12, 13, 39, 41-43, 45-48, 54-56, 60.
 // ---------------------------------------------------------------------------------------------------------------------------------
 enum SatGemmFamily {
     SAT_GEMM_NONE = 0,
@@ -93,24 +82,8 @@ enum SatTileId {
     SAT_TILE_128_KGROUP = 49,      // 128x128 on two K-groups of 2 x 2 waves (64 x 64 each), 2 x 64 k per stage, 2 stages, fp32 output only:
                                    // one round of 128x128 tiles (to_out / FF-out at 1 prompt)
     SAT_TILE_PH8 = 80,             // 256x256x64, 8 waves, 8-phase schedule: FF-in always, every wide GEMM from 4 prompts on
-    SAT_TILE_PH8_128 = 81,         // experiments: its 128x128 geometry (4 waves, two workgroups per CU); the shipped build runs 80 for it
     SAT_TILE_128x64_XATTN = 256,   // tile 16 with the pieces in front of the loop body and the fused cross-attention epilogue (heads
                                    // epilogue only).  Not a value of the tile field: chosen by GemmArgs::heads.xa_k alone
-    // experiments build only
-    SAT_TILE_X_REG_256x128 = 2, SAT_TILE_X_REG_256 = 3, SAT_TILE_X_DMA_256 = 7,
-    SAT_TILE_X_128_4W = 10, SAT_TILE_X_256x128 = 12, SAT_TILE_X_256_BK32 = 13,
-    SAT_TILE_X_128_BK128 = 39,     // 256-B rows: half the barriers per k
-    SAT_TILE_X_256x128_BK32 = 41,  // 72 KiB, <= 128 VGPRs: two workgroups per CU
-    SAT_TILE_X_128_4W_DEEP = 42,   // 4 waves of 64x64 (half the LDS reads per MFMA of tile 15), 4 stages
-    SAT_TILE_X_128_4W_2ST = 43,    // same, 2 stages = 64 KiB: two workgroups per CU
-    SAT_TILE_X_128_DEEP5 = 45,     // prefetch distance 4 (160 KiB), fp32 output only
-    SAT_TILE_X_128x64_DEEP5 = 46,  // tile 16 with prefetch distance 4
-    SAT_TILE_X_128x64_DEEP6 = 47,  //                               distance 5 (144 KiB)
-    SAT_TILE_X_128_BK128_4W = 48,  // tile 39 on 4 waves of 64x64 (the vendor library's pick for FF-out at one prompt)
-    SAT_TILE_X_128_DEEP_DIL = 54,  // tiles 44 / 15 / 30 with the LDS-DMA pieces in the MFMA stream (A/B)
-    SAT_TILE_X_128_DIL = 55,
-    SAT_TILE_X_128x64_FRONT = 56,  // tile 16 with its pieces in front of the loop body (A/B)
-    SAT_TILE_X_256x192_DIL = 60,
 };
 
 struct SatTile {
@@ -133,27 +106,6 @@ constexpr SatTile sat_tile_geom(int id) {
         case SAT_TILE_128_DEEP: return {SAT_GEMM_PIPE, 128, 128, 64, 4, 2, 4, 1, false, true};
         case SAT_TILE_128_KGROUP: return {SAT_GEMM_PIPE, 128, 128, 64, 2, 2, 2, 2, false, true};
         case SAT_TILE_PH8: return {SAT_GEMM_PH8, 256, 256, 64, 2, 4, 2, 1, false, false};
-        case SAT_TILE_PH8_128: return {SAT_GEMM_PH8, 128, 128, 64, 2, 2, 2, 1, false, false};
-#ifdef SAT_GEMM_EXPERIMENTS
-        case SAT_TILE_X_REG_256x128: return {SAT_GEMM_REG, 256, 128, 64, 4, 2, 2, 1, false, false};
-        case SAT_TILE_X_REG_256: return {SAT_GEMM_REG, 256, 256, 64, 2, 4, 2, 1, false, false};
-        case SAT_TILE_X_DMA_256: return {SAT_GEMM_DMA2, 256, 256, 64, 2, 4, 2, 1, false, false};
-        case SAT_TILE_X_128_4W: return {SAT_GEMM_PIPE, 128, 128, 64, 2, 2, 3, 1, false, false};
-        case SAT_TILE_X_256x128: return {SAT_GEMM_PIPE, 256, 128, 64, 4, 2, 3, 1, false, false};
-        case SAT_TILE_X_256_BK32: return {SAT_GEMM_PIPE, 256, 256, 32, 2, 4, 3, 1, false, false};
-        case SAT_TILE_X_128_BK128: return {SAT_GEMM_PIPE, 128, 128, 128, 4, 2, 2, 1, false, false};
-        case SAT_TILE_X_256x128_BK32: return {SAT_GEMM_PIPE, 256, 128, 32, 4, 2, 3, 1, false, false};
-        case SAT_TILE_X_128_4W_DEEP: return {SAT_GEMM_PIPE, 128, 128, 64, 2, 2, 4, 1, false, false};
-        case SAT_TILE_X_128_4W_2ST: return {SAT_GEMM_PIPE, 128, 128, 64, 2, 2, 2, 1, false, false};
-        case SAT_TILE_X_128_DEEP5: return {SAT_GEMM_PIPE, 128, 128, 64, 4, 2, 5, 1, false, true};
-        case SAT_TILE_X_128x64_DEEP5: return {SAT_GEMM_PIPE, 128, 64, 64, 4, 1, 5, 1, false, false};
-        case SAT_TILE_X_128x64_DEEP6: return {SAT_GEMM_PIPE, 128, 64, 64, 4, 1, 6, 1, false, false};
-        case SAT_TILE_X_128_BK128_4W: return {SAT_GEMM_PIPE, 128, 128, 128, 2, 2, 2, 1, false, false};
-        case SAT_TILE_X_128_DEEP_DIL: return {SAT_GEMM_PIPE, 128, 128, 64, 4, 2, 4, 1, true, true};
-        case SAT_TILE_X_128_DIL: return {SAT_GEMM_PIPE, 128, 128, 64, 4, 2, 3, 1, true, false};
-        case SAT_TILE_X_128x64_FRONT: return {SAT_GEMM_PIPE, 128, 64, 64, 4, 1, 3, 1, false, false};
-        case SAT_TILE_X_256x192_DIL: return {SAT_GEMM_PIPE, 256, 192, 64, 4, 3, 2, 1, true, false};
-#endif
         default: return {SAT_GEMM_NONE, 0, 0, 0, 0, 0, 0, 0, false, false};
     }
 }
@@ -163,33 +115,18 @@ enum SatPh8Build {
     SAT_PH8_PLAIN = 0,
     SAT_PH8_GATED,           // fp32 output with the adaLN gate
     SAT_PH8_E4M3,            // e4m3 operands on the block-scaled MFMA (SwiGLU / heads; bf16 build of the library only)
-    // experiments build only
-    SAT_PH8_FOUR_PHASE,      // the four-phase main loop (fp32 output, SwiGLU)
-    SAT_PH8_WHI_EARLY,       // W-hi issued one phase earlier (fp32 output, SwiGLU)
-    SAT_PH8_ABLATION_1, SAT_PH8_ABLATION_2, SAT_PH8_ABLATION_3,          // fp32 output
-    SAT_PH8_TIMESTAMPS,      // ablation code 9
-    SAT_PH8_GEOM_128,        // The 128 x 128 geometry (4 waves, two workgroups per CU): measured SLOWER than the 16-wave-family tiles at every
-                             // one-prompt shape (FF-out 69.5 us vs 62.3, to_out 26.8 vs 22.4, cross 25.0 vs 16.2, QKV 68 vs 51;
-                             // profiles/r03_ph8_128x128_geometry_negative.txt) -- 16 MFMAs between barriers and half the operand reuse per LDS byte.
+    SAT_PH8_TIMESTAMPS,      // experiments build only: ablation code 9
 };
 struct SatPh8Params {
-    int dbg;
-    bool ph2;
-    int ph2v, wn, mfq, fp8;
+    int dbg, fp8;
     bool gated;
 };
 constexpr SatPh8Params sat_ph8_params(int build) {
     switch (build) {
-        case SAT_PH8_GATED: return {0, true, 1, 4, 4, 0, true};
-        case SAT_PH8_E4M3: return {0, true, 1, 4, 4, 2, false};
-        case SAT_PH8_FOUR_PHASE: return {0, false, 1, 4, 4, 0, false};
-        case SAT_PH8_WHI_EARLY: return {0, true, 2, 4, 4, 0, false};
-        case SAT_PH8_ABLATION_1: return {1, false, 1, 4, 4, 0, false};
-        case SAT_PH8_ABLATION_2: return {2, false, 1, 4, 4, 0, false};
-        case SAT_PH8_ABLATION_3: return {3, false, 1, 4, 4, 0, false};
-        case SAT_PH8_TIMESTAMPS: return {9, true, 1, 4, 4, 0, false};
-        case SAT_PH8_GEOM_128: return {0, true, 1, 2, 2, 0, false};
-        default: return {0, true, 1, 4, 4, 0, false};
+        case SAT_PH8_GATED: return {0, 0, true};
+        case SAT_PH8_E4M3: return {0, 2, false};
+        case SAT_PH8_TIMESTAMPS: return {9, 0, false};
+        default: return {0, 0, false};
     }
 }
 
@@ -209,7 +146,6 @@ struct GemmShape {          // what the rule reads of a GemmArgs, the build and 
     bool xattn;              // heads.xa_k: fused cross-attention
     bool slab_ok;            // GemmArgs::slab holds one accumulator image (65536 floats) per compute unit
     bool e4m3_built;         // this build of the library has the e4m3 instantiations (the fp16 build has none)
-    bool no_deep_ring;       // experiments build, SAT_GEMM_NO_DEEP=1: keep the 3-stage ring for FF-out (A/B)
 };
 enum SatRouteMsg {
     SAT_ROUTE_OK = 0,
@@ -253,20 +189,12 @@ inline GemmRoute sat_ph8_route(int epi, const GemmShape& s) {
     GemmRoute r{SAT_ROUTE_OK, SAT_GEMM_PH8, SAT_TILE_PH8, 0, SAT_PH8_PLAIN, false};
     const int dbg = sat_variant_ablation(s.variant);
     const bool f32 = epi == EPI_F32 || epi == EPI_RESID, swiglu = epi == EPI_SWIGLU, heads = epi == EPI_HEADS;
-    if (SAT_GEMM_EXP && sat_variant_ph8_code(s.variant) == 81 && (f32 || swiglu || heads)) {
-        r.tile = SAT_TILE_PH8_128;
-        r.ph8 = SAT_PH8_GEOM_128;
-        return r;
-    }
     if (dbg == 0 && (f32 || swiglu || heads)) {
-        if (SAT_GEMM_EXP && !heads && sat_variant_has(s.variant, SAT_VARIANT_PH8_FOUR_PHASE)) r.ph8 = SAT_PH8_FOUR_PHASE;
-        else if (SAT_GEMM_EXP && !heads && sat_variant_has(s.variant, SAT_VARIANT_PH8_WHI_EARLY)) r.ph8 = SAT_PH8_WHI_EARLY;
-        else if (f32) r.ph8 = s.gate ? SAT_PH8_GATED : SAT_PH8_PLAIN;
+        if (f32) r.ph8 = s.gate ? SAT_PH8_GATED : SAT_PH8_PLAIN;
         else r.ph8 = (s.e4m3_built && s.fp8) ? SAT_PH8_E4M3 : SAT_PH8_PLAIN;
         return r;
     }
     if (SAT_GEMM_EXP && dbg == 9 && (f32 || swiglu || heads)) r.ph8 = SAT_PH8_TIMESTAMPS;
-    else if (SAT_GEMM_EXP && f32 && dbg >= 1 && dbg <= 3) r.ph8 = SAT_PH8_ABLATION_1 + (dbg - 1);
     else {
         r.msg = SAT_ROUTE_PH8_NOT_BUILT;
         r.tile = dbg;
@@ -333,7 +261,7 @@ inline GemmRoute sat_gemm_route(int epi, const GemmShape& s, int cus_) {
             if (s.K < 384 && (v == SAT_TILE_128 || v == SAT_TILE_128x64)) v = SAT_TILE_256;     // the 3-stage tiles need K >= 384 bytes
         } else {
             // long reductions (FF-out: 96 K-tiles) gain 4 % from a fourth ring stage (prefetch distance 3); K = 1536 does not care
-            if (v == SAT_TILE_128 && f32 && s.K >= 4096 && !s.no_deep_ring) v = SAT_TILE_128_DEEP;
+            if (v == SAT_TILE_128 && f32 && s.K >= 4096) v = SAT_TILE_128_DEEP;
             // one round of 128 x 128 tiles (to_out / FF-out at one prompt: 204 workgroups on 256 CUs): the two-K-group build puts 8 waves of
             // 64 x 64 on every CU instead of 8 waves of 32 x 64 -- FF-out 56.5 us against 60.7, to_out 20.6 against 21.4 (tools/ph8_probe.py narrow)
             if ((v == SAT_TILE_128 || v == SAT_TILE_128_DEEP) && f32 && !s.fp8 && s.K % 128 == 0 && s.K >= 256 &&

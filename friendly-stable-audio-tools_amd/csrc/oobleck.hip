@@ -662,16 +662,6 @@ struct Snake {
     int act = ACT_SNAKE;
 };
 inline int pad64(int c) { return (int)round_up(c, 64); }
-// experiments build only: SAT_OOBLECK_UNFUSED=1 in the environment runs every ResidualUnit as two launches (conv7, conv1) for A/B
-// measurements (tools/codec_only.py)
-#ifdef SAT_GEMM_EXPERIMENTS
-const bool g_ru_unfused = [] {
-    const char* e = getenv("SAT_OOBLECK_UNFUSED");
-    return e && e[0] == '1';
-}();
-#else
-constexpr bool g_ru_unfused = false;
-#endif
 struct ConvW {
     op_t* W = nullptr;
     float* bias = nullptr;
@@ -929,7 +919,7 @@ int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const
     c.out_raw = need_raw ? R : nullptr;   // in place: each thread reads then writes its own elements
     set_act(c, Sout, next);
 #if !SAT_OP_IS_F32      // (fp32 build: the 128 x C intermediate would not fit next to the weight ring; two launches through Y)
-    if (!g_ru_unfused && (C == 128 || C == 256)) {      // the whole unit in one launch, the intermediate never leaves LDS
+    if (C == 128 || C == 256) {      // the whole unit in one launch, the intermediate never leaves LDS
         RuArgs f{a, c};
         f.c7.out_snk = nullptr;
         f.c1.in = nullptr;

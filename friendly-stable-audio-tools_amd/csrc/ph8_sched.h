@@ -121,8 +121,8 @@ inline bool ph8_auto_split(int M, int N, int K, bool epi_f32, int cus) {
     return epi_f32 && K >= 4096 && t_all > cus && rem > 0 && 2 * rem <= cus;
 }
 
-// `balance` argument of ph8_schedule_ints: two independent switches (bits)
-enum { PH8_BALANCE_TWO_ROUNDS = 0, PH8_BALANCE_OFF = 1, PH8_BALANCE_ANY = 2 };
+// `balance` argument of ph8_schedule_ints
+enum { PH8_BALANCE_TWO_ROUNDS = 0, PH8_BALANCE_OFF = 1 };
 
 // The schedule of one launch on `cus` compute units.
 // split: 0 = the remainder round's tiles stay whole (contiguous shares, light tiles last), 1 = every remainder tile is cut along K
@@ -149,10 +149,6 @@ inline long ph8_schedule_ints(int M, int N, int K, int split, bool epi_f32, int 
     // less than a half-empty second round: FF-out at 8 prompts 336 -> 311 us, FF-in at one prompt 85.4 -> 82.6 us.  With many rounds it
     // loses (FF-in at 8 prompts, 12.2 rounds: 479 -> 488 us): profiles/r04_ph8_balanced_rounds.txt.  PH8_BALANCE_OFF switches it off (A/B).
     if (!split && !(balance & PH8_BALANCE_OFF) && t_all > s.G && t_all <= 2L * s.G) s.G = (int)((t_all + 1) / 2);
-    if (!split && (balance & PH8_BALANCE_ANY) && t_all > s.G) {          // (A/B, experiments build): balanced rounds at any round count
-        const long rounds = (t_all + s.G - 1) / s.G;
-        s.G = (int)((t_all + rounds - 1) / rounds);
-    }
     s.dp_rounds = (int)((split ? t_all : t_full) / s.G);
     // K-split with at least one whole round: the light tiles go FIRST (they idle their workgroup for half of round 0 -- a handful of
     // them) so that the remainder round holds full tiles only and splits evenly

@@ -26,12 +26,13 @@ static int routes(bool with_split) {
             printf("err %d\n", route_error_code(r.msg));
         } else if (r.family == SAT_GEMM_PH8) {
             const SatPh8Params p = sat_ph8_params(r.ph8);
-            printf("ph8 %d %d %d %d %d %d %d %d", tepi, p.dbg, (int)p.ph2, p.ph2v, p.wn, p.mfq, p.fp8, (int)p.gated);
+            // (the fixture's lines record `dbg ph2 ph2v wn mfq fp8 gated`; the four in the middle were template parameters of retired variants
+            // of the kernel -- four-phase loop, W-hi issue order, 128 x 128 geometry -- and are now the constants 1 1 4 4)
+            printf("ph8 %d %d 1 1 4 4 %d %d", tepi, p.dbg, p.fp8, (int)p.gated);
             if (with_split) {          // what the score assumed, and what the schedule of that launch does (launch_ph8: slab_ok = have_slab)
                 Ph8Sched sc;
-                const int bm = 64 * p.mfq, bn = 64 * p.wn;
                 // (K / 2 for e4m3 operands mirrors launch_ph8, gemm_ph8.hip: `a.K = a0.K / 2` -- the kernel and its schedule count 16-bit columns)
-                ph8_schedule_ints(M, N, p.fp8 ? K / 2 : K, sat_variant_split(variant), tepi == EPI_F32, bm, bn, bm == 256 ? 1 : 2, cus, slab != 0, 0, sc);
+                ph8_schedule_ints(M, N, p.fp8 ? K / 2 : K, sat_variant_split(variant), tepi == EPI_F32, 256, 256, 1, cus, slab != 0, 0, sc);
                 printf(" splits=%d schedule.split=%d", (int)r.splits, sc.split);
             }
             printf("\n");

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Compare the device assembly (hipcc --cuda-device-only -S) of two builds of one source file function by function.
 
-usage: asm_compare.py A.s B.s   (or two directories of *.s files with the same names)
+usage: asm_compare.py [--rename OLD=NEW]... [--subset] A.s B.s   (or two directories of *.s files with the same names)
+  --rename OLD=NEW   replace OLD by NEW in A's text first: a kernel whose template parameter list changed carries a new mangled name
+  --subset           B may lack functions of A (retired template instantiations); what B has must be A's, nothing may be new
 
 A refactor that only moves host code or changes the order in which templates are instantiated leaves every kernel's instructions
 alone but may reorder the functions of the file, which renumbers the local labels (.LBB<function>_<block>), and the compilation-unit
@@ -12,10 +14,13 @@ status 1 if anything differs."""
 import os
 import re
 import sys
+from collections import Counter
 
 
-def functions(path):
+def functions(path, renames=()):
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", open(path).read())
+    for old, new in renames:
+        text = text.replace(old, new)
     text = re.sub(r"\.(LBB|Lfunc_end|Lfunc_begin|LJTI|Ltmp)(\d+)(_?)", lambda m: "." + m.group(1) + ("_" if m.group(3) else ""), text)
     out, rest = {}, []
     name, body = None, []
@@ -46,10 +51,14 @@ def functions(path):
     return out, meta, head
 
 
-def compare(a, b):
-    fa, ma, ha = functions(a)
+def compare(a, b, renames=(), subset=False):
+    fa, ma, ha = functions(a, renames)
     fb, mb, hb = functions(b)
     problems = []
+    if subset:          # A keeps only what B also has; anything of B that A lacks still shows below
+        fa = {k: v for k, v in fa.items() if k in fb}
+        ma = [m for m in ma if m in mb]
+        ha = "\n".join(sorted((Counter(ha.split("\n")) & Counter(hb.split("\n"))).elements()))
     if set(fa) != set(fb):
         problems.append(f"symbols differ: only A {sorted(set(fa) - set(fb))[:3]} only B {sorted(set(fb) - set(fa))[:3]}")
     problems += [f"body differs: {k}" for k in sorted(set(fa) & set(fb)) if fa[k] != fb[k]]
@@ -58,15 +67,25 @@ def compare(a, b):
     if ha != hb:
         problems.append("file-level lines differ")
     same_order = list(fa) == list(fb)
-    return problems, len(fa), same_order
+    return problems, len(fb), same_order
 
 
 def main():
-    a, b = sys.argv[1:3]
+    args = sys.argv[1:]
+    renames, subset = [], False
+    while args and args[0].startswith("--"):
+        if args[0] == "--subset":
+            subset = True
+            args = args[1:]
+        else:
+            assert args[0] == "--rename", __doc__
+            renames.append(tuple(args[1].split("=", 1)))
+            args = args[2:]
+    a, b = args
     pairs = [(os.path.join(a, f), os.path.join(b, f)) for f in sorted(os.listdir(a)) if f.endswith(".s")] if os.path.isdir(a) else [(a, b)]
     bad = 0
     for x, y in pairs:
-        problems, n, same_order = compare(x, y)
+        problems, n, same_order = compare(x, y, renames, subset)
         status = "IDENTICAL" if not problems else "DIFFERENT"
         print(f"{status}  {os.path.basename(x)}: {n} functions, {'same order' if same_order else 'order differs'}" + "".join("\n    " + p for p in problems[:8]))
         bad += bool(problems)

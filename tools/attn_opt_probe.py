@@ -1,4 +1,4 @@
-"""A/B of the attention kernel's softmax recurrences (attn_core.h MODE 0 / 1 / 2; experiments build, SAT_ATTN_MODE read at every launch): time at the four shipped shapes and
+"""A/B of the attention kernel's softmax recurrences (attn_core.h MODE 1 / 2; experiments build, SAT_ATTN_MODE read at every launch): time at the four shipped shapes and
 error against an fp32 softmax(QK^T/8)V of the same bf16 inputs.    python tools/attn_opt_probe.py [opts...]"""
 import os, sys
 sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/friendly-stable-audio-tools_amd")
@@ -6,7 +6,7 @@ import torch
 from stable_audio_tools import _hip
 _hip.LIB_PATH = os.path.join(os.path.dirname(_hip.LIB_PATH), os.environ.get("SAT_PROBE_LIB", "libsat_hip_exp.so"))
 lib = _hip.lib(); dev = torch.device("cuda:0")
-opts = [int(a) for a in sys.argv[1:]] or [0, 1, 2]
+opts = [int(a) for a in sys.argv[1:]] or [1, 2]
 
 
 def timeit(fn, iters=20, warm=3):

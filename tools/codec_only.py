@@ -1,5 +1,5 @@
 """Developer probe: full-size Oobleck decode (1024 latent frames) and encode (the same audio back) alone, for rocprofv3 / A-B runs
-of the codec kernels (SAT_HIP_EXP=1 SAT_OOBLECK_UNFUSED=1: experiments build, two launches per ResidualUnit).  Not part of the product or the tests.
+of the codec kernels.  Not part of the product or the tests.
 Usage: python tools/codec_only.py [fp16|bf16|fp32]   (operand format of the codec kernels; default: the package default).
 CODEC_CONFIG picks the shape: full (default, the Stable Audio VAE), full_nearest (the same with use_nearest_upsample=True: three-tap
 polyphase upsamplers), small16 (16 channels, stage widths 16 ... 256, padded to 64 ... 256 inside the plan) or small64 (64 channels,
@@ -19,8 +19,6 @@ from stable_audio_tools.models import _init
 
 from stable_audio_tools import _hip
 
-if os.environ.get("SAT_HIP_EXP"):       # experiments build: honours SAT_OOBLECK_UNFUSED=1
-    _hip.LIB_PATH = os.path.join(os.path.dirname(_hip.LIB_PATH), "libsat_hip_exp.so")
 dev = torch.device("cuda:0")
 config = MC.stable_audio_vae()
 which = os.environ.get("CODEC_CONFIG", "full")

@@ -14,7 +14,7 @@ import torch
 from stable_audio_tools import _hip
 
 dev = torch.device("cuda:0")
-if os.environ.get("SAT_HIP_EXP"):       # developer build with the experimental tiles / ablation modes (make -C csrc exp)
+if os.environ.get("SAT_HIP_EXP"):       # developer build with the instruments of the shipped kernels (make -C csrc exp)
     _hip.LIB_PATH = os.path.join(os.path.dirname(_hip.LIB_PATH), "libsat_hip_exp.so")
 if os.environ.get("SAT_HIP_LIB"):       # another build of the library (tools/ab/*.so: same-box comparisons against an earlier round)
     _hip.LIB_PATH = os.path.join(ROOT, os.environ["SAT_HIP_LIB"])
@@ -94,20 +94,13 @@ def gemm_bench():
 
 
 def epi_ab():
-    """A/B of the accumulator orientation (transposed: lane = token, 16-byte stores | legacy: lane = channel, bit 12 of the variant)
-    on the shipped tiles at the shapes the plan launches, all three epilogues, interleaved rounds, median of per-round means."""
+    """The three epilogues on the shipped tiles at the shapes the plan launches, median of per-round means."""
     import statistics
-    LEG = 0x1000
     rounds = 5
 
     def ab(label, make, flops):
-        fs = {"T": make(0), "L": make(LEG)}
-        res = {k: [] for k in fs}
-        for _ in range(rounds):
-            for k, f in fs.items():
-                res[k].append(timeit(f, iters=10, warm=2))
-        t, l = statistics.median(res["T"]), statistics.median(res["L"])
-        print(f"{label:44s} transposed {t*1e3:7.1f} us {flops/t/1e9:7.1f} TF | legacy {l*1e3:7.1f} us {flops/l/1e9:7.1f} TF | x{l/t:.3f}", flush=True)
+        t = statistics.median([timeit(make(0), iters=10, warm=2) for _ in range(rounds)])
+        print(f"{label:44s} {t*1e3:7.1f} us {flops/t/1e9:7.1f} TF", flush=True)
 
     # fp32 output + residual accumulate (to_out, FF-out, cross out)
     for name, m, n, k, v in [("to_out B1 v15", 2050, 1536, 1536, 15), ("ff_out B1 v15", 2050, 1536, 6144, 15), ("cross B1 v16", 1025, 1536, 1536, 16),
@@ -183,31 +176,13 @@ def b8_tiles():
                                                                   _hip.ptr(scratch), b, s_len, s_pad, d, v, _hip.stream()))))
 
 
-def f32_epi_ab():
-    """fp32 residual epilogue: LDS-staged 16-byte coalesced (default) vs direct dword (bit 15) vs transposed 16-byte (bit 13)."""
-    import statistics
-    for name, m, n, k, v in [("to_out B1 v15", 2050, 1536, 1536, 15), ("ff_out B1 v15", 2050, 1536, 6144, 15), ("cross B1 v16", 1025, 1536, 1536, 16),
-                             ("to_out B8 v26", 16400, 1536, 1536, 26), ("ff_out B8 v26", 16400, 1536, 6144, 26), ("ff_out B8 v22", 16400, 1536, 6144, 22)]:
-        a = torch.randn(m, k, device=dev).to(torch.bfloat16)
-        w = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
-        c = torch.zeros(m, n, device=dev)
-        bias = torch.randn(n, device=dev)
-        mk = lambda flag: (lambda: _hip.check(lib.sat_gemm_bf16_f32(_hip.ptr(a), _hip.ptr(w), _hip.ptr(bias), _hip.ptr(c), m, n, k, 1, v | flag, _hip.stream())))
-        fs = {"staged": mk(0), "direct": mk(0x8000), "transposed": mk(0x2000)}
-        res = {kk: [] for kk in fs}
-        for _ in range(5):
-            for kk, f in fs.items():
-                res[kk].append(timeit(f, iters=10, warm=2))
-        print(f"f32+resid {name:16s} " + "  ".join(f"{kk}: {statistics.median(vv)*1e3:6.1f} us" for kk, vv in res.items()), flush=True)
-
-
 def splitk_probe():
     """What a K-split of the narrow fp32-output GEMMs could buy: time of ONE part (fewer, bigger tiles over a fraction of K) against
     the shipped single-pass launch.  A split launch would take about max(part) + one epilogue hand-off."""
     import statistics
-    cases = [("ff_out  full K=6144", 2050, 1536, 6144, 15), ("ff_out  256x128 K=3072", 2050, 1536, 3072, 12), ("ff_out  256x128 K=2816", 2050, 1536, 2816, 12),
+    cases = [("ff_out  full K=6144", 2050, 1536, 6144, 15),
              ("ff_out  256x192 K=2048", 2050, 1536, 2048, 30), ("ff_out  256x256 K=1536", 2050, 1536, 1536, 22),
-             ("to_out  full K=1536", 2050, 1536, 1536, 15), ("to_out  256x128 K=768", 2050, 1536, 768, 12),
+             ("to_out  full K=1536", 2050, 1536, 1536, 15),
              ("cross   full K=1536 (128x64)", 1025, 1536, 1536, 16), ("cross   128x128 K=768", 1025, 1536, 768, 15)]
     fs = {}
     for name, m, n, k, v in cases:
@@ -226,33 +201,14 @@ def splitk_probe():
         print(f"splitk {kk:30s} {ms*1e3:7.1f} us  {fl/ms/1e9:7.1f} TFLOP/s", flush=True)
 
 
-def small_tiles():
-    """The narrow fp32-output GEMMs (to_out, FF-out, cross to_q / to_out): wave tile 32x64 on 8 waves (shipped 15) against 64x64 on 4
-    waves (10: 3 stages, 42: 4 stages, 43: 2 stages / two workgroups per CU) and BK = 128 (39)."""
-    import statistics
-    shapes = [("ff_out", 2050, 1536, 6144), ("to_out", 2050, 1536, 1536), ("cross", 1025, 1536, 1536)]
-    for name, m, n, k in shapes:
-        a = torch.randn(m, k, device=dev).to(torch.bfloat16)
-        w = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
-        c = torch.zeros(m, n, device=dev)
-        bias = torch.randn(n, device=dev)
-        fs = {v: (lambda v=v: _hip.check(lib.sat_gemm_bf16_f32(_hip.ptr(a), _hip.ptr(w), _hip.ptr(bias), _hip.ptr(c), m, n, k, 1, v, _hip.stream())))
-              for v in ([15, 16, 10, 42, 43, 39, 12] if not os.environ.get("PROBE_DEPTH") else [15, 44, 45, 16, 46, 47])}
-        res = {v: [] for v in fs}
-        for _ in range(5):
-            for v, f in fs.items():
-                res[v].append(timeit(f, iters=10, warm=2))
-        print(f"tiles {name:8s} " + "  ".join(f"v{v}: {statistics.median(r)*1e3:6.1f} us" for v, r in res.items()), flush=True)
-
-
 def hybrid_probe():
     """FF-in (SwiGLU) at 1 prompt is 384 full 256x256 tiles + 48 two-row tiles on 256 CUs = 1.5 rounds run as 2.  How long do the pieces
     of a two-launch split take: N = 8192 on 256x256 tiles (one full round) + N = 4096 on smaller tiles (a second full round of less work)?"""
     import statistics
     k = 1536
-    cases = [("full  N=12288 v22", 2050, 12288, 22), ("A     N=8192  v22", 2050, 8192, 22), ("B     N=4096  v12 (256x128)", 2050, 4096, 12),
-             ("B     N=4096  v15 (128x128)", 2050, 4096, 15), ("B     N=4096  v22", 2050, 4096, 22), ("B     N=4096  v10 (128x128, 4 waves)", 2050, 4096, 10),
-             ("A'    N=6144  v22", 2050, 6144, 22), ("B'    N=6144  v12", 2050, 6144, 12), ("B'    N=6144  v30", 2050, 6144, 30),
+    cases = [("full  N=12288 v22", 2050, 12288, 22), ("A     N=8192  v22", 2050, 8192, 22),
+             ("B     N=4096  v15 (128x128)", 2050, 4096, 15), ("B     N=4096  v22", 2050, 4096, 22),
+             ("A'    N=6144  v22", 2050, 6144, 22), ("B'    N=6144  v30", 2050, 6144, 30),
              ("M2048 N=12288 v22", 2048, 12288, 22), ("M2048 N=8192 v22", 2048, 8192, 22)]
     fs = {}
     for name, m, n, v in cases:
@@ -319,61 +275,9 @@ def two_streams():
           f"both on two streams {ms_b:.3f} ms", flush=True)
 
 
-def ablate():
-    """Where does the time of each shipped GEMM go?  Ablation modes of the experiments build (SAT_HIP_EXP=1): 2 = no LDS-DMA in the
-    loop, 4 = + no barrier, 5 = + no ds_read (MFMA on register fragments), 6 = + no epilogue, 7 = 5 with the epilogue arithmetic but
-    no stores, 8 = production loop without stores.  Interleaved, median of 5 rounds."""
-    import statistics
-    NOPACK = 0x4000
-
-    def run(label, fns, flops):
-        res = {k: [] for k in fns}
-        for _ in range(5):
-            for k, f in fns.items():
-                res[k].append(timeit(f, iters=10, warm=2))
-        print(f"{label:34s} " + "  ".join(f"{k}:{statistics.median(v)*1e3:6.1f}" for k, v in res.items()), flush=True)
-
-    for name, m, n, k, tile in [("ff_out B1", 2050, 1536, 6144, 15), ("to_out B1", 2050, 1536, 1536, 15), ("cross B1", 1025, 1536, 1536, 16),
-                                ("ff_out B1 tile22", 2050, 1536, 6144, 22), ("ff_out B8 tile22", 16400, 1536, 6144, 22)]:
-        a = torch.randn(m, k, device=dev).to(torch.bfloat16)
-        w = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
-        c = torch.zeros(m, n, device=dev)
-        bias = torch.randn(n, device=dev)
-        mk = lambda v: (lambda: _hip.check(lib.sat_gemm_bf16_f32(_hip.ptr(a), _hip.ptr(w), _hip.ptr(bias), _hip.ptr(c), m, n, k, 1, v, _hip.stream())))
-        run(f"f32+resid {name} (us)", {"prod": mk(tile), "noload": mk(200 + tile), "nobar": mk(400 + tile), "nolds": mk(500 + tile), "noepi": mk(600 + tile)},
-            2.0 * m * n * k)
-    for name, m in [("ff_in B1", 2050), ("ff_in B8", 16400)]:
-        n, k = 12288, 1536
-        a = torch.randn(m, k, device=dev).to(torch.bfloat16)
-        w = torch.randn(n, k, device=dev) * 0.05
-        bias = torch.randn(n, device=dev) * 0.1
-        wp = torch.empty((n, k), dtype=torch.bfloat16, device=dev)
-        bp = torch.empty((n,), dtype=torch.float32, device=dev)
-        out = torch.empty((m, n // 2), dtype=torch.bfloat16, device=dev)
-        mk = lambda v: (lambda: _hip.check(lib.sat_gemm_swiglu_bf16(_hip.ptr(a), _hip.ptr(w), _hip.ptr(bias), _hip.ptr(wp), _hip.ptr(bp), _hip.ptr(out), m, n, k,
-                                                                    v, _hip.stream())))
-        mk(22)()        # pack once
-        run(f"swiglu {name} tile22 (us)", {"prod": mk(22 | NOPACK), "legacy": mk(22 | NOPACK | 0x1000), "nostore": mk(822 | NOPACK), "noload": mk(222 | NOPACK),
-                                           "nobar": mk(422 | NOPACK), "nolds": mk(522 | NOPACK), "nolds+math": mk(722 | NOPACK), "noepi": mk(622 | NOPACK),
-                                           "tile26": mk(26 | NOPACK)}, 2.0 * m * n * k)
-    for name, b in [("qkv B1", 2), ("qkv B8", 16)]:
-        s_len, s_pad, d = 1025, 1152, 1536
-        a = torch.randn(b * s_len, d, device=dev).to(torch.bfloat16)
-        w = (torch.randn(3 * d, d, device=dev) * 0.05).to(torch.bfloat16)
-        inv_freq = (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32))).to(dev)
-        q = torch.empty((b, 24, s_pad, 64), dtype=torch.bfloat16, device=dev)
-        kk = torch.empty_like(q)
-        vt = torch.empty((b, 24, 64, s_pad), dtype=torch.bfloat16, device=dev)
-        scratch = torch.empty((2 * s_len * 16,), dtype=torch.float32, device=dev)
-        mk = lambda v: (lambda: _hip.check(lib.sat_qkv_rope_bf16(_hip.ptr(a), _hip.ptr(w), _hip.ptr(inv_freq), _hip.ptr(q), _hip.ptr(kk), _hip.ptr(vt),
-                                                                 _hip.ptr(scratch), b, s_len, s_pad, d, v, _hip.stream())))
-        run(f"heads {name} tile30 (+memsets, us)", {"prod": mk(30), "noload": mk(230), "nobar": mk(430), "nolds": mk(530), "noepi": mk(630), "tile22": mk(22),
-                                                    "tile26": mk(26)}, 0)
-
-
 def gemm_pmc():
     """few launches of selected variants for rocprofv3 --pmc runs"""
-    for name, m, n, k, vs in [("ff_inB8", 16400, 12288, 1536, (7, 22, 26, 13)), ("ff_in", 2050, 12288, 1536, (22, 26))]:
+    for name, m, n, k, vs in [("ff_inB8", 16400, 12288, 1536, (22, 26)), ("ff_in", 2050, 12288, 1536, (22, 26))]:
         a = torch.randn(m, k, device=dev).to(torch.bfloat16)
         w = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
         c = torch.zeros(m, n, device=dev)
@@ -482,21 +386,15 @@ if __name__ == "__main__":
     if "gemm" in which:
         section("gemm", gemm_bench)
     if "epi" in which:
-        section("epilogue A/B", epi_ab)
+        section("epilogues", epi_ab)
     if "b8tiles" in which:
         section("8 prompts: tile 22 vs 26", b8_tiles)
-    if "f32epi" in which:
-        section("fp32 epilogue A/B", f32_epi_ab)
     if "twostreams" in which:
         section("two CFG halves on two streams", two_streams)
     if "hybrid" in which:
         section("FF-in two-launch split", hybrid_probe)
-    if "smalltiles" in which:
-        section("small tiles", small_tiles)
     if "splitk" in which:
         section("split-K parts", splitk_probe)
-    if "ablate" in which:
-        section("ablation", ablate)
     if "gemm_pmc" in which:
         section("gemm_pmc", gemm_pmc)
     if "attn" in which:

@@ -1,7 +1,7 @@
 """Developer probe (GPU box): calibration of the 8-wave / 8-phase 256x256 GEMM tile (variant 80, csrc/gemm_ph8.hip) against the
 16-wave tile 22 and hipBLASLt (torch.matmul) on the same random operands, all arms interleaved in ONE process; correctness
 against an fp32 product of the same bf16 operands; repeated-run race screen.  Not part of the product or the tests.
-usage: python tools/ph8_probe.py [calib] [shapes] [race] [ablate]"""
+usage: python tools/ph8_probe.py [calib] [shapes] [race] [timeline] ...   (every top-level function is a mode)"""
 import os
 import statistics
 import sys
@@ -131,10 +131,10 @@ def libcal():
 def quant6():
     """Round 6, pricing the M-tail BEFORE building anything: what would every block GEMM cost if M were a whole number of
     tiles -- M = 2048 / 16384 (the tokens without the 2 / 16 rows that spill into a ninth / 65th row of tiles) against the model's M = 2050 /
-    16400 -- with the shipped tile choice (v0), the 8-phase tile (80), the 12-wave 256 x 192 (30), the 256 x 128 8-wave tile (12, experiments
-    build: 768 tiles = 3.0 rounds at M = 16384) and the vendor library, all interleaved; plain fp32 output (the epilogue is the same on both M)."""
+    16400 -- with the shipped tile choice (v0), the 8-phase tile (80), the 16-wave tile (22) and the vendor library, all interleaved; plain
+    fp32 output (the epilogue is the same on both M)."""
     for name, n, k, vs1, vs8 in (("ff_in", 12288, 1536, [0], [0]), ("qkv", 4608, 1536, [0, 80 | 0x20000], [0]),
-                                 ("to_out", 1536, 1536, [0, 15], [0, 22, 80 | 0x20000, 12]), ("ff_out", 1536, 6144, [0, 44], [0, 22, 12])):
+                                 ("to_out", 1536, 1536, [0, 15], [0, 22, 80 | 0x20000]), ("ff_out", 1536, 6144, [0, 44], [0, 22])):
         for m in (2050, 2048):
             arms_bench(f"quant6 {name} B1", m, n, k, vs1, rounds=4, iters=10)
         for m in (16400, 16384):
@@ -142,11 +142,13 @@ def quant6():
     for m in (1025, 1024):
         arms_bench("quant6 cross B1", m, 1536, 1536, [0, 15], rounds=4, iters=10)
     for m in (8200, 8192):
-        arms_bench("quant6 cross B8", m, 1536, 1536, [0, 22, 12], rounds=3, iters=6)
+        arms_bench("quant6 cross B8", m, 1536, 1536, [0, 22], rounds=3, iters=6)
 
 
-def balance(bit=0x200000):
+def balance():
     """schedule A/B on the real epilogues: every CU a workgroup (256 + remainder) vs balanced rounds on fewer workgroups (variant bit 21)"""
+    bit = 0x200000
+
     def ab(label, mk, flops, arms, rounds=5):
         fs = {k_: mk(v) for k_, v in arms.items()}
         res = {k_: [] for k_ in fs}
@@ -221,15 +223,6 @@ def kg():
             a, w2 = sets[cnt[0] % nset]
             cnt[0] += 1
             _hip.check(fn(_hip.ptr(a), _hip.ptr(w2), _hip.ptr(b2), _hip.ptr(c), _hip.ptr(xo), _hip.ptr(po), m, n, k, v, _hip.stream()))
-        if 50 in arms:
-            outs = {}
-            for v in (49, 50):
-                c.copy_(torch.arange(m * n, device=dev, dtype=torch.float32).view(m, n) * 1e-6)
-                cnt[0] = 0
-                call(v)
-                torch.cuda.synchronize()
-                outs[v] = (c.clone(), xo.float().clone(), po.clone())
-            print("   v50 vs v49:", ["%.2e" % ((x50 - x49).abs().max().item()) for x49, x50 in zip(outs[49], outs[50])], flush=True)
         res = {v: [] for v in arms}
         for _ in range(7):
             for v in arms:
@@ -239,14 +232,12 @@ def kg():
 
 
 def narrow():
-    """the narrow one-prompt GEMMs (fp32 residual + LayerNorm-fold producer epilogue): shipped tiles against the experiments build's 4-wave / BK = 128 tiles"""
-    for name, m, n, k, arms in [("ff_out B1", 2050, 1536, 6144, (44, 15, 49, 39, 42, 43, 10, 48)), ("to_out B1", 2050, 1536, 1536, (15, 49, 16, 39, 42, 43, 10, 48)),
-                                ("cross out B1", 1025, 1536, 1536, (16, 15, 49, 42, 48)),
-                                # two workgroups of tile 43 (4 waves of 64 x 64, 64 KiB) share a CU once there are >= 512 tiles: 8 waves per CU with half
-                                # the LDS reads per MFMA of tile 15 / 44 -- does the fragment traffic bound the narrow tiles?
-                                ("ff_out 4 prompts", 8200, 1536, 6144, (44, 49, 43, 80)), ("to_out 4 prompts", 8200, 1536, 1536, (15, 49, 43, 22, 80)),
-                                ("ff_out 8 prompts", 16400, 1536, 6144, (44, 49, 43, 80)), ("to_out 8 prompts", 16400, 1536, 1536, (15, 49, 43, 22, 80)),
-                                ("cross out 8 prompts", 8200, 1536, 1536, (15, 49, 43, 22, 80))]:
+    """the narrow one-prompt GEMMs (fp32 residual + LayerNorm-fold producer epilogue): the shipped narrow tiles against each other"""
+    for name, m, n, k, arms in [("ff_out B1", 2050, 1536, 6144, (44, 15, 49)), ("to_out B1", 2050, 1536, 1536, (15, 49, 16)),
+                                ("cross out B1", 1025, 1536, 1536, (16, 15, 49)),
+                                ("ff_out 4 prompts", 8200, 1536, 6144, (44, 49, 80)), ("to_out 4 prompts", 8200, 1536, 1536, (15, 49, 22, 80)),
+                                ("ff_out 8 prompts", 16400, 1536, 6144, (44, 49, 80)), ("to_out 8 prompts", 16400, 1536, 1536, (15, 49, 22, 80)),
+                                ("cross out 8 prompts", 8200, 1536, 1536, (15, 49, 22, 80))]:
         a = torch.randn(m, k, device=dev).to(torch.bfloat16)
         w2 = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
         b2 = torch.randn(n, device=dev)
@@ -276,11 +267,6 @@ def narrow():
         print(f"narrow resid+ln {name} {m}x{n}x{k}: " + "  ".join(f"v{v} {statistics.median(t)*1e3:.1f} us ({fl/statistics.median(t)/1e9:.0f} TF)" for v, t in res.items()), flush=True)
 
 
-def balance_any():
-    """experiments build: balanced rounds at ANY round count (variant bit 22, the 'balanced' arm) against the shipped policy (only 1 < rounds <= 2)"""
-    balance(bit=0x400000)
-
-
 def race():
     # The same launch 40 times, alternating between two different A operands: every output must be bit-identical to the first run on
     # that operand and equal to its fp32 reference (a DMA / ds_read race shows up as rare differing tiles; a stale stream-K slab or
@@ -305,9 +291,8 @@ def race():
 
 
 def opts():
-    vs = [80] + [80 | (o << 16) for o in (1, 2, 3, 4, 5, 8, 9)]
-    for o in (1, 4, 5, 9):
-        check(512, 512, 512, 80 | (o << 16))
+    vs = [80] + [80 | (o << 16) for o in (1, 2)]          # K-split forced / off
+    check(512, 512, 512, 80 | 0x10000)
     for name, m, n, k in [("4096^3", 4096, 4096, 4096), ("ff_out B8", 16400, 1536, 6144), ("qkv B8", 16400, 4608, 1536)]:
         arms_bench("opts " + name, m, n, k, vs, blas=False, rounds=5)
 
@@ -439,109 +424,6 @@ def timeline():
                       f"  epilogue {np.median(x[:,3]-x[:,2]):6.2f} (p90 {np.percentile(x[:,3]-x[:,2],90):6.2f})  end at {np.median(x[:,3]):6.1f} (max {x[:,3].max():6.1f})", flush=True)
 
 
-def ph2():
-    """A/B of the shipped two-phase K-tile (32 MFMAs per phase, 4 barriers) against a variant selected by PH2_BIT: 0x40000 = the first
-    version's four phases of 16 MFMAs (8 barriers), 0x80000 = W-hi issued one phase earlier"""
-    V2 = 80 | (int(os.environ.get("PH2_BIT", "0x40000"), 16))          # bit 18: the four-phase loop; bit 19: W-hi issued one phase earlier
-    for (m, n, k) in [(256, 256, 256), (512, 512, 512), (300, 512, 384), (2050, 1536, 1536), (257, 768, 6144)]:
-        check(m, n, k, V2)
-    for (m, n, k) in [(512, 512, 512), (4096, 4096, 4096), (2050, 12288, 1536)]:
-        w = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
-        As = [torch.randn(m, k, device=dev).to(torch.bfloat16), (torch.randn(m, k, device=dev) * 2 + 0.5).to(torch.bfloat16)]
-        first, diff = [None, None], 0
-        for i in range(40):
-            c = torch.full((m, n), float("nan"), device=dev)
-            gemm_fn(As[i & 1], w, c, m, n, k, V2)()
-            if first[i & 1] is None:
-                first[i & 1] = c
-            else:
-                diff += int(not torch.equal(c, first[i & 1]))
-        print(f"race(ph2) M={m} N={n} K={k}: {diff} of 38 repeats differ", flush=True)
-    for name, m, n, k in [("4096^3", 4096, 4096, 4096), ("1 round K=1536", 2048, 8192, 1536), ("ff_out B8", 16400, 1536, 6144), ("f32 ff_in-shape B8", 16400, 12288, 1536)]:
-        arms_bench("ph2 " + name, m, n, k, [80, V2], blas=False, rounds=5)
-    # SwiGLU + LayerNorm fold at the plan's shapes
-    for name, m in [("B1", 2050), ("B8", 16400)]:
-        n, k = 12288, 1536
-        xb = torch.randn(m, k, device=dev).to(torch.bfloat16)
-        part = torch.stack([xb.float().view(m, k // 64, 64).sum(-1), (xb.float() ** 2).view(m, k // 64, 64).sum(-1)], -1).contiguous()
-        w = torch.randn(n, k, device=dev) * 0.05
-        gamma = 0.8 + 0.2 * torch.rand(k, device=dev)
-        beta = 0.1 * torch.randn(k, device=dev)
-        bias = torch.randn(n, device=dev) * 0.1
-        wp = torch.empty((n, k), dtype=torch.bfloat16, device=dev)
-        c12 = torch.empty((2 * n,), dtype=torch.float32, device=dev)
-        outs = {}
-        res = {80: [], V2: []}
-        for v in res:
-            out = torch.empty((m, n // 2), dtype=torch.bfloat16, device=dev)
-            _hip.check(lib.sat_gemm_swiglu_ln_bf16(_hip.ptr(xb), _hip.ptr(part), _hip.ptr(w), _hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(bias), _hip.ptr(wp),
-                                                   _hip.ptr(c12), _hip.ptr(out), m, n, k, v, _hip.stream()))
-            outs[v] = out
-        print(f"ph2 swiglu {name}: outputs equal: {torch.equal(outs[80], outs[V2])}")
-        out = outs[80]
-        for _ in range(5):
-            for v in res:
-                res[v].append(timeit(lambda: _hip.check(lib.sat_gemm_swiglu_ln_bf16(_hip.ptr(xb), _hip.ptr(part), _hip.ptr(w), _hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(bias),
-                                                                                   _hip.ptr(wp), _hip.ptr(c12), _hip.ptr(out), m, n, k, v | 0x4000, _hip.stream())), iters=10, warm=2))
-        a, b = statistics.median(res[80]), statistics.median(res[V2])
-        print(f"ph2 swiglu+ln {name}: v80 {a*1e3:.1f} us  v80+{V2 >> 16:x} {b*1e3:.1f} us  x{a/b:.3f}", flush=True)
-
-
-def small():
-    """the 128 x 128 geometry of the 8-phase kernel (variant 81: 4 waves, two workgroups per CU) against the 16-wave-family tiles the plan
-    uses at one prompt: 44 / 15 (128 x 128, 8 waves), 16 (128 x 64), 30 (256 x 192)"""
-    for (m, n, k) in [(128, 128, 128), (256, 256, 256), (300, 512, 384), (2050, 1536, 1536), (257, 768, 6144), (1025, 1536, 1536)]:
-        check(m, n, k, 81)
-        check(m, n, k, 81, fill="rows")
-    for (m, n, k) in [(512, 512, 512), (2050, 1536, 6144), (1025, 1536, 1536)]:
-        w = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
-        As = [torch.randn(m, k, device=dev).to(torch.bfloat16), (torch.randn(m, k, device=dev) * 2 + 0.5).to(torch.bfloat16)]
-        first, diff = [None, None], 0
-        for i in range(40):
-            c = torch.full((m, n), float("nan"), device=dev)
-            gemm_fn(As[i & 1], w, c, m, n, k, 81)()
-            if first[i & 1] is None:
-                first[i & 1] = c
-            else:
-                diff += int(not torch.equal(c, first[i & 1]))
-        print(f"race(81) M={m} N={n} K={k}: {diff} of 38 repeats differ", flush=True)
-    for name, m, n, k, olds in [("ff_out B1", 2050, 1536, 6144, (44, 15)), ("to_out B1", 2050, 1536, 1536, (15, 16)), ("cross out B1", 1025, 1536, 1536, (16, 15))]:
-        a = torch.randn(m, k, device=dev).to(torch.bfloat16)
-        w2 = (torch.randn(n, k, device=dev) * 0.05).to(torch.bfloat16)
-        b2 = torch.randn(n, device=dev)
-        c = torch.zeros(m, n, device=dev)
-        xo = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
-        po = torch.empty((m, n // 64, 2), dtype=torch.float32, device=dev)
-        arms = {f"v{v}": v for v in olds}
-        arms["v81"] = 81
-        res = {kk: [] for kk in arms}
-        for _ in range(5):
-            for kk, v in arms.items():
-                res[kk].append(timeit(lambda: _hip.check(lib.sat_gemm_resid_ln_bf16(_hip.ptr(a), _hip.ptr(w2), _hip.ptr(b2), _hip.ptr(c), _hip.ptr(xo), _hip.ptr(po), m, n, k,
-                                                                                   v, _hip.stream())), iters=10, warm=2))
-        fl = 2.0 * m * n * k
-        print(f"small resid+ln {name} {m}x{n}x{k}: " + "  ".join(f"{kk} {statistics.median(vv)*1e3:.1f} us ({fl/statistics.median(vv)/1e9:.0f} TF)" for kk, vv in res.items()), flush=True)
-    b, s_len, s_pad, d = 2, 1025, 1152, 1536
-    a = torch.randn(b * s_len, d, device=dev).to(torch.bfloat16)
-    w = (torch.randn(3 * d, d, device=dev) * 0.05).to(torch.bfloat16)
-    inv_freq = (1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32))).to(dev)
-    q = torch.empty((b, 24, s_pad, 64), dtype=torch.bfloat16, device=dev)
-    kk_ = torch.empty_like(q)
-    vt = torch.empty((b, 24, 64, s_pad), dtype=torch.bfloat16, device=dev)
-    scratch = torch.empty((2 * s_len * 16,), dtype=torch.float32, device=dev)
-    res = {30: [], 80: [], 81: []}
-    for _ in range(5):
-        for v in res:
-            res[v].append(timeit(lambda: _hip.check(lib.sat_qkv_rope_bf16(_hip.ptr(a), _hip.ptr(w), _hip.ptr(inv_freq), _hip.ptr(q), _hip.ptr(kk_), _hip.ptr(vt), _hip.ptr(scratch),
-                                                                       b, s_len, s_pad, d, v, _hip.stream())), iters=10, warm=2))
-    print("small qkv heads+rope B1 (+memsets): " + "  ".join(f"v{v} {statistics.median(t)*1e3:.1f} us" for v, t in res.items()), flush=True)
-
-
-def ablate():
-    for name, m, n, k in [("4096^3", 4096, 4096, 4096), ("ff_in B8", 16400, 12288, 1536)]:
-        arms_bench("ablate " + name, m, n, k, [80, 180, 280, 380], blas=False, rounds=3)
-
-
 def ffout():
     """FF-out (fp32 residual update + LayerNorm-fold producer, K = 6144): whole tiles vs per-tile K parts vs contiguous stream-K shares of
     the remainder round, interleaved; the split results are checked against the whole-tile result"""
@@ -628,7 +510,7 @@ def qkv8():
             return f
         mk(0)()
         torch.cuda.synchronize()
-        arms = {"auto": 0x4000, "v80": 80 | 0x4000, "v30": 30 | 0x4000, "v60": 60 | 0x4000}
+        arms = {"auto": 0x4000, "v80": 80 | 0x4000, "v30": 30 | 0x4000}
         res = {k2: [] for k2 in arms}
         for _ in range(5):
             for k2, v in arms.items():
