@@ -13,6 +13,10 @@ int glue_input_proj(const float* x, const float* Weff, float* X, int Bf, int xB,
 // P prepared prepend rows copied to X[b, 0..P-1]; S = P + 1 + T
 int glue_input_proj_extra(const float* x, const float* Weff, float* X, int Bf, int xB, int C, int T, int S, int D, float xscale,
                           const float* concat, int Cc, int Tc, const float* prep, int P, hipStream_t s);
+// position embeddings added to the stream (ContinuousTransformer use_sinusoidal_emb / use_abs_pos_emb): the [rows, D] table once per plan
+// (mode 1: sinusoidal, src = the learnt scale [1]; mode 2: absolute, src = emb.weight [>= rows, D]), then X[b, s, :] += table[s, :] per forward
+int glue_pos_table(int mode, const float* src, float* table, int rows, int D, hipStream_t s);
+int glue_add_pos(float* X, const float* table, int Bf, int S, int D, hipStream_t s);
 int glue_output_proj(const float* X, const float* Weff, float* out, int Bf, int C, int T, int S, int D, hipStream_t s);
 int glue_cfg_denoise(const float* mo, const float* x, float* den, int B, int C, int T, int use_cfg, float cfg_scale,
                      float scale_phi, float c_out, float c_skip, hipStream_t s);

@@ -456,6 +456,51 @@ int glue_input_proj_extra(const float* x, const float* Weff, float* X, int Bf, i
     return 0;
 }
 
+// ---- position embeddings added to the residual stream (transformer.py:50-96, 796-797)
+namespace {
+// table[s][c], s < rows.  mode 1 (ScaledSinusoidalEmbedding): cat(sin, cos)(s * theta^(-j / (D/2))) * src[0] (the learnt `scale`);
+// mode 2 (AbsolutePositionalEmbedding): src[s][c] * D^-0.5.  Once per plan (finalize).
+__global__ __launch_bounds__(256) void pos_table_kernel(int mode, const float* __restrict__ src, float* __restrict__ table, int rows, int D) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)rows * D) return;
+    if (mode == 2) {
+        table[idx] = src[idx] * (float)(1.0 / sqrt((double)D));
+        return;
+    }
+    const int pos = (int)(idx / D), c = (int)(idx - (int64_t)pos * D), hd = D / 2, j = c < hd ? c : c - hd;
+    const float inv_freq = (float)pow(10000.0, -(double)((float)j / (float)hd));      // fp32 freq_seq, theta ** -freq_seq
+    const float f = (float)pos * inv_freq;
+    table[idx] = (c < hd ? sinf(f) : cosf(f)) * src[0];
+}
+
+// X[b, s, :] += table[s, :] for every row of every sequence, 4 channels per lane
+__global__ __launch_bounds__(256) void add_pos_kernel(float* __restrict__ X, const float* __restrict__ table, int64_t n4, int S, int D4) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n4) return;
+    const int64_t row = idx / D4;
+    const int c4 = (int)(idx - row * D4), sq = (int)(row % S);
+    f32x4 v = reinterpret_cast<f32x4*>(X)[idx];
+    const f32x4 t = reinterpret_cast<const f32x4*>(table)[(size_t)sq * D4 + c4];
+    v += t;
+    reinterpret_cast<f32x4*>(X)[idx] = v;
+}
+}  // namespace
+
+int glue_pos_table(int mode, const float* src, float* table, int rows, int D, hipStream_t s) {
+    SAT_CHECK_ARG((mode == 1 || mode == 2) && src && table && rows > 0 && D > 0 && D % 2 == 0, SAT_E_INVALID, "pos_table: bad arguments");
+    hipLaunchKernelGGL(pos_table_kernel, dim3(cdiv((int64_t)rows * D, 256)), dim3(256), 0, s, mode, src, table, rows, D);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int glue_add_pos(float* X, const float* table, int Bf, int S, int D, hipStream_t s) {
+    SAT_CHECK_ARG(X && table && Bf > 0 && S > 0 && D > 0 && D % 4 == 0, SAT_E_INVALID, "add_pos: bad arguments");
+    const int64_t n4 = (int64_t)Bf * S * (D / 4);
+    hipLaunchKernelGGL(add_pos_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, X, table, n4, S, D / 4);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
 int glue_output_proj(const float* X, const float* WeffT, float* out, int Bf, int C, int T, int S, int D, hipStream_t s) {
     SAT_CHECK_ARG(C <= 64 && C % 4 == 0 && D % 16 == 0, SAT_E_UNSUPPORTED, "output_proj: C=%d (multiple of 4, <= 64) D=%d unsupported", C, D);
     const int lds = (OP_TOK * D + 8 * OP_TOK * 64) * 4;

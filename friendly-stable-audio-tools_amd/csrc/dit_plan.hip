@@ -51,6 +51,13 @@ struct sat_dit_plan {
     // input-concat / prepend conditioning (sat_dit_plan_set_extra_conditioning): win_eff then spans io_channels + concat_dim input channels
     int concat_dim = 0, prepend_dim = 0, max_prep = 0;
     float *pe0_w = nullptr, *pe2_w = nullptr;      // to_prepend_embed.0 / .2 (dit.py:160-165)
+    // ContinuousTransformer switches off the shipped configs' path (sat_dit_plan_set_transformer_options); the defaults change nothing
+    bool qk_norm = false;           // attn_kwargs qk_norm: q / k L2-normalised per head in the projections' epilogues (HeadsEpi::kind bit 4)
+    int pos_emb = SAT_DIT_POS_NONE; // use_sinusoidal_emb / use_abs_pos_emb: pos_table is added to the stream behind the input projection
+    int abs_max = 0;                // abs_pos_emb_max_length
+    bool rotary = true;             // rotary_pos_emb=False: no inv_freq tensor, the rotation table is the identity (cos 1, sin 0)
+    float* pos_table = nullptr;     // [pos_rows, D] fp32, position = row of the sequence (0 = first prepended row)
+    int pos_rows = 0;
     // per-generation context (sat_dit_prepare_context)
     DevBuf ctx_buf;
     int ctx_bf = 0, ctx_lc = 0, ctx_lcpad = 0;
@@ -127,6 +134,13 @@ int pack_w8(sat_dit_plan* p, Bump& ar, const std::string& name, int n, int k, in
     return sat_launch_quant_rows_fp8(src, *dst, *scale, n, k, interleave, s);
 }
 
+// ff_kwargs no_bias (transformer.py:270): the output Linear of the feed-forward has no bias tensor; FF-out then runs without one
+int copy_ff2_bias(sat_dit_plan* p, Bump& ar, const std::string& pf, int D, float** dst, hipStream_t s) {
+    *dst = nullptr;
+    if (p->tensors.m.find(pf + "ff.ff.2.bias") == p->tensors.m.end()) return 0;
+    return copy_f32(p, ar, pf + "ff.ff.2.bias", D, dst, s);
+}
+
 int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
     const sat_dit_cfg& c = p->cfg;
     const int D = c.embed_dim, C = c.io_channels, Dc = c.cond_embed_dim, Dct = c.cond_token_dim, Dg = c.global_cond_dim;
@@ -148,13 +162,20 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         SAT_TRY(copy_f32(p, ar, "to_prepend_embed.0.weight", (int64_t)D * p->prepend_dim, &p->pe0_w, s));
         SAT_TRY(copy_f32(p, ar, "to_prepend_embed.2.weight", (int64_t)D * D, &p->pe2_w, s));
     }
-    SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 16, &p->inv_freq, s));
+    if (p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 16, &p->inv_freq, s));
+    else {      // frequencies 0: rope_table below comes out as cos 1 / sin 0 and the rotating epilogues are the identity
+        p->inv_freq = (float*)ar.take(16 * 4);
+        if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, 16 * 4, s));
+    }
     const int Ci = C + p->concat_dim;       // preprocess_conv / project_in see cat([x, input_concat_cond]) (dit.py:38,130,173)
     p->win_eff = (float*)ar.take((size_t)D * Ci * 4);
     p->wout_eff = (float*)ar.take((size_t)D * C * 4);
     const int smax = seq_len(p, c.max_seq_len, p->max_prep);
     p->rope_cos = (float*)ar.take((size_t)smax * 16 * 4);
     p->rope_sin = (float*)ar.take((size_t)smax * 16 * 4);
+    // the absolute table has abs_pos_emb_max_length rows and no more: run_forward refuses longer sequences as the reference does
+    p->pos_rows = p->pos_emb == SAT_DIT_POS_ABSOLUTE && p->abs_max < smax ? p->abs_max : smax;
+    p->pos_table = p->pos_emb != SAT_DIT_POS_NONE ? (float*)ar.take((size_t)p->pos_rows * D * 4) : nullptr;
     if (!ar.dry()) {
         const float *win, *wpre, *wout, *wpost;
         SAT_TRY(get_tensor(p, "transformer.project_in.weight", (int64_t)D * Ci, &win));
@@ -164,6 +185,15 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         SAT_TRY(glue_fold_in(win, wpre, p->win_eff, D, Ci, s));
         SAT_TRY(glue_fold_out(wout, wpost, p->wout_eff, D, C, s));
         SAT_TRY(sat_launch_rope_table(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
+        if (p->pos_emb == SAT_DIT_POS_SINUSOIDAL) {     // inv_freq is not in the state dict (persistent=False), the learnt scale is
+            const float* sc;
+            SAT_TRY(get_tensor(p, "transformer.pos_emb.scale", 1, &sc));
+            SAT_TRY(glue_pos_table(1, sc, p->pos_table, p->pos_rows, D, s));
+        } else if (p->pos_emb == SAT_DIT_POS_ABSOLUTE) {
+            const float* ew;
+            SAT_TRY(get_tensor(p, "transformer.pos_emb.emb.weight", (int64_t)p->abs_max * D, &ew));
+            SAT_TRY(glue_pos_table(2, ew, p->pos_table, p->pos_rows, D, s));
+        }
     }
     if (c.adaln) p->ssg_w = (float*)ar.take((size_t)c.depth * 6 * D * D * 4);
     p->layers.resize(c.depth);
@@ -191,7 +221,7 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
             SAT_TRY(w32("ff.ff.0.proj.weight", (int64_t)2 * inner * D, &L.w_ff1));
             SAT_TRY(copy_f32(p, ar, pf + "ff.ff.0.proj.bias", 2 * inner, &L.b_ff1, s));
             SAT_TRY(w32("ff.ff.2.weight", (int64_t)D * inner, &L.w_ff2));
-            SAT_TRY(copy_f32(p, ar, pf + "ff.ff.2.bias", D, &L.b_ff2, s));
+            SAT_TRY(copy_ff2_bias(p, ar, pf, D, &L.b_ff2, s));
             continue;
         }
         const bool lf = p->ln_fold;
@@ -223,7 +253,7 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         }
         if (p->f8_ff2) SAT_TRY(pack_w8(p, ar, pf + "ff.ff.2.weight", D, inner, 0, &L.w_ff2, &L.s_ff2, s));
         else SAT_TRY(pack_w(p, ar, pf + "ff.ff.2.weight", D, inner, 0, &L.w_ff2, s));
-        SAT_TRY(copy_f32(p, ar, pf + "ff.ff.2.bias", D, &L.b_ff2, s));
+        SAT_TRY(copy_ff2_bias(p, ar, pf, D, &L.b_ff2, s));
     }
     return 0;
 }
@@ -316,6 +346,11 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     const int f16 = p->f16;
     const int S = seq_len(p, T, P), M = bf * S, Spad = (int)round_up(S + 3, 128);
     const int ssg_ld = c.depth * 6 * D;      // per-sequence stride of the adaLN modulation vectors
+    // transformer.py:59-61, before anything is launched
+    SAT_CHECK_ARG(p->pos_emb != SAT_DIT_POS_ABSOLUTE || S <= p->abs_max, SAT_E_INVALID,
+                  "dit forward: you are passing in a sequence length of %d but your absolute positional embedding has a max sequence length of %d", S,
+                  p->abs_max);
+    const int qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
 
     // pads of q/k/vt must be finite (zero): one memset per forward
     if (!f32) SAT_HIP(hipMemsetAsync(w.Q, 0, 3 * (size_t)round_up((int64_t)w.qkv_bytes, 256), s));
@@ -339,6 +374,8 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
                                       p->ext_prep, P, s));
     else
         SAT_TRY(glue_input_proj(x, p->win_eff, w.X, bf, xB, C, T, S, D, xscale, s));
+    // transformer.py:796-797: x + pos_emb(x) on every row behind project_in and the prepend concat; block 0's LayerNorm reads X itself
+    if (p->pos_table) SAT_TRY(glue_add_pos(w.X, p->pos_table, bf, S, D, s));
 
     if (p->dbg) SAT_HIP(hipMemsetAsync(p->dbg, 0, (size_t)c.depth * 3 * 4 * sizeof(float), s));
     GemmArgs g{};
@@ -349,7 +386,7 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
         float *A32 = (float*)w.A, *AO32 = (float*)w.AO, *Q32 = (float*)w.Q, *K32 = (float*)w.K, *V32 = (float*)w.Vt, *H32 = (float*)w.Hh;
         SAT_TRY(sat_launch_layernorm_f32(w.X, L.pre_g, L.pre_b, A32, M, D, mod, mod ? mod + D : nullptr, S, ssg_ld, s));
         SAT_TRY(sat_launch_gemm_f32(A32, (const float*)L.w_qkv, nullptr, w.f32_wide, M, 3 * D, D, 3 * D, 0, nullptr, 1, 0, s));
-        SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s));
+        SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
         SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
         SAT_TRY(sat_launch_gemm_f32(AO32, (const float*)L.w_o, nullptr, w.X, M, D, D, D, 1, adaln ? mod + 2 * D : nullptr, S, ssg_ld, s));
         if (cross) {
@@ -358,7 +395,7 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
             if (bc > 0) {
                 SAT_TRY(sat_launch_layernorm_f32(w.X, L.cross_g, L.cross_b, A32, Mc, D, nullptr, nullptr, 1, 0, s));
                 SAT_TRY(sat_launch_gemm_f32(A32, (const float*)L.w_cq, nullptr, w.f32_wide, Mc, D, D, D, 0, nullptr, 1, 0, s));
-                SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, nullptr, nullptr, s));
+                SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
                 const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lc * 64;
                 SAT_TRY(sat_launch_attention_f32(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, S, p->ctx_lc, s));
                 SAT_TRY(sat_launch_gemm_f32(AO32, (const float*)L.w_co, nullptr, w.X, Mc, D, D, D, 1, nullptr, 1, 0, s));
@@ -389,7 +426,7 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
         if (L.fold_qkv) fold_in(g, L.c1_qkv, L.c2_qkv);
         if (p->f8_qkv) { g.fp8 = p->fp8_mode; g.a_scale = w.As; g.w_scale = L.s_qkv; }
         g.heads.out[0] = w.Q; g.heads.out[1] = w.K; g.heads.out[2] = w.Vt;
-        g.heads.kind[0] = 2 | 8; g.heads.kind[1] = 2 | 4; g.heads.kind[2] = 1 | 4; g.heads.qscale = SAT_ATTN_QSCALE;
+        g.heads.kind[0] = 2 | 8 | qn; g.heads.kind[1] = 2 | 4 | qn; g.heads.kind[2] = 1 | 4; g.heads.qscale = SAT_ATTN_QSCALE;
         g.heads.parts = 3; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
         g.heads.rope_cos = p->rope_cos; g.heads.rope_sin = p->rope_sin;
         SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
@@ -415,7 +452,7 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
                 g.A = w.A; g.W = L.w_cq; g.M = Mc; g.N = D; g.K = D;
                 if (lf) fold_in(g, L.c1_cq, L.c2_cq);
                 if (p->f8_cq) { g.fp8 = p->fp8_mode; g.a_scale = w.As; g.w_scale = L.s_cq; }
-                g.heads.out[0] = w.Q; g.heads.kind[0] = 8; g.heads.qscale = SAT_ATTN_QSCALE;
+                g.heads.out[0] = w.Q; g.heads.kind[0] = 8 | qn; g.heads.qscale = SAT_ATTN_QSCALE;
                 g.heads.parts = 1; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
                 const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * 64;
                 // One launch for to_q + softmax(q k^T) v where the 128 x 64 tile is the choice anyway and its workgroups fit one round
@@ -638,7 +675,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
         for (int l = 0; l < c.depth; ++l) {
             SAT_TRY(sat_launch_gemm_f32(ce32, (const float*)p->layers[l].w_ckv, nullptr, kv32, R, 2 * Dc, Dc, 2 * Dc, 0, nullptr, 1, 0, s));
             SAT_TRY(sat_launch_split_heads_f32(kv32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, nullptr, R, lc, 2, p->kvh_cross, 0, nullptr,
-                                               nullptr, s));
+                                               nullptr, s, p->qk_norm ? 1 : 0));
         }
     } else if (cross) {   // dit.py:150 then per-layer to_kv (transformer.py:420-427)
         float* ch = (float*)(p->ctx_buf.ptr + o_ch);
@@ -653,7 +690,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
             g.f16 = p->f16;
             g.A = ce; g.W = p->layers[l].w_ckv; g.M = R; g.N = 2 * Dc; g.K = Dc;
             g.heads.out[0] = p->kc + l * per_layer; g.heads.out[1] = p->vct + l * per_layer;
-            g.heads.kind[0] = 4; g.heads.kind[1] = 1 | 4; g.heads.parts = 2; g.heads.heads = p->kvh_cross;
+            g.heads.kind[0] = 4 | (p->qk_norm ? 16 : 0); g.heads.kind[1] = 1 | 4; g.heads.parts = 2; g.heads.heads = p->kvh_cross;
             g.heads.S = lc; g.heads.Spad = lcpad;
             g.variant = 1;
             SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
@@ -700,6 +737,28 @@ extern "C" int sat_dit_plan_set_extra_conditioning(sat_dit_plan* p, int32_t inpu
     p->concat_dim = input_concat_dim;
     p->prepend_dim = prepend_cond_dim;
     p->max_prep = max_prepend_len;
+    return 0;
+}
+
+extern "C" int sat_dit_plan_set_transformer_options(sat_dit_plan* p, const sat_dit_transformer_options* o, size_t options_bytes) {
+    SAT_CHECK_ARG(p && o, SAT_E_INVALID, "dit_plan_set_transformer_options: null argument");
+    SAT_CHECK_ARG(options_bytes == sizeof(sat_dit_transformer_options), SAT_E_INVALID,
+                  "dit_plan_set_transformer_options: sat_dit_transformer_options of %zu bytes; this library knows %zu", options_bytes,
+                  sizeof(sat_dit_transformer_options));
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_transformer_options: plan already finalized (call it between create and finalize)");
+    SAT_CHECK_ARG((o->qk_norm == 0 || o->qk_norm == 1) && (o->rotary == 0 || o->rotary == 1) && o->pos_emb >= SAT_DIT_POS_NONE &&
+                      o->pos_emb <= SAT_DIT_POS_ABSOLUTE,
+                  SAT_E_UNSUPPORTED, "dit_plan_set_transformer_options: unknown value (qk_norm %d, pos_emb %d, rotary %d)", o->qk_norm, o->pos_emb,
+                  o->rotary);
+    SAT_CHECK_ARG(o->pos_emb != SAT_DIT_POS_ABSOLUTE || (o->abs_pos_max_len > 0 && o->abs_pos_max_len <= (1 << 20)), SAT_E_INVALID,
+                  "dit_plan_set_transformer_options: abs_pos_max_len %d with absolute position embeddings", o->abs_pos_max_len);
+    // the e4m3 epilogues (per-token x per-channel scales, the 8-phase block-scaled build) carry no normalisation
+    SAT_CHECK_ARG(!(o->qk_norm && p->cfg.gemm_dtype == 1), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_transformer_options: qk_norm with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
+    p->qk_norm = o->qk_norm != 0;
+    p->pos_emb = o->pos_emb;
+    p->abs_max = o->pos_emb == SAT_DIT_POS_ABSOLUTE ? o->abs_pos_max_len : 0;
+    p->rotary = o->rotary != 0;
     return 0;
 }
 

@@ -141,10 +141,11 @@ __global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restr
     }
 }
 
-// [M, parts * H * 64] -> per part [B, H, S, 64] fp32; parts with rope: partial rotary on d < 32 (pairs d, d + 16)
+// [M, parts * H * 64] -> per part [B, H, S, 64] fp32; parts with rope: partial rotary on d < 32 (pairs d, d + 16); parts in norm_mask:
+// L2-normalised per head first (qk_norm, transformer.py:433-436; F.normalize: x / max(|x|, 1e-12)).  One wave = the 64 channels of one head row.
 __global__ __launch_bounds__(256) void split_heads_f32_kernel(const float* __restrict__ src, float* __restrict__ d0, float* __restrict__ d1,
                                                               float* __restrict__ d2, int M, int S, int parts, int H, int rope_mask,
-                                                              const float* __restrict__ rope_cos, const float* __restrict__ rope_sin) {
+                                                              const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, int norm_mask) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t total = (int64_t)M * parts * H * 64;
     if (idx >= total) return;
@@ -161,6 +162,8 @@ __global__ __launch_bounds__(256) void split_heads_f32_kernel(const float* __res
         const float cs = rope_cos[(size_t)s * 16 + (d & 15)], sn = rope_sin[(size_t)s * 16 + (d & 15)];
         v = d < 16 ? v * cs - row[d + 16] * sn : v * cs + row[d - 16] * sn;
     }
+    // (the rotation is orthogonal: the norm of the rotated row is the norm of the row; total % 64 == 0, so whole waves get here)
+    if ((norm_mask >> part) & 1) v /= fmaxf(sqrtf(wave_sum(v * v)), 1e-12f);
     float* dst = part == 0 ? d0 : (part == 1 ? d1 : d2);
     dst[(((size_t)b * H + h) * S + s) * 64 + d] = v;
 }
@@ -262,11 +265,11 @@ int sat_launch_layernorm_f32(const float* x, const float* gamma, const float* be
 }
 
 int sat_launch_split_heads_f32(const float* src, float* d0, float* d1, float* d2, int M, int S, int parts, int H, int rope_mask,
-                               const float* rope_cos, const float* rope_sin, hipStream_t s) {
+                               const float* rope_cos, const float* rope_sin, hipStream_t s, int norm_mask) {
     SAT_CHECK_ARG(src && d0 && parts >= 1 && parts <= 3 && (rope_mask == 0 || (rope_cos && rope_sin)), SAT_E_INVALID, "split_heads_f32: bad args");
     const int64_t total = (int64_t)M * parts * H * 64;
     hipLaunchKernelGGL(split_heads_f32_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, src, d0, d1, d2, M, S, parts, H, rope_mask, rope_cos,
-                       rope_sin);
+                       rope_sin, norm_mask);
     SAT_LAUNCH_CHECK();
     return 0;
 }

@@ -22,7 +22,8 @@
 
 namespace {
 
-template <int EPI, int MI, int NI, bool LNC = false>
+// QKN (EPI_HEADS only): the instantiation behind EPI_HEADS_QKN -- parts with kind bit 4 are L2-normalised per head (qk_norm)
+template <int EPI, int MI, int NI, bool LNC = false, bool QKN = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[MI][NI], const int mw, const int nw, const int half,
                                               const int l31, const float2* ln = nullptr, const float* lc1 = nullptr,
                                               const float* lc2 = nullptr) {
@@ -153,6 +154,13 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[M
                         v0[e] = rstd * (v0[e] - mean * c1a) + c2a;
                         v1[e] = rstd * (v1[e] - mean * c1b) + c2b;
                     }
+                    if constexpr (QKN) {
+                        if (kind & 16) {   // wave-uniform: the 64 channels of this head row sit in the 32 lanes of this half, two each
+                            const float inv = rsqrtf(fmaxf(half32_sum(v0[e] * v0[e] + v1[e] * v1[e]), 1e-24f));      // 1 / max(|x|, 1e-12)
+                            v0[e] *= inv;
+                            v1[e] *= inv;
+                        }
+                    }
                     if (kind & 2) {   // wave-uniform: partial RoPE on d < 32 (pairs d, d^16)
                         float p = __shfl_xor(v0[e], 16, 64);
                         int jf = l31 & 15;
@@ -220,7 +228,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[M
 // V^T (token-contiguous destination) and fp32 output keep the un-swapped orientation: the epilogue above, resp. the staged one below.
 // ---------------------------------------------------------------------------------------------
 // ROPE_PRE: the rotation table rows of all MI row blocks are fetched up front (not in the 128-register budget of the 16-wave tile)
-template <int EPI, int MI, int NI, bool LNC = false, bool ROPE_PRE = true>
+template <int EPI, int MI, int NI, bool LNC = false, bool ROPE_PRE = true, bool QKN = false>
 __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& g, f32x16 (&acc)[MI][NI], const int mw, const int nw, const int half,
                                                 const int l31, const float2* ln = nullptr, const float* lc1 = nullptr,
                                                 const float* lc2 = nullptr, unsigned (*qfrag)[8] = nullptr) {
@@ -354,6 +362,22 @@ __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& g, f32x16 (&acc)
                         for (int e = 0; e < 4; ++e) acc[i][j][4 * q + e] = st.y * (acc[i][j][4 * q + e] - st.x * c1[e]) + c2[e];
                     }
             }
+            if constexpr (QKN) {
+                if (kind & 16) {   // qk_norm: the 64 channels of the lane's head row are its own 32 registers and those of lane ^ 32
+                    float ss = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) ss += acc[i][j][r] * acc[i][j][r];
+                    unsigned a = __float_as_uint(ss), b = a;
+                    half_swap(a, b);                   // a: the low half's sum in both halves, b: the high half's
+                    const float inv = rsqrtf(fmaxf(__uint_as_float(a) + __uint_as_float(b), 1e-24f));      // 1 / max(|x|, 1e-12)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[i][j][r] *= inv;
+                }
+            }
             if (kind & 2) {   // partial RoPE on d < 32 (block j = 0): partner of d < 16 is d + 16 = register r + 8 of this lane
                 if constexpr (!ROPE_PRE) {
                     rcs[i][0] = *reinterpret_cast<const f32x4*>(he.rope_cos + (size_t)s * 16 + 4 * half);
@@ -471,9 +495,11 @@ __device__ __forceinline__ void gemm_epilogue_f32_staged(const GemmArgs& g, f32x
     }
 }
 
-template <int BM, int BN, int WM, int WN, int EPI>
+template <int BM, int BN, int WM, int WN, int EPIX>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs g) {
     sat_f16_saturate();
+    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX;
+    constexpr bool QKN = EPIX == EPI_HEADS_QKN;
     constexpr int NT = WM * WN * 64;
     constexpr int TM = BM / WM;
     constexpr int TN = BN / WN;
@@ -593,7 +619,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs g) {
     }
     compute((nk - 1) & 1);
 
-    gemm_epilogue<EPI, MI, NI>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31);
+    gemm_epilogue<EPI, MI, NI, false, QKN>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -603,9 +629,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs g) {
 // section 5.4 rule 21): lane l of the piece that covers rows 8p..8p+7 lands at row 8p + l/8,
 // position l%8, so it fetches logical chunk (l%8) ^ ((row>>1)&7) of that row.
 // ---------------------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, int EPI>
+template <int BM, int BN, int WM, int WN, int EPIX>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs g) {
     sat_f16_saturate();
+    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX;
+    constexpr bool QKN = EPIX == EPI_HEADS_QKN;
     constexpr int NT = WM * WN * 64;
     constexpr int TM = BM / WM;
     constexpr int TN = BN / WN;
@@ -711,7 +739,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs g) {
     }
     compute((nk - 1) & 1);
 
-    gemm_epilogue<EPI, MI, NI>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31);
+    gemm_epilogue<EPI, MI, NI, false, QKN>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -746,9 +774,12 @@ __device__ __forceinline__ int lds_off_bk(int row, int chunk) {
 // pieces in a row per producer wave stretch that chain, eight per wave in parallel with the MFMAs do not.  The ablation without any DMA runs 36.9 us.)
 // DIL ("DMA in loop", bf16 / fp16 operands): the iteration's LDS-DMA pieces are issued inside compute(), behind the MFMAs of the first k-steps, instead of
 // in front of it -- always on with K-groups; a per-tile choice otherwise (SatTile::dil, gemm_tiles.h)
-template <int BM, int BN, int BK, int WM, int WN, int NS, int EPI, int FP8 = 0, int KG = 1, bool DIL = false>
+template <int BM, int BN, int BK, int WM, int WN, int NS, int EPIX, int FP8 = 0, int KG = 1, bool DIL = false>
 __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g) {
     sat_f16_saturate();
+    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX;          // EPI_HEADS_QKN: the heads kernel with the qk_norm epilogue
+    constexpr bool QKN = EPIX == EPI_HEADS_QKN;
+    static_assert(!QKN || FP8 == 0, "qk_norm: 16-bit operands only");
     static_assert(KG == 1 || (KG == 2 && EPI == EPI_F32 && FP8 == 0 && BK == 64 && BM / WM == 64 && BN / WN == 64),
                   "K-groups: fp32 output, 64 x 64 wave tiles, 128-byte rows");
     constexpr int NT = KG * WM * WN * 64;
@@ -1246,7 +1277,7 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) qp[j][e] = 0u;
-            if (wave_rows_valid) gemm_epilogue_t<EPI, MI, NI, LN_CONS>(g, acc, m0 + wm * TM, n0, half, l31, lnst + wm * TM, lnc, lnc + BN, qp);
+            if (wave_rows_valid) gemm_epilogue_t<EPI, MI, NI, LN_CONS, true, QKN>(g, acc, m0 + wm * TM, n0, half, l31, lnst + wm * TM, lnc, lnc + BN, qp);
             opx8 qf[4];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -1366,13 +1397,14 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                 gemm_epilogue_f32_staged<MI>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane);
         }
     } else if (wave_rows_valid) {
-        if (tr) gemm_epilogue_t<EPI, MI, NI, LN_CONS, (NT < 1024)>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
-        else gemm_epilogue<EPI, MI, NI, LN_CONS>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
+        if (tr) gemm_epilogue_t<EPI, MI, NI, LN_CONS, (NT < 1024), QKN>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
+        else gemm_epilogue<EPI, MI, NI, LN_CONS, QKN>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
     }
 }
 
-template <int BM, int BN, int BK, int WM, int WN, int NS, int EPI, int FP8 = 0, int KG = 1, bool DIL = false>
+template <int BM, int BN, int BK, int WM, int WN, int NS, int EPIX, int FP8 = 0, int KG = 1, bool DIL = false>
 int launch_pipe(const GemmArgs& a, hipStream_t stream) {
+    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX;
     constexpr int NT = KG * WM * WN * 64;
     constexpr bool LN_CONS = (EPI == EPI_SWIGLU || EPI == EPI_HEADS) && FP8 == 0;
     constexpr int LDS = NS * KG * ((BM + BN) * BK * 2 + (FP8 == 3 ? BM * 4 : 0)) + (LN_CONS ? (BM + BN) * 8 : 0);     // + (mean, rstd) per row, (c1, c2) per column
@@ -1381,7 +1413,7 @@ int launch_pipe(const GemmArgs& a, hipStream_t stream) {
     SAT_CHECK_ARG((!a.xb && !a.ln_part_out) || (EPI == EPI_F32 && BN / WN == 64 && FP8 == 0 && a.xb && a.ln_part_out), SAT_E_UNSUPPORTED,
                   "gemm: the bf16 image / row statistics come from the bf16 fp32-output tiles with 64-column wave tiles");
     static_assert(EPI != EPI_F32 || BN / WN != 64 || LDS >= WM * WN * 8192, "the staged fp32 epilogue needs 8 KiB of LDS per wave");
-    auto kern = gemm_pipe_kernel<BM, BN, BK, WM, WN, NS, EPI, FP8, KG, DIL>;
+    auto kern = gemm_pipe_kernel<BM, BN, BK, WM, WN, NS, EPIX, FP8, KG, DIL>;
     // fused cross-attention (HeadsEpi::xa_k): three K / V^T tiles of 64 keys behind the ring and the LayerNorm constants
     constexpr bool XA_OK = EPI == EPI_HEADS && BM == 128 && BN == 64 && BK == 64 && WM == 4 && WN == 1 && NS == 3 && FP8 == 0;
     constexpr int XA_LDS = XA_OK ? ((NS * (BM + BN) * BK * 2 + (BM + BN) * 8 + 1023) & ~1023) + 3 * 16384 : LDS;
@@ -1392,7 +1424,7 @@ int launch_pipe(const GemmArgs& a, hipStream_t stream) {
         if (xa) {
             const HeadsEpi& he = a.heads;
             SAT_CHECK_ARG(XA_OK, SAT_E_UNSUPPORTED, "gemm: the fused cross-attention epilogue lives in the 128 x 64 tile (variant 16)");
-            SAT_CHECK_ARG(he.parts == 1 && he.kind[0] == 8 && he.qscale == SAT_ATTN_QSCALE && he.xa_vt && he.xa_out && he.xa_kvh > 0 &&
+            SAT_CHECK_ARG(he.parts == 1 && (he.kind[0] & ~16) == 8 && he.qscale == SAT_ATTN_QSCALE && he.xa_vt && he.xa_out && he.xa_kvh > 0 &&
                               he.heads % he.xa_kvh == 0 && he.xa_sk > 0 && he.xa_sk + 3 <= 192 && he.xa_sk_pad >= he.xa_sk + 3 && he.xa_sk_pad % 64 == 0,
                           SAT_E_UNSUPPORTED, "gemm: fused cross-attention needs one pre-scaled row-major part and at most 189 keys (got %d)", he.xa_sk);
         }
@@ -1457,7 +1489,7 @@ int launch_epi(int tile, const GemmArgs& a, hipStream_t stream) {
                 SAT_TILE_CASE(SAT_TILE_128_KGROUP)
             }
         }
-        if constexpr (EPI == EPI_HEADS) {
+        if constexpr (EPI == EPI_HEADS || EPI == EPI_HEADS_QKN) {
             switch (tile) { SAT_TILE_CASE(SAT_TILE_128x64_XATTN) }
         }
     }
@@ -1518,6 +1550,14 @@ int SAT_OPNS::sat_launch_gemm(int epi, const GemmArgs& a, hipStream_t stream) {
     s.heads = a.heads.heads; s.xattn = a.heads.xa_k != nullptr;
     s.slab_ok = cus > 0 && a.slab && a.slab_bytes >= (size_t)cus * 65536 * sizeof(float);
     s.e4m3_built = !SAT_OP_IS_F16;
+    // qk_norm (HeadsEpi::kind bit 4) is built into the ring tiles' heads epilogues: tile policy 22 keeps the 8-phase kernel out of the choice
+    const bool qkn = epi == EPI_HEADS && ((a.heads.kind[0] | a.heads.kind[1] | a.heads.kind[2]) & 16);
+    if (qkn) {
+        SAT_CHECK_ARG(!a.fp8, SAT_E_UNSUPPORTED, "gemm: qk_norm with e4m3 operands is not built");
+        for (int pt = 0; pt < a.heads.parts; ++pt)
+            SAT_CHECK_ARG(!(a.heads.kind[pt] & 16) || !(a.heads.kind[pt] & 1), SAT_E_UNSUPPORTED, "gemm: qk_norm on a transposed destination");
+        s.variant = (a.variant & ~(7 << SAT_TILE_POLICY_SHIFT)) | sat_tile_policy_bits(22);
+    }
     const GemmRoute r = sat_gemm_route(epi, s, cus);
     switch (r.msg) {
         case SAT_ROUTE_OK: break;
@@ -1527,10 +1567,11 @@ int SAT_OPNS::sat_launch_gemm(int epi, const GemmArgs& a, hipStream_t stream) {
         case SAT_ROUTE_PH8_NOT_BUILT: sat_set_error("gemm(8-phase): epilogue %d / ablation %d not built", epi, r.tile); return SAT_E_UNSUPPORTED;
         default: sat_set_error("gemm: unknown variant %d (or not built for this epilogue)", r.tile); return SAT_E_INVALID;
     }
+    SAT_CHECK_ARG(!qkn || r.family != SAT_GEMM_PH8, SAT_E_UNSUPPORTED, "gemm(8-phase): no qk_norm epilogue (variant %d forces the kernel)", a.variant);
     if (r.family == SAT_GEMM_PH8) return sat_launch_gemm_ph8(epi, r.ph8, a, stream);
     switch (epi) {
         case EPI_SWIGLU: return launch_flavour<EPI_SWIGLU>(r, a, stream);
-        case EPI_HEADS: return launch_flavour<EPI_HEADS>(r, a, stream);
+        case EPI_HEADS: return qkn ? launch_epi<EPI_HEADS_QKN, 0>(r.tile, a, stream) : launch_flavour<EPI_HEADS>(r, a, stream);
         default: return launch_flavour<EPI_F32>(r, a, stream);          // EPI_F32, EPI_RESID
     }
 }

@@ -134,6 +134,9 @@ constexpr SatPh8Params sat_ph8_params(int build) {
 // The choice
 // ---------------------------------------------------------------------------------------------------------------------------------
 enum { EPI_F32 = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_HEADS = 3 };
+// Template argument only, never a caller's `epi` (sat_gemm_route answers for EPI_HEADS): the heads epilogue built with the per-head L2
+// normalisation of qk_norm (HeadsEpi::kind bit 4).  A separate instantiation so that the default heads kernels keep their code and registers.
+enum { EPI_HEADS_QKN = 4 };
 
 struct GemmShape {          // what the rule reads of a GemmArgs, the build and the device
     int M, N, K;

@@ -195,6 +195,11 @@ __device__ __forceinline__ float row16_sum(float v) {
     v += dpp_move<0x140>(v);
     return v;
 }
+// sum over the 32 lanes of a wave half, result in every lane (half32_max with +)
+__device__ __forceinline__ float half32_sum(float v) {
+    v = row16_sum(v);
+    return v + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x401F));   // lane ^ 16
+}
 
 // Accumulators of a 32x32 MFMA block issued with the operands swapped (weight fragment first) hold C^T: lane l31 owns one output ROW,
 // its 16 registers are channels 8*(r>>2) + 4*half + (r&3) -- four runs of four.  half_swap exchanges one dword of runs g and g+1
@@ -268,6 +273,9 @@ struct HeadsEpi {
                          // bit2: key-side tensor (K / V^T): rows/columns of sequence b shifted by (b*S)&3
                          // bit3: query tensor written PRE-SCALED by `qscale` (row-major destinations only): the attention
                          //       kernel then gets log2-domain scores straight out of its first MFMA (SAT_ATTN_QSCALE)
+                         // bit4: qk_norm (transformer.py:433-436): every head row is L2-normalised on the fp32 accumulators, x / max(|x|, 1e-12),
+                         //       before the rotation and the pre-scale (row-major destinations, 16-bit operands).  Any part with this bit sends
+                         //       the launch to the EPI_HEADS_QKN instantiations of the ring tiles; without it nothing changes
     float qscale;
     // Fused cross-attention (one part, row-major, pre-scaled, 128 x 64 tile = one head per workgroup column): the epilogue does not
     // store Q at all -- each wave keeps its 32 queries x 64 channels as MFMA fragments and runs softmax(q k^T) v against the
@@ -369,7 +377,7 @@ int sat_launch_gemm_f32(const float* A, const float* W, const float* bias, float
 int sat_launch_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int m, int d, const float* sc,
                              const float* sh, int rps, int ld, hipStream_t s, float eps = 1e-5f);
 int sat_launch_split_heads_f32(const float* src, float* d0, float* d1, float* d2, int M, int S, int parts, int H, int rope_mask,
-                               const float* rope_cos, const float* rope_sin, hipStream_t s);
+                               const float* rope_cos, const float* rope_sin, hipStream_t s, int norm_mask = 0);      // norm_mask: parts L2-normalised per head (qk_norm)
 int sat_launch_swiglu_f32(const float* hg, float* h, int64_t M, int inner, hipStream_t s);
 int sat_launch_attention_f32(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int sq, int sk,
                              hipStream_t s);

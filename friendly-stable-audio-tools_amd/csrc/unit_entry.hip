@@ -134,9 +134,10 @@ extern "C" int sat_attention_prescaled_f16(const void* q, const void* k, const v
     return attention_prescaled_bf16_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
 }
 
+// qkn: q and k L2-normalised per head (qk_norm), q pre-scaled for the attention kernel as in the plan
 static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
                                  float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
-                                 sat_stream_t stream) {
+                                 sat_stream_t stream, bool qkn = false) {
     SAT_CHECK_ARG(a && w && inv_freq && q && k && vt && rope_scratch, SAT_E_INVALID, "qkv_rope: null pointer");
     SAT_CHECK_ARG(d % 64 == 0 && s_pad >= s_len + 3 && s_pad % 128 == 0, SAT_E_INVALID, "qkv_rope: bad dims (s_pad >= s + 3, %% 128)");
     hipStream_t s = (hipStream_t)stream;
@@ -153,9 +154,20 @@ static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float
     g.A = (const op_t*)a; g.W = (const op_t*)w; g.M = b * s_len; g.N = 3 * d; g.K = d; g.variant = variant;
     g.heads.out[0] = (op_t*)q; g.heads.out[1] = (op_t*)k; g.heads.out[2] = (op_t*)vt;
     g.heads.kind[0] = 2; g.heads.kind[1] = 2 | 4; g.heads.kind[2] = 1 | 4;
+    if (qkn) { g.heads.kind[0] |= 8 | 16; g.heads.kind[1] |= 16; g.heads.qscale = SAT_ATTN_QSCALE; }
     g.heads.parts = 3; g.heads.heads = H; g.heads.S = s_len; g.heads.Spad = s_pad;
     g.heads.rope_cos = cs; g.heads.rope_sin = sn;
     return sat_launch_gemm(EPI_HEADS, g, s);
+}
+extern "C" int sat_qkv_rope_qknorm_bf16(const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
+                                        float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
+                                        sat_stream_t stream) {
+    return qkv_rope_bf16_impl(0, a, w, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream, true);
+}
+extern "C" int sat_qkv_rope_qknorm_f16(const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
+                                       float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,
+                                       sat_stream_t stream) {
+    return qkv_rope_bf16_impl(1, a, w, inv_freq, q, k, vt, rope_scratch, b, s_len, s_pad, d, variant, stream, true);
 }
 extern "C" int sat_qkv_rope_bf16(const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
                                  float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,

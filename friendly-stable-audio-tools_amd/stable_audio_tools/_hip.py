@@ -28,6 +28,13 @@ class SatDitCfg(Structure):
                 ("cross_attention", c_int32), ("tile_policy", c_int32)]
 
 
+class SatDitTransformerOptions(Structure):
+    _fields_ = [("qk_norm", c_int32), ("pos_emb", c_int32), ("abs_pos_max_len", c_int32), ("rotary", c_int32)]
+
+
+DIT_POS_NONE, DIT_POS_SINUSOIDAL, DIT_POS_ABSOLUTE = 0, 1, 2     # include/sat_hip.h: SAT_DIT_POS_*
+
+
 class SatT5Cfg(Structure):
     _fields_ = [("vocab_size", c_int32), ("d_model", c_int32), ("d_kv", c_int32), ("d_ff", c_int32), ("num_layers", c_int32),
                 ("num_heads", c_int32), ("rel_buckets", c_int32), ("rel_max_distance", c_int32), ("gated_gelu", c_int32),
@@ -64,6 +71,7 @@ _SIGNATURES = {
     "sat_dit_prepare_context": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "sat_dit_set_null_context_from": (c_int32, [c_void_p, c_int32]),
     "sat_dit_plan_set_extra_conditioning": (c_int32, [c_void_p, c_int32, c_int32, c_int32]),
+    "sat_dit_plan_set_transformer_options": (c_int32, [c_void_p, POINTER(SatDitTransformerOptions), c_size_t]),
     "sat_dit_prepare_extra_conditioning": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "sat_dit_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_dit_denoise_cfg": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int32, c_int32, c_void_p,
@@ -117,6 +125,8 @@ _SIGNATURES = {
                                                c_int32, c_int32, c_void_p]),
     "sat_qkv_rope_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                     c_int32, c_int32, c_int32, c_void_p]),
+    "sat_qkv_rope_qknorm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                           c_int32, c_int32, c_int32, c_void_p]),
     "sat_gemm_resid_ln_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                          c_void_p]),
     "sat_gemm_swiglu_ln_bf16": (c_int32, [c_void_p] * 9 + [c_int32, c_int32, c_int32, c_int32, c_void_p]),
@@ -140,7 +150,7 @@ _SIGNATURES = {
 }
 
 # the same unit-level entry points on IEEE fp16 operands (gemm_dtype = 3): identical signatures
-for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_qkv_rope_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws"):
+for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws"):
     _SIGNATURES[_n.replace("bf16", "f16")] = _SIGNATURES[_n]
 
 _lib = None

@@ -84,6 +84,8 @@ class DiffusionTransformer(nn.Module):
 
         self._plan = None
         self._plan_version = None
+        self._plan_options = None
+        self._gen_prepend_len = 0
         self._ws = None
         self._ctx_key = None
         self._ext_key = None
@@ -92,6 +94,27 @@ class DiffusionTransformer(nn.Module):
         self.layernorm_fusion = True
         self.cross_attention_fusion = True
         self.tile_policy = 0
+        self._check_options(self.gemm_dtype)
+
+    def transformer_options(self):
+        """``(qk_norm, pos_emb, abs_pos_max_len, rotary)`` of ``self.transformer`` as ``sat_dit_plan_set_transformer_options`` takes them."""
+        tr = self.transformer
+        pos = _hip.DIT_POS_SINUSOIDAL if tr.use_sinusoidal_emb else _hip.DIT_POS_ABSOLUTE if tr.use_abs_pos_emb else _hip.DIT_POS_NONE
+        return (1 if tr.qk_norm else 0, pos, tr.pos_emb.max_seq_len if tr.use_abs_pos_emb and not tr.use_sinusoidal_emb else 0,
+                0 if tr.rotary_pos_emb is None else 1)
+
+    def _check_options(self, gemm_dtype):
+        if self.transformer.qk_norm and GEMM_DTYPES[gemm_dtype] == 1:
+            raise NotImplementedError(f"attn_kwargs qk_norm=True with gemm_dtype={gemm_dtype!r}: the e4m3 projections have no normalising epilogue; "
+                                      "use gemm_dtype 'fp16', 'bf16' or 'fp32x' for a qk_norm model")
+
+    def _check_seq_len(self, t_len, prepend_len):
+        """The reference's ``AbsolutePositionalEmbedding`` assertion (transformer.py:59-61), on the host before anything is launched."""
+        pe = self.transformer.pos_emb
+        if self.transformer.use_abs_pos_emb and not self.transformer.use_sinusoidal_emb:
+            seq_len = prepend_len + t_len + (0 if self.global_cond_type == "adaLN" else 1)
+            assert seq_len <= pe.max_seq_len, \
+                f"you are passing in a sequence length of {seq_len} but your absolute positional embedding has a max sequence length of {pe.max_seq_len}"
 
     def residual_stream_report(self, enable: bool = True):
         """Build extension (``sat_dit_debug``), for checkpoints this build was never run on.  ``residual_stream_report(True)`` switches the
@@ -152,6 +175,7 @@ class DiffusionTransformer(nn.Module):
         MFMA, fp32 q / k / v / P; ~20x slower): the same plan and data flow with no operand rounding.  Rebuilds the plan on next use."""
         if dtype not in GEMM_DTYPES:
             raise ValueError(f"gemm_dtype must be one of {sorted(GEMM_DTYPES)}")
+        self._check_options(dtype)
         if dtype != self.gemm_dtype:
             self.gemm_dtype = dtype
             self._plan_version = None
@@ -166,8 +190,10 @@ class DiffusionTransformer(nn.Module):
 
     def _ensure_plan(self):
         ver = _init.params_version(self)
-        if self._plan is not None and ver == self._plan_version:
+        options = self.transformer_options()
+        if self._plan is not None and ver == self._plan_version and options == self._plan_options:
             return self._plan
+        self._check_options(self.gemm_dtype)
         lib = _hip.lib()
         dev = self.timestep_features.weight.device
         if dev.type != "cuda":
@@ -182,10 +208,14 @@ class DiffusionTransformer(nn.Module):
         def configure(plan):
             if self.input_concat_dim > 0 or self.prepend_cond_dim > 0:
                 _hip.check(lib.sat_dit_plan_set_extra_conditioning(plan, self.input_concat_dim, self.prepend_cond_dim, self.max_prepend_len))
+            if options != (0, _hip.DIT_POS_NONE, 0, 1):       # a model with none of these switches never makes the call
+                opts = _hip.SatDitTransformerOptions(*options)
+                _hip.check(lib.sat_dit_plan_set_transformer_options(plan, ctypes.byref(opts), ctypes.sizeof(opts)))
 
         create = lambda: _hip.new_handle(lib.sat_dit_plan_create_sized, ctypes.byref(cfg), ctypes.sizeof(cfg))
         plan = self._plan = _hip.build_plan("dit", create, self.state_dict(), dev, configure)
         self._plan_version = ver
+        self._plan_options = options
         self._ctx_key = None
         self._ext_key = None
         return plan
@@ -270,6 +300,7 @@ class DiffusionTransformer(nn.Module):
         x = x.detach().float().contiguous()
         t = t.detach().float().contiguous()
         bf, _, t_len = x.shape
+        self._check_seq_len(t_len, 0 if prepend_cond is None else prepend_cond.shape[1])
         if cross_attn_cond is None and global_embed is None:
             self.prepare_context_bf(bf)
         else:
@@ -345,11 +376,13 @@ class DiffusionTransformer(nn.Module):
             self.prepare_context(bc, bg, null_from)
         self.prepare_extra(bcat, bpre, self._ctx_nseq)
         self._gen_prepend = prepend_cond is not None
+        self._gen_prepend_len = 0 if prepend_cond is None else prepend_cond.shape[1]
 
     @torch.no_grad()
     def denoise(self, x, sigma: float, cfg_scale: float = 1.0, scale_phi: float = 0.0, out=None):
         """k-diffusion VDenoiser(DiT with batched CFG)(x, sigma) -- ``sat_dit_denoise_cfg``."""
         b, _, t_len = x.shape
+        self._check_seq_len(t_len, self._gen_prepend_len)
         use_cfg = cfg_scale != 1.0 and (self.cond_token_dim > 0 or self._gen_prepend)
         ws = self._workspace(2 * b if use_cfg else b, t_len)
         if out is None:

@@ -2,8 +2,10 @@
 
 Mirror of the module tree of the reference's ``models/transformer.py`` (``LayerNorm`` :188-206,
 ``GLU``/``FeedForward`` :211-287, ``Attention`` :290-554, ``TransformerBlock`` :594-702,
-``RotaryEmbedding`` :99-155, ``ContinuousTransformer`` :705-809) restricted to the options
-the shipped DiT configs use.  These classes only *hold* parameters under the reference's
+``RotaryEmbedding`` :99-155, ``AbsolutePositionalEmbedding`` / ``ScaledSinusoidalEmbedding`` :50-96,
+``ContinuousTransformer`` :705-809) restricted to the options the HIP plan runs: those of the shipped DiT
+configs plus ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False`` and
+bias-free / ``mult``-sized feed-forwards.  These classes only *hold* parameters under the reference's
 names; the forward pass of the whole stack is one C-ABI call (``sat_dit_forward`` /
 ``sat_dit_denoise_cfg``) issued by ``models/dit.py``.  Unsupported options raise.
 """
@@ -33,6 +35,26 @@ class RotaryEmbedding(nn.Module):
         self.register_buffer("inv_freq", inv_freq)
 
 
+class AbsolutePositionalEmbedding(nn.Module):
+    """``emb.weight[pos] * dim ** -0.5`` added to the stream (reference :50-71); the plan builds the table once."""
+
+    def __init__(self, dim, max_seq_len):
+        super().__init__()
+        self.scale = dim ** -0.5
+        self.max_seq_len = max_seq_len
+        self.emb = nn.Embedding(max_seq_len, dim)
+
+
+class ScaledSinusoidalEmbedding(nn.Module):
+    """``cat(sin, cos)(pos * theta ** -(j / (dim / 2))) * scale`` (reference :74-96).  ``inv_freq`` is not persistent there, so only
+    ``scale`` is in the state dict."""
+
+    def __init__(self, dim, theta=10000):
+        super().__init__()
+        assert (dim % 2) == 0, "dimension must be divisible by 2"
+        self.scale = nn.Parameter(torch.ones(1) * dim ** -0.5)
+
+
 class GLU(nn.Module):
     def __init__(self, dim_in, dim_out):
         super().__init__()
@@ -40,23 +62,31 @@ class GLU(nn.Module):
 
 
 class FeedForward(nn.Module):
-    def __init__(self, dim, mult=4, zero_init_output=True, **unsupported):
+    def __init__(self, dim, mult=4, glu=True, no_bias=False, use_conv=False, zero_init_output=True, **unsupported):
         super().__init__()
-        if unsupported:
-            raise NotImplementedError(f"FeedForward options not supported by the HIP path: {sorted(unsupported)}")
+        if not glu or use_conv or unsupported:
+            raise NotImplementedError("FeedForward options not supported by the HIP path (the FF-in GEMM has the SwiGLU epilogue only, no "
+                                      f"convolution): glu={glu} use_conv={use_conv} {sorted(unsupported)}")
         inner_dim = int(dim * mult)
-        linear_out = _init.linear(inner_dim, dim, zero=zero_init_output)
+        if inner_dim <= 0 or inner_dim % 64:
+            raise NotImplementedError(f"FeedForward mult={mult}: the HIP plan needs an inner dim that is a multiple of 64, got {inner_dim}")
+        self.no_bias = no_bias
+        # reference :222,270: GLU builds its own nn.Linear and keeps the bias; no_bias only drops the one of the output projection
+        linear_out = _init.linear(inner_dim, dim, bias=not no_bias, zero=zero_init_output)
         self.ff = nn.Sequential(GLU(dim, inner_dim), nn.Identity(), linear_out, nn.Identity())
 
 
 class Attention(nn.Module):
-    def __init__(self, dim, dim_heads=64, dim_context=None, causal=False, zero_init_output=True, **unsupported):
+    def __init__(self, dim, dim_heads=64, dim_context=None, causal=False, zero_init_output=True, qk_norm=False, natten_kernel_size=None,
+                 **unsupported):
         super().__init__()
-        if causal or unsupported:
-            raise NotImplementedError(f"Attention options not supported by the HIP path: causal={causal} {sorted(unsupported)}")
+        if causal or natten_kernel_size is not None or unsupported:
+            raise NotImplementedError(f"Attention options not supported by the HIP path (full non-causal attention only): causal={causal} "
+                                      f"natten_kernel_size={natten_kernel_size} {sorted(unsupported)}")
         if dim_heads != 64:
             raise NotImplementedError("the HIP attention kernel is built for dim_heads == 64")
         self.dim, self.dim_heads = dim, dim_heads
+        self.qk_norm = bool(qk_norm)
         dim_kv = dim_context if dim_context else dim
         self.num_heads = dim // dim_heads
         self.kv_heads = dim_kv // dim_heads
@@ -99,18 +129,26 @@ class ContinuousTransformer(nn.Module):
                  global_cond_dim=None, causal=False, rotary_pos_emb=True, zero_init_branch_outputs=True, conformer=False,
                  use_sinusoidal_emb=False, use_abs_pos_emb=False, abs_pos_emb_max_length=10000, **kwargs):
         super().__init__()
-        if not rotary_pos_emb or use_sinusoidal_emb or use_abs_pos_emb:
-            raise NotImplementedError("only rotary positional embedding is supported by the HIP path")
+        assert not (use_sinusoidal_emb and use_abs_pos_emb), "Can't select both of sinusoidal/abs positional embedding type."
         self.dim, self.depth, self.causal = dim, depth, causal
         self.project_in = _init.linear(dim_in, dim, bias=False) if dim_in else nn.Identity()
         self.project_out = _init.linear(dim, dim_out, bias=False) if dim_out else nn.Identity()
-        self.rotary_pos_emb = RotaryEmbedding(max(dim_heads // 2, 32))
+        self.rotary_pos_emb = RotaryEmbedding(max(dim_heads // 2, 32)) if rotary_pos_emb else None
+        self.use_sinusoidal_emb, self.use_abs_pos_emb = use_sinusoidal_emb, use_abs_pos_emb
+        self.pos_emb = None
+        if use_sinusoidal_emb:
+            self.pos_emb = ScaledSinusoidalEmbedding(dim)
+        elif use_abs_pos_emb:
+            self.pos_emb = AbsolutePositionalEmbedding(dim, abs_pos_emb_max_length)
         self.layers = nn.ModuleList([
             TransformerBlock(dim, dim_heads=dim_heads, cross_attend=cross_attend, dim_context=cond_token_dim,
                              global_cond_dim=global_cond_dim, causal=causal, zero_init_branch_outputs=zero_init_branch_outputs,
                              conformer=conformer, layer_ix=i, **kwargs)
             for i in range(depth)
         ])
+        # one attn_kwargs for every block and both attentions of it: the plan takes a single flag
+        self.qk_norm = bool(kwargs.get("attn_kwargs", {}).get("qk_norm", False))
+        assert all(a.qk_norm == self.qk_norm for l in self.layers for a in (l.self_attn, getattr(l, "cross_attn", l.self_attn)))
 
     def forward(self, *args, **kwargs):
         raise RuntimeError("ContinuousTransformer has no standalone forward in this build: the stack runs inside "

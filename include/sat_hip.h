@@ -59,6 +59,8 @@ const char* sat_last_error(void);
  * models/transformer.py:787-802).  Input-concat and prepend conditioning (dit.py:160-197)
  * through sat_dit_plan_set_extra_conditioning / sat_dit_prepare_extra_conditioning; prepend
  * conditioning with "adaLN" is rejected (the reference returns P + T frames there).
+ * qk_norm, the sinusoidal / absolute position embeddings and rotary_pos_emb=False through
+ * sat_dit_plan_set_transformer_options; a feed-forward without output bias by leaving the tensor out.
  * ---------------------------------------------------------------------------------- */
 typedef struct sat_dit_plan sat_dit_plan;
 
@@ -125,7 +127,9 @@ typedef struct sat_dit_cfg {
                                   round of workgroups (one prompt; transformer.py:430-437 + 496-536), two kernels otherwise; 1: always two kernels */
     int32_t tile_policy;       /* 0 / 80 (default): the measured tile choice; A/B measurement switches: 22 = the 16-wave 256 x 256 tile of rounds
                                   1-2 instead of the 8-phase kernel, 81 = the 8-phase kernel also for fp32-output GEMMs with K < 4096, 82 = no
-                                  two-K-group 128 x 128 tile */
+                                  two-K-group 128 x 128 tile.  The heads GEMMs of a qk_norm plan (sat_dit_plan_set_transformer_options) always run
+                                  under 22 whatever stands here: their normalising epilogue exists in the ring tiles only (81 / 82 concern the
+                                  fp32-output GEMMs and keep their meaning there) */
 } sat_dit_cfg;
 #define SAT_DIT_CFG_BYTES_V5 56          /* the layout sat_dit_plan_create reads: 14 int32 fields, up to and including tile_policy */
 
@@ -161,6 +165,33 @@ int sat_dit_plan_set_tensor(sat_dit_plan* plan, const char* name, const float* d
  * at most 256. */
 int sat_dit_plan_set_extra_conditioning(sat_dit_plan* plan, int32_t input_concat_dim, int32_t prepend_cond_dim,
                                         int32_t max_prepend_len);
+
+/* ContinuousTransformer switches beyond the shipped configs (models/transformer.py:298,433-436 qk_norm; :50-96,740-746,796-797
+ * use_sinusoidal_emb / use_abs_pos_emb; :737 rotary_pos_emb), between create and finalize; a plan never given this call has
+ * {0, SAT_DIT_POS_NONE, 0, 1} and builds and launches exactly what it did before this call existed.
+ *   qk_norm 1: q and k of the self-attention and of the cross-attention are L2-normalised per head over the 64 channels,
+ *     x / max(|x|, 1e-12), on the fp32 accumulators of their projection (before the rotation and the 1/sqrt(64) scale; one
+ *     16-bit rounding); the cross-attention keys once per generation in sat_dit_prepare_context.  gemm_dtype SAT_GEMM_FP8
+ *     with qk_norm is SAT_E_UNSUPPORTED.
+ *   pos_emb SAT_DIT_POS_SINUSOIDAL: cat(sin, cos)(pos * 10000^(-j / (D/2))) * scale is added to every row of the stream behind
+ *     project_in and the prepend concat (position 0 = the first prepended row); needs "transformer.pos_emb.scale" [1].
+ *     SAT_DIT_POS_ABSOLUTE: emb.weight[pos] * D^-0.5, needs "transformer.pos_emb.emb.weight" [abs_pos_max_len, D]; a forward
+ *     whose sequence (prepend rows + global token + t_len) is longer than abs_pos_max_len fails with SAT_E_INVALID before
+ *     any launch (the reference asserts).  The table is built once in finalize; one small launch per forward adds it.
+ *   rotary 0: no "transformer.rotary_pos_emb.inv_freq" tensor, q / k are not rotated.
+ * options_bytes = sizeof(sat_dit_transformer_options) of the caller's header; any other size is SAT_E_INVALID, a value outside the
+ * ones above SAT_E_UNSUPPORTED, a call after finalize SAT_E_STATE.
+ * Independent of this call, a state dict without "transformer.layers.N.ff.ff.2.bias" (ff_kwargs no_bias) runs FF-out without a bias. */
+#define SAT_DIT_POS_NONE 0
+#define SAT_DIT_POS_SINUSOIDAL 1
+#define SAT_DIT_POS_ABSOLUTE 2
+typedef struct sat_dit_transformer_options {
+    int32_t qk_norm;           /* attn_kwargs {"qk_norm": true} */
+    int32_t pos_emb;           /* SAT_DIT_POS_* */
+    int32_t abs_pos_max_len;   /* "abs_pos_emb_max_length" (SAT_DIT_POS_ABSOLUTE only; ignored otherwise) */
+    int32_t rotary;            /* "rotary_pos_emb" (1 in every shipped config) */
+} sat_dit_transformer_options;
+int sat_dit_plan_set_transformer_options(sat_dit_plan* plan, const sat_dit_transformer_options* options, size_t options_bytes);
 
 /* Checks that every required tensor was set, converts GEMM weights to bf16 (SwiGLU rows
  * interleaved), folds the 1x1 pre/post convs into the in/out projections, builds the RoPE
@@ -416,6 +447,12 @@ int sat_cross_attention_fused_bf16(const void* a_bf16_dev, const void* wq_bf16_d
 int sat_qkv_rope_bf16(const void* a_bf16_dev, const void* w_bf16_dev, const float* inv_freq_dev,
                       void* q_dev, void* k_dev, void* vt_dev, float* rope_scratch_dev,
                       int32_t b, int32_t s, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream);
+/* The same step of a qk_norm model (sat_dit_transformer_options.qk_norm; transformer.py:433-436): q and k are L2-normalised per head,
+ * x / max(|x|, 1e-12), on the fp32 accumulators before the rotation, and q is written pre-scaled by log2(e) / 8 (the layout
+ * sat_attention_prescaled_bf16 reads).  Ring tiles only: a variant that forces the 8-phase kernel is SAT_E_UNSUPPORTED. */
+int sat_qkv_rope_qknorm_bf16(const void* a_bf16_dev, const void* w_bf16_dev, const float* inv_freq_dev,
+                             void* q_dev, void* k_dev, void* vt_dev, float* rope_scratch_dev,
+                             int32_t b, int32_t s, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream);
 /* LayerNorm folded into the GEMMs either side of it (sat_dit_cfg.ln_fold; models/transformer.py:692-700: x + f(LayerNorm(x))).
  * Producer = the GEMM that updates the residual stream (to_out, FF-out; transformer.py:319, 270):
  *   c [m, n] fp32 += a [m, k] . w [n, k]^T + bias; xb [m, n] bf16 = bf16(c); ln_part [m][n / 64][2] fp32 = per 64-column block
@@ -468,6 +505,9 @@ int sat_cross_attention_fused_f16(const void* a_f16_dev, const void* wq_f16_dev,
 int sat_qkv_rope_f16(const void* a_f16_dev, const void* w_f16_dev, const float* inv_freq_dev,
                      void* q_dev, void* k_dev, void* vt_dev, float* rope_scratch_dev,
                      int32_t b, int32_t s, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream);
+int sat_qkv_rope_qknorm_f16(const void* a_f16_dev, const void* w_f16_dev, const float* inv_freq_dev,
+                            void* q_dev, void* k_dev, void* vt_dev, float* rope_scratch_dev,
+                            int32_t b, int32_t s, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream);
 int sat_gemm_resid_ln_f16(const void* a_f16_dev, const void* w_f16_dev, const float* bias_dev, float* c_dev, void* xb_dev,
                           float* ln_part_dev, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream);
 int sat_gemm_swiglu_ln_f16(const void* xb_dev, const float* ln_part_dev, const float* w_f32_dev, const float* gamma_dev,
