@@ -16,14 +16,25 @@
 // ------------------------------------------------------------------------------ plan
 namespace {
 
+// One Linear of a block as its GEMM sees it.  The kind is decided once (proj_kind), written by pack_proj and read by every launch
+enum ProjKind {
+    PROJ_PLAIN,        // w: 16-bit [n, k] (bf16, or fp16 in the fp16 build)
+    PROJ_LN_FOLD,      // w: 16-bit gamma (.) W of the LayerNorm in front, finished in the epilogue with c1 / c2 (GemmArgs::ln_c1 / ln_c2; the bias is in c2)
+    PROJ_FP8_ROW,      // w: e4m3 bytes, scale per output channel; A: e4m3 with one scale per row, written by the quantising LayerNorm
+    PROJ_FP8_MX,       // w: as above; A: MXFP8, E8M0 block scales written by A's producer (attention kernels, FF-in epilogue)
+    PROJ_F32,          // w: the reference's own fp32 weights, no re-packing (fp32 verification mode, f32_ref.hip)
+};
+struct Proj {
+    op_t* w = nullptr;
+    int n = 0, k = 0;
+    ProjKind kind = PROJ_PLAIN;
+    float *scale = nullptr, *c1 = nullptr, *c2 = nullptr, *bias = nullptr;
+};
+enum ProjFamily { FAM_QKV, FAM_O, FAM_CQ, FAM_CKV, FAM_CO, FAM_FF1, FAM_FF2 };
+
 struct LayerW {
     float *pre_g, *pre_b, *cross_g, *cross_b, *ff_g, *ff_b;
-    op_t *w_qkv, *w_o, *w_cq, *w_ckv, *w_co, *w_ff1, *w_ff2;
-    float *b_ff1, *b_ff2;
-    float *s_qkv, *s_cq, *s_ff1, *s_ff2, *s_o, *s_co;      // gemm_dtype: per-output-channel scales (the weights above then hold e4m3 bytes)
-    // LayerNorm folded into the GEMM behind it (plan->ln_fold): the weights above are bf16(gamma (.) W); GemmArgs::ln_c1 / ln_c2
-    float *c1_qkv, *c2_qkv, *c1_cq, *c2_cq, *c1_ff1, *c2_ff1;
-    bool fold_qkv;      // false for layer 0: its pre_norm reads rows written by the input projection, not by a GEMM epilogue
+    Proj qkv, o, cq, ckv, co, ff1, ff2;
 };
 
 }  // namespace
@@ -45,8 +56,7 @@ struct sat_dit_plan {
     int tile_bits = 0;              // cfg.tile_policy as GemmArgs::variant bits (sat_tile_policy_bits)
     bool ln_fold = false;           // cfg.ln_fold, bf16 / fp16 operands, "prepend" conditioning: LayerNorms run inside the GEMM epilogues
     int fp8_mode = 2;               // 2: v_mfma_scale_f32_32x32x64_f8f6f4 (unit scales, 2x rate); 1: v_mfma_f32_32x32x16_fp8_fp8
-    // gemm_dtype == 1: which GEMM families take e4m3 operands (sat_dit_cfg.fp8_families; SAT_FP8_* bits); 0 in every other mode
-    bool f8_qkv = false, f8_cq = false, f8_ff1 = false, f8_ff2 = false, f8_o = false;
+    int fp8_families = 0;           // gemm_dtype == 1: which GEMM families take e4m3 operands (sat_dit_cfg.fp8_families; SAT_FP8_* bits); 0 in every other mode
     float* ssg_w = nullptr;         // adaLN: [depth * 6D, D] stacked to_scale_shift_gate weights
     // input-concat / prepend conditioning (sat_dit_plan_set_extra_conditioning): win_eff then spans io_channels + concat_dim input channels
     int concat_dim = 0, prepend_dim = 0, max_prep = 0;
@@ -98,47 +108,47 @@ int seq_len(const sat_dit_plan* p, int T, int P) { return P + T + (p->cfg.adaln 
 int get_tensor(sat_dit_plan* p, const std::string& name, int64_t numel, const float** out) { return p->tensors.get("dit", name, numel, out); }
 
 int copy_f32(sat_dit_plan* p, Bump& ar, const std::string& name, int64_t numel, float** dst, hipStream_t s) {
-    *dst = (float*)ar.take(numel * 4);
-    return ar.dry() ? 0 : p->tensors.copy("dit", name, numel, *dst, s);
+    return p->tensors.place("dit", ar, name, numel, dst, s);
 }
 
-int pack_w(sat_dit_plan* p, Bump& ar, const std::string& name, int n, int k, int interleave, op_t** dst, hipStream_t s) {
-    *dst = (op_t*)ar.take((size_t)n * k * 2);
+// How the Linear of `family` in layer `l` runs.  e4m3 by the plan's families (to_kv has no e4m3 form: once per generation); the fold for the
+// LayerNorm-fed ones, except layer 0's to_qkv: its pre_norm reads rows written by the input projection, not by a GEMM epilogue
+ProjKind proj_kind(const sat_dit_plan* p, ProjFamily family, int l) {
+    static const int fp8_bit[] = {SAT_FP8_QKV, SAT_FP8_TO_OUT, SAT_FP8_CROSS_Q, 0, SAT_FP8_TO_OUT, SAT_FP8_FF_IN, SAT_FP8_FF_OUT};
+    const bool ln_fed = family == FAM_QKV || family == FAM_CQ || family == FAM_FF1;
+    if (p->cfg.gemm_dtype == 2) return PROJ_F32;
+    if (p->fp8_families & fp8_bit[family]) return ln_fed ? PROJ_FP8_ROW : PROJ_FP8_MX;
+    return p->ln_fold && ln_fed && !(family == FAM_QKV && l == 0) ? PROJ_LN_FOLD : PROJ_PLAIN;
+}
+
+// Tensors `pf + weight` [n, k] and, where `bias` is given, `pf + bias` [n] into the arena in the form of the projection's kind.  interleave: the
+// SwiGLU row order of the FF-in epilogue (weight rows, bias, c1 / c2; the fp32 mode keeps the reference's order).  gamma / beta: the LayerNorm
+// in front, read under the fold
+int pack_proj(sat_dit_plan* p, Bump& ar, const std::string& pf, const char* weight, const char* bias, ProjFamily family, int l, int n, int k,
+              int interleave, const float* gamma, const float* beta, Proj* out, hipStream_t s) {
+    Proj& r = *out;
+    r = Proj{};
+    r.n = n; r.k = k; r.kind = proj_kind(p, family, l);
+    const bool fp8 = r.kind == PROJ_FP8_ROW || r.kind == PROJ_FP8_MX;
+    r.w = (op_t*)ar.take((size_t)n * k * (r.kind == PROJ_F32 ? 4 : fp8 ? 1 : 2));
+    if (fp8) r.scale = (float*)ar.take((size_t)n * 4);
+    if (r.kind == PROJ_LN_FOLD) {
+        r.c1 = (float*)ar.take((size_t)n * 4);
+        r.c2 = (float*)ar.take((size_t)n * 4);
+    }
+    if (bias) r.bias = (float*)ar.take((size_t)n * 4);
     if (ar.dry()) return 0;
-    const float* src;
-    SAT_TRY(get_tensor(p, name, (int64_t)n * k, &src));
-    return sat_launch_pack_rows_bf16(src, *dst, n, k, interleave, s, p->f16);
-}
-
-// LayerNorm fold: bf16(gamma (.) W) + the two correction vectors of GemmArgs::ln_c1 / ln_c2 (bias folded into c2)
-int pack_w_ln(sat_dit_plan* p, Bump& ar, const std::string& name, const float* gamma, const float* beta, const std::string& bias_name, int n,
-              int k, int interleave, op_t** dst, float** c1, float** c2, hipStream_t s) {
-    *dst = (op_t*)ar.take((size_t)n * k * 2);
-    *c1 = (float*)ar.take((size_t)n * 4);
-    *c2 = (float*)ar.take((size_t)n * 4);
-    if (ar.dry()) return 0;
-    const float *src, *bias = nullptr;
-    SAT_TRY(get_tensor(p, name, (int64_t)n * k, &src));
-    if (!bias_name.empty()) SAT_TRY(get_tensor(p, bias_name, n, &bias));
-    return sat_launch_pack_rows_ln(src, gamma, beta, bias, *dst, *c1, *c2, n, k, interleave, s, p->f16);
-}
-
-// gemm_dtype: e4m3 bytes + one scale per output channel instead of bf16
-int pack_w8(sat_dit_plan* p, Bump& ar, const std::string& name, int n, int k, int interleave, op_t** dst, float** scale,
-            hipStream_t s) {
-    *dst = (op_t*)ar.take((size_t)n * k);
-    *scale = (float*)ar.take((size_t)n * 4);
-    if (ar.dry()) return 0;
-    const float* src;
-    SAT_TRY(get_tensor(p, name, (int64_t)n * k, &src));
-    return sat_launch_quant_rows_fp8(src, *dst, *scale, n, k, interleave, s);
-}
-
-// ff_kwargs no_bias (transformer.py:270): the output Linear of the feed-forward has no bias tensor; FF-out then runs without one
-int copy_ff2_bias(sat_dit_plan* p, Bump& ar, const std::string& pf, int D, float** dst, hipStream_t s) {
-    *dst = nullptr;
-    if (p->tensors.m.find(pf + "ff.ff.2.bias") == p->tensors.m.end()) return 0;
-    return copy_f32(p, ar, pf + "ff.ff.2.bias", D, dst, s);
+    const float *src, *b = nullptr;
+    SAT_TRY(get_tensor(p, pf + weight, (int64_t)n * k, &src));
+    if (bias) SAT_TRY(get_tensor(p, pf + bias, n, &b));
+    if (r.kind == PROJ_F32) SAT_HIP(hipMemcpyAsync(r.w, src, (size_t)n * k * 4, hipMemcpyDeviceToDevice, s));
+    else if (fp8) SAT_TRY(sat_launch_quant_rows_fp8(src, r.w, r.scale, n, k, interleave, s));
+    else if (r.kind == PROJ_LN_FOLD) SAT_TRY(sat_launch_pack_rows_ln(src, gamma, beta, b, r.w, r.c1, r.c2, n, k, interleave, s, p->f16));
+    else SAT_TRY(sat_launch_pack_rows_bf16(src, r.w, n, k, interleave, s, p->f16));
+    if (!bias) return 0;
+    if (interleave && r.kind != PROJ_F32) return sat_launch_pack_bias(b, r.bias, n, interleave, s);
+    SAT_HIP(hipMemcpyAsync(r.bias, b, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
 }
 
 int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
@@ -200,6 +210,9 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
     for (int l = 0; l < c.depth; ++l) {
         LayerW& L = p->layers[l];
         const std::string pf = "transformer.layers." + std::to_string(l) + ".";
+        auto pack = [&](const char* weight, const char* bias, ProjFamily family, int n, int k, int interleave, const float* gamma, const float* beta, Proj* out) {
+            return pack_proj(p, ar, pf, weight, bias, family, l, n, k, interleave, gamma, beta, out, s);
+        };
         if (c.adaln && !ar.dry()) {   // transformer.py:651-655: Sequential(SiLU, Linear(D, 6D, bias=False)) -> key "...1.weight"
             SAT_TRY(p->tensors.copy("dit", pf + "to_scale_shift_gate.1.weight", (int64_t)6 * D * D, p->ssg_w + (size_t)l * 6 * D * D, s));
         }
@@ -207,53 +220,18 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         SAT_TRY(copy_f32(p, ar, pf + "pre_norm.beta", D, &L.pre_b, s));
         SAT_TRY(copy_f32(p, ar, pf + "ff_norm.gamma", D, &L.ff_g, s));
         SAT_TRY(copy_f32(p, ar, pf + "ff_norm.beta", D, &L.ff_b, s));
-        if (c.gemm_dtype == 2) {      // fp32 verification mode: the reference's own fp32 weights, no re-packing (f32_ref.hip)
-            auto w32 = [&](const std::string& name, int64_t numel, op_t** dst) { return copy_f32(p, ar, pf + name, numel, (float**)dst, s); };
-            SAT_TRY(w32("self_attn.to_qkv.weight", (int64_t)3 * D * D, &L.w_qkv));
-            SAT_TRY(w32("self_attn.to_out.weight", (int64_t)D * D, &L.w_o));
-            if (Dct > 0) {
-                SAT_TRY(copy_f32(p, ar, pf + "cross_attend_norm.gamma", D, &L.cross_g, s));
-                SAT_TRY(copy_f32(p, ar, pf + "cross_attend_norm.beta", D, &L.cross_b, s));
-                SAT_TRY(w32("cross_attn.to_q.weight", (int64_t)D * D, &L.w_cq));
-                SAT_TRY(w32("cross_attn.to_kv.weight", (int64_t)2 * Dc * Dc, &L.w_ckv));
-                SAT_TRY(w32("cross_attn.to_out.weight", (int64_t)D * D, &L.w_co));
-            }
-            SAT_TRY(w32("ff.ff.0.proj.weight", (int64_t)2 * inner * D, &L.w_ff1));
-            SAT_TRY(copy_f32(p, ar, pf + "ff.ff.0.proj.bias", 2 * inner, &L.b_ff1, s));
-            SAT_TRY(w32("ff.ff.2.weight", (int64_t)D * inner, &L.w_ff2));
-            SAT_TRY(copy_ff2_bias(p, ar, pf, D, &L.b_ff2, s));
-            continue;
-        }
-        const bool lf = p->ln_fold;
-        L.fold_qkv = lf && l > 0;
-        if (p->f8_qkv) SAT_TRY(pack_w8(p, ar, pf + "self_attn.to_qkv.weight", 3 * D, D, 0, &L.w_qkv, &L.s_qkv, s));
-        else if (L.fold_qkv) SAT_TRY(pack_w_ln(p, ar, pf + "self_attn.to_qkv.weight", L.pre_g, L.pre_b, "", 3 * D, D, 0, &L.w_qkv, &L.c1_qkv, &L.c2_qkv, s));
-        else SAT_TRY(pack_w(p, ar, pf + "self_attn.to_qkv.weight", 3 * D, D, 0, &L.w_qkv, s));
-        if (p->f8_o) SAT_TRY(pack_w8(p, ar, pf + "self_attn.to_out.weight", D, D, 0, &L.w_o, &L.s_o, s));
-        else SAT_TRY(pack_w(p, ar, pf + "self_attn.to_out.weight", D, D, 0, &L.w_o, s));
+        SAT_TRY(pack("self_attn.to_qkv.weight", nullptr, FAM_QKV, 3 * D, D, 0, L.pre_g, L.pre_b, &L.qkv));
+        SAT_TRY(pack("self_attn.to_out.weight", nullptr, FAM_O, D, D, 0, nullptr, nullptr, &L.o));
         if (Dct > 0) {
             SAT_TRY(copy_f32(p, ar, pf + "cross_attend_norm.gamma", D, &L.cross_g, s));
             SAT_TRY(copy_f32(p, ar, pf + "cross_attend_norm.beta", D, &L.cross_b, s));
-            if (p->f8_cq) SAT_TRY(pack_w8(p, ar, pf + "cross_attn.to_q.weight", D, D, 0, &L.w_cq, &L.s_cq, s));
-            else if (lf) SAT_TRY(pack_w_ln(p, ar, pf + "cross_attn.to_q.weight", L.cross_g, L.cross_b, "", D, D, 0, &L.w_cq, &L.c1_cq, &L.c2_cq, s));
-            else SAT_TRY(pack_w(p, ar, pf + "cross_attn.to_q.weight", D, D, 0, &L.w_cq, s));
-            SAT_TRY(pack_w(p, ar, pf + "cross_attn.to_kv.weight", 2 * Dc, Dc, 0, &L.w_ckv, s));
-            if (p->f8_o) SAT_TRY(pack_w8(p, ar, pf + "cross_attn.to_out.weight", D, D, 0, &L.w_co, &L.s_co, s));
-            else SAT_TRY(pack_w(p, ar, pf + "cross_attn.to_out.weight", D, D, 0, &L.w_co, s));
+            SAT_TRY(pack("cross_attn.to_q.weight", nullptr, FAM_CQ, D, D, 0, L.cross_g, L.cross_b, &L.cq));
+            SAT_TRY(pack("cross_attn.to_kv.weight", nullptr, FAM_CKV, 2 * Dc, Dc, 0, nullptr, nullptr, &L.ckv));
+            SAT_TRY(pack("cross_attn.to_out.weight", nullptr, FAM_CO, D, D, 0, nullptr, nullptr, &L.co));
         }
-        if (p->f8_ff1) SAT_TRY(pack_w8(p, ar, pf + "ff.ff.0.proj.weight", 2 * inner, D, 1, &L.w_ff1, &L.s_ff1, s));
-        else if (lf) SAT_TRY(pack_w_ln(p, ar, pf + "ff.ff.0.proj.weight", L.ff_g, L.ff_b, pf + "ff.ff.0.proj.bias", 2 * inner, D, 1, &L.w_ff1, &L.c1_ff1,
-                                       &L.c2_ff1, s));
-        else SAT_TRY(pack_w(p, ar, pf + "ff.ff.0.proj.weight", 2 * inner, D, 1, &L.w_ff1, s));
-        L.b_ff1 = (float*)ar.take((size_t)2 * inner * 4);
-        if (!ar.dry()) {
-            const float* b1;
-            SAT_TRY(get_tensor(p, pf + "ff.ff.0.proj.bias", 2 * inner, &b1));
-            SAT_TRY(sat_launch_pack_bias(b1, L.b_ff1, 2 * inner, 1, s));
-        }
-        if (p->f8_ff2) SAT_TRY(pack_w8(p, ar, pf + "ff.ff.2.weight", D, inner, 0, &L.w_ff2, &L.s_ff2, s));
-        else SAT_TRY(pack_w(p, ar, pf + "ff.ff.2.weight", D, inner, 0, &L.w_ff2, s));
-        SAT_TRY(copy_ff2_bias(p, ar, pf, D, &L.b_ff2, s));
+        SAT_TRY(pack("ff.ff.0.proj.weight", "ff.ff.0.proj.bias", FAM_FF1, 2 * inner, D, 1, L.ff_g, L.ff_b, &L.ff1));
+        // ff_kwargs no_bias (transformer.py:270): the output Linear of the feed-forward has no bias tensor; FF-out then runs without one
+        SAT_TRY(pack("ff.ff.2.weight", p->tensors.has(pf + "ff.ff.2.bias") ? "ff.ff.2.bias" : nullptr, FAM_FF2, D, inner, 0, nullptr, nullptr, &L.ff2));
     }
     return 0;
 }
@@ -326,6 +304,148 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     return w;
 }
 
+// One forward's constants and the launches of one block on them (transformer.py:656-702)
+struct Forward {
+    sat_dit_plan* p;
+    Workspace w;
+    hipStream_t s;
+    int bf, S, M, Spad, D, H;
+    int bc, Mc;           // cross-attention runs on the first bc sequences (Mc rows): see block()
+    int ssg_ld;           // per-sequence stride of the adaLN modulation vectors
+
+    const float* mod(int l) const { return p->cfg.adaln ? w.ssg + (size_t)l * 6 * D : nullptr; }      // + {0..5} * D: scale1p / shift / gate of self, then of ff
+
+    // The GemmArgs fields that follow from the projection's kind; the launch site adds what its epilogue needs
+    GemmArgs gemm(const Proj& r, const op_t* A, int rows) const {
+        GemmArgs g{};
+        g.f16 = p->f16; g.variant = p->tile_bits;
+        g.A = A; g.W = r.w; g.M = rows; g.N = r.n; g.K = r.k;
+        g.bias = r.kind == PROJ_LN_FOLD ? nullptr : r.bias;          // the fold has it in c2
+        if (r.kind == PROJ_LN_FOLD) { g.ln_part = w.ln_part; g.ln_c1 = r.c1; g.ln_c2 = r.c2; g.ln_eps = 1e-5f; }
+        if (r.kind == PROJ_FP8_ROW) { g.fp8 = p->fp8_mode; g.a_scale = w.As; g.w_scale = r.scale; }
+        // MXFP8 A: the E8M0 scales its producer wrote beside it (attention kernels: AOs, FF-in epilogue: Hs)
+        if (r.kind == PROJ_FP8_MX) { g.fp8 = 3; g.a_bscale = (const unsigned*)(A == w.AO ? w.AOs : w.Hs); g.w_scale = r.scale; }
+        return g;
+    }
+
+    // The standalone LayerNorm of X into A in front of a projection: quantising for e4m3 operands, none under the fold (from the first to_out
+    // on, A holds the 16-bit image of X and ln_part its row statistics, both written by the epilogue of the GEMM that last updated X; the
+    // LayerNorms of transformer.py:692, 695, 700 are finished in the epilogues of their consumers).  modulated: the adaLN form (sc / sh may be null)
+    int layernorm(const Proj& r, const float* gamma, const float* beta, int rows, bool modulated, const float* sc, const float* sh) const {
+        if (r.kind == PROJ_LN_FOLD) return 0;
+        if (r.kind == PROJ_FP8_ROW)
+            return sat_launch_layernorm_fp8(w.X, gamma, beta, w.A, w.As, rows, D, sc, sh, modulated ? S : 1, modulated ? ssg_ld : 0, s);
+        if (modulated) return sat_launch_layernorm_mod(w.X, gamma, beta, w.A, rows, D, sc, sh, S, ssg_ld, s, p->f16);
+        return sat_launch_layernorm(w.X, gamma, beta, w.A, rows, D, s, p->f16);
+    }
+
+    // X += [gate (.)] (A W^T + bias), update `slot` (0 self-attention, 1 cross-attention, 2 feed-forward) of block l.  feeds_ln: a LayerNorm reads
+    // the new rows, so under the fold the epilogue also writes their 16-bit image and statistics
+    int resid(const Proj& r, const op_t* A, int rows, const float* gate, bool feeds_ln, int l, int slot) const {
+        GemmArgs g = gemm(r, A, rows);
+        g.C = w.X; g.ldc = D; g.accumulate = 1;
+        if (gate) { g.gate = gate; g.gate_rows = S; g.gate_ld = ssg_ld; }
+        if (slot == 2) { g.slab = w.slab; g.slab_bytes = w.slab_bytes; }          // FF-out: the one reduction long enough to split (carve)
+        if (feeds_ln && p->ln_fold) { g.xb = w.A; g.ln_part_out = w.ln_part; }
+        SAT_TRY(sat_launch_gemm(EPI_RESID, g, s));
+        return p->dbg ? glue_resid_stats(w.X, rows, D, p->dbg + ((size_t)l * 3 + slot) * 4, s) : 0;
+    }
+
+    int block(int l) const;
+    int block_f32(int l) const;
+};
+
+// fp32 verification mode: the same block on f32_ref.hip, fp32 everywhere
+int Forward::block_f32(int l) const {
+    const LayerW& L = p->layers[l];
+    const float* m = mod(l);
+    const int inner = p->inner;
+    float *A32 = (float*)w.A, *AO32 = (float*)w.AO, *Q32 = (float*)w.Q, *K32 = (float*)w.K, *V32 = (float*)w.Vt, *H32 = (float*)w.Hh;
+    auto W32 = [](const Proj& r) { return (const float*)r.w; };
+    SAT_TRY(sat_launch_layernorm_f32(w.X, L.pre_g, L.pre_b, A32, M, D, m, m ? m + D : nullptr, S, ssg_ld, s));
+    SAT_TRY(sat_launch_gemm_f32(A32, W32(L.qkv), nullptr, w.f32_wide, M, 3 * D, D, 3 * D, 0, nullptr, 1, 0, s));
+    SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
+    SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
+    SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.o), nullptr, w.X, M, D, D, D, 1, m ? m + 2 * D : nullptr, S, ssg_ld, s));
+    if (bc > 0) {
+        SAT_TRY(sat_launch_layernorm_f32(w.X, L.cross_g, L.cross_b, A32, Mc, D, nullptr, nullptr, 1, 0, s));
+        SAT_TRY(sat_launch_gemm_f32(A32, W32(L.cq), nullptr, w.f32_wide, Mc, D, D, D, 0, nullptr, 1, 0, s));
+        SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
+        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lc * 64;
+        SAT_TRY(sat_launch_attention_f32(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, S, p->ctx_lc, s));
+        SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.co), nullptr, w.X, Mc, D, D, D, 1, nullptr, 1, 0, s));
+    }
+    SAT_TRY(sat_launch_layernorm_f32(w.X, L.ff_g, L.ff_b, A32, M, D, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr, S, ssg_ld, s));
+    SAT_TRY(sat_launch_gemm_f32(A32, W32(L.ff1), L.ff1.bias, w.f32_wide, M, 2 * inner, D, 2 * inner, 0, nullptr, 1, 0, s));
+    SAT_TRY(sat_launch_swiglu_f32(w.f32_wide, H32, M, inner, s));
+    return sat_launch_gemm_f32(H32, W32(L.ff2), L.ff2.bias, w.X, M, D, inner, D, 1, m ? m + 5 * D : nullptr, S, ssg_ld, s);
+}
+
+int Forward::block(int l) const {
+    const LayerW& L = p->layers[l];
+    const float* m = mod(l);
+    const int f16 = p->f16, qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
+    auto mx_scales = [&](const Proj& out) { return out.kind == PROJ_FP8_MX ? w.AOs : nullptr; };      // the attention kernels write to_out's MXFP8 operand
+    // ---- self-attention branch (transformer.py:692)
+    SAT_TRY(layernorm(L.qkv, L.pre_g, L.pre_b, M, true, m, m ? m + D : nullptr));
+    GemmArgs g = gemm(L.qkv, w.A, M);
+    g.heads.out[0] = w.Q; g.heads.out[1] = w.K; g.heads.out[2] = w.Vt;
+    g.heads.kind[0] = 2 | 8 | qn; g.heads.kind[1] = 2 | 4 | qn; g.heads.kind[2] = 1 | 4; g.heads.qscale = SAT_ATTN_QSCALE;
+    g.heads.parts = 3; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
+    g.heads.rope_cos = p->rope_cos; g.heads.rope_sin = p->rope_sin;
+    SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
+    SAT_TRY(sat_launch_attention(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, mx_scales(L.o), 1.0f, f16));
+    SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
+    // ---- cross-attention branch (transformer.py:694-695).  Sequences whose context is all-zero (the
+    // unconditional CFG half, dit.py:294-300) get k = v = 0 from the bias-free to_cond_embed / to_kv, hence an
+    // attention output of exactly 0 and, through the bias-free to_out, a branch contribution of exactly 0:
+    // the branch runs only on the first `bc` sequences (rows are ordered by sequence).
+    if (bc > 0) {
+        SAT_TRY(layernorm(L.cq, L.cross_g, L.cross_b, Mc, false, nullptr, nullptr));
+        g = gemm(L.cq, w.A, Mc);
+        g.heads.out[0] = w.Q; g.heads.kind[0] = 8 | qn; g.heads.qscale = SAT_ATTN_QSCALE;
+        g.heads.parts = 1; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
+        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * 64;
+        // One launch for to_q + softmax(q k^T) v where the 128 x 64 tile is the choice anyway and its workgroups fit one round
+        // (one prompt: 9 x 24 = 216): the projection's epilogue keeps Q in registers and attends to the <= 189 context keys
+        // staged in LDS (gemm_bf16.hip, XA_OK).  Saves the attention launch and the Q round trip.  16-bit operands only.
+        const bool fuse = p->cross_fusion && L.cq.kind != PROJ_FP8_ROW && L.co.kind != PROJ_FP8_MX && D >= 192 && p->ctx_lc + 3 <= 192 &&
+                          cdiv(Mc, 128) * (D / 64) <= 256;
+        if (fuse) {
+            g.heads.xa_k = p->kc + l * per_layer; g.heads.xa_vt = p->vct + l * per_layer; g.heads.xa_out = w.AO;
+            g.heads.xa_kvh = p->kvh_cross; g.heads.xa_sk = p->ctx_lc; g.heads.xa_sk_pad = p->ctx_lcpad;
+        }
+        SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
+        if (!fuse)
+            SAT_TRY(sat_launch_attention(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, w.AO, bc, H, p->kvh_cross, S, p->ctx_lc, Spad,
+                                         p->ctx_lcpad, s, mx_scales(L.co), 1.0f, f16));
+        SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
+    }
+    // ---- feed-forward branch (transformer.py:700)
+    SAT_TRY(layernorm(L.ff1, L.ff_g, L.ff_b, M, true, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr));
+    g = gemm(L.ff1, w.A, M);
+    g.H = w.Hh;
+    if (L.ff2.kind == PROJ_FP8_MX) { g.H8 = (unsigned char*)w.Hh; g.Hs = w.Hs; }          // FF-out's MXFP8 operand; otherwise the e4m3 GEMM writes a 16-bit hidden state
+    const bool prof = p->prof_on && l == p->cfg.depth / 2 && p->prof_n < kProfMaxPairs;
+    if (prof) {
+        if ((int)p->prof_ev.size() < 2 * (p->prof_n + 1)) {
+            hipEvent_t e0, e1;
+            SAT_HIP(hipEventCreate(&e0));
+            SAT_HIP(hipEventCreate(&e1));
+            p->prof_ev.push_back(e0);
+            p->prof_ev.push_back(e1);
+        }
+        SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n], s));
+    }
+    SAT_TRY(sat_launch_gemm(EPI_SWIGLU, g, s));
+    if (prof) {
+        SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n + 1], s));
+        p->prof_n++;
+        p->prof_m = g.M; p->prof_nn = g.N; p->prof_k = g.K;
+    }
+    return resid(L.ff2, w.Hh, M, m ? m + 5 * D : nullptr, l + 1 < p->cfg.depth, l, 2);      // nobody normalises the output of the last block
+}
+
 int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const float* t_dev, float t_const, float* out, int bf,
                 int T, void* ws, size_t ws_bytes, hipStream_t s) {
     SAT_CHECK_ARG(p && p->finalized, SAT_E_STATE, "dit forward: plan not finalized");
@@ -343,14 +463,12 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     SAT_CHECK_ARG(ws_bytes >= w.total, SAT_E_WORKSPACE, "dit forward: workspace %zu < required %zu", ws_bytes, w.total);
     const int D = c.embed_dim, H = c.num_heads, C = c.io_channels;
     const bool adaln = c.adaln != 0, f32 = c.gemm_dtype == 2;
-    const int f16 = p->f16;
     const int S = seq_len(p, T, P), M = bf * S, Spad = (int)round_up(S + 3, 128);
     const int ssg_ld = c.depth * 6 * D;      // per-sequence stride of the adaLN modulation vectors
     // transformer.py:59-61, before anything is launched
     SAT_CHECK_ARG(p->pos_emb != SAT_DIT_POS_ABSOLUTE || S <= p->abs_max, SAT_E_INVALID,
                   "dit forward: you are passing in a sequence length of %d but your absolute positional embedding has a max sequence length of %d", S,
                   p->abs_max);
-    const int qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
 
     // pads of q/k/vt must be finite (zero): one memset per forward
     if (!f32) SAT_HIP(hipMemsetAsync(w.Q, 0, 3 * (size_t)round_up((int64_t)w.qkv_bytes, 256), s));
@@ -378,141 +496,10 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     if (p->pos_table) SAT_TRY(glue_add_pos(w.X, p->pos_table, bf, S, D, s));
 
     if (p->dbg) SAT_HIP(hipMemsetAsync(p->dbg, 0, (size_t)c.depth * 3 * 4 * sizeof(float), s));
-    GemmArgs g{};
-    for (int l = 0; l < c.depth && f32; ++l) {
-        // fp32 verification mode: the same block (transformer.py:656-702) on f32_ref.hip, fp32 everywhere
-        const LayerW& L = p->layers[l];
-        const float* mod = adaln ? w.ssg + (size_t)l * 6 * D : nullptr;
-        float *A32 = (float*)w.A, *AO32 = (float*)w.AO, *Q32 = (float*)w.Q, *K32 = (float*)w.K, *V32 = (float*)w.Vt, *H32 = (float*)w.Hh;
-        SAT_TRY(sat_launch_layernorm_f32(w.X, L.pre_g, L.pre_b, A32, M, D, mod, mod ? mod + D : nullptr, S, ssg_ld, s));
-        SAT_TRY(sat_launch_gemm_f32(A32, (const float*)L.w_qkv, nullptr, w.f32_wide, M, 3 * D, D, 3 * D, 0, nullptr, 1, 0, s));
-        SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
-        SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
-        SAT_TRY(sat_launch_gemm_f32(AO32, (const float*)L.w_o, nullptr, w.X, M, D, D, D, 1, adaln ? mod + 2 * D : nullptr, S, ssg_ld, s));
-        if (cross) {
-            const int bc = (p->ctx_null_from >= 0 && p->ctx_null_from < bf) ? p->ctx_null_from : bf;
-            const int Mc = bc * S;
-            if (bc > 0) {
-                SAT_TRY(sat_launch_layernorm_f32(w.X, L.cross_g, L.cross_b, A32, Mc, D, nullptr, nullptr, 1, 0, s));
-                SAT_TRY(sat_launch_gemm_f32(A32, (const float*)L.w_cq, nullptr, w.f32_wide, Mc, D, D, D, 0, nullptr, 1, 0, s));
-                SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
-                const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lc * 64;
-                SAT_TRY(sat_launch_attention_f32(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, S, p->ctx_lc, s));
-                SAT_TRY(sat_launch_gemm_f32(AO32, (const float*)L.w_co, nullptr, w.X, Mc, D, D, D, 1, nullptr, 1, 0, s));
-            }
-        }
-        SAT_TRY(sat_launch_layernorm_f32(w.X, L.ff_g, L.ff_b, A32, M, D, mod ? mod + 3 * D : nullptr, mod ? mod + 4 * D : nullptr, S, ssg_ld, s));
-        SAT_TRY(sat_launch_gemm_f32(A32, (const float*)L.w_ff1, L.b_ff1, w.f32_wide, M, 2 * p->inner, D, 2 * p->inner, 0, nullptr, 1, 0, s));
-        SAT_TRY(sat_launch_swiglu_f32(w.f32_wide, H32, M, p->inner, s));
-        SAT_TRY(sat_launch_gemm_f32(H32, (const float*)L.w_ff2, L.b_ff2, w.X, M, D, p->inner, D, 1, adaln ? mod + 5 * D : nullptr, S, ssg_ld, s));
-    }
-    for (int l = 0; l < c.depth && !f32; ++l) {
-        const LayerW& L = p->layers[l];
-        // ---- self-attention branch (transformer.py:692)
-        const float* mod = adaln ? w.ssg + (size_t)l * 6 * D : nullptr;     // + {0..5} * D: scale1p/shift/gate self, then ff
-        // ln_fold: from the first to_out on, A holds bf16(X) and ln_part its row statistics, both written by the epilogue of the
-        // GEMM that last updated X; the LayerNorms (transformer.py:692, 695, 700) are finished in the epilogues of their consumers
-        const bool lf = p->ln_fold;
-        auto fold_in = [&](GemmArgs& ga, const float* c1, const float* c2) {
-            ga.ln_part = w.ln_part; ga.ln_c1 = c1; ga.ln_c2 = c2; ga.ln_eps = 1e-5f;
-        };
-        auto fold_out = [&](GemmArgs& ga) {
-            if (lf) { ga.xb = w.A; ga.ln_part_out = w.ln_part; }
-        };
-        if (p->f8_qkv) SAT_TRY(sat_launch_layernorm_fp8(w.X, L.pre_g, L.pre_b, w.A, w.As, M, D, mod, mod ? mod + D : nullptr, S, ssg_ld, s));
-        else if (!L.fold_qkv) SAT_TRY(sat_launch_layernorm_mod(w.X, L.pre_g, L.pre_b, w.A, M, D, mod, mod ? mod + D : nullptr, S, ssg_ld, s, f16));
-        g = GemmArgs{}; g.f16 = f16; g.variant = p->tile_bits;
-        g.A = w.A; g.W = L.w_qkv; g.M = M; g.N = 3 * D; g.K = D;
-        if (L.fold_qkv) fold_in(g, L.c1_qkv, L.c2_qkv);
-        if (p->f8_qkv) { g.fp8 = p->fp8_mode; g.a_scale = w.As; g.w_scale = L.s_qkv; }
-        g.heads.out[0] = w.Q; g.heads.out[1] = w.K; g.heads.out[2] = w.Vt;
-        g.heads.kind[0] = 2 | 8 | qn; g.heads.kind[1] = 2 | 4 | qn; g.heads.kind[2] = 1 | 4; g.heads.qscale = SAT_ATTN_QSCALE;
-        g.heads.parts = 3; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
-        g.heads.rope_cos = p->rope_cos; g.heads.rope_sin = p->rope_sin;
-        SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
-        SAT_TRY(sat_launch_attention(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, p->f8_o ? w.AOs : nullptr, 1.0f, f16));
-        g = GemmArgs{}; g.f16 = f16; g.variant = p->tile_bits;
-        g.A = w.AO; g.W = L.w_o; g.M = M; g.N = D; g.K = D; g.C = w.X; g.ldc = D; g.accumulate = 1;
-        if (p->f8_o) { g.fp8 = 3; g.a_bscale = (const unsigned*)w.AOs; g.w_scale = L.s_o; }
-        if (adaln) { g.gate = mod + 2 * D; g.gate_rows = S; g.gate_ld = ssg_ld; }
-        fold_out(g);
-        SAT_TRY(sat_launch_gemm(EPI_RESID, g, s));
-        if (p->dbg) SAT_TRY(glue_resid_stats(w.X, M, D, p->dbg + ((size_t)l * 3 + 0) * 4, s));
-        // ---- cross-attention branch (transformer.py:694-695).  Sequences whose context is all-zero (the
-        // unconditional CFG half, dit.py:294-300) get k = v = 0 from the bias-free to_cond_embed / to_kv, hence an
-        // attention output of exactly 0 and, through the bias-free to_out, a branch contribution of exactly 0:
-        // the branch runs only on the first `bc` sequences (rows are ordered by sequence).
-        if (cross) {
-            const int bc = (p->ctx_null_from >= 0 && p->ctx_null_from < bf) ? p->ctx_null_from : bf;
-            const int Mc = bc * S;
-            if (bc > 0) {
-                if (p->f8_cq) SAT_TRY(sat_launch_layernorm_fp8(w.X, L.cross_g, L.cross_b, w.A, w.As, Mc, D, nullptr, nullptr, 1, 0, s));
-                else if (!lf) SAT_TRY(sat_launch_layernorm(w.X, L.cross_g, L.cross_b, w.A, Mc, D, s, f16));
-                g = GemmArgs{}; g.f16 = f16; g.variant = p->tile_bits;
-                g.A = w.A; g.W = L.w_cq; g.M = Mc; g.N = D; g.K = D;
-                if (lf) fold_in(g, L.c1_cq, L.c2_cq);
-                if (p->f8_cq) { g.fp8 = p->fp8_mode; g.a_scale = w.As; g.w_scale = L.s_cq; }
-                g.heads.out[0] = w.Q; g.heads.kind[0] = 8 | qn; g.heads.qscale = SAT_ATTN_QSCALE;
-                g.heads.parts = 1; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
-                const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * 64;
-                // One launch for to_q + softmax(q k^T) v where the 128 x 64 tile is the choice anyway and its workgroups fit one round
-                // (one prompt: 9 x 24 = 216): the projection's epilogue keeps Q in registers and attends to the <= 189 context keys
-                // staged in LDS (gemm_bf16.hip, XA_OK).  Saves the attention launch and the Q round trip.
-                const bool fuse = p->cross_fusion && !p->f8_cq && !p->f8_o && D >= 192 && p->ctx_lc + 3 <= 192 && cdiv(Mc, 128) * (D / 64) <= 256;
-                if (fuse) {
-                    g.heads.xa_k = p->kc + l * per_layer; g.heads.xa_vt = p->vct + l * per_layer; g.heads.xa_out = w.AO;
-                    g.heads.xa_kvh = p->kvh_cross; g.heads.xa_sk = p->ctx_lc; g.heads.xa_sk_pad = p->ctx_lcpad;
-                }
-                SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
-                if (!fuse)
-                    SAT_TRY(sat_launch_attention(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, w.AO, bc, H, p->kvh_cross, S,
-                                                 p->ctx_lc, Spad, p->ctx_lcpad, s, p->f8_o ? w.AOs : nullptr, 1.0f, f16));
-                g = GemmArgs{}; g.f16 = f16; g.variant = p->tile_bits;
-                g.A = w.AO; g.W = L.w_co; g.M = Mc; g.N = D; g.K = D; g.C = w.X; g.ldc = D; g.accumulate = 1;
-                if (p->f8_o) { g.fp8 = 3; g.a_bscale = (const unsigned*)w.AOs; g.w_scale = L.s_co; }
-                fold_out(g);
-                SAT_TRY(sat_launch_gemm(EPI_RESID, g, s));
-                if (p->dbg) SAT_TRY(glue_resid_stats(w.X, Mc, D, p->dbg + ((size_t)l * 3 + 1) * 4, s));
-            }
-        }
-        // ---- feed-forward branch (transformer.py:700)
-        if (p->f8_ff1) SAT_TRY(sat_launch_layernorm_fp8(w.X, L.ff_g, L.ff_b, w.A, w.As, M, D, mod ? mod + 3 * D : nullptr, mod ? mod + 4 * D : nullptr,
-                                                       S, ssg_ld, s));
-        else if (!lf) SAT_TRY(sat_launch_layernorm_mod(w.X, L.ff_g, L.ff_b, w.A, M, D, mod ? mod + 3 * D : nullptr, mod ? mod + 4 * D : nullptr, S,
-                                                       ssg_ld, s, f16));
-        g = GemmArgs{}; g.f16 = f16; g.variant = p->tile_bits;
-        g.A = w.A; g.W = L.w_ff1; g.bias = L.b_ff1; g.M = M; g.N = 2 * p->inner; g.K = D; g.H = w.Hh;
-        if (lf) { g.bias = nullptr; fold_in(g, L.c1_ff1, L.c2_ff1); }
-        if (p->f8_ff1) {
-            g.fp8 = p->fp8_mode; g.a_scale = w.As; g.w_scale = L.s_ff1;
-            if (p->f8_ff2) { g.H8 = (unsigned char*)w.Hh; g.Hs = w.Hs; }          // FF-out's MXFP8 operand; otherwise the e4m3 GEMM writes a bf16 hidden state
-        }
-        const bool prof = p->prof_on && l == c.depth / 2 && p->prof_n < kProfMaxPairs;
-        if (prof) {
-            if ((int)p->prof_ev.size() < 2 * (p->prof_n + 1)) {
-                hipEvent_t e0, e1;
-                SAT_HIP(hipEventCreate(&e0));
-                SAT_HIP(hipEventCreate(&e1));
-                p->prof_ev.push_back(e0);
-                p->prof_ev.push_back(e1);
-            }
-            SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n], s));
-        }
-        SAT_TRY(sat_launch_gemm(EPI_SWIGLU, g, s));
-        if (prof) {
-            SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n + 1], s));
-            p->prof_n++;
-            p->prof_m = g.M; p->prof_nn = g.N; p->prof_k = g.K;
-        }
-        g = GemmArgs{}; g.f16 = f16; g.variant = p->tile_bits;
-        g.A = w.Hh; g.W = L.w_ff2; g.bias = L.b_ff2; g.M = M; g.N = D; g.K = p->inner; g.C = w.X; g.ldc = D; g.accumulate = 1;
-        if (p->f8_ff2) { g.fp8 = 3; g.a_bscale = (const unsigned*)w.Hs; g.w_scale = L.s_ff2; }
-        if (adaln) { g.gate = mod + 5 * D; g.gate_rows = S; g.gate_ld = ssg_ld; }
-        g.slab = w.slab; g.slab_bytes = w.slab_bytes;
-        if (l + 1 < c.depth) fold_out(g);       // nobody normalises the output of the last block
-        SAT_TRY(sat_launch_gemm(EPI_RESID, g, s));
-        if (p->dbg) SAT_TRY(glue_resid_stats(w.X, M, D, p->dbg + ((size_t)l * 3 + 2) * 4, s));
-    }
+    // cross-attention: not on the sequences behind ctx_null_from (Forward::block)
+    const int bc = !cross ? 0 : (p->ctx_null_from >= 0 && p->ctx_null_from < bf) ? p->ctx_null_from : bf;
+    const Forward f{p, w, s, bf, S, M, Spad, D, H, bc, bc * S, ssg_ld};
+    for (int l = 0; l < c.depth; ++l) SAT_TRY(f32 ? f.block_f32(l) : f.block(l));
     // project_out + drop prepend + postprocess_conv + residual (transformer.py:807, dit.py:219-224)
     SAT_TRY(glue_output_proj(w.X, p->wout_eff, out, bf, C, T, S, D, s));
     return 0;
@@ -571,10 +558,7 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
     // the fold lives in the bf16 pipelined GEMM tiles (K >= 192); adaLN modulates between LayerNorm and GEMM per sequence, the e4m3
     // path quantises the LayerNorm output per token: both keep the standalone kernels
     p->f16 = cfg->gemm_dtype == 3 ? 1 : 0;
-    if (cfg->gemm_dtype == 1) {
-        p->f8_qkv = fam & SAT_FP8_QKV; p->f8_cq = fam & SAT_FP8_CROSS_Q; p->f8_ff1 = fam & SAT_FP8_FF_IN; p->f8_ff2 = fam & SAT_FP8_FF_OUT;
-        p->f8_o = fam & SAT_FP8_TO_OUT;
-    }
+    p->fp8_families = cfg->gemm_dtype == 1 ? fam : 0;
     p->cross_fusion = cfg->cross_attention == 0;
     p->tile_bits = sat_tile_policy_bits(cfg->tile_policy);
     p->ln_fold = cfg->ln_fold != 0 && (cfg->gemm_dtype == 0 || cfg->gemm_dtype == 3) && !cfg->adaln && cfg->embed_dim >= 256;
@@ -597,10 +581,10 @@ extern "C" int sat_dit_plan_finalize(sat_dit_plan* p, sat_stream_t stream) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "dit_plan_finalize: null plan");
     hipStream_t s = (hipStream_t)stream;
     const int D = p->cfg.embed_dim;
-    auto it = p->tensors.m.find("transformer.layers.0.ff.ff.0.proj.weight");
-    SAT_CHECK_ARG(it != p->tensors.m.end(), SAT_E_MISSING, "dit plan: tensor 'transformer.layers.0.ff.ff.0.proj.weight' was never set");
-    SAT_CHECK_ARG(it->second.second % (2 * (int64_t)D) == 0, SAT_E_INVALID, "dit plan: FF weight size not divisible by 2*embed_dim");
-    p->inner = (int)(it->second.second / (2 * (int64_t)D));
+    const int64_t ff_numel = p->tensors.numel("transformer.layers.0.ff.ff.0.proj.weight");
+    SAT_CHECK_ARG(ff_numel > 0, SAT_E_MISSING, "dit plan: tensor 'transformer.layers.0.ff.ff.0.proj.weight' was never set");
+    SAT_CHECK_ARG(ff_numel % (2 * (int64_t)D) == 0, SAT_E_INVALID, "dit plan: FF weight size not divisible by 2*embed_dim");
+    p->inner = (int)(ff_numel / (2 * (int64_t)D));
     SAT_CHECK_ARG(p->inner % 64 == 0, SAT_E_UNSUPPORTED, "dit plan: FF inner dim %d must be a multiple of 64", p->inner);
     SAT_CHECK_ARG(p->cfg.gemm_dtype != 1 || p->inner % 128 == 0, SAT_E_UNSUPPORTED, "dit plan: gemm_dtype needs an FF inner dim that is a multiple of 128");
     p->wsq_bf = p->wsq_t = -1;
@@ -673,7 +657,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
         SAT_TRY(glue_small_linear(ch, Dc, p->ce2_w, nullptr, nullptr, 0, ce32, Dc, R, Dc, Dc, 0, 0, s));
         const size_t per_layer = (size_t)bf * p->kvh_cross * lc * 64;
         for (int l = 0; l < c.depth; ++l) {
-            SAT_TRY(sat_launch_gemm_f32(ce32, (const float*)p->layers[l].w_ckv, nullptr, kv32, R, 2 * Dc, Dc, 2 * Dc, 0, nullptr, 1, 0, s));
+            SAT_TRY(sat_launch_gemm_f32(ce32, (const float*)p->layers[l].ckv.w, nullptr, kv32, R, 2 * Dc, Dc, 2 * Dc, 0, nullptr, 1, 0, s));
             SAT_TRY(sat_launch_split_heads_f32(kv32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, nullptr, R, lc, 2, p->kvh_cross, 0, nullptr,
                                                nullptr, s, p->qk_norm ? 1 : 0));
         }
@@ -688,7 +672,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
         for (int l = 0; l < c.depth; ++l) {
             GemmArgs g{};
             g.f16 = p->f16;
-            g.A = ce; g.W = p->layers[l].w_ckv; g.M = R; g.N = 2 * Dc; g.K = Dc;
+            g.A = ce; g.W = p->layers[l].ckv.w; g.M = R; g.N = 2 * Dc; g.K = Dc;
             g.heads.out[0] = p->kc + l * per_layer; g.heads.out[1] = p->vct + l * per_layer;
             g.heads.kind[0] = 4 | (p->qk_norm ? 16 : 0); g.heads.kind[1] = 1 | 4; g.heads.parts = 2; g.heads.heads = p->kvh_cross;
             g.heads.S = lc; g.heads.Spad = lcpad;

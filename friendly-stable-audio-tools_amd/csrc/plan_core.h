@@ -57,6 +57,10 @@ struct TensorTable {
         return 0;
     }
     bool has(const std::string& name) const { return m.count(name) != 0; }
+    int64_t numel(const std::string& name) const {          // 0: never set
+        auto it = m.find(name);
+        return it == m.end() ? 0 : it->second.second;
+    }
     // first_rows: the first `numel` elements of a table of whole rows of `numel` (RoBERTa's token-type table)
     int get(const char* what, const std::string& name, int64_t numel, const float** out, bool first_rows = false) const {
         auto it = m.find(name);
@@ -73,6 +77,11 @@ struct TensorTable {
         SAT_TRY(get(what, name, numel, &src, first_rows));
         SAT_HIP(hipMemcpyAsync(dst, src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
         return 0;
+    }
+    // finalize, both passes: the named tensor takes the arena's next `numel` floats; copied there unless the pass only counts
+    int place(const char* what, Bump& ar, const std::string& name, int64_t numel, float** dst, hipStream_t s, bool first_rows = false) const {
+        *dst = (float*)ar.take((size_t)numel * 4);
+        return ar.dry() ? 0 : copy(what, name, numel, *dst, s, first_rows);
     }
     void clear() { m.clear(); }
 };

@@ -132,12 +132,11 @@ int roberta_build(sat_roberta_plan* p, Bump& ar, hipStream_t s) {
     const sat_roberta_cfg& c = p->cfg;
     const int64_t D = c.hidden_size, F = c.intermediate_size;
     // the named tensor as part `part` of a buffer of equal parts stacked behind each other
-    auto fill = [&](const std::string& name, int64_t numel, float* dst, int part = 0, bool first_rows = false) -> int {
-        return ar.dry() ? 0 : p->tensors.copy("roberta", name, numel, dst + part * numel, s, first_rows);
+    auto fill = [&](const std::string& name, int64_t numel, float* dst, int part) -> int {
+        return ar.dry() ? 0 : p->tensors.copy("roberta", name, numel, dst + part * numel, s);
     };
     auto place = [&](const std::string& name, int64_t numel, float** dst, bool first_rows = false) -> int {
-        *dst = (float*)ar.take((size_t)numel * 4);
-        return fill(name, numel, *dst, 0, first_rows);
+        return p->tensors.place("roberta", ar, name, numel, dst, s, first_rows);
     };
     SAT_TRY(place("embeddings.word_embeddings.weight", (int64_t)c.vocab_size * D, &p->word));
     SAT_TRY(place("embeddings.position_embeddings.weight", (int64_t)c.max_positions * D, &p->posw));

@@ -156,10 +156,7 @@ int t5_build(sat_t5_plan* p, Bump& ar, hipStream_t s) {
     auto fill = [&](const std::string& name, int64_t numel, float* dst, int part = 0) -> int {
         return ar.dry() ? 0 : p->tensors.copy("t5", name, numel, dst + part * numel, s);
     };
-    auto place = [&](const std::string& name, int64_t numel, float** dst) -> int {
-        *dst = (float*)ar.take((size_t)numel * 4);
-        return fill(name, numel, *dst);
-    };
+    auto place = [&](const std::string& name, int64_t numel, float** dst) -> int { return p->tensors.place("t5", ar, name, numel, dst, s); };
     // "shared.weight" and "encoder.embed_tokens.weight" are the same tensor in a T5 checkpoint; accept either
     const bool has_shared = p->tensors.has("shared.weight");
     SAT_TRY(place(has_shared ? "shared.weight" : "encoder.embed_tokens.weight", (int64_t)c.vocab_size * D, &p->emb));
