@@ -45,6 +45,7 @@ struct sat_dit_plan {
     bool finalized = false;
     int inner = 0;          // FF inner dim
     int kvh_cross = 0;
+    int hd = 64;            // channels per attention head, embed_dim / num_heads: 64, or 128 = the staged route (Forward::block)
     DevBuf arena;
     std::vector<LayerW> layers;
     float *ts_w, *te0_w, *te0_b, *te2_w, *te2_b;
@@ -172,8 +173,10 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         SAT_TRY(copy_f32(p, ar, "to_prepend_embed.0.weight", (int64_t)D * p->prepend_dim, &p->pe0_w, s));
         SAT_TRY(copy_f32(p, ar, "to_prepend_embed.2.weight", (int64_t)D * D, &p->pe2_w, s));
     }
-    if (p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 16, &p->inv_freq, s));
-    else {      // frequencies 0: rope_table below comes out as cos 1 / sin 0 and the rotating epilogues are the identity
+    // RotaryEmbedding(max(dim_heads / 2, 32)): 16 frequencies for 64-channel heads, 32 for 128-channel ones (their table: the end of build)
+    const bool hd128 = p->hd == 128;
+    if (!hd128 && p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 16, &p->inv_freq, s));
+    else if (!hd128) {      // frequencies 0: rope_table below comes out as cos 1 / sin 0 and the rotating epilogues are the identity
         p->inv_freq = (float*)ar.take(16 * 4);
         if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, 16 * 4, s));
     }
@@ -181,8 +184,10 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
     p->win_eff = (float*)ar.take((size_t)D * Ci * 4);
     p->wout_eff = (float*)ar.take((size_t)D * C * 4);
     const int smax = seq_len(p, c.max_seq_len, p->max_prep);
-    p->rope_cos = (float*)ar.take((size_t)smax * 16 * 4);
-    p->rope_sin = (float*)ar.take((size_t)smax * 16 * 4);
+    if (!hd128) {
+        p->rope_cos = (float*)ar.take((size_t)smax * 16 * 4);
+        p->rope_sin = (float*)ar.take((size_t)smax * 16 * 4);
+    }
     // the absolute table has abs_pos_emb_max_length rows and no more: run_forward refuses longer sequences as the reference does
     p->pos_rows = p->pos_emb == SAT_DIT_POS_ABSOLUTE && p->abs_max < smax ? p->abs_max : smax;
     p->pos_table = p->pos_emb != SAT_DIT_POS_NONE ? (float*)ar.take((size_t)p->pos_rows * D * 4) : nullptr;
@@ -194,7 +199,7 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         SAT_TRY(get_tensor(p, "postprocess_conv.weight", (int64_t)C * C, &wpost));
         SAT_TRY(glue_fold_in(win, wpre, p->win_eff, D, Ci, s));
         SAT_TRY(glue_fold_out(wout, wpost, p->wout_eff, D, C, s));
-        SAT_TRY(sat_launch_rope_table(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
+        if (!hd128) SAT_TRY(sat_launch_rope_table(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
         if (p->pos_emb == SAT_DIT_POS_SINUSOIDAL) {     // inv_freq is not in the state dict (persistent=False), the learnt scale is
             const float* sc;
             SAT_TRY(get_tensor(p, "transformer.pos_emb.scale", 1, &sc));
@@ -233,6 +238,16 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         // ff_kwargs no_bias (transformer.py:270): the output Linear of the feed-forward has no bias tensor; FF-out then runs without one
         SAT_TRY(pack("ff.ff.2.weight", p->tensors.has(pf + "ff.ff.2.bias") ? "ff.ff.2.bias" : nullptr, FAM_FF2, D, inner, 0, nullptr, nullptr, &L.ff2));
     }
+    if (hd128) {      // behind everything a 64-channel plan places: the 32 frequencies and the [smax][32] table the head split rotates with
+        if (p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 32, &p->inv_freq, s));
+        else {
+            p->inv_freq = (float*)ar.take(32 * 4);
+            if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, 32 * 4, s));
+        }
+        p->rope_cos = (float*)ar.take((size_t)smax * 32 * 4);
+        p->rope_sin = (float*)ar.take((size_t)smax * 32 * 4);
+        if (!ar.dry()) SAT_TRY(sat_launch_rope_table_hd128(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
+    }
     return 0;
 }
 
@@ -248,6 +263,7 @@ struct Workspace {
     float* f32_wide = nullptr;   // fp32 verification mode: [M, max(3D, 2 inner)] GEMM output before the head split / SwiGLU
     float* slab = nullptr;       // K-split scratch of the 8-phase FF-out GEMM (GemmArgs::slab), present where that schedule splits
     size_t slab_bytes = 0;
+    float* qkv32 = nullptr;      // 128-channel heads: [M, 3D] fp32 output of to_qkv / [Mc, D] of the cross to_q in front of the head split
     size_t qkv_bytes;
     size_t total;
 };
@@ -281,7 +297,7 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     }
     w.A = (op_t*)ws.take(M * D * 2);
     w.AO = (op_t*)ws.take(M * D * 2);
-    w.qkv_bytes = (size_t)bf * H * Spad * 64 * 2;
+    w.qkv_bytes = (size_t)bf * H * Spad * p->hd * 2;
     // Q, K, Vt contiguous so that one memset clears all pads
     w.Q = (op_t*)ws.take(w.qkv_bytes);
     w.K = (op_t*)ws.take(w.qkv_bytes);
@@ -300,6 +316,7 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     // round (SA-2.0 shape): its slabs live here, per workspace = per caller and stream
     w.slab_bytes = (c.gemm_dtype == 0 || c.gemm_dtype == 3) ? sat_gemm_ph8_slab_bytes(EPI_RESID, (int)M, D, p->inner) : 0;
     w.slab = w.slab_bytes ? (float*)ws.take(w.slab_bytes) : nullptr;
+    if (p->hd == 128) w.qkv32 = (float*)ws.take(M * (size_t)(3 * D) * 4);      // behind every buffer a 64-channel plan carves
     w.total = ws.off;
     return w;
 }
@@ -353,6 +370,8 @@ struct Forward {
 
     int block(int l) const;
     int block_f32(int l) const;
+    int attention_hd128(int l) const;
+    int feed_forward(int l) const;
 };
 
 // fp32 verification mode: the same block on f32_ref.hip, fp32 everywhere
@@ -381,11 +400,52 @@ int Forward::block_f32(int l) const {
     return sat_launch_gemm_f32(H32, W32(L.ff2), L.ff2.bias, w.X, M, D, inner, D, 1, m ? m + 5 * D : nullptr, S, ssg_ld, s);
 }
 
+// The two attention branches of a block with 128-channel heads, staged: the heads epilogues, the fused to_q + cross-attention launch and the
+// LayerNorm fold keep one head = one 64-column wave tile (gemm_bf16.hip), so each projection runs as a plain fp32-output GEMM into qkv32, the
+// head split (head_split.hip: qk_norm, rotation, pre-scale, one rounding) writes Q / K / V^T, and attention_hd128.hip attends.  Two more
+// launches and one fp32 round trip per attention than the 64-channel route
+int Forward::attention_hd128(int l) const {
+    const LayerW& L = p->layers[l];
+    const float* m = mod(l);
+    const int f16 = p->f16, qn = p->qk_norm ? 16 : 0;
+    SAT_TRY(layernorm(L.qkv, L.pre_g, L.pre_b, M, true, m, m ? m + D : nullptr));
+    GemmArgs g = gemm(L.qkv, w.A, M);
+    g.C = w.qkv32; g.ldc = 3 * D;
+    SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
+    HeadsEpi he{};
+    he.out[0] = w.Q; he.out[1] = w.K; he.out[2] = w.Vt;
+    he.kind[0] = 2 | 8 | qn; he.kind[1] = 2 | 4 | qn; he.kind[2] = 1 | 4; he.qscale = SAT_ATTN_QSCALE_HD128;
+    he.parts = 3; he.heads = H; he.S = S; he.Spad = Spad;
+    he.rope_cos = p->rope_cos; he.rope_sin = p->rope_sin;
+    SAT_TRY(sat_launch_head_split_hd128(w.qkv32, he, bf, s, f16));
+    SAT_TRY(sat_launch_attention_hd128(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, f16));
+    SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
+    if (bc > 0) {      // (the sequences behind bc have an all-zero context: Forward::block)
+        SAT_TRY(layernorm(L.cq, L.cross_g, L.cross_b, Mc, false, nullptr, nullptr));
+        g = gemm(L.cq, w.A, Mc);
+        g.C = w.qkv32; g.ldc = D;
+        SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
+        he = HeadsEpi{};
+        he.out[0] = w.Q; he.kind[0] = 8 | qn; he.qscale = SAT_ATTN_QSCALE_HD128;
+        he.parts = 1; he.heads = H; he.S = S; he.Spad = Spad;
+        SAT_TRY(sat_launch_head_split_hd128(w.qkv32, he, bc, s, f16));
+        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * 128;
+        SAT_TRY(sat_launch_attention_hd128(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, w.AO, bc, H, p->kvh_cross, S, p->ctx_lc, Spad,
+                                           p->ctx_lcpad, s, f16));
+        SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
+    }
+    return 0;
+}
+
 int Forward::block(int l) const {
     const LayerW& L = p->layers[l];
     const float* m = mod(l);
     const int f16 = p->f16, qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
     auto mx_scales = [&](const Proj& out) { return out.kind == PROJ_FP8_MX ? w.AOs : nullptr; };      // the attention kernels write to_out's MXFP8 operand
+    if (p->hd == 128) {
+        SAT_TRY(attention_hd128(l));
+        return feed_forward(l);
+    }
     // ---- self-attention branch (transformer.py:692)
     SAT_TRY(layernorm(L.qkv, L.pre_g, L.pre_b, M, true, m, m ? m + D : nullptr));
     GemmArgs g = gemm(L.qkv, w.A, M);
@@ -421,9 +481,15 @@ int Forward::block(int l) const {
                                          p->ctx_lcpad, s, mx_scales(L.co), 1.0f, f16));
         SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
     }
-    // ---- feed-forward branch (transformer.py:700)
+    return feed_forward(l);
+}
+
+// ---- feed-forward branch (transformer.py:700)
+int Forward::feed_forward(int l) const {
+    const LayerW& L = p->layers[l];
+    const float* m = mod(l);
     SAT_TRY(layernorm(L.ff1, L.ff_g, L.ff_b, M, true, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr));
-    g = gemm(L.ff1, w.A, M);
+    GemmArgs g = gemm(L.ff1, w.A, M);
     g.H = w.Hh;
     if (L.ff2.kind == PROJ_FP8_MX) { g.H8 = (unsigned char*)w.Hh; g.Hs = w.Hs; }          // FF-out's MXFP8 operand; otherwise the e4m3 GEMM writes a 16-bit hidden state
     const bool prof = p->prof_on && l == p->cfg.depth / 2 && p->prof_n < kProfMaxPairs;
@@ -521,8 +587,9 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
     sat_dit_cfg cfg_local{};
     memcpy(&cfg_local, cfg_in, cfg_bytes);
     const sat_dit_cfg* cfg = &cfg_local;
-    SAT_CHECK_ARG(cfg->embed_dim > 0 && cfg->num_heads > 0 && cfg->embed_dim == cfg->num_heads * 64, SAT_E_UNSUPPORTED,
-                  "dit_plan_create: dim_heads must be 64 (embed_dim %d, heads %d)", cfg->embed_dim, cfg->num_heads);
+    SAT_CHECK_ARG(cfg->embed_dim > 0 && cfg->num_heads > 0 && (cfg->embed_dim == cfg->num_heads * 64 || cfg->embed_dim == cfg->num_heads * 128),
+                  SAT_E_UNSUPPORTED, "dit_plan_create: dim_heads must be 64 or 128 (embed_dim %d, heads %d)", cfg->embed_dim, cfg->num_heads);
+    const int hd = cfg->embed_dim / cfg->num_heads;
     SAT_CHECK_ARG(cfg->embed_dim % 128 == 0 && cfg->embed_dim <= 2048, SAT_E_UNSUPPORTED,
                   "dit_plan_create: embed_dim %d must be a multiple of 128 and <= 2048", cfg->embed_dim);
     // (the input / output projection kernels move 4 channels per lane: glue_output_proj checks the same at forward time)
@@ -530,9 +597,9 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
                   "dit_plan_create: io_channels %d must be a multiple of 4 in 4..64", cfg->io_channels);
     SAT_CHECK_ARG(cfg->depth > 0 && cfg->max_seq_len > 0, SAT_E_INVALID, "dit_plan_create: depth/max_seq_len must be positive");
     if (cfg->cond_token_dim > 0) {
-        SAT_CHECK_ARG(cfg->cond_embed_dim % 64 == 0 && cfg->cond_embed_dim > 0 && cfg->cond_token_dim % 4 == 0, SAT_E_UNSUPPORTED,
-                      "dit_plan_create: cond_embed_dim %d must be a multiple of 64", cfg->cond_embed_dim);
-        int kvh = cfg->cond_embed_dim / 64;
+        SAT_CHECK_ARG(cfg->cond_embed_dim % hd == 0 && cfg->cond_embed_dim > 0 && cfg->cond_token_dim % 4 == 0, SAT_E_UNSUPPORTED,
+                      "dit_plan_create: cond_embed_dim %d must be a multiple of %d", cfg->cond_embed_dim, hd);
+        int kvh = cfg->cond_embed_dim / hd;
         SAT_CHECK_ARG(cfg->num_heads % kvh == 0, SAT_E_UNSUPPORTED, "dit_plan_create: %d query heads not divisible by %d kv heads",
                       cfg->num_heads, kvh);
     }
@@ -540,6 +607,11 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
     SAT_CHECK_ARG(cfg->gemm_dtype >= 0 && cfg->gemm_dtype <= 3, SAT_E_INVALID,
                   "dit_plan_create: gemm_dtype must be 0 (bf16), 1 (e4m3), 2 (fp32 verification) or 3 (fp16)");
     SAT_CHECK_ARG(cfg->gemm_dtype != 1 || cfg->embed_dim % 256 == 0, SAT_E_UNSUPPORTED, "dit_plan_create: gemm_dtype needs embed_dim %% 256 == 0");
+    // the e4m3 attention outputs (MXFP8) and the fp32 verification kernels (a head row in registers: f32_ref.hip) are built for 64 channels
+    SAT_CHECK_ARG(hd == 64 || cfg->gemm_dtype == 0 || cfg->gemm_dtype == 3, SAT_E_UNSUPPORTED,
+                  "dit_plan_create: dim_heads 128 runs with bf16 or fp16 operands only (gemm_dtype %d)", cfg->gemm_dtype);
+    SAT_CHECK_ARG(hd == 64 || (sat_launch_head_split_hd128 && sat_launch_attention_hd128 && sat_launch_rope_table_hd128), SAT_E_UNSUPPORTED,
+                  "dit_plan_create: dim_heads 128: built without the 128-channel-head kernels");
     SAT_CHECK_ARG(cfg->gemm_dtype == 1 || cfg->fp8_families == 0, SAT_E_INVALID,
                   "dit_plan_create: fp8_families = 0x%x with gemm_dtype %d (a caller built against an older sat_dit_cfg layout?)", cfg->fp8_families, cfg->gemm_dtype);
     SAT_CHECK_ARG(cfg->cross_attention == 0 || cfg->cross_attention == 1, SAT_E_INVALID, "dit_plan_create: cross_attention must be 0 (fused where it applies) or 1 (two kernels)");
@@ -554,14 +626,15 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
     sat_dit_plan* p = new (std::nothrow) sat_dit_plan();
     SAT_CHECK_ARG(p, SAT_E_INVALID, "dit_plan_create: out of host memory");
     p->cfg = *cfg;
-    p->kvh_cross = cfg->cond_token_dim > 0 ? cfg->cond_embed_dim / 64 : 0;
+    p->hd = hd;
+    p->kvh_cross = cfg->cond_token_dim > 0 ? cfg->cond_embed_dim / hd : 0;
     // the fold lives in the bf16 pipelined GEMM tiles (K >= 192); adaLN modulates between LayerNorm and GEMM per sequence, the e4m3
     // path quantises the LayerNorm output per token: both keep the standalone kernels
     p->f16 = cfg->gemm_dtype == 3 ? 1 : 0;
     p->fp8_families = cfg->gemm_dtype == 1 ? fam : 0;
     p->cross_fusion = cfg->cross_attention == 0;
     p->tile_bits = sat_tile_policy_bits(cfg->tile_policy);
-    p->ln_fold = cfg->ln_fold != 0 && (cfg->gemm_dtype == 0 || cfg->gemm_dtype == 3) && !cfg->adaln && cfg->embed_dim >= 256;
+    p->ln_fold = cfg->ln_fold != 0 && (cfg->gemm_dtype == 0 || cfg->gemm_dtype == 3) && !cfg->adaln && cfg->embed_dim >= 256 && hd == 64;
     *out_plan = p;
     return 0;
 }
@@ -631,11 +704,12 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
     const size_t o_ch = cross ? lay.take_off((size_t)R * Dc * 4) : 0;
     const size_t o_ce = cross ? lay.take_off((size_t)R * Dc * 2) : 0;
     const bool f32 = c.gemm_dtype == 2;
-    const size_t kv_elems = cross ? (size_t)c.depth * bf * p->kvh_cross * (f32 ? lc : lcpad) * 64 : 0;
+    const size_t kv_elems = cross ? (size_t)c.depth * bf * p->kvh_cross * (f32 ? lc : lcpad) * p->hd : 0;
     const size_t o_kc = lay.take_off(kv_elems * (f32 ? 4 : 2));
     const size_t o_vc = lay.take_off(kv_elems * (f32 ? 4 : 2));
     const size_t o_kv32 = (cross && f32) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;
     const size_t o_ce32 = (cross && f32) ? lay.take_off((size_t)R * Dc * 4) : 0;
+    const size_t o_kv128 = (cross && p->hd == 128) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;      // fp32 to_kv output in front of the head split
     if (lay.off > p->ctx_buf.cap) SAT_HIP(hipStreamSynchronize(s));      // launches of the previous generation may still read the old buffer
     SAT_TRY(p->ctx_buf.reserve(lay.off));
     p->ge = (float*)(p->ctx_buf.ptr + o_ge);
@@ -668,11 +742,22 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
         SAT_TRY(glue_small_linear(ch, Dc, p->ce2_w, nullptr, nullptr, 0, ce, Dc, R, Dc, Dc, 0, p->f16 ? 2 : 1, s));
         SAT_HIP(hipMemsetAsync(p->kc, 0, kv_elems * 2, s));
         SAT_HIP(hipMemsetAsync(p->vct, 0, kv_elems * 2, s));
-        const size_t per_layer = (size_t)bf * p->kvh_cross * lcpad * 64;
+        const size_t per_layer = (size_t)bf * p->kvh_cross * lcpad * p->hd;
         for (int l = 0; l < c.depth; ++l) {
             GemmArgs g{};
             g.f16 = p->f16;
             g.A = ce; g.W = p->layers[l].ckv.w; g.M = R; g.N = 2 * Dc; g.K = Dc;
+            if (p->hd == 128) {      // staged, as Forward::attention_hd128: fp32 [R, 2 Dc] -> head split (k: normalised under qk_norm, v transposed)
+                float* kv32 = (float*)(p->ctx_buf.ptr + o_kv128);
+                g.C = kv32; g.ldc = 2 * Dc;
+                SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
+                HeadsEpi he{};
+                he.out[0] = p->kc + l * per_layer; he.out[1] = p->vct + l * per_layer;
+                he.kind[0] = 4 | (p->qk_norm ? 16 : 0); he.kind[1] = 1 | 4; he.parts = 2; he.heads = p->kvh_cross;
+                he.S = lc; he.Spad = lcpad;
+                SAT_TRY(sat_launch_head_split_hd128(kv32, he, bf, s, p->f16));
+                continue;
+            }
             g.heads.out[0] = p->kc + l * per_layer; g.heads.out[1] = p->vct + l * per_layer;
             g.heads.kind[0] = 4 | (p->qk_norm ? 16 : 0); g.heads.kind[1] = 1 | 4; g.heads.parts = 2; g.heads.heads = p->kvh_cross;
             g.heads.S = lc; g.heads.Spad = lcpad;

@@ -352,8 +352,21 @@ int sat_launch_gemm_ph8(int epi, int build, const GemmArgs& a, hipStream_t strea
 int sat_launch_attention(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh,
                          int sq, int sk, int sq_pad, int sk_pad, hipStream_t s, unsigned char* out_scales = nullptr,
                          float q_scale = SAT_ATTN_QSCALE, int f16 = 0);
+// ---- 128-channel heads (the staged route of dit_plan.hip): head_split.hip, attention_hd128.hip.  Declared WEAK: dit_plan.hip is also linked,
+// host-only, into a test driver that defines every launcher the 64-channel routes call and knows nothing of these; there they resolve to null
+// and are never reached, in libsat_hip.so they resolve at link time.  The plan answers SAT_E_UNSUPPORTED where one is null.
+// Q pre-scaled by SAT_ATTN_QSCALE_HD128; layouts as sat_launch_attention with 128 channels per head; no MXFP8 output form
+#define SAT_ATTN_QSCALE_HD128 (0.08838834764831845f * 1.4426950408889634f)
+__attribute__((weak)) int sat_launch_attention_hd128(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int sq, int sk,
+                                                     int sq_pad, int sk_pad, hipStream_t s, int f16 = 0);
+// x: fp32 [b * S, parts * heads * 128]; he: out / kind / qscale / parts / heads / S / Spad and the [S][32] rotation tables
+__attribute__((weak)) int sat_launch_head_split_hd128(const float* x, const HeadsEpi& he, int b, hipStream_t s, int f16 = 0);
 }  // namespace SAT_OPNS
 using namespace SAT_OPNS;
+__attribute__((weak)) int sat_launch_rope_table_hd128(const float* inv_freq, float* cos_t, float* sin_t, int s_len, hipStream_t s);      // [s_len][32]
+int sat_launch_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int sq, int sk, int sq_pad,
+                                   int sk_pad, hipStream_t s);
+int sat_launch_head_split_hd128_f16(const float* x, const void* heads_epi, int b, hipStream_t s);
 // entry points of the fp16 build for the dispatchers of the bf16 build (GemmArgs is layout-identical in both builds: the pointer
 // element type is the only difference)
 int sat_launch_gemm_f16(int epi, const void* gemm_args, hipStream_t stream);

@@ -134,6 +134,53 @@ extern "C" int sat_attention_prescaled_f16(const void* q, const void* k, const v
     return attention_prescaled_bf16_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
 }
 
+// ---- 128-channel heads: the attention kernel and the head split of the plan's staged route
+static int attention_hd128_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
+                                int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return sat_launch_attention_hd128((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, sq, sk, sq_pad, sk_pad,
+                                      (hipStream_t)stream, f16);
+}
+extern "C" int sat_attention_hd128_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
+                                        int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_hd128_impl(0, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
+}
+extern "C" int sat_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
+                                       int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_hd128_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
+}
+
+static int head_split_hd128_impl(int f16, const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch,
+                                 int32_t b, int32_t s_len, int32_t s_pad, int32_t heads, int32_t parts, sat_stream_t stream) {
+    SAT_CHECK_ARG(x && dst && kind && b > 0 && s_len > 0 && heads > 0 && parts >= 1 && parts <= 3, SAT_E_INVALID, "head_split_hd128: bad argument");
+    SAT_CHECK_ARG(s_pad % 64 == 0 && s_pad >= s_len + 3, SAT_E_INVALID, "head_split_hd128: bad dims (s_pad >= s + 3, %% 64)");
+    hipStream_t s = (hipStream_t)stream;
+    HeadsEpi he{};
+    bool rope = false;
+    for (int pt = 0; pt < parts; ++pt) {
+        SAT_CHECK_ARG(dst[pt], SAT_E_INVALID, "head_split_hd128: null destination %d", pt);
+        SAT_HIP(hipMemsetAsync(dst[pt], 0, (size_t)b * heads * s_pad * 128 * 2, s));
+        he.out[pt] = (op_t*)dst[pt];
+        he.kind[pt] = kind[pt];
+        rope = rope || (kind[pt] & 2);
+    }
+    if (rope) {
+        SAT_CHECK_ARG(inv_freq && rope_scratch, SAT_E_INVALID, "head_split_hd128: a rotating part needs inv_freq and rope_scratch");
+        he.rope_cos = rope_scratch;
+        he.rope_sin = rope_scratch + (size_t)s_len * 32;
+        SAT_TRY(sat_launch_rope_table_hd128(inv_freq, rope_scratch, rope_scratch + (size_t)s_len * 32, s_len, s));
+    }
+    he.qscale = SAT_ATTN_QSCALE_HD128; he.parts = parts; he.heads = heads; he.S = s_len; he.Spad = s_pad;
+    return sat_launch_head_split_hd128(x, he, b, s, f16);
+}
+extern "C" int sat_head_split_hd128_bf16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch,
+                                         int32_t b, int32_t s_len, int32_t s_pad, int32_t heads, int32_t parts, sat_stream_t stream) {
+    return head_split_hd128_impl(0, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, parts, stream);
+}
+extern "C" int sat_head_split_hd128_f16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch,
+                                        int32_t b, int32_t s_len, int32_t s_pad, int32_t heads, int32_t parts, sat_stream_t stream) {
+    return head_split_hd128_impl(1, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, parts, stream);
+}
+
 // qkn: q and k L2-normalised per head (qk_norm), q pre-scaled for the attention kernel as in the plan
 static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
                                  float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,

@@ -107,6 +107,10 @@ class DiffusionTransformer(nn.Module):
         if self.transformer.qk_norm and GEMM_DTYPES[gemm_dtype] == 1:
             raise NotImplementedError(f"attn_kwargs qk_norm=True with gemm_dtype={gemm_dtype!r}: the e4m3 projections have no normalising epilogue; "
                                       "use gemm_dtype 'fp16', 'bf16' or 'fp32x' for a qk_norm model")
+        if self.transformer.dim_heads == 128 and GEMM_DTYPES[gemm_dtype] in (1, 2):
+            raise NotImplementedError(f"dim_heads=128 (embed_dim {self.embed_dim} / num_heads {self.num_heads}) with gemm_dtype={gemm_dtype!r}: the "
+                                      "128-channel-head route (fp32 projection, head split, attention) is built for 'fp16' and 'bf16' operands; the "
+                                      "e4m3 attention outputs and the fp32 verification kernels keep 64-channel heads")
 
     def _check_seq_len(self, t_len, prepend_len):
         """The reference's ``AbsolutePositionalEmbedding`` assertion (transformer.py:59-61), on the host before anything is launched."""
@@ -157,7 +161,9 @@ class DiffusionTransformer(nn.Module):
 
     def set_layernorm_fusion(self, on: bool):
         """Build extension: run the LayerNorms of the blocks (transformer.py:692-700) inside the epilogues of the GEMMs either side of
-        them (``sat_dit_cfg.ln_fold``; bf16 / "prepend" models) or as standalone kernels.  Rebuilds the plan on next use."""
+        them (``sat_dit_cfg.ln_fold``; bf16 / "prepend" models) or as standalone kernels.  Rebuilds the plan on next use.  Accepted
+        without effect by an adaLN model and by one with 128-channel heads (as ``set_cross_attention_fusion``): their plans keep the
+        standalone kernels."""
         if bool(on) != self.layernorm_fusion:
             self.layernorm_fusion = bool(on)
             self._plan_version = None

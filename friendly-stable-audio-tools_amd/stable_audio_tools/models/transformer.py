@@ -4,7 +4,7 @@ Mirror of the module tree of the reference's ``models/transformer.py`` (``LayerN
 ``GLU``/``FeedForward`` :211-287, ``Attention`` :290-554, ``TransformerBlock`` :594-702,
 ``RotaryEmbedding`` :99-155, ``AbsolutePositionalEmbedding`` / ``ScaledSinusoidalEmbedding`` :50-96,
 ``ContinuousTransformer`` :705-809) restricted to the options the HIP plan runs: those of the shipped DiT
-configs plus ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False`` and
+configs plus 128-channel heads, ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False`` and
 bias-free / ``mult``-sized feed-forwards.  These classes only *hold* parameters under the reference's
 names; the forward pass of the whole stack is one C-ABI call (``sat_dit_forward`` /
 ``sat_dit_denoise_cfg``) issued by ``models/dit.py``.  Unsupported options raise.
@@ -83,8 +83,8 @@ class Attention(nn.Module):
         if causal or natten_kernel_size is not None or unsupported:
             raise NotImplementedError(f"Attention options not supported by the HIP path (full non-causal attention only): causal={causal} "
                                       f"natten_kernel_size={natten_kernel_size} {sorted(unsupported)}")
-        if dim_heads != 64:
-            raise NotImplementedError("the HIP attention kernel is built for dim_heads == 64")
+        if dim_heads not in (64, 128):
+            raise NotImplementedError(f"the HIP attention kernels are built for dim_heads 64 and 128 (embed_dim / num_heads), got dim_heads={dim_heads}")
         self.dim, self.dim_heads = dim, dim_heads
         self.qk_norm = bool(qk_norm)
         dim_kv = dim_context if dim_context else dim
@@ -130,7 +130,7 @@ class ContinuousTransformer(nn.Module):
                  use_sinusoidal_emb=False, use_abs_pos_emb=False, abs_pos_emb_max_length=10000, **kwargs):
         super().__init__()
         assert not (use_sinusoidal_emb and use_abs_pos_emb), "Can't select both of sinusoidal/abs positional embedding type."
-        self.dim, self.depth, self.causal = dim, depth, causal
+        self.dim, self.depth, self.causal, self.dim_heads = dim, depth, causal, dim_heads
         self.project_in = _init.linear(dim_in, dim, bias=False) if dim_in else nn.Identity()
         self.project_out = _init.linear(dim, dim_out, bias=False) if dim_out else nn.Identity()
         self.rotary_pos_emb = RotaryEmbedding(max(dim_heads // 2, 32)) if rotary_pos_emb else None

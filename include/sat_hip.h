@@ -81,7 +81,8 @@ typedef struct sat_dit_cfg {
     int32_t io_channels;       /* config "io_channels" (64) */
     int32_t embed_dim;         /* "embed_dim" (1536); multiple of 128 */
     int32_t depth;             /* "depth" (24) */
-    int32_t num_heads;         /* "num_heads" (24); embed_dim / num_heads must be 64 */
+    int32_t num_heads;         /* "num_heads" (24); embed_dim / num_heads must be 64, or 128 = the staged attention route: bf16 / fp16
+                                  operands only, no LayerNorm fold, no fused cross-attention launch */
     int32_t cond_token_dim;    /* "cond_token_dim" (768); 0 = no cross-attention */
     int32_t cond_embed_dim;    /* cond_token_dim if project_cond_tokens=false else embed_dim */
     int32_t global_cond_dim;   /* "global_cond_dim" (1536); 0 = timestep embedding only */
@@ -434,6 +435,23 @@ int sat_attention_bf16(const void* q_dev, const void* k_dev, const void* vt_dev,
 int sat_attention_prescaled_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                                  int32_t b, int32_t h, int32_t kvh, int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad,
                                  sat_stream_t stream);
+/* ---- 128-channel heads (embed_dim == 128 * num_heads): the two kernels of the plan's staged route.
+ * sat_attention_hd128_*: arguments and layouts of sat_attention_prescaled_* with 128 channels per head -- q [b, h, sq_pad, 128]
+ * pre-scaled by log2(e) / sqrt(128), k [b, kvh, sk_pad, 128] and vt [b, kvh, 128, sk_pad] in the key-side layout (sequence i from row /
+ * column (i * sk) & 3, vt's key index permuted inside aligned groups of 16 as [0-3, 8-11, 4-7, 12-15]), zero pads, sq_pad % 128 == 0,
+ * sk_pad % 64 == 0, sk_pad >= sk + 3; out [b * sq, h * 128]. */
+int sat_attention_hd128_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev,
+                             int32_t b, int32_t h, int32_t kvh, int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad,
+                             sat_stream_t stream);
+/* sat_head_split_hd128_*: x [b * s, parts * heads * 128] fp32 (the output of a bias-free projection), parts <= 3, part p -> dst_dev[p] with
+ * kind[p] bits: 1 transposed [b, heads, 128, s_pad] with the key permutation above (no other bit but 4), else row-major [b, heads, s_pad, 128];
+ * 2 rotate channels 0..63 in pairs (j, j + 32) by position * inv_freq[j] (inv_freq_dev: 32 floats; may be null when no part rotates);
+ * 4 key-side: sequence i starts at row / column (i * s) & 3; 8 multiply by log2(e) / sqrt(128); 16 L2-normalise the 128 channels first,
+ * x / max(|x|, 1e-12).  Order: normalise, rotate, scale, one rounding.  The destinations are zeroed first (pads), s_pad % 64 == 0,
+ * s_pad >= s + 3; rope_scratch_dev: 2 * s * 32 floats. */
+int sat_head_split_hd128_bf16(const float* x_dev, const float* inv_freq_dev, void* const* dst_dev, const int32_t* kind,
+                              float* rope_scratch_dev, int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t parts,
+                              sat_stream_t stream);
 /* Cross-attention query projection and attention core in one launch (models/transformer.py:430-437 + 496-536; what the DiT plan
  * runs per layer while the 128 x 64 GEMM tiles of the projection fit one round of workgroups, i.e. at one prompt):
  * out [b*s, d] bf16 = softmax((a wq^T) k^T / 8) v per head of 64, a [b*s, d] bf16, wq [d, d] bf16, k / vt in the key-side layout of
@@ -500,6 +518,12 @@ int sat_attention_f16(const void* q_dev, const void* k_dev, const void* vt_dev, 
 int sat_attention_prescaled_f16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                                 int32_t b, int32_t h, int32_t kvh, int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad,
                                 sat_stream_t stream);
+int sat_attention_hd128_f16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev,
+                            int32_t b, int32_t h, int32_t kvh, int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad,
+                            sat_stream_t stream);
+int sat_head_split_hd128_f16(const float* x_dev, const float* inv_freq_dev, void* const* dst_dev, const int32_t* kind,
+                             float* rope_scratch_dev, int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t parts,
+                             sat_stream_t stream);
 int sat_cross_attention_fused_f16(const void* a_f16_dev, const void* wq_f16_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                                   int32_t b, int32_t s, int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream);
 int sat_qkv_rope_f16(const void* a_f16_dev, const void* w_f16_dev, const float* inv_freq_dev,
