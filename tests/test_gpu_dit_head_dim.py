@@ -15,7 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import cases  # noqa: E402
 import dit_head_dim_cases as HC  # noqa: E402
-from util import FORMATS, SUITE, assert_close, rel_l2  # noqa: E402
+import mask_edge  # noqa: E402
+from util import FORMATS, SUITE, assert_close, assert_close_sliced, guarded, rel_l2  # noqa: E402
 
 T = SUITE.tol
 pytestmark = pytest.mark.gpu
@@ -58,11 +59,18 @@ def _attention(dev, fmt, q, k, v):
     qd = _pad_heads(q, sq_pad).to(dev)
     kd = _pad_heads(k, sk_pad, key_side=True).to(dev)
     vtd = _pad_heads(v, sk_pad, key_side=True).transpose(2, 3)[..., _vt_perm(sk_pad)].contiguous().to(dev)
-    out = torch.empty((b * sq, h * 128), dtype=fmt.dtype, device=dev)
+    og = guarded((b * sq, h * 128), fmt.dtype, dev, name="out")          # between guard bands, NaN where the kernel has not written
+    out = og.t
     _hip.check(fmt.fn(lib, "sat_attention_hd128_bf16")(_hip.ptr(qd), _hip.ptr(kd), _hip.ptr(vtd), _hip.ptr(out), b, h, kvh, sq, sk, sq_pad,
                                                        sk_pad, _hip.stream()))
     torch.cuda.synchronize()
+    og.check().assert_written()
     return out.view(b, sq, h * 128)
+
+
+def _per_query(x, h):
+    b, sq, _ = x.shape
+    return x.view(b, sq, h, 128)          # keep_dims (0, 1, 2): one slice per (sequence, query, head)
 
 
 # (3, 2, 1, 200, 61): a single tile with first-tile masking at the key shifts 0, 1, 2; (1, 2, 2, 1025, 1025): 17 tiles, a one-row query tail
@@ -85,6 +93,8 @@ def test_attention_hd128(dev, b, h, kvh, sq, sk, fmt):
     print(f"\n[attention_hd128 {fmt} {b}x{h}/{kvh}x{sq}x{sk}] rel-L2 vs matched rounding {e:.2e} (gate {fmt.tol(5e-3):.1e}), vs exact {ex:.2e} "
           f"(gate {fmt.tol(1e-2):.1e})")
     assert_close(f"attention_hd128 {b}x{h}x{sq}x{sk}", out, want, fmt.tol(5e-3))
+    assert_close_sliced(f"attention_hd128 {b}x{h}x{sq}x{sk} per (sequence, query, head)", _per_query(out, h), _per_query(want, h), fmt.tol(5e-3),
+                        (0, 1, 2), fmt.round)
     assert ex < fmt.tol(1e-2)
 
 
@@ -110,7 +120,25 @@ def test_attention_hd128_all_scores_strongly_negative(dev, fmt):
     out = _attention(dev, fmt, q, k, v)
     e0 = assert_close("attention_hd128, all-negative rows", out[:, :32], want[:, :32], 2e-2 if not fmt.f16 else 5e-3)
     e1 = assert_close("attention_hd128, ordinary rows", out[:, 32:], want[:, 32:], fmt.tol(5e-3))
+    got4, want4 = _per_query(out, h), _per_query(want, h)
+    assert_close_sliced("attention_hd128, all-negative rows per (sequence, query, head)", got4[:, :32], want4[:, :32], 2e-2 if not fmt.f16 else 5e-3,
+                        (0, 1, 2), fmt.round)
+    assert_close_sliced("attention_hd128, ordinary rows per (sequence, query, head)", got4[:, 32:], want4[:, 32:], fmt.tol(5e-3), (0, 1, 2), fmt.round)
     print(f"\n[attention_hd128 {fmt} strongly negative] rel-L2 negative rows {e0:.2e}, ordinary rows {e1:.2e}")
+
+
+@pytest.mark.parametrize("fmt", FORMATS, ids=repr)
+@pytest.mark.parametrize("sk", [63, 573])
+def test_attention_hd128_masks_front_pad_keys(dev, sk, fmt):
+    """mask_edge.py: four sequences at the key shifts 0, 1, 2, 3 (one and two key tiles at 63 keys, nine at 573), every real logit near
+    -159 -- an attended front pad key (score 0, V = 0) takes its whole row.  Gates of the all-strongly-negative test, whole and per
+    (sequence, query, head)."""
+    case = mask_edge.self_attention_case(fmt, 128, sk, prescaled=True)
+    out = _attention(dev, fmt, case["q"], case["k"], case["v"])
+    gate, h = mask_edge.NEG_GATE[fmt.name], case["h"]
+    assert_close(f"attention_hd128, mask edge, {sk} keys", out, case["want"], gate)
+    assert_close_sliced(f"attention_hd128, mask edge, {sk} keys per (sequence, query, head)", _per_query(out, h), _per_query(case["want"], h), gate,
+                        (0, 1, 2), fmt.round)
 
 
 @pytest.mark.parametrize("fmt", FORMATS, ids=repr)
@@ -140,18 +168,20 @@ def test_head_split_hd128(dev, fmt, qk_norm):
 
     q, k = norm_rope(q) * QSCALE, norm_rope(k)
     xd, fd = x.to(dev), inv_freq.to(dev)
-    qd = torch.full((b, h, s_pad, 128), float("nan"), dtype=fmt.dtype, device=dev)
-    kd = torch.full_like(qd, float("nan"))
-    vtd = torch.full((b, h, 128, s_pad), float("nan"), dtype=fmt.dtype, device=dev)
-    scratch = torch.empty((2 * s * 32,), dtype=torch.float32, device=dev)
+    guards = (guarded((b, h, s_pad, 128), fmt.dtype, dev, name="q"), guarded((b, h, s_pad, 128), fmt.dtype, dev, name="k"),
+              guarded((b, h, 128, s_pad), fmt.dtype, dev, name="v^T"), guarded((2 * s * 32,), torch.float32, dev, name="rope scratch"))
+    qd, kd, vtd, scratch = (g_.t for g_ in guards)
     qn = 16 if qk_norm else 0
     dst = (ctypes.c_void_p * 3)(qd.data_ptr(), kd.data_ptr(), vtd.data_ptr())
     kind = (ctypes.c_int32 * 3)(2 | 8 | qn, 2 | 4 | qn, 1 | 4)          # what the plan passes for to_qkv
     _hip.check(fmt.fn(lib, "sat_head_split_hd128_bf16")(_hip.ptr(xd), _hip.ptr(fd), dst, kind, _hip.ptr(scratch), b, s, s_pad, h, 3, _hip.stream()))
     torch.cuda.synchronize()
+    for g_ in guards:
+        g_.check()
     for name, buf in (("q", qd), ("k", kd), ("v^T", vtd)):
         assert torch.isfinite(buf.float()).all(), f"non-finite values in the padded {name} buffer"
     eq = assert_close("head split q", qd[:, :, :s], q.float(), fmt.tol(4e-3))
+    assert_close_sliced("head split q per (sequence, head, token)", qd[:, :, :s], q.float(), fmt.tol(4e-3), (0, 1, 2), fmt.round)
     assert (qd[:, :, s:] == 0).all(), "Q pads must be zero"
     vtd = vtd[..., _vt_perm(s_pad).to(vtd.device)]
     ek = ev = 0.0
@@ -159,6 +189,8 @@ def test_head_split_hd128(dev, fmt, qk_norm):
         ob = (i * s) & 3
         ek = max(ek, assert_close("head split k", kd[i, :, ob:ob + s], k[i].float(), fmt.tol(4e-3)))
         ev = max(ev, assert_close("head split v^T", vtd[i, :, :, ob:ob + s], v[i].transpose(1, 2).float(), fmt.tol(4e-3)))
+        assert_close_sliced("head split k per (head, token)", kd[i, :, ob:ob + s], k[i].float(), fmt.tol(4e-3), (0, 1), fmt.round)
+        assert_close_sliced("head split v^T per (head, key column)", vtd[i, :, :, ob:ob + s], v[i].transpose(1, 2).float(), fmt.tol(4e-3), (0, 2), fmt.round)
         assert (kd[i, :, :ob] == 0).all() and (kd[i, :, ob + s:] == 0).all(), "K pads must be zero"
         assert (vtd[i, :, :, :ob] == 0).all() and (vtd[i, :, :, ob + s:] == 0).all(), "V^T pads must be zero"
     assert (qd[0, :, 5] == 0).all() and (kd[0, :, 5] == 0).all()          # the all-zero row stays zero (0 / max(0, 1e-12))

@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import cases  # noqa: E402
 import dit_options_cases as OC  # noqa: E402
-from util import FORMATS, SUITE, assert_close, rel_l2  # noqa: E402
+from util import FORMATS, SUITE, assert_close, assert_close_sliced, guarded, rel_l2  # noqa: E402
 
 T = SUITE.tol
 pytestmark = pytest.mark.gpu
@@ -200,17 +200,19 @@ def test_qkv_rope_qknorm(dev, variant, fmt):
 
     q, k = norm_rope(q) * (1.4426950408889634 / 8.0), norm_rope(k)
     ad, wd, fd = a.to(dev), w.to(dev), inv_freq.to(dev)
-    qd = torch.full((b, h, s_pad, 64), float("nan"), dtype=fmt.dtype, device=dev)
-    kd = torch.full_like(qd, float("nan"))
-    vtd = torch.full((b, h, 64, s_pad), float("nan"), dtype=fmt.dtype, device=dev)
-    scratch = torch.empty((2 * s * 16,), dtype=torch.float32, device=dev)
+    guards = (guarded((b, h, s_pad, 64), fmt.dtype, dev, name="q"), guarded((b, h, s_pad, 64), fmt.dtype, dev, name="k"),
+              guarded((b, h, 64, s_pad), fmt.dtype, dev, name="v^T"), guarded((2 * s * 16,), torch.float32, dev, name="rope scratch"))
+    qd, kd, vtd, scratch = (g_.t for g_ in guards)
     fn = fmt.fn(lib, "sat_qkv_rope_qknorm_bf16")
     _hip.check(fn(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(fd), _hip.ptr(qd), _hip.ptr(kd), _hip.ptr(vtd), _hip.ptr(scratch), b, s, s_pad, d, variant,
                   _hip.stream()))
     torch.cuda.synchronize()
+    for g_ in guards:
+        g_.check()
     for name, buf in (("q", qd), ("k", kd), ("v^T", vtd)):
         assert torch.isfinite(buf.float()).all(), f"non-finite values in the padded {name} buffer"
     eq = assert_close("qk_norm q", qd[:, :, :s], q.float(), fmt.tol(4e-3))
+    assert_close_sliced("qk_norm q per (sequence, head, token)", qd[:, :, :s], q.float(), fmt.tol(4e-3), (0, 1, 2), fmt.round)
     assert (qd[:, :, s:] == 0).all(), "Q pads must be zero"
     vtd = vtd[..., _vt_perm(s_pad).to(vtd.device)]
     ek = 0.0
@@ -218,6 +220,8 @@ def test_qkv_rope_qknorm(dev, variant, fmt):
         ob = (i * s) & 3
         ek = max(ek, assert_close("qk_norm k", kd[i, :, ob:ob + s], k[i].float(), fmt.tol(4e-3)))
         assert_close("v^T", vtd[i, :, :, ob:ob + s], v[i].transpose(1, 2).float(), fmt.tol(4e-3))
+        assert_close_sliced("qk_norm k per (head, token)", kd[i, :, ob:ob + s], k[i].float(), fmt.tol(4e-3), (0, 1), fmt.round)
+        assert_close_sliced("qk_norm v^T per (head, key column)", vtd[i, :, :, ob:ob + s], v[i].transpose(1, 2).float(), fmt.tol(4e-3), (0, 2), fmt.round)
         assert (kd[i, :, :ob] == 0).all() and (kd[i, :, ob + s:] == 0).all(), "K pads must be zero"
         assert (vtd[i, :, :, :ob] == 0).all() and (vtd[i, :, :, ob + s:] == 0).all(), "V^T pads must be zero"
     # the all-zero input row stays zero (0 / max(0, 1e-12)), every other head row has unit norm

@@ -8,7 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from util import FORMATS, assert_close, bf16_round, rel_l2
+import mask_edge
+from util import FORMATS, assert_close, assert_close_rows_blocks, assert_close_sliced, bf16_round, e4m3_code_distance, guarded, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +33,14 @@ def test_layernorm(dev, m, d, fmt):
     b = 0.05 * _rand((d,), 3)
     want = F.layer_norm(x, (d,), g, b, eps=1e-5)
     xd, gd, bd = x.to(dev), g.to(dev), b.to(dev)
-    y = torch.empty((m, d), dtype=fmt.dtype, device=dev)
+    yg = guarded((m, d), fmt.dtype, dev, name="y")
+    y = yg.t
     _hip.check(fmt.fn(lib, "sat_layernorm_bf16")(_hip.ptr(xd), _hip.ptr(gd), _hip.ptr(bd), _hip.ptr(y), m, d, _hip.stream()))
+    yg.check().assert_written()
     assert_close("layernorm", y, want, fmt.tol(4e-3))
+    assert_close_rows_blocks("layernorm", y, want, fmt.tol(4e-3), fmt.round)
     assert_close("layernorm-vs-rounded", y, fmt.round(want), fmt.tol(1e-3))
+    assert_close_rows_blocks("layernorm-vs-rounded", y, fmt.round(want), fmt.tol(1e-3))
 
 
 @pytest.mark.parametrize("fmt", FORMATS, ids=repr)
@@ -45,8 +50,10 @@ def test_cast_bf16(dev, fmt):
     if fmt.f16:       # range policy of the fp16 build: saturate at +-65504, keep subnormals, flush below 2^-25
         x[:8] = torch.tensor([7e4, -7e4, 65504.0, 65520.0, 1e30, 3e-6, 2e-8, -1e-9])
     xd = x.to(dev)
-    y = torch.empty(x.shape, dtype=fmt.dtype, device=dev)
+    yg = guarded(x.shape, fmt.dtype, dev, name="y", pitch=4096)          # a flat output of 10^6 elements: 2^20 elements of guard on each side
+    y = yg.t
     _hip.check(fmt.fn(lib, "sat_cast_bf16")(_hip.ptr(xd), _hip.ptr(y), x.numel(), _hip.stream()))
+    yg.check().assert_written()
     assert torch.equal(y.cpu(), x.clamp(-65504.0, 65504.0).to(fmt.dtype) if fmt.f16 else x.to(fmt.dtype))
 
 
@@ -97,18 +104,25 @@ def test_gemm_f32(dev, variant, m, n, k, fmt):
     bias = _rand((n,), 7)
     c0 = _rand((m, n), 8)
     want = a.float() @ w.float().T + bias + c0
-    ad, wd, bd, cd = a.to(dev), w.to(dev), bias.to(dev), c0.to(dev)
+    ad, wd, bd = a.to(dev), w.to(dev), bias.to(dev)
+    cg = guarded((m, n), torch.float32, dev, init=c0, name="c")
+    cd = cg.t
     if variant & 0x10000:
         ws, ws_bytes = _split_ws(dev, m, n, k, variant)
         assert ws_bytes == 256 * 65536 * 4
         _hip.check(fmt.fn(lib, "sat_gemm_bf16_f32_ws")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(bd), _hip.ptr(cd), m, n, k, 1, variant, _hip.ptr(ws),
                                                        ws_bytes, _hip.stream()))
         # a forced split without scratch is refused, not silently run whole (a single tile with a single K unit has nothing to split)
-        rc = -4 if (m, n, k) == (130, 256, 128) else fmt.fn(lib, "sat_gemm_bf16_f32")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(bd), _hip.ptr(torch.empty_like(cd)), m, n, k, 1, variant, _hip.stream())
+        rg = guarded((m, n), torch.float32, dev, name="c of the refused call")
+        rc = -4 if (m, n, k) == (130, 256, 128) else fmt.fn(lib, "sat_gemm_bf16_f32")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(bd), _hip.ptr(rg.t), m, n, k, 1, variant, _hip.stream())
         assert rc == -4, f"forced K-split without workspace returned {rc}, expected SAT_E_WORKSPACE"
+        rg.check()
+        assert bool(torch.isnan(rg.t).all()), "a refused call writes nothing"
     else:
         _hip.check(fmt.fn(lib, "sat_gemm_bf16_f32")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(bd), _hip.ptr(cd), m, n, k, 1, variant, _hip.stream()))
+    cg.check().assert_written()
     assert_close(f"gemm v{variant} {m}x{n}x{k}", cd, want, 1e-3 if not fmt.f16 else 1e-5)      # same operands: fp32 summation order only
+    assert_close_rows_blocks(f"gemm v{variant} {m}x{n}x{k}", cd, want, 1e-3 if not fmt.f16 else 1e-5)
 
 
 @pytest.mark.parametrize("fmt", FORMATS, ids=repr)
@@ -125,12 +139,15 @@ def test_gemm_swiglu(dev, variant, m, fmt):
     val, gate = h.chunk(2, dim=-1)
     want = val * F.silu(gate)
     ad, wd, bd = a.to(dev), w.to(dev), bias.to(dev)
-    wp = torch.empty((2 * inner, k), dtype=fmt.dtype, device=dev)
-    bp = torch.empty((2 * inner,), dtype=torch.float32, device=dev)
-    out = torch.empty((m, inner), dtype=fmt.dtype, device=dev)
+    wpg, bpg = guarded((2 * inner, k), fmt.dtype, dev, name="wp"), guarded((2 * inner,), torch.float32, dev, name="bp")
+    og = guarded((m, inner), fmt.dtype, dev, name="out")
+    wp, bp, out = wpg.t, bpg.t, og.t
     _hip.check(fmt.fn(lib, "sat_gemm_swiglu_bf16")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(bd), _hip.ptr(wp), _hip.ptr(bp), _hip.ptr(out), m,
                                                    2 * inner, k, variant, _hip.stream()))
+    for g_ in (wpg, bpg, og):
+        g_.check().assert_written()
     assert_close("swiglu", out, want, fmt.tol(4e-3))
+    assert_close_rows_blocks("swiglu", out, want, fmt.tol(4e-3), fmt.round)
 
 
 def _vt_perm(n):
@@ -180,9 +197,13 @@ def test_attention(dev, b, h, kvh, sq, sk, prescaled, fmt):
     qd = _pad_heads(q, sq_pad).to(dev)
     kd = _pad_heads(k, sk_pad, key_side=True).to(dev)
     vtd = _pad_heads(v, sk_pad, key_side=True).transpose(2, 3)[..., _vt_perm(sk_pad)].contiguous().to(dev)
-    out = torch.empty((b * sq, h * 64), dtype=fmt.dtype, device=dev)
+    og = guarded((b * sq, h * 64), fmt.dtype, dev, name="out")
+    out = og.t
     _hip.check(fn(_hip.ptr(qd), _hip.ptr(kd), _hip.ptr(vtd), _hip.ptr(out), b, h, kvh, sq, sk, sq_pad, sk_pad, _hip.stream()))
+    og.check().assert_written()
     assert_close(f"attention {b}x{h}x{sq}x{sk}", out.view(b, sq, h * 64), want, fmt.tol(5e-3))
+    assert_close_sliced(f"attention {b}x{h}x{sq}x{sk} per (sequence, query, head)", out.view(b, sq, h, 64), want.view(b, sq, h, 64), fmt.tol(5e-3),
+                        (0, 1, 2), fmt.round)
     exact = odit._merge(odit.attention_core(q_eff, k.float(), v.float()))
     assert rel_l2(out.view(b, sq, h * 64), exact) < fmt.tol(1e-2)
 
@@ -218,10 +239,67 @@ def test_attention_all_scores_strongly_negative(dev, prescaled, fmt):
     qd = _pad_heads(q, sq_pad).to(dev)
     kd = _pad_heads(k, sk_pad, key_side=True).to(dev)
     vtd = _pad_heads(v, sk_pad, key_side=True).transpose(2, 3)[..., _vt_perm(sk_pad)].contiguous().to(dev)
-    out = torch.empty((b * sq, h * 64), dtype=fmt.dtype, device=dev)
+    og = guarded((b * sq, h * 64), fmt.dtype, dev, name="out")
+    out = og.t
     _hip.check(fn(_hip.ptr(qd), _hip.ptr(kd), _hip.ptr(vtd), _hip.ptr(out), b, h, kvh, sq, sk, sq_pad, sk_pad, _hip.stream()))
+    og.check().assert_written()
     assert_close("attention, all-negative rows", out.view(b, sq, h * 64)[:, :32], want[:, :32], 2e-2 if not fmt.f16 else 5e-3)
     assert_close("attention, ordinary rows", out.view(b, sq, h * 64)[:, 32:], want[:, 32:], fmt.tol(5e-3))
+    got4, want4 = out.view(b, sq, h, 64), want.view(b, sq, h, 64)
+    assert_close_sliced("attention, all-negative rows per (sequence, query, head)", got4[:, :32], want4[:, :32], 2e-2 if not fmt.f16 else 5e-3, (0, 1, 2), fmt.round)
+    assert_close_sliced("attention, ordinary rows per (sequence, query, head)", got4[:, 32:], want4[:, 32:], fmt.tol(5e-3), (0, 1, 2), fmt.round)
+
+
+def _mask_edge_self_attention(dev, fmt, sk, prescaled):
+    """mask_edge.py: four sequences at the key shifts 0, 1, 2, 3, every real logit near -150 -- an attended front pad key (score 0, V = 0)
+    takes its whole row.  Gates of the all-strongly-negative test, whole and per (sequence, query, head)."""
+    _hip, lib = _lib()
+    case = mask_edge.self_attention_case(fmt, 64, sk, prescaled)
+    b, h, kvh, sq = case["b"], case["h"], case["kvh"], case["sq"]
+    sq_pad, sk_pad = 128, (sk + 3 + 63) // 64 * 64
+    qd = _pad_heads(case["q"], sq_pad).to(dev)
+    kd = _pad_heads(case["k"], sk_pad, key_side=True).to(dev)                   # (pads stay zero, as the producers guarantee)
+    vtd = _pad_heads(case["v"], sk_pad, key_side=True).transpose(2, 3)[..., _vt_perm(sk_pad)].contiguous().to(dev)
+    og = guarded((b * sq, h * 64), fmt.dtype, dev, name="out")
+    fn = fmt.fn(lib, "sat_attention_prescaled_bf16" if prescaled else "sat_attention_bf16")
+    _hip.check(fn(_hip.ptr(qd), _hip.ptr(kd), _hip.ptr(vtd), _hip.ptr(og.t), b, h, kvh, sq, sk, sq_pad, sk_pad, _hip.stream()))
+    og.check().assert_written()
+    gate, name = mask_edge.NEG_GATE[fmt.name], f"attention{' (pre-scaled)' if prescaled else ''}, mask edge, {sk} keys"
+    assert_close(name, og.t.view(b, sq, h * 64), case["want"], gate)
+    assert_close_sliced(name + " per (sequence, query, head)", og.t.view(b, sq, h, 64), case["want"].view(b, sq, h, 64), gate, (0, 1, 2), fmt.round)
+
+
+@pytest.mark.parametrize("fmt", FORMATS, ids=repr)
+@pytest.mark.parametrize("sk", [63, 573])
+def test_attention_masks_front_pad_keys(dev, sk, fmt):
+    _mask_edge_self_attention(dev, fmt, sk, prescaled=False)
+
+
+@pytest.mark.parametrize("fmt", FORMATS, ids=repr)
+@pytest.mark.parametrize("sk", [63, 573])
+def test_attention_prescaled_masks_front_pad_keys(dev, sk, fmt):
+    _mask_edge_self_attention(dev, fmt, sk, prescaled=True)
+
+
+@pytest.mark.parametrize("fmt", FORMATS, ids=repr)
+def test_cross_attention_fused_masks_front_pad_keys(dev, fmt):
+    """The same for to_q + cross-attention in one launch: a and w_q project every query onto the opposite of the keys' direction.  Four
+    heads, not two: the entry needs d >= 192.  96-row sequences: every 128-row tile straddles two of them."""
+    _hip, lib = _lib()
+    case = mask_edge.fused_cross_attention_case(fmt, 63)
+    b, h, kvh, s, sk, d = case["b"], case["h"], case["kvh"], case["sq"], case["sk"], case["d"]
+    sk_pad = (sk + 3 + 63) // 64 * 64
+    kd = _pad_heads(case["k"], sk_pad, key_side=True).to(dev)
+    vtd = _pad_heads(case["v"], sk_pad, key_side=True).transpose(2, 3)[..., _vt_perm(sk_pad)].contiguous().to(dev)
+    ad, wd = case["a"].to(dev), case["wq"].to(dev)
+    og = guarded((b * s, d), fmt.dtype, dev, name="out")
+    _hip.check(fmt.fn(lib, "sat_cross_attention_fused_bf16")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(kd), _hip.ptr(vtd), _hip.ptr(og.t), b, s, d,
+                                                             kvh, sk, sk_pad, _hip.stream()))
+    og.check().assert_written()
+    gate = mask_edge.NEG_GATE[fmt.name]
+    assert_close("fused cross-attention, mask edge", og.t.view(b, s, d), case["want"], gate)
+    assert_close_sliced("fused cross-attention, mask edge per (sequence, query, head)", og.t.view(b, s, h, 64), case["want"].view(b, s, h, 64), gate,
+                        (0, 1, 2), fmt.round)
 
 
 def test_fp16_range_policy(dev):
@@ -238,28 +316,35 @@ def test_fp16_range_policy(dev):
     beta = 0.1 * _rand((d,), 403)
     bias = 0.1 * _rand((2 * inner,), 404)
     wd, gd, bd, bbd = w.to(dev), gamma.to(dev), beta.to(dev), bias.to(dev)
-    wp = torch.empty((2 * inner, d), dtype=fmt.dtype, device=dev)
-    c12 = torch.empty((4 * inner,), dtype=torch.float32, device=dev)
-    out = torch.full((m, inner), float("nan"), dtype=fmt.dtype, device=dev)
+    wpg, cg = guarded((2 * inner, d), fmt.dtype, dev, name="wp"), guarded((4 * inner,), torch.float32, dev, name="c12")
+    og = guarded((m, inner), fmt.dtype, dev, name="out")
+    wp, c12, out = wpg.t, cg.t, og.t
     _hip.check(lib.sat_gemm_swiglu_ln_f16(_hip.ptr(xb), _hip.ptr(part), _hip.ptr(wd), _hip.ptr(gd), _hip.ptr(bd), _hip.ptr(bbd), _hip.ptr(wp),
                                           _hip.ptr(c12), _hip.ptr(out), m, 2 * inner, d, 0, _hip.stream()))
+    for g_ in (wpg, cg, og):
+        g_.check().assert_written()
     val, gate = F.linear(F.layer_norm(cd.cpu(), (d,), gamma, beta, eps=1e-5), w, bias).chunk(2, dim=-1)
     assert_close("fp16 fold on rows of magnitude 3e4 vs fp32 LayerNorm + Linear", out, val * F.silu(gate), 2.5e-3)
+    assert_close_rows_blocks("fp16 fold on rows of magnitude 3e4 vs fp32 LayerNorm + Linear", out, val * F.silu(gate), 2.5e-3, fmt.round)
     # beyond the range: saturation, not infinity
     x = _rand((64, d), 405) * 3.0e4
     x[:, 7] = 2.0e5
     x[:, 9] = -1.0e6
-    y = torch.empty((64, d), dtype=torch.float16, device=dev)
+    yg = guarded((64, d), torch.float16, dev, name="y")
+    y = yg.t
     xd = x.to(dev)
     _hip.check(lib.sat_cast_f16(_hip.ptr(xd), _hip.ptr(y), x.numel(), _hip.stream()))
+    yg.check()
     assert torch.isfinite(y).all() and y[:, 7].eq(65504).all() and y[:, 9].eq(-65504).all()
     a = torch.full((64, 256), 200.0, dtype=torch.float16)
     wq = torch.full((d, 256), 2.0, dtype=torch.float16)
     c0 = torch.zeros((64, d))
-    xb2 = torch.empty((64, d), dtype=torch.float16, device=dev)
-    part2 = torch.empty((64, d // 64, 2), dtype=torch.float32, device=dev)
-    ad, wqd, c0d = a.to(dev), wq.to(dev), c0.to(dev)
+    xg2, pg2, cg2 = guarded((64, d), torch.float16, dev, name="xb"), guarded((64, d // 64, 2), torch.float32, dev, name="ln_part", pitch=2 * (d // 64)), guarded((64, d), torch.float32, dev, init=c0, name="c")
+    xb2, part2, c0d = xg2.t, pg2.t, cg2.t
+    ad, wqd = a.to(dev), wq.to(dev)
     _hip.check(lib.sat_gemm_resid_ln_f16(_hip.ptr(ad), _hip.ptr(wqd), None, _hip.ptr(c0d), _hip.ptr(xb2), _hip.ptr(part2), 64, d, 256, 0, _hip.stream()))
+    for g_ in (xg2, pg2, cg2):
+        g_.check().assert_written()
     assert c0d.eq(102400.0).all(), "fp32 output: exact"
     assert xb2.eq(65504).all(), "the fp16 image of an over-range row saturates"
     assert torch.allclose(part2[..., 0].cpu(), torch.full((64, d // 64), 64 * 65504.0)), "row statistics are those of the saturated image"
@@ -268,9 +353,10 @@ def test_fp16_range_policy(dev):
         a = torch.full((256, 256), 2.0 ** -20, dtype=torch.float16)
         a[:, ::2] = 3 * 2.0 ** -24
         wq = torch.full((256, 256), 4.0, dtype=torch.float16)
-        cz = torch.zeros((256, 256))
-        ad, wqd, czd = a.to(dev), wq.to(dev), cz.to(dev)
+        czg = guarded((256, 256), torch.float32, dev, name="c")          # accumulate = 0: the kernel writes every element
+        ad, wqd, czd = a.to(dev), wq.to(dev), czg.t
         _hip.check(lib.sat_gemm_f16_f32(_hip.ptr(ad), _hip.ptr(wqd), None, _hip.ptr(czd), 256, 256, 256, 0, variant, _hip.stream()))
+        czg.check().assert_written()
         assert torch.equal(czd.cpu(), a.float() @ wq.float().T), f"tile {variant}: subnormal fp16 operands were flushed by the MFMA"
 
 
@@ -294,11 +380,15 @@ def test_cross_attention_fused(dev, b, s, d, kvh, sk, fmt):
     sk_pad = (sk + 3 + 63) // 64 * 64
     kd = _pad_heads(k, sk_pad, key_side=True).to(dev)
     vtd = _pad_heads(v, sk_pad, key_side=True).transpose(2, 3)[..., _vt_perm(sk_pad)].contiguous().to(dev)
-    out = torch.zeros((b * s, d), dtype=fmt.dtype, device=dev)
+    og = guarded((b * s, d), fmt.dtype, dev, name="out")
+    out = og.t
     ad, wd = a.to(dev), wq.to(dev)          # (named: a temporary would be freed before the launch reads it)
     _hip.check(fmt.fn(lib, "sat_cross_attention_fused_bf16")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(kd), _hip.ptr(vtd), _hip.ptr(out), b, s, d,
                                                              kvh, sk, sk_pad, _hip.stream()))
+    og.check().assert_written()
     assert_close(f"fused cross-attention {b}x{s}x{d} kv{kvh} sk{sk}", out.view(b, s, d), want, fmt.tol(5e-3))
+    assert_close_sliced(f"fused cross-attention {b}x{s}x{d} kv{kvh} sk{sk} per (sequence, query, head)", out.view(b, s, h, 64), want.view(b, s, h, 64),
+                        fmt.tol(5e-3), (0, 1, 2), fmt.round)
 
 
 @pytest.mark.parametrize("fmt", FORMATS, ids=repr)
@@ -318,21 +408,38 @@ def test_qkv_rope(dev, variant, s, s_pad, fmt):
     freqs = odit.rotary_freqs(inv_freq, s)
     q, k = odit.apply_rotary(q, freqs), odit.apply_rotary(k, freqs)
     ad, wd, fd = a.to(dev), w.to(dev), inv_freq.to(dev)
-    qd = torch.full((b, h, s_pad, 64), float("nan"), dtype=fmt.dtype, device=dev)
-    kd = torch.full_like(qd, float("nan"))
-    vtd = torch.full((b, h, 64, s_pad), float("nan"), dtype=fmt.dtype, device=dev)
-    scratch = torch.empty((2 * s * 16,), dtype=torch.float32, device=dev)
+    guards, (qd, kd, vtd, scratch) = _qkv_outputs(dev, fmt, b, h, s, s_pad, 64)
     _hip.check(fmt.fn(lib, "sat_qkv_rope_bf16")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(fd), _hip.ptr(qd), _hip.ptr(kd), _hip.ptr(vtd),
                                                 _hip.ptr(scratch), b, s, s_pad, d, variant, _hip.stream()))
+    _check_qkv_outputs(guards)
     assert_close("rope q", qd[:, :, :s], q, fmt.tol(4e-3))
+    assert_close_sliced("rope q per (sequence, head, token)", qd[:, :, :s], q, fmt.tol(4e-3), (0, 1, 2), fmt.round)
     vtd = vtd[..., _vt_perm(s_pad).to(vtd.device)]      # undo the key permutation of the V^T layout
     for i in range(b):     # key-side tensors of sequence i start at row/column (i*s) & 3
         ob = (i * s) & 3
         assert_close("rope k", kd[i, :, ob:ob + s], k[i], fmt.tol(4e-3))
         assert_close("v^T", vtd[i, :, :, ob:ob + s], v[i].transpose(1, 2), fmt.tol(4e-3))
+        assert_close_sliced("rope k per (head, token)", kd[i, :, ob:ob + s], k[i], fmt.tol(4e-3), (0, 1), fmt.round)
+        assert_close_sliced("v^T per (head, key column)", vtd[i, :, :, ob:ob + s], v[i].transpose(1, 2), fmt.tol(4e-3), (0, 2), fmt.round)
         assert (kd[i, :, :ob] == 0).all() and (kd[i, :, ob + s:] == 0).all(), "K pads must be zero"
         assert (vtd[i, :, :, :ob] == 0).all() and (vtd[i, :, :, ob + s:] == 0).all(), "V^T pads must be zero"
     assert (qd[:, :, s:] == 0).all(), "Q pads must be zero"
+
+
+def _qkv_outputs(dev, fmt, b, h, s, s_pad, dh):
+    """q, k [b, h, s_pad, dh], V^T [b, h, dh, s_pad] and the rotation scratch, each between guard bands (the contract writes every element:
+    pads are zero) -> (guards, (q, k, vt, scratch))"""
+    qg, kg = guarded((b, h, s_pad, dh), fmt.dtype, dev, name="q"), guarded((b, h, s_pad, dh), fmt.dtype, dev, name="k")
+    vg = guarded((b, h, dh, s_pad), fmt.dtype, dev, name="v^T")
+    sg = guarded((2 * s * (dh // 4),), torch.float32, dev, name="rope scratch")
+    return (qg, kg, vg, sg), (qg.t, kg.t, vg.t, sg.t)
+
+
+def _check_qkv_outputs(guards):
+    for g_ in guards:
+        g_.check()
+    for g_ in guards[:3]:          # (the rotation scratch is no output: only its guards count)
+        g_.assert_written()
 
 
 def _ln_fold_producer(dev, m, d, k, variant, seed=40, fmt=FORMATS[0], x_scale=2.0):
@@ -343,9 +450,10 @@ def _ln_fold_producer(dev, m, d, k, variant, seed=40, fmt=FORMATS[0], x_scale=2.
     bias = _rand((d,), seed + 2)
     x0 = _rand((m, d), seed + 3, x_scale) + 0.3       # rows with a mean: the fold has to subtract it
     want = a.float() @ w.float().T + bias + x0
-    ad, wd, bd, cd = a.to(dev), w.to(dev), bias.to(dev), x0.to(dev)
-    xb = torch.full((m, d), float("nan"), dtype=fmt.dtype, device=dev)
-    part = torch.full((m, d // 64, 2), float("nan"), dtype=torch.float32, device=dev)
+    ad, wd, bd = a.to(dev), w.to(dev), bias.to(dev)
+    cg = guarded((m, d), torch.float32, dev, init=x0, name="c")
+    xg, pg = guarded((m, d), fmt.dtype, dev, name="xb"), guarded((m, d // 64, 2), torch.float32, dev, name="ln_part", pitch=2 * (d // 64))
+    cd, xb, part = cg.t, xg.t, pg.t
     if variant & 0x10000:
         ws, ws_bytes = _split_ws(dev, m, d, k, variant)
         _hip.check(fmt.fn(lib, "sat_gemm_resid_ln_bf16_ws")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(bd), _hip.ptr(cd), _hip.ptr(xb), _hip.ptr(part), m, d, k,
@@ -353,11 +461,16 @@ def _ln_fold_producer(dev, m, d, k, variant, seed=40, fmt=FORMATS[0], x_scale=2.
     else:
         _hip.check(fmt.fn(lib, "sat_gemm_resid_ln_bf16")(_hip.ptr(ad), _hip.ptr(wd), _hip.ptr(bd), _hip.ptr(cd), _hip.ptr(xb), _hip.ptr(part), m, d, k,
                                                          variant, _hip.stream()))
+    for g_ in (cg, xg, pg):
+        g_.check().assert_written()
     assert_close(f"ln-fold producer v{variant}", cd, want, 1e-3)
+    assert_close_rows_blocks(f"ln-fold producer v{variant}", cd, want, 1e-3)
     assert torch.equal(xb, cd.clamp(-65504.0, 65504.0).to(fmt.dtype)), "xb must be the 16-bit rounding (fp16: saturating) of the fp32 rows just written"
     blocks = xb.float().view(m, d // 64, 64).double()
     assert_close("ln-fold partial sums", part[..., 0], blocks.sum(-1), 1e-5)
     assert_close("ln-fold partial squares", part[..., 1], (blocks * blocks).sum(-1), 1e-5)
+    assert_close_sliced("ln-fold partial sums per row", part[..., 0], blocks.sum(-1), 1e-5, (0,))
+    assert_close_sliced("ln-fold partial squares per row", part[..., 1], (blocks * blocks).sum(-1), 1e-5, (0,))
     return cd, xb, part
 
 
@@ -387,15 +500,19 @@ def test_ln_fold_swiglu(dev, prod, cons, m, fmt):
     beta = 0.1 * _rand((d,), 52)
     bias = 0.1 * _rand((2 * inner,), 53)
     wd, gd, bd, bbd = w.to(dev), gamma.to(dev), beta.to(dev), bias.to(dev)
-    wp = torch.empty((2 * inner, d), dtype=fmt.dtype, device=dev)
-    c12 = torch.empty((4 * inner,), dtype=torch.float32, device=dev)
-    out = torch.full((m, inner), float("nan"), dtype=fmt.dtype, device=dev)
+    wpg, cg = guarded((2 * inner, d), fmt.dtype, dev, name="wp"), guarded((4 * inner,), torch.float32, dev, name="c12")
+    og = guarded((m, inner), fmt.dtype, dev, name="out")
+    wp, c12, out = wpg.t, cg.t, og.t
     _hip.check(fmt.fn(lib, "sat_gemm_swiglu_ln_bf16")(_hip.ptr(xb), _hip.ptr(part), _hip.ptr(wd), _hip.ptr(gd), _hip.ptr(bd), _hip.ptr(bbd),
                                                       _hip.ptr(wp), _hip.ptr(c12), _hip.ptr(out), m, 2 * inner, d, cons, _hip.stream()))
+    for g_ in (wpg, cg, og):
+        g_.check().assert_written()
     val, gate = _ln_fold_reference(xb, w, gamma, beta, bias, fmt).chunk(2, dim=-1)
     assert_close("ln-fold swiglu vs same arithmetic", out, val * F.silu(gate), fmt.tol(4e-3))
+    assert_close_rows_blocks("ln-fold swiglu vs same arithmetic", out, val * F.silu(gate), fmt.tol(4e-3), fmt.round)
     val, gate = F.linear(F.layer_norm(cd.cpu(), (d,), gamma, beta, eps=1e-5), w, bias).chunk(2, dim=-1)
     assert_close("ln-fold swiglu vs fp32 LayerNorm + Linear", out, val * F.silu(gate), fmt.tol(1e-2))
+    assert_close_rows_blocks("ln-fold swiglu vs fp32 LayerNorm + Linear", out, val * F.silu(gate), fmt.tol(1e-2), fmt.round)
 
 
 @pytest.mark.parametrize("row_mean,outlier", [(0.0, 0.0), (8.0, 0.0), (30.0, 0.0), (0.0, 60.0)])
@@ -422,19 +539,20 @@ def test_ln_fold_rows_with_common_mode(dev, row_mean, outlier):
     xb = xd.to(torch.bfloat16)
     blocks = xb.float().view(m, d // 64, 64)
     part = torch.stack([blocks.sum(-1), (blocks * blocks).sum(-1)], -1).contiguous()
-    wp = torch.empty((2 * inner, d), dtype=torch.bfloat16, device=dev)
-    c12 = torch.empty((4 * inner,), dtype=torch.float32, device=dev)
-    out_f = torch.full((m, inner), float("nan"), dtype=torch.bfloat16, device=dev)
+    wpg, cg, ofg = guarded((2 * inner, d), torch.bfloat16, dev, name="wp"), guarded((4 * inner,), torch.float32, dev, name="c12"), guarded((m, inner), torch.bfloat16, dev, name="out (fold)")
+    wp, c12, out_f = wpg.t, cg.t, ofg.t
     _hip.check(lib.sat_gemm_swiglu_ln_bf16(_hip.ptr(xb), _hip.ptr(part), _hip.ptr(wd), _hip.ptr(gd), _hip.ptr(bd), _hip.ptr(bbd), _hip.ptr(wp),
                                            _hip.ptr(c12), _hip.ptr(out_f), m, 2 * inner, d, 0, _hip.stream()))
     # three-kernel plan: LayerNorm kernel (fp32 statistics of the fp32 rows, bf16 output) -> SwiGLU GEMM
-    y = torch.empty((m, d), dtype=torch.bfloat16, device=dev)
+    yg = guarded((m, d), torch.bfloat16, dev, name="y")
+    y = yg.t
     _hip.check(lib.sat_layernorm_bf16(_hip.ptr(xd), _hip.ptr(gd), _hip.ptr(bd), _hip.ptr(y), m, d, _hip.stream()))
-    wp2 = torch.empty((2 * inner, d), dtype=torch.bfloat16, device=dev)
-    bp2 = torch.empty((2 * inner,), dtype=torch.float32, device=dev)
-    out_s = torch.full((m, inner), float("nan"), dtype=torch.bfloat16, device=dev)
+    wpg2, bpg2, osg = guarded((2 * inner, d), torch.bfloat16, dev, name="wp"), guarded((2 * inner,), torch.float32, dev, name="bp"), guarded((m, inner), torch.bfloat16, dev, name="out (three kernels)")
+    wp2, bp2, out_s = wpg2.t, bpg2.t, osg.t
     _hip.check(lib.sat_gemm_swiglu_bf16(_hip.ptr(y), _hip.ptr(wd), _hip.ptr(bbd), _hip.ptr(wp2), _hip.ptr(bp2), _hip.ptr(out_s), m, 2 * inner, d, 0,
                                         _hip.stream()))
+    for g_ in (wpg, cg, ofg, yg, wpg2, bpg2, osg):
+        g_.check().assert_written()
     e_f, e_s = rel_l2(out_f, want), rel_l2(out_s, want)
     var = x.var(-1, unbiased=False).mean().item()
     ratio = (1.0 + (x.mean(-1) ** 2).mean().item() / var) ** 0.5 if not outlier else (x.pow(2).mean().item() / _rand((m, d), 90).var().item()) ** 0.5
@@ -471,22 +589,25 @@ def test_ln_fold_qkv_rope(dev, prod, cons, s, s_pad, fmt):
     same = split(_ln_fold_reference(xb, w, gamma, beta, None, fmt))
     plain = split(F.linear(F.layer_norm(cd.cpu(), (d,), gamma, beta, eps=1e-5), w))
     wd, gd, bd, fd = w.to(dev), gamma.to(dev), beta.to(dev), inv_freq.to(dev)
-    wp = torch.empty((3 * d, d), dtype=fmt.dtype, device=dev)
-    c12 = torch.empty((6 * d,), dtype=torch.float32, device=dev)
-    qd = torch.full((b, h, s_pad, 64), float("nan"), dtype=fmt.dtype, device=dev)
-    kd = torch.full_like(qd, float("nan"))
-    vtd = torch.full((b, h, 64, s_pad), float("nan"), dtype=fmt.dtype, device=dev)
-    scratch = torch.empty((2 * s * 16,), dtype=torch.float32, device=dev)
+    wpg, cg = guarded((3 * d, d), fmt.dtype, dev, name="wp"), guarded((6 * d,), torch.float32, dev, name="c12")
+    wp, c12 = wpg.t, cg.t
+    guards, (qd, kd, vtd, scratch) = _qkv_outputs(dev, fmt, b, h, s, s_pad, 64)
     _hip.check(fmt.fn(lib, "sat_qkv_rope_ln_bf16")(_hip.ptr(xb), _hip.ptr(part), _hip.ptr(wd), _hip.ptr(gd), _hip.ptr(bd), _hip.ptr(wp),
                                                    _hip.ptr(c12), _hip.ptr(fd), _hip.ptr(qd), _hip.ptr(kd), _hip.ptr(vtd), _hip.ptr(scratch),
                                                    b, s, s_pad, d, cons, _hip.stream()))
+    for g_ in (wpg, cg):
+        g_.check().assert_written()
+    _check_qkv_outputs(guards)
     vtd = vtd[..., _vt_perm(s_pad).to(vtd.device)]
-    for (q, k, v), tol in ((same, fmt.tol(4e-3)), (plain, fmt.tol(1e-2))):
+    for which, (q, k, v), tol in (("same arithmetic", same, fmt.tol(4e-3)), ("fp32 LayerNorm + Linear", plain, fmt.tol(1e-2))):
         assert_close("ln-fold q", qd[:, :, :s], q, tol)
+        assert_close_sliced(f"ln-fold q vs {which} per (sequence, head, token)", qd[:, :, :s], q, tol, (0, 1, 2), fmt.round)
         for i in range(b):
             ob = (i * s) & 3
             assert_close("ln-fold k", kd[i, :, ob:ob + s], k[i], tol)
             assert_close("ln-fold v^T", vtd[i, :, :, ob:ob + s], v[i].transpose(1, 2), tol)
+            assert_close_sliced(f"ln-fold k vs {which} per (head, token)", kd[i, :, ob:ob + s], k[i], tol, (0, 1), fmt.round)
+            assert_close_sliced(f"ln-fold v^T vs {which} per (head, key column)", vtd[i, :, :, ob:ob + s], v[i].transpose(1, 2), tol, (0, 2), fmt.round)
     assert (qd[:, :, s:] == 0).all(), "Q pads must be zero"
 
 
@@ -497,16 +618,20 @@ def test_snake_vae_int16(dev):
     al, be = _rand((5,), 18, 0.3), _rand((5,), 19, 0.3)
     want = oob.snake_beta(x, al, be)
     xd, ad, bd = x.to(dev), al.to(dev), be.to(dev)
-    y = torch.empty_like(xd)
+    yg = guarded((2, 5, 333), torch.float32, dev, name="y")
+    y = yg.t
     _hip.check(lib.sat_snake_beta(_hip.ptr(xd), _hip.ptr(ad), _hip.ptr(bd), _hip.ptr(y), 2, 5, 333, _hip.stream()))
+    yg.check().assert_written()
     assert_close("snake", y, want, 1e-5)
 
     ms = _rand((2, 8, 50), 20)
     nz = _rand((2, 4, 50), 21)
     want = oob.vae_sample(ms, nz)
-    z = torch.empty((2, 4, 50), device=dev)
+    zg = guarded((2, 4, 50), torch.float32, dev, name="z")
+    z = zg.t
     msd, nzd = ms.to(dev), nz.to(dev)     # keep the device tensors alive across the call
     _hip.check(lib.sat_vae_sample(_hip.ptr(msd), _hip.ptr(nzd), _hip.ptr(z), 2, 4, 50, _hip.stream()))
+    zg.check().assert_written()
     assert_close("vae_sample", z, want, 1e-6)
 
     from stable_audio_tools.utils.audio_utils import float_to_int16_audio
@@ -564,9 +689,11 @@ def test_cfg_combine_and_sampler_update(dev):
         cfg = uncond + (cond - uncond) * 7.0
         if scale_phi:
             cfg = scale_phi * (cfg * (cond.std(dim=1, keepdim=True) / cfg.std(dim=1, keepdim=True))) + (1 - scale_phi) * cfg
-        out = torch.empty((b, c, t), device=dev)
+        og = guarded((b, c, t), torch.float32, dev, name="out")
+        out = og.t
         mod = mo.to(dev)
         _hip.check(lib.sat_cfg_combine(_hip.ptr(mod), _hip.ptr(out), b, c, t, 7.0, scale_phi, _hip.stream()))
+        og.check().assert_written()
         assert_close(f"cfg combine phi={scale_phi}", out, cfg, 1e-5)
 
     # the fused (a,b,c1,c2,cn) update must reproduce the multistep form of the oracle sampler on a linear denoiser
@@ -603,6 +730,27 @@ def _deq8(q_bytes, scale):
     return q_bytes.view(torch.float8_e4m3fn).to(torch.float32) * scale[:, None]
 
 
+def _quant_rows_fp8(dev, xd):
+    """sat_quant_rows_fp8 into guarded buffers -> (bytes [rows, k], scales [rows]).  Bytes carry no NaN to find an unwritten element by:
+    every one is compared with torch's e4m3 conversion at the kernel's own scale (the kernel multiplies by 1 / scale: one code at the most
+    on a rounding boundary, and a sentinel byte that survived is further off than that)."""
+    _hip, lib = _lib()
+    rows, k = xd.shape
+    qg, sg = guarded((rows, k), torch.uint8, dev, name="e4m3 bytes"), guarded((rows,), torch.float32, dev, name="row scales")
+    _hip.check(lib.sat_quant_rows_fp8(_hip.ptr(xd), _hip.ptr(qg.t), _hip.ptr(sg.t), rows, k, _hip.stream()))
+    qg.check()
+    sg.check().assert_written()
+    _check_e4m3_bytes("fp8 rows", qg.t, xd.cpu() * (1.0 / sg.t.cpu())[:, None])
+    return qg.t, sg.t
+
+
+def _check_e4m3_bytes(name, got_bytes, scaled):
+    want = scaled.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    dist = e4m3_code_distance(got_bytes, want)
+    assert int(dist.max()) <= 1, f"{name}: {int((dist > 1).sum())} bytes are more than one e4m3 code from the reference, the first at {tuple(int(i) for i in (dist > 1).nonzero()[0])}"
+    assert (dist > 0).float().mean().item() < 1e-2, f"{name}: {(dist > 0).float().mean().item():.2%} of the bytes differ from the reference (rounding boundaries only)"
+
+
 def test_fp8_quant_and_layernorm(dev):
     """sat_quant_rows_fp8 / sat_layernorm_fp8 (BASELINE config 5 building blocks) against torch's e4m3 conversion: the bytes must
     be identical except where x / scale sits on a rounding boundary (kernel multiplies by 1/scale), and never off by more than
@@ -613,9 +761,7 @@ def test_fp8_quant_and_layernorm(dev):
         x = _rand((rows, k), 200, 3.0)
         x[1] = 0
         xd = x.to(dev)
-        q = torch.empty((rows, k), dtype=torch.uint8, device=dev)
-        sc = torch.empty((rows,), dtype=torch.float32, device=dev)
-        _hip.check(lib.sat_quant_rows_fp8(_hip.ptr(xd), _hip.ptr(q), _hip.ptr(sc), rows, k, _hip.stream()))
+        q, sc = _quant_rows_fp8(dev, xd)
         amax = x.abs().amax(dim=1)
         want_sc = torch.where(amax > 0, amax * (1.0 / 448.0), torch.ones_like(amax))
         assert torch.allclose(sc.cpu(), want_sc, rtol=1e-6)
@@ -627,9 +773,12 @@ def test_fp8_quant_and_layernorm(dev):
     x = _rand((m, d), 201, 2.0)
     gm, bt = 1 + 0.1 * _rand((d,), 202), 0.1 * _rand((d,), 203)
     xd, gd, bd = x.to(dev), gm.to(dev), bt.to(dev)
-    q = torch.empty((m, d), dtype=torch.uint8, device=dev)
-    sc = torch.empty((m,), dtype=torch.float32, device=dev)
+    qg, sg = guarded((m, d), torch.uint8, dev, name="e4m3 bytes"), guarded((m,), torch.float32, dev, name="row scales")
+    q, sc = qg.t, sg.t
     _hip.check(lib.sat_layernorm_fp8(_hip.ptr(xd), _hip.ptr(gd), _hip.ptr(bd), _hip.ptr(q), _hip.ptr(sc), m, d, _hip.stream()))
+    qg.check()
+    sg.check().assert_written()
+    _check_e4m3_bytes("layernorm fp8", q, F.layer_norm(x, (d,), gm, bt) * (1.0 / sc.cpu())[:, None])
     want = odit.fp8_rows(F.layer_norm(x, (d,), gm, bt))
     assert_close("layernorm fp8", _deq8(q.cpu(), sc.cpu()), want, 3e-3)
 
@@ -655,17 +804,16 @@ def test_gemm_fp8(dev, variant, m, n, k, plain):
     bias = _rand((n,), 212)
     c0 = _rand((m, n), 213)
     ad, wd = a.to(dev), w.to(dev)
-    a8 = torch.empty((m, k), dtype=torch.uint8, device=dev)
-    w8 = torch.empty((n, k), dtype=torch.uint8, device=dev)
-    sa = torch.empty((m,), dtype=torch.float32, device=dev)
-    sw = torch.empty((n,), dtype=torch.float32, device=dev)
-    _hip.check(lib.sat_quant_rows_fp8(_hip.ptr(ad), _hip.ptr(a8), _hip.ptr(sa), m, k, _hip.stream()))
-    _hip.check(lib.sat_quant_rows_fp8(_hip.ptr(wd), _hip.ptr(w8), _hip.ptr(sw), n, k, _hip.stream()))
+    a8, sa = _quant_rows_fp8(dev, ad)
+    w8, sw = _quant_rows_fp8(dev, wd)
     want = _deq8(a8.cpu(), sa.cpu()) @ _deq8(w8.cpu(), sw.cpu()).T + bias + c0
-    cd, bd = c0.to(dev), bias.to(dev)
+    cg = guarded((m, n), torch.float32, dev, init=c0, name="c")
+    cd, bd = cg.t, bias.to(dev)
     _hip.check(lib.sat_gemm_fp8_f32(_hip.ptr(a8), _hip.ptr(sa), _hip.ptr(w8), _hip.ptr(sw), _hip.ptr(bd), _hip.ptr(cd), m, n, k, 1,
                                     variant | plain, _hip.stream()))
+    cg.check().assert_written()
     assert_close(f"gemm fp8 v{variant} {m}x{n}x{k}", cd, want, 1e-4)
+    assert_close_rows_blocks(f"gemm fp8 v{variant} {m}x{n}x{k}", cd, want, 1e-4)
     full = a @ w.T + bias + c0
     assert rel_l2(cd, full) < 5e-2, "e4m3 operands: a few percent from the fp32 product"
 
@@ -694,17 +842,27 @@ def test_gemm_mxfp8(dev, variant, m, n, k):
     w = _rand((n, k), 221) * 0.05 + torch.linspace(-0.02, 0.03, n)[:, None]
     bias, c0 = _rand((n,), 222), _rand((m, n), 223)
     ad, wd = a.to(dev), w.to(dev)
-    a8 = torch.empty((m, k), dtype=torch.uint8, device=dev)
-    asc = torch.empty((m, k // 32), dtype=torch.uint8, device=dev)
-    w8 = torch.empty((n, k), dtype=torch.uint8, device=dev)
-    sw = torch.empty((n,), dtype=torch.float32, device=dev)
+    ag, asg = guarded((m, k), torch.uint8, dev, name="mx e4m3 bytes"), guarded((m, k // 32), torch.uint8, dev, name="E8M0 scales")
+    a8, asc = ag.t, asg.t
     _hip.check(lib.sat_quant_mx_rows_fp8(_hip.ptr(ad), _hip.ptr(a8), _hip.ptr(asc), m, k, _hip.stream()))
-    _hip.check(lib.sat_quant_rows_fp8(_hip.ptr(wd), _hip.ptr(w8), _hip.ptr(sw), n, k, _hip.stream()))
+    ag.check()
+    asg.check()
+    w8, sw = _quant_rows_fp8(dev, wd)
+    # the bytes against the reference (no NaN marks an unwritten byte): the scale is the smallest power of two with amax / scale <= 448
+    # (0 for an all-zero block), the values are torch's e4m3 conversion at that scale -- a power of two: exact, identical bytes
+    amax = a.view(m, k // 32, 32).abs().amax(-1)
+    sc2 = torch.pow(2.0, asc.cpu().to(torch.float64) - 127.0)
+    t = amax.double() * (1.0 / 448.0)
+    assert bool(((sc2 >= t * (1 - 1e-6)) & (sc2 < 2 * t * (1 + 1e-6)))[amax > 0].all()) and bool((asc.cpu()[amax == 0] == 0).all()), "E8M0 scales: not ceil(log2(amax / 448))"
+    _check_e4m3_bytes("mxfp8 rows", a8, (a.view(m, k // 32, 32).double() / sc2[:, :, None]).float().view(m, k))
     a_deq = _deq_mx(a8.cpu(), asc.cpu())
     assert_close("mxfp8 producer vs oracle", a_deq, odit.mxfp8_blocks(a), 1e-3)
     assert (asc.cpu()[0, :2] == 0).all() and (a8.cpu()[0, :64] == 0).all()
     want = a_deq @ _deq8(w8.cpu(), sw.cpu()).T + bias + c0
-    cd, bd = c0.to(dev), bias.to(dev)
+    cg = guarded((m, n), torch.float32, dev, init=c0, name="c")
+    cd, bd = cg.t, bias.to(dev)
     _hip.check(lib.sat_gemm_mxfp8_f32(_hip.ptr(a8), _hip.ptr(asc), _hip.ptr(w8), _hip.ptr(sw), _hip.ptr(bd), _hip.ptr(cd), m, n, k, 1,
                                       variant, _hip.stream()))
+    cg.check().assert_written()
     assert_close(f"gemm mxfp8 v{variant} {m}x{n}x{k}", cd, want, 1e-4)
+    assert_close_rows_blocks(f"gemm mxfp8 v{variant} {m}x{n}x{k}", cd, want, 1e-4)
