@@ -97,10 +97,28 @@ struct sat_dit_plan {
     // optional diagnostics of the residual stream (sat_dit_debug): [depth][3 updates][4] floats, overwritten by every forward while enabled
     DevBuf dbg_buf;
     float* dbg = nullptr;
+    // optional fp16 range report of the 16-bit buffers (sat_dit_range_report): [depth][SAT_DIT_RANGE_SLOTS] records, accumulated by every forward
+    // and sat_dit_prepare_context while enabled, until reset or disabled
+    DevBuf rr_buf;
+    sat_range_record* rr = nullptr;
 };
 static const int kProfMaxPairs = 4096;
 
 namespace {
+
+// Slots of the range report per layer, in the order of sat_dit_range_slot_name
+enum RangeSlot { RS_A_QKV, RS_Q, RS_K, RS_V, RS_ATTN_OUT, RS_A_CROSS_Q, RS_CROSS_Q, RS_CROSS_K, RS_CROSS_V, RS_CROSS_ATTN_OUT, RS_A_FF, RS_FF_HIDDEN };
+const char* const kRangeSlotNames[SAT_DIT_RANGE_SLOTS] = {"a_qkv", "q", "k", "v", "attn_out", "a_cross_q", "cross_q", "cross_k", "cross_v",
+                                                           "cross_attn_out", "a_ff", "ff_hidden"};
+
+// One reduction of the range report over `scanned` contiguous 16-bit elements at buf, into slot `slot` of layer l; `logical` of them are values
+// of the model (the rest: zero pads of the layout).  Launched right behind the buffer's producer: the next layer reuses the buffer.  Nothing
+// without the report
+int range_stats(const sat_dit_plan* p, int l, int slot, const op_t* buf, size_t scanned, size_t logical, hipStream_t s) {
+    if (!p->rr) return 0;
+    return sat_launch_range_stats(buf, p->f16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16, 1, (int64_t)scanned, (int64_t)scanned, logical,
+                                  p->rr + (size_t)l * SAT_DIT_RANGE_SLOTS + slot, s);
+}
 
 // Rows of one sequence in the residual stream: [P prepend tokens | global token | T latent frames] (dit.py:185-197), no global
 // token under adaLN (P is 0 there: sat_dit_plan_set_extra_conditioning rejects adaLN + prepend)
@@ -368,6 +386,12 @@ struct Forward {
         return p->dbg ? glue_resid_stats(w.X, rows, D, p->dbg + ((size_t)l * 3 + slot) * 4, s) : 0;
     }
 
+    int range(int l, int slot, const op_t* buf, size_t scanned, size_t logical) const { return range_stats(p, l, slot, buf, scanned, logical, s); }
+    // q / k / v of `seqs` sequences behind their head split: the scan covers the Spad - S zero pad rows of every head
+    int range_heads(int l, int slot, const op_t* buf, int seqs) const {
+        return range(l, slot, buf, (size_t)seqs * H * Spad * p->hd, (size_t)seqs * S * D);
+    }
+
     int block(int l) const;
     int block_f32(int l) const;
     int attention_hd128(int l) const;
@@ -409,6 +433,7 @@ int Forward::attention_hd128(int l) const {
     const float* m = mod(l);
     const int f16 = p->f16, qn = p->qk_norm ? 16 : 0;
     SAT_TRY(layernorm(L.qkv, L.pre_g, L.pre_b, M, true, m, m ? m + D : nullptr));
+    SAT_TRY(range(l, RS_A_QKV, w.A, (size_t)M * D, (size_t)M * D));
     GemmArgs g = gemm(L.qkv, w.A, M);
     g.C = w.qkv32; g.ldc = 3 * D;
     SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
@@ -418,10 +443,15 @@ int Forward::attention_hd128(int l) const {
     he.parts = 3; he.heads = H; he.S = S; he.Spad = Spad;
     he.rope_cos = p->rope_cos; he.rope_sin = p->rope_sin;
     SAT_TRY(sat_launch_head_split_hd128(w.qkv32, he, bf, s, f16));
+    SAT_TRY(range_heads(l, RS_Q, w.Q, bf));
+    SAT_TRY(range_heads(l, RS_K, w.K, bf));
+    SAT_TRY(range_heads(l, RS_V, w.Vt, bf));
     SAT_TRY(sat_launch_attention_hd128(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, f16));
+    SAT_TRY(range(l, RS_ATTN_OUT, w.AO, (size_t)M * D, (size_t)M * D));
     SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
     if (bc > 0) {      // (the sequences behind bc have an all-zero context: Forward::block)
         SAT_TRY(layernorm(L.cq, L.cross_g, L.cross_b, Mc, false, nullptr, nullptr));
+        SAT_TRY(range(l, RS_A_CROSS_Q, w.A, (size_t)Mc * D, (size_t)Mc * D));
         g = gemm(L.cq, w.A, Mc);
         g.C = w.qkv32; g.ldc = D;
         SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
@@ -429,9 +459,11 @@ int Forward::attention_hd128(int l) const {
         he.out[0] = w.Q; he.kind[0] = 8 | qn; he.qscale = SAT_ATTN_QSCALE_HD128;
         he.parts = 1; he.heads = H; he.S = S; he.Spad = Spad;
         SAT_TRY(sat_launch_head_split_hd128(w.qkv32, he, bc, s, f16));
+        SAT_TRY(range_heads(l, RS_CROSS_Q, w.Q, bc));
         const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * 128;
         SAT_TRY(sat_launch_attention_hd128(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, w.AO, bc, H, p->kvh_cross, S, p->ctx_lc, Spad,
                                            p->ctx_lcpad, s, f16));
+        SAT_TRY(range(l, RS_CROSS_ATTN_OUT, w.AO, (size_t)Mc * D, (size_t)Mc * D));
         SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
     }
     return 0;
@@ -448,13 +480,18 @@ int Forward::block(int l) const {
     }
     // ---- self-attention branch (transformer.py:692)
     SAT_TRY(layernorm(L.qkv, L.pre_g, L.pre_b, M, true, m, m ? m + D : nullptr));
+    SAT_TRY(range(l, RS_A_QKV, w.A, (size_t)M * D, (size_t)M * D));
     GemmArgs g = gemm(L.qkv, w.A, M);
     g.heads.out[0] = w.Q; g.heads.out[1] = w.K; g.heads.out[2] = w.Vt;
     g.heads.kind[0] = 2 | 8 | qn; g.heads.kind[1] = 2 | 4 | qn; g.heads.kind[2] = 1 | 4; g.heads.qscale = SAT_ATTN_QSCALE;
     g.heads.parts = 3; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
     g.heads.rope_cos = p->rope_cos; g.heads.rope_sin = p->rope_sin;
     SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
+    SAT_TRY(range_heads(l, RS_Q, w.Q, bf));
+    SAT_TRY(range_heads(l, RS_K, w.K, bf));
+    SAT_TRY(range_heads(l, RS_V, w.Vt, bf));
     SAT_TRY(sat_launch_attention(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, mx_scales(L.o), 1.0f, f16));
+    SAT_TRY(range(l, RS_ATTN_OUT, w.AO, (size_t)M * D, (size_t)M * D));
     SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
     // ---- cross-attention branch (transformer.py:694-695).  Sequences whose context is all-zero (the
     // unconditional CFG half, dit.py:294-300) get k = v = 0 from the bias-free to_cond_embed / to_kv, hence an
@@ -462,6 +499,7 @@ int Forward::block(int l) const {
     // the branch runs only on the first `bc` sequences (rows are ordered by sequence).
     if (bc > 0) {
         SAT_TRY(layernorm(L.cq, L.cross_g, L.cross_b, Mc, false, nullptr, nullptr));
+        SAT_TRY(range(l, RS_A_CROSS_Q, w.A, (size_t)Mc * D, (size_t)Mc * D));
         g = gemm(L.cq, w.A, Mc);
         g.heads.out[0] = w.Q; g.heads.kind[0] = 8 | qn; g.heads.qscale = SAT_ATTN_QSCALE;
         g.heads.parts = 1; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
@@ -476,9 +514,12 @@ int Forward::block(int l) const {
             g.heads.xa_kvh = p->kvh_cross; g.heads.xa_sk = p->ctx_lc; g.heads.xa_sk_pad = p->ctx_lcpad;
         }
         SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
-        if (!fuse)
+        if (!fuse) {      // (the fused launch keeps Q in registers: its slot of the range report stays empty)
+            SAT_TRY(range_heads(l, RS_CROSS_Q, w.Q, bc));
             SAT_TRY(sat_launch_attention(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, w.AO, bc, H, p->kvh_cross, S, p->ctx_lc, Spad,
                                          p->ctx_lcpad, s, mx_scales(L.co), 1.0f, f16));
+        }
+        SAT_TRY(range(l, RS_CROSS_ATTN_OUT, w.AO, (size_t)Mc * D, (size_t)Mc * D));
         SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
     }
     return feed_forward(l);
@@ -489,6 +530,7 @@ int Forward::feed_forward(int l) const {
     const LayerW& L = p->layers[l];
     const float* m = mod(l);
     SAT_TRY(layernorm(L.ff1, L.ff_g, L.ff_b, M, true, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr));
+    SAT_TRY(range(l, RS_A_FF, w.A, (size_t)M * D, (size_t)M * D));
     GemmArgs g = gemm(L.ff1, w.A, M);
     g.H = w.Hh;
     if (L.ff2.kind == PROJ_FP8_MX) { g.H8 = (unsigned char*)w.Hh; g.Hs = w.Hs; }          // FF-out's MXFP8 operand; otherwise the e4m3 GEMM writes a 16-bit hidden state
@@ -509,6 +551,7 @@ int Forward::feed_forward(int l) const {
         p->prof_n++;
         p->prof_m = g.M; p->prof_nn = g.N; p->prof_k = g.K;
     }
+    SAT_TRY(range(l, RS_FF_HIDDEN, w.Hh, (size_t)M * p->inner, (size_t)M * p->inner));
     return resid(L.ff2, w.Hh, M, m ? m + 5 * D : nullptr, l + 1 < p->cfg.depth, l, 2);      // nobody normalises the output of the last block
 }
 
@@ -756,6 +799,8 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
                 he.kind[0] = 4 | (p->qk_norm ? 16 : 0); he.kind[1] = 1 | 4; he.parts = 2; he.heads = p->kvh_cross;
                 he.S = lc; he.Spad = lcpad;
                 SAT_TRY(sat_launch_head_split_hd128(kv32, he, bf, s, p->f16));
+                SAT_TRY(range_stats(p, l, RS_CROSS_K, p->kc + l * per_layer, per_layer, (size_t)R * Dc, s));
+                SAT_TRY(range_stats(p, l, RS_CROSS_V, p->vct + l * per_layer, per_layer, (size_t)R * Dc, s));
                 continue;
             }
             g.heads.out[0] = p->kc + l * per_layer; g.heads.out[1] = p->vct + l * per_layer;
@@ -763,6 +808,9 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
             g.heads.S = lc; g.heads.Spad = lcpad;
             g.variant = 1;
             SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
+            // (the layer's whole cache: lcpad - lc zero pad keys per head beside the bf * lc * Dc values)
+            SAT_TRY(range_stats(p, l, RS_CROSS_K, p->kc + l * per_layer, per_layer, (size_t)R * Dc, s));
+            SAT_TRY(range_stats(p, l, RS_CROSS_V, p->vct + l * per_layer, per_layer, (size_t)R * Dc, s));
         }
     }
     p->ctx_bf = bf;
@@ -940,6 +988,49 @@ extern "C" int sat_dit_debug_read(sat_dit_plan* p, float* out_host, int32_t capa
     SAT_HIP(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }
+
+extern "C" int sat_dit_range_report(sat_dit_plan* p, int32_t enable) {
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "dit_range_report: null plan");
+    SAT_CHECK_ARG(enable >= 0 && enable <= 2, SAT_E_INVALID, "dit_range_report: enable must be 0 (off), 1 (on) or 2 (zero the records), got %d", enable);
+    if (enable == 0) {
+        if (!p->rr) return 0;
+        SAT_HIP(hipDeviceSynchronize());          // launches in flight still accumulate into the records
+        p->rr_buf.release();
+        p->rr = nullptr;
+        return 0;
+    }
+    // e4m3 plans quantise A / AO / Hh to bytes with scales beside them, the fp32 verification mode has no 16-bit buffer at all
+    SAT_CHECK_ARG(p->cfg.gemm_dtype == SAT_GEMM_BF16 || p->cfg.gemm_dtype == SAT_GEMM_FP16, SAT_E_UNSUPPORTED,
+                  "dit_range_report: the report reads 16-bit operand buffers (gemm_dtype bf16 or fp16), this plan has gemm_dtype %d", p->cfg.gemm_dtype);
+    SAT_CHECK_ARG(sat_launch_range_stats, SAT_E_UNSUPPORTED, "dit_range_report: built without the range statistics kernel");
+    const size_t bytes = (size_t)p->cfg.depth * SAT_DIT_RANGE_SLOTS * sizeof(sat_range_record);
+    if (enable == 2) {
+        SAT_CHECK_ARG(p->rr, SAT_E_STATE, "dit_range_report: the report is not enabled, there is nothing to zero");
+        SAT_HIP(hipDeviceSynchronize());
+        SAT_HIP(hipMemset(p->rr, 0, bytes));
+        return 0;
+    }
+    if (p->rr) return 0;          // already on: the records keep accumulating
+    SAT_TRY(p->rr_buf.reserve(bytes));
+    SAT_HIP(hipMemset(p->rr_buf.ptr, 0, bytes));
+    p->rr = (sat_range_record*)p->rr_buf.ptr;
+    return 0;
+}
+
+extern "C" int sat_dit_range_report_read(sat_dit_plan* p, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes,
+                                         sat_stream_t stream) {
+    SAT_CHECK_ARG(p && out_host, SAT_E_INVALID, "dit_range_report_read: null argument");
+    SAT_CHECK_ARG(record_bytes == sizeof(sat_range_record), SAT_E_INVALID,
+                  "dit_range_report_read: sat_range_record of %zu bytes; this library knows %zu", record_bytes, sizeof(sat_range_record));
+    const int n = p->cfg.depth * SAT_DIT_RANGE_SLOTS;
+    SAT_CHECK_ARG(capacity_records >= n, SAT_E_INVALID, "dit_range_report_read: room for %d records, need %d", capacity_records, n);
+    SAT_CHECK_ARG(p->rr, SAT_E_STATE, "dit_range_report_read: the report is not enabled (sat_dit_range_report)");
+    SAT_HIP(hipMemcpyAsync(out_host, p->rr, (size_t)n * sizeof(sat_range_record), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    SAT_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return 0;
+}
+
+extern "C" const char* sat_dit_range_slot_name(int32_t slot) { return slot >= 0 && slot < SAT_DIT_RANGE_SLOTS ? kRangeSlotNames[slot] : nullptr; }
 
 extern "C" int sat_cfg_combine(const float* model_out_dev, float* out_dev, int32_t b, int32_t c, int32_t t, float cfg_scale,
                                float scale_phi, sat_stream_t stream) {

@@ -693,6 +693,11 @@ struct OobPlan {
     std::vector<Block> blocks;
     Snake final_snake;
     op_t* zero_page = nullptr;
+    // optional fp16 range report (sat_oobleck_range_report): one record per activation tensor a run writes to the workspace, in launch order;
+    // the names are fixed by the blocks (oob_plan_create), the records exist while the report is on
+    std::vector<std::string> rr_names;
+    DevBuf rr_buf;
+    sat_range_record* rr = nullptr;
 };
 }  // namespace SAT_OPNS
 using SAT_OPNS::OobPlan;
@@ -895,6 +900,57 @@ void set_act(ConvArgs& a, op_t* out, const Snake& sn) {
     a.out_snk = out; a.act = sn.act; a.sn_a = sn.a; a.sn_ib = sn.ib;
 }
 
+// The range report of one run: the next record takes the contiguous tensor of n elements at buf, right behind the launch that wrote it (the
+// four workspace buffers are reused all along).  The order of the calls is the order of range_names
+struct Ranger {
+    const OobPlan* p;
+    hipStream_t s;
+    int next = 0;
+    bool on() const { return p->rr != nullptr; }
+    int operator()(const op_t* buf, size_t n) {
+        if (!on()) return 0;
+        SAT_CHECK_ARG(next < (int)p->rr_names.size(), SAT_E_STATE, "oobleck range report: more tensors than records (%d)", next);
+        return sat_launch_range_stats(buf, SAT_OP_IS_F32 ? SAT_GEMM_FP32X : SAT_OP_IS_F16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16, 1, (int64_t)n, (int64_t)n, n,
+                                      p->rr + next++, s);
+    }
+    int done() const {
+        SAT_CHECK_ARG(!on() || next == (int)p->rr_names.size(), SAT_E_STATE, "oobleck range report: %d tensors for %d records", next, (int)p->rr_names.size());
+        return 0;
+    }
+};
+
+// The records of a plan in launch order (sat_oobleck_range_report_name): the module path of the layer whose launch writes the tensor -- the
+// activated tensor the next convolution reads, then "<path>.raw" where the launch also keeps the un-activated sum for the next residual add
+std::vector<std::string> range_names(const sat_oobleck_cfg& c, const sat_oobleck_options& o) {
+    std::vector<std::string> n;
+    auto both = [&](const std::string& path, bool raw) {
+        n.push_back(path);
+        if (raw) n.push_back(path + ".raw");
+    };
+    auto unit = [&](const std::string& ru, int r) {
+        n.push_back(ru + "layers.1");
+        both(ru + "layers.3", r < 2);
+    };
+    const int nb = c.n_blocks;
+    if (c.is_decoder) {
+        n.push_back("input");
+        n.push_back("layers.0");
+        for (int bi = 0; bi < nb; ++bi) {
+            const std::string pf = "layers." + std::to_string(bi + 1) + ".";
+            both(pf + (o.nearest_upsample ? "layers.1.1" : "layers.1"), true);
+            for (int r = 0; r < 3; ++r) unit(pf + "layers." + std::to_string(2 + r) + ".", r);
+        }
+    } else {
+        both("layers.0", true);
+        for (int bi = 0; bi < nb; ++bi) {
+            const std::string pf = "layers." + std::to_string(bi + 1) + ".";
+            for (int r = 0; r < 3; ++r) unit(pf + "layers." + std::to_string(r) + ".", r);
+            both(pf + "layers.4", bi + 1 < nb);
+        }
+    }
+    return n;
+}
+
 #if !SAT_OP_IS_F32
 template <int BN, int WM, int WN, int NS>
 int launch_ru_fused(const RuArgs& a, int B, hipStream_t s) {
@@ -908,8 +964,9 @@ int launch_ru_fused(const RuArgs& a, int B, hipStream_t s) {
 #endif
 
 // one ResidualUnit (autoencoders.py:45-68): in S (snaked x) + R (raw x) -> R (raw x') and/or Sout (snake_next(x'))
+// With the range report on, every unit takes the two launches: the tensor between its convolutions then reaches memory (Y) and has a record
 int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const op_t* S, op_t* Y, op_t* Sout,
-           const Snake& next, bool need_raw, hipStream_t s) {
+           const Snake& next, bool need_raw, hipStream_t s, Ranger& rg) {
     static const int dil[3] = {1, 3, 9};
     ConvArgs a = base_args(blk.ru_c7[r], S, L, L);
     a.off0 = -3 * dil[r]; a.doff = dil[r];
@@ -919,7 +976,7 @@ int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const
     c.out_raw = need_raw ? R : nullptr;   // in place: each thread reads then writes its own elements
     set_act(c, Sout, next);
 #if !SAT_OP_IS_F32      // (fp32 build: the 128 x C intermediate would not fit next to the weight ring; two launches through Y)
-    if (C == 128 || C == 256) {      // the whole unit in one launch, the intermediate never leaves LDS
+    if ((C == 128 || C == 256) && !rg.on()) {      // the whole unit in one launch, the intermediate never leaves LDS
         RuArgs f{a, c};
         f.c7.out_snk = nullptr;
         f.c1.in = nullptr;
@@ -928,9 +985,12 @@ int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const
         return launch_ru_fused<256, 2, 4, 3>(f, B, s);
     }
 #endif
+    const size_t n = (size_t)B * L * C;
     SAT_TRY(launch_conv(a, B, s));
+    SAT_TRY(rg(Y, n));
     SAT_TRY(launch_conv(c, B, s));
-    return 0;
+    SAT_TRY(rg(Sout, n));
+    return need_raw ? rg(R, n) : 0;
 }
 
 }  // namespace
@@ -948,6 +1008,7 @@ int oob_plan_create(const sat_oobleck_cfg* cfg, const sat_oobleck_options* opt, 
     SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_create: out of host memory");
     p->cfg = *cfg;
     p->opt = *opt;
+    p->rr_names = range_names(*cfg, *opt);
     p->ratio = 1;
     for (int i = 0; i < cfg->n_blocks; ++i) {
         SAT_CHECK_ARG(cfg->strides[i] >= 1 && cfg->strides[i] <= 16 && cfg->c_mults[i] >= 1, SAT_E_UNSUPPORTED, "oobleck_plan_create: bad stride/c_mult");
@@ -991,6 +1052,8 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
     hipLaunchKernelGGL(cf_to_cl_kernel, dim3(cdiv(T, 64), pad64(c.latent_dim) / 64, B), dim3(256), 0, s, z, bf.Y, c.latent_dim,
                        pad64(c.latent_dim), T);
     SAT_LAUNCH_CHECK();
+    Ranger rg{p, s};
+    SAT_TRY(rg(bf.Y, (size_t)B * T * pad64(c.latent_dim)));
     op_t* S = bf.S0;
     op_t* Sn = bf.S1;
     {
@@ -998,6 +1061,7 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
         a.off0 = -3;
         set_act(a, S, p->blocks[0].sn_in);
         SAT_TRY(launch_conv(a, B, s));
+        SAT_TRY(rg(S, (size_t)B * T * p->first.Cout));
     }
     int L = T;
     for (int bi = 0; bi < nb; ++bi) {
@@ -1016,9 +1080,11 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
         SAT_TRY(launch_conv(a, B, s));
         std::swap(S, Sn);
         L *= st;
+        SAT_TRY(rg(S, (size_t)B * L * blk.cout));
+        SAT_TRY(rg(bf.R, (size_t)B * L * blk.cout));
         for (int r = 0; r < 3; ++r) {
             const Snake& next = r < 2 ? blk.ru_sn1[r + 1] : (bi + 1 < nb ? p->blocks[bi + 1].sn_in : p->final_snake);
-            SAT_TRY(run_ru(blk, r, blk.cout, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s));
+            SAT_TRY(run_ru(blk, r, blk.cout, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s, rg));
             std::swap(S, Sn);
         }
     }
@@ -1027,7 +1093,7 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
     a.off0 = -3;
     a.out_cf = audio; a.cf_channels = c.io_channels; a.tanh_out = p->opt.final_tanh;
     SAT_TRY(launch_conv(a, B, s));
-    return 0;
+    return rg.done();
 }
 
 int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T, void* ws,
@@ -1048,11 +1114,14 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
     hipLaunchKernelGGL(general ? first_conv_kernel<true> : first_conv_kernel<false>, dim3(cdiv(L, 64), B), dim3(256), 0, s, audio,
                        p->first_w_f32, p->first.bias, sn0.a, sn0.ib, sn0.act, bf.R, S, c.io_channels, c.channels, pad64(c.channels), L);
     SAT_LAUNCH_CHECK();
+    Ranger rg{p, s};
+    SAT_TRY(rg(S, (size_t)B * L * pad64(c.channels)));
+    SAT_TRY(rg(bf.R, (size_t)B * L * pad64(c.channels)));
     for (int bi = 0; bi < nb; ++bi) {
         const auto& blk = p->blocks[bi];
         for (int r = 0; r < 3; ++r) {
             const Snake& next = r < 2 ? blk.ru_sn1[r + 1] : blk.sn_in;
-            SAT_TRY(run_ru(blk, r, blk.cin, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s));
+            SAT_TRY(run_ru(blk, r, blk.cin, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s, rg));
             std::swap(S, Sn);
         }
         const int st = blk.stride, pad = (st + 1) / 2;
@@ -1066,11 +1135,60 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
         SAT_TRY(launch_conv(a, B, s));
         std::swap(S, Sn);
         L = Lo;
+        SAT_TRY(rg(S, (size_t)B * L * blk.cout));
+        if (!lastb) SAT_TRY(rg(bf.R, (size_t)B * L * blk.cout));
     }
     ConvArgs a = base_args(p->last, S, L, L);
     a.off0 = -1;
     a.out_cf = out; a.cf_channels = c.latent_dim;
     SAT_TRY(launch_conv(a, B, s));
+    return rg.done();
+}
+
+// ---- sat_oobleck_range_report and its companions, per build
+int oob_range_report(OobPlan* p, int32_t enable) {
+    SAT_CHECK_ARG(enable >= 0 && enable <= 2, SAT_E_INVALID, "oobleck_range_report: enable must be 0 (off), 1 (on) or 2 (zero the records), got %d", enable);
+    if (enable == 0) {
+        if (!p->rr) return 0;
+        SAT_HIP(hipDeviceSynchronize());          // launches in flight still accumulate into the records
+        p->rr_buf.release();
+        p->rr = nullptr;
+        return 0;
+    }
+    SAT_CHECK_ARG(sat_launch_range_stats, SAT_E_UNSUPPORTED, "oobleck_range_report: built without the range statistics kernel");
+    const size_t bytes = p->rr_names.size() * sizeof(sat_range_record);
+    if (enable == 2) {
+        SAT_CHECK_ARG(p->rr, SAT_E_STATE, "oobleck_range_report: the report is not enabled, there is nothing to zero");
+        SAT_HIP(hipDeviceSynchronize());
+        SAT_HIP(hipMemset(p->rr, 0, bytes));
+        return 0;
+    }
+    if (p->rr) return 0;          // already on: the records keep accumulating
+    SAT_TRY(p->rr_buf.reserve(bytes));
+    SAT_HIP(hipMemset(p->rr_buf.ptr, 0, bytes));
+    p->rr = (sat_range_record*)p->rr_buf.ptr;
+    return 0;
+}
+
+int oob_range_report_count(OobPlan* p, int32_t* out_records) {
+    SAT_CHECK_ARG(out_records, SAT_E_INVALID, "oobleck_range_report_count: null argument");
+    *out_records = (int32_t)p->rr_names.size();
+    return 0;
+}
+
+const char* oob_range_report_name(OobPlan* p, int32_t index) {
+    return index >= 0 && index < (int32_t)p->rr_names.size() ? p->rr_names[index].c_str() : nullptr;
+}
+
+int oob_range_report_read(OobPlan* p, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes, sat_stream_t stream) {
+    SAT_CHECK_ARG(out_host, SAT_E_INVALID, "oobleck_range_report_read: null argument");
+    SAT_CHECK_ARG(record_bytes == sizeof(sat_range_record), SAT_E_INVALID,
+                  "oobleck_range_report_read: sat_range_record of %zu bytes; this library knows %zu", record_bytes, sizeof(sat_range_record));
+    const int n = (int)p->rr_names.size();
+    SAT_CHECK_ARG(capacity_records >= n, SAT_E_INVALID, "oobleck_range_report_read: room for %d records, need %d", capacity_records, n);
+    SAT_CHECK_ARG(p->rr, SAT_E_STATE, "oobleck_range_report_read: the report is not enabled (sat_oobleck_range_report)");
+    SAT_HIP(hipMemcpyAsync(out_host, p->rr, (size_t)n * sizeof(sat_range_record), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    SAT_HIP(hipStreamSynchronize((hipStream_t)stream));
     return 0;
 }
 
@@ -1088,6 +1206,10 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
     int oob_workspace_bytes(const OobPlan* p, int32_t b, int32_t t_len, size_t* out_bytes);                                       \
     int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, void* ws, size_t ws_bytes, sat_stream_t stream); \
     int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T, void* ws, size_t ws_bytes, sat_stream_t stream); \
+    int oob_range_report(OobPlan* p, int32_t enable);                                                                             \
+    int oob_range_report_count(OobPlan* p, int32_t* out_records);                                                                 \
+    const char* oob_range_report_name(OobPlan* p, int32_t index);                                                                 \
+    int oob_range_report_read(OobPlan* p, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes, sat_stream_t stream); \
     }
 SAT_OOB_DECLARE(f16)
 SAT_OOB_DECLARE(f32)
@@ -1164,6 +1286,23 @@ extern "C" int sat_oobleck_encode(sat_oobleck_plan* p, const float* audio_dev, f
                                   sat_stream_t stream) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_encode: null plan");
     return SAT_OOB_CALL(p, oob_encode, audio_dev, out_dev, b, t_len, ws, ws_bytes, stream);
+}
+extern "C" int sat_oobleck_range_report(sat_oobleck_plan* p, int32_t enable) {
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_range_report: null plan");
+    return SAT_OOB_CALL(p, oob_range_report, enable);
+}
+extern "C" int sat_oobleck_range_report_count(const sat_oobleck_plan* p, int32_t* out_records) {
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_range_report_count: null plan");
+    return SAT_OOB_CALL(p, oob_range_report_count, out_records);
+}
+extern "C" const char* sat_oobleck_range_report_name(const sat_oobleck_plan* p, int32_t index) {
+    if (!p) return nullptr;
+    return SAT_OOB_CALL(p, oob_range_report_name, index);
+}
+extern "C" int sat_oobleck_range_report_read(sat_oobleck_plan* p, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes,
+                                             sat_stream_t stream) {
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_range_report_read: null plan");
+    return SAT_OOB_CALL(p, oob_range_report_read, out_host, capacity_records, record_bytes, stream);
 }
 #undef SAT_OOB_CALL
 #endif

@@ -364,6 +364,12 @@ __attribute__((weak)) int sat_launch_head_split_hd128(const float* x, const Head
 }  // namespace SAT_OPNS
 using namespace SAT_OPNS;
 __attribute__((weak)) int sat_launch_rope_table_hd128(const float* inv_freq, float* cos_t, float* sin_t, int s_len, hipStream_t s);      // [s_len][32]
+// range_stats.hip: the reduction of the range reports (sat_range_record) over x[r * pitch + c], r < rows, c < cols, of `dtype` elements
+// (SAT_GEMM_BF16 / SAT_GEMM_FP16 / SAT_GEMM_FP32X).  `counted` is what the record's `elements` grows by: rows * cols, or the logical count of
+// a view that also scans the zero pads of its layout.  WEAK for the same reason as the 128-channel-head launchers: null in the host test driver,
+// where the plans answer SAT_E_UNSUPPORTED to the request for a report and never reach it
+__attribute__((weak)) int sat_launch_range_stats(const void* x, int dtype, int64_t rows, int64_t cols, int64_t pitch, uint64_t counted,
+                                                 sat_range_record* rec, hipStream_t s);
 int sat_launch_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int sq, int sk, int sq_pad,
                                    int sk_pad, hipStream_t s);
 int sat_launch_head_split_hd128_f16(const float* x, const void* heads_epi, int b, hipStream_t s);

@@ -26,6 +26,20 @@ extern "C" int sat_cast_f16(const float* x, void* y, int64_t n, sat_stream_t str
     return cast_bf16_impl(1, x, y, n, stream);
 }
 
+static int range_stats_impl(int dtype, const void* x, int64_t rows, int64_t cols, int64_t pitch, sat_range_record* record, sat_stream_t stream) {
+    SAT_CHECK_ARG(rows > 0 && cols > 0, SAT_E_INVALID, "range_stats: view of %lld x %lld", (long long)rows, (long long)cols);
+    return sat_launch_range_stats(x, dtype, rows, cols, pitch, (uint64_t)rows * (uint64_t)cols, record, (hipStream_t)stream);
+}
+extern "C" int sat_range_stats_f16(const void* x, int64_t rows, int64_t cols, int64_t pitch, sat_range_record* record, sat_stream_t stream) {
+    return range_stats_impl(SAT_GEMM_FP16, x, rows, cols, pitch, record, stream);
+}
+extern "C" int sat_range_stats_bf16(const void* x, int64_t rows, int64_t cols, int64_t pitch, sat_range_record* record, sat_stream_t stream) {
+    return range_stats_impl(SAT_GEMM_BF16, x, rows, cols, pitch, record, stream);
+}
+extern "C" int sat_range_stats_f32(const void* x, int64_t rows, int64_t cols, int64_t pitch, sat_range_record* record, sat_stream_t stream) {
+    return range_stats_impl(SAT_GEMM_FP32X, x, rows, cols, pitch, record, stream);
+}
+
 static int gemm_bf16_f32_impl(int f16, const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
                               int32_t accumulate, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
     SAT_CHECK_ARG(c, SAT_E_INVALID, "gemm: null output");

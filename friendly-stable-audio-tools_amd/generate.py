@@ -63,6 +63,10 @@ def get_args():
     p.add_argument("--codec-final-tanh", action="store_true",
                    help="build extension: the VAE decoder was trained with final_tanh=True (write \"final_tanh\": false in the model config, "
                         "which the constructor requires, and pass this flag: set_final_tanh(True))")
+    p.add_argument("--check-fp16-range", action="store_true",
+                   help="build extension, for a checkpoint this build was never run on: before generating, run the first batch once for 8 "
+                        "steps with the activation range reports of the DiT and the codec on and print how close their 16-bit buffers come "
+                        "to the fp16 limit (+-65504, where conversions saturate silently), with advice; changes no setting")
     return p.parse_args()
 
 
@@ -201,6 +205,11 @@ def main():
         call_seed = -1 if args.seed < 0 else args.seed + rank + world * i
         order = model.cross_attn_cond_ids + [k for k in cond if k not in model.cross_attn_cond_ids]
         cond = {k: cond[k] for k in order if k in cond}
+        if args.check_fp16_range and i == 0 and rank == 0:
+            from stable_audio_tools.inference.preflight import check_fp16_range, format_fp16_range
+            print("\n".join(format_fp16_range(check_fp16_range(
+                model, steps=min(8, args.sample_steps), cfg_scale=args.cfg_scale, conditioning_tensors=cond, sample_size=sample_size, sigma_min=0.3,
+                sigma_max=500, sampler_type=args.sampler_type, device=str(device), seed=call_seed))))
         audio = generate_diffusion_cond(model, steps=args.sample_steps, cfg_scale=args.cfg_scale, conditioning_tensors=cond,
                                         sample_size=sample_size, sigma_min=0.3, sigma_max=500, sampler_type=args.sampler_type,
                                         device=str(device), seed=call_seed)

@@ -6,7 +6,7 @@ calling an op with non-HIP tensors, raises.  Build with
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 import torch
 
@@ -59,6 +59,16 @@ class SatOobleckOptions(Structure):
 OOBLECK_ACT_SNAKE, OOBLECK_ACT_ELU = 0, 1     # include/sat_hip.h: SAT_OOBLECK_ACT_*
 
 
+class SatRangeRecord(Structure):
+    """include/sat_hip.h: sat_range_record, the fp16 range use of one activation buffer (32 bytes)."""
+    _fields_ = [("max_abs", c_float), ("launches", c_uint32), ("over_fp16", c_uint64), ("nonfinite", c_uint64), ("elements", c_uint64)]
+
+
+DIT_RANGE_SLOTS = 12     # include/sat_hip.h: SAT_DIT_RANGE_SLOTS
+# sat_dit_range_slot_name(0..11) (tests/test_range_report_host.py holds the two together)
+DIT_RANGE_SLOT_NAMES = ("a_qkv", "q", "k", "v", "attn_out", "a_cross_q", "cross_q", "cross_k", "cross_v", "cross_attn_out", "a_ff", "ff_hidden")
+
+
 _SIGNATURES = {
     "sat_version": (c_int32, []),
     "sat_last_error": (c_char_p, []),
@@ -81,6 +91,9 @@ _SIGNATURES = {
                                        POINTER(c_int64)]),
     "sat_dit_debug": (c_int32, [c_void_p, c_int32]),
     "sat_dit_debug_read": (c_int32, [c_void_p, POINTER(c_float), c_int32, c_void_p]),
+    "sat_dit_range_report": (c_int32, [c_void_p, c_int32]),
+    "sat_dit_range_report_read": (c_int32, [c_void_p, POINTER(SatRangeRecord), c_int32, c_size_t, c_void_p]),
+    "sat_dit_range_slot_name": (c_char_p, [c_int32]),
     "sat_cfg_combine": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),
     "sat_quant_rows_fp8": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "sat_layernorm_fp8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
@@ -103,10 +116,16 @@ _SIGNATURES = {
     "sat_oobleck_workspace_bytes": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_size_t)]),
     "sat_oobleck_decode": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_oobleck_encode": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "sat_oobleck_range_report": (c_int32, [c_void_p, c_int32]),
+    "sat_oobleck_range_report_count": (c_int32, [c_void_p, POINTER(c_int32)]),
+    "sat_oobleck_range_report_name": (c_char_p, [c_void_p, c_int32]),
+    "sat_oobleck_range_report_read": (c_int32, [c_void_p, POINTER(SatRangeRecord), c_int32, c_size_t, c_void_p]),
     "sat_vae_sample": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "sat_float_to_int16": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "sat_layernorm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "sat_cast_bf16": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "sat_range_stats_bf16": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "sat_range_stats_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "sat_cross_attention_fused_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                                  c_int32, c_int32, c_void_p]),
     "sat_resample_sinc": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
@@ -154,7 +173,7 @@ _SIGNATURES = {
 }
 
 # the same unit-level entry points on IEEE fp16 operands (gemm_dtype = 3): identical signatures
-for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_attention_hd128_bf16", "sat_head_split_hd128_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws"):
+for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_attention_hd128_bf16", "sat_head_split_hd128_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws", "sat_range_stats_bf16"):
     _SIGNATURES[_n.replace("bf16", "f16")] = _SIGNATURES[_n]
 
 _lib = None
@@ -235,6 +254,12 @@ def build_plan(kind, create, tensors, device, configure=None):
         destroy_plan(kind, handle)
         raise
     return handle
+
+
+def range_rows(records, n):
+    """The first ``n`` ``SatRangeRecord`` of a ctypes array as dicts (``sat_*_range_report_read``)."""
+    return [dict(max_abs=float(r.max_abs), over_fp16=int(r.over_fp16), nonfinite=int(r.nonfinite), elements=int(r.elements),
+                 launches=int(r.launches)) for r in records[:n]]
 
 
 def same_device(a, b):

@@ -126,6 +126,47 @@ class _OobleckHip(nn.Module):
         self._plan = None
         self._plan_version = None
         self._ws = None
+        self._range_report = False
+
+    def activation_range_report(self, enable: bool = True):
+        """Build extension (``sat_oobleck_range_report``): fp16 range use of every activation tensor a forward writes to its workspace.
+        ``(True)`` switches it on and the following forwards accumulate; ``(False)`` returns one dict per tensor in launch order -- ``index``,
+        ``name`` (module path of the producing layer; ``"input"`` for the decoder's channels-last latents, ``<path>.raw`` for the
+        un-activated copy kept for a residual add), ``max_abs``, ``over_fp16``, ``nonfinite``, ``elements``, ``launches`` -- and switches it
+        off.  In an fp16 codec ``over_fp16`` counts clamped elements; run the codec with ``set_gemm_dtype("fp32")`` to read what fp16
+        WOULD clamp together with the un-clamped ``max_abs``.  While on, every ResidualUnit runs as two launches (the tensor between its
+        convolutions then exists in memory): +60 % per decode, inside the codec gates (measured bit-equal to the fused kernel, not promised).  The setting
+        survives a plan rebuild, the records collected so far do not."""
+        lib = _hip.lib()
+        if enable:
+            self._range_report = True
+            try:
+                _hip.check(lib.sat_oobleck_range_report(self._ensure_plan(), 1))
+            except BaseException:
+                self._range_report = False
+                raise
+            return None
+        plan = self._ensure_plan()
+        rows = []
+        try:
+            count = ctypes.c_int32()
+            _hip.check(lib.sat_oobleck_range_report_count(plan, ctypes.byref(count)))
+            n = count.value
+            buf = (_hip.SatRangeRecord * max(n, 1))()
+            _hip.check(lib.sat_oobleck_range_report_read(plan, buf, n, ctypes.sizeof(_hip.SatRangeRecord), _hip.stream()))
+            names = [lib.sat_oobleck_range_report_name(plan, i) for i in range(n)]
+            rows = [dict(index=i, name=names[i].decode(), **r) for i, r in enumerate(_hip.range_rows(buf, n))]
+        finally:
+            self._range_report = False
+            rc = lib.sat_oobleck_range_report(plan, 0)
+        _hip.check(rc)
+        return rows
+
+    def reset_activation_range_report(self):
+        """Zeroes the records of ``activation_range_report`` and leaves it on."""
+        if not self._range_report:
+            raise _hip.SatError("activation_range_report is not enabled")
+        _hip.check(_hip.lib().sat_oobleck_range_report(self._ensure_plan(), 2))
 
     def set_gemm_dtype(self, dtype: str):
         """Build extension: format of the activations and weights inside the convolution kernels -- "fp16" (the package default,
@@ -146,14 +187,18 @@ class _OobleckHip(nn.Module):
         except Exception:
             pass
 
+    def _plan_device(self):
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise _hip.SatError("Oobleck modules must be on a HIP device (model.to('cuda')); there is no CPU path")
+        return dev
+
     def _ensure_plan(self):
         ver = _init.params_version(self)
         if self._plan is not None and ver == self._plan_version:
             return self._plan
         lib = _hip.lib()
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise _hip.SatError("Oobleck modules must be on a HIP device (model.to('cuda')); there is no CPU path")
+        dev = self._plan_device()
         _hip.destroy_plan("oobleck", self._plan)
         self._plan = None
         cfg = _hip.SatOobleckCfg()
@@ -171,7 +216,12 @@ class _OobleckHip(nn.Module):
         opt.final_tanh = 1 if self.final_tanh else 0
         opt.nearest_upsample = 1 if self.use_nearest_upsample else 0
         create = lambda: _hip.new_handle(lib.sat_oobleck_plan_create_ex, ctypes.byref(cfg), ctypes.byref(opt), ctypes.sizeof(opt))
-        self._plan, self._plan_version = _hip.build_plan("oobleck", create, self.state_dict(), dev), ver
+
+        def configure(plan):
+            if self._range_report:        # the report belongs to the module: a rebuilt plan starts with it on (and with empty records)
+                _hip.check(lib.sat_oobleck_range_report(plan, 1))
+
+        self._plan, self._plan_version = _hip.build_plan("oobleck", create, self.state_dict(), dev, configure), ver
         return self._plan
 
     def _workspace(self, b, t_len):
@@ -291,6 +341,16 @@ class AudioAutoencoder(nn.Module):
             if isinstance(part, _OobleckHip):
                 part.set_gemm_dtype(dtype)
         return self
+
+    def activation_range_report(self, enable: bool = True):
+        """``activation_range_report`` of the encoder and the decoder (``_OobleckHip.activation_range_report``); ``(False)`` returns the rows
+        of both, each tagged ``part="encoder"`` / ``"decoder"``."""
+        rows = []
+        for part, module in (("encoder", self.encoder), ("decoder", self.decoder)):
+            if isinstance(module, _OobleckHip):
+                got = module.activation_range_report(enable)
+                rows += [dict(part=part, **r) for r in (got or [])]
+        return None if enable else rows
 
     def set_final_tanh(self, enabled: bool = True):
         """The decoder's final tanh (see ``OobleckDecoder.set_final_tanh``)."""

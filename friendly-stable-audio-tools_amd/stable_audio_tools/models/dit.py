@@ -94,6 +94,7 @@ class DiffusionTransformer(nn.Module):
         self.layernorm_fusion = True
         self.cross_attention_fusion = True
         self.tile_policy = 0
+        self._range_report = False      # activation_range_report: lives here, not in the plan, so that a plan rebuild keeps it
         self._check_options(self.gemm_dtype)
 
     def transformer_options(self):
@@ -140,6 +141,53 @@ class DiffusionTransformer(nn.Module):
         names = ("self_attn.to_out", "cross_attn.to_out", "ff.out")
         return [dict(layer=l, update=names[j], max_abs=buf[(l * 3 + j) * 4], common_mode=buf[(l * 3 + j) * 4 + 1],
                      saturated=int(buf[(l * 3 + j) * 4 + 2]), crest=buf[(l * 3 + j) * 4 + 3]) for l in range(self.depth) for j in range(3)]
+
+    def activation_range_report(self, enable: bool = True):
+        """Build extension (``sat_dit_range_report``): fp16 range use of the 16-bit buffers of the blocks, which ``residual_stream_report``
+        never reads -- the GEMM operand ``A`` (LayerNorm output or, under the LayerNorm fold, the 16-bit image of the residual rows), ``q`` /
+        ``k`` / ``v``, the two attention outputs, the SwiGLU hidden state and the per-generation cross K / V cache.  ``(True)`` switches it on;
+        from then on ``prepare_generation`` and every forward / ``denoise`` ACCUMULATE, so a whole sampler run is covered, not its last step.
+        ``(False)`` returns one dict per layer and buffer -- ``layer``, ``buffer``, ``max_abs``, ``over_fp16`` (fp16 plan: elements that were
+        clamped at +-65504; bf16 plan: elements fp16 would clamp), ``nonfinite``, ``elements`` (0: this plan does not materialise the buffer),
+        ``launches``, ``holds`` ("layernorm output" / "residual image" for the ``a_*`` buffers, else None) -- and switches it off.  Outputs are
+        bit-identical with the report on and off.  The setting survives a plan rebuild (``set_gemm_dtype`` ...), the records collected so far
+        do not.  fp16 / bf16 plans only."""
+        lib = _hip.lib()
+        if enable:
+            self._range_report = True
+            try:
+                _hip.check(lib.sat_dit_range_report(self._ensure_plan(), 1))      # (a plan built just now already has it on: no-op then)
+            except BaseException:
+                self._range_report = False
+                raise
+            return None
+        plan = self._ensure_plan()
+        n = self.depth * _hip.DIT_RANGE_SLOTS
+        buf = (_hip.SatRangeRecord * n)()
+        try:
+            _hip.check(lib.sat_dit_range_report_read(plan, buf, n, ctypes.sizeof(_hip.SatRangeRecord), _hip.stream()))
+        finally:
+            self._range_report = False
+            rc = lib.sat_dit_range_report(plan, 0)
+        _hip.check(rc)
+        # which a_* buffers hold the un-normalised residual image: sat_dit_plan_create's ln_fold rule and proj_kind (csrc/dit_plan.hip)
+        fold = (self.layernorm_fusion and self.gemm_dtype in ("fp16", "bf16") and self.global_cond_type != "adaLN" and self.embed_dim >= 256
+                and self.transformer.dim_heads == 64)
+        rows = []
+        for i, r in enumerate(_hip.range_rows(buf, n)):
+            layer, name = divmod(i, _hip.DIT_RANGE_SLOTS)
+            name = _hip.DIT_RANGE_SLOT_NAMES[name]
+            holds = None
+            if name.startswith("a_"):
+                holds = "residual image" if fold and not (name == "a_qkv" and layer == 0) else "layernorm output"
+            rows.append(dict(layer=layer, buffer=name, holds=holds, **r))
+        return rows
+
+    def reset_activation_range_report(self):
+        """Zeroes the records of ``activation_range_report`` and leaves it on (between two generations, say)."""
+        if not self._range_report:
+            raise _hip.SatError("activation_range_report is not enabled")
+        _hip.check(_hip.lib().sat_dit_range_report(self._ensure_plan(), 2))
 
     def set_cross_attention_fusion(self, on: bool):
         """Build extension, A/B switch: the to_q projection + cross-attention core as ONE launch where it applies (one prompt; the default) or
@@ -194,6 +242,12 @@ class DiffusionTransformer(nn.Module):
         except Exception:
             pass
 
+    def _plan_device(self):
+        dev = self.timestep_features.weight.device
+        if dev.type != "cuda":
+            raise _hip.SatError("DiffusionTransformer must be on a HIP device (model.to('cuda')); there is no CPU path")
+        return dev
+
     def _ensure_plan(self):
         ver = _init.params_version(self)
         options = self.transformer_options()
@@ -201,9 +255,7 @@ class DiffusionTransformer(nn.Module):
             return self._plan
         self._check_options(self.gemm_dtype)
         lib = _hip.lib()
-        dev = self.timestep_features.weight.device
-        if dev.type != "cuda":
-            raise _hip.SatError("DiffusionTransformer must be on a HIP device (model.to('cuda')); there is no CPU path")
+        dev = self._plan_device()
         _hip.destroy_plan("dit", self._plan)
         self._plan = None
         cfg = _hip.SatDitCfg(self.io_channels, self.embed_dim, self.depth, self.num_heads, self.cond_token_dim,
@@ -217,6 +269,8 @@ class DiffusionTransformer(nn.Module):
             if options != (0, _hip.DIT_POS_NONE, 0, 1):       # a model with none of these switches never makes the call
                 opts = _hip.SatDitTransformerOptions(*options)
                 _hip.check(lib.sat_dit_plan_set_transformer_options(plan, ctypes.byref(opts), ctypes.sizeof(opts)))
+            if self._range_report:        # the report belongs to the module: a rebuilt plan starts with it on (and with empty records)
+                _hip.check(lib.sat_dit_range_report(plan, 1))
 
         create = lambda: _hip.new_handle(lib.sat_dit_plan_create_sized, ctypes.byref(cfg), ctypes.sizeof(cfg))
         plan = self._plan = _hip.build_plan("dit", create, self.state_dict(), dev, configure)

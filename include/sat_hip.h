@@ -262,6 +262,46 @@ int sat_dit_profile_read(sat_dit_plan* plan, double* total_ms, int32_t* launches
 int sat_dit_debug(sat_dit_plan* plan, int32_t enable);
 int sat_dit_debug_read(sat_dit_plan* plan, float* out_host, int32_t capacity_floats, sat_stream_t stream);
 
+/* fp16 range use of an activation buffer, accumulated on the device (csrc/range_stats.hip).  Every fp32 -> fp16 conversion of the fp16 build
+ * SATURATES silently at +-65504; a record says how close a buffer came.  over_fp16: in an fp16 buffer the elements that sit AT the clamp
+ * (|x| == 65504: clamped, or exactly there) or are non-finite; in a bf16 / fp32 buffer the elements fp16 WOULD clamp.  max_abs is the
+ * largest finite |x|.  Maximum and integer sums do not depend on the order of accumulation: a record is bit-reproducible. */
+typedef struct sat_range_record {
+    float    max_abs;     /* max |x| over finite elements */
+    uint32_t launches;    /* times this record was accumulated into */
+    uint64_t over_fp16;   /* elements with |x| >= 65504 or non-finite */
+    uint64_t nonfinite;   /* inf / NaN */
+    uint64_t elements;    /* rows * cols summed over launches */
+} sat_range_record;
+
+/* Range report of the 16-bit buffers a DiT forward writes, beside sat_dit_debug (which reads the fp32 residual stream only and is not changed by
+ * this; both may be on).  enable = 1: allocate depth * SAT_DIT_RANGE_SLOTS zeroed records (allowed before finalize); 0: free them (synchronises
+ * the device); 2: zero the records and stay enabled.  While enabled, sat_dit_prepare_context and every forward / denoise launch one small
+ * reduction behind each producer of a slot, and the records ACCUMULATE over all forwards until mode 2 or 0 -- a sampler run is covered as a
+ * whole, not its last step.  Record (layer l, slot s) is at index l * SAT_DIT_RANGE_SLOTS + s; sat_dit_range_slot_name(s) names the slot (NULL
+ * outside 0..SAT_DIT_RANGE_SLOTS-1):
+ *   a_qkv, a_cross_q, a_ff     the A operand in front of to_qkv / cross to_q / FF-in: the LayerNorm output, or under ln_fold (every such GEMM
+ *                              but layer 0's to_qkv) the 16-bit image of the residual rows written by the previous residual GEMM
+ *   q, k, v                    the head-split buffers of self-attention
+ *   attn_out, cross_attn_out   the attention outputs in front of the two to_out projections
+ *   cross_q                    the cross branch's query buffer: only where the fused to_q + cross-attention launch is NOT taken
+ *   ff_hidden                  the SwiGLU hidden state in front of FF-out
+ *   cross_k, cross_v           the layer's context cache, once per sat_dit_prepare_context
+ * `elements` counts the logical values (rows x channels of the model); the scan of q / k / v and of the context cache also covers the zero
+ * pads of their layouts, which change neither max_abs nor a counter.  A slot the forward does not materialise keeps elements == 0.  The report
+ * changes no decision of the forward (tile routing, the fused cross launch): outputs are bit-identical with it on and off, and a plan never given
+ * the call launches exactly what it did before this entry point existed.  Toggling it changes what a forward ENQUEUES: a hipGraph captured
+ * across a toggle (or a mode-2 reset expected inside it) is invalid -- capture with the report in the state it will replay in, or not at all.
+ * 16-bit operand plans only: SAT_GEMM_FP8 (its A operands are e4m3) and SAT_GEMM_FP32X are SAT_E_UNSUPPORTED, as is a library built without
+ * range_stats.hip.  sat_dit_range_report_read copies all depth * SAT_DIT_RANGE_SLOTS records to the host (synchronises the stream):
+ * record_bytes = sizeof(sat_range_record) of the caller's header, any other size or too small a capacity is SAT_E_INVALID, a report that is
+ * not enabled SAT_E_STATE. */
+#define SAT_DIT_RANGE_SLOTS 12
+int sat_dit_range_report(sat_dit_plan* plan, int32_t enable);
+int sat_dit_range_report_read(sat_dit_plan* plan, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes,
+                              sat_stream_t stream);
+const char* sat_dit_range_slot_name(int32_t slot);
+
 /* Batched-CFG combine alone (models/dit.py:336-345): model_out_dev [2*b, c, t] (cond half, then
  * uncond half) -> out_dev [b, c, t] = uncond + (cond - uncond) * cfg_scale, with the optional
  * std rescale when scale_phi != 0. */
@@ -377,6 +417,21 @@ int sat_oobleck_decode(sat_oobleck_plan* plan, const float* z_dev, float* audio_
 int sat_oobleck_encode(sat_oobleck_plan* plan, const float* audio_dev, float* out_dev, int32_t b, int32_t t_len,
                        void* workspace_dev, size_t workspace_bytes, sat_stream_t stream);
 
+/* Range report of the codec (sat_range_record, modes 0 / 1 / 2 and the hipGraph rule as sat_dit_range_report; all three builds, allowed before
+ * finalize).  One record per activation tensor an encode / decode writes to its workspace, in launch order; the count depends on the plan's
+ * blocks only.  sat_oobleck_range_report_name(plan, i) is the module path of the layer whose launch wrote tensor i, relative to the encoder /
+ * decoder as in sat_oobleck_plan_set_tensor ("layers.3.layers.1.layers.1"), "input" for record 0 (the channels-last image of the decoder's
+ * latents; the encoder reads its fp32 audio directly and has no such record), and path + ".raw" for the un-activated copy a launch keeps for
+ * the next residual add beside the activated tensor.  NULL outside 0..count-1.  Pad channels of narrow stages are exact zeros and are scanned
+ * and counted.  The fp32 build is the one to ask whether fp16 is safe: its over_fp16 is what the fp16 build would clamp.
+ * While enabled, every ResidualUnit runs on the two-launch route (the one used above 256 channels and by the fp32 build), so that the tensor
+ * between its two convolutions reaches memory and has a record; with the report off the fused kernel runs as before. */
+int sat_oobleck_range_report(sat_oobleck_plan* plan, int32_t enable);
+int sat_oobleck_range_report_count(const sat_oobleck_plan* plan, int32_t* out_records);
+const char* sat_oobleck_range_report_name(const sat_oobleck_plan* plan, int32_t index);
+int sat_oobleck_range_report_read(sat_oobleck_plan* plan, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes,
+                                  sat_stream_t stream);
+
 /* VAEBottleneck.encode / vae_sample (models/bottleneck.py:46-62) with the Gaussian noise
  * supplied by the caller: z = noise * (softplus(scale) + 1e-4) + mean.
  * mean_scale_dev [b, 2*c, t], noise_dev/z_dev [b, c, t]. */
@@ -398,6 +453,12 @@ int sat_layernorm_bf16(const float* x_dev, const float* gamma_dev, const float* 
                        int32_t m, int32_t d, sat_stream_t stream);
 /* fp32 -> bf16 (round to nearest even) */
 int sat_cast_bf16(const float* x_dev, void* y_bf16_dev, int64_t n, sat_stream_t stream);
+/* The reduction behind the range reports: accumulates the view x[r * pitch + c], r < rows, c < cols (elements; pitch >= cols; a 1-D buffer is
+ * rows = 1) into *record_dev (sat_range_record, 8-byte aligned; the caller owns and zeroes it).  Elements cols..pitch-1 of a row are not
+ * read into the statistics.  x of IEEE fp16, bf16 or fp32 elements. */
+int sat_range_stats_f16(const void* x_dev, int64_t rows, int64_t cols, int64_t pitch, sat_range_record* record_dev, sat_stream_t stream);
+int sat_range_stats_bf16(const void* x_dev, int64_t rows, int64_t cols, int64_t pitch, sat_range_record* record_dev, sat_stream_t stream);
+int sat_range_stats_f32(const void* x_dev, int64_t rows, int64_t cols, int64_t pitch, sat_range_record* record_dev, sat_stream_t stream);
 /* C[m,n] (fp32) = A[m,k] (bf16) * W[n,k]^T (bf16)  (+ bias[n]) ; accumulate != 0 adds into C.
  * n % 128 == 0, k % 64 == 0.  variant selects a tile configuration (0 = default). */
 int sat_gemm_bf16_f32(const void* a_bf16_dev, const void* w_bf16_dev, const float* bias_dev, float* c_dev,
