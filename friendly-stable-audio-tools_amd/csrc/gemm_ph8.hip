@@ -41,6 +41,9 @@
 //     forward can be captured into a hipGraph.  (Round 3 also built the in-kernel last-arriver fix-up with arrival tickets, and
 //     contiguous stream-K shares: both measured slower than this -- profiles/r03_ph8_streamk_timeline.txt,
 //     r03_ph8_ffout_streamk_negative.txt -- and are gone from the source.)
+//   * the 16-bit SwiGLU GEMM with 1 - 1.5 rounds of full tiles and an M tail of <= 16 rows (FF-in at one prompt) runs the HALF-ROW schedule
+//     instead (ph8_half_rows_ints, asked first): one full tile and at most one half tile (128 rows, every wave's second quadrant skipped)
+//     per CU, the tail as one more 16-row block of wave row 1 -- in the HRK build of the kernel, which no other launch uses;
 //   * the whole schedule is a handful of integers computed on the host per launch in closed form and passed by value: no device
 //     tables, no cache, no lock;
 //   * the LDS-DMA prologue of the next K-range (6 half-tiles) is issued BEFORE the epilogue of the current one -- the ring is
@@ -126,6 +129,8 @@ struct Seg {                // one K-range of one tile
     int kt0, nk;            // first K-tile, K-tiles (even)
     bool whole;             // the K-range covers the tile: plain epilogue
     bool tr;                // accumulator orientation (transposed unless a V^T destination)
+    bool half;              // half tile (ph8_half_rows_ints): rows [m0, m0 + 128), wave row w owns m0 + 64 w .. + 63 as its quadrant 0
+    bool ext;               // half tile + the 16-row block at m0 + 128 (the M tail) as block 0 of wave row 1's quadrant 1
 };
 
 // fp32 output / residual update of ONE token row piece (transformer.py:692-700), adaLN gate (:674, 688), and the producer side of the
@@ -224,7 +229,10 @@ __device__ __forceinline__ void ph8_epi_f32_row(const Ph8F32Epi& e, f32x4_t (&v)
 // GATED (fp32 output only): the adaLN build of the residual epilogue -- (acc + bias) * gate[sequence] before the add
 // (transformer.py:674, 688).  A kernel of its own: a second copy of the straight-line epilogue inside one kernel made the register
 // allocator spill, a uniform branch inside it hides the vmcnt bookkeeping.
-template <int EPI, int DBG = 0, int FP8 = 0, bool GATED = false>
+// HRK: the build that also walks half tiles (ph8_half_rows_ints; 16-bit SwiGLU only).  A kernel of its own, launched only for a half-row
+// schedule: it adds one scalar branch to the full tile's K-tile (main_loop, q1_blocks), and every other launch keeps the kernel without it --
+// instruction for instruction the loop it had (profiles/ffin_half_rows_timing.txt).
+template <int EPI, int DBG = 0, int FP8 = 0, bool GATED = false, bool HRK = false>
 __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, unsigned long long* ts = nullptr) {
     sat_f16_saturate();
     constexpr int WN = 4, MFQ = 4;
@@ -255,8 +263,38 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
     int sk_b = 0, sk_e = 0;
     if (sc.sk_tiles) ph8_wg_units(sc, wgi, sk_b, sk_e);
     int sk_u = sk_b;
+    // Half tiles exist in the HRK build only (ph8_half_rows_ints, ph8_sched.h): everywhere else HR folds every trace of them away
+    constexpr bool HR = HRK;
+    static_assert(!HRK || (EPI == EPI_SWIGLU && FP8 == 0 && DBG == 0), "half tiles: the 16-bit SwiGLU epilogue only");
+    [[maybe_unused]] int hr_step = 0;
     auto next_seg = [&](Seg& s) -> bool {
         int tm, tn;
+        s.half = s.ext = false;
+        if constexpr (HR) {
+            if (sc.hr) {          // one full tile, then at most one half tile (restated for the CPU in tests/host/ph8_half_rows_dump.cpp)
+                s.kt0 = 0; s.nk = 2 * sc.nkp; s.whole = true; s.tr = true;
+                if (hr_step == 0) {
+                    hr_step = 1;
+                    if (ph8_hr_has_full(sc, wgi)) {
+                        ph8_hr_full_of(sc, wgi, tm, tn);
+                        s.m0 = tm * BM; s.n0 = tn * BN;
+                        return true;
+                    }
+                }
+                if (hr_step == 1) {
+                    hr_step = 2;
+                    const int j = ph8_hr_half_index(sc, wgi);
+                    if (j >= 0) {
+                        int r0, ext;
+                        ph8_hr_half_of(sc, j, r0, tn, ext);
+                        s.m0 = r0; s.n0 = tn * BN;
+                        s.half = true; s.ext = ext != 0;
+                        return true;
+                    }
+                }
+                return false;
+            }
+        }
         if (dp_s < sc.dp_rounds) {
             tile_of(dp_s * sc.G + wgi, tm, tn);
             ++dp_s;
@@ -282,17 +320,31 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)g.A, 0, (int)((unsigned)M * (unsigned)K * 2u), 0x00020000);
     __amdgpu_buffer_rsrc_t rsW = rsA;
     int voffA[2], voffW[2][2];          // [round] (A: lo; hi = + 64 rows), [ni][round]
+    // A-hi (the second quadrants): a full tile's rows are 64 below A-lo's.  A half tile has the wave rows 64 rows apart, so "lo + 64 rows" would
+    // be the OTHER wave row's quadrant 0: its A-hi pieces are still issued (every counted vmcnt of the ring stays valid) but aimed beyond the
+    // descriptor's range -- zeros, no memory traffic -- except LDS rows 64..79 of an extended half tile, wave row 1's block at m0 + 128.
+    [[maybe_unused]] int voffAh[2];
+    const int hiA = QR * K * 2;
+    constexpr int VOFF_OOR = (int)0x80000000u;          // >= the range of rsA (launch_ph8: A < 2 GiB), and + kt * 128 does not wrap
     auto setup_dma = [&](const Seg& s) {
         int lane_l = lane;
         asm volatile("" : "+v"(lane_l));
         rsW = __builtin_amdgcn_make_buffer_rsrc((void*)(g.W + (size_t)s.n0 * K), 0, BN * K * 2, 0x00020000);
+        int wrs = WR;                                                 // rows between the two wave rows
+        if constexpr (HR) {
+            wrs = s.half ? QR : WR;
+        }
         const int sub = lane_l >> 3, pos = lane_l & 7;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r = i * (NW * 8) + wave * 8 + sub;             // LDS row of the half-tile
             const int c = pos ^ ((r >> 1) & 7);
             // A: LDS rows [0,64) belong to wave row 0, [64,128) to wave row 1; rows beyond M are out of range of rsA: zeros
-            voffA[i] = (s.m0 + (r / QR) * WR + (r % QR)) * (K * 2) + c * 16;
+            voffA[i] = (s.m0 + (r / QR) * wrs + (r % QR)) * (K * 2) + c * 16;
+            voffAh[i] = voffA[i] + QR * (K * 2);
+            if constexpr (HR) {          // (half tile: LDS row r of A-lo is row m0 + r, so + 64 rows is right for the extended block's r = 64..79)
+                if (s.half && !(s.ext && r >= QR && r < QR + 16)) voffAh[i] = VOFF_OOR;
+            }
             // W: LDS rows [32 w', 32 w' + 32) belong to wave column w'; row = 16 nf + fragment row
             const int wcol = r >> 5, nf = (r >> 4) & 1, fi = r & 15;
 #pragma unroll
@@ -305,14 +357,13 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
             }
         }
     };
-    const int hiA = QR * K * 2;
     auto issue = [&](int kind, int buf, int kt) {          // kind: 0 W-lo, 1 A-lo, 2 W-hi, 3 A-hi (compile-time after inlining)
         char* dst = smem + buf * BUF_BYTES + koff(kind) + wave * 1024;
         const int soff = __builtin_amdgcn_readfirstlane(kt * 128);      // (stays scalar even if the K-tile counter was spilled to a VGPR lane)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if (kind & 1)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_p)(dst + i * (NW * 1024)), 16, voffA[i] + (kind == 3 ? hiA : 0), soff, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_p)(dst + i * (NW * 1024)), 16, kind != 3 ? voffA[i] : HR ? voffAh[i] : voffA[i] + hiA, soff, 0, 0);
             else
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_void_p)(dst + i * (NW * 1024)), 16, voffW[kind >> 1][i], soff, 0, 0);
         }
@@ -369,10 +420,14 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
     // K-tiles kt0 .. kt0 + nk - 1 (nk even); on entry half-tiles 0..5 of the range are in flight or landed and tile kt0 is visible.
     // Quadrant mi of a wave is skipped when its 64 rows lie beyond M (M-tail tiles: the wave keeps staging and joining barriers).
     // One K-tile = phases A and B of the header comment.
-    auto main_loop = [&](auto swap_c, const int kt0, const int nk, const bool q_valid0, const bool q_valid1) {
+    // q1_blocks: the 16-row blocks of quadrant 1 that exist -- MFQ, 0, or (HR kernels) 1: the extended block of a half tile, wave row 1, 8 of
+    // phase B's 32 MFMAs.  (One loop for all three: with a second inlined copy of the loop for half tiles, and also with the one-block case as
+    // the `else` of the full one, the register allocator spilled 240-480 registers inside the loop.  As two consecutive `if`s the kernel keeps
+    // its 250 registers; the price is ONE scalar branch more per K-tile on the full tile's path, behind phase B's MFMAs and in front of its
+    // barrier.  It exists in the HRK build only -- see the kernel's head: everywhere else HR folds it away.)
+    auto main_loop = [&](auto swap_c, const int kt0, const int nk, const bool q_valid0, const int q1_blocks) {
         constexpr bool SWAP = decltype(swap_c)::value;
-        auto mfma_half = [&](int mi, int ni_first) {
-            if (!(mi ? q_valid1 : q_valid0)) return;
+        auto mfma_blocks = [&](int mi, int ni_first, int nblk) {
             __builtin_amdgcn_s_setprio(1);
             if constexpr (FP8 != 0) {
 #pragma unroll
@@ -397,13 +452,21 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-                    for (int f = 0; f < MFQ; ++f)
+                    for (int f = 0; f < nblk; ++f)
 #pragma unroll
                         for (int n = 0; n < 2; ++n)
                             acc[mi * MFQ + f][ni * 2 + n] = SWAP ? mfma_16x16x32(fw[n][ks], fa[f][ks], acc[mi * MFQ + f][ni * 2 + n])
                                                                  : mfma_16x16x32(fa[f][ks], fw[n][ks], acc[mi * MFQ + f][ni * 2 + n]);
             }
             __builtin_amdgcn_s_setprio(0);
+        };
+        auto mfma_half = [&](int mi, int ni_first) {
+            if (mi == 0) {
+                if (q_valid0) mfma_blocks(0, ni_first, MFQ);
+            } else {          // (two `if`s in a row, not else-if: see q1_blocks above)
+                if (q1_blocks == MFQ) mfma_blocks(1, ni_first, MFQ);
+                if (HR && q1_blocks == 1) mfma_blocks(1, ni_first, 1);
+            }
         };
         // MODE 0: steady state (tiles t + 1 and t + 2 exist); 1: tile t + 1 is the range's last; 2: tile t is the last
         auto k_tile = [&](auto buf_c, auto mode_c, int t) {
@@ -615,9 +678,12 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
         // loop, where it would stay live across the main loop and push its 128 + 64 registers into scratch)
         int l15 = l15_, q4 = q4_;
         asm volatile("" : "+v"(l15), "+v"(q4));
-        const int mrow0 = s.m0 + wr * WR + l15;
+        // (half tile: the wave rows are QR apart; its (mean, rstd) rows sit in LDS by tile row like a full tile's, and block mb of a wave is row
+        // wr * QR + 16 mb of the tile in both -- the extended block, mb = MFQ of wave row 1, is row 128)
+        const int wrow = wr * ((HR && s.half) ? QR : WR);
+        const int mrow0 = s.m0 + wrow + l15;
         const int ncol0 = s.n0 + wc * 64;
-        [[maybe_unused]] const float2* ln = reinterpret_cast<const float2*>(smem + RING_BYTES + lb * LN_BYTES) + wr * WR;
+        [[maybe_unused]] const float2* ln = reinterpret_cast<const float2*>(smem + RING_BYTES + lb * LN_BYTES) + wrow;
         [[maybe_unused]] const float* lc1 = reinterpret_cast<const float*>(smem + RING_BYTES + lb * LN_BYTES + BM * 8) + wc * 64;
         [[maybe_unused]] const float* lc2 = lc1 + BN;
         if constexpr (EPI == EPI_F32) {
@@ -672,6 +738,17 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
             // wait at the top of that range can be counted (EPI_STORES): it no longer waits for these stores to be acknowledged.
             const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc((void*)g.H, 0, (int)((unsigned)M * (unsigned)ldh * 2u), 0x00020000);
             const int hcol = (ncol0 >> 1) + q4 * 8;
+            // Byte offset of block mb's store = off_q0 / off_b4 / off_q1 + mb * (16 rows).  A full tile: all three are the lane's first row.  A half
+            // tile has no quadrant 1 -- blocks MFQ.. of wave row 0 would be wave row 1's rows -- so those stores are aimed beyond the descriptor's
+            // range (dropped, but still issued: EPI_STORES counts them), except block MFQ of wave row 1 in an extended tile.  launch_ph8 checks
+            // (M + 256) ldh 2 < 2^31, so off_oor + mb * (16 rows) stays in [M ldh 2, 2^31) for mb = MFQ .. MB - 1.
+            [[maybe_unused]] int off_q0 = 0, off_b4 = 0, off_q1 = 0;
+            if constexpr (HR) {
+                off_q0 = (mrow0 * ldh + hcol) * 2;
+                const int off_oor = 0x7ffffff0 - (MB - 1) * 16 * ldh * 2;
+                off_q1 = s.half ? off_oor : off_q0;
+                off_b4 = (s.half && !(s.ext && wr == 1)) ? off_oor : off_q0;
+            }
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 const int m = mrow0 + mb * 16;
@@ -717,7 +794,8 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
                         continue;
                     }
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(ph8_u32x4{pk[0], pk[1], pk[2], pk[3]}, rsH, (m * ldh + hcol) * 2, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(ph8_u32x4{pk[0], pk[1], pk[2], pk[3]}, rsH,
+                                                       HR ? (mb < MFQ ? off_q0 : mb == MFQ ? off_b4 : off_q1) + mb * 16 * ldh * 2 : (m * ldh + hcol) * 2, 0, 0);
             }
         } else {   // EPI_HEADS: split into heads, LayerNorm fold, partial RoPE on d < 32 (transformer.py:158-183, 438-452)
             const HeadsEpi& he = g.heads;
@@ -929,10 +1007,14 @@ __global__ __launch_bounds__(512) void gemm_ph8_kernel(GemmArgs g, Ph8Sched sc, 
         __builtin_amdgcn_s_barrier();
         [[maybe_unused]] unsigned long long t0 = 0, t1 = 0, t2 = 0;
         if constexpr (DBG == 9) t0 = __builtin_amdgcn_s_memrealtime();
-        const int mq = cur.m0 + wr * WR;
+        const int mq = cur.m0 + wr * ((HR && cur.half) ? QR : WR);          // the wave's first row
         const bool rows_valid = mq < M;
-        if (cur.tr) main_loop(std::true_type{}, cur.kt0, cur.nk, rows_valid, mq + QR < M);
-        else main_loop(std::false_type{}, cur.kt0, cur.nk, rows_valid, mq + QR < M);
+        int q1_blocks = mq + QR < M ? MFQ : 0;
+        if constexpr (HR) {
+            if (cur.half) q1_blocks = (cur.ext && wr == 1) ? 1 : 0;
+        }
+        if (cur.tr) main_loop(std::true_type{}, cur.kt0, cur.nk, rows_valid, q1_blocks);
+        else main_loop(std::false_type{}, cur.kt0, cur.nk, rows_valid, q1_blocks);
         if constexpr (DBG == 9) t1 = __builtin_amdgcn_s_memrealtime();
         const bool more = next_seg(nxt);
         [[maybe_unused]] RopePre rp;
@@ -1015,9 +1097,12 @@ int ph8_cus(int& out) {
     return out > 0 ? 0 : SAT_E_INVALID;
 }
 
-int ph8_schedule(const GemmArgs& a, bool epi_f32, int bm, int bn, int wgs_per_cu, Ph8Sched& s) {
+int ph8_schedule(const GemmArgs& a, bool epi_f32, bool swiglu16, int bm, int bn, int wgs_per_cu, Ph8Sched& s) {
     int cus = 0;
     SAT_TRY(ph8_cus(cus));
+    // asked first: one full + at most one half tile per workgroup (16-bit SwiGLU, one to one and a half rounds); bit 27 / the balance bit: A/B
+    const bool hr_off = sat_variant_has(a.variant, SAT_VARIANT_HALF_ROWS_OFF) || sat_variant_has(a.variant, SAT_VARIANT_BALANCE_OFF);
+    if (bm == 256 && bn == 256 && wgs_per_cu == 1 && ph8_half_rows_ints(a.M, a.N, a.K, swiglu16, cus, hr_off, s)) return 0;
     // the automatic policy only splits when the caller's slab holds one accumulator image per workgroup -- the same condition the tile score
     // assumes (GemmShape::slab_ok); an undersized workspace runs the unsplit schedule.  A FORCED split keeps the hard error.
     const int split = sat_variant_split(a.variant);
@@ -1073,9 +1158,12 @@ int launch_ph8(const GemmArgs& a0, hipStream_t stream) {
         SAT_CHECK_ARG(!a.heads.xa_k, SAT_E_UNSUPPORTED, "gemm(8-phase): the fused cross-attention epilogue lives in the 128 x 64 tile");
     }
     Ph8Sched sc;
-    SAT_TRY(ph8_schedule(a, EPI == EPI_F32, BM, BN, 1, sc));
+    SAT_TRY(ph8_schedule(a, EPI == EPI_F32, EPI == EPI_SWIGLU && FP8 == 0 && DBG == 0, BM, BN, 1, sc));
     SAT_CHECK_ARG(GATED == (a0.gate != nullptr), SAT_E_INVALID, "gemm(8-phase): gated / plain build mismatch");
     auto kern = gemm_ph8_kernel<EPI, DBG, FP8, GATED>;
+    if constexpr (EPI == EPI_SWIGLU && FP8 == 0 && DBG == 0) {
+        if (sc.hr) kern = gemm_ph8_kernel<EPI, DBG, FP8, GATED, true>;
+    }
     SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS));
     unsigned long long* ts = nullptr;
 #ifdef SAT_GEMM_EXPERIMENTS

@@ -25,6 +25,8 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 //   bit  17     SAT_VARIANT_SPLIT_OFF       8-phase: never                                                launch_ph8, sat_gemm_f32_workspace_bytes
 //   bit  21     SAT_VARIANT_BALANCE_OFF     8-phase: no balanced rounds (A/B)                             launch_ph8
 //   bit  23     SAT_VARIANT_NO_KGROUP   never the two-K-group 128 x 128 tile (49)                         sat_gemm_route
+//   bit  27     SAT_VARIANT_HALF_ROWS_OFF   8-phase, 16-bit SwiGLU: no half-row schedule (ph8_half_rows_ints), i.e. the balanced
+//                                       rounds it replaced (A/B, and the bit-equality test of the two)   launch_ph8
 //   bits 24-26  tile policy (sat_tile_policy_bits / sat_wide_tile_of): sat_dit_cfg.tile_policy puts them there for every GEMM of a
 //               plan; the unit-level entry points leave them 0                                            sat_gemm_route
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -37,6 +39,7 @@ enum {
     SAT_VARIANT_SPLIT_OFF = 0x20000,
     SAT_VARIANT_BALANCE_OFF = 0x200000,
     SAT_VARIANT_NO_KGROUP = 0x800000,
+    SAT_VARIANT_HALF_ROWS_OFF = 0x8000000,
 };
 static inline int sat_variant_tile(int variant) { return variant & SAT_VARIANT_TILE; }
 static inline int sat_variant_ph8_code(int variant) { return (variant & SAT_VARIANT_CODE) % 100; }          // 80 / 81: the 8-phase kernel is forced

@@ -37,6 +37,12 @@ struct Ph8Sched {          // host-computed per launch (ph8_schedule), passed by
     int sk_q, sk_r;         // split 0: workgroup i takes sk_q (+ 1 if i < sk_r) consecutive remainder tiles
     int cls_n[3], cls_p[3]; // split 1: three consecutive classes of remainder tiles, cls_n[c] tiles of cls_p[c] parts each
     float* sk_slab;         // split 1: [G][65536] raw accumulator images (caller's workspace)
+    // the half-row schedule (ph8_half_rows_ints below).  hr = 1: the walk described above is empty (dp_rounds = sk_tiles = 0) and workgroup i takes
+    // full tile i (i < hr_full), then half tile i - (G - hr_half) (i >= G - hr_half)
+    int hr;
+    int hr_full, hr_half;   // full tiles, half tiles (128 rows of one column tile)
+    int hr_q, hr_r;         // row tiles cut into two half tiles: the LAST hr_q (+ 1 in the columns < hr_r) of every column
+    int hr_ext;             // 1: the last half tile of every column is extended by the 16-row block that holds the M tail
 };
 
 // units [b, e) of the remainder space (unit = 128 k of one tile, tile j = units [j nkp, (j + 1) nkp)) that workgroup i works on
@@ -103,6 +109,42 @@ SAT_HD void ph8_tile_of(const Ph8Sched& sc, int id, int& tm, int& tn) {
         tm = band * 8 + (rem - tn * gm);
     }
 }
+
+// ---- the half-row schedule: work-order index -> tile.  Column-major like the short-M order above (the W panel of a column stays in one
+// XCD's L2): column tn holds tiles_m_full - s(tn) full tiles on top of 2 s(tn) half tiles, s(tn) = hr_q + (tn < hr_r).
+SAT_HD void ph8_hr_full_of(const Ph8Sched& sc, int L, int& tm, int& tn) {
+    const int fa = sc.tiles_m_full - sc.hr_q - 1, fb = fa + 1;          // full tiles of a column < hr_r, of the others
+    const int na = sc.hr_r * fa;
+    if (L < na) {
+        tn = L / fa;
+        tm = L - tn * fa;
+    } else {
+        const int c = (L - na) / fb;
+        tn = sc.hr_r + c;
+        tm = L - na - c * fb;
+    }
+}
+// half tile j -> its first row r0 (a multiple of 128), its column tile, and whether it carries the M tail (rows [r0 + 128, M))
+SAT_HD void ph8_hr_half_of(const Ph8Sched& sc, int j, int& r0, int& tn, int& ext) {
+    const int ha = 2 * (sc.hr_q + 1), hb = 2 * sc.hr_q;                 // half tiles of a column < hr_r, of the others
+    const int na = sc.hr_r * ha;
+    int k, s;
+    if (j < na) {
+        tn = j / ha;
+        k = j - tn * ha;
+        s = sc.hr_q + 1;
+    } else {
+        const int c = (j - na) / hb;
+        tn = sc.hr_r + c;
+        k = j - na - c * hb;
+        s = sc.hr_q;
+    }
+    r0 = (sc.tiles_m_full - s) * 256 + k * 128;
+    ext = (sc.hr_ext && k == 2 * s - 1) ? 1 : 0;
+}
+// the (at most two) pieces of workgroup wgi, in the order it walks them: step 0 = its full tile, step 1 = its half tile
+SAT_HD bool ph8_hr_has_full(const Ph8Sched& sc, int wgi) { return wgi < sc.hr_full; }
+SAT_HD int ph8_hr_half_index(const Ph8Sched& sc, int wgi) { return wgi - (sc.G - sc.hr_half); }          // < 0: none
 
 // The walk of workgroup `wgi` (= xcd_remap(blockIdx.x, G)) over its work is the `next_seg` lambda of gemm_ph8_kernel: dp_rounds
 // whole tiles at work-order positions d * G + wgi, then the units [b, e) of ph8_wg_units, cut at tile borders.  It stays in the
@@ -182,6 +224,41 @@ inline long ph8_schedule_ints(int M, int N, int K, int split, bool epi_f32, int 
     }
     out = s;
     return 0;
+}
+
+// Half-row schedule of the remainder round (16-bit SwiGLU epilogue only; asked FIRST by the launcher, everything it refuses runs
+// ph8_schedule_ints above).  With t full 256 x 256 tiles on G compute units, G < t <= 1.5 G, two balanced rounds cost every workgroup two
+// tile slots for 1.5-1.6 tiles' worth of work.  Here every compute unit gets a workgroup with ONE full tile and at most ONE half tile (128
+// rows x 256 columns: the wave rows move together to a 64-row stride and each wave skips its second quadrant, the kernel's q_valid1 path --
+// half the MFMAs, the same MFMA shape and K order per output element, so bit-identical results).  S = t - G row tiles are cut in two,
+// the last ones of their columns.  An M tail of <= 16 rows rides on the last half tile of its column as one more 16-row block of wave row 1
+// ("extended": 8 more MFMAs per K-tile) instead of a light tile, so with a tail every column needs a cut tile: S = max(t - G, tiles_n).
+// Refused: any other epilogue or operand format, a tail of 17..255 rows, t <= G (one round), t > 1.5 G or 2 S > G (a workgroup would need
+// two half tiles).  FF-in at one prompt (2050 x 12288 x 1536, 256 CUs): 256 full + 256 half tiles, 48 of them extended, no light tile.
+// Measured (profiles/ffin_half_rows_timing.txt): a half tile costs 0.59-0.64 of a full one, the extended block nothing that shows; the
+// launch alone 82.4 -> 74.5 us (fp16) / 79.7 -> 71.5 (bf16), in the model 76.5 -> 73.1 us, a generation at one prompt -0.7 .. -1.1 %.
+inline bool ph8_half_rows_ints(int M, int N, int K, bool swiglu16, int cus, bool off, Ph8Sched& out) {
+    if (off || !swiglu16 || cus < 1 || M < 256 || N < 256 || N % 256 || K < 128 || K % 128) return false;
+    const int tail = M % 256;
+    if (tail > 16) return false;
+    const int tmf = M / 256, tiles_n = N / 256;
+    const long t = (long)tmf * tiles_n, G = cus;
+    if (!(t > G && 2 * t <= 3 * G)) return false;
+    const long S = (tail && t - G < tiles_n) ? tiles_n : t - G;
+    if (2 * S > G) return false;
+    Ph8Sched s{};
+    s.G = (int)G;
+    s.tiles_n = tiles_n;
+    s.tiles_m_full = tmf;
+    s.nkp = K / 128;
+    s.hr = 1;
+    s.hr_full = (int)(t - S);
+    s.hr_half = (int)(2 * S);
+    s.hr_q = (int)(S / tiles_n);
+    s.hr_r = (int)(S % tiles_n);
+    s.hr_ext = tail ? 1 : 0;
+    out = s;
+    return true;
 }
 
 }  // namespace
