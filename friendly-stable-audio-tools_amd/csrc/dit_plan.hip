@@ -28,6 +28,7 @@ struct Proj {
     op_t* w = nullptr;
     int n = 0, k = 0;
     ProjKind kind = PROJ_PLAIN;
+    int f16 = 0;          // 16-bit kinds: the operand format of its block (layer_f16), 1 = IEEE fp16
     float *scale = nullptr, *c1 = nullptr, *c2 = nullptr, *bias = nullptr;
 };
 enum ProjFamily { FAM_QKV, FAM_O, FAM_CQ, FAM_CKV, FAM_CO, FAM_FF1, FAM_FF2 };
@@ -53,6 +54,7 @@ struct sat_dit_plan {
     float *win_eff, *wout_eff;
     float *rope_cos, *rope_sin, *inv_freq;
     int f16 = 0;                    // cfg.gemm_dtype == 3: every 16-bit operand buffer holds IEEE fp16 and the fp16 build of the kernels runs
+    std::vector<int> block_f16;     // sat_dit_plan_set_block_formats: the same per block (layer_f16); empty = f16 for every block
     bool cross_fusion = true;       // cfg.cross_attention == 0: to_q + cross-attention core in one launch where it applies
     int tile_bits = 0;              // cfg.tile_policy as GemmArgs::variant bits (sat_tile_policy_bits)
     bool ln_fold = false;           // cfg.ln_fold, bf16 / fp16 operands, "prepend" conditioning: LayerNorms run inside the GEMM epilogues
@@ -114,9 +116,13 @@ const char* const kRangeSlotNames[SAT_DIT_RANGE_SLOTS] = {"a_qkv", "q", "k", "v"
 // One reduction of the range report over `scanned` contiguous 16-bit elements at buf, into slot `slot` of layer l; `logical` of them are values
 // of the model (the rest: zero pads of the layout).  Launched right behind the buffer's producer: the next layer reuses the buffer.  Nothing
 // without the report
+// Operand format of block l: every 16-bit buffer the block writes or reads (weight images, A / AO / Q / K / V^T / Hh, its slice of the
+// cross-attention cache) holds IEEE fp16 (1) or bf16 (0).  The residual stream between blocks is fp32, so neighbours may differ
+int layer_f16(const sat_dit_plan* p, int l) { return p->block_f16.empty() ? p->f16 : p->block_f16[l]; }
+
 int range_stats(const sat_dit_plan* p, int l, int slot, const op_t* buf, size_t scanned, size_t logical, hipStream_t s) {
     if (!p->rr) return 0;
-    return sat_launch_range_stats(buf, p->f16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16, 1, (int64_t)scanned, (int64_t)scanned, logical,
+    return sat_launch_range_stats(buf, layer_f16(p, l) ? SAT_GEMM_FP16 : SAT_GEMM_BF16, 1, (int64_t)scanned, (int64_t)scanned, logical,
                                   p->rr + (size_t)l * SAT_DIT_RANGE_SLOTS + slot, s);
 }
 
@@ -131,13 +137,15 @@ int copy_f32(sat_dit_plan* p, Bump& ar, const std::string& name, int64_t numel, 
 }
 
 // How the Linear of `family` in layer `l` runs.  e4m3 by the plan's families (to_kv has no e4m3 form: once per generation); the fold for the
-// LayerNorm-fed ones, except layer 0's to_qkv: its pre_norm reads rows written by the input projection, not by a GEMM epilogue
+// LayerNorm-fed ones, except layer 0's to_qkv: its pre_norm reads rows written by the input projection, not by a GEMM epilogue.  The same
+// for the first block of another operand format: the image the previous FF-out's epilogue could write would be in the writer's format
 ProjKind proj_kind(const sat_dit_plan* p, ProjFamily family, int l) {
     static const int fp8_bit[] = {SAT_FP8_QKV, SAT_FP8_TO_OUT, SAT_FP8_CROSS_Q, 0, SAT_FP8_TO_OUT, SAT_FP8_FF_IN, SAT_FP8_FF_OUT};
     const bool ln_fed = family == FAM_QKV || family == FAM_CQ || family == FAM_FF1;
     if (p->cfg.gemm_dtype == 2) return PROJ_F32;
     if (p->fp8_families & fp8_bit[family]) return ln_fed ? PROJ_FP8_ROW : PROJ_FP8_MX;
-    return p->ln_fold && ln_fed && !(family == FAM_QKV && l == 0) ? PROJ_LN_FOLD : PROJ_PLAIN;
+    const bool own_ln = family == FAM_QKV && (l == 0 || layer_f16(p, l) != layer_f16(p, l - 1));
+    return p->ln_fold && ln_fed && !own_ln ? PROJ_LN_FOLD : PROJ_PLAIN;
 }
 
 // Tensors `pf + weight` [n, k] and, where `bias` is given, `pf + bias` [n] into the arena in the form of the projection's kind.  interleave: the
@@ -147,7 +155,7 @@ int pack_proj(sat_dit_plan* p, Bump& ar, const std::string& pf, const char* weig
               int interleave, const float* gamma, const float* beta, Proj* out, hipStream_t s) {
     Proj& r = *out;
     r = Proj{};
-    r.n = n; r.k = k; r.kind = proj_kind(p, family, l);
+    r.n = n; r.k = k; r.kind = proj_kind(p, family, l); r.f16 = layer_f16(p, l);
     const bool fp8 = r.kind == PROJ_FP8_ROW || r.kind == PROJ_FP8_MX;
     r.w = (op_t*)ar.take((size_t)n * k * (r.kind == PROJ_F32 ? 4 : fp8 ? 1 : 2));
     if (fp8) r.scale = (float*)ar.take((size_t)n * 4);
@@ -162,8 +170,8 @@ int pack_proj(sat_dit_plan* p, Bump& ar, const std::string& pf, const char* weig
     if (bias) SAT_TRY(get_tensor(p, pf + bias, n, &b));
     if (r.kind == PROJ_F32) SAT_HIP(hipMemcpyAsync(r.w, src, (size_t)n * k * 4, hipMemcpyDeviceToDevice, s));
     else if (fp8) SAT_TRY(sat_launch_quant_rows_fp8(src, r.w, r.scale, n, k, interleave, s));
-    else if (r.kind == PROJ_LN_FOLD) SAT_TRY(sat_launch_pack_rows_ln(src, gamma, beta, b, r.w, r.c1, r.c2, n, k, interleave, s, p->f16));
-    else SAT_TRY(sat_launch_pack_rows_bf16(src, r.w, n, k, interleave, s, p->f16));
+    else if (r.kind == PROJ_LN_FOLD) SAT_TRY(sat_launch_pack_rows_ln(src, gamma, beta, b, r.w, r.c1, r.c2, n, k, interleave, s, r.f16));
+    else SAT_TRY(sat_launch_pack_rows_bf16(src, r.w, n, k, interleave, s, r.f16));
     if (!bias) return 0;
     if (interleave && r.kind != PROJ_F32) return sat_launch_pack_bias(b, r.bias, n, interleave, s);
     SAT_HIP(hipMemcpyAsync(r.bias, b, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
@@ -353,7 +361,7 @@ struct Forward {
     // The GemmArgs fields that follow from the projection's kind; the launch site adds what its epilogue needs
     GemmArgs gemm(const Proj& r, const op_t* A, int rows) const {
         GemmArgs g{};
-        g.f16 = p->f16; g.variant = p->tile_bits;
+        g.f16 = r.f16; g.variant = p->tile_bits;
         g.A = A; g.W = r.w; g.M = rows; g.N = r.n; g.K = r.k;
         g.bias = r.kind == PROJ_LN_FOLD ? nullptr : r.bias;          // the fold has it in c2
         if (r.kind == PROJ_LN_FOLD) { g.ln_part = w.ln_part; g.ln_c1 = r.c1; g.ln_c2 = r.c2; g.ln_eps = 1e-5f; }
@@ -370,8 +378,8 @@ struct Forward {
         if (r.kind == PROJ_LN_FOLD) return 0;
         if (r.kind == PROJ_FP8_ROW)
             return sat_launch_layernorm_fp8(w.X, gamma, beta, w.A, w.As, rows, D, sc, sh, modulated ? S : 1, modulated ? ssg_ld : 0, s);
-        if (modulated) return sat_launch_layernorm_mod(w.X, gamma, beta, w.A, rows, D, sc, sh, S, ssg_ld, s, p->f16);
-        return sat_launch_layernorm(w.X, gamma, beta, w.A, rows, D, s, p->f16);
+        if (modulated) return sat_launch_layernorm_mod(w.X, gamma, beta, w.A, rows, D, sc, sh, S, ssg_ld, s, r.f16);
+        return sat_launch_layernorm(w.X, gamma, beta, w.A, rows, D, s, r.f16);
     }
 
     // X += [gate (.)] (A W^T + bias), update `slot` (0 self-attention, 1 cross-attention, 2 feed-forward) of block l.  feeds_ln: a LayerNorm reads
@@ -431,7 +439,7 @@ int Forward::block_f32(int l) const {
 int Forward::attention_hd128(int l) const {
     const LayerW& L = p->layers[l];
     const float* m = mod(l);
-    const int f16 = p->f16, qn = p->qk_norm ? 16 : 0;
+    const int f16 = L.qkv.f16, qn = p->qk_norm ? 16 : 0;
     SAT_TRY(layernorm(L.qkv, L.pre_g, L.pre_b, M, true, m, m ? m + D : nullptr));
     SAT_TRY(range(l, RS_A_QKV, w.A, (size_t)M * D, (size_t)M * D));
     GemmArgs g = gemm(L.qkv, w.A, M);
@@ -472,7 +480,7 @@ int Forward::attention_hd128(int l) const {
 int Forward::block(int l) const {
     const LayerW& L = p->layers[l];
     const float* m = mod(l);
-    const int f16 = p->f16, qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
+    const int f16 = L.qkv.f16, qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
     auto mx_scales = [&](const Proj& out) { return out.kind == PROJ_FP8_MX ? w.AOs : nullptr; };      // the attention kernels write to_out's MXFP8 operand
     if (p->hd == 128) {
         SAT_TRY(attention_hd128(l));
@@ -552,7 +560,9 @@ int Forward::feed_forward(int l) const {
         p->prof_m = g.M; p->prof_nn = g.N; p->prof_k = g.K;
     }
     SAT_TRY(range(l, RS_FF_HIDDEN, w.Hh, (size_t)M * p->inner, (size_t)M * p->inner));
-    return resid(L.ff2, w.Hh, M, m ? m + 5 * D : nullptr, l + 1 < p->cfg.depth, l, 2);      // nobody normalises the output of the last block
+    // nobody normalises the output of the last block, and a next block of another format normalises the fp32 rows itself (proj_kind)
+    const bool feeds_ln = l + 1 < p->cfg.depth && layer_f16(p, l + 1) == layer_f16(p, l);
+    return resid(L.ff2, w.Hh, M, m ? m + 5 * D : nullptr, feeds_ln, l, 2);
 }
 
 int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const float* t_dev, float t_const, float* out, int bf,
@@ -753,6 +763,10 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
     const size_t o_kv32 = (cross && f32) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;
     const size_t o_ce32 = (cross && f32) ? lay.take_off((size_t)R * Dc * 4) : 0;
     const size_t o_kv128 = (cross && p->hd == 128) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;      // fp32 to_kv output in front of the head split
+    // blocks of both operand formats (sat_dit_plan_set_block_formats): a second image of the context embedding, in the other format than layer 0's
+    int mixed = 0;
+    for (int l = 1; l < c.depth; ++l) mixed |= layer_f16(p, l) != layer_f16(p, 0);
+    const size_t o_ce_other = (cross && !f32 && mixed) ? lay.take_off((size_t)R * Dc * 2) : 0;
     if (lay.off > p->ctx_buf.cap) SAT_HIP(hipStreamSynchronize(s));      // launches of the previous generation may still read the old buffer
     SAT_TRY(p->ctx_buf.reserve(lay.off));
     p->ge = (float*)(p->ctx_buf.ptr + o_ge);
@@ -782,14 +796,17 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
         float* ch = (float*)(p->ctx_buf.ptr + o_ch);
         op_t* ce = (op_t*)(p->ctx_buf.ptr + o_ce);
         SAT_TRY(glue_small_linear(cond, Dct, p->ce0_w, nullptr, nullptr, 0, ch, Dc, R, Dc, Dct, 1, 0, s));
-        SAT_TRY(glue_small_linear(ch, Dc, p->ce2_w, nullptr, nullptr, 0, ce, Dc, R, Dc, Dc, 0, p->f16 ? 2 : 1, s));
+        const int f16_0 = layer_f16(p, 0);
+        op_t* ce_other = mixed ? (op_t*)(p->ctx_buf.ptr + o_ce_other) : nullptr;
+        SAT_TRY(glue_small_linear(ch, Dc, p->ce2_w, nullptr, nullptr, 0, ce, Dc, R, Dc, Dc, 0, f16_0 ? 2 : 1, s));
+        if (mixed) SAT_TRY(glue_small_linear(ch, Dc, p->ce2_w, nullptr, nullptr, 0, ce_other, Dc, R, Dc, Dc, 0, f16_0 ? 1 : 2, s));
         SAT_HIP(hipMemsetAsync(p->kc, 0, kv_elems * 2, s));
         SAT_HIP(hipMemsetAsync(p->vct, 0, kv_elems * 2, s));
         const size_t per_layer = (size_t)bf * p->kvh_cross * lcpad * p->hd;
         for (int l = 0; l < c.depth; ++l) {
             GemmArgs g{};
-            g.f16 = p->f16;
-            g.A = ce; g.W = p->layers[l].ckv.w; g.M = R; g.N = 2 * Dc; g.K = Dc;
+            g.f16 = layer_f16(p, l);
+            g.A = g.f16 == f16_0 ? ce : ce_other; g.W = p->layers[l].ckv.w; g.M = R; g.N = 2 * Dc; g.K = Dc;
             if (p->hd == 128) {      // staged, as Forward::attention_hd128: fp32 [R, 2 Dc] -> head split (k: normalised under qk_norm, v transposed)
                 float* kv32 = (float*)(p->ctx_buf.ptr + o_kv128);
                 g.C = kv32; g.ldc = 2 * Dc;
@@ -798,7 +815,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
                 he.out[0] = p->kc + l * per_layer; he.out[1] = p->vct + l * per_layer;
                 he.kind[0] = 4 | (p->qk_norm ? 16 : 0); he.kind[1] = 1 | 4; he.parts = 2; he.heads = p->kvh_cross;
                 he.S = lc; he.Spad = lcpad;
-                SAT_TRY(sat_launch_head_split_hd128(kv32, he, bf, s, p->f16));
+                SAT_TRY(sat_launch_head_split_hd128(kv32, he, bf, s, g.f16));
                 SAT_TRY(range_stats(p, l, RS_CROSS_K, p->kc + l * per_layer, per_layer, (size_t)R * Dc, s));
                 SAT_TRY(range_stats(p, l, RS_CROSS_V, p->vct + l * per_layer, per_layer, (size_t)R * Dc, s));
                 continue;
@@ -876,6 +893,22 @@ extern "C" int sat_dit_plan_set_transformer_options(sat_dit_plan* p, const sat_d
     p->pos_emb = o->pos_emb;
     p->abs_max = o->pos_emb == SAT_DIT_POS_ABSOLUTE ? o->abs_pos_max_len : 0;
     p->rotary = o->rotary != 0;
+    return 0;
+}
+
+extern "C" int sat_dit_plan_set_block_formats(sat_dit_plan* p, const int32_t* formats, int32_t n) {
+    SAT_CHECK_ARG(p && formats, SAT_E_INVALID, "dit_plan_set_block_formats: null argument");
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_block_formats: plan already finalized (call it between create and finalize)");
+    // e4m3 plans choose their operand formats per GEMM family, the fp32 verification mode has no 16-bit operand
+    SAT_CHECK_ARG(p->cfg.gemm_dtype == SAT_GEMM_BF16 || p->cfg.gemm_dtype == SAT_GEMM_FP16, SAT_E_UNSUPPORTED,
+                  "dit_plan_set_block_formats: per-block formats need a plan with gemm_dtype bf16 or fp16, this plan has gemm_dtype %d", p->cfg.gemm_dtype);
+    SAT_CHECK_ARG(n == p->cfg.depth, SAT_E_INVALID, "dit_plan_set_block_formats: %d formats for a plan of depth %d", n, p->cfg.depth);
+    for (int l = 0; l < n; ++l)
+        SAT_CHECK_ARG(formats[l] == SAT_GEMM_BF16 || formats[l] == SAT_GEMM_FP16, SAT_E_INVALID,
+                      "dit_plan_set_block_formats: formats[%d] = %d is neither SAT_GEMM_BF16 (%d) nor SAT_GEMM_FP16 (%d)", l, formats[l], SAT_GEMM_BF16,
+                      SAT_GEMM_FP16);
+    p->block_f16.resize(n);
+    for (int l = 0; l < n; ++l) p->block_f16[l] = formats[l] == SAT_GEMM_FP16 ? 1 : 0;
     return 0;
 }
 

@@ -53,10 +53,12 @@ def get_args():
     p.add_argument("--batch-size", type=int, default=10)
     p.add_argument("--clip-length", action="store_true")
     p.add_argument("--seed", type=int, default=-1)
-    p.add_argument("--gemm-dtype", choices=["fp16", "bf16", "fp8", "fp8-all"], default=None,
+    p.add_argument("--gemm-dtype", choices=["fp16", "bf16", "fp8", "fp8-all", "auto"], default=None,
                    help="build extension: operand format of the transformer GEMMs / attention (and, for fp16 / bf16, the codec).  Default: the "
                         "package default (fp16, the reference's own GPU arithmetic); bf16 = 3-4 %% faster, 8x the operand rounding; fp8 = OCP e4m3 "
-                        "/ MXFP8 operands for the block GEMMs (BASELINE config 5)")
+                        "/ MXFP8 operands for the block GEMMs (BASELINE config 5); auto = fp16, and before generating the first batch runs once "
+                        "for 8 steps with the range reports on: the DiT blocks whose 16-bit buffers reach +-65504 are switched to bf16 "
+                        "(printed), every other block keeps fp16")
     p.add_argument("--codec-dtype", choices=["fp16", "bf16", "fp32"], default=None,
                    help="build extension: operand format of the VAE decoder, overriding the rule that ties it to --gemm-dtype.  fp32 = the "
                         "reference's full-precision decode (model_half=False) on the exact f32 MFMA, no fp16 range limit, slower")
@@ -155,11 +157,13 @@ def main():
             model.load_state_dict(synthetic.synth_state_dict(model.state_dict(), args.synthetic_weights))
     sample_rate, sample_size = model_config["sample_rate"], model_config["sample_size"]
     model = model.to(device).eval()
+    auto_formats = args.gemm_dtype == "auto"          # fp16 now; the blocks that need bf16 are chosen in front of the first batch
     if args.gemm_dtype is not None:
         from stable_audio_tools import _config
-        model.model.model.set_gemm_dtype(args.gemm_dtype)
+        gemm_dtype = "fp16" if auto_formats else args.gemm_dtype
+        model.model.model.set_gemm_dtype(gemm_dtype)
         if model.pretransform is not None:          # the codec follows by ONE rule (same in bench.py): fp16 with fp16, bf16 with bf16 and the e4m3 modes
-            model.pretransform.model.set_gemm_dtype(_config.codec_gemm_dtype(args.gemm_dtype))
+            model.pretransform.model.set_gemm_dtype(_config.codec_gemm_dtype(gemm_dtype))
     if args.codec_dtype is not None and model.pretransform is not None:
         model.pretransform.model.set_gemm_dtype(args.codec_dtype)
     if args.codec_final_tanh and model.pretransform is not None:
@@ -205,6 +209,15 @@ def main():
         call_seed = -1 if args.seed < 0 else args.seed + rank + world * i
         order = model.cross_attn_cond_ids + [k for k in cond if k not in model.cross_attn_cond_ids]
         cond = {k: cond[k] for k in order if k in cond}
+        if auto_formats and i == 0:          # every rank: each configures its own copy of the model, on its own first batch
+            from stable_audio_tools.inference.preflight import apply_fp16_range_fix, format_fp16_range
+            _, after = apply_fp16_range_fix(
+                model, steps=min(8, args.sample_steps), cfg_scale=args.cfg_scale, conditioning_tensors=cond, sample_size=sample_size, sigma_min=0.3,
+                sigma_max=500, sampler_type=args.sampler_type, device=str(device), seed=call_seed)
+            moved = [l for l, f in enumerate(model.model.model.block_gemm_dtypes) if f == "bf16"]
+            print(f"Rank-{rank}: --gemm-dtype auto: " + (f"DiT blocks {moved} run in bf16, the other {model.model.model.depth - len(moved)} in fp16"
+                                                          if moved else "no DiT block reaches the fp16 range, all stay in fp16"))
+            print("\n".join(format_fp16_range(after)))
         if args.check_fp16_range and i == 0 and rank == 0:
             from stable_audio_tools.inference.preflight import check_fp16_range, format_fp16_range
             print("\n".join(format_fp16_range(check_fp16_range(

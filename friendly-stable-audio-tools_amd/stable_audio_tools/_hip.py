@@ -82,6 +82,7 @@ _SIGNATURES = {
     "sat_dit_set_null_context_from": (c_int32, [c_void_p, c_int32]),
     "sat_dit_plan_set_extra_conditioning": (c_int32, [c_void_p, c_int32, c_int32, c_int32]),
     "sat_dit_plan_set_transformer_options": (c_int32, [c_void_p, POINTER(SatDitTransformerOptions), c_size_t]),
+    "sat_dit_plan_set_block_formats": (c_int32, [c_void_p, POINTER(c_int32), c_int32]),
     "sat_dit_prepare_extra_conditioning": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "sat_dit_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_dit_denoise_cfg": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int32, c_int32, c_void_p,

@@ -91,6 +91,7 @@ class DiffusionTransformer(nn.Module):
         self._ext_key = None
         self._gen_prepend = False
         self.gemm_dtype = _config.default_gemm_dtype()
+        self._block_gemm_dtypes = None      # set_block_gemm_dtypes: None = gemm_dtype in every block
         self.layernorm_fusion = True
         self.cross_attention_fusion = True
         self.tile_policy = 0
@@ -147,8 +148,9 @@ class DiffusionTransformer(nn.Module):
         never reads -- the GEMM operand ``A`` (LayerNorm output or, under the LayerNorm fold, the 16-bit image of the residual rows), ``q`` /
         ``k`` / ``v``, the two attention outputs, the SwiGLU hidden state and the per-generation cross K / V cache.  ``(True)`` switches it on;
         from then on ``prepare_generation`` and every forward / ``denoise`` ACCUMULATE, so a whole sampler run is covered, not its last step.
-        ``(False)`` returns one dict per layer and buffer -- ``layer``, ``buffer``, ``max_abs``, ``over_fp16`` (fp16 plan: elements that were
-        clamped at +-65504; bf16 plan: elements fp16 would clamp), ``nonfinite``, ``elements`` (0: this plan does not materialise the buffer),
+        ``(False)`` returns one dict per layer and buffer -- ``layer``, ``buffer``, ``max_abs``, ``format`` ("fp16" / "bf16": the operand format of the row's block; only on a
+        model with ``set_block_gemm_dtypes`` in effect, every other model has ``gemm_dtype`` in all rows), ``over_fp16`` (fp16 block: elements that were clamped at +-65504; bf16 block: elements fp16 would clamp),
+        ``nonfinite``, ``elements`` (0: this plan does not materialise the buffer),
         ``launches``, ``holds`` ("layernorm output" / "residual image" for the ``a_*`` buffers, else None) -- and switches it off.  Outputs are
         bit-identical with the report on and off.  The setting survives a plan rebuild (``set_gemm_dtype`` ...), the records collected so far
         do not.  fp16 / bf16 plans only."""
@@ -173,14 +175,18 @@ class DiffusionTransformer(nn.Module):
         # which a_* buffers hold the un-normalised residual image: sat_dit_plan_create's ln_fold rule and proj_kind (csrc/dit_plan.hip)
         fold = (self.layernorm_fusion and self.gemm_dtype in ("fp16", "bf16") and self.global_cond_type != "adaLN" and self.embed_dim >= 256
                 and self.transformer.dim_heads == 64)
+        formats = self.block_gemm_dtypes
         rows = []
         for i, r in enumerate(_hip.range_rows(buf, n)):
             layer, name = divmod(i, _hip.DIT_RANGE_SLOTS)
             name = _hip.DIT_RANGE_SLOT_NAMES[name]
             holds = None
             if name.startswith("a_"):
-                holds = "residual image" if fold and not (name == "a_qkv" and layer == 0) else "layernorm output"
+                own_ln = name == "a_qkv" and (layer == 0 or formats[layer] != formats[layer - 1])      # a format boundary: as block 0
+                holds = "residual image" if fold and not own_ln else "layernorm output"
             rows.append(dict(layer=layer, buffer=name, holds=holds, **r))
+            if self._block_gemm_dtypes is not None:
+                rows[-1]["format"] = formats[layer]
         return rows
 
     def reset_activation_range_report(self):
@@ -230,10 +236,38 @@ class DiffusionTransformer(nn.Module):
         if dtype not in GEMM_DTYPES:
             raise ValueError(f"gemm_dtype must be one of {sorted(GEMM_DTYPES)}")
         self._check_options(dtype)
-        if dtype != self.gemm_dtype:
+        if dtype != self.gemm_dtype or self._block_gemm_dtypes is not None:
             self.gemm_dtype = dtype
+            self._block_gemm_dtypes = None
             self._plan_version = None
         return self
+
+    def set_block_gemm_dtypes(self, formats):
+        """Build extension (``sat_dit_plan_set_block_formats``): the operand format per block, a list of ``depth`` names "fp16" / "bf16", or
+        ``None`` for ``gemm_dtype`` in every block again.  For a checkpoint where a few blocks leave the fp16 range
+        (``inference.preflight.choose_block_formats`` names them): those run in bf16, every other block keeps fp16's 8x finer operand rounding.
+        The residual stream between blocks is fp32; under the LayerNorm fusion a block behind a format change runs its first LayerNorm as the
+        standalone kernel (one more launch per change).  ``gemm_dtype`` must be "fp16" or "bf16"; a later ``set_gemm_dtype`` clears the list.
+        Rebuilds the plan on next use."""
+        if formats is not None:
+            if GEMM_DTYPES[self.gemm_dtype] not in (0, 3):
+                raise NotImplementedError(f"per-block operand formats with gemm_dtype={self.gemm_dtype!r}: the e4m3 modes choose their formats per GEMM "
+                                          "family and the fp32 verification mode has no 16-bit operand; set_gemm_dtype('fp16') or 'bf16' first")
+            formats = list(formats)
+            if len(formats) != self.depth:
+                raise ValueError(f"set_block_gemm_dtypes: {len(formats)} formats for a model of depth {self.depth}")
+            for f in formats:
+                if f not in ("fp16", "bf16"):
+                    raise ValueError(f"set_block_gemm_dtypes: every format must be 'fp16' or 'bf16', got {f!r}")
+        if formats != self._block_gemm_dtypes:
+            self._block_gemm_dtypes = formats
+            self._plan_version = None
+        return self
+
+    @property
+    def block_gemm_dtypes(self):
+        """The operand format every block runs in, a list of ``depth`` names: what ``set_block_gemm_dtypes`` set, else ``gemm_dtype``."""
+        return list(self._block_gemm_dtypes) if self._block_gemm_dtypes is not None else [self.gemm_dtype] * self.depth
 
     # ------------------------------------------------------------------ plan management
     def __del__(self):
@@ -269,6 +303,9 @@ class DiffusionTransformer(nn.Module):
             if options != (0, _hip.DIT_POS_NONE, 0, 1):       # a model with none of these switches never makes the call
                 opts = _hip.SatDitTransformerOptions(*options)
                 _hip.check(lib.sat_dit_plan_set_transformer_options(plan, ctypes.byref(opts), ctypes.sizeof(opts)))
+            if self._block_gemm_dtypes is not None:       # a model that never set them never makes the call
+                fm = (ctypes.c_int32 * self.depth)(*[GEMM_DTYPES[f] for f in self._block_gemm_dtypes])
+                _hip.check(lib.sat_dit_plan_set_block_formats(plan, fm, self.depth))
             if self._range_report:        # the report belongs to the module: a rebuilt plan starts with it on (and with empty records)
                 _hip.check(lib.sat_dit_range_report(plan, 1))
 

@@ -194,6 +194,19 @@ typedef struct sat_dit_transformer_options {
 } sat_dit_transformer_options;
 int sat_dit_plan_set_transformer_options(sat_dit_plan* plan, const sat_dit_transformer_options* options, size_t options_bytes);
 
+/* Operand format per block, between create and finalize: formats[l] is SAT_GEMM_FP16 or SAT_GEMM_BF16 for block l, n == depth.  A plan never
+ * given this call, or given gemm_dtype in every entry, runs every block in gemm_dtype and builds and launches exactly what it did before this
+ * call existed.  Block l then keeps its 16-bit weight images, every 16-bit activation buffer it writes (LayerNorm outputs, q / k / v, attention
+ * outputs, the SwiGLU hidden state) and its slice of the cross-attention K / V cache in formats[l] and runs that build of the kernels; the range
+ * report reads its buffers in that format.  The residual stream between blocks is fp32 in either case.  Meant for checkpoints where a few
+ * blocks leave the fp16 range (sat_dit_range_report): those run in bf16, the rest keep fp16's 8x finer operand rounding.
+ * Under ln_fold the first LayerNorm of a block whose format differs from the block before it runs as the standalone kernel (the image the
+ * previous epilogue would write is in the writer's format): one more launch per format boundary, as block 0 has anyway.
+ * Workspace and arena sizes do not change; with both formats in use sat_dit_prepare_context keeps a second 16-bit image of the context embedding.
+ * The plan's gemm_dtype must be SAT_GEMM_BF16 or SAT_GEMM_FP16 (SAT_E_UNSUPPORTED otherwise); n != depth or any other value is SAT_E_INVALID,
+ * a call after finalize SAT_E_STATE. */
+int sat_dit_plan_set_block_formats(sat_dit_plan* plan, const int32_t* formats, int32_t n);
+
 /* Checks that every required tensor was set, converts GEMM weights to bf16 (SwiGLU rows
  * interleaved), folds the 1x1 pre/post convs into the in/out projections, builds the RoPE
  * table.  Replaces nn.Module.load_state_dict for the DiT. */
