@@ -29,13 +29,18 @@ struct Proj {
     int n = 0, k = 0;
     ProjKind kind = PROJ_PLAIN;
     int f16 = 0;          // 16-bit kinds: the operand format of its block (layer_f16), 1 = IEEE fp16
+    bool nonorm = false;  // remove_norms: no LayerNorm in front, A is the residual row itself, rounded (Forward::layernorm)
+    bool image = false;   // ... and that rounding is already in A: the 16-bit image the previous residual epilogue wrote under ln_fold
     float *scale = nullptr, *c1 = nullptr, *c2 = nullptr, *bias = nullptr;
 };
-enum ProjFamily { FAM_QKV, FAM_O, FAM_CQ, FAM_CKV, FAM_CO, FAM_FF1, FAM_FF2 };
+enum ProjFamily { FAM_QKV, FAM_O, FAM_CQ, FAM_CKV, FAM_CO, FAM_FF1, FAM_FF2, FAM_CPW1, FAM_CGLU, FAM_CPW2 };      // the last three: the conformer's GEMMs
 
 struct LayerW {
     float *pre_g, *pre_b, *cross_g, *cross_b, *ff_g, *ff_b;
     Proj qkv, o, cq, ckv, co, ff1, ff2;
+    // ConformerModule (transformer.py:557-591): in_norm, pointwise_conv, glu.proj, depthwise_conv [D, 17] fp32, mid_norm, pointwise_conv_2
+    float *cin_g = nullptr, *cin_b = nullptr, *cmid_g = nullptr, *cmid_b = nullptr, *cdw = nullptr;
+    Proj cpw1, cglu, cpw2;
 };
 
 }  // namespace
@@ -71,6 +76,11 @@ struct sat_dit_plan {
     bool rotary = true;             // rotary_pos_emb=False: no inv_freq tensor, the rotation table is the identity (cos 1, sin 0)
     float* pos_table = nullptr;     // [pos_rows, D] fp32, position = row of the sequence (0 = first prepended row)
     int pos_rows = 0;
+    // TransformerBlock options off the shipped configs' path (sat_dit_plan_set_block_options); the defaults change nothing
+    bool conformer = false;         // x += conformer(x) behind the cross-attention update (Forward::conformer)
+    bool remove_norms = false;      // pre_norm / cross_attend_norm / ff_norm are the identity (Proj::nonorm)
+    bool ff_glu = true;             // false: ff.ff.0 is Linear + SiLU, FF-in runs with the plain-activation epilogue (EPI_ACT16)
+    bool block_options() const { return conformer || remove_norms || !ff_glu; }
     // per-generation context (sat_dit_prepare_context)
     DevBuf ctx_buf;
     int ctx_bf = 0, ctx_lc = 0, ctx_lcpad = 0;
@@ -139,13 +149,22 @@ int copy_f32(sat_dit_plan* p, Bump& ar, const std::string& name, int64_t numel, 
 // How the Linear of `family` in layer `l` runs.  e4m3 by the plan's families (to_kv has no e4m3 form: once per generation); the fold for the
 // LayerNorm-fed ones, except layer 0's to_qkv: its pre_norm reads rows written by the input projection, not by a GEMM epilogue.  The same
 // for the first block of another operand format: the image the previous FF-out's epilogue could write would be in the writer's format
+// Whether A holds the 16-bit image of the residual rows (and ln_part their statistics) when the projection of `family` in layer l runs
+bool has_image(const sat_dit_plan* p, ProjFamily family, int l) {
+    const bool own_ln = family == FAM_QKV && (l == 0 || layer_f16(p, l) != layer_f16(p, l - 1));
+    return p->ln_fold && !own_ln;
+}
+// remove_norms takes the LayerNorm from in front of the block's three projections; the conformer's in_norm stays
+bool norm_removed(const sat_dit_plan* p, ProjFamily family) {
+    return p->remove_norms && (family == FAM_QKV || family == FAM_CQ || family == FAM_FF1);
+}
 ProjKind proj_kind(const sat_dit_plan* p, ProjFamily family, int l) {
-    static const int fp8_bit[] = {SAT_FP8_QKV, SAT_FP8_TO_OUT, SAT_FP8_CROSS_Q, 0, SAT_FP8_TO_OUT, SAT_FP8_FF_IN, SAT_FP8_FF_OUT};
-    const bool ln_fed = family == FAM_QKV || family == FAM_CQ || family == FAM_FF1;
+    static const int fp8_bit[] = {SAT_FP8_QKV, SAT_FP8_TO_OUT, SAT_FP8_CROSS_Q, 0, SAT_FP8_TO_OUT, SAT_FP8_FF_IN, SAT_FP8_FF_OUT, 0, 0, 0};
+    const bool ln_fed = family == FAM_QKV || family == FAM_CQ || family == FAM_FF1 || family == FAM_CPW1;
     if (p->cfg.gemm_dtype == 2) return PROJ_F32;
     if (p->fp8_families & fp8_bit[family]) return ln_fed ? PROJ_FP8_ROW : PROJ_FP8_MX;
-    const bool own_ln = family == FAM_QKV && (l == 0 || layer_f16(p, l) != layer_f16(p, l - 1));
-    return p->ln_fold && ln_fed && !own_ln ? PROJ_LN_FOLD : PROJ_PLAIN;
+    if (norm_removed(p, family)) return PROJ_PLAIN;
+    return ln_fed && has_image(p, family, l) ? PROJ_LN_FOLD : PROJ_PLAIN;
 }
 
 // Tensors `pf + weight` [n, k] and, where `bias` is given, `pf + bias` [n] into the arena in the form of the projection's kind.  interleave: the
@@ -156,6 +175,8 @@ int pack_proj(sat_dit_plan* p, Bump& ar, const std::string& pf, const char* weig
     Proj& r = *out;
     r = Proj{};
     r.n = n; r.k = k; r.kind = proj_kind(p, family, l); r.f16 = layer_f16(p, l);
+    r.nonorm = norm_removed(p, family);
+    r.image = r.nonorm && r.kind == PROJ_PLAIN && has_image(p, family, l);
     const bool fp8 = r.kind == PROJ_FP8_ROW || r.kind == PROJ_FP8_MX;
     r.w = (op_t*)ar.take((size_t)n * k * (r.kind == PROJ_F32 ? 4 : fp8 ? 1 : 2));
     if (fp8) r.scale = (float*)ar.take((size_t)n * 4);
@@ -247,20 +268,39 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         if (c.adaln && !ar.dry()) {   // transformer.py:651-655: Sequential(SiLU, Linear(D, 6D, bias=False)) -> key "...1.weight"
             SAT_TRY(p->tensors.copy("dit", pf + "to_scale_shift_gate.1.weight", (int64_t)6 * D * D, p->ssg_w + (size_t)l * 6 * D * D, s));
         }
-        SAT_TRY(copy_f32(p, ar, pf + "pre_norm.gamma", D, &L.pre_g, s));
-        SAT_TRY(copy_f32(p, ar, pf + "pre_norm.beta", D, &L.pre_b, s));
-        SAT_TRY(copy_f32(p, ar, pf + "ff_norm.gamma", D, &L.ff_g, s));
-        SAT_TRY(copy_f32(p, ar, pf + "ff_norm.beta", D, &L.ff_b, s));
+        L.pre_g = L.pre_b = L.cross_g = L.cross_b = L.ff_g = L.ff_b = nullptr;      // remove_norms (transformer.py:621,632,642): nn.Identity, no tensors
+        if (!p->remove_norms) {
+            SAT_TRY(copy_f32(p, ar, pf + "pre_norm.gamma", D, &L.pre_g, s));
+            SAT_TRY(copy_f32(p, ar, pf + "pre_norm.beta", D, &L.pre_b, s));
+            SAT_TRY(copy_f32(p, ar, pf + "ff_norm.gamma", D, &L.ff_g, s));
+            SAT_TRY(copy_f32(p, ar, pf + "ff_norm.beta", D, &L.ff_b, s));
+        }
         SAT_TRY(pack("self_attn.to_qkv.weight", nullptr, FAM_QKV, 3 * D, D, 0, L.pre_g, L.pre_b, &L.qkv));
         SAT_TRY(pack("self_attn.to_out.weight", nullptr, FAM_O, D, D, 0, nullptr, nullptr, &L.o));
         if (Dct > 0) {
-            SAT_TRY(copy_f32(p, ar, pf + "cross_attend_norm.gamma", D, &L.cross_g, s));
-            SAT_TRY(copy_f32(p, ar, pf + "cross_attend_norm.beta", D, &L.cross_b, s));
+            if (!p->remove_norms) {
+                SAT_TRY(copy_f32(p, ar, pf + "cross_attend_norm.gamma", D, &L.cross_g, s));
+                SAT_TRY(copy_f32(p, ar, pf + "cross_attend_norm.beta", D, &L.cross_b, s));
+            }
             SAT_TRY(pack("cross_attn.to_q.weight", nullptr, FAM_CQ, D, D, 0, L.cross_g, L.cross_b, &L.cq));
             SAT_TRY(pack("cross_attn.to_kv.weight", nullptr, FAM_CKV, 2 * Dc, Dc, 0, nullptr, nullptr, &L.ckv));
             SAT_TRY(pack("cross_attn.to_out.weight", nullptr, FAM_CO, D, D, 0, nullptr, nullptr, &L.co));
         }
-        SAT_TRY(pack("ff.ff.0.proj.weight", "ff.ff.0.proj.bias", FAM_FF1, 2 * inner, D, 1, L.ff_g, L.ff_b, &L.ff1));
+        if (p->conformer) {      // (behind the attention tensors in the arena; a plan without the option places nothing here)
+            SAT_TRY(copy_f32(p, ar, pf + "conformer.in_norm.gamma", D, &L.cin_g, s));
+            SAT_TRY(copy_f32(p, ar, pf + "conformer.in_norm.beta", D, &L.cin_b, s));
+            SAT_TRY(copy_f32(p, ar, pf + "conformer.mid_norm.gamma", D, &L.cmid_g, s));
+            SAT_TRY(copy_f32(p, ar, pf + "conformer.mid_norm.beta", D, &L.cmid_b, s));
+            SAT_TRY(copy_f32(p, ar, pf + "conformer.depthwise_conv.weight", (int64_t)D * 17, &L.cdw, s));
+            SAT_TRY(pack("conformer.pointwise_conv.weight", nullptr, FAM_CPW1, D, D, 0, L.cin_g, L.cin_b, &L.cpw1));
+            SAT_TRY(pack("conformer.glu.proj.weight", "conformer.glu.proj.bias", FAM_CGLU, 2 * D, D, 1, nullptr, nullptr, &L.cglu));
+            SAT_TRY(pack("conformer.pointwise_conv_2.weight", nullptr, FAM_CPW2, D, D, 0, nullptr, nullptr, &L.cpw2));
+        }
+        // ff_kwargs glu=False (transformer.py:262-268): Sequential(Identity, Linear(D, inner, bias=not no_bias), Identity, SiLU) -> keys "ff.ff.0.1.*"
+        if (!p->ff_glu)
+            SAT_TRY(pack("ff.ff.0.1.weight", p->tensors.has(pf + "ff.ff.0.1.bias") ? "ff.ff.0.1.bias" : nullptr, FAM_FF1, inner, D, 0, L.ff_g, L.ff_b, &L.ff1));
+        else
+            SAT_TRY(pack("ff.ff.0.proj.weight", "ff.ff.0.proj.bias", FAM_FF1, 2 * inner, D, 1, L.ff_g, L.ff_b, &L.ff1));
         // ff_kwargs no_bias (transformer.py:270): the output Linear of the feed-forward has no bias tensor; FF-out then runs without one
         SAT_TRY(pack("ff.ff.2.weight", p->tensors.has(pf + "ff.ff.2.bias") ? "ff.ff.2.bias" : nullptr, FAM_FF2, D, inner, 0, nullptr, nullptr, &L.ff2));
     }
@@ -300,6 +340,7 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     const int S = seq_len(p, T, P);
     const size_t M = (size_t)bf * S;
     const int Spad = (int)round_up(S + 3, 128);
+    const int hid = p->conformer && D > p->inner ? D : p->inner;      // Hh: the FF hidden state [M, inner]; the conformer's GLU output [M, D] as well
     Workspace w;
     Bump ws{base};
     w.X = (float*)ws.take(M * D * 4);
@@ -310,7 +351,7 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
         w.Q = (op_t*)ws.take(w.qkv_bytes);
         w.K = (op_t*)ws.take(w.qkv_bytes);
         w.Vt = (op_t*)ws.take(w.qkv_bytes);
-        w.Hh = (op_t*)ws.take(M * (size_t)p->inner * 4);
+        w.Hh = (op_t*)ws.take(M * (size_t)hid * 4);
         w.f32_wide = (float*)ws.take(M * (size_t)(2 * p->inner > 3 * D ? 2 * p->inner : 3 * D) * 4);     // [M, 3D] qkv / [M, 2 inner] FF-in
         w.ff = (float*)ws.take((size_t)bf * 256 * 4);
         w.h1 = (float*)ws.take((size_t)bf * D * 4);
@@ -328,7 +369,7 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     w.Q = (op_t*)ws.take(w.qkv_bytes);
     w.K = (op_t*)ws.take(w.qkv_bytes);
     w.Vt = (op_t*)ws.take(w.qkv_bytes);
-    w.Hh = (op_t*)ws.take(M * (size_t)p->inner * 2);
+    w.Hh = (op_t*)ws.take(M * (size_t)hid * 2);
     w.ff = (float*)ws.take((size_t)bf * 256 * 4);
     w.h1 = (float*)ws.take((size_t)bf * D * 4);
     w.mo = (float*)ws.take((size_t)bf * c.io_channels * T * 4);
@@ -376,6 +417,10 @@ struct Forward {
     // LayerNorms of transformer.py:692, 695, 700 are finished in the epilogues of their consumers).  modulated: the adaLN form (sc / sh may be null)
     int layernorm(const Proj& r, const float* gamma, const float* beta, int rows, bool modulated, const float* sc, const float* sh) const {
         if (r.kind == PROJ_LN_FOLD) return 0;
+        if (r.nonorm) {      // remove_norms: the rounded row (modulated under adaLN, transformer.py:672,686); under the fold A already holds it
+            if (r.image) return 0;
+            return sat_launch_round_rows(w.X, w.A, rows, D, modulated ? sc : nullptr, sh, S, ssg_ld, r.f16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16, s);
+        }
         if (r.kind == PROJ_FP8_ROW)
             return sat_launch_layernorm_fp8(w.X, gamma, beta, w.A, w.As, rows, D, sc, sh, modulated ? S : 1, modulated ? ssg_ld : 0, s);
         if (modulated) return sat_launch_layernorm_mod(w.X, gamma, beta, w.A, rows, D, sc, sh, S, ssg_ld, s, r.f16);
@@ -391,7 +436,7 @@ struct Forward {
         if (slot == 2) { g.slab = w.slab; g.slab_bytes = w.slab_bytes; }          // FF-out: the one reduction long enough to split (carve)
         if (feeds_ln && p->ln_fold) { g.xb = w.A; g.ln_part_out = w.ln_part; }
         SAT_TRY(sat_launch_gemm(EPI_RESID, g, s));
-        return p->dbg ? glue_resid_stats(w.X, rows, D, p->dbg + ((size_t)l * 3 + slot) * 4, s) : 0;
+        return p->dbg && slot >= 0 ? glue_resid_stats(w.X, rows, D, p->dbg + ((size_t)l * 3 + slot) * 4, s) : 0;      // (slot -1: the conformer's update, not in the table)
     }
 
     int range(int l, int slot, const op_t* buf, size_t scanned, size_t logical) const { return range_stats(p, l, slot, buf, scanned, logical, s); }
@@ -403,6 +448,7 @@ struct Forward {
     int block(int l) const;
     int block_f32(int l) const;
     int attention_hd128(int l) const;
+    int conformer(int l) const;
     int feed_forward(int l) const;
 };
 
@@ -413,22 +459,40 @@ int Forward::block_f32(int l) const {
     const int inner = p->inner;
     float *A32 = (float*)w.A, *AO32 = (float*)w.AO, *Q32 = (float*)w.Q, *K32 = (float*)w.K, *V32 = (float*)w.Vt, *H32 = (float*)w.Hh;
     auto W32 = [](const Proj& r) { return (const float*)r.w; };
-    SAT_TRY(sat_launch_layernorm_f32(w.X, L.pre_g, L.pre_b, A32, M, D, m, m ? m + D : nullptr, S, ssg_ld, s));
+    // the LayerNorm in front of a projection, or under remove_norms the row itself (modulated under adaLN)
+    auto norm = [&](const float* gamma, const float* beta, int rows, const float* sc, const float* sh, int rps, int ld) {
+        if (p->remove_norms) return sat_launch_round_rows(w.X, A32, rows, D, sc, sh, rps, ld, SAT_GEMM_FP32X, s);
+        return sat_launch_layernorm_f32(w.X, gamma, beta, A32, rows, D, sc, sh, rps, ld, s);
+    };
+    SAT_TRY(norm(L.pre_g, L.pre_b, M, m, m ? m + D : nullptr, S, ssg_ld));
     SAT_TRY(sat_launch_gemm_f32(A32, W32(L.qkv), nullptr, w.f32_wide, M, 3 * D, D, 3 * D, 0, nullptr, 1, 0, s));
     SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
     SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
     SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.o), nullptr, w.X, M, D, D, D, 1, m ? m + 2 * D : nullptr, S, ssg_ld, s));
     if (bc > 0) {
-        SAT_TRY(sat_launch_layernorm_f32(w.X, L.cross_g, L.cross_b, A32, Mc, D, nullptr, nullptr, 1, 0, s));
+        SAT_TRY(norm(L.cross_g, L.cross_b, Mc, nullptr, nullptr, 1, 0));
         SAT_TRY(sat_launch_gemm_f32(A32, W32(L.cq), nullptr, w.f32_wide, Mc, D, D, D, 0, nullptr, 1, 0, s));
         SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
         const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lc * 64;
         SAT_TRY(sat_launch_attention_f32(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, S, p->ctx_lc, s));
         SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.co), nullptr, w.X, Mc, D, D, D, 1, nullptr, 1, 0, s));
     }
-    SAT_TRY(sat_launch_layernorm_f32(w.X, L.ff_g, L.ff_b, A32, M, D, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr, S, ssg_ld, s));
-    SAT_TRY(sat_launch_gemm_f32(A32, W32(L.ff1), L.ff1.bias, w.f32_wide, M, 2 * inner, D, 2 * inner, 0, nullptr, 1, 0, s));
-    SAT_TRY(sat_launch_swiglu_f32(w.f32_wide, H32, M, inner, s));
+    if (p->conformer) {      // transformer.py:680-681, 697-698 (the launches of Forward::conformer in fp32)
+        SAT_TRY(sat_launch_layernorm_f32(w.X, L.cin_g, L.cin_b, A32, M, D, nullptr, nullptr, 1, 0, s));
+        SAT_TRY(sat_launch_gemm_f32(A32, W32(L.cpw1), nullptr, AO32, M, D, D, D, 0, nullptr, 1, 0, s));
+        SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.cglu), L.cglu.bias, w.f32_wide, M, 2 * D, D, 2 * D, 0, nullptr, 1, 0, s));
+        SAT_TRY(sat_launch_swiglu_f32(w.f32_wide, H32, M, D, s));
+        SAT_TRY(sat_launch_dwconv_ln_silu(H32, L.cdw, L.cmid_g, L.cmid_b, AO32, bf, S, D, SAT_GEMM_FP32X, s));
+        SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.cpw2), nullptr, w.X, M, D, D, D, 1, nullptr, 1, 0, s));
+    }
+    SAT_TRY(norm(L.ff_g, L.ff_b, M, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr, S, ssg_ld));
+    if (!p->ff_glu) {      // Linear + SiLU
+        SAT_TRY(sat_launch_gemm_f32(A32, W32(L.ff1), L.ff1.bias, H32, M, inner, D, inner, 0, nullptr, 1, 0, s));
+        SAT_TRY(sat_launch_silu_f32(H32, (int64_t)M * inner, s));
+    } else {
+        SAT_TRY(sat_launch_gemm_f32(A32, W32(L.ff1), L.ff1.bias, w.f32_wide, M, 2 * inner, D, 2 * inner, 0, nullptr, 1, 0, s));
+        SAT_TRY(sat_launch_swiglu_f32(w.f32_wide, H32, M, inner, s));
+    }
     return sat_launch_gemm_f32(H32, W32(L.ff2), L.ff2.bias, w.X, M, D, inner, D, 1, m ? m + 5 * D : nullptr, S, ssg_ld, s);
 }
 
@@ -530,7 +594,26 @@ int Forward::block(int l) const {
         SAT_TRY(range(l, RS_CROSS_ATTN_OUT, w.AO, (size_t)Mc * D, (size_t)Mc * D));
         SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
     }
+    if (p->conformer) SAT_TRY(conformer(l));
     return feed_forward(l);
+}
+
+// ---- conformer branch (transformer.py:680-681, 697-698; ConformerModule :576-591): x += conformer(x) on every sequence, not modulated by adaLN.
+// in_norm + pointwise_conv as one LayerNorm-fed GEMM with a 16-bit output (the fold applies as for to_qkv), glu as the FF-in SwiGLU GEMM at
+// inner dim D on that 16-bit output (the reference rounds between the two), depthwise_conv + mid_norm + SiLU in one pass, pointwise_conv_2 with
+// the residual epilogue of to_out.  Buffers: A -> AO -> Hh -> AO -> X
+int Forward::conformer(int l) const {
+    const LayerW& L = p->layers[l];
+    const int f16 = L.cpw1.f16;
+    SAT_TRY(layernorm(L.cpw1, L.cin_g, L.cin_b, M, false, nullptr, nullptr));
+    GemmArgs g = gemm(L.cpw1, w.A, M);
+    g.H = w.AO; g.act = 0;
+    SAT_TRY(sat_launch_gemm(EPI_ACT16, g, s));
+    g = gemm(L.cglu, w.AO, M);
+    g.H = w.Hh;
+    SAT_TRY(sat_launch_gemm(EPI_SWIGLU, g, s));
+    SAT_TRY(sat_launch_dwconv_ln_silu(w.Hh, L.cdw, L.cmid_g, L.cmid_b, w.AO, bf, S, D, f16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16, s));
+    return resid(L.cpw2, w.AO, M, nullptr, true, l, -1);
 }
 
 // ---- feed-forward branch (transformer.py:700)
@@ -553,7 +636,8 @@ int Forward::feed_forward(int l) const {
         }
         SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n], s));
     }
-    SAT_TRY(sat_launch_gemm(EPI_SWIGLU, g, s));
+    if (!p->ff_glu) g.act = 1;      // ff_kwargs glu=False: H [M, inner] = silu(A W^T + bias)
+    SAT_TRY(sat_launch_gemm(p->ff_glu ? EPI_SWIGLU : EPI_ACT16, g, s));
     if (prof) {
         SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n + 1], s));
         p->prof_n++;
@@ -707,11 +791,28 @@ extern "C" int sat_dit_plan_finalize(sat_dit_plan* p, sat_stream_t stream) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "dit_plan_finalize: null plan");
     hipStream_t s = (hipStream_t)stream;
     const int D = p->cfg.embed_dim;
-    const int64_t ff_numel = p->tensors.numel("transformer.layers.0.ff.ff.0.proj.weight");
-    SAT_CHECK_ARG(ff_numel > 0, SAT_E_MISSING, "dit plan: tensor 'transformer.layers.0.ff.ff.0.proj.weight' was never set");
-    SAT_CHECK_ARG(ff_numel % (2 * (int64_t)D) == 0, SAT_E_INVALID, "dit plan: FF weight size not divisible by 2*embed_dim");
-    p->inner = (int)(ff_numel / (2 * (int64_t)D));
-    SAT_CHECK_ARG(p->inner % 64 == 0, SAT_E_UNSUPPORTED, "dit plan: FF inner dim %d must be a multiple of 64", p->inner);
+    if (p->ff_glu) {
+        const int64_t ff_numel = p->tensors.numel("transformer.layers.0.ff.ff.0.proj.weight");
+        SAT_CHECK_ARG(ff_numel > 0, SAT_E_MISSING, "dit plan: tensor 'transformer.layers.0.ff.ff.0.proj.weight' was never set");
+        SAT_CHECK_ARG(ff_numel % (2 * (int64_t)D) == 0, SAT_E_INVALID, "dit plan: FF weight size not divisible by 2*embed_dim");
+        p->inner = (int)(ff_numel / (2 * (int64_t)D));
+        SAT_CHECK_ARG(p->inner % 64 == 0, SAT_E_UNSUPPORTED, "dit plan: FF inner dim %d must be a multiple of 64", p->inner);
+    } else {      // ff_glu 0: the input Linear is [inner, D] and all of its columns are outputs of the GEMM (N % 128)
+        const int64_t ff_numel = p->tensors.numel("transformer.layers.0.ff.ff.0.1.weight");
+        SAT_CHECK_ARG(ff_numel > 0, SAT_E_MISSING, "dit plan: tensor 'transformer.layers.0.ff.ff.0.1.weight' was never set");
+        SAT_CHECK_ARG(ff_numel % (int64_t)D == 0, SAT_E_INVALID, "dit plan: FF weight size not divisible by embed_dim");
+        p->inner = (int)(ff_numel / (int64_t)D);
+        SAT_CHECK_ARG(p->inner % 128 == 0, SAT_E_UNSUPPORTED, "dit plan: FF inner dim %d of a feed-forward without GLU must be a multiple of 128", p->inner);
+    }
+    if (p->conformer) {      // by name and before anything is allocated, as the FF weight above
+        static const char* const names[] = {"in_norm.gamma", "in_norm.beta", "pointwise_conv.weight", "glu.proj.weight", "glu.proj.bias",
+                                            "depthwise_conv.weight", "mid_norm.gamma", "mid_norm.beta", "pointwise_conv_2.weight"};
+        for (int l = 0; l < p->cfg.depth; ++l)
+            for (const char* n : names) {
+                const std::string name = "transformer.layers." + std::to_string(l) + ".conformer." + n;
+                SAT_CHECK_ARG(p->tensors.has(name), SAT_E_MISSING, "dit plan: tensor '%s' was never set", name.c_str());
+            }
+    }
     SAT_CHECK_ARG(p->cfg.gemm_dtype != 1 || p->inner % 128 == 0, SAT_E_UNSUPPORTED, "dit plan: gemm_dtype needs an FF inner dim that is a multiple of 128");
     p->wsq_bf = p->wsq_t = -1;
     return plan_finalize(p, s, [&](Bump& ar) { return build(p, ar, s); });
@@ -896,6 +997,29 @@ extern "C" int sat_dit_plan_set_transformer_options(sat_dit_plan* p, const sat_d
     return 0;
 }
 
+extern "C" int sat_dit_plan_set_block_options(sat_dit_plan* p, const sat_dit_block_options* o, size_t options_bytes) {
+    SAT_CHECK_ARG(p && o, SAT_E_INVALID, "dit_plan_set_block_options: null argument");
+    SAT_CHECK_ARG(options_bytes == sizeof(sat_dit_block_options), SAT_E_INVALID,
+                  "dit_plan_set_block_options: sat_dit_block_options of %zu bytes; this library knows %zu", options_bytes, sizeof(sat_dit_block_options));
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_block_options: plan already finalized (call it between create and finalize)");
+    SAT_CHECK_ARG((o->conformer == 0 || o->conformer == 1) && (o->remove_norms == 0 || o->remove_norms == 1) && (o->ff_glu == 0 || o->ff_glu == 1),
+                  SAT_E_UNSUPPORTED, "dit_plan_set_block_options: unknown value (conformer %d, remove_norms %d, ff_glu %d)", o->conformer, o->remove_norms,
+                  o->ff_glu);
+    const bool any = o->conformer || o->remove_norms || !o->ff_glu;
+    // the e4m3 epilogues and the quantising LayerNorm know neither a missing norm nor the plain activation; the staged 128-channel-head route
+    // keeps the standalone LayerNorms of the shipped block
+    SAT_CHECK_ARG(!any || p->cfg.gemm_dtype != SAT_GEMM_FP8, SAT_E_UNSUPPORTED,
+                  "dit_plan_set_block_options: conformer / remove_norms / ff_glu 0 with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
+    SAT_CHECK_ARG(!any || p->hd == 64, SAT_E_UNSUPPORTED, "dit_plan_set_block_options: conformer / remove_norms / ff_glu 0 with dim_heads 128 is not built");
+    SAT_CHECK_ARG(!any || (sat_launch_dwconv_ln_silu && sat_launch_round_rows && sat_launch_silu_f32), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_block_options: built without the block-option kernels");
+    SAT_CHECK_ARG(!any || !p->rr, SAT_E_UNSUPPORTED, "dit_plan_set_block_options: the range report has no rows for the buffers of these options (sat_dit_range_report off first)");
+    p->conformer = o->conformer != 0;
+    p->remove_norms = o->remove_norms != 0;
+    p->ff_glu = o->ff_glu != 0;
+    return 0;
+}
+
 extern "C" int sat_dit_plan_set_block_formats(sat_dit_plan* p, const int32_t* formats, int32_t n) {
     SAT_CHECK_ARG(p && formats, SAT_E_INVALID, "dit_plan_set_block_formats: null argument");
     SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_block_formats: plan already finalized (call it between create and finalize)");
@@ -1036,6 +1160,8 @@ extern "C" int sat_dit_range_report(sat_dit_plan* p, int32_t enable) {
     SAT_CHECK_ARG(p->cfg.gemm_dtype == SAT_GEMM_BF16 || p->cfg.gemm_dtype == SAT_GEMM_FP16, SAT_E_UNSUPPORTED,
                   "dit_range_report: the report reads 16-bit operand buffers (gemm_dtype bf16 or fp16), this plan has gemm_dtype %d", p->cfg.gemm_dtype);
     SAT_CHECK_ARG(sat_launch_range_stats, SAT_E_UNSUPPORTED, "dit_range_report: built without the range statistics kernel");
+    SAT_CHECK_ARG(!p->block_options(), SAT_E_UNSUPPORTED,
+                  "dit_range_report: no rows for the 16-bit buffers of a plan with conformer / remove_norms / ff_glu 0 (sat_dit_plan_set_block_options)");
     const size_t bytes = (size_t)p->cfg.depth * SAT_DIT_RANGE_SLOTS * sizeof(sat_range_record);
     if (enable == 2) {
         SAT_CHECK_ARG(p->rr, SAT_E_STATE, "dit_range_report: the report is not enabled, there is nothing to zero");

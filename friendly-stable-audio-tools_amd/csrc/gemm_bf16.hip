@@ -22,7 +22,8 @@
 
 namespace {
 
-// QKN (EPI_HEADS only): the instantiation behind EPI_HEADS_QKN -- parts with kind bit 4 are L2-normalised per head (qk_norm)
+// QKN: the alternative build of an epilogue.  EPI_HEADS: the instantiation behind EPI_HEADS_QKN -- parts with kind bit 4 are L2-normalised per
+// head (qk_norm).  EPI_SWIGLU: the one behind EPI_ACT16 -- H [M, N] = act(acc + bias), no value / gate pairing (GemmArgs::act)
 template <int EPI, int MI, int NI, bool LNC = false, bool QKN = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[MI][NI], const int mw, const int nw, const int half,
                                               const int l31, const float2* ln = nullptr, const float* lc1 = nullptr,
@@ -69,6 +70,25 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[M
 #pragma unroll
                             for (int j = 0; j < NI; ++j) C[(size_t)m * ldc + nw + j * 32 + l31] = acc[i][j][r] + bia[j] + old[r8][j];
                         }
+                    }
+                }
+            }
+    } else if constexpr (EPI == EPI_SWIGLU && QKN) {      // EPI_ACT16 (the 2-stage kernels: no LayerNorm fold here)
+        op_t* __restrict__ H = g.H;
+        const bool silu = g.act != 0;
+        float bia[NI];
+#pragma unroll
+        for (int j = 0; j < NI; ++j) bia[j] = g.bias ? g.bias[nw + j * 32 + l31] : 0.f;
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = mw + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (m < M) {
+#pragma unroll
+                    for (int j = 0; j < NI; ++j) {
+                        const float v = acc[i][j][r] + bia[j];
+                        H[(size_t)m * N + nw + j * 32 + l31] = f32_to_op(silu ? silu_f(v) : v);
                     }
                 }
             }
@@ -235,7 +255,50 @@ __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& g, f32x16 (&acc)
     const int M = g.M, N = g.N;
     (void)N;
     static_assert(EPI == EPI_SWIGLU || EPI == EPI_HEADS, "fp32 output is never transposed");
-    if constexpr (EPI == EPI_SWIGLU) {
+    if constexpr (EPI == EPI_SWIGLU && QKN) {      // EPI_ACT16: lane = token row m, 16 channels of each 32-column block in its registers
+        const bool silu = g.act != 0;
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+            const int m = mw + i * 32 + l31;
+            float2 st = {0.f, 1.f};
+            if constexpr (LNC) st = ln[i * 32 + l31];      // (mean, rstd) of the row under the LayerNorm fold, (0, 1) without it
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                float hv[16];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = j * 32 + 4 * half + q * 8;
+                    f32x4 c1 = {0.f, 0.f, 0.f, 0.f}, c2;
+                    if constexpr (LNC) {      // lc2: ln_c2 under the fold (the bias is part of it), else the bias or zeros
+                        c1 = *reinterpret_cast<const f32x4*>(lc1 + c);
+                        c2 = *reinterpret_cast<const f32x4*>(lc2 + c);
+                    } else {
+                        c2 = g.bias ? *reinterpret_cast<const f32x4*>(g.bias + nw + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float v = st.y * (acc[i][j][4 * q + e] - st.x * c1[e]) + c2[e];
+                        hv[4 * q + e] = silu ? silu_f(v) : v;
+                    }
+                }
+                unsigned pk[8];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    pk[2 * q] = pack_op2(hv[4 * q], hv[4 * q + 1]);
+                    pk[2 * q + 1] = pack_op2(hv[4 * q + 2], hv[4 * q + 3]);
+                }
+                half_swap(pk[0], pk[2]);      // 8 consecutive channels per lane: 16-byte stores (as the SwiGLU build below)
+                half_swap(pk[1], pk[3]);
+                half_swap(pk[4], pk[6]);
+                half_swap(pk[5], pk[7]);
+                if (m < M) {
+                    op_t* hrow = g.H + (size_t)m * N + nw + j * 32 + 8 * half;
+                    *reinterpret_cast<u32x4*>(hrow) = u32x4{pk[0], pk[1], pk[2], pk[3]};
+                    *reinterpret_cast<u32x4*>(hrow + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};
+                }
+            }
+        }
+    } else if constexpr (EPI == EPI_SWIGLU) {
         static_assert(NI == 2, "value block + gate block");
         const int ldh = N >> 1;
         const int hc0 = nw >> 1;                       // first hidden column of this wave's 32
@@ -498,8 +561,8 @@ __device__ __forceinline__ void gemm_epilogue_f32_staged(const GemmArgs& g, f32x
 template <int BM, int BN, int WM, int WN, int EPIX>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs g) {
     sat_f16_saturate();
-    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX;
-    constexpr bool QKN = EPIX == EPI_HEADS_QKN;
+    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX == EPI_ACT16 ? EPI_SWIGLU : EPIX;
+    constexpr bool QKN = EPIX == EPI_HEADS_QKN || EPIX == EPI_ACT16;      // the alternative build of the epilogue (gemm_epilogue)
     constexpr int NT = WM * WN * 64;
     constexpr int TM = BM / WM;
     constexpr int TN = BN / WN;
@@ -632,8 +695,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs g) {
 template <int BM, int BN, int WM, int WN, int EPIX>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs g) {
     sat_f16_saturate();
-    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX;
-    constexpr bool QKN = EPIX == EPI_HEADS_QKN;
+    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX == EPI_ACT16 ? EPI_SWIGLU : EPIX;
+    constexpr bool QKN = EPIX == EPI_HEADS_QKN || EPIX == EPI_ACT16;      // the alternative build of the epilogue (gemm_epilogue)
     constexpr int NT = WM * WN * 64;
     constexpr int TM = BM / WM;
     constexpr int TN = BN / WN;
@@ -777,9 +840,9 @@ __device__ __forceinline__ int lds_off_bk(int row, int chunk) {
 template <int BM, int BN, int BK, int WM, int WN, int NS, int EPIX, int FP8 = 0, int KG = 1, bool DIL = false>
 __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g) {
     sat_f16_saturate();
-    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX;          // EPI_HEADS_QKN: the heads kernel with the qk_norm epilogue
-    constexpr bool QKN = EPIX == EPI_HEADS_QKN;
-    static_assert(!QKN || FP8 == 0, "qk_norm: 16-bit operands only");
+    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX == EPI_ACT16 ? EPI_SWIGLU : EPIX;          // EPI_HEADS_QKN: the heads kernel with the qk_norm epilogue
+    constexpr bool QKN = EPIX == EPI_HEADS_QKN || EPIX == EPI_ACT16;      // the alternative build of the epilogue (gemm_epilogue)
+    static_assert(!QKN || FP8 == 0, "qk_norm / plain activation: 16-bit operands only");
     static_assert(KG == 1 || (KG == 2 && EPI == EPI_F32 && FP8 == 0 && BK == 64 && BM / WM == 64 && BN / WN == 64),
                   "K-groups: fp32 output, 64 x 64 wave tiles, 128-byte rows");
     constexpr int NT = KG * WM * WN * 64;
@@ -1404,7 +1467,7 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
 
 template <int BM, int BN, int BK, int WM, int WN, int NS, int EPIX, int FP8 = 0, int KG = 1, bool DIL = false>
 int launch_pipe(const GemmArgs& a, hipStream_t stream) {
-    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX;
+    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX == EPI_ACT16 ? EPI_SWIGLU : EPIX;
     constexpr int NT = KG * WM * WN * 64;
     constexpr bool LN_CONS = (EPI == EPI_SWIGLU || EPI == EPI_HEADS) && FP8 == 0;
     constexpr int LDS = NS * KG * ((BM + BN) * BK * 2 + (FP8 == 3 ? BM * 4 : 0)) + (LN_CONS ? (BM + BN) * 8 : 0);     // + (mean, rstd) per row, (c1, c2) per column
@@ -1558,7 +1621,13 @@ int SAT_OPNS::sat_launch_gemm(int epi, const GemmArgs& a, hipStream_t stream) {
             SAT_CHECK_ARG(!(a.heads.kind[pt] & 16) || !(a.heads.kind[pt] & 1), SAT_E_UNSUPPORTED, "gemm: qk_norm on a transposed destination");
         s.variant = (a.variant & ~(7 << SAT_TILE_POLICY_SHIFT)) | sat_tile_policy_bits(22);
     }
-    const GemmRoute r = sat_gemm_route(epi, s, cus);
+    // EPI_ACT16 is built into the ring tiles' SwiGLU kernels and routed as they are, with the 8-phase kernel out of the choice (as qk_norm)
+    const bool act16 = epi == EPI_ACT16;
+    if (act16) {
+        SAT_CHECK_ARG(!a.fp8 && !a.H8 && a.H && (a.act == 0 || a.act == 1), SAT_E_UNSUPPORTED, "gemm: the plain-activation epilogue takes 16-bit operands and writes a 16-bit H (act %d)", a.act);
+        s.variant = (a.variant & ~(7 << SAT_TILE_POLICY_SHIFT)) | sat_tile_policy_bits(22);
+    }
+    const GemmRoute r = sat_gemm_route(act16 ? EPI_SWIGLU : epi, s, cus);
     switch (r.msg) {
         case SAT_ROUTE_OK: break;
         case SAT_ROUTE_UNKNOWN_EPI: sat_set_error("gemm: unknown epilogue %d", epi); return SAT_E_INVALID;
@@ -1568,8 +1637,10 @@ int SAT_OPNS::sat_launch_gemm(int epi, const GemmArgs& a, hipStream_t stream) {
         default: sat_set_error("gemm: unknown variant %d (or not built for this epilogue)", r.tile); return SAT_E_INVALID;
     }
     SAT_CHECK_ARG(!qkn || r.family != SAT_GEMM_PH8, SAT_E_UNSUPPORTED, "gemm(8-phase): no qk_norm epilogue (variant %d forces the kernel)", a.variant);
+    SAT_CHECK_ARG(!act16 || r.family != SAT_GEMM_PH8, SAT_E_UNSUPPORTED, "gemm(8-phase): no plain-activation epilogue (variant %d forces the kernel)", a.variant);
     if (r.family == SAT_GEMM_PH8) return sat_launch_gemm_ph8(epi, r.ph8, a, stream);
     switch (epi) {
+        case EPI_ACT16: return launch_epi<EPI_ACT16, 0>(r.tile, a, stream);
         case EPI_SWIGLU: return launch_flavour<EPI_SWIGLU>(r, a, stream);
         case EPI_HEADS: return qkn ? launch_epi<EPI_HEADS_QKN, 0>(r.tile, a, stream) : launch_flavour<EPI_HEADS>(r, a, stream);
         default: return launch_flavour<EPI_F32>(r, a, stream);          // EPI_F32, EPI_RESID

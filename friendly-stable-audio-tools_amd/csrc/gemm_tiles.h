@@ -140,6 +140,10 @@ enum { EPI_F32 = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_HEADS = 3 };
 // Template argument only, never a caller's `epi` (sat_gemm_route answers for EPI_HEADS): the heads epilogue built with the per-head L2
 // normalisation of qk_norm (HeadsEpi::kind bit 4).  A separate instantiation so that the default heads kernels keep their code and registers.
 enum { EPI_HEADS_QKN = 4 };
+// A caller's `epi`, routed as EPI_SWIGLU on the ring tiles (the 8-phase kernel has no such build): H [M, N] (16-bit) = act(acc + bias), every
+// column of the wave tile an output -- GemmArgs::act 0 the identity (the conformer's pointwise_conv), 1 SiLU (ff_kwargs glu=False,
+// transformer.py:262-268).  Built as a separate instantiation of the SwiGLU kernels, as EPI_HEADS_QKN is of the heads kernels.
+enum { EPI_ACT16 = 5 };
 
 struct GemmShape {          // what the rule reads of a GemmArgs, the build and the device
     int M, N, K;

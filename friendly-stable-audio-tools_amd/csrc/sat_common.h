@@ -337,6 +337,8 @@ struct GemmArgs {
     // workspace), used by this launch only; nullptr = the remainder round's tiles stay whole.
     float* slab;
     size_t slab_bytes;
+    // EPI_ACT16: H [M, N] = act(acc + bias), 0 = identity, 1 = SiLU (gemm_tiles.h)
+    int act;
 };
 
 // bf16 build: checks a.f16 and forwards fp16 work to sat_launch_gemm_f16 (the fp16 build of the same file)
@@ -370,6 +372,19 @@ __attribute__((weak)) int sat_launch_rope_table_hd128(const float* inv_freq, flo
 // where the plans answer SAT_E_UNSUPPORTED to the request for a report and never reach it
 __attribute__((weak)) int sat_launch_range_stats(const void* x, int dtype, int64_t rows, int64_t cols, int64_t pitch, uint64_t counted,
                                                  sat_range_record* rec, hipStream_t s);
+// ---- block options (sat_dit_plan_set_block_options): conformer.hip.  WEAK as the launchers above: null in the host test driver, where a plan
+// with block options answers SAT_E_UNSUPPORTED.  fmt: SAT_GEMM_BF16 / SAT_GEMM_FP16 (16-bit rows) or SAT_GEMM_FP32X (fp32 rows, the verification mode)
+// The conformer's depthwise_conv (17 taps along the sequence, zero-padded by 8 at both ends of each of the b sequences of s_len rows), mid_norm
+// over d and SiLU in one pass: x [b * s_len, d] -> y [b * s_len, d], both of `fmt`; w [d, 17] fp32 (transformer.py:571-573, 583-586)
+__attribute__((weak)) int sat_launch_dwconv_ln_silu(const void* x, const float* w, const float* gamma, const float* beta, void* y, int b, int s_len,
+                                                    int d, int fmt, hipStream_t s);
+int sat_launch_dwconv_ln_silu_variant(const void* x, const float* w, const float* gamma, const float* beta, void* y, int b, int s_len, int d, int fmt,
+                                      int variant, hipStream_t s);      // unit_entry.hip only: 1 one row per workgroup, 2 LDS-staged tile (measurements)
+// remove_norms: the A operand of a projection is the residual row itself, y = x, or x * scale1p[b] + shift[b] under adaLN (b = row / rows_per_seq,
+// vectors ld apart; scale1p null: no modulation), rounded to `fmt`
+__attribute__((weak)) int sat_launch_round_rows(const float* x, void* y, int m, int d, const float* scale1p, const float* shift, int rows_per_seq,
+                                                int ld, int fmt, hipStream_t s);
+__attribute__((weak)) int sat_launch_silu_f32(float* h, int64_t n, hipStream_t s);      // fp32 verification mode: h = silu(h) in place (ff_kwargs glu=False)
 int sat_launch_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int sq, int sk, int sq_pad,
                                    int sk_pad, hipStream_t s);
 int sat_launch_head_split_hd128_f16(const float* x, const void* heads_epi, int b, hipStream_t s);

@@ -364,3 +364,30 @@ extern "C" int sat_gemm_mxfp8_f32(const void* a8, const void* a_scales, const vo
     g.C = c; g.ldc = n; g.accumulate = accumulate; g.a_bscale = (const unsigned*)a_scales; g.w_scale = w_scale; g.fp8 = 3;
     return sat_launch_gemm(EPI_F32, g, (hipStream_t)stream);
 }
+
+// the kernels of sat_dit_plan_set_block_options alone
+extern "C" int sat_dwconv_ln_silu_bf16(const void* x, const float* w, const float* gamma, const float* beta, void* y, int32_t b, int32_t s_len,
+                                       int32_t d, int32_t variant, sat_stream_t stream) {
+    return sat_launch_dwconv_ln_silu_variant(x, w, gamma, beta, y, b, s_len, d, SAT_GEMM_BF16, variant, (hipStream_t)stream);
+}
+extern "C" int sat_dwconv_ln_silu_f16(const void* x, const float* w, const float* gamma, const float* beta, void* y, int32_t b, int32_t s_len,
+                                      int32_t d, int32_t variant, sat_stream_t stream) {
+    return sat_launch_dwconv_ln_silu_variant(x, w, gamma, beta, y, b, s_len, d, SAT_GEMM_FP16, variant, (hipStream_t)stream);
+}
+static int gemm_act_impl(int f16, const void* a, const void* w, const float* bias, void* h, int32_t m, int32_t n, int32_t k, int32_t act,
+                         int32_t variant, sat_stream_t stream) {
+    SAT_CHECK_ARG(h, SAT_E_INVALID, "gemm_act: null output");
+    GemmArgs g{};
+    g.f16 = f16;
+    g.A = (const op_t*)a; g.W = (const op_t*)w; g.bias = bias; g.M = m; g.N = n; g.K = k;
+    g.H = (op_t*)h; g.act = act; g.variant = variant;
+    return sat_launch_gemm(EPI_ACT16, g, (hipStream_t)stream);
+}
+extern "C" int sat_gemm_act_bf16(const void* a, const void* w, const float* bias, void* h, int32_t m, int32_t n, int32_t k, int32_t act,
+                                 int32_t variant, sat_stream_t stream) {
+    return gemm_act_impl(0, a, w, bias, h, m, n, k, act, variant, stream);
+}
+extern "C" int sat_gemm_act_f16(const void* a, const void* w, const float* bias, void* h, int32_t m, int32_t n, int32_t k, int32_t act,
+                                int32_t variant, sat_stream_t stream) {
+    return gemm_act_impl(1, a, w, bias, h, m, n, k, act, variant, stream);
+}

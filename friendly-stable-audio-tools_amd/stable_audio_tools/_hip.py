@@ -35,6 +35,10 @@ class SatDitTransformerOptions(Structure):
 DIT_POS_NONE, DIT_POS_SINUSOIDAL, DIT_POS_ABSOLUTE = 0, 1, 2     # include/sat_hip.h: SAT_DIT_POS_*
 
 
+class SatDitBlockOptions(Structure):
+    _fields_ = [("conformer", c_int32), ("remove_norms", c_int32), ("ff_glu", c_int32)]
+
+
 class SatT5Cfg(Structure):
     _fields_ = [("vocab_size", c_int32), ("d_model", c_int32), ("d_kv", c_int32), ("d_ff", c_int32), ("num_layers", c_int32),
                 ("num_heads", c_int32), ("rel_buckets", c_int32), ("rel_max_distance", c_int32), ("gated_gelu", c_int32),
@@ -83,6 +87,7 @@ _SIGNATURES = {
     "sat_dit_plan_set_extra_conditioning": (c_int32, [c_void_p, c_int32, c_int32, c_int32]),
     "sat_dit_plan_set_transformer_options": (c_int32, [c_void_p, POINTER(SatDitTransformerOptions), c_size_t]),
     "sat_dit_plan_set_block_formats": (c_int32, [c_void_p, POINTER(c_int32), c_int32]),
+    "sat_dit_plan_set_block_options": (c_int32, [c_void_p, POINTER(SatDitBlockOptions), c_size_t]),
     "sat_dit_prepare_extra_conditioning": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "sat_dit_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_dit_denoise_cfg": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int32, c_int32, c_void_p,
@@ -151,6 +156,8 @@ _SIGNATURES = {
                                     c_int32, c_int32, c_int32, c_void_p]),
     "sat_qkv_rope_qknorm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                            c_int32, c_int32, c_int32, c_void_p]),
+    "sat_dwconv_ln_silu_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "sat_gemm_act_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "sat_gemm_resid_ln_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                          c_void_p]),
     "sat_gemm_swiglu_ln_bf16": (c_int32, [c_void_p] * 9 + [c_int32, c_int32, c_int32, c_int32, c_void_p]),
@@ -174,7 +181,7 @@ _SIGNATURES = {
 }
 
 # the same unit-level entry points on IEEE fp16 operands (gemm_dtype = 3): identical signatures
-for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_attention_hd128_bf16", "sat_head_split_hd128_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws", "sat_range_stats_bf16"):
+for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_attention_hd128_bf16", "sat_head_split_hd128_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws", "sat_range_stats_bf16", "sat_dwconv_ln_silu_bf16", "sat_gemm_act_bf16"):
     _SIGNATURES[_n.replace("bf16", "f16")] = _SIGNATURES[_n]
 
 _lib = None

@@ -27,6 +27,8 @@ class DiTWrapper(ConditionedDiffusionModel):
 
     def __init__(self, *args, **kwargs):
         super().__init__(supports_cross_attention=True, supports_global_cond=False, supports_input_concat=False)
+        # config-driven construction: the TransformerBlock options off the shipped configs' path (conformer, remove_norms, glu=False) are accepted
+        kwargs.setdefault("allow_block_options", True)
         self.model = DiffusionTransformer(*args, **kwargs)
         from . import _init
         if not _init._SKIP:

@@ -29,7 +29,10 @@ class DiffusionTransformer(nn.Module):
     def __init__(self, io_channels: int = 32, patch_size: int = 1, embed_dim: int = 768, cond_token_dim: int = 0,
                  project_cond_tokens: bool = True, global_cond_dim: int = 0, project_global_cond: bool = True,
                  input_concat_dim: int = 0, prepend_cond_dim: int = 0, depth: int = 12, num_heads: int = 8,
-                 transformer_type: str = "x-transformers", global_cond_type: str = "prepend", max_seq_len: int = 8192, **kwargs):
+                 transformer_type: str = "x-transformers", global_cond_type: str = "prepend", max_seq_len: int = 8192,
+                 allow_block_options: bool = False, **kwargs):
+        """``allow_block_options``: the TransformerBlock options ``conformer``, ``remove_norms`` and ``ff_kwargs={"glu": False}`` are off the
+        shipped configs' path and refused unless this is set; ``create_model_from_config`` and every other config-driven path set it."""
         super().__init__()
         if transformer_type != "continuous_transformer":
             raise NotImplementedError("only transformer_type='continuous_transformer' is implemented (the shipped DiT configs)")
@@ -78,7 +81,8 @@ class DiffusionTransformer(nn.Module):
         self.transformer = ContinuousTransformer(dim=embed_dim, depth=depth, dim_heads=embed_dim // num_heads,
                                                  dim_in=dim_in, dim_out=io_channels, cross_attend=cond_token_dim > 0,
                                                  cond_token_dim=cond_embed_dim,
-                                                 global_cond_dim=embed_dim if global_cond_type == "adaLN" else None, **kwargs)
+                                                 global_cond_dim=embed_dim if global_cond_type == "adaLN" else None,
+                                                 allow_block_options=allow_block_options, **kwargs)
         self.preprocess_conv = _init.conv1d(dim_in, dim_in, 1, bias=False, zero=True)
         self.postprocess_conv = _init.conv1d(io_channels, io_channels, 1, bias=False, zero=True)
 
@@ -106,6 +110,9 @@ class DiffusionTransformer(nn.Module):
                 0 if tr.rotary_pos_emb is None else 1)
 
     def _check_options(self, gemm_dtype):
+        if self.transformer.block_options != (0, 0, 1) and GEMM_DTYPES[gemm_dtype] == 1:
+            raise NotImplementedError(f"conformer / remove_norms / glu=False with gemm_dtype={gemm_dtype!r}: the e4m3 epilogues and the quantising "
+                                      "LayerNorm know neither a missing norm nor the plain SiLU; use gemm_dtype 'fp16', 'bf16' or 'fp32x'")
         if self.transformer.qk_norm and GEMM_DTYPES[gemm_dtype] == 1:
             raise NotImplementedError(f"attn_kwargs qk_norm=True with gemm_dtype={gemm_dtype!r}: the e4m3 projections have no normalising epilogue; "
                                       "use gemm_dtype 'fp16', 'bf16' or 'fp32x' for a qk_norm model")
@@ -155,6 +162,9 @@ class DiffusionTransformer(nn.Module):
         bit-identical with the report on and off.  The setting survives a plan rebuild (``set_gemm_dtype`` ...), the records collected so far
         do not.  fp16 / bf16 plans only."""
         lib = _hip.lib()
+        if enable and self.transformer.block_options != (0, 0, 1):
+            raise NotImplementedError("activation_range_report on a model with conformer / remove_norms / glu=False: the report has no rows for the "
+                                      "16-bit buffers these options add (the conformer's three, the SiLU hidden state)")
         if enable:
             self._range_report = True
             try:
@@ -284,7 +294,7 @@ class DiffusionTransformer(nn.Module):
 
     def _ensure_plan(self):
         ver = _init.params_version(self)
-        options = self.transformer_options()
+        options = self.transformer_options() + self.transformer.block_options
         if self._plan is not None and ver == self._plan_version and options == self._plan_options:
             return self._plan
         self._check_options(self.gemm_dtype)
@@ -300,9 +310,12 @@ class DiffusionTransformer(nn.Module):
         def configure(plan):
             if self.input_concat_dim > 0 or self.prepend_cond_dim > 0:
                 _hip.check(lib.sat_dit_plan_set_extra_conditioning(plan, self.input_concat_dim, self.prepend_cond_dim, self.max_prepend_len))
-            if options != (0, _hip.DIT_POS_NONE, 0, 1):       # a model with none of these switches never makes the call
-                opts = _hip.SatDitTransformerOptions(*options)
+            if options[:4] != (0, _hip.DIT_POS_NONE, 0, 1):       # a model with none of these switches never makes the call
+                opts = _hip.SatDitTransformerOptions(*options[:4])
                 _hip.check(lib.sat_dit_plan_set_transformer_options(plan, ctypes.byref(opts), ctypes.sizeof(opts)))
+            if options[4:] != (0, 0, 1):       # conformer / remove_norms / glu=False; likewise
+                bopts = _hip.SatDitBlockOptions(*options[4:])
+                _hip.check(lib.sat_dit_plan_set_block_options(plan, ctypes.byref(bopts), ctypes.sizeof(bopts)))
             if self._block_gemm_dtypes is not None:       # a model that never set them never makes the call
                 fm = (ctypes.c_int32 * self.depth)(*[GEMM_DTYPES[f] for f in self._block_gemm_dtypes])
                 _hip.check(lib.sat_dit_plan_set_block_formats(plan, fm, self.depth))

@@ -4,8 +4,9 @@ Mirror of the module tree of the reference's ``models/transformer.py`` (``LayerN
 ``GLU``/``FeedForward`` :211-287, ``Attention`` :290-554, ``TransformerBlock`` :594-702,
 ``RotaryEmbedding`` :99-155, ``AbsolutePositionalEmbedding`` / ``ScaledSinusoidalEmbedding`` :50-96,
 ``ContinuousTransformer`` :705-809) restricted to the options the HIP plan runs: those of the shipped DiT
-configs plus 128-channel heads, ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False`` and
-bias-free / ``mult``-sized feed-forwards.  These classes only *hold* parameters under the reference's
+configs plus 128-channel heads, ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False``,
+bias-free / ``mult``-sized feed-forwards and, behind the ``allow_block_options`` opt-in, ``conformer`` (:557-591), ``remove_norms``
+and feed-forwards without GLU.  These classes only *hold* parameters under the reference's
 names; the forward pass of the whole stack is one C-ABI call (``sat_dit_forward`` /
 ``sat_dit_denoise_cfg``) issued by ``models/dit.py``.  Unsupported options raise.
 """
@@ -61,19 +62,30 @@ class GLU(nn.Module):
         self.proj = _init.linear(dim_in, dim_out * 2)
 
 
+BLOCK_OPTIONS_HINT = ("pass allow_block_options=True to DiffusionTransformer (create_model_from_config and every config-driven path do): "
+                      "the option then runs on the HIP plan (sat_dit_plan_set_block_options)")
+
+
 class FeedForward(nn.Module):
-    def __init__(self, dim, mult=4, glu=True, no_bias=False, use_conv=False, zero_init_output=True, **unsupported):
+    def __init__(self, dim, mult=4, glu=True, no_bias=False, use_conv=False, zero_init_output=True, allow_block_options=False, **unsupported):
         super().__init__()
-        if not glu or use_conv or unsupported:
-            raise NotImplementedError("FeedForward options not supported by the HIP path (the FF-in GEMM has the SwiGLU epilogue only, no "
-                                      f"convolution): glu={glu} use_conv={use_conv} {sorted(unsupported)}")
+        if use_conv or unsupported:
+            raise NotImplementedError("FeedForward options not supported by the HIP path, with or without allow_block_options (use_conv needs GEMM "
+                                      f"operands shifted by a row per tap, which no kernel here has yet): use_conv={use_conv} {sorted(unsupported)}")
+        if not glu and not allow_block_options:
+            raise NotImplementedError(f"FeedForward glu={glu} (use_conv={use_conv}) is off the shipped configs' path: {BLOCK_OPTIONS_HINT}")
         inner_dim = int(dim * mult)
         if inner_dim <= 0 or inner_dim % 64:
             raise NotImplementedError(f"FeedForward mult={mult}: the HIP plan needs an inner dim that is a multiple of 64, got {inner_dim}")
-        self.no_bias = no_bias
-        # reference :222,270: GLU builds its own nn.Linear and keeps the bias; no_bias only drops the one of the output projection
+        if not glu and inner_dim % 128:
+            raise NotImplementedError(f"FeedForward mult={mult} with glu=False: every column of the input Linear is an output of the GEMM, whose N "
+                                      f"must be a multiple of 128, got inner dim {inner_dim}")
+        self.no_bias, self.glu = no_bias, bool(glu)
+        # reference :222,270: GLU builds its own nn.Linear and keeps the bias; no_bias only drops the one of the output projection.
+        # Without GLU (:262-268) the input Linear follows no_bias as well
         linear_out = _init.linear(inner_dim, dim, bias=not no_bias, zero=zero_init_output)
-        self.ff = nn.Sequential(GLU(dim, inner_dim), nn.Identity(), linear_out, nn.Identity())
+        linear_in = GLU(dim, inner_dim) if glu else nn.Sequential(nn.Identity(), _init.linear(dim, inner_dim, bias=not no_bias), nn.Identity(), nn.SiLU())
+        self.ff = nn.Sequential(linear_in, nn.Identity(), linear_out, nn.Identity())
 
 
 class Attention(nn.Module):
@@ -98,23 +110,45 @@ class Attention(nn.Module):
         self.to_out = _init.linear(dim, dim, bias=False, zero=zero_init_output)
 
 
+class ConformerModule(nn.Module):
+    """Parameters of the reference's ``ConformerModule`` (:557-591): ``in_norm`` -> ``pointwise_conv`` (1 x 1) -> ``glu`` -> 17-tap
+    ``depthwise_conv`` along the sequence -> ``mid_norm`` -> SiLU -> ``pointwise_conv_2``."""
+
+    def __init__(self, dim, norm_kwargs={}):
+        super().__init__()
+        self.dim = dim
+        self.in_norm = LayerNorm(dim, **norm_kwargs)
+        self.pointwise_conv = _init.conv1d(dim, dim, 1, bias=False)
+        self.glu = GLU(dim, dim)
+        self.depthwise_conv = _init.conv1d(dim, dim, 17, bias=False, groups=dim, padding=8)
+        self.mid_norm = LayerNorm(dim, **norm_kwargs)
+        self.swish = nn.SiLU()
+        self.pointwise_conv_2 = _init.conv1d(dim, dim, 1, bias=False)
+
+
 class TransformerBlock(nn.Module):
     def __init__(self, dim, dim_heads=64, cross_attend=False, dim_context=None, global_cond_dim=None, causal=False,
                  zero_init_branch_outputs=True, conformer=False, layer_ix=-1, remove_norms=False, attn_kwargs={}, ff_kwargs={},
-                 norm_kwargs={}):
+                 norm_kwargs={}, allow_block_options=False):
         super().__init__()
-        if conformer or remove_norms:
-            raise NotImplementedError("conformer / remove_norms are not supported by the HIP path")
+        if (conformer or remove_norms) and not allow_block_options:
+            raise NotImplementedError(f"conformer={conformer} / remove_norms={remove_norms} are off the shipped configs' path: {BLOCK_OPTIONS_HINT}")
+        if dim_heads != 64 and (conformer or remove_norms or not ff_kwargs.get("glu", True)):
+            raise NotImplementedError(f"conformer / remove_norms / glu=False with dim_heads={dim_heads}: the staged 128-channel-head route keeps the "
+                                      "shipped block (standalone LayerNorms, SwiGLU feed-forward); these options run with dim_heads=64")
         self.dim, self.dim_heads, self.cross_attend, self.dim_context = dim, dim_heads, cross_attend, dim_context
         self.layer_ix = layer_ix
-        self.pre_norm = LayerNorm(dim, **norm_kwargs)
+        self.remove_norms = bool(remove_norms)
+        norm = (lambda: nn.Identity()) if remove_norms else (lambda: LayerNorm(dim, **norm_kwargs))      # reference :621,632,642
+        self.pre_norm = norm()
         self.self_attn = Attention(dim, dim_heads=dim_heads, causal=causal, zero_init_output=zero_init_branch_outputs, **attn_kwargs)
         if cross_attend:
-            self.cross_attend_norm = LayerNorm(dim, **norm_kwargs)
+            self.cross_attend_norm = norm()
             self.cross_attn = Attention(dim, dim_heads=dim_heads, dim_context=dim_context, causal=causal,
                                         zero_init_output=zero_init_branch_outputs, **attn_kwargs)
-        self.ff_norm = LayerNorm(dim, **norm_kwargs)
-        self.ff = FeedForward(dim, zero_init_output=zero_init_branch_outputs, **ff_kwargs)
+        self.ff_norm = norm()
+        self.ff = FeedForward(dim, zero_init_output=zero_init_branch_outputs, allow_block_options=allow_block_options, **ff_kwargs)
+        self.conformer = ConformerModule(dim, norm_kwargs=norm_kwargs) if conformer else None      # its two norms stay under remove_norms
         self.global_cond_dim = global_cond_dim
         if global_cond_dim:
             # adaLN (reference transformer.py:650-656): SiLU -> Linear(global_cond_dim, 6*dim, no bias), zero-initialised;
@@ -148,6 +182,9 @@ class ContinuousTransformer(nn.Module):
         ])
         # one attn_kwargs for every block and both attentions of it: the plan takes a single flag
         self.qk_norm = bool(kwargs.get("attn_kwargs", {}).get("qk_norm", False))
+        # likewise one conformer / remove_norms / glu for every block (sat_dit_plan_set_block_options)
+        self.block_options = (1 if conformer else 0, 1 if kwargs.get("remove_norms", False) else 0,
+                              1 if kwargs.get("ff_kwargs", {}).get("glu", True) else 0)
         assert all(a.qk_norm == self.qk_norm for l in self.layers for a in (l.self_attn, getattr(l, "cross_attn", l.self_attn)))
 
     def forward(self, *args, **kwargs):

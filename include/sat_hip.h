@@ -194,6 +194,34 @@ typedef struct sat_dit_transformer_options {
 } sat_dit_transformer_options;
 int sat_dit_plan_set_transformer_options(sat_dit_plan* plan, const sat_dit_transformer_options* options, size_t options_bytes);
 
+/* TransformerBlock options beyond the shipped configs (models/transformer.py:557-591,645,680-681,697-698 conformer; :621,632,642
+ * remove_norms; :259-268 ff_kwargs glu), between create and finalize; a plan never given this call has {0, 0, 1} and builds and launches
+ * exactly what it did before this call existed.
+ *   conformer 1: every block runs x += conformer(x) behind its cross-attention update (behind the self-attention update in a model without
+ *     cross-attention) and in front of its feed-forward, on every sequence, not modulated by adaLN: in_norm + pointwise_conv (one
+ *     LayerNorm-fed GEMM, 16-bit output), glu (Linear(D, 2D) + x * silu(gate), on that 16-bit output), the 17-tap depthwise_conv along the
+ *     sequence [prepend rows | global token | frames] (zero-padded by 8 at both ends of each sequence) + mid_norm + SiLU in one pass,
+ *     pointwise_conv_2 added to the fp32 stream.  Needs "transformer.layers.N.conformer.{in_norm,mid_norm}.{gamma,beta}" [D],
+ *     ".pointwise_conv.weight" / ".pointwise_conv_2.weight" [D, D, 1], ".glu.proj.weight" [2D, D], ".glu.proj.bias" [2D] and
+ *     ".depthwise_conv.weight" [D, 1, 17]; finalize names a missing one with SAT_E_MISSING.
+ *   remove_norms 1: pre_norm, cross_attend_norm and ff_norm are the identity and have no tensors: to_qkv, the cross-attention to_q and the
+ *     feed-forward read the residual row itself, rounded to the block's operand format -- under adaLN x * (1 + scale) + shift of the raw
+ *     row.  The conformer's in_norm and mid_norm stay.  ln_fold changes nothing in the results of such a plan (the rounded row is then the
+ *     image the previous residual epilogue wrote).
+ *   ff_glu 0: ff.ff.0 is Linear(D, inner) + SiLU, tensors "transformer.layers.N.ff.ff.0.1.weight" [inner, D] and optionally ".0.1.bias"
+ *     [inner] instead of ".0.proj.*"; inner must be a multiple of 128.  These FF-in GEMMs always run on the ring tiles (the 8-phase kernel
+ *     has no plain-activation epilogue).
+ * options_bytes = sizeof(sat_dit_block_options) of the caller's header; any other size is SAT_E_INVALID, a value outside 0 / 1
+ * SAT_E_UNSUPPORTED, a call after finalize SAT_E_STATE.  SAT_E_UNSUPPORTED as well: any of the three options (conformer 1, remove_norms 1,
+ * ff_glu 0) on a plan with gemm_dtype SAT_GEMM_FP8 or with 128-channel heads, and sat_dit_range_report on a plan with one of them.
+ * A feed-forward built on a convolution (ff_kwargs use_conv) has no form in this ABI. */
+typedef struct sat_dit_block_options {
+    int32_t conformer;      /* "conformer" */
+    int32_t remove_norms;   /* "remove_norms" */
+    int32_t ff_glu;         /* ff_kwargs "glu" (1 in every shipped config) */
+} sat_dit_block_options;
+int sat_dit_plan_set_block_options(sat_dit_plan* plan, const sat_dit_block_options* options, size_t options_bytes);
+
 /* Operand format per block, between create and finalize: formats[l] is SAT_GEMM_FP16 or SAT_GEMM_BF16 for block l, n == depth.  A plan never
  * given this call, or given gemm_dtype in every entry, runs every block in gemm_dtype and builds and launches exactly what it did before this
  * call existed.  Block l then keeps its 16-bit weight images, every 16-bit activation buffer it writes (LayerNorm outputs, q / k / v, attention
@@ -606,6 +634,23 @@ int sat_qkv_rope_f16(const void* a_f16_dev, const void* w_f16_dev, const float* 
 int sat_qkv_rope_qknorm_f16(const void* a_f16_dev, const void* w_f16_dev, const float* inv_freq_dev,
                             void* q_dev, void* k_dev, void* vt_dev, float* rope_scratch_dev,
                             int32_t b, int32_t s, int32_t s_pad, int32_t d, int32_t variant, sat_stream_t stream);
+
+/* The two kernels of sat_dit_plan_set_block_options alone, for the parity tests (bf16 / fp16 operands).
+ * sat_dwconv_ln_silu_*: y [b * s_len, d] = silu(LayerNorm_d(depthwise 17-tap convolution of x along each of the b sequences)), x and y
+ *   16-bit, w [d, 17] / gamma / beta [d] fp32; d a multiple of 4, at most 2048.  variant 0: the kernel the plan runs (a 16-row tile and
+ *   its 16 halo rows in registers).  1 to 3 are the designs it was measured against, with the same results: 1 one output row per
+ *   workgroup, i.e. 17 reads of every input row out of L2; 2 a 32-row tile staged in LDS (d a multiple of 8, at most 1664); 3 the
+ *   plan's kernel on an 8-row tile.
+ * sat_gemm_act_*: h [m, n] (16-bit) = act(a [m, k] . w [n, k]^T + bias), act 0 identity / 1 SiLU, bias fp32 or NULL; variant as
+ *   sat_gemm_bf16_f32 (a variant that forces the 8-phase kernel is SAT_E_UNSUPPORTED). */
+int sat_dwconv_ln_silu_bf16(const void* x_bf16_dev, const float* w_dev, const float* gamma_dev, const float* beta_dev, void* y_bf16_dev,
+                            int32_t b, int32_t s_len, int32_t d, int32_t variant, sat_stream_t stream);
+int sat_dwconv_ln_silu_f16(const void* x_f16_dev, const float* w_dev, const float* gamma_dev, const float* beta_dev, void* y_f16_dev,
+                           int32_t b, int32_t s_len, int32_t d, int32_t variant, sat_stream_t stream);
+int sat_gemm_act_bf16(const void* a_bf16_dev, const void* w_bf16_dev, const float* bias_dev, void* h_bf16_dev, int32_t m, int32_t n,
+                      int32_t k, int32_t act, int32_t variant, sat_stream_t stream);
+int sat_gemm_act_f16(const void* a_f16_dev, const void* w_f16_dev, const float* bias_dev, void* h_f16_dev, int32_t m, int32_t n,
+                     int32_t k, int32_t act, int32_t variant, sat_stream_t stream);
 int sat_gemm_resid_ln_f16(const void* a_f16_dev, const void* w_f16_dev, const float* bias_dev, float* c_dev, void* xb_dev,
                           float* ln_part_dev, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream);
 int sat_gemm_swiglu_ln_f16(const void* xb_dev, const float* ln_part_dev, const float* w_f32_dev, const float* gamma_dev,
