@@ -900,13 +900,86 @@ void set_act(ConvArgs& a, op_t* out, const Snake& sn) {
     a.out_snk = out; a.act = sn.act; a.sn_a = sn.a; a.sn_ib = sn.ib;
 }
 
+// ---- the ConvArgs of each layer kind.  oob_decode / oob_encode and the unit-level entry (oob_unit) both build their launches from these, so
+// a test of one layer runs the very off0 / doff / stride / M / out_shift / out_limit / out_bstride the plan runs
+// k-tap convolution over the rows' own length, padding k / 2: the decoder's first and last k = 7, the encoder's last k = 3
+ConvArgs same_conv_args(const ConvW& w, const op_t* in, int L) {
+    ConvArgs a = base_args(w, in, L, L);
+    a.off0 = -(w.taps / 2);
+    return a;
+}
+// the last convolution of either direction: fp32 channel-first result, the first `channels` columns; tanh by option (decoder)
+ConvArgs final_conv_args(const ConvW& w, const op_t* in, int L, float* out_cf, int channels, int tanh_out) {
+    ConvArgs a = same_conv_args(w, in, L);
+    a.out_cf = out_cf; a.cf_channels = channels; a.tanh_out = tanh_out;
+    return a;
+}
+// the dilated k = 7 convolution of a ResidualUnit (autoencoders.py:56)
+ConvArgs ru_c7_args(const ConvW& w, const op_t* S, int L, int dil) {
+    ConvArgs a = base_args(w, S, L, L);
+    a.off0 = -3 * dil; a.doff = dil;
+    return a;
+}
+// its 1 x 1 convolution: adds the raw x in R; the sum returns to R in place where a later unit needs it
+ConvArgs ru_c1_args(const ConvW& w, const op_t* Y, int L, op_t* R, bool need_raw) {
+    ConvArgs c = base_args(w, Y, L, L);
+    c.res = R;
+    c.out_raw = need_raw ? R : nullptr;   // in place: each thread reads then writes its own elements
+    return c;
+}
+// a decoder block's upsampler, L rows -> L * st rows of w.Cout channels:
+// transposed conv (autoencoders.py:102-105): rows m = 0..L, output row span (m*st - pad)*Cout, taps at rows m, m-1;
+// nearest upsample + conv (:95-99): rows m = 0..L-1, output row span m*st*Cout, taps at rows m-1, m, m+1
+ConvArgs upsample_args(const ConvW& w, const op_t* S, int L, int st, bool nearest) {
+    const int pad = (st + 1) / 2;
+    ConvArgs a = base_args(w, S, L, nearest ? L : L + 1);
+    a.off0 = nearest ? -1 : 0; a.doff = nearest ? 1 : -1;
+    a.out_bstride = (long long)L * st * w.Cout;
+    a.out_shift = nearest ? 0 : -(long long)pad * w.Cout;
+    a.out_limit = (long long)L * st * w.Cout;
+    return a;
+}
+// an encoder block's strided convolution (autoencoders.py:80-81), L rows -> L / st rows
+ConvArgs strided_args(const ConvW& w, const op_t* S, int L, int st) {
+    ConvArgs a = base_args(w, S, L, L / st);
+    a.stride = st; a.off0 = -((st + 1) / 2); a.doff = 1;
+    return a;
+}
+
+// What the plan's length bookkeeping can run: a block turns L rows into L * st (decoder) or L / st (encoder).  The reference's
+// ConvTranspose1d(k = 2 st, stride st, padding ceil(st / 2)) yields L * st + st - 2 ceil(st / 2) rows, which is L * st - 1 at odd st, and its
+// encoder convolution yields L + 1 rows at st = 1; Upsample(st) + Conv1d("same") and the strided convolution at st >= 2 keep the plan's lengths.
+bool resample_stride_ok(bool is_decoder, bool nearest, int st) {
+    if (st < 1 || st > 16) return false;
+    if (is_decoder) return nearest || st % 2 == 0;
+    return st >= 2;
+}
+
+int launch_cf_to_cl(const float* z, op_t* y, int C, int T, int B, hipStream_t s) {
+    hipLaunchKernelGGL(cf_to_cl_kernel, dim3(cdiv(T, 64), pad64(C) / 64, B), dim3(256), 0, s, z, y, C, pad64(C), T);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+// the encoder's first convolution (VALU): C channels out of Cin <= 2, raw and activated (sn0) rows of pad64(C) channels
+int launch_first_conv(const float* audio, const float* w_f32, const ConvW& first, const Snake& sn0, op_t* raw, op_t* snk, int Cin, int C,
+                      int L, int B, hipStream_t s) {
+    const bool general = sn0.act != ACT_SNAKE || pad64(C) != C;
+    hipLaunchKernelGGL(general ? first_conv_kernel<true> : first_conv_kernel<false>, dim3(cdiv(L, 64), B), dim3(256), 0, s, audio, w_f32,
+                       first.bias, sn0.a, sn0.ib, sn0.act, raw, snk, Cin, C, pad64(C), L);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
 // The range report of one run: the next record takes the contiguous tensor of n elements at buf, right behind the launch that wrote it (the
 // four workspace buffers are reused all along).  The order of the calls is the order of range_names
 struct Ranger {
     const OobPlan* p;
     hipStream_t s;
     int next = 0;
+    bool unfused = false;      // the unit-level entry's switch: the two-launch route without a report
     bool on() const { return p->rr != nullptr; }
+    bool two_launches() const { return on() || unfused; }
     int operator()(const op_t* buf, size_t n) {
         if (!on()) return 0;
         SAT_CHECK_ARG(next < (int)p->rr_names.size(), SAT_E_STATE, "oobleck range report: more tensors than records (%d)", next);
@@ -968,15 +1041,12 @@ int launch_ru_fused(const RuArgs& a, int B, hipStream_t s) {
 int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const op_t* S, op_t* Y, op_t* Sout,
            const Snake& next, bool need_raw, hipStream_t s, Ranger& rg) {
     static const int dil[3] = {1, 3, 9};
-    ConvArgs a = base_args(blk.ru_c7[r], S, L, L);
-    a.off0 = -3 * dil[r]; a.doff = dil[r];
+    ConvArgs a = ru_c7_args(blk.ru_c7[r], S, L, dil[r]);
     set_act(a, Y, blk.ru_sn2[r]);
-    ConvArgs c = base_args(blk.ru_c1[r], Y, L, L);
-    c.res = R;
-    c.out_raw = need_raw ? R : nullptr;   // in place: each thread reads then writes its own elements
+    ConvArgs c = ru_c1_args(blk.ru_c1[r], Y, L, R, need_raw);
     set_act(c, Sout, next);
 #if !SAT_OP_IS_F32      // (fp32 build: the 128 x C intermediate would not fit next to the weight ring; two launches through Y)
-    if ((C == 128 || C == 256) && !rg.on()) {      // the whole unit in one launch, the intermediate never leaves LDS
+    if ((C == 128 || C == 256) && !rg.two_launches()) {      // the whole unit in one launch, the intermediate never leaves LDS
         RuArgs f{a, c};
         f.c7.out_snk = nullptr;
         f.c1.in = nullptr;
@@ -1012,6 +1082,10 @@ int oob_plan_create(const sat_oobleck_cfg* cfg, const sat_oobleck_options* opt, 
     p->ratio = 1;
     for (int i = 0; i < cfg->n_blocks; ++i) {
         SAT_CHECK_ARG(cfg->strides[i] >= 1 && cfg->strides[i] <= 16 && cfg->c_mults[i] >= 1, SAT_E_UNSUPPORTED, "oobleck_plan_create: bad stride/c_mult");
+        SAT_CHECK_ARG(resample_stride_ok(cfg->is_decoder != 0, opt->nearest_upsample != 0, cfg->strides[i]), SAT_E_UNSUPPORTED,
+                      "oobleck_plan_create: stride %d of block %d is not supported: the reference's %s", cfg->strides[i], i,
+                      cfg->is_decoder ? "ConvTranspose1d yields L * stride - 1 samples at an odd stride, the plan L * stride (nearest_upsample takes odd strides)"
+                                      : "stride-1 encoder convolution (k = 2, padding 1) yields L + 1 samples, the plan L");
         p->ratio *= cfg->strides[i];
     }
     *out_plan = p;
@@ -1049,16 +1123,13 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
     const sat_oobleck_cfg& c = p->cfg;
     const int nb = c.n_blocks;
     // latents -> channels-last bf16 (in Y), first conv (autoencoders.py:175) -> S0 = snake_block1(x)
-    hipLaunchKernelGGL(cf_to_cl_kernel, dim3(cdiv(T, 64), pad64(c.latent_dim) / 64, B), dim3(256), 0, s, z, bf.Y, c.latent_dim,
-                       pad64(c.latent_dim), T);
-    SAT_LAUNCH_CHECK();
+    SAT_TRY(launch_cf_to_cl(z, bf.Y, c.latent_dim, T, B, s));
     Ranger rg{p, s};
     SAT_TRY(rg(bf.Y, (size_t)B * T * pad64(c.latent_dim)));
     op_t* S = bf.S0;
     op_t* Sn = bf.S1;
     {
-        ConvArgs a = base_args(p->first, bf.Y, T, T);
-        a.off0 = -3;
+        ConvArgs a = same_conv_args(p->first, bf.Y, T);
         set_act(a, S, p->blocks[0].sn_in);
         SAT_TRY(launch_conv(a, B, s));
         SAT_TRY(rg(S, (size_t)B * T * p->first.Cout));
@@ -1066,15 +1137,8 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
     int L = T;
     for (int bi = 0; bi < nb; ++bi) {
         const auto& blk = p->blocks[bi];
-        const int st = blk.stride, pad = (st + 1) / 2;
-        // transposed conv (autoencoders.py:102-105): rows m = 0..L, output row span (m*st - pad)*Cout, taps at rows m, m-1;
-        // nearest upsample + conv (:95-99): rows m = 0..L-1, output row span m*st*Cout, taps at rows m-1, m, m+1
-        const bool nearest = p->opt.nearest_upsample != 0;
-        ConvArgs a = base_args(blk.resample, S, L, nearest ? L : L + 1);
-        a.off0 = nearest ? -1 : 0; a.doff = nearest ? 1 : -1;
-        a.out_bstride = (long long)L * st * blk.cout;
-        a.out_shift = nearest ? 0 : -(long long)pad * blk.cout;
-        a.out_limit = (long long)L * st * blk.cout;
+        const int st = blk.stride;
+        ConvArgs a = upsample_args(blk.resample, S, L, st, p->opt.nearest_upsample != 0);
         a.out_raw = bf.R;
         set_act(a, Sn, blk.ru_sn1[0]);
         SAT_TRY(launch_conv(a, B, s));
@@ -1089,9 +1153,7 @@ int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, v
         }
     }
     // final conv (autoencoders.py:187-188): no bias, tanh by option -> fp32 channel-first audio
-    ConvArgs a = base_args(p->last, S, L, L);
-    a.off0 = -3;
-    a.out_cf = audio; a.cf_channels = c.io_channels; a.tanh_out = p->opt.final_tanh;
+    ConvArgs a = final_conv_args(p->last, S, L, audio, c.io_channels, p->opt.final_tanh);
     SAT_TRY(launch_conv(a, B, s));
     return rg.done();
 }
@@ -1110,10 +1172,7 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
     op_t* S = bf.S0;
     op_t* Sn = bf.S1;
     const Snake& sn0 = p->blocks[0].ru_sn1[0];
-    const bool general = sn0.act != ACT_SNAKE || pad64(c.channels) != c.channels;
-    hipLaunchKernelGGL(general ? first_conv_kernel<true> : first_conv_kernel<false>, dim3(cdiv(L, 64), B), dim3(256), 0, s, audio,
-                       p->first_w_f32, p->first.bias, sn0.a, sn0.ib, sn0.act, bf.R, S, c.io_channels, c.channels, pad64(c.channels), L);
-    SAT_LAUNCH_CHECK();
+    SAT_TRY(launch_first_conv(audio, p->first_w_f32, p->first, sn0, bf.R, S, c.io_channels, c.channels, L, B, s));
     Ranger rg{p, s};
     SAT_TRY(rg(S, (size_t)B * L * pad64(c.channels)));
     SAT_TRY(rg(bf.R, (size_t)B * L * pad64(c.channels)));
@@ -1124,10 +1183,9 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
             SAT_TRY(run_ru(blk, r, blk.cin, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s, rg));
             std::swap(S, Sn);
         }
-        const int st = blk.stride, pad = (st + 1) / 2;
+        const int st = blk.stride;
         const int Lo = L / st;
-        ConvArgs a = base_args(blk.resample, S, L, Lo);
-        a.stride = st; a.off0 = -pad; a.doff = 1;
+        ConvArgs a = strided_args(blk.resample, S, L, st);
         const bool lastb = bi + 1 == nb;
         a.out_raw = lastb ? nullptr : bf.R;
         const Snake& nx = lastb ? p->final_snake : p->blocks[bi + 1].ru_sn1[0];
@@ -1138,9 +1196,7 @@ int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T,
         SAT_TRY(rg(S, (size_t)B * L * blk.cout));
         if (!lastb) SAT_TRY(rg(bf.R, (size_t)B * L * blk.cout));
     }
-    ConvArgs a = base_args(p->last, S, L, L);
-    a.off0 = -1;
-    a.out_cf = out; a.cf_channels = c.latent_dim;
+    ConvArgs a = final_conv_args(p->last, S, L, out, c.latent_dim, 0);
     SAT_TRY(launch_conv(a, B, s));
     return rg.done();
 }
@@ -1192,6 +1248,117 @@ int oob_range_report_read(OobPlan* p, sat_range_record* out_host, int32_t capaci
     return 0;
 }
 
+// ---- sat_oobleck_unit: one layer on the caller's tensors (tests).  A plan object of its own holds the caller's fp32 tensors under fixed
+// names ("conv." / "act.": the layer and the activation behind it; "conv2." / "act2.": a ResidualUnit's 1 x 1 convolution and the activation
+// behind the unit), plan_finalize runs the make_* the plan's build() would run for that layer, and the launch goes through the helpers above
+int oob_unit(const sat_oobleck_unit_desc* u, sat_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int kind = u->kind, B = u->b, L = u->t_len, Ci = u->c_in, Co = u->c_out, st = u->stride;
+    SAT_CHECK_ARG(kind >= SAT_OOBLECK_UNIT_CONV7 && kind <= SAT_OOBLECK_UNIT_CF_TO_CL, SAT_E_UNSUPPORTED, "oobleck_unit: unknown kind %d", kind);
+    SAT_CHECK_ARG(u->activation == ACT_SNAKE || u->activation == ACT_ELU, SAT_E_UNSUPPORTED, "oobleck_unit: unknown activation %d", u->activation);
+    SAT_CHECK_ARG(B > 0 && L > 0 && Ci > 0 && (Co > 0 || kind == SAT_OOBLECK_UNIT_CF_TO_CL), SAT_E_INVALID, "oobleck_unit: b, t_len, c_in, c_out must be positive");
+    const bool resample = kind == SAT_OOBLECK_UNIT_CONVT || kind == SAT_OOBLECK_UNIT_NEAREST || kind == SAT_OOBLECK_UNIT_STRIDED;
+    const bool dilated = kind == SAT_OOBLECK_UNIT_CONV7 || kind == SAT_OOBLECK_UNIT_RESIDUAL;
+    const bool residual = kind == SAT_OOBLECK_UNIT_CONV1_RES || kind == SAT_OOBLECK_UNIT_RESIDUAL;
+    const bool from_cf = kind == SAT_OOBLECK_UNIT_FIRST_CONV || kind == SAT_OOBLECK_UNIT_CF_TO_CL;
+    const bool to_cf = kind == SAT_OOBLECK_UNIT_FINAL_DEC || kind == SAT_OOBLECK_UNIT_FINAL_ENC;
+    if (resample) {
+        SAT_CHECK_ARG(resample_stride_ok(kind != SAT_OOBLECK_UNIT_STRIDED, kind == SAT_OOBLECK_UNIT_NEAREST, st), SAT_E_UNSUPPORTED,
+                      "oobleck_unit: stride %d is outside what a plan runs for kind %d", st, kind);
+        SAT_CHECK_ARG(kind != SAT_OOBLECK_UNIT_STRIDED || L % st == 0, SAT_E_INVALID, "oobleck_unit: t_len %d is no multiple of stride %d", L, st);
+    }
+    const int r = u->dilation == 1 ? 0 : u->dilation == 3 ? 1 : 2;
+    SAT_CHECK_ARG(!dilated || u->dilation == 1 || u->dilation == 3 || u->dilation == 9, SAT_E_UNSUPPORTED, "oobleck_unit: dilation %d is not 1, 3 or 9", u->dilation);
+    SAT_CHECK_ARG(!residual || (Ci == Co && u->res && (!u->out_raw || u->out_raw == u->res) && u->out_snk), SAT_E_INVALID,
+                  "oobleck_unit: a residual layer needs c_in == c_out, res, out_snk, and out_raw NULL or == res");
+    SAT_CHECK_ARG(kind != SAT_OOBLECK_UNIT_FIRST_CONV || (Ci <= 2 && u->out_raw && u->out_snk), SAT_E_INVALID,
+                  "oobleck_unit: the first convolution takes 1 or 2 channels and writes out_raw and out_snk");
+    SAT_CHECK_ARG(from_cf ? u->in_cf != nullptr : u->in != nullptr, SAT_E_INVALID, "oobleck_unit: input pointer missing");
+    SAT_CHECK_ARG(to_cf ? u->out_cf != nullptr : (u->out_raw || u->out_snk), SAT_E_INVALID, "oobleck_unit: output pointer missing");
+    SAT_CHECK_ARG(kind == SAT_OOBLECK_UNIT_CF_TO_CL || (u->weight_g && u->weight_v), SAT_E_INVALID, "oobleck_unit: weight_g / weight_v missing");
+    const bool has_bias = kind != SAT_OOBLECK_UNIT_NEAREST && kind != SAT_OOBLECK_UNIT_FINAL_DEC && kind != SAT_OOBLECK_UNIT_CF_TO_CL;
+    SAT_CHECK_ARG(!has_bias || u->bias, SAT_E_INVALID, "oobleck_unit: bias missing");
+    const bool act_behind = u->out_snk != nullptr;      // the activation whose result out_snk holds
+    const bool snake = u->activation == ACT_SNAKE;
+    SAT_CHECK_ARG(!(act_behind && snake && kind != SAT_OOBLECK_UNIT_RESIDUAL) || (u->alpha && u->beta), SAT_E_INVALID, "oobleck_unit: alpha / beta missing");
+    if (kind == SAT_OOBLECK_UNIT_RESIDUAL)
+        SAT_CHECK_ARG(u->weight_g2 && u->weight_v2 && u->bias2 && (!snake || (u->alpha && u->beta && u->alpha2 && u->beta2)), SAT_E_INVALID,
+                      "oobleck_unit: a ResidualUnit needs both convolutions and both activations");
+
+    OobPlan p;
+    p.cfg = sat_oobleck_cfg{};
+    p.cfg.gemm_dtype = u->gemm_dtype;
+    p.opt = sat_oobleck_options{u->activation, u->final_tanh, kind == SAT_OOBLECK_UNIT_NEAREST};
+    auto set = [&](const char* name, const float* ptr, int64_t n) { return ptr ? p.tensors.set("oobleck", name, ptr, n) : 0; };
+    const int ktaps = kind == SAT_OOBLECK_UNIT_CONV1_RES ? 1 : kind == SAT_OOBLECK_UNIT_FINAL_ENC ? 3 : resample ? 2 * st : 7;
+    if (kind != SAT_OOBLECK_UNIT_CF_TO_CL) {
+        const int gdim = kind == SAT_OOBLECK_UNIT_CONVT ? Ci : Co;      // weight norm runs over dim 0: ConvTranspose1d weights are [c_in, c_out, k]
+        SAT_TRY(set("conv.weight_g", u->weight_g, gdim));
+        SAT_TRY(set("conv.weight_v", u->weight_v, (int64_t)Ci * Co * ktaps));
+        if (has_bias) SAT_TRY(set("conv.bias", u->bias, Co));
+        SAT_TRY(set("act.alpha", u->alpha, Co));
+        SAT_TRY(set("act.beta", u->beta, Co));
+    }
+    if (kind == SAT_OOBLECK_UNIT_RESIDUAL) {
+        SAT_TRY(set("conv2.weight_g", u->weight_g2, Co));
+        SAT_TRY(set("conv2.weight_v", u->weight_v2, (int64_t)Co * Co));
+        SAT_TRY(set("conv2.bias", u->bias2, Co));
+        SAT_TRY(set("act2.alpha", u->alpha2, Co));
+        SAT_TRY(set("act2.beta", u->beta2, Co));
+    }
+    OobPlan::Block blk;
+    ConvW cw;
+    Snake sn, next;
+    float* w_f32 = nullptr;
+    op_t* Y = nullptr;
+    SAT_TRY(plan_finalize(&p, s, [&](Bump& ar) -> int {
+        p.zero_page = (op_t*)ar.take(256);
+        if (!ar.dry()) SAT_HIP(hipMemsetAsync(p.zero_page, 0, 256, s));
+        if (kind == SAT_OOBLECK_UNIT_CF_TO_CL) return 0;
+        if (kind == SAT_OOBLECK_UNIT_RESIDUAL) {
+            SAT_TRY(make_conv(&p, ar, "conv.", Ci, Co, 7, true, &blk.ru_c7[r], s));
+            SAT_TRY(make_snake(&p, ar, "act.", Co, &blk.ru_sn2[r], s));
+            SAT_TRY(make_conv(&p, ar, "conv2.", Co, Co, 1, true, &blk.ru_c1[r], s));
+            SAT_TRY(make_snake(&p, ar, "act2.", Co, &next, s));
+            Y = (op_t*)ar.take((size_t)B * L * pad64(Co) * sizeof(op_t));
+            return 0;
+        }
+        if (act_behind) SAT_TRY(make_snake(&p, ar, "act.", Co, &sn, s));
+        if (kind == SAT_OOBLECK_UNIT_CONVT) return make_convT(&p, ar, "conv.", Ci, Co, st, &cw, s);
+        if (kind == SAT_OOBLECK_UNIT_NEAREST) return make_nearest(&p, ar, "conv.", Ci, Co, st, &cw, s);
+        return make_conv(&p, ar, "conv.", Ci, Co, ktaps, has_bias, &cw, s, kind == SAT_OOBLECK_UNIT_FIRST_CONV ? &w_f32 : nullptr);
+    }));
+
+    const op_t* in = (const op_t*)u->in;
+    op_t *res = (op_t*)const_cast<void*>(u->res), *out_raw = (op_t*)u->out_raw, *out_snk = (op_t*)u->out_snk;
+    Ranger rg{&p, s};
+    rg.unfused = u->two_launch != 0;
+    ConvArgs a{};
+    switch (kind) {
+        case SAT_OOBLECK_UNIT_CF_TO_CL: SAT_TRY(launch_cf_to_cl(u->in_cf, out_raw ? out_raw : out_snk, Ci, L, B, s)); break;
+        case SAT_OOBLECK_UNIT_FIRST_CONV: SAT_TRY(launch_first_conv(u->in_cf, w_f32, cw, sn, out_raw, out_snk, Ci, Co, L, B, s)); break;
+        case SAT_OOBLECK_UNIT_RESIDUAL:
+            SAT_TRY(run_ru(blk, r, pad64(Co), L, B, res, in, Y, out_snk, next, out_raw != nullptr, s, rg));
+            break;
+        case SAT_OOBLECK_UNIT_CONV7: a = ru_c7_args(cw, in, L, u->dilation); break;
+        case SAT_OOBLECK_UNIT_CONV1_RES: a = ru_c1_args(cw, in, L, res, out_raw != nullptr); break;
+        case SAT_OOBLECK_UNIT_CONVT: a = upsample_args(cw, in, L, st, false); break;
+        case SAT_OOBLECK_UNIT_NEAREST: a = upsample_args(cw, in, L, st, true); break;
+        case SAT_OOBLECK_UNIT_STRIDED: a = strided_args(cw, in, L, st); break;
+        case SAT_OOBLECK_UNIT_FINAL_DEC: a = final_conv_args(cw, in, L, u->out_cf, Co, u->final_tanh != 0); break;
+        default: a = final_conv_args(cw, in, L, u->out_cf, Co, 0); break;      // SAT_OOBLECK_UNIT_FINAL_ENC
+    }
+    if (a.W) {      // the kinds that are one launch of the convolution kernel
+        if (!to_cf) {
+            if (kind != SAT_OOBLECK_UNIT_CONV1_RES) a.out_raw = out_raw;
+            if (out_snk) set_act(a, out_snk, sn);
+        }
+        SAT_TRY(launch_conv(a, B, s));
+    }
+    SAT_HIP(hipStreamSynchronize(s));      // the arena goes with p
+    return 0;
+}
+
 }  // namespace SAT_OPNS
 
 #if !defined(SAT_OPERAND_F16) && !defined(SAT_OPERAND_F32)
@@ -1210,6 +1377,7 @@ int oob_range_report_read(OobPlan* p, sat_range_record* out_host, int32_t capaci
     int oob_range_report_count(OobPlan* p, int32_t* out_records);                                                                 \
     const char* oob_range_report_name(OobPlan* p, int32_t index);                                                                 \
     int oob_range_report_read(OobPlan* p, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes, sat_stream_t stream); \
+    int oob_unit(const sat_oobleck_unit_desc* u, sat_stream_t stream);                                                            \
     }
 SAT_OOB_DECLARE(f16)
 SAT_OOB_DECLARE(f32)
@@ -1305,4 +1473,17 @@ extern "C" int sat_oobleck_range_report_read(sat_oobleck_plan* p, sat_range_reco
     return SAT_OOB_CALL(p, oob_range_report_read, out_host, capacity_records, record_bytes, stream);
 }
 #undef SAT_OOB_CALL
+// one layer alone (tests): the descriptor's gemm_dtype picks the build, as a plan's does
+extern "C" int sat_oobleck_unit(const sat_oobleck_unit_desc* desc, size_t desc_bytes, sat_stream_t stream) {
+    SAT_CHECK_ARG(desc, SAT_E_INVALID, "oobleck_unit: null descriptor");
+    SAT_CHECK_ARG(desc_bytes == sizeof(sat_oobleck_unit_desc), SAT_E_INVALID,
+                  "oobleck_unit: desc_bytes %zu is not the size of this version's sat_oobleck_unit_desc (%zu)", desc_bytes, sizeof(sat_oobleck_unit_desc));
+    switch (desc->gemm_dtype) {
+        case SAT_GEMM_BF16: return bf16::oob_unit(desc, stream);
+        case SAT_GEMM_FP16: return f16::oob_unit(desc, stream);
+        case SAT_GEMM_FP32X: return f32::oob_unit(desc, stream);
+    }
+    SAT_CHECK_ARG(false, SAT_E_UNSUPPORTED, "oobleck_unit: gemm_dtype must be 0 (bf16), 3 (fp16) or 2 (fp32)");
+    return SAT_E_UNSUPPORTED;
+}
 #endif

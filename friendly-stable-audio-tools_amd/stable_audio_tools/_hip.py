@@ -63,6 +63,19 @@ class SatOobleckOptions(Structure):
 OOBLECK_ACT_SNAKE, OOBLECK_ACT_ELU = 0, 1     # include/sat_hip.h: SAT_OOBLECK_ACT_*
 
 
+class SatOobleckUnitDesc(Structure):
+    """include/sat_hip.h: sat_oobleck_unit_desc, one codec layer on the caller's tensors (``sat_oobleck_unit``, for tests)."""
+    _fields_ = ([(n, c_int32) for n in ("kind", "gemm_dtype", "activation", "b", "t_len", "c_in", "c_out", "stride", "dilation", "two_launch",
+                                        "final_tanh", "reserved")]
+                + [(n, c_void_p) for n in ("weight_g", "weight_v", "bias", "alpha", "beta", "weight_g2", "weight_v2", "bias2", "alpha2", "beta2",
+                                           "in_", "in_cf", "res", "out_raw", "out_snk", "out_cf")])
+
+
+# include/sat_hip.h: SAT_OOBLECK_UNIT_*
+(OOBLECK_UNIT_CONV7, OOBLECK_UNIT_CONV1_RES, OOBLECK_UNIT_RESIDUAL, OOBLECK_UNIT_CONVT, OOBLECK_UNIT_NEAREST, OOBLECK_UNIT_STRIDED,
+ OOBLECK_UNIT_FIRST_CONV, OOBLECK_UNIT_FINAL_DEC, OOBLECK_UNIT_FINAL_ENC, OOBLECK_UNIT_CF_TO_CL) = range(10)
+
+
 class SatRangeRecord(Structure):
     """include/sat_hip.h: sat_range_record, the fp16 range use of one activation buffer (32 bytes)."""
     _fields_ = [("max_abs", c_float), ("launches", c_uint32), ("over_fp16", c_uint64), ("nonfinite", c_uint64), ("elements", c_uint64)]
@@ -122,6 +135,7 @@ _SIGNATURES = {
     "sat_oobleck_workspace_bytes": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_size_t)]),
     "sat_oobleck_decode": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_oobleck_encode": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "sat_oobleck_unit": (c_int32, [POINTER(SatOobleckUnitDesc), c_size_t, c_void_p]),
     "sat_oobleck_range_report": (c_int32, [c_void_p, c_int32]),
     "sat_oobleck_range_report_count": (c_int32, [c_void_p, POINTER(c_int32)]),
     "sat_oobleck_range_report_name": (c_char_p, [c_void_p, c_int32]),

@@ -233,6 +233,10 @@ class OobleckEncoder(_OobleckHip):
     def __init__(self, in_channels=2, channels=128, latent_dim=32, c_mults=[1, 2, 4, 8], strides=[2, 4, 8, 8], use_snake=False,
                  antialias_activation=False):
         super().__init__()
+        if any(int(s) < 2 for s in strides):
+            raise NotImplementedError(
+                f"strides {list(strides)}: a stride-1 encoder block (Conv1d k=2, padding 1) yields L + 1 samples in the reference; the HIP "
+                "codec keeps L / stride per block and runs strides of 2 and more")
         self.io_channels, self.channels, self.latent_dim = in_channels, channels, latent_dim
         self.c_mults, self.strides = list(c_mults), list(strides)
         self.use_snake = bool(use_snake)
@@ -270,6 +274,10 @@ class OobleckDecoder(_OobleckHip):
             raise NotImplementedError(
                 "final_tanh=True cannot be given to the constructor of the HIP codec: build the decoder with final_tanh=False, then call "
                 "set_final_tanh(True) (a tanh has no parameters, so a checkpoint trained with final_tanh=True loads unchanged)")
+        if not use_nearest_upsample and any(int(s) % 2 for s in strides):
+            raise NotImplementedError(
+                f"strides {list(strides)}: ConvTranspose1d(k=2s, stride s, padding ceil(s/2)) yields L * s - 1 samples at an odd stride in the "
+                "reference; the HIP codec keeps L * s per block and runs even strides there (use_nearest_upsample=True takes odd ones)")
         self.io_channels, self.channels, self.latent_dim = out_channels, channels, latent_dim
         self.c_mults, self.strides = list(c_mults), list(strides)
         self.use_snake, self.use_nearest_upsample = bool(use_snake), bool(use_nearest_upsample)

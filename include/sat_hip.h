@@ -438,7 +438,10 @@ typedef struct sat_oobleck_options {
  * sat_dit_plan_create_sized); options == NULL takes the defaults {SNAKE, 0, 0}.  No rule on channel counts: `channels`, every
  * channels * c_mults[i] and `latent_dim` may be any positive integer.  The plan rounds each stage width up to a multiple of 64 and
  * zero-pads weights, biases and Snake parameters at finalize, so a narrow codec costs what the next multiple of 64 costs, and
- * sat_oobleck_workspace_bytes counts the padded widths.  An unknown option value is SAT_E_UNSUPPORTED. */
+ * sat_oobleck_workspace_bytes counts the padded widths.  An unknown option value is SAT_E_UNSUPPORTED.
+ * Strides: 1..16, except where the reference's layer does not map L rows to L * stride (decoder) or L / stride (encoder) -- odd strides of
+ * a transposed-convolution decoder (ConvTranspose1d yields L * stride - 1) and stride 1 of an encoder (L + 1) are SAT_E_UNSUPPORTED;
+ * nearest_upsample decoders take every stride. */
 int sat_oobleck_plan_create_ex(const sat_oobleck_cfg* cfg, const sat_oobleck_options* options, size_t options_bytes,
                                sat_oobleck_plan** out_plan);
 void sat_oobleck_plan_destroy(sat_oobleck_plan* plan);
@@ -472,6 +475,49 @@ int sat_oobleck_range_report_count(const sat_oobleck_plan* plan, int32_t* out_re
 const char* sat_oobleck_range_report_name(const sat_oobleck_plan* plan, int32_t index);
 int sat_oobleck_range_report_read(sat_oobleck_plan* plan, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes,
                                   sat_stream_t stream);
+
+/* One layer of the codec on the caller's tensors, for tests: the same weight packing (weight norm, polyphase forms, Snake parameters), the
+ * same launch set-up and the same kernels a plan runs for that layer, nothing else.  Allocates and frees a temporary arena and synchronises
+ * the stream before it returns: not for hot paths. */
+#define SAT_OOBLECK_UNIT_CONV7 0        /* dilated k = 7 convolution + bias: in [b, t_len, Cp(c_in)] -> out_raw and / or out_snk [b, t_len, Cp(c_out)] */
+#define SAT_OOBLECK_UNIT_CONV1_RES 1    /* 1 x 1 convolution + bias + res: out_raw (NULL, or == res: in place) and out_snk; c_in == c_out */
+#define SAT_OOBLECK_UNIT_RESIDUAL 2     /* ResidualUnit: in = act(x), res = x -> out_raw (NULL or == res) = x + conv1(act2(conv7(in))), out_snk = act_next(that);
+                                           conv7 = weight_g/_v/bias, act2 = alpha/beta, conv1 = weight_g2/_v2/bias2, act_next = alpha2/beta2; c_in == c_out.
+                                           One fused launch where a plan fuses (16-bit builds, 128 or 256 channels) unless two_launch is set */
+#define SAT_OOBLECK_UNIT_CONVT 3        /* ConvTranspose1d(k = 2 stride, stride, padding ceil(stride / 2)) + bias, weight_v [c_in, c_out, 2 stride]:
+                                           in [b, t_len, Cp(c_in)] -> out_raw / out_snk [b, t_len * stride, Cp(c_out)]; even strides */
+#define SAT_OOBLECK_UNIT_NEAREST 4      /* Upsample(nearest, stride) + Conv1d(k = 2 stride, "same"), no bias: shapes as CONVT, any stride */
+#define SAT_OOBLECK_UNIT_STRIDED 5      /* encoder Conv1d(k = 2 stride, stride, padding ceil(stride / 2)) + bias: t_len (a multiple of stride >= 2) rows
+                                           -> out_raw / out_snk [b, t_len / stride, Cp(c_out)] */
+#define SAT_OOBLECK_UNIT_FIRST_CONV 6   /* encoder first convolution: in_cf [b, c_in <= 2, t_len] fp32 -> out_raw and out_snk [b, t_len, Cp(c_out)] */
+#define SAT_OOBLECK_UNIT_FINAL_DEC 7    /* decoder last convolution, k = 7, no bias, tanh by final_tanh: -> out_cf [b, c_out, t_len] fp32 */
+#define SAT_OOBLECK_UNIT_FINAL_ENC 8    /* encoder last convolution, k = 3, bias: -> out_cf [b, c_out, t_len] fp32 */
+#define SAT_OOBLECK_UNIT_CF_TO_CL 9     /* in_cf [b, c_in, t_len] fp32 -> out_raw [b, t_len, Cp(c_in)], pad channels zero */
+typedef struct sat_oobleck_unit_desc {
+    int32_t kind;              /* SAT_OOBLECK_UNIT_* */
+    int32_t gemm_dtype;        /* as sat_oobleck_cfg: picks the bf16 / fp16 / fp32 build; the type of in, res, out_raw, out_snk */
+    int32_t activation;        /* SAT_OOBLECK_ACT_*: the activation behind out_snk (and inside a ResidualUnit) */
+    int32_t b, t_len;          /* batch items, input rows (time steps) per item */
+    int32_t c_in, c_out;       /* channel counts of the reference layer; activations are Cp(c) = c rounded up to a multiple of 64 wide,
+                                  pad channels of inputs zero */
+    int32_t stride;            /* CONVT, NEAREST, STRIDED */
+    int32_t dilation;          /* CONV7, RESIDUAL: 1, 3 or 9 */
+    int32_t two_launch;        /* RESIDUAL: 1 = the two-launch route through memory whatever the width */
+    int32_t final_tanh;        /* FINAL_DEC */
+    int32_t reserved;          /* 0 */
+    /* fp32 device tensors in the reference layout; bias NULL where the layer has none, alpha / beta NULL under ELU or without out_snk */
+    const float *weight_g, *weight_v, *bias, *alpha, *beta;
+    const float *weight_g2, *weight_v2, *bias2, *alpha2, *beta2;        /* RESIDUAL only */
+    const void* in;            /* channels-last activations in the build's operand type */
+    const float* in_cf;        /* FIRST_CONV, CF_TO_CL: channel-first fp32 input */
+    const void* res;           /* CONV1_RES, RESIDUAL */
+    void* out_raw;
+    void* out_snk;
+    float* out_cf;
+} sat_oobleck_unit_desc;
+/* desc_bytes = sizeof(sat_oobleck_unit_desc) of the caller's header (any other size: SAT_E_INVALID).  A kind, stride or dilation outside the
+ * plan's repertoire is SAT_E_UNSUPPORTED, a missing pointer SAT_E_INVALID. */
+int sat_oobleck_unit(const sat_oobleck_unit_desc* desc, size_t desc_bytes, sat_stream_t stream);
 
 /* VAEBottleneck.encode / vae_sample (models/bottleneck.py:46-62) with the Gaussian noise
  * supplied by the caller: z = noise * (softplus(scale) + 1e-4) + mean.

@@ -48,6 +48,20 @@ def residual_unit(sd, pfx, v, dilation, rnd=None):
     return h + _r(rnd, v)
 
 
+# models/autoencoders.py:102-105: the DecoderBlock's Snake + WNConvTranspose1d(k = 2 stride, stride, padding ceil(stride / 2))
+def decoder_upsample(sd, pfx, v, stride, rnd=None):
+    h = _r(rnd, snake_beta(v, sd[pfx + "layers.0.alpha"], sd[pfx + "layers.0.beta"]))
+    return F.conv_transpose1d(h, _wconv(sd, pfx + "layers.1.", rnd), sd[pfx + "layers.1.bias"],
+                              stride=stride, padding=math.ceil(stride / 2))
+
+
+# models/autoencoders.py:80-81: the EncoderBlock's Snake + WNConv1d(k = 2 stride, stride, padding ceil(stride / 2))
+def encoder_downsample(sd, pfx, v, stride, rnd=None):
+    h = _r(rnd, snake_beta(v, sd[pfx + "layers.3.alpha"], sd[pfx + "layers.3.beta"]))
+    return F.conv1d(h, _wconv(sd, pfx + "layers.4.", rnd), sd[pfx + "layers.4.bias"],
+                    stride=stride, padding=math.ceil(stride / 2))
+
+
 # models/autoencoders.py:88-116 (DecoderBlock) + :156-194 (OobleckDecoder)
 def oobleck_decoder(sd, z, strides=(2, 4, 4, 8, 8), rnd=None, return_stages=False):
     """z [B,latent,T] -> [B,out_channels,T*prod(strides)]."""
@@ -58,9 +72,7 @@ def oobleck_decoder(sd, z, strides=(2, 4, 4, 8, 8), rnd=None, return_stages=Fals
     for bi in range(depth):
         stride = strides[depth - 1 - bi]
         pfx = f"layers.{bi + 1}."
-        h = _r(rnd, snake_beta(v, sd[pfx + "layers.0.alpha"], sd[pfx + "layers.0.beta"]))
-        v = F.conv_transpose1d(h, _wconv(sd, pfx + "layers.1.", rnd), sd[pfx + "layers.1.bias"],
-                               stride=stride, padding=math.ceil(stride / 2))
+        v = decoder_upsample(sd, pfx, v, stride, rnd)
         for ri, dil in enumerate((1, 3, 9)):
             v = residual_unit(sd, f"{pfx}layers.{2 + ri}.", v, dil, rnd)
         stages.append(v)
@@ -81,9 +93,7 @@ def oobleck_encoder(sd, audio, strides=(2, 4, 4, 8, 8), rnd=None):
         pfx = f"layers.{bi + 1}."
         for ri, dil in enumerate((1, 3, 9)):
             v = residual_unit(sd, f"{pfx}layers.{ri}.", v, dil, rnd)
-        h = _r(rnd, snake_beta(v, sd[pfx + "layers.3.alpha"], sd[pfx + "layers.3.beta"]))
-        v = F.conv1d(h, _wconv(sd, pfx + "layers.4.", rnd), sd[pfx + "layers.4.bias"],
-                     stride=stride, padding=math.ceil(stride / 2))
+        v = encoder_downsample(sd, pfx, v, stride, rnd)
     k = depth + 1
     h = _r(rnd, snake_beta(v, sd[f"layers.{k}.alpha"], sd[f"layers.{k}.beta"]))
     return F.conv1d(h, _wconv(sd, f"layers.{k + 1}.", rnd), sd[f"layers.{k + 1}.bias"], padding=1)
