@@ -397,8 +397,12 @@ __global__ __launch_bounds__(256) void snake_kernel(const float* __restrict__ x,
 
 int glue_small_linear(const float* x, int ldx, const float* W, const float* bias, const float* add, int ldadd, void* y,
                       int ldy, int R, int N, int K, int act, int out16, hipStream_t s) {
-    SAT_CHECK_ARG(x && W && y && R > 0 && N > 0 && K > 0 && K % 4 == 0 && ldx % 4 == 0, SAT_E_INVALID,
-                  "small_linear: bad args R=%d N=%d K=%d", R, N, K);
+    SAT_CHECK_ARG(x && W && y && R > 0 && N > 0 && K > 0 && ldx >= K && ldy >= N && (!add || ldadd >= N) && act >= 0 && act <= 2 && out16 >= 0 &&
+                      out16 <= 2,
+                  SAT_E_INVALID, "small_linear: bad args R=%d N=%d K=%d ldx=%d ldy=%d ldadd=%d act=%d out16=%d", R, N, K, ldx, ldy, ldadd, act, out16);
+    // rows of x and W are read as float4
+    SAT_CHECK_ARG(K % 4 == 0 && ldx % 4 == 0, SAT_E_UNSUPPORTED, "small_linear: K=%d and ldx=%d must be multiples of 4", K, ldx);
+    SAT_CHECK_ARG((((uintptr_t)x | (uintptr_t)W) & 15) == 0, SAT_E_INVALID, "small_linear: x and W must be 16-byte aligned");
     constexpr int RB = 8;
     dim3 grid(cdiv(N, 4), cdiv(R, RB));
     if (out16 == 1)
@@ -412,23 +416,27 @@ int glue_small_linear(const float* x, int ldx, const float* W, const float* bias
 }
 
 int glue_adaln_finish(float* ssg, int64_t n, int D, hipStream_t s) {
+    SAT_CHECK_ARG(ssg && n > 0 && D > 0 && n % (6 * (int64_t)D) == 0, SAT_E_INVALID, "adaln_finish: bad arguments (n %lld, D %d)", (long long)n, D);
     hipLaunchKernelGGL(adaln_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ssg, n, D);
     SAT_LAUNCH_CHECK();
     return 0;
 }
 
 int glue_fourier(const float* t, float t_const, const float* w, float* out, int B, int half_feat, hipStream_t s) {
+    SAT_CHECK_ARG(w && out && B > 0 && half_feat > 0, SAT_E_INVALID, "fourier: bad arguments");
     hipLaunchKernelGGL(fourier_kernel, dim3(cdiv(B * half_feat, 256)), dim3(256), 0, s, t, t_const, w, out, B, half_feat);
     SAT_LAUNCH_CHECK();
     return 0;
 }
 
 int glue_fold_in(const float* Win, const float* Wpre, float* Weff, int D, int C, hipStream_t s) {
+    SAT_CHECK_ARG(Win && Wpre && Weff && D > 0 && C > 0, SAT_E_INVALID, "fold_in: bad arguments");
     hipLaunchKernelGGL(fold_in_kernel, dim3(cdiv(D * C, 256)), dim3(256), 0, s, Win, Wpre, Weff, D, C);
     SAT_LAUNCH_CHECK();
     return 0;
 }
 int glue_fold_out(const float* Wout, const float* Wpost, float* Weff, int D, int C, hipStream_t s) {
+    SAT_CHECK_ARG(Wout && Wpost && Weff && D > 0 && C > 0, SAT_E_INVALID, "fold_out: bad arguments");
     hipLaunchKernelGGL(fold_out_kernel, dim3(cdiv(D * C, 256)), dim3(256), 0, s, Wout, Wpost, Weff, D, C);
     SAT_LAUNCH_CHECK();
     return 0;
@@ -436,6 +444,8 @@ int glue_fold_out(const float* Wout, const float* Wpost, float* Weff, int D, int
 
 int glue_input_proj(const float* x, const float* Weff, float* X, int Bf, int xB, int C, int T, int S, int D, float xscale,
                     hipStream_t s) {
+    SAT_CHECK_ARG(x && Weff && X && Bf > 0 && xB > 0 && C > 0 && T > 0 && S >= T && D > 0 && Bf <= 65535, SAT_E_INVALID,
+                  "input_proj: bad arguments (Bf %d, xB %d, C %d, T %d, S %d, D %d)", Bf, xB, C, T, S, D);
     SAT_CHECK_ARG(C <= 64, SAT_E_UNSUPPORTED, "input_proj: io_channels %d > 64", C);
     hipLaunchKernelGGL(input_proj_kernel<false>, dim3(cdiv(T, IP_TT), cdiv(D, 256), Bf), dim3(256), 0, s, x, Weff, X, xB, C, T, S, D, xscale,
                        nullptr, 0, 1, 1.0f, nullptr, 0);
@@ -445,6 +455,8 @@ int glue_input_proj(const float* x, const float* Weff, float* X, int Bf, int xB,
 
 int glue_input_proj_extra(const float* x, const float* Weff, float* X, int Bf, int xB, int C, int T, int S, int D, float xscale,
                           const float* concat, int Cc, int Tc, const float* prep, int P, hipStream_t s) {
+    SAT_CHECK_ARG(x && Weff && X && Bf > 0 && xB > 0 && C > 0 && T > 0 && S >= T && D > 0 && Cc >= 0 && Bf <= 65535, SAT_E_INVALID,
+                  "input_proj: bad arguments (Bf %d, xB %d, C %d, T %d, S %d, D %d, Cc %d)", Bf, xB, C, T, S, D, Cc);
     SAT_CHECK_ARG(C <= 64, SAT_E_UNSUPPORTED, "input_proj: io_channels %d > 64", C);
     SAT_CHECK_ARG(P >= 0 && (S == P + 1 + T || (P == 0 && S == T)) && (P == 0 || prep) && (Cc == 0 || (concat && Tc > 0)), SAT_E_INVALID,
                   "input_proj: bad extra conditioning (S %d, P %d, T %d, Cc %d, Tc %d)", S, P, T, Cc, Tc);
@@ -494,7 +506,9 @@ int glue_pos_table(int mode, const float* src, float* table, int rows, int D, hi
 }
 
 int glue_add_pos(float* X, const float* table, int Bf, int S, int D, hipStream_t s) {
-    SAT_CHECK_ARG(X && table && Bf > 0 && S > 0 && D > 0 && D % 4 == 0, SAT_E_INVALID, "add_pos: bad arguments");
+    SAT_CHECK_ARG(X && table && Bf > 0 && S > 0 && D > 0, SAT_E_INVALID, "add_pos: bad arguments");
+    SAT_CHECK_ARG(D % 4 == 0, SAT_E_UNSUPPORTED, "add_pos: embed_dim %d must be a multiple of 4", D);
+    SAT_CHECK_ARG((((uintptr_t)X | (uintptr_t)table) & 15) == 0, SAT_E_INVALID, "add_pos: X and the table must be 16-byte aligned");
     const int64_t n4 = (int64_t)Bf * S * (D / 4);
     hipLaunchKernelGGL(add_pos_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, X, table, n4, S, D / 4);
     SAT_LAUNCH_CHECK();
@@ -502,6 +516,9 @@ int glue_add_pos(float* X, const float* table, int Bf, int S, int D, hipStream_t
 }
 
 int glue_output_proj(const float* X, const float* WeffT, float* out, int Bf, int C, int T, int S, int D, hipStream_t s) {
+    SAT_CHECK_ARG(X && WeffT && out && Bf > 0 && C > 0 && T > 0 && S >= T && D > 0, SAT_E_INVALID,
+                  "output_proj: bad arguments (Bf %d, C %d, T %d, S %d, D %d)", Bf, C, T, S, D);
+    SAT_CHECK_ARG((((uintptr_t)X | (uintptr_t)WeffT) & 15) == 0, SAT_E_INVALID, "output_proj: X and the weight must be 16-byte aligned");
     SAT_CHECK_ARG(C <= 64 && C % 4 == 0 && D % 16 == 0, SAT_E_UNSUPPORTED, "output_proj: C=%d (multiple of 4, <= 64) D=%d unsupported", C, D);
     const int lds = (OP_TOK * D + 8 * OP_TOK * 64) * 4;
     SAT_CHECK_ARG(lds <= 160 * 1024 && D % 128 == 0, SAT_E_UNSUPPORTED, "output_proj: embed_dim %d unsupported (multiple of 128, <= 2048)", D);
@@ -513,6 +530,8 @@ int glue_output_proj(const float* X, const float* WeffT, float* out, int Bf, int
 
 int glue_cfg_denoise(const float* mo, const float* x, float* den, int B, int C, int T, int use_cfg, float cfg_scale,
                      float scale_phi, float c_out, float c_skip, hipStream_t s) {
+    SAT_CHECK_ARG(mo && x && den && B > 0 && C > 0 && T > 0, SAT_E_INVALID, "cfg_denoise: bad arguments");
+    SAT_CHECK_ARG(!(use_cfg && scale_phi != 0.0f) || C > 1, SAT_E_INVALID, "cfg_denoise: the std rescale (scale_phi %g) needs more than one channel", scale_phi);
     if (!(use_cfg && scale_phi != 0.0f)) {
         const int64_t n = (int64_t)B * C * T;
         hipLaunchKernelGGL(cfg_denoise_ew_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, mo, x, den, n, use_cfg, cfg_scale,
@@ -524,6 +543,45 @@ int glue_cfg_denoise(const float* mo, const float* x, float* den, int B, int C, 
                        cfg_scale, scale_phi, c_out, c_skip);
     SAT_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- unit entries (include/sat_hip.h): one glue kernel each on caller tensors, through the launchers the DiT plan calls
+extern "C" int sat_small_linear(const float* x, int32_t ldx, const float* w, const float* bias, const float* add, int32_t ldadd, void* y,
+                                int32_t ldy, int32_t r, int32_t n, int32_t k, int32_t act, int32_t out16, sat_stream_t stream) {
+    return glue_small_linear(x, ldx, w, bias, add, ldadd, y, ldy, r, n, k, act, out16, (hipStream_t)stream);
+}
+extern "C" int sat_adaln_finish(float* ssg, int64_t n, int32_t d, sat_stream_t stream) { return glue_adaln_finish(ssg, n, d, (hipStream_t)stream); }
+extern "C" int sat_fourier_features(const float* t, float t_const, const float* w, float* out, int32_t b, int32_t half_feat, sat_stream_t stream) {
+    return glue_fourier(t, t_const, w, out, b, half_feat, (hipStream_t)stream);
+}
+extern "C" int sat_fold_in(const float* w_in, const float* w_pre, float* w_eff_t, int32_t d, int32_t c, sat_stream_t stream) {
+    return glue_fold_in(w_in, w_pre, w_eff_t, d, c, (hipStream_t)stream);
+}
+extern "C" int sat_fold_out(const float* w_out, const float* w_post, float* w_eff_t, int32_t d, int32_t c, sat_stream_t stream) {
+    return glue_fold_out(w_out, w_post, w_eff_t, d, c, (hipStream_t)stream);
+}
+extern "C" int sat_input_proj(const float* x, const float* w_eff_t, float* X, int32_t bf, int32_t xb, int32_t c, int32_t t, int32_t s_len, int32_t d,
+                              float xscale, sat_stream_t stream) {
+    return glue_input_proj(x, w_eff_t, X, bf, xb, c, t, s_len, d, xscale, (hipStream_t)stream);
+}
+extern "C" int sat_input_proj_extra(const float* x, const float* w_eff_t, float* X, int32_t bf, int32_t xb, int32_t c, int32_t t, int32_t s_len,
+                                    int32_t d, float xscale, const float* concat, int32_t cc, int32_t tc, const float* prep, int32_t p,
+                                    sat_stream_t stream) {
+    return glue_input_proj_extra(x, w_eff_t, X, bf, xb, c, t, s_len, d, xscale, concat, cc, tc, prep, p, (hipStream_t)stream);
+}
+extern "C" int sat_output_proj(const float* X, const float* w_eff_t, float* out, int32_t bf, int32_t c, int32_t t, int32_t s_len, int32_t d,
+                               sat_stream_t stream) {
+    return glue_output_proj(X, w_eff_t, out, bf, c, t, s_len, d, (hipStream_t)stream);
+}
+extern "C" int sat_pos_table(int32_t mode, const float* src, float* table, int32_t rows, int32_t d, sat_stream_t stream) {
+    return glue_pos_table(mode, src, table, rows, d, (hipStream_t)stream);
+}
+extern "C" int sat_add_pos(float* X, const float* table, int32_t bf, int32_t s_len, int32_t d, sat_stream_t stream) {
+    return glue_add_pos(X, table, bf, s_len, d, (hipStream_t)stream);
+}
+extern "C" int sat_cfg_denoise(const float* model_out, const float* x, float* den, int32_t b, int32_t c, int32_t t, int32_t use_cfg, float cfg_scale,
+                               float scale_phi, float c_out, float c_skip, sat_stream_t stream) {
+    return glue_cfg_denoise(model_out, x, den, b, c, t, use_cfg, cfg_scale, scale_phi, c_out, c_skip, (hipStream_t)stream);
 }
 
 // out <- sum_i c_i * t_i over up to five terms (NULL terms are skipped; any t_i may alias out): the state update of the

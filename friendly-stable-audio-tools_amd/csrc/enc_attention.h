@@ -68,4 +68,21 @@ __global__ __launch_bounds__(64) void enc_attention_kernel(const float* __restri
     }
 }
 
+// The one launch of the kernel: both encoders and the unit entry (sat_enc_attention) come through here.  The scores of a query live in
+// ENC_MAX_KEYS_PER_LANE registers per lane (a longer sequence would silently lose its keys beyond 64 * that), K rows are read as float4.
+int enc_attention_launch(const float* qkv, const float* pb, const int* mask, float* out, int B, int L, int H, int dkv, float scale,
+                         hipStream_t s) {
+    SAT_CHECK_ARG(qkv && mask && out && B > 0 && L > 0 && H > 0 && dkv > 0, SAT_E_INVALID, "enc_attention: bad arguments");
+    SAT_CHECK_ARG(((uintptr_t)qkv & 15) == 0, SAT_E_INVALID, "enc_attention: qkv must be 16-byte aligned");
+    SAT_CHECK_ARG(L <= 64 * ENC_MAX_KEYS_PER_LANE, SAT_E_UNSUPPORTED, "enc_attention: sequence length %d > %d", L, 64 * ENC_MAX_KEYS_PER_LANE);
+    SAT_CHECK_ARG(dkv % 4 == 0, SAT_E_UNSUPPORTED, "enc_attention: head dim %d must be a multiple of 4", dkv);
+    SAT_CHECK_ARG(H <= 65535 && B <= 65535, SAT_E_UNSUPPORTED, "enc_attention: %d heads / %d sequences exceed the grid", H, B);
+    const size_t lds = (size_t)(dkv + L) * sizeof(float);
+    SAT_CHECK_ARG(lds <= 64 * 1024, SAT_E_UNSUPPORTED, "enc_attention: head dim %d + %d keys need %zu bytes of LDS (64 KiB without opting in to more)",
+                  dkv, L, lds);
+    hipLaunchKernelGGL(enc_attention_kernel, dim3(L, H, B), dim3(64), lds, s, qkv, pb, mask, out, L, H, dkv, scale);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace

@@ -247,7 +247,8 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
 
 int sat_launch_gemm_f32(const float* A, const float* W, const float* bias, float* C, int M, int N, int K, int ldc, int accumulate,
                         const float* gate, int gate_rows, int gate_ld, hipStream_t s) {
-    SAT_CHECK_ARG(A && W && C && M > 0 && N > 0 && K > 0, SAT_E_INVALID, "gemm_f32: bad arguments");
+    SAT_CHECK_ARG(A && W && C && M > 0 && N > 0 && K > 0 && ldc >= N && (!gate || gate_ld >= N), SAT_E_INVALID, "gemm_f32: bad arguments");
+    SAT_CHECK_ARG((((uintptr_t)A | (uintptr_t)W) & 15) == 0, SAT_E_INVALID, "gemm_f32: operands must be 16-byte aligned");
     SAT_CHECK_ARG(K % F_BK == 0, SAT_E_UNSUPPORTED, "gemm_f32: K=%d must be a multiple of %d", K, F_BK);
     const int tiles = cdiv(M, F_BM) * cdiv(N, F_BN);
     hipLaunchKernelGGL(gemm_f32_kernel, dim3(tiles), dim3(256), 0, s, A, W, bias, C, M, N, K, ldc, accumulate, gate, gate_rows > 0 ? gate_rows : 1,
@@ -258,7 +259,7 @@ int sat_launch_gemm_f32(const float* A, const float* W, const float* bias, float
 
 int sat_launch_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int m, int d, const float* sc,
                              const float* sh, int rps, int ld, hipStream_t s, float eps) {
-    SAT_CHECK_ARG(x && gamma && y && m > 0 && d > 0, SAT_E_INVALID, "layernorm_f32: bad args");
+    SAT_CHECK_ARG(x && gamma && y && m > 0 && d > 0 && (!sc || (sh && ld >= d)), SAT_E_INVALID, "layernorm_f32: bad args");
     hipLaunchKernelGGL(layernorm_f32_kernel, dim3(cdiv(m, 4)), dim3(256), 0, s, x, gamma, beta, y, m, d, sc, sh, rps > 0 ? rps : 1, ld, eps);
     SAT_LAUNCH_CHECK();
     return 0;
@@ -267,6 +268,10 @@ int sat_launch_layernorm_f32(const float* x, const float* gamma, const float* be
 int sat_launch_split_heads_f32(const float* src, float* d0, float* d1, float* d2, int M, int S, int parts, int H, int rope_mask,
                                const float* rope_cos, const float* rope_sin, hipStream_t s, int norm_mask) {
     SAT_CHECK_ARG(src && d0 && parts >= 1 && parts <= 3 && (rope_mask == 0 || (rope_cos && rope_sin)), SAT_E_INVALID, "split_heads_f32: bad args");
+    SAT_CHECK_ARG(M > 0 && S > 0 && M % S == 0 && H > 0 && (parts < 2 || d1) && (parts < 3 || d2) && rope_mask >= 0 && norm_mask >= 0 &&
+                      (rope_mask >> parts) == 0 && (norm_mask >> parts) == 0,
+                  SAT_E_INVALID, "split_heads_f32: bad dims (M %d, S %d, H %d, parts %d, rope_mask %d, norm_mask %d)", M, S, H, parts, rope_mask,
+                  norm_mask);
     const int64_t total = (int64_t)M * parts * H * 64;
     hipLaunchKernelGGL(split_heads_f32_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, src, d0, d1, d2, M, S, parts, H, rope_mask, rope_cos,
                        rope_sin, norm_mask);
@@ -275,6 +280,7 @@ int sat_launch_split_heads_f32(const float* src, float* d0, float* d1, float* d2
 }
 
 int sat_launch_swiglu_f32(const float* hg, float* h, int64_t M, int inner, hipStream_t s) {
+    SAT_CHECK_ARG(hg && h && M > 0 && inner > 0, SAT_E_INVALID, "swiglu_f32: bad args");
     hipLaunchKernelGGL(swiglu_f32_kernel, dim3(cdiv(M * inner, 256)), dim3(256), 0, s, hg, h, M, inner);
     SAT_LAUNCH_CHECK();
     return 0;
@@ -283,6 +289,8 @@ int sat_launch_swiglu_f32(const float* hg, float* h, int64_t M, int inner, hipSt
 int sat_launch_attention_f32(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int sq, int sk,
                              hipStream_t s) {
     SAT_CHECK_ARG(q && k && v && out && b > 0 && h > 0 && kvh > 0 && h % kvh == 0 && sq > 0 && sk > 0, SAT_E_INVALID, "attention_f32: bad args");
+    SAT_CHECK_ARG((((uintptr_t)q | (uintptr_t)out) & 15) == 0, SAT_E_INVALID, "attention_f32: q and out must be 16-byte aligned");
+    SAT_CHECK_ARG(h <= 65535 && b <= 65535, SAT_E_UNSUPPORTED, "attention_f32: %d heads / %d sequences exceed the grid", h, b);
     hipLaunchKernelGGL(attention_f32_kernel, dim3(cdiv(sq, 64), h, b), dim3(64), 0, s, q, k, v, out, h, kvh, sq, sk);
     SAT_LAUNCH_CHECK();
     return 0;

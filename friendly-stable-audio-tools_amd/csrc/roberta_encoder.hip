@@ -73,6 +73,28 @@ __global__ __launch_bounds__(256) void roberta_gelu_kernel(float* __restrict__ h
     h[i] = 0.5f * x * (1.0f + erff(x * 0.7071067811865476f));
 }
 
+// ---- the launches: sat_roberta_encode and the unit entries at the end of this file share them
+int roberta_launch_embed_ln(const int* ids, const float* word, const float* posw, const float* type0, const float* gamma, const float* beta,
+                            float* y, int B, int L, int D, int vocab, int pad_id, int max_positions, float eps, hipStream_t s) {
+    SAT_CHECK_ARG(ids && word && posw && type0 && gamma && beta && y && B > 0 && L > 0 && D > 0 && vocab > 0 && pad_id >= 0 && pad_id < vocab,
+                  SAT_E_INVALID, "roberta_embed_ln: bad arguments");
+    // the last token of a pad-free sequence sits at pad_id + L
+    SAT_CHECK_ARG(pad_id + L < max_positions, SAT_E_UNSUPPORTED, "roberta_embed_ln: sequence length %d needs position %d of a table of %d", L,
+                  pad_id + L, max_positions);
+    const int M = B * L;
+    hipLaunchKernelGGL(roberta_embed_ln_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, ids, word, posw, type0, gamma, beta, y, M, L, D, vocab, pad_id,
+                       eps);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int roberta_launch_gelu(float* h, int64_t n, hipStream_t s) {
+    SAT_CHECK_ARG(h && n > 0, SAT_E_INVALID, "roberta_gelu: bad arguments");
+    hipLaunchKernelGGL(roberta_gelu_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, h, n);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
 struct RobertaLayer {
     float *wqkv, *bqkv, *wo, *bo, *ln1g, *ln1b, *w1, *b1, *w2, *b2, *ln2g, *ln2b;
 };
@@ -227,24 +249,19 @@ extern "C" int sat_roberta_encode(sat_roberta_plan* p, const int32_t* input_ids_
 
     // hidden_states[run_layers] lands in `ha`; without layers and without proj_out the embeddings are the output
     float* ha = (c.run_layers == 0 && !proj) ? out_dev : w.ha;
-    hipLaunchKernelGGL(roberta_embed_ln_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, input_ids_dev, p->word, p->posw, p->type0, p->emb_g, p->emb_b,
-                       ha, M, l, D, c.vocab_size, c.pad_id, c.eps);
-    SAT_LAUNCH_CHECK();
-    const size_t att_lds = (size_t)(dh + l) * 4;
+    SAT_TRY(roberta_launch_embed_ln(input_ids_dev, p->word, p->posw, p->type0, p->emb_g, p->emb_b, ha, b, l, D, c.vocab_size, c.pad_id,
+                                    c.max_positions, c.eps, s));
     const float scale = 1.0f / sqrtf((float)dh);
     for (int li = 0; li < c.run_layers; ++li) {
         const RobertaLayer& L = p->layers[li];
         const bool last = li == c.run_layers - 1;
         SAT_TRY(sat_launch_gemm_f32(ha, L.wqkv, L.bqkv, w.qkv, M, 3 * D, D, 3 * D, 0, nullptr, 1, 0, s));
-        hipLaunchKernelGGL(enc_attention_kernel, dim3(l, H, b), dim3(64), att_lds, s, w.qkv, (const float*)nullptr, attention_mask_dev, w.att, l, H,
-                           dh, scale);
-        SAT_LAUNCH_CHECK();
+        SAT_TRY(enc_attention_launch(w.qkv, nullptr, attention_mask_dev, w.att, b, l, H, dh, scale, s));
         // the residuals ride the GEMM's accumulate path: ha += att Wo^T + bo, then hb = LN(ha)
         SAT_TRY(sat_launch_gemm_f32(w.att, L.wo, L.bo, ha, M, D, D, D, 1, nullptr, 1, 0, s));
         SAT_TRY(sat_launch_layernorm_f32(ha, L.ln1g, L.ln1b, w.hb, M, D, nullptr, nullptr, 1, 0, s, c.eps));
         SAT_TRY(sat_launch_gemm_f32(w.hb, L.w1, L.b1, w.ff, M, F, D, F, 0, nullptr, 1, 0, s));
-        hipLaunchKernelGGL(roberta_gelu_kernel, dim3((unsigned)cdiv((int64_t)M * F, 256)), dim3(256), 0, s, w.ff, (int64_t)M * F);
-        SAT_LAUNCH_CHECK();
+        SAT_TRY(roberta_launch_gelu(w.ff, (int64_t)M * F, s));
         SAT_TRY(sat_launch_gemm_f32(w.ff, L.w2, L.b2, w.hb, M, D, F, D, 1, nullptr, 1, 0, s));
         float* next = (last && !proj) ? out_dev : w.ha;
         SAT_TRY(sat_launch_layernorm_f32(w.hb, L.ln2g, L.ln2b, next, M, D, nullptr, nullptr, 1, 0, s, c.eps));
@@ -254,3 +271,11 @@ extern "C" int sat_roberta_encode(sat_roberta_plan* p, const int32_t* input_ids_
     if (proj) SAT_TRY(sat_launch_gemm_f32(ha, p->proj_w, p->proj_b, out_dev, M, c.proj_dim, D, c.proj_dim, 0, nullptr, 1, 0, s));
     return 0;
 }
+
+// ---- unit entries (include/sat_hip.h): one kernel each on caller tensors, through the launchers sat_roberta_encode uses
+extern "C" int sat_roberta_embed_ln(const int32_t* ids, const float* word, const float* posw, const float* type0, const float* gamma,
+                                    const float* beta, float* y, int32_t b, int32_t l, int32_t d, int32_t vocab, int32_t pad_id,
+                                    int32_t max_positions, float eps, sat_stream_t stream) {
+    return roberta_launch_embed_ln(ids, word, posw, type0, gamma, beta, y, b, l, d, vocab, pad_id, max_positions, eps, (hipStream_t)stream);
+}
+extern "C" int sat_roberta_gelu(float* h, int64_t n, sat_stream_t stream) { return roberta_launch_gelu(h, n, (hipStream_t)stream); }

@@ -84,6 +84,44 @@ __global__ __launch_bounds__(256) void t5_mask_rows_kernel(float* __restrict__ y
     if (i < rows * D && !mask[i / D]) y[i] = 0.f;
 }
 
+// ---- the launches: sat_t5_encode and the unit entries at the end of this file share them
+int t5_launch_embed(const int* ids, const float* emb, float* out, int rows, int D, int vocab, hipStream_t s) {
+    SAT_CHECK_ARG(ids && emb && out && rows > 0 && D > 0 && vocab > 0, SAT_E_INVALID, "t5_embed: bad arguments");
+    SAT_CHECK_ARG(D % 4 == 0, SAT_E_UNSUPPORTED, "t5_embed: d_model %d must be a multiple of 4", D);
+    hipLaunchKernelGGL(t5_embed_kernel, dim3(rows), dim3(256), 0, s, ids, emb, out, rows, D, vocab);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int t5_launch_rmsnorm(const float* x, const float* w, float* y, int M, int D, float eps, hipStream_t s) {
+    SAT_CHECK_ARG(x && w && y && M > 0 && D > 0, SAT_E_INVALID, "t5_rmsnorm: bad arguments");
+    SAT_CHECK_ARG(D % 4 == 0, SAT_E_UNSUPPORTED, "t5_rmsnorm: d_model %d must be a multiple of 4", D);
+    hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, x, w, y, M, D, eps);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int t5_launch_position_bias(const float* relb, const int* bucket, float* pb, int H, int n, hipStream_t s) {
+    SAT_CHECK_ARG(relb && bucket && pb && H > 0 && n > 0, SAT_E_INVALID, "t5_position_bias: bad arguments");
+    hipLaunchKernelGGL(t5_position_bias_kernel, dim3(cdiv(H * n, 256)), dim3(256), 0, s, relb, bucket, pb, H, n);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int t5_launch_act(const float* g, float* h, int64_t rows, int F, int gated, hipStream_t s) {
+    SAT_CHECK_ARG(g && h && rows > 0 && F > 0, SAT_E_INVALID, "t5_act: bad arguments");
+    hipLaunchKernelGGL(t5_act_kernel, dim3((unsigned)cdiv(rows * F, 256)), dim3(256), 0, s, g, h, rows, F, gated);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int t5_launch_mask_rows(float* y, const int* mask, int64_t rows, int D, hipStream_t s) {
+    SAT_CHECK_ARG(y && mask && rows > 0 && D > 0, SAT_E_INVALID, "t5_mask_rows: bad arguments");
+    hipLaunchKernelGGL(t5_mask_rows_kernel, dim3((unsigned)cdiv(rows * D, 256)), dim3(256), 0, s, y, mask, rows, D);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
 struct T5Layer {
     float *ln1, *wqkv, *wo, *ln2, *wi, *wo2;
 };
@@ -246,37 +284,48 @@ extern "C" int sat_t5_encode(sat_t5_plan* p, const int32_t* input_ids_dev, const
         SAT_TRY(sat_t5_relative_buckets(l, c.rel_buckets, c.rel_max_distance, bucket.data()));
     }
     SAT_HIP(hipMemcpyAsync(w.bucket, bucket.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(t5_position_bias_kernel, dim3(cdiv(H * n, 256)), dim3(256), 0, s, p->relb, w.bucket, w.pb, H, n);
-    SAT_LAUNCH_CHECK();
+    SAT_TRY(t5_launch_position_bias(p->relb, w.bucket, w.pb, H, n, s));
 
-    hipLaunchKernelGGL(t5_embed_kernel, dim3(M), dim3(256), 0, s, input_ids_dev, p->emb, w.hid, M, D, c.vocab_size);
-    SAT_LAUNCH_CHECK();
-    const size_t att_lds = (size_t)(c.d_kv + l) * 4;
+    SAT_TRY(t5_launch_embed(input_ids_dev, p->emb, w.hid, M, D, c.vocab_size, s));
     for (int li = 0; li < c.num_layers; ++li) {
         const T5Layer& L = p->layers[li];
-        hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, w.hid, L.ln1, w.nrm, M, D, c.eps);
-        SAT_LAUNCH_CHECK();
+        SAT_TRY(t5_launch_rmsnorm(w.hid, L.ln1, w.nrm, M, D, c.eps, s));
         SAT_TRY(sat_launch_gemm_f32(w.nrm, L.wqkv, nullptr, w.qkv, M, 3 * I, D, 3 * I, 0, nullptr, 1, 0, s));
         // T5Attention: no 1/sqrt(d) scale, bucketed relative-position bias
-        hipLaunchKernelGGL(enc_attention_kernel, dim3(l, H, b), dim3(64), att_lds, s, w.qkv, w.pb, attention_mask_dev, w.att, l, H, c.d_kv, 1.0f);
-        SAT_LAUNCH_CHECK();
+        SAT_TRY(enc_attention_launch(w.qkv, w.pb, attention_mask_dev, w.att, b, l, H, c.d_kv, 1.0f, s));
         SAT_TRY(sat_launch_gemm_f32(w.att, L.wo, nullptr, w.hid, M, D, I, D, 1, nullptr, 1, 0, s));
-        hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, w.hid, L.ln2, w.nrm, M, D, c.eps);
-        SAT_LAUNCH_CHECK();
+        SAT_TRY(t5_launch_rmsnorm(w.hid, L.ln2, w.nrm, M, D, c.eps, s));
         const int Fw = c.gated_gelu ? 2 * F : F;
         SAT_TRY(sat_launch_gemm_f32(w.nrm, L.wi, nullptr, w.ff, M, Fw, D, Fw, 0, nullptr, 1, 0, s));
-        hipLaunchKernelGGL(t5_act_kernel, dim3((unsigned)cdiv((int64_t)M * F, 256)), dim3(256), 0, s, w.ff, w.ffh, (int64_t)M, F, c.gated_gelu);
-        SAT_LAUNCH_CHECK();
+        SAT_TRY(t5_launch_act(w.ff, w.ffh, (int64_t)M, F, c.gated_gelu, s));
         SAT_TRY(sat_launch_gemm_f32(w.ffh, L.wo2, nullptr, w.hid, M, D, F, D, 1, nullptr, 1, 0, s));
     }
     float* last = c.proj_dim > 0 ? w.nrm : out_dev;
-    hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, w.hid, p->final_ln, last, M, D, c.eps);
-    SAT_LAUNCH_CHECK();
+    SAT_TRY(t5_launch_rmsnorm(w.hid, p->final_ln, last, M, D, c.eps, s));
     const int Dout = c.proj_dim > 0 ? c.proj_dim : D;
     if (c.proj_dim > 0) SAT_TRY(sat_launch_gemm_f32(w.nrm, p->proj_w, p->proj_b, out_dev, M, Dout, D, Dout, 0, nullptr, 1, 0, s));
-    if (mask_output) {
-        hipLaunchKernelGGL(t5_mask_rows_kernel, dim3((unsigned)cdiv((int64_t)M * Dout, 256)), dim3(256), 0, s, out_dev, attention_mask_dev, (int64_t)M, Dout);
-        SAT_LAUNCH_CHECK();
-    }
+    if (mask_output) SAT_TRY(t5_launch_mask_rows(out_dev, attention_mask_dev, (int64_t)M, Dout, s));
     return 0;
+}
+
+// ---- unit entries (include/sat_hip.h): one kernel each on caller tensors, through the launchers sat_t5_encode uses
+extern "C" int sat_enc_attention(const float* qkv, const float* pb, const int32_t* mask, float* out, int32_t b, int32_t l, int32_t h, int32_t dkv,
+                                 float scale, sat_stream_t stream) {
+    return enc_attention_launch(qkv, pb, mask, out, b, l, h, dkv, scale, (hipStream_t)stream);
+}
+extern "C" int sat_t5_embed(const int32_t* ids, const float* emb, float* out, int32_t rows, int32_t d, int32_t vocab, sat_stream_t stream) {
+    return t5_launch_embed(ids, emb, out, rows, d, vocab, (hipStream_t)stream);
+}
+extern "C" int sat_t5_rmsnorm(const float* x, const float* w, float* y, int32_t m, int32_t d, float eps, sat_stream_t stream) {
+    return t5_launch_rmsnorm(x, w, y, m, d, eps, (hipStream_t)stream);
+}
+extern "C" int sat_t5_position_bias(const float* relb, const int32_t* bucket, float* pb, int32_t h, int32_t n, sat_stream_t stream) {
+    return t5_launch_position_bias(relb, bucket, pb, h, n, (hipStream_t)stream);
+}
+extern "C" int sat_t5_act(const float* g, float* h, int64_t rows, int32_t f, int32_t gated, sat_stream_t stream) {
+    SAT_CHECK_ARG(gated == 0 || gated == 1, SAT_E_INVALID, "t5_act: gated must be 0 or 1");
+    return t5_launch_act(g, h, rows, f, gated, (hipStream_t)stream);
+}
+extern "C" int sat_t5_mask_rows(float* y, const int32_t* mask, int64_t rows, int32_t d, sat_stream_t stream) {
+    return t5_launch_mask_rows(y, mask, rows, d, (hipStream_t)stream);
 }

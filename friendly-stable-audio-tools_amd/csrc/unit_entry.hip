@@ -40,6 +40,31 @@ extern "C" int sat_range_stats_f32(const void* x, int64_t rows, int64_t cols, in
     return range_stats_impl(SAT_GEMM_FP32X, x, rows, cols, pitch, record, stream);
 }
 
+// ---- the fp32 verification path (f32_ref.hip), one kernel each: the launchers the DiT plan and both text encoders call
+extern "C" int sat_gemm_f32(const float* a, const float* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k, int32_t ldc,
+                            int32_t accumulate, const float* gate, int32_t gate_rows, int32_t gate_ld, sat_stream_t stream) {
+    SAT_CHECK_ARG(!gate || gate_rows > 0, SAT_E_INVALID, "gemm_f32: gate_rows %d", gate_rows);
+    return sat_launch_gemm_f32(a, w, bias, c, m, n, k, ldc, accumulate, gate, gate_rows, gate_ld, (hipStream_t)stream);
+}
+extern "C" int sat_layernorm_f32(const float* x, const float* gamma, const float* beta, float* y, int32_t m, int32_t d, const float* scale,
+                                 const float* shift, int32_t rows_per_seq, int32_t ld, float eps, sat_stream_t stream) {
+    SAT_CHECK_ARG(!scale || rows_per_seq > 0, SAT_E_INVALID, "layernorm_f32: rows_per_seq %d", rows_per_seq);
+    SAT_CHECK_ARG(eps > 0.f, SAT_E_INVALID, "layernorm_f32: eps must be positive");
+    return sat_launch_layernorm_f32(x, gamma, beta, y, m, d, scale, shift, rows_per_seq, ld, (hipStream_t)stream, eps);
+}
+extern "C" int sat_split_heads_f32(const float* src, float* d0, float* d1, float* d2, int32_t b, int32_t s_len, int32_t parts, int32_t heads,
+                                   int32_t rope_mask, const float* rope_cos, const float* rope_sin, int32_t norm_mask, sat_stream_t stream) {
+    SAT_CHECK_ARG(b > 0 && s_len > 0 && (int64_t)b * s_len <= INT32_MAX, SAT_E_INVALID, "split_heads_f32: b %d, s_len %d", b, s_len);
+    return sat_launch_split_heads_f32(src, d0, d1, d2, b * s_len, s_len, parts, heads, rope_mask, rope_cos, rope_sin, (hipStream_t)stream, norm_mask);
+}
+extern "C" int sat_swiglu_f32(const float* hg, float* h, int64_t m, int32_t inner, sat_stream_t stream) {
+    return sat_launch_swiglu_f32(hg, h, m, inner, (hipStream_t)stream);
+}
+extern "C" int sat_attention_f32(const float* q, const float* k, const float* v, float* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
+                                 int32_t sk, sat_stream_t stream) {
+    return sat_launch_attention_f32(q, k, v, out, b, h, kvh, sq, sk, (hipStream_t)stream);
+}
+
 static int gemm_bf16_f32_impl(int f16, const void* a, const void* w, const float* bias, float* c, int32_t m, int32_t n, int32_t k,
                               int32_t accumulate, int32_t variant, void* ws, size_t ws_bytes, sat_stream_t stream) {
     SAT_CHECK_ARG(c, SAT_E_INVALID, "gemm: null output");

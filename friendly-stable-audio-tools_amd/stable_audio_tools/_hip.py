@@ -192,6 +192,31 @@ _SIGNATURES = {
     "sat_snake_beta": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "sat_overlap_add": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "sat_number_embed": (c_int32, [c_void_p, c_int32, c_float, c_float, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    # one kernel each of the fp32 path, the text encoders and the DiT glue (tests/test_gpu_fp32_kernels.py)
+    "sat_gemm_f32": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_void_p, c_int32, c_int32, c_void_p]),
+    "sat_layernorm_f32": (c_int32, [c_void_p] * 4 + [c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
+    "sat_split_heads_f32": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_void_p, c_void_p, c_int32, c_void_p]),
+    "sat_swiglu_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "sat_attention_f32": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_void_p]),
+    "sat_enc_attention": (c_int32, [c_void_p] * 4 + [c_int32] * 4 + [c_float, c_void_p]),
+    "sat_t5_embed": (c_int32, [c_void_p] * 3 + [c_int32] * 3 + [c_void_p]),
+    "sat_t5_rmsnorm": (c_int32, [c_void_p] * 3 + [c_int32, c_int32, c_float, c_void_p]),
+    "sat_t5_position_bias": (c_int32, [c_void_p] * 3 + [c_int32, c_int32, c_void_p]),
+    "sat_t5_act": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
+    "sat_t5_mask_rows": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "sat_roberta_embed_ln": (c_int32, [c_void_p] * 7 + [c_int32] * 6 + [c_float, c_void_p]),
+    "sat_roberta_gelu": (c_int32, [c_void_p, c_int64, c_void_p]),
+    "sat_small_linear": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p] + [c_int32] * 6 + [c_void_p]),
+    "sat_adaln_finish": (c_int32, [c_void_p, c_int64, c_int32, c_void_p]),
+    "sat_fourier_features": (c_int32, [c_void_p, c_float, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "sat_fold_in": (c_int32, [c_void_p] * 3 + [c_int32, c_int32, c_void_p]),
+    "sat_fold_out": (c_int32, [c_void_p] * 3 + [c_int32, c_int32, c_void_p]),
+    "sat_input_proj": (c_int32, [c_void_p] * 3 + [c_int32] * 6 + [c_float, c_void_p]),
+    "sat_input_proj_extra": (c_int32, [c_void_p] * 3 + [c_int32] * 6 + [c_float, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "sat_output_proj": (c_int32, [c_void_p] * 3 + [c_int32] * 5 + [c_void_p]),
+    "sat_pos_table": (c_int32, [c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "sat_add_pos": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "sat_cfg_denoise": (c_int32, [c_void_p] * 3 + [c_int32] * 4 + [c_float] * 4 + [c_void_p]),
 }
 
 # the same unit-level entry points on IEEE fp16 operands (gemm_dtype = 3): identical signatures

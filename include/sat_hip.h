@@ -813,6 +813,83 @@ int sat_number_embed(const float* values_dev, int32_t count, float min_val, floa
                      int32_t half_dim, const float* linear_w_dev, const float* linear_b_dev, int32_t features, float* out_dev,
                      sat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Unit entries of the fp32 path, the text-encoder kernels and the DiT glue: ONE kernel each on caller tensors, through the very launcher
+ * (grid, LDS size, argument checks) the plans call.  For the parity tests (tests/test_gpu_fp32_kernels.py) and for probes; every pointer is
+ * a device pointer, every tensor contiguous fp32 unless noted.  A NULL pointer or a non-positive / inconsistent dimension is SAT_E_INVALID,
+ * a dimension outside the kernel's repertoire SAT_E_UNSUPPORTED; both are decided before anything is launched.
+ * ---------------------------------------------------------------------------------- */
+/* fp32 GEMM (gemm_dtype fp32x, both text encoders): C[m, :n] (row pitch ldc >= n) (+)= (A[m,k] W[n,k]^T + bias[n]) * gate[m / gate_rows][n]
+ * (gate row pitch gate_ld; bias and gate may be NULL).  k % 16 == 0; A and W 16-byte aligned.  Columns n..ldc-1 of C are not touched. */
+int sat_gemm_f32(const float* a_dev, const float* w_dev, const float* bias_dev, float* c_dev, int32_t m, int32_t n, int32_t k, int32_t ldc,
+                 int32_t accumulate, const float* gate_dev, int32_t gate_rows, int32_t gate_ld, sat_stream_t stream);
+/* LayerNorm x [m,d] -> y [m,d]: (x - mean) * rsqrt(var + eps) * gamma + beta (beta may be NULL), then, with scale_dev / shift_dev,
+ * * scale[r / rows_per_seq][:] + shift[r / rows_per_seq][:] (row pitch ld >= d: the adaLN modulation). */
+int sat_layernorm_f32(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev, int32_t m, int32_t d,
+                      const float* scale_dev, const float* shift_dev, int32_t rows_per_seq, int32_t ld, float eps, sat_stream_t stream);
+/* src [b * s_len, parts * heads * 64] -> d0 / d1 / d2 [b, heads, s_len, 64] (parts = 1..3).  Parts in rope_mask (bit = part): partial rotary on
+ * channels < 32, pairs (c, c + 16), with rope_cos / rope_sin [s_len, 16] from the caller; parts in norm_mask: L2-normalised per head. */
+int sat_split_heads_f32(const float* src_dev, float* d0_dev, float* d1_dev, float* d2_dev, int32_t b, int32_t s_len, int32_t parts,
+                        int32_t heads, int32_t rope_mask, const float* rope_cos_dev, const float* rope_sin_dev, int32_t norm_mask,
+                        sat_stream_t stream);
+/* hg [m, 2 * inner] (value | gate) -> h [m, inner] = value * silu(gate) */
+int sat_swiglu_f32(const float* hg_dev, float* h_dev, int64_t m, int32_t inner, sat_stream_t stream);
+/* softmax(q k^T / 8) v on 64-channel heads: q [b,h,sq,64], k / v [b,kvh,sk,64] (h % kvh == 0) -> out [b * sq, h * 64] */
+int sat_attention_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
+                      int32_t sq, int32_t sk, sat_stream_t stream);
+/* Self-attention of the text encoders: qkv [b * l, 3 * h * dkv] (q | k | v) -> out [b * l, h * dkv] = softmax(scale * q k^T + pb + mask) v;
+ * pb [h, 2l - 1] indexed by key - query + l - 1, or NULL; keys with mask [b, l] == 0 get finfo(float32).min added (an all-padding row is the
+ * uniform average over all l keys).  l <= 512, dkv % 4 == 0, (dkv + l) * 4 bytes of LDS <= 64 KiB. */
+int sat_enc_attention(const float* qkv_dev, const float* pb_dev, const int32_t* mask_dev, float* out_dev, int32_t b, int32_t l, int32_t h,
+                      int32_t dkv, float scale, sat_stream_t stream);
+/* The T5 kernels: embedding rows (ids clamped to [0, vocab)); T5LayerNorm x * rsqrt(mean(x^2) + eps) * w; pb[h][i] = relb[bucket[i]][h]
+ * (relb [buckets, h], i < n); relu (gated = 0: g, h [rows, f], may alias) or gelu_new(g[:, :f]) * g[:, f:] (gated = 1: g [rows, 2f]);
+ * rows with mask == 0 set to zero in place.  d % 4 == 0 for the first two. */
+int sat_t5_embed(const int32_t* ids_dev, const float* emb_dev, float* out_dev, int32_t rows, int32_t d, int32_t vocab, sat_stream_t stream);
+int sat_t5_rmsnorm(const float* x_dev, const float* w_dev, float* y_dev, int32_t m, int32_t d, float eps, sat_stream_t stream);
+int sat_t5_position_bias(const float* relb_dev, const int32_t* bucket_dev, float* pb_dev, int32_t h, int32_t n, sat_stream_t stream);
+int sat_t5_act(const float* g_dev, float* h_dev, int64_t rows, int32_t f, int32_t gated, sat_stream_t stream);
+int sat_t5_mask_rows(float* y_dev, const int32_t* mask_dev, int64_t rows, int32_t d, sat_stream_t stream);
+/* RobertaEmbeddings: y [b * l, d] = LayerNorm(word[id] + type0 + posw[pos]), pos = pad_id + (number of non-pad ids up to and including
+ * the token) at non-pad tokens, pad_id at pad tokens; posw [max_positions, d], pad_id + l < max_positions.  Exact (erf) GELU in place. */
+int sat_roberta_embed_ln(const int32_t* ids_dev, const float* word_dev, const float* posw_dev, const float* type0_dev, const float* gamma_dev,
+                         const float* beta_dev, float* y_dev, int32_t b, int32_t l, int32_t d, int32_t vocab, int32_t pad_id,
+                         int32_t max_positions, float eps, sat_stream_t stream);
+int sat_roberta_gelu(float* h_dev, int64_t n, sat_stream_t stream);
+/* y[r][:n] (row pitch ldy; out16 0: fp32, 1: bf16, 2: fp16) = act(x[r][:k] (pitch ldx) W[n,k]^T + bias) + add[r][:n] (pitch ldadd);
+ * act 0: none, 1: SiLU before the add, 2: SiLU after it; bias / add may be NULL.  k % 4 == 0, ldx % 4 == 0. */
+int sat_small_linear(const float* x_dev, int32_t ldx, const float* w_dev, const float* bias_dev, const float* add_dev, int32_t ldadd,
+                     void* y_dev, int32_t ldy, int32_t r, int32_t n, int32_t k, int32_t act, int32_t out16, sat_stream_t stream);
+/* ssg [n / (6 d), 6, d] in place: chunks 0 and 3 -> 1 + v, chunks 2 and 5 -> sigmoid(1 - v), the others unchanged */
+int sat_adaln_finish(float* ssg_dev, int64_t n, int32_t d, sat_stream_t stream);
+/* out [b, 2 * half_feat] = cat(cos f, sin f), f = 2 pi t w[j]; t = t_dev[b], or t_const for every b when t_dev is NULL */
+int sat_fourier_features(const float* t_dev, float t_const, const float* w_dev, float* out_dev, int32_t b, int32_t half_feat,
+                         sat_stream_t stream);
+/* The folded projections, stored transposed: w_eff_t [c, d] = (W_in (I + W_pre))^T for W_in [d, c], W_pre [c, c];
+ * w_eff_t [d, c] = ((I + W_post) W_out)^T for W_out [c, d], W_post [c, c]. */
+int sat_fold_in(const float* w_in_dev, const float* w_pre_dev, float* w_eff_t_dev, int32_t d, int32_t c, sat_stream_t stream);
+int sat_fold_out(const float* w_out_dev, const float* w_post_dev, float* w_eff_t_dev, int32_t d, int32_t c, sat_stream_t stream);
+/* X [bf, s_len, d]: X[b, (s_len - t) + i, :] = xscale * w_eff_t[:c]^T x[b % xb, :, i] for x [xb, c, t], c <= 64; rows below s_len - t are
+ * not touched.  _extra: + w_eff_t[c : c + cc]^T concat[b, :, src(i)] (concat [bf, cc, tc], src the nearest-neighbour frame of
+ * F.interpolate, unscaled), and X[b, j, :] = prep[b, j, :] for j < p (prep [bf, p, d]); s_len = p + 1 + t, or t when p == 0;
+ * row p, the global token's, is not touched. */
+int sat_input_proj(const float* x_dev, const float* w_eff_t_dev, float* X_dev, int32_t bf, int32_t xb, int32_t c, int32_t t, int32_t s_len,
+                   int32_t d, float xscale, sat_stream_t stream);
+int sat_input_proj_extra(const float* x_dev, const float* w_eff_t_dev, float* X_dev, int32_t bf, int32_t xb, int32_t c, int32_t t,
+                         int32_t s_len, int32_t d, float xscale, const float* concat_dev, int32_t cc, int32_t tc, const float* prep_dev,
+                         int32_t p, sat_stream_t stream);
+/* out [bf, c, t]: out[b, :, i] = w_eff_t^T X[b, (s_len - t) + i, :] for w_eff_t [d, c]; c % 4 == 0, c <= 64, d % 128 == 0, d <= 2048 */
+int sat_output_proj(const float* X_dev, const float* w_eff_t_dev, float* out_dev, int32_t bf, int32_t c, int32_t t, int32_t s_len, int32_t d,
+                    sat_stream_t stream);
+/* table [rows, d]: mode 1 cat(sin, cos)(pos * 10000^(-j / (d / 2))) * src[0]; mode 2 src[pos][:] * d^-0.5 (src [>= rows, d]).
+ * X [bf, s_len, d] += table[s] (the caller's table, [>= s_len, d]); d % 4 == 0. */
+int sat_pos_table(int32_t mode, const float* src_dev, float* table_dev, int32_t rows, int32_t d, sat_stream_t stream);
+int sat_add_pos(float* X_dev, const float* table_dev, int32_t bf, int32_t s_len, int32_t d, sat_stream_t stream);
+/* den [b,c,t] = g * c_out + x * c_skip; g = model_out[:b] without CFG, else u + (cond - u) * cfg_scale with cond = model_out[:b],
+ * u = model_out[b:2b], times scale_phi * std_c(cond) / std_c(g) + 1 - scale_phi when scale_phi != 0 (sat_cfg_combine is c_out 1, c_skip 0) */
+int sat_cfg_denoise(const float* model_out_dev, const float* x_dev, float* den_dev, int32_t b, int32_t c, int32_t t, int32_t use_cfg,
+                    float cfg_scale, float scale_phi, float c_out, float c_skip, sat_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
