@@ -20,44 +20,13 @@
 // the epilogue of its last convolution; both are wave-uniform run-time fields of ConvArgs, not further kernel instantiations.
 // Stage widths that are not multiples of 64 are rounded up inside the plan: weights, biases and Snake parameters are zero-padded at
 // finalize, so the pad channels of every activation tensor are written as exact zeros (act(0) = 0) and no kernel masks channels.
+// This file holds what depends on the operand type: the kernels and the launchers that own grid, LDS size and tile choice.  It is built
+// once per format (bf16, fp16, fp32) and exports SAT_OPNS::oob_kernels (oobleck_kernels.h) to the plan, oobleck_plan.hip, which is built once.
 #include <math.h>
 
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include <stdlib.h>
-
-#include "sat_common.h"
-#include "plan_core.h"
+#include "oobleck_kernels.h"      // ConvArgs, RuArgs (namespace SAT_OPNS, opened by sat_common.h), OobKernels
 
 namespace {
-
-struct ConvArgs {
-    const op_t* in;        // [B][Tin][Cin]
-    int Tin, Cin;
-    const op_t* W;         // [taps][N][Cin]
-    int taps, N, M;          // M GEMM rows per batch item
-    int stride, off0, doff;
-    const float* bias;       // [Cout] or null ; n -> bias[n % Cout]
-    int Cout;
-    const op_t* res;       // residual (raw), same indexing as out ; or null
-    op_t* out_raw;         // or null
-    op_t* out_snk;         // or null
-    const float* sn_a;     // exp(alpha)[Cout]
-    const float* sn_ib;      // 1/(exp(beta)+1e-9)[Cout]
-    long long out_bstride;   // elements per batch item
-    long long out_shift;     // flat = m*N + out_shift + n ; valid if 0 <= flat < out_limit
-    long long out_limit;
-    float* out_cf;           // channel-first fp32 output [B][cf_channels][M] (final convs) or null
-    int cf_channels;
-    const op_t* zero_page; // >= one K-tile row (ROW_B <= 256 B) of zeros: LDS-DMA source of the rows that fall into the conv padding
-    // (the option fields come last: the fields above keep the offsets they had before the options existed)
-    int act;                 // activation behind out_snk: ACT_SNAKE (sn_a / sn_ib) or ACT_ELU (no parameters)
-    int tanh_out;            // out_cf only: tanh on the result (OobleckDecoder final_tanh)
-};
-
-enum { ACT_SNAKE = SAT_OOBLECK_ACT_SNAKE, ACT_ELU = SAT_OOBLECK_ACT_ELU, ACT_RUNTIME = -1 };
 
 // nn.ELU(alpha = 1) on the fp32 accumulator; elu(0) == 0 exactly in both forms, which keeps the pad channels zero
 __device__ __forceinline__ float elu_f(float v) {
@@ -368,10 +337,6 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_pipe_kernel(ConvArgs g) {
 // activation (537 MB each at the top decoder level), the <= 4-K-tile kernel whose time was all prologue and epilogue, and a launch.
 // ---------------------------------------------------------------------------------------------
 #if !SAT_OP_IS_F32
-struct RuArgs {
-    ConvArgs c7;     // in = snake1(x); bias / sn_a / sn_ib: those of the k = 7 convolution and of the Snake behind it
-    ConvArgs c1;     // W / bias of the 1 x 1 convolution, res = raw x, out_raw / out_snk (+ the next layer's Snake)
-};
 
 template <int BN, int WM, int WN, int NS, int ACT>      // ACT: the plan's activation (both Snakes / ELUs of the unit and the one behind it)
 __global__ __launch_bounds__(WM * WN * 64) void ru_fused_kernel(RuArgs ga) {
@@ -635,7 +600,8 @@ int launch_conv_cfg(const ConvArgs& a, int B, hipStream_t s) {
     return 0;
 }
 
-int launch_conv(const ConvArgs& a, int B, hipStream_t s) {
+int launch_conv(const void* conv_args, int B, hipStream_t s) {
+    const ConvArgs& a = *static_cast<const ConvArgs*>(conv_args);
     SAT_CHECK_ARG(a.Cin % 64 == 0, SAT_E_UNSUPPORTED, "conv: Cin=%d must be a multiple of 64", a.Cin);
     SAT_CHECK_ARG(a.N % 64 == 0, SAT_E_UNSUPPORTED, "conv: N=%d must be a multiple of 64", a.N);
     SAT_CHECK_ARG(a.zero_page != nullptr, SAT_E_STATE, "conv: zero page missing");
@@ -656,372 +622,20 @@ int launch_conv(const ConvArgs& a, int B, hipStream_t s) {
 #endif
 }
 
-// the activation in front of a convolution: SnakeBeta with its folded parameters, or ELU (no parameters)
-struct Snake {
-    float *a = nullptr, *ib = nullptr;
-    int act = ACT_SNAKE;
-};
-inline int pad64(int c) { return (int)round_up(c, 64); }
-struct ConvW {
-    op_t* W = nullptr;
-    float* bias = nullptr;
-    int Cin = 0, Cout = 0, taps = 0, N = 0;      // Cin / Cout: the padded widths the kernels see
-    const op_t* zero = nullptr;   // the plan's zero page (LDS-DMA source for padding rows)
-};
-
-}  // namespace
-
-namespace SAT_OPNS {
-struct OobPlan {
-    sat_oobleck_cfg cfg;          // first member: the C entry points read cfg.gemm_dtype through the opaque pointer to pick the build
-    sat_oobleck_options opt;
-    TensorTable tensors;
-    bool finalized = false;
-    DevBuf arena;
-    int ratio = 1;
-    std::vector<int> chans;   // channels after each stage, decoder order or encoder order
-    // decoder / encoder share the block structure
-    ConvW first, last;
-    float* first_w_f32 = nullptr;   // encoder first conv (VALU)
-    struct Block {
-        Snake sn_in;             // decoder: block snake before convT ; encoder: snake before strided conv
-        ConvW resample;          // convT (decoder) / strided conv (encoder)
-        Snake ru_sn1[3], ru_sn2[3];
-        ConvW ru_c7[3], ru_c1[3];
-        int stride, cin, cout;   // cin / cout: padded to multiples of 64
-    };
-    std::vector<Block> blocks;
-    Snake final_snake;
-    op_t* zero_page = nullptr;
-    // optional fp16 range report (sat_oobleck_range_report): one record per activation tensor a run writes to the workspace, in launch order;
-    // the names are fixed by the blocks (oob_plan_create), the records exist while the report is on
-    std::vector<std::string> rr_names;
-    DevBuf rr_buf;
-    sat_range_record* rr = nullptr;
-};
-}  // namespace SAT_OPNS
-using SAT_OPNS::OobPlan;
-
-namespace {
-
-int get_tensor(OobPlan* p, const std::string& name, int64_t numel, const float** out) { return p->tensors.get("oobleck", name, numel, out); }
-
-int make_snake(OobPlan* p, Bump& ar, const std::string& pfx, int C, Snake* sn, hipStream_t s) {
-    sn->act = p->opt.activation;
-    if (sn->act == ACT_ELU) return 0;        // nn.ELU has no tensors: nothing to ask for
-    const int Cp = pad64(C);
-    sn->a = (float*)ar.take((size_t)Cp * 4);
-    sn->ib = (float*)ar.take((size_t)Cp * 4);
-    if (ar.dry()) return 0;
-    const float *al, *be;
-    SAT_TRY(get_tensor(p, pfx + "alpha", C, &al));
-    SAT_TRY(get_tensor(p, pfx + "beta", C, &be));
-    hipLaunchKernelGGL(snake_params_kernel, dim3(cdiv(Cp, 256)), dim3(256), 0, s, al, be, sn->a, sn->ib, C, Cp);
+int launch_cf_to_cl(const float* z, void* y, int C, int T, int B, hipStream_t s) {
+    hipLaunchKernelGGL(cf_to_cl_kernel, dim3(cdiv(T, 64), pad64(C) / 64, B), dim3(256), 0, s, z, (op_t*)y, C, pad64(C), T);
     SAT_LAUNCH_CHECK();
     return 0;
 }
 
-// bias[Cp]: the tensor's C values, then zeros
-int make_bias(OobPlan* p, Bump& ar, const std::string& name, int C, float** out, hipStream_t s) {
-    const int Cp = pad64(C);
-    *out = (float*)ar.take((size_t)Cp * 4);
-    if (ar.dry()) return 0;
-    if (Cp > C) SAT_HIP(hipMemsetAsync(*out + C, 0, (size_t)(Cp - C) * 4, s));
-    return p->tensors.copy("oobleck", name, C, *out, s);
-}
-
-// Conv1d weight [Cout][Cin][k]
-int make_conv(OobPlan* p, Bump& ar, const std::string& pfx, int Cin, int Cout, int k, bool has_bias, ConvW* cw,
-              hipStream_t s, float** w_f32 = nullptr) {
-    const int Npad = pad64(Cout), Kpad = pad64(Cin);
-    cw->Cin = Kpad; cw->Cout = Npad; cw->taps = k; cw->N = Npad; cw->zero = p->zero_page;
-    float* scale = (float*)ar.take((size_t)Cout * 4);
-    if (w_f32) *w_f32 = (float*)ar.take((size_t)Cout * Cin * k * 4);
-    else cw->W = (op_t*)ar.take((size_t)k * Npad * Kpad * sizeof(op_t));
-    cw->bias = nullptr;
-    if (has_bias) SAT_TRY(make_bias(p, ar, pfx + "bias", Cout, &cw->bias, s));
-    if (ar.dry()) return 0;
-    const float *g, *v;
-    SAT_TRY(get_tensor(p, pfx + "weight_g", Cout, &g));
-    SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cout * Cin * k, &v));
-    hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cout), dim3(256), 0, s, v, g, scale, Cin * k);
-    if (w_f32) {
-        size_t n = (size_t)Cout * Cin * k;
-        hipLaunchKernelGGL(wn_fold_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, *w_f32, Cin * k, n);
-    } else {
-        size_t n = (size_t)k * Npad * Kpad;
-        hipLaunchKernelGGL(wn_pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, cw->W, Cout, Cin, k, Npad,
-                           Kpad);
-    }
-    SAT_LAUNCH_CHECK();
-    return 0;
-}
-
-// ConvTranspose1d weight [Cin][Cout][2s]
-int make_convT(OobPlan* p, Bump& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
-    const int Kp = pad64(Cin), Np = pad64(Cout);
-    cw->Cin = Kp; cw->Cout = Np; cw->taps = 2; cw->N = stride * Np; cw->zero = p->zero_page;
-    float* scale = (float*)ar.take((size_t)Cin * 4);
-    cw->W = (op_t*)ar.take((size_t)2 * cw->N * Kp * sizeof(op_t));
-    SAT_TRY(make_bias(p, ar, pfx + "bias", Cout, &cw->bias, s));
-    if (ar.dry()) return 0;
-    const float *g, *v;
-    SAT_TRY(get_tensor(p, pfx + "weight_g", Cin, &g));
-    SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cin * Cout * 2 * stride, &v));
-    hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cin), dim3(256), 0, s, v, g, scale, Cout * 2 * stride);
-    size_t n = (size_t)2 * cw->N * Kp;
-    hipLaunchKernelGGL(wn_pack_convT_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, cw->W, Cin, Cout, stride, Kp,
-                       Np);
-    SAT_LAUNCH_CHECK();
-    return 0;
-}
-
-// Upsample(nearest, s) + bias-free Conv1d weight [Cout][Cin][2s] -> the three-tap polyphase form
-int make_nearest(OobPlan* p, Bump& ar, const std::string& pfx, int Cin, int Cout, int stride, ConvW* cw, hipStream_t s) {
-    const int Kp = pad64(Cin), Np = pad64(Cout);
-    cw->Cin = Kp; cw->Cout = Np; cw->taps = 3; cw->N = stride * Np; cw->zero = p->zero_page;
-    float* scale = (float*)ar.take((size_t)Cout * 4);
-    cw->W = (op_t*)ar.take((size_t)3 * cw->N * Kp * sizeof(op_t));
-    cw->bias = nullptr;
-    if (ar.dry()) return 0;
-    const float *g, *v;
-    SAT_TRY(get_tensor(p, pfx + "weight_g", Cout, &g));
-    SAT_TRY(get_tensor(p, pfx + "weight_v", (int64_t)Cout * Cin * 2 * stride, &v));
-    hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cout), dim3(256), 0, s, v, g, scale, Cin * 2 * stride);
-    size_t n = (size_t)3 * cw->N * Kp;
-    hipLaunchKernelGGL(wn_pack_nearest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, cw->W, Cin, Cout, stride, Kp,
-                       Np);
-    SAT_LAUNCH_CHECK();
-    return 0;
-}
-
-int make_ru(OobPlan* p, Bump& ar, const std::string& pfx, int C, OobPlan::Block& blk, int r, hipStream_t s) {
-    SAT_TRY(make_snake(p, ar, pfx + "layers.0.", C, &blk.ru_sn1[r], s));
-    SAT_TRY(make_conv(p, ar, pfx + "layers.1.", C, C, 7, true, &blk.ru_c7[r], s));
-    SAT_TRY(make_snake(p, ar, pfx + "layers.2.", C, &blk.ru_sn2[r], s));
-    SAT_TRY(make_conv(p, ar, pfx + "layers.3.", C, C, 1, true, &blk.ru_c1[r], s));
-    return 0;
-}
-
-int build(OobPlan* p, Bump& ar, hipStream_t s) {
-    const sat_oobleck_cfg& c = p->cfg;
-    const int nb = c.n_blocks;
-    p->blocks.resize(nb);
-    p->zero_page = (op_t*)ar.take(256);
-    if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->zero_page, 0, 256, s));
-    if (c.is_decoder) {
-        // autoencoders.py:174-191: channel list c_mults=[1]+c_mults ; blocks from deepest to shallowest
-        const int ctop = c.c_mults[nb - 1] * c.channels;
-        SAT_TRY(make_conv(p, ar, "layers.0.", c.latent_dim, ctop, 7, true, &p->first, s));
-        for (int bi = 0; bi < nb; ++bi) {
-            const int i = nb - bi;   // reference loop index: range(depth-1, 0, -1)
-            auto& blk = p->blocks[bi];
-            const int cin = c.c_mults[i - 1] * c.channels;
-            const int cout = (i - 2 >= 0 ? c.c_mults[i - 2] : 1) * c.channels;
-            blk.cin = pad64(cin);
-            blk.cout = pad64(cout);
-            blk.stride = c.strides[i - 1];
-            const std::string pf = "layers." + std::to_string(bi + 1) + ".";
-            SAT_TRY(make_snake(p, ar, pf + "layers.0.", cin, &blk.sn_in, s));
-            if (p->opt.nearest_upsample)      // Sequential(Upsample, WNConv1d): the convolution is layers.1.1
-                SAT_TRY(make_nearest(p, ar, pf + "layers.1.1.", cin, cout, blk.stride, &blk.resample, s));
-            else
-                SAT_TRY(make_convT(p, ar, pf + "layers.1.", cin, cout, blk.stride, &blk.resample, s));
-            for (int r = 0; r < 3; ++r) SAT_TRY(make_ru(p, ar, pf + "layers." + std::to_string(2 + r) + ".", cout, blk, r, s));
-        }
-        SAT_TRY(make_snake(p, ar, "layers." + std::to_string(nb + 1) + ".", c.channels, &p->final_snake, s));
-        SAT_TRY(make_conv(p, ar, "layers." + std::to_string(nb + 2) + ".", c.channels, c.io_channels, 7, false, &p->last, s));
-    } else {
-        // autoencoders.py:131-151
-        SAT_TRY(make_conv(p, ar, "layers.0.", c.io_channels, c.channels, 7, true, &p->first, s, &p->first_w_f32));
-        for (int bi = 0; bi < nb; ++bi) {
-            auto& blk = p->blocks[bi];
-            const int cin = (bi == 0 ? 1 : c.c_mults[bi - 1]) * c.channels;
-            const int cout = c.c_mults[bi] * c.channels;
-            blk.cin = pad64(cin);
-            blk.cout = pad64(cout);
-            blk.stride = c.strides[bi];
-            const std::string pf = "layers." + std::to_string(bi + 1) + ".";
-            for (int r = 0; r < 3; ++r) SAT_TRY(make_ru(p, ar, pf + "layers." + std::to_string(r) + ".", cin, blk, r, s));
-            SAT_TRY(make_snake(p, ar, pf + "layers.3.", cin, &blk.sn_in, s));
-            SAT_TRY(make_conv(p, ar, pf + "layers.4.", cin, cout, 2 * blk.stride, true, &blk.resample, s));
-        }
-        const int ctop = c.c_mults[nb - 1] * c.channels;
-        SAT_TRY(make_snake(p, ar, "layers." + std::to_string(nb + 1) + ".", ctop, &p->final_snake, s));
-        SAT_TRY(make_conv(p, ar, "layers." + std::to_string(nb + 2) + ".", ctop, c.latent_dim, 3, true, &p->last, s));
-    }
-    return 0;
-}
-
-struct Bufs {
-    op_t *R, *S0, *S1, *Y;
-    size_t total;
-};
-Bufs carve(const OobPlan* p, int B, int T, char* base) {
-    // largest channels-last tensor of the network (padded widths), in elements per batch item
-    const sat_oobleck_cfg& c = p->cfg;
-    size_t len = (size_t)T, mx = 0;
-    if (c.is_decoder) {
-        mx = std::max((size_t)T * pad64(c.latent_dim), (size_t)T * p->blocks[0].cin);
-        for (auto& b : p->blocks) {
-            len *= b.stride;
-            mx = std::max(mx, len * b.cout);
-        }
-    } else {
-        len = (size_t)T * p->ratio;
-        mx = len * pad64(c.channels);
-        for (auto& b : p->blocks) {
-            mx = std::max(mx, len * b.cin);
-            len /= b.stride;
-            mx = std::max(mx, len * b.cout);
-        }
-    }
-    size_t per = (size_t)round_up((int64_t)(mx * B * sizeof(op_t)), 256);
-    Bufs o;
-    o.R = (op_t*)(base ? base : nullptr);
-    o.S0 = (op_t*)(base ? base + per : nullptr);
-    o.S1 = (op_t*)(base ? base + 2 * per : nullptr);
-    o.Y = (op_t*)(base ? base + 3 * per : nullptr);
-    o.total = 4 * per;
-    return o;
-}
-
-ConvArgs base_args(const ConvW& w, const op_t* in, int Tin, int M) {
-    ConvArgs a{};
-    a.zero_page = w.zero;
-    a.in = in; a.Tin = Tin; a.Cin = w.Cin; a.W = w.W; a.taps = w.taps; a.N = w.N; a.M = M;
-    a.stride = 1; a.off0 = 0; a.doff = 1; a.bias = w.bias; a.Cout = w.Cout;
-    a.out_bstride = (long long)M * w.N; a.out_shift = 0; a.out_limit = (long long)M * w.N;
-    return a;
-}
-
-// out = the activated copy of the result, for the consumer whose activation is sn
-void set_act(ConvArgs& a, op_t* out, const Snake& sn) {
-    a.out_snk = out; a.act = sn.act; a.sn_a = sn.a; a.sn_ib = sn.ib;
-}
-
-// ---- the ConvArgs of each layer kind.  oob_decode / oob_encode and the unit-level entry (oob_unit) both build their launches from these, so
-// a test of one layer runs the very off0 / doff / stride / M / out_shift / out_limit / out_bstride the plan runs
-// k-tap convolution over the rows' own length, padding k / 2: the decoder's first and last k = 7, the encoder's last k = 3
-ConvArgs same_conv_args(const ConvW& w, const op_t* in, int L) {
-    ConvArgs a = base_args(w, in, L, L);
-    a.off0 = -(w.taps / 2);
-    return a;
-}
-// the last convolution of either direction: fp32 channel-first result, the first `channels` columns; tanh by option (decoder)
-ConvArgs final_conv_args(const ConvW& w, const op_t* in, int L, float* out_cf, int channels, int tanh_out) {
-    ConvArgs a = same_conv_args(w, in, L);
-    a.out_cf = out_cf; a.cf_channels = channels; a.tanh_out = tanh_out;
-    return a;
-}
-// the dilated k = 7 convolution of a ResidualUnit (autoencoders.py:56)
-ConvArgs ru_c7_args(const ConvW& w, const op_t* S, int L, int dil) {
-    ConvArgs a = base_args(w, S, L, L);
-    a.off0 = -3 * dil; a.doff = dil;
-    return a;
-}
-// its 1 x 1 convolution: adds the raw x in R; the sum returns to R in place where a later unit needs it
-ConvArgs ru_c1_args(const ConvW& w, const op_t* Y, int L, op_t* R, bool need_raw) {
-    ConvArgs c = base_args(w, Y, L, L);
-    c.res = R;
-    c.out_raw = need_raw ? R : nullptr;   // in place: each thread reads then writes its own elements
-    return c;
-}
-// a decoder block's upsampler, L rows -> L * st rows of w.Cout channels:
-// transposed conv (autoencoders.py:102-105): rows m = 0..L, output row span (m*st - pad)*Cout, taps at rows m, m-1;
-// nearest upsample + conv (:95-99): rows m = 0..L-1, output row span m*st*Cout, taps at rows m-1, m, m+1
-ConvArgs upsample_args(const ConvW& w, const op_t* S, int L, int st, bool nearest) {
-    const int pad = (st + 1) / 2;
-    ConvArgs a = base_args(w, S, L, nearest ? L : L + 1);
-    a.off0 = nearest ? -1 : 0; a.doff = nearest ? 1 : -1;
-    a.out_bstride = (long long)L * st * w.Cout;
-    a.out_shift = nearest ? 0 : -(long long)pad * w.Cout;
-    a.out_limit = (long long)L * st * w.Cout;
-    return a;
-}
-// an encoder block's strided convolution (autoencoders.py:80-81), L rows -> L / st rows
-ConvArgs strided_args(const ConvW& w, const op_t* S, int L, int st) {
-    ConvArgs a = base_args(w, S, L, L / st);
-    a.stride = st; a.off0 = -((st + 1) / 2); a.doff = 1;
-    return a;
-}
-
-// What the plan's length bookkeeping can run: a block turns L rows into L * st (decoder) or L / st (encoder).  The reference's
-// ConvTranspose1d(k = 2 st, stride st, padding ceil(st / 2)) yields L * st + st - 2 ceil(st / 2) rows, which is L * st - 1 at odd st, and its
-// encoder convolution yields L + 1 rows at st = 1; Upsample(st) + Conv1d("same") and the strided convolution at st >= 2 keep the plan's lengths.
-bool resample_stride_ok(bool is_decoder, bool nearest, int st) {
-    if (st < 1 || st > 16) return false;
-    if (is_decoder) return nearest || st % 2 == 0;
-    return st >= 2;
-}
-
-int launch_cf_to_cl(const float* z, op_t* y, int C, int T, int B, hipStream_t s) {
-    hipLaunchKernelGGL(cf_to_cl_kernel, dim3(cdiv(T, 64), pad64(C) / 64, B), dim3(256), 0, s, z, y, C, pad64(C), T);
-    SAT_LAUNCH_CHECK();
-    return 0;
-}
-
-// the encoder's first convolution (VALU): C channels out of Cin <= 2, raw and activated (sn0) rows of pad64(C) channels
-int launch_first_conv(const float* audio, const float* w_f32, const ConvW& first, const Snake& sn0, op_t* raw, op_t* snk, int Cin, int C,
-                      int L, int B, hipStream_t s) {
-    const bool general = sn0.act != ACT_SNAKE || pad64(C) != C;
+// the encoder's first convolution (VALU): C channels out of Cin <= 2, raw and activated rows of pad64(C) channels
+int launch_first_conv(const float* audio, const float* w_f32, const float* bias, const float* sn_a, const float* sn_ib, int act, void* raw,
+                      void* snk, int Cin, int C, int L, int B, hipStream_t s) {
+    const bool general = act != ACT_SNAKE || pad64(C) != C;
     hipLaunchKernelGGL(general ? first_conv_kernel<true> : first_conv_kernel<false>, dim3(cdiv(L, 64), B), dim3(256), 0, s, audio, w_f32,
-                       first.bias, sn0.a, sn0.ib, sn0.act, raw, snk, Cin, C, pad64(C), L);
+                       bias, sn_a, sn_ib, act, (op_t*)raw, (op_t*)snk, Cin, C, pad64(C), L);
     SAT_LAUNCH_CHECK();
     return 0;
-}
-
-// The range report of one run: the next record takes the contiguous tensor of n elements at buf, right behind the launch that wrote it (the
-// four workspace buffers are reused all along).  The order of the calls is the order of range_names
-struct Ranger {
-    const OobPlan* p;
-    hipStream_t s;
-    int next = 0;
-    bool unfused = false;      // the unit-level entry's switch: the two-launch route without a report
-    bool on() const { return p->rr != nullptr; }
-    bool two_launches() const { return on() || unfused; }
-    int operator()(const op_t* buf, size_t n) {
-        if (!on()) return 0;
-        SAT_CHECK_ARG(next < (int)p->rr_names.size(), SAT_E_STATE, "oobleck range report: more tensors than records (%d)", next);
-        return sat_launch_range_stats(buf, SAT_OP_IS_F32 ? SAT_GEMM_FP32X : SAT_OP_IS_F16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16, 1, (int64_t)n, (int64_t)n, n,
-                                      p->rr + next++, s);
-    }
-    int done() const {
-        SAT_CHECK_ARG(!on() || next == (int)p->rr_names.size(), SAT_E_STATE, "oobleck range report: %d tensors for %d records", next, (int)p->rr_names.size());
-        return 0;
-    }
-};
-
-// The records of a plan in launch order (sat_oobleck_range_report_name): the module path of the layer whose launch writes the tensor -- the
-// activated tensor the next convolution reads, then "<path>.raw" where the launch also keeps the un-activated sum for the next residual add
-std::vector<std::string> range_names(const sat_oobleck_cfg& c, const sat_oobleck_options& o) {
-    std::vector<std::string> n;
-    auto both = [&](const std::string& path, bool raw) {
-        n.push_back(path);
-        if (raw) n.push_back(path + ".raw");
-    };
-    auto unit = [&](const std::string& ru, int r) {
-        n.push_back(ru + "layers.1");
-        both(ru + "layers.3", r < 2);
-    };
-    const int nb = c.n_blocks;
-    if (c.is_decoder) {
-        n.push_back("input");
-        n.push_back("layers.0");
-        for (int bi = 0; bi < nb; ++bi) {
-            const std::string pf = "layers." + std::to_string(bi + 1) + ".";
-            both(pf + (o.nearest_upsample ? "layers.1.1" : "layers.1"), true);
-            for (int r = 0; r < 3; ++r) unit(pf + "layers." + std::to_string(2 + r) + ".", r);
-        }
-    } else {
-        both("layers.0", true);
-        for (int bi = 0; bi < nb; ++bi) {
-            const std::string pf = "layers." + std::to_string(bi + 1) + ".";
-            for (int r = 0; r < 3; ++r) unit(pf + "layers." + std::to_string(r) + ".", r);
-            both(pf + "layers.4", bi + 1 < nb);
-        }
-    }
-    return n;
 }
 
 #if !SAT_OP_IS_F32
@@ -1034,456 +648,73 @@ int launch_ru_fused(const RuArgs& a, int B, hipStream_t s) {
     SAT_LAUNCH_CHECK();
     return 0;
 }
+// the whole unit in one launch where its channel count is one workgroup tile; the intermediate never leaves LDS
+int launch_ru(const void* ru_args, int B, hipStream_t s) {
+    const RuArgs& a = *static_cast<const RuArgs*>(ru_args);
+    SAT_CHECK_ARG(a.c7.N == 128 || a.c7.N == 256, SAT_E_UNSUPPORTED, "fused ResidualUnit: %d channels are neither 128 nor 256", a.c7.N);
+    // C = 128: a 2-stage ring (64 KiB) puts two workgroups on a CU, so one's epilogues overlap the other's main loop
+    if (a.c7.N == 128) return launch_ru_fused<128, 4, 2, 2>(a, B, s);
+    return launch_ru_fused<256, 2, 4, 3>(a, B, s);
+}
 #endif
 
-// one ResidualUnit (autoencoders.py:45-68): in S (snaked x) + R (raw x) -> R (raw x') and/or Sout (snake_next(x'))
-// With the range report on, every unit takes the two launches: the tensor between its convolutions then reaches memory (Y) and has a record
-int run_ru(const OobPlan::Block& blk, int r, int C, int L, int B, op_t* R, const op_t* S, op_t* Y, op_t* Sout,
-           const Snake& next, bool need_raw, hipStream_t s, Ranger& rg) {
-    static const int dil[3] = {1, 3, 9};
-    ConvArgs a = ru_c7_args(blk.ru_c7[r], S, L, dil[r]);
-    set_act(a, Y, blk.ru_sn2[r]);
-    ConvArgs c = ru_c1_args(blk.ru_c1[r], Y, L, R, need_raw);
-    set_act(c, Sout, next);
-#if !SAT_OP_IS_F32      // (fp32 build: the 128 x C intermediate would not fit next to the weight ring; two launches through Y)
-    if ((C == 128 || C == 256) && !rg.two_launches()) {      // the whole unit in one launch, the intermediate never leaves LDS
-        RuArgs f{a, c};
-        f.c7.out_snk = nullptr;
-        f.c1.in = nullptr;
-        // C = 128: a 2-stage ring (64 KiB) puts two workgroups on a CU, so one's epilogues overlap the other's main loop
-        if (C == 128) return launch_ru_fused<128, 4, 2, 2>(f, B, s);
-        return launch_ru_fused<256, 2, 4, 3>(f, B, s);
-    }
-#endif
-    const size_t n = (size_t)B * L * C;
-    SAT_TRY(launch_conv(a, B, s));
-    SAT_TRY(rg(Y, n));
-    SAT_TRY(launch_conv(c, B, s));
-    SAT_TRY(rg(Sout, n));
-    return need_raw ? rg(R, n) : 0;
+// ---- finalize: the launches behind each weight kind (weight norm folded: scale[i] = g[i] / ||v[i]||, one float per slice of v)
+int launch_pack_conv(const float* v, const float* g, float* scale, void* W, int Cout, int Cin, int k, int Npad, int Kpad, hipStream_t s) {
+    hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cout), dim3(256), 0, s, v, g, scale, Cin * k);
+    size_t n = (size_t)k * Npad * Kpad;
+    hipLaunchKernelGGL(wn_pack_conv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, (op_t*)W, Cout, Cin, k, Npad, Kpad);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+int launch_fold_f32(const float* v, const float* g, float* scale, float* w, int Cout, int slice, hipStream_t s) {
+    hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cout), dim3(256), 0, s, v, g, scale, slice);
+    size_t n = (size_t)Cout * slice;
+    hipLaunchKernelGGL(wn_fold_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, w, slice, n);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+int launch_pack_convT(const float* v, const float* g, float* scale, void* W, int Cin, int Cout, int stride, int Kp, int Np, hipStream_t s) {
+    hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cin), dim3(256), 0, s, v, g, scale, Cout * 2 * stride);
+    size_t n = (size_t)2 * stride * Np * Kp;
+    hipLaunchKernelGGL(wn_pack_convT_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, (op_t*)W, Cin, Cout, stride, Kp, Np);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+int launch_pack_nearest(const float* v, const float* g, float* scale, void* W, int Cin, int Cout, int stride, int Kp, int Np, hipStream_t s) {
+    hipLaunchKernelGGL(wn_invnorm_kernel, dim3(Cout), dim3(256), 0, s, v, g, scale, Cin * 2 * stride);
+    size_t n = (size_t)3 * stride * Np * Kp;
+    hipLaunchKernelGGL(wn_pack_nearest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, scale, (op_t*)W, Cin, Cout, stride, Kp, Np);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+int launch_snake_params(const float* alpha, const float* beta, float* a, float* ib, int C, int Cp, hipStream_t s) {
+    hipLaunchKernelGGL(snake_params_kernel, dim3(cdiv(Cp, 256)), dim3(256), 0, s, alpha, beta, a, ib, C, Cp);
+    SAT_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace
 
 namespace SAT_OPNS {
-
-// (the options were validated by sat_oobleck_plan_create_ex; channel counts are free: the plan pads every width to a multiple of 64)
-int oob_plan_create(const sat_oobleck_cfg* cfg, const sat_oobleck_options* opt, OobPlan** out_plan) {
-    SAT_CHECK_ARG(cfg && opt && out_plan, SAT_E_INVALID, "oobleck_plan_create: null argument");
-    SAT_CHECK_ARG(cfg->n_blocks >= 1 && cfg->n_blocks <= 8, SAT_E_UNSUPPORTED, "oobleck_plan_create: n_blocks %d not in 1..8", cfg->n_blocks);
-    SAT_CHECK_ARG(cfg->channels > 0, SAT_E_UNSUPPORTED, "oobleck_plan_create: channels %d must be positive", cfg->channels);
-    SAT_CHECK_ARG(cfg->io_channels >= 1 && cfg->io_channels <= 2, SAT_E_UNSUPPORTED, "oobleck_plan_create: io_channels must be 1 or 2");
-    SAT_CHECK_ARG(cfg->latent_dim > 0, SAT_E_UNSUPPORTED, "oobleck_plan_create: latent_dim %d must be positive", cfg->latent_dim);
-    OobPlan* p = new (std::nothrow) OobPlan();
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_create: out of host memory");
-    p->cfg = *cfg;
-    p->opt = *opt;
-    p->rr_names = range_names(*cfg, *opt);
-    p->ratio = 1;
-    for (int i = 0; i < cfg->n_blocks; ++i) {
-        SAT_CHECK_ARG(cfg->strides[i] >= 1 && cfg->strides[i] <= 16 && cfg->c_mults[i] >= 1, SAT_E_UNSUPPORTED, "oobleck_plan_create: bad stride/c_mult");
-        SAT_CHECK_ARG(resample_stride_ok(cfg->is_decoder != 0, opt->nearest_upsample != 0, cfg->strides[i]), SAT_E_UNSUPPORTED,
-                      "oobleck_plan_create: stride %d of block %d is not supported: the reference's %s", cfg->strides[i], i,
-                      cfg->is_decoder ? "ConvTranspose1d yields L * stride - 1 samples at an odd stride, the plan L * stride (nearest_upsample takes odd strides)"
-                                      : "stride-1 encoder convolution (k = 2, padding 1) yields L + 1 samples, the plan L");
-        p->ratio *= cfg->strides[i];
-    }
-    *out_plan = p;
-    return 0;
+const OobKernels* oob_kernels() {
+    static const OobKernels k = {
+        (int)sizeof(op_t),
+        SAT_OP_IS_F32 ? SAT_GEMM_FP32X : SAT_OP_IS_F16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16,
+        launch_conv,
+#if SAT_OP_IS_F32
+        nullptr,      // the 128 x C intermediate would not fit next to the weight ring: two launches through memory
+#else
+        launch_ru,
+#endif
+        launch_cf_to_cl,
+        launch_first_conv,
+        launch_pack_conv,
+        launch_fold_f32,
+        launch_pack_convT,
+        launch_pack_nearest,
+        launch_snake_params,
+    };
+    return &k;
 }
-
-void oob_plan_destroy(OobPlan* p) { delete p; }
-
-int oob_plan_set_tensor(OobPlan* p, const char* name, const float* data_dev, int64_t numel) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_set_tensor: bad argument");
-    return p->tensors.set("oobleck", name, data_dev, numel);
-}
-
-int oob_plan_finalize(OobPlan* p, sat_stream_t stream) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_finalize: null plan");
-    hipStream_t s = (hipStream_t)stream;
-    return plan_finalize(p, s, [&](Bump& ar) { return build(p, ar, s); });
-}
-
-int oob_workspace_bytes(const OobPlan* p, int32_t b, int32_t t_len, size_t* out_bytes) {
-    SAT_CHECK_ARG(p && out_bytes && b > 0 && t_len > 0, SAT_E_INVALID, "oobleck_workspace_bytes: bad argument");
-    SAT_CHECK_ARG(p->finalized, SAT_E_STATE, "oobleck_workspace_bytes: plan not finalized");
-    *out_bytes = carve(p, b, t_len, nullptr).total;
-    return 0;
-}
-
-int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, void* ws, size_t ws_bytes,
-                                  sat_stream_t stream) {
-    SAT_CHECK_ARG(p && p->finalized && p->cfg.is_decoder, SAT_E_STATE, "oobleck_decode: not a finalized decoder plan");
-    SAT_CHECK_ARG(z && audio && ws && B > 0 && T > 0, SAT_E_INVALID, "oobleck_decode: bad arguments");
-    SAT_CHECK_ARG(((uintptr_t)ws & 255) == 0, SAT_E_INVALID, "oobleck_decode: workspace must be 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    Bufs bf = carve(p, B, T, (char*)ws);
-    SAT_CHECK_ARG(ws_bytes >= bf.total, SAT_E_WORKSPACE, "oobleck_decode: workspace %zu < required %zu", ws_bytes, bf.total);
-    const sat_oobleck_cfg& c = p->cfg;
-    const int nb = c.n_blocks;
-    // latents -> channels-last bf16 (in Y), first conv (autoencoders.py:175) -> S0 = snake_block1(x)
-    SAT_TRY(launch_cf_to_cl(z, bf.Y, c.latent_dim, T, B, s));
-    Ranger rg{p, s};
-    SAT_TRY(rg(bf.Y, (size_t)B * T * pad64(c.latent_dim)));
-    op_t* S = bf.S0;
-    op_t* Sn = bf.S1;
-    {
-        ConvArgs a = same_conv_args(p->first, bf.Y, T);
-        set_act(a, S, p->blocks[0].sn_in);
-        SAT_TRY(launch_conv(a, B, s));
-        SAT_TRY(rg(S, (size_t)B * T * p->first.Cout));
-    }
-    int L = T;
-    for (int bi = 0; bi < nb; ++bi) {
-        const auto& blk = p->blocks[bi];
-        const int st = blk.stride;
-        ConvArgs a = upsample_args(blk.resample, S, L, st, p->opt.nearest_upsample != 0);
-        a.out_raw = bf.R;
-        set_act(a, Sn, blk.ru_sn1[0]);
-        SAT_TRY(launch_conv(a, B, s));
-        std::swap(S, Sn);
-        L *= st;
-        SAT_TRY(rg(S, (size_t)B * L * blk.cout));
-        SAT_TRY(rg(bf.R, (size_t)B * L * blk.cout));
-        for (int r = 0; r < 3; ++r) {
-            const Snake& next = r < 2 ? blk.ru_sn1[r + 1] : (bi + 1 < nb ? p->blocks[bi + 1].sn_in : p->final_snake);
-            SAT_TRY(run_ru(blk, r, blk.cout, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s, rg));
-            std::swap(S, Sn);
-        }
-    }
-    // final conv (autoencoders.py:187-188): no bias, tanh by option -> fp32 channel-first audio
-    ConvArgs a = final_conv_args(p->last, S, L, audio, c.io_channels, p->opt.final_tanh);
-    SAT_TRY(launch_conv(a, B, s));
-    return rg.done();
-}
-
-int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T, void* ws,
-                                  size_t ws_bytes, sat_stream_t stream) {
-    SAT_CHECK_ARG(p && p->finalized && !p->cfg.is_decoder, SAT_E_STATE, "oobleck_encode: not a finalized encoder plan");
-    SAT_CHECK_ARG(audio && out && ws && B > 0 && T > 0, SAT_E_INVALID, "oobleck_encode: bad arguments");
-    SAT_CHECK_ARG(((uintptr_t)ws & 255) == 0, SAT_E_INVALID, "oobleck_encode: workspace must be 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    Bufs bf = carve(p, B, T, (char*)ws);
-    SAT_CHECK_ARG(ws_bytes >= bf.total, SAT_E_WORKSPACE, "oobleck_encode: workspace %zu < required %zu", ws_bytes, bf.total);
-    const sat_oobleck_cfg& c = p->cfg;
-    const int nb = c.n_blocks;
-    int L = T * p->ratio;
-    op_t* S = bf.S0;
-    op_t* Sn = bf.S1;
-    const Snake& sn0 = p->blocks[0].ru_sn1[0];
-    SAT_TRY(launch_first_conv(audio, p->first_w_f32, p->first, sn0, bf.R, S, c.io_channels, c.channels, L, B, s));
-    Ranger rg{p, s};
-    SAT_TRY(rg(S, (size_t)B * L * pad64(c.channels)));
-    SAT_TRY(rg(bf.R, (size_t)B * L * pad64(c.channels)));
-    for (int bi = 0; bi < nb; ++bi) {
-        const auto& blk = p->blocks[bi];
-        for (int r = 0; r < 3; ++r) {
-            const Snake& next = r < 2 ? blk.ru_sn1[r + 1] : blk.sn_in;
-            SAT_TRY(run_ru(blk, r, blk.cin, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s, rg));
-            std::swap(S, Sn);
-        }
-        const int st = blk.stride;
-        const int Lo = L / st;
-        ConvArgs a = strided_args(blk.resample, S, L, st);
-        const bool lastb = bi + 1 == nb;
-        a.out_raw = lastb ? nullptr : bf.R;
-        const Snake& nx = lastb ? p->final_snake : p->blocks[bi + 1].ru_sn1[0];
-        set_act(a, Sn, nx);
-        SAT_TRY(launch_conv(a, B, s));
-        std::swap(S, Sn);
-        L = Lo;
-        SAT_TRY(rg(S, (size_t)B * L * blk.cout));
-        if (!lastb) SAT_TRY(rg(bf.R, (size_t)B * L * blk.cout));
-    }
-    ConvArgs a = final_conv_args(p->last, S, L, out, c.latent_dim, 0);
-    SAT_TRY(launch_conv(a, B, s));
-    return rg.done();
-}
-
-// ---- sat_oobleck_range_report and its companions, per build
-int oob_range_report(OobPlan* p, int32_t enable) {
-    SAT_CHECK_ARG(enable >= 0 && enable <= 2, SAT_E_INVALID, "oobleck_range_report: enable must be 0 (off), 1 (on) or 2 (zero the records), got %d", enable);
-    if (enable == 0) {
-        if (!p->rr) return 0;
-        SAT_HIP(hipDeviceSynchronize());          // launches in flight still accumulate into the records
-        p->rr_buf.release();
-        p->rr = nullptr;
-        return 0;
-    }
-    SAT_CHECK_ARG(sat_launch_range_stats, SAT_E_UNSUPPORTED, "oobleck_range_report: built without the range statistics kernel");
-    const size_t bytes = p->rr_names.size() * sizeof(sat_range_record);
-    if (enable == 2) {
-        SAT_CHECK_ARG(p->rr, SAT_E_STATE, "oobleck_range_report: the report is not enabled, there is nothing to zero");
-        SAT_HIP(hipDeviceSynchronize());
-        SAT_HIP(hipMemset(p->rr, 0, bytes));
-        return 0;
-    }
-    if (p->rr) return 0;          // already on: the records keep accumulating
-    SAT_TRY(p->rr_buf.reserve(bytes));
-    SAT_HIP(hipMemset(p->rr_buf.ptr, 0, bytes));
-    p->rr = (sat_range_record*)p->rr_buf.ptr;
-    return 0;
-}
-
-int oob_range_report_count(OobPlan* p, int32_t* out_records) {
-    SAT_CHECK_ARG(out_records, SAT_E_INVALID, "oobleck_range_report_count: null argument");
-    *out_records = (int32_t)p->rr_names.size();
-    return 0;
-}
-
-const char* oob_range_report_name(OobPlan* p, int32_t index) {
-    return index >= 0 && index < (int32_t)p->rr_names.size() ? p->rr_names[index].c_str() : nullptr;
-}
-
-int oob_range_report_read(OobPlan* p, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes, sat_stream_t stream) {
-    SAT_CHECK_ARG(out_host, SAT_E_INVALID, "oobleck_range_report_read: null argument");
-    SAT_CHECK_ARG(record_bytes == sizeof(sat_range_record), SAT_E_INVALID,
-                  "oobleck_range_report_read: sat_range_record of %zu bytes; this library knows %zu", record_bytes, sizeof(sat_range_record));
-    const int n = (int)p->rr_names.size();
-    SAT_CHECK_ARG(capacity_records >= n, SAT_E_INVALID, "oobleck_range_report_read: room for %d records, need %d", capacity_records, n);
-    SAT_CHECK_ARG(p->rr, SAT_E_STATE, "oobleck_range_report_read: the report is not enabled (sat_oobleck_range_report)");
-    SAT_HIP(hipMemcpyAsync(out_host, p->rr, (size_t)n * sizeof(sat_range_record), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    SAT_HIP(hipStreamSynchronize((hipStream_t)stream));
-    return 0;
-}
-
-// ---- sat_oobleck_unit: one layer on the caller's tensors (tests).  A plan object of its own holds the caller's fp32 tensors under fixed
-// names ("conv." / "act.": the layer and the activation behind it; "conv2." / "act2.": a ResidualUnit's 1 x 1 convolution and the activation
-// behind the unit), plan_finalize runs the make_* the plan's build() would run for that layer, and the launch goes through the helpers above
-int oob_unit(const sat_oobleck_unit_desc* u, sat_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const int kind = u->kind, B = u->b, L = u->t_len, Ci = u->c_in, Co = u->c_out, st = u->stride;
-    SAT_CHECK_ARG(kind >= SAT_OOBLECK_UNIT_CONV7 && kind <= SAT_OOBLECK_UNIT_CF_TO_CL, SAT_E_UNSUPPORTED, "oobleck_unit: unknown kind %d", kind);
-    SAT_CHECK_ARG(u->activation == ACT_SNAKE || u->activation == ACT_ELU, SAT_E_UNSUPPORTED, "oobleck_unit: unknown activation %d", u->activation);
-    SAT_CHECK_ARG(B > 0 && L > 0 && Ci > 0 && (Co > 0 || kind == SAT_OOBLECK_UNIT_CF_TO_CL), SAT_E_INVALID, "oobleck_unit: b, t_len, c_in, c_out must be positive");
-    const bool resample = kind == SAT_OOBLECK_UNIT_CONVT || kind == SAT_OOBLECK_UNIT_NEAREST || kind == SAT_OOBLECK_UNIT_STRIDED;
-    const bool dilated = kind == SAT_OOBLECK_UNIT_CONV7 || kind == SAT_OOBLECK_UNIT_RESIDUAL;
-    const bool residual = kind == SAT_OOBLECK_UNIT_CONV1_RES || kind == SAT_OOBLECK_UNIT_RESIDUAL;
-    const bool from_cf = kind == SAT_OOBLECK_UNIT_FIRST_CONV || kind == SAT_OOBLECK_UNIT_CF_TO_CL;
-    const bool to_cf = kind == SAT_OOBLECK_UNIT_FINAL_DEC || kind == SAT_OOBLECK_UNIT_FINAL_ENC;
-    if (resample) {
-        SAT_CHECK_ARG(resample_stride_ok(kind != SAT_OOBLECK_UNIT_STRIDED, kind == SAT_OOBLECK_UNIT_NEAREST, st), SAT_E_UNSUPPORTED,
-                      "oobleck_unit: stride %d is outside what a plan runs for kind %d", st, kind);
-        SAT_CHECK_ARG(kind != SAT_OOBLECK_UNIT_STRIDED || L % st == 0, SAT_E_INVALID, "oobleck_unit: t_len %d is no multiple of stride %d", L, st);
-    }
-    const int r = u->dilation == 1 ? 0 : u->dilation == 3 ? 1 : 2;
-    SAT_CHECK_ARG(!dilated || u->dilation == 1 || u->dilation == 3 || u->dilation == 9, SAT_E_UNSUPPORTED, "oobleck_unit: dilation %d is not 1, 3 or 9", u->dilation);
-    SAT_CHECK_ARG(!residual || (Ci == Co && u->res && (!u->out_raw || u->out_raw == u->res) && u->out_snk), SAT_E_INVALID,
-                  "oobleck_unit: a residual layer needs c_in == c_out, res, out_snk, and out_raw NULL or == res");
-    SAT_CHECK_ARG(kind != SAT_OOBLECK_UNIT_FIRST_CONV || (Ci <= 2 && u->out_raw && u->out_snk), SAT_E_INVALID,
-                  "oobleck_unit: the first convolution takes 1 or 2 channels and writes out_raw and out_snk");
-    SAT_CHECK_ARG(from_cf ? u->in_cf != nullptr : u->in != nullptr, SAT_E_INVALID, "oobleck_unit: input pointer missing");
-    SAT_CHECK_ARG(to_cf ? u->out_cf != nullptr : (u->out_raw || u->out_snk), SAT_E_INVALID, "oobleck_unit: output pointer missing");
-    SAT_CHECK_ARG(kind == SAT_OOBLECK_UNIT_CF_TO_CL || (u->weight_g && u->weight_v), SAT_E_INVALID, "oobleck_unit: weight_g / weight_v missing");
-    const bool has_bias = kind != SAT_OOBLECK_UNIT_NEAREST && kind != SAT_OOBLECK_UNIT_FINAL_DEC && kind != SAT_OOBLECK_UNIT_CF_TO_CL;
-    SAT_CHECK_ARG(!has_bias || u->bias, SAT_E_INVALID, "oobleck_unit: bias missing");
-    const bool act_behind = u->out_snk != nullptr;      // the activation whose result out_snk holds
-    const bool snake = u->activation == ACT_SNAKE;
-    SAT_CHECK_ARG(!(act_behind && snake && kind != SAT_OOBLECK_UNIT_RESIDUAL) || (u->alpha && u->beta), SAT_E_INVALID, "oobleck_unit: alpha / beta missing");
-    if (kind == SAT_OOBLECK_UNIT_RESIDUAL)
-        SAT_CHECK_ARG(u->weight_g2 && u->weight_v2 && u->bias2 && (!snake || (u->alpha && u->beta && u->alpha2 && u->beta2)), SAT_E_INVALID,
-                      "oobleck_unit: a ResidualUnit needs both convolutions and both activations");
-
-    OobPlan p;
-    p.cfg = sat_oobleck_cfg{};
-    p.cfg.gemm_dtype = u->gemm_dtype;
-    p.opt = sat_oobleck_options{u->activation, u->final_tanh, kind == SAT_OOBLECK_UNIT_NEAREST};
-    auto set = [&](const char* name, const float* ptr, int64_t n) { return ptr ? p.tensors.set("oobleck", name, ptr, n) : 0; };
-    const int ktaps = kind == SAT_OOBLECK_UNIT_CONV1_RES ? 1 : kind == SAT_OOBLECK_UNIT_FINAL_ENC ? 3 : resample ? 2 * st : 7;
-    if (kind != SAT_OOBLECK_UNIT_CF_TO_CL) {
-        const int gdim = kind == SAT_OOBLECK_UNIT_CONVT ? Ci : Co;      // weight norm runs over dim 0: ConvTranspose1d weights are [c_in, c_out, k]
-        SAT_TRY(set("conv.weight_g", u->weight_g, gdim));
-        SAT_TRY(set("conv.weight_v", u->weight_v, (int64_t)Ci * Co * ktaps));
-        if (has_bias) SAT_TRY(set("conv.bias", u->bias, Co));
-        SAT_TRY(set("act.alpha", u->alpha, Co));
-        SAT_TRY(set("act.beta", u->beta, Co));
-    }
-    if (kind == SAT_OOBLECK_UNIT_RESIDUAL) {
-        SAT_TRY(set("conv2.weight_g", u->weight_g2, Co));
-        SAT_TRY(set("conv2.weight_v", u->weight_v2, (int64_t)Co * Co));
-        SAT_TRY(set("conv2.bias", u->bias2, Co));
-        SAT_TRY(set("act2.alpha", u->alpha2, Co));
-        SAT_TRY(set("act2.beta", u->beta2, Co));
-    }
-    OobPlan::Block blk;
-    ConvW cw;
-    Snake sn, next;
-    float* w_f32 = nullptr;
-    op_t* Y = nullptr;
-    SAT_TRY(plan_finalize(&p, s, [&](Bump& ar) -> int {
-        p.zero_page = (op_t*)ar.take(256);
-        if (!ar.dry()) SAT_HIP(hipMemsetAsync(p.zero_page, 0, 256, s));
-        if (kind == SAT_OOBLECK_UNIT_CF_TO_CL) return 0;
-        if (kind == SAT_OOBLECK_UNIT_RESIDUAL) {
-            SAT_TRY(make_conv(&p, ar, "conv.", Ci, Co, 7, true, &blk.ru_c7[r], s));
-            SAT_TRY(make_snake(&p, ar, "act.", Co, &blk.ru_sn2[r], s));
-            SAT_TRY(make_conv(&p, ar, "conv2.", Co, Co, 1, true, &blk.ru_c1[r], s));
-            SAT_TRY(make_snake(&p, ar, "act2.", Co, &next, s));
-            Y = (op_t*)ar.take((size_t)B * L * pad64(Co) * sizeof(op_t));
-            return 0;
-        }
-        if (act_behind) SAT_TRY(make_snake(&p, ar, "act.", Co, &sn, s));
-        if (kind == SAT_OOBLECK_UNIT_CONVT) return make_convT(&p, ar, "conv.", Ci, Co, st, &cw, s);
-        if (kind == SAT_OOBLECK_UNIT_NEAREST) return make_nearest(&p, ar, "conv.", Ci, Co, st, &cw, s);
-        return make_conv(&p, ar, "conv.", Ci, Co, ktaps, has_bias, &cw, s, kind == SAT_OOBLECK_UNIT_FIRST_CONV ? &w_f32 : nullptr);
-    }));
-
-    const op_t* in = (const op_t*)u->in;
-    op_t *res = (op_t*)const_cast<void*>(u->res), *out_raw = (op_t*)u->out_raw, *out_snk = (op_t*)u->out_snk;
-    Ranger rg{&p, s};
-    rg.unfused = u->two_launch != 0;
-    ConvArgs a{};
-    switch (kind) {
-        case SAT_OOBLECK_UNIT_CF_TO_CL: SAT_TRY(launch_cf_to_cl(u->in_cf, out_raw ? out_raw : out_snk, Ci, L, B, s)); break;
-        case SAT_OOBLECK_UNIT_FIRST_CONV: SAT_TRY(launch_first_conv(u->in_cf, w_f32, cw, sn, out_raw, out_snk, Ci, Co, L, B, s)); break;
-        case SAT_OOBLECK_UNIT_RESIDUAL:
-            SAT_TRY(run_ru(blk, r, pad64(Co), L, B, res, in, Y, out_snk, next, out_raw != nullptr, s, rg));
-            break;
-        case SAT_OOBLECK_UNIT_CONV7: a = ru_c7_args(cw, in, L, u->dilation); break;
-        case SAT_OOBLECK_UNIT_CONV1_RES: a = ru_c1_args(cw, in, L, res, out_raw != nullptr); break;
-        case SAT_OOBLECK_UNIT_CONVT: a = upsample_args(cw, in, L, st, false); break;
-        case SAT_OOBLECK_UNIT_NEAREST: a = upsample_args(cw, in, L, st, true); break;
-        case SAT_OOBLECK_UNIT_STRIDED: a = strided_args(cw, in, L, st); break;
-        case SAT_OOBLECK_UNIT_FINAL_DEC: a = final_conv_args(cw, in, L, u->out_cf, Co, u->final_tanh != 0); break;
-        default: a = final_conv_args(cw, in, L, u->out_cf, Co, 0); break;      // SAT_OOBLECK_UNIT_FINAL_ENC
-    }
-    if (a.W) {      // the kinds that are one launch of the convolution kernel
-        if (!to_cf) {
-            if (kind != SAT_OOBLECK_UNIT_CONV1_RES) a.out_raw = out_raw;
-            if (out_snk) set_act(a, out_snk, sn);
-        }
-        SAT_TRY(launch_conv(a, B, s));
-    }
-    SAT_HIP(hipStreamSynchronize(s));      // the arena goes with p
-    return 0;
-}
-
 }  // namespace SAT_OPNS
 
-#if !defined(SAT_OPERAND_F16) && !defined(SAT_OPERAND_F32)
-// ---- C ABI (bf16 build only): the plan's operand format (sat_oobleck_cfg.gemm_dtype, first member of every build's plan) picks the build
-#define SAT_OOB_DECLARE(NS)                                                                                                       \
-    namespace NS {                                                                                                                \
-    struct OobPlan;                                                                                                               \
-    int oob_plan_create(const sat_oobleck_cfg* cfg, const sat_oobleck_options* opt, OobPlan** out_plan);                          \
-    void oob_plan_destroy(OobPlan* p);                                                                                            \
-    int oob_plan_set_tensor(OobPlan* p, const char* name, const float* data_dev, int64_t numel);                                  \
-    int oob_plan_finalize(OobPlan* p, sat_stream_t stream);                                                                       \
-    int oob_workspace_bytes(const OobPlan* p, int32_t b, int32_t t_len, size_t* out_bytes);                                       \
-    int oob_decode(OobPlan* p, const float* z, float* audio, int32_t B, int32_t T, void* ws, size_t ws_bytes, sat_stream_t stream); \
-    int oob_encode(OobPlan* p, const float* audio, float* out, int32_t B, int32_t T, void* ws, size_t ws_bytes, sat_stream_t stream); \
-    int oob_range_report(OobPlan* p, int32_t enable);                                                                             \
-    int oob_range_report_count(OobPlan* p, int32_t* out_records);                                                                 \
-    const char* oob_range_report_name(OobPlan* p, int32_t index);                                                                 \
-    int oob_range_report_read(OobPlan* p, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes, sat_stream_t stream); \
-    int oob_unit(const sat_oobleck_unit_desc* u, sat_stream_t stream);                                                            \
-    }
-SAT_OOB_DECLARE(f16)
-SAT_OOB_DECLARE(f32)
-#undef SAT_OOB_DECLARE
-static inline int32_t oob_dtype(const void* p) { return static_cast<const sat_oobleck_cfg*>(p)->gemm_dtype; }
-// one call into the build that owns plan p (the same function name in namespaces bf16 / f16 / f32)
-#define SAT_OOB_CALL(p, fn, ...)                                                                                                  \
-    (oob_dtype(p) == SAT_GEMM_FP16    ? f16::fn(reinterpret_cast<f16::OobPlan*>(const_cast<sat_oobleck_plan*>(p)), __VA_ARGS__)   \
-     : oob_dtype(p) == SAT_GEMM_FP32X ? f32::fn(reinterpret_cast<f32::OobPlan*>(const_cast<sat_oobleck_plan*>(p)), __VA_ARGS__)   \
-                                      : bf16::fn(reinterpret_cast<bf16::OobPlan*>(const_cast<sat_oobleck_plan*>(p)), __VA_ARGS__))
-
-extern "C" int sat_oobleck_plan_create_ex(const sat_oobleck_cfg* cfg, const sat_oobleck_options* options, size_t options_bytes,
-                                          sat_oobleck_plan** out_plan) {
-    SAT_CHECK_ARG(cfg && out_plan, SAT_E_INVALID, "oobleck_plan_create: null argument");
-    sat_oobleck_options opt = {SAT_OOBLECK_ACT_SNAKE, 0, 0};      // options == NULL: the defaults of sat_oobleck_plan_create
-    if (options) {
-        SAT_CHECK_ARG(options_bytes == sizeof(sat_oobleck_options), SAT_E_INVALID,
-                      "oobleck_plan_create_ex: options_bytes %zu is not the size of this version's sat_oobleck_options (%zu)", options_bytes,
-                      sizeof(sat_oobleck_options));
-        opt = *options;
-    }
-    SAT_CHECK_ARG(cfg->gemm_dtype == SAT_GEMM_BF16 || cfg->gemm_dtype == SAT_GEMM_FP16 || cfg->gemm_dtype == SAT_GEMM_FP32X,
-                  SAT_E_UNSUPPORTED, "oobleck_plan_create: gemm_dtype must be 0 (bf16), 3 (fp16) or 2 (fp32)");
-    SAT_CHECK_ARG(opt.activation == SAT_OOBLECK_ACT_SNAKE || opt.activation == SAT_OOBLECK_ACT_ELU, SAT_E_UNSUPPORTED,
-                  "oobleck_plan_create_ex: activation %d is neither SAT_OOBLECK_ACT_SNAKE (0) nor SAT_OOBLECK_ACT_ELU (1)", opt.activation);
-    SAT_CHECK_ARG((opt.final_tanh == 0 || opt.final_tanh == 1) && (opt.nearest_upsample == 0 || opt.nearest_upsample == 1), SAT_E_UNSUPPORTED,
-                  "oobleck_plan_create_ex: final_tanh / nearest_upsample must be 0 or 1");
-    SAT_CHECK_ARG(cfg->is_decoder || (!opt.final_tanh && !opt.nearest_upsample), SAT_E_UNSUPPORTED,
-                  "oobleck_plan_create_ex: final_tanh / nearest_upsample are decoder options");
-    switch (cfg->gemm_dtype) {
-        case SAT_GEMM_FP16: return f16::oob_plan_create(cfg, &opt, reinterpret_cast<f16::OobPlan**>(out_plan));
-        case SAT_GEMM_FP32X: return f32::oob_plan_create(cfg, &opt, reinterpret_cast<f32::OobPlan**>(out_plan));
-        default: return bf16::oob_plan_create(cfg, &opt, reinterpret_cast<bf16::OobPlan**>(out_plan));
-    }
-}
-// The original entry point and its contract: Snake, transposed convolutions, no tanh, channels and the decoder's latent_dim multiples of 64
-extern "C" int sat_oobleck_plan_create(const sat_oobleck_cfg* cfg, sat_oobleck_plan** out_plan) {
-    SAT_CHECK_ARG(cfg && out_plan, SAT_E_INVALID, "oobleck_plan_create: null argument");
-    SAT_CHECK_ARG(cfg->gemm_dtype == SAT_GEMM_BF16 || cfg->gemm_dtype == SAT_GEMM_FP16 || cfg->gemm_dtype == SAT_GEMM_FP32X,
-                  SAT_E_UNSUPPORTED, "oobleck_plan_create: gemm_dtype must be 0 (bf16), 3 (fp16) or 2 (fp32)");
-    SAT_CHECK_ARG(cfg->channels % 64 == 0 && cfg->channels > 0, SAT_E_UNSUPPORTED,
-                  "oobleck_plan_create: channels %d must be a multiple of 64 (sat_oobleck_plan_create_ex takes any)", cfg->channels);
-    if (cfg->is_decoder)
-        SAT_CHECK_ARG(cfg->latent_dim % 64 == 0, SAT_E_UNSUPPORTED,
-                      "oobleck_plan_create: decoder latent_dim %d must be a multiple of 64 (sat_oobleck_plan_create_ex takes any)", cfg->latent_dim);
-    return sat_oobleck_plan_create_ex(cfg, nullptr, 0, out_plan);
-}
-extern "C" void sat_oobleck_plan_destroy(sat_oobleck_plan* p) {
-    if (!p) return;
-    switch (oob_dtype(p)) {
-        case SAT_GEMM_FP16: f16::oob_plan_destroy(reinterpret_cast<f16::OobPlan*>(p)); break;
-        case SAT_GEMM_FP32X: f32::oob_plan_destroy(reinterpret_cast<f32::OobPlan*>(p)); break;
-        default: bf16::oob_plan_destroy(reinterpret_cast<bf16::OobPlan*>(p));
-    }
-}
-extern "C" int sat_oobleck_plan_set_tensor(sat_oobleck_plan* p, const char* name, const float* data_dev, int64_t numel) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_set_tensor: null plan");
-    return SAT_OOB_CALL(p, oob_plan_set_tensor, name, data_dev, numel);
-}
-extern "C" int sat_oobleck_plan_finalize(sat_oobleck_plan* p, sat_stream_t stream) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_finalize: null plan");
-    return SAT_OOB_CALL(p, oob_plan_finalize, stream);
-}
-extern "C" int sat_oobleck_workspace_bytes(const sat_oobleck_plan* p, int32_t b, int32_t t_len, size_t* out_bytes) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_workspace_bytes: null plan");
-    return SAT_OOB_CALL(p, oob_workspace_bytes, b, t_len, out_bytes);
-}
-extern "C" int sat_oobleck_decode(sat_oobleck_plan* p, const float* z_dev, float* audio_dev, int32_t b, int32_t t_len, void* ws, size_t ws_bytes,
-                                  sat_stream_t stream) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_decode: null plan");
-    return SAT_OOB_CALL(p, oob_decode, z_dev, audio_dev, b, t_len, ws, ws_bytes, stream);
-}
-extern "C" int sat_oobleck_encode(sat_oobleck_plan* p, const float* audio_dev, float* out_dev, int32_t b, int32_t t_len, void* ws, size_t ws_bytes,
-                                  sat_stream_t stream) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_encode: null plan");
-    return SAT_OOB_CALL(p, oob_encode, audio_dev, out_dev, b, t_len, ws, ws_bytes, stream);
-}
-extern "C" int sat_oobleck_range_report(sat_oobleck_plan* p, int32_t enable) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_range_report: null plan");
-    return SAT_OOB_CALL(p, oob_range_report, enable);
-}
-extern "C" int sat_oobleck_range_report_count(const sat_oobleck_plan* p, int32_t* out_records) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_range_report_count: null plan");
-    return SAT_OOB_CALL(p, oob_range_report_count, out_records);
-}
-extern "C" const char* sat_oobleck_range_report_name(const sat_oobleck_plan* p, int32_t index) {
-    if (!p) return nullptr;
-    return SAT_OOB_CALL(p, oob_range_report_name, index);
-}
-extern "C" int sat_oobleck_range_report_read(sat_oobleck_plan* p, sat_range_record* out_host, int32_t capacity_records, size_t record_bytes,
-                                             sat_stream_t stream) {
-    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_range_report_read: null plan");
-    return SAT_OOB_CALL(p, oob_range_report_read, out_host, capacity_records, record_bytes, stream);
-}
-#undef SAT_OOB_CALL
-// one layer alone (tests): the descriptor's gemm_dtype picks the build, as a plan's does
-extern "C" int sat_oobleck_unit(const sat_oobleck_unit_desc* desc, size_t desc_bytes, sat_stream_t stream) {
-    SAT_CHECK_ARG(desc, SAT_E_INVALID, "oobleck_unit: null descriptor");
-    SAT_CHECK_ARG(desc_bytes == sizeof(sat_oobleck_unit_desc), SAT_E_INVALID,
-                  "oobleck_unit: desc_bytes %zu is not the size of this version's sat_oobleck_unit_desc (%zu)", desc_bytes, sizeof(sat_oobleck_unit_desc));
-    switch (desc->gemm_dtype) {
-        case SAT_GEMM_BF16: return bf16::oob_unit(desc, stream);
-        case SAT_GEMM_FP16: return f16::oob_unit(desc, stream);
-        case SAT_GEMM_FP32X: return f32::oob_unit(desc, stream);
-    }
-    SAT_CHECK_ARG(false, SAT_E_UNSUPPORTED, "oobleck_unit: gemm_dtype must be 0 (bf16), 3 (fp16) or 2 (fp32)");
-    return SAT_E_UNSUPPORTED;
-}
-#endif

@@ -1,4 +1,4 @@
-// The host-side lifecycle every plan shares (dit_plan.hip, oobleck.hip in its three builds, t5_encoder.hip, roberta_encoder.hip):
+// The host-side lifecycle every plan shares (dit_plan.hip, oobleck_plan.hip, t5_encoder.hip, roberta_encoder.hip):
 // create -> set_tensor (name -> caller's fp32 device pointer) -> finalize (count the arena, allocate it, copy / re-pack into it,
 // synchronise, forget the pointers) -> per-call workspace carved with the same allocator -> destroy.  Host code only, internal linkage.
 #pragma once

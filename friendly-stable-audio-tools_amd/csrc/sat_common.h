@@ -21,12 +21,13 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 // models/transformer.py:496-504 flash-attn fp16, models/pretransforms.py:39-59 model_half).  Everything that names the element type
 // in those files goes through op_t / opx8 / f32_to_op / mfma_*; the host-facing launchers of the two builds live in namespace
 // bf16 / f16 (SAT_OPNS), the bf16 build owns the un-namespaced dispatchers and every extern "C" symbol.  Files compiled once
-// (dit_plan.hip, layernorm.hip, ...) see op_t = bf16 and treat operand buffers as opaque 16-bit storage.
+// (dit_plan.hip, oobleck_plan.hip, layernorm.hip, ...) see op_t = bf16 and treat operand buffers as opaque storage.
 // fp16 range policy: conversions SATURATE at +-65504 (MODE.FP16_OVFL, set by sat_f16_saturate() at the top of every kernel of the
 // fp16 build) instead of producing infinities; inf / NaN inputs still propagate.
 // A third operand format exists for oobleck.hip only: -DSAT_OPERAND_F32, op_t = float (namespace f32), the convolutions on the
 // exact f32-input MFMA (the reference's model_half=False codec).  The 16-bit helpers below (mfma_32x32x16, pack_op2, ...) are not
-// defined in that build.
+// defined in that build.  oobleck.hip holds kernels and launchers only and exports one table of launchers per build
+// (SAT_OPNS::oob_kernels(), oobleck_kernels.h); the codec's plan and its extern "C" symbols are oobleck_plan.hip, compiled once.
 #ifdef SAT_OPERAND_F16
 typedef _Float16 op_t;
 #define SAT_OPNS f16
