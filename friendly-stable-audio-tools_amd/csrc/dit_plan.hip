@@ -29,6 +29,7 @@ struct Proj {
     int n = 0, k = 0;
     ProjKind kind = PROJ_PLAIN;
     int f16 = 0;          // 16-bit kinds: the operand format of its block (layer_f16), 1 = IEEE fp16
+    int taps = 1;         // sat_dit_plan_set_ff_conv: w is the tap-major image [n, taps * k] of a Conv1d weight [n, k, taps] (pack_conv)
     bool nonorm = false;  // remove_norms: no LayerNorm in front, A is the residual row itself, rounded (Forward::layernorm)
     bool image = false;   // ... and that rounding is already in A: the 16-bit image the previous residual epilogue wrote under ln_fold
     float *scale = nullptr, *c1 = nullptr, *c2 = nullptr, *bias = nullptr;
@@ -81,6 +82,9 @@ struct sat_dit_plan {
     bool remove_norms = false;      // pre_norm / cross_attend_norm / ff_norm are the identity (Proj::nonorm)
     bool ff_glu = true;             // false: ff.ff.0 is Linear + SiLU, FF-in runs with the plain-activation epilogue (EPI_ACT16)
     bool block_options() const { return conformer || remove_norms || !ff_glu; }
+    // ff_kwargs use_conv (sat_dit_plan_set_ff_conv): kernel size of the feed-forward's convolutions, 1 = Linear and nothing changes
+    int ff_conv = 1;
+    bool ln_fold_asked = false;     // what sat_dit_plan_create made of cfg.ln_fold; ln_fold is this and ff_conv == 1
     // per-generation context (sat_dit_prepare_context)
     DevBuf ctx_buf;
     int ctx_bf = 0, ctx_lc = 0, ctx_lcpad = 0;
@@ -199,6 +203,28 @@ int pack_proj(sat_dit_plan* p, Bump& ar, const std::string& pf, const char* weig
     return 0;
 }
 
+// A feed-forward Conv1d (ff_kwargs use_conv): `pf + weight` [n, k, taps] as the tap-major image [n, taps * k] in the block's format (fp32 in the
+// verification mode), the operand of the contraction over taps row-shifted copies of A (ff_conv.hip); `pf + bias` [n] as it is.  No fold: the
+// row statistics of the LayerNorm in front would differ per tap
+int pack_conv(sat_dit_plan* p, Bump& ar, const std::string& pf, const char* weight, const char* bias, ProjFamily family, int l, int n, int k,
+              Proj* out, hipStream_t s) {
+    Proj& r = *out;
+    r = Proj{};
+    r.n = n; r.k = k; r.taps = p->ff_conv; r.f16 = layer_f16(p, l);
+    r.kind = p->cfg.gemm_dtype == 2 ? PROJ_F32 : PROJ_PLAIN;
+    r.nonorm = norm_removed(p, family);
+    const size_t numel = (size_t)n * k * r.taps;
+    r.w = (op_t*)ar.take(numel * (r.kind == PROJ_F32 ? 4 : 2));
+    if (bias) r.bias = (float*)ar.take((size_t)n * 4);
+    if (ar.dry()) return 0;
+    const float *src, *b = nullptr;
+    SAT_TRY(get_tensor(p, pf + weight, (int64_t)numel, &src));
+    if (bias) SAT_TRY(get_tensor(p, pf + bias, n, &b));
+    SAT_TRY(sat_launch_pack_conv_taps(src, r.w, n, k, r.taps, r.kind == PROJ_F32 ? SAT_GEMM_FP32X : r.f16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16, s));
+    if (bias) SAT_HIP(hipMemcpyAsync(r.bias, b, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
 int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
     const sat_dit_cfg& c = p->cfg;
     const int D = c.embed_dim, C = c.io_channels, Dc = c.cond_embed_dim, Dct = c.cond_token_dim, Dg = c.global_cond_dim;
@@ -297,12 +323,20 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
             SAT_TRY(pack("conformer.pointwise_conv_2.weight", nullptr, FAM_CPW2, D, D, 0, nullptr, nullptr, &L.cpw2));
         }
         // ff_kwargs glu=False (transformer.py:262-268): Sequential(Identity, Linear(D, inner, bias=not no_bias), Identity, SiLU) -> keys "ff.ff.0.1.*"
-        if (!p->ff_glu)
+        // ff_kwargs use_conv (transformer.py:222,262-287): the output projection is Conv1d(inner, D, k), without GLU the input one Conv1d(D, inner, k)
+        // under the same keys; GLU builds its own Linear and stays one
+        const bool conv = p->ff_conv > 1;
+        const char* b1 = p->tensors.has(pf + "ff.ff.0.1.bias") ? "ff.ff.0.1.bias" : nullptr;
+        if (conv && !p->ff_glu)
+            SAT_TRY(pack_conv(p, ar, pf, "ff.ff.0.1.weight", b1, FAM_FF1, l, inner, D, &L.ff1, s));
+        else if (!p->ff_glu)
             SAT_TRY(pack("ff.ff.0.1.weight", p->tensors.has(pf + "ff.ff.0.1.bias") ? "ff.ff.0.1.bias" : nullptr, FAM_FF1, inner, D, 0, L.ff_g, L.ff_b, &L.ff1));
         else
             SAT_TRY(pack("ff.ff.0.proj.weight", "ff.ff.0.proj.bias", FAM_FF1, 2 * inner, D, 1, L.ff_g, L.ff_b, &L.ff1));
         // ff_kwargs no_bias (transformer.py:270): the output Linear of the feed-forward has no bias tensor; FF-out then runs without one
-        SAT_TRY(pack("ff.ff.2.weight", p->tensors.has(pf + "ff.ff.2.bias") ? "ff.ff.2.bias" : nullptr, FAM_FF2, D, inner, 0, nullptr, nullptr, &L.ff2));
+        const char* b2 = p->tensors.has(pf + "ff.ff.2.bias") ? "ff.ff.2.bias" : nullptr;
+        if (conv) SAT_TRY(pack_conv(p, ar, pf, "ff.ff.2.weight", b2, FAM_FF2, l, D, inner, &L.ff2, s));
+        else SAT_TRY(pack("ff.ff.2.weight", b2, FAM_FF2, D, inner, 0, nullptr, nullptr, &L.ff2));
     }
     if (hd128) {      // behind everything a 64-channel plan places: the 32 frequencies and the [smax][32] table the head split rotates with
         if (p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 32, &p->inv_freq, s));
@@ -329,6 +363,7 @@ struct Workspace {
     float* f32_wide = nullptr;   // fp32 verification mode: [M, max(3D, 2 inner)] GEMM output before the head split / SwiGLU
     float* slab = nullptr;       // K-split scratch of the 8-phase FF-out GEMM (GemmArgs::slab), present where that schedule splits
     size_t slab_bytes = 0;
+    float* f32_col = nullptr;    // fp32 verification mode of a plan with sat_dit_plan_set_ff_conv: [M, taps * max(D, inner)] row gather in front of sat_gemm_f32
     float* qkv32 = nullptr;      // 128-channel heads: [M, 3D] fp32 output of to_qkv / [Mc, D] of the cross to_q in front of the head split
     size_t qkv_bytes;
     size_t total;
@@ -359,6 +394,7 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
         w.As = nullptr; w.Hs = nullptr; w.AOs = nullptr;
         w.gsum = c.adaln ? (float*)ws.take((size_t)bf * D * 4) : nullptr;
         w.ssg = c.adaln ? (float*)ws.take((size_t)bf * c.depth * 6 * D * 4) : nullptr;
+        if (p->ff_conv > 1) w.f32_col = (float*)ws.take(M * (size_t)p->ff_conv * (p->inner > D ? p->inner : D) * 4);      // behind everything a Linear plan carves
         w.total = ws.off;
         return w;
     }
@@ -445,11 +481,32 @@ struct Forward {
         return range(l, slot, buf, (size_t)seqs * H * Spad * p->hd, (size_t)seqs * S * D);
     }
 
+    // sat_dit_profile: the event pair round the FF-in launch of block depth / 2
+    bool profiled(int l) const { return p->prof_on && l == p->cfg.depth / 2 && p->prof_n < kProfMaxPairs; }
+    int prof_begin() const {
+        if ((int)p->prof_ev.size() < 2 * (p->prof_n + 1)) {
+            hipEvent_t e0, e1;
+            SAT_HIP(hipEventCreate(&e0));
+            SAT_HIP(hipEventCreate(&e1));
+            p->prof_ev.push_back(e0);
+            p->prof_ev.push_back(e1);
+        }
+        SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n], s));
+        return 0;
+    }
+    int prof_end(long long m, long long n, long long k) const {      // the launch's GEMM shape
+        SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n + 1], s));
+        p->prof_n++;
+        p->prof_m = m; p->prof_nn = n; p->prof_k = k;
+        return 0;
+    }
+
     int block(int l) const;
     int block_f32(int l) const;
     int attention_hd128(int l) const;
     int conformer(int l) const;
     int feed_forward(int l) const;
+    int feed_forward_conv(int l) const;
 };
 
 // fp32 verification mode: the same block on f32_ref.hip, fp32 everywhere
@@ -486,12 +543,21 @@ int Forward::block_f32(int l) const {
         SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.cpw2), nullptr, w.X, M, D, D, D, 1, nullptr, 1, 0, s));
     }
     SAT_TRY(norm(L.ff_g, L.ff_b, M, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr, S, ssg_ld));
-    if (!p->ff_glu) {      // Linear + SiLU
+    const int taps = p->ff_conv;
+    if (!p->ff_glu && taps > 1) {      // Conv1d(D, inner, k) + SiLU: the rows of the window gathered side by side, then the same GEMM at K = k D
+        SAT_TRY(sat_launch_im2col_rows_f32(A32, w.f32_col, bf, S, D, taps, s));
+        SAT_TRY(sat_launch_gemm_f32(w.f32_col, W32(L.ff1), L.ff1.bias, H32, M, inner, taps * D, inner, 0, nullptr, 1, 0, s));
+        SAT_TRY(sat_launch_silu_f32(H32, (int64_t)M * inner, s));
+    } else if (!p->ff_glu) {      // Linear + SiLU
         SAT_TRY(sat_launch_gemm_f32(A32, W32(L.ff1), L.ff1.bias, H32, M, inner, D, inner, 0, nullptr, 1, 0, s));
         SAT_TRY(sat_launch_silu_f32(H32, (int64_t)M * inner, s));
     } else {
         SAT_TRY(sat_launch_gemm_f32(A32, W32(L.ff1), L.ff1.bias, w.f32_wide, M, 2 * inner, D, 2 * inner, 0, nullptr, 1, 0, s));
         SAT_TRY(sat_launch_swiglu_f32(w.f32_wide, H32, M, inner, s));
+    }
+    if (taps > 1) {
+        SAT_TRY(sat_launch_im2col_rows_f32(H32, w.f32_col, bf, S, inner, taps, s));
+        return sat_launch_gemm_f32(w.f32_col, W32(L.ff2), L.ff2.bias, w.X, M, D, taps * inner, D, 1, m ? m + 5 * D : nullptr, S, ssg_ld, s);
     }
     return sat_launch_gemm_f32(H32, W32(L.ff2), L.ff2.bias, w.X, M, D, inner, D, 1, m ? m + 5 * D : nullptr, S, ssg_ld, s);
 }
@@ -616,8 +682,40 @@ int Forward::conformer(int l) const {
     return resid(L.cpw2, w.AO, M, nullptr, true, l, -1);
 }
 
+// ---- feed-forward branch of a plan with sat_dit_plan_set_ff_conv (ff_kwargs use_conv, transformer.py:211-287): the standalone LayerNorm (or
+// the rounded row) into A; FF-in as the Linear SwiGLU GEMM under GLU, else the convolution GEMM with the SiLU epilogue; FF-out as the
+// convolution GEMM with the residual epilogue (bias, adaLN gate, += into the fp32 stream).  A -> Hh -> X, the dense buffers of the Linear plan:
+// ff_conv.hip tests the sequence boundary where it stages a row
+int Forward::feed_forward_conv(int l) const {
+    const LayerW& L = p->layers[l];
+    const float* m = mod(l);
+    SAT_TRY(layernorm(L.ff1, L.ff_g, L.ff_b, M, true, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr));
+    FfConvArgs a{};
+    a.fmt = L.ff2.f16 ? SAT_GEMM_FP16 : SAT_GEMM_BF16;
+    a.B = bf; a.S = S; a.taps = p->ff_conv;
+    const bool prof = profiled(l);
+    if (prof) SAT_TRY(prof_begin());
+    if (p->ff_glu) {
+        GemmArgs g = gemm(L.ff1, w.A, M);
+        g.H = w.Hh;
+        SAT_TRY(sat_launch_gemm(EPI_SWIGLU, g, s));
+        if (prof) SAT_TRY(prof_end(g.M, g.N, g.K));
+    } else {
+        a.A = w.A; a.W = L.ff1.w; a.bias = L.ff1.bias; a.N = L.ff1.n; a.K = L.ff1.k;
+        a.epi = FFC_ACT16; a.H = w.Hh; a.act = 1;
+        SAT_TRY(sat_launch_ff_conv(a, s));
+        if (prof) SAT_TRY(prof_end(M, a.N, (long long)a.taps * a.K));      // the contraction runs over taps * K
+    }
+    a.A = w.Hh; a.W = L.ff2.w; a.bias = L.ff2.bias; a.N = L.ff2.n; a.K = L.ff2.k;
+    a.epi = FFC_RESID; a.H = nullptr; a.act = 0; a.C = w.X; a.ldc = D; a.accumulate = 1;
+    if (m) { a.gate = m + 5 * D; a.gate_rows = S; a.gate_ld = ssg_ld; }
+    SAT_TRY(sat_launch_ff_conv(a, s));
+    return p->dbg ? glue_resid_stats(w.X, M, D, p->dbg + ((size_t)l * 3 + 2) * 4, s) : 0;
+}
+
 // ---- feed-forward branch (transformer.py:700)
 int Forward::feed_forward(int l) const {
+    if (p->ff_conv > 1) return feed_forward_conv(l);
     const LayerW& L = p->layers[l];
     const float* m = mod(l);
     SAT_TRY(layernorm(L.ff1, L.ff_g, L.ff_b, M, true, m ? m + 3 * D : nullptr, m ? m + 4 * D : nullptr));
@@ -625,24 +723,11 @@ int Forward::feed_forward(int l) const {
     GemmArgs g = gemm(L.ff1, w.A, M);
     g.H = w.Hh;
     if (L.ff2.kind == PROJ_FP8_MX) { g.H8 = (unsigned char*)w.Hh; g.Hs = w.Hs; }          // FF-out's MXFP8 operand; otherwise the e4m3 GEMM writes a 16-bit hidden state
-    const bool prof = p->prof_on && l == p->cfg.depth / 2 && p->prof_n < kProfMaxPairs;
-    if (prof) {
-        if ((int)p->prof_ev.size() < 2 * (p->prof_n + 1)) {
-            hipEvent_t e0, e1;
-            SAT_HIP(hipEventCreate(&e0));
-            SAT_HIP(hipEventCreate(&e1));
-            p->prof_ev.push_back(e0);
-            p->prof_ev.push_back(e1);
-        }
-        SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n], s));
-    }
+    const bool prof = profiled(l);
+    if (prof) SAT_TRY(prof_begin());
     if (!p->ff_glu) g.act = 1;      // ff_kwargs glu=False: H [M, inner] = silu(A W^T + bias)
     SAT_TRY(sat_launch_gemm(p->ff_glu ? EPI_SWIGLU : EPI_ACT16, g, s));
-    if (prof) {
-        SAT_HIP(hipEventRecord(p->prof_ev[2 * p->prof_n + 1], s));
-        p->prof_n++;
-        p->prof_m = g.M; p->prof_nn = g.N; p->prof_k = g.K;
-    }
+    if (prof) SAT_TRY(prof_end(g.M, g.N, g.K));
     SAT_TRY(range(l, RS_FF_HIDDEN, w.Hh, (size_t)M * p->inner, (size_t)M * p->inner));
     // nobody normalises the output of the last block, and a next block of another format normalises the fp32 rows itself (proj_kind)
     const bool feeds_ln = l + 1 < p->cfg.depth && layer_f16(p, l + 1) == layer_f16(p, l);
@@ -772,6 +857,7 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
     p->cross_fusion = cfg->cross_attention == 0;
     p->tile_bits = sat_tile_policy_bits(cfg->tile_policy);
     p->ln_fold = cfg->ln_fold != 0 && (cfg->gemm_dtype == 0 || cfg->gemm_dtype == 3) && !cfg->adaln && cfg->embed_dim >= 256 && hd == 64;
+    p->ln_fold_asked = p->ln_fold;
     *out_plan = p;
     return 0;
 }
@@ -800,8 +886,8 @@ extern "C" int sat_dit_plan_finalize(sat_dit_plan* p, sat_stream_t stream) {
     } else {      // ff_glu 0: the input Linear is [inner, D] and all of its columns are outputs of the GEMM (N % 128)
         const int64_t ff_numel = p->tensors.numel("transformer.layers.0.ff.ff.0.1.weight");
         SAT_CHECK_ARG(ff_numel > 0, SAT_E_MISSING, "dit plan: tensor 'transformer.layers.0.ff.ff.0.1.weight' was never set");
-        SAT_CHECK_ARG(ff_numel % (int64_t)D == 0, SAT_E_INVALID, "dit plan: FF weight size not divisible by embed_dim");
-        p->inner = (int)(ff_numel / (int64_t)D);
+        SAT_CHECK_ARG(ff_numel % ((int64_t)D * p->ff_conv) == 0, SAT_E_INVALID, "dit plan: FF weight size not divisible by embed_dim (x the kernel size %d)", p->ff_conv);
+        p->inner = (int)(ff_numel / ((int64_t)D * p->ff_conv));
         SAT_CHECK_ARG(p->inner % 128 == 0, SAT_E_UNSUPPORTED, "dit plan: FF inner dim %d of a feed-forward without GLU must be a multiple of 128", p->inner);
     }
     if (p->conformer) {      // by name and before anything is allocated, as the FF weight above
@@ -814,6 +900,15 @@ extern "C" int sat_dit_plan_finalize(sat_dit_plan* p, sat_stream_t stream) {
             }
     }
     SAT_CHECK_ARG(p->cfg.gemm_dtype != 1 || p->inner % 128 == 0, SAT_E_UNSUPPORTED, "dit plan: gemm_dtype needs an FF inner dim that is a multiple of 128");
+    if (p->ff_conv > 1) {      // by name and before anything is allocated; a Conv1d weight of another kernel size than the plan was told has another size
+        for (int l = 0; l < p->cfg.depth; ++l) {
+            const std::string name = "transformer.layers." + std::to_string(l) + ".ff.ff.2.weight";
+            SAT_CHECK_ARG(p->tensors.has(name), SAT_E_MISSING, "dit plan: tensor '%s' was never set", name.c_str());
+            SAT_CHECK_ARG(p->tensors.numel(name) == (int64_t)D * p->inner * p->ff_conv, SAT_E_INVALID,
+                          "dit plan: tensor '%s' has %lld elements, a Conv1d(%d, %d, %d) weight has %lld", name.c_str(), (long long)p->tensors.numel(name),
+                          p->inner, D, p->ff_conv, (long long)D * p->inner * p->ff_conv);
+        }
+    }
     p->wsq_bf = p->wsq_t = -1;
     return plan_finalize(p, s, [&](Bump& ar) { return build(p, ar, s); });
 }
@@ -1020,6 +1115,31 @@ extern "C" int sat_dit_plan_set_block_options(sat_dit_plan* p, const sat_dit_blo
     return 0;
 }
 
+extern "C" int sat_dit_plan_set_ff_conv(sat_dit_plan* p, const sat_dit_ff_conv_options* o, size_t options_bytes) {
+    SAT_CHECK_ARG(p && o, SAT_E_INVALID, "dit_plan_set_ff_conv: null argument");
+    SAT_CHECK_ARG(options_bytes == sizeof(sat_dit_ff_conv_options), SAT_E_INVALID,
+                  "dit_plan_set_ff_conv: sat_dit_ff_conv_options of %zu bytes; this library knows %zu", options_bytes, sizeof(sat_dit_ff_conv_options));
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_ff_conv: plan already finalized (call it between create and finalize)");
+    const int k = o->kernel_size;
+    SAT_CHECK_ARG(k >= 1, SAT_E_INVALID, "dit_plan_set_ff_conv: kernel_size %d", k);
+    // transformer.py:245,285: Conv1d(padding = k // 2) returns n + 1 rows for an even k and the reference's own residual add fails
+    SAT_CHECK_ARG(k % 2 == 1, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: kernel_size %d is even: the reference's convolution then returns one row more than it was given", k);
+    SAT_CHECK_ARG(k <= 7, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: kernel_size %d: the convolution GEMM is built for 1, 3, 5 and 7", k);
+    // the e4m3 operands carry one scale per row or per 32 k of a row, which a row-shifted read would have to shift as well; the staged
+    // 128-channel-head route keeps the shipped block, as for sat_dit_plan_set_block_options
+    SAT_CHECK_ARG(k == 1 || p->cfg.gemm_dtype != SAT_GEMM_FP8, SAT_E_UNSUPPORTED,
+                  "dit_plan_set_ff_conv: a convolutional feed-forward with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
+    SAT_CHECK_ARG(k == 1 || p->hd == 64, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: a convolutional feed-forward with dim_heads 128 is not built");
+    SAT_CHECK_ARG(k == 1 || (sat_launch_ff_conv && sat_launch_pack_conv_taps && sat_launch_im2col_rows_f32), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_ff_conv: built without the convolution GEMM");
+    SAT_CHECK_ARG(k == 1 || !p->rr, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: the range report has no rows for such a plan (sat_dit_range_report off first)");
+    p->ff_conv = k;
+    // FF-out's epilogue here writes no 16-bit image and no row statistics, and a convolutional FF-in could not use them (they differ per tap):
+    // every LayerNorm of such a plan is the standalone kernel
+    p->ln_fold = p->ln_fold_asked && k == 1;
+    return 0;
+}
+
 extern "C" int sat_dit_plan_set_block_formats(sat_dit_plan* p, const int32_t* formats, int32_t n) {
     SAT_CHECK_ARG(p && formats, SAT_E_INVALID, "dit_plan_set_block_formats: null argument");
     SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_block_formats: plan already finalized (call it between create and finalize)");
@@ -1160,6 +1280,7 @@ extern "C" int sat_dit_range_report(sat_dit_plan* p, int32_t enable) {
     SAT_CHECK_ARG(p->cfg.gemm_dtype == SAT_GEMM_BF16 || p->cfg.gemm_dtype == SAT_GEMM_FP16, SAT_E_UNSUPPORTED,
                   "dit_range_report: the report reads 16-bit operand buffers (gemm_dtype bf16 or fp16), this plan has gemm_dtype %d", p->cfg.gemm_dtype);
     SAT_CHECK_ARG(sat_launch_range_stats, SAT_E_UNSUPPORTED, "dit_range_report: built without the range statistics kernel");
+    SAT_CHECK_ARG(p->ff_conv == 1, SAT_E_UNSUPPORTED, "dit_range_report: no rows for a plan with a convolutional feed-forward (sat_dit_plan_set_ff_conv)");
     SAT_CHECK_ARG(!p->block_options(), SAT_E_UNSUPPORTED,
                   "dit_range_report: no rows for the 16-bit buffers of a plan with conformer / remove_norms / ff_glu 0 (sat_dit_plan_set_block_options)");
     const size_t bytes = (size_t)p->cfg.depth * SAT_DIT_RANGE_SLOTS * sizeof(sat_range_record);

@@ -386,6 +386,29 @@ int sat_launch_dwconv_ln_silu_variant(const void* x, const float* w, const float
 __attribute__((weak)) int sat_launch_round_rows(const float* x, void* y, int m, int d, const float* scale1p, const float* shift, int rows_per_seq,
                                                 int ld, int fmt, hipStream_t s);
 __attribute__((weak)) int sat_launch_silu_f32(float* h, int64_t n, hipStream_t s);      // fp32 verification mode: h = silu(h) in place (ff_kwargs glu=False)
+// ---- convolutional feed-forward (sat_dit_plan_set_ff_conv): ff_conv.hip.  WEAK as the launchers above: null in the host test driver, where
+// sat_dit_plan_set_ff_conv answers SAT_E_UNSUPPORTED to a kernel size above 1.  out[b, s, :] = sum_j W_j A[b, s + j - taps / 2, :] with zero
+// rows outside [0, S) of sequence b: one contraction of length taps * K, fp32 accumulation
+enum { FFC_RESID = 0, FFC_ACT16 = 1 };
+struct FfConvArgs {
+    int fmt;             // SAT_GEMM_BF16 / SAT_GEMM_FP16: the element type of A, W and H
+    const void* A;       // [B * S, K], dense rows
+    const void* W;       // [N, taps * K], tap-major (sat_launch_pack_conv_taps)
+    const float* bias;   // [N] or nullptr
+    int B, S, N, K, taps;
+    int epi;             // FFC_RESID: C [B * S, ldc] (+)= [gate (.)] (acc + bias), gate as GemmArgs::gate; FFC_ACT16: H [B * S, N] = act(acc + bias)
+    float* C;
+    int ldc, accumulate;
+    const float* gate;
+    int gate_rows, gate_ld;
+    void* H;
+    int act;             // 0 identity, 1 SiLU
+};
+__attribute__((weak)) int sat_launch_ff_conv(const FfConvArgs& a, hipStream_t s);
+// Conv1d weight w [n, k, taps] fp32 -> out [n, taps * k] of `fmt` (SAT_GEMM_BF16 / SAT_GEMM_FP16 / SAT_GEMM_FP32X), out[n][j * k + c] = w[n][c][j]
+__attribute__((weak)) int sat_launch_pack_conv_taps(const float* w, void* out, int n, int k, int taps, int fmt, hipStream_t s);
+// fp32 verification mode: out [b * s_len, taps * k], out[m][j * k + c] = a[m + j - taps / 2][c], zero outside the row's sequence
+__attribute__((weak)) int sat_launch_im2col_rows_f32(const float* a, float* out, int b, int s_len, int k, int taps, hipStream_t s);
 int sat_launch_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int sq, int sk, int sq_pad,
                                    int sk_pad, hipStream_t s);
 int sat_launch_head_split_hd128_f16(const float* x, const void* heads_epi, int b, hipStream_t s);

@@ -416,3 +416,39 @@ extern "C" int sat_gemm_act_f16(const void* a, const void* w, const float* bias,
                                 int32_t variant, sat_stream_t stream) {
     return gemm_act_impl(1, a, w, bias, h, m, n, k, act, variant, stream);
 }
+
+// ---- the convolution GEMM of sat_dit_plan_set_ff_conv alone: the plan's packing launch, then the launches of Forward::feed_forward_conv (16-bit)
+// or of Forward::block_f32 (row gather + sat_gemm_f32)
+static size_t ff_conv_pack_bytes(int32_t format, int32_t n, int32_t k, int32_t taps) {
+    return (size_t)round_up((int64_t)n * k * taps * (format == SAT_GEMM_FP32X ? 4 : 2), 256);
+}
+extern "C" int sat_ff_conv_workspace_bytes(int32_t format, int32_t b, int32_t s_len, int32_t n, int32_t k, int32_t kernel_size, size_t* out_bytes) {
+    SAT_CHECK_ARG(out_bytes && b > 0 && s_len > 0 && n > 0 && k > 0 && kernel_size > 0, SAT_E_INVALID, "ff_conv_workspace_bytes: bad argument");
+    SAT_CHECK_ARG(format == SAT_GEMM_BF16 || format == SAT_GEMM_FP16 || format == SAT_GEMM_FP32X, SAT_E_INVALID, "ff_conv_workspace_bytes: format %d", format);
+    *out_bytes = ff_conv_pack_bytes(format, n, k, kernel_size) + (format == SAT_GEMM_FP32X ? (size_t)b * s_len * kernel_size * k * 4 : 0);
+    return 0;
+}
+extern "C" int sat_ff_conv(int32_t format, const void* a, const float* w, const float* bias, int32_t epilogue, void* out, const float* gate, int32_t b,
+                           int32_t s_len, int32_t n, int32_t k, int32_t kernel_size, void* ws, size_t ws_bytes, sat_stream_t stream) {
+    SAT_CHECK_ARG(a && out && ws && b > 0 && s_len > 0 && (int64_t)b * s_len <= (1 << 30), SAT_E_INVALID, "ff_conv: bad argument");
+    SAT_CHECK_ARG(epilogue == FFC_RESID || (epilogue == FFC_ACT16 && !gate), SAT_E_INVALID, "ff_conv: epilogue %d (0 residual, 1 SiLU without a gate)", epilogue);
+    SAT_CHECK_ARG(kernel_size >= 1 && kernel_size <= 7 && (kernel_size & 1), SAT_E_UNSUPPORTED, "ff_conv: kernel size %d (odd, 1 to 7)", kernel_size);
+    SAT_CHECK_ARG(k > 0 && k % 64 == 0 && n > 0 && n % 128 == 0, SAT_E_UNSUPPORTED, "ff_conv: k = %d must be a multiple of 64 and n = %d of 128", k, n);
+    size_t need = 0;
+    SAT_TRY(sat_ff_conv_workspace_bytes(format, b, s_len, n, k, kernel_size, &need));
+    SAT_CHECK_ARG(ws_bytes >= need && ((uintptr_t)ws & 255) == 0, SAT_E_WORKSPACE, "ff_conv: workspace of %zu bytes (256-byte aligned), need %zu", ws_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    if (w) SAT_TRY(sat_launch_pack_conv_taps(w, ws, n, k, kernel_size, format, s));      // (null: the image an earlier call left in ws)
+    const int M = b * s_len;
+    if (format == SAT_GEMM_FP32X) {
+        float* col = (float*)((char*)ws + ff_conv_pack_bytes(format, n, k, kernel_size));
+        SAT_TRY(sat_launch_im2col_rows_f32((const float*)a, col, b, s_len, k, kernel_size, s));
+        SAT_TRY(sat_launch_gemm_f32(col, (const float*)ws, bias, (float*)out, M, n, kernel_size * k, n, epilogue == FFC_RESID, gate, s_len, n, s));
+        return epilogue == FFC_ACT16 ? sat_launch_silu_f32((float*)out, (int64_t)M * n, s) : 0;
+    }
+    FfConvArgs g{};
+    g.fmt = format; g.A = a; g.W = ws; g.bias = bias; g.B = b; g.S = s_len; g.N = n; g.K = k; g.taps = kernel_size; g.epi = epilogue;
+    if (epilogue == FFC_RESID) { g.C = (float*)out; g.ldc = n; g.accumulate = 1; g.gate = gate; g.gate_rows = s_len; g.gate_ld = n; }
+    else { g.H = out; g.act = 1; }
+    return sat_launch_ff_conv(g, s);
+}

@@ -65,11 +65,26 @@ def get_args():
     p.add_argument("--codec-final-tanh", action="store_true",
                    help="build extension: the VAE decoder was trained with final_tanh=True (write \"final_tanh\": false in the model config, "
                         "which the constructor requires, and pass this flag: set_final_tanh(True))")
+    p.add_argument("--allow-conv-ff", action="store_true",
+                   help="build extension: the model config's DiT has ff_kwargs use_conv (convolutional feed-forwards), which the constructor "
+                        "refuses without an opt-in: sets \"allow_conv_ff\": true in model.diffusion.config before the model is built "
+                        "(with --model-config or the built-in config; an error with --model-name)")
     p.add_argument("--check-fp16-range", action="store_true",
                    help="build extension, for a checkpoint this build was never run on: before generating, run the first batch once for 8 "
                         "steps with the activation range reports of the DiT and the codec on and print how close their 16-bit buffers come "
                         "to the fp16 limit (+-65504, where conversions saturate silently), with advice; changes no setting")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.allow_conv_ff and args.model_name:
+        p.error("--allow-conv-ff is written into the model config before the model is built: it goes with --model-config, not with "
+                "--model-name (a pretrained model is built from its own config)")
+    return args
+
+
+def apply_config_flags(args, model_config):
+    """The command-line flags that are written into the model config before the model is built."""
+    if args.allow_conv_ff:
+        model_config["model"]["diffusion"]["config"]["allow_conv_ff"] = True
+    return model_config
 
 
 def flatten_conditions(tree, parent="", sep="/"):
@@ -149,6 +164,7 @@ def main():
                     c["config"]["clap_ckpt_path"] = args.clap_ckpt
             keep = lambda c: c["type"] in ("number", "int") or (c["type"] == "clap_text" and args.clap_ckpt)
             model_config["model"]["conditioning"]["configs"] = [c for c in cc if keep(c)]
+        apply_config_flags(args, model_config)
         model = create_model_from_config(model_config)
         if args.ckpt_path:
             copy_state_dict(model, load_ckpt_state_dict(args.ckpt_path))

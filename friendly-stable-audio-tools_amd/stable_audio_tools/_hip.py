@@ -39,6 +39,10 @@ class SatDitBlockOptions(Structure):
     _fields_ = [("conformer", c_int32), ("remove_norms", c_int32), ("ff_glu", c_int32)]
 
 
+class SatDitFfConvOptions(Structure):
+    _fields_ = [("kernel_size", c_int32)]
+
+
 class SatT5Cfg(Structure):
     _fields_ = [("vocab_size", c_int32), ("d_model", c_int32), ("d_kv", c_int32), ("d_ff", c_int32), ("num_layers", c_int32),
                 ("num_heads", c_int32), ("rel_buckets", c_int32), ("rel_max_distance", c_int32), ("gated_gelu", c_int32),
@@ -101,6 +105,7 @@ _SIGNATURES = {
     "sat_dit_plan_set_transformer_options": (c_int32, [c_void_p, POINTER(SatDitTransformerOptions), c_size_t]),
     "sat_dit_plan_set_block_formats": (c_int32, [c_void_p, POINTER(c_int32), c_int32]),
     "sat_dit_plan_set_block_options": (c_int32, [c_void_p, POINTER(SatDitBlockOptions), c_size_t]),
+    "sat_dit_plan_set_ff_conv": (c_int32, [c_void_p, POINTER(SatDitFfConvOptions), c_size_t]),
     "sat_dit_prepare_extra_conditioning": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "sat_dit_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_dit_denoise_cfg": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int32, c_int32, c_void_p,
@@ -172,6 +177,9 @@ _SIGNATURES = {
                                            c_int32, c_int32, c_int32, c_void_p]),
     "sat_dwconv_ln_silu_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "sat_gemm_act_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    # the convolution GEMM of sat_dit_plan_set_ff_conv alone (tests/test_gpu_conv_ff_kernels.py)
+    "sat_ff_conv_workspace_bytes": (c_int32, [c_int32] * 6 + [POINTER(c_size_t)]),
+    "sat_ff_conv": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_size_t, c_void_p]),
     "sat_gemm_resid_ln_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                          c_void_p]),
     "sat_gemm_swiglu_ln_bf16": (c_int32, [c_void_p] * 9 + [c_int32, c_int32, c_int32, c_int32, c_void_p]),

@@ -29,6 +29,7 @@ class DiTWrapper(ConditionedDiffusionModel):
         super().__init__(supports_cross_attention=True, supports_global_cond=False, supports_input_concat=False)
         # config-driven construction: the TransformerBlock options off the shipped configs' path (conformer, remove_norms, glu=False) are accepted
         kwargs.setdefault("allow_block_options", True)
+        # ... ff_kwargs use_conv is not: a config opts in with "allow_conv_ff": true, which arrives here in kwargs and is passed on as it is
         self.model = DiffusionTransformer(*args, **kwargs)
         from . import _init
         if not _init._SKIP:

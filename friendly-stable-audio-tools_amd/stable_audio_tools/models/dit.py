@@ -30,9 +30,11 @@ class DiffusionTransformer(nn.Module):
                  project_cond_tokens: bool = True, global_cond_dim: int = 0, project_global_cond: bool = True,
                  input_concat_dim: int = 0, prepend_cond_dim: int = 0, depth: int = 12, num_heads: int = 8,
                  transformer_type: str = "x-transformers", global_cond_type: str = "prepend", max_seq_len: int = 8192,
-                 allow_block_options: bool = False, **kwargs):
+                 allow_block_options: bool = False, allow_conv_ff: bool = False, **kwargs):
         """``allow_block_options``: the TransformerBlock options ``conformer``, ``remove_norms`` and ``ff_kwargs={"glu": False}`` are off the
-        shipped configs' path and refused unless this is set; ``create_model_from_config`` and every other config-driven path set it."""
+        shipped configs' path and refused unless this is set; ``create_model_from_config`` and every other config-driven path set it.
+        ``allow_conv_ff``: likewise for ``ff_kwargs={"use_conv": True}`` (``sat_dit_plan_set_ff_conv``); no path sets it by default, a config
+        asks for it with ``"allow_conv_ff": true`` in ``model.diffusion.config``."""
         super().__init__()
         if transformer_type != "continuous_transformer":
             raise NotImplementedError("only transformer_type='continuous_transformer' is implemented (the shipped DiT configs)")
@@ -82,7 +84,7 @@ class DiffusionTransformer(nn.Module):
                                                  dim_in=dim_in, dim_out=io_channels, cross_attend=cond_token_dim > 0,
                                                  cond_token_dim=cond_embed_dim,
                                                  global_cond_dim=embed_dim if global_cond_type == "adaLN" else None,
-                                                 allow_block_options=allow_block_options, **kwargs)
+                                                 allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff, **kwargs)
         self.preprocess_conv = _init.conv1d(dim_in, dim_in, 1, bias=False, zero=True)
         self.postprocess_conv = _init.conv1d(io_channels, io_channels, 1, bias=False, zero=True)
 
@@ -110,6 +112,10 @@ class DiffusionTransformer(nn.Module):
                 0 if tr.rotary_pos_emb is None else 1)
 
     def _check_options(self, gemm_dtype):
+        if self.transformer.ff_conv_kernel > 1 and GEMM_DTYPES[gemm_dtype] == 1:
+            raise NotImplementedError(f"ff_kwargs use_conv with gemm_dtype={gemm_dtype!r}: the e4m3 operands carry one scale per row or per 32 "
+                                      "columns of a row, which the row-shifted reads of the convolution GEMM do not move; use gemm_dtype 'fp16', "
+                                      "'bf16' or 'fp32x'")
         if self.transformer.block_options != (0, 0, 1) and GEMM_DTYPES[gemm_dtype] == 1:
             raise NotImplementedError(f"conformer / remove_norms / glu=False with gemm_dtype={gemm_dtype!r}: the e4m3 epilogues and the quantising "
                                       "LayerNorm know neither a missing norm nor the plain SiLU; use gemm_dtype 'fp16', 'bf16' or 'fp32x'")
@@ -162,6 +168,9 @@ class DiffusionTransformer(nn.Module):
         bit-identical with the report on and off.  The setting survives a plan rebuild (``set_gemm_dtype`` ...), the records collected so far
         do not.  fp16 / bf16 plans only."""
         lib = _hip.lib()
+        if enable and self.transformer.ff_conv_kernel > 1:
+            raise NotImplementedError("activation_range_report on a model with a convolutional feed-forward (ff_kwargs use_conv): the report has "
+                                      "no rows for such a plan")
         if enable and self.transformer.block_options != (0, 0, 1):
             raise NotImplementedError("activation_range_report on a model with conformer / remove_norms / glu=False: the report has no rows for the "
                                       "16-bit buffers these options add (the conformer's three, the SiLU hidden state)")
@@ -294,7 +303,7 @@ class DiffusionTransformer(nn.Module):
 
     def _ensure_plan(self):
         ver = _init.params_version(self)
-        options = self.transformer_options() + self.transformer.block_options
+        options = self.transformer_options() + self.transformer.block_options + (self.transformer.ff_conv_kernel,)
         if self._plan is not None and ver == self._plan_version and options == self._plan_options:
             return self._plan
         self._check_options(self.gemm_dtype)
@@ -313,9 +322,12 @@ class DiffusionTransformer(nn.Module):
             if options[:4] != (0, _hip.DIT_POS_NONE, 0, 1):       # a model with none of these switches never makes the call
                 opts = _hip.SatDitTransformerOptions(*options[:4])
                 _hip.check(lib.sat_dit_plan_set_transformer_options(plan, ctypes.byref(opts), ctypes.sizeof(opts)))
-            if options[4:] != (0, 0, 1):       # conformer / remove_norms / glu=False; likewise
-                bopts = _hip.SatDitBlockOptions(*options[4:])
+            if options[4:7] != (0, 0, 1):       # conformer / remove_norms / glu=False; likewise
+                bopts = _hip.SatDitBlockOptions(*options[4:7])
                 _hip.check(lib.sat_dit_plan_set_block_options(plan, ctypes.byref(bopts), ctypes.sizeof(bopts)))
+            if options[7] > 1:       # ff_kwargs use_conv; likewise
+                copts = _hip.SatDitFfConvOptions(options[7])
+                _hip.check(lib.sat_dit_plan_set_ff_conv(plan, ctypes.byref(copts), ctypes.sizeof(copts)))
             if self._block_gemm_dtypes is not None:       # a model that never set them never makes the call
                 fm = (ctypes.c_int32 * self.depth)(*[GEMM_DTYPES[f] for f in self._block_gemm_dtypes])
                 _hip.check(lib.sat_dit_plan_set_block_formats(plan, fm, self.depth))

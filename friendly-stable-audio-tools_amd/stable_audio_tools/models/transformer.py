@@ -6,7 +6,7 @@ Mirror of the module tree of the reference's ``models/transformer.py`` (``LayerN
 ``ContinuousTransformer`` :705-809) restricted to the options the HIP plan runs: those of the shipped DiT
 configs plus 128-channel heads, ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False``,
 bias-free / ``mult``-sized feed-forwards and, behind the ``allow_block_options`` opt-in, ``conformer`` (:557-591), ``remove_norms``
-and feed-forwards without GLU.  These classes only *hold* parameters under the reference's
+and feed-forwards without GLU, and behind ``allow_conv_ff`` convolutional feed-forwards (``ff_kwargs use_conv``).  These classes only *hold* parameters under the reference's
 names; the forward pass of the whole stack is one C-ABI call (``sat_dit_forward`` /
 ``sat_dit_denoise_cfg``) issued by ``models/dit.py``.  Unsupported options raise.
 """
@@ -66,12 +66,24 @@ BLOCK_OPTIONS_HINT = ("pass allow_block_options=True to DiffusionTransformer (cr
                       "the option then runs on the HIP plan (sat_dit_plan_set_block_options)")
 
 
+CONV_FF_HINT = ("pass allow_conv_ff=True to DiffusionTransformer, or write \"allow_conv_ff\": true into the model config's model.diffusion.config "
+                "(generate.py --allow-conv-ff does): the convolutions then run on the HIP plan (sat_dit_plan_set_ff_conv)")
+
+
 class FeedForward(nn.Module):
-    def __init__(self, dim, mult=4, glu=True, no_bias=False, use_conv=False, zero_init_output=True, allow_block_options=False, **unsupported):
+    def __init__(self, dim, mult=4, glu=True, no_bias=False, use_conv=False, conv_kernel_size=3, zero_init_output=True, allow_block_options=False,
+                 allow_conv_ff=False, **unsupported):
         super().__init__()
-        if use_conv or unsupported:
-            raise NotImplementedError("FeedForward options not supported by the HIP path, with or without allow_block_options (use_conv needs GEMM "
-                                      f"operands shifted by a row per tap, which no kernel here has yet): use_conv={use_conv} {sorted(unsupported)}")
+        if unsupported or (use_conv and not allow_conv_ff):
+            raise NotImplementedError("FeedForward options not supported by the HIP path, with or without allow_block_options (use_conv is behind "
+                                      f"an opt-in of its own: {CONV_FF_HINT}): use_conv={use_conv} {sorted(unsupported)}")
+        if use_conv:
+            if conv_kernel_size < 1 or conv_kernel_size % 2 == 0:
+                # reference :245,285: Conv1d(padding=k // 2) returns n + 1 rows for an even k and the block's residual add does not fit
+                raise ValueError(f"FeedForward conv_kernel_size={conv_kernel_size}: the reference's own forward fails for an even kernel size "
+                                 "(its convolution returns one row more than it was given)")
+            if conv_kernel_size > 7:
+                raise NotImplementedError(f"FeedForward conv_kernel_size={conv_kernel_size}: the HIP convolution GEMM is built for kernel sizes 1, 3, 5 and 7")
         if not glu and not allow_block_options:
             raise NotImplementedError(f"FeedForward glu={glu} (use_conv={use_conv}) is off the shipped configs' path: {BLOCK_OPTIONS_HINT}")
         inner_dim = int(dim * mult)
@@ -81,10 +93,18 @@ class FeedForward(nn.Module):
             raise NotImplementedError(f"FeedForward mult={mult} with glu=False: every column of the input Linear is an output of the GEMM, whose N "
                                       f"must be a multiple of 128, got inner dim {inner_dim}")
         self.no_bias, self.glu = no_bias, bool(glu)
+        self.conv_kernel_size = conv_kernel_size if use_conv else 1      # 1: Linears (a use_conv model with kernel size 1 keeps Conv1d-shaped weights)
+        self.use_conv = bool(use_conv)
         # reference :222,270: GLU builds its own nn.Linear and keeps the bias; no_bias only drops the one of the output projection.
         # Without GLU (:262-268) the input Linear follows no_bias as well
-        linear_out = _init.linear(inner_dim, dim, bias=not no_bias, zero=zero_init_output)
-        linear_in = GLU(dim, inner_dim) if glu else nn.Sequential(nn.Identity(), _init.linear(dim, inner_dim, bias=not no_bias), nn.Identity(), nn.SiLU())
+        # use_conv (:222,262-287): both become Conv1d(k, padding=k // 2) along the sequence under the same keys; GLU is built without use_conv
+        # and keeps its Linear
+        if use_conv:
+            proj = lambda i, o, zero=False: _init.conv1d(i, o, conv_kernel_size, bias=not no_bias, padding=conv_kernel_size // 2, zero=zero)
+        else:
+            proj = lambda i, o, zero=False: _init.linear(i, o, bias=not no_bias, zero=zero)
+        linear_out = proj(inner_dim, dim, zero=zero_init_output)
+        linear_in = GLU(dim, inner_dim) if glu else nn.Sequential(nn.Identity(), proj(dim, inner_dim), nn.Identity(), nn.SiLU())
         self.ff = nn.Sequential(linear_in, nn.Identity(), linear_out, nn.Identity())
 
 
@@ -129,13 +149,16 @@ class ConformerModule(nn.Module):
 class TransformerBlock(nn.Module):
     def __init__(self, dim, dim_heads=64, cross_attend=False, dim_context=None, global_cond_dim=None, causal=False,
                  zero_init_branch_outputs=True, conformer=False, layer_ix=-1, remove_norms=False, attn_kwargs={}, ff_kwargs={},
-                 norm_kwargs={}, allow_block_options=False):
+                 norm_kwargs={}, allow_block_options=False, allow_conv_ff=False):
         super().__init__()
         if (conformer or remove_norms) and not allow_block_options:
             raise NotImplementedError(f"conformer={conformer} / remove_norms={remove_norms} are off the shipped configs' path: {BLOCK_OPTIONS_HINT}")
         if dim_heads != 64 and (conformer or remove_norms or not ff_kwargs.get("glu", True)):
             raise NotImplementedError(f"conformer / remove_norms / glu=False with dim_heads={dim_heads}: the staged 128-channel-head route keeps the "
                                       "shipped block (standalone LayerNorms, SwiGLU feed-forward); these options run with dim_heads=64")
+        if dim_heads != 64 and ff_kwargs.get("use_conv", False) and allow_conv_ff:
+            raise NotImplementedError(f"ff_kwargs use_conv with dim_heads={dim_heads}: the staged 128-channel-head route keeps the shipped block; "
+                                      "a convolutional feed-forward runs with dim_heads=64")
         self.dim, self.dim_heads, self.cross_attend, self.dim_context = dim, dim_heads, cross_attend, dim_context
         self.layer_ix = layer_ix
         self.remove_norms = bool(remove_norms)
@@ -147,7 +170,8 @@ class TransformerBlock(nn.Module):
             self.cross_attn = Attention(dim, dim_heads=dim_heads, dim_context=dim_context, causal=causal,
                                         zero_init_output=zero_init_branch_outputs, **attn_kwargs)
         self.ff_norm = norm()
-        self.ff = FeedForward(dim, zero_init_output=zero_init_branch_outputs, allow_block_options=allow_block_options, **ff_kwargs)
+        self.ff = FeedForward(dim, zero_init_output=zero_init_branch_outputs, allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff,
+                              **ff_kwargs)
         self.conformer = ConformerModule(dim, norm_kwargs=norm_kwargs) if conformer else None      # its two norms stay under remove_norms
         self.global_cond_dim = global_cond_dim
         if global_cond_dim:
@@ -185,6 +209,8 @@ class ContinuousTransformer(nn.Module):
         # likewise one conformer / remove_norms / glu for every block (sat_dit_plan_set_block_options)
         self.block_options = (1 if conformer else 0, 1 if kwargs.get("remove_norms", False) else 0,
                               1 if kwargs.get("ff_kwargs", {}).get("glu", True) else 0)
+        # and one conv_kernel_size (sat_dit_plan_set_ff_conv); 1 = Linear feed-forwards
+        self.ff_conv_kernel = self.layers[0].ff.conv_kernel_size
         assert all(a.qk_norm == self.qk_norm for l in self.layers for a in (l.self_attn, getattr(l, "cross_attn", l.self_attn)))
 
     def forward(self, *args, **kwargs):

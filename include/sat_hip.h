@@ -214,13 +214,35 @@ int sat_dit_plan_set_transformer_options(sat_dit_plan* plan, const sat_dit_trans
  * options_bytes = sizeof(sat_dit_block_options) of the caller's header; any other size is SAT_E_INVALID, a value outside 0 / 1
  * SAT_E_UNSUPPORTED, a call after finalize SAT_E_STATE.  SAT_E_UNSUPPORTED as well: any of the three options (conformer 1, remove_norms 1,
  * ff_glu 0) on a plan with gemm_dtype SAT_GEMM_FP8 or with 128-channel heads, and sat_dit_range_report on a plan with one of them.
- * A feed-forward built on a convolution (ff_kwargs use_conv) has no form in this ABI. */
+ * A feed-forward built on a convolution (ff_kwargs use_conv) is a call of its own, sat_dit_plan_set_ff_conv below: this struct's size is
+ * checked and does not grow. */
 typedef struct sat_dit_block_options {
     int32_t conformer;      /* "conformer" */
     int32_t remove_norms;   /* "remove_norms" */
     int32_t ff_glu;         /* ff_kwargs "glu" (1 in every shipped config) */
 } sat_dit_block_options;
 int sat_dit_plan_set_block_options(sat_dit_plan* plan, const sat_dit_block_options* options, size_t options_bytes);
+
+/* Convolutional feed-forward (ff_kwargs use_conv, models/transformer.py:211-287), between create and finalize; a plan never given this call
+ * has kernel_size 1 (Linear) and builds and launches exactly what it did before this call existed.  With kernel_size k = 3, 5 or 7 the
+ * output projection of every block's feed-forward is Conv1d(inner, D, k, padding = k / 2) along the sequence [prepend rows | global token |
+ * frames]: tensors "transformer.layers.N.ff.ff.2.weight" [D, inner, k] and optionally ".ff.ff.2.bias" [D].  With ff_glu 0
+ * (sat_dit_plan_set_block_options) the input projection is Conv1d(D, inner, k) + SiLU as well, "….ff.ff.0.1.weight" [inner, D, k] and
+ * optionally ".0.1.bias" [inner]; under GLU it stays the Linear SwiGLU (the reference's GLU builds its own nn.Linear).  The window is
+ * zero-padded by k / 2 at both ends of each sequence and never reaches into the neighbouring batch item.  Finalize packs each weight
+ * tap-major into one [N, k * K] operand in the block's format (fp32 in the verification mode) and names a missing tensor with SAT_E_MISSING.
+ * A convolution runs as one contraction of length k * K over k row-shifted reads of its dense A operand (16-bit MFMA, fp32 accumulation)
+ * with the epilogue of the Linear it replaces: bias, adaLN gate and the add into the fp32 stream for FF-out, bias + SiLU and a 16-bit
+ * output for FF-in.  The LayerNorm fold is off in such a plan (ln_fold is accepted without effect, as for adaLN).  The workspace grows in
+ * the fp32 verification mode only, by the row gather in front of its GEMM.
+ * options_bytes = sizeof(sat_dit_ff_conv_options) of the caller's header; any other size is SAT_E_INVALID, as is kernel_size < 1; a call
+ * after finalize is SAT_E_STATE.  SAT_E_UNSUPPORTED: an even kernel_size (the reference's convolution then returns one row too many and its
+ * own residual add fails), one above 7, and a kernel_size above 1 on a plan with gemm_dtype SAT_GEMM_FP8, with 128-channel heads or with
+ * the range report on; sat_dit_range_report on such a plan likewise. */
+typedef struct sat_dit_ff_conv_options {
+    int32_t kernel_size;    /* ff_kwargs "conv_kernel_size" under "use_conv"; 1 = Linear */
+} sat_dit_ff_conv_options;
+int sat_dit_plan_set_ff_conv(sat_dit_plan* plan, const sat_dit_ff_conv_options* options, size_t options_bytes);
 
 /* Operand format per block, between create and finalize: formats[l] is SAT_GEMM_FP16 or SAT_GEMM_BF16 for block l, n == depth.  A plan never
  * given this call, or given gemm_dtype in every entry, runs every block in gemm_dtype and builds and launches exactly what it did before this
@@ -288,7 +310,9 @@ int sat_dit_denoise_cfg(sat_dit_plan* plan, const float* x_dev, float sigma, flo
 /* Measurement hook for bench.py: while enabled, every forward brackets the FFN-in (SwiGLU) GEMM
  * launch of ONE transformer layer (depth/2) with a hipEvent pair on the launch stream (at most
  * 4096 pairs; enabling resets the count).  sat_dit_profile_read synchronises on the recorded
- * events and returns the summed elapsed time, the number of launches and the GEMM shape. */
+ * events and returns the summed elapsed time, the number of launches and the GEMM shape.  On a
+ * plan with sat_dit_plan_set_ff_conv and glu=False the launch is the convolution GEMM and k is
+ * kernel_size * embed_dim, the length of its contraction. */
 int sat_dit_profile(sat_dit_plan* plan, int32_t enable);
 int sat_dit_profile_read(sat_dit_plan* plan, double* total_ms, int32_t* launches, int64_t* m, int64_t* n, int64_t* k);
 
@@ -697,6 +721,21 @@ int sat_gemm_act_bf16(const void* a_bf16_dev, const void* w_bf16_dev, const floa
                       int32_t k, int32_t act, int32_t variant, sat_stream_t stream);
 int sat_gemm_act_f16(const void* a_f16_dev, const void* w_f16_dev, const float* bias_dev, void* h_f16_dev, int32_t m, int32_t n,
                      int32_t k, int32_t act, int32_t variant, sat_stream_t stream);
+
+/* The convolution GEMM of sat_dit_plan_set_ff_conv alone, for the parity tests, through the plan's own packing and launches:
+ *   acc[b, s, :] = sum_j w[:, :, j] . a[b, s + j - kernel_size / 2, :], rows outside [0, s_len) of sequence b zero.
+ * format SAT_GEMM_BF16 / SAT_GEMM_FP16: a [b * s_len, k] in that format; SAT_GEMM_FP32X: a fp32 (row gather + sat_gemm_f32).  w [n, k,
+ * kernel_size] (the Conv1d weight) and bias [n] or NULL are fp32.  epilogue 0, FF-out: out fp32 [b * s_len, n] += [gate[b] (.)] (acc + bias),
+ * out holding the residual rows on entry; gate [b, n] fp32 or NULL.  epilogue 1, FF-in: out [b * s_len, n] = silu(acc + bias) in `format`
+ * (fp32 under SAT_GEMM_FP32X); gate must be NULL.  ws of sat_ff_conv_workspace_bytes, 256-byte aligned: it starts with the tap-major weight
+ * image [n, kernel_size * k] in `format`, which the call writes; every byte the kernels read of it the call has written.  w NULL: the
+ * call packs nothing and runs on the image that an earlier call with the same format, n, k and kernel_size left in ws (the plan packs once,
+ * at finalize: this times the convolution GEMM as the plan launches it).  k a multiple of 64, n of 128, kernel_size 1, 3, 5 or 7.  Returns
+ * without synchronising, as every entry here. */
+int sat_ff_conv_workspace_bytes(int32_t format, int32_t b, int32_t s_len, int32_t n, int32_t k, int32_t kernel_size, size_t* out_bytes);
+int sat_ff_conv(int32_t format, const void* a_dev, const float* w_dev, const float* bias_dev, int32_t epilogue, void* out_dev,
+                const float* gate_dev, int32_t b, int32_t s_len, int32_t n, int32_t k, int32_t kernel_size, void* ws, size_t ws_bytes,
+                sat_stream_t stream);
 int sat_gemm_resid_ln_f16(const void* a_f16_dev, const void* w_f16_dev, const float* bias_dev, float* c_dev, void* xb_dev,
                           float* ln_part_dev, int32_t m, int32_t n, int32_t k, int32_t variant, sat_stream_t stream);
 int sat_gemm_swiglu_ln_f16(const void* xb_dev, const float* ln_part_dev, const float* w_f32_dev, const float* gamma_dev,
