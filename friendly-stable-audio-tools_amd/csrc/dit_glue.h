@@ -18,6 +18,16 @@ int glue_input_proj_extra(const float* x, const float* Weff, float* X, int Bf, i
 int glue_pos_table(int mode, const float* src, float* table, int rows, int D, hipStream_t s);
 int glue_add_pos(float* X, const float* table, int Bf, int S, int D, hipStream_t s);
 int glue_output_proj(const float* X, const float* Weff, float* out, int Bf, int C, int T, int S, int D, hipStream_t s);
+// ---- patchified DiT (sat_dit_plan_set_patch, patch_size P > 1): dit_patch.hip.  WEAK as the optional launchers of sat_common.h: null in the
+// host test driver, where sat_dit_plan_set_patch answers SAT_E_UNSUPPORTED to a patch size above 1.  T stays in latent frames (a multiple
+// of P), S counts token rows: prepend rows + (1 global token) + T / P.  Weights [D, Ci P] / [C P, D] with feature index c * P + p; the folds
+// write [Ci P][D] and [D][C P].  The input projection is one entry: Cc = 0 and Pl = 0 is the plain model.
+__attribute__((weak)) int glue_fold_in_patch(const float* Win, const float* Wpre, float* Weff, int D, int Ci, int P, hipStream_t s);
+__attribute__((weak)) int glue_fold_out_patch(const float* Wout, const float* Wpost, float* Weff, int D, int C, int P, hipStream_t s);
+__attribute__((weak)) int glue_input_proj_patch(const float* x, const float* Weff, float* X, int Bf, int xB, int C, int P, int T, int S, int D,
+                                                float xscale, const float* concat, int Cc, int Tc, const float* prep, int Pl, hipStream_t s);
+__attribute__((weak)) int glue_output_proj_patch(const float* X, const float* Weff, float* out, int Bf, int C, int P, int T, int S, int D,
+                                                 hipStream_t s);
 int glue_cfg_denoise(const float* mo, const float* x, float* den, int B, int C, int T, int use_cfg, float cfg_scale,
                      float scale_phi, float c_out, float c_skip, hipStream_t s);
 // diagnostics of the residual stream (sat_dit_debug): per launch 4 floats at `out`, combined with atomics over the M rows:

@@ -85,6 +85,10 @@ struct sat_dit_plan {
     // ff_kwargs use_conv (sat_dit_plan_set_ff_conv): kernel size of the feed-forward's convolutions, 1 = Linear and nothing changes
     int ff_conv = 1;
     bool ln_fold_asked = false;     // what sat_dit_plan_create made of cfg.ln_fold; ln_fold is this and ff_conv == 1
+    // patch_size (sat_dit_plan_set_patch): latent frames per token, 1 = a token per frame and nothing changes.  t_len stays in frames at the
+    // ABI; rows, workspace, position tables count tokens (tokens()), and the two boundary launches are those of dit_patch.hip
+    int patch = 1;
+    int tokens(int t_len) const { return t_len / patch; }
     // per-generation context (sat_dit_prepare_context)
     DevBuf ctx_buf;
     int ctx_bf = 0, ctx_lc = 0, ctx_lcpad = 0;
@@ -254,9 +258,10 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, 16 * 4, s));
     }
     const int Ci = C + p->concat_dim;       // preprocess_conv / project_in see cat([x, input_concat_cond]) (dit.py:38,130,173)
-    p->win_eff = (float*)ar.take((size_t)D * Ci * 4);
-    p->wout_eff = (float*)ar.take((size_t)D * C * 4);
-    const int smax = seq_len(p, c.max_seq_len, p->max_prep);
+    const int pt = p->patch;                // project_in [D, Ci pt], project_out [C pt, D]; the two 1x1 convs stay per frame (dit.py:88-89,119-120)
+    p->win_eff = (float*)ar.take((size_t)D * Ci * pt * 4);
+    p->wout_eff = (float*)ar.take((size_t)D * C * pt * 4);
+    const int smax = seq_len(p, p->tokens(c.max_seq_len), p->max_prep);
     if (!hd128) {
         p->rope_cos = (float*)ar.take((size_t)smax * 16 * 4);
         p->rope_sin = (float*)ar.take((size_t)smax * 16 * 4);
@@ -266,12 +271,17 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
     p->pos_table = p->pos_emb != SAT_DIT_POS_NONE ? (float*)ar.take((size_t)p->pos_rows * D * 4) : nullptr;
     if (!ar.dry()) {
         const float *win, *wpre, *wout, *wpost;
-        SAT_TRY(get_tensor(p, "transformer.project_in.weight", (int64_t)D * Ci, &win));
+        SAT_TRY(get_tensor(p, "transformer.project_in.weight", (int64_t)D * Ci * pt, &win));
         SAT_TRY(get_tensor(p, "preprocess_conv.weight", (int64_t)Ci * Ci, &wpre));
-        SAT_TRY(get_tensor(p, "transformer.project_out.weight", (int64_t)D * C, &wout));
+        SAT_TRY(get_tensor(p, "transformer.project_out.weight", (int64_t)D * C * pt, &wout));
         SAT_TRY(get_tensor(p, "postprocess_conv.weight", (int64_t)C * C, &wpost));
-        SAT_TRY(glue_fold_in(win, wpre, p->win_eff, D, Ci, s));
-        SAT_TRY(glue_fold_out(wout, wpost, p->wout_eff, D, C, s));
+        if (pt > 1) {
+            SAT_TRY(glue_fold_in_patch(win, wpre, p->win_eff, D, Ci, pt, s));
+            SAT_TRY(glue_fold_out_patch(wout, wpost, p->wout_eff, D, C, pt, s));
+        } else {
+            SAT_TRY(glue_fold_in(win, wpre, p->win_eff, D, Ci, s));
+            SAT_TRY(glue_fold_out(wout, wpost, p->wout_eff, D, C, s));
+        }
         if (!hd128) SAT_TRY(sat_launch_rope_table(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
         if (p->pos_emb == SAT_DIT_POS_SINUSOIDAL) {     // inv_freq is not in the state dict (persistent=False), the learnt scale is
             const float* sc;
@@ -372,7 +382,7 @@ struct Workspace {
 Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     const sat_dit_cfg& c = p->cfg;
     const int D = c.embed_dim, H = c.num_heads;
-    const int S = seq_len(p, T, P);
+    const int S = seq_len(p, p->tokens(T), P);      // T: latent frames (w.mo below is [bf, io_channels, T]); rows are tokens
     const size_t M = (size_t)bf * S;
     const int Spad = (int)round_up(S + 3, 128);
     const int hid = p->conformer && D > p->inner ? D : p->inner;      // Hh: the FF hidden state [M, inner]; the conformer's GLU output [M, D] as well
@@ -740,6 +750,7 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     const sat_dit_cfg& c = p->cfg;
     SAT_CHECK_ARG(x && out && ws && bf > 0 && T > 0, SAT_E_INVALID, "dit forward: bad arguments");
     SAT_CHECK_ARG(T <= c.max_seq_len, SAT_E_INVALID, "dit forward: t_len %d exceeds plan max_seq_len %d", T, c.max_seq_len);
+    SAT_CHECK_ARG(T % p->patch == 0, SAT_E_INVALID, "dit forward: t_len %d is not a multiple of patch_size %d", T, p->patch);
     SAT_CHECK_ARG(((uintptr_t)ws & 255) == 0, SAT_E_INVALID, "dit forward: workspace must be 256-byte aligned");
     const bool cross = c.cond_token_dim > 0;
     SAT_CHECK_ARG(p->ctx_bf == bf, SAT_E_STATE, "dit forward: context prepared for %d sequences, forward called with %d",
@@ -751,7 +762,7 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     SAT_CHECK_ARG(ws_bytes >= w.total, SAT_E_WORKSPACE, "dit forward: workspace %zu < required %zu", ws_bytes, w.total);
     const int D = c.embed_dim, H = c.num_heads, C = c.io_channels;
     const bool adaln = c.adaln != 0, f32 = c.gemm_dtype == 2;
-    const int S = seq_len(p, T, P), M = bf * S, Spad = (int)round_up(S + 3, 128);
+    const int S = seq_len(p, p->tokens(T), P), M = bf * S, Spad = (int)round_up(S + 3, 128);
     const int ssg_ld = c.depth * 6 * D;      // per-sequence stride of the adaLN modulation vectors
     // transformer.py:59-61, before anything is launched
     SAT_CHECK_ARG(p->pos_emb != SAT_DIT_POS_ABSOLUTE || S <= p->abs_max, SAT_E_INVALID,
@@ -775,7 +786,10 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     }
     // preprocess_conv + residual + project_in (dit.py:197-199, transformer.py:778); with extra conditioning the same launch adds the
     // concat channels (dit.py:167-173, unscaled by c_in) and copies the prepared prepend rows X[b, 0..P-1, :]
-    if (p->ext_ready)
+    if (p->patch > 1)      // "b (t p) c -> b t (c p)" in front of project_in: one launch for the plain model and the extra conditioning
+        SAT_TRY(glue_input_proj_patch(x, p->win_eff, w.X, bf, xB, C, p->patch, T, S, D, xscale, p->ext_ready ? p->ext_concat : nullptr,
+                                      p->ext_ready ? p->concat_dim : 0, p->ext_concat_len, p->ext_ready ? p->ext_prep : nullptr, p->ext_ready ? P : 0, s));
+    else if (p->ext_ready)
         SAT_TRY(glue_input_proj_extra(x, p->win_eff, w.X, bf, xB, C, T, S, D, xscale, p->ext_concat, p->concat_dim, p->ext_concat_len,
                                       p->ext_prep, P, s));
     else
@@ -789,7 +803,8 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     const Forward f{p, w, s, bf, S, M, Spad, D, H, bc, bc * S, ssg_ld};
     for (int l = 0; l < c.depth; ++l) SAT_TRY(f32 ? f.block_f32(l) : f.block(l));
     // project_out + drop prepend + postprocess_conv + residual (transformer.py:807, dit.py:219-224)
-    SAT_TRY(glue_output_proj(w.X, p->wout_eff, out, bf, C, T, S, D, s));
+    if (p->patch > 1) SAT_TRY(glue_output_proj_patch(w.X, p->wout_eff, out, bf, C, p->patch, T, S, D, s));      // + "b (c p) t -> b c (t p)"
+    else SAT_TRY(glue_output_proj(w.X, p->wout_eff, out, bf, C, T, S, D, s));
     return 0;
 }
 
@@ -916,6 +931,7 @@ extern "C" int sat_dit_plan_finalize(sat_dit_plan* p, sat_stream_t stream) {
 extern "C" int sat_dit_workspace_bytes(const sat_dit_plan* p, int32_t bf, int32_t t_len, size_t* out_bytes) {
     SAT_CHECK_ARG(p && out_bytes && bf > 0 && t_len > 0, SAT_E_INVALID, "dit_workspace_bytes: bad argument");
     SAT_CHECK_ARG(p->finalized, SAT_E_STATE, "dit_workspace_bytes: plan not finalized");
+    SAT_CHECK_ARG(t_len % p->patch == 0, SAT_E_INVALID, "dit_workspace_bytes: t_len %d is not a multiple of patch_size %d", t_len, p->patch);
     // enough for any prepend length up to max_prepend_len (the layout is not monotonic in P: the FF-out K-split slab depends on M).
     // Host arithmetic only, once per (bf, t_len): the hot calls check carve() of the prepared P instead.
     if (p->max_prep == 0) {
@@ -1062,6 +1078,9 @@ extern "C" int sat_dit_plan_set_extra_conditioning(sat_dit_plan* p, int32_t inpu
                   prepend_cond_dim);
     SAT_CHECK_ARG(p->cfg.io_channels + input_concat_dim <= 256, SAT_E_UNSUPPORTED,
                   "dit_plan_set_extra_conditioning: io_channels + input_concat_dim = %d exceeds 256", p->cfg.io_channels + input_concat_dim);
+    SAT_CHECK_ARG(p->patch == 1 || (int64_t)(p->cfg.io_channels + input_concat_dim) * p->patch <= 1024, SAT_E_UNSUPPORTED,
+                  "dit_plan_set_extra_conditioning: (io_channels + input_concat_dim) * patch_size = %lld exceeds 1024",
+                  (long long)(p->cfg.io_channels + input_concat_dim) * p->patch);
     SAT_CHECK_ARG((int64_t)p->cfg.max_seq_len + 1 + max_prepend_len <= (1 << 20), SAT_E_INVALID,
                   "dit_plan_set_extra_conditioning: max_prepend_len %d too large", max_prepend_len);
     p->concat_dim = input_concat_dim;
@@ -1112,6 +1131,25 @@ extern "C" int sat_dit_plan_set_block_options(sat_dit_plan* p, const sat_dit_blo
     p->conformer = o->conformer != 0;
     p->remove_norms = o->remove_norms != 0;
     p->ff_glu = o->ff_glu != 0;
+    return 0;
+}
+
+extern "C" int sat_dit_plan_set_patch(sat_dit_plan* p, const sat_dit_patch_options* o, size_t options_bytes) {
+    SAT_CHECK_ARG(p && o, SAT_E_INVALID, "dit_plan_set_patch: null argument");
+    SAT_CHECK_ARG(options_bytes == sizeof(sat_dit_patch_options), SAT_E_INVALID,
+                  "dit_plan_set_patch: sat_dit_patch_options of %zu bytes; this library knows %zu", options_bytes, sizeof(sat_dit_patch_options));
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_patch: plan already finalized (call it between create and finalize)");
+    const int pt = o->patch_size;
+    SAT_CHECK_ARG(pt >= 1, SAT_E_INVALID, "dit_plan_set_patch: patch_size %d", pt);
+    // the limits of the two boundary kernels (dit_patch.hip checks the same at launch); io_channels and the concat width: create / set_extra_conditioning
+    const int64_t C = p->cfg.io_channels, Ci = C + p->concat_dim;
+    SAT_CHECK_ARG(pt == 1 || C * pt <= 512, SAT_E_UNSUPPORTED, "dit_plan_set_patch: io_channels * patch_size = %lld exceeds 512", (long long)(C * pt));
+    SAT_CHECK_ARG(pt == 1 || Ci * pt <= 1024, SAT_E_UNSUPPORTED,
+                  "dit_plan_set_patch: (io_channels + input_concat_dim) * patch_size = %lld exceeds 1024", (long long)(Ci * pt));
+    SAT_CHECK_ARG(pt == 1 || p->cfg.max_seq_len >= pt, SAT_E_INVALID, "dit_plan_set_patch: patch_size %d exceeds max_seq_len %d", pt, p->cfg.max_seq_len);
+    SAT_CHECK_ARG(pt == 1 || (glue_fold_in_patch && glue_fold_out_patch && glue_input_proj_patch && glue_output_proj_patch), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_patch: built without the patch kernels");
+    p->patch = pt;
     return 0;
 }
 
@@ -1201,6 +1239,7 @@ extern "C" int sat_dit_denoise_cfg(sat_dit_plan* p, const float* x_dev, float si
                                    float* denoised_dev, int32_t b, int32_t t_len, void* ws, size_t ws_bytes, sat_stream_t stream) {
     SAT_CHECK_ARG(p && p->finalized, SAT_E_STATE, "dit_denoise_cfg: plan not finalized");
     SAT_CHECK_ARG(x_dev && denoised_dev && b > 0 && t_len > 0 && ws, SAT_E_INVALID, "dit_denoise_cfg: bad arguments");
+    SAT_CHECK_ARG(t_len % p->patch == 0, SAT_E_INVALID, "dit_denoise_cfg: t_len %d is not a multiple of patch_size %d", t_len, p->patch);
     hipStream_t s = (hipStream_t)stream;
     // models/dit.py:270: CFG only when cfg_scale != 1 and there is cross-attention or prepend conditioning
     const int use_cfg = (cfg_scale != 1.0f && (p->cfg.cond_token_dim > 0 || p->ctx_prep > 0)) ? 1 : 0;

@@ -1,6 +1,7 @@
 // Unit-level C entry points (include/sat_hip.h): one kernel launcher each, for tests, probes and callers that drive single
 // operations; the bf16 / fp16 pairs share an _impl.  Host code only; no kernel, nothing of the DiT plan.
 #include "sat_common.h"
+#include "dit_glue.h"
 
 // ------------------------------------------------------------------------------ unit-level entry points
 static int layernorm_bf16_impl(int f16, const float* x, const float* gamma, const float* beta, void* y, int32_t m, int32_t d,
@@ -451,4 +452,22 @@ extern "C" int sat_ff_conv(int32_t format, const void* a, const float* w, const 
     if (epilogue == FFC_RESID) { g.C = (float*)out; g.ldc = n; g.accumulate = 1; g.gate = gate; g.gate_rows = s_len; g.gate_ld = n; }
     else { g.H = out; g.act = 1; }
     return sat_launch_ff_conv(g, s);
+}
+
+// ---- the two boundary kernels of sat_dit_plan_set_patch alone (dit_patch.hip): the launchers Forward's run_forward calls, on folded weights
+// of sat_fold_in_patch / sat_fold_out_patch, which are the launches of the plan's finalize
+extern "C" int sat_fold_in_patch(const float* w_in, const float* w_pre, float* w_eff_t, int32_t d, int32_t ci, int32_t patch_size, sat_stream_t stream) {
+    return glue_fold_in_patch(w_in, w_pre, w_eff_t, d, ci, patch_size, (hipStream_t)stream);
+}
+extern "C" int sat_fold_out_patch(const float* w_out, const float* w_post, float* w_eff_t, int32_t d, int32_t c, int32_t patch_size, sat_stream_t stream) {
+    return glue_fold_out_patch(w_out, w_post, w_eff_t, d, c, patch_size, (hipStream_t)stream);
+}
+extern "C" int sat_input_proj_patch(const float* x, const float* w_eff_t, float* X, int32_t bf, int32_t xb, int32_t c, int32_t patch_size, int32_t t,
+                                    int32_t s_len, int32_t d, float xscale, const float* concat, int32_t cc, int32_t tc, const float* prep, int32_t p,
+                                    sat_stream_t stream) {
+    return glue_input_proj_patch(x, w_eff_t, X, bf, xb, c, patch_size, t, s_len, d, xscale, concat, cc, tc, prep, p, (hipStream_t)stream);
+}
+extern "C" int sat_output_proj_patch(const float* X, const float* w_eff_t, float* out, int32_t bf, int32_t c, int32_t patch_size, int32_t t, int32_t s_len,
+                                     int32_t d, sat_stream_t stream) {
+    return glue_output_proj_patch(X, w_eff_t, out, bf, c, patch_size, t, s_len, d, (hipStream_t)stream);
 }

@@ -69,6 +69,10 @@ def get_args():
                    help="build extension: the model config's DiT has ff_kwargs use_conv (convolutional feed-forwards), which the constructor "
                         "refuses without an opt-in: sets \"allow_conv_ff\": true in model.diffusion.config before the model is built "
                         "(with --model-config or the built-in config; an error with --model-name)")
+    p.add_argument("--allow-patch-size", action="store_true",
+                   help="build extension: the model config's DiT has patch_size > 1 (a token is patch_size latent frames), which the constructor "
+                        "refuses without an opt-in: sets \"allow_patch_size\": true in model.diffusion.config before the model is built "
+                        "(with --model-config or the built-in config; an error with --model-name)")
     p.add_argument("--check-fp16-range", action="store_true",
                    help="build extension, for a checkpoint this build was never run on: before generating, run the first batch once for 8 "
                         "steps with the activation range reports of the DiT and the codec on and print how close their 16-bit buffers come "
@@ -77,6 +81,9 @@ def get_args():
     if args.allow_conv_ff and args.model_name:
         p.error("--allow-conv-ff is written into the model config before the model is built: it goes with --model-config, not with "
                 "--model-name (a pretrained model is built from its own config)")
+    if args.allow_patch_size and args.model_name:
+        p.error("--allow-patch-size is written into the model config before the model is built: it goes with --model-config, not with "
+                "--model-name (a pretrained model is built from its own config)")
     return args
 
 
@@ -84,6 +91,8 @@ def apply_config_flags(args, model_config):
     """The command-line flags that are written into the model config before the model is built."""
     if args.allow_conv_ff:
         model_config["model"]["diffusion"]["config"]["allow_conv_ff"] = True
+    if args.allow_patch_size:
+        model_config["model"]["diffusion"]["config"]["allow_patch_size"] = True
     return model_config
 
 

@@ -43,6 +43,10 @@ class SatDitFfConvOptions(Structure):
     _fields_ = [("kernel_size", c_int32)]
 
 
+class SatDitPatchOptions(Structure):
+    _fields_ = [("patch_size", c_int32)]
+
+
 class SatT5Cfg(Structure):
     _fields_ = [("vocab_size", c_int32), ("d_model", c_int32), ("d_kv", c_int32), ("d_ff", c_int32), ("num_layers", c_int32),
                 ("num_heads", c_int32), ("rel_buckets", c_int32), ("rel_max_distance", c_int32), ("gated_gelu", c_int32),
@@ -106,6 +110,7 @@ _SIGNATURES = {
     "sat_dit_plan_set_block_formats": (c_int32, [c_void_p, POINTER(c_int32), c_int32]),
     "sat_dit_plan_set_block_options": (c_int32, [c_void_p, POINTER(SatDitBlockOptions), c_size_t]),
     "sat_dit_plan_set_ff_conv": (c_int32, [c_void_p, POINTER(SatDitFfConvOptions), c_size_t]),
+    "sat_dit_plan_set_patch": (c_int32, [c_void_p, POINTER(SatDitPatchOptions), c_size_t]),
     "sat_dit_prepare_extra_conditioning": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "sat_dit_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_dit_denoise_cfg": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int32, c_int32, c_void_p,
@@ -177,6 +182,11 @@ _SIGNATURES = {
                                            c_int32, c_int32, c_int32, c_void_p]),
     "sat_dwconv_ln_silu_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "sat_gemm_act_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    # the boundary kernels of sat_dit_plan_set_patch alone, with their weight folds (tests/test_gpu_dit_patch_kernels.py)
+    "sat_fold_in_patch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "sat_fold_out_patch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "sat_input_proj_patch": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_float, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "sat_output_proj_patch": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p]),
     # the convolution GEMM of sat_dit_plan_set_ff_conv alone (tests/test_gpu_conv_ff_kernels.py)
     "sat_ff_conv_workspace_bytes": (c_int32, [c_int32] * 6 + [POINTER(c_size_t)]),
     "sat_ff_conv": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_size_t, c_void_p]),

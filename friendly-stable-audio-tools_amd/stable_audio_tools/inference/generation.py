@@ -47,6 +47,11 @@ def generate_diffusion_cond(model, steps: int = 250, cfg_scale: float = 6, condi
     as the reference's generation.py:95-261: audio ``[B, channels, sample_size]`` (or latents with ``return_latents``).
     ``noise=`` (build extension) overrides the initial draw, for parity tests.  Pinned against the reference's own runs by
     tests/test_reference_generate.py."""
+    # a patchified DiT (patch_size > 1) takes whole patches of latent frames: refused here, before the conditioners run and anything is sampled
+    patch = getattr(getattr(model.model, "model", None), "patch_size", 1)
+    frames = sample_size // (model.pretransform.downsampling_ratio if model.pretransform else 1)
+    if frames % patch != 0:
+        raise ValueError(f"latent length T = {frames} (sample_size {sample_size}) is not a multiple of patch_size = {patch}")
     if model.conditioner is not None:
         model.conditioner.set_device(device)
     assert conditioning or conditioning_tensors, "Must provide either conditioning or conditioning_tensors"

@@ -19,6 +19,11 @@ from .blocks import FourierFeatures
 from .transformer import ContinuousTransformer
 
 
+PATCH_SIZE_HINT = ("pass allow_patch_size=True to DiffusionTransformer, or write \"allow_patch_size\": true into the model config's "
+                   "model.diffusion.config (generate.py --allow-patch-size does): the patchified model then runs on the HIP plan "
+                   "(sat_dit_plan_set_patch)")
+
+
 GEMM_DTYPES = {"bf16": 0, "fp8": 1, "fp8-all": 1, "fp32x": 2, "fp16": 3}      # sat_dit_cfg.gemm_dtype (include/sat_hip.h)
 # sat_dit_cfg.fp8_families (SAT_FP8_*): "fp8" = cross to_q + FF-in + FF-out in e4m3 (the subset whose quantisation the 12-step trajectory
 # tolerates: tools/fp8_budget.py), "fp8-all" = every GEMM of the blocks (round 3's mode: to_qkv and the to_out projections as well)
@@ -30,18 +35,27 @@ class DiffusionTransformer(nn.Module):
                  project_cond_tokens: bool = True, global_cond_dim: int = 0, project_global_cond: bool = True,
                  input_concat_dim: int = 0, prepend_cond_dim: int = 0, depth: int = 12, num_heads: int = 8,
                  transformer_type: str = "x-transformers", global_cond_type: str = "prepend", max_seq_len: int = 8192,
-                 allow_block_options: bool = False, allow_conv_ff: bool = False, **kwargs):
+                 allow_block_options: bool = False, allow_conv_ff: bool = False, allow_patch_size: bool = False, **kwargs):
         """``allow_block_options``: the TransformerBlock options ``conformer``, ``remove_norms`` and ``ff_kwargs={"glu": False}`` are off the
         shipped configs' path and refused unless this is set; ``create_model_from_config`` and every other config-driven path set it.
         ``allow_conv_ff``: likewise for ``ff_kwargs={"use_conv": True}`` (``sat_dit_plan_set_ff_conv``); no path sets it by default, a config
-        asks for it with ``"allow_conv_ff": true`` in ``model.diffusion.config``."""
+        asks for it with ``"allow_conv_ff": true`` in ``model.diffusion.config``.
+        ``allow_patch_size``: likewise for ``patch_size`` above 1 (``sat_dit_plan_set_patch``): a token is then ``patch_size`` consecutive
+        latent frames, ``x`` and the output keep their ``[B, io_channels, T]`` layout and ``T`` must be a multiple of ``patch_size``; a config
+        asks for it with ``"allow_patch_size": true``."""
         super().__init__()
         if transformer_type != "continuous_transformer":
             raise NotImplementedError("only transformer_type='continuous_transformer' is implemented (the shipped DiT configs)")
         if global_cond_type not in ("prepend", "adaLN"):
             raise ValueError(f"Unknown global_cond_type: {global_cond_type}")
-        if patch_size != 1:
-            raise NotImplementedError("patch_size>1 is outside the supported hot path")
+        if patch_size < 1:
+            raise ValueError(f"patch_size must be >= 1, got {patch_size}")
+        if patch_size != 1 and not allow_patch_size:
+            raise NotImplementedError(f"patch_size={patch_size} (patch_size>1) is behind an opt-in: {PATCH_SIZE_HINT}")
+        if patch_size != 1 and (io_channels * patch_size > 512 or (io_channels + input_concat_dim) * patch_size > 1024):
+            raise NotImplementedError(f"patch_size={patch_size} with io_channels {io_channels} and input_concat_dim {input_concat_dim}: the two "
+                                      "boundary kernels are built for io_channels * patch_size <= 512 and (io_channels + input_concat_dim) * "
+                                      "patch_size <= 1024")
         if prepend_cond_dim > 0 and global_cond_type == "adaLN":
             # the reference sets prepend_length only in the "prepend" branch (dit.py:158,185-195) and so returns P + T frames (:219)
             raise NotImplementedError("prepend_cond_dim with global_cond_type='adaLN' has no working reference behaviour (reference dit.py:158,"
@@ -80,8 +94,9 @@ class DiffusionTransformer(nn.Module):
             self.to_prepend_embed = nn.Sequential(_init.linear(prepend_cond_dim, embed_dim, bias=False), nn.SiLU(),
                                                   _init.linear(embed_dim, embed_dim, bias=False))
         dim_in = io_channels + input_concat_dim      # dit.py:38: the input projection sees cat([x, input_concat_cond])
+        # dit.py:119-120: the transformer sees tokens of patch_size frames, "b (t p) c -> b t (c p)"; the two 1x1 convs below stay per frame
         self.transformer = ContinuousTransformer(dim=embed_dim, depth=depth, dim_heads=embed_dim // num_heads,
-                                                 dim_in=dim_in, dim_out=io_channels, cross_attend=cond_token_dim > 0,
+                                                 dim_in=dim_in * patch_size, dim_out=io_channels * patch_size, cross_attend=cond_token_dim > 0,
                                                  cond_token_dim=cond_embed_dim,
                                                  global_cond_dim=embed_dim if global_cond_type == "adaLN" else None,
                                                  allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff, **kwargs)
@@ -127,11 +142,16 @@ class DiffusionTransformer(nn.Module):
                                       "128-channel-head route (fp32 projection, head split, attention) is built for 'fp16' and 'bf16' operands; the "
                                       "e4m3 attention outputs and the fp32 verification kernels keep 64-channel heads")
 
+    def _check_t_len(self, t_len):
+        """``T`` must hold whole patches: the reference fails inside its rearrange (dit.py:198); here before anything is launched."""
+        if t_len % self.patch_size != 0:
+            raise ValueError(f"latent length T = {t_len} is not a multiple of patch_size = {self.patch_size}")
+
     def _check_seq_len(self, t_len, prepend_len):
         """The reference's ``AbsolutePositionalEmbedding`` assertion (transformer.py:59-61), on the host before anything is launched."""
         pe = self.transformer.pos_emb
         if self.transformer.use_abs_pos_emb and not self.transformer.use_sinusoidal_emb:
-            seq_len = prepend_len + t_len + (0 if self.global_cond_type == "adaLN" else 1)
+            seq_len = prepend_len + t_len // self.patch_size + (0 if self.global_cond_type == "adaLN" else 1)
             assert seq_len <= pe.max_seq_len, \
                 f"you are passing in a sequence length of {seq_len} but your absolute positional embedding has a max sequence length of {pe.max_seq_len}"
 
@@ -303,7 +323,7 @@ class DiffusionTransformer(nn.Module):
 
     def _ensure_plan(self):
         ver = _init.params_version(self)
-        options = self.transformer_options() + self.transformer.block_options + (self.transformer.ff_conv_kernel,)
+        options = self.transformer_options() + self.transformer.block_options + (self.transformer.ff_conv_kernel, self.patch_size)
         if self._plan is not None and ver == self._plan_version and options == self._plan_options:
             return self._plan
         self._check_options(self.gemm_dtype)
@@ -328,6 +348,9 @@ class DiffusionTransformer(nn.Module):
             if options[7] > 1:       # ff_kwargs use_conv; likewise
                 copts = _hip.SatDitFfConvOptions(options[7])
                 _hip.check(lib.sat_dit_plan_set_ff_conv(plan, ctypes.byref(copts), ctypes.sizeof(copts)))
+            if options[8] > 1:       # patch_size; likewise
+                popts = _hip.SatDitPatchOptions(options[8])
+                _hip.check(lib.sat_dit_plan_set_patch(plan, ctypes.byref(popts), ctypes.sizeof(popts)))
             if self._block_gemm_dtypes is not None:       # a model that never set them never makes the call
                 fm = (ctypes.c_int32 * self.depth)(*[GEMM_DTYPES[f] for f in self._block_gemm_dtypes])
                 _hip.check(lib.sat_dit_plan_set_block_formats(plan, fm, self.depth))
@@ -417,6 +440,7 @@ class DiffusionTransformer(nn.Module):
     @torch.no_grad()
     def _forward(self, x, t, cross_attn_cond=None, global_embed=None, null_from=-1, input_concat_cond=None, prepend_cond=None, **ignored):
         """dit.py:135-226 on the given batch (no CFG logic)."""
+        self._check_t_len(x.shape[2])
         self._reserve_prepend(prepend_cond)
         self._ensure_plan()
         x = x.detach().float().contiguous()
@@ -442,6 +466,7 @@ class DiffusionTransformer(nn.Module):
         assert not causal, "Causal mode is not supported for DiffusionTransformer"
         if return_info:
             raise NotImplementedError("return_info is outside the supported hot path")
+        self._check_t_len(x.shape[2])
         # masks are discarded exactly as the reference does at inference (dit.py:250-252); prepend_cond_mask never reaches
         # the layers there either (transformer.py:787-802)
         if cfg_scale != 1.0 and (cross_attn_cond is not None or prepend_cond is not None):
@@ -504,6 +529,7 @@ class DiffusionTransformer(nn.Module):
     def denoise(self, x, sigma: float, cfg_scale: float = 1.0, scale_phi: float = 0.0, out=None):
         """k-diffusion VDenoiser(DiT with batched CFG)(x, sigma) -- ``sat_dit_denoise_cfg``."""
         b, _, t_len = x.shape
+        self._check_t_len(t_len)
         self._check_seq_len(t_len, self._gen_prepend_len)
         use_cfg = cfg_scale != 1.0 and (self.cond_token_dim > 0 or self._gen_prepend)
         ws = self._workspace(2 * b if use_cfg else b, t_len)

@@ -54,7 +54,8 @@ const char* sat_last_error(void);
  * models/transformer.py:99-809 (ContinuousTransformer, TransformerBlock, Attention,
  * FeedForward, LayerNorm, RotaryEmbedding), models/diffusion.py:482-529 (DiTWrapper).
  * Supported set: transformer_type "continuous_transformer", global_cond_type "prepend"
- * or "adaLN", dim_heads 64, patch_size 1, non-causal, no masks (the reference discards
+ * or "adaLN", dim_heads 64 or 128, patch_size 1 or, through sat_dit_plan_set_patch, above,
+ * non-causal, no masks (the reference discards
  * them at inference: models/dit.py:250-252; prepend_cond_mask never reaches the layers,
  * models/transformer.py:787-802).  Input-concat and prepend conditioning (dit.py:160-197)
  * through sat_dit_plan_set_extra_conditioning / sat_dit_prepare_extra_conditioning; prepend
@@ -243,6 +244,26 @@ typedef struct sat_dit_ff_conv_options {
     int32_t kernel_size;    /* ff_kwargs "conv_kernel_size" under "use_conv"; 1 = Linear */
 } sat_dit_ff_conv_options;
 int sat_dit_plan_set_ff_conv(sat_dit_plan* plan, const sat_dit_ff_conv_options* options, size_t options_bytes);
+
+/* Patchified DiT (DiffusionTransformer patch_size, models/dit.py:38,88-89,119-120,197-224), between create and finalize; a plan never
+ * given this call, or given patch_size 1, has a token per latent frame and builds and launches exactly what it did before this call existed.
+ * With patch_size P >= 2 a token is P consecutive frames: "transformer.project_in.weight" is [D, (io_channels + input_concat_dim) * P] and
+ * "transformer.project_out.weight" [io_channels * P, D], feature index c * P + p (channel-major, frame-minor: the reference's
+ * "b (t p) c -> b t (c p)" and "b (c p) t -> b c (t p)"); "preprocess_conv.weight" and "postprocess_conv.weight" keep their per-frame
+ * shapes and finalize folds them into the two projections inside each p.  Input-concat conditioning is resized to t_len FRAMES (nearest
+ * source frame per frame, as at P = 1) before the patchify.  t_len stays in latent frames in sat_dit_workspace_bytes, sat_dit_forward,
+ * sat_dit_denoise_cfg and against max_seq_len, and x / out keep their [bf, io_channels, t_len] layout; the sequence the blocks see is
+ * [prepend rows | global token | t_len / P tokens], and the workspace, the rotary and position tables and abs_pos_max_len count those
+ * rows.  A t_len that is not a multiple of P is SAT_E_INVALID in those three calls, before anything is launched (the reference fails
+ * inside its rearrange).  Everything between the two projections is the P = 1 plan on fewer rows, in every gemm_dtype.
+ * options_bytes = sizeof(sat_dit_patch_options) of the caller's header; any other size is SAT_E_INVALID, as is patch_size < 1 or one
+ * above max_seq_len; a call after finalize is SAT_E_STATE.  SAT_E_UNSUPPORTED (the widths the two boundary kernels are built for, beside
+ * io_channels <= 64, a multiple of 4, and io_channels + input_concat_dim <= 256 at P = 1): io_channels * P > 512, and
+ * (io_channels + input_concat_dim) * P > 1024, checked by whichever of this call and sat_dit_plan_set_extra_conditioning comes second. */
+typedef struct sat_dit_patch_options {
+    int32_t patch_size;     /* "patch_size"; 1 = a token per frame */
+} sat_dit_patch_options;
+int sat_dit_plan_set_patch(sat_dit_plan* plan, const sat_dit_patch_options* options, size_t options_bytes);
 
 /* Operand format per block, between create and finalize: formats[l] is SAT_GEMM_FP16 or SAT_GEMM_BF16 for block l, n == depth.  A plan never
  * given this call, or given gemm_dtype in every entry, runs every block in gemm_dtype and builds and launches exactly what it did before this
@@ -920,6 +941,22 @@ int sat_input_proj_extra(const float* x_dev, const float* w_eff_t_dev, float* X_
 /* out [bf, c, t]: out[b, :, i] = w_eff_t^T X[b, (s_len - t) + i, :] for w_eff_t [d, c]; c % 4 == 0, c <= 64, d % 128 == 0, d <= 2048 */
 int sat_output_proj(const float* X_dev, const float* w_eff_t_dev, float* out_dev, int32_t bf, int32_t c, int32_t t, int32_t s_len, int32_t d,
                     sat_stream_t stream);
+/* The same four for a plan with sat_dit_plan_set_patch, patch_size P >= 2 (t a multiple of P, else SAT_E_INVALID; c * P <= 512 and
+ * (c + cc) * P <= 1024, else SAT_E_UNSUPPORTED).  Folds: W_in [d, ci * P] -> w_eff_t [ci * P, d], W_out [c * P, d] -> w_eff_t [d, c * P],
+ * feature index channel * P + p, W_pre [ci, ci] / W_post [c, c] applied inside each p.  sat_input_proj_patch: X [bf, s_len, d],
+ * X[b, (s_len - t / P) + i, :] = xscale * sum_{ch, p} w_eff_t[ch * P + p] x[b % xb, ch, i * P + p] + the cc concat channels (rows
+ * (c + j) * P + p of w_eff_t) read at the nearest-neighbour source frame of frame i * P + p, unscaled, and X[b, j, :] = prep[b, j, :]
+ * for j < p; cc = 0 with concat NULL and p = 0 with prep NULL is the plain model.  sat_output_proj_patch: out [bf, c, t],
+ * out[b, ch, i * P + p] = w_eff_t[:, ch * P + p]^T X[b, (s_len - t / P) + i, :]. */
+int sat_fold_in_patch(const float* w_in_dev, const float* w_pre_dev, float* w_eff_t_dev, int32_t d, int32_t ci, int32_t patch_size,
+                      sat_stream_t stream);
+int sat_fold_out_patch(const float* w_out_dev, const float* w_post_dev, float* w_eff_t_dev, int32_t d, int32_t c, int32_t patch_size,
+                       sat_stream_t stream);
+int sat_input_proj_patch(const float* x_dev, const float* w_eff_t_dev, float* X_dev, int32_t bf, int32_t xb, int32_t c, int32_t patch_size,
+                         int32_t t, int32_t s_len, int32_t d, float xscale, const float* concat_dev, int32_t cc, int32_t tc,
+                         const float* prep_dev, int32_t p, sat_stream_t stream);
+int sat_output_proj_patch(const float* X_dev, const float* w_eff_t_dev, float* out_dev, int32_t bf, int32_t c, int32_t patch_size, int32_t t,
+                          int32_t s_len, int32_t d, sat_stream_t stream);
 /* table [rows, d]: mode 1 cat(sin, cos)(pos * 10000^(-j / (d / 2))) * src[0]; mode 2 src[pos][:] * d^-0.5 (src [>= rows, d]).
  * X [bf, s_len, d] += table[s] (the caller's table, [>= s_len, d]); d % 4 == 0. */
 int sat_pos_table(int32_t mode, const float* src_dev, float* table_dev, int32_t rows, int32_t d, sat_stream_t stream);
