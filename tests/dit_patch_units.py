@@ -4,7 +4,7 @@ through its unit entry and compares with ``reference(case)`` in float64 under th
 (n + 4) 2^-24 |W| |x| with n the contraction length, 1e-5 per row and 32 x 32 block); the host test (test_dit_patch_host.py) proves these
 references against plain fp32 PyTorch -- reshape / permute, 1x1 conv, Linear -- and shows that the gates reject the faults of ``FAULTS``.
 
-``patchify`` / ``unpatchify`` restate the reference's two rearranges (models/dit.py:207,222); tests/golden/make_golden_dit_patch.py checks them
+``patchify`` / ``unpatchify`` restate the reference's two rearranges (models/dit.py:207,222); tests/golden/make_golden_dit_families.py checks them
 against einops on the golden cases' shapes."""
 import torch
 import torch.nn.functional as F

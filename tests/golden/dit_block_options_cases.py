@@ -1,13 +1,12 @@
 """The TransformerBlock options of the reduced DiT -- conformer, remove_norms, ff_kwargs glu=False (reference models/transformer.py:557-591,
-621-645, 259-268) -- that tests/golden/make_golden_dit_block_options.py (reference side) and tests/test_dit_block_options_host.py /
-tests/test_gpu_dit_block_options.py (product side) share: configs, forward cases, inputs and the gains on the synthetic weights.  Weights
-and inputs come from (seed, name) through ``stable_audio_tools.synthetic``."""
-import torch
-
+621-645, 259-268) -- that tests/golden/make_golden_dit_families.py (reference side) and tests/test_dit_block_options_host.py /
+tests/test_gpu_dit_block_options.py (product side) share: configs, forward cases and the gains on the synthetic weights.  Weights
+and inputs come from (seed, name) through ``stable_audio_tools.synthetic`` (dit_family.py)."""
 import cases
+import dit_family
 from stable_audio_tools import synthetic
 
-PREPEND_DIM = 48
+PREPEND_DIM = dit_family.PREPEND_DIM
 CONF, NONORM, SILU = dict(conformer=True), dict(remove_norms=True), dict(ff_kwargs={"glu": False})
 ADALN = dict(global_cond_type="adaLN")
 # name -> the reference's DiffusionTransformer kwargs (the product's take allow_block_options=True on top: PRODUCT_KWARGS)
@@ -25,7 +24,7 @@ CONFIGS = {
     "silu_mult2": dict(cases.SMALL_DIT, ff_kwargs={"glu": False, "mult": 2}),
 }
 PRODUCT_KWARGS = dict(allow_block_options=True)
-# what make_golden_dit_block_options.py compares every case with: the same model without the option(s).  ff_kwargs loses its "glu" only
+# what the generator compares every case with: the same model without the option(s).  ff_kwargs loses its "glu" only
 OPTION_KEYS = ("conformer", "remove_norms")
 
 
@@ -44,12 +43,7 @@ GAINS = {"conformer.pointwise_conv_2.weight": 4.0}
 
 
 def synth_weights(template_sd, seed=0):
-    sd = synthetic.synth_state_dict(template_sd, seed)
-    for k in sd:
-        for suffix, gain in GAINS.items():
-            if k.endswith(suffix):
-                sd[k] = sd[k] * gain
-    return sd
+    return dit_family.scaled(synthetic.synth_state_dict(template_sd, seed), dit_family.suffix_gain(GAINS))
 
 
 # forward cases: name -> (config, t_len, prepend length P or None, cfg_scale).  Batch 2, 130 context tokens.  T = 77 on a "prepend" model
@@ -62,10 +56,7 @@ for _c in CONFIGS:
     CASES[f"{_c}_cfg7_T77"] = (_c, 77, _p, 7.0)
 
 
-def case_inputs(name):
-    """(x, t, cross_attn_cond, global_embed, prepend_cond or None, prepend_cond_mask or None)"""
-    _, t_len, p, _ = CASES[name]
-    x, t, c, g = cases.dit_inputs(2, t_len, 128, 96, 1)
-    pc = synthetic.synth_input("prepend", (2, p, PREPEND_DIM), 300 + p) if p else None
-    pm = torch.ones(2, p) if p else None           # (the reference concatenates it, dit.py:193; it never reaches the layers)
-    return x, t, c, g, pc, pm
+FAMILY = dit_family.Family(
+    title="dit block options", stem="dit_block_options_small", keys_file="dit_block_options_state_dict_keys.json", configs=CONFIGS, cases=CASES,
+    product_kwargs=PRODUCT_KWARGS, weights=lambda cfg_name, template_sd, seed=0: synth_weights(template_sd, seed), r16=True,
+    baseline=lambda cfg_name: ("the model without the option", without_options(CONFIGS[cfg_name]), None))

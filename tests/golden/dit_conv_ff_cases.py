@@ -1,13 +1,14 @@
 """The convolutional feed-forward of the reduced DiT -- ff_kwargs use_conv (reference models/transformer.py:211-287) -- that
-tests/golden/make_golden_dit_conv_ff.py (reference side) and tests/test_dit_conv_ff_host.py / tests/test_gpu_dit_conv_ff.py (product side)
-share: configs, forward cases, inputs and the gain on the synthetic weights.  Weights and inputs come from (seed, name) through
-``stable_audio_tools.synthetic``."""
+tests/golden/make_golden_dit_families.py (reference side) and tests/test_dit_conv_ff_host.py / tests/test_gpu_dit_conv_ff.py (product side)
+share: configs, forward cases and the gain on the synthetic weights.  Weights and inputs come from (seed, name) through
+``stable_audio_tools.synthetic`` (dit_family.py)."""
 import torch
 
 import cases
+import dit_family
 from stable_audio_tools import synthetic
 
-PREPEND_DIM = 48
+PREPEND_DIM = dit_family.PREPEND_DIM
 ADALN = dict(global_cond_type="adaLN")
 CONV = {"use_conv": True}
 # name -> the reference's DiffusionTransformer kwargs (the product's take both opt-ins on top: PRODUCT_KWARGS)
@@ -40,22 +41,19 @@ def is_ff_conv_weight(key, tensor):
 
 
 def synth_weights(template_sd, seed=0):
-    sd = synthetic.synth_state_dict(template_sd, seed)
-    for k in sd:
-        for suffix, gain in GAINS.items():
-            if k.endswith(suffix):
-                sd[k] = sd[k] * gain
-        if k.endswith(".ff.ff.2.weight") and sd[k].dim() == 3 and k[:-len("2.weight")] + "0.proj.weight" in sd:     # glu: FF-in is the Linear SwiGLU
-            centre = sd[k].shape[2] // 2
-            g = torch.full((sd[k].shape[2],), OFF_CENTRE_GAIN)
-            g[centre] = 1.0
-            sd[k] = sd[k] * g
-    return sd
+    sd = dit_family.scaled(synthetic.synth_state_dict(template_sd, seed), dit_family.suffix_gain(GAINS))
+
+    def off_centre(k, v):
+        if k.endswith(".ff.ff.2.weight") and v.dim() == 3 and k[:-len("2.weight")] + "0.proj.weight" in sd:     # glu: FF-in is the Linear SwiGLU
+            g = torch.full((v.shape[2],), OFF_CENTRE_GAIN)
+            g[v.shape[2] // 2] = 1.0
+            return g
+    return dit_family.scaled(sd, off_centre)
 
 
 def centre_taps_only(sd):
     """The same weights with every off-centre tap of every feed-forward convolution set to zero: what a kernel computes that reads only the
-    row itself.  Every case must differ from this model by MIN_EFFECT (make_golden_dit_conv_ff.py)."""
+    row itself.  Every case must differ from this model by FAMILY.min_effect (make_golden_dit_families.py)."""
     out = dict(sd)
     for k, v in sd.items():
         if is_ff_conv_weight(k, v):
@@ -75,10 +73,8 @@ for _c in CONFIGS:
     CASES[f"{_c}_cfg7_T77"] = (_c, 77, _p, 7.0)
 
 
-def case_inputs(name):
-    """(x, t, cross_attn_cond, global_embed, prepend_cond or None, prepend_cond_mask or None)"""
-    _, t_len, p, _ = CASES[name]
-    x, t, c, g = cases.dit_inputs(2, t_len, 128, 96, 1)
-    pc = synthetic.synth_input("prepend", (2, p, PREPEND_DIM), 300 + p) if p else None
-    pm = torch.ones(2, p) if p else None           # (the reference concatenates it, dit.py:193; it never reaches the layers)
-    return x, t, c, g, pc, pm
+FAMILY = dit_family.Family(
+    title="dit conv ff", stem="dit_conv_ff_small", keys_file="dit_conv_ff_state_dict_keys.json", configs=CONFIGS, cases=CASES,
+    product_kwargs=PRODUCT_KWARGS, weights=lambda cfg_name, template_sd, seed=0: synth_weights(template_sd, seed), r16=True,
+    effect_of=f"the off-centre taps (OFF_CENTRE_GAIN {OFF_CENTRE_GAIN})",
+    baseline=lambda cfg_name: ("the centre taps alone", CONFIGS[cfg_name], centre_taps_only))

@@ -1,11 +1,9 @@
-"""The reduced DiT with 128-channel attention heads (embed_dim == 128 * num_heads) that tests/golden/make_golden_dit_head_dim.py
-(reference side) and tests/test_dit_head_dim_host.py / tests/test_gpu_dit_head_dim.py (product side) share: configs, forward cases and
-inputs.  Weights come from (seed, name) through ``dit_options_cases.synth_weights``, inputs through ``stable_audio_tools.synthetic``."""
-import torch
-
+"""The reduced DiT with 128-channel attention heads (embed_dim == 128 * num_heads) that tests/golden/make_golden_dit_families.py
+(reference side) and tests/test_dit_head_dim_host.py / tests/test_gpu_dit_head_dim.py (product side) share: configs and forward cases.
+Weights come from (seed, name) through ``dit_options_cases.synth_weights``, inputs through ``stable_audio_tools.synthetic`` (dit_family.py)."""
 import cases
+import dit_family
 import dit_options_cases as OC
-from stable_audio_tools import synthetic
 
 PREPEND_DIM, CONCAT_DIM = OC.PREPEND_DIM, OC.CONCAT_DIM
 HD128 = dict(cases.SMALL_DIT, num_heads=2)          # 256 / 2: two heads of 128, one kv head (cond_embed_dim 128)
@@ -25,7 +23,7 @@ synth_weights = OC.synth_weights
 
 
 def with_64_channel_heads(cfg):
-    """The same model with twice the heads of half the width: what make_golden_dit_head_dim.py compares every case with."""
+    """The same model with twice the heads of half the width: what the generator compares every case with."""
     return dict(cfg, num_heads=cfg["embed_dim"] // 64)
 
 
@@ -39,14 +37,8 @@ for _c in BASIC:
 CASES["hd128_qk_concat_cfg7_T77"] = ("hd128_qk_concat", 77, None, 7.0)
 
 
-def case_inputs(name):
-    """(x, t, cross_attn_cond or None, global_embed, prepend_cond or None, prepend_cond_mask or None, input_concat_cond or None)"""
-    cfg_name, t_len, p, _ = CASES[name]
-    cfg = CONFIGS[cfg_name]
-    x, t, c, g = cases.dit_inputs(2, t_len, cfg["cond_token_dim"] or 128, 96, 1)
-    if cfg["cond_token_dim"] == 0:
-        c = None
-    pc = synthetic.synth_input("prepend", (2, p, PREPEND_DIM), 300 + p) if p else None
-    pm = torch.ones(2, p) if p else None           # (the reference concatenates it, dit.py:193; it never reaches the layers)
-    cc = synthetic.synth_input("concat", (2, CONCAT_DIM, t_len), 200 + t_len) if cfg.get("input_concat_dim") else None
-    return x, t, c, g, pc, pm, cc
+# 3e-2, not the 5e-2 of the other families: what halving the head width moves the least case by
+FAMILY = dit_family.Family(
+    title="dit head dim", stem="dit_head_dim_small", keys_file="dit_head_dim_state_dict_keys.json", configs=CONFIGS, cases=CASES,
+    weights=OC.FAMILY.weights, concat=OC.FAMILY.concat, min_effect=3e-2, effect_of="the head width",
+    baseline=lambda cfg_name: ("the model with 64-channel heads", with_64_channel_heads(CONFIGS[cfg_name]), None))

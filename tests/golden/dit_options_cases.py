@@ -1,12 +1,11 @@
-"""The ContinuousTransformer options of the reduced DiT that tests/golden/make_golden_dit_options.py (reference side) and
-tests/test_dit_options_host.py / tests/test_gpu_dit_options.py (product side) share: configs, forward cases, inputs and the gain on the
-position-embedding tensors.  Weights and inputs come from (seed, name) through ``stable_audio_tools.synthetic``."""
-import torch
-
+"""The ContinuousTransformer options of the reduced DiT that tests/golden/make_golden_dit_families.py (reference side) and
+tests/test_dit_options_host.py / tests/test_gpu_dit_options.py (product side) share: configs, forward cases and the gain on the
+position-embedding tensors.  Weights and inputs come from (seed, name) through ``stable_audio_tools.synthetic`` (dit_family.py)."""
 import cases
+import dit_family
 from stable_audio_tools import synthetic
 
-PREPEND_DIM, CONCAT_DIM = 48, 65
+PREPEND_DIM, CONCAT_DIM = dit_family.PREPEND_DIM, 65
 QK = {"attn_kwargs": {"qk_norm": True}}
 ABS = dict(use_abs_pos_emb=True, abs_pos_emb_max_length=256, prepend_cond_dim=PREPEND_DIM)      # (prepend_cond_dim: one case brings 3 prepend tokens)
 # name -> DiffusionTransformer kwargs
@@ -27,7 +26,7 @@ CONFIGS.update({
     "sin_prepend": dict(cases.SMALL_DIT, use_sinusoidal_emb=True, prepend_cond_dim=PREPEND_DIM),
     "mult2": dict(cases.SMALL_DIT, ff_kwargs={"mult": 2, "no_bias": True}),
 })
-# what make_golden_dit_options.py compares every case with: the same model without the option(s)
+# what the generator compares every case with: the same model without the option(s)
 OPTION_KEYS = ("attn_kwargs", "ff_kwargs", "use_sinusoidal_emb", "use_abs_pos_emb", "abs_pos_emb_max_length", "rotary_pos_emb")
 
 # synth_state_dict draws transformer.pos_emb.scale from +-0.05 and emb.weight from +-0.03 (times D^-0.5 in the model): the embedding would
@@ -37,11 +36,11 @@ POS_EMB_GAIN = 40.0
 
 
 def synth_weights(template_sd, seed=0):
-    sd = synthetic.synth_state_dict(template_sd, seed)
-    for k in sd:
-        if k.startswith("transformer.pos_emb."):
-            sd[k] = sd[k] * POS_EMB_GAIN
-    return sd
+    return dit_family.scaled(synthetic.synth_state_dict(template_sd, seed), lambda k, v: POS_EMB_GAIN if k.startswith("transformer.pos_emb.") else None)
+
+
+def without_options(cfg):
+    return {k: v for k, v in cfg.items() if k not in OPTION_KEYS}
 
 
 # forward cases: name -> (config, t_len, prepend length P or None, cfg_scale).  Batch 2, 130 context tokens.  T = 77 on a "prepend" model is
@@ -59,13 +58,8 @@ CASES["sin_prepend_P3_cfg7_T77"] = ("sin_prepend", 77, 3, 7.0)
 CASES["mult2_cfg1_T77"] = ("mult2", 77, None, 1.0)
 
 
-def case_inputs(name):
-    """(x, t, cross_attn_cond or None, global_embed, prepend_cond or None, prepend_cond_mask or None, input_concat_cond or None)"""
-    cfg_name, t_len, p, _ = CASES[name]
-    x, t, c, g = cases.dit_inputs(2, t_len, 128, 96, 1)
-    if CONFIGS[cfg_name]["cond_token_dim"] == 0:
-        c = None
-    pc = synthetic.synth_input("prepend", (2, p, PREPEND_DIM), 300 + p) if p else None
-    pm = torch.ones(2, p) if p else None           # (the reference concatenates it, dit.py:193; it never reaches the layers)
-    cc = synthetic.synth_input("concat", (2, CONCAT_DIM, t_len), 200 + t_len) if CONFIGS[cfg_name].get("input_concat_dim") else None
-    return x, t, c, g, pc, pm, cc
+# the concat tensor has the latent's length, seed 200 + T
+FAMILY = dit_family.Family(
+    title="dit options", stem="dit_options_small", keys_file="dit_options_state_dict_keys.json", configs=CONFIGS, cases=CASES,
+    weights=lambda cfg_name, template_sd, seed=0: synth_weights(template_sd, seed), concat=lambda t_len: ((CONCAT_DIM, t_len), 200 + t_len),
+    baseline=lambda cfg_name: ("the model without the option", without_options(CONFIGS[cfg_name]), None))

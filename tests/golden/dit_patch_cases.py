@@ -1,13 +1,14 @@
 """The patchified reduced DiT -- DiffusionTransformer patch_size > 1 (reference models/dit.py:38,88-89,119-120,168-173,197-224) -- that
-tests/golden/make_golden_dit_patch.py (reference side) and tests/test_dit_patch_host.py / tests/test_gpu_dit_patch.py (product side) share:
-configs, forward cases, inputs, and the four mistakes every case must be able to tell from the model.  Weights and inputs come from
-(seed, name) through ``stable_audio_tools.synthetic``; synth_state_dict draws non-zero preprocess / postprocess convs."""
+tests/golden/make_golden_dit_families.py (reference side) and tests/test_dit_patch_host.py / tests/test_gpu_dit_patch.py (product side) share:
+configs, forward cases, and the mistakes every case must be able to tell from the model.  Weights and inputs come from
+(seed, name) through ``stable_audio_tools.synthetic`` (dit_family.py); synth_state_dict draws non-zero preprocess / postprocess convs."""
 import torch
 
 import cases
+import dit_family
 from stable_audio_tools import synthetic
 
-PREPEND_DIM = 48
+PREPEND_DIM = dit_family.PREPEND_DIM
 CONCAT_DIM = 8
 # name -> the reference's DiffusionTransformer kwargs (the product's take the opt-ins on top: PRODUCT_KWARGS)
 CONFIGS = {
@@ -46,24 +47,6 @@ def synth_weights(cfg_name, template_sd, seed=0):
         import dit_conv_ff_cases as CC
         return CC.synth_weights(template_sd, seed)
     return synthetic.synth_state_dict(template_sd, seed)
-
-
-def case_inputs(name):
-    """(x, t, cross_attn_cond, global_embed, prepend_cond or None, prepend_cond_mask or None, input_concat_cond or None)"""
-    cfg_name, t_len, p, _ = CASES[name]
-    cfg = CONFIGS[cfg_name]
-    x, t, c, g = cases.dit_inputs(2, t_len, 128, 96, 1)
-    if cfg["io_channels"] != 64:
-        x = synthetic.synth_input("x", (2, cfg["io_channels"], t_len), 1)
-    pc = synthetic.synth_input("prepend", (2, p, PREPEND_DIM), 300 + p) if p else None
-    pm = torch.ones(2, p) if p else None           # (the reference concatenates it, dit.py:193; it never reaches the layers)
-    cat = synthetic.synth_input("concat", (2, CONCAT_DIM, t_len // 3), 400) if cfg.get("input_concat_dim") else None
-    return x, t, c, g, pc, pm, cat
-
-
-def forward_kwargs(name):
-    x, t, c, g, pc, pm, cat = case_inputs(name)
-    return x, t, dict(cross_attn_cond=c, global_embed=g, prepend_cond=pc, prepend_cond_mask=pm, input_concat_cond=cat, cfg_scale=CASES[name][3])
 
 
 # ---- the mistakes a boundary kernel can make, as state dicts: a model with these weights computes what the mistaken kernel would
@@ -121,3 +104,8 @@ def convs_dropped(sd, P):
 
 MISTAKES = {"project_in columns as (p c)": in_columns_pc, "project_out rows as (p c)": out_rows_pc, "frames reversed inside a patch (input)": frames_reversed,
             "frames reversed inside a patch (output)": frames_reversed_out, "both 1x1 convs dropped": convs_dropped}
+
+# the concat tensor has a third of the latent's length (the model resizes it), seed 400
+FAMILY = dit_family.Family(
+    title="dit patch", stem="dit_patch_small", keys_file="dit_patch_state_dict_keys.json", configs=CONFIGS, cases=CASES,
+    product_kwargs=PRODUCT_KWARGS, weights=synth_weights, concat=lambda t_len: ((CONCAT_DIM, t_len // 3), 400), mistakes=MISTAKES, r16=True)

@@ -2,9 +2,7 @@
 modules hold the reference's parameter names and shapes, the options come in through the allow_block_options opt-in only (which the config
 factory passes), the combinations outside the HIP path raise with a reason, and sat_dit_plan_set_block_options checks its arguments.
 (Its SAT_E_STATE answer after finalize needs a finalized plan, i.e. a device: tests/test_gpu_dit_block_options.py.)"""
-import copy
 import ctypes
-import json
 import os
 import sys
 
@@ -15,22 +13,14 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 
 import cases  # noqa: E402
 import dit_block_options_cases as BC  # noqa: E402
+from dit_family_host import build as _build, check_state_dict_keys, model_config as _model_config  # noqa: E402
 
 OPTIONS = [dict(conformer=True), dict(remove_norms=True), dict(ff_kwargs={"glu": False})]
 
 
-def _build(**kwargs):
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
-    with _init.skip_init():
-        return DiffusionTransformer(**kwargs)
-
-
 @pytest.mark.parametrize("name", sorted(BC.CONFIGS))
 def test_dit_state_dict_matches_reference(name):
-    want = json.load(open(os.path.join(HERE, "golden", "dit_block_options_state_dict_keys.json")))[name]
-    got = {k: list(v.shape) for k, v in _build(**BC.CONFIGS[name], **BC.PRODUCT_KWARGS).state_dict().items()}
-    assert got == want
+    check_state_dict_keys(BC.FAMILY, name)
 
 
 def test_option_keys_that_come_and_go():
@@ -83,13 +73,6 @@ def test_use_conv_raises_on_both_paths(allow):
     assert "allow_block_options" in str(e.value)
     with pytest.raises(NotImplementedError, match="use_conv"):
         _build(**dict(cases.SMALL_DIT, ff_kwargs={"use_conv": True, "glu": False}), allow_block_options=allow)
-
-
-def _model_config(**dit_kwargs):
-    from stable_audio_tools import model_configs as MC
-    cfg = copy.deepcopy(MC.reduced(MC.stable_audio_open_1_0()))
-    cfg["model"]["diffusion"]["config"].update(dit_kwargs)
-    return cfg
 
 
 @pytest.mark.parametrize("kwargs", OPTIONS + [dict(conformer=True, remove_norms=True, ff_kwargs={"glu": False, "no_bias": True})])

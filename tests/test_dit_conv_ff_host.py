@@ -3,9 +3,7 @@ or by generate.py --allow-conv-ff), the modules hold the reference's parameter n
 with a reason, sat_dit_plan_set_ff_conv checks its arguments, the float64 restatement of the convolution GEMM (tests/conv_ff_units.py) is
 F.conv1d, and the per-row / 32 x 32-block gate of tests/util.py rejects the faults this kernel can have.
 (That the plan's tap-major packing equals the restatement's is shown on the device, where the packing runs: tests/test_gpu_conv_ff_kernels.py.)"""
-import copy
 import ctypes
-import json
 import os
 import sys
 
@@ -18,21 +16,8 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 import cases  # noqa: E402
 import conv_ff_units as cu  # noqa: E402
 import dit_conv_ff_cases as CC  # noqa: E402
+from dit_family_host import build as _build, check_state_dict_keys, model_config as _model_config  # noqa: E402
 from util import assert_close_rows_blocks, bf16_round  # noqa: E402
-
-
-def _build(**kwargs):
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
-    with _init.skip_init():
-        return DiffusionTransformer(**kwargs)
-
-
-def _model_config(**dit_kwargs):
-    from stable_audio_tools import model_configs as MC
-    cfg = copy.deepcopy(MC.reduced(MC.stable_audio_open_1_0()))
-    cfg["model"]["diffusion"]["config"].update(dit_kwargs)
-    return cfg
 
 
 # ------------------------------------------------------------------------------------------------------------------- construction
@@ -88,11 +73,7 @@ def test_generate_flag_sets_the_config_key(monkeypatch):
 
 @pytest.mark.parametrize("name", list(CC.CONFIGS))
 def test_state_dict_keys_and_shapes_are_the_references(name):
-    want = json.load(open(os.path.join(cases.GOLDEN_DIR, "dit_conv_ff_state_dict_keys.json")))[name]
-    m = _build(**CC.CONFIGS[name], **CC.PRODUCT_KWARGS)
-    got = {k: list(v.shape) for k, v in m.state_dict().items()}
-    assert got == want
-    m.load_state_dict(CC.synth_weights(m.state_dict(), 0), strict=True)
+    m, got = check_state_dict_keys(CC.FAMILY, name)
     k = CC.CONFIGS[name]["ff_kwargs"].get("conv_kernel_size", 3)
     assert m.transformer.ff_conv_kernel == k and got["transformer.layers.0.ff.ff.2.weight"][2] == k
     # the gain touches the off-centre taps of FF-out only, and centre_taps_only zeroes them in both convolutions

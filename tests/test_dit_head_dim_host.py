@@ -3,7 +3,6 @@ the modules hold the reference's parameter names and shapes (inv_freq has 32 ent
 HIP path still raise with a reason, sat_dit_plan_create admits exactly 64 and 128, the new kernels keep their register budget without
 scratch, and the LDS tile maps of the attention kernel are bijections.  No GPU."""
 import ctypes
-import json
 import os
 import re
 import shutil
@@ -17,27 +16,17 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 
 import cases  # noqa: E402
 import dit_head_dim_cases as HC  # noqa: E402
+from dit_family_host import build as _build, check_state_dict_keys  # noqa: E402
 
 CSRC = os.path.join(os.path.dirname(HERE), "friendly-stable-audio-tools_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
-def _build(**kwargs):
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
-    with _init.skip_init():
-        return DiffusionTransformer(**kwargs)
-
-
 @pytest.mark.parametrize("name", sorted(HC.CONFIGS))
 def test_dit_state_dict_matches_reference(name):
-    want = json.load(open(os.path.join(HERE, "golden", "dit_head_dim_state_dict_keys.json")))[name]
-    m = _build(**HC.CONFIGS[name])
-    got = {k: list(v.shape) for k, v in m.state_dict().items()}
-    assert got == want
+    _, got = check_state_dict_keys(HC.FAMILY, name)
     if HC.CONFIGS[name].get("rotary_pos_emb", True):
         assert got["transformer.rotary_pos_emb.inv_freq"] == [32]          # RotaryEmbedding(max(128 // 2, 32))
-    m.load_state_dict(HC.synth_weights(m.state_dict(), 0), strict=True)
 
 
 def test_head_counts_follow_the_head_width():

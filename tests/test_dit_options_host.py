@@ -3,7 +3,6 @@ models/transformer.py:50-96, 244-276, 298, 433-436, 718-746), host side: the mod
 the options that stay outside the HIP path still raise with a reason, and sat_dit_plan_set_transformer_options checks its arguments.
 (Its SAT_E_STATE answer after finalize needs a finalized plan, i.e. a device: tests/test_gpu_dit_options.py.)"""
 import ctypes
-import json
 import os
 import sys
 
@@ -14,20 +13,12 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 
 import cases  # noqa: E402
 import dit_options_cases as OC  # noqa: E402
-
-
-def _build(**kwargs):
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
-    with _init.skip_init():
-        return DiffusionTransformer(**kwargs)
+from dit_family_host import build as _build, check_state_dict_keys  # noqa: E402
 
 
 @pytest.mark.parametrize("name", sorted(OC.CONFIGS))
 def test_dit_state_dict_matches_reference(name):
-    want = json.load(open(os.path.join(HERE, "golden", "dit_options_state_dict_keys.json")))[name]
-    got = {k: list(v.shape) for k, v in _build(**OC.CONFIGS[name]).state_dict().items()}
-    assert got == want
+    check_state_dict_keys(OC.FAMILY, name)
 
 
 def test_option_keys_that_come_and_go():

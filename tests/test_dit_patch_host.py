@@ -3,9 +3,7 @@ generate.py --allow-patch-size), the modules hold the reference's parameter name
 of patches is a ValueError before the library is touched, sat_dit_plan_set_patch checks its arguments, the float64 restatements of the two
 boundary kernels (tests/dit_patch_units.py) are the reference's modules run in plain PyTorch, and the gates of tests/fp32_units.py reject the
 faults these kernels can have."""
-import copy
 import ctypes
-import json
 import os
 import sys
 
@@ -17,22 +15,9 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 
 import cases  # noqa: E402
 import dit_patch_cases as PC  # noqa: E402
+from dit_family_host import build as _build, check_state_dict_keys, model_config as _model_config  # noqa: E402
 import dit_patch_units as pu  # noqa: E402
 import fp32_units as fu  # noqa: E402
-
-
-def _build(**kwargs):
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
-    with _init.skip_init():
-        return DiffusionTransformer(**kwargs)
-
-
-def _model_config(**dit_kwargs):
-    from stable_audio_tools import model_configs as MC
-    cfg = copy.deepcopy(MC.reduced(MC.stable_audio_open_1_0()))
-    cfg["model"]["diffusion"]["config"].update(dit_kwargs)
-    return cfg
 
 
 # ------------------------------------------------------------------------------------------------------------------- construction
@@ -97,12 +82,8 @@ def test_generate_flag_sets_the_config_key(monkeypatch):
 
 @pytest.mark.parametrize("name", list(PC.CONFIGS))
 def test_state_dict_keys_and_shapes_are_the_references(name):
-    want = json.load(open(os.path.join(cases.GOLDEN_DIR, "dit_patch_state_dict_keys.json")))[name]
-    m = _build(**PC.CONFIGS[name], **PC.PRODUCT_KWARGS)
-    got = {k: list(v.shape) for k, v in m.state_dict().items()}
-    assert got == want
-    m.load_state_dict({k: torch.zeros(s) for k, s in want.items()}, strict=True)          # a reference-shaped state dict
-    m.load_state_dict(PC.synth_weights(name, m.state_dict(), 0), strict=True)
+    m, got = check_state_dict_keys(PC.FAMILY, name)
+    _build(**PC.CONFIGS[name], **PC.PRODUCT_KWARGS).load_state_dict({k: torch.zeros(shape) for k, shape in got.items()}, strict=True)          # a reference-shaped state dict
     cfg = PC.CONFIGS[name]
     P, c, ci = cfg["patch_size"], cfg["io_channels"], cfg["io_channels"] + cfg.get("input_concat_dim", 0)
     assert got["transformer.project_in.weight"] == [256, ci * P] and got["transformer.project_out.weight"] == [c * P, 256]

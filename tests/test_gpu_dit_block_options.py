@@ -1,8 +1,9 @@
 """conformer, remove_norms and ff_kwargs glu=False on the HIP DiT (reference models/transformer.py:557-591, 621-645, 259-268, 680-700)
-against the REFERENCE's own outputs (tests/golden/dit_block_options_small*.npz: tests/golden/make_golden_dit_block_options.py).
+against the REFERENCE's own outputs (tests/golden/dit_block_options_small*.npz: tests/golden/make_golden_dit_families.py block_options).
+Gates: the harness, tests/dit_family_gpu.py.
 
-* the suite's operand format at the reduced-DiT gates of test_gpu_dit_options.py: T(2.5e-3) at CFG 1, T(1.2e-2) at CFG 7;
-* the fp32 verification mode (gemm_dtype "fp32x") at 1e-4: what separates an indexing error (a conv window off by one row or leaking
+* the suite's operand format at the reduced-DiT gates;
+* the fp32 verification mode (gemm_dtype "fp32x"): what separates an indexing error (a conv window off by one row or leaking
   into the neighbouring sequence, the chunk order of the GLU, a norm applied where it was removed) from rounding;
 * four cases again with the LayerNorm fold off and with the fused to_q + cross-attention launch off, and through the fused sampler step;
 * all three options with per-block operand formats;
@@ -19,75 +20,22 @@ import torch.nn.functional as F
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-import cases  # noqa: E402
 import dit_block_options_cases as BC  # noqa: E402
+from dit_family_gpu import FP32X_GATE, Harness, generate, reduced_model  # noqa: E402
 from util import FORMATS, SUITE, assert_close, assert_close_rows_blocks, assert_close_sliced, guarded, rel_l2  # noqa: E402
 
-T = SUITE.tol
 pytestmark = pytest.mark.gpu
-
-_MODELS = {}
-_GOLD = []
-
-
-def _gold():
-    if not _GOLD:
-        _GOLD.append(cases.load("dit_block_options_small"))
-    return _GOLD[0]
-
-
-def _model(cfg_name, dev):
-    if cfg_name not in _MODELS:
-        from stable_audio_tools.models import _init
-        from stable_audio_tools.models.dit import DiffusionTransformer
-        with _init.skip_init():
-            m = DiffusionTransformer(**BC.CONFIGS[cfg_name], **BC.PRODUCT_KWARGS)
-        m.load_state_dict(BC.synth_weights(m.state_dict(), 0), strict=True)
-        _MODELS[cfg_name] = m.to(dev).eval()
-    return _MODELS[cfg_name]
-
-
-def _inputs(name, dev):
-    to = lambda v: None if v is None else v.to(dev)
-    return tuple(to(v) for v in BC.case_inputs(name))
-
-
-def _run(name, dev, dtype, ln_fold=True, cross_fusion=True, formats=None):
-    cfg_name, _, _, cfg_scale = BC.CASES[name]
-    m = _model(cfg_name, dev)
-    m.set_gemm_dtype(dtype).set_layernorm_fusion(ln_fold).set_cross_attention_fusion(cross_fusion).set_block_gemm_dtypes(formats)
-    try:
-        x, t, c, g, pc, pm = _inputs(name, dev)
-        out = m(x, t, cross_attn_cond=c, global_embed=g, prepend_cond=pc, prepend_cond_mask=pm, cfg_scale=cfg_scale)
-        torch.cuda.synchronize()
-    finally:
-        m.set_block_gemm_dtypes(None).set_gemm_dtype(SUITE.gemm_dtype).set_layernorm_fusion(True).set_cross_attention_fusion(True)
-    return out
-
-
-def _gate(name, fmt=SUITE):
-    return fmt.tol(2.5e-3) if BC.CASES[name][3] == 1.0 else fmt.tol(1.2e-2)
-
-
-def _r16(name, fmt=SUITE):
-    """What 16-bit operands of the Linears / convs alone cost the REFERENCE on this case (computed on the CPU by the generator)."""
-    return rel_l2(_gold()[f"{name}__r16_{fmt.gemm_dtype}"], _gold()[name])
+H = Harness(BC.FAMILY)
 
 
 @pytest.mark.parametrize("name", list(BC.CASES))
 def test_block_options_vs_reference(dev, name):
-    got = _run(name, dev, SUITE.gemm_dtype)
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit block options {name}, {SUITE.gemm_dtype}] rel-L2 vs reference {e:.2e} (gate {_gate(name):.1e}; reference with rounded operands {_r16(name):.2e})")
-    assert_close(f"{name} ({SUITE.gemm_dtype}) vs reference", got, _gold()[name], _gate(name))
+    H.check_vs_reference(dev, name, SUITE.gemm_dtype, H.gate(name), rounded=True)
 
 
 @pytest.mark.parametrize("name", list(BC.CASES))
 def test_block_options_fp32_vs_reference(dev, name):
-    got = _run(name, dev, "fp32x")
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit block options {name}, fp32x] rel-L2 vs reference {e:.2e}")
-    assert_close(f"{name} (fp32x) vs reference", got, _gold()[name], 1e-4)
+    H.check_vs_reference(dev, name, "fp32x", FP32X_GATE)
 
 
 OTHER_PATHS = ["conf_cfg7_T77", "nonorm_adaln_cfg7_T77", "all3_cfg7_T77", "conf_prepend_cfg7_T77"]
@@ -98,66 +46,35 @@ OTHER_PATHS = ["conf_cfg7_T77", "nonorm_adaln_cfg7_T77", "all3_cfg7_T77", "conf_
 def test_block_options_on_the_other_launch_paths(dev, name, path):
     """The standalone LayerNorm in front of pointwise_conv and the rounding launch of remove_norms instead of the residual image; to_q +
     attention core as two kernels."""
-    got = _run(name, dev, SUITE.gemm_dtype, ln_fold=path != "ln_fold_off", cross_fusion=path != "cross_fusion_off")
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit block options {name}, {SUITE.gemm_dtype}, {path}] rel-L2 vs reference {e:.2e} (gate {_gate(name):.1e})")
-    assert_close(f"{name} ({SUITE.gemm_dtype}, {path}) vs reference", got, _gold()[name], _gate(name))
+    H.check_vs_reference(dev, name, SUITE.gemm_dtype, H.gate(name), path, ln_fold=path != "ln_fold_off", cross_fusion=path != "cross_fusion_off")
 
 
 def test_remove_norms_results_do_not_depend_on_the_layernorm_fusion(dev):
     """With remove_norms the A operand is the rounded residual row either way: written by the previous residual epilogue under the fold,
     by the rounding launch without it.  Same bits in, same kernels behind: same bits out."""
-    a = _run("nonorm_cfg7_T77", dev, SUITE.gemm_dtype, ln_fold=True)
-    b = _run("nonorm_cfg7_T77", dev, SUITE.gemm_dtype, ln_fold=False)
+    a = H.run("nonorm_cfg7_T77", dev, SUITE.gemm_dtype, ln_fold=True)
+    b = H.run("nonorm_cfg7_T77", dev, SUITE.gemm_dtype, ln_fold=False)
     assert torch.equal(a, b), f"remove_norms: fold on / off differ, rel-L2 {rel_l2(a, b):.3e}"
 
 
 @pytest.mark.parametrize("dtype", ["suite", "fp32x"])
 @pytest.mark.parametrize("name", OTHER_PATHS)
 def test_fused_denoise_matches_forward(dev, name, dtype):
-    """prepare_generation + denoise (one sat_dit_denoise_cfg per step) == VDenoiser(forward), as in test_gpu_dit_options.py: 1e-5 in fp32;
-    in the suite's format the two round c_in * x at different points and CFG 7 amplifies the 16-bit roundings that flip."""
-    cfg_name, _, _, cfg_scale = BC.CASES[name]
-    fmt = SUITE.gemm_dtype if dtype == "suite" else dtype
-    gate = T(2e-2) if dtype == "suite" else 1e-5
-    m = _model(cfg_name, dev)
-    m.set_gemm_dtype(fmt)
-    try:
-        x, _, c, g, pc, _ = _inputs(name, dev)
-        for sigma in (0.7, 12.0):
-            c_skip, c_out, c_in = 1.0 / (sigma ** 2 + 1), -sigma / (sigma ** 2 + 1) ** 0.5, 1.0 / (sigma ** 2 + 1) ** 0.5
-            t = torch.full((x.shape[0],), float(torch.atan(torch.tensor(sigma, dtype=torch.float64)) / torch.pi * 2), device=dev)
-            want = m(x * c_in, t, cross_attn_cond=c, global_embed=g, prepend_cond=pc, cfg_scale=cfg_scale) * c_out + x * c_skip
-            m.prepare_generation(c, g, cfg_scale, prepend_cond=pc)
-            got = m.denoise(x, sigma, cfg_scale=cfg_scale)
-            torch.cuda.synchronize()
-            e = rel_l2(got, want)
-            print(f"\n[fused denoise {name}, {fmt}, sigma {sigma}] rel-L2 vs VDenoiser(forward) {e:.2e}")
-            assert torch.isfinite(got).all()
-            assert e <= gate, f"{name} {fmt} sigma {sigma}: fused denoise vs VDenoiser(forward) rel-L2 {e:.3e} > {gate:.1e}"
-    finally:
-        m.set_gemm_dtype(SUITE.gemm_dtype)
+    H.check_fused_denoise(dev, name, dtype)
 
 
 @pytest.mark.parametrize("name", ["all3_cfg1_T64", "all3_cfg7_T77"])
 def test_all_three_options_with_per_block_formats(dev, name):
     """[fp16, bf16, fp16]: block 1 keeps its weight images, the conformer's three 16-bit buffers and the SiLU hidden state in bf16, and its
-    to_qkv rounds the fp32 rows itself (no image from block 0's FF-out in its format).  Gated at the bf16 gates of the model size, the
-    coarsest format in the plan."""
-    bf16 = FORMATS[0]
-    got = _run(name, dev, "fp16", formats=["fp16", "bf16", "fp16"])
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit block options {name}, fp16 / bf16 / fp16] rel-L2 vs reference {e:.2e} (gate {_gate(name, bf16):.1e})")
-    assert_close(f"{name} (fp16 / bf16 / fp16) vs reference", got, _gold()[name], _gate(name, bf16))
-    uniform = _run(name, dev, "fp16")
-    assert not torch.equal(got, uniform), "the per-block formats changed no bit: block 1 did not run in bf16"
+    to_qkv rounds the fp32 rows itself (no image from block 0's FF-out in its format)."""
+    H.check_per_block_formats(dev, name)
 
 
 def test_block_options_c_abi_after_finalize_and_range_report(dev):
     """sat_dit_plan_set_block_options is refused once the plan is finalized; the range report has no rows for these plans."""
     from stable_audio_tools import _hip
     lib = _hip.lib()
-    m = _model("conf", dev)
+    m = H.model("conf", dev)
     plan = m._ensure_plan()
     opts = _hip.SatDitBlockOptions(0, 0, 1)
     assert lib.sat_dit_plan_set_block_options(plan, ctypes.byref(opts), ctypes.sizeof(opts)) == -5 and b"finalized" in lib.sat_last_error()
@@ -169,29 +86,11 @@ def test_block_options_c_abi_after_finalize_and_range_report(dev):
 def test_config_driven_model_generates(dev):
     """A config with all three options builds through create_model_from_config, loads a reference-layout state dict with strict=True
     and generates through generate_diffusion_cond."""
-    import copy
-    import stable_audio_tools as S
-    from stable_audio_tools import model_configs as MC, synthetic
-    from stable_audio_tools.inference.generation import generate_diffusion_cond
-    from stable_audio_tools.models import _init
-    cfg = copy.deepcopy(MC.reduced(MC.stable_audio_open_1_0()))
-    dc = cfg["model"]["diffusion"]["config"]
-    dc.update(conformer=True, remove_norms=True, ff_kwargs={"glu": False})
-    with _init.skip_init():
-        model = S.create_model_from_config(cfg)
+    from stable_audio_tools import synthetic
+    cfg, model = reduced_model(conformer=True, remove_norms=True, ff_kwargs={"glu": False})
     sd = synthetic.synth_state_dict(model.state_dict(), 0)
     assert any(".conformer.depthwise_conv.weight" in k for k in sd) and any(".ff.ff.0.1.weight" in k for k in sd) and not any("pre_norm" in k for k in sd)
-    model.load_state_dict(sd, strict=True)
-    model = model.to(dev).eval()
-    b, steps, t_len = 1, 2, 16
-    ratio = cfg["model"]["pretransform"]["config"]["downsampling_ratio"]
-    cond = model.conditioner([{"seconds_start": 0, "seconds_total": 12}])
-    cond["prompt"] = (synthetic.synth_input("prompt", (b, 128, dc["cond_token_dim"]), 1).to(dev), torch.ones(b, 128, device=dev))
-    cond = {k: cond[k] for k in ("prompt", "seconds_start", "seconds_total")}
-    audio = generate_diffusion_cond(model, steps=steps, cfg_scale=7.0, conditioning_tensors=cond, sample_size=t_len * ratio, seed=3,
-                                    device=str(dev), sampler_type="dpmpp-3m-sde", sigma_min=0.3, sigma_max=500)
-    torch.cuda.synchronize()
-    assert audio.shape == (b, 2, t_len * ratio) and torch.isfinite(audio).all() and float(audio.abs().max()) > 0
+    generate(model, cfg, dev, sd, steps=2, seed=3)
 
 
 # ------------------------------------------------------------------------------------------------------------ the two kernels alone

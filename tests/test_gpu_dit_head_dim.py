@@ -1,7 +1,7 @@
 """DiTs with 128-channel attention heads (embed_dim == 128 * num_heads) on the device: the attention kernel (csrc/attention_hd128.hip) and
 the head split (csrc/head_split.hip) alone, then the plan's staged route against the REFERENCE's own outputs
-(tests/golden/dit_head_dim_small.npz: tests/golden/make_golden_dit_head_dim.py) at the reduced-DiT gates of test_gpu_dit_options.py --
-T(2.5e-3) at CFG 1, T(1.2e-2) at CFG 7 --, the fused prepare_generation + denoise step and generate_diffusion_cond."""
+(tests/golden/dit_head_dim_small.npz: tests/golden/make_golden_dit_families.py head_dim) at the reduced-DiT gates of the harness
+(tests/dit_family_gpu.py), the fused prepare_generation + denoise step and generate_diffusion_cond."""
 import ctypes
 import math
 import os
@@ -13,17 +13,14 @@ import torch.nn.functional as F
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-import cases  # noqa: E402
 import dit_head_dim_cases as HC  # noqa: E402
 import mask_edge  # noqa: E402
+from dit_family_gpu import Harness, generate, reduced_model  # noqa: E402
 from util import FORMATS, SUITE, assert_close, assert_close_sliced, guarded, rel_l2  # noqa: E402
 
-T = SUITE.tol
 pytestmark = pytest.mark.gpu
 QSCALE = 1.4426950408889634 / math.sqrt(128.0)          # log2(e) / sqrt(128): what the head split multiplies into Q
-
-_MODELS = {}
-_GOLD = []
+H = Harness(HC.FAMILY)
 
 
 def _lib():
@@ -202,49 +199,17 @@ def test_head_split_hd128(dev, fmt, qk_norm):
 
 
 # ------------------------------------------------------------------------------- the plan
-def _gold():
-    if not _GOLD:
-        _GOLD.append(cases.load("dit_head_dim_small"))
-    return _GOLD[0]
-
-
-def _model(cfg_name, dev):
-    if cfg_name not in _MODELS:
-        from stable_audio_tools.models import _init
-        from stable_audio_tools.models.dit import DiffusionTransformer
-        with _init.skip_init():
-            m = DiffusionTransformer(**HC.CONFIGS[cfg_name])
-        m.load_state_dict(HC.synth_weights(m.state_dict(), 0))
-        _MODELS[cfg_name] = m.to(dev).eval()
-    return _MODELS[cfg_name]
-
-
-def _inputs(name, dev):
-    to = lambda v: None if v is None else v.to(dev)
-    return tuple(to(v) for v in HC.case_inputs(name))
-
-
-def _gate(name):
-    return T(2.5e-3) if HC.CASES[name][3] == 1.0 else T(1.2e-2)
-
-
 @pytest.mark.parametrize("name", list(HC.CASES))
 def test_dit_head_dim_vs_reference(dev, name):
-    cfg_name, _, _, cfg_scale = HC.CASES[name]
-    m = _model(cfg_name, dev)
-    x, t, c, g, pc, pm, cc = _inputs(name, dev)
-    got = m(x, t, cross_attn_cond=c, global_embed=g, prepend_cond=pc, prepend_cond_mask=pm, input_concat_cond=cc, cfg_scale=cfg_scale)
-    torch.cuda.synchronize()
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit head dim {name}, {SUITE.gemm_dtype}] rel-L2 vs reference {e:.2e} (gate {_gate(name):.1e})")
-    assert_close(f"{name} ({SUITE.gemm_dtype}) vs reference", got, _gold()[name], _gate(name))
+    H.check_vs_reference(dev, name, SUITE.gemm_dtype, H.gate(name))
 
 
 def test_fusion_switches_change_nothing(dev):
     """set_layernorm_fusion / set_cross_attention_fusion are accepted and have no effect on a plan with 128-channel heads (as for adaLN)."""
     name = "hd128_cfg7_T77"
-    m = _model("hd128", dev)
-    x, t, c, g, *_ = _inputs(name, dev)
+    m = H.model("hd128", dev)
+    x, t, kw = H.inputs(name, dev)
+    c, g = kw["cross_attn_cond"], kw["global_embed"]
     want = m(x, t, cross_attn_cond=c, global_embed=g, cfg_scale=7.0)
     m.set_layernorm_fusion(False).set_cross_attention_fusion(False)
     try:
@@ -256,55 +221,26 @@ def test_fusion_switches_change_nothing(dev):
 
 
 def test_residual_stream_report(dev):
-    m = _model("hd128", dev)
-    x, t, c, g, *_ = _inputs("hd128_cfg1_T64", dev)
+    m = H.model("hd128", dev)
+    x, t, kw = H.inputs("hd128_cfg1_T64", dev)
     m.residual_stream_report(True)
-    m(x, t, cross_attn_cond=c, global_embed=g)
+    m(x, t, cross_attn_cond=kw["cross_attn_cond"], global_embed=kw["global_embed"])
     rows = m.residual_stream_report(False)
     assert len(rows) == 3 * 3 and all(r["max_abs"] > 0 and math.isfinite(r["crest"]) and r["saturated"] == 0 for r in rows), rows
 
 
 @pytest.mark.parametrize("name", ["hd128_cfg7_T77", "hd128_adaln_cfg7_T77", "hd128_prepend_only_cfg7_T77"])
 def test_fused_denoise_matches_forward(dev, name):
-    """prepare_generation + denoise (one sat_dit_denoise_cfg per step) == VDenoiser(forward), as in test_gpu_dit_options.py: the two
-    round c_in * x at different points and CFG 7 amplifies the 16-bit roundings that flip."""
-    cfg_name, _, _, cfg_scale = HC.CASES[name]
-    m = _model(cfg_name, dev)
-    x, _, c, g, pc, _, _ = _inputs(name, dev)
-    for sigma in (0.7, 12.0):
-        c_skip, c_out, c_in = 1.0 / (sigma ** 2 + 1), -sigma / (sigma ** 2 + 1) ** 0.5, 1.0 / (sigma ** 2 + 1) ** 0.5
-        t = torch.full((x.shape[0],), float(torch.atan(torch.tensor(sigma, dtype=torch.float64)) / torch.pi * 2), device=dev)
-        want = m(x * c_in, t, cross_attn_cond=c, global_embed=g, prepend_cond=pc, cfg_scale=cfg_scale) * c_out + x * c_skip
-        m.prepare_generation(c, g, cfg_scale, prepend_cond=pc)
-        got = m.denoise(x, sigma, cfg_scale=cfg_scale)
-        torch.cuda.synchronize()
-        e = rel_l2(got, want)
-        print(f"\n[fused denoise {name}, {SUITE.gemm_dtype}, sigma {sigma}] rel-L2 vs VDenoiser(forward) {e:.2e} (gate {T(2e-2):.1e})")
-        assert torch.isfinite(got).all()
-        assert e <= T(2e-2), f"{name} sigma {sigma}: fused denoise vs VDenoiser(forward) rel-L2 {e:.3e} > {T(2e-2):.1e}"
+    H.check_fused_denoise(dev, name, "suite")
 
 
 def test_generate_diffusion_cond_with_128_channel_heads(dev):
     """generate_diffusion_cond on a reduced diffusion_cond model with num_heads=2 (two heads of 128, one kv head): 4 steps of
     dpmpp-3m-sde at CFG 7; finite audio of the right shape, and two runs with one seed are bit-identical."""
-    import stable_audio_tools as S
-    from stable_audio_tools import model_configs as MC, synthetic
-    from stable_audio_tools.inference.generation import generate_diffusion_cond
-    from stable_audio_tools.models import _init
-    cfg = MC.reduced(MC.stable_audio_open_1_0(), num_heads=2)
-    with _init.skip_init():
-        model = S.create_model_from_config(cfg)
-    model.load_state_dict(synthetic.synth_state_dict(model.state_dict(), 0))
-    model = model.to(dev).eval()
+    from stable_audio_tools import synthetic
+    cfg, model = reduced_model(num_heads=2)
     assert model.model.model.transformer.dim_heads == 128
-    b, t_len = 1, 16
-    ratio = cfg["model"]["pretransform"]["config"]["downsampling_ratio"]
-    cond = model.conditioner([{"seconds_start": 0, "seconds_total": 12}])
-    cond["prompt"] = (synthetic.synth_input("prompt", (b, 128, 128), 1).to(dev), torch.ones(b, 128, device=dev))
-    cond = {k: cond[k] for k in ("prompt", "seconds_start", "seconds_total")}
-    run = lambda: generate_diffusion_cond(model, steps=4, cfg_scale=7.0, conditioning_tensors=cond, sample_size=t_len * ratio, seed=3,
-                                          device=str(dev), sampler_type="dpmpp-3m-sde", sigma_min=0.3, sigma_max=500)
+    sd = synthetic.synth_state_dict(model.state_dict(), 0)
+    run = lambda: generate(model, cfg, dev, sd, steps=4, seed=3)[0]
     a0, a1 = run(), run()
-    torch.cuda.synchronize()
-    assert a0.shape == (b, 2, t_len * ratio) and torch.isfinite(a0).all() and float(a0.abs().max()) > 0
     assert torch.equal(a0, a1)

@@ -1,9 +1,9 @@
 """qk_norm, sinusoidal / absolute position embeddings, rotary_pos_emb=False and bias-free feed-forwards on the HIP DiT (reference
 models/transformer.py:50-96, 270, 433-436, 796-797) against the REFERENCE's own outputs (tests/golden/dit_options_small.npz:
-tests/golden/make_golden_dit_options.py).
+tests/golden/make_golden_dit_families.py options).  Gates: the harness, tests/dit_family_gpu.py.
 
-* the suite's operand format at the reduced-DiT gates of test_gpu_extra_conditioning.py: T(2.5e-3) at CFG 1, T(1.2e-2) at CFG 7;
-* the fp32 verification mode (gemm_dtype "fp32x") at 1e-4: what separates an indexing error (the position of a prepended row, a
+* the suite's operand format at the reduced-DiT gates;
+* the fp32 verification mode (gemm_dtype "fp32x"): what separates an indexing error (the position of a prepended row, a
   normalisation over the wrong 64 channels, a key shift) from rounding;
 * the qk_norm cases again with the LayerNorm fold off and with the fused to_q + cross-attention launch off;
 * the normalising QKV step alone (sat_qkv_rope_qknorm_*) against a float64 restatement.
@@ -17,71 +17,22 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-import cases  # noqa: E402
 import dit_options_cases as OC  # noqa: E402
-from util import FORMATS, SUITE, assert_close, assert_close_sliced, guarded, rel_l2  # noqa: E402
+from dit_family_gpu import FP32X_GATE, Harness  # noqa: E402
+from util import FORMATS, SUITE, assert_close, assert_close_sliced, guarded  # noqa: E402
 
-T = SUITE.tol
 pytestmark = pytest.mark.gpu
-
-_MODELS = {}
-_GOLD = []
-
-
-def _gold():
-    if not _GOLD:
-        _GOLD.append(cases.load("dit_options_small"))
-    return _GOLD[0]
-
-
-def _model(cfg_name, dev, **more):
-    key = (cfg_name, tuple(sorted(more.items())))
-    if key not in _MODELS:
-        from stable_audio_tools.models import _init
-        from stable_audio_tools.models.dit import DiffusionTransformer
-        with _init.skip_init():
-            m = DiffusionTransformer(**OC.CONFIGS[cfg_name], **more)
-        m.load_state_dict(OC.synth_weights(m.state_dict(), 0))
-        _MODELS[key] = m.to(dev).eval()
-    return _MODELS[key]
-
-
-def _inputs(name, dev):
-    to = lambda v: None if v is None else v.to(dev)
-    return tuple(to(v) for v in OC.case_inputs(name))
-
-
-def _run(name, dev, dtype, ln_fold=True, cross_fusion=True, **more):
-    cfg_name, _, _, cfg_scale = OC.CASES[name]
-    m = _model(cfg_name, dev, **more)
-    m.set_gemm_dtype(dtype).set_layernorm_fusion(ln_fold).set_cross_attention_fusion(cross_fusion)
-    try:
-        x, t, c, g, pc, pm, cc = _inputs(name, dev)
-        out = m(x, t, cross_attn_cond=c, global_embed=g, prepend_cond=pc, prepend_cond_mask=pm, input_concat_cond=cc, cfg_scale=cfg_scale)
-        torch.cuda.synchronize()
-    finally:
-        m.set_gemm_dtype(SUITE.gemm_dtype).set_layernorm_fusion(True).set_cross_attention_fusion(True)
-    return out
-
-
-def _gate(name):
-    return T(2.5e-3) if OC.CASES[name][3] == 1.0 else T(1.2e-2)
+H = Harness(OC.FAMILY)
 
 
 @pytest.mark.parametrize("name", list(OC.CASES))
 def test_dit_options_vs_reference(dev, name):
-    got = _run(name, dev, SUITE.gemm_dtype)
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit options {name}, {SUITE.gemm_dtype}] rel-L2 vs reference {e:.2e} (gate {_gate(name):.1e})")
-    assert_close(f"{name} ({SUITE.gemm_dtype}) vs reference", got, _gold()[name], _gate(name))
+    H.check_vs_reference(dev, name, SUITE.gemm_dtype, H.gate(name))
 
 
 @pytest.mark.parametrize("name", list(OC.CASES))
 def test_dit_options_fp32_vs_reference(dev, name):
-    got = _run(name, dev, "fp32x")
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit options {name}, fp32x] rel-L2 vs reference {e:.2e}")
-    assert_close(f"{name} (fp32x) vs reference", got, _gold()[name], 1e-4)
+    H.check_vs_reference(dev, name, "fp32x", FP32X_GATE)
 
 
 @pytest.mark.parametrize("path", ["ln_fold_off", "cross_fusion_off"])
@@ -89,55 +40,28 @@ def test_dit_options_fp32_vs_reference(dev, name):
 def test_qk_norm_on_the_other_launch_paths(dev, name, path):
     """The standalone LayerNorms in front of the normalising projections, and to_q + attention core as two kernels (the normalised Q
     then goes through memory instead of staying in the fused launch's registers)."""
-    got = _run(name, dev, SUITE.gemm_dtype, ln_fold=path != "ln_fold_off", cross_fusion=path != "cross_fusion_off")
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit options {name}, {SUITE.gemm_dtype}, {path}] rel-L2 vs reference {e:.2e} (gate {_gate(name):.1e})")
-    assert_close(f"{name} ({SUITE.gemm_dtype}, {path}) vs reference", got, _gold()[name], _gate(name))
+    H.check_vs_reference(dev, name, SUITE.gemm_dtype, H.gate(name), path, ln_fold=path != "ln_fold_off", cross_fusion=path != "cross_fusion_off")
 
 
 @pytest.mark.parametrize("dtype", ["suite", "fp32x"])
 @pytest.mark.parametrize("name", ["qk_cfg7_T77", "qk_adaln_cfg7_T77", "qk_prepend_only_cfg7_T77", "all_cfg7_T77", "abs_norope_P3_cfg7_T64"])
 def test_fused_denoise_matches_forward(dev, name, dtype):
-    """prepare_generation + denoise (one sat_dit_denoise_cfg per step) == VDenoiser(forward), as in test_gpu_extra_conditioning.py: 1e-5 in
-    fp32; in the suite's format the two round c_in * x at different points and CFG 7 amplifies the 16-bit roundings that flip."""
-    cfg_name, _, _, cfg_scale = OC.CASES[name]
-    fmt = SUITE.gemm_dtype if dtype == "suite" else dtype
-    gate = T(2e-2) if dtype == "suite" else 1e-5
-    m = _model(cfg_name, dev)
-    m.set_gemm_dtype(fmt)
-    try:
-        x, _, c, g, pc, _, _ = _inputs(name, dev)
-        for sigma in (0.7, 12.0):
-            c_skip, c_out, c_in = 1.0 / (sigma ** 2 + 1), -sigma / (sigma ** 2 + 1) ** 0.5, 1.0 / (sigma ** 2 + 1) ** 0.5
-            t = torch.full((x.shape[0],), float(torch.atan(torch.tensor(sigma, dtype=torch.float64)) / torch.pi * 2), device=dev)
-            want = m(x * c_in, t, cross_attn_cond=c, global_embed=g, prepend_cond=pc, cfg_scale=cfg_scale) * c_out + x * c_skip
-            m.prepare_generation(c, g, cfg_scale, prepend_cond=pc)
-            got = m.denoise(x, sigma, cfg_scale=cfg_scale)
-            torch.cuda.synchronize()
-            e = rel_l2(got, want)
-            print(f"\n[fused denoise {name}, {fmt}, sigma {sigma}] rel-L2 vs VDenoiser(forward) {e:.2e}")
-            assert torch.isfinite(got).all()
-            assert e <= gate, f"{name} {fmt} sigma {sigma}: fused denoise vs VDenoiser(forward) rel-L2 {e:.3e} > {gate:.1e}"
-    finally:
-        m.set_gemm_dtype(SUITE.gemm_dtype)
+    H.check_fused_denoise(dev, name, dtype)
 
 
 @pytest.mark.parametrize("name", ["abs_P3_cfg1_T77", "abs_cfg7_T77"])
 def test_abs_table_longer_than_the_plan(dev, name):
     """abs_pos_emb_max_length 256 on a plan of max_seq_len 100 (at most 64 + 1 + 100 rows): the table then has the plan's rows, not the
     embedding's -- same weights, same golden as the plan of the default max_seq_len, whose table stops at the embedding's 256 rows."""
-    got = _run(name, dev, SUITE.gemm_dtype, max_seq_len=100)
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit options {name}, {SUITE.gemm_dtype}, max_seq_len 100] rel-L2 vs reference {e:.2e} (gate {_gate(name):.1e})")
-    assert_close(f"{name} ({SUITE.gemm_dtype}, max_seq_len 100) vs reference", got, _gold()[name], _gate(name))
-
+    H.check_vs_reference(dev, name, SUITE.gemm_dtype, H.gate(name), "max_seq_len 100", max_seq_len=100)
 
 def test_sequence_longer_than_abs_pos_emb_max_length(dev):
     """The reference's AssertionError (transformer.py:59-61), on the host: forward and the fused path; the C entry point answers
     SAT_E_INVALID with the same sentence before it launches anything; and the options call is refused once the plan is finalized."""
     from stable_audio_tools import _hip
-    m = _model("abs", dev)
-    x, t, c, g, pc, pm, _ = _inputs("abs_P3_cfg1_T77", dev)
+    m = H.model("abs", dev)
+    x, t, kw = H.inputs("abs_P3_cfg1_T77", dev)
+    c, g, pc, pm = kw["cross_attn_cond"], kw["global_embed"], kw["prepend_cond"], kw["prepend_cond_mask"]
     m(x, t, cross_attn_cond=c, global_embed=g, prepend_cond=pc, prepend_cond_mask=pm)          # 3 + 1 + 77 rows: fine
     long = torch.zeros(2, 64, 255, device=dev)                                                 # 1 + 255 = 256 rows: the last that fits
     assert torch.isfinite(m(long, t, cross_attn_cond=c, global_embed=g)).all()

@@ -1,8 +1,9 @@
 """Patchified DiTs (DiffusionTransformer patch_size > 1, reference models/dit.py:38,88-89,119-120,197-224) on the HIP DiT against the
-REFERENCE's own outputs (tests/golden/dit_patch_small*.npz: tests/golden/make_golden_dit_patch.py).
+REFERENCE's own outputs (tests/golden/dit_patch_small*.npz: tests/golden/make_golden_dit_families.py patch).  Gates: the harness,
+tests/dit_family_gpu.py.
 
-* the suite's operand format at the reduced-DiT gates of test_gpu_dit_conv_ff.py: T(2.5e-3) at CFG 1, T(1.2e-2) at CFG 7;
-* the fp32 verification mode (gemm_dtype "fp32x") at 1e-4: what separates an indexing error (feature order, a frame or a row off by one, a
+* the suite's operand format at the reduced-DiT gates;
+* the fp32 verification mode (gemm_dtype "fp32x"): what separates an indexing error (feature order, a frame or a row off by one, a
   concat source frame per token) from rounding.  The generator asserts that each such mistake moves the output by at least 5e-2;
 * four cases again with the LayerNorm fusion off and with the fused to_q + cross-attention launch off, and through the fused sampler step;
 * per-block operand formats, conformer + convolutional feed-forward under the three opt-ins, fp8;
@@ -10,7 +11,6 @@ REFERENCE's own outputs (tests/golden/dit_patch_small*.npz: tests/golden/make_go
 * the C ABI: sat_dit_plan_set_patch after finalize, a t_len that is no multiple of the patch size.
 Measured errors, the reference's own rounded-operand figures (``<case>__r16_*``) and the gates: profiles/dit_patch_verification.txt.
 """
-import copy
 import ctypes
 import os
 import sys
@@ -20,59 +20,12 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
-import cases  # noqa: E402
 import dit_patch_cases as PC  # noqa: E402
-from util import FORMATS, SUITE, assert_close, rel_l2  # noqa: E402
+from dit_family_gpu import FP32X_GATE, Harness, generate, reduced_model  # noqa: E402
+from util import SUITE, rel_l2  # noqa: E402
 
-T = SUITE.tol
 pytestmark = pytest.mark.gpu
-
-_MODELS = {}
-_GOLD = []
-
-
-def _gold():
-    if not _GOLD:
-        _GOLD.append(cases.load("dit_patch_small"))
-    return _GOLD[0]
-
-
-def _model(cfg_name, dev):
-    if cfg_name not in _MODELS:
-        from stable_audio_tools.models import _init
-        from stable_audio_tools.models.dit import DiffusionTransformer
-        with _init.skip_init():
-            m = DiffusionTransformer(**PC.CONFIGS[cfg_name], **PC.PRODUCT_KWARGS)
-        m.load_state_dict(PC.synth_weights(cfg_name, m.state_dict(), 0), strict=True)
-        _MODELS[cfg_name] = m.to(dev).eval()
-    return _MODELS[cfg_name]
-
-
-def _inputs(name, dev):
-    x, t, kw = PC.forward_kwargs(name)
-    to = lambda v: v.to(dev) if torch.is_tensor(v) else v
-    return to(x), to(t), {k: to(v) for k, v in kw.items()}
-
-
-def _run(name, dev, dtype, ln_fold=True, cross_fusion=True, formats=None):
-    m = _model(PC.CASES[name][0], dev)
-    m.set_gemm_dtype(dtype).set_layernorm_fusion(ln_fold).set_cross_attention_fusion(cross_fusion).set_block_gemm_dtypes(formats)
-    try:
-        x, t, kw = _inputs(name, dev)
-        out = m(x, t, **kw)
-        torch.cuda.synchronize()
-    finally:
-        m.set_block_gemm_dtypes(None).set_gemm_dtype(SUITE.gemm_dtype).set_layernorm_fusion(True).set_cross_attention_fusion(True)
-    return out
-
-
-def _gate(name, fmt=SUITE):
-    return fmt.tol(2.5e-3) if PC.CASES[name][3] == 1.0 else fmt.tol(1.2e-2)
-
-
-def _r16(name, fmt=SUITE):
-    """What 16-bit operands of the Linears / convs alone cost the REFERENCE on this case (computed on the CPU by the generator)."""
-    return rel_l2(_gold()[f"{name}__r16_{fmt.gemm_dtype}"], _gold()[name])
+H = Harness(PC.FAMILY)
 
 
 @pytest.mark.parametrize("name", list(PC.CASES))
@@ -83,10 +36,7 @@ def test_patch_vs_reference(dev, name):
     LayerNorm or the cross-attention fusion; without CFG this 8-channel, 10-rows-per-sequence model is 3.06e-3 from its own fp32x output in
     bf16 against 1.99e-3 for p2: 1.5 times as sensitive to operand rounding, in fp16 alike, and CFG 7 multiplies it (the reference with
     bf16-rounded operands: 1.96e-2).  The gate is the one set for this test and is kept."""
-    got = _run(name, dev, SUITE.gemm_dtype)
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit patch {name}, {SUITE.gemm_dtype}] rel-L2 vs reference {e:.2e} (gate {_gate(name):.1e}; reference with rounded operands {_r16(name):.2e})")
-    assert_close(f"{name} ({SUITE.gemm_dtype}) vs reference", got, _gold()[name], _gate(name))
+    H.check_vs_reference(dev, name, SUITE.gemm_dtype, H.gate(name), rounded=True)
 
 
 @pytest.mark.parametrize("name", list(PC.CASES))
@@ -95,12 +45,9 @@ def test_patch_fp32_vs_reference(dev, name):
         # the fp32 verification kernels keep 64-channel heads, with or without patches (DiffusionTransformer._check_options): the
         # 128-channel-head case has its 16-bit gates above and the boundary kernels their fp32 gates on every other case
         with pytest.raises(NotImplementedError, match="dim_heads=128"):
-            _run(name, dev, "fp32x")
+            H.run(name, dev, "fp32x")
         return
-    got = _run(name, dev, "fp32x")
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit patch {name}, fp32x] rel-L2 vs reference {e:.2e} (gate 1.0e-04)")
-    assert_close(f"{name} (fp32x) vs reference", got, _gold()[name], 1e-4)
+    H.check_vs_reference(dev, name, "fp32x", FP32X_GATE)
 
 
 OTHER_PATHS = ["p2_cfg7_T78", "p2_adaln_cfg7_T78", "p2_prepend_cfg7_T78", "p2_concat_cfg7_T78"]
@@ -109,49 +56,19 @@ OTHER_PATHS = ["p2_cfg7_T78", "p2_adaln_cfg7_T78", "p2_prepend_cfg7_T78", "p2_co
 @pytest.mark.parametrize("path", ["ln_fold_off", "cross_fusion_off"])
 @pytest.mark.parametrize("name", OTHER_PATHS)
 def test_patch_on_the_other_launch_paths(dev, name, path):
-    got = _run(name, dev, SUITE.gemm_dtype, ln_fold=path != "ln_fold_off", cross_fusion=path != "cross_fusion_off")
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit patch {name}, {SUITE.gemm_dtype}, {path}] rel-L2 vs reference {e:.2e} (gate {_gate(name):.1e})")
-    assert_close(f"{name} ({SUITE.gemm_dtype}, {path}) vs reference", got, _gold()[name], _gate(name))
+    H.check_vs_reference(dev, name, SUITE.gemm_dtype, H.gate(name), path, ln_fold=path != "ln_fold_off", cross_fusion=path != "cross_fusion_off")
 
 
 @pytest.mark.parametrize("dtype", ["suite", "fp32x"])
 @pytest.mark.parametrize("name", OTHER_PATHS)
 def test_fused_denoise_matches_forward(dev, name, dtype):
-    """prepare_generation + denoise (one sat_dit_denoise_cfg per step) == VDenoiser(forward), at the gates of test_gpu_dit_conv_ff.py: 1e-5 in
-    fp32; T(2e-2) in the suite's format, where the two round c_in * x at different points and CFG 7 amplifies the roundings that flip.  c_in
-    scales the latent channels only: on p2_concat an xscale on the concat channels shows here."""
-    cfg_name, _, _, cfg_scale = PC.CASES[name]
-    fmt = SUITE.gemm_dtype if dtype == "suite" else dtype
-    gate = T(2e-2) if dtype == "suite" else 1e-5
-    m = _model(cfg_name, dev)
-    m.set_gemm_dtype(fmt)
-    try:
-        x, _, kw = _inputs(name, dev)
-        c, g, pc, cat = kw["cross_attn_cond"], kw["global_embed"], kw["prepend_cond"], kw["input_concat_cond"]
-        for sigma in (0.7, 12.0):
-            c_skip, c_out, c_in = 1.0 / (sigma ** 2 + 1), -sigma / (sigma ** 2 + 1) ** 0.5, 1.0 / (sigma ** 2 + 1) ** 0.5
-            t = torch.full((x.shape[0],), float(torch.atan(torch.tensor(sigma, dtype=torch.float64)) / torch.pi * 2), device=dev)
-            want = m(x * c_in, t, cross_attn_cond=c, global_embed=g, prepend_cond=pc, input_concat_cond=cat, cfg_scale=cfg_scale) * c_out + x * c_skip
-            m.prepare_generation(c, g, cfg_scale, prepend_cond=pc, input_concat_cond=cat)
-            got = m.denoise(x, sigma, cfg_scale=cfg_scale)
-            torch.cuda.synchronize()
-            e = rel_l2(got, want)
-            print(f"\n[fused denoise {name}, {fmt}, sigma {sigma}] rel-L2 vs VDenoiser(forward) {e:.2e} (gate {gate:.1e})")
-            assert torch.isfinite(got).all()
-            assert e <= gate, f"{name} {fmt} sigma {sigma}: fused denoise vs VDenoiser(forward) rel-L2 {e:.3e} > {gate:.1e}"
-    finally:
-        m.set_gemm_dtype(SUITE.gemm_dtype)
+    """c_in scales the latent channels only: on p2_concat an xscale on the concat channels shows here."""
+    H.check_fused_denoise(dev, name, dtype)
 
 
 def test_patch_with_per_block_formats(dev):
-    """[fp16, bf16, fp16] on p2 at CFG 7, gated at the bf16 gate, the coarsest format in the plan."""
-    name, bf16 = "p2_cfg7_T78", FORMATS[0]
-    got = _run(name, dev, "fp16", formats=["fp16", "bf16", "fp16"])
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit patch {name}, fp16 / bf16 / fp16] rel-L2 vs reference {e:.2e} (gate {_gate(name, bf16):.1e})")
-    assert_close(f"{name} (fp16 / bf16 / fp16) vs reference", got, _gold()[name], _gate(name, bf16))
-    assert not torch.equal(got, _run(name, dev, "fp16")), "the per-block formats changed no bit: block 1 did not run in bf16"
+    """[fp16, bf16, fp16] on p2 at CFG 7."""
+    H.check_per_block_formats(dev, "p2_cfg7_T78")
 
 
 @pytest.mark.parametrize("mode", ["fp8", "fp8-all"])
@@ -159,21 +76,17 @@ def test_patch_fp8(dev, mode):
     """The e4m3 modes take a patchified model (the block kernels are the P = 1 plan's on half the rows).  Gate: what
     tests/test_gpu_models.py::test_dit_fp8_gemm_mode applies to the reduced DiT against the fp32 reference without CFG, 3e-2."""
     name = "p2_cfg1_T64"
-    got = _run(name, dev, mode)
-    e = rel_l2(got, _gold()[name])
-    print(f"\n[dit patch {name}, {mode}] rel-L2 vs reference {e:.2e} (gate 3.0e-02)")
-    assert torch.isfinite(got).all()
-    assert_close(f"{name} ({mode}) vs reference", got, _gold()[name], 3e-2)
+    assert torch.isfinite(H.check_vs_reference(dev, name, mode, 3e-2)).all()
 
 
 def test_range_and_residual_reports_run_on_a_patch_plan(dev):
     name = "p2_cfg1_T64"
-    m = _model("p2", dev)
-    base = _run(name, dev, SUITE.gemm_dtype)
+    m = H.model("p2", dev)
+    base = H.run(name, dev, SUITE.gemm_dtype)
     m.activation_range_report(True)
     m.residual_stream_report(True)
     try:
-        got = _run(name, dev, SUITE.gemm_dtype)
+        got = H.run(name, dev, SUITE.gemm_dtype)
     finally:
         resid = m.residual_stream_report(False)
         rows = m.activation_range_report(False)
@@ -189,8 +102,8 @@ def test_patch_c_abi_state_and_bad_length(dev):
     not a bit of `out` is written."""
     from stable_audio_tools import _hip
     lib = _hip.lib()
-    m = _model("p2", dev)
-    x, t, kw = _inputs("p2_cfg1_T64", dev)
+    m = H.model("p2", dev)
+    x, t, kw = H.inputs("p2_cfg1_T64", dev)
     m(x, t, **kw)            # plan, context and workspace for bf = 2
     plan = m._plan
     opts = _hip.SatDitPatchOptions(2)
@@ -215,35 +128,19 @@ def test_config_driven_model_generates(dev):
     """A config with patch_size 2 and "allow_patch_size": true builds through create_model_from_config, loads a reference-layout state dict
     with strict=True and generates through generate_diffusion_cond; the same seed with the project_in columns in (p c) order gives another
     result, and a sample_size that is no whole number of patches is refused before sampling."""
-    import stable_audio_tools as S
-    from stable_audio_tools import model_configs as MC, synthetic
+    from stable_audio_tools import synthetic
     from stable_audio_tools.inference.generation import generate_diffusion_cond
-    from stable_audio_tools.models import _init
-    cfg = copy.deepcopy(MC.reduced(MC.stable_audio_open_1_0()))
-    dc = cfg["model"]["diffusion"]["config"]
-    dc.update(patch_size=2, allow_patch_size=True)
-    with _init.skip_init():
-        model = S.create_model_from_config(cfg)
+    cfg, model = reduced_model(patch_size=2, allow_patch_size=True)
     sd = synthetic.synth_state_dict(model.state_dict(), 0)
-    assert sd["model.model.transformer.project_in.weight"].shape[1] == 2 * dc["io_channels"]
+    assert sd["model.model.transformer.project_in.weight"].shape[1] == 2 * cfg["model"]["diffusion"]["config"]["io_channels"]
     wrong = dict(sd)
     wrong["model.model.transformer.project_in.weight"] = PC.in_columns_pc(
         {"transformer.project_in.weight": sd["model.model.transformer.project_in.weight"]}, 2)["transformer.project_in.weight"]
-    b, steps, t_len = 1, 8, 16
+    steps, t_len = 8, 16
     ratio = cfg["model"]["pretransform"]["config"]["downsampling_ratio"]
     assert model.min_input_length == 2 * ratio
-    audio = []
-    for weights in (sd, wrong):
-        model.load_state_dict(weights, strict=True)
-        model = model.to(dev).eval()
-        cond = model.conditioner([{"seconds_start": 0, "seconds_total": 12}])
-        cond["prompt"] = (synthetic.synth_input("prompt", (b, 128, dc["cond_token_dim"]), 1).to(dev), torch.ones(b, 128, device=dev))
-        cond = {k: cond[k] for k in ("prompt", "seconds_start", "seconds_total")}
-        audio.append(generate_diffusion_cond(model, steps=steps, cfg_scale=7.0, conditioning_tensors=cond, sample_size=t_len * ratio, seed=3,
-                                             device=str(dev), sampler_type="dpmpp-3m-sde", sigma_min=0.3, sigma_max=500))
-        torch.cuda.synchronize()
-        assert audio[-1].shape == (b, 2, t_len * ratio) and torch.isfinite(audio[-1]).all() and float(audio[-1].abs().max()) > 0
-    e = rel_l2(audio[0], audio[1])
+    (a0, cond), (a1, _) = (generate(model, cfg, dev, weights, steps=steps, seed=3, t_len=t_len) for weights in (sd, wrong))
+    e = rel_l2(a0, a1)
     print(f"\n[dit patch generate, 8 steps] rel-L2 between the model and its project_in columns in (p c) order {e:.2e}")
     assert e > 1e-3, f"permuting the project_in columns moved the audio by {e:.2e} only"
     with pytest.raises(ValueError, match="patch_size = 2"):

@@ -10,30 +10,10 @@ Synthetic weights and random operands (the time does not depend on the values). 
     python tools/dit_block_options_timing.py --out profiles/dit_block_options_timing.txt
 """
 import argparse
-import gc
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "friendly-stable-audio-tools_amd"))
-
-
-def _windows(fn, a):
-    for _ in range(a.warmup):
-        fn()
-    per = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.window):
-            fn()
-        e1.record()
-        e1.synchronize()
-        per.append(e0.elapsed_time(e1) / a.window)
-    return statistics.median(per), min(per), max(per)
+import dit_step_timing as ST          # (puts the package on sys.path)
 
 
 def dwconv_rows(a, dev):
@@ -52,7 +32,7 @@ def dwconv_rows(a, dev):
         for variant, name in ((0, "16-row tile + halo in registers (the plan's)"), (1, "one row per workgroup (17 reads out of L2)"), (2, "32-row tile + halo staged in LDS"),
                               (3, "8-row tile + halo in registers")):
             call = lambda: _hip.check(fn(_hip.ptr(x), _hip.ptr(w), _hip.ptr(gamma), _hip.ptr(beta), _hip.ptr(y), b, s, d, variant, _hip.stream()))
-            med, lo, hi = _windows(call, a)
+            med, lo, hi = ST.windows(call, a)
             rows.append(f"dwconv_ln_silu {sfx:4s} M {b * s} D {d}  {name:46s} {1e3 * med:7.1f} us / launch  (min {1e3 * lo:.1f}, max {1e3 * hi:.1f})   "
                         f"{nbytes / med / 1e6:7.1f} GB/s of the {nbytes / 1e6:.1f} MB it has to move")
             print(rows[-1], flush=True)
@@ -60,49 +40,23 @@ def dwconv_rows(a, dev):
 
 
 def step_rows(a, dev):
-    from stable_audio_tools import model_configs as MC, synthetic
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
-    base = MC.stable_audio_open_1_0()["model"]["diffusion"]["config"]
-    x = synthetic.synth_input("x", (1, 64, a.t_len), 1).to(dev)
-    c = synthetic.synth_input("c", (1, 130, base["cond_token_dim"]), 2).to(dev)
-    g = synthetic.synth_input("g", (1, base["global_cond_dim"]), 3).to(dev)
     rows, ref = [], None
     for name, extra in (("as shipped", {}), ("conformer=True", dict(conformer=True)), ('ff_kwargs={"glu": False}', dict(ff_kwargs={"glu": False})),
                         ("remove_norms=True", dict(remove_norms=True))):
-        with _init.skip_init():
-            m = DiffusionTransformer(**dict(base, **extra), allow_block_options=True)
-        m.load_state_dict(synthetic.synth_state_dict(m.state_dict(), 0))
-        m = m.to(dev).eval()
-        if a.dtype:
-            m.set_gemm_dtype(a.dtype)
-        m.prepare_generation(c, g, 7.0)
-        med, lo, hi = _windows(lambda: m.denoise(x, 1.0, cfg_scale=7.0), a)
+        med, lo, hi = ST.step_windows(dev, a, extra, dict(allow_block_options=True))
         ref = med if ref is None else ref
         rows.append(f"step  {name:26s} {med:8.3f} ms  (min {lo:.3f}, max {hi:.3f})   {1e3 * (med - ref):+8.1f} us vs as shipped ({100 * (med / ref - 1):+.2f} %)")
         print(rows[-1], flush=True)
-        del m
-        gc.collect()
-        torch.cuda.empty_cache()
     return rows
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--t-len", type=int, default=1024)
-    ap.add_argument("--window", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--dtype", default=None, help="gemm_dtype of the step rows (default: the package default)")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = ST.add_common_args(argparse.ArgumentParser()).parse_args()
     dev = torch.device("cuda:0")
     lines = dwconv_rows(a, dev) + step_rows(a, dev)
     head = (f"TransformerBlock options, cost: {torch.cuda.get_device_name(0)}; {a.window} launches / steps per event pair, median of {a.reps} windows; step rows: "
             f"full-depth DiT (24 blocks, D 1536), T = {a.t_len}, one prompt, CFG 7 (2 sequences), gemm_dtype {a.dtype or 'package default'}\n")
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(head + "\n".join(lines) + "\n")
+    ST.write_report(a.out, head, lines)
 
 
 if __name__ == "__main__":

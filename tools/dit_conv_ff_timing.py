@@ -11,31 +11,14 @@ Synthetic weights and random operands (the time does not depend on the values). 
 """
 import argparse
 import ctypes
-import gc
 import os
-import statistics
 import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "friendly-stable-audio-tools_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import dit_step_timing as ST          # (puts the package on sys.path)
 
-
-def _windows(fn, a):
-    for _ in range(a.warmup):
-        fn()
-    per = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.window):
-            fn()
-        e1.record()
-        e1.synchronize()
-        per.append(e0.elapsed_time(e1) / a.window)
-    return statistics.median(per), min(per), max(per)
+sys.path.insert(0, os.path.join(ST.ROOT, "tests", "golden"))
 
 
 def gemm_rows(a, dev):
@@ -55,7 +38,7 @@ def gemm_rows(a, dev):
         slab = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dev)
         fn = getattr(lib, f"sat_gemm_{sfx}_f32_ws")
         lin = lambda: _hip.check(fn(_hip.ptr(x), _hip.ptr(w16), _hip.ptr(bias), _hip.ptr(c), m, n, k, 1, 0, _hip.ptr(slab), need.value, _hip.stream()))
-        med, lo, hi = _windows(lin, a)
+        med, lo, hi = ST.windows(lin, a)
         ref = med
         rows.append(f"FF-out {sfx:4s} M {m} N {n} K {k}  Linear, the shipped plan's GEMM route          {1e3 * med:8.1f} us / launch  (min {1e3 * lo:.1f}, max {1e3 * hi:.1f})   "
                     f"{2.0 * m * n * k / med / 1e9:7.1f} TFLOP/s")
@@ -69,7 +52,7 @@ def gemm_rows(a, dev):
             call = lambda wp: _hip.check(lib.sat_ff_conv(fmt, _hip.ptr(x), wp, _hip.ptr(bias), 0, _hip.ptr(c), None, b, s, n, k, taps, _hip.ptr(ws),
                                                          need.value, _hip.stream()))
             call(_hip.ptr(w))
-            med, lo, hi = _windows(lambda: call(None), a)
+            med, lo, hi = ST.windows(lambda: call(None), a)
             rows.append(f"FF-out {sfx:4s} M {m} N {n} K {k}  convolution GEMM k = {taps}, weight packed once          {1e3 * med:8.1f} us / launch  (min {1e3 * lo:.1f}, max {1e3 * hi:.1f})   "
                         f"{2.0 * m * n * k * taps / med / 1e9:7.1f} TFLOP/s, {med / ref:.2f} x the Linear")
             print(rows[-1], flush=True)
@@ -78,53 +61,29 @@ def gemm_rows(a, dev):
 
 def step_rows(a, dev):
     import cases
-    from stable_audio_tools import model_configs as MC, synthetic
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
+    from stable_audio_tools import model_configs as MC
     full = MC.stable_audio_open_1_0()["model"]["diffusion"]["config"]
     rows = []
-    for label, base, t_len, lc in (("reduced DiT (3 blocks, D 256)", dict(cases.SMALL_DIT), 64, 130), ("full-depth DiT (24 blocks, D 1536)", full, a.t_len, 130)):
-        x = synthetic.synth_input("x", (1, 64, t_len), 1).to(dev)
-        c = synthetic.synth_input("c", (1, lc, base["cond_token_dim"]), 2).to(dev)
-        g = synthetic.synth_input("g", (1, base["global_cond_dim"]), 3).to(dev)
+    for label, base, t_len in (("reduced DiT (3 blocks, D 256)", dict(cases.SMALL_DIT), 64), ("full-depth DiT (24 blocks, D 1536)", full, a.t_len)):
         ref = {}
         for name, ff in (("Linear, glu (as shipped)", {}), ("use_conv k 3, glu", dict(use_conv=True)), ("Linear, glu=False", dict(glu=False)),
                          ("use_conv k 3, glu=False", dict(use_conv=True, glu=False))):
-            with _init.skip_init():
-                m = DiffusionTransformer(**dict(base, ff_kwargs=ff), allow_block_options=True, allow_conv_ff=True)
-            m.load_state_dict(synthetic.synth_state_dict(m.state_dict(), 0))
-            m = m.to(dev).eval()
-            if a.dtype:
-                m.set_gemm_dtype(a.dtype)
-            m.prepare_generation(c, g, 7.0)
-            med, lo, hi = _windows(lambda: m.denoise(x, 1.0, cfg_scale=7.0), a)
+            med, lo, hi = ST.step_windows(dev, a, dict(ff_kwargs=ff), dict(allow_block_options=True, allow_conv_ff=True), base=base, t_len=t_len)
             glu = ff.get("glu", True)
             ref.setdefault(glu, med)
             rows.append(f"step  {label:36s} T {t_len:5d}  {name:26s} {med:8.3f} ms  (min {lo:.3f}, max {hi:.3f})   "
                         f"{1e3 * (med - ref[glu]):+9.1f} us vs the Linear model ({100 * (med / ref[glu] - 1):+.1f} %)")
             print(rows[-1], flush=True)
-            del m
-            gc.collect()
-            torch.cuda.empty_cache()
     return rows
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--t-len", type=int, default=1024)
-    ap.add_argument("--window", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--dtype", default=None, help="gemm_dtype of the step rows (default: the package default)")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = ST.add_common_args(argparse.ArgumentParser()).parse_args()
     dev = torch.device("cuda:0")
     lines = gemm_rows(a, dev) + step_rows(a, dev)
     head = (f"Convolutional feed-forward, cost: {torch.cuda.get_device_name(0)}; {a.window} launches / steps per event pair, median of {a.reps} windows; "
             f"step rows: one prompt, CFG 7 (2 sequences), gemm_dtype {a.dtype or 'package default'}\n")
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(head + "\n".join(lines) + "\n")
+    ST.write_report(a.out, head, lines)
 
 
 if __name__ == "__main__":

@@ -10,30 +10,10 @@ Synthetic weights and random operands (the time does not depend on the values). 
     python tools/dit_head_dim_timing.py --out profiles/dit_head_dim_timing.txt
 """
 import argparse
-import gc
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "friendly-stable-audio-tools_amd"))
-
-
-def _windows(fn, a):
-    for _ in range(a.warmup):
-        fn()
-    per = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.window):
-            fn()
-        e1.record()
-        e1.synchronize()
-        per.append(e0.elapsed_time(e1) / a.window)
-    return statistics.median(per), min(per), max(per)
+import dit_step_timing as ST          # (puts the package on sys.path)
 
 
 def attention_rows(a, dev, f16):
@@ -54,7 +34,7 @@ def attention_rows(a, dev, f16):
         out = torch.empty((b * s, h * hd), dtype=dtype, device=dev)
         fn = getattr(lib, fn_name)
         call = lambda: _hip.check(fn(_hip.ptr(q), _hip.ptr(k), _hip.ptr(vt), _hip.ptr(out), b, h, h, s, s, s_pad, k_pad, _hip.stream()))
-        med, lo, hi = _windows(call, a)
+        med, lo, hi = ST.windows(call, a)
         flops = 4.0 * b * h * s * s * hd
         rows.append(f"attention {sfx}  {name}  2 x S 1025: {1e3 * med:8.1f} us / launch  (min {1e3 * lo:.1f}, max {1e3 * hi:.1f})   {flops / med / 1e9:7.1f} TFLOP/s")
         print(rows[-1], flush=True)
@@ -62,50 +42,23 @@ def attention_rows(a, dev, f16):
 
 
 def step_rows(a, dev):
-    from stable_audio_tools import model_configs as MC, synthetic
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
-    base = MC.stable_audio_open_1_0()["model"]["diffusion"]["config"]
-    x = synthetic.synth_input("x", (1, 64, a.t_len), 1).to(dev)
-    c = synthetic.synth_input("c", (1, 130, base["cond_token_dim"]), 2).to(dev)
-    g = synthetic.synth_input("g", (1, base["global_cond_dim"]), 3).to(dev)
     rows, ref = [], None
     for name, heads, fused in (("24 heads of 64, fusions off (like for like)", 24, False), ("12 heads of 128 (staged route)", 12, False),
                                ("24 heads of 64 as shipped (fold + fused cross)", 24, True)):
-        with _init.skip_init():
-            m = DiffusionTransformer(**dict(base, num_heads=heads))
-        m.load_state_dict(synthetic.synth_state_dict(m.state_dict(), 0))
-        m = m.to(dev).eval()
-        if a.dtype:
-            m.set_gemm_dtype(a.dtype)
-        m.set_layernorm_fusion(fused).set_cross_attention_fusion(fused)
-        m.prepare_generation(c, g, 7.0)
-        med, lo, hi = _windows(lambda: m.denoise(x, 1.0, cfg_scale=7.0), a)
+        med, lo, hi = ST.step_windows(dev, a, dict(num_heads=heads), before_plan=lambda m: m.set_layernorm_fusion(fused).set_cross_attention_fusion(fused))
         ref = med if ref is None else ref
         rows.append(f"step  {name:48s} {med:8.3f} ms  (min {lo:.3f}, max {hi:.3f})   {1e3 * (med - ref):+8.1f} us vs like for like ({100 * (med / ref - 1):+.2f} %)")
         print(rows[-1], flush=True)
-        del m
-        gc.collect()
-        torch.cuda.empty_cache()
     return rows
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--t-len", type=int, default=1024)
-    ap.add_argument("--window", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--dtype", default=None, help="gemm_dtype of the step rows (default: the package default)")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = ST.add_common_args(argparse.ArgumentParser()).parse_args()
     dev = torch.device("cuda:0")
     lines = attention_rows(a, dev, True) + attention_rows(a, dev, False) + step_rows(a, dev)
     head = (f"128-channel heads, cost: {torch.cuda.get_device_name(0)}; {a.window} launches / steps per event pair, median of {a.reps} windows; step rows: "
             f"full-depth DiT (24 blocks, D 1536), T = {a.t_len}, one prompt, CFG 7 (2 sequences), gemm_dtype {a.dtype or 'package default'}\n")
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(head + "\n".join(lines) + "\n")
+    ST.write_report(a.out, head, lines)
 
 
 if __name__ == "__main__":

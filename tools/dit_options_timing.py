@@ -9,15 +9,10 @@ steps.  Weights are the synthetic ones of the benchmark (the time does not depen
     python tools/dit_options_timing.py --out profiles/dit_options_timing.txt
 """
 import argparse
-import gc
-import os
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "friendly-stable-audio-tools_amd"))
+import dit_step_timing as ST          # (puts the package on sys.path)
 
 VARIANTS = {
     "shipped config": {},
@@ -29,55 +24,18 @@ VARIANTS = {
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--t-len", type=int, default=1024)
-    ap.add_argument("--window", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--dtype", default=None, help="gemm_dtype (default: the package default)")
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    from stable_audio_tools import model_configs as MC, synthetic
-    from stable_audio_tools.models import _init
-    from stable_audio_tools.models.dit import DiffusionTransformer
+    a = ST.add_common_args(argparse.ArgumentParser()).parse_args()
     dev = torch.device("cuda:0")
-    base = MC.stable_audio_open_1_0()["model"]["diffusion"]["config"]
-    x = synthetic.synth_input("x", (1, 64, a.t_len), 1).to(dev)
-    c = synthetic.synth_input("c", (1, 130, base["cond_token_dim"]), 2).to(dev)
-    g = synthetic.synth_input("g", (1, base["global_cond_dim"]), 3).to(dev)
     lines, ref = [], None
     for name, extra in VARIANTS.items():
-        with _init.skip_init():
-            m = DiffusionTransformer(**base, **extra)
-        m.load_state_dict(synthetic.synth_state_dict(m.state_dict(), 0))
-        m = m.to(dev).eval()
-        if a.dtype:
-            m.set_gemm_dtype(a.dtype)
-        m.prepare_generation(c, g, 7.0)
-        for _ in range(a.warmup):
-            m.denoise(x, 1.0, cfg_scale=7.0)
-        per_step = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.window):
-                m.denoise(x, 1.0, cfg_scale=7.0)
-            e1.record()
-            e1.synchronize()
-            per_step.append(e0.elapsed_time(e1) / a.window)
-        med = statistics.median(per_step)
+        med, lo, hi = ST.step_windows(dev, a, extra)
         ref = med if ref is None else ref
-        lines.append(f"{name:34s} {med:8.3f} ms / step  (min {min(per_step):.3f}, max {max(per_step):.3f})   {1e3 * (med - ref):+8.1f} us vs the shipped config"
+        lines.append(f"{name:34s} {med:8.3f} ms / step  (min {lo:.3f}, max {hi:.3f})   {1e3 * (med - ref):+8.1f} us vs the shipped config"
                      f"  ({100 * (med / ref - 1):+.2f} %)")
         print(lines[-1], flush=True)
-        del m
-        gc.collect()
-        torch.cuda.empty_cache()
     head = (f"DiT options, cost per sampler step: full-size DiT, T = {a.t_len}, one prompt, CFG 7 (2 sequences), gemm_dtype "
             f"{a.dtype or 'package default'}, {torch.cuda.get_device_name(0)}\n{a.window} steps per event pair, median of {a.reps} windows\n")
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(head + "\n".join(lines) + "\n")
+    ST.write_report(a.out, head, lines)
 
 
 if __name__ == "__main__":
