@@ -52,7 +52,8 @@ struct sat_dit_plan {
     bool finalized = false;
     int inner = 0;          // FF inner dim
     int kvh_cross = 0;
-    int hd = 64;            // channels per attention head, embed_dim / num_heads: 64, or 128 = the staged route (Forward::block)
+    int hd = 64;            // channels per attention head, embed_dim / num_heads: 64, or 128 / 32 / 96 = the staged route (Forward::block)
+    bool staged() const { return hd != 64; }
     DevBuf arena;
     std::vector<LayerW> layers;
     float *ts_w, *te0_w, *te0_b, *te2_w, *te2_b;
@@ -250,10 +251,11 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         SAT_TRY(copy_f32(p, ar, "to_prepend_embed.0.weight", (int64_t)D * p->prepend_dim, &p->pe0_w, s));
         SAT_TRY(copy_f32(p, ar, "to_prepend_embed.2.weight", (int64_t)D * D, &p->pe2_w, s));
     }
-    // RotaryEmbedding(max(dim_heads / 2, 32)): 16 frequencies for 64-channel heads, 32 for 128-channel ones (their table: the end of build)
-    const bool hd128 = p->hd == 128;
-    if (!hd128 && p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 16, &p->inv_freq, s));
-    else if (!hd128) {      // frequencies 0: rope_table below comes out as cos 1 / sin 0 and the rotating epilogues are the identity
+    // RotaryEmbedding(max(dim_heads / 2, 32)): 16 frequencies for 64-channel heads; 32 for 128-channel ones, 16 for 32 and 24 for 96 (the
+    // staged route: its table is placed at the end of build)
+    const bool staged = p->staged();
+    if (!staged && p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 16, &p->inv_freq, s));
+    else if (!staged) {      // frequencies 0: rope_table below comes out as cos 1 / sin 0 and the rotating epilogues are the identity
         p->inv_freq = (float*)ar.take(16 * 4);
         if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, 16 * 4, s));
     }
@@ -262,7 +264,7 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
     p->win_eff = (float*)ar.take((size_t)D * Ci * pt * 4);
     p->wout_eff = (float*)ar.take((size_t)D * C * pt * 4);
     const int smax = seq_len(p, p->tokens(c.max_seq_len), p->max_prep);
-    if (!hd128) {
+    if (!staged) {
         p->rope_cos = (float*)ar.take((size_t)smax * 16 * 4);
         p->rope_sin = (float*)ar.take((size_t)smax * 16 * 4);
     }
@@ -282,7 +284,7 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
             SAT_TRY(glue_fold_in(win, wpre, p->win_eff, D, Ci, s));
             SAT_TRY(glue_fold_out(wout, wpost, p->wout_eff, D, C, s));
         }
-        if (!hd128) SAT_TRY(sat_launch_rope_table(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
+        if (!staged) SAT_TRY(sat_launch_rope_table(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
         if (p->pos_emb == SAT_DIT_POS_SINUSOIDAL) {     // inv_freq is not in the state dict (persistent=False), the learnt scale is
             const float* sc;
             SAT_TRY(get_tensor(p, "transformer.pos_emb.scale", 1, &sc));
@@ -348,15 +350,19 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         if (conv) SAT_TRY(pack_conv(p, ar, pf, "ff.ff.2.weight", b2, FAM_FF2, l, D, inner, &L.ff2, s));
         else SAT_TRY(pack("ff.ff.2.weight", b2, FAM_FF2, D, inner, 0, nullptr, nullptr, &L.ff2));
     }
-    if (hd128) {      // behind everything a 64-channel plan places: the 32 frequencies and the [smax][32] table the head split rotates with
-        if (p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 32, &p->inv_freq, s));
+    if (staged) {      // behind everything a 64-channel plan places: the frequencies and the [smax][pairs] table the head split rotates with
+        const int pairs = sat_rope_pairs(p->hd);      // 32 (128-channel heads), 16 (32), 24 (96)
+        if (p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", pairs, &p->inv_freq, s));
         else {
-            p->inv_freq = (float*)ar.take(32 * 4);
-            if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, 32 * 4, s));
+            p->inv_freq = (float*)ar.take(pairs * 4);
+            if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, pairs * 4, s));
         }
-        p->rope_cos = (float*)ar.take((size_t)smax * 32 * 4);
-        p->rope_sin = (float*)ar.take((size_t)smax * 32 * 4);
-        if (!ar.dry()) SAT_TRY(sat_launch_rope_table_hd128(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
+        p->rope_cos = (float*)ar.take((size_t)smax * pairs * 4);
+        p->rope_sin = (float*)ar.take((size_t)smax * pairs * 4);
+        if (!ar.dry()) {
+            if (p->hd == 128) SAT_TRY(sat_launch_rope_table_hd128(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
+            else SAT_TRY(sat_launch_rope_table_hdw(p->inv_freq, p->rope_cos, p->rope_sin, smax, p->hd, s));
+        }
     }
     return 0;
 }
@@ -374,7 +380,7 @@ struct Workspace {
     float* slab = nullptr;       // K-split scratch of the 8-phase FF-out GEMM (GemmArgs::slab), present where that schedule splits
     size_t slab_bytes = 0;
     float* f32_col = nullptr;    // fp32 verification mode of a plan with sat_dit_plan_set_ff_conv: [M, taps * max(D, inner)] row gather in front of sat_gemm_f32
-    float* qkv32 = nullptr;      // 128-channel heads: [M, 3D] fp32 output of to_qkv / [Mc, D] of the cross to_q in front of the head split
+    float* qkv32 = nullptr;      // staged route (128-, 32-, 96-channel heads): [M, 3D] fp32 output of to_qkv / [Mc, D] of the cross to_q in front of the head split
     size_t qkv_bytes;
     size_t total;
 };
@@ -429,7 +435,7 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     // round (SA-2.0 shape): its slabs live here, per workspace = per caller and stream
     w.slab_bytes = (c.gemm_dtype == 0 || c.gemm_dtype == 3) ? sat_gemm_ph8_slab_bytes(EPI_RESID, (int)M, D, p->inner) : 0;
     w.slab = w.slab_bytes ? (float*)ws.take(w.slab_bytes) : nullptr;
-    if (p->hd == 128) w.qkv32 = (float*)ws.take(M * (size_t)(3 * D) * 4);      // behind every buffer a 64-channel plan carves
+    if (p->staged()) w.qkv32 = (float*)ws.take(M * (size_t)(3 * D) * 4);      // behind every buffer a 64-channel plan carves
     w.total = ws.off;
     return w;
 }
@@ -511,6 +517,16 @@ struct Forward {
         return 0;
     }
 
+    // The two kernels of the staged route by head width: head_split.hip / attention_hd128.hip, or their siblings for 32 and 96 channels
+    float staged_qscale() const { return p->hd == 128 ? SAT_ATTN_QSCALE_HD128 : sat_attn_qscale(p->hd); }
+    int head_split(const float* x, const HeadsEpi& he, int seqs, int f16) const {
+        return p->hd == 128 ? sat_launch_head_split_hd128(x, he, seqs, s, f16) : sat_launch_head_split_hdw(x, he, p->hd, seqs, s, f16);
+    }
+    int attend(const op_t* q, const op_t* k, const op_t* vt, int seqs, int kvh, int sk, int sk_pad, int f16) const {
+        if (p->hd == 128) return sat_launch_attention_hd128(q, k, vt, w.AO, seqs, H, kvh, S, sk, Spad, sk_pad, s, f16);
+        return sat_launch_attention_hdw(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, sk, Spad, sk_pad, s, f16);
+    }
+
     int block(int l) const;
     int block_f32(int l) const;
     int attention_hd128(int l) const;
@@ -533,15 +549,27 @@ int Forward::block_f32(int l) const {
     };
     SAT_TRY(norm(L.pre_g, L.pre_b, M, m, m ? m + D : nullptr, S, ssg_ld));
     SAT_TRY(sat_launch_gemm_f32(A32, W32(L.qkv), nullptr, w.f32_wide, M, 3 * D, D, 3 * D, 0, nullptr, 1, 0, s));
-    SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
-    SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
+    // (32- and 96-channel heads: the same kernels with a head width; the launches of a 64-channel plan are what they were)
+    const int hd = p->hd;
+    if (hd == 64) {
+        SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
+        SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
+    } else {
+        SAT_TRY(sat_launch_split_heads_f32_w(w.f32_wide, Q32, K32, V32, M, S, 3, H, hd, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
+        SAT_TRY(sat_launch_attention_f32_w(Q32, K32, V32, AO32, bf, H, H, hd, S, S, s));
+    }
     SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.o), nullptr, w.X, M, D, D, D, 1, m ? m + 2 * D : nullptr, S, ssg_ld, s));
     if (bc > 0) {
         SAT_TRY(norm(L.cross_g, L.cross_b, Mc, nullptr, nullptr, 1, 0));
         SAT_TRY(sat_launch_gemm_f32(A32, W32(L.cq), nullptr, w.f32_wide, Mc, D, D, D, 0, nullptr, 1, 0, s));
-        SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
-        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lc * 64;
-        SAT_TRY(sat_launch_attention_f32(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, S, p->ctx_lc, s));
+        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lc * hd;
+        if (hd == 64) {
+            SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
+            SAT_TRY(sat_launch_attention_f32(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, S, p->ctx_lc, s));
+        } else {
+            SAT_TRY(sat_launch_split_heads_f32_w(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, hd, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
+            SAT_TRY(sat_launch_attention_f32_w(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, hd, S, p->ctx_lc, s));
+        }
         SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.co), nullptr, w.X, Mc, D, D, D, 1, nullptr, 1, 0, s));
     }
     if (p->conformer) {      // transformer.py:680-681, 697-698 (the launches of Forward::conformer in fp32)
@@ -572,10 +600,11 @@ int Forward::block_f32(int l) const {
     return sat_launch_gemm_f32(H32, W32(L.ff2), L.ff2.bias, w.X, M, D, inner, D, 1, m ? m + 5 * D : nullptr, S, ssg_ld, s);
 }
 
-// The two attention branches of a block with 128-channel heads, staged: the heads epilogues, the fused to_q + cross-attention launch and the
+// The two attention branches of a block with 128-, 32- or 96-channel heads, staged: the heads epilogues, the fused to_q + cross-attention launch and the
 // LayerNorm fold keep one head = one 64-column wave tile (gemm_bf16.hip), so each projection runs as a plain fp32-output GEMM into qkv32, the
-// head split (head_split.hip: qk_norm, rotation, pre-scale, one rounding) writes Q / K / V^T, and attention_hd128.hip attends.  Two more
-// launches and one fp32 round trip per attention than the 64-channel route
+// head split (head_split.hip: qk_norm, rotation, pre-scale, one rounding) writes Q / K / V^T, and attention_hd128.hip attends; for 32 and 96
+// channels their siblings head_split_hdw.hip / attention_hdw.hip (Forward::head_split / attend).  Two more launches and one fp32 round trip
+// per attention than the 64-channel route
 int Forward::attention_hd128(int l) const {
     const LayerW& L = p->layers[l];
     const float* m = mod(l);
@@ -587,14 +616,14 @@ int Forward::attention_hd128(int l) const {
     SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
     HeadsEpi he{};
     he.out[0] = w.Q; he.out[1] = w.K; he.out[2] = w.Vt;
-    he.kind[0] = 2 | 8 | qn; he.kind[1] = 2 | 4 | qn; he.kind[2] = 1 | 4; he.qscale = SAT_ATTN_QSCALE_HD128;
+    he.kind[0] = 2 | 8 | qn; he.kind[1] = 2 | 4 | qn; he.kind[2] = 1 | 4; he.qscale = staged_qscale();
     he.parts = 3; he.heads = H; he.S = S; he.Spad = Spad;
     he.rope_cos = p->rope_cos; he.rope_sin = p->rope_sin;
-    SAT_TRY(sat_launch_head_split_hd128(w.qkv32, he, bf, s, f16));
+    SAT_TRY(head_split(w.qkv32, he, bf, f16));
     SAT_TRY(range_heads(l, RS_Q, w.Q, bf));
     SAT_TRY(range_heads(l, RS_K, w.K, bf));
     SAT_TRY(range_heads(l, RS_V, w.Vt, bf));
-    SAT_TRY(sat_launch_attention_hd128(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, f16));
+    SAT_TRY(attend(w.Q, w.K, w.Vt, bf, H, S, Spad, f16));
     SAT_TRY(range(l, RS_ATTN_OUT, w.AO, (size_t)M * D, (size_t)M * D));
     SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
     if (bc > 0) {      // (the sequences behind bc have an all-zero context: Forward::block)
@@ -604,13 +633,12 @@ int Forward::attention_hd128(int l) const {
         g.C = w.qkv32; g.ldc = D;
         SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
         he = HeadsEpi{};
-        he.out[0] = w.Q; he.kind[0] = 8 | qn; he.qscale = SAT_ATTN_QSCALE_HD128;
+        he.out[0] = w.Q; he.kind[0] = 8 | qn; he.qscale = staged_qscale();
         he.parts = 1; he.heads = H; he.S = S; he.Spad = Spad;
-        SAT_TRY(sat_launch_head_split_hd128(w.qkv32, he, bc, s, f16));
+        SAT_TRY(head_split(w.qkv32, he, bc, f16));
         SAT_TRY(range_heads(l, RS_CROSS_Q, w.Q, bc));
-        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * 128;
-        SAT_TRY(sat_launch_attention_hd128(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, w.AO, bc, H, p->kvh_cross, S, p->ctx_lc, Spad,
-                                           p->ctx_lcpad, s, f16));
+        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * p->hd;
+        SAT_TRY(attend(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, bc, p->kvh_cross, p->ctx_lc, p->ctx_lcpad, f16));
         SAT_TRY(range(l, RS_CROSS_ATTN_OUT, w.AO, (size_t)Mc * D, (size_t)Mc * D));
         SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
     }
@@ -622,7 +650,7 @@ int Forward::block(int l) const {
     const float* m = mod(l);
     const int f16 = L.qkv.f16, qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
     auto mx_scales = [&](const Proj& out) { return out.kind == PROJ_FP8_MX ? w.AOs : nullptr; };      // the attention kernels write to_out's MXFP8 operand
-    if (p->hd == 128) {
+    if (p->staged()) {
         SAT_TRY(attention_hd128(l));
         return feed_forward(l);
     }
@@ -816,7 +844,20 @@ extern "C" int sat_dit_plan_create(const sat_dit_cfg* cfg, sat_dit_plan** out_pl
 }
 
 extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_bytes, sat_dit_plan** out_plan) {
+    return sat_dit_plan_create_ex(cfg_in, cfg_bytes, nullptr, 0, out_plan);
+}
+
+extern "C" int sat_dit_plan_create_ex(const sat_dit_cfg* cfg_in, size_t cfg_bytes, const sat_dit_create_options* options, size_t options_bytes,
+                                      sat_dit_plan** out_plan) {
     SAT_CHECK_ARG(cfg_in && out_plan, SAT_E_INVALID, "dit_plan_create: null argument");
+    sat_dit_create_options opt{};
+    if (options) {
+        SAT_CHECK_ARG(options_bytes == sizeof(sat_dit_create_options), SAT_E_INVALID,
+                      "dit_plan_create_ex: options_bytes %zu is not the size of this version's sat_dit_create_options (%zu)", options_bytes,
+                      sizeof(sat_dit_create_options));
+        opt = *options;
+        SAT_CHECK_ARG(opt.head_widths == 0 || opt.head_widths == 1, SAT_E_INVALID, "dit_plan_create_ex: head_widths must be 0 (64 / 128) or 1 (32 and 96 as well)");
+    }
     static_assert(sizeof(sat_dit_cfg) == SAT_DIT_CFG_BYTES_V5, "sat_dit_cfg layout");
     // (the one layout this library knows; when the struct grows again, the older sizes are accepted here and the fields behind them defaulted)
     SAT_CHECK_ARG(cfg_bytes == sizeof(sat_dit_cfg), SAT_E_INVALID, "dit_plan_create: sat_dit_cfg of %zu bytes; this library (ABI version %d) knows %zu",
@@ -824,9 +865,12 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
     sat_dit_cfg cfg_local{};
     memcpy(&cfg_local, cfg_in, cfg_bytes);
     const sat_dit_cfg* cfg = &cfg_local;
-    SAT_CHECK_ARG(cfg->embed_dim > 0 && cfg->num_heads > 0 && (cfg->embed_dim == cfg->num_heads * 64 || cfg->embed_dim == cfg->num_heads * 128),
-                  SAT_E_UNSUPPORTED, "dit_plan_create: dim_heads must be 64 or 128 (embed_dim %d, heads %d)", cfg->embed_dim, cfg->num_heads);
+    SAT_CHECK_ARG(cfg->embed_dim > 0 && cfg->num_heads > 0 && (cfg->embed_dim == cfg->num_heads * 64 || cfg->embed_dim == cfg->num_heads * 128 ||
+                                                               (opt.head_widths && (cfg->embed_dim == cfg->num_heads * 32 || cfg->embed_dim == cfg->num_heads * 96))),
+                  SAT_E_UNSUPPORTED, "dit_plan_create: dim_heads must be 64 or 128%s (embed_dim %d, heads %d)",
+                  opt.head_widths ? ", 32 or 96" : "; 32 and 96 through sat_dit_plan_create_ex with head_widths 1", cfg->embed_dim, cfg->num_heads);
     const int hd = cfg->embed_dim / cfg->num_heads;
+    const bool hdw = hd == 32 || hd == 96;
     SAT_CHECK_ARG(cfg->embed_dim % 128 == 0 && cfg->embed_dim <= 2048, SAT_E_UNSUPPORTED,
                   "dit_plan_create: embed_dim %d must be a multiple of 128 and <= 2048", cfg->embed_dim);
     // (the input / output projection kernels move 4 channels per lane: glue_output_proj checks the same at forward time)
@@ -843,12 +887,17 @@ extern "C" int sat_dit_plan_create_sized(const sat_dit_cfg* cfg_in, size_t cfg_b
     SAT_CHECK_ARG(cfg->global_cond_dim % 4 == 0, SAT_E_UNSUPPORTED, "dit_plan_create: global_cond_dim must be a multiple of 4");
     SAT_CHECK_ARG(cfg->gemm_dtype >= 0 && cfg->gemm_dtype <= 3, SAT_E_INVALID,
                   "dit_plan_create: gemm_dtype must be 0 (bf16), 1 (e4m3), 2 (fp32 verification) or 3 (fp16)");
+    // 32 / 96: the fp32 kernels take a head width, the MXFP8 attention output does not exist
+    SAT_CHECK_ARG(!hdw || cfg->gemm_dtype != 1, SAT_E_UNSUPPORTED, "dit_plan_create: dim_heads %d does not run with e4m3 operands (gemm_dtype 1)", hd);
     SAT_CHECK_ARG(cfg->gemm_dtype != 1 || cfg->embed_dim % 256 == 0, SAT_E_UNSUPPORTED, "dit_plan_create: gemm_dtype needs embed_dim %% 256 == 0");
     // the e4m3 attention outputs (MXFP8) and the fp32 verification kernels (a head row in registers: f32_ref.hip) are built for 64 channels
-    SAT_CHECK_ARG(hd == 64 || cfg->gemm_dtype == 0 || cfg->gemm_dtype == 3, SAT_E_UNSUPPORTED,
+    SAT_CHECK_ARG(hd != 128 || cfg->gemm_dtype == 0 || cfg->gemm_dtype == 3, SAT_E_UNSUPPORTED,
                   "dit_plan_create: dim_heads 128 runs with bf16 or fp16 operands only (gemm_dtype %d)", cfg->gemm_dtype);
-    SAT_CHECK_ARG(hd == 64 || (sat_launch_head_split_hd128 && sat_launch_attention_hd128 && sat_launch_rope_table_hd128), SAT_E_UNSUPPORTED,
+    SAT_CHECK_ARG(hd != 128 || (sat_launch_head_split_hd128 && sat_launch_attention_hd128 && sat_launch_rope_table_hd128), SAT_E_UNSUPPORTED,
                   "dit_plan_create: dim_heads 128: built without the 128-channel-head kernels");
+    SAT_CHECK_ARG(!hdw || (sat_launch_head_split_hdw && sat_launch_attention_hdw && sat_launch_rope_table_hdw && sat_launch_split_heads_f32_w &&
+                           sat_launch_attention_f32_w),
+                  SAT_E_UNSUPPORTED, "dit_plan_create: dim_heads %d: built without the 32- / 96-channel-head kernels", hd);
     SAT_CHECK_ARG(cfg->gemm_dtype == 1 || cfg->fp8_families == 0, SAT_E_INVALID,
                   "dit_plan_create: fp8_families = 0x%x with gemm_dtype %d (a caller built against an older sat_dit_cfg layout?)", cfg->fp8_families, cfg->gemm_dtype);
     SAT_CHECK_ARG(cfg->cross_attention == 0 || cfg->cross_attention == 1, SAT_E_INVALID, "dit_plan_create: cross_attention must be 0 (fused where it applies) or 1 (two kernels)");
@@ -960,7 +1009,8 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
     SAT_CHECK_ARG(bf > 0, SAT_E_INVALID, "dit_prepare_context: bf must be positive");
     SAT_CHECK_ARG(!cross || (cond && lc > 0), SAT_E_INVALID, "dit_prepare_context: model has cross-attention but no cond given");
     SAT_CHECK_ARG(!(global_cond && Dg == 0), SAT_E_INVALID, "dit_prepare_context: model has no global conditioning");
-    const int lcpad = cross ? (int)round_up(lc + 3, 64) : 0;
+    // (a multiple of the attention kernel's key tile: 64 keys, 128 with 32-channel heads -- attn_hdw_tiles.h)
+    const int lcpad = cross ? (int)round_up(lc + 3, p->hd == 32 ? sat_attn_hdw_key_tile(32) : 64) : 0;
     const int R = bf * lc;
     // layout of the context buffer
     Bump lay;
@@ -974,7 +1024,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
     const size_t o_vc = lay.take_off(kv_elems * (f32 ? 4 : 2));
     const size_t o_kv32 = (cross && f32) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;
     const size_t o_ce32 = (cross && f32) ? lay.take_off((size_t)R * Dc * 4) : 0;
-    const size_t o_kv128 = (cross && p->hd == 128) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;      // fp32 to_kv output in front of the head split
+    const size_t o_kv128 = (cross && p->staged() && !f32) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;      // fp32 to_kv output in front of the head split
     // blocks of both operand formats (sat_dit_plan_set_block_formats): a second image of the context embedding, in the other format than layer 0's
     int mixed = 0;
     for (int l = 1; l < c.depth; ++l) mixed |= layer_f16(p, l) != layer_f16(p, 0);
@@ -998,11 +1048,15 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
         p->vc32 = (float*)(p->ctx_buf.ptr + o_vc);
         SAT_TRY(glue_small_linear(cond, Dct, p->ce0_w, nullptr, nullptr, 0, ch, Dc, R, Dc, Dct, 1, 0, s));
         SAT_TRY(glue_small_linear(ch, Dc, p->ce2_w, nullptr, nullptr, 0, ce32, Dc, R, Dc, Dc, 0, 0, s));
-        const size_t per_layer = (size_t)bf * p->kvh_cross * lc * 64;
+        const size_t per_layer = (size_t)bf * p->kvh_cross * lc * p->hd;
         for (int l = 0; l < c.depth; ++l) {
             SAT_TRY(sat_launch_gemm_f32(ce32, (const float*)p->layers[l].ckv.w, nullptr, kv32, R, 2 * Dc, Dc, 2 * Dc, 0, nullptr, 1, 0, s));
-            SAT_TRY(sat_launch_split_heads_f32(kv32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, nullptr, R, lc, 2, p->kvh_cross, 0, nullptr,
-                                               nullptr, s, p->qk_norm ? 1 : 0));
+            if (p->hd == 64)
+                SAT_TRY(sat_launch_split_heads_f32(kv32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, nullptr, R, lc, 2, p->kvh_cross, 0, nullptr,
+                                                   nullptr, s, p->qk_norm ? 1 : 0));
+            else
+                SAT_TRY(sat_launch_split_heads_f32_w(kv32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, nullptr, R, lc, 2, p->kvh_cross, p->hd, 0,
+                                                     nullptr, nullptr, s, p->qk_norm ? 1 : 0));
         }
     } else if (cross) {   // dit.py:150 then per-layer to_kv (transformer.py:420-427)
         float* ch = (float*)(p->ctx_buf.ptr + o_ch);
@@ -1019,7 +1073,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
             GemmArgs g{};
             g.f16 = layer_f16(p, l);
             g.A = g.f16 == f16_0 ? ce : ce_other; g.W = p->layers[l].ckv.w; g.M = R; g.N = 2 * Dc; g.K = Dc;
-            if (p->hd == 128) {      // staged, as Forward::attention_hd128: fp32 [R, 2 Dc] -> head split (k: normalised under qk_norm, v transposed)
+            if (p->staged()) {      // staged, as Forward::attention_hd128: fp32 [R, 2 Dc] -> head split (k: normalised under qk_norm, v transposed)
                 float* kv32 = (float*)(p->ctx_buf.ptr + o_kv128);
                 g.C = kv32; g.ldc = 2 * Dc;
                 SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
@@ -1027,7 +1081,8 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
                 he.out[0] = p->kc + l * per_layer; he.out[1] = p->vct + l * per_layer;
                 he.kind[0] = 4 | (p->qk_norm ? 16 : 0); he.kind[1] = 1 | 4; he.parts = 2; he.heads = p->kvh_cross;
                 he.S = lc; he.Spad = lcpad;
-                SAT_TRY(sat_launch_head_split_hd128(kv32, he, bf, s, g.f16));
+                if (p->hd == 128) SAT_TRY(sat_launch_head_split_hd128(kv32, he, bf, s, g.f16));
+                else SAT_TRY(sat_launch_head_split_hdw(kv32, he, p->hd, bf, s, g.f16));
                 SAT_TRY(range_stats(p, l, RS_CROSS_K, p->kc + l * per_layer, per_layer, (size_t)R * Dc, s));
                 SAT_TRY(range_stats(p, l, RS_CROSS_V, p->vct + l * per_layer, per_layer, (size_t)R * Dc, s));
                 continue;
@@ -1124,7 +1179,7 @@ extern "C" int sat_dit_plan_set_block_options(sat_dit_plan* p, const sat_dit_blo
     // keeps the standalone LayerNorms of the shipped block
     SAT_CHECK_ARG(!any || p->cfg.gemm_dtype != SAT_GEMM_FP8, SAT_E_UNSUPPORTED,
                   "dit_plan_set_block_options: conformer / remove_norms / ff_glu 0 with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
-    SAT_CHECK_ARG(!any || p->hd == 64, SAT_E_UNSUPPORTED, "dit_plan_set_block_options: conformer / remove_norms / ff_glu 0 with dim_heads 128 is not built");
+    SAT_CHECK_ARG(!any || p->hd == 64, SAT_E_UNSUPPORTED, "dit_plan_set_block_options: conformer / remove_norms / ff_glu 0 with dim_heads %d is not built (64 only)", p->hd);
     SAT_CHECK_ARG(!any || (sat_launch_dwconv_ln_silu && sat_launch_round_rows && sat_launch_silu_f32), SAT_E_UNSUPPORTED,
                   "dit_plan_set_block_options: built without the block-option kernels");
     SAT_CHECK_ARG(!any || !p->rr, SAT_E_UNSUPPORTED, "dit_plan_set_block_options: the range report has no rows for the buffers of these options (sat_dit_range_report off first)");
@@ -1167,7 +1222,7 @@ extern "C" int sat_dit_plan_set_ff_conv(sat_dit_plan* p, const sat_dit_ff_conv_o
     // 128-channel-head route keeps the shipped block, as for sat_dit_plan_set_block_options
     SAT_CHECK_ARG(k == 1 || p->cfg.gemm_dtype != SAT_GEMM_FP8, SAT_E_UNSUPPORTED,
                   "dit_plan_set_ff_conv: a convolutional feed-forward with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
-    SAT_CHECK_ARG(k == 1 || p->hd == 64, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: a convolutional feed-forward with dim_heads 128 is not built");
+    SAT_CHECK_ARG(k == 1 || p->hd == 64, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: a convolutional feed-forward with dim_heads %d is not built (64 only)", p->hd);
     SAT_CHECK_ARG(k == 1 || (sat_launch_ff_conv && sat_launch_pack_conv_taps && sat_launch_im2col_rows_f32), SAT_E_UNSUPPORTED,
                   "dit_plan_set_ff_conv: built without the convolution GEMM");
     SAT_CHECK_ARG(k == 1 || !p->rr, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: the range report has no rows for such a plan (sat_dit_range_report off first)");

@@ -168,6 +168,40 @@ __global__ __launch_bounds__(256) void split_heads_f32_kernel(const float* __res
     dst[(((size_t)b * H + h) * S + s) * 64 + d] = v;
 }
 
+// The same for heads of W channels that do not fill a wave (32, 96): [M, parts * H * W] -> per part [B, H, S, W]; rotation of the first 2 RH
+// channels in pairs (d, d + RH) with RH = sat_rope_pairs(W) angles per position (RotaryEmbedding(max(W / 2, 32))).  One lane per element; a
+// lane of a normalised part sums the squares of its head row itself (the verification path is no fast path), and normalises BEFORE the
+// rotation as the reference does
+__global__ __launch_bounds__(256) void split_heads_f32_w_kernel(const float* __restrict__ src, float* __restrict__ d0, float* __restrict__ d1,
+                                                                float* __restrict__ d2, int M, int S, int parts, int H, int W, int RH, int rope_mask,
+                                                                const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, int norm_mask) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = (int64_t)M * parts * H * W;
+    if (idx >= total) return;
+    const int d = (int)(idx % W);
+    int64_t t = idx / W;
+    const int h = (int)(t % H);
+    t /= H;
+    const int part = (int)(t % parts);
+    const int m = (int)(t / parts);
+    const int b = m / S, s = m - b * S;
+    const float* row = src + (size_t)m * parts * H * W + (size_t)part * H * W + (size_t)h * W;
+    float inv = 1.0f;
+    if ((norm_mask >> part) & 1) {
+        float ss = 0.f;
+        for (int c = 0; c < W; ++c) ss = fmaf(row[c], row[c], ss);
+        inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    }
+    float v = row[d] * inv;
+    if (((rope_mask >> part) & 1) && d < 2 * RH) {
+        const int j = d < RH ? d : d - RH;
+        const float cs = rope_cos[(size_t)s * RH + j], sn = rope_sin[(size_t)s * RH + j];
+        v = d < RH ? v * cs - row[d + RH] * inv * sn : v * cs + row[d - RH] * inv * sn;
+    }
+    float* dst = part == 0 ? d0 : (part == 1 ? d1 : d2);
+    dst[(((size_t)b * H + h) * S + s) * W + d] = v;
+}
+
 // x, gate = chunk(2); x * silu(gate)  (transformer.py:232-235), fp32
 __global__ __launch_bounds__(256) void swiglu_f32_kernel(const float* __restrict__ hg, float* __restrict__ h, int64_t M, int inner) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -178,8 +212,10 @@ __global__ __launch_bounds__(256) void swiglu_f32_kernel(const float* __restrict
     h[idx] = v * (g / (1.0f + expf(-g)));
 }
 
-// softmax(q k^T / 8) v in fp32, one query per lane (q and the output row in registers), K / V rows are wave-uniform loads.
-// Online softmax over chunks of 8 keys.  q [B,H,Sq,64], k / v [B,KVH,Sk,64] -> out [B*Sq, H*64].
+// softmax(q k^T / sqrt(W)) v in fp32, one query per lane (q and the output row in registers), K / V rows are wave-uniform loads.
+// Online softmax over chunks of 8 keys.  q [B,H,Sq,W], k / v [B,KVH,Sk,W] -> out [B*Sq, H*W].  W = 64 is the kernel the 64-channel plans
+// have always run (scale 1/8); 32 and 96 are the widths of the staged route (attention_hdw.hip)
+template <int W>
 __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                            const float* __restrict__ v, float* __restrict__ out, int H, int KVH, int Sq,
                                                            int Sk) {
@@ -187,21 +223,22 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
     const int kvh = h / (H / KVH);
     const int qi = blockIdx.x * 64 + threadIdx.x;
     const int qc = qi < Sq ? qi : Sq - 1;
-    float qr[64], o[64];
-    const f32x4* qp = reinterpret_cast<const f32x4*>(q + (((size_t)b * H + h) * Sq + qc) * 64);
+    constexpr float SCALE = W == 64 ? 0.125f : W == 32 ? 0.17677669529663687f : 0.10206207261596575f;      // 1 / sqrt(W)
+    float qr[W], o[W];
+    const f32x4* qp = reinterpret_cast<const f32x4*>(q + (((size_t)b * H + h) * Sq + qc) * W);
 #pragma unroll
-    for (int t = 0; t < 16; ++t) {
+    for (int t = 0; t < W / 4; ++t) {
         const f32x4 x = qp[t];
-        qr[4 * t] = x[0] * 0.125f;
-        qr[4 * t + 1] = x[1] * 0.125f;
-        qr[4 * t + 2] = x[2] * 0.125f;
-        qr[4 * t + 3] = x[3] * 0.125f;
+        qr[4 * t] = x[0] * SCALE;
+        qr[4 * t + 1] = x[1] * SCALE;
+        qr[4 * t + 2] = x[2] * SCALE;
+        qr[4 * t + 3] = x[3] * SCALE;
     }
 #pragma unroll
-    for (int d = 0; d < 64; ++d) o[d] = 0.f;
+    for (int d = 0; d < W; ++d) o[d] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
-    const float* kb = k + ((size_t)b * KVH + kvh) * Sk * 64;
-    const float* vb = v + ((size_t)b * KVH + kvh) * Sk * 64;
+    const float* kb = k + ((size_t)b * KVH + kvh) * Sk * W;
+    const float* vb = v + ((size_t)b * KVH + kvh) * Sk * W;
     for (int j0 = 0; j0 < Sk; j0 += 8) {
         float sc[8];
         float mx = m_run;
@@ -210,10 +247,10 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
             const int j = j0 + u;
             float s = -INFINITY;
             if (j < Sk) {
-                const float* kr = kb + (size_t)j * 64;
+                const float* kr = kb + (size_t)j * W;
                 s = 0.f;
 #pragma unroll
-                for (int d = 0; d < 64; ++d) s = fmaf(qr[d], kr[d], s);
+                for (int d = 0; d < W; ++d) s = fmaf(qr[d], kr[d], s);
             }
             sc[u] = s;
             mx = fmaxf(mx, s);
@@ -222,24 +259,24 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
         m_run = mx;
         l_run *= alpha;
 #pragma unroll
-        for (int d = 0; d < 64; ++d) o[d] *= alpha;
+        for (int d = 0; d < W; ++d) o[d] *= alpha;
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int j = j0 + u;
             if (j < Sk) {
                 const float p = expf(sc[u] - mx);
                 l_run += p;
-                const float* vr = vb + (size_t)j * 64;
+                const float* vr = vb + (size_t)j * W;
 #pragma unroll
-                for (int d = 0; d < 64; ++d) o[d] = fmaf(p, vr[d], o[d]);
+                for (int d = 0; d < W; ++d) o[d] = fmaf(p, vr[d], o[d]);
             }
         }
     }
     if (qi < Sq) {
         const float inv = 1.0f / l_run;
-        f32x4* op = reinterpret_cast<f32x4*>(out + ((size_t)b * Sq + qi) * ((size_t)H * 64) + h * 64);
+        f32x4* op = reinterpret_cast<f32x4*>(out + ((size_t)b * Sq + qi) * ((size_t)H * W) + h * W);
 #pragma unroll
-        for (int t = 0; t < 16; ++t) op[t] = f32x4{o[4 * t] * inv, o[4 * t + 1] * inv, o[4 * t + 2] * inv, o[4 * t + 3] * inv};
+        for (int t = 0; t < W / 4; ++t) op[t] = f32x4{o[4 * t] * inv, o[4 * t + 1] * inv, o[4 * t + 2] * inv, o[4 * t + 3] * inv};
     }
 }
 
@@ -291,7 +328,36 @@ int sat_launch_attention_f32(const float* q, const float* k, const float* v, flo
     SAT_CHECK_ARG(q && k && v && out && b > 0 && h > 0 && kvh > 0 && h % kvh == 0 && sq > 0 && sk > 0, SAT_E_INVALID, "attention_f32: bad args");
     SAT_CHECK_ARG((((uintptr_t)q | (uintptr_t)out) & 15) == 0, SAT_E_INVALID, "attention_f32: q and out must be 16-byte aligned");
     SAT_CHECK_ARG(h <= 65535 && b <= 65535, SAT_E_UNSUPPORTED, "attention_f32: %d heads / %d sequences exceed the grid", h, b);
-    hipLaunchKernelGGL(attention_f32_kernel, dim3(cdiv(sq, 64), h, b), dim3(64), 0, s, q, k, v, out, h, kvh, sq, sk);
+    hipLaunchKernelGGL(attention_f32_kernel<64>, dim3(cdiv(sq, 64), h, b), dim3(64), 0, s, q, k, v, out, h, kvh, sq, sk);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int sat_launch_split_heads_f32_w(const float* src, float* d0, float* d1, float* d2, int M, int S, int parts, int H, int head_dim, int rope_mask,
+                                 const float* rope_cos, const float* rope_sin, hipStream_t s, int norm_mask) {
+    if (head_dim == 64) return sat_launch_split_heads_f32(src, d0, d1, d2, M, S, parts, H, rope_mask, rope_cos, rope_sin, s, norm_mask);
+    SAT_CHECK_ARG(head_dim == 32 || head_dim == 96, SAT_E_UNSUPPORTED, "split_heads_f32: dim_heads %d (built for 32, 64 and 96)", head_dim);
+    SAT_CHECK_ARG(src && d0 && parts >= 1 && parts <= 3 && (rope_mask == 0 || (rope_cos && rope_sin)), SAT_E_INVALID, "split_heads_f32: bad args");
+    SAT_CHECK_ARG(M > 0 && S > 0 && M % S == 0 && H > 0 && (parts < 2 || d1) && (parts < 3 || d2) && rope_mask >= 0 && norm_mask >= 0 &&
+                      (rope_mask >> parts) == 0 && (norm_mask >> parts) == 0,
+                  SAT_E_INVALID, "split_heads_f32: bad dims (M %d, S %d, H %d, parts %d, rope_mask %d, norm_mask %d)", M, S, H, parts, rope_mask,
+                  norm_mask);
+    const int64_t total = (int64_t)M * parts * H * head_dim;
+    hipLaunchKernelGGL(split_heads_f32_w_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, src, d0, d1, d2, M, S, parts, H, head_dim,
+                       sat_rope_pairs(head_dim), rope_mask, rope_cos, rope_sin, norm_mask);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+int sat_launch_attention_f32_w(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int head_dim, int sq, int sk,
+                               hipStream_t s) {
+    if (head_dim == 64) return sat_launch_attention_f32(q, k, v, out, b, h, kvh, sq, sk, s);
+    SAT_CHECK_ARG(head_dim == 32 || head_dim == 96, SAT_E_UNSUPPORTED, "attention_f32: dim_heads %d (built for 32, 64 and 96)", head_dim);
+    SAT_CHECK_ARG(q && k && v && out && b > 0 && h > 0 && kvh > 0 && h % kvh == 0 && sq > 0 && sk > 0, SAT_E_INVALID, "attention_f32: bad args");
+    SAT_CHECK_ARG((((uintptr_t)q | (uintptr_t)out) & 15) == 0, SAT_E_INVALID, "attention_f32: q and out must be 16-byte aligned");
+    SAT_CHECK_ARG(h <= 65535 && b <= 65535, SAT_E_UNSUPPORTED, "attention_f32: %d heads / %d sequences exceed the grid", h, b);
+    if (head_dim == 32) hipLaunchKernelGGL(attention_f32_kernel<32>, dim3(cdiv(sq, 64), h, b), dim3(64), 0, s, q, k, v, out, h, kvh, sq, sk);
+    else hipLaunchKernelGGL(attention_f32_kernel<96>, dim3(cdiv(sq, 64), h, b), dim3(64), 0, s, q, k, v, out, h, kvh, sq, sk);
     SAT_LAUNCH_CHECK();
     return 0;
 }

@@ -1,6 +1,7 @@
 // Shared device/host helpers for libsat_hip (gfx950 / CDNA4 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
@@ -364,8 +365,20 @@ __attribute__((weak)) int sat_launch_attention_hd128(const op_t* q, const op_t* 
                                                      int sq_pad, int sk_pad, hipStream_t s, int f16 = 0);
 // x: fp32 [b * S, parts * heads * 128]; he: out / kind / qscale / parts / heads / S / Spad and the [S][32] rotation tables
 __attribute__((weak)) int sat_launch_head_split_hd128(const float* x, const HeadsEpi& he, int b, hipStream_t s, int f16 = 0);
+// ---- 32- and 96-channel heads (the same staged route): head_split_hdw.hip, attention_hdw.hip.  WEAK for the same reason.  Layouts as the
+// 128-channel pair with head_dim channels per head; Q pre-scaled by sat_attn_qscale(head_dim); sk_pad a multiple of sat_attn_hdw_key_tile(head_dim)
+__attribute__((weak)) int sat_launch_attention_hdw(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int head_dim, int sq,
+                                                   int sk, int sq_pad, int sk_pad, hipStream_t s, int f16 = 0);
+// x: fp32 [b * S, parts * heads * head_dim]; he: out / kind / qscale / parts / heads / S / Spad and the [S][sat_rope_pairs(head_dim)] rotation tables
+__attribute__((weak)) int sat_launch_head_split_hdw(const float* x, const HeadsEpi& he, int head_dim, int b, hipStream_t s, int f16 = 0);
 }  // namespace SAT_OPNS
 using namespace SAT_OPNS;
+// RotaryEmbedding(max(dim_heads / 2, 32)) (transformer.py:737): pairs (j, j + sat_rope_pairs) rotate, one angle per pair -- 16 for 32- and
+// 64-channel heads, 24 for 96, 32 for 128
+inline int sat_rope_pairs(int head_dim) { return (head_dim / 2 > 32 ? head_dim / 2 : 32) / 2; }
+inline float sat_attn_qscale(int head_dim) { return (float)(1.4426950408889634 / sqrt((double)head_dim)); }      // log2(e) / sqrt(dim_heads)
+inline int sat_attn_hdw_key_tile(int head_dim) { return head_dim == 32 ? 128 : 64; }                                // attn_hdw_tiles.h
+__attribute__((weak)) int sat_launch_rope_table_hdw(const float* inv_freq, float* cos_t, float* sin_t, int s_len, int head_dim, hipStream_t s);      // [s_len][sat_rope_pairs]
 __attribute__((weak)) int sat_launch_rope_table_hd128(const float* inv_freq, float* cos_t, float* sin_t, int s_len, hipStream_t s);      // [s_len][32]
 // range_stats.hip: the reduction of the range reports (sat_range_record) over x[r * pitch + c], r < rows, c < cols, of `dtype` elements
 // (SAT_GEMM_BF16 / SAT_GEMM_FP16 / SAT_GEMM_FP32X).  `counted` is what the record's `elements` grows by: rows * cols, or the logical count of
@@ -412,6 +425,9 @@ __attribute__((weak)) int sat_launch_im2col_rows_f32(const float* a, float* out,
 int sat_launch_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int sq, int sk, int sq_pad,
                                    int sk_pad, hipStream_t s);
 int sat_launch_head_split_hd128_f16(const float* x, const void* heads_epi, int b, hipStream_t s);
+int sat_launch_attention_hdw_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int head_dim, int sq, int sk,
+                                 int sq_pad, int sk_pad, hipStream_t s);
+int sat_launch_head_split_hdw_f16(const float* x, const void* heads_epi, int head_dim, int b, hipStream_t s);
 // entry points of the fp16 build for the dispatchers of the bf16 build (GemmArgs is layout-identical in both builds: the pointer
 // element type is the only difference)
 int sat_launch_gemm_f16(int epi, const void* gemm_args, hipStream_t stream);
@@ -439,6 +455,12 @@ int sat_launch_split_heads_f32(const float* src, float* d0, float* d1, float* d2
 int sat_launch_swiglu_f32(const float* hg, float* h, int64_t M, int inner, hipStream_t s);
 int sat_launch_attention_f32(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int sq, int sk,
                              hipStream_t s);
+// the two kernels above for any built head width (32, 64, 96): head_dim channels per head, rotation tables [S][sat_rope_pairs(head_dim)], scores
+// scaled by 1 / sqrt(head_dim).  WEAK as the staged-route launchers: the host test driver of the 64-channel routes does not define them
+__attribute__((weak)) int sat_launch_split_heads_f32_w(const float* src, float* d0, float* d1, float* d2, int M, int S, int parts, int H, int head_dim,
+                                                       int rope_mask, const float* rope_cos, const float* rope_sin, hipStream_t s, int norm_mask = 0);
+__attribute__((weak)) int sat_launch_attention_f32_w(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int head_dim,
+                                                     int sq, int sk, hipStream_t s);
 int sat_launch_cast_bf16(const float* x, op_t* y, int64_t n, hipStream_t s, int f16 = 0);
 int sat_launch_pack_rows_bf16(const float* w, op_t* out, int n, int k, int swiglu_interleave, hipStream_t s, int f16 = 0);
 int sat_launch_pack_bias(const float* b, float* out, int n, int swiglu_interleave, hipStream_t s);

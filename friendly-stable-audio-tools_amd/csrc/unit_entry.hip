@@ -221,6 +221,72 @@ extern "C" int sat_head_split_hd128_f16(const float* x, const float* inv_freq, v
     return head_split_hd128_impl(1, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, parts, stream);
 }
 
+// ---- 32- and 96-channel heads: the same pair (attention_hdw.hip, head_split_hdw.hip), and the fp32 verification kernels with a head width
+static int attention_hdw_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
+                              int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return sat_launch_attention_hdw((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, head_dim, sq, sk, sq_pad, sk_pad,
+                                    (hipStream_t)stream, f16);
+}
+extern "C" int sat_attention_hdw_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
+                                      int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_hdw_impl(0, q, k, vt, out, b, h, kvh, head_dim, sq, sk, sq_pad, sk_pad, stream);
+}
+extern "C" int sat_attention_hdw_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
+                                     int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_hdw_impl(1, q, k, vt, out, b, h, kvh, head_dim, sq, sk, sq_pad, sk_pad, stream);
+}
+
+static int head_split_hdw_impl(int f16, const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch, int32_t b,
+                               int32_t s_len, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream) {
+    SAT_CHECK_ARG(head_dim == 32 || head_dim == 96, SAT_E_UNSUPPORTED, "head_split_hdw: dim_heads %d (this kernel is built for 32 and 96)", head_dim);
+    SAT_CHECK_ARG(x && dst && kind && b > 0 && s_len > 0 && heads > 0 && parts >= 1 && parts <= 3, SAT_E_INVALID, "head_split_hdw: bad argument");
+    SAT_CHECK_ARG(s_pad % 64 == 0 && s_pad >= s_len + 3, SAT_E_INVALID, "head_split_hdw: bad dims (s_pad >= s + 3, %% 64)");
+    hipStream_t s = (hipStream_t)stream;
+    const int pairs = sat_rope_pairs(head_dim);
+    HeadsEpi he{};
+    bool rope = false;
+    for (int pt = 0; pt < parts; ++pt) {
+        SAT_CHECK_ARG(dst[pt] && ((uintptr_t)dst[pt] & 15) == 0, SAT_E_INVALID, "head_split_hdw: destination %d null or not 16-byte aligned", pt);
+        rope = rope || (kind[pt] & 2);
+    }
+    SAT_CHECK_ARG(((uintptr_t)x & 15) == 0, SAT_E_INVALID, "head_split_hdw: the input must be 16-byte aligned");
+    SAT_CHECK_ARG(!rope || (inv_freq && rope_scratch && ((uintptr_t)rope_scratch & 15) == 0), SAT_E_INVALID,
+                  "head_split_hdw: a rotating part needs inv_freq and a 16-byte aligned rope_scratch");
+    for (int pt = 0; pt < parts; ++pt) {
+        SAT_HIP(hipMemsetAsync(dst[pt], 0, (size_t)b * heads * s_pad * head_dim * 2, s));
+        he.out[pt] = (op_t*)dst[pt];
+        he.kind[pt] = kind[pt];
+    }
+    if (rope) {
+        he.rope_cos = rope_scratch;
+        he.rope_sin = rope_scratch + (size_t)s_len * pairs;
+        SAT_TRY(sat_launch_rope_table_hdw(inv_freq, rope_scratch, rope_scratch + (size_t)s_len * pairs, s_len, head_dim, s));
+    }
+    he.qscale = sat_attn_qscale(head_dim); he.parts = parts; he.heads = heads; he.S = s_len; he.Spad = s_pad;
+    return sat_launch_head_split_hdw(x, he, head_dim, b, s, f16);
+}
+extern "C" int sat_head_split_hdw_bf16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch, int32_t b,
+                                       int32_t s_len, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream) {
+    return head_split_hdw_impl(0, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, head_dim, parts, stream);
+}
+extern "C" int sat_head_split_hdw_f16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch, int32_t b,
+                                      int32_t s_len, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream) {
+    return head_split_hdw_impl(1, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, head_dim, parts, stream);
+}
+extern "C" int sat_split_heads_f32_hdw(const float* src, float* d0, float* d1, float* d2, int32_t b, int32_t s_len, int32_t parts, int32_t heads,
+                                       int32_t head_dim, int32_t rope_mask, const float* rope_cos, const float* rope_sin, int32_t norm_mask,
+                                       sat_stream_t stream) {
+    SAT_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 96, SAT_E_UNSUPPORTED, "split_heads_f32: dim_heads %d (built for 32, 64 and 96)", head_dim);
+    SAT_CHECK_ARG(b > 0 && s_len > 0 && (int64_t)b * s_len <= INT32_MAX, SAT_E_INVALID, "split_heads_f32: b %d, s_len %d", b, s_len);
+    return sat_launch_split_heads_f32_w(src, d0, d1, d2, b * s_len, s_len, parts, heads, head_dim, rope_mask, rope_cos, rope_sin, (hipStream_t)stream,
+                                        norm_mask);
+}
+extern "C" int sat_attention_f32_hdw(const float* q, const float* k, const float* v, float* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
+                                     int32_t sq, int32_t sk, sat_stream_t stream) {
+    SAT_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 96, SAT_E_UNSUPPORTED, "attention_f32: dim_heads %d (built for 32, 64 and 96)", head_dim);
+    return sat_launch_attention_f32_w(q, k, v, out, b, h, kvh, head_dim, sq, sk, (hipStream_t)stream);
+}
+
 // qkn: q and k L2-normalised per head (qk_norm), q pre-scaled for the attention kernel as in the plan
 static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
                                  float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,

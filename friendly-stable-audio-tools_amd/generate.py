@@ -73,6 +73,10 @@ def get_args():
                    help="build extension: the model config's DiT has patch_size > 1 (a token is patch_size latent frames), which the constructor "
                         "refuses without an opt-in: sets \"allow_patch_size\": true in model.diffusion.config before the model is built "
                         "(with --model-config or the built-in config; an error with --model-name)")
+    p.add_argument("--allow-head-widths", action="store_true",
+                   help="build extension: the model config's DiT has attention heads of 32 or 96 channels (embed_dim / num_heads), which the "
+                        "constructor refuses without an opt-in: sets \"allow_head_widths\": true in model.diffusion.config before the model is "
+                        "built (with --model-config or the built-in config; an error with --model-name)")
     p.add_argument("--check-fp16-range", action="store_true",
                    help="build extension, for a checkpoint this build was never run on: before generating, run the first batch once for 8 "
                         "steps with the activation range reports of the DiT and the codec on and print how close their 16-bit buffers come "
@@ -84,6 +88,9 @@ def get_args():
     if args.allow_patch_size and args.model_name:
         p.error("--allow-patch-size is written into the model config before the model is built: it goes with --model-config, not with "
                 "--model-name (a pretrained model is built from its own config)")
+    if args.allow_head_widths and args.model_name:
+        p.error("--allow-head-widths is written into the model config before the model is built: it goes with --model-config, not with "
+                "--model-name (a pretrained model is built from its own config)")
     return args
 
 
@@ -93,6 +100,8 @@ def apply_config_flags(args, model_config):
         model_config["model"]["diffusion"]["config"]["allow_conv_ff"] = True
     if args.allow_patch_size:
         model_config["model"]["diffusion"]["config"]["allow_patch_size"] = True
+    if args.allow_head_widths:
+        model_config["model"]["diffusion"]["config"]["allow_head_widths"] = True
     return model_config
 
 

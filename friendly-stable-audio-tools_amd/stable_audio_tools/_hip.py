@@ -59,6 +59,11 @@ class SatRobertaCfg(Structure):
                 ("proj_dim", c_int32), ("eps", c_float)]
 
 
+class SatDitCreateOptions(Structure):
+    """include/sat_hip.h: sat_dit_create_options (sat_dit_plan_create_ex).  head_widths 1 admits 32- and 96-channel attention heads."""
+    _fields_ = [("head_widths", c_int32)]
+
+
 class SatOobleckCfg(Structure):
     _fields_ = [("is_decoder", c_int32), ("io_channels", c_int32), ("channels", c_int32), ("latent_dim", c_int32),
                 ("n_blocks", c_int32), ("c_mults", c_int32 * 8), ("strides", c_int32 * 8), ("gemm_dtype", c_int32)]
@@ -99,6 +104,7 @@ _SIGNATURES = {
     "sat_last_error": (c_char_p, []),
     "sat_dit_plan_create": (c_int32, [POINTER(SatDitCfg), POINTER(c_void_p)]),
     "sat_dit_plan_create_sized": (c_int32, [POINTER(SatDitCfg), c_size_t, POINTER(c_void_p)]),
+    "sat_dit_plan_create_ex": (c_int32, [POINTER(SatDitCfg), c_size_t, POINTER(SatDitCreateOptions), c_size_t, POINTER(c_void_p)]),
     "sat_dit_plan_destroy": (None, [c_void_p]),
     "sat_dit_plan_set_tensor": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64]),
     "sat_dit_plan_finalize": (c_int32, [c_void_p, c_void_p]),
@@ -176,6 +182,10 @@ _SIGNATURES = {
                                            c_int32, c_int32, c_void_p]),
     "sat_head_split_hd128_bf16": (c_int32, [c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int32), c_void_p, c_int32, c_int32, c_int32,
                                             c_int32, c_int32, c_void_p]),
+    # 32- / 96-channel heads: (q, k, vt, out, b, h, kvh, head_dim, sq, sk, sq_pad, sk_pad, stream) and
+    # (x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, head_dim, parts, stream)
+    "sat_attention_hdw_bf16": (c_int32, [c_void_p] * 4 + [c_int32] * 8 + [c_void_p]),
+    "sat_head_split_hdw_bf16": (c_int32, [c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int32), c_void_p] + [c_int32] * 6 + [c_void_p]),
     "sat_qkv_rope_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                     c_int32, c_int32, c_int32, c_void_p]),
     "sat_qkv_rope_qknorm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
@@ -216,6 +226,8 @@ _SIGNATURES = {
     "sat_split_heads_f32": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_void_p, c_void_p, c_int32, c_void_p]),
     "sat_swiglu_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "sat_attention_f32": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_void_p]),
+    "sat_split_heads_f32_hdw": (c_int32, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p, c_void_p, c_int32, c_void_p]),
+    "sat_attention_f32_hdw": (c_int32, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p]),
     "sat_enc_attention": (c_int32, [c_void_p] * 4 + [c_int32] * 4 + [c_float, c_void_p]),
     "sat_t5_embed": (c_int32, [c_void_p] * 3 + [c_int32] * 3 + [c_void_p]),
     "sat_t5_rmsnorm": (c_int32, [c_void_p] * 3 + [c_int32, c_int32, c_float, c_void_p]),
@@ -238,7 +250,7 @@ _SIGNATURES = {
 }
 
 # the same unit-level entry points on IEEE fp16 operands (gemm_dtype = 3): identical signatures
-for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_attention_hd128_bf16", "sat_head_split_hd128_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws", "sat_range_stats_bf16", "sat_dwconv_ln_silu_bf16", "sat_gemm_act_bf16"):
+for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_attention_hd128_bf16", "sat_head_split_hd128_bf16", "sat_attention_hdw_bf16", "sat_head_split_hdw_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws", "sat_range_stats_bf16", "sat_dwconv_ln_silu_bf16", "sat_gemm_act_bf16"):
     _SIGNATURES[_n.replace("bf16", "f16")] = _SIGNATURES[_n]
 
 _lib = None

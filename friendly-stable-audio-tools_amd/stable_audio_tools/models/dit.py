@@ -35,14 +35,18 @@ class DiffusionTransformer(nn.Module):
                  project_cond_tokens: bool = True, global_cond_dim: int = 0, project_global_cond: bool = True,
                  input_concat_dim: int = 0, prepend_cond_dim: int = 0, depth: int = 12, num_heads: int = 8,
                  transformer_type: str = "x-transformers", global_cond_type: str = "prepend", max_seq_len: int = 8192,
-                 allow_block_options: bool = False, allow_conv_ff: bool = False, allow_patch_size: bool = False, **kwargs):
+                 allow_block_options: bool = False, allow_conv_ff: bool = False, allow_patch_size: bool = False, allow_head_widths: bool = False,
+                 **kwargs):
         """``allow_block_options``: the TransformerBlock options ``conformer``, ``remove_norms`` and ``ff_kwargs={"glu": False}`` are off the
         shipped configs' path and refused unless this is set; ``create_model_from_config`` and every other config-driven path set it.
         ``allow_conv_ff``: likewise for ``ff_kwargs={"use_conv": True}`` (``sat_dit_plan_set_ff_conv``); no path sets it by default, a config
         asks for it with ``"allow_conv_ff": true`` in ``model.diffusion.config``.
         ``allow_patch_size``: likewise for ``patch_size`` above 1 (``sat_dit_plan_set_patch``): a token is then ``patch_size`` consecutive
         latent frames, ``x`` and the output keep their ``[B, io_channels, T]`` layout and ``T`` must be a multiple of ``patch_size``; a config
-        asks for it with ``"allow_patch_size": true``."""
+        asks for it with ``"allow_patch_size": true``.
+        ``allow_head_widths``: likewise for attention heads of 32 or 96 channels (``embed_dim // num_heads``; ``sat_dit_plan_create_ex``), next
+        to the 64- and 128-channel ones that need no opt-in; a config asks for it with ``"allow_head_widths": true``.  Such a model runs
+        with 'fp16', 'bf16' (also per block) and 'fp32x' operands; 'fp8', the block options and ``use_conv`` keep 64-channel heads."""
         super().__init__()
         if transformer_type != "continuous_transformer":
             raise NotImplementedError("only transformer_type='continuous_transformer' is implemented (the shipped DiT configs)")
@@ -75,6 +79,7 @@ class DiffusionTransformer(nn.Module):
         self.prepend_cond_dim = prepend_cond_dim
         self.max_prepend_len = 64 if prepend_cond_dim > 0 else 0     # grows (plan rebuild) when a generation brings more tokens
         self.max_seq_len = max_seq_len
+        self.allow_head_widths = bool(allow_head_widths)
         self.transformer_type = transformer_type
         self.global_cond_type = global_cond_type
 
@@ -99,7 +104,8 @@ class DiffusionTransformer(nn.Module):
                                                  dim_in=dim_in * patch_size, dim_out=io_channels * patch_size, cross_attend=cond_token_dim > 0,
                                                  cond_token_dim=cond_embed_dim,
                                                  global_cond_dim=embed_dim if global_cond_type == "adaLN" else None,
-                                                 allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff, **kwargs)
+                                                 allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff,
+                                                 allow_head_widths=allow_head_widths, **kwargs)
         self.preprocess_conv = _init.conv1d(dim_in, dim_in, 1, bias=False, zero=True)
         self.postprocess_conv = _init.conv1d(io_channels, io_channels, 1, bias=False, zero=True)
 
@@ -141,6 +147,10 @@ class DiffusionTransformer(nn.Module):
             raise NotImplementedError(f"dim_heads=128 (embed_dim {self.embed_dim} / num_heads {self.num_heads}) with gemm_dtype={gemm_dtype!r}: the "
                                       "128-channel-head route (fp32 projection, head split, attention) is built for 'fp16' and 'bf16' operands; the "
                                       "e4m3 attention outputs and the fp32 verification kernels keep 64-channel heads")
+        if self.transformer.dim_heads in (32, 96) and GEMM_DTYPES[gemm_dtype] == 1:
+            raise NotImplementedError(f"dim_heads={self.transformer.dim_heads} (embed_dim {self.embed_dim} / num_heads {self.num_heads}) with "
+                                      f"gemm_dtype={gemm_dtype!r}: the staged route (fp32 projection, head split, attention) runs 'fp16', 'bf16' "
+                                      "and 'fp32x' operands; the e4m3 attention outputs keep 64-channel heads")
 
     def _check_t_len(self, t_len):
         """``T`` must hold whole patches: the reference fails inside its rearrange (dit.py:198); here before anything is launched."""
@@ -255,7 +265,7 @@ class DiffusionTransformer(nn.Module):
     def set_layernorm_fusion(self, on: bool):
         """Build extension: run the LayerNorms of the blocks (transformer.py:692-700) inside the epilogues of the GEMMs either side of
         them (``sat_dit_cfg.ln_fold``; bf16 / "prepend" models) or as standalone kernels.  Rebuilds the plan on next use.  Accepted
-        without effect by an adaLN model and by one with 128-channel heads (as ``set_cross_attention_fusion``): their plans keep the
+        without effect by an adaLN model and by one with 128-, 32- or 96-channel heads (as ``set_cross_attention_fusion``): their plans keep the
         standalone kernels."""
         if bool(on) != self.layernorm_fusion:
             self.layernorm_fusion = bool(on)
@@ -357,7 +367,11 @@ class DiffusionTransformer(nn.Module):
             if self._range_report:        # the report belongs to the module: a rebuilt plan starts with it on (and with empty records)
                 _hip.check(lib.sat_dit_range_report(plan, 1))
 
-        create = lambda: _hip.new_handle(lib.sat_dit_plan_create_sized, ctypes.byref(cfg), ctypes.sizeof(cfg))
+        if self.allow_head_widths and self.transformer.dim_heads in (32, 96):       # only a model that opted in and needs it makes this call
+            copt = _hip.SatDitCreateOptions(1)
+            create = lambda: _hip.new_handle(lib.sat_dit_plan_create_ex, ctypes.byref(cfg), ctypes.sizeof(cfg), ctypes.byref(copt), ctypes.sizeof(copt))
+        else:
+            create = lambda: _hip.new_handle(lib.sat_dit_plan_create_sized, ctypes.byref(cfg), ctypes.sizeof(cfg))
         plan = self._plan = _hip.build_plan("dit", create, self.state_dict(), dev, configure)
         self._plan_version = ver
         self._plan_options = options

@@ -4,7 +4,7 @@ Mirror of the module tree of the reference's ``models/transformer.py`` (``LayerN
 ``GLU``/``FeedForward`` :211-287, ``Attention`` :290-554, ``TransformerBlock`` :594-702,
 ``RotaryEmbedding`` :99-155, ``AbsolutePositionalEmbedding`` / ``ScaledSinusoidalEmbedding`` :50-96,
 ``ContinuousTransformer`` :705-809) restricted to the options the HIP plan runs: those of the shipped DiT
-configs plus 128-channel heads, ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False``,
+configs plus 128-channel heads (and, behind ``allow_head_widths``, 32- and 96-channel ones), ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False``,
 bias-free / ``mult``-sized feed-forwards and, behind the ``allow_block_options`` opt-in, ``conformer`` (:557-591), ``remove_norms``
 and feed-forwards without GLU, and behind ``allow_conv_ff`` convolutional feed-forwards (``ff_kwargs use_conv``).  These classes only *hold* parameters under the reference's
 names; the forward pass of the whole stack is one C-ABI call (``sat_dit_forward`` /
@@ -70,6 +70,11 @@ CONV_FF_HINT = ("pass allow_conv_ff=True to DiffusionTransformer, or write \"all
                 "(generate.py --allow-conv-ff does): the convolutions then run on the HIP plan (sat_dit_plan_set_ff_conv)")
 
 
+HEAD_WIDTHS_HINT = ("pass allow_head_widths=True to DiffusionTransformer, or write \"allow_head_widths\": true into the model config's "
+                    "model.diffusion.config (generate.py --allow-head-widths does): 32- and 96-channel heads then run on the HIP plan "
+                    "(sat_dit_plan_create_ex)")
+
+
 class FeedForward(nn.Module):
     def __init__(self, dim, mult=4, glu=True, no_bias=False, use_conv=False, conv_kernel_size=3, zero_init_output=True, allow_block_options=False,
                  allow_conv_ff=False, **unsupported):
@@ -110,16 +115,24 @@ class FeedForward(nn.Module):
 
 class Attention(nn.Module):
     def __init__(self, dim, dim_heads=64, dim_context=None, causal=False, zero_init_output=True, qk_norm=False, natten_kernel_size=None,
-                 **unsupported):
+                 allow_head_widths=False, **unsupported):
         super().__init__()
         if causal or natten_kernel_size is not None or unsupported:
             raise NotImplementedError(f"Attention options not supported by the HIP path (full non-causal attention only): causal={causal} "
                                       f"natten_kernel_size={natten_kernel_size} {sorted(unsupported)}")
-        if dim_heads not in (64, 128):
-            raise NotImplementedError(f"the HIP attention kernels are built for dim_heads 64 and 128 (embed_dim / num_heads), got dim_heads={dim_heads}")
+        if dim_heads in (32, 96) and not allow_head_widths:
+            raise NotImplementedError(f"the HIP attention kernels run dim_heads 64 and 128 (embed_dim / num_heads) by default, got dim_heads={dim_heads}: "
+                                      f"{HEAD_WIDTHS_HINT}")
+        if dim_heads not in (32, 64, 96, 128):
+            raise NotImplementedError("the HIP attention kernels are built for dim_heads 64 and 128 (embed_dim / num_heads), and 32 and 96 behind "
+                                      f"allow_head_widths, got dim_heads={dim_heads}")
         self.dim, self.dim_heads = dim, dim_heads
         self.qk_norm = bool(qk_norm)
         dim_kv = dim_context if dim_context else dim
+        if dim_heads in (32, 96) and dim_kv % dim_heads:
+            # the reference builds such a model (kv_heads = dim_kv // dim_heads) and fails inside its first forward, where to_kv's output does
+            # not split into heads
+            raise ValueError(f"Attention: the context width {dim_kv} (cond_embed_dim) is no multiple of dim_heads={dim_heads}")
         self.num_heads = dim // dim_heads
         self.kv_heads = dim_kv // dim_heads
         if dim_context:
@@ -149,26 +162,28 @@ class ConformerModule(nn.Module):
 class TransformerBlock(nn.Module):
     def __init__(self, dim, dim_heads=64, cross_attend=False, dim_context=None, global_cond_dim=None, causal=False,
                  zero_init_branch_outputs=True, conformer=False, layer_ix=-1, remove_norms=False, attn_kwargs={}, ff_kwargs={},
-                 norm_kwargs={}, allow_block_options=False, allow_conv_ff=False):
+                 norm_kwargs={}, allow_block_options=False, allow_conv_ff=False, allow_head_widths=False):
         super().__init__()
         if (conformer or remove_norms) and not allow_block_options:
             raise NotImplementedError(f"conformer={conformer} / remove_norms={remove_norms} are off the shipped configs' path: {BLOCK_OPTIONS_HINT}")
         if dim_heads != 64 and (conformer or remove_norms or not ff_kwargs.get("glu", True)):
-            raise NotImplementedError(f"conformer / remove_norms / glu=False with dim_heads={dim_heads}: the staged 128-channel-head route keeps the "
-                                      "shipped block (standalone LayerNorms, SwiGLU feed-forward); these options run with dim_heads=64")
+            raise NotImplementedError(f"conformer / remove_norms / glu=False with dim_heads={dim_heads}: the staged route of the 128-channel heads "
+                                      "(and of the 32- / 96-channel ones) keeps the shipped block (standalone LayerNorms, SwiGLU feed-forward); these options run with dim_heads=64")
         if dim_heads != 64 and ff_kwargs.get("use_conv", False) and allow_conv_ff:
-            raise NotImplementedError(f"ff_kwargs use_conv with dim_heads={dim_heads}: the staged 128-channel-head route keeps the shipped block; "
+            raise NotImplementedError(f"ff_kwargs use_conv with dim_heads={dim_heads}: the staged route of the 128-channel heads (and of the 32- / 96-channel ones) "
+                                      "keeps the shipped block; "
                                       "a convolutional feed-forward runs with dim_heads=64")
         self.dim, self.dim_heads, self.cross_attend, self.dim_context = dim, dim_heads, cross_attend, dim_context
         self.layer_ix = layer_ix
         self.remove_norms = bool(remove_norms)
         norm = (lambda: nn.Identity()) if remove_norms else (lambda: LayerNorm(dim, **norm_kwargs))      # reference :621,632,642
         self.pre_norm = norm()
-        self.self_attn = Attention(dim, dim_heads=dim_heads, causal=causal, zero_init_output=zero_init_branch_outputs, **attn_kwargs)
+        self.self_attn = Attention(dim, dim_heads=dim_heads, causal=causal, zero_init_output=zero_init_branch_outputs,
+                                   allow_head_widths=allow_head_widths, **attn_kwargs)
         if cross_attend:
             self.cross_attend_norm = norm()
             self.cross_attn = Attention(dim, dim_heads=dim_heads, dim_context=dim_context, causal=causal,
-                                        zero_init_output=zero_init_branch_outputs, **attn_kwargs)
+                                        zero_init_output=zero_init_branch_outputs, allow_head_widths=allow_head_widths, **attn_kwargs)
         self.ff_norm = norm()
         self.ff = FeedForward(dim, zero_init_output=zero_init_branch_outputs, allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff,
                               **ff_kwargs)

@@ -141,6 +141,19 @@ typedef struct sat_dit_cfg {
  * sat_dit_plan_create(cfg, out) == sat_dit_plan_create_sized(cfg, SAT_DIT_CFG_BYTES_V5, out). */
 int sat_dit_plan_create_sized(const sat_dit_cfg* cfg, size_t cfg_bytes, sat_dit_plan** out_plan);
 int sat_dit_plan_create(const sat_dit_cfg* cfg, sat_dit_plan** out_plan);
+/* Creation options that are not part of sat_dit_cfg (whose layout and size stay what version 5 fixed), following sat_oobleck_plan_create_ex.
+ * head_widths: which attention head widths embed_dim / num_heads the plan admits.  0: 64 and 128 only -- exactly sat_dit_plan_create_sized;
+ * 1: 32 and 96 as well.  A plan with 32- or 96-channel heads runs the staged route of the 128-channel heads (fp32-output projection, head
+ * split, attention kernel: DESIGN.md section 7) with bf16 / fp16 operands (gemm_dtype 0 / 3, per block with sat_dit_plan_set_block_formats)
+ * and, unlike 128, the fp32 verification mode (gemm_dtype 2); e4m3 (gemm_dtype 1), sat_dit_plan_set_block_options with an option on and
+ * sat_dit_plan_set_ff_conv above kernel size 1 answer SAT_E_UNSUPPORTED with "dim_heads" in the message, any other width likewise.
+ * options == NULL (options_bytes ignored) behaves as sat_dit_plan_create_sized; otherwise options_bytes must be sizeof(sat_dit_create_options)
+ * of this version and head_widths 0 or 1 (SAT_E_INVALID). */
+typedef struct {
+    int32_t head_widths;
+} sat_dit_create_options;
+int sat_dit_plan_create_ex(const sat_dit_cfg* cfg, size_t cfg_bytes, const sat_dit_create_options* options, size_t options_bytes,
+                           sat_dit_plan** out_plan);
 void sat_dit_plan_destroy(sat_dit_plan* plan);
 
 /* Hand one fp32 tensor of the reference state dict to the plan.  `name` is the key
@@ -645,6 +658,19 @@ int sat_attention_hd128_bf16(const void* q_dev, const void* k_dev, const void* v
 int sat_head_split_hd128_bf16(const float* x_dev, const float* inv_freq_dev, void* const* dst_dev, const int32_t* kind,
                               float* rope_scratch_dev, int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t parts,
                               sat_stream_t stream);
+/* ---- 32- and 96-channel heads (sat_dit_plan_create_ex, head_widths 1): the same two kernels for head_dim 32 or 96; any other head_dim is
+ * SAT_E_UNSUPPORTED.  Test-only, as the 128-channel pair.
+ * sat_attention_hdw_*: layouts of sat_attention_hd128_* with head_dim channels per head, q pre-scaled by log2(e) / sqrt(head_dim).  Rules
+ * (SAT_E_INVALID otherwise): 16-byte aligned pointers, h % kvh == 0, sq_pad % 128 == 0, sq_pad >= sq, sk_pad >= sk + 3, and sk_pad a
+ * multiple of the key tile -- 128 for head_dim 32, 64 for head_dim 96. */
+int sat_attention_hdw_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
+                           int32_t head_dim, int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream);
+/* sat_head_split_hdw_*: sat_head_split_hd128_* with head_dim channels per head.  Bit 2 of kind rotates as RotaryEmbedding(max(head_dim / 2, 32)):
+ * head_dim 32: the whole head, pairs (j, j + 16), inv_freq_dev 16 floats; head_dim 96: channels 0..47, pairs (j, j + 24), inv_freq_dev 24
+ * floats, channels 48..95 pass.  Bit 8 multiplies by log2(e) / sqrt(head_dim).  Rules (SAT_E_INVALID otherwise): s_pad % 64 == 0, s_pad >= s + 3,
+ * x_dev and the destinations 16-byte aligned; rope_scratch_dev: 2 * s * 16 (32) or 2 * s * 24 (96) floats, 16-byte aligned. */
+int sat_head_split_hdw_bf16(const float* x_dev, const float* inv_freq_dev, void* const* dst_dev, const int32_t* kind, float* rope_scratch_dev,
+                            int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream);
 /* Cross-attention query projection and attention core in one launch (models/transformer.py:430-437 + 496-536; what the DiT plan
  * runs per layer while the 128 x 64 GEMM tiles of the projection fit one round of workgroups, i.e. at one prompt):
  * out [b*s, d] bf16 = softmax((a wq^T) k^T / 8) v per head of 64, a [b*s, d] bf16, wq [d, d] bf16, k / vt in the key-side layout of
@@ -717,6 +743,10 @@ int sat_attention_hd128_f16(const void* q_dev, const void* k_dev, const void* vt
 int sat_head_split_hd128_f16(const float* x_dev, const float* inv_freq_dev, void* const* dst_dev, const int32_t* kind,
                              float* rope_scratch_dev, int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t parts,
                              sat_stream_t stream);
+int sat_attention_hdw_f16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
+                          int32_t head_dim, int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream);
+int sat_head_split_hdw_f16(const float* x_dev, const float* inv_freq_dev, void* const* dst_dev, const int32_t* kind, float* rope_scratch_dev,
+                           int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream);
 int sat_cross_attention_fused_f16(const void* a_f16_dev, const void* wq_f16_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                                   int32_t b, int32_t s, int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream);
 int sat_qkv_rope_f16(const void* a_f16_dev, const void* w_f16_dev, const float* inv_freq_dev,
@@ -897,6 +927,14 @@ int sat_swiglu_f32(const float* hg_dev, float* h_dev, int64_t m, int32_t inner, 
 /* softmax(q k^T / 8) v on 64-channel heads: q [b,h,sq,64], k / v [b,kvh,sk,64] (h % kvh == 0) -> out [b * sq, h * 64] */
 int sat_attention_f32(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
                       int32_t sq, int32_t sk, sat_stream_t stream);
+/* The two kernels above for heads of head_dim channels, 32, 64 or 96 (SAT_E_UNSUPPORTED otherwise; 64 is exactly the pair above): tensors
+ * [.., head_dim]; the rotation is RotaryEmbedding(max(head_dim / 2, 32)) -- tables [s_len, 16] and pairs (c, c + 16) for 32 and 64, [s_len, 24]
+ * and pairs (c, c + 24) for 96; scores scaled by 1 / sqrt(head_dim).  Pointer rules as above (q and out 16-byte aligned). */
+int sat_split_heads_f32_hdw(const float* src_dev, float* d0_dev, float* d1_dev, float* d2_dev, int32_t b, int32_t s_len, int32_t parts,
+                            int32_t heads, int32_t head_dim, int32_t rope_mask, const float* rope_cos_dev, const float* rope_sin_dev,
+                            int32_t norm_mask, sat_stream_t stream);
+int sat_attention_f32_hdw(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
+                          int32_t head_dim, int32_t sq, int32_t sk, sat_stream_t stream);
 /* Self-attention of the text encoders: qkv [b * l, 3 * h * dkv] (q | k | v) -> out [b * l, h * dkv] = softmax(scale * q k^T + pb + mask) v;
  * pb [h, 2l - 1] indexed by key - query + l - 1, or NULL; keys with mask [b, l] == 0 get finfo(float32).min added (an all-padding row is the
  * uniform average over all l keys).  l <= 512, dkv % 4 == 0, (dkv + l) * 4 bytes of LDS <= 64 KiB. */
