@@ -359,10 +359,7 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         }
         p->rope_cos = (float*)ar.take((size_t)smax * pairs * 4);
         p->rope_sin = (float*)ar.take((size_t)smax * pairs * 4);
-        if (!ar.dry()) {
-            if (p->hd == 128) SAT_TRY(sat_launch_rope_table_hd128(p->inv_freq, p->rope_cos, p->rope_sin, smax, s));
-            else SAT_TRY(sat_launch_rope_table_hdw(p->inv_freq, p->rope_cos, p->rope_sin, smax, p->hd, s));
-        }
+        if (!ar.dry()) SAT_TRY(sat_launch_rope_table_hdw(p->inv_freq, p->rope_cos, p->rope_sin, smax, p->hd, s));
     }
     return 0;
 }
@@ -517,19 +514,16 @@ struct Forward {
         return 0;
     }
 
-    // The two kernels of the staged route by head width: head_split.hip / attention_hd128.hip, or their siblings for 32 and 96 channels
-    float staged_qscale() const { return p->hd == 128 ? SAT_ATTN_QSCALE_HD128 : sat_attn_qscale(p->hd); }
-    int head_split(const float* x, const HeadsEpi& he, int seqs, int f16) const {
-        return p->hd == 128 ? sat_launch_head_split_hd128(x, he, seqs, s, f16) : sat_launch_head_split_hdw(x, he, p->hd, seqs, s, f16);
-    }
+    // The two kernels of the staged route (head_split_hdw.hip, attention_hdw.hip) at the plan's head width
+    float staged_qscale() const { return sat_attn_qscale(p->hd); }
+    int head_split(const float* x, const HeadsEpi& he, int seqs, int f16) const { return sat_launch_head_split_hdw(x, he, p->hd, seqs, s, f16); }
     int attend(const op_t* q, const op_t* k, const op_t* vt, int seqs, int kvh, int sk, int sk_pad, int f16) const {
-        if (p->hd == 128) return sat_launch_attention_hd128(q, k, vt, w.AO, seqs, H, kvh, S, sk, Spad, sk_pad, s, f16);
         return sat_launch_attention_hdw(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, sk, Spad, sk_pad, s, f16);
     }
 
     int block(int l) const;
     int block_f32(int l) const;
-    int attention_hd128(int l) const;
+    int attention_staged(int l) const;
     int conformer(int l) const;
     int feed_forward(int l) const;
     int feed_forward_conv(int l) const;
@@ -602,10 +596,9 @@ int Forward::block_f32(int l) const {
 
 // The two attention branches of a block with 128-, 32- or 96-channel heads, staged: the heads epilogues, the fused to_q + cross-attention launch and the
 // LayerNorm fold keep one head = one 64-column wave tile (gemm_bf16.hip), so each projection runs as a plain fp32-output GEMM into qkv32, the
-// head split (head_split.hip: qk_norm, rotation, pre-scale, one rounding) writes Q / K / V^T, and attention_hd128.hip attends; for 32 and 96
-// channels their siblings head_split_hdw.hip / attention_hdw.hip (Forward::head_split / attend).  Two more launches and one fp32 round trip
-// per attention than the 64-channel route
-int Forward::attention_hd128(int l) const {
+// head split (head_split_hdw.hip: qk_norm, rotation, pre-scale, one rounding) writes Q / K / V^T, and attention_hdw.hip attends
+// (Forward::head_split / attend).  Two more launches and one fp32 round trip per attention than the 64-channel route
+int Forward::attention_staged(int l) const {
     const LayerW& L = p->layers[l];
     const float* m = mod(l);
     const int f16 = L.qkv.f16, qn = p->qk_norm ? 16 : 0;
@@ -651,7 +644,7 @@ int Forward::block(int l) const {
     const int f16 = L.qkv.f16, qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
     auto mx_scales = [&](const Proj& out) { return out.kind == PROJ_FP8_MX ? w.AOs : nullptr; };      // the attention kernels write to_out's MXFP8 operand
     if (p->staged()) {
-        SAT_TRY(attention_hd128(l));
+        SAT_TRY(attention_staged(l));
         return feed_forward(l);
     }
     // ---- self-attention branch (transformer.py:692)
@@ -893,11 +886,10 @@ extern "C" int sat_dit_plan_create_ex(const sat_dit_cfg* cfg_in, size_t cfg_byte
     // the e4m3 attention outputs (MXFP8) and the fp32 verification kernels (a head row in registers: f32_ref.hip) are built for 64 channels
     SAT_CHECK_ARG(hd != 128 || cfg->gemm_dtype == 0 || cfg->gemm_dtype == 3, SAT_E_UNSUPPORTED,
                   "dit_plan_create: dim_heads 128 runs with bf16 or fp16 operands only (gemm_dtype %d)", cfg->gemm_dtype);
-    SAT_CHECK_ARG(hd != 128 || (sat_launch_head_split_hd128 && sat_launch_attention_hd128 && sat_launch_rope_table_hd128), SAT_E_UNSUPPORTED,
-                  "dit_plan_create: dim_heads 128: built without the 128-channel-head kernels");
-    SAT_CHECK_ARG(!hdw || (sat_launch_head_split_hdw && sat_launch_attention_hdw && sat_launch_rope_table_hdw && sat_launch_split_heads_f32_w &&
-                           sat_launch_attention_f32_w),
-                  SAT_E_UNSUPPORTED, "dit_plan_create: dim_heads %d: built without the 32- / 96-channel-head kernels", hd);
+    // (32 / 96 also run in the fp32 verification mode, on the kernels with a head width)
+    SAT_CHECK_ARG(hd == 64 || (sat_launch_head_split_hdw && sat_launch_attention_hdw && sat_launch_rope_table_hdw &&
+                               (!hdw || (sat_launch_split_heads_f32_w && sat_launch_attention_f32_w))),
+                  SAT_E_UNSUPPORTED, "dit_plan_create: dim_heads %d: built without the %d-channel-head kernels", hd, hd);
     SAT_CHECK_ARG(cfg->gemm_dtype == 1 || cfg->fp8_families == 0, SAT_E_INVALID,
                   "dit_plan_create: fp8_families = 0x%x with gemm_dtype %d (a caller built against an older sat_dit_cfg layout?)", cfg->fp8_families, cfg->gemm_dtype);
     SAT_CHECK_ARG(cfg->cross_attention == 0 || cfg->cross_attention == 1, SAT_E_INVALID, "dit_plan_create: cross_attention must be 0 (fused where it applies) or 1 (two kernels)");
@@ -1010,7 +1002,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
     SAT_CHECK_ARG(!cross || (cond && lc > 0), SAT_E_INVALID, "dit_prepare_context: model has cross-attention but no cond given");
     SAT_CHECK_ARG(!(global_cond && Dg == 0), SAT_E_INVALID, "dit_prepare_context: model has no global conditioning");
     // (a multiple of the attention kernel's key tile: 64 keys, 128 with 32-channel heads -- attn_hdw_tiles.h)
-    const int lcpad = cross ? (int)round_up(lc + 3, p->hd == 32 ? sat_attn_hdw_key_tile(32) : 64) : 0;
+    const int lcpad = cross ? (int)round_up(lc + 3, sat_attn_hdw_key_tile(p->hd)) : 0;
     const int R = bf * lc;
     // layout of the context buffer
     Bump lay;
@@ -1073,7 +1065,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
             GemmArgs g{};
             g.f16 = layer_f16(p, l);
             g.A = g.f16 == f16_0 ? ce : ce_other; g.W = p->layers[l].ckv.w; g.M = R; g.N = 2 * Dc; g.K = Dc;
-            if (p->staged()) {      // staged, as Forward::attention_hd128: fp32 [R, 2 Dc] -> head split (k: normalised under qk_norm, v transposed)
+            if (p->staged()) {      // staged, as Forward::attention_staged: fp32 [R, 2 Dc] -> head split (k: normalised under qk_norm, v transposed)
                 float* kv32 = (float*)(p->ctx_buf.ptr + o_kv128);
                 g.C = kv32; g.ldc = 2 * Dc;
                 SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
@@ -1081,8 +1073,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
                 he.out[0] = p->kc + l * per_layer; he.out[1] = p->vct + l * per_layer;
                 he.kind[0] = 4 | (p->qk_norm ? 16 : 0); he.kind[1] = 1 | 4; he.parts = 2; he.heads = p->kvh_cross;
                 he.S = lc; he.Spad = lcpad;
-                if (p->hd == 128) SAT_TRY(sat_launch_head_split_hd128(kv32, he, bf, s, g.f16));
-                else SAT_TRY(sat_launch_head_split_hdw(kv32, he, p->hd, bf, s, g.f16));
+                SAT_TRY(sat_launch_head_split_hdw(kv32, he, p->hd, bf, s, g.f16));
                 SAT_TRY(range_stats(p, l, RS_CROSS_K, p->kc + l * per_layer, per_layer, (size_t)R * Dc, s));
                 SAT_TRY(range_stats(p, l, RS_CROSS_V, p->vct + l * per_layer, per_layer, (size_t)R * Dc, s));
                 continue;

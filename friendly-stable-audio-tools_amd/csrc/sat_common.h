@@ -356,17 +356,11 @@ int sat_launch_gemm_ph8(int epi, int build, const GemmArgs& a, hipStream_t strea
 int sat_launch_attention(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh,
                          int sq, int sk, int sq_pad, int sk_pad, hipStream_t s, unsigned char* out_scales = nullptr,
                          float q_scale = SAT_ATTN_QSCALE, int f16 = 0);
-// ---- 128-channel heads (the staged route of dit_plan.hip): head_split.hip, attention_hd128.hip.  Declared WEAK: dit_plan.hip is also linked,
-// host-only, into a test driver that defines every launcher the 64-channel routes call and knows nothing of these; there they resolve to null
-// and are never reached, in libsat_hip.so they resolve at link time.  The plan answers SAT_E_UNSUPPORTED where one is null.
-// Q pre-scaled by SAT_ATTN_QSCALE_HD128; layouts as sat_launch_attention with 128 channels per head; no MXFP8 output form
-#define SAT_ATTN_QSCALE_HD128 (0.08838834764831845f * 1.4426950408889634f)
-__attribute__((weak)) int sat_launch_attention_hd128(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int sq, int sk,
-                                                     int sq_pad, int sk_pad, hipStream_t s, int f16 = 0);
-// x: fp32 [b * S, parts * heads * 128]; he: out / kind / qscale / parts / heads / S / Spad and the [S][32] rotation tables
-__attribute__((weak)) int sat_launch_head_split_hd128(const float* x, const HeadsEpi& he, int b, hipStream_t s, int f16 = 0);
-// ---- 32- and 96-channel heads (the same staged route): head_split_hdw.hip, attention_hdw.hip.  WEAK for the same reason.  Layouts as the
-// 128-channel pair with head_dim channels per head; Q pre-scaled by sat_attn_qscale(head_dim); sk_pad a multiple of sat_attn_hdw_key_tile(head_dim)
+// ---- 32-, 96- and 128-channel heads (the staged route of dit_plan.hip): head_split_hdw.hip, attention_hdw.hip.  Declared WEAK: dit_plan.hip
+// is also linked, host-only, into a test driver that defines every launcher the 64-channel routes call and knows nothing of these; there they
+// resolve to null and are never reached, in libsat_hip.so they resolve at link time.  The plan answers SAT_E_UNSUPPORTED where one is null.
+// Layouts as sat_launch_attention with head_dim channels per head; Q pre-scaled by sat_attn_qscale(head_dim); sk_pad a multiple of
+// sat_attn_hdw_key_tile(head_dim); no MXFP8 output form
 __attribute__((weak)) int sat_launch_attention_hdw(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int head_dim, int sq,
                                                    int sk, int sq_pad, int sk_pad, hipStream_t s, int f16 = 0);
 // x: fp32 [b * S, parts * heads * head_dim]; he: out / kind / qscale / parts / heads / S / Spad and the [S][sat_rope_pairs(head_dim)] rotation tables
@@ -377,9 +371,8 @@ using namespace SAT_OPNS;
 // 64-channel heads, 24 for 96, 32 for 128
 inline int sat_rope_pairs(int head_dim) { return (head_dim / 2 > 32 ? head_dim / 2 : 32) / 2; }
 inline float sat_attn_qscale(int head_dim) { return (float)(1.4426950408889634 / sqrt((double)head_dim)); }      // log2(e) / sqrt(dim_heads)
-inline int sat_attn_hdw_key_tile(int head_dim) { return head_dim == 32 ? 128 : 64; }                                // attn_hdw_tiles.h
+inline int sat_attn_hdw_key_tile(int head_dim) { return head_dim == 32 ? 128 : 64; }                                // attn_hdw_tiles.h: 32 | 96, 128
 __attribute__((weak)) int sat_launch_rope_table_hdw(const float* inv_freq, float* cos_t, float* sin_t, int s_len, int head_dim, hipStream_t s);      // [s_len][sat_rope_pairs]
-__attribute__((weak)) int sat_launch_rope_table_hd128(const float* inv_freq, float* cos_t, float* sin_t, int s_len, hipStream_t s);      // [s_len][32]
 // range_stats.hip: the reduction of the range reports (sat_range_record) over x[r * pitch + c], r < rows, c < cols, of `dtype` elements
 // (SAT_GEMM_BF16 / SAT_GEMM_FP16 / SAT_GEMM_FP32X).  `counted` is what the record's `elements` grows by: rows * cols, or the logical count of
 // a view that also scans the zero pads of its layout.  WEAK for the same reason as the 128-channel-head launchers: null in the host test driver,
@@ -422,9 +415,6 @@ __attribute__((weak)) int sat_launch_ff_conv(const FfConvArgs& a, hipStream_t s)
 __attribute__((weak)) int sat_launch_pack_conv_taps(const float* w, void* out, int n, int k, int taps, int fmt, hipStream_t s);
 // fp32 verification mode: out [b * s_len, taps * k], out[m][j * k + c] = a[m + j - taps / 2][c], zero outside the row's sequence
 __attribute__((weak)) int sat_launch_im2col_rows_f32(const float* a, float* out, int b, int s_len, int k, int taps, hipStream_t s);
-int sat_launch_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int sq, int sk, int sq_pad,
-                                   int sk_pad, hipStream_t s);
-int sat_launch_head_split_hd128_f16(const float* x, const void* heads_epi, int b, hipStream_t s);
 int sat_launch_attention_hdw_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int head_dim, int sq, int sk,
                                  int sq_pad, int sk_pad, hipStream_t s);
 int sat_launch_head_split_hdw_f16(const float* x, const void* heads_epi, int head_dim, int b, hipStream_t s);

@@ -174,71 +174,38 @@ extern "C" int sat_attention_prescaled_f16(const void* q, const void* k, const v
     return attention_prescaled_bf16_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
 }
 
-// ---- 128-channel heads: the attention kernel and the head split of the plan's staged route
-static int attention_hd128_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
-                                int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return sat_launch_attention_hd128((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, sq, sk, sq_pad, sk_pad,
-                                      (hipStream_t)stream, f16);
-}
-extern "C" int sat_attention_hd128_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
-                                        int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return attention_hd128_impl(0, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
-}
-extern "C" int sat_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
-                                       int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
-    return attention_hd128_impl(1, q, k, vt, out, b, h, kvh, sq, sk, sq_pad, sk_pad, stream);
-}
-
-static int head_split_hd128_impl(int f16, const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch,
-                                 int32_t b, int32_t s_len, int32_t s_pad, int32_t heads, int32_t parts, sat_stream_t stream) {
-    SAT_CHECK_ARG(x && dst && kind && b > 0 && s_len > 0 && heads > 0 && parts >= 1 && parts <= 3, SAT_E_INVALID, "head_split_hd128: bad argument");
-    SAT_CHECK_ARG(s_pad % 64 == 0 && s_pad >= s_len + 3, SAT_E_INVALID, "head_split_hd128: bad dims (s_pad >= s + 3, %% 64)");
-    hipStream_t s = (hipStream_t)stream;
-    HeadsEpi he{};
-    bool rope = false;
-    for (int pt = 0; pt < parts; ++pt) {
-        SAT_CHECK_ARG(dst[pt], SAT_E_INVALID, "head_split_hd128: null destination %d", pt);
-        SAT_HIP(hipMemsetAsync(dst[pt], 0, (size_t)b * heads * s_pad * 128 * 2, s));
-        he.out[pt] = (op_t*)dst[pt];
-        he.kind[pt] = kind[pt];
-        rope = rope || (kind[pt] & 2);
-    }
-    if (rope) {
-        SAT_CHECK_ARG(inv_freq && rope_scratch, SAT_E_INVALID, "head_split_hd128: a rotating part needs inv_freq and rope_scratch");
-        he.rope_cos = rope_scratch;
-        he.rope_sin = rope_scratch + (size_t)s_len * 32;
-        SAT_TRY(sat_launch_rope_table_hd128(inv_freq, rope_scratch, rope_scratch + (size_t)s_len * 32, s_len, s));
-    }
-    he.qscale = SAT_ATTN_QSCALE_HD128; he.parts = parts; he.heads = heads; he.S = s_len; he.Spad = s_pad;
-    return sat_launch_head_split_hd128(x, he, b, s, f16);
-}
-extern "C" int sat_head_split_hd128_bf16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch,
-                                         int32_t b, int32_t s_len, int32_t s_pad, int32_t heads, int32_t parts, sat_stream_t stream) {
-    return head_split_hd128_impl(0, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, parts, stream);
-}
-extern "C" int sat_head_split_hd128_f16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch,
-                                        int32_t b, int32_t s_len, int32_t s_pad, int32_t heads, int32_t parts, sat_stream_t stream) {
-    return head_split_hd128_impl(1, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, parts, stream);
-}
-
-// ---- 32- and 96-channel heads: the same pair (attention_hdw.hip, head_split_hdw.hip), and the fp32 verification kernels with a head width
+// ---- 32-, 96- and 128-channel heads: the attention kernel and the head split of the plan's staged route (attention_hdw.hip,
+// head_split_hdw.hip), and the fp32 verification kernels with a head width.  The *_hd128_* entry points pass 128; the *_hdw_* ones take 32 or 96
 static int attention_hdw_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
                               int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
     return sat_launch_attention_hdw((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, head_dim, sq, sk, sq_pad, sk_pad,
                                     (hipStream_t)stream, f16);
 }
+extern "C" int sat_attention_hd128_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
+                                        int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_hdw_impl(0, q, k, vt, out, b, h, kvh, 128, sq, sk, sq_pad, sk_pad, stream);
+}
+extern "C" int sat_attention_hd128_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t sq,
+                                       int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    return attention_hdw_impl(1, q, k, vt, out, b, h, kvh, 128, sq, sk, sq_pad, sk_pad, stream);
+}
+static int hdw_entry_width(const char* what, int32_t head_dim) {
+    SAT_CHECK_ARG(head_dim == 32 || head_dim == 96, SAT_E_UNSUPPORTED, "%s: dim_heads %d (this entry point takes 32 and 96)", what, head_dim);
+    return 0;
+}
 extern "C" int sat_attention_hdw_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
                                       int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    SAT_TRY(hdw_entry_width("attention_hdw", head_dim));
     return attention_hdw_impl(0, q, k, vt, out, b, h, kvh, head_dim, sq, sk, sq_pad, sk_pad, stream);
 }
 extern "C" int sat_attention_hdw_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
                                      int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream) {
+    SAT_TRY(hdw_entry_width("attention_hdw", head_dim));
     return attention_hdw_impl(1, q, k, vt, out, b, h, kvh, head_dim, sq, sk, sq_pad, sk_pad, stream);
 }
 
 static int head_split_hdw_impl(int f16, const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch, int32_t b,
                                int32_t s_len, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream) {
-    SAT_CHECK_ARG(head_dim == 32 || head_dim == 96, SAT_E_UNSUPPORTED, "head_split_hdw: dim_heads %d (this kernel is built for 32 and 96)", head_dim);
     SAT_CHECK_ARG(x && dst && kind && b > 0 && s_len > 0 && heads > 0 && parts >= 1 && parts <= 3, SAT_E_INVALID, "head_split_hdw: bad argument");
     SAT_CHECK_ARG(s_pad % 64 == 0 && s_pad >= s_len + 3, SAT_E_INVALID, "head_split_hdw: bad dims (s_pad >= s + 3, %% 64)");
     hipStream_t s = (hipStream_t)stream;
@@ -265,12 +232,22 @@ static int head_split_hdw_impl(int f16, const float* x, const float* inv_freq, v
     he.qscale = sat_attn_qscale(head_dim); he.parts = parts; he.heads = heads; he.S = s_len; he.Spad = s_pad;
     return sat_launch_head_split_hdw(x, he, head_dim, b, s, f16);
 }
+extern "C" int sat_head_split_hd128_bf16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch,
+                                         int32_t b, int32_t s_len, int32_t s_pad, int32_t heads, int32_t parts, sat_stream_t stream) {
+    return head_split_hdw_impl(0, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, 128, parts, stream);
+}
+extern "C" int sat_head_split_hd128_f16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch,
+                                        int32_t b, int32_t s_len, int32_t s_pad, int32_t heads, int32_t parts, sat_stream_t stream) {
+    return head_split_hdw_impl(1, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, 128, parts, stream);
+}
 extern "C" int sat_head_split_hdw_bf16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch, int32_t b,
                                        int32_t s_len, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream) {
+    SAT_TRY(hdw_entry_width("head_split_hdw", head_dim));
     return head_split_hdw_impl(0, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, head_dim, parts, stream);
 }
 extern "C" int sat_head_split_hdw_f16(const float* x, const float* inv_freq, void* const* dst, const int32_t* kind, float* rope_scratch, int32_t b,
                                       int32_t s_len, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream) {
+    SAT_TRY(hdw_entry_width("head_split_hdw", head_dim));
     return head_split_hdw_impl(1, x, inv_freq, dst, kind, rope_scratch, b, s_len, s_pad, heads, head_dim, parts, stream);
 }
 extern "C" int sat_split_heads_f32_hdw(const float* src, float* d0, float* d1, float* d2, int32_t b, int32_t s_len, int32_t parts, int32_t heads,

@@ -645,7 +645,7 @@ int sat_attention_prescaled_bf16(const void* q_dev, const void* k_dev, const voi
  * sat_attention_hd128_*: arguments and layouts of sat_attention_prescaled_* with 128 channels per head -- q [b, h, sq_pad, 128]
  * pre-scaled by log2(e) / sqrt(128), k [b, kvh, sk_pad, 128] and vt [b, kvh, 128, sk_pad] in the key-side layout (sequence i from row /
  * column (i * sk) & 3, vt's key index permuted inside aligned groups of 16 as [0-3, 8-11, 4-7, 12-15]), zero pads, sq_pad % 128 == 0,
- * sk_pad % 64 == 0, sk_pad >= sk + 3; out [b * sq, h * 128]. */
+ * sk_pad % 64 == 0, sk_pad >= sk + 3; out [b * sq, h * 128].  h and b above 65535 (the launch grid) are SAT_E_UNSUPPORTED. */
 int sat_attention_hd128_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                              int32_t b, int32_t h, int32_t kvh, int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad,
                              sat_stream_t stream);

@@ -5,7 +5,6 @@ scratch, and the LDS tile maps of the attention kernel are bijections.  No GPU."
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -16,6 +15,7 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 
 import cases  # noqa: E402
 import dit_head_dim_cases as HC  # noqa: E402
+import dit_head_width_units as WU  # noqa: E402
 from dit_family_host import build as _build, check_state_dict_keys  # noqa: E402
 
 CSRC = os.path.join(os.path.dirname(HERE), "friendly-stable-audio-tools_amd", "csrc")
@@ -100,64 +100,30 @@ def _kernels(src, defines, tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
 @pytest.mark.parametrize("defines", [[], ["-DSAT_OPERAND_F16"]], ids=["bf16", "f16"])
-@pytest.mark.parametrize("src, kernel", [("attention_hd128.hip", "attention_hd128_kernel"), ("head_split.hip", "head_split_hd128_kernel")])
+@pytest.mark.parametrize("src, kernel", [("attention_hdw.hip", "attention_hdw_kernelILi128E"), ("head_split_hdw.hip", "head_split_hdw_kernelILi128E")],
+                         ids=["attention", "head_split"])
 def test_hd128_kernels_use_no_scratch(src, kernel, defines, tmp_path):
-    """512 threads per workgroup = 256 VGPRs at most; the 64-register O^T accumulator must not push anything into private memory."""
+    """512 threads per workgroup = 256 VGPRs at most; the 64-register O^T accumulator must not push anything into private memory.  The head
+    split at 128 channels holds the transposed image alone in LDS, 128 rows of 64 + 8 elements: no fp32 staging block as for 32 and 96, which
+    would halve the workgroups resident per CU."""
     meta = _kernels(src, defines, str(tmp_path))
     assert any(kernel in k for k in meta), sorted(meta)
     for name, m in meta.items():
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, f"{name}: {m}"
         assert m["vgpr_count"] <= 256, f"{name}: {m}"
-        assert m["group_segment_fixed_size"] <= 64 * 1024, f"{name}: {m}"          # (the attention ring is dynamic LDS: attn_hd128_tiles.h)
-
-
-_TILE_DUMP = r"""
-#include <stdio.h>
-#include "attn_hd128_tiles.h"
-using namespace attn128;
-static_assert(STAGE_BYTES == 32 * 1024 && LDS_BYTES == STAGES * STAGE_BYTES && LDS_BYTES <= 160 * 1024, "ring");
-static_assert(k_tile_off(0, 0) == 0 && vt_tile_off(0, 0) == 0, "constexpr in host code");
-int main() {
-    printf("K %d %d %d\n", KV_TILE, K_ROW_BYTES / 16, K_TILE_BYTES);
-    for (int r = 0; r < KV_TILE; ++r) for (int c = 0; c < K_ROW_BYTES / 16; ++c) printf("%d %d %d\n", r, c, k_tile_off(r, c));
-    printf("V %d %d %d\n", HEAD_DIM, VT_ROW_BYTES / 16, VT_TILE_BYTES);
-    for (int r = 0; r < HEAD_DIM; ++r) for (int c = 0; c < VT_ROW_BYTES / 16; ++c) printf("%d %d %d\n", r, c, vt_tile_off(r, c));
-}
-"""
-# lanes of the four 16-lane groups one ds_read_b128 is served in (gfx950)
-_B128_GROUPS = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27], [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]]
-_B128_GROUPS += [[l + 32 for l in g] for g in _B128_GROUPS]
+        assert m["group_segment_fixed_size"] <= 64 * 1024, f"{name}: {m}"          # (the attention ring is dynamic LDS: attn_hdw_tiles.h)
+        if "head_split_hdw_kernelILi128E" in name:
+            assert m["group_segment_fixed_size"] == 128 * (64 + 8) * 2 == 18432, f"{name}: {m}"
 
 
 def test_lds_tile_maps_are_bijections_and_conflict_free(tmp_path):
-    """attn_hd128_tiles.h compiled as plain host C++: every (row, 16-byte chunk) of the K tile (64 x 16) and of the V^T tile (128 x 8) has
-    its own 16-byte-aligned slot inside the tile, a row's chunks stay inside the row (the LDS-DMA writes whole rows), and the fragment reads
-    of the kernel (lane l: row 32 kb + (l & 31), chunk 2 t + (l >> 5)) put the 16 lanes of every ds_read_b128 group on 16 different slots
-    of the 256-byte bank row."""
-    cxx = shutil.which("g++") or "/opt/rocm/lib/llvm/bin/clang++"
-    src, exe = tmp_path / "tiles.cpp", tmp_path / "tiles"
-    src.write_text(_TILE_DUMP)
-    subprocess.run([cxx, "-std=c++17", "-I", CSRC, str(src), "-o", str(exe)], check=True, capture_output=True)
-    lines = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")[:-1]
-    tiles, cur = {}, None
-    for ln in lines:
-        if ln[0] in "KV":
-            _, rows, chunks, size = ln.split()
-            cur = tiles[ln[0]] = dict(rows=int(rows), chunks=int(chunks), size=int(size), off={})
-        else:
-            r, c, o = map(int, ln.split())
-            cur["off"][(r, c)] = o
-    assert (tiles["K"]["rows"], tiles["K"]["chunks"], tiles["K"]["size"]) == (64, 16, 16384)
-    assert (tiles["V"]["rows"], tiles["V"]["chunks"], tiles["V"]["size"]) == (128, 8, 16384)
-    for t in tiles.values():
-        off = t["off"]
-        assert len(off) == t["rows"] * t["chunks"] == t["size"] // 16
-        assert all(o % 16 == 0 and 0 <= o <= t["size"] - 16 for o in off.values())
-        assert len(set(off.values())) == len(off)
-        row_bytes = t["chunks"] * 16
-        assert all(o // row_bytes == r for (r, _), o in off.items())
-        for first_row in range(0, t["rows"], 32):
-            for chunk_pair in range(t["chunks"] // 2):
-                for group in _B128_GROUPS:
-                    slots = {off[(first_row + (l & 31), 2 * chunk_pair + (l >> 5))] % 256 // 16 for l in group}
-                    assert len(slots) == 16, (first_row, chunk_pair, group)
+    """attn_hdw_tiles.h at W = 128 compiled as plain host C++ (WU.check_lds_tile_maps): every (row, 16-byte chunk) of the K tile (64 x 16) and
+    of the V^T tile (128 x 8) has its own 16-byte-aligned slot inside the tile, a row's chunks stay inside the row (the LDS-DMA writes whole
+    rows), every LDS-DMA lane fetches the chunk whose slot it lands on -- no hole, no spare row --, and the fragment reads of the kernel (lane
+    l: row 32 kb + (l & 31), chunk 2 t + (l >> 5)) put the 16 lanes of every ds_read_b128 group on 16 different slots of the 256-byte bank
+    row."""
+    k, v = WU.check_lds_tile_maps(CSRC, str(tmp_path), (128,))
+    assert (k["kind"], k["rows"], k["chunks"], k["size"], k["pieces"]) == ("K", 64, 16, 16384, 2)
+    assert (v["kind"], v["rows"], v["chunks"], v["size"], v["pieces"]) == ("V", 128, 8, 16384, 2)
+    for t in (k, v):
+        assert len(t["off"]) == t["rows"] * t["chunks"] == t["size"] // 16 and t["holes"] == 0

@@ -1,5 +1,5 @@
-"""DiTs with 128-channel attention heads (embed_dim == 128 * num_heads) on the device: the attention kernel (csrc/attention_hd128.hip) and
-the head split (csrc/head_split.hip) alone, then the plan's staged route against the REFERENCE's own outputs
+"""DiTs with 128-channel attention heads (embed_dim == 128 * num_heads) on the device: the attention kernel (csrc/attention_hdw.hip) and
+the head split (csrc/head_split_hdw.hip) at that width alone, then the plan's staged route against the REFERENCE's own outputs
 (tests/golden/dit_head_dim_small.npz: tests/golden/make_golden_dit_families.py head_dim) at the reduced-DiT gates of the harness
 (tests/dit_family_gpu.py), the fused prepare_generation + denoise step and generate_diffusion_cond."""
 import ctypes
@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 import dit_head_dim_cases as HC  # noqa: E402
 import mask_edge  # noqa: E402
 from dit_family_gpu import Harness, generate, reduced_model  # noqa: E402
+from dit_head_width_units import _pad_heads, _vt_perm  # noqa: E402
 from util import FORMATS, SUITE, assert_close, assert_close_sliced, guarded, rel_l2  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -30,21 +31,6 @@ def _lib():
 
 def _rand(shape, seed):
     return torch.randn(shape, generator=torch.Generator().manual_seed(seed))
-
-
-def _vt_perm(n):
-    p = torch.arange(n)
-    return (p & ~12) | ((p & 4) << 1) | ((p & 8) >> 1)
-
-
-def _pad_heads(x, s_pad, key_side=False):
-    # [B,H,S,128] -> zero-padded [B,H,s_pad,128]; key-side tensors (K, V) of sequence b start at row (b*S) & 3
-    b, h, s, d = x.shape
-    out = torch.zeros((b, h, s_pad, d), dtype=x.dtype)
-    for i in range(b):
-        ob = (i * s) & 3 if key_side else 0
-        out[i, :, ob:ob + s] = x[i]
-    return out
 
 
 def _attention(dev, fmt, q, k, v):

@@ -1,4 +1,4 @@
-"""What 128-channel attention heads cost: (1) the attention kernel of csrc/attention_hd128.hip beside the 64-channel one at the same FLOPs and
+"""What 128-channel attention heads cost: (1) the attention kernel of csrc/attention_hdw.hip at W = 128 beside the 64-channel one at the same FLOPs and
 bytes -- two sequences of S = 1025, H = 12 heads of 128 against H = 24 heads of 64 (D 1536), and H = 8 heads of 128 (D 1024); (2) one
 sampler step (`denoise` = one sat_dit_denoise_cfg call) of a full-depth embed_dim 1536 / num_heads 12 DiT at T = 1024, one prompt with CFG 7,
 beside the shipped 24-head model with set_layernorm_fusion(False).set_cross_attention_fusion(False) -- the like-for-like route: what is left
