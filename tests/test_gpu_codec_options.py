@@ -12,7 +12,7 @@ import sys
 import pytest
 import torch
 
-from util import assert_close, rel_l2
+from util import NAN_BYTE, WORKSPACE_FILLS, assert_bit_equal, assert_close, rel_l2
 from test_gpu_codec_fp32 import TOL as TOL_FP32
 from test_gpu_models import CODEC
 
@@ -28,7 +28,6 @@ pytestmark = pytest.mark.gpu
 GATE = {"bf16": CODEC["bf16"][1], "fp16": CODEC["fp16"][1], "fp32": TOL_FP32}
 FMTS = ["fp16", "bf16", "fp32"]
 NAMES = sorted(GO.CONFIGS)
-NAN_BYTE = 255          # 0xFFFF is a NaN in fp16 and bf16, 0xFFFFFFFF in fp32
 
 
 def _codec(name, dev, fmt):
@@ -78,22 +77,30 @@ def test_decode_and_encode_vs_reference(dev, golden, name, fmt):
 @pytest.mark.parametrize("fmt", FMTS)
 def test_pad_channels_do_not_read_stale_workspace(dev, golden, fmt):
     """narrow_all (widths 48 / 96 / 144, latent 20) pads every tensor of the workspace; the pad channels must be WRITTEN as zeros by
-    the producers, not inherited: with the cached workspace filled with NaN patterns before the call the gate still holds."""
+    the producers, not inherited: with the cached workspace filled with NaN patterns before the call the gate still holds -- and, under
+    every fill of util.WORKSPACE_FILLS, the outputs are the bits of the un-poisoned run of the same module (the gate alone dilutes one stale
+    pad row among all the correct ones)."""
     name = "narrow_all"
     model = _codec(name, dev, fmt)
     z, _, audio = GO.inputs(name)
-    model.decode(z.to(dev))
-    model.encoder(audio.to(dev))
-    for part in (model.decoder, model.encoder):
-        assert part._ws is not None and part._ws.dtype == torch.uint8
-        part._ws.fill_(NAN_BYTE)
-    ws_d, ws_e = model.decoder._ws, model.encoder._ws
-    got = model.decode(z.to(dev))
-    lat = model.encoder(audio.to(dev))
-    assert model.decoder._ws is ws_d and model.encoder._ws is ws_e      # the poisoned buffers are the ones that ran
-    e = assert_close(f"narrow_all decode on a NaN workspace ({fmt})", got, golden[f"{name}/decode"], GATE[fmt])
-    e2 = assert_close(f"narrow_all encode on a NaN workspace ({fmt})", lat, golden[f"{name}/encode"], GATE[fmt])
-    print(f"\n[narrow_all on a NaN-filled workspace, {fmt}] decode {e:.2e}, encode {e2:.2e}")
+    clean_d = model.decode(z.to(dev))
+    clean_e = model.encoder(audio.to(dev))
+    assert_bit_equal(f"narrow_all decode twice ({fmt}): the call is not repeatable", model.decode(z.to(dev)), clean_d)
+    assert_bit_equal(f"narrow_all encode twice ({fmt}): the call is not repeatable", model.encoder(audio.to(dev)), clean_e)
+    for byte in WORKSPACE_FILLS:
+        for part in (model.decoder, model.encoder):
+            assert part._ws is not None and part._ws.dtype == torch.uint8
+            part._ws.fill_(byte)
+        ws_d, ws_e = model.decoder._ws, model.encoder._ws
+        got = model.decode(z.to(dev))
+        lat = model.encoder(audio.to(dev))
+        assert model.decoder._ws is ws_d and model.encoder._ws is ws_e      # the poisoned buffers are the ones that ran
+        if byte == NAN_BYTE:
+            e = assert_close(f"narrow_all decode on a NaN workspace ({fmt})", got, golden[f"{name}/decode"], GATE[fmt])
+            e2 = assert_close(f"narrow_all encode on a NaN workspace ({fmt})", lat, golden[f"{name}/encode"], GATE[fmt])
+            print(f"\n[narrow_all on a NaN-filled workspace, {fmt}] decode {e:.2e}, encode {e2:.2e}")
+        assert_bit_equal(f"narrow_all decode on a workspace of 0x{byte:02X} bytes ({fmt})", got, clean_d)
+        assert_bit_equal(f"narrow_all encode on a workspace of 0x{byte:02X} bytes ({fmt})", lat, clean_e)
 
 
 # ------------------------------------------------------------------------------- the reference's 16-channel goldens, on the device

@@ -195,3 +195,66 @@ def test_pad_key_at_ordinary_scores_passes_the_whole_tensor_gate():
     msg = _fails(assert_close_sliced, "attention_hd128 with attended pads", bad.view(b, sq, h, 128), want.view(b, sq, h, 128), fmt.tol(5e-3), (0, 1, 2),
                  fmt.round)
     assert msg and "slice (" in msg
+
+
+# ------------------------------------------------------------------------------------ bit equality and the workspace fill patterns
+def test_workspace_fill_patterns_decode_to_what_they_claim():
+    """WORKSPACE_FILLS, read as the formats the plans keep in a workspace."""
+    from util import NAN_BYTE, WORKSPACE_FILLS, fill_pattern
+    assert sorted(WORKSPACE_FILLS) == [0x00, 0x3C, 0x7B, 0xFF] and NAN_BYTE == 0xFF
+    assert all(isinstance(reason, str) and reason and "\n" not in reason for reason in WORKSPACE_FILLS.values())
+    value = lambda byte, dtype: fill_pattern(byte, dtype, 3).double()
+    for dtype in (torch.float16, torch.bfloat16, torch.float32):
+        assert fill_pattern(0x00, dtype, 3).shape == (3,)
+        assert torch.equal(value(0x00, dtype), torch.zeros(3, dtype=torch.float64)) and not torch.signbit(fill_pattern(0x00, dtype)).any()
+        assert torch.isnan(value(0xFF, dtype)).all()
+        assert torch.isfinite(value(0x7B, dtype)).all() and torch.isfinite(value(0x3C, dtype)).all()
+    # 0x7B7B: 2^15 (1 + 891 / 1024) as fp16, 2^119 (1 + 123 / 128) as bf16, 2^119 (1 + 0x7B7B7B / 2^23) as fp32
+    assert value(0x7B, torch.float16)[0].item() == 61280.0
+    assert value(0x7B, torch.bfloat16)[0].item() == 2.0 ** 119 * (1 + 123 / 128)
+    assert value(0x7B, torch.float32)[0].item() == 2.0 ** 119 * (1 + 0x7B7B7B / 2 ** 23)
+    assert 1.3e36 < value(0x7B, torch.bfloat16)[0].item() < 1.31e36 and 1.3e36 < value(0x7B, torch.float32)[0].item() < 1.31e36
+    # one multiply by itself overflows each of them
+    for dtype in (torch.float16, torch.bfloat16, torch.float32):
+        assert torch.isinf(fill_pattern(0x7B, dtype) * fill_pattern(0x7B, dtype)).all()
+    # 0x3C3C: 1 + 60 / 1024 as fp16, 2^-7 (1 + 60 / 128) as bf16, 2^-7 (1 + 0x3C3C3C / 2^23) as fp32
+    assert value(0x3C, torch.float16)[0].item() == 1 + 60 / 1024
+    assert value(0x3C, torch.bfloat16)[0].item() == 2.0 ** -7 * (1 + 60 / 128)
+    assert value(0x3C, torch.float32)[0].item() == 2.0 ** -7 * (1 + 0x3C3C3C / 2 ** 23)
+    if hasattr(torch, "float8_e4m3fn"):
+        assert torch.isnan(value(0xFF, torch.float8_e4m3fn)).all() and value(0x7B, torch.float8_e4m3fn)[0].item() == 352.0
+
+
+def test_assert_bit_equal_accepts_a_clone_and_names_one_flipped_bit():
+    from util import assert_bit_equal
+    for dtype in (torch.float32, torch.float16, torch.bfloat16):
+        x = _rand((1000, 1000), 70).to(dtype)
+        x[3, 5], x[999, 999], x[0, 0] = float("nan"), float("inf"), -0.0
+        assert_bit_equal("clone", x.clone(), x)          # NaNs with the same bits are equal
+        bits = {4: torch.int32, 2: torch.int16}[x.element_size()]
+        y = x.clone()
+        y.view(bits)[617, 283] ^= 1          # the lowest mantissa bit of one element in 10^6
+        assert x[617, 283].item() != y[617, 283].item()
+        msg = _fails(assert_bit_equal, "one ulp", y, x)
+        assert msg and "1 of 1000000 elements differ" in msg and "the first at (617, 283)" in msg, msg
+        assert repr(y[617, 283].item()) in msg and repr(x[617, 283].item()) in msg and "largest absolute difference" in msg
+        ulp = abs(y[617, 283].double().item() - x[617, 283].double().item())
+        assert f"{ulp:.3e}" in msg
+    # a NaN whose payload differs is a difference; so is a NaN against a number
+    a = torch.tensor([1.0, float("nan")])
+    b = a.clone()
+    b.view(torch.int32)[1] ^= 1
+    assert torch.isnan(b[1]) and _fails(assert_bit_equal, "payload", b, a)
+    assert "largest absolute difference inf" in _fails(assert_bit_equal, "nan", torch.tensor([1.0, 2.0]), a)
+    # integer images (e4m3 bytes) compare as they are
+    assert_bit_equal("bytes", torch.arange(256, dtype=torch.uint8), torch.arange(256, dtype=torch.uint8))
+    assert _fails(assert_bit_equal, "bytes", torch.zeros(4, dtype=torch.uint8), torch.tensor([0, 0, 1, 0], dtype=torch.uint8))
+
+
+def test_assert_bit_equal_tells_the_two_zeros_apart():
+    from util import assert_bit_equal
+    assert torch.equal(torch.tensor([0.0]), torch.tensor([-0.0]))          # what torch.equal would let through
+    msg = _fails(assert_bit_equal, "zeros", torch.tensor([1.0, -0.0]), torch.tensor([1.0, 0.0]))
+    assert msg and "1 of 2 elements differ" in msg and "the first at (1,)" in msg and "-0.0" in msg
+    with pytest.raises(AssertionError):
+        assert_bit_equal("dtype", torch.zeros(2), torch.zeros(2, dtype=torch.float16))

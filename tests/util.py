@@ -205,6 +205,50 @@ def guarded(shape, dtype, device, init=None, name="output", pitch=None):
     return Guarded(shape, dtype, device, init=init, name=name, pitch=pitch)
 
 
+# --------------------------------------------------------------------------------------- bit equality, poisoned workspaces
+# The output of a plan call is a pure function of weights and inputs (no atomics on the compute path, a bit-deterministic K-split reduce),
+# so "does not depend on the workspace's bytes or on earlier calls" is asserted bit for bit: tests/test_gpu_state_independence.py.
+NAN_BYTE = 0xFF
+# byte -> why a uint8 workspace is filled with it before a call
+WORKSPACE_FILLS = {
+    0x00: "the baseline: what a pad reads as when somebody did clear it",
+    NAN_BYTE: "a NaN in fp32, fp16, bf16, e4m3 and E8M0: any arithmetic on a stale element poisons the result",
+    0x7B: "large but finite (61280 as fp16, about 1.3e36 as bf16 / fp32, 352 as e4m3): survives a max or a compare-based mask that drops a NaN",
+    0x3C: "ordinary magnitude (about 1.06 as fp16, 0.0115 as bf16 / fp32): garbage that no range check would ever flag",
+}
+
+
+def fill_pattern(byte, dtype, n=1):
+    """n elements of ``dtype`` whose every byte is ``byte``: what a filled uint8 workspace reads as in that format."""
+    item = torch.empty((), dtype=dtype).element_size()
+    return torch.full((n * item,), byte, dtype=torch.uint8).view(dtype)
+
+
+def _bits(x):
+    x = x.detach().cpu().contiguous()
+    return x if not x.dtype.is_floating_point and x.dtype != torch.bool else x.view(_BITS[x.element_size()])
+
+
+def assert_bit_equal(name, got, want):
+    """got and want hold the same bit patterns (compared as same-width integers on the CPU): +0.0 and -0.0 differ, two NaNs with the same
+    bits are equal.  On failure: how many elements differ, the first differing index, both values there, the largest absolute difference."""
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{name}: {tuple(got.shape)} {got.dtype} vs {tuple(want.shape)} {want.dtype}"
+    g, w = _bits(got), _bits(want)
+    diff = g != w
+    n = int(diff.sum())
+    if n == 0:
+        return
+    flat = int(diff.reshape(-1).nonzero()[0, 0])
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(flat), diff.shape)) if diff.dim() else ()
+    gv, wv = got.detach().cpu().reshape(-1)[flat], want.detach().cpu().reshape(-1)[flat]
+    d = (got.detach().cpu().double() - want.detach().cpu().double()).abs()
+    d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)      # a NaN on one side only is as far off as it gets
+    d = torch.where(diff, d, torch.zeros_like(d))
+    raise AssertionError(f"{name}: {n} of {diff.numel()} elements differ in their bits, the first at {idx}: got {gv.item()!r} "
+                         f"(0x{int(g.reshape(-1)[flat]) & (2 ** (8 * g.element_size()) - 1):x}), want {wv.item()!r} "
+                         f"(0x{int(w.reshape(-1)[flat]) & (2 ** (8 * w.element_size()) - 1):x}); largest absolute difference {d.max().item():.3e}")
+
+
 def e4m3_code_distance(got_bytes, want_bytes):
     """|distance in e4m3 codes| per element between two uint8 images (sign-magnitude order; +0 and -0 coincide)."""
     def order(b):
