@@ -1,6 +1,9 @@
 // Flash-style attention core for the DiT: softmax(q k^T / sqrt(64)) v,
-// non-causal, no mask, GQA by head index (models/transformer.py:496-536; the reference's
+// no mask, GQA by head index (models/transformer.py:496-536; the reference's
 // CPU branch is einsum + softmax(fp32) + einsum, :525-536; GQA repeat_interleave :512-515).
+// Non-causal by default; the CAUSAL instantiations (sat_launch_attention_causal, at the end of the file) are the self-attention of a
+// causal model: query i sees the keys j <= i of its sequence, and the key tiles above a workgroup's last query are never walked
+// (attn_causal.h has the ranges, the template parameter's comment below the rules).
 //
 // gfx950 design.  One workgroup = 8 waves = 128 queries of one (batch, head) x 2 key ranges: waves 0-3 ("group 0") walk the first
 // half of the KV tiles, waves 4-7 the second half, for the SAME 4 x 32 queries; the two partial results (running max, row sum,
@@ -52,7 +55,12 @@ __device__ __forceinline__ void swap_halves(unsigned& lo_run, unsigned& hi_run) 
 // MODE: the softmax recurrence of attn_core.h -- 1 (default): standing reference, the row sum is the overflow check; 2: the same with
 // the reference carried through the matrix pipe, for a Q its producer wrote pre-scaled (scale_log2 == 1; anything else is multiplied
 // into Q here and rounded to bf16 a second time: experiments).
-template <bool MX8, int DBG = 0, int NGRP = 2, int MODE = 1>
+// CAUSAL: self-attention of a causal model (Sq == Sk, query i sees the keys j <= i of its sequence; attn_causal.h has the ranges).  The
+// workgroup walks only the tiles up to the diagonal of its last query -- the two-group layout halves THAT range --, and inside a tile every
+// wave skips the 32-key blocks above its own last query (it still copies its pieces and joins every barrier), masks per element in the
+// blocks the diagonal crosses and runs the blocks below it as they are.  MODE 1 only: MODE 2 with the flag does not fit 128 VGPRs, so a
+// pre-scaled Q runs MODE 1 with scale_log2 == 1.  No MXFP8 output form.
+template <bool MX8, int DBG = 0, int NGRP = 2, int MODE = 1, bool CAUSAL = false>
 __global__ __launch_bounds__(512, 2) void attention_kernel(const op_t* __restrict__ q, const op_t* __restrict__ k,
                                                            const op_t* __restrict__ vt, op_t* __restrict__ out,
                                                            unsigned char* __restrict__ out_scales,
@@ -100,7 +108,7 @@ __global__ __launch_bounds__(512, 2) void attention_kernel(const op_t* __restric
     // K rows / V^T columns of sequence b start at ob = (b*Sk) & 3 (see EPI_HEADS in gemm_bf16.hip)
     const int ob = (b * Sk) & 3;
     const int k_end = ob + Sk;
-    const int n_tiles = (k_end + KV_TILE - 1) / KV_TILE;
+    const int n_tiles = CAUSAL ? attnc::tiles_walked(bx * QB, QB, ob, Sk, KV_TILE) : (k_end + KV_TILE - 1) / KV_TILE;
     const int n0 = NGRP == 2 ? (n_tiles + 1) >> 1 : n_tiles;   // group 0: tiles [0, n0), group 1: [n0, n_tiles)
     const int t_first = grp ? n0 : 0;
     const int t_count = grp ? n_tiles - n0 : n0;
@@ -147,7 +155,10 @@ __global__ __launch_bounds__(512, 2) void attention_kernel(const op_t* __restric
         const char* sk = ring + stage * STAGE_BYTES;
         const char* sv = sk + KV_TILE * 128;
         const bool edge = (tile == 0 && ob != 0) || (tile == n_tiles - 1 && (k_end & (KV_TILE - 1)) != 0);
-        attn::tile<MODE, DBG>(st, qf, sk, sv, edge, tile * KV_TILE, ob, k_end, tile == t_first, scale_log2, l31, half);
+        if constexpr (CAUSAL)
+            attn::tile<MODE, DBG, true>(st, qf, sk, sv, false, tile * KV_TILE, ob, attnc::key_end(qi, ob, Sk), tile == t_first, scale_log2, l31, half,
+                                        __builtin_amdgcn_readfirstlane(bx * QB + wq * 32), Sk);
+        else attn::tile<MODE, DBG>(st, qf, sk, sv, edge, tile * KV_TILE, ob, k_end, tile == t_first, scale_log2, l31, half);
     };
 
     if constexpr (NGRP == 1) {
@@ -393,6 +404,47 @@ int SAT_OPNS::sat_launch_attention(const op_t* q, const op_t* k, const op_t* vt,
     } else {
         SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(attention_kernel<false>), ATT_LDS));
         hipLaunchKernelGGL(attention_kernel<false>, grid, dim3(512), ATT_LDS, s, q, k, vt, out, out_scales, h, kvh, sq, sk, sq_pad, sk_pad, scale_log2);
+    }
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+// Causal self-attention (sq == sk == s_len): the checks and the layout rule of sat_launch_attention, the CAUSAL instantiations.  Both layouts run
+// MODE 1; a pre-scaled Q (q_scale == 1) multiplies its scores by 1.
+#ifdef SAT_OPERAND_F16
+int sat_launch_attention_causal_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int s_len, int sq_pad, int sk_pad,
+                                    hipStream_t s, float q_scale) {
+    return f16::sat_launch_attention_causal((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, s_len, sq_pad, sk_pad, s, q_scale, 1);
+}
+#endif
+
+int SAT_OPNS::sat_launch_attention_causal(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int s_len, int sq_pad,
+                                          int sk_pad, hipStream_t s, float q_scale, int f16) {
+#ifndef SAT_OPERAND_F16
+    if (f16) return sat_launch_attention_causal_f16(q, k, vt, out, b, h, kvh, s_len, sq_pad, sk_pad, s, q_scale);
+#else
+    SAT_CHECK_ARG(f16, SAT_E_INVALID, "attention (causal): the fp16 build takes fp16 tensors and writes fp16");
+#endif
+    SAT_CHECK_ARG(q && k && vt && out, SAT_E_INVALID, "attention (causal): null pointer");
+    SAT_CHECK_ARG(b > 0 && h > 0 && kvh > 0 && h % kvh == 0, SAT_E_INVALID, "attention (causal): bad heads %d/%d", h, kvh);
+    SAT_CHECK_ARG(h <= 65535 && b <= 65535, SAT_E_UNSUPPORTED, "attention (causal): %d heads / %d sequences exceed the grid", h, b);
+    SAT_CHECK_ARG(s_len > 0 && sq_pad >= s_len && sk_pad >= s_len, SAT_E_INVALID, "attention (causal): bad lengths");
+    SAT_CHECK_ARG(sq_pad % Q_BLOCK == 0 && sk_pad % KV_TILE == 0, SAT_E_INVALID,
+                  "attention (causal): sq_pad %% 128 and sk_pad %% 64 must be 0 (got %d, %d)", sq_pad, sk_pad);
+    SAT_CHECK_ARG(sk_pad >= s_len + 3, SAT_E_INVALID, "attention (causal): sk_pad must be >= s + 3 (key-side shift), got %d for s=%d", sk_pad, s_len);
+    SAT_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)out) & 15) == 0, SAT_E_INVALID,
+                  "attention (causal): pointers must be 16-byte aligned");
+    const long wg1 = (long)cdiv(s_len, 256) * h * b;
+    const bool one_group = wg1 >= 1024 || s_len <= 512 || (q_scale == 1.0f && wg1 >= 200 && s_len <= 2048);      // the rule of sat_launch_attention
+    unsigned char* const no_scales = nullptr;
+    if (one_group) {
+        SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(attention_kernel<false, 0, 1, 1, true>), 3 * STAGE_BYTES));
+        hipLaunchKernelGGL((attention_kernel<false, 0, 1, 1, true>), dim3(cdiv(s_len, 256), h, b), dim3(512), 3 * STAGE_BYTES, s, q, k, vt, out, no_scales,
+                           h, kvh, s_len, s_len, sq_pad, sk_pad, q_scale);
+    } else {
+        SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(attention_kernel<false, 0, 2, 1, true>), ATT_LDS));
+        hipLaunchKernelGGL((attention_kernel<false, 0, 2, 1, true>), dim3(cdiv(s_len, Q_BLOCK), h, b), dim3(512), ATT_LDS, s, q, k, vt, out, no_scales, h,
+                           kvh, s_len, s_len, sq_pad, sk_pad, q_scale);
     }
     SAT_LAUNCH_CHECK();
     return 0;

@@ -17,6 +17,7 @@
 //           [1, 0, ...] x [-m_ref, 0, ...] makes the accumulator come out as log2-domain score minus reference, p = exp2(acc): the 16
 //           v_fma_f32 disappear from the VALU stream, the matrix pipe has the slack.  m_ref is kept representable in the operand type (bf16 / fp16).
 #pragma once
+#include "attn_causal.h"
 #include "sat_common.h"
 
 namespace attn {
@@ -63,11 +64,23 @@ struct State {
 // layout of lds_tile_off.  edge: some keys of the tile lie outside [k_lo, k_hi) and are masked; key_base = the tile's first key.
 // first: the sequence's first tile for this wave (MODE 2 fixes a real reference there whatever the sums say: underflow safety).
 // DBG (experiments build, wrong results): 1 no exp / max / sum; 3 no MFMA; 5 fragments not read from LDS.
-template <int MODE, int DBG = 0>
+// CAUSAL (self-attention of a causal model, MODE 1 only): the wave owns the queries [cq_first, cq_first + 32) of a sequence of cS rows whose keys
+// start at k_lo; each 32-key block is classed by attn_causal.h -- SKIP ends the tile (wave-uniform; the later blocks lie higher still), DIAG
+// takes the edge path with the LANE's own k_hi (attnc::key_end of its query), FULL the unmasked path.  `edge` is not read.  The first block
+// of a sequence holds key k_lo, which every query sees: it sets a real reference; a later block that is all masked for a lane gives p =
+// exp2(-inf - m) = 0 there, and a wave that has met no key yet keeps (m, l, O) = (-1e30, 0, 0) through exp2(-inf + 1e30) = 0
+template <int MODE, int DBG = 0, bool CAUSAL = false>
 __device__ __forceinline__ void tile(State<MODE>& st, const opx8 (&qf)[4], const char* sk, const char* sv, const bool edge, const int key_base,
-                                     const int k_lo, const int k_hi, const bool first, const float scale_log2, const int l31, const int half) {
+                                     const int k_lo, const int k_hi, const bool first, const float scale_log2, const int l31, const int half,
+                                     const int cq_first = 0, const int cS = 0) {
+    static_assert(!CAUSAL || MODE == 1, "the causal walk is built for the standing-reference recurrence");
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
+        [[maybe_unused]] int cls = attnc::FULL;
+        if constexpr (CAUSAL) {
+            cls = attnc::block_class(key_base + kb * 32, cq_first, 32, k_lo, cS);
+            if (cls == attnc::SKIP) break;
+        }
         // ---- S^T = K Q^T for 32 keys
         opx8 kf[4];
 #pragma unroll
@@ -92,7 +105,7 @@ __device__ __forceinline__ void tile(State<MODE>& st, const opx8 (&qf)[4], const
                 if constexpr (DBG == 5) vf[db][u] = qf[db * 2 + u];
                 else vf[db][u] = *reinterpret_cast<const opx8*>(sv + lds_tile_off(db * 32 + l31, (kb * 2 + u) * 2 + half));
         // ---- mask the keys outside [k_lo, k_hi) (wave-uniform branch: first and last tile only)
-        if (edge) {
+        if (CAUSAL ? cls == attnc::DIAG : edge) {
             const int key0 = key_base + kb * 32 + 4 * half;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {

@@ -90,6 +90,8 @@ struct sat_dit_plan {
     // ABI; rows, workspace, position tables count tokens (tokens()), and the two boundary launches are those of dit_patch.hip
     int patch = 1;
     int tokens(int t_len) const { return t_len / patch; }
+    // ContinuousTransformer causal (sat_dit_plan_set_attention_options): every self-attention runs the causal launchers; false changes nothing
+    bool causal = false;
     // per-generation context (sat_dit_prepare_context)
     DevBuf ctx_buf;
     int ctx_bf = 0, ctx_lc = 0, ctx_lcpad = 0;
@@ -517,7 +519,8 @@ struct Forward {
     // The two kernels of the staged route (head_split_hdw.hip, attention_hdw.hip) at the plan's head width
     float staged_qscale() const { return sat_attn_qscale(p->hd); }
     int head_split(const float* x, const HeadsEpi& he, int seqs, int f16) const { return sat_launch_head_split_hdw(x, he, p->hd, seqs, s, f16); }
-    int attend(const op_t* q, const op_t* k, const op_t* vt, int seqs, int kvh, int sk, int sk_pad, int f16) const {
+    int attend(const op_t* q, const op_t* k, const op_t* vt, int seqs, int kvh, int sk, int sk_pad, int f16, bool self = false) const {
+        if (self && p->causal) return sat_launch_attention_hdw_causal(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, Spad, sk_pad, s, f16);
         return sat_launch_attention_hdw(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, sk, Spad, sk_pad, s, f16);
     }
 
@@ -547,10 +550,12 @@ int Forward::block_f32(int l) const {
     const int hd = p->hd;
     if (hd == 64) {
         SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
-        SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
+        if (p->causal) SAT_TRY(sat_launch_attention_f32_causal(Q32, K32, V32, AO32, bf, H, H, hd, S, s));
+        else SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
     } else {
         SAT_TRY(sat_launch_split_heads_f32_w(w.f32_wide, Q32, K32, V32, M, S, 3, H, hd, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
-        SAT_TRY(sat_launch_attention_f32_w(Q32, K32, V32, AO32, bf, H, H, hd, S, S, s));
+        if (p->causal) SAT_TRY(sat_launch_attention_f32_causal(Q32, K32, V32, AO32, bf, H, H, hd, S, s));
+        else SAT_TRY(sat_launch_attention_f32_w(Q32, K32, V32, AO32, bf, H, H, hd, S, S, s));
     }
     SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.o), nullptr, w.X, M, D, D, D, 1, m ? m + 2 * D : nullptr, S, ssg_ld, s));
     if (bc > 0) {
@@ -616,7 +621,7 @@ int Forward::attention_staged(int l) const {
     SAT_TRY(range_heads(l, RS_Q, w.Q, bf));
     SAT_TRY(range_heads(l, RS_K, w.K, bf));
     SAT_TRY(range_heads(l, RS_V, w.Vt, bf));
-    SAT_TRY(attend(w.Q, w.K, w.Vt, bf, H, S, Spad, f16));
+    SAT_TRY(attend(w.Q, w.K, w.Vt, bf, H, S, Spad, f16, true));
     SAT_TRY(range(l, RS_ATTN_OUT, w.AO, (size_t)M * D, (size_t)M * D));
     SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
     if (bc > 0) {      // (the sequences behind bc have an all-zero context: Forward::block)
@@ -659,7 +664,8 @@ int Forward::block(int l) const {
     SAT_TRY(range_heads(l, RS_Q, w.Q, bf));
     SAT_TRY(range_heads(l, RS_K, w.K, bf));
     SAT_TRY(range_heads(l, RS_V, w.Vt, bf));
-    SAT_TRY(sat_launch_attention(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, mx_scales(L.o), 1.0f, f16));
+    if (p->causal) SAT_TRY(sat_launch_attention_causal(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, Spad, Spad, s, 1.0f, f16));      // (never an e4m3 plan)
+    else SAT_TRY(sat_launch_attention(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, mx_scales(L.o), 1.0f, f16));
     SAT_TRY(range(l, RS_ATTN_OUT, w.AO, (size_t)M * D, (size_t)M * D));
     SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
     // ---- cross-attention branch (transformer.py:694-695).  Sequences whose context is all-zero (the
@@ -1177,6 +1183,27 @@ extern "C" int sat_dit_plan_set_block_options(sat_dit_plan* p, const sat_dit_blo
     p->conformer = o->conformer != 0;
     p->remove_norms = o->remove_norms != 0;
     p->ff_glu = o->ff_glu != 0;
+    return 0;
+}
+
+extern "C" int sat_dit_plan_set_attention_options(sat_dit_plan* p, const sat_dit_attention_options* o, size_t options_bytes) {
+    SAT_CHECK_ARG(p && o, SAT_E_INVALID, "dit_plan_set_attention_options: null argument");
+    SAT_CHECK_ARG(options_bytes == sizeof(sat_dit_attention_options), SAT_E_INVALID,
+                  "dit_plan_set_attention_options: sat_dit_attention_options of %zu bytes; this library knows %zu", options_bytes,
+                  sizeof(sat_dit_attention_options));
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_attention_options: plan already finalized (call it between create and finalize)");
+    SAT_CHECK_ARG(o->causal == 0 || o->causal == 1, SAT_E_INVALID, "dit_plan_set_attention_options: causal %d is neither 0 nor 1", o->causal);
+    // transformer.py:371, 530: with more context keys than queries the reference fails, with fewer its backends disagree on where the mask
+    // sits; there is no working behaviour to reproduce
+    SAT_CHECK_ARG(!(o->causal && p->cfg.cond_token_dim > 0), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_attention_options: causal with cross-attention (cond_token_dim %d): the reference has no working behaviour there",
+                  p->cfg.cond_token_dim);
+    // the MXFP8 output form of the attention kernels has no causal variant (gemm_dtype is fixed at create: no later call can make the plan e4m3)
+    SAT_CHECK_ARG(!(o->causal && p->cfg.gemm_dtype == SAT_GEMM_FP8), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_attention_options: causal with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
+    SAT_CHECK_ARG(!o->causal || (sat_launch_attention_causal && sat_launch_attention_hdw_causal && sat_launch_attention_f32_causal), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_attention_options: built without the causal attention kernels");
+    p->causal = o->causal != 0;
     return 0;
 }
 

@@ -6,6 +6,7 @@
 // (tests/test_gpu_models.py: test_fp32x_mode_vs_reference_golden).
 // Replaces the same reference code as gemm_bf16.hip / attention.hip / layernorm.hip (models/transformer.py:188-206, 158-183,
 // 222-235, 270, 311-319, 496-536).
+#include "attn_causal.h"
 #include "sat_common.h"
 
 namespace {
@@ -214,8 +215,10 @@ __global__ __launch_bounds__(256) void swiglu_f32_kernel(const float* __restrict
 
 // softmax(q k^T / sqrt(W)) v in fp32, one query per lane (q and the output row in registers), K / V rows are wave-uniform loads.
 // Online softmax over chunks of 8 keys.  q [B,H,Sq,W], k / v [B,KVH,Sk,W] -> out [B*Sq, H*W].  W = 64 is the kernel the 64-channel plans
-// have always run (scale 1/8); 32 and 96 are the widths of the staged route (attention_hdw.hip)
-template <int W>
+// have always run (scale 1/8); 32 and 96 are the widths of the staged route (attention_hdw.hip).  CAUSAL (Sq == Sk): the key loop ends with the
+// chunk that holds the diagonal of the wave's last query (attn_causal.h at 8-key tiles, no key shift) and a lane masks the keys j > its query;
+// key 0 is in the first chunk and visible to everybody, so the running maximum is finite from there on
+template <int W, bool CAUSAL = false>
 __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                            const float* __restrict__ v, float* __restrict__ out, int H, int KVH, int Sq,
                                                            int Sk) {
@@ -239,7 +242,8 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
     float m_run = -INFINITY, l_run = 0.f;
     const float* kb = k + ((size_t)b * KVH + kvh) * Sk * W;
     const float* vb = v + ((size_t)b * KVH + kvh) * Sk * W;
-    for (int j0 = 0; j0 < Sk; j0 += 8) {
+    const int j_end = CAUSAL ? attnc::tiles_walked(blockIdx.x * 64, 64, 0, Sk, 8) * 8 : Sk;
+    for (int j0 = 0; j0 < j_end; j0 += 8) {
         float sc[8];
         float mx = m_run;
 #pragma unroll
@@ -251,6 +255,7 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(const float* __restri
                 s = 0.f;
 #pragma unroll
                 for (int d = 0; d < W; ++d) s = fmaf(qr[d], kr[d], s);
+                if (CAUSAL && j > qc) s = -INFINITY;
             }
             sc[u] = s;
             mx = fmaxf(mx, s);
@@ -358,6 +363,22 @@ int sat_launch_attention_f32_w(const float* q, const float* k, const float* v, f
     SAT_CHECK_ARG(h <= 65535 && b <= 65535, SAT_E_UNSUPPORTED, "attention_f32: %d heads / %d sequences exceed the grid", h, b);
     if (head_dim == 32) hipLaunchKernelGGL(attention_f32_kernel<32>, dim3(cdiv(sq, 64), h, b), dim3(64), 0, s, q, k, v, out, h, kvh, sq, sk);
     else hipLaunchKernelGGL(attention_f32_kernel<96>, dim3(cdiv(sq, 64), h, b), dim3(64), 0, s, q, k, v, out, h, kvh, sq, sk);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
+// Causal self-attention in fp32 (sq == sk == s_len) at any built head width
+int sat_launch_attention_f32_causal(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int head_dim, int s_len,
+                                    hipStream_t s) {
+    SAT_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 96, SAT_E_UNSUPPORTED, "attention_f32 (causal): dim_heads %d (built for 32, 64 and 96)",
+                  head_dim);
+    SAT_CHECK_ARG(q && k && v && out && b > 0 && h > 0 && kvh > 0 && h % kvh == 0 && s_len > 0, SAT_E_INVALID, "attention_f32 (causal): bad args");
+    SAT_CHECK_ARG((((uintptr_t)q | (uintptr_t)out) & 15) == 0, SAT_E_INVALID, "attention_f32 (causal): q and out must be 16-byte aligned");
+    SAT_CHECK_ARG(h <= 65535 && b <= 65535, SAT_E_UNSUPPORTED, "attention_f32 (causal): %d heads / %d sequences exceed the grid", h, b);
+    const dim3 grid(cdiv(s_len, 64), h, b);
+    if (head_dim == 32) hipLaunchKernelGGL((attention_f32_kernel<32, true>), grid, dim3(64), 0, s, q, k, v, out, h, kvh, s_len, s_len);
+    else if (head_dim == 64) hipLaunchKernelGGL((attention_f32_kernel<64, true>), grid, dim3(64), 0, s, q, k, v, out, h, kvh, s_len, s_len);
+    else hipLaunchKernelGGL((attention_f32_kernel<96, true>), grid, dim3(64), 0, s, q, k, v, out, h, kvh, s_len, s_len);
     SAT_LAUNCH_CHECK();
     return 0;
 }

@@ -365,6 +365,13 @@ __attribute__((weak)) int sat_launch_attention_hdw(const op_t* q, const op_t* k,
                                                    int sk, int sq_pad, int sk_pad, hipStream_t s, int f16 = 0);
 // x: fp32 [b * S, parts * heads * head_dim]; he: out / kind / qscale / parts / heads / S / Spad and the [S][sat_rope_pairs(head_dim)] rotation tables
 __attribute__((weak)) int sat_launch_head_split_hdw(const float* x, const HeadsEpi& he, int head_dim, int b, hipStream_t s, int f16 = 0);
+// ---- causal self-attention (sat_dit_plan_set_attention_options): sq == sk == s_len, query i sees the keys j <= i of its sequence (attn_causal.h).
+// Layouts, pads and q_scale as the launchers above; no MXFP8 output form.  WEAK as the staged-route launchers: null in the host test driver,
+// where sat_dit_plan_set_attention_options answers SAT_E_UNSUPPORTED to causal = 1
+__attribute__((weak)) int sat_launch_attention_causal(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int s_len, int sq_pad,
+                                                      int sk_pad, hipStream_t s, float q_scale = SAT_ATTN_QSCALE, int f16 = 0);
+__attribute__((weak)) int sat_launch_attention_hdw_causal(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int head_dim,
+                                                          int s_len, int sq_pad, int sk_pad, hipStream_t s, int f16 = 0);
 }  // namespace SAT_OPNS
 using namespace SAT_OPNS;
 // RotaryEmbedding(max(dim_heads / 2, 32)) (transformer.py:737): pairs (j, j + sat_rope_pairs) rotate, one angle per pair -- 16 for 32- and
@@ -418,6 +425,10 @@ __attribute__((weak)) int sat_launch_im2col_rows_f32(const float* a, float* out,
 int sat_launch_attention_hdw_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int head_dim, int sq, int sk,
                                  int sq_pad, int sk_pad, hipStream_t s);
 int sat_launch_head_split_hdw_f16(const float* x, const void* heads_epi, int head_dim, int b, hipStream_t s);
+int sat_launch_attention_causal_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int s_len, int sq_pad, int sk_pad,
+                                    hipStream_t s, float q_scale);
+int sat_launch_attention_hdw_causal_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int head_dim, int s_len,
+                                        int sq_pad, int sk_pad, hipStream_t s);
 // entry points of the fp16 build for the dispatchers of the bf16 build (GemmArgs is layout-identical in both builds: the pointer
 // element type is the only difference)
 int sat_launch_gemm_f16(int epi, const void* gemm_args, hipStream_t stream);
@@ -451,6 +462,9 @@ __attribute__((weak)) int sat_launch_split_heads_f32_w(const float* src, float* 
                                                        int rope_mask, const float* rope_cos, const float* rope_sin, hipStream_t s, int norm_mask = 0);
 __attribute__((weak)) int sat_launch_attention_f32_w(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int head_dim,
                                                      int sq, int sk, hipStream_t s);
+// causal self-attention in fp32 for head_dim 32 / 64 / 96 (sq == sk == s_len).  WEAK as above
+__attribute__((weak)) int sat_launch_attention_f32_causal(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int head_dim,
+                                                          int s_len, hipStream_t s);
 int sat_launch_cast_bf16(const float* x, op_t* y, int64_t n, hipStream_t s, int f16 = 0);
 int sat_launch_pack_rows_bf16(const float* w, op_t* out, int n, int k, int swiglu_interleave, hipStream_t s, int f16 = 0);
 int sat_launch_pack_bias(const float* b, float* out, int n, int swiglu_interleave, hipStream_t s);

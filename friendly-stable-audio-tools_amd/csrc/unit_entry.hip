@@ -264,6 +264,33 @@ extern "C" int sat_attention_f32_hdw(const float* q, const float* k, const float
     return sat_launch_attention_f32_w(q, k, v, out, b, h, kvh, head_dim, sq, sk, (hipStream_t)stream);
 }
 
+// ---- causal self-attention alone (sat_dit_plan_set_attention_options): the three launchers Forward calls.  head_dim 64 is attention.hip
+// (prescaled 0: a plain Q, scaled here; 1: a Q pre-scaled by log2(e) / 8), 32 / 96 / 128 attention_hdw.hip (Q always pre-scaled)
+static int attention_causal_impl(int f16, const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
+                                 int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t prescaled, sat_stream_t stream) {
+    SAT_CHECK_ARG(head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128, SAT_E_UNSUPPORTED,
+                  "attention_causal: dim_heads %d (built for 32, 64, 96 and 128)", head_dim);
+    SAT_CHECK_ARG(prescaled == 0 || prescaled == 1, SAT_E_INVALID, "attention_causal: prescaled %d is neither 0 nor 1", prescaled);
+    SAT_CHECK_ARG(head_dim == 64 || prescaled == 1, SAT_E_UNSUPPORTED, "attention_causal: dim_heads %d takes a pre-scaled Q only", head_dim);
+    if (head_dim == 64)
+        return sat_launch_attention_causal((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, s, s_pad_q, s_pad_k, (hipStream_t)stream,
+                                           prescaled ? 1.0f : SAT_ATTN_QSCALE, f16);
+    return sat_launch_attention_hdw_causal((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, head_dim, s, s_pad_q, s_pad_k,
+                                           (hipStream_t)stream, f16);
+}
+extern "C" int sat_attention_causal_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
+                                         int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t prescaled, sat_stream_t stream) {
+    return attention_causal_impl(0, q, k, vt, out, b, h, kvh, head_dim, s, s_pad_q, s_pad_k, prescaled, stream);
+}
+extern "C" int sat_attention_causal_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
+                                        int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t prescaled, sat_stream_t stream) {
+    return attention_causal_impl(1, q, k, vt, out, b, h, kvh, head_dim, s, s_pad_q, s_pad_k, prescaled, stream);
+}
+extern "C" int sat_attention_f32_causal(const float* q, const float* k, const float* v, float* out, int32_t b, int32_t h, int32_t kvh, int32_t head_dim,
+                                        int32_t s, sat_stream_t stream) {
+    return sat_launch_attention_f32_causal(q, k, v, out, b, h, kvh, head_dim, s, (hipStream_t)stream);
+}
+
 // qkn: q and k L2-normalised per head (qk_norm), q pre-scaled for the attention kernel as in the plan
 static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
                                  float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,

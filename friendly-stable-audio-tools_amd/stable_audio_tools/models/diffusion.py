@@ -32,6 +32,7 @@ class DiTWrapper(ConditionedDiffusionModel):
         # ... ff_kwargs use_conv is not: a config opts in with "allow_conv_ff": true, which arrives here in kwargs and is passed on as it is
         # ... nor is patch_size > 1: "allow_patch_size": true, likewise
         # ... nor are 32- / 96-channel attention heads: "allow_head_widths": true, likewise
+        # ... nor is causal=True: "allow_causal": true, likewise
         self.model = DiffusionTransformer(*args, **kwargs)
         from . import _init
         if not _init._SKIP:

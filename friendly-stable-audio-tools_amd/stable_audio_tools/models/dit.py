@@ -36,7 +36,7 @@ class DiffusionTransformer(nn.Module):
                  input_concat_dim: int = 0, prepend_cond_dim: int = 0, depth: int = 12, num_heads: int = 8,
                  transformer_type: str = "x-transformers", global_cond_type: str = "prepend", max_seq_len: int = 8192,
                  allow_block_options: bool = False, allow_conv_ff: bool = False, allow_patch_size: bool = False, allow_head_widths: bool = False,
-                 **kwargs):
+                 allow_causal: bool = False, **kwargs):
         """``allow_block_options``: the TransformerBlock options ``conformer``, ``remove_norms`` and ``ff_kwargs={"glu": False}`` are off the
         shipped configs' path and refused unless this is set; ``create_model_from_config`` and every other config-driven path set it.
         ``allow_conv_ff``: likewise for ``ff_kwargs={"use_conv": True}`` (``sat_dit_plan_set_ff_conv``); no path sets it by default, a config
@@ -46,7 +46,11 @@ class DiffusionTransformer(nn.Module):
         asks for it with ``"allow_patch_size": true``.
         ``allow_head_widths``: likewise for attention heads of 32 or 96 channels (``embed_dim // num_heads``; ``sat_dit_plan_create_ex``), next
         to the 64- and 128-channel ones that need no opt-in; a config asks for it with ``"allow_head_widths": true``.  Such a model runs
-        with 'fp16', 'bf16' (also per block) and 'fp32x' operands; 'fp8', the block options and ``use_conv`` keep 64-channel heads."""
+        with 'fp16', 'bf16' (also per block) and 'fp32x' operands; 'fp8', the block options and ``use_conv`` keep 64-channel heads.
+        ``allow_causal``: likewise for ``causal=True`` (``sat_dit_plan_set_attention_options``): every self-attention is then causal over the
+        sequence ``[prepend rows | global token | tokens]``, row i attends to the rows j <= i; a config asks for it with
+        ``"allow_causal": true``.  Such a model has no cross-attention (``cond_token_dim=0``; the reference has no working behaviour there) and
+        runs with 'fp16', 'bf16' (also per block) and 'fp32x' operands at every head width; it adds no parameter."""
         super().__init__()
         if transformer_type != "continuous_transformer":
             raise NotImplementedError("only transformer_type='continuous_transformer' is implemented (the shipped DiT configs)")
@@ -105,7 +109,7 @@ class DiffusionTransformer(nn.Module):
                                                  cond_token_dim=cond_embed_dim,
                                                  global_cond_dim=embed_dim if global_cond_type == "adaLN" else None,
                                                  allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff,
-                                                 allow_head_widths=allow_head_widths, **kwargs)
+                                                 allow_head_widths=allow_head_widths, allow_causal=allow_causal, **kwargs)
         self.preprocess_conv = _init.conv1d(dim_in, dim_in, 1, bias=False, zero=True)
         self.postprocess_conv = _init.conv1d(io_channels, io_channels, 1, bias=False, zero=True)
 
@@ -143,6 +147,9 @@ class DiffusionTransformer(nn.Module):
         if self.transformer.qk_norm and GEMM_DTYPES[gemm_dtype] == 1:
             raise NotImplementedError(f"attn_kwargs qk_norm=True with gemm_dtype={gemm_dtype!r}: the e4m3 projections have no normalising epilogue; "
                                       "use gemm_dtype 'fp16', 'bf16' or 'fp32x' for a qk_norm model")
+        if self.transformer.causal and GEMM_DTYPES[gemm_dtype] == 1:
+            raise NotImplementedError(f"causal=True with gemm_dtype={gemm_dtype!r}: the MXFP8 output form of the attention kernels has no causal "
+                                      "variant; use gemm_dtype 'fp16', 'bf16' or 'fp32x'")
         if self.transformer.dim_heads == 128 and GEMM_DTYPES[gemm_dtype] in (1, 2):
             raise NotImplementedError(f"dim_heads=128 (embed_dim {self.embed_dim} / num_heads {self.num_heads}) with gemm_dtype={gemm_dtype!r}: the "
                                       "128-channel-head route (fp32 projection, head split, attention) is built for 'fp16' and 'bf16' operands; the "
@@ -333,7 +340,8 @@ class DiffusionTransformer(nn.Module):
 
     def _ensure_plan(self):
         ver = _init.params_version(self)
-        options = self.transformer_options() + self.transformer.block_options + (self.transformer.ff_conv_kernel, self.patch_size)
+        options = (self.transformer_options() + self.transformer.block_options
+                   + (self.transformer.ff_conv_kernel, self.patch_size, 1 if self.transformer.causal else 0))
         if self._plan is not None and ver == self._plan_version and options == self._plan_options:
             return self._plan
         self._check_options(self.gemm_dtype)
@@ -361,6 +369,9 @@ class DiffusionTransformer(nn.Module):
             if options[8] > 1:       # patch_size; likewise
                 popts = _hip.SatDitPatchOptions(options[8])
                 _hip.check(lib.sat_dit_plan_set_patch(plan, ctypes.byref(popts), ctypes.sizeof(popts)))
+            if options[9]:       # causal; likewise
+                aopts = _hip.SatDitAttentionOptions(1)
+                _hip.check(lib.sat_dit_plan_set_attention_options(plan, ctypes.byref(aopts), ctypes.sizeof(aopts)))
             if self._block_gemm_dtypes is not None:       # a model that never set them never makes the call
                 fm = (ctypes.c_int32 * self.depth)(*[GEMM_DTYPES[f] for f in self._block_gemm_dtypes])
                 _hip.check(lib.sat_dit_plan_set_block_formats(plan, fm, self.depth))

@@ -4,7 +4,7 @@ Mirror of the module tree of the reference's ``models/transformer.py`` (``LayerN
 ``GLU``/``FeedForward`` :211-287, ``Attention`` :290-554, ``TransformerBlock`` :594-702,
 ``RotaryEmbedding`` :99-155, ``AbsolutePositionalEmbedding`` / ``ScaledSinusoidalEmbedding`` :50-96,
 ``ContinuousTransformer`` :705-809) restricted to the options the HIP plan runs: those of the shipped DiT
-configs plus 128-channel heads (and, behind ``allow_head_widths``, 32- and 96-channel ones), ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False``,
+configs plus causal self-attention (behind ``allow_causal``), 128-channel heads (and, behind ``allow_head_widths``, 32- and 96-channel ones), ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False``,
 bias-free / ``mult``-sized feed-forwards and, behind the ``allow_block_options`` opt-in, ``conformer`` (:557-591), ``remove_norms``
 and feed-forwards without GLU, and behind ``allow_conv_ff`` convolutional feed-forwards (``ff_kwargs use_conv``).  These classes only *hold* parameters under the reference's
 names; the forward pass of the whole stack is one C-ABI call (``sat_dit_forward`` /
@@ -75,6 +75,10 @@ HEAD_WIDTHS_HINT = ("pass allow_head_widths=True to DiffusionTransformer, or wri
                     "(sat_dit_plan_create_ex)")
 
 
+CAUSAL_HINT = ("pass allow_causal=True to DiffusionTransformer, or write \"allow_causal\": true into the model config's model.diffusion.config "
+               "(generate.py --allow-causal does): every self-attention then runs causal on the HIP plan (sat_dit_plan_set_attention_options)")
+
+
 class FeedForward(nn.Module):
     def __init__(self, dim, mult=4, glu=True, no_bias=False, use_conv=False, conv_kernel_size=3, zero_init_output=True, allow_block_options=False,
                  allow_conv_ff=False, **unsupported):
@@ -115,11 +119,20 @@ class FeedForward(nn.Module):
 
 class Attention(nn.Module):
     def __init__(self, dim, dim_heads=64, dim_context=None, causal=False, zero_init_output=True, qk_norm=False, natten_kernel_size=None,
-                 allow_head_widths=False, **unsupported):
+                 allow_head_widths=False, allow_causal=False, **unsupported):
         super().__init__()
-        if causal or natten_kernel_size is not None or unsupported:
-            raise NotImplementedError(f"Attention options not supported by the HIP path (full non-causal attention only): causal={causal} "
+        if natten_kernel_size is not None or unsupported:
+            raise NotImplementedError("Attention options not supported by the HIP path (full attention, non-causal or behind allow_causal causal): "
                                       f"natten_kernel_size={natten_kernel_size} {sorted(unsupported)}")
+        if causal and not allow_causal:
+            raise NotImplementedError(f"causal={causal} is behind an opt-in: {CAUSAL_HINT}")
+        if causal and dim_context:
+            # reference :371, 530: more context keys than queries fail inside create_causal_mask, which Attention does not have; with fewer
+            # SDPA aligns the mask top-left, flash-attn >= 2.1 bottom-right and the einsum path would give uniform rows
+            raise NotImplementedError("causal=True with cross-attention (cond_token_dim > 0) has no working reference behaviour (reference "
+                                      "transformer.py:371,530 fail with more context keys than queries, and its attention backends disagree with "
+                                      "fewer); use cond_token_dim=0")
+        self.causal = bool(causal)
         if dim_heads in (32, 96) and not allow_head_widths:
             raise NotImplementedError(f"the HIP attention kernels run dim_heads 64 and 128 (embed_dim / num_heads) by default, got dim_heads={dim_heads}: "
                                       f"{HEAD_WIDTHS_HINT}")
@@ -162,7 +175,7 @@ class ConformerModule(nn.Module):
 class TransformerBlock(nn.Module):
     def __init__(self, dim, dim_heads=64, cross_attend=False, dim_context=None, global_cond_dim=None, causal=False,
                  zero_init_branch_outputs=True, conformer=False, layer_ix=-1, remove_norms=False, attn_kwargs={}, ff_kwargs={},
-                 norm_kwargs={}, allow_block_options=False, allow_conv_ff=False, allow_head_widths=False):
+                 norm_kwargs={}, allow_block_options=False, allow_conv_ff=False, allow_head_widths=False, allow_causal=False):
         super().__init__()
         if (conformer or remove_norms) and not allow_block_options:
             raise NotImplementedError(f"conformer={conformer} / remove_norms={remove_norms} are off the shipped configs' path: {BLOCK_OPTIONS_HINT}")
@@ -179,11 +192,12 @@ class TransformerBlock(nn.Module):
         norm = (lambda: nn.Identity()) if remove_norms else (lambda: LayerNorm(dim, **norm_kwargs))      # reference :621,632,642
         self.pre_norm = norm()
         self.self_attn = Attention(dim, dim_heads=dim_heads, causal=causal, zero_init_output=zero_init_branch_outputs,
-                                   allow_head_widths=allow_head_widths, **attn_kwargs)
+                                   allow_head_widths=allow_head_widths, allow_causal=allow_causal, **attn_kwargs)
         if cross_attend:
             self.cross_attend_norm = norm()
             self.cross_attn = Attention(dim, dim_heads=dim_heads, dim_context=dim_context, causal=causal,
-                                        zero_init_output=zero_init_branch_outputs, allow_head_widths=allow_head_widths, **attn_kwargs)
+                                        zero_init_output=zero_init_branch_outputs, allow_head_widths=allow_head_widths, allow_causal=allow_causal,
+                                        **attn_kwargs)
         self.ff_norm = norm()
         self.ff = FeedForward(dim, zero_init_output=zero_init_branch_outputs, allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff,
                               **ff_kwargs)
@@ -203,7 +217,7 @@ class ContinuousTransformer(nn.Module):
                  use_sinusoidal_emb=False, use_abs_pos_emb=False, abs_pos_emb_max_length=10000, **kwargs):
         super().__init__()
         assert not (use_sinusoidal_emb and use_abs_pos_emb), "Can't select both of sinusoidal/abs positional embedding type."
-        self.dim, self.depth, self.causal, self.dim_heads = dim, depth, causal, dim_heads
+        self.dim, self.depth, self.causal, self.dim_heads = dim, depth, bool(causal), dim_heads      # causal: sat_dit_plan_set_attention_options
         self.project_in = _init.linear(dim_in, dim, bias=False) if dim_in else nn.Identity()
         self.project_out = _init.linear(dim, dim_out, bias=False) if dim_out else nn.Identity()
         self.rotary_pos_emb = RotaryEmbedding(max(dim_heads // 2, 32)) if rotary_pos_emb else None

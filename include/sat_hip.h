@@ -55,7 +55,7 @@ const char* sat_last_error(void);
  * FeedForward, LayerNorm, RotaryEmbedding), models/diffusion.py:482-529 (DiTWrapper).
  * Supported set: transformer_type "continuous_transformer", global_cond_type "prepend"
  * or "adaLN", dim_heads 64 or 128, patch_size 1 or, through sat_dit_plan_set_patch, above,
- * non-causal, no masks (the reference discards
+ * non-causal or, through sat_dit_plan_set_attention_options, causal self-attention without cross-attention, no masks (the reference discards
  * them at inference: models/dit.py:250-252; prepend_cond_mask never reaches the layers,
  * models/transformer.py:787-802).  Input-concat and prepend conditioning (dit.py:160-197)
  * through sat_dit_plan_set_extra_conditioning / sat_dit_prepare_extra_conditioning; prepend
@@ -277,6 +277,22 @@ typedef struct sat_dit_patch_options {
     int32_t patch_size;     /* "patch_size"; 1 = a token per frame */
 } sat_dit_patch_options;
 int sat_dit_plan_set_patch(sat_dit_plan* plan, const sat_dit_patch_options* options, size_t options_bytes);
+
+/* Causal DiT (ContinuousTransformer causal, models/transformer.py:296,304,359-398 of the reference), between create and finalize; a plan
+ * never given this call, or given causal 0, builds and launches exactly what it did before this call existed.  With causal 1 every
+ * self-attention is causal over the sequence the blocks see, [prepend rows | global token | tokens]: row i attends to the rows j <= i of
+ * its own sequence (what the reference computes through SDPA is_causal=True and through flash-attn with q_len == k_len).  The kernels walk
+ * only the key tiles up to a workgroup's last query and compare per element only where the diagonal crosses a block of 32 keys.  No
+ * tensor is added or renamed.  The convolutions of conformer and use_conv blocks stay non-causal, as in the reference.  Runs with
+ * gemm_dtype bf16, fp16, per-block formats and the fp32 verification mode, at every head width the plan accepts.
+ * options_bytes = sizeof(sat_dit_attention_options) of the caller's header; any other size is SAT_E_INVALID, as is a value outside 0 / 1; a
+ * call after finalize is SAT_E_STATE.  SAT_E_UNSUPPORTED, with "causal" in the message: causal 1 on a plan with cross-attention
+ * (cond_token_dim > 0: the reference fails with more context keys than queries and its backends disagree with fewer) or with gemm_dtype
+ * SAT_GEMM_FP8 (the MXFP8 output form of the attention kernels has no causal variant). */
+typedef struct sat_dit_attention_options {
+    int32_t causal;         /* "causal" */
+} sat_dit_attention_options;
+int sat_dit_plan_set_attention_options(sat_dit_plan* plan, const sat_dit_attention_options* options, size_t options_bytes);
 
 /* Operand format per block, between create and finalize: formats[l] is SAT_GEMM_FP16 or SAT_GEMM_BF16 for block l, n == depth.  A plan never
  * given this call, or given gemm_dtype in every entry, runs every block in gemm_dtype and builds and launches exactly what it did before this
@@ -671,6 +687,12 @@ int sat_attention_hdw_bf16(const void* q_dev, const void* k_dev, const void* vt_
  * x_dev and the destinations 16-byte aligned; rope_scratch_dev: 2 * s * 16 (32) or 2 * s * 24 (96) floats, 16-byte aligned. */
 int sat_head_split_hdw_bf16(const float* x_dev, const float* inv_freq_dev, void* const* dst_dev, const int32_t* kind, float* rope_scratch_dev,
                             int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream);
+/* ---- causal self-attention (sat_dit_plan_set_attention_options), test-only: query i of each of the b sequences of s rows sees the keys
+ * j <= i.  head_dim 64: layouts and pad rules of sat_attention_bf16 (prescaled 0) / sat_attention_prescaled_bf16 (prescaled 1) with
+ * sq == sk == s, sq_pad = s_pad_q, sk_pad = s_pad_k; head_dim 32 / 96 / 128: those of sat_attention_hdw_* / sat_attention_hd128_*, prescaled
+ * must be 1.  Any other head_dim is SAT_E_UNSUPPORTED. */
+int sat_attention_causal_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
+                              int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t prescaled, sat_stream_t stream);
 /* Cross-attention query projection and attention core in one launch (models/transformer.py:430-437 + 496-536; what the DiT plan
  * runs per layer while the 128 x 64 GEMM tiles of the projection fit one round of workgroups, i.e. at one prompt):
  * out [b*s, d] bf16 = softmax((a wq^T) k^T / 8) v per head of 64, a [b*s, d] bf16, wq [d, d] bf16, k / vt in the key-side layout of
@@ -747,6 +769,8 @@ int sat_attention_hdw_f16(const void* q_dev, const void* k_dev, const void* vt_d
                           int32_t head_dim, int32_t sq, int32_t sk, int32_t sq_pad, int32_t sk_pad, sat_stream_t stream);
 int sat_head_split_hdw_f16(const float* x_dev, const float* inv_freq_dev, void* const* dst_dev, const int32_t* kind, float* rope_scratch_dev,
                            int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream);
+int sat_attention_causal_f16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
+                             int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t prescaled, sat_stream_t stream);
 int sat_cross_attention_fused_f16(const void* a_f16_dev, const void* wq_f16_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                                   int32_t b, int32_t s, int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream);
 int sat_qkv_rope_f16(const void* a_f16_dev, const void* w_f16_dev, const float* inv_freq_dev,
@@ -935,6 +959,9 @@ int sat_split_heads_f32_hdw(const float* src_dev, float* d0_dev, float* d1_dev, 
                             int32_t norm_mask, sat_stream_t stream);
 int sat_attention_f32_hdw(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
                           int32_t head_dim, int32_t sq, int32_t sk, sat_stream_t stream);
+/* The same attention, causal (sq == sk == s, query i sees the keys j <= i), for head_dim 32, 64 or 96 */
+int sat_attention_f32_causal(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
+                             int32_t head_dim, int32_t s, sat_stream_t stream);
 /* Self-attention of the text encoders: qkv [b * l, 3 * h * dkv] (q | k | v) -> out [b * l, h * dkv] = softmax(scale * q k^T + pb + mask) v;
  * pb [h, 2l - 1] indexed by key - query + l - 1, or NULL; keys with mask [b, l] == 0 get finfo(float32).min added (an all-padding row is the
  * uniform average over all l keys).  l <= 512, dkv % 4 == 0, (dkv + l) * 4 bytes of LDS <= 64 KiB. */
