@@ -134,13 +134,13 @@ enum RangeSlot { RS_A_QKV, RS_Q, RS_K, RS_V, RS_ATTN_OUT, RS_A_CROSS_Q, RS_CROSS
 const char* const kRangeSlotNames[SAT_DIT_RANGE_SLOTS] = {"a_qkv", "q", "k", "v", "attn_out", "a_cross_q", "cross_q", "cross_k", "cross_v",
                                                            "cross_attn_out", "a_ff", "ff_hidden"};
 
-// One reduction of the range report over `scanned` contiguous 16-bit elements at buf, into slot `slot` of layer l; `logical` of them are values
-// of the model (the rest: zero pads of the layout).  Launched right behind the buffer's producer: the next layer reuses the buffer.  Nothing
-// without the report
 // Operand format of block l: every 16-bit buffer the block writes or reads (weight images, A / AO / Q / K / V^T / Hh, its slice of the
 // cross-attention cache) holds IEEE fp16 (1) or bf16 (0).  The residual stream between blocks is fp32, so neighbours may differ
 int layer_f16(const sat_dit_plan* p, int l) { return p->block_f16.empty() ? p->f16 : p->block_f16[l]; }
 
+// One reduction of the range report over `scanned` contiguous 16-bit elements at buf, into slot `slot` of layer l; `logical` of them are values
+// of the model (the rest: zero pads of the layout).  Launched right behind the buffer's producer: the next layer reuses the buffer.  Nothing
+// without the report
 int range_stats(const sat_dit_plan* p, int l, int slot, const op_t* buf, size_t scanned, size_t logical, hipStream_t s) {
     if (!p->rr) return 0;
     return sat_launch_range_stats(buf, layer_f16(p, l) ? SAT_GEMM_FP16 : SAT_GEMM_BF16, 1, (int64_t)scanned, (int64_t)scanned, logical,
@@ -157,10 +157,38 @@ int copy_f32(sat_dit_plan* p, Bump& ar, const std::string& name, int64_t numel, 
     return p->tensors.place("dit", ar, name, numel, dst, s);
 }
 
-// How the Linear of `family` in layer `l` runs.  e4m3 by the plan's families (to_kv has no e4m3 form: once per generation); the fold for the
-// LayerNorm-fed ones, except layer 0's to_qkv: its pre_norm reads rows written by the input projection, not by a GEMM epilogue.  The same
-// for the first block of another operand format: the image the previous FF-out's epilogue could write would be in the writer's format
-// Whether A holds the 16-bit image of the residual rows (and ln_part their statistics) when the projection of `family` in layer l runs
+// A projection into attention heads, the same on both routes: q / k / v of to_qkv, q of the cross to_q, k / v of to_kv.  `he` says where and in
+// which form the parts go.  64-channel heads: the heads epilogue of the GEMM itself (one head = one 64-column wave tile, gemm_bf16.hip).  The
+// staged route (128-, 32-, 96-channel heads): a plain fp32-output GEMM into `staging` [g.M, g.N], then the head split at the plan's width
+// (head_split_hdw.hip: qk_norm, rotation, pre-scale, one rounding) over the `seqs` sequences of the rows
+int project_heads(const sat_dit_plan* p, GemmArgs g, const HeadsEpi& he, float* staging, int seqs, hipStream_t s) {
+    if (!p->staged()) {
+        g.heads = he;
+        return sat_launch_gemm(EPI_HEADS, g, s);
+    }
+    g.C = staging; g.ldc = g.N;
+    SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
+    return sat_launch_head_split_hdw(staging, he, p->hd, seqs, s, g.f16);
+}
+
+// fp32 verification mode: the head split and the attention of f32_ref.hip at the plan's head width (64: the kernels without one; the causal
+// kernel takes any).  rope_mask 0: no rotation
+int split_heads_f32(const sat_dit_plan* p, const float* src, float* d0, float* d1, float* d2, int M, int S, int parts, int H, int rope_mask,
+                    int norm_mask, hipStream_t s) {
+    const float *rc = rope_mask ? p->rope_cos : nullptr, *rs = rope_mask ? p->rope_sin : nullptr;
+    if (p->hd == 64) return sat_launch_split_heads_f32(src, d0, d1, d2, M, S, parts, H, rope_mask, rc, rs, s, norm_mask);
+    return sat_launch_split_heads_f32_w(src, d0, d1, d2, M, S, parts, H, p->hd, rope_mask, rc, rs, s, norm_mask);
+}
+int attention_f32(const sat_dit_plan* p, bool causal, const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int sq, int sk,
+                  hipStream_t s) {
+    if (causal) return sat_launch_attention_f32_causal(q, k, v, out, b, h, kvh, p->hd, sq, s);
+    if (p->hd == 64) return sat_launch_attention_f32(q, k, v, out, b, h, kvh, sq, sk, s);
+    return sat_launch_attention_f32_w(q, k, v, out, b, h, kvh, p->hd, sq, sk, s);
+}
+
+// Whether A holds the 16-bit image of the residual rows (and ln_part their statistics) when the projection of `family` in layer l runs: under
+// the fold, except for layer 0's to_qkv, whose pre_norm reads rows written by the input projection, not by a GEMM epilogue.  The same for the
+// first block of another operand format: the image the previous FF-out's epilogue could write would be in the writer's format
 bool has_image(const sat_dit_plan* p, ProjFamily family, int l) {
     const bool own_ln = family == FAM_QKV && (l == 0 || layer_f16(p, l) != layer_f16(p, l - 1));
     return p->ln_fold && !own_ln;
@@ -169,6 +197,8 @@ bool has_image(const sat_dit_plan* p, ProjFamily family, int l) {
 bool norm_removed(const sat_dit_plan* p, ProjFamily family) {
     return p->remove_norms && (family == FAM_QKV || family == FAM_CQ || family == FAM_FF1);
 }
+// How the Linear of `family` in layer `l` runs.  e4m3 by the plan's families (to_kv has no e4m3 form: once per generation); the fold for the
+// LayerNorm-fed ones where A holds the image (has_image)
 ProjKind proj_kind(const sat_dit_plan* p, ProjFamily family, int l) {
     static const int fp8_bit[] = {SAT_FP8_QKV, SAT_FP8_TO_OUT, SAT_FP8_CROSS_Q, 0, SAT_FP8_TO_OUT, SAT_FP8_FF_IN, SAT_FP8_FF_OUT, 0, 0, 0};
     const bool ln_fed = family == FAM_QKV || family == FAM_CQ || family == FAM_FF1 || family == FAM_CPW1;
@@ -254,22 +284,27 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         SAT_TRY(copy_f32(p, ar, "to_prepend_embed.2.weight", (int64_t)D * D, &p->pe2_w, s));
     }
     // RotaryEmbedding(max(dim_heads / 2, 32)): 16 frequencies for 64-channel heads; 32 for 128-channel ones, 16 for 32 and 24 for 96 (the
-    // staged route: its table is placed at the end of build)
+    // staged route: its frequencies and table are placed at the end of build)
     const bool staged = p->staged();
-    if (!staged && p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", 16, &p->inv_freq, s));
-    else if (!staged) {      // frequencies 0: rope_table below comes out as cos 1 / sin 0 and the rotating epilogues are the identity
-        p->inv_freq = (float*)ar.take(16 * 4);
-        if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, 16 * 4, s));
-    }
+    const int pairs = sat_rope_pairs(p->hd);
+    auto place_inv_freq = [&]() -> int {
+        if (p->rotary) return copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", pairs, &p->inv_freq, s);
+        // frequencies 0: the rotation table comes out as cos 1 / sin 0 and the rotating epilogues are the identity
+        p->inv_freq = (float*)ar.take(pairs * 4);
+        if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, pairs * 4, s));
+        return 0;
+    };
+    auto take_rope_tables = [&](int rows) {      // [rows][pairs] each
+        p->rope_cos = (float*)ar.take((size_t)rows * pairs * 4);
+        p->rope_sin = (float*)ar.take((size_t)rows * pairs * 4);
+    };
+    if (!staged) SAT_TRY(place_inv_freq());
     const int Ci = C + p->concat_dim;       // preprocess_conv / project_in see cat([x, input_concat_cond]) (dit.py:38,130,173)
     const int pt = p->patch;                // project_in [D, Ci pt], project_out [C pt, D]; the two 1x1 convs stay per frame (dit.py:88-89,119-120)
     p->win_eff = (float*)ar.take((size_t)D * Ci * pt * 4);
     p->wout_eff = (float*)ar.take((size_t)D * C * pt * 4);
     const int smax = seq_len(p, p->tokens(c.max_seq_len), p->max_prep);
-    if (!staged) {
-        p->rope_cos = (float*)ar.take((size_t)smax * 16 * 4);
-        p->rope_sin = (float*)ar.take((size_t)smax * 16 * 4);
-    }
+    if (!staged) take_rope_tables(smax);
     // the absolute table has abs_pos_emb_max_length rows and no more: run_forward refuses longer sequences as the reference does
     p->pos_rows = p->pos_emb == SAT_DIT_POS_ABSOLUTE && p->abs_max < smax ? p->abs_max : smax;
     p->pos_table = p->pos_emb != SAT_DIT_POS_NONE ? (float*)ar.take((size_t)p->pos_rows * D * 4) : nullptr;
@@ -353,14 +388,8 @@ int build(sat_dit_plan* p, Bump& ar, hipStream_t s) {
         else SAT_TRY(pack("ff.ff.2.weight", b2, FAM_FF2, D, inner, 0, nullptr, nullptr, &L.ff2));
     }
     if (staged) {      // behind everything a 64-channel plan places: the frequencies and the [smax][pairs] table the head split rotates with
-        const int pairs = sat_rope_pairs(p->hd);      // 32 (128-channel heads), 16 (32), 24 (96)
-        if (p->rotary) SAT_TRY(copy_f32(p, ar, "transformer.rotary_pos_emb.inv_freq", pairs, &p->inv_freq, s));
-        else {
-            p->inv_freq = (float*)ar.take(pairs * 4);
-            if (!ar.dry()) SAT_HIP(hipMemsetAsync(p->inv_freq, 0, pairs * 4, s));
-        }
-        p->rope_cos = (float*)ar.take((size_t)smax * pairs * 4);
-        p->rope_sin = (float*)ar.take((size_t)smax * pairs * 4);
+        SAT_TRY(place_inv_freq());      // 32 pairs (128-channel heads), 16 (32), 24 (96)
+        take_rope_tables(smax);
         if (!ar.dry()) SAT_TRY(sat_launch_rope_table_hdw(p->inv_freq, p->rope_cos, p->rope_sin, smax, p->hd, s));
     }
     return 0;
@@ -391,50 +420,35 @@ Workspace carve(const sat_dit_plan* p, int bf, int T, int P, char* base) {
     const size_t M = (size_t)bf * S;
     const int Spad = (int)round_up(S + 3, 128);
     const int hid = p->conformer && D > p->inner ? D : p->inner;      // Hh: the FF hidden state [M, inner]; the conformer's GLU output [M, D] as well
+    const bool f32 = c.gemm_dtype == 2, fp8 = c.gemm_dtype == 1;
+    const size_t el = f32 ? 4 : 2;      // fp32 verification mode: every intermediate is fp32
     Workspace w;
     Bump ws{base};
     w.X = (float*)ws.take(M * D * 4);
-    if (c.gemm_dtype == 2) {      // fp32 verification mode: every intermediate is fp32, q / k / v un-padded [bf, H, S, 64]
-        w.A = (op_t*)ws.take(M * D * 4);
-        w.AO = (op_t*)ws.take(M * D * 4);
-        w.qkv_bytes = M * D * 4;
-        w.Q = (op_t*)ws.take(w.qkv_bytes);
-        w.K = (op_t*)ws.take(w.qkv_bytes);
-        w.Vt = (op_t*)ws.take(w.qkv_bytes);
-        w.Hh = (op_t*)ws.take(M * (size_t)hid * 4);
-        w.f32_wide = (float*)ws.take(M * (size_t)(2 * p->inner > 3 * D ? 2 * p->inner : 3 * D) * 4);     // [M, 3D] qkv / [M, 2 inner] FF-in
-        w.ff = (float*)ws.take((size_t)bf * 256 * 4);
-        w.h1 = (float*)ws.take((size_t)bf * D * 4);
-        w.mo = (float*)ws.take((size_t)bf * c.io_channels * T * 4);
-        w.As = nullptr; w.Hs = nullptr; w.AOs = nullptr;
-        w.gsum = c.adaln ? (float*)ws.take((size_t)bf * D * 4) : nullptr;
-        w.ssg = c.adaln ? (float*)ws.take((size_t)bf * c.depth * 6 * D * 4) : nullptr;
-        if (p->ff_conv > 1) w.f32_col = (float*)ws.take(M * (size_t)p->ff_conv * (p->inner > D ? p->inner : D) * 4);      // behind everything a Linear plan carves
-        w.total = ws.off;
-        return w;
-    }
-    w.A = (op_t*)ws.take(M * D * 2);
-    w.AO = (op_t*)ws.take(M * D * 2);
-    w.qkv_bytes = (size_t)bf * H * Spad * p->hd * 2;
-    // Q, K, Vt contiguous so that one memset clears all pads
+    w.A = (op_t*)ws.take(M * D * el);
+    w.AO = (op_t*)ws.take(M * D * el);
+    // q / k / v: padded heads [bf, H, Spad, hd]; un-padded [bf, H, S, hd] in the fp32 mode.  Contiguous so that one memset clears all pads
+    w.qkv_bytes = f32 ? M * D * 4 : (size_t)bf * H * Spad * p->hd * 2;
     w.Q = (op_t*)ws.take(w.qkv_bytes);
     w.K = (op_t*)ws.take(w.qkv_bytes);
     w.Vt = (op_t*)ws.take(w.qkv_bytes);
-    w.Hh = (op_t*)ws.take(M * (size_t)hid * 2);
+    w.Hh = (op_t*)ws.take(M * (size_t)hid * el);
+    if (f32) w.f32_wide = (float*)ws.take(M * (size_t)(2 * p->inner > 3 * D ? 2 * p->inner : 3 * D) * 4);     // [M, 3D] qkv / [M, 2 inner] FF-in
     w.ff = (float*)ws.take((size_t)bf * 256 * 4);
     w.h1 = (float*)ws.take((size_t)bf * D * 4);
     w.mo = (float*)ws.take((size_t)bf * c.io_channels * T * 4);
-    w.As = c.gemm_dtype == 1 ? (float*)ws.take(M * 4) : nullptr;
-    w.Hs = c.gemm_dtype == 1 ? (unsigned char*)ws.take(M * (size_t)(p->inner / 32)) : nullptr;
-    w.AOs = c.gemm_dtype == 1 ? (unsigned char*)ws.take(M * (size_t)(D / 32)) : nullptr;
+    w.As = fp8 ? (float*)ws.take(M * 4) : nullptr;
+    w.Hs = fp8 ? (unsigned char*)ws.take(M * (size_t)(p->inner / 32)) : nullptr;
+    w.AOs = fp8 ? (unsigned char*)ws.take(M * (size_t)(D / 32)) : nullptr;
     w.gsum = c.adaln ? (float*)ws.take((size_t)bf * D * 4) : nullptr;
     w.ssg = c.adaln ? (float*)ws.take((size_t)bf * c.depth * 6 * D * 4) : nullptr;
-    w.ln_part = p->ln_fold ? (float*)ws.take(M * (size_t)(D / 64) * 2 * 4) : nullptr;
+    w.ln_part = p->ln_fold ? (float*)ws.take(M * (size_t)(D / 64) * 2 * 4) : nullptr;      // (16-bit plans only: sat_dit_plan_create_ex)
     // FF-out (K = inner) is the one fp32-output GEMM with a reduction long enough for the 8-phase kernel's K-split of the remainder
     // round (SA-2.0 shape): its slabs live here, per workspace = per caller and stream
     w.slab_bytes = (c.gemm_dtype == 0 || c.gemm_dtype == 3) ? sat_gemm_ph8_slab_bytes(EPI_RESID, (int)M, D, p->inner) : 0;
     w.slab = w.slab_bytes ? (float*)ws.take(w.slab_bytes) : nullptr;
-    if (p->staged()) w.qkv32 = (float*)ws.take(M * (size_t)(3 * D) * 4);      // behind every buffer a 64-channel plan carves
+    if (p->staged() && !f32) w.qkv32 = (float*)ws.take(M * (size_t)(3 * D) * 4);      // behind every buffer a 64-channel plan carves
+    if (f32 && p->ff_conv > 1) w.f32_col = (float*)ws.take(M * (size_t)p->ff_conv * (p->inner > D ? p->inner : D) * 4);      // behind everything a Linear plan carves
     w.total = ws.off;
     return w;
 }
@@ -516,17 +530,23 @@ struct Forward {
         return 0;
     }
 
-    // The two kernels of the staged route (head_split_hdw.hip, attention_hdw.hip) at the plan's head width
-    float staged_qscale() const { return sat_attn_qscale(p->hd); }
-    int head_split(const float* x, const HeadsEpi& he, int seqs, int f16) const { return sat_launch_head_split_hdw(x, he, p->hd, seqs, s, f16); }
-    int attend(const op_t* q, const op_t* k, const op_t* vt, int seqs, int kvh, int sk, int sk_pad, int f16, bool self = false) const {
-        if (self && p->causal) return sat_launch_attention_hdw_causal(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, Spad, sk_pad, s, f16);
-        return sat_launch_attention_hdw(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, sk, Spad, sk_pad, s, f16);
+    // log2(e) / sqrt(dim_heads), what the projections pre-scale q by (HeadsEpi kind bit 3): the constant the 64-channel kernels were built with
+    float qscale() const { return p->staged() ? sat_attn_qscale(p->hd) : SAT_ATTN_QSCALE; }
+    // AO = softmax(q k^T) v for `seqs` sequences of S queries against sk keys (pad sk_pad) in kvh heads: attention.hip at 64 channels per head,
+    // attention_hdw.hip at the staged widths; the causal kernels for the self-attention of a causal plan (sk == S; never an e4m3 plan).  `out`: the
+    // projection that reads AO; as an MXFP8 operand the kernel writes its block scales beside it (64 channels only)
+    int attend(const op_t* q, const op_t* k, const op_t* vt, int seqs, int kvh, int sk, int sk_pad, int f16, const Proj& out, bool self) const {
+        const bool causal = self && p->causal;
+        if (p->staged()) {
+            if (causal) return sat_launch_attention_hdw_causal(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, Spad, sk_pad, s, f16);
+            return sat_launch_attention_hdw(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, sk, Spad, sk_pad, s, f16);
+        }
+        if (causal) return sat_launch_attention_causal(q, k, vt, w.AO, seqs, H, kvh, S, Spad, sk_pad, s, 1.0f, f16);
+        return sat_launch_attention(q, k, vt, w.AO, seqs, H, kvh, S, sk, Spad, sk_pad, s, out.kind == PROJ_FP8_MX ? w.AOs : nullptr, 1.0f, f16);
     }
 
     int block(int l) const;
     int block_f32(int l) const;
-    int attention_staged(int l) const;
     int conformer(int l) const;
     int feed_forward(int l) const;
     int feed_forward_conv(int l) const;
@@ -546,29 +566,15 @@ int Forward::block_f32(int l) const {
     };
     SAT_TRY(norm(L.pre_g, L.pre_b, M, m, m ? m + D : nullptr, S, ssg_ld));
     SAT_TRY(sat_launch_gemm_f32(A32, W32(L.qkv), nullptr, w.f32_wide, M, 3 * D, D, 3 * D, 0, nullptr, 1, 0, s));
-    // (32- and 96-channel heads: the same kernels with a head width; the launches of a 64-channel plan are what they were)
-    const int hd = p->hd;
-    if (hd == 64) {
-        SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
-        if (p->causal) SAT_TRY(sat_launch_attention_f32_causal(Q32, K32, V32, AO32, bf, H, H, hd, S, s));
-        else SAT_TRY(sat_launch_attention_f32(Q32, K32, V32, AO32, bf, H, H, S, S, s));
-    } else {
-        SAT_TRY(sat_launch_split_heads_f32_w(w.f32_wide, Q32, K32, V32, M, S, 3, H, hd, 3, p->rope_cos, p->rope_sin, s, p->qk_norm ? 3 : 0));
-        if (p->causal) SAT_TRY(sat_launch_attention_f32_causal(Q32, K32, V32, AO32, bf, H, H, hd, S, s));
-        else SAT_TRY(sat_launch_attention_f32_w(Q32, K32, V32, AO32, bf, H, H, hd, S, S, s));
-    }
+    SAT_TRY(split_heads_f32(p, w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->qk_norm ? 3 : 0, s));
+    SAT_TRY(attention_f32(p, p->causal, Q32, K32, V32, AO32, bf, H, H, S, S, s));
     SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.o), nullptr, w.X, M, D, D, D, 1, m ? m + 2 * D : nullptr, S, ssg_ld, s));
     if (bc > 0) {
         SAT_TRY(norm(L.cross_g, L.cross_b, Mc, nullptr, nullptr, 1, 0));
         SAT_TRY(sat_launch_gemm_f32(A32, W32(L.cq), nullptr, w.f32_wide, Mc, D, D, D, 0, nullptr, 1, 0, s));
-        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lc * hd;
-        if (hd == 64) {
-            SAT_TRY(sat_launch_split_heads_f32(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
-            SAT_TRY(sat_launch_attention_f32(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, S, p->ctx_lc, s));
-        } else {
-            SAT_TRY(sat_launch_split_heads_f32_w(w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, hd, 0, nullptr, nullptr, s, p->qk_norm ? 1 : 0));
-            SAT_TRY(sat_launch_attention_f32_w(Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, hd, S, p->ctx_lc, s));
-        }
+        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lc * p->hd;
+        SAT_TRY(split_heads_f32(p, w.f32_wide, Q32, nullptr, nullptr, Mc, S, 1, H, 0, p->qk_norm ? 1 : 0, s));
+        SAT_TRY(attention_f32(p, false, Q32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, AO32, bc, H, p->kvh_cross, S, p->ctx_lc, s));
         SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.co), nullptr, w.X, Mc, D, D, D, 1, nullptr, 1, 0, s));
     }
     if (p->conformer) {      // transformer.py:680-681, 697-698 (the launches of Forward::conformer in fp32)
@@ -599,73 +605,26 @@ int Forward::block_f32(int l) const {
     return sat_launch_gemm_f32(H32, W32(L.ff2), L.ff2.bias, w.X, M, D, inner, D, 1, m ? m + 5 * D : nullptr, S, ssg_ld, s);
 }
 
-// The two attention branches of a block with 128-, 32- or 96-channel heads, staged: the heads epilogues, the fused to_q + cross-attention launch and the
-// LayerNorm fold keep one head = one 64-column wave tile (gemm_bf16.hip), so each projection runs as a plain fp32-output GEMM into qkv32, the
-// head split (head_split_hdw.hip: qk_norm, rotation, pre-scale, one rounding) writes Q / K / V^T, and attention_hdw.hip attends
-// (Forward::head_split / attend).  Two more launches and one fp32 round trip per attention than the 64-channel route
-int Forward::attention_staged(int l) const {
-    const LayerW& L = p->layers[l];
-    const float* m = mod(l);
-    const int f16 = L.qkv.f16, qn = p->qk_norm ? 16 : 0;
-    SAT_TRY(layernorm(L.qkv, L.pre_g, L.pre_b, M, true, m, m ? m + D : nullptr));
-    SAT_TRY(range(l, RS_A_QKV, w.A, (size_t)M * D, (size_t)M * D));
-    GemmArgs g = gemm(L.qkv, w.A, M);
-    g.C = w.qkv32; g.ldc = 3 * D;
-    SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
-    HeadsEpi he{};
-    he.out[0] = w.Q; he.out[1] = w.K; he.out[2] = w.Vt;
-    he.kind[0] = 2 | 8 | qn; he.kind[1] = 2 | 4 | qn; he.kind[2] = 1 | 4; he.qscale = staged_qscale();
-    he.parts = 3; he.heads = H; he.S = S; he.Spad = Spad;
-    he.rope_cos = p->rope_cos; he.rope_sin = p->rope_sin;
-    SAT_TRY(head_split(w.qkv32, he, bf, f16));
-    SAT_TRY(range_heads(l, RS_Q, w.Q, bf));
-    SAT_TRY(range_heads(l, RS_K, w.K, bf));
-    SAT_TRY(range_heads(l, RS_V, w.Vt, bf));
-    SAT_TRY(attend(w.Q, w.K, w.Vt, bf, H, S, Spad, f16, true));
-    SAT_TRY(range(l, RS_ATTN_OUT, w.AO, (size_t)M * D, (size_t)M * D));
-    SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
-    if (bc > 0) {      // (the sequences behind bc have an all-zero context: Forward::block)
-        SAT_TRY(layernorm(L.cq, L.cross_g, L.cross_b, Mc, false, nullptr, nullptr));
-        SAT_TRY(range(l, RS_A_CROSS_Q, w.A, (size_t)Mc * D, (size_t)Mc * D));
-        g = gemm(L.cq, w.A, Mc);
-        g.C = w.qkv32; g.ldc = D;
-        SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
-        he = HeadsEpi{};
-        he.out[0] = w.Q; he.kind[0] = 8 | qn; he.qscale = staged_qscale();
-        he.parts = 1; he.heads = H; he.S = S; he.Spad = Spad;
-        SAT_TRY(head_split(w.qkv32, he, bc, f16));
-        SAT_TRY(range_heads(l, RS_CROSS_Q, w.Q, bc));
-        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * p->hd;
-        SAT_TRY(attend(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, bc, p->kvh_cross, p->ctx_lc, p->ctx_lcpad, f16));
-        SAT_TRY(range(l, RS_CROSS_ATTN_OUT, w.AO, (size_t)Mc * D, (size_t)Mc * D));
-        SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
-    }
-    return 0;
-}
-
+// The two attention branches, the conformer and the feed-forward of one block.  The branches are the same launches at every head width but for
+// the projections into heads (project_heads) and the attention kernel (attend): the staged widths (128, 32, 96) take two more launches and one
+// fp32 round trip through qkv32 per attention than the 64-channel route, and neither the fused to_q + cross-attention launch nor the fold
 int Forward::block(int l) const {
     const LayerW& L = p->layers[l];
     const float* m = mod(l);
     const int f16 = L.qkv.f16, qn = p->qk_norm ? 16 : 0;      // HeadsEpi::kind bit 4 on the q / k parts
-    auto mx_scales = [&](const Proj& out) { return out.kind == PROJ_FP8_MX ? w.AOs : nullptr; };      // the attention kernels write to_out's MXFP8 operand
-    if (p->staged()) {
-        SAT_TRY(attention_staged(l));
-        return feed_forward(l);
-    }
     // ---- self-attention branch (transformer.py:692)
     SAT_TRY(layernorm(L.qkv, L.pre_g, L.pre_b, M, true, m, m ? m + D : nullptr));
     SAT_TRY(range(l, RS_A_QKV, w.A, (size_t)M * D, (size_t)M * D));
-    GemmArgs g = gemm(L.qkv, w.A, M);
-    g.heads.out[0] = w.Q; g.heads.out[1] = w.K; g.heads.out[2] = w.Vt;
-    g.heads.kind[0] = 2 | 8 | qn; g.heads.kind[1] = 2 | 4 | qn; g.heads.kind[2] = 1 | 4; g.heads.qscale = SAT_ATTN_QSCALE;
-    g.heads.parts = 3; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
-    g.heads.rope_cos = p->rope_cos; g.heads.rope_sin = p->rope_sin;
-    SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
+    HeadsEpi he{};
+    he.out[0] = w.Q; he.out[1] = w.K; he.out[2] = w.Vt;
+    he.kind[0] = 2 | 8 | qn; he.kind[1] = 2 | 4 | qn; he.kind[2] = 1 | 4; he.qscale = qscale();
+    he.parts = 3; he.heads = H; he.S = S; he.Spad = Spad;
+    he.rope_cos = p->rope_cos; he.rope_sin = p->rope_sin;
+    SAT_TRY(project_heads(p, gemm(L.qkv, w.A, M), he, w.qkv32, bf, s));
     SAT_TRY(range_heads(l, RS_Q, w.Q, bf));
     SAT_TRY(range_heads(l, RS_K, w.K, bf));
     SAT_TRY(range_heads(l, RS_V, w.Vt, bf));
-    if (p->causal) SAT_TRY(sat_launch_attention_causal(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, Spad, Spad, s, 1.0f, f16));      // (never an e4m3 plan)
-    else SAT_TRY(sat_launch_attention(w.Q, w.K, w.Vt, w.AO, bf, H, H, S, S, Spad, Spad, s, mx_scales(L.o), 1.0f, f16));
+    SAT_TRY(attend(w.Q, w.K, w.Vt, bf, H, S, Spad, f16, L.o, true));
     SAT_TRY(range(l, RS_ATTN_OUT, w.AO, (size_t)M * D, (size_t)M * D));
     SAT_TRY(resid(L.o, w.AO, M, m ? m + 2 * D : nullptr, true, l, 0));
     // ---- cross-attention branch (transformer.py:694-695).  Sequences whose context is all-zero (the
@@ -675,29 +634,29 @@ int Forward::block(int l) const {
     if (bc > 0) {
         SAT_TRY(layernorm(L.cq, L.cross_g, L.cross_b, Mc, false, nullptr, nullptr));
         SAT_TRY(range(l, RS_A_CROSS_Q, w.A, (size_t)Mc * D, (size_t)Mc * D));
-        g = gemm(L.cq, w.A, Mc);
-        g.heads.out[0] = w.Q; g.heads.kind[0] = 8 | qn; g.heads.qscale = SAT_ATTN_QSCALE;
-        g.heads.parts = 1; g.heads.heads = H; g.heads.S = S; g.heads.Spad = Spad;
-        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * 64;
+        he = HeadsEpi{};
+        he.out[0] = w.Q; he.kind[0] = 8 | qn; he.qscale = qscale();
+        he.parts = 1; he.heads = H; he.S = S; he.Spad = Spad;
+        const size_t per_layer = (size_t)bf * p->kvh_cross * p->ctx_lcpad * p->hd;
+        const op_t *kc = p->kc + l * per_layer, *vct = p->vct + l * per_layer;
         // One launch for to_q + softmax(q k^T) v where the 128 x 64 tile is the choice anyway and its workgroups fit one round
         // (one prompt: 9 x 24 = 216): the projection's epilogue keeps Q in registers and attends to the <= 189 context keys
-        // staged in LDS (gemm_bf16.hip, XA_OK).  Saves the attention launch and the Q round trip.  16-bit operands only.
-        const bool fuse = p->cross_fusion && L.cq.kind != PROJ_FP8_ROW && L.co.kind != PROJ_FP8_MX && D >= 192 && p->ctx_lc + 3 <= 192 &&
-                          cdiv(Mc, 128) * (D / 64) <= 256;
+        // staged in LDS (gemm_bf16.hip, XA_OK).  Saves the attention launch and the Q round trip.  16-bit operands, 64-channel heads only.
+        const bool fuse = !p->staged() && p->cross_fusion && L.cq.kind != PROJ_FP8_ROW && L.co.kind != PROJ_FP8_MX && D >= 192 &&
+                          p->ctx_lc + 3 <= 192 && cdiv(Mc, 128) * (D / 64) <= 256;
         if (fuse) {
-            g.heads.xa_k = p->kc + l * per_layer; g.heads.xa_vt = p->vct + l * per_layer; g.heads.xa_out = w.AO;
-            g.heads.xa_kvh = p->kvh_cross; g.heads.xa_sk = p->ctx_lc; g.heads.xa_sk_pad = p->ctx_lcpad;
+            he.xa_k = kc; he.xa_vt = vct; he.xa_out = w.AO;
+            he.xa_kvh = p->kvh_cross; he.xa_sk = p->ctx_lc; he.xa_sk_pad = p->ctx_lcpad;
         }
-        SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
+        SAT_TRY(project_heads(p, gemm(L.cq, w.A, Mc), he, w.qkv32, bc, s));
         if (!fuse) {      // (the fused launch keeps Q in registers: its slot of the range report stays empty)
             SAT_TRY(range_heads(l, RS_CROSS_Q, w.Q, bc));
-            SAT_TRY(sat_launch_attention(w.Q, p->kc + l * per_layer, p->vct + l * per_layer, w.AO, bc, H, p->kvh_cross, S, p->ctx_lc, Spad,
-                                         p->ctx_lcpad, s, mx_scales(L.co), 1.0f, f16));
+            SAT_TRY(attend(w.Q, kc, vct, bc, p->kvh_cross, p->ctx_lc, p->ctx_lcpad, f16, L.co, false));
         }
         SAT_TRY(range(l, RS_CROSS_ATTN_OUT, w.AO, (size_t)Mc * D, (size_t)Mc * D));
         SAT_TRY(resid(L.co, w.AO, Mc, nullptr, true, l, 1));
     }
-    if (p->conformer) SAT_TRY(conformer(l));
+    if (p->conformer) SAT_TRY(conformer(l));      // (64-channel heads only: sat_dit_plan_set_block_options)
     return feed_forward(l);
 }
 
@@ -1022,7 +981,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
     const size_t o_vc = lay.take_off(kv_elems * (f32 ? 4 : 2));
     const size_t o_kv32 = (cross && f32) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;
     const size_t o_ce32 = (cross && f32) ? lay.take_off((size_t)R * Dc * 4) : 0;
-    const size_t o_kv128 = (cross && p->staged() && !f32) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;      // fp32 to_kv output in front of the head split
+    const size_t o_kv_staged = (cross && p->staged() && !f32) ? lay.take_off((size_t)R * 2 * Dc * 4) : 0;      // fp32 to_kv output in front of the head split
     // blocks of both operand formats (sat_dit_plan_set_block_formats): a second image of the context embedding, in the other format than layer 0's
     int mixed = 0;
     for (int l = 1; l < c.depth; ++l) mixed |= layer_f16(p, l) != layer_f16(p, 0);
@@ -1049,12 +1008,7 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
         const size_t per_layer = (size_t)bf * p->kvh_cross * lc * p->hd;
         for (int l = 0; l < c.depth; ++l) {
             SAT_TRY(sat_launch_gemm_f32(ce32, (const float*)p->layers[l].ckv.w, nullptr, kv32, R, 2 * Dc, Dc, 2 * Dc, 0, nullptr, 1, 0, s));
-            if (p->hd == 64)
-                SAT_TRY(sat_launch_split_heads_f32(kv32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, nullptr, R, lc, 2, p->kvh_cross, 0, nullptr,
-                                                   nullptr, s, p->qk_norm ? 1 : 0));
-            else
-                SAT_TRY(sat_launch_split_heads_f32_w(kv32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, nullptr, R, lc, 2, p->kvh_cross, p->hd, 0,
-                                                     nullptr, nullptr, s, p->qk_norm ? 1 : 0));
+            SAT_TRY(split_heads_f32(p, kv32, p->kc32 + l * per_layer, p->vc32 + l * per_layer, nullptr, R, lc, 2, p->kvh_cross, 0, p->qk_norm ? 1 : 0, s));
         }
     } else if (cross) {   // dit.py:150 then per-layer to_kv (transformer.py:420-427)
         float* ch = (float*)(p->ctx_buf.ptr + o_ch);
@@ -1067,28 +1021,17 @@ extern "C" int sat_dit_prepare_context(sat_dit_plan* p, const float* cond, int32
         SAT_HIP(hipMemsetAsync(p->kc, 0, kv_elems * 2, s));
         SAT_HIP(hipMemsetAsync(p->vct, 0, kv_elems * 2, s));
         const size_t per_layer = (size_t)bf * p->kvh_cross * lcpad * p->hd;
-        for (int l = 0; l < c.depth; ++l) {
+        float* kv32 = p->staged() ? (float*)(p->ctx_buf.ptr + o_kv_staged) : nullptr;
+        for (int l = 0; l < c.depth; ++l) {      // k: normalised under qk_norm, v transposed
             GemmArgs g{};
             g.f16 = layer_f16(p, l);
             g.A = g.f16 == f16_0 ? ce : ce_other; g.W = p->layers[l].ckv.w; g.M = R; g.N = 2 * Dc; g.K = Dc;
-            if (p->staged()) {      // staged, as Forward::attention_staged: fp32 [R, 2 Dc] -> head split (k: normalised under qk_norm, v transposed)
-                float* kv32 = (float*)(p->ctx_buf.ptr + o_kv128);
-                g.C = kv32; g.ldc = 2 * Dc;
-                SAT_TRY(sat_launch_gemm(EPI_F32, g, s));
-                HeadsEpi he{};
-                he.out[0] = p->kc + l * per_layer; he.out[1] = p->vct + l * per_layer;
-                he.kind[0] = 4 | (p->qk_norm ? 16 : 0); he.kind[1] = 1 | 4; he.parts = 2; he.heads = p->kvh_cross;
-                he.S = lc; he.Spad = lcpad;
-                SAT_TRY(sat_launch_head_split_hdw(kv32, he, p->hd, bf, s, g.f16));
-                SAT_TRY(range_stats(p, l, RS_CROSS_K, p->kc + l * per_layer, per_layer, (size_t)R * Dc, s));
-                SAT_TRY(range_stats(p, l, RS_CROSS_V, p->vct + l * per_layer, per_layer, (size_t)R * Dc, s));
-                continue;
-            }
-            g.heads.out[0] = p->kc + l * per_layer; g.heads.out[1] = p->vct + l * per_layer;
-            g.heads.kind[0] = 4 | (p->qk_norm ? 16 : 0); g.heads.kind[1] = 1 | 4; g.heads.parts = 2; g.heads.heads = p->kvh_cross;
-            g.heads.S = lc; g.heads.Spad = lcpad;
-            g.variant = 1;
-            SAT_TRY(sat_launch_gemm(EPI_HEADS, g, s));
+            if (!p->staged()) g.variant = 1;
+            HeadsEpi he{};
+            he.out[0] = p->kc + l * per_layer; he.out[1] = p->vct + l * per_layer;
+            he.kind[0] = 4 | (p->qk_norm ? 16 : 0); he.kind[1] = 1 | 4; he.parts = 2; he.heads = p->kvh_cross;
+            he.S = lc; he.Spad = lcpad;
+            SAT_TRY(project_heads(p, g, he, kv32, bf, s));
             // (the layer's whole cache: lcpad - lc zero pad keys per head beside the bf * lc * Dc values)
             SAT_TRY(range_stats(p, l, RS_CROSS_K, p->kc + l * per_layer, per_layer, (size_t)R * Dc, s));
             SAT_TRY(range_stats(p, l, RS_CROSS_V, p->vct + l * per_layer, per_layer, (size_t)R * Dc, s));
@@ -1172,8 +1115,8 @@ extern "C" int sat_dit_plan_set_block_options(sat_dit_plan* p, const sat_dit_blo
                   SAT_E_UNSUPPORTED, "dit_plan_set_block_options: unknown value (conformer %d, remove_norms %d, ff_glu %d)", o->conformer, o->remove_norms,
                   o->ff_glu);
     const bool any = o->conformer || o->remove_norms || !o->ff_glu;
-    // the e4m3 epilogues and the quantising LayerNorm know neither a missing norm nor the plain activation; the staged 128-channel-head route
-    // keeps the standalone LayerNorms of the shipped block
+    // the e4m3 epilogues and the quantising LayerNorm know neither a missing norm nor the plain activation; the staged route (128-, 32-
+    // and 96-channel heads) keeps the standalone LayerNorms of the shipped block
     SAT_CHECK_ARG(!any || p->cfg.gemm_dtype != SAT_GEMM_FP8, SAT_E_UNSUPPORTED,
                   "dit_plan_set_block_options: conformer / remove_norms / ff_glu 0 with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
     SAT_CHECK_ARG(!any || p->hd == 64, SAT_E_UNSUPPORTED, "dit_plan_set_block_options: conformer / remove_norms / ff_glu 0 with dim_heads %d is not built (64 only)", p->hd);
@@ -1237,7 +1180,7 @@ extern "C" int sat_dit_plan_set_ff_conv(sat_dit_plan* p, const sat_dit_ff_conv_o
     SAT_CHECK_ARG(k % 2 == 1, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: kernel_size %d is even: the reference's convolution then returns one row more than it was given", k);
     SAT_CHECK_ARG(k <= 7, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: kernel_size %d: the convolution GEMM is built for 1, 3, 5 and 7", k);
     // the e4m3 operands carry one scale per row or per 32 k of a row, which a row-shifted read would have to shift as well; the staged
-    // 128-channel-head route keeps the shipped block, as for sat_dit_plan_set_block_options
+    // route (128-, 32- and 96-channel heads) keeps the shipped block, as for sat_dit_plan_set_block_options
     SAT_CHECK_ARG(k == 1 || p->cfg.gemm_dtype != SAT_GEMM_FP8, SAT_E_UNSUPPORTED,
                   "dit_plan_set_ff_conv: a convolutional feed-forward with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
     SAT_CHECK_ARG(k == 1 || p->hd == 64, SAT_E_UNSUPPORTED, "dit_plan_set_ff_conv: a convolutional feed-forward with dim_heads %d is not built (64 only)", p->hd);
