@@ -669,6 +669,8 @@ extern "C" int sat_dpmpp3m_update(float* x_dev, const float* d_dev, const float*
     SAT_CHECK_ARG(x_dev && d_dev && n > 0, SAT_E_INVALID, "dpmpp3m_update: null state or n <= 0");
     SAT_CHECK_ARG(!(c1 != 0.f && !d1_dev) && !(c2 != 0.f && !d2_dev) && !(cn != 0.f && !noise_dev), SAT_E_INVALID,
                   "dpmpp3m_update: non-zero coefficient with a NULL tensor");
+    // c2 multiplies (d1 - d2): it needs d1 as much as d2
+    SAT_CHECK_ARG(!(c2 != 0.f && !d1_dev), SAT_E_INVALID, "dpmpp3m_update: c2 != 0 needs d1_dev as well as d2_dev");
     int blocks = (int)((n + 255) / 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(dpmpp3m_update_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x_dev, d_dev,

@@ -427,7 +427,9 @@ int sat_cfg_combine(const float* model_out_dev, float* out_dev, int32_t b, int32
  * inference/sampling.py:228), fused elementwise over n elements:
  *   x <- a*x + b*d + c1*(d - d1) + c2*(d1 - d2) + cn*noise     (in place on x_dev)
  * The host computes the scalars from the sigma schedule (see the Python host code);
- * d1_dev / d2_dev / noise_dev may be NULL when their coefficient is 0. */
+ * d1_dev / d2_dev / noise_dev may be NULL when their coefficient is 0.  A non-zero coefficient
+ * with a NULL tensor is SAT_E_INVALID; c2 multiplies (d1 - d2), so c2 != 0 needs d1_dev as well
+ * as d2_dev (the term is never dropped). */
 int sat_dpmpp3m_update(float* x_dev, const float* d_dev, const float* d1_dev, const float* d2_dev,
                        const float* noise_dev, float a, float b, float c1, float c2, float cn,
                        int64_t n, sat_stream_t stream);
@@ -601,7 +603,8 @@ int sat_vae_sample(const float* mean_scale_dev, const float* noise_dev, float* z
 
 /* float_to_int16_audio (utils/audio_utils.py:21-26) for one item of n samples:
  * peak = max|x| (device reduction), div = maximize ? peak : max(peak, 1),
- * out = (int16) trunc(x / div * 32767).  scratch_dev: >= 4 bytes. */
+ * out = (int16) trunc(x / div * 32767).  scratch_dev: >= 4 bytes (overwritten, need not be cleared).
+ * All-zero input gives all-zero output under both settings of maximize. */
 int sat_float_to_int16(const float* x_dev, int16_t* out_dev, int64_t n, int32_t maximize,
                        void* scratch_dev, sat_stream_t stream);
 
