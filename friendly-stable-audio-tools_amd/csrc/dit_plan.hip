@@ -92,6 +92,9 @@ struct sat_dit_plan {
     int tokens(int t_len) const { return t_len / patch; }
     // ContinuousTransformer causal (sat_dit_plan_set_attention_options): every self-attention runs the causal launchers; false changes nothing
     bool causal = false;
+    // attn_kwargs natten_kernel_size (sat_dit_plan_set_neighborhood_attention): every self-attention sees a window of this many keys and its
+    // logits are not scaled by 1 / sqrt(dim_heads) (attention_window.hip); 0 = full attention and nothing changes
+    int natten = 0;
     // per-generation context (sat_dit_prepare_context)
     DevBuf ctx_buf;
     int ctx_bf = 0, ctx_lc = 0, ctx_lcpad = 0;
@@ -179,9 +182,11 @@ int split_heads_f32(const sat_dit_plan* p, const float* src, float* d0, float* d
     if (p->hd == 64) return sat_launch_split_heads_f32(src, d0, d1, d2, M, S, parts, H, rope_mask, rc, rs, s, norm_mask);
     return sat_launch_split_heads_f32_w(src, d0, d1, d2, M, S, parts, H, p->hd, rope_mask, rc, rs, s, norm_mask);
 }
-int attention_f32(const sat_dit_plan* p, bool causal, const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int sq, int sk,
+// self: the self-attention of a block (sq == sk), which a causal or a neighbourhood plan runs on its own kernel (never both: the setters refuse)
+int attention_f32(const sat_dit_plan* p, bool self, const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int sq, int sk,
                   hipStream_t s) {
-    if (causal) return sat_launch_attention_f32_causal(q, k, v, out, b, h, kvh, p->hd, sq, s);
+    if (self && p->causal) return sat_launch_attention_f32_causal(q, k, v, out, b, h, kvh, p->hd, sq, s);
+    if (self && p->natten) return sat_launch_attention_f32_window(q, k, v, out, b, h, kvh, sq, p->natten, 1.0f, s);      // unscaled logits
     if (p->hd == 64) return sat_launch_attention_f32(q, k, v, out, b, h, kvh, sq, sk, s);
     return sat_launch_attention_f32_w(q, k, v, out, b, h, kvh, p->hd, sq, sk, s);
 }
@@ -531,7 +536,8 @@ struct Forward {
     }
 
     // log2(e) / sqrt(dim_heads), what the projections pre-scale q by (HeadsEpi kind bit 3): the constant the 64-channel kernels were built with
-    float qscale() const { return p->staged() ? sat_attn_qscale(p->hd) : SAT_ATTN_QSCALE; }
+    // A neighbourhood plan (64-channel heads, no cross-attention) does not scale its logits: log2(e) alone
+    float qscale() const { return p->natten ? 1.4426950408889634f : p->staged() ? sat_attn_qscale(p->hd) : SAT_ATTN_QSCALE; }
     // AO = softmax(q k^T) v for `seqs` sequences of S queries against sk keys (pad sk_pad) in kvh heads: attention.hip at 64 channels per head,
     // attention_hdw.hip at the staged widths; the causal kernels for the self-attention of a causal plan (sk == S; never an e4m3 plan).  `out`: the
     // projection that reads AO; as an MXFP8 operand the kernel writes its block scales beside it (64 channels only)
@@ -542,6 +548,8 @@ struct Forward {
             return sat_launch_attention_hdw(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, sk, Spad, sk_pad, s, f16);
         }
         if (causal) return sat_launch_attention_causal(q, k, vt, w.AO, seqs, H, kvh, S, Spad, sk_pad, s, 1.0f, f16);
+        // the projection wrote Q times log2(e) (qscale): the kernel multiplies its scores by 1
+        if (self && p->natten) return sat_launch_attention_window(q, k, vt, w.AO, seqs, H, kvh, S, Spad, sk_pad, p->natten, 1.0f, s, f16);
         return sat_launch_attention(q, k, vt, w.AO, seqs, H, kvh, S, sk, Spad, sk_pad, s, out.kind == PROJ_FP8_MX ? w.AOs : nullptr, 1.0f, f16);
     }
 
@@ -567,7 +575,7 @@ int Forward::block_f32(int l) const {
     SAT_TRY(norm(L.pre_g, L.pre_b, M, m, m ? m + D : nullptr, S, ssg_ld));
     SAT_TRY(sat_launch_gemm_f32(A32, W32(L.qkv), nullptr, w.f32_wide, M, 3 * D, D, 3 * D, 0, nullptr, 1, 0, s));
     SAT_TRY(split_heads_f32(p, w.f32_wide, Q32, K32, V32, M, S, 3, H, 3, p->qk_norm ? 3 : 0, s));
-    SAT_TRY(attention_f32(p, p->causal, Q32, K32, V32, AO32, bf, H, H, S, S, s));
+    SAT_TRY(attention_f32(p, true, Q32, K32, V32, AO32, bf, H, H, S, S, s));
     SAT_TRY(sat_launch_gemm_f32(AO32, W32(L.o), nullptr, w.X, M, D, D, D, 1, m ? m + 2 * D : nullptr, S, ssg_ld, s));
     if (bc > 0) {
         SAT_TRY(norm(L.cross_g, L.cross_b, Mc, nullptr, nullptr, 1, 0));
@@ -754,6 +762,9 @@ int run_forward(sat_dit_plan* p, const float* x, int xB, float xscale, const flo
     SAT_CHECK_ARG(p->pos_emb != SAT_DIT_POS_ABSOLUTE || S <= p->abs_max, SAT_E_INVALID,
                   "dit forward: you are passing in a sequence length of %d but your absolute positional embedding has a max sequence length of %d", S,
                   p->abs_max);
+    // what NATTEN rejects, before anything is launched: the window does not fit the rows the blocks see
+    SAT_CHECK_ARG(!p->natten || S >= p->natten, SAT_E_INVALID,
+                  "dit forward: a sequence of %d rows (prepend rows + global token + tokens) is shorter than natten_kernel_size %d", S, p->natten);
 
     // pads of q/k/vt must be finite (zero): one memset per forward
     if (!f32) SAT_HIP(hipMemsetAsync(w.Q, 0, 3 * (size_t)round_up((int64_t)w.qkv_bytes, 256), s));
@@ -1146,7 +1157,36 @@ extern "C" int sat_dit_plan_set_attention_options(sat_dit_plan* p, const sat_dit
                   "dit_plan_set_attention_options: causal with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
     SAT_CHECK_ARG(!o->causal || (sat_launch_attention_causal && sat_launch_attention_hdw_causal && sat_launch_attention_f32_causal), SAT_E_UNSUPPORTED,
                   "dit_plan_set_attention_options: built without the causal attention kernels");
+    SAT_CHECK_ARG(!(o->causal && p->natten), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_attention_options: causal on a neighbourhood-attention plan: the reference ignores causal in that branch");
     p->causal = o->causal != 0;
+    return 0;
+}
+
+extern "C" int sat_dit_plan_set_neighborhood_attention(sat_dit_plan* p, const sat_dit_neighborhood_options* o, size_t options_bytes) {
+    SAT_CHECK_ARG(p && o, SAT_E_INVALID, "dit_plan_set_neighborhood_attention: null argument");
+    SAT_CHECK_ARG(options_bytes == sizeof(sat_dit_neighborhood_options), SAT_E_INVALID,
+                  "dit_plan_set_neighborhood_attention: sat_dit_neighborhood_options of %zu bytes; this library knows %zu", options_bytes,
+                  sizeof(sat_dit_neighborhood_options));
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_neighborhood_attention: plan already finalized (call it between create and finalize)");
+    const int ks = o->kernel_size;
+    // 0: full attention (the reference tests the value's truth); else what NATTEN takes: odd and greater than 1
+    SAT_CHECK_ARG(ks == 0 || (ks > 1 && (ks & 1)), SAT_E_INVALID,
+                  "dit_plan_set_neighborhood_attention: kernel_size %d must be 0 (off) or odd and greater than 1", ks);
+    // transformer.py:299, 324: attn_kwargs reach cross_attn too, where q and k differ in length and NATTEN fails: no behaviour to reproduce
+    SAT_CHECK_ARG(!(ks && p->cfg.cond_token_dim > 0), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention: natten_kernel_size with cross-attention (cond_token_dim %d): the reference has no working behaviour there",
+                  p->cfg.cond_token_dim);
+    // transformer.py:479: the branch never looks at causal
+    SAT_CHECK_ARG(!(ks && p->causal), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention: natten_kernel_size on a causal plan: the reference ignores causal in that branch");
+    SAT_CHECK_ARG(!(ks && p->cfg.gemm_dtype == SAT_GEMM_FP8), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention: natten_kernel_size with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
+    SAT_CHECK_ARG(!(ks && p->hd != 64), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention: natten_kernel_size with dim_heads %d is not built (64 only; the staged widths are a follow-up)", p->hd);
+    SAT_CHECK_ARG(!ks || (sat_launch_attention_window && sat_launch_attention_f32_window), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention: built without the neighbourhood attention kernels");
+    p->natten = ks;
     return 0;
 }
 

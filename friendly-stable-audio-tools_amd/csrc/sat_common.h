@@ -372,6 +372,12 @@ __attribute__((weak)) int sat_launch_attention_causal(const op_t* q, const op_t*
                                                       int sk_pad, hipStream_t s, float q_scale = SAT_ATTN_QSCALE, int f16 = 0);
 __attribute__((weak)) int sat_launch_attention_hdw_causal(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int head_dim,
                                                           int s_len, int sq_pad, int sk_pad, hipStream_t s, int f16 = 0);
+// ---- neighbourhood self-attention (sat_dit_plan_set_neighborhood_attention; attention_window.hip, attn_window.h): 64-channel heads, sq == sk ==
+// s_len >= kernel_size, query i sees the kernel_size keys from min(max(i - kernel_size / 2, 0), s_len - kernel_size) on.  Layouts and pads as
+// sat_launch_attention.  score_scale: what the scores are multiplied by in front of exp2 -- log2(e) for a plain Q (the reference does not scale
+// the logits of this branch), 1 for a Q its producer wrote times log2(e).  WEAK as the causal launchers
+__attribute__((weak)) int sat_launch_attention_window(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int s_len, int sq_pad,
+                                                      int sk_pad, int kernel_size, float score_scale, hipStream_t s, int f16 = 0);
 }  // namespace SAT_OPNS
 using namespace SAT_OPNS;
 // RotaryEmbedding(max(dim_heads / 2, 32)) (transformer.py:737): pairs (j, j + sat_rope_pairs) rotate, one angle per pair -- 16 for 32- and
@@ -429,6 +435,8 @@ int sat_launch_attention_causal_f16(const void* q, const void* k, const void* vt
                                     hipStream_t s, float q_scale);
 int sat_launch_attention_hdw_causal_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int head_dim, int s_len,
                                         int sq_pad, int sk_pad, hipStream_t s);
+int sat_launch_attention_window_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int s_len, int sq_pad, int sk_pad,
+                                    int kernel_size, float score_scale, hipStream_t s);
 // entry points of the fp16 build for the dispatchers of the bf16 build (GemmArgs is layout-identical in both builds: the pointer
 // element type is the only difference)
 int sat_launch_gemm_f16(int epi, const void* gemm_args, hipStream_t stream);
@@ -465,6 +473,9 @@ __attribute__((weak)) int sat_launch_attention_f32_w(const float* q, const float
 // causal self-attention in fp32 for head_dim 32 / 64 / 96 (sq == sk == s_len).  WEAK as above
 __attribute__((weak)) int sat_launch_attention_f32_causal(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int head_dim,
                                                           int s_len, hipStream_t s);
+// neighbourhood self-attention in fp32, 64-channel heads; the scores are multiplied by score_scale (the plan passes 1).  WEAK as above
+__attribute__((weak)) int sat_launch_attention_f32_window(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int s_len,
+                                                          int kernel_size, float score_scale, hipStream_t s);
 int sat_launch_cast_bf16(const float* x, op_t* y, int64_t n, hipStream_t s, int f16 = 0);
 int sat_launch_pack_rows_bf16(const float* w, op_t* out, int n, int k, int swiglu_interleave, hipStream_t s, int f16 = 0);
 int sat_launch_pack_bias(const float* b, float* out, int n, int swiglu_interleave, hipStream_t s);

@@ -291,6 +291,23 @@ extern "C" int sat_attention_f32_causal(const float* q, const float* k, const fl
     return sat_launch_attention_f32_causal(q, k, v, out, b, h, kvh, head_dim, s, (hipStream_t)stream);
 }
 
+// ---- neighbourhood self-attention alone (sat_dit_plan_set_neighborhood_attention): the two launchers Forward calls.  score_scale multiplies
+// q . k and nothing else does; the kernel works in the log2 domain, so the 16-bit launcher gets score_scale * log2(e)
+extern "C" int sat_attention_window_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t s,
+                                         int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, float score_scale, sat_stream_t stream) {
+    return sat_launch_attention_window((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, s, s_pad_q, s_pad_k, kernel_size,
+                                       score_scale * 1.4426950408889634f, (hipStream_t)stream, 0);
+}
+extern "C" int sat_attention_window_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh, int32_t s,
+                                        int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, float score_scale, sat_stream_t stream) {
+    return sat_launch_attention_window((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, s, s_pad_q, s_pad_k, kernel_size,
+                                       score_scale * 1.4426950408889634f, (hipStream_t)stream, 1);
+}
+extern "C" int sat_attention_f32_window(const float* q, const float* k, const float* v, float* out, int32_t b, int32_t h, int32_t kvh, int32_t s,
+                                        int32_t kernel_size, float score_scale, sat_stream_t stream) {
+    return sat_launch_attention_f32_window(q, k, v, out, b, h, kvh, s, kernel_size, score_scale, (hipStream_t)stream);
+}
+
 // qkn: q and k L2-normalised per head (qk_norm), q pre-scaled for the attention kernel as in the plan
 static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,
                                  float* rope_scratch, int32_t b, int32_t s_len, int32_t s_pad, int32_t d, int32_t variant,

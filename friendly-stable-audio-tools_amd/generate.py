@@ -81,6 +81,10 @@ def get_args():
                    help="build extension: the model config's DiT has causal=True (every self-attention is causal), which the constructor "
                         "refuses without an opt-in: sets \"allow_causal\": true in model.diffusion.config before the model is built "
                         "(with --model-config or the built-in config; an error with --model-name)")
+    p.add_argument("--allow-natten", action="store_true",
+                   help="build extension: the model config's DiT has attn_kwargs natten_kernel_size (every self-attention sees a neighbourhood "
+                        "of that many rows), which the constructor refuses without an opt-in: sets \"allow_natten\": true in "
+                        "model.diffusion.config before the model is built (with --model-config or the built-in config; an error with --model-name)")
     p.add_argument("--check-fp16-range", action="store_true",
                    help="build extension, for a checkpoint this build was never run on: before generating, run the first batch once for 8 "
                         "steps with the activation range reports of the DiT and the codec on and print how close their 16-bit buffers come "
@@ -98,6 +102,9 @@ def get_args():
     if args.allow_causal and args.model_name:
         p.error("--allow-causal is written into the model config before the model is built: it goes with --model-config, not with "
                 "--model-name (a pretrained model is built from its own config)")
+    if args.allow_natten and args.model_name:
+        p.error("--allow-natten is written into the model config before the model is built: it goes with --model-config, not with "
+                "--model-name (a pretrained model is built from its own config)")
     return args
 
 
@@ -111,6 +118,8 @@ def apply_config_flags(args, model_config):
         model_config["model"]["diffusion"]["config"]["allow_head_widths"] = True
     if args.allow_causal:
         model_config["model"]["diffusion"]["config"]["allow_causal"] = True
+    if args.allow_natten:
+        model_config["model"]["diffusion"]["config"]["allow_natten"] = True
     return model_config
 
 

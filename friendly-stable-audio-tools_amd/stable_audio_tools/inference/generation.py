@@ -66,7 +66,13 @@ def generate_diffusion_cond(model, steps: int = 250, cfg_scale: float = 6, condi
     if negative_conditioning_tensors:
         negative = model.get_conditioning_inputs(negative_conditioning_tensors, negative=True)
         cond_inputs.update({k: (None if v is None else v.float()) for k, v in negative.items()})
-    num_sample = next(iter(conditioning_tensors.values()))[0].shape[0]           # batch size = that of the first conditioning tensor
+    # a neighbourhood-attention DiT (natten_kernel_size) needs a window's worth of rows: refused as soon as the prepend length is known, before
+    # anything is sampled (ValueError; the same check as forward / denoise)
+    dit = getattr(model.model, "model", None)
+    if getattr(getattr(dit, "transformer", None), "natten_kernel_size", 0):
+        prep = cond_inputs.get("prepend_cond")
+        dit._check_seq_len(frames, 0 if prep is None else prep.shape[1])
+    num_sample = next(iter(conditioning_tensors.values()))[0].shape[0]          # batch size = that of the first conditioning tensor
 
     ratio = model.pretransform.downsampling_ratio if model.pretransform else 1
     length = sample_size // ratio                                                # what the denoiser sees (latent frames)

@@ -33,6 +33,7 @@ class DiTWrapper(ConditionedDiffusionModel):
         # ... nor is patch_size > 1: "allow_patch_size": true, likewise
         # ... nor are 32- / 96-channel attention heads: "allow_head_widths": true, likewise
         # ... nor is causal=True: "allow_causal": true, likewise
+        # ... nor is attn_kwargs natten_kernel_size: "allow_natten": true, likewise
         self.model = DiffusionTransformer(*args, **kwargs)
         from . import _init
         if not _init._SKIP:

@@ -36,7 +36,7 @@ class DiffusionTransformer(nn.Module):
                  input_concat_dim: int = 0, prepend_cond_dim: int = 0, depth: int = 12, num_heads: int = 8,
                  transformer_type: str = "x-transformers", global_cond_type: str = "prepend", max_seq_len: int = 8192,
                  allow_block_options: bool = False, allow_conv_ff: bool = False, allow_patch_size: bool = False, allow_head_widths: bool = False,
-                 allow_causal: bool = False, **kwargs):
+                 allow_causal: bool = False, allow_natten: bool = False, **kwargs):
         """``allow_block_options``: the TransformerBlock options ``conformer``, ``remove_norms`` and ``ff_kwargs={"glu": False}`` are off the
         shipped configs' path and refused unless this is set; ``create_model_from_config`` and every other config-driven path set it.
         ``allow_conv_ff``: likewise for ``ff_kwargs={"use_conv": True}`` (``sat_dit_plan_set_ff_conv``); no path sets it by default, a config
@@ -50,7 +50,12 @@ class DiffusionTransformer(nn.Module):
         ``allow_causal``: likewise for ``causal=True`` (``sat_dit_plan_set_attention_options``): every self-attention is then causal over the
         sequence ``[prepend rows | global token | tokens]``, row i attends to the rows j <= i; a config asks for it with
         ``"allow_causal": true``.  Such a model has no cross-attention (``cond_token_dim=0``; the reference has no working behaviour there) and
-        runs with 'fp16', 'bf16' (also per block) and 'fp32x' operands at every head width; it adds no parameter."""
+        runs with 'fp16', 'bf16' (also per block) and 'fp32x' operands at every head width; it adds no parameter.
+        ``allow_natten``: likewise for ``attn_kwargs={"natten_kernel_size": K}`` (``sat_dit_plan_set_neighborhood_attention``): row i of the
+        n rows ``[prepend rows | global token | tokens]`` attends to the K rows from ``min(max(i - K // 2, 0), n - K)`` on, and the logits
+        are not scaled by ``dim_heads ** -0.5`` (the reference hands q to NATTEN as it is); a config asks for it with
+        ``"allow_natten": true``.  K is odd and greater than 1 and no sequence may be shorter than K (``ValueError``).  Such a model has
+        64-channel heads and no cross-attention, is not causal, and runs with 'fp16', 'bf16' (also per block) and 'fp32x' operands."""
         super().__init__()
         if transformer_type != "continuous_transformer":
             raise NotImplementedError("only transformer_type='continuous_transformer' is implemented (the shipped DiT configs)")
@@ -109,7 +114,8 @@ class DiffusionTransformer(nn.Module):
                                                  cond_token_dim=cond_embed_dim,
                                                  global_cond_dim=embed_dim if global_cond_type == "adaLN" else None,
                                                  allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff,
-                                                 allow_head_widths=allow_head_widths, allow_causal=allow_causal, **kwargs)
+                                                 allow_head_widths=allow_head_widths, allow_causal=allow_causal,
+                                                 allow_natten=allow_natten, **kwargs)
         self.preprocess_conv = _init.conv1d(dim_in, dim_in, 1, bias=False, zero=True)
         self.postprocess_conv = _init.conv1d(io_channels, io_channels, 1, bias=False, zero=True)
 
@@ -150,6 +156,9 @@ class DiffusionTransformer(nn.Module):
         if self.transformer.causal and GEMM_DTYPES[gemm_dtype] == 1:
             raise NotImplementedError(f"causal=True with gemm_dtype={gemm_dtype!r}: the MXFP8 output form of the attention kernels has no causal "
                                       "variant; use gemm_dtype 'fp16', 'bf16' or 'fp32x'")
+        if self.transformer.natten_kernel_size and GEMM_DTYPES[gemm_dtype] == 1:
+            raise NotImplementedError(f"natten_kernel_size={self.transformer.natten_kernel_size} with gemm_dtype={gemm_dtype!r}: the MXFP8 output "
+                                      "form of the attention kernels has no neighbourhood variant; use gemm_dtype 'fp16', 'bf16' or 'fp32x'")
         if self.transformer.dim_heads == 128 and GEMM_DTYPES[gemm_dtype] in (1, 2):
             raise NotImplementedError(f"dim_heads=128 (embed_dim {self.embed_dim} / num_heads {self.num_heads}) with gemm_dtype={gemm_dtype!r}: the "
                                       "128-channel-head route (fp32 projection, head split, attention) is built for 'fp16' and 'bf16' operands; the "
@@ -167,6 +176,11 @@ class DiffusionTransformer(nn.Module):
     def _check_seq_len(self, t_len, prepend_len):
         """The reference's ``AbsolutePositionalEmbedding`` assertion (transformer.py:59-61), on the host before anything is launched."""
         pe = self.transformer.pos_emb
+        if self.transformer.natten_kernel_size:      # what NATTEN rejects: a window that does not fit the rows the blocks see
+            seq_len = prepend_len + t_len // self.patch_size + (0 if self.global_cond_type == "adaLN" else 1)
+            if seq_len < self.transformer.natten_kernel_size:
+                raise ValueError(f"a sequence of {seq_len} rows (prepend rows + global token + tokens) is shorter than "
+                                 f"natten_kernel_size={self.transformer.natten_kernel_size}")
         if self.transformer.use_abs_pos_emb and not self.transformer.use_sinusoidal_emb:
             seq_len = prepend_len + t_len // self.patch_size + (0 if self.global_cond_type == "adaLN" else 1)
             assert seq_len <= pe.max_seq_len, \
@@ -341,7 +355,7 @@ class DiffusionTransformer(nn.Module):
     def _ensure_plan(self):
         ver = _init.params_version(self)
         options = (self.transformer_options() + self.transformer.block_options
-                   + (self.transformer.ff_conv_kernel, self.patch_size, 1 if self.transformer.causal else 0))
+                   + (self.transformer.ff_conv_kernel, self.patch_size, 1 if self.transformer.causal else 0, self.transformer.natten_kernel_size))
         if self._plan is not None and ver == self._plan_version and options == self._plan_options:
             return self._plan
         self._check_options(self.gemm_dtype)
@@ -372,6 +386,9 @@ class DiffusionTransformer(nn.Module):
             if options[9]:       # causal; likewise
                 aopts = _hip.SatDitAttentionOptions(1)
                 _hip.check(lib.sat_dit_plan_set_attention_options(plan, ctypes.byref(aopts), ctypes.sizeof(aopts)))
+            if options[10]:       # natten_kernel_size; likewise
+                nopts = _hip.SatDitNeighborhoodOptions(options[10])
+                _hip.check(lib.sat_dit_plan_set_neighborhood_attention(plan, ctypes.byref(nopts), ctypes.sizeof(nopts)))
             if self._block_gemm_dtypes is not None:       # a model that never set them never makes the call
                 fm = (ctypes.c_int32 * self.depth)(*[GEMM_DTYPES[f] for f in self._block_gemm_dtypes])
                 _hip.check(lib.sat_dit_plan_set_block_formats(plan, fm, self.depth))
@@ -466,12 +483,12 @@ class DiffusionTransformer(nn.Module):
     def _forward(self, x, t, cross_attn_cond=None, global_embed=None, null_from=-1, input_concat_cond=None, prepend_cond=None, **ignored):
         """dit.py:135-226 on the given batch (no CFG logic)."""
         self._check_t_len(x.shape[2])
+        self._check_seq_len(x.shape[2], 0 if prepend_cond is None else prepend_cond.shape[1])      # (host only: before the plan is built)
         self._reserve_prepend(prepend_cond)
         self._ensure_plan()
         x = x.detach().float().contiguous()
         t = t.detach().float().contiguous()
         bf, _, t_len = x.shape
-        self._check_seq_len(t_len, 0 if prepend_cond is None else prepend_cond.shape[1])
         if cross_attn_cond is None and global_embed is None:
             self.prepare_context_bf(bf)
         else:

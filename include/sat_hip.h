@@ -55,7 +55,8 @@ const char* sat_last_error(void);
  * FeedForward, LayerNorm, RotaryEmbedding), models/diffusion.py:482-529 (DiTWrapper).
  * Supported set: transformer_type "continuous_transformer", global_cond_type "prepend"
  * or "adaLN", dim_heads 64 or 128, patch_size 1 or, through sat_dit_plan_set_patch, above,
- * non-causal or, through sat_dit_plan_set_attention_options, causal self-attention without cross-attention, no masks (the reference discards
+ * non-causal or, through sat_dit_plan_set_attention_options, causal self-attention without cross-attention, or, through
+ * sat_dit_plan_set_neighborhood_attention, NATTEN's 1-D neighbourhood (natten_kernel_size; 64-channel heads, no cross-attention), no masks (the reference discards
  * them at inference: models/dit.py:250-252; prepend_cond_mask never reaches the layers,
  * models/transformer.py:787-802).  Input-concat and prepend conditioning (dit.py:160-197)
  * through sat_dit_plan_set_extra_conditioning / sat_dit_prepare_extra_conditioning; prepend
@@ -293,6 +294,26 @@ typedef struct sat_dit_attention_options {
     int32_t causal;         /* "causal" */
 } sat_dit_attention_options;
 int sat_dit_plan_set_attention_options(sat_dit_plan* plan, const sat_dit_attention_options* options, size_t options_bytes);
+
+/* Neighbourhood-attention DiT (ContinuousTransformer attn_kwargs natten_kernel_size, models/transformer.py:299,324,479-493 of the reference),
+ * between create and finalize; a plan never given this call, or given kernel_size 0, builds and launches exactly what it did before this
+ * call existed.  With kernel_size K every self-attention is NATTEN's 1-D neighbourhood of K keys, dilation 1, over the sequence the blocks
+ * see, n rows of [prepend rows | global token | tokens]: row i attends to the K rows start(i) .. start(i) + K - 1 of its own sequence,
+ * start(i) = min(max(i - K / 2, 0), n - K) -- the window is shifted, not truncated, at both ends.  q and k are taken behind qk_norm and
+ * the rotation, the softmax over the K logits runs in fp32, and the logits are NOT scaled by 1 / sqrt(dim_heads): the reference hands q to
+ * natten1dqk as it is.  The kernels copy and walk only the key tiles that hold a workgroup's windows (csrc/attn_window.h).  No tensor is
+ * added or renamed.  Runs with everything the 64-channel route runs with: bf16 / fp16 / per-block formats / SAT_GEMM_FP32X, both global
+ * conditionings, prepend and input-concat conditioning, the transformer and block options, ff_conv and patch_size (the window counts tokens).
+ * options_bytes = sizeof(sat_dit_neighborhood_options) of the caller's header; any other size is SAT_E_INVALID, as is a kernel_size that is
+ * neither 0 nor odd and greater than 1 (what NATTEN rejects); a call after finalize is SAT_E_STATE.  SAT_E_UNSUPPORTED, with
+ * "natten_kernel_size" in the message, for a kernel_size above 0 on a plan with cross-attention (cond_token_dim > 0: attn_kwargs reach
+ * cross_attn too, where NATTEN fails on q and k of different lengths), on a causal plan (the reference ignores causal in this branch; the
+ * causal call after this one is refused the same way), with gemm_dtype SAT_GEMM_FP8, or with dim_heads other than 64 (the staged widths are
+ * a follow-up).  sat_dit_forward and the fused denoise answer SAT_E_INVALID before any launch when n < kernel_size. */
+typedef struct sat_dit_neighborhood_options {
+    int32_t kernel_size;    /* "natten_kernel_size"; 0 = full attention */
+} sat_dit_neighborhood_options;
+int sat_dit_plan_set_neighborhood_attention(sat_dit_plan* plan, const sat_dit_neighborhood_options* options, size_t options_bytes);
 
 /* Operand format per block, between create and finalize: formats[l] is SAT_GEMM_FP16 or SAT_GEMM_BF16 for block l, n == depth.  A plan never
  * given this call, or given gemm_dtype in every entry, runs every block in gemm_dtype and builds and launches exactly what it did before this
@@ -696,6 +717,13 @@ int sat_head_split_hdw_bf16(const float* x_dev, const float* inv_freq_dev, void*
  * must be 1.  Any other head_dim is SAT_E_UNSUPPORTED. */
 int sat_attention_causal_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
                               int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t prescaled, sat_stream_t stream);
+/* ---- neighbourhood self-attention (sat_dit_plan_set_neighborhood_attention), test-only, 64-channel heads: query i of each of the b
+ * sequences of s rows sees the kernel_size keys from min(max(i - kernel_size / 2, 0), s - kernel_size) on.  Layouts and pad rules of
+ * sat_attention_causal_bf16 at head_dim 64.  score = q . k * score_scale with no other factor (1 / 8 reproduces scaled attention; the plan's
+ * logits are unscaled).  SAT_E_INVALID for an even kernel_size, one of 1 or less, s < kernel_size, or a score_scale that is not a positive
+ * finite number. */
+int sat_attention_window_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
+                              int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, float score_scale, sat_stream_t stream);
 /* Cross-attention query projection and attention core in one launch (models/transformer.py:430-437 + 496-536; what the DiT plan
  * runs per layer while the 128 x 64 GEMM tiles of the projection fit one round of workgroups, i.e. at one prompt):
  * out [b*s, d] bf16 = softmax((a wq^T) k^T / 8) v per head of 64, a [b*s, d] bf16, wq [d, d] bf16, k / vt in the key-side layout of
@@ -774,6 +802,8 @@ int sat_head_split_hdw_f16(const float* x_dev, const float* inv_freq_dev, void* 
                            int32_t b, int32_t s, int32_t s_pad, int32_t heads, int32_t head_dim, int32_t parts, sat_stream_t stream);
 int sat_attention_causal_f16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
                              int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t prescaled, sat_stream_t stream);
+int sat_attention_window_f16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
+                             int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, float score_scale, sat_stream_t stream);
 int sat_cross_attention_fused_f16(const void* a_f16_dev, const void* wq_f16_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                                   int32_t b, int32_t s, int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream);
 int sat_qkv_rope_f16(const void* a_f16_dev, const void* w_f16_dev, const float* inv_freq_dev,
@@ -965,6 +995,10 @@ int sat_attention_f32_hdw(const float* q_dev, const float* k_dev, const float* v
 /* The same attention, causal (sq == sk == s, query i sees the keys j <= i), for head_dim 32, 64 or 96 */
 int sat_attention_f32_causal(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
                              int32_t head_dim, int32_t s, sat_stream_t stream);
+/* The same attention over a neighbourhood of kernel_size keys (sat_attention_window_bf16's rule and errors), 64-channel heads, scores times
+ * score_scale: q [b,h,s,64], k / v [b,kvh,s,64] -> out [b*s, h*64] */
+int sat_attention_f32_window(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
+                             int32_t s, int32_t kernel_size, float score_scale, sat_stream_t stream);
 /* Self-attention of the text encoders: qkv [b * l, 3 * h * dkv] (q | k | v) -> out [b * l, h * dkv] = softmax(scale * q k^T + pb + mask) v;
  * pb [h, 2l - 1] indexed by key - query + l - 1, or NULL; keys with mask [b, l] == 0 get finfo(float32).min added (an all-padding row is the
  * uniform average over all l keys).  l <= 512, dkv % 4 == 0, (dkv + l) * 4 bytes of LDS <= 64 KiB. */
