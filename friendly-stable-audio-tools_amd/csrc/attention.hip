@@ -39,11 +39,6 @@ constexpr int ATT_LDS = 2 * GROUP_BYTES;                  // 64 KiB: two workgro
 
 using attn::half_max;
 using attn::half_sum;
-__device__ __forceinline__ void swap_halves(unsigned& lo_run, unsigned& hi_run) {
-    u32x2 r = __builtin_amdgcn_permlane32_swap(lo_run, hi_run, false, false);
-    lo_run = r[0];
-    hi_run = r[1];
-}
 
 // MX8: fp8_gemm mode -- the output is the A operand of the to_out GEMM and is written as MXFP8 (e4m3 bytes at `out`, one E8M0
 // scale per 32 channels = half a head at `out_scales` [B*Sq][H*2]) instead of bf16
@@ -156,7 +151,7 @@ __global__ __launch_bounds__(512, 2) void attention_kernel(const op_t* __restric
         const char* sv = sk + KV_TILE * 128;
         const bool edge = (tile == 0 && ob != 0) || (tile == n_tiles - 1 && (k_end & (KV_TILE - 1)) != 0);
         if constexpr (CAUSAL)
-            attn::tile<MODE, DBG, true>(st, qf, sk, sv, false, tile * KV_TILE, ob, attnc::key_end(qi, ob, Sk), tile == t_first, scale_log2, l31, half,
+            attn::tile<MODE, DBG, attn::MASK_CAUSAL>(st, qf, sk, sv, false, tile * KV_TILE, ob, attnc::key_end(qi, ob, Sk), tile == t_first, scale_log2, l31, half,
                                         __builtin_amdgcn_readfirstlane(bx * QB + wq * 32), Sk);
         else attn::tile<MODE, DBG>(st, qf, sk, sv, edge, tile * KV_TILE, ob, k_end, tile == t_first, scale_log2, l31, half);
     };
@@ -250,8 +245,8 @@ __global__ __launch_bounds__(512, 2) void attention_kernel(const op_t* __restric
                 unsigned p = __builtin_amdgcn_cvt_pk_fp8_f32(oacc[db][rq * 4] * qs, oacc[db][rq * 4 + 1] * qs, 0u, false);
                 q8[rq] = __builtin_amdgcn_cvt_pk_fp8_f32(oacc[db][rq * 4 + 2] * qs, oacc[db][rq * 4 + 3] * qs, p, true);
             }
-            swap_halves(q8[0], q8[1]);            // lanes 0-31: channels 0-7 | 16-23, lanes 32-63: 8-15 | 24-31
-            swap_halves(q8[2], q8[3]);
+            half_swap(q8[0], q8[1]);            // lanes 0-31: channels 0-7 | 16-23, lanes 32-63: 8-15 | 24-31
+            half_swap(q8[2], q8[3]);
             if (qi < Sq) {
                 unsigned char* op = reinterpret_cast<unsigned char*>(out) + ((size_t)b * Sq + qi) * ((size_t)H * 64) + h * 64 + db * 32 + 8 * half;
                 *reinterpret_cast<u32x2*>(op) = u32x2{q8[0], q8[1]};
@@ -274,10 +269,10 @@ __global__ __launch_bounds__(512, 2) void attention_kernel(const op_t* __restric
                 pk[2 * rq] = __builtin_bit_cast(unsigned, lo);
                 pk[2 * rq + 1] = __builtin_bit_cast(unsigned, hi);
             }
-            swap_halves(pk[0], pk[2]);            // 8 consecutive channels per lane: one 16-byte store instead of two 8-byte ones
-            swap_halves(pk[1], pk[3]);
-            swap_halves(pk[4], pk[6]);
-            swap_halves(pk[5], pk[7]);
+            half_swap(pk[0], pk[2]);            // 8 consecutive channels per lane: one 16-byte store instead of two 8-byte ones
+            half_swap(pk[1], pk[3]);
+            half_swap(pk[4], pk[6]);
+            half_swap(pk[5], pk[7]);
             if (qi < Sq) {
                 *reinterpret_cast<u32x4*>(op + db * 32) = u32x4{pk[0], pk[1], pk[2], pk[3]};
                 *reinterpret_cast<u32x4*>(op + db * 32 + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};
@@ -316,13 +311,7 @@ int SAT_OPNS::sat_launch_attention(const op_t* q, const op_t* k, const op_t* vt,
 #else
     SAT_CHECK_ARG(f16 && !out_scales, SAT_E_INVALID, "attention: the fp16 build takes fp16 tensors and writes fp16");
 #endif
-    SAT_CHECK_ARG(q && k && vt && out, SAT_E_INVALID, "attention: null pointer");
-    SAT_CHECK_ARG(b > 0 && h > 0 && kvh > 0 && h % kvh == 0, SAT_E_INVALID, "attention: bad heads %d/%d", h, kvh);
-    SAT_CHECK_ARG(sq > 0 && sk > 0 && sq_pad >= sq && sk_pad >= sk, SAT_E_INVALID, "attention: bad lengths");
-    SAT_CHECK_ARG(sq_pad % Q_BLOCK == 0 && sk_pad % KV_TILE == 0, SAT_E_INVALID,
-                  "attention: sq_pad %% 128 and sk_pad %% 64 must be 0 (got %d, %d)", sq_pad, sk_pad);
-    SAT_CHECK_ARG(sk_pad >= sk + 3, SAT_E_INVALID, "attention: sk_pad must be >= sk + 3 (key-side shift), got %d for sk=%d", sk_pad, sk);
-    SAT_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)out) & 15) == 0, SAT_E_INVALID, "attention: pointers must be 16-byte aligned");
+    SAT_CHECK_ATTENTION("attention", "sk", sq, sk, false, true);
     const float scale_log2 = q_scale;       // SAT_ATTN_QSCALE = 1/sqrt(64) * log2(e), or 1 for a pre-scaled Q
     dim3 grid(cdiv(sq, Q_BLOCK), h, b);
     // One KV group (256 queries per workgroup, every wave walks all the KV tiles of one shared ring: half the LDS-DMA and K / V^T traffic per
@@ -425,15 +414,7 @@ int SAT_OPNS::sat_launch_attention_causal(const op_t* q, const op_t* k, const op
 #else
     SAT_CHECK_ARG(f16, SAT_E_INVALID, "attention (causal): the fp16 build takes fp16 tensors and writes fp16");
 #endif
-    SAT_CHECK_ARG(q && k && vt && out, SAT_E_INVALID, "attention (causal): null pointer");
-    SAT_CHECK_ARG(b > 0 && h > 0 && kvh > 0 && h % kvh == 0, SAT_E_INVALID, "attention (causal): bad heads %d/%d", h, kvh);
-    SAT_CHECK_ARG(h <= 65535 && b <= 65535, SAT_E_UNSUPPORTED, "attention (causal): %d heads / %d sequences exceed the grid", h, b);
-    SAT_CHECK_ARG(s_len > 0 && sq_pad >= s_len && sk_pad >= s_len, SAT_E_INVALID, "attention (causal): bad lengths");
-    SAT_CHECK_ARG(sq_pad % Q_BLOCK == 0 && sk_pad % KV_TILE == 0, SAT_E_INVALID,
-                  "attention (causal): sq_pad %% 128 and sk_pad %% 64 must be 0 (got %d, %d)", sq_pad, sk_pad);
-    SAT_CHECK_ARG(sk_pad >= s_len + 3, SAT_E_INVALID, "attention (causal): sk_pad must be >= s + 3 (key-side shift), got %d for s=%d", sk_pad, s_len);
-    SAT_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)out) & 15) == 0, SAT_E_INVALID,
-                  "attention (causal): pointers must be 16-byte aligned");
+    SAT_CHECK_ATTENTION("attention (causal)", "s", s_len, s_len, true, true);
     const long wg1 = (long)cdiv(s_len, 256) * h * b;
     const bool one_group = wg1 >= 1024 || s_len <= 512 || (q_scale == 1.0f && wg1 >= 200 && s_len <= 2048);      // the rule of sat_launch_attention
     unsigned char* const no_scales = nullptr;

@@ -3,14 +3,13 @@
 // ranges), softmax in fp32, 64-channel heads.  The score scale is the launcher's argument: the reference hands q to natten1dqk unscaled.
 //
 // The 16-bit kernel is the one-group layout of attention.hip -- 8 waves = 256 queries of one (batch, head), K / V^T tiles of 64 keys copied by
-// LDS-DMA into a 3-stage ring shared by all waves, both products transposed, the per-wave step of attn_core.h -- with three differences:
+// LDS-DMA into a 3-stage ring shared by all waves (attn::walk3), both products transposed -- built from the pieces of attn_core.h: the
+// per-wave step attn::tile with MASK_WINDOW, the ring walk, the output store.  What is the kernel's own:
 //   * the workgroup copies and walks only the tiles [first_tile, last_tile] that hold the union of its queries' windows;
-//   * inside a tile every wave classes each 32-key block against the windows of ITS 32 queries: SKIP (no MFMA, no softmax; the wave still
-//     copies its pieces and joins every barrier), FULL (no compare) or EDGE (each lane masks the keys outside its own [k_lo, k_hi));
-//   * a wave's first visible block is not its first tile, and the lanes of a wave meet their first key in different blocks.  The standing
-//     reference starts at -1e30: a lane's first visible key gives p = exp2(s + 1e30) = inf, the row sum fails the overflow check and the
-//     block is redone with the true maximum; a lane that sees no key of a block has scores of -inf, p = exp2(-inf + 1e30) = 0, a maximum
-//     of fmax(-1e30, -inf) = -1e30 and a rescale by exp2(0) = 1, so (m, l, O) = (-1e30, 0, 0) survives until its window begins.
+//   * inside a tile the step classes each 32-key block against the windows of the WAVE's 32 queries: SKIP (no MFMA, no softmax; the wave
+//     still copies its pieces and joins every barrier), FULL (no compare) or EDGE (each lane masks the keys outside its own [k_lo, k_hi));
+//   * a wave's first visible block is not its first tile, and the lanes of a wave meet their first key in different blocks: attn_core.h
+//     says why the standing reference of -1e30 carries (m, l, O) = (-1e30, 0, 0) unharmed until a lane's window begins.
 // The fp32 kernel (the fp32 verification mode) is one query per lane as in f32_ref.hip, over the keys of the wave's union.
 #include "attn_core.h"
 #include "attn_window.h"
@@ -22,82 +21,6 @@ constexpr int KV_TILE = attn::KV_TILE;
 constexpr int QB = 256;                                   // queries per workgroup
 constexpr int STAGE_BYTES = 2 * KV_TILE * 128;            // K tile + V^T tile
 constexpr int WIN_LDS = 3 * STAGE_BYTES;                  // 48 KiB
-
-__device__ __forceinline__ void swap_halves(unsigned& lo_run, unsigned& hi_run) {
-    u32x2 r = __builtin_amdgcn_permlane32_swap(lo_run, hi_run, false, false);
-    lo_run = r[0];
-    hi_run = r[1];
-}
-
-// One tile of 64 keys for one wave: attn::tile's MODE 1 step with the block classes of attn_window.h.  wr: the wave's union / intersection;
-// [k_lo, k_hi): the lane's own window, in physical keys
-__device__ __forceinline__ void tile_window(attn::State<1>& st, const opx8 (&qf)[4], const char* sk, const char* sv, const int key_base,
-                                            const attnw::Range& wr, const int k_lo, const int k_hi, const float scale_log2, const int l31,
-                                            const int half) {
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        const int cls = attnw::block_class(key_base + kb * 32, wr);      // wave-uniform
-        if (cls == attnw::SKIP) continue;
-        // ---- S^T = K Q^T for 32 keys
-        opx8 kf[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) kf[t] = *reinterpret_cast<const opx8*>(sk + lds_tile_off(kb * 32 + l31, t * 2 + half));
-        f32x16 sacc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) sacc = mfma_32x32x16(kf[t], qf[t], sacc);
-        opx8 vf[2][2];
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) vf[db][u] = *reinterpret_cast<const opx8*>(sv + lds_tile_off(db * 32 + l31, (kb * 2 + u) * 2 + half));
-        // ---- mask the keys outside the lane's window (pads lie outside every window)
-        if (cls == attnw::EDGE) {
-            const int key0 = key_base + kb * 32 + 4 * half;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = key0 + (r & 3) + 8 * (r >> 2);
-                if (key < k_lo || key >= k_hi) sacc[r] = -INFINITY;
-            }
-        }
-        // ---- online softmax step against the standing reference; the row sum is the overflow check
-        opx8 pb[2];
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float p = __builtin_amdgcn_exp2f(fmaf(sacc[r], scale_log2, -st.m_run));
-            psum += p;
-            pb[r >> 3][r & 7] = f32_to_op(p);
-        }
-        if (!__all(psum <= 4096.0f)) {      // wave-uniform; NaN-safe (inf - inf cannot arise: m_run is finite)
-            float mloc = sacc[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, sacc[r]);
-            const float m_new = fmaxf(st.m_run, attn::half_max(mloc) * scale_log2);
-            const float alpha = __builtin_amdgcn_exp2f(st.m_run - m_new);
-            st.m_run = m_new;
-            st.l_run *= alpha;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) st.oacc[i][r] *= alpha;
-            psum = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(sacc[r], scale_log2, -st.m_run));
-                psum += p;
-                pb[r >> 3][r & 7] = f32_to_op(p);
-            }
-        }
-        st.l_run += psum;
-        // ---- O^T += V^T P^T
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) st.oacc[db] = mfma_32x32x16(vf[db][u], pb[u], st.oacc[db]);
-    }
-}
 
 // q [B,H,S_pad_q,64], k [B,KVH,Sk_pad,64] (rows shifted by ob), vt [B,KVH,64,Sk_pad] (vt_pos order) -> out [B*S, H*64]
 __global__ __launch_bounds__(512, 2) void attention_window_kernel(const op_t* __restrict__ q, const op_t* __restrict__ k, const op_t* __restrict__ vt,
@@ -158,48 +81,14 @@ __global__ __launch_bounds__(512, 2) void attention_window_kernel(const op_t* __
     const attnw::Range wr = attnw::wave_range(wave_active ? wq_first : S - 1, 32, ob, KS, S);
     const int k_lo = attnw::key_lo(qi, ob, KS, S), k_hi = k_lo + KS;
 
-    // three stages, prefetch distance 2 (the NGRP == 1 walk of attention.hip)
-    stage_in(t_first, 0);
-    if (t_count > 1) stage_in(t_first + 1, 1);
-    int stg = 0;
-    for (int it = 0; it < t_count; ++it) {
-        if (it + 1 < t_count) wait_vmcnt<2>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        const int stg2 = stg >= 1 ? stg - 1 : 2;                 // (it + 2) % 3
-        if (it + 2 < t_count) stage_in(t_first + it + 2, stg2);
-        if (wave_active) {
-            const char* sk = smem + stg * STAGE_BYTES;
-            tile_window(st, qf, sk, sk + KV_TILE * 128, (t_first + it) * KV_TILE, wr, k_lo, k_hi, scale_log2, l31, half);
-        }
-        stg = stg == 2 ? 0 : stg + 1;
-    }
+    attn::walk3<2>(t_first, t_count, stage_in, [&](int tile, int stage) {
+        if (!wave_active) return;
+        const char* sk = smem + stage * STAGE_BYTES;
+        attn::tile<1, 0, attn::MASK_WINDOW>(st, qf, sk, sk + KV_TILE * 128, false, tile * KV_TILE, k_lo, k_hi, false, scale_log2, l31, half, 0, 0, wr);
+    });
 
-    const float inv = 1.0f / attn::half_sum(st.l_run);
-    // O^T registers of a lane: channels d = db*32 + 8*(r>>2) + 4*half + (r&3) of ITS query
     op_t* op = out + ((size_t)b * S + qi) * ((size_t)H * 64) + h * 64 + 8 * half;
-#pragma unroll
-    for (int db = 0; db < 2; ++db) {
-        unsigned pk[8];
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-            opx2 lo, hi;
-            lo[0] = f32_to_op(st.oacc[db][rq * 4] * inv);
-            lo[1] = f32_to_op(st.oacc[db][rq * 4 + 1] * inv);
-            hi[0] = f32_to_op(st.oacc[db][rq * 4 + 2] * inv);
-            hi[1] = f32_to_op(st.oacc[db][rq * 4 + 3] * inv);
-            pk[2 * rq] = __builtin_bit_cast(unsigned, lo);
-            pk[2 * rq + 1] = __builtin_bit_cast(unsigned, hi);
-        }
-        swap_halves(pk[0], pk[2]);            // 8 consecutive channels per lane: one 16-byte store instead of two 8-byte ones
-        swap_halves(pk[1], pk[3]);
-        swap_halves(pk[4], pk[6]);
-        swap_halves(pk[5], pk[7]);
-        if (qi < S) {
-            *reinterpret_cast<u32x4*>(op + db * 32) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-            *reinterpret_cast<u32x4*>(op + db * 32 + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};
-        }
-    }
+    attn::store_out(st.oacc, 1.0f / attn::half_sum(st.l_run), op, qi < S);
 }
 
 #ifndef SAT_OPERAND_F16
@@ -295,15 +184,7 @@ int SAT_OPNS::sat_launch_attention_window(const op_t* q, const op_t* k, const op
 #else
     SAT_CHECK_ARG(f16, SAT_E_INVALID, "attention (window): the fp16 build takes fp16 tensors and writes fp16");
 #endif
-    SAT_CHECK_ARG(q && k && vt && out, SAT_E_INVALID, "attention (window): null pointer");
-    SAT_CHECK_ARG(b > 0 && h > 0 && kvh > 0 && h % kvh == 0, SAT_E_INVALID, "attention (window): bad heads %d/%d", h, kvh);
-    SAT_CHECK_ARG(h <= 65535 && b <= 65535, SAT_E_UNSUPPORTED, "attention (window): %d heads / %d sequences exceed the grid", h, b);
-    SAT_CHECK_ARG(s_len > 0 && sq_pad >= s_len && sk_pad >= s_len, SAT_E_INVALID, "attention (window): bad lengths");
-    SAT_CHECK_ARG(sq_pad % 128 == 0 && sk_pad % KV_TILE == 0, SAT_E_INVALID,
-                  "attention (window): sq_pad %% 128 and sk_pad %% 64 must be 0 (got %d, %d)", sq_pad, sk_pad);
-    SAT_CHECK_ARG(sk_pad >= s_len + 3, SAT_E_INVALID, "attention (window): sk_pad must be >= s + 3 (key-side shift), got %d for s=%d", sk_pad, s_len);
-    SAT_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)out) & 15) == 0, SAT_E_INVALID,
-                  "attention (window): pointers must be 16-byte aligned");
+    SAT_CHECK_ATTENTION("attention (window)", "s", s_len, s_len, true, true);
     SAT_CHECK_WINDOW("attention (window)", kernel_size, s_len);
     SAT_CHECK_ARG(score_scale > 0.f && score_scale <= 1e6f, SAT_E_INVALID, "attention (window): score scale %g is not a positive finite number",
                   (double)score_scale);

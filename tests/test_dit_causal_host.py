@@ -204,7 +204,7 @@ def test_causal_ranges_agree_with_brute_force(tmp_path):
 
 def test_every_kernel_takes_its_ranges_from_the_header():
     for src, calls in (("attention.hip", ("attnc::tiles_walked", "attnc::key_end")), ("attn_core.h", ("attnc::block_class",)),
-                       ("attention_hdw_kernel.inc", ("attnc::tiles_walked", "attnc::block_class", "attnc::key_end")),
+                       ("attention_hdw.hip", ("attnc::tiles_walked", "attnc::key_end")),          # (its blocks are classed by attn_core.h's step)
                        ("f32_ref.hip", ("attnc::tiles_walked",))):
         text = open(os.path.join(CSRC, src)).read()
         for c in calls:
@@ -235,7 +235,7 @@ def test_causal_kernels_keep_their_register_budgets(defines, tmp_path):
         assert "ELi1ELb1EE" in n, n                # MODE 1
         assert m["vgpr_count"] <= 128 and m["vgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (n, m)
     meta = _kernels("attention_hdw.hip", defines, str(tmp_path))
-    twins = {n: m for n, m in meta.items() if "attention_hdw_causal_kernelILi" in n}
+    twins = {n: m for n, m in meta.items() if "attention_hdw_kernelILi" in n and "ELb1EE" in n}
     assert len(twins) == 3, sorted(meta)
     for n, m in twins.items():
         budget = 128 if "kernelILi32E" in n else 256

@@ -269,8 +269,9 @@ def test_window_ranges_agree_with_brute_force(tmp_path):
 
 def test_the_kernels_take_their_ranges_from_the_header():
     text = open(os.path.join(CSRC, "attention_window.hip")).read()
-    for c in ("attnw::first_tile", "attnw::last_tile", "attnw::wave_range", "attnw::block_class", "attnw::key_lo", "attnw::union_lo", "attnw::union_hi"):
+    for c in ("attnw::first_tile", "attnw::last_tile", "attnw::wave_range", "attnw::key_lo", "attnw::union_lo", "attnw::union_hi"):
         assert c in text, c
+    assert "attn::MASK_WINDOW" in text and "attnw::block_class" in open(os.path.join(CSRC, "attn_core.h")).read()      # the shared step classes the blocks
 
 
 # ------------------------------------------------------------------------------- the kernels, compiled and inspected

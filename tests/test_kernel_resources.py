@@ -63,6 +63,21 @@ def test_one_prompt_gemm_tiles_keep_their_occupancy(defines, tmp_path):
     assert next(iter(kgroup.values()))["vgpr_count"] <= 256
 
 
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.parametrize("defines", [[], ["-DSAT_OPERAND_F16"]], ids=["bf16", "f16"])
+def test_ring_attention_kernels_keep_their_workgroups_per_cu(defines, tmp_path):
+    """The kernels built from attn_core.h's step outside attention.hip: the six head-width kernels (32, 96, 128 channels, each with and
+    without the causal mask) and the neighbourhood kernel, none with scratch or spills.  32-channel heads and the neighbourhood kernel
+    (declared __launch_bounds__(512, 2)) have 48-KiB rings sized for two workgroups per CU, which 512 threads reach at 128 VGPRs or fewer."""
+    hdw = {k: v for k, v in _kernels("attention_hdw.hip", defines, str(tmp_path)).items() if "attention_hdw_kernelILi" in k}
+    assert len(hdw) == 6 and len([k for k in hdw if "kernelILi32E" in k]) == 2, sorted(hdw)
+    win = {k: v for k, v in _kernels("attention_window.hip", defines, str(tmp_path)).items() if "attention_window_kernel" in k}
+    assert len(win) == 1, sorted(win)
+    for name, m in {**hdw, **win}.items():
+        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, f"{name}: {m}"
+        assert m["vgpr_count"] <= (128 if "kernelILi32E" in name or name in win else 256), f"{name}: {m}"
+
+
 def _regs(tok):
     """VGPR numbers named by one operand token: v12 -> {12}, v[4:7] -> {4..7}"""
     out = set()

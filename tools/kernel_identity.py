@@ -2,7 +2,8 @@
 operand build) and compares kernel by kernel: the instruction stream with symbol names replaced by their demangled, namespace-free form, and
 the resource metadata.  A plain diff of two compilations; developer tool, no GPU.
 
-usage: python tools/kernel_identity.py <parent tree's csrc> [file.hip]      (default oobleck.hip; exit code 1 when a kernel differs)"""
+usage: python tools/kernel_identity.py [--rename old=new]... <parent tree's csrc> [file.hip]      (default oobleck.hip; exit code 1 when a
+kernel differs; --rename: the parent's kernel `old`, named as the table prints it, is compared with the branch's kernel `new`)"""
 import os
 import re
 import subprocess
@@ -29,14 +30,15 @@ def plain(names):
     return res
 
 
-def kernels(csrc, src, defs, workdir):
+def kernels(csrc, src, defs, workdir, rename={}):
     """{kernel: (instruction lines, {metadata})} of one compilation"""
     out = os.path.join(workdir, "k.s")
     cmd = [HIPCC, *FLAGS, *defs, os.path.join(csrc, src), "-o", out]
     subprocess.run(cmd, check=True, capture_output=True)
     text = open(out).read()
-    names = plain(sorted(set(re.findall(r"\b_Z\w+", text))))
-    sub = lambda s: re.sub(r"\b_Z\w+", lambda m: names[m.group(0)], s)
+    names = {m: rename.get(d, d) for m, d in plain(sorted(set(re.findall(r"\b_Z\w+", text)))).items()}
+    # (basic-block labels carry the function's position in the file, which a renamed kernel need not keep)
+    sub = lambda s: re.sub(r"\bL?BB\d+_", "BB_", re.sub(r"\b_Z\w+", lambda m: names[m.group(0)], s))
     meta = {}
     for blk in text.split("  - .agpr_count:")[1:]:
         blk = ".agpr_count:" + blk
@@ -51,11 +53,16 @@ def kernels(csrc, src, defs, workdir):
 
 
 def main():
-    parent, src = sys.argv[1], sys.argv[2] if len(sys.argv) > 2 else "oobleck.hip"
+    argv, rename = sys.argv[1:], {}
+    while argv and argv[0] == "--rename":
+        old, new = argv[1].split("=", 1)
+        rename[old] = new
+        argv = argv[2:]
+    parent, src = argv[0], argv[1] if len(argv) > 1 else "oobleck.hip"
     bad = 0
     for build, defs in BUILDS.items():
         with tempfile.TemporaryDirectory() as d:
-            (old, cmd), (new, _) = kernels(parent, src, defs, d), kernels(CSRC, src, defs, d)
+            (old, cmd), (new, _) = kernels(parent, src, defs, d, rename), kernels(CSRC, src, defs, d)
         print(f"== {build}: {cmd}")
         print(f"{'kernel':44s} {'instr':>6s} " + " ".join(f"{k.replace('_segment', '').replace('_fixed_size', '').replace('_count', ''):>10s}" for k in META) + "  stream  metadata")
         same = sorted(old) == sorted(new)
