@@ -18,11 +18,15 @@
 // (and the raw tensor only where a residual needs it).  Weight norm (dac WNConv1d) is
 // folded once at plan finalize.  ELU (use_snake=False) takes Snake's place in the same epilogues, and the decoder's final tanh sits in
 // the epilogue of its last convolution; both are wave-uniform run-time fields of ConvArgs, not further kernel instantiations.
+// The one activation that is a pass of its own is the anti-aliased one (antialias_activation=True, aa_act_kernel below): it reads 11 rows
+// per output row, so the convolution in front writes its un-activated result in fp32 (ConvArgs::out_cf with cf_channels == 0) instead.
 // Stage widths that are not multiples of 64 are rounded up inside the plan: weights, biases and Snake parameters are zero-padded at
 // finalize, so the pad channels of every activation tensor are written as exact zeros (act(0) = 0) and no kernel masks channels.
 // This file holds what depends on the operand type: the kernels and the launchers that own grid, LDS size and tile choice.  It is built
 // once per format (bf16, fp16, fp32) and exports SAT_OPNS::oob_kernels (oobleck_kernels.h) to the plan, oobleck_plan.hip, which is built once.
 #include <math.h>
+
+#include <type_traits>
 
 #include "oobleck_kernels.h"      // ConvArgs, RuArgs (namespace SAT_OPNS, opened by sat_common.h), OobKernels
 
@@ -78,7 +82,7 @@ __device__ __forceinline__ void store_op8(op_t* p, const float (&x)[8]) {
 template <int MI, int ACT>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& g, f32x16 (&acc)[MI][2], const int mw, const int nw, const int b,
                                               const int half, const int l31) {
-    if (g.out_cf) {      // fp32 channel-first result of the last convolution: consecutive lanes = consecutive time steps
+    if (g.out_cf && g.cf_channels) {      // fp32 channel-first result of the last convolution: consecutive lanes = consecutive time steps
         float* __restrict__ o = g.out_cf + (size_t)b * g.cf_channels * g.M;
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
@@ -99,6 +103,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& g, f32x16 (&acc)[M
     const op_t* res = g.res ? g.res + (size_t)b * g.out_bstride : nullptr;
     op_t* oraw = g.out_raw ? g.out_raw + (size_t)b * g.out_bstride : nullptr;
     op_t* __restrict__ osnk = g.out_snk ? g.out_snk + (size_t)b * g.out_bstride : nullptr;
+    // out_cf without cf_channels: the un-activated result once more, in fp32 and indexed as out_raw, for the anti-aliased activation
+    // behind this convolution (aa_act_kernel), which would otherwise read it rounded to the operand format
+    float* __restrict__ of32 = g.out_cf ? g.out_cf + (size_t)b * g.out_bstride : nullptr;
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
         const int m = mw + i * 32 + l31;
@@ -129,6 +136,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& g, f32x16 (&acc)[M
                     for (int e = 0; e < 8; ++e) x[e] += op_to_f32(rv[e]);
                 }
                 if (oraw && ok) store_op8(oraw + flat, x);
+                if (of32 && ok) {
+                    *reinterpret_cast<f32x4*>(of32 + flat) = f32x4{x[0], x[1], x[2], x[3]};
+                    *reinterpret_cast<f32x4*>(of32 + flat + 4) = f32x4{x[4], x[5], x[6], x[7]};
+                }
                 if (osnk) {
                     float y[8];
                     if (ACT == ACT_RUNTIME ? g.act == ACT_ELU : ACT == ACT_ELU) {
@@ -512,6 +523,131 @@ __global__ __launch_bounds__(256) void first_conv_kernel(const float* __restrict
     }
 }
 
+// ---- the anti-aliased activation (antialias_activation=True: alias_free_torch.Activation1d around SnakeBeta / ELU, autoencoders.py:39-40)
+// Per channel along time, with f the 12-tap Kaiser-windowed sinc (cutoff 0.25, half-width 0.3, sum 1; symmetric, f[j] == f[11 - j]):
+//     u[m] = 2 sum_i xp[i] f[m + 15 - 2 i],  xp[i] = x[clamp(i - 5, 0, L - 1)]      (replicate pad 5, transposed convolution stride 2, cut 15)
+//     v[m] = act(u[m]),  m = 0 .. 2 L - 1
+//     y[t] = sum_j f[j] v[clamp(2 t + j - 5, 0, 2 L - 1)]                            (replicate pad 5 / 6 of the ACTIVATED signal, stride 2)
+// so u[2 k] reads rows k - 3 .. k + 2 on the odd taps, u[2 k + 1] rows k - 2 .. k + 3 on the even ones, and y[t] the pairs t - 3 .. t + 3.
+// One thread owns 16 bytes of channels and walks AA_TIME_TILE output rows in registers: a window of 7 input rows and 7 partial sums.  Step k
+// computes the pair v[2 k], v[2 k + 1] once and scatters it into the sums of y[k - 3 .. k + 3]; y[k - 3] is then complete.  The clamp of the
+// activated signal only ever repeats v[0] and v[2 L - 1]: their weights in y[t] are prefix / suffix sums of f, added at k == 0 / k == L - 1
+// on top of the plain tap (for L < 6 both happen to the same sums).  Every row is read once per tile (plus the halo of 6 steps, from L2),
+// every v computed once per tile; no LDS.  Reads stay inside [0, L) of the batch item by the clamps, writes inside the tile's rows.
+constexpr int AA_CH = CH_EL;      // channels per thread: 8 (16-bit builds) or 4 (fp32)
+typedef float aa_f2 __attribute__((ext_vector_type(2)));
+typedef op_t aa_opv __attribute__((ext_vector_type(AA_CH)));
+typedef float aa_f32v __attribute__((ext_vector_type(AA_CH)));
+__host__ __device__ constexpr float aa_tap(int j) {
+    constexpr float h[6] = {0.0020289664498962f, 0.0093894639440679f, -0.0255434640652947f, -0.0576573754753650f, 0.1285726090813288f, 0.4432098000653667f};
+    return h[j < 6 ? j : 11 - j];
+}
+__host__ __device__ constexpr float aa_prefix(int n) {      // f[0] + ... + f[n]; by symmetry also f[11 - n] + ... + f[11]
+    float s = 0.f;
+    for (int j = 0; j <= n; ++j) s += aa_tap(j);
+    return s;
+}
+__device__ __forceinline__ aa_f2 aa_activate(aa_f2 u, bool elu, aa_f2 a, aa_f2 ib) {
+    if (elu) return aa_f2{elu_f(u[0]), elu_f(u[1])};
+    return aa_f2{snake_f(u[0], a[0], ib[0]), snake_f(u[1], a[1], ib[1])};
+}
+template <typename V>
+__device__ __forceinline__ void aa_unpack(const V r, aa_f2 (&x)[AA_CH / 2]) {
+#pragma unroll
+    for (int e = 0; e < AA_CH / 2; ++e) x[e] = aa_f2{(float)r[2 * e], (float)r[2 * e + 1]};
+}
+// IN_F32: the input rows are fp32 whatever the build -- what the plan's convolutions leave for this kernel (ConvArgs::out_cf without
+// cf_channels), so that the un-activated tensor is not rounded to a 16-bit format on its way here; otherwise rows of the operand type
+// ELU: the activation, a template parameter here -- as a run-time field the compiler evaluates Snake and ELU for every element and selects
+template <bool IN_F32, bool ELU>
+__global__ __launch_bounds__(256) void aa_act_kernel(const void* __restrict__ in_rows, op_t* __restrict__ out, const float* __restrict__ sn_a,
+                                                     const float* __restrict__ sn_ib, int Cp, int L, int ntile, long long nwork) {
+    using in_t = typename std::conditional<IN_F32, float, op_t>::type;
+    using in_v = typename std::conditional<IN_F32, aa_f32v, aa_opv>::type;
+    const in_t* __restrict__ in = static_cast<const in_t*>(in_rows);
+    sat_f16_saturate();
+    constexpr int TT = AA_TIME_TILE, P = AA_CH / 2;
+    const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= nwork) return;
+    const int G = Cp / AA_CH;
+    const int cg = (int)(id % G);
+    const long long tile = id / G;
+    const int b = (int)(tile / ntile), t0 = (int)(tile % ntile) * TT, tend = min(t0 + TT, L);
+    const in_t* __restrict__ x = in + (size_t)b * L * Cp + cg * AA_CH;
+    op_t* __restrict__ y = out + (size_t)b * L * Cp + cg * AA_CH;
+    constexpr bool elu = ELU;
+    aa_f2 a[P], ib[P];
+#pragma unroll
+    for (int e = 0; e < P; ++e) {
+        a[e] = elu ? aa_f2{0.f, 0.f} : *reinterpret_cast<const aa_f2*>(sn_a + cg * AA_CH + 2 * e);
+        ib[e] = elu ? aa_f2{0.f, 0.f} : *reinterpret_cast<const aa_f2*>(sn_ib + cg * AA_CH + 2 * e);
+    }
+    auto row = [&](int r) { return *reinterpret_cast<const in_v*>(x + (size_t)min(max(r, 0), L - 1) * Cp); };
+    // xw[d] = x[clamp(k - 3 + d)], acc[d] = the partial sum of y[k - 3 + d]; q0 / q1: rows k + 4, k + 5 on their way
+    aa_f2 xw[7][P], acc[7][P];
+#pragma unroll
+    for (int d = 0; d < 7; ++d) {
+        aa_unpack(row(t0 - 6 + d), xw[d]);
+#pragma unroll
+        for (int e = 0; e < P; ++e) acc[d][e] = aa_f2{0.f, 0.f};
+    }
+    in_v q0 = row(t0 + 1), q1 = row(t0 + 2);
+    auto step = [&](const int k, in_v& q) {
+        if (k >= 0 && k < L) {
+#pragma unroll
+            for (int e = 0; e < P; ++e) {
+                aa_f2 ue = aa_tap(11) * xw[0][e], uo = aa_tap(10) * xw[1][e];
+#pragma unroll
+                for (int d = 1; d < 6; ++d) {
+                    ue += aa_tap(11 - 2 * d) * xw[d][e];
+                    uo += aa_tap(10 - 2 * d) * xw[d + 1][e];
+                }
+                const aa_f2 ve = aa_activate(2.f * ue, elu, a[e], ib[e]), vo = aa_activate(2.f * uo, elu, a[e], ib[e]);
+#pragma unroll
+                for (int d = 0; d < 6; ++d) {
+                    acc[d][e] += aa_tap(11 - 2 * d) * ve;          // v[2 k] in y[k - 3 + d]: tap 2 k + 5 - 2 t
+                    acc[d + 1][e] += aa_tap(10 - 2 * d) * vo;      // v[2 k + 1] in y[k - 2 + d]
+                }
+                if (k == 0) {          // v[0] also stands for v[-5 .. -1]: y[t] takes it on the taps 0 .. 5 - 2 t
+#pragma unroll
+                    for (int d = 3; d < 6; ++d) acc[d][e] += (aa_prefix(11 - 2 * d) - aa_tap(11 - 2 * d)) * ve;
+                }
+                if (k == L - 1) {      // v[2 L - 1] also stands for v[2 L .. 2 L + 5]: y[L - 3 + d] takes it on the taps 10 - 2 d .. 11
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) acc[d + 1][e] += (aa_prefix(1 + 2 * d) - aa_tap(10 - 2 * d)) * vo;
+                }
+            }
+        }
+        const int t = k - 3;
+        if (t >= t0 && t < tend) {
+            aa_opv o;
+#pragma unroll
+            for (int e = 0; e < P; ++e) {
+                o[2 * e] = f32_to_op(acc[0][e][0]);
+                o[2 * e + 1] = f32_to_op(acc[0][e][1]);
+            }
+            *reinterpret_cast<aa_opv*>(y + (size_t)t * Cp) = o;
+        }
+#pragma unroll
+        for (int d = 0; d < 6; ++d)
+#pragma unroll
+            for (int e = 0; e < P; ++e) {
+                xw[d][e] = xw[d + 1][e];
+                acc[d][e] = acc[d + 1][e];
+            }
+        aa_unpack(q, xw[6]);
+#pragma unroll
+        for (int e = 0; e < P; ++e) acc[6][e] = aa_f2{0.f, 0.f};
+        q = row(k + 6);      // consumed two steps on, as row (k + 2) + 4
+    };
+    static_assert((TT + 6) % 2 == 0, "the walk below takes its steps in pairs");
+#pragma unroll 1
+    for (int k = t0 - 3; k < t0 + TT + 3; k += 2) {
+        step(k, q0);
+        step(k + 1, q1);
+    }
+}
+
 // ---- weight-norm folding (dac WNConv1d == torch weight_norm dim 0): w = g * v / ||v||
 __global__ __launch_bounds__(256) void wn_invnorm_kernel(const float* __restrict__ v, const float* __restrict__ gsc,
                                                          float* __restrict__ scale, int slice) {
@@ -638,6 +774,21 @@ int launch_first_conv(const float* audio, const float* w_f32, const float* bias,
     return 0;
 }
 
+// the anti-aliased activation: one thread per 16 bytes of channels and AA_TIME_TILE output rows
+int launch_aa_act(const void* in, int in_f32, void* out, const float* sn_a, const float* sn_ib, int act, int Cp, int L, int B, hipStream_t s) {
+    SAT_CHECK_ARG(in && out && in != out, SAT_E_INVALID, "aa_act: needs an input and an output of its own (an output row reads 11 input rows)");
+    SAT_CHECK_ARG(Cp > 0 && Cp % 64 == 0 && L > 0 && B > 0, SAT_E_INVALID, "aa_act: bad shape [%d][%d][%d]", B, L, Cp);
+    SAT_CHECK_ARG(act == ACT_ELU || (act == ACT_SNAKE && sn_a && sn_ib), SAT_E_INVALID, "aa_act: Snake parameters missing or unknown activation %d", act);
+    const int ntile = cdiv(L, AA_TIME_TILE);
+    const long long nwork = (long long)B * ntile * (Cp / AA_CH);
+    SAT_CHECK_ARG(nwork / 256 < 0x7fffffffLL, SAT_E_UNSUPPORTED, "aa_act: [%d][%d][%d] is more than one grid", B, L, Cp);
+    const bool elu = act == ACT_ELU;
+    auto kern = in_f32 ? (elu ? aa_act_kernel<true, true> : aa_act_kernel<true, false>) : (elu ? aa_act_kernel<false, true> : aa_act_kernel<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((nwork + 255) / 256)), dim3(256), 0, s, in, (op_t*)out, sn_a, sn_ib, Cp, L, ntile, nwork);
+    SAT_LAUNCH_CHECK();
+    return 0;
+}
+
 #if !SAT_OP_IS_F32
 template <int BN, int WM, int WN, int NS>
 int launch_ru_fused(const RuArgs& a, int B, hipStream_t s) {
@@ -713,6 +864,7 @@ const OobKernels* oob_kernels() {
         launch_pack_convT,
         launch_pack_nearest,
         launch_snake_params,
+        launch_aa_act,
     };
     return &k;
 }

@@ -29,8 +29,8 @@ struct ConvArgs {
     long long out_bstride;   // elements per batch item
     long long out_shift;     // flat = m*N + out_shift + n ; valid if 0 <= flat < out_limit
     long long out_limit;
-    float* out_cf;           // channel-first fp32 output [B][cf_channels][M] (final convs) or null
-    int cf_channels;
+    float* out_cf;           // channel-first fp32 output [B][cf_channels][M] (final convs) or null; with cf_channels == 0: the un-activated
+    int cf_channels;         // result in fp32, channels-last and indexed as out_raw (the input of an anti-aliased activation)
     const op_t* zero_page; // >= one K-tile row (ROW_B <= 256 B) of zeros: LDS-DMA source of the rows that fall into the conv padding
     // (the option fields come last: the fields above keep the offsets they had before the options existed)
     int act;                 // activation behind out_snk: ACT_SNAKE (sn_a / sn_ib) or ACT_ELU (no parameters)
@@ -67,7 +67,12 @@ struct OobKernels {
     int (*pack_convT)(const float* v, const float* g, float* scale, void* W, int Cin, int Cout, int stride, int Kp, int Np, hipStream_t s);
     int (*pack_nearest)(const float* v, const float* g, float* scale, void* W, int Cin, int Cout, int stride, int Kp, int Np, hipStream_t s);
     int (*snake_params)(const float* alpha, const float* beta, float* a, float* ib, int C, int Cp, hipStream_t s);
+    // the anti-aliased activation (alias_free_torch.Activation1d, sat_oobleck_plan_set_antialias): in [B][L][Cp] un-activated rows -> out, the
+    // same shape, never in place (an output row reads 11 input rows); sn_a / sn_ib [Cp] as the convolution epilogues take them, null under ELU.
+    // in_f32: the input rows are fp32 in every build (what a convolution writes through ConvArgs::out_cf with cf_channels == 0)
+    int (*aa_act)(const void* in, int in_f32, void* out, const float* sn_a, const float* sn_ib, int act, int Cp, int L, int B, hipStream_t s);
 };
+enum { AA_TIME_TILE = SAT_OOBLECK_AA_TIME_TILE };      // output rows per thread of that kernel
 namespace bf16 { const OobKernels* oob_kernels(); }
 namespace f16 { const OobKernels* oob_kernels(); }
 namespace f32 { const OobKernels* oob_kernels(); }

@@ -32,6 +32,7 @@ const OobKernels* kernels_of(int gemm_dtype) {
 struct Snake {
     float *a = nullptr, *ib = nullptr;
     int act = ACT_SNAKE;
+    bool aa = false;      // wrapped in Activation1d: a launch of its own (OobKernels::aa_act) behind the convolution, not that convolution's epilogue
 };
 struct ConvW {
     void* W = nullptr;
@@ -46,6 +47,7 @@ struct sat_oobleck_plan {
     const OobKernels* k = nullptr;      // the build of cfg.gemm_dtype
     sat_oobleck_cfg cfg;
     sat_oobleck_options opt;
+    bool antialias = false;      // sat_oobleck_plan_set_antialias: the reference's antialias_activation=True
     TensorTable tensors;
     bool finalized = false;
     DevBuf arena;
@@ -75,8 +77,12 @@ namespace {
 
 int get_tensor(OobPlan* p, const std::string& name, int64_t numel, const float** out) { return p->tensors.get("oobleck", name, numel, out); }
 
-int make_snake(OobPlan* p, Bump& ar, const std::string& pfx, int C, Snake* sn, hipStream_t s) {
+// aa: one of the activations the reference builds with antialias=antialias_activation (get_activation, autoencoders.py:39-40).  Activation1d
+// holds the activation as ".act"; its filter buffers are constants of the kernel and no plan tensors
+int make_snake(OobPlan* p, Bump& ar, std::string pfx, int C, Snake* sn, hipStream_t s, bool aa = false) {
     sn->act = p->opt.activation;
+    sn->aa = aa && p->antialias;
+    if (sn->aa) pfx += "act.";
     if (sn->act == ACT_ELU) return 0;        // nn.ELU has no tensors: nothing to ask for
     const int Cp = pad64(C);
     sn->a = (float*)ar.take((size_t)Cp * 4);
@@ -176,14 +182,14 @@ int build(OobPlan* p, Bump& ar, hipStream_t s) {
             blk.cout = pad64(cout);
             blk.stride = c.strides[i - 1];
             const std::string pf = "layers." + std::to_string(bi + 1) + ".";
-            SAT_TRY(make_snake(p, ar, pf + "layers.0.", cin, &blk.sn_in, s));
+            SAT_TRY(make_snake(p, ar, pf + "layers.0.", cin, &blk.sn_in, s, true));
             if (p->opt.nearest_upsample)      // Sequential(Upsample, WNConv1d): the convolution is layers.1.1
                 SAT_TRY(make_nearest(p, ar, pf + "layers.1.1.", cin, cout, blk.stride, &blk.resample, s));
             else
                 SAT_TRY(make_convT(p, ar, pf + "layers.1.", cin, cout, blk.stride, &blk.resample, s));
             for (int r = 0; r < 3; ++r) SAT_TRY(make_ru(p, ar, pf + "layers." + std::to_string(2 + r) + ".", cout, blk, r, s));
         }
-        SAT_TRY(make_snake(p, ar, "layers." + std::to_string(nb + 1) + ".", c.channels, &p->final_snake, s));
+        SAT_TRY(make_snake(p, ar, "layers." + std::to_string(nb + 1) + ".", c.channels, &p->final_snake, s, true));
         SAT_TRY(make_conv(p, ar, "layers." + std::to_string(nb + 2) + ".", c.channels, c.io_channels, 7, false, &p->last, s));
     } else {
         // autoencoders.py:131-151
@@ -201,7 +207,9 @@ int build(OobPlan* p, Bump& ar, hipStream_t s) {
             SAT_TRY(make_conv(p, ar, pf + "layers.4.", cin, cout, 2 * blk.stride, true, &blk.resample, s));
         }
         const int ctop = c.c_mults[nb - 1] * c.channels;
-        SAT_TRY(make_snake(p, ar, "layers." + std::to_string(nb + 1) + ".", ctop, &p->final_snake, s));
+        // (the reference's OobleckEncoder hands antialias_activation to this activation alone, autoencoders.py:139-148: its blocks are
+        // built without it)
+        SAT_TRY(make_snake(p, ar, "layers." + std::to_string(nb + 1) + ".", ctop, &p->final_snake, s, true));
         SAT_TRY(make_conv(p, ar, "layers." + std::to_string(nb + 2) + ".", ctop, c.latent_dim, 3, true, &p->last, s));
     }
     return 0;
@@ -209,17 +217,20 @@ int build(OobPlan* p, Bump& ar, hipStream_t s) {
 
 struct Bufs {
     void *R, *S0, *S1, *Y;
+    float* F;      // anti-aliased plans only: the fp32 un-activated tensor between a convolution and the activation's own kernel
     size_t total;
 };
 Bufs carve(const OobPlan* p, int B, int T, char* base) {
     // largest channels-last tensor of the network (padded widths), in elements per batch item
     const sat_oobleck_cfg& c = p->cfg;
-    size_t len = (size_t)T, mx = 0;
+    size_t len = (size_t)T, mx = 0, aa = 0;      // aa: the largest tensor in front of an anti-aliased activation
     if (c.is_decoder) {
         mx = std::max((size_t)T * pad64(c.latent_dim), (size_t)T * p->blocks[0].cin);
+        aa = (size_t)T * p->blocks[0].cin;
         for (auto& b : p->blocks) {
             len *= b.stride;
             mx = std::max(mx, len * b.cout);
+            aa = std::max(aa, len * b.cout);
         }
     } else {
         len = (size_t)T * p->ratio;
@@ -229,6 +240,7 @@ Bufs carve(const OobPlan* p, int B, int T, char* base) {
             len /= b.stride;
             mx = std::max(mx, len * b.cout);
         }
+        aa = len * p->blocks.back().cout;
     }
     size_t per = (size_t)round_up((int64_t)(mx * B * p->k->elem_bytes), 256);
     Bufs o;
@@ -237,6 +249,11 @@ Bufs carve(const OobPlan* p, int B, int T, char* base) {
     o.S1 = base ? base + 2 * per : nullptr;
     o.Y = base ? base + 3 * per : nullptr;
     o.total = 4 * per;
+    o.F = nullptr;
+    if (p->antialias) {      // the workspace grows only with the option on
+        o.F = base ? (float*)(base + o.total) : nullptr;
+        o.total += (size_t)round_up((int64_t)(aa * B * sizeof(float)), 256);
+    }
     return o;
 }
 
@@ -252,6 +269,16 @@ ConvArgs base_args(const ConvW& w, const void* in, int Tin, int M) {
 // out = the activated copy of the result, for the consumer whose activation is sn
 void set_act(ConvArgs& a, void* out, const Snake& sn) {
     a.out_snk = opq(out); a.act = sn.act; a.sn_a = sn.a; a.sn_ib = sn.ib;
+}
+// The same where sn may be an anti-aliased activation: the convolution then writes its un-activated result in fp32 to `raw32` (Bufs::F: in
+// the 16-bit builds the tensor would otherwise be rounded once more than in the fused epilogue, which the bf16 codec gate does not bear)
+// and after_conv() turns it into `out` with one launch of the activation's own kernel
+void set_act_or_raw(ConvArgs& a, void* out, float* raw32, const Snake& sn) {
+    if (sn.aa) { a.out_cf = raw32; a.cf_channels = 0; }
+    else set_act(a, out, sn);
+}
+int after_conv(const OobKernels* k, const Snake& sn, const float* raw32, void* out, int Cp, int L, int B, hipStream_t s) {
+    return sn.aa ? k->aa_act(raw32, 1, out, sn.a, sn.ib, sn.act, Cp, L, B, s) : 0;
 }
 
 // ---- the ConvArgs of each layer kind.  decode / encode and the unit-level entry (sat_oobleck_unit) both build their launches from these, so
@@ -363,13 +390,13 @@ std::vector<std::string> range_names(const sat_oobleck_cfg& c, const sat_oobleck
 
 // one ResidualUnit (autoencoders.py:45-68): in S (snaked x) + R (raw x) -> R (raw x') and/or Sout (snake_next(x'))
 // With the range report on, every unit takes the two launches: the tensor between its convolutions then reaches memory (Y) and has a record
-int run_ru(const OobPlan* p, const OobPlan::Block& blk, int r, int C, int L, int B, void* R, const void* S, void* Y, void* Sout,
+int run_ru(const OobPlan* p, const OobPlan::Block& blk, int r, int C, int L, int B, void* R, const void* S, void* Y, void* Sout, float* F,
            const Snake& next, bool need_raw, hipStream_t s, Ranger& rg) {
     static const int dil[3] = {1, 3, 9};
     ConvArgs a = ru_c7_args(blk.ru_c7[r], S, L, dil[r]);
     set_act(a, Y, blk.ru_sn2[r]);
     ConvArgs c = ru_c1_args(blk.ru_c1[r], Y, L, R, need_raw);
-    set_act(c, Sout, next);
+    set_act_or_raw(c, Sout, F, next);      // next.aa: the sum goes to F in fp32, the caller's after_conv() makes Sout of it
     // the whole unit in one launch where the build has the fused kernel and C is one of its tiles: the intermediate never leaves LDS
     if (p->k->ru_fused && (C == 128 || C == 256) && !rg.two_launches()) {
         RuArgs f{a, c};
@@ -391,9 +418,11 @@ int run_ru(const OobPlan* p, const OobPlan::Block& blk, int r, int C, int L, int
 int oob_unit(const OobKernels* k, const sat_oobleck_unit_desc* u, sat_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const int kind = u->kind, B = u->b, L = u->t_len, Ci = u->c_in, Co = u->c_out, st = u->stride;
-    SAT_CHECK_ARG(kind >= SAT_OOBLECK_UNIT_CONV7 && kind <= SAT_OOBLECK_UNIT_CF_TO_CL, SAT_E_UNSUPPORTED, "oobleck_unit: unknown kind %d", kind);
+    SAT_CHECK_ARG((kind >= SAT_OOBLECK_UNIT_CONV7 && kind <= SAT_OOBLECK_UNIT_CF_TO_CL) || kind == SAT_OOBLECK_UNIT_AA_ACT, SAT_E_UNSUPPORTED,
+                  "oobleck_unit: unknown kind %d", kind);
+    const bool aa = kind == SAT_OOBLECK_UNIT_AA_ACT, no_conv = aa || kind == SAT_OOBLECK_UNIT_CF_TO_CL;
     SAT_CHECK_ARG(u->activation == ACT_SNAKE || u->activation == ACT_ELU, SAT_E_UNSUPPORTED, "oobleck_unit: unknown activation %d", u->activation);
-    SAT_CHECK_ARG(B > 0 && L > 0 && Ci > 0 && (Co > 0 || kind == SAT_OOBLECK_UNIT_CF_TO_CL), SAT_E_INVALID, "oobleck_unit: b, t_len, c_in, c_out must be positive");
+    SAT_CHECK_ARG(B > 0 && L > 0 && Ci > 0 && (Co > 0 || no_conv), SAT_E_INVALID, "oobleck_unit: b, t_len, c_in, c_out must be positive");
     const bool resample = kind == SAT_OOBLECK_UNIT_CONVT || kind == SAT_OOBLECK_UNIT_NEAREST || kind == SAT_OOBLECK_UNIT_STRIDED;
     const bool dilated = kind == SAT_OOBLECK_UNIT_CONV7 || kind == SAT_OOBLECK_UNIT_RESIDUAL;
     const bool residual = kind == SAT_OOBLECK_UNIT_CONV1_RES || kind == SAT_OOBLECK_UNIT_RESIDUAL;
@@ -412,8 +441,9 @@ int oob_unit(const OobKernels* k, const sat_oobleck_unit_desc* u, sat_stream_t s
                   "oobleck_unit: the first convolution takes 1 or 2 channels and writes out_raw and out_snk");
     SAT_CHECK_ARG(from_cf ? u->in_cf != nullptr : u->in != nullptr, SAT_E_INVALID, "oobleck_unit: input pointer missing");
     SAT_CHECK_ARG(to_cf ? u->out_cf != nullptr : (u->out_raw || u->out_snk), SAT_E_INVALID, "oobleck_unit: output pointer missing");
-    SAT_CHECK_ARG(kind == SAT_OOBLECK_UNIT_CF_TO_CL || (u->weight_g && u->weight_v), SAT_E_INVALID, "oobleck_unit: weight_g / weight_v missing");
-    const bool has_bias = kind != SAT_OOBLECK_UNIT_NEAREST && kind != SAT_OOBLECK_UNIT_FINAL_DEC && kind != SAT_OOBLECK_UNIT_CF_TO_CL;
+    SAT_CHECK_ARG(no_conv || (u->weight_g && u->weight_v), SAT_E_INVALID, "oobleck_unit: weight_g / weight_v missing");
+    SAT_CHECK_ARG(!aa || (u->out_snk && u->out_snk != u->in), SAT_E_INVALID, "oobleck_unit: the anti-aliased activation writes out_snk, not in place");
+    const bool has_bias = kind != SAT_OOBLECK_UNIT_NEAREST && kind != SAT_OOBLECK_UNIT_FINAL_DEC && !no_conv;
     SAT_CHECK_ARG(!has_bias || u->bias, SAT_E_INVALID, "oobleck_unit: bias missing");
     const bool act_behind = u->out_snk != nullptr;      // the activation whose result out_snk holds
     const bool snake = u->activation == ACT_SNAKE;
@@ -429,7 +459,11 @@ int oob_unit(const OobKernels* k, const sat_oobleck_unit_desc* u, sat_stream_t s
     p.opt = sat_oobleck_options{u->activation, u->final_tanh, kind == SAT_OOBLECK_UNIT_NEAREST};
     auto set = [&](const char* name, const float* ptr, int64_t n) { return ptr ? p.tensors.set("oobleck", name, ptr, n) : 0; };
     const int ktaps = kind == SAT_OOBLECK_UNIT_CONV1_RES ? 1 : kind == SAT_OOBLECK_UNIT_FINAL_ENC ? 3 : resample ? 2 * st : 7;
-    if (kind != SAT_OOBLECK_UNIT_CF_TO_CL) {
+    if (aa) {
+        p.antialias = true;
+        SAT_TRY(set("act.alpha", u->alpha, Ci));
+        SAT_TRY(set("act.beta", u->beta, Ci));
+    } else if (kind != SAT_OOBLECK_UNIT_CF_TO_CL) {
         const int gdim = kind == SAT_OOBLECK_UNIT_CONVT ? Ci : Co;      // weight norm runs over dim 0: ConvTranspose1d weights are [c_in, c_out, k]
         SAT_TRY(set("conv.weight_g", u->weight_g, gdim));
         SAT_TRY(set("conv.weight_v", u->weight_v, (int64_t)Ci * Co * ktaps));
@@ -452,6 +486,7 @@ int oob_unit(const OobKernels* k, const sat_oobleck_unit_desc* u, sat_stream_t s
     SAT_TRY(plan_finalize(&p, s, [&](Bump& ar) -> int {
         SAT_TRY(make_zero_page(&p, ar, s));
         if (kind == SAT_OOBLECK_UNIT_CF_TO_CL) return 0;
+        if (aa) return make_snake(&p, ar, "", Ci, &sn, s, true);      // the plan's own packing; the tensors are "act.alpha" / "act.beta"
         if (kind == SAT_OOBLECK_UNIT_RESIDUAL) {
             SAT_TRY(make_conv(&p, ar, "conv.", Ci, Co, 7, true, &blk.ru_c7[r], s));
             SAT_TRY(make_snake(&p, ar, "act.", Co, &blk.ru_sn2[r], s));
@@ -473,9 +508,10 @@ int oob_unit(const OobKernels* k, const sat_oobleck_unit_desc* u, sat_stream_t s
     ConvArgs a{};
     switch (kind) {
         case SAT_OOBLECK_UNIT_CF_TO_CL: SAT_TRY(k->cf_to_cl(u->in_cf, out_raw ? out_raw : out_snk, Ci, L, B, s)); break;
+        case SAT_OOBLECK_UNIT_AA_ACT: SAT_TRY(k->aa_act(in, 0, out_snk, sn.a, sn.ib, sn.act, pad64(Ci), L, B, s)); break;
         case SAT_OOBLECK_UNIT_FIRST_CONV: SAT_TRY(k->first_conv(u->in_cf, w_f32, cw.bias, sn.a, sn.ib, sn.act, out_raw, out_snk, Ci, Co, L, B, s)); break;
         case SAT_OOBLECK_UNIT_RESIDUAL:
-            SAT_TRY(run_ru(&p, blk, r, pad64(Co), L, B, res, in, Y, out_snk, next, out_raw != nullptr, s, rg));
+            SAT_TRY(run_ru(&p, blk, r, pad64(Co), L, B, res, in, Y, out_snk, nullptr, next, out_raw != nullptr, s, rg));
             break;
         case SAT_OOBLECK_UNIT_CONV7: a = ru_c7_args(cw, in, L, u->dilation); break;
         case SAT_OOBLECK_UNIT_CONV1_RES: a = ru_c1_args(cw, in, L, res, out_raw != nullptr); break;
@@ -552,6 +588,14 @@ extern "C" int sat_oobleck_plan_create(const sat_oobleck_cfg* cfg, sat_oobleck_p
                       "oobleck_plan_create: decoder latent_dim %d must be a multiple of 64 (sat_oobleck_plan_create_ex takes any)", cfg->latent_dim);
     return sat_oobleck_plan_create_ex(cfg, nullptr, 0, out_plan);
 }
+extern "C" int sat_oobleck_plan_set_antialias(sat_oobleck_plan* p, int32_t enable) {
+    SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_set_antialias: null plan");
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "oobleck_plan_set_antialias: the plan is finalized");
+    SAT_CHECK_ARG(enable == 0 || enable == 1, SAT_E_UNSUPPORTED, "oobleck_plan_set_antialias: enable must be 0 or 1, got %d", enable);
+    SAT_CHECK_ARG(!enable || !p->rr, SAT_E_UNSUPPORTED, "oobleck_plan_set_antialias: the range report is on and has no records for the anti-aliased tensors");
+    p->antialias = enable != 0;
+    return 0;
+}
 extern "C" void sat_oobleck_plan_destroy(sat_oobleck_plan* p) { delete p; }
 extern "C" int sat_oobleck_plan_set_tensor(sat_oobleck_plan* p, const char* name, const float* data_dev, int64_t numel) {
     SAT_CHECK_ARG(p, SAT_E_INVALID, "oobleck_plan_set_tensor: null plan");
@@ -589,8 +633,9 @@ extern "C" int sat_oobleck_decode(sat_oobleck_plan* p, const float* z, float* au
     void* Sn = bf.S1;
     {
         ConvArgs a = same_conv_args(p->first, bf.Y, T);
-        set_act(a, S, p->blocks[0].sn_in);
+        set_act_or_raw(a, S, bf.F, p->blocks[0].sn_in);
         SAT_TRY(k->conv(&a, B, s));
+        SAT_TRY(after_conv(k, p->blocks[0].sn_in, bf.F, S, p->first.Cout, T, B, s));
         SAT_TRY(rg(S, (size_t)B * T * p->first.Cout));
     }
     int L = T;
@@ -607,7 +652,8 @@ extern "C" int sat_oobleck_decode(sat_oobleck_plan* p, const float* z, float* au
         SAT_TRY(rg(bf.R, (size_t)B * L * blk.cout));
         for (int r = 0; r < 3; ++r) {
             const Snake& next = r < 2 ? blk.ru_sn1[r + 1] : (bi + 1 < nb ? p->blocks[bi + 1].sn_in : p->final_snake);
-            SAT_TRY(run_ru(p, blk, r, blk.cout, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s, rg));
+            SAT_TRY(run_ru(p, blk, r, blk.cout, L, B, bf.R, S, bf.Y, Sn, bf.F, next, r < 2, s, rg));
+            SAT_TRY(after_conv(k, next, bf.F, Sn, blk.cout, L, B, s));
             std::swap(S, Sn);
         }
     }
@@ -640,7 +686,7 @@ extern "C" int sat_oobleck_encode(sat_oobleck_plan* p, const float* audio, float
         const auto& blk = p->blocks[bi];
         for (int r = 0; r < 3; ++r) {
             const Snake& next = r < 2 ? blk.ru_sn1[r + 1] : blk.sn_in;
-            SAT_TRY(run_ru(p, blk, r, blk.cin, L, B, bf.R, S, bf.Y, Sn, next, r < 2, s, rg));
+            SAT_TRY(run_ru(p, blk, r, blk.cin, L, B, bf.R, S, bf.Y, Sn, bf.F, next, r < 2, s, rg));
             std::swap(S, Sn);
         }
         const int st = blk.stride;
@@ -649,8 +695,9 @@ extern "C" int sat_oobleck_encode(sat_oobleck_plan* p, const float* audio, float
         const bool lastb = bi + 1 == nb;
         a.out_raw = lastb ? nullptr : opq(bf.R);
         const Snake& nx = lastb ? p->final_snake : p->blocks[bi + 1].ru_sn1[0];
-        set_act(a, Sn, nx);
+        set_act_or_raw(a, Sn, bf.F, nx);
         SAT_TRY(k->conv(&a, B, s));
+        SAT_TRY(after_conv(k, nx, bf.F, Sn, blk.cout, Lo, B, s));
         std::swap(S, Sn);
         L = Lo;
         SAT_TRY(rg(S, (size_t)B * L * blk.cout));
@@ -673,6 +720,7 @@ extern "C" int sat_oobleck_range_report(sat_oobleck_plan* p, int32_t enable) {
         return 0;
     }
     SAT_CHECK_ARG(sat_launch_range_stats, SAT_E_UNSUPPORTED, "oobleck_range_report: built without the range statistics kernel");
+    SAT_CHECK_ARG(!p->antialias, SAT_E_UNSUPPORTED, "oobleck_range_report: no records for the tensors of an anti-aliased plan (sat_oobleck_plan_set_antialias)");
     const size_t bytes = p->rr_names.size() * sizeof(sat_range_record);
     if (enable == 2) {
         SAT_CHECK_ARG(p->rr, SAT_E_STATE, "oobleck_range_report: the report is not enabled, there is nothing to zero");

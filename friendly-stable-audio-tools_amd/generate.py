@@ -65,6 +65,10 @@ def get_args():
     p.add_argument("--codec-final-tanh", action="store_true",
                    help="build extension: the VAE decoder was trained with final_tanh=True (write \"final_tanh\": false in the model config, "
                         "which the constructor requires, and pass this flag: set_final_tanh(True))")
+    p.add_argument("--codec-allow-antialias", action="store_true",
+                   help="build extension: the codec's config has antialias_activation=True (alias_free_torch's Activation1d around its "
+                        "activations), which the constructors refuse without an opt-in: sets \"allow_antialias\": true in the encoder's and "
+                        "the decoder's config before the model is built (with --model-config or the built-in config; an error with --model-name)")
     p.add_argument("--allow-conv-ff", action="store_true",
                    help="build extension: the model config's DiT has ff_kwargs use_conv (convolutional feed-forwards), which the constructor "
                         "refuses without an opt-in: sets \"allow_conv_ff\": true in model.diffusion.config before the model is built "
@@ -105,7 +109,21 @@ def get_args():
     if args.allow_natten and args.model_name:
         p.error("--allow-natten is written into the model config before the model is built: it goes with --model-config, not with "
                 "--model-name (a pretrained model is built from its own config)")
+    if args.codec_allow_antialias and args.model_name:
+        p.error("--codec-allow-antialias is written into the model config before the model is built: it goes with --model-config, not with "
+                "--model-name (a pretrained model is built from its own config)")
     return args
+
+
+def allow_codec_antialias(model_config):
+    """--codec-allow-antialias: writes "allow_antialias": true into the Oobleck encoder's and decoder's "config", where the constructors look
+    for the opt-in to antialias_activation=True; the codec is the model itself (an autoencoder config) or its pretransform."""
+    model = model_config["model"]
+    codec = model if "encoder" in model or "decoder" in model else (model.get("pretransform") or {}).get("config", {})
+    for part in ("encoder", "decoder"):
+        if part in codec:
+            codec[part].setdefault("config", {})["allow_antialias"] = True
+    return model_config
 
 
 def apply_config_flags(args, model_config):
@@ -120,6 +138,8 @@ def apply_config_flags(args, model_config):
         model_config["model"]["diffusion"]["config"]["allow_causal"] = True
     if args.allow_natten:
         model_config["model"]["diffusion"]["config"]["allow_natten"] = True
+    if args.codec_allow_antialias:
+        allow_codec_antialias(model_config)
     return model_config
 
 

@@ -33,7 +33,22 @@ def get_args():
     p.add_argument("--codec-final-tanh", action="store_true",
                    help="build extension: the decoder was trained with final_tanh=True (write \"final_tanh\": false in the model config, "
                         "which the constructor requires, and pass this flag: set_final_tanh(True))")
+    p.add_argument("--codec-allow-antialias", action="store_true",
+                   help="build extension: the codec's config has antialias_activation=True (alias_free_torch's Activation1d around its "
+                        "activations), which the constructors refuse without an opt-in: sets \"allow_antialias\": true in the encoder's and "
+                        "the decoder's config before the model is built")
     return p.parse_args()
+
+
+def allow_codec_antialias(model_config):
+    """--codec-allow-antialias: writes "allow_antialias": true into the Oobleck encoder's and decoder's "config", where the constructors look
+    for the opt-in to antialias_activation=True; the codec is the model itself (an autoencoder config) or its pretransform."""
+    model = model_config["model"]
+    codec = model if "encoder" in model or "decoder" in model else (model.get("pretransform") or {}).get("config", {})
+    for part in ("encoder", "decoder"):
+        if part in codec:
+            codec[part].setdefault("config", {})["allow_antialias"] = True
+    return model_config
 
 
 def main():
@@ -47,6 +62,8 @@ def main():
     rank, world = get_rank(), get_world_size()
 
     cfg = json.load(open(args.model_config)) if args.model_config else model_configs.stable_audio_vae()
+    if args.codec_allow_antialias:
+        allow_codec_antialias(cfg)
     model = create_model_from_config(cfg)
     if args.ckpt_path:
         copy_state_dict(model, load_ckpt_state_dict(args.ckpt_path))

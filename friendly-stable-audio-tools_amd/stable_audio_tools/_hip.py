@@ -97,6 +97,8 @@ class SatOobleckUnitDesc(Structure):
 # include/sat_hip.h: SAT_OOBLECK_UNIT_*
 (OOBLECK_UNIT_CONV7, OOBLECK_UNIT_CONV1_RES, OOBLECK_UNIT_RESIDUAL, OOBLECK_UNIT_CONVT, OOBLECK_UNIT_NEAREST, OOBLECK_UNIT_STRIDED,
  OOBLECK_UNIT_FIRST_CONV, OOBLECK_UNIT_FINAL_DEC, OOBLECK_UNIT_FINAL_ENC, OOBLECK_UNIT_CF_TO_CL) = range(10)
+OOBLECK_UNIT_AA_ACT = 11      # (10 is unassigned and refused)
+OOBLECK_AA_TIME_TILE = 32     # include/sat_hip.h: SAT_OOBLECK_AA_TIME_TILE, the output rows one thread of the anti-aliased activation walks
 
 
 class SatRangeRecord(Structure):
@@ -157,6 +159,7 @@ _SIGNATURES = {
                                      c_float, c_int64, c_void_p]),
     "sat_oobleck_plan_create": (c_int32, [POINTER(SatOobleckCfg), POINTER(c_void_p)]),
     "sat_oobleck_plan_create_ex": (c_int32, [POINTER(SatOobleckCfg), POINTER(SatOobleckOptions), c_size_t, POINTER(c_void_p)]),
+    "sat_oobleck_plan_set_antialias": (c_int32, [c_void_p, c_int32]),
     "sat_oobleck_plan_destroy": (None, [c_void_p]),
     "sat_oobleck_plan_set_tensor": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64]),
     "sat_oobleck_plan_finalize": (c_int32, [c_void_p, c_void_p]),

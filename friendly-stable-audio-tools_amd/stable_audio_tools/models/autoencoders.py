@@ -50,12 +50,76 @@ class WNConvTranspose1d(_WNBase):
         self._register(_init.conv_transpose1d(in_channels, out_channels, kernel_size, stride=stride, padding=padding), True)
 
 
-def _act(use_snake, channels, antialias_activation=False):
-    """``get_activation("snake" if use_snake else "elu")`` (autoencoders.py:27-42): SnakeBeta, or the parameter-free ``nn.ELU``.  Either
-    runs inside the producing convolution's epilogue; the module only holds the parameters (none for ELU)."""
-    if antialias_activation:
-        raise NotImplementedError("antialias_activation is not supported by the HIP codec")
-    return SnakeBeta(channels) if use_snake else nn.ELU()
+def antialias_filter():
+    """The 12 taps of ``alias_free_torch``'s ``kaiser_sinc_filter1d(cutoff=0.25, half_width=0.3, kernel_size=12)`` as the library's
+    buffers hold them, [1, 1, 12] fp32: a sinc of cutoff 0.25 under a Kaiser window whose beta follows from the transition width
+    (Kaiser's formula at an attenuation of 2.285 * 5 * pi * 1.2 + 7.95 = 51 dB), normalised to sum 1.  ``Activation1d`` uses the same taps
+    for its 2x upsampling and for the low-pass in front of its 2x decimation; the HIP kernel (csrc/oobleck.hip, aa_act_kernel) has them
+    as constants."""
+    size, cutoff, half_width = 12, 0.25, 0.3
+    atten = 2.285 * (size // 2 - 1) * math.pi * 4 * half_width + 7.95
+    beta = 0.1102 * (atten - 8.7)          # Kaiser's formula above 50 dB, the only branch these constants reach
+    window = torch.kaiser_window(size, periodic=False, beta=beta, dtype=torch.float64)
+    time = torch.arange(-size // 2, size // 2, dtype=torch.float64) + 0.5
+    taps = 2 * cutoff * window * torch.sinc(2 * cutoff * time)
+    return (taps / taps.sum()).float().view(1, 1, size)
+
+
+class _FilterHolder(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.register_buffer("filter", antialias_filter())
+
+
+class UpSample1d(_FilterHolder):
+    pass
+
+
+class LowPassFilter1d(_FilterHolder):
+    pass
+
+
+class DownSample1d(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.lowpass = LowPassFilter1d()
+
+
+class Activation1d(nn.Module):
+    """``alias_free_torch.Activation1d(act)`` with the library's defaults (2x up, 2x down, 12 taps each way) as a parameter holder: the
+    module tree and buffer names of alias_free_torch 0.0.6 (``act``, ``upsample.filter``, ``downsample.lowpass.filter``), so that the
+    reference's checkpoints load with ``strict=True``.  On the device it is one launch of aa_act_kernel behind the producing convolution.
+    The kernel holds the taps as constants: a checkpoint may overwrite the buffers, but only with the same filter (``check_filters``)."""
+
+    def __init__(self, act):
+        super().__init__()
+        self.act = act
+        self.upsample = UpSample1d()
+        self.downsample = DownSample1d()
+
+    def check_filters(self):
+        want = antialias_filter()
+        for name, buf in (("upsample.filter", self.upsample.filter), ("downsample.lowpass.filter", self.downsample.lowpass.filter)):
+            if tuple(buf.shape) != tuple(want.shape) or not bool(((buf.detach().float().cpu() - want).abs() <= 1e-6).all()):
+                raise ValueError(f"Activation1d: the buffer {name} is not the 12-tap Kaiser-sinc filter (cutoff 0.25, half-width 0.3) that "
+                                 "the HIP kernel has as constants; other filters are not supported")
+
+
+_ANTIALIAS_REFUSAL = (
+    "antialias_activation=True runs only on request in the HIP codec: pass allow_antialias=True beside it (config key "
+    "\"allow_antialias\": true in the encoder's and the decoder's \"config\"; generate.py / reconstruct_audios.py --codec-allow-antialias).  "
+    "The anti-aliased activation is pinned by this project's stand-in for alias_free_torch, not by the library (README, \"Oobleck "
+    "configurations\")")
+
+
+def _act(use_snake, channels, antialias_activation=False, allow_antialias=False):
+    """``get_activation("snake" if use_snake else "elu", antialias=...)`` (autoencoders.py:27-42): SnakeBeta, or the parameter-free
+    ``nn.ELU``, which run inside the producing convolution's epilogue -- the module only holds the parameters (none for ELU) -- or
+    either wrapped in ``Activation1d``, which runs as a launch of its own."""
+    if antialias_activation and not allow_antialias:
+        raise NotImplementedError(_ANTIALIAS_REFUSAL)
+    act = SnakeBeta(channels) if use_snake else nn.ELU()
+    return Activation1d(act) if antialias_activation else act
 
 
 def nearest_upsample_taps(weight, stride):
@@ -75,29 +139,32 @@ def nearest_upsample_taps(weight, stride):
 
 
 class ResidualUnit(nn.Module):
-    def __init__(self, in_channels, out_channels, dilation, use_snake=False, antialias_activation=False):
+    def __init__(self, in_channels, out_channels, dilation, use_snake=False, antialias_activation=False, allow_antialias=False):
         super().__init__()
         self.dilation = dilation
+        # (the reference's blocks build their units without antialias_activation, autoencoders.py:76-78 and :110-112: a unit with the
+        # option on exists as a module of its own only, and no plan of this package runs one)
         self.layers = nn.Sequential(
-            _act(use_snake, out_channels, antialias_activation),
+            _act(use_snake, out_channels, antialias_activation, allow_antialias),
             WNConv1d(in_channels, out_channels, 7, dilation=dilation, padding=(dilation * 6) // 2),
-            _act(use_snake, out_channels, antialias_activation),
+            _act(use_snake, out_channels, antialias_activation, allow_antialias),
             WNConv1d(out_channels, out_channels, 1))
 
 
 class EncoderBlock(nn.Module):
-    def __init__(self, in_channels, out_channels, stride, use_snake=False, antialias_activation=False):
+    def __init__(self, in_channels, out_channels, stride, use_snake=False, antialias_activation=False, allow_antialias=False):
         super().__init__()
         self.layers = nn.Sequential(
             ResidualUnit(in_channels, in_channels, 1, use_snake=use_snake),
             ResidualUnit(in_channels, in_channels, 3, use_snake=use_snake),
             ResidualUnit(in_channels, in_channels, 9, use_snake=use_snake),
-            _act(use_snake, in_channels, antialias_activation),
+            _act(use_snake, in_channels, antialias_activation, allow_antialias),
             WNConv1d(in_channels, out_channels, 2 * stride, stride=stride, padding=math.ceil(stride / 2)))
 
 
 class DecoderBlock(nn.Module):
-    def __init__(self, in_channels, out_channels, stride, use_snake=False, antialias_activation=False, use_nearest_upsample=False):
+    def __init__(self, in_channels, out_channels, stride, use_snake=False, antialias_activation=False, use_nearest_upsample=False,
+                 allow_antialias=False):
         super().__init__()
         if use_nearest_upsample:      # autoencoders.py:95-99; on the device a three-tap polyphase convolution (nearest_upsample_taps)
             upsample_layer = nn.Sequential(nn.Upsample(scale_factor=stride, mode="nearest"),
@@ -105,7 +172,7 @@ class DecoderBlock(nn.Module):
         else:
             upsample_layer = WNConvTranspose1d(in_channels, out_channels, 2 * stride, stride=stride, padding=math.ceil(stride / 2))
         self.layers = nn.Sequential(
-            _act(use_snake, in_channels, antialias_activation),
+            _act(use_snake, in_channels, antialias_activation, allow_antialias),
             upsample_layer,
             ResidualUnit(out_channels, out_channels, 1, use_snake=use_snake),
             ResidualUnit(out_channels, out_channels, 3, use_snake=use_snake),
@@ -119,7 +186,7 @@ _CODEC_GEMM_DTYPES = {"bf16": 0, "fp16": 3, "fp32": 2}
 class _OobleckHip(nn.Module):
     """Shared plan handling of encoder and decoder."""
     _is_decoder = False
-    use_snake, use_nearest_upsample, final_tanh = True, False, False
+    use_snake, use_nearest_upsample, final_tanh, antialias_activation = True, False, False, False
 
     def _init_plan_state(self):
         self.gemm_dtype = _config.default_gemm_dtype()
@@ -138,6 +205,8 @@ class _OobleckHip(nn.Module):
         convolutions then exists in memory): +60 % per decode, inside the codec gates (measured bit-equal to the fused kernel, not promised).  The setting
         survives a plan rebuild, the records collected so far do not."""
         lib = _hip.lib()
+        if enable and self.antialias_activation:
+            raise NotImplementedError("activation_range_report has no rows for the tensors of an antialias_activation codec")
         if enable:
             self._range_report = True
             try:
@@ -217,11 +286,20 @@ class _OobleckHip(nn.Module):
         opt.nearest_upsample = 1 if self.use_nearest_upsample else 0
         create = lambda: _hip.new_handle(lib.sat_oobleck_plan_create_ex, ctypes.byref(cfg), ctypes.byref(opt), ctypes.sizeof(opt))
 
+        tensors = self.state_dict()
+        if self.antialias_activation:      # the kernel has the filter taps as constants: the buffers are checked here and are no plan tensors
+            for m in self.modules():
+                if isinstance(m, Activation1d):
+                    m.check_filters()
+            tensors = {k: v for k, v in tensors.items() if not k.endswith(".filter")}
+
         def configure(plan):
+            if self.antialias_activation:
+                _hip.check(lib.sat_oobleck_plan_set_antialias(plan, 1))
             if self._range_report:        # the report belongs to the module: a rebuilt plan starts with it on (and with empty records)
                 _hip.check(lib.sat_oobleck_range_report(plan, 1))
 
-        self._plan, self._plan_version = _hip.build_plan("oobleck", create, self.state_dict(), dev, configure), ver
+        self._plan, self._plan_version = _hip.build_plan("oobleck", create, tensors, dev, configure), ver
         return self._plan
 
     def _workspace(self, b, t_len):
@@ -231,22 +309,26 @@ class _OobleckHip(nn.Module):
 
 class OobleckEncoder(_OobleckHip):
     def __init__(self, in_channels=2, channels=128, latent_dim=32, c_mults=[1, 2, 4, 8], strides=[2, 4, 8, 8], use_snake=False,
-                 antialias_activation=False):
+                 antialias_activation=False, allow_antialias=False):
         super().__init__()
+        if antialias_activation and not allow_antialias:
+            raise NotImplementedError(_ANTIALIAS_REFUSAL)
         if any(int(s) < 2 for s in strides):
             raise NotImplementedError(
                 f"strides {list(strides)}: a stride-1 encoder block (Conv1d k=2, padding 1) yields L + 1 samples in the reference; the HIP "
                 "codec keeps L / stride per block and runs strides of 2 and more")
         self.io_channels, self.channels, self.latent_dim = in_channels, channels, latent_dim
         self.c_mults, self.strides = list(c_mults), list(strides)
-        self.use_snake = bool(use_snake)
+        self.use_snake, self.antialias_activation = bool(use_snake), bool(antialias_activation)
         self.ratio = int(math.prod(strides))
         cm = [1] + list(c_mults)
         self.depth = len(cm)
         layers = [WNConv1d(in_channels, cm[0] * channels, 7, padding=3)]
         for i in range(self.depth - 1):
             layers.append(EncoderBlock(cm[i] * channels, cm[i + 1] * channels, strides[i], use_snake=use_snake))
-        layers += [_act(use_snake, cm[-1] * channels, antialias_activation), WNConv1d(cm[-1] * channels, latent_dim, 3, padding=1)]
+        # (the blocks above are built without the option, as the reference's are, autoencoders.py:139-143: it reaches this activation alone)
+        layers += [_act(use_snake, cm[-1] * channels, antialias_activation, allow_antialias),
+                   WNConv1d(cm[-1] * channels, latent_dim, 3, padding=1)]
         self.layers = nn.Sequential(*layers)
         self._init_plan_state()
 
@@ -268,8 +350,10 @@ class OobleckDecoder(_OobleckHip):
     _is_decoder = True
 
     def __init__(self, out_channels=2, channels=128, latent_dim=32, c_mults=[1, 2, 4, 8], strides=[2, 4, 8, 8], use_snake=False,
-                 antialias_activation=False, use_nearest_upsample=False, final_tanh=True):
+                 antialias_activation=False, use_nearest_upsample=False, final_tanh=True, allow_antialias=False):
         super().__init__()
+        if antialias_activation and not allow_antialias:
+            raise NotImplementedError(_ANTIALIAS_REFUSAL)
         if final_tanh:
             raise NotImplementedError(
                 "final_tanh=True cannot be given to the constructor of the HIP codec: build the decoder with final_tanh=False, then call "
@@ -281,14 +365,16 @@ class OobleckDecoder(_OobleckHip):
         self.io_channels, self.channels, self.latent_dim = out_channels, channels, latent_dim
         self.c_mults, self.strides = list(c_mults), list(strides)
         self.use_snake, self.use_nearest_upsample = bool(use_snake), bool(use_nearest_upsample)
+        self.antialias_activation = bool(antialias_activation)
         self.ratio = int(math.prod(strides))
         cm = [1] + list(c_mults)
         self.depth = len(cm)
         layers = [WNConv1d(latent_dim, cm[-1] * channels, 7, padding=3)]
         for i in range(self.depth - 1, 0, -1):
             layers.append(DecoderBlock(cm[i] * channels, cm[i - 1] * channels, strides[i - 1], use_snake=use_snake,
-                                       antialias_activation=antialias_activation, use_nearest_upsample=use_nearest_upsample))
-        layers += [_act(use_snake, cm[0] * channels, antialias_activation),
+                                       antialias_activation=antialias_activation, use_nearest_upsample=use_nearest_upsample,
+                                       allow_antialias=allow_antialias))
+        layers += [_act(use_snake, cm[0] * channels, antialias_activation, allow_antialias),
                    WNConv1d(cm[0] * channels, out_channels, 7, padding=3, bias=False), nn.Identity()]
         self.layers = nn.Sequential(*layers)
         self._init_plan_state()

@@ -541,6 +541,16 @@ typedef struct sat_oobleck_options {
  * nearest_upsample decoders take every stride. */
 int sat_oobleck_plan_create_ex(const sat_oobleck_cfg* cfg, const sat_oobleck_options* options, size_t options_bytes,
                                sat_oobleck_plan** out_plan);
+/* antialias_activation=True of the reference (models/autoencoders.py:29-41): the activations the reference wraps in
+ * alias_free_torch.Activation1d -- the one in front of every decoder block's upsampler and the one in front of the last convolution of either
+ * direction; the ResidualUnits inside the blocks keep their plain activations, as the reference builds them -- run as 2x Kaiser-sinc
+ * upsampling (12 taps, replicate padding), the activation at the doubled rate, low-pass and 2x decimation.  The convolution in front then
+ * writes its un-activated result, in fp32 in every build, and one launch of a kernel of its own produces the tensor the next convolution
+ * reads; sat_oobleck_workspace_bytes grows by the largest such fp32 tensor, with the option on only.  The 12 taps (cutoff 0.25, half-width 0.3) are constants of the kernel and no plan tensors; Snake parameters keep their names
+ * ("layers.1.layers.0.act.alpha": the module tree puts the activation under ".act").  enable: 0 or 1 (SAT_E_UNSUPPORTED otherwise); allowed
+ * between create and finalize (SAT_E_STATE afterwards).  A plan that never calls it, or calls it with 0, launches what it launched before the
+ * option existed.  sat_oobleck_range_report(plan, 1) on a plan with the option on is SAT_E_UNSUPPORTED (no records for the added tensors). */
+int sat_oobleck_plan_set_antialias(sat_oobleck_plan* plan, int32_t enable);
 void sat_oobleck_plan_destroy(sat_oobleck_plan* plan);
 /* `name` relative to the OobleckEncoder/OobleckDecoder module, e.g.
  * "layers.1.layers.2.layers.1.weight_v".  Pointer lifetime and the synchronising finalize: see sat_dit_plan_set_tensor. */
@@ -590,6 +600,11 @@ int sat_oobleck_range_report_read(sat_oobleck_plan* plan, sat_range_record* out_
 #define SAT_OOBLECK_UNIT_FINAL_DEC 7    /* decoder last convolution, k = 7, no bias, tanh by final_tanh: -> out_cf [b, c_out, t_len] fp32 */
 #define SAT_OOBLECK_UNIT_FINAL_ENC 8    /* encoder last convolution, k = 3, bias: -> out_cf [b, c_out, t_len] fp32 */
 #define SAT_OOBLECK_UNIT_CF_TO_CL 9     /* in_cf [b, c_in, t_len] fp32 -> out_raw [b, t_len, Cp(c_in)], pad channels zero */
+#define SAT_OOBLECK_UNIT_AA_ACT 11      /* the anti-aliased activation (sat_oobleck_plan_set_antialias): in [b, t_len, Cp(c_in)] -> out_snk of the same
+                                           shape (not in place); activation, alpha / beta [c_in]; no weights, c_out ignored.  A plan hands the
+                                           same kernel fp32 rows.  (10 stays unassigned and refused: the recorded launch list of
+                                           tests/test_oobleck_launches_host.py pins "unknown kind 10") */
+#define SAT_OOBLECK_AA_TIME_TILE 32     /* output rows one thread of that kernel walks: the seams of its time tiling (tests) */
 typedef struct sat_oobleck_unit_desc {
     int32_t kind;              /* SAT_OOBLECK_UNIT_* */
     int32_t gemm_dtype;        /* as sat_oobleck_cfg: picks the bf16 / fp16 / fp32 build; the type of in, res, out_raw, out_snk */
