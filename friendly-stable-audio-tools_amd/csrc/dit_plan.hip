@@ -186,6 +186,7 @@ int split_heads_f32(const sat_dit_plan* p, const float* src, float* d0, float* d
 int attention_f32(const sat_dit_plan* p, bool self, const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int sq, int sk,
                   hipStream_t s) {
     if (self && p->causal) return sat_launch_attention_f32_causal(q, k, v, out, b, h, kvh, p->hd, sq, s);
+    if (self && p->natten && p->hd != 64) return sat_launch_attention_f32_window_w(q, k, v, out, b, h, kvh, p->hd, sq, p->natten, 1.0f, s);
     if (self && p->natten) return sat_launch_attention_f32_window(q, k, v, out, b, h, kvh, sq, p->natten, 1.0f, s);      // unscaled logits
     if (p->hd == 64) return sat_launch_attention_f32(q, k, v, out, b, h, kvh, sq, sk, s);
     return sat_launch_attention_f32_w(q, k, v, out, b, h, kvh, p->hd, sq, sk, s);
@@ -536,15 +537,18 @@ struct Forward {
     }
 
     // log2(e) / sqrt(dim_heads), what the projections pre-scale q by (HeadsEpi kind bit 3): the constant the 64-channel kernels were built with
-    // A neighbourhood plan (64-channel heads, no cross-attention) does not scale its logits: log2(e) alone
+    // A neighbourhood plan (any head width, no cross-attention) does not scale its logits: log2(e) alone
     float qscale() const { return p->natten ? 1.4426950408889634f : p->staged() ? sat_attn_qscale(p->hd) : SAT_ATTN_QSCALE; }
     // AO = softmax(q k^T) v for `seqs` sequences of S queries against sk keys (pad sk_pad) in kvh heads: attention.hip at 64 channels per head,
-    // attention_hdw.hip at the staged widths; the causal kernels for the self-attention of a causal plan (sk == S; never an e4m3 plan).  `out`: the
+    // attention_hdw.hip at the staged widths; the causal kernels for the self-attention of a causal plan (sk == S; never an e4m3 plan), the window
+    // kernels (attention_window.hip, attention_hdw_window.hip) for that of a neighbourhood plan (never causal, never e4m3).  `out`: the
     // projection that reads AO; as an MXFP8 operand the kernel writes its block scales beside it (64 channels only)
     int attend(const op_t* q, const op_t* k, const op_t* vt, int seqs, int kvh, int sk, int sk_pad, int f16, const Proj& out, bool self) const {
         const bool causal = self && p->causal;
         if (p->staged()) {
             if (causal) return sat_launch_attention_hdw_causal(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, Spad, sk_pad, s, f16);
+            // the head split wrote Q times log2(e) (qscale): the kernel has no scale of its own
+            if (self && p->natten) return sat_launch_attention_hdw_window(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, Spad, sk_pad, p->natten, s, f16);
             return sat_launch_attention_hdw(q, k, vt, w.AO, seqs, H, kvh, p->hd, S, sk, Spad, sk_pad, s, f16);
         }
         if (causal) return sat_launch_attention_causal(q, k, vt, w.AO, seqs, H, kvh, S, Spad, sk_pad, s, 1.0f, f16);
@@ -1186,6 +1190,36 @@ extern "C" int sat_dit_plan_set_neighborhood_attention(sat_dit_plan* p, const sa
                   "dit_plan_set_neighborhood_attention: natten_kernel_size with dim_heads %d is not built (64 only; the staged widths are a follow-up)", p->hd);
     SAT_CHECK_ARG(!ks || (sat_launch_attention_window && sat_launch_attention_f32_window), SAT_E_UNSUPPORTED,
                   "dit_plan_set_neighborhood_attention: built without the neighbourhood attention kernels");
+    p->natten = ks;
+    return 0;
+}
+
+// The same call for every built head width: 64 as above, and the staged widths 128, 32 and 96 (attention_hdw_window.hip).  Its own entry, so
+// that sat_dit_plan_set_neighborhood_attention keeps answering what it answered; the checks are that one's, but for the width
+extern "C" int sat_dit_plan_set_neighborhood_attention_hdw(sat_dit_plan* p, const sat_dit_neighborhood_options* o, size_t options_bytes) {
+    SAT_CHECK_ARG(p && o, SAT_E_INVALID, "dit_plan_set_neighborhood_attention_hdw: null argument");
+    SAT_CHECK_ARG(options_bytes == sizeof(sat_dit_neighborhood_options), SAT_E_INVALID,
+                  "dit_plan_set_neighborhood_attention_hdw: sat_dit_neighborhood_options of %zu bytes; this library knows %zu", options_bytes,
+                  sizeof(sat_dit_neighborhood_options));
+    SAT_CHECK_ARG(!p->finalized, SAT_E_STATE, "dit_plan_set_neighborhood_attention_hdw: plan already finalized (call it between create and finalize)");
+    const int ks = o->kernel_size;
+    // 0: full attention (the reference tests the value's truth); else what NATTEN takes: odd and greater than 1
+    SAT_CHECK_ARG(ks == 0 || (ks > 1 && (ks & 1)), SAT_E_INVALID,
+                  "dit_plan_set_neighborhood_attention_hdw: kernel_size %d must be 0 (off) or odd and greater than 1", ks);
+    // transformer.py:299, 324: attn_kwargs reach cross_attn too, where q and k differ in length and NATTEN fails: no behaviour to reproduce
+    SAT_CHECK_ARG(!(ks && p->cfg.cond_token_dim > 0), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention_hdw: natten_kernel_size with cross-attention (cond_token_dim %d): the reference has no working behaviour there",
+                  p->cfg.cond_token_dim);
+    // transformer.py:479: the branch never looks at causal
+    SAT_CHECK_ARG(!(ks && p->causal), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention_hdw: natten_kernel_size on a causal plan: the reference ignores causal in that branch");
+    SAT_CHECK_ARG(!(ks && p->cfg.gemm_dtype == SAT_GEMM_FP8), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention_hdw: natten_kernel_size with gemm_dtype fp8 is not built (use bf16, fp16 or the fp32 verification mode)");
+    SAT_CHECK_ARG(!ks || (sat_launch_attention_window && sat_launch_attention_f32_window), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention_hdw: built without the neighbourhood attention kernels");
+    SAT_CHECK_ARG(!(ks && p->staged()) || (sat_launch_attention_hdw_window && sat_launch_attention_f32_window_w), SAT_E_UNSUPPORTED,
+                  "dit_plan_set_neighborhood_attention_hdw: natten_kernel_size with dim_heads %d: built without the neighbourhood attention kernels of the "
+                  "staged widths", p->hd);
     p->natten = ks;
     return 0;
 }

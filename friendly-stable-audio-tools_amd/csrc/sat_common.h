@@ -378,6 +378,10 @@ __attribute__((weak)) int sat_launch_attention_hdw_causal(const op_t* q, const o
 // the logits of this branch), 1 for a Q its producer wrote times log2(e).  WEAK as the causal launchers
 __attribute__((weak)) int sat_launch_attention_window(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int s_len, int sq_pad,
                                                       int sk_pad, int kernel_size, float score_scale, hipStream_t s, int f16 = 0);
+// the same at 32-, 96- and 128-channel heads (sat_dit_plan_set_neighborhood_attention_hdw; attention_hdw_window.hip): layouts and pads as
+// sat_launch_attention_hdw; there is no scale argument, Q arrives times log2(e) from the head split.  WEAK as above
+__attribute__((weak)) int sat_launch_attention_hdw_window(const op_t* q, const op_t* k, const op_t* vt, op_t* out, int b, int h, int kvh, int head_dim,
+                                                          int s_len, int sq_pad, int sk_pad, int kernel_size, hipStream_t s, int f16 = 0);
 }  // namespace SAT_OPNS
 using namespace SAT_OPNS;
 // RotaryEmbedding(max(dim_heads / 2, 32)) (transformer.py:737): pairs (j, j + sat_rope_pairs) rotate, one angle per pair -- 16 for 32- and
@@ -437,6 +441,8 @@ int sat_launch_attention_hdw_causal_f16(const void* q, const void* k, const void
                                         int sq_pad, int sk_pad, hipStream_t s);
 int sat_launch_attention_window_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int s_len, int sq_pad, int sk_pad,
                                     int kernel_size, float score_scale, hipStream_t s);
+int sat_launch_attention_hdw_window_f16(const void* q, const void* k, const void* vt, void* out, int b, int h, int kvh, int head_dim, int s_len,
+                                        int sq_pad, int sk_pad, int kernel_size, hipStream_t s);
 // entry points of the fp16 build for the dispatchers of the bf16 build (GemmArgs is layout-identical in both builds: the pointer
 // element type is the only difference)
 int sat_launch_gemm_f16(int epi, const void* gemm_args, hipStream_t stream);
@@ -476,6 +482,9 @@ __attribute__((weak)) int sat_launch_attention_f32_causal(const float* q, const 
 // neighbourhood self-attention in fp32, 64-channel heads; the scores are multiplied by score_scale (the plan passes 1).  WEAK as above
 __attribute__((weak)) int sat_launch_attention_f32_window(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh, int s_len,
                                                           int kernel_size, float score_scale, hipStream_t s);
+// the same for head_dim 32 / 96 (attention_hdw_window.hip).  WEAK as above
+__attribute__((weak)) int sat_launch_attention_f32_window_w(const float* q, const float* k, const float* v, float* out, int b, int h, int kvh,
+                                                            int head_dim, int s_len, int kernel_size, float score_scale, hipStream_t s);
 int sat_launch_cast_bf16(const float* x, op_t* y, int64_t n, hipStream_t s, int f16 = 0);
 int sat_launch_pack_rows_bf16(const float* w, op_t* out, int n, int k, int swiglu_interleave, hipStream_t s, int f16 = 0);
 int sat_launch_pack_bias(const float* b, float* out, int n, int swiglu_interleave, hipStream_t s);

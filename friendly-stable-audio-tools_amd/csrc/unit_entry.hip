@@ -307,6 +307,21 @@ extern "C" int sat_attention_f32_window(const float* q, const float* k, const fl
                                         int32_t kernel_size, float score_scale, sat_stream_t stream) {
     return sat_launch_attention_f32_window(q, k, v, out, b, h, kvh, s, kernel_size, score_scale, (hipStream_t)stream);
 }
+// the same at 32-, 96- and 128-channel heads (sat_dit_plan_set_neighborhood_attention_hdw): q arrives in the log2 domain, there is no scale
+extern "C" int sat_attention_hdw_window_bf16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
+                                             int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, sat_stream_t stream) {
+    return sat_launch_attention_hdw_window((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, head_dim, s, s_pad_q, s_pad_k,
+                                           kernel_size, (hipStream_t)stream, 0);
+}
+extern "C" int sat_attention_hdw_window_f16(const void* q, const void* k, const void* vt, void* out, int32_t b, int32_t h, int32_t kvh,
+                                            int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, sat_stream_t stream) {
+    return sat_launch_attention_hdw_window((const op_t*)q, (const op_t*)k, (const op_t*)vt, (op_t*)out, b, h, kvh, head_dim, s, s_pad_q, s_pad_k,
+                                           kernel_size, (hipStream_t)stream, 1);
+}
+extern "C" int sat_attention_f32_window_w(const float* q, const float* k, const float* v, float* out, int32_t b, int32_t h, int32_t kvh,
+                                          int32_t head_dim, int32_t s, int32_t kernel_size, float score_scale, sat_stream_t stream) {
+    return sat_launch_attention_f32_window_w(q, k, v, out, b, h, kvh, head_dim, s, kernel_size, score_scale, (hipStream_t)stream);
+}
 
 // qkn: q and k L2-normalised per head (qk_norm), q pre-scaled for the attention kernel as in the plan
 static int qkv_rope_bf16_impl(int f16, const void* a, const void* w, const float* inv_freq, void* q, void* k, void* vt,

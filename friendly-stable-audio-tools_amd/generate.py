@@ -89,6 +89,11 @@ def get_args():
                    help="build extension: the model config's DiT has attn_kwargs natten_kernel_size (every self-attention sees a neighbourhood "
                         "of that many rows), which the constructor refuses without an opt-in: sets \"allow_natten\": true in "
                         "model.diffusion.config before the model is built (with --model-config or the built-in config; an error with --model-name)")
+    p.add_argument("--allow-natten-head-widths", action="store_true",
+                   help="build extension: the model config's DiT has attn_kwargs natten_kernel_size on attention heads of 128, 32 or 96 "
+                        "channels, which the constructor refuses without an opt-in of its own next to --allow-natten (and --allow-head-widths for "
+                        "32 / 96): sets \"allow_natten_head_widths\": true in model.diffusion.config before the model is built (with "
+                        "--model-config or the built-in config; an error with --model-name)")
     p.add_argument("--check-fp16-range", action="store_true",
                    help="build extension, for a checkpoint this build was never run on: before generating, run the first batch once for 8 "
                         "steps with the activation range reports of the DiT and the codec on and print how close their 16-bit buffers come "
@@ -108,6 +113,9 @@ def get_args():
                 "--model-name (a pretrained model is built from its own config)")
     if args.allow_natten and args.model_name:
         p.error("--allow-natten is written into the model config before the model is built: it goes with --model-config, not with "
+                "--model-name (a pretrained model is built from its own config)")
+    if args.allow_natten_head_widths and args.model_name:
+        p.error("--allow-natten-head-widths is written into the model config before the model is built: it goes with --model-config, not with "
                 "--model-name (a pretrained model is built from its own config)")
     if args.codec_allow_antialias and args.model_name:
         p.error("--codec-allow-antialias is written into the model config before the model is built: it goes with --model-config, not with "
@@ -138,6 +146,8 @@ def apply_config_flags(args, model_config):
         model_config["model"]["diffusion"]["config"]["allow_causal"] = True
     if args.allow_natten:
         model_config["model"]["diffusion"]["config"]["allow_natten"] = True
+    if args.allow_natten_head_widths:
+        model_config["model"]["diffusion"]["config"]["allow_natten_head_widths"] = True
     if args.codec_allow_antialias:
         allow_codec_antialias(model_config)
     return model_config

@@ -131,6 +131,7 @@ _SIGNATURES = {
     "sat_dit_plan_set_patch": (c_int32, [c_void_p, POINTER(SatDitPatchOptions), c_size_t]),
     "sat_dit_plan_set_attention_options": (c_int32, [c_void_p, POINTER(SatDitAttentionOptions), c_size_t]),
     "sat_dit_plan_set_neighborhood_attention": (c_int32, [c_void_p, POINTER(SatDitNeighborhoodOptions), c_size_t]),
+    "sat_dit_plan_set_neighborhood_attention_hdw": (c_int32, [c_void_p, POINTER(SatDitNeighborhoodOptions), c_size_t]),
     "sat_dit_prepare_extra_conditioning": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "sat_dit_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "sat_dit_denoise_cfg": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int32, c_int32, c_void_p,
@@ -205,6 +206,8 @@ _SIGNATURES = {
     "sat_attention_causal_bf16": (c_int32, [c_void_p] * 4 + [c_int32] * 8 + [c_void_p]),
     # neighbourhood self-attention alone: (q, k, vt, out, b, h, kvh, s, s_pad_q, s_pad_k, kernel_size, score_scale, stream)
     "sat_attention_window_bf16": (c_int32, [c_void_p] * 4 + [c_int32] * 7 + [c_float, c_void_p]),
+    # the same at head_dim 32 / 96 / 128: (q, k, vt, out, b, h, kvh, head_dim, s, s_pad_q, s_pad_k, kernel_size, stream)
+    "sat_attention_hdw_window_bf16": (c_int32, [c_void_p] * 4 + [c_int32] * 8 + [c_void_p]),
     "sat_qkv_rope_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                     c_int32, c_int32, c_int32, c_void_p]),
     "sat_qkv_rope_qknorm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
@@ -249,6 +252,7 @@ _SIGNATURES = {
     "sat_attention_f32_hdw": (c_int32, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p]),
     "sat_attention_f32_causal": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_void_p]),
     "sat_attention_f32_window": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_float, c_void_p]),
+    "sat_attention_f32_window_w": (c_int32, [c_void_p] * 4 + [c_int32] * 6 + [c_float, c_void_p]),
     "sat_enc_attention": (c_int32, [c_void_p] * 4 + [c_int32] * 4 + [c_float, c_void_p]),
     "sat_t5_embed": (c_int32, [c_void_p] * 3 + [c_int32] * 3 + [c_void_p]),
     "sat_t5_rmsnorm": (c_int32, [c_void_p] * 3 + [c_int32, c_int32, c_float, c_void_p]),
@@ -271,7 +275,7 @@ _SIGNATURES = {
 }
 
 # the same unit-level entry points on IEEE fp16 operands (gemm_dtype = 3): identical signatures
-for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_attention_hd128_bf16", "sat_head_split_hd128_bf16", "sat_attention_hdw_bf16", "sat_head_split_hdw_bf16", "sat_attention_causal_bf16", "sat_attention_window_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws", "sat_range_stats_bf16", "sat_dwconv_ln_silu_bf16", "sat_gemm_act_bf16"):
+for _n in ("sat_layernorm_bf16", "sat_cast_bf16", "sat_gemm_bf16_f32", "sat_gemm_swiglu_bf16", "sat_attention_bf16", "sat_cross_attention_fused_bf16", "sat_attention_prescaled_bf16", "sat_attention_hd128_bf16", "sat_head_split_hd128_bf16", "sat_attention_hdw_bf16", "sat_head_split_hdw_bf16", "sat_attention_causal_bf16", "sat_attention_window_bf16", "sat_attention_hdw_window_bf16", "sat_qkv_rope_bf16", "sat_qkv_rope_qknorm_bf16", "sat_gemm_resid_ln_bf16", "sat_gemm_swiglu_ln_bf16", "sat_qkv_rope_ln_bf16", "sat_gemm_bf16_f32_ws", "sat_gemm_resid_ln_bf16_ws", "sat_range_stats_bf16", "sat_dwconv_ln_silu_bf16", "sat_gemm_act_bf16"):
     _SIGNATURES[_n.replace("bf16", "f16")] = _SIGNATURES[_n]
 
 _lib = None

@@ -34,6 +34,7 @@ class DiTWrapper(ConditionedDiffusionModel):
         # ... nor are 32- / 96-channel attention heads: "allow_head_widths": true, likewise
         # ... nor is causal=True: "allow_causal": true, likewise
         # ... nor is attn_kwargs natten_kernel_size: "allow_natten": true, likewise
+        # ... nor is it off 64-channel heads: "allow_natten_head_widths": true next to it, likewise
         self.model = DiffusionTransformer(*args, **kwargs)
         from . import _init
         if not _init._SKIP:

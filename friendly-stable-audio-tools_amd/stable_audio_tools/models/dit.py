@@ -36,7 +36,7 @@ class DiffusionTransformer(nn.Module):
                  input_concat_dim: int = 0, prepend_cond_dim: int = 0, depth: int = 12, num_heads: int = 8,
                  transformer_type: str = "x-transformers", global_cond_type: str = "prepend", max_seq_len: int = 8192,
                  allow_block_options: bool = False, allow_conv_ff: bool = False, allow_patch_size: bool = False, allow_head_widths: bool = False,
-                 allow_causal: bool = False, allow_natten: bool = False, **kwargs):
+                 allow_causal: bool = False, allow_natten: bool = False, allow_natten_head_widths: bool = False, **kwargs):
         """``allow_block_options``: the TransformerBlock options ``conformer``, ``remove_norms`` and ``ff_kwargs={"glu": False}`` are off the
         shipped configs' path and refused unless this is set; ``create_model_from_config`` and every other config-driven path set it.
         ``allow_conv_ff``: likewise for ``ff_kwargs={"use_conv": True}`` (``sat_dit_plan_set_ff_conv``); no path sets it by default, a config
@@ -55,7 +55,12 @@ class DiffusionTransformer(nn.Module):
         n rows ``[prepend rows | global token | tokens]`` attends to the K rows from ``min(max(i - K // 2, 0), n - K)`` on, and the logits
         are not scaled by ``dim_heads ** -0.5`` (the reference hands q to NATTEN as it is); a config asks for it with
         ``"allow_natten": true``.  K is odd and greater than 1 and no sequence may be shorter than K (``ValueError``).  Such a model has
-        64-channel heads and no cross-attention, is not causal, and runs with 'fp16', 'bf16' (also per block) and 'fp32x' operands."""
+        64-channel heads and no cross-attention, is not causal, and runs with 'fp16', 'bf16' (also per block) and 'fp32x' operands.
+        ``allow_natten_head_widths``: next to ``allow_natten`` (and to ``allow_head_widths`` for 32 / 96), the same neighbourhood at 128-,
+        32- and 96-channel heads (``sat_dit_plan_set_neighborhood_attention_hdw``); a config asks for it with
+        ``"allow_natten_head_widths": true``.  Such a model runs with 'fp16' and 'bf16' (also per block) operands and, at 32 and 96,
+        'fp32x'; what the staged widths are refused without the window they are refused with it ('fp8', 'fp32x' at 128, the block options
+        and ``use_conv``), and cross-attention and ``causal`` stay refused as at 64."""
         super().__init__()
         if transformer_type != "continuous_transformer":
             raise NotImplementedError("only transformer_type='continuous_transformer' is implemented (the shipped DiT configs)")
@@ -89,6 +94,7 @@ class DiffusionTransformer(nn.Module):
         self.max_prepend_len = 64 if prepend_cond_dim > 0 else 0     # grows (plan rebuild) when a generation brings more tokens
         self.max_seq_len = max_seq_len
         self.allow_head_widths = bool(allow_head_widths)
+        self.allow_natten_head_widths = bool(allow_natten_head_widths)
         self.transformer_type = transformer_type
         self.global_cond_type = global_cond_type
 
@@ -115,7 +121,7 @@ class DiffusionTransformer(nn.Module):
                                                  global_cond_dim=embed_dim if global_cond_type == "adaLN" else None,
                                                  allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff,
                                                  allow_head_widths=allow_head_widths, allow_causal=allow_causal,
-                                                 allow_natten=allow_natten, **kwargs)
+                                                 allow_natten=allow_natten, allow_natten_head_widths=allow_natten_head_widths, **kwargs)
         self.preprocess_conv = _init.conv1d(dim_in, dim_in, 1, bias=False, zero=True)
         self.postprocess_conv = _init.conv1d(io_channels, io_channels, 1, bias=False, zero=True)
 
@@ -388,7 +394,10 @@ class DiffusionTransformer(nn.Module):
                 _hip.check(lib.sat_dit_plan_set_attention_options(plan, ctypes.byref(aopts), ctypes.sizeof(aopts)))
             if options[10]:       # natten_kernel_size; likewise
                 nopts = _hip.SatDitNeighborhoodOptions(options[10])
-                _hip.check(lib.sat_dit_plan_set_neighborhood_attention(plan, ctypes.byref(nopts), ctypes.sizeof(nopts)))
+                # only a model that opted in and has staged heads calls the entry that takes them
+                hdw = self.allow_natten_head_widths and self.transformer.dim_heads != 64
+                setter = lib.sat_dit_plan_set_neighborhood_attention_hdw if hdw else lib.sat_dit_plan_set_neighborhood_attention
+                _hip.check(setter(plan, ctypes.byref(nopts), ctypes.sizeof(nopts)))
             if self._block_gemm_dtypes is not None:       # a model that never set them never makes the call
                 fm = (ctypes.c_int32 * self.depth)(*[GEMM_DTYPES[f] for f in self._block_gemm_dtypes])
                 _hip.check(lib.sat_dit_plan_set_block_formats(plan, fm, self.depth))

@@ -4,7 +4,7 @@ Mirror of the module tree of the reference's ``models/transformer.py`` (``LayerN
 ``GLU``/``FeedForward`` :211-287, ``Attention`` :290-554, ``TransformerBlock`` :594-702,
 ``RotaryEmbedding`` :99-155, ``AbsolutePositionalEmbedding`` / ``ScaledSinusoidalEmbedding`` :50-96,
 ``ContinuousTransformer`` :705-809) restricted to the options the HIP plan runs: those of the shipped DiT
-configs plus causal self-attention (behind ``allow_causal``), neighbourhood self-attention (``natten_kernel_size``, behind ``allow_natten``), 128-channel heads (and, behind ``allow_head_widths``, 32- and 96-channel ones), ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False``,
+configs plus causal self-attention (behind ``allow_causal``), neighbourhood self-attention (``natten_kernel_size``, behind ``allow_natten``; off 64-channel heads also behind ``allow_natten_head_widths``), 128-channel heads (and, behind ``allow_head_widths``, 32- and 96-channel ones), ``qk_norm``, the sinusoidal / absolute position embeddings, ``rotary_pos_emb=False``,
 bias-free / ``mult``-sized feed-forwards and, behind the ``allow_block_options`` opt-in, ``conformer`` (:557-591), ``remove_norms``
 and feed-forwards without GLU, and behind ``allow_conv_ff`` convolutional feed-forwards (``ff_kwargs use_conv``).  These classes only *hold* parameters under the reference's
 names; the forward pass of the whole stack is one C-ABI call (``sat_dit_forward`` /
@@ -84,6 +84,12 @@ NATTEN_HINT = ("pass allow_natten=True to DiffusionTransformer, or write \"allow
                "(sat_dit_plan_set_neighborhood_attention)")
 
 
+NATTEN_HEAD_WIDTHS_HINT = ("pass allow_natten_head_widths=True to DiffusionTransformer, or write \"allow_natten_head_widths\": true into the model "
+                           "config's model.diffusion.config (generate.py --allow-natten-head-widths does), next to allow_natten (and to "
+                           "allow_head_widths for 32 / 96): the neighbourhood then runs at 128-, 32- and 96-channel heads on the HIP plan "
+                           "(sat_dit_plan_set_neighborhood_attention_hdw)")
+
+
 class FeedForward(nn.Module):
     def __init__(self, dim, mult=4, glu=True, no_bias=False, use_conv=False, conv_kernel_size=3, zero_init_output=True, allow_block_options=False,
                  allow_conv_ff=False, **unsupported):
@@ -124,7 +130,7 @@ class FeedForward(nn.Module):
 
 class Attention(nn.Module):
     def __init__(self, dim, dim_heads=64, dim_context=None, causal=False, zero_init_output=True, qk_norm=False, natten_kernel_size=None,
-                 allow_head_widths=False, allow_causal=False, allow_natten=False, **unsupported):
+                 allow_head_widths=False, allow_causal=False, allow_natten=False, allow_natten_head_widths=False, **unsupported):
         super().__init__()
         if (natten_kernel_size is not None and not allow_natten) or unsupported:
             raise NotImplementedError("Attention options not supported by the HIP path (full attention, non-causal or behind allow_causal causal; "
@@ -143,9 +149,9 @@ class Attention(nn.Module):
             if causal:
                 raise NotImplementedError(f"natten_kernel_size={k} with causal=True: the reference silently ignores causal in its NATTEN branch "
                                           "(transformer.py:479-493); drop one of the two")
-            if dim_heads != 64:
+            if dim_heads != 64 and not allow_natten_head_widths:
                 raise NotImplementedError(f"natten_kernel_size={k} with dim_heads={dim_heads}: the neighbourhood kernels are built for 64-channel "
-                                          "heads; the staged widths (128, 32, 96) are a follow-up")
+                                          f"heads; the staged widths (128, 32, 96) are a follow-up behind an opt-in: {NATTEN_HEAD_WIDTHS_HINT}")
         if causal and not allow_causal:
             raise NotImplementedError(f"causal={causal} is behind an opt-in: {CAUSAL_HINT}")
         if causal and dim_context:
@@ -198,7 +204,7 @@ class TransformerBlock(nn.Module):
     def __init__(self, dim, dim_heads=64, cross_attend=False, dim_context=None, global_cond_dim=None, causal=False,
                  zero_init_branch_outputs=True, conformer=False, layer_ix=-1, remove_norms=False, attn_kwargs={}, ff_kwargs={},
                  norm_kwargs={}, allow_block_options=False, allow_conv_ff=False, allow_head_widths=False, allow_causal=False,
-                 allow_natten=False):
+                 allow_natten=False, allow_natten_head_widths=False):
         super().__init__()
         if (conformer or remove_norms) and not allow_block_options:
             raise NotImplementedError(f"conformer={conformer} / remove_norms={remove_norms} are off the shipped configs' path: {BLOCK_OPTIONS_HINT}")
@@ -215,12 +221,13 @@ class TransformerBlock(nn.Module):
         norm = (lambda: nn.Identity()) if remove_norms else (lambda: LayerNorm(dim, **norm_kwargs))      # reference :621,632,642
         self.pre_norm = norm()
         self.self_attn = Attention(dim, dim_heads=dim_heads, causal=causal, zero_init_output=zero_init_branch_outputs,
-                                   allow_head_widths=allow_head_widths, allow_causal=allow_causal, allow_natten=allow_natten, **attn_kwargs)
+                                   allow_head_widths=allow_head_widths, allow_causal=allow_causal, allow_natten=allow_natten,
+                                   allow_natten_head_widths=allow_natten_head_widths, **attn_kwargs)
         if cross_attend:
             self.cross_attend_norm = norm()
             self.cross_attn = Attention(dim, dim_heads=dim_heads, dim_context=dim_context, causal=causal,
                                         zero_init_output=zero_init_branch_outputs, allow_head_widths=allow_head_widths, allow_causal=allow_causal,
-                                        allow_natten=allow_natten, **attn_kwargs)
+                                        allow_natten=allow_natten, allow_natten_head_widths=allow_natten_head_widths, **attn_kwargs)
         self.ff_norm = norm()
         self.ff = FeedForward(dim, zero_init_output=zero_init_branch_outputs, allow_block_options=allow_block_options, allow_conv_ff=allow_conv_ff,
                               **ff_kwargs)
@@ -258,7 +265,7 @@ class ContinuousTransformer(nn.Module):
         ])
         # one attn_kwargs for every block and both attentions of it: the plan takes a single flag
         self.qk_norm = bool(kwargs.get("attn_kwargs", {}).get("qk_norm", False))
-        # one window for every block (sat_dit_plan_set_neighborhood_attention); 0 = full attention
+        # one window for every block (sat_dit_plan_set_neighborhood_attention, or its _hdw twin off 64-channel heads); 0 = full attention
         self.natten_kernel_size = self.layers[0].self_attn.natten_kernel_size if depth else 0
         # likewise one conformer / remove_norms / glu for every block (sat_dit_plan_set_block_options)
         self.block_options = (1 if conformer else 0, 1 if kwargs.get("remove_norms", False) else 0,

@@ -56,7 +56,7 @@ const char* sat_last_error(void);
  * Supported set: transformer_type "continuous_transformer", global_cond_type "prepend"
  * or "adaLN", dim_heads 64 or 128, patch_size 1 or, through sat_dit_plan_set_patch, above,
  * non-causal or, through sat_dit_plan_set_attention_options, causal self-attention without cross-attention, or, through
- * sat_dit_plan_set_neighborhood_attention, NATTEN's 1-D neighbourhood (natten_kernel_size; 64-channel heads, no cross-attention), no masks (the reference discards
+ * sat_dit_plan_set_neighborhood_attention, NATTEN's 1-D neighbourhood (natten_kernel_size; no cross-attention; sat_dit_plan_set_neighborhood_attention_hdw off 64-channel heads), no masks (the reference discards
  * them at inference: models/dit.py:250-252; prepend_cond_mask never reaches the layers,
  * models/transformer.py:787-802).  Input-concat and prepend conditioning (dit.py:160-197)
  * through sat_dit_plan_set_extra_conditioning / sat_dit_prepare_extra_conditioning; prepend
@@ -314,6 +314,11 @@ typedef struct sat_dit_neighborhood_options {
     int32_t kernel_size;    /* "natten_kernel_size"; 0 = full attention */
 } sat_dit_neighborhood_options;
 int sat_dit_plan_set_neighborhood_attention(sat_dit_plan* plan, const sat_dit_neighborhood_options* options, size_t options_bytes);
+/* The same call for every built head width: dim_heads 64 as above, and 128, 32 and 96 (the staged route; csrc/attention_hdw_window.hip), in
+ * bf16 / fp16 / per-block formats and, for 32 and 96, SAT_GEMM_FP32X.  Same struct, same checks and codes; SAT_E_UNSUPPORTED with a reason
+ * if the library was built without those kernels.  What a staged plan is refused elsewhere stays refused: SAT_GEMM_FP32X at 128, the block
+ * options and ff_conv off 64-channel heads.  sat_dit_plan_set_neighborhood_attention itself keeps refusing the staged widths. */
+int sat_dit_plan_set_neighborhood_attention_hdw(sat_dit_plan* plan, const sat_dit_neighborhood_options* options, size_t options_bytes);
 
 /* Operand format per block, between create and finalize: formats[l] is SAT_GEMM_FP16 or SAT_GEMM_BF16 for block l, n == depth.  A plan never
  * given this call, or given gemm_dtype in every entry, runs every block in gemm_dtype and builds and launches exactly what it did before this
@@ -739,6 +744,11 @@ int sat_attention_causal_bf16(const void* q_dev, const void* k_dev, const void* 
  * finite number. */
 int sat_attention_window_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
                               int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, float score_scale, sat_stream_t stream);
+/* The same at head_dim 32, 96 or 128 (sat_dit_plan_set_neighborhood_attention_hdw), test-only.  Layouts and pad rules of sat_attention_hdw_bf16
+ * (s_pad_k a multiple of 128 at head_dim 32, of 64 otherwise); there is no scale: score = q . k in the log2 domain, so the caller hands in q
+ * times log2(e) times whatever factor it wants.  Any other head_dim is SAT_E_UNSUPPORTED. */
+int sat_attention_hdw_window_bf16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
+                                  int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, sat_stream_t stream);
 /* Cross-attention query projection and attention core in one launch (models/transformer.py:430-437 + 496-536; what the DiT plan
  * runs per layer while the 128 x 64 GEMM tiles of the projection fit one round of workgroups, i.e. at one prompt):
  * out [b*s, d] bf16 = softmax((a wq^T) k^T / 8) v per head of 64, a [b*s, d] bf16, wq [d, d] bf16, k / vt in the key-side layout of
@@ -819,6 +829,8 @@ int sat_attention_causal_f16(const void* q_dev, const void* k_dev, const void* v
                              int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t prescaled, sat_stream_t stream);
 int sat_attention_window_f16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
                              int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, float score_scale, sat_stream_t stream);
+int sat_attention_hdw_window_f16(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int32_t b, int32_t h, int32_t kvh,
+                                 int32_t head_dim, int32_t s, int32_t s_pad_q, int32_t s_pad_k, int32_t kernel_size, sat_stream_t stream);
 int sat_cross_attention_fused_f16(const void* a_f16_dev, const void* wq_f16_dev, const void* k_dev, const void* vt_dev, void* out_dev,
                                   int32_t b, int32_t s, int32_t d, int32_t kvh, int32_t sk, int32_t sk_pad, sat_stream_t stream);
 int sat_qkv_rope_f16(const void* a_f16_dev, const void* w_f16_dev, const float* inv_freq_dev,
@@ -1014,6 +1026,9 @@ int sat_attention_f32_causal(const float* q_dev, const float* k_dev, const float
  * score_scale: q [b,h,s,64], k / v [b,kvh,s,64] -> out [b*s, h*64] */
 int sat_attention_f32_window(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
                              int32_t s, int32_t kernel_size, float score_scale, sat_stream_t stream);
+/* The same for head_dim 32 or 96 (any other is SAT_E_UNSUPPORTED): q [b,h,s,head_dim], k / v [b,kvh,s,head_dim] -> out [b*s, h*head_dim] */
+int sat_attention_f32_window_w(const float* q_dev, const float* k_dev, const float* v_dev, float* out_dev, int32_t b, int32_t h, int32_t kvh,
+                               int32_t head_dim, int32_t s, int32_t kernel_size, float score_scale, sat_stream_t stream);
 /* Self-attention of the text encoders: qkv [b * l, 3 * h * dkv] (q | k | v) -> out [b * l, h * dkv] = softmax(scale * q k^T + pb + mask) v;
  * pb [h, 2l - 1] indexed by key - query + l - 1, or NULL; keys with mask [b, l] == 0 get finfo(float32).min added (an all-padding row is the
  * uniform average over all l keys).  l <= 512, dkv % 4 == 0, (dkv + l) * 4 bytes of LDS <= 64 KiB. */
