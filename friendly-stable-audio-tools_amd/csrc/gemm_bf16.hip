@@ -501,10 +501,35 @@ __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& g, f32x16 (&acc)
 // ---------------------------------------------------------------------------------------------
 // PRE: the residual values were loaded at kernel start (`pre`, MI == 1 only): their HBM / L2 latency is then hidden behind
 // the whole K loop instead of sitting between the last MFMA and the first store.
-template <int MI, bool PRE = false>
-__device__ __forceinline__ void gemm_epilogue_f32_staged(const GemmArgs& g, f32x16 (&acc)[MI][2], float* ep, const int mw, const int nw,
-                                                         const int lane, const f32x4* pre = nullptr) {
+// The accumulators of the 32 x 64 row block i of a wave tile -> the wave's staging block ([32][64] floats), for the two MFMA shapes of
+// the ring tiles.  32 x 32 x 16: lane = column l & 31 of column block j, register r = row (r & 3) + 8 (r >> 2) + 4 (l >> 5).
+template <int MI>
+__device__ __forceinline__ void stage_rows32(float* ep, const f32x16 (&acc)[MI][2], const int i, const int lane) {
     const int half = lane >> 5, l31 = lane & 31;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ep[((r & 3) + 8 * (r >> 2) + 4 * half) * 64 + j * 32 + l31] = acc[i][j][r];
+}
+// 16 x 16 x 32 (un-swapped: the activation rows are the MFMA's A operand), blocks [2 i + rb][cb]: lane = column l & 15 of column block
+// cb, register r = row 4 (l >> 4) + r of row block rb.  As many dword stores as above.  (Swapped operands would give one 16-byte store
+// per block, but a 16-byte store is served in groups of 8 consecutive lanes and those would hold 8 rows of one column, 256 bytes
+// apart: an 8-way bank conflict.  Here lanes l and l + 16 of a 32-lane group share a bank, 2-way, which is the 4 cycles the store's
+// register transfer takes anyway.)
+template <int MB>
+__device__ __forceinline__ void stage_rows32(float* ep, const f32x4 (&acc)[MB][4], const int i, const int lane) {
+    const int l15 = lane & 15, q = lane >> 4;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ep[(rb * 16 + 4 * q + r) * 64 + cb * 16 + l15] = acc[2 * i + rb][cb][r];
+}
+
+template <int MI, bool PRE = false, typename Acc>
+__device__ __forceinline__ void gemm_epilogue_f32_staged(const GemmArgs& g, Acc& acc, float* ep, const int mw, const int nw,
+                                                         const int lane, const f32x4* pre = nullptr) {
     const int M = g.M;
     const int prow = lane >> 4;            // row of this lane inside a 4-row pass
     const int c4 = (lane & 15) * 4;        // first of its 4 columns
@@ -512,10 +537,7 @@ __device__ __forceinline__ void gemm_epilogue_f32_staged(const GemmArgs& g, f32x
     const f32x4 bia = g.bias ? *reinterpret_cast<const f32x4*>(g.bias + nw + c4) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) ep[((r & 3) + 8 * (r >> 2) + 4 * half) * 64 + j * 32 + l31] = acc[i][j][r];
+        stage_rows32(ep, acc, i, lane);
 #pragma unroll
         for (int grp = 0; grp < 2; ++grp) {     // two batches of four passes: 16 registers of residual values in flight
             f32x4 old[4];
@@ -813,6 +835,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs g) {
 //   iteration k:  wait(tile k landed) ; barrier ; issue tile k+NS-1 -> stage (k-1)%NS ; compute k
 // BK = 64 (128-B rows, 8 chunks) or 32 (64-B rows, 4 chunks; swizzle c ^ ((row>>2)&3)).
 // ---------------------------------------------------------------------------------------------
+// -DSAT_RING_MFMA_32X32: every ring tile on the 32 x 32 x 16 MFMA (A/B builds only; see S16 in gemm_pipe_kernel)
+#ifdef SAT_RING_MFMA_32X32
+constexpr bool SAT_RING_MFMA_16 = false;
+#else
+constexpr bool SAT_RING_MFMA_16 = true;
+#endif
+
 template <int BK>
 __device__ __forceinline__ int lds_off_bk(int row, int chunk) {
     if constexpr (BK == 128) return row * 256 + ((chunk ^ (row & 15)) << 4);      // 256-B rows: 16 chunks, XOR with the row
@@ -848,6 +877,15 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     constexpr int NT = KG * WM * WN * 64;
     constexpr int TM = BM / WM;
     constexpr int TN = BN / WN;
+    // MFMA shape: the 8-wave fp32-output tiles with 16-bit operands (15, 44, 49) run v_mfma_f32_16x16x32 into 16 x 16 blocks (acc16),
+    // every other build v_mfma_f32_32x32x16 (acc).  Same LDS image, fragment bytes, matrix-pipe cycles per k and bit-identical sums;
+    // under the socket's power cap the smaller shape is the faster one on random data: FF-out 56.7 -> 50.4 us on tile 15, 53.3 -> 50.7
+    // on tile 49, to_out 20.5 -> 19.8 (profiles/ring_mfma_shape_timing.txt).  Only the staged fp32 epilogue is shape-agnostic behind
+    // its first line (stage_rows32).  The 4-wave tile 16 measured 1.5-2 % slower at its own shape (cross to_out, 14.55 -> 14.8 us) in
+    // three interleaves of its reads and DMA pieces and keeps the old shape; the 16-wave tile has no room for two sets of the twice as
+    // many fragments.
+    constexpr bool S16 = SAT_RING_MFMA_16 && EPI == EPI_F32 && FP8 == 0 && NT == 512;
+    static_assert(!S16 || BK == 64, "16 x 16 x 32 fragments: two 32-k steps per 128-byte row");
     // the fused epilogues need a whole head / a value-gate pair per wave, the staged fp32 epilogue a 64-column block
     static_assert(TN == 64, "wave tile is TM x 64");
     constexpr int MI = TM / 32;
@@ -871,7 +909,9 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     constexpr int D = NS - 1;                      // prefetch distance
     constexpr bool DIL_ON = (DIL || KG == 2) && FP8 == 0;
     constexpr int NDIL = !DIL_ON ? 0 : UNIFORM ? LPT : LPT - 1;          // pieces EVERY wave issues in the loop body (a ragged tile's extra piece stays in front)
-    constexpr int DIL_STEPS = KG == 2 ? BK / 32 : BK / 16 - 1;            // k-steps that carry them (K-groups: the half in front of the mid-iteration barrier)
+    // k-steps that carry them (K-groups: the half in front of the mid-iteration barrier, which is one 32-k step of the 16 x 16 x 32 loop)
+    constexpr int DIL_STEPS = KG == 2 ? (S16 ? 1 : BK / 32) : BK / 16 - 1;
+    static_assert(!S16 || KG == 2 || !DIL_ON, "16 x 16 x 32, one K-group: the LDS-DMA pieces are issued in front of compute()");
     constexpr int DIL_PER = (NDIL + DIL_STEPS - 1) / (DIL_STEPS > 0 ? DIL_STEPS : 1);
     static_assert(!MXA || D == 1 || UNIFORM, "MXFP8: counted waits are built for uniform tiles or 2-stage rings");
     static_assert((BM * CPR) % 64 == 0 && (BN * CPR) % 64 == 0 && (D - 1) * LPT < 64, "bad pipeline geometry");
@@ -989,6 +1029,13 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
         for (int j = 0; j < NI; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // 16 x 16 x 32 builds (S16): MB 16-row blocks x four 16-column blocks instead (acc is dead there)
+    constexpr int MB = S16 ? TM / 16 : 1;
+    [[maybe_unused]] f32x4 acc16[MB][4];
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto stage_in = [&](int kt, int stage) {
         char* sa = smem + stage * STAGE_BYTES;
 #pragma unroll
@@ -1140,6 +1187,86 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                     __builtin_amdgcn_sched_group_barrier(0x8, 2 * MI * NI - (MI + NI), 0);
                 } else {
                     __builtin_amdgcn_sched_group_barrier(0x8, 2 * MI * NI, 0);
+                }
+            }
+            return;
+        }
+        if constexpr (S16) {
+            // v_mfma_f32_16x16x32: a step is 32 k = four 16-byte chunks of the row, lane (row l & 15, chunk l >> 4) -- the fragment the
+            // 8-phase kernel reads from the same image (gemm_ph8.hip), conflict-free under the row-pair XOR.  Per step MB + 4 reads feed
+            // 4 MB MFMAs of 16 matrix-pipe cycles: the reads, cycles and registers per k of the 32 x 32 x 16 loop below, in half as many steps.
+            static_assert(!TRc, "16 x 16 x 32: fp32 output, un-swapped");
+            constexpr int KS2 = BK / 32, NR = MB + 4, NM = MB * 4;
+            const int l15 = lane & 15, q = lane >> 4;
+            opx8 af[2][MB], bfr[2][4];
+            auto frag = [&](int ks, int buf) {
+#pragma unroll
+                for (int i = 0; i < MB; ++i)
+                    af[buf][i] = *reinterpret_cast<const opx8*>(sa + lds_off_bk<BK>(wm * TM + i * 16 + l15, ks * 4 + q));
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    bfr[buf][j] = *reinterpret_cast<const opx8*>(sb + lds_off_bk<BK>(wn * TN + j * 16 + l15, ks * 4 + q));
+            };
+            frag(0, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
+#pragma unroll
+            for (int ks = 0; ks < KS2; ++ks) {
+                if (ks + 1 < KS2) frag(ks + 1, (ks + 1) & 1);
+                if constexpr (KG == 2) {          // the iteration's LDS-DMA pieces ride in the MFMA stream of the first step (DIL_STEPS)
+                    if (ks < DIL_STEPS && kt_issue >= 0) {
+                        char* sdst = smem + st_issue * STAGE_BYTES;
+#pragma unroll
+                        for (int i = ks * DIL_PER; i < (ks + 1) * DIL_PER && i < NDIL; ++i)
+                            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ld_ptr[i] + kt_issue * (BK * KG)),
+                                                             (__attribute__((address_space(3))) void*)(sdst + (grp * WLG + i * (WM * WN) + wv) * 1024), 16, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < MB; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc16[i][j] = mfma_16x16x32(af[ks & 1][i], bfr[ks & 1][j], acc16[i][j]);
+                // the pinned interleave, the patterns of the 32 x 32 x 16 loop re-counted in MFMAs of half the length
+                if constexpr (KG == 2) {
+                    if (ks + 1 < KS2) {
+                        // the next step's reads behind the first two MFMAs (the same ~100 cycles of head start), then the iteration's DMA
+                        // pieces two at a time through the rest of the step, which is the half in front of the mid-iteration barrier
+                        // (measured and not kept: one read behind each of the first eight MFMAs, 51.9 us against 50.7 on FF-out; reads
+                        // and pieces together behind the first eight, 54.6)
+                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x100, NR / 2, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x100, NR - NR / 2, 0);
+                        if (DIL_PER == 8 && NM == 16) {
+                            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                                __builtin_amdgcn_sched_group_barrier(0x20, 2, 0);
+                                __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
+                            }
+                            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                        } else {
+                            __builtin_amdgcn_sched_group_barrier(0x8, NM - 2, 0);
+                        }
+                    } else {
+                        __builtin_amdgcn_sched_group_barrier(0x8, NM, 0);
+                    }
+                    if (ks == KS2 / 2 - 1) {          // the OTHER group's iteration boundary (it runs half an iteration out of phase)
+                        __builtin_amdgcn_sched_barrier(0);
+                        __builtin_amdgcn_s_barrier();
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else if (ks + 1 < KS2) {
+                    // one read of the next step's fragments behind each of the first MFMAs
+#pragma unroll
+                    for (int r = 0; r < (NR < NM ? NR : NM); ++r) {
+                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    }
+                    if (NM > NR) __builtin_amdgcn_sched_group_barrier(0x8, NM - NR, 0);
+                    if (NR > NM) __builtin_amdgcn_sched_group_barrier(0x100, NR - NM, 0);
+                } else {
+                    __builtin_amdgcn_sched_group_barrier(0x8, NM, 0);
                 }
             }
             return;
@@ -1434,6 +1561,33 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
         // exchange: group 0 keeps row block 0 of its 64 x 64 wave tile and sends block 1, group 1 the other way round; lane-contiguous
         // dwords, 8 KiB per wave in the first half of the (free) ring, the staged epilogue's areas in the second half
         __builtin_amdgcn_s_barrier();
+        if constexpr (S16) {
+            // the same split by 32-row block, in 16 x 16 blocks: rows 0-31 are acc16[0..1], rows 32-63 acc16[2..3]; lane-contiguous 16 bytes
+            f32x4* mine = reinterpret_cast<f32x4*>(smem) + wave * 512;
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) {
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = grp ? acc16[rb][cb][e] : acc16[2 + rb][cb][e];
+                    mine[(rb * 4 + cb) * 64 + lane] = v;
+                }
+            __syncthreads();
+            const f32x4* theirs = reinterpret_cast<const f32x4*>(smem) + (wave ^ (WM * WN)) * 512;
+            f32x4 fin[2][4];
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int cb = 0; cb < 4; ++cb) {
+                    const f32x4 t = theirs[(rb * 4 + cb) * 64 + lane];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) fin[rb][cb][e] = (grp ? acc16[2 + rb][cb][e] : acc16[rb][cb][e]) + t[e];
+                }
+            if (epi_rows_valid)
+                gemm_epilogue_f32_staged<1, true>(g, fin, reinterpret_cast<float*>(smem + NW * 8192) + wave * 2048, epi_m, n0 + wn * TN, lane, resid);
+            return;
+        }
         float* mine = reinterpret_cast<float*>(smem) + wave * 2048;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -1454,7 +1608,11 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     if constexpr (EPI == EPI_F32) {
         __builtin_amdgcn_s_barrier();       // every wave is done reading the ring: it becomes the staging area
         if (wave_rows_valid) {
-            if constexpr (PRE_RESID)
+            if constexpr (S16 && PRE_RESID)
+                gemm_epilogue_f32_staged<MI, true>(g, acc16, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane, resid);
+            else if constexpr (S16)
+                gemm_epilogue_f32_staged<MI>(g, acc16, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane);
+            else if constexpr (PRE_RESID)
                 gemm_epilogue_f32_staged<MI, true>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane, resid);
             else
                 gemm_epilogue_f32_staged<MI>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane);
