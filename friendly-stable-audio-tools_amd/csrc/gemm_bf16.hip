@@ -493,6 +493,195 @@ __device__ __forceinline__ void gemm_epilogue_t(const GemmArgs& g, f32x16 (&acc)
 }
 
 // ---------------------------------------------------------------------------------------------
+// The two heads epilogues on 16 x 16 accumulator blocks (v_mfma_f32_16x16x32, the 12-wave tile: S16 in gemm_pipe_kernel), acc[i][j] = row
+// block i, column block j of the wave's TM x 64 tile = one head.  The arithmetic and its order per element are those of gemm_epilogue_t /
+// gemm_epilogue above; only which lane and register hold an element differs.
+// ---------------------------------------------------------------------------------------------
+// one dword of blocks j and j + 1 exchanged between the 16-lane rows of the wave (v_permlane16_swap: rows 1 and 3 of `a` against rows 0 and
+// 2 of `b`): afterwards row 0 holds (a of row 0, a of row 1), row 1 (b of row 0, b of row 1), rows 2 and 3 the same of rows 2 and 3
+__device__ __forceinline__ void row16_swap(unsigned& a, unsigned& b) {
+    u32x2 r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = r[0];
+    b = r[1];
+}
+
+// q / k (swapped operands, C^T): lane l & 15 owns TOKEN row m = mw + 16 i + (l & 15), its quarter qt = l >> 4 the channels 16 j + 4 qt + e.
+// The rotation partner d + 16 of d < 16 is block 1 against block 0 in the same registers of the same lane; the table rows of all MB row
+// blocks are fetched up front (8 registers each).  Rows of two sequences meet inside a row block, so position and key offset are per lane.
+template <int MB, bool LNC>
+__device__ __forceinline__ void gemm_heads16_t(const GemmArgs& g, f32x4 (&acc)[MB][4], const int mw, const int nw, const int lane,
+                                               const float2* ln, const float* lc1, const float* lc2) {
+    const int M = g.M;
+    const int l15 = lane & 15, qt = lane >> 4;
+    const HeadsEpi& he = g.heads;
+    const int hp = he.heads * 64;
+    const int part = nw / hp;
+    const int head = (nw - part * hp) >> 6;
+    const int kind = he.kind[part];
+    op_t* __restrict__ dst = he.out[part];
+    const int S = he.S, Spad = he.Spad;
+    [[maybe_unused]] f32x4 rcs[MB], rsn[MB];
+    if (kind & 2) {
+#pragma unroll
+        for (int i = 0; i < MB; ++i) {
+            const int m = mw + i * 16 + l15;
+            const int s = (m < M ? m : M - 1) % S;
+            rcs[i] = *reinterpret_cast<const f32x4*>(he.rope_cos + (size_t)s * 16 + 4 * qt);
+            rsn[i] = *reinterpret_cast<const f32x4*>(he.rope_sin + (size_t)s * 16 + 4 * qt);
+        }
+    }
+    [[maybe_unused]] f32x4 c1[4], c2[4];
+    if constexpr (LNC) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c1[j] = *reinterpret_cast<const f32x4*>(lc1 + j * 16 + 4 * qt);
+            c2[j] = *reinterpret_cast<const f32x4*>(lc2 + j * 16 + 4 * qt);
+        }
+    }
+    // after the exchange a lane's two 16-byte runs are channels 16 (qt & 1) + 8 (qt >> 1) + [0, 8) of blocks 0 | 1 and of blocks 2 | 3
+    // (measured and not kept: no exchange and four 8-byte stores per row block, 36.6 us against 36.3 for to_qkv in fp16, 35.5 against 35.2
+    // in bf16.  Not built: W rows permuted at ld_ptr so that a block pair holds eight consecutive channels without an exchange -- the
+    // rotation partner d + 16 would then sit in another lane quarter.)
+    const int crun = 16 * (qt & 1) + 8 * (qt >> 1);
+#pragma unroll
+    for (int i = 0; i < MB; ++i) {
+        const int m = mw + i * 16 + l15;
+        const int mc = m < M ? m : M - 1;
+        const int b = mc / S;
+        const int s = mc - b * S;
+        const int ob = (kind & 4) ? ((b * S) & 3) : 0;
+        if constexpr (LNC) {         // LayerNorm fold (before the rotation: both are linear, this one is per channel)
+            const float2 st = ln[i * 16 + l15];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[i][j][e] = st.y * (acc[i][j][e] - st.x * c1[j][e]) + c2[j][e];
+        }
+        if (kind & 2) {   // partial RoPE on d < 32
+            // x1 cs - x2 sn and x2 cs + x1 sn, with the roundings spelled out: which product of each sum is fused is the compiler's choice
+            // in gemm_epilogue_t, and it is not the same for all of that epilogue's registers (r = 6, 7, the channels d = 10, 11, 14, 15,
+            // get two products and an addition for the second sum).  The same forms here keep q and k bit-identical between the two MFMA
+            // shapes (-DSAT_RING_MFMA_32X32); without them about one rotated element in 10^4 differs by an ulp.
+#pragma clang fp contract(off)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float cs = rcs[i][e], sn = rsn[i][e];
+                const float x1 = acc[i][0][e], x2 = acc[i][1][e];
+                const float t = x2 * cs;
+                float hi = __builtin_fmaf(x1, sn, t);
+                if (e >= 2) {
+                    const float u = x1 * sn;
+                    hi = qt >= 2 ? t + u : hi;
+                }
+                acc[i][0][e] = __builtin_fmaf(x1, cs, -(x2 * sn));
+                acc[i][1][e] = hi;
+            }
+        }
+        if (kind & 8) {   // query: pre-scaled for the attention kernel (one rounding, here)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[i][j][e] *= he.qscale;
+        }
+        op_t* row = dst + ((size_t)(b * he.heads + head) * Spad + s + ob) * 64 + crun;
+#pragma unroll
+        for (int jp = 0; jp < 2; ++jp) {
+            unsigned a0 = pack_op2(acc[i][2 * jp][0], acc[i][2 * jp][1]), a1 = pack_op2(acc[i][2 * jp][2], acc[i][2 * jp][3]);
+            unsigned b0 = pack_op2(acc[i][2 * jp + 1][0], acc[i][2 * jp + 1][1]), b1 = pack_op2(acc[i][2 * jp + 1][2], acc[i][2 * jp + 1][3]);
+            row16_swap(a0, b0);
+            row16_swap(a1, b1);
+            if (m < M) *reinterpret_cast<u32x4*>(row + jp * 32) = u32x4{a0, a1, b0, b1};
+        }
+    }
+}
+
+// V^T (un-swapped): lane l & 15 owns CHANNEL column 16 j + (l & 15) of block j, its registers the token rows 16 i + 4 (l >> 4) + r: four
+// consecutive tokens = one 8-byte store into the token-contiguous destination, with its key permutation (vt_pos) and key offset, exactly
+// as the 32 x 32 epilogue writes it.  Pads are not touched (the forward's memset owns them).
+template <int MB, bool LNC>
+__device__ __forceinline__ void gemm_heads16_vt(const GemmArgs& g, f32x4 (&acc)[MB][4], const int mw, const int nw, const int lane,
+                                                const float2* ln, const float* lc1, const float* lc2) {
+    const int M = g.M;
+    const int l15 = lane & 15, qt = lane >> 4;
+    const HeadsEpi& he = g.heads;
+    const int hp = he.heads * 64;
+    const int part = nw / hp;
+    const int head = (nw - part * hp) >> 6;
+    const int kind = he.kind[part];
+    op_t* __restrict__ dst = he.out[part];
+    const int S = he.S, Spad = he.Spad;
+    const bool shift = (kind & 4) != 0;
+    [[maybe_unused]] float c1[4], c2[4];
+    if constexpr (LNC) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c1[j] = lc1[j * 16 + l15];
+            c2[j] = lc2[j * 16 + l15];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < MB; ++i) {
+        const int mb = mw + i * 16 + 4 * qt;          // first of 4 consecutive rows, multiple of 4
+        float v[4][4];          // [column block][row]
+        int bb[4], ss[4];
+        f32x4 st01 = {0.f, 1.f, 0.f, 1.f}, st23 = {0.f, 1.f, 0.f, 1.f};      // (mean, rstd) of rows e = 0,1 / 2,3
+        if constexpr (LNC) {
+            const f32x4* sp = reinterpret_cast<const f32x4*>(ln + i * 16 + 4 * qt);
+            st01 = sp[0];
+            st23 = sp[1];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int mm = mb + e;
+            mm = mm < M ? mm : M - 1;
+            bb[e] = mm / S;
+            ss[e] = mm - bb[e] * S;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j][e] = acc[i][j][e];
+                if constexpr (LNC) {
+                    const float mean = e < 2 ? st01[2 * e] : st23[2 * e - 4];
+                    const float rstd = e < 2 ? st01[2 * e + 1] : st23[2 * e - 3];
+                    v[j][e] = rstd * (v[j][e] - mean * c1[j]) + c2[j];
+                }
+            }
+            if (kind & 2) {   // wave-uniform: partial RoPE on d < 32, the partner d + 16 is block 1 of the same lane
+                const float cs = he.rope_cos[ss[e] * 16 + l15], sn = he.rope_sin[ss[e] * 16 + l15];
+                const float x1 = v[0][e], x2 = v[1][e];
+                v[0][e] = x1 * cs - x2 * sn;
+                v[1][e] = x2 * cs + x1 * sn;
+            }
+        }
+        if (mb + 3 < M && bb[0] == bb[3]) {
+            const int ob = shift ? ((bb[0] * S) & 3) : 0;
+            const size_t hbase = ((size_t)(bb[0] * he.heads + head) * 64) * Spad;
+            const size_t base = hbase + vt_pos(ss[0] + ob);         // aligned group of 4 keys: stays a group of 4
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                opx4 p;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) p[e] = f32_to_op(v[j][e]);
+                if (shift) {     // aligned: (ss[0] + ob) % 4 == mb % 4 == 0
+                    *reinterpret_cast<opx4*>(dst + base + (size_t)(j * 16 + l15) * Spad) = p;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dst[hbase + vt_pos(ss[0] + e) + (size_t)(j * 16 + l15) * Spad] = p[e];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (mb + e < M) {
+                    const int ob = shift ? ((bb[e] * S) & 3) : 0;
+                    const size_t base = ((size_t)(bb[e] * he.heads + head) * 64) * Spad + vt_pos(ss[e] + ob);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) dst[base + (size_t)(j * 16 + l15) * Spad] = f32_to_op(v[j][e]);
+                }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // fp32 output / residual epilogue staged through LDS (un-swapped orientation, wave tile TM x 64).  Each wave writes one
 // 32 x 64 fp32 block of its accumulators into a private 8 KiB LDS region (row-major, ds_write_b32: the 32 lanes of a half cover
 // one 128-byte row segment, conflict-free) and reads it back as 16-byte pieces of whole rows, so that the read-modify-write of
@@ -884,7 +1073,11 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     // its first line (stage_rows32).  The 4-wave tile 16 measured 1.5-2 % slower at its own shape (cross to_out, 14.55 -> 14.8 us) in
     // three interleaves of its reads and DMA pieces and keeps the old shape; the 16-wave tile has no room for two sets of the twice as
     // many fragments.
-    constexpr bool S16 = SAT_RING_MFMA_16 && EPI == EPI_F32 && FP8 == 0 && NT == 512;
+    // The 12-wave heads build of tile 30 (one-prompt to_qkv) runs it too, in both orientations (q / k swapped, V^T un-swapped: gemm_heads16_t,
+    // gemm_heads16_vt); its qk_norm, SwiGLU, plain-activation, fp32 and e4m3 builds keep 32 x 32 x 16.  The product call (M = 2050,
+    // d = 1536, LayerNorm fold) went 40.0 -> 36.3 us in fp16 and 38.1 -> 35.2 in bf16, 27 and 10 times the spread of one build, with
+    // q, k and V^T bit-identical (profiles/qkv_mfma_shape_timing.txt); 164 VGPRs of the 168 that three waves per SIMD leave, no scratch.
+    constexpr bool S16 = SAT_RING_MFMA_16 && FP8 == 0 && ((EPI == EPI_F32 && NT == 512) || (EPI == EPI_HEADS && !QKN && NT == 768));
     static_assert(!S16 || BK == 64, "16 x 16 x 32 fragments: two 32-k steps per 128-byte row");
     // the fused epilogues need a whole head / a value-gate pair per wave, the staged fp32 epilogue a 64-column block
     static_assert(TN == 64, "wave tile is TM x 64");
@@ -1195,7 +1388,9 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
             // v_mfma_f32_16x16x32: a step is 32 k = four 16-byte chunks of the row, lane (row l & 15, chunk l >> 4) -- the fragment the
             // 8-phase kernel reads from the same image (gemm_ph8.hip), conflict-free under the row-pair XOR.  Per step MB + 4 reads feed
             // 4 MB MFMAs of 16 matrix-pipe cycles: the reads, cycles and registers per k of the 32 x 32 x 16 loop below, in half as many steps.
-            static_assert(!TRc, "16 x 16 x 32: fp32 output, un-swapped");
+            // TRc (heads, q / k): operands swapped, a block holds C^T -- lane l & 15 owns a token row, quarter l >> 4 four consecutive
+            // channels of each 16-column block (gemm_heads16_t)
+            static_assert(!TRc || EPI == EPI_HEADS, "16 x 16 x 32: fp32 output is un-swapped");
             constexpr int KS2 = BK / 32, NR = MB + 4, NM = MB * 4;
             const int l15 = lane & 15, q = lane >> 4;
             opx8 af[2][MB], bfr[2][4];
@@ -1224,7 +1419,9 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
 #pragma unroll
                 for (int i = 0; i < MB; ++i)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc16[i][j] = mfma_16x16x32(af[ks & 1][i], bfr[ks & 1][j], acc16[i][j]);
+                    for (int j = 0; j < 4; ++j)
+                        acc16[i][j] = TRc ? mfma_16x16x32(bfr[ks & 1][j], af[ks & 1][i], acc16[i][j])
+                                          : mfma_16x16x32(af[ks & 1][i], bfr[ks & 1][j], acc16[i][j]);
                 // the pinned interleave, the patterns of the 32 x 32 x 16 loop re-counted in MFMAs of half the length
                 if constexpr (KG == 2) {
                     if (ks + 1 < KS2) {
@@ -1258,6 +1455,8 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                     }
                 } else if (ks + 1 < KS2) {
                     // one read of the next step's fragments behind each of the first MFMAs
+                    // (measured on the 12-wave heads tile and not kept: two reads behind each of the first four MFMAs, 37.2 us against 36.3
+                    // for to_qkv in fp16, 35.8 against 35.2 in bf16)
 #pragma unroll
                     for (int r = 0; r < (NR < NM ? NR : NM); ++r) {
                         __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
@@ -1396,7 +1595,8 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     int rd = 0;          // stage of tile k
     int wr = D;          // stage that receives tile k+D (== stage of tile k-1)
     // steady state: tiles k+1..k+D-1 stay in flight across the barrier
-    // Orientation (uniform over the workgroup: tiles never straddle a q / k / v part): transposed accumulators everywhere except
+    // Orientation (per wave: a 64-column wave tile never straddles a q / k / v part, a workgroup's 192 columns may -- the two loops pass the
+    // same barriers): transposed accumulators everywhere except
     // for a V^T destination (token-contiguous stores want lane = channel), the MXFP8 A operand and the fp32 output.
     // Measured (profiles/r02_epilogue_ab.txt): bf16 outputs gain 3-4 % (SwiGLU) / 13 % (heads) from the transposed orientation, the
     // fp32 residual epilogue LOSES 6-10 % at 8 prompts (a lane-per-token store instruction touches 32 cache lines; in the legacy
@@ -1616,6 +1816,11 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                 gemm_epilogue_f32_staged<MI, true>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane, resid);
             else
                 gemm_epilogue_f32_staged<MI>(g, acc, reinterpret_cast<float*>(smem) + wave * 2048, m0 + wm * TM, n0 + wn * TN, lane);
+        }
+    } else if constexpr (S16) {
+        if (wave_rows_valid) {
+            if (tr) gemm_heads16_t<MB, LN_CONS>(g, acc16, m0 + wm * TM, n0 + wn * TN, lane, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
+            else gemm_heads16_vt<MB, LN_CONS>(g, acc16, m0 + wm * TM, n0 + wn * TN, lane, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
         }
     } else if (wave_rows_valid) {
         if (tr) gemm_epilogue_t<EPI, MI, NI, LN_CONS, (NT < 1024), QKN>(g, acc, m0 + wm * TM, n0 + wn * TN, half, l31, lnst + wm * TM, lnc + wn * TN, lnc + BN + wn * TN);
