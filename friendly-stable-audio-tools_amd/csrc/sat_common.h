@@ -493,3 +493,8 @@ int sat_launch_pack_bias(const float* b, float* out, int n, int swiglu_interleav
 int sat_launch_pack_rows_ln(const float* w, const float* gamma, const float* beta, const float* bias, op_t* out, float* c1, float* c2,
                             int n, int k, int swiglu_interleave, hipStream_t s, int f16 = 0);
 int sat_launch_rope_table(const float* inv_freq, float* cos_t, float* sin_t, int s_len, hipStream_t s);
+// ---- the audio boundary of the local-attention codec (local_attn_io.hip), fp32 in every build: x [b, c_in, t] channel-first through the bias-free
+// w [d, c_in] into rows [b * t, d] (d % 4 == 0, c_in <= 128: a tile of the input is staged in LDS); rows [b * t, d] through the bias-free
+// w [c_out, d] into out [b, c_out, t] channel-first (d % 64 == 0)
+int sat_launch_local_attn_project_in(const float* x, const float* w, float* rows, int b, int c_in, int t, int d, hipStream_t s);
+int sat_launch_local_attn_project_out(const float* rows, const float* w, float* out, int b, int c_out, int t, int d, hipStream_t s);

@@ -573,3 +573,12 @@ extern "C" int sat_output_proj_patch(const float* X, const float* w_eff_t, float
                                      int32_t d, sat_stream_t stream) {
     return glue_output_proj_patch(X, w_eff_t, out, bf, c, patch_size, t, s_len, d, (hipStream_t)stream);
 }
+
+// ---- the two projections at the audio boundary of the local-attention codec alone (local_attn_io.hip): the launchers sat_local_attn_forward calls
+extern "C" int sat_local_attn_project_in(const float* x, const float* w, float* rows, int32_t b, int32_t c_in, int32_t t, int32_t d, sat_stream_t stream) {
+    return sat_launch_local_attn_project_in(x, w, rows, b, c_in, t, d, (hipStream_t)stream);
+}
+extern "C" int sat_local_attn_project_out(const float* rows, const float* w, float* out, int32_t b, int32_t c_out, int32_t t, int32_t d,
+                                          sat_stream_t stream) {
+    return sat_launch_local_attn_project_out(rows, w, out, b, c_out, t, d, (hipStream_t)stream);
+}

@@ -86,6 +86,16 @@ class SatOobleckOptions(Structure):
 OOBLECK_ACT_SNAKE, OOBLECK_ACT_ELU = 0, 1     # include/sat_hip.h: SAT_OOBLECK_ACT_*
 
 
+LOCAL_ATTN_MAX_STAGES = 16     # include/sat_hip.h: SAT_LOCAL_ATTN_MAX_STAGES
+
+
+class SatLocalAttnCfg(Structure):
+    """include/sat_hip.h: sat_local_attn_cfg (sat_local_attn_plan_create), one encoder or decoder of the local-attention codec."""
+    _fields_ = ([("is_decoder", c_int32), ("in_channels", c_int32), ("out_channels", c_int32), ("n_stages", c_int32)]
+                + [(n, c_int32 * LOCAL_ATTN_MAX_STAGES) for n in ("embed_dims", "heads", "depths", "ratios", "ff_inner")]
+                + [("window", c_int32), ("gemm_dtype", c_int32)])
+
+
 class SatOobleckUnitDesc(Structure):
     """include/sat_hip.h: sat_oobleck_unit_desc, one codec layer on the caller's tensors (``sat_oobleck_unit``, for tests)."""
     _fields_ = ([(n, c_int32) for n in ("kind", "gemm_dtype", "activation", "b", "t_len", "c_in", "c_out", "stride", "dilation", "two_launch",
@@ -172,6 +182,15 @@ _SIGNATURES = {
     "sat_oobleck_range_report_count": (c_int32, [c_void_p, POINTER(c_int32)]),
     "sat_oobleck_range_report_name": (c_char_p, [c_void_p, c_int32]),
     "sat_oobleck_range_report_read": (c_int32, [c_void_p, POINTER(SatRangeRecord), c_int32, c_size_t, c_void_p]),
+    "sat_local_attn_plan_create": (c_int32, [POINTER(SatLocalAttnCfg), c_size_t, POINTER(c_void_p)]),
+    "sat_local_attn_plan_destroy": (None, [c_void_p]),
+    "sat_local_attn_plan_set_tensor": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64]),
+    "sat_local_attn_plan_finalize": (c_int32, [c_void_p, c_void_p]),
+    "sat_local_attn_workspace_bytes": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_size_t)]),
+    "sat_local_attn_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    # the two boundary kernels of the local-attention codec alone: (x, w, rows, b, c_in, t, d, stream) and (rows, w, out, b, c_out, t, d, stream)
+    "sat_local_attn_project_in": (c_int32, [c_void_p] * 3 + [c_int32] * 4 + [c_void_p]),
+    "sat_local_attn_project_out": (c_int32, [c_void_p] * 3 + [c_int32] * 4 + [c_void_p]),
     "sat_vae_sample": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "sat_float_to_int16": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "sat_layernorm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),

@@ -1,4 +1,5 @@
-"""Oobleck encoder/decoder + ``AudioAutoencoder`` on the HIP C ABI.
+"""Oobleck encoder/decoder + ``AudioAutoencoder`` on the HIP C ABI (the local-attention transformer codec, ``"type": "local_attn"``, is
+``models/local_attention.py``; the factories below build either, and an ``AudioAutoencoder`` may mix the two).
 
 Module tree and state-dict keys follow the reference's ``models/autoencoders.py``
 (``ResidualUnit`` :45-68, ``EncoderBlock`` :71-85, ``DecoderBlock`` :88-116, ``OobleckEncoder``
@@ -19,6 +20,7 @@ from . import _init
 from .blocks import SnakeBeta
 from .bottleneck import Bottleneck
 from .factory import create_bottleneck_from_config, create_pretransform_from_config
+from .local_attention import TransformerDecoder1D, TransformerEncoder1D, _LocalAttnHip
 
 
 class _WNBase(nn.Module):
@@ -430,15 +432,18 @@ class AudioAutoencoder(nn.Module):
         self.is_discrete = self.bottleneck and self.bottleneck.is_discrete
 
     def set_gemm_dtype(self, dtype: str):
-        """"bf16" | "fp16" | "fp32" for the encoder and decoder kernels (see ``_OobleckHip.set_gemm_dtype``)."""
+        """"bf16" | "fp16" | "fp32" for the encoder and decoder kernels (see ``_OobleckHip.set_gemm_dtype``, ``_LocalAttnHip.set_gemm_dtype``)."""
         for part in (self.encoder, self.decoder):
-            if isinstance(part, _OobleckHip):
+            if isinstance(part, (_OobleckHip, _LocalAttnHip)):
                 part.set_gemm_dtype(dtype)
         return self
 
     def activation_range_report(self, enable: bool = True):
         """``activation_range_report`` of the encoder and the decoder (``_OobleckHip.activation_range_report``); ``(False)`` returns the rows
-        of both, each tagged ``part="encoder"`` / ``"decoder"``."""
+        of both, each tagged ``part="encoder"`` / ``"decoder"``.  A local_attn encoder or decoder has no report: ``(True)`` raises
+        NotImplementedError before anything is switched on."""
+        if enable and any(isinstance(m, _LocalAttnHip) for m in (self.encoder, self.decoder)):
+            raise NotImplementedError("activation_range_report has no rows for the tensors of a local_attn codec")
         rows = []
         for part, module in (("encoder", self.encoder), ("decoder", self.decoder)):
             if isinstance(module, _OobleckHip):
@@ -563,9 +568,12 @@ class AudioAutoencoder(nn.Module):
 
 # ---------------------------------------------------------------------------------- factories (autoencoders.py:695-787)
 def create_encoder_from_config(encoder_config: tp.Dict[str, tp.Any]):
-    if encoder_config["type"] != "oobleck":
-        raise NotImplementedError(f"encoder type '{encoder_config['type']}' is outside this build's hot path (oobleck only)")
-    encoder = OobleckEncoder(**encoder_config["config"])
+    if encoder_config["type"] == "local_attn":          # autoencoders.py:709-712
+        encoder = TransformerEncoder1D(**encoder_config["config"])
+    elif encoder_config["type"] != "oobleck":
+        raise NotImplementedError(f"encoder type '{encoder_config['type']}' is outside this build's hot path (oobleck and local_attn only)")
+    else:
+        encoder = OobleckEncoder(**encoder_config["config"])
     if not encoder_config.get("requires_grad", True):
         for p in encoder.parameters():
             p.requires_grad = False
@@ -573,9 +581,12 @@ def create_encoder_from_config(encoder_config: tp.Dict[str, tp.Any]):
 
 
 def create_decoder_from_config(decoder_config: tp.Dict[str, tp.Any]):
-    if decoder_config["type"] != "oobleck":
-        raise NotImplementedError(f"decoder type '{decoder_config['type']}' is outside this build's hot path (oobleck only)")
-    decoder = OobleckDecoder(**decoder_config["config"])
+    if decoder_config["type"] == "local_attn":          # autoencoders.py:735-738
+        decoder = TransformerDecoder1D(**decoder_config["config"])
+    elif decoder_config["type"] != "oobleck":
+        raise NotImplementedError(f"decoder type '{decoder_config['type']}' is outside this build's hot path (oobleck and local_attn only)")
+    else:
+        decoder = OobleckDecoder(**decoder_config["config"])
     if not decoder_config.get("requires_grad", True):
         for p in decoder.parameters():
             p.requires_grad = False

@@ -1098,6 +1098,52 @@ int sat_add_pos(float* X_dev, const float* table_dev, int32_t bf, int32_t s_len,
 int sat_cfg_denoise(const float* model_out_dev, const float* x_dev, float* den_dev, int32_t b, int32_t c, int32_t t, int32_t use_cfg,
                     float cfg_scale, float scale_phi, float c_out, float c_skip, sat_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Local-attention transformer codec.  Replaces models/local_attention.py:17-282 (ContinuousLocalTransformer without conditioning, cross-attention
+ * or causal masking; TransformerDownsampleBlock1D / TransformerUpsampleBlock1D; TransformerEncoder1D / TransformerDecoder1D), the codec that
+ * models/autoencoders.py:709-712, 735-738 select with "type": "local_attn".  One plan per encoder or decoder.
+ *   encoder: x [b, in_channels, t] -> out [b, out_channels, t / prod(ratios)];  decoder: x [b, in_channels, t] -> out [b, out_channels, t * prod(ratios)].
+ * Stage i runs depths[i] layers of embed_dims[i] channels in heads[i] heads, every self-attention over NATTEN's 1-D neighbourhood of `window` keys
+ * with unscaled logits, behind a rotary embedding of max(dim_heads / 2, 32) channels; ff_inner[i] = int(embed_dims[i] * ff_mult) is the SwiGLU's
+ * hidden width.  The residual stream is fp32; gemm_dtype SAT_GEMM_BF16 / SAT_GEMM_FP16 / SAT_GEMM_FP32X selects the operands of every GEMM and of
+ * the attention inside the stages (the two projections at the audio boundary are fp32 in every build).
+ * Tensors (sat_local_attn_plan_set_tensor, the reference's state-dict names, fp32): project_in.weight, project_out.weight and per stage
+ * layers.<i>.{project_in.weight (where embed_dims[i - 1] != embed_dims[i]), project_down.weight | project_up.weight,
+ * transformer.rotary_pos_emb.inv_freq, transformer.layers.<l>.{0.gamma, 0.beta, 1.to_qkv.weight, 1.to_out.weight, 3.gamma, 3.beta,
+ * 4.ff.0.proj.weight, 4.ff.0.proj.bias, 4.ff.2.weight}}; finalize names a missing one with SAT_E_MISSING.
+ * sat_local_attn_plan_create: cfg_bytes = sizeof(sat_local_attn_cfg) of the caller's header, any other size is SAT_E_INVALID, as is an even window
+ * or one of 1 or less (NATTEN's rule).  SAT_E_UNSUPPORTED: a stage whose embed_dim / heads is not 32, 64, 96 or 128; 128 with SAT_GEMM_FP32X; an
+ * embed_dim that is no multiple of 128 or an ff_inner that is no multiple of 64 (the GEMM launchers: N % 128, K % 64); in_channels above 128.
+ * sat_local_attn_workspace_bytes / sat_local_attn_forward answer SAT_E_INVALID, before anything is launched, to an encoder input whose length is no
+ * multiple of prod(ratios) and to a stage whose rows per item are fewer than `window`.  The output depends on the weights and the input alone: the
+ * workspace may hold anything when the call starts. */
+#define SAT_LOCAL_ATTN_MAX_STAGES 16
+typedef struct sat_local_attn_plan sat_local_attn_plan;
+typedef struct sat_local_attn_cfg {
+    int32_t is_decoder;
+    int32_t in_channels, out_channels;
+    int32_t n_stages;
+    int32_t embed_dims[SAT_LOCAL_ATTN_MAX_STAGES];
+    int32_t heads[SAT_LOCAL_ATTN_MAX_STAGES];
+    int32_t depths[SAT_LOCAL_ATTN_MAX_STAGES];
+    int32_t ratios[SAT_LOCAL_ATTN_MAX_STAGES];
+    int32_t ff_inner[SAT_LOCAL_ATTN_MAX_STAGES];
+    int32_t window;
+    int32_t gemm_dtype;
+} sat_local_attn_cfg;
+int sat_local_attn_plan_create(const sat_local_attn_cfg* cfg, size_t cfg_bytes, sat_local_attn_plan** out_plan);
+void sat_local_attn_plan_destroy(sat_local_attn_plan* plan);
+int sat_local_attn_plan_set_tensor(sat_local_attn_plan* plan, const char* name, const float* data_dev, int64_t numel);
+int sat_local_attn_plan_finalize(sat_local_attn_plan* plan, sat_stream_t stream);
+int sat_local_attn_workspace_bytes(const sat_local_attn_plan* plan, int32_t b, int32_t t, size_t* out_bytes);
+int sat_local_attn_forward(sat_local_attn_plan* plan, const float* x_dev, float* out_dev, int32_t b, int32_t t, void* workspace_dev, size_t workspace_bytes,
+                           sat_stream_t stream);
+/* The two boundary kernels alone (tests/test_gpu_local_attn_kernels.py), fp32: rows [b * t, d] = x [b, c_in, t]^T w [d, c_in]^T (d % 4 == 0,
+ * c_in <= 128) and out [b, c_out, t] = (rows [b * t, d] w [c_out, d]^T)^T (d % 64 == 0). */
+int sat_local_attn_project_in(const float* x_dev, const float* w_dev, float* rows_dev, int32_t b, int32_t c_in, int32_t t, int32_t d, sat_stream_t stream);
+int sat_local_attn_project_out(const float* rows_dev, const float* w_dev, float* out_dev, int32_t b, int32_t c_out, int32_t t, int32_t d,
+                               sat_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
