@@ -498,3 +498,22 @@ int sat_launch_rope_table(const float* inv_freq, float* cos_t, float* sin_t, int
 // w [c_out, d] into out [b, c_out, t] channel-first (d % 64 == 0)
 int sat_launch_local_attn_project_in(const float* x, const float* w, float* rows, int b, int c_in, int t, int d, hipStream_t s);
 int sat_launch_local_attn_project_out(const float* rows, const float* w, float* out, int b, int c_out, int t, int d, hipStream_t s);
+// ---- the Dance Diffusion U-Net (unet_kernels.hip), fp32 inside in every format; fmt (SAT_GEMM_BF16 / SAT_GEMM_FP16 / SAT_GEMM_FP32X) is the
+// element type of the operand image a kernel leaves for the next convolution (fp32 in the verification mode).  Rows are [b * rows, c].
+int sat_unet_gn_tiles(int64_t n);      // partials per item of n elements: part holds [b][tiles][2] floats
+// GroupNorm(1, c) statistics of b items of n contiguous floats: stats [b][2] = (mean, 1 / sqrt(biased variance + eps)).  No atomics
+int sat_launch_unet_gn_stats(const float* x, float* part, float* stats, int b, int64_t n, float eps, hipStream_t s);
+// y = act((x - mean) rstd gamma + beta) (+ skip), act 1 = GELU (erf); y -> out32 [b * rows, c] and / or out_op [b * rows, ld]; out32 may alias x or skip
+int sat_launch_unet_gn_apply(const float* x, const float* stats, const float* gamma, const float* beta, const float* skip, float* out32, void* out_op, int b,
+                             int rows, int c, int ld, int act, int fmt, hipStream_t s);
+int sat_launch_unet_cast_rows(const float* x, void* out, int64_t m, int c, int ld, int fmt, hipStream_t s);      // out [m, ld][:, :c] = x [m, c]
+// Downsample1d("cubic") / Upsample1d("cubic") of blocks.py on rows, reflect indices computed in the kernel: [b * s_len, c] -> [b * s_len / 2, c]
+// (fp32 and / or operand image) and [b * s_len, c] -> out [b * 2 s_len, ld] (operand image: the first half of the parent level's concat buffer)
+int sat_launch_unet_downsample(const float* x, float* out32, void* out_op, int b, int s_len, int c, int fmt, hipStream_t s);
+int sat_launch_unet_upsample(const float* x, void* out, int b, int s_len, int c, int ld, int fmt, hipStream_t s);
+// x [b, io, t] * in_scale and the 16 timestep planes through w_main [c, io + 16, taps] (+ b_main) -> y [b * t, c] and w_skip [c, io + 16] -> sk
+int sat_launch_unet_input(const float* x, const float* tval, float in_scale, const float* w_embed, const float* w_main, const float* b_main,
+                          const float* w_skip, float* y, float* sk, int b, int io, int t, int c, int taps, hipStream_t s);
+// out [b, io, t] = conv(h [b * t, c], w_main [io, c, taps]) + b_main + xin [b * t, c] w_skip [io, c]^T
+int sat_launch_unet_output(const float* h, const float* xin, const float* w_main, const float* b_main, const float* w_skip, float* out, int b, int io, int t,
+                           int c, int taps, hipStream_t s);

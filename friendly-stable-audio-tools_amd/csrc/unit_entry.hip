@@ -582,3 +582,30 @@ extern "C" int sat_local_attn_project_out(const float* rows, const float* w, flo
                                           sat_stream_t stream) {
     return sat_launch_local_attn_project_out(rows, w, out, b, c_out, t, d, (hipStream_t)stream);
 }
+
+// ---- the Dance Diffusion U-Net's own kernels alone (unet_kernels.hip): the launchers sat_unet_forward calls
+extern "C" int sat_unet_groupnorm_partials(int64_t n) { return n > 0 ? sat_unet_gn_tiles(n) : 0; }
+extern "C" int sat_unet_groupnorm_stats(const float* x, float* part, float* stats, int32_t b, int64_t n, float eps, sat_stream_t stream) {
+    return sat_launch_unet_gn_stats(x, part, stats, b, n, eps, (hipStream_t)stream);
+}
+extern "C" int sat_unet_groupnorm_apply(const float* x, const float* stats, const float* gamma, const float* beta, const float* skip, float* out32, void* out_op,
+                                        int32_t b, int32_t rows, int32_t c, int32_t ld, int32_t act, int32_t fmt, sat_stream_t stream) {
+    return sat_launch_unet_gn_apply(x, stats, gamma, beta, skip, out32, out_op, b, rows, c, ld, act, fmt, (hipStream_t)stream);
+}
+extern "C" int sat_unet_cast_rows(const float* x, void* out_op, int64_t m, int32_t c, int32_t ld, int32_t fmt, sat_stream_t stream) {
+    return sat_launch_unet_cast_rows(x, out_op, m, c, ld, fmt, (hipStream_t)stream);
+}
+extern "C" int sat_unet_downsample(const float* x, float* out32, void* out_op, int32_t b, int32_t s_len, int32_t c, int32_t fmt, sat_stream_t stream) {
+    return sat_launch_unet_downsample(x, out32, out_op, b, s_len, c, fmt, (hipStream_t)stream);
+}
+extern "C" int sat_unet_upsample(const float* x, void* out_op, int32_t b, int32_t s_len, int32_t c, int32_t ld, int32_t fmt, sat_stream_t stream) {
+    return sat_launch_unet_upsample(x, out_op, b, s_len, c, ld, fmt, (hipStream_t)stream);
+}
+extern "C" int sat_unet_input(const float* x, const float* t_in, float in_scale, const float* w_embed, const float* w_main, const float* b_main,
+                              const float* w_skip, float* y, float* sk, int32_t b, int32_t io, int32_t t, int32_t c, int32_t taps, sat_stream_t stream) {
+    return sat_launch_unet_input(x, t_in, in_scale, w_embed, w_main, b_main, w_skip, y, sk, b, io, t, c, taps, (hipStream_t)stream);
+}
+extern "C" int sat_unet_output(const float* h, const float* xin, const float* w_main, const float* b_main, const float* w_skip, float* out, int32_t b,
+                               int32_t io, int32_t t, int32_t c, int32_t taps, sat_stream_t stream) {
+    return sat_launch_unet_output(h, xin, w_main, b_main, w_skip, out, b, io, t, c, taps, (hipStream_t)stream);
+}

@@ -96,6 +96,16 @@ class SatLocalAttnCfg(Structure):
                 + [("window", c_int32), ("gemm_dtype", c_int32)])
 
 
+UNET_MAX_DEPTH = 16      # include/sat_hip.h: SAT_UNET_MAX_DEPTH
+
+
+class SatUnetCfg(Structure):
+    """include/sat_hip.h: sat_unet_cfg (sat_unet_plan_create), the Dance Diffusion U-Net."""
+    _fields_ = ([(n, c_int32) for n in ("io_channels", "depth", "n_attn_layers", "kernel_size", "conv_bias", "cond_dim", "cond_noise_aug",
+                                       "learned_resample", "use_snake", "gemm_dtype")]
+                + [("channels", c_int32 * UNET_MAX_DEPTH)])
+
+
 class SatOobleckUnitDesc(Structure):
     """include/sat_hip.h: sat_oobleck_unit_desc, one codec layer on the caller's tensors (``sat_oobleck_unit``, for tests)."""
     _fields_ = ([(n, c_int32) for n in ("kind", "gemm_dtype", "activation", "b", "t_len", "c_in", "c_out", "stride", "dilation", "two_launch",
@@ -191,6 +201,22 @@ _SIGNATURES = {
     # the two boundary kernels of the local-attention codec alone: (x, w, rows, b, c_in, t, d, stream) and (rows, w, out, b, c_out, t, d, stream)
     "sat_local_attn_project_in": (c_int32, [c_void_p] * 3 + [c_int32] * 4 + [c_void_p]),
     "sat_local_attn_project_out": (c_int32, [c_void_p] * 3 + [c_int32] * 4 + [c_void_p]),
+    "sat_unet_plan_create": (c_int32, [POINTER(SatUnetCfg), c_size_t, POINTER(c_void_p)]),
+    "sat_unet_plan_destroy": (None, [c_void_p]),
+    "sat_unet_plan_set_tensor": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64]),
+    "sat_unet_plan_finalize": (c_int32, [c_void_p, c_void_p]),
+    "sat_unet_workspace_bytes": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_size_t)]),
+    # (plan, x, t, in_scale, out, b, t_len, ws, ws_bytes, stream)
+    "sat_unet_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    # the U-Net's own kernels alone (include/sat_hip.h)
+    "sat_unet_groupnorm_partials": (c_int32, [c_int64]),
+    "sat_unet_groupnorm_stats": (c_int32, [c_void_p] * 3 + [c_int32, c_int64, c_float, c_void_p]),
+    "sat_unet_groupnorm_apply": (c_int32, [c_void_p] * 7 + [c_int32] * 6 + [c_void_p]),
+    "sat_unet_cast_rows": (c_int32, [c_void_p] * 2 + [c_int64] + [c_int32] * 3 + [c_void_p]),
+    "sat_unet_downsample": (c_int32, [c_void_p] * 3 + [c_int32] * 4 + [c_void_p]),
+    "sat_unet_upsample": (c_int32, [c_void_p] * 2 + [c_int32] * 5 + [c_void_p]),
+    "sat_unet_input": (c_int32, [c_void_p] * 2 + [c_float] + [c_void_p] * 6 + [c_int32] * 5 + [c_void_p]),
+    "sat_unet_output": (c_int32, [c_void_p] * 6 + [c_int32] * 5 + [c_void_p]),
     "sat_vae_sample": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "sat_float_to_int16": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "sat_layernorm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),

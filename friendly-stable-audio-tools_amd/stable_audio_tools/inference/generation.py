@@ -1,5 +1,5 @@
-"""``generate_diffusion_cond`` (reference ``inference/generation.py:95-261``) -- same signature,
-same RNG order (manual_seed -> initial noise -> init-audio VAE noise -> sampler noise), same
+"""``generate_diffusion_cond`` (reference ``inference/generation.py:95-261``) and ``generate_diffusion_uncond`` (:12-91) -- same
+signatures, same RNG order (manual_seed -> initial noise -> init-audio VAE noise -> sampler noise), same
 return values; the sampler loop and the decode run on the HIP C ABI."""
 import math
 import typing as tp
@@ -34,6 +34,36 @@ def _cut_and_paste(init, mask_args, length):
     canvas = torch.zeros_like(init)
     canvas[:, :, paste_from:paste_from + span] = init[:, :, crop_from:crop_from + span]
     return canvas
+
+
+@torch.no_grad()
+def generate_diffusion_uncond(model, steps: int = 250, batch_size: int = 1, sample_size: int = 2097152, seed: int = -1, device: str = "cuda",
+                              init_audio: tp.Optional[tp.Tuple[int, torch.Tensor]] = None, init_noise_level: float = 1.0,
+                              return_latents: bool = False, disable_tqdm: bool = False, **sampler_kwargs) -> torch.Tensor:
+    """Same arguments, Gaussian-draw order (seed -> initial noise -> VAE noise of the init audio -> sampler draws) and return value as the
+    reference's generation.py:12-91: audio ``[batch_size, channels, sample_size]`` (or latents with ``return_latents``).  Variations start
+    from ``init_audio`` + noise at ``init_noise_level`` (``sigma_max``).  The reference reads ``model.diffusion_objective``, which its
+    ``DiffusionModelWrapper`` never sets; here the wrapper carries "v"."""
+    ratio = model.pretransform.downsampling_ratio if model.pretransform else 1
+    length = sample_size // ratio
+    check_length = getattr(model.model, "check_length", None)
+    if check_length is not None:
+        check_length(length)                                           # ValueError before anything is sampled
+    torch.manual_seed(int(seed if seed != -1 else np.random.randint(0, 2**32 - 1, dtype=np.uint32)))
+    noise = torch.randn([batch_size, model.io_channels, length], device=device)
+    init = None
+    if init_audio is not None:
+        init = _init_latents(model, init_audio, sample_size, batch_size, device)
+        sampler_kwargs["sigma_max"] = init_noise_level                  # variations
+    if model.diffusion_objective == "v":
+        sampled = sample_k(model.model, noise, init, None, steps, **sampler_kwargs, device=device, disable_tqdm=disable_tqdm)
+    elif model.diffusion_objective == "rectified_flow":
+        sampled = sample_rf(model.model, noise, init_data=init, steps=steps, **sampler_kwargs, device=device, disable_tqdm=disable_tqdm)
+    else:
+        raise RuntimeError(f"No such sampling mode: '{model.diffusion_objective}'")
+    if model.pretransform and not return_latents:
+        sampled = model.pretransform.decode(sampled)
+    return sampled
 
 
 @torch.no_grad()

@@ -10,6 +10,8 @@ the per-step scalars of the published DPM-Solver++(3M) SDE update from the sigma
 (float64, a few flops per step) and the device does the tensor work in two C-ABI calls per
 step: ``sat_dit_denoise_cfg`` (DiT with batched CFG + VDenoiser scalings) and
 ``sat_dpmpp3m_update`` (fused elementwise state update).  No host<->device sync inside the loop.
+The Dance Diffusion U-Net (``DiffusionAttnUnet1D``) is driven through the same two calls of a denoiser, ``prepare_generation`` once and
+``denoise(x, sigma, out=)`` per evaluation, with every sampler type; inpainting masks stay with the DiT.
 
 Noise: k-diffusion's default ``BrownianTreeNoiseSampler`` (torchsde) is replaced by i.i.d.
 ``randn`` per step, which has the same distribution on a fixed sigma grid; ``noise_sampler=``
@@ -20,7 +22,7 @@ import math
 import torch
 
 from .. import _hip
-from ..models.diffusion import DiTWrapper
+from ..models.diffusion import DiffusionAttnUnet1D, DiTWrapper
 
 SUPPORTED_SAMPLERS = ("dpmpp-3m-sde", "dpmpp-2m-sde", "k-heun", "k-lms", "k-dpmpp-2s-ancestral", "k-dpm-2", "k-dpm-fast",
                       "k-dpm-adaptive")
@@ -354,10 +356,18 @@ def sample_k(model_fn, noise, init_data=None, mask=None, steps=100, sampler_type
         raise NotImplementedError("cond_fn (gradient guidance through the denoiser) is outside the supported hot path")
     if mask is not None and init_data is None:
         mask = None                                                     # sampling.py:166-201: a mask without init data is ignored
-    if not isinstance(model_fn, DiTWrapper):
-        raise NotImplementedError("sample_k drives the HIP DiT (DiTWrapper) only; there is no eager/CPU denoiser path")
-    assert batch_cfg, "batch_cfg must be True for DiTWrapper"
-    dit = model_fn.model
+    # the denoiser protocol: prepare_generation(conditioning ...) once, then denoise(x, sigma, out=) per evaluation.  DiTWrapper's DiT and the
+    # Dance Diffusion U-Net implement it; a plain callable would need an eager denoiser, which does not exist here
+    if isinstance(model_fn, DiTWrapper):
+        assert batch_cfg, "batch_cfg must be True for DiTWrapper"
+        dit = model_fn.model
+    elif isinstance(model_fn, DiffusionAttnUnet1D):
+        if mask is not None:
+            raise NotImplementedError("inpainting masks are driven through the DiT only; the U-Net samples and makes variations")
+        dit = model_fn
+    else:
+        raise NotImplementedError("sample_k drives the HIP DiT (DiTWrapper) and the HIP U-Net (DiffusionAttnUnet1D) only; there is no eager/CPU "
+                                  "denoiser path")
 
     sigmas = get_sigmas_polyexponential(steps, sigma_min, sigma_max, rho)
     lib = _hip.lib()

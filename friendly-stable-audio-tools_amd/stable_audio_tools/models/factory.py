@@ -1,10 +1,11 @@
 """Model construction from the reference's JSON configs (counterpart of ``models/factory.py:4-142``), for what this build
-accelerates: ``diffusion_cond`` models with a DiT denoiser and ``autoencoder`` models / pretransforms with an Oobleck VAE.
+accelerates: ``diffusion_cond`` models with a DiT denoiser, ``diffusion_uncond`` models with the Dance Diffusion U-Net (``DAU1d``) and
+``autoencoder`` models / pretransforms with an Oobleck VAE.
 Every other ``model_type`` / ``type`` the reference knows is refused with a reason instead of being half-built.
 """
 import json
 
-_REFERENCE_ONLY_MODELS = ("diffusion_uncond", "diffusion_prior", "diffusion_autoencoder", "lm")
+_REFERENCE_ONLY_MODELS = ("diffusion_prior", "diffusion_autoencoder", "lm")
 
 
 def create_model_from_config(model_config):
@@ -13,6 +14,8 @@ def create_model_from_config(model_config):
         from .autoencoders import create_autoencoder_from_config as build
     elif kind in ("diffusion_cond", "diffusion_cond_inpaint"):
         from .diffusion import create_diffusion_cond_from_config as build
+    elif kind == "diffusion_uncond":
+        from .diffusion import create_diffusion_uncond_from_config as build
     elif kind in _REFERENCE_ONLY_MODELS:
         raise NotImplementedError(f"model type '{kind}' exists in the reference but is outside this build's hot path")
     else:

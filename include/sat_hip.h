@@ -1144,6 +1144,67 @@ int sat_local_attn_project_in(const float* x_dev, const float* w_dev, float* row
 int sat_local_attn_project_out(const float* rows_dev, const float* w_dev, float* out_dev, int32_t b, int32_t c_out, int32_t t, int32_t d,
                                sat_stream_t stream);
 
+/* ---- The Dance Diffusion U-Net: DiffusionAttnUnet1D of the reference's models/diffusion.py:376-479 (ResConvBlock, SelfAttention1d, SkipBlock,
+ * Downsample1d("cubic"), Upsample1d("cubic") of models/blocks.py), what create_model_from_config builds for "model_type": "diffusion_uncond" with
+ * "type": "DAU1d".  out [b, io, t] = net(cat([x * in_scale, planes(FourierFeatures(1, 16)(t_in))])), fp32 in and out; in_scale is the c_in of a
+ * v-objective denoiser (1 for the plain forward).  Activations are channel-last rows inside; the residual / skip stream, the GroupNorm
+ * statistics, the softmax and the two boundary layers are fp32; gemm_dtype SAT_GEMM_BF16 / SAT_GEMM_FP16 / SAT_GEMM_FP32X selects the operands
+ * of every convolution between them and of the attention.  Outputs are a function of the weights and the inputs alone: no atomics.
+ * Tensors (sat_unet_plan_set_tensor, the reference's state-dict names, fp32): timestep_embed.weight and, under "net.", per ResConvBlock
+ * main.{0,3}.{weight,bias} (no bias with conv_bias 0), main.{1,4}.{weight,bias} (none at main.4 of the last block), skip.weight where the widths
+ * differ; per SelfAttention1d norm.{weight,bias}, qkv_proj.{weight,bias}, out_proj.{weight,bias}.  The resamplers' `kernel` buffers are not read:
+ * the cubic filter is a constant of the kernels (the Python module refuses any other).  finalize names a missing tensor with SAT_E_MISSING.
+ * sat_unet_plan_create: cfg_bytes = sizeof(sat_unet_cfg) of the caller's header, any other size is SAT_E_INVALID, as is depth < 2 (the reference
+ * fails there).  SAT_E_UNSUPPORTED, each with its reason: use_snake, learned_resample, cond_dim > 0 or cond_noise_aug, a kernel_size outside
+ * 1 / 3 / 5 / 7, a channels entry that is no multiple of 128, depth > SAT_UNET_MAX_DEPTH, io_channels + 16 > 128, SAT_GEMM_FP8.
+ * sat_unet_workspace_bytes / sat_unet_forward answer SAT_E_INVALID, before anything is launched, to a t that is no multiple of 2^(depth - 1) or
+ * leaves fewer than 3 rows at the deepest level (the reference fails in F.pad or torch.cat there). */
+#define SAT_UNET_MAX_DEPTH 16
+typedef struct sat_unet_plan sat_unet_plan;
+typedef struct sat_unet_cfg {
+    int32_t io_channels;
+    int32_t depth;
+    int32_t n_attn_layers;
+    int32_t kernel_size;
+    int32_t conv_bias;         /* 0 / 1 */
+    int32_t cond_dim;          /* must be 0 */
+    int32_t cond_noise_aug;    /* must be 0 */
+    int32_t learned_resample;  /* must be 0 */
+    int32_t use_snake;         /* must be 0 */
+    int32_t gemm_dtype;
+    int32_t channels[SAT_UNET_MAX_DEPTH];
+} sat_unet_cfg;
+int sat_unet_plan_create(const sat_unet_cfg* cfg, size_t cfg_bytes, sat_unet_plan** out_plan);
+void sat_unet_plan_destroy(sat_unet_plan* plan);
+int sat_unet_plan_set_tensor(sat_unet_plan* plan, const char* name, const float* data_dev, int64_t numel);
+int sat_unet_plan_finalize(sat_unet_plan* plan, sat_stream_t stream);
+int sat_unet_workspace_bytes(const sat_unet_plan* plan, int32_t b, int32_t t, size_t* out_bytes);
+int sat_unet_forward(sat_unet_plan* plan, const float* x_dev, const float* t_dev, float in_scale, float* out_dev, int32_t b, int32_t t,
+                     void* workspace_dev, size_t workspace_bytes, sat_stream_t stream);
+/* The U-Net's own kernels alone (tests/test_gpu_unet_kernels.py); fmt is SAT_GEMM_BF16 / SAT_GEMM_FP16 / SAT_GEMM_FP32X, the element type of an
+ * operand image (fp32 for the last).  Rows are [b * rows, c], one item is rows * c contiguous floats; pointers 16-byte aligned.
+ * groupnorm_stats: stats [b][2] = (mean, 1 / sqrt(biased variance + eps)) over the n = rows * c elements of each item (n % 4 == 0); part_dev holds
+ *   b * sat_unet_groupnorm_partials(n) * 2 floats of per-tile (mean, M2) partials, combined in a fixed order.
+ * groupnorm_apply: y = act((x - mean) rstd gamma[ch] + beta[ch]) + skip, act 1 = GELU (erf form), 0 = none; skip may be NULL; y goes to out32
+ *   [b * rows, c] and / or out_op [b * rows, ld] (either may be NULL; out32 may alias x or skip).
+ * cast_rows: out_op [m, ld][:, :c] = x [m, c].
+ * downsample: Downsample1d("cubic"), [b * s, c] -> [b * s / 2, c] (s even, s > 3), fp32 and / or operand image.
+ * upsample: Upsample1d("cubic"), [b * s, c] -> out_op [b * 2 s, ld] (s > 2).
+ * input: x [b, io, t] * in_scale and the 16 planes of FourierFeatures(t_in [b]; w_embed [8]) through w_main [c, io + 16, taps] (+ b_main or NULL,
+ *   zero padding of the concatenated tensor) -> y [b * t, c], and through w_skip [c, io + 16] -> sk [b * t, c].
+ * output: out [b, io, t] = conv(h [b * t, c], w_main [io, c, taps]) + b_main (or NULL) + xin [b * t, c] w_skip [io, c]^T (c % 64 == 0). */
+int sat_unet_groupnorm_partials(int64_t n);
+int sat_unet_groupnorm_stats(const float* x_dev, float* part_dev, float* stats_dev, int32_t b, int64_t n, float eps, sat_stream_t stream);
+int sat_unet_groupnorm_apply(const float* x_dev, const float* stats_dev, const float* gamma_dev, const float* beta_dev, const float* skip_dev,
+                             float* out32_dev, void* out_op_dev, int32_t b, int32_t rows, int32_t c, int32_t ld, int32_t act, int32_t fmt, sat_stream_t stream);
+int sat_unet_cast_rows(const float* x_dev, void* out_op_dev, int64_t m, int32_t c, int32_t ld, int32_t fmt, sat_stream_t stream);
+int sat_unet_downsample(const float* x_dev, float* out32_dev, void* out_op_dev, int32_t b, int32_t s, int32_t c, int32_t fmt, sat_stream_t stream);
+int sat_unet_upsample(const float* x_dev, void* out_op_dev, int32_t b, int32_t s, int32_t c, int32_t ld, int32_t fmt, sat_stream_t stream);
+int sat_unet_input(const float* x_dev, const float* t_dev, float in_scale, const float* w_embed_dev, const float* w_main_dev, const float* b_main_dev,
+                   const float* w_skip_dev, float* y_dev, float* sk_dev, int32_t b, int32_t io, int32_t t, int32_t c, int32_t taps, sat_stream_t stream);
+int sat_unet_output(const float* h_dev, const float* xin_dev, const float* w_main_dev, const float* b_main_dev, const float* w_skip_dev, float* out_dev,
+                    int32_t b, int32_t io, int32_t t, int32_t c, int32_t taps, sat_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
