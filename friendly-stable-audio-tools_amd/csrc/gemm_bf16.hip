@@ -15,10 +15,9 @@
 
 #include <type_traits>
 
-#include "attn_core.h"
 #include <algorithm>
 
-#include "sat_common.h"
+#include "gemm_ring.h"
 
 namespace {
 
@@ -772,8 +771,8 @@ __device__ __forceinline__ void gemm_epilogue_f32_staged(const GemmArgs& g, Acc&
 template <int BM, int BN, int WM, int WN, int EPIX>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs g) {
     sat_f16_saturate();
-    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX == EPI_ACT16 ? EPI_SWIGLU : EPIX;
-    constexpr bool QKN = EPIX == EPI_HEADS_QKN || EPIX == EPI_ACT16;      // the alternative build of the epilogue (gemm_epilogue)
+    constexpr int EPI = EpiOf<EPIX>::EPI;
+    constexpr bool QKN = EpiOf<EPIX>::QKN;
     constexpr int NT = WM * WN * 64;
     constexpr int TM = BM / WM;
     constexpr int TN = BN / WN;
@@ -906,8 +905,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs g) {
 template <int BM, int BN, int WM, int WN, int EPIX>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs g) {
     sat_f16_saturate();
-    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX == EPI_ACT16 ? EPI_SWIGLU : EPIX;
-    constexpr bool QKN = EPIX == EPI_HEADS_QKN || EPIX == EPI_ACT16;      // the alternative build of the epilogue (gemm_epilogue)
+    constexpr int EPI = EpiOf<EPIX>::EPI;
+    constexpr bool QKN = EpiOf<EPIX>::QKN;
     constexpr int NT = WM * WN * 64;
     constexpr int TM = BM / WM;
     constexpr int TN = BN / WN;
@@ -1022,22 +1021,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_glds_kernel(GemmArgs g) {
 // stay in flight across every barrier (guide T3+T4).  This is what hides the L2/HBM -> LDS latency
 // when only one workgroup fits a CU (B=1: 204..432 workgroups on 256 CUs).
 //   iteration k:  wait(tile k landed) ; barrier ; issue tile k+NS-1 -> stage (k-1)%NS ; compute k
-// BK = 64 (128-B rows, 8 chunks) or 32 (64-B rows, 4 chunks; swizzle c ^ ((row>>2)&3)).
+// BK = 64: 128-byte rows of 8 chunks, the image of lds_tile_off.  Every constant of a tile is a member of RingGeom (gemm_ring_geom.h),
+// which the launcher reads as well; the pieces are those of gemm_ring.h.
 // ---------------------------------------------------------------------------------------------
-// -DSAT_RING_MFMA_32X32: every ring tile on the 32 x 32 x 16 MFMA (A/B builds only; see S16 in gemm_pipe_kernel)
-#ifdef SAT_RING_MFMA_32X32
-constexpr bool SAT_RING_MFMA_16 = false;
-#else
-constexpr bool SAT_RING_MFMA_16 = true;
-#endif
-
-template <int BK>
-__device__ __forceinline__ int lds_off_bk(int row, int chunk) {
-    if constexpr (BK == 128) return row * 256 + ((chunk ^ (row & 15)) << 4);      // 256-B rows: 16 chunks, XOR with the row
-    else if constexpr (BK == 64) return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-    else return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4);
-}
-
 // (The ablation modes of rounds 1-2 -- no LDS-DMA / no ds_read / no barrier / no epilogue builds of this kernel -- are in the git
 // history at 9661dcc; what they measured is in profiles/r01_gemm_ablation.txt, r02_gemm_ablation.txt.)
 // FP8: A and W are e4m3 bytes.  The launcher hands the kernel K/2 "bf16 columns", so staging, LDS layout and swizzle are
@@ -1058,57 +1044,11 @@ __device__ __forceinline__ int lds_off_bk(int row, int chunk) {
 template <int BM, int BN, int BK, int WM, int WN, int NS, int EPIX, int FP8 = 0, int KG = 1, bool DIL = false>
 __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g) {
     sat_f16_saturate();
-    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX == EPI_ACT16 ? EPI_SWIGLU : EPIX;          // EPI_HEADS_QKN: the heads kernel with the qk_norm epilogue
-    constexpr bool QKN = EPIX == EPI_HEADS_QKN || EPIX == EPI_ACT16;      // the alternative build of the epilogue (gemm_epilogue)
-    static_assert(!QKN || FP8 == 0, "qk_norm / plain activation: 16-bit operands only");
-    static_assert(KG == 1 || (KG == 2 && EPI == EPI_F32 && FP8 == 0 && BK == 64 && BM / WM == 64 && BN / WN == 64),
-                  "K-groups: fp32 output, 64 x 64 wave tiles, 128-byte rows");
-    constexpr int NT = KG * WM * WN * 64;
-    constexpr int TM = BM / WM;
-    constexpr int TN = BN / WN;
-    // MFMA shape: the 8-wave fp32-output tiles with 16-bit operands (15, 44, 49) run v_mfma_f32_16x16x32 into 16 x 16 blocks (acc16),
-    // every other build v_mfma_f32_32x32x16 (acc).  Same LDS image, fragment bytes, matrix-pipe cycles per k and bit-identical sums;
-    // under the socket's power cap the smaller shape is the faster one on random data: FF-out 56.7 -> 50.4 us on tile 15, 53.3 -> 50.7
-    // on tile 49, to_out 20.5 -> 19.8 (profiles/ring_mfma_shape_timing.txt).  Only the staged fp32 epilogue is shape-agnostic behind
-    // its first line (stage_rows32).  The 4-wave tile 16 measured 1.5-2 % slower at its own shape (cross to_out, 14.55 -> 14.8 us) in
-    // three interleaves of its reads and DMA pieces and keeps the old shape; the 16-wave tile has no room for two sets of the twice as
-    // many fragments.
-    // The 12-wave heads build of tile 30 (one-prompt to_qkv) runs it too, in both orientations (q / k swapped, V^T un-swapped: gemm_heads16_t,
-    // gemm_heads16_vt); its qk_norm, SwiGLU, plain-activation, fp32 and e4m3 builds keep 32 x 32 x 16.  The product call (M = 2050,
-    // d = 1536, LayerNorm fold) went 40.0 -> 36.3 us in fp16 and 38.1 -> 35.2 in bf16, 27 and 10 times the spread of one build, with
-    // q, k and V^T bit-identical (profiles/qkv_mfma_shape_timing.txt); 164 VGPRs of the 168 that three waves per SIMD leave, no scratch.
-    constexpr bool S16 = SAT_RING_MFMA_16 && FP8 == 0 && ((EPI == EPI_F32 && NT == 512) || (EPI == EPI_HEADS && !QKN && NT == 768));
-    static_assert(!S16 || BK == 64, "16 x 16 x 32 fragments: two 32-k steps per 128-byte row");
-    // the fused epilogues need a whole head / a value-gate pair per wave, the staged fp32 epilogue a 64-column block
-    static_assert(TN == 64, "wave tile is TM x 64");
-    constexpr int MI = TM / 32;
-    constexpr int NI = TN / 32;
-    constexpr int CPR = BK / 8;                    // 16-B chunks per row
-    // One LDS-DMA instruction of one wave moves 64 chunks = 1 KiB.  A stage holds WL_A + WL_B of them (A rows first, then
-    // W rows, contiguous); wave w issues wave-loads w, w+NW, w+2NW, ...  When NW does not divide WL (256x192 on 12 waves:
-    // 56 wave-loads) the first WL%NW waves carry one more than the rest, and the counted vmcnt wait is per wave.
-    constexpr int NW = KG * WM * WN;                  // every wave loads
-    constexpr int WL_A = BM * CPR / 64;
-    constexpr int WLG = (BM + BN) * CPR / 64;         // wave-loads of one K-group's rows of a stage
-    constexpr int WL = KG * WLG;
-    constexpr int LPT = (WL + NW - 1) / NW;        // max LDS-DMA instructions per tile per wave
-    constexpr int N_FULL = WL - (LPT - 1) * NW;    // waves [0, N_FULL) issue LPT, the others LPT-1
-    constexpr bool UNIFORM = (WL % NW) == 0;
-    constexpr int ROWB = BK * 2;
-    constexpr bool MXA = FP8 == 3;                 // MXFP8 A operand: + one dword of E8M0 block scales per A row per stage
-    constexpr int SCALE_WAVES = MXA ? BM / 64 : 0; // the first BM/64 waves each DMA 64 scale dwords per stage
-    constexpr int GROUP_BYTES = (BM + BN) * ROWB + (MXA ? BM * 4 : 0);
-    constexpr int STAGE_BYTES = KG * GROUP_BYTES;
-    constexpr int D = NS - 1;                      // prefetch distance
-    constexpr bool DIL_ON = (DIL || KG == 2) && FP8 == 0;
-    constexpr int NDIL = !DIL_ON ? 0 : UNIFORM ? LPT : LPT - 1;          // pieces EVERY wave issues in the loop body (a ragged tile's extra piece stays in front)
-    // k-steps that carry them (K-groups: the half in front of the mid-iteration barrier, which is one 32-k step of the 16 x 16 x 32 loop)
-    constexpr int DIL_STEPS = KG == 2 ? (S16 ? 1 : BK / 32) : BK / 16 - 1;
-    static_assert(!S16 || KG == 2 || !DIL_ON, "16 x 16 x 32, one K-group: the LDS-DMA pieces are issued in front of compute()");
-    constexpr int DIL_PER = (NDIL + DIL_STEPS - 1) / (DIL_STEPS > 0 ? DIL_STEPS : 1);
-    static_assert(!MXA || D == 1 || UNIFORM, "MXFP8: counted waits are built for uniform tiles or 2-stage rings");
-    static_assert((BM * CPR) % 64 == 0 && (BN * CPR) % 64 == 0 && (D - 1) * LPT < 64, "bad pipeline geometry");
-    static_assert(!FP8 || BK == 64, "fp8: 128-byte rows only");
+    using G = RingGeom<BM, BN, BK, WM, WN, NS, EPIX, FP8, KG, DIL>;
+    constexpr int EPI = G::EPI, NT = G::NT, TM = G::TM, TN = G::TN, MI = G::MI, NI = G::NI, MB = G::MB, NW = G::NW, WLG = G::WLG, LPT = G::LPT;
+    constexpr int ROWB = G::ROWB, SCALE_WAVES = G::SCALE_WAVES, GROUP_BYTES = G::GROUP_BYTES, STAGE_BYTES = G::STAGE_BYTES, D = G::D;
+    constexpr int NDIL = G::NDIL, DIL_STEPS = G::DIL_STEPS, DIL_PER = G::DIL_PER, ORI = G::ORI;
+    constexpr bool QKN = G::QKN, S16 = G::S16, UNIFORM = G::UNIFORM, MXA = G::MXA, DIL_ON = G::DIL_ON, LN_CONS = G::LN_CONS, PRE_RESID = G::PRE_RESID;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -1142,35 +1082,16 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     // Fused cross-attention (HeadsEpi::xa_k, 128 x 64 tile: one head per workgroup column, one 32-query block per wave): the K / V^T
     // tiles of the (sequence, kv-head) go to LDS behind the ring and the LayerNorm constants NOW -- they are the oldest entries of the
     // vector-memory queue, so every counted vmcnt wait of the K loop still holds, and the loop's barriers publish them.
-    constexpr bool XA_OK = EPI == EPI_HEADS && MI == 1 && NI == 2 && NW == 4 && BN == 64 && BK == 64 && NS == 3 && FP8 == 0;
-    constexpr int XA_OFF = (NS * STAGE_BYTES + (BM + BN) * 8 + 1023) & ~1023;
+    constexpr bool XA_OK = G::XA_OK;
+    constexpr int XA_OFF = G::XA_OFF;
     [[maybe_unused]] bool xa_on = false;
-    [[maybe_unused]] auto xa_stage = [&](int b) {
-        const HeadsEpi& he = g.heads;
-        const int kvh = (n0 >> 6) / (he.heads / he.xa_kvh);
-        const op_t* kbase = he.xa_k + (size_t)(b * he.xa_kvh + kvh) * he.xa_sk_pad * 64;
-        const op_t* vbase = he.xa_vt + (size_t)(b * he.xa_kvh + kvh) * 64 * he.xa_sk_pad;
-        const int n_t = (((b * he.xa_sk) & 3) + he.xa_sk + 63) >> 6;
-        for (int t = 0; t < n_t; ++t)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int p = wave + 4 * i;                          // 1-KiB piece = 8 rows of 128 B
-                const int row = p * 8 + (lane >> 3);
-                const int c = (lane & 7) ^ ((row >> 1) & 7);         // source-side XOR swizzle (lds_tile_off)
-                char* dst = smem + XA_OFF + t * 16384 + p * 1024;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + (size_t)(t * 64 + row) * 64 + c * 8),
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + (size_t)row * he.xa_sk_pad + t * 64 + c * 8),
-                                                 (__attribute__((address_space(3))) void*)(dst + 8192), 16, 0, 0);
-            }
-    };
+    [[maybe_unused]] auto xa_stage = [&](int b) { xattn_stage_kv(g.heads, smem + XA_OFF, b, n0, wave, lane); };
     if constexpr (XA_OK) {
         xa_on = g.heads.xa_k != nullptr;
         if (xa_on) xa_stage(m0 / g.heads.S);
     }
     // fp32 residual epilogue of the small tiles (one 32-row block per wave, registers to spare): fetch the residual values NOW.
     // They are the oldest entries of the vector-memory queue, so every counted vmcnt wait of the K loop still holds.
-    constexpr bool PRE_RESID = EPI == EPI_F32 && (MI == 1 || KG == 2) && NI == 2 && NT <= 512;
     // K-groups: the 32 rows this wave finishes
     const int epi_m = m0 + wm * TM + (KG == 2 ? grp * 32 : 0);
     const bool epi_rows_valid = KG == 2 ? epi_m < M : wave_rows_valid;
@@ -1187,27 +1108,26 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
 
     // LayerNorm fold, consumer side: mean and 1/std of the BM rows of this tile from the producer's per-block partial sums, into
     // LDS behind the ring (filled right after the prologue's LDS-DMA below, read by the epilogue).
-    constexpr bool LN_CONS = (EPI == EPI_SWIGLU || EPI == EPI_HEADS) && FP8 == 0;
     // LDS behind the ring: (mean, 1/std) of the BM rows, then the BN (c1, c2) pairs of this tile's output channels
-    [[maybe_unused]] float2* lnst = reinterpret_cast<float2*>(smem + NS * STAGE_BYTES);
-    [[maybe_unused]] float* lnc = reinterpret_cast<float*>(smem + NS * STAGE_BYTES + BM * 8);      // c1[BN] then c2[BN]
+    [[maybe_unused]] float2* lnst = reinterpret_cast<float2*>(smem + G::LN_OFF);
+    [[maybe_unused]] float* lnc = reinterpret_cast<float*>(smem + G::LN_OFF + BM * 8);      // c1[BN] then c2[BN]
     const op_t* ld_ptr[LPT];
 #pragma unroll
     for (int i = 0; i < LPT; ++i) {
         const int L = KG == 2 ? grp * WLG + i * (WM * WN) + wv : i * NW + wave;               // wave-uniform; K-groups: a group stages its own rows
         const int lg = KG == 2 ? grp : 0;
         const int Lg = KG == 2 ? i * (WM * WN) + wv : L;
-        const bool is_a = Lg < WL_A;
-        int q = (is_a ? Lg : Lg - WL_A) * 64 + lane;
-        int row = q / CPR, pos = q % CPR;
-        int c = (BK == 128) ? (pos ^ (row & 15)) : (BK == 64) ? (pos ^ ((row >> 1) & 7)) : (pos ^ ((row >> 2) & 3));
+        const bool is_a = Lg < G::WL_A;
+        int q = (is_a ? Lg : Lg - G::WL_A) * 64 + lane;
+        int row = q / G::CPR, pos = q % G::CPR;
+        int c = pos ^ ((row >> 1) & 7);
         int gm = m0 + row;
         gm = gm < M ? gm : M - 1;
         int gn = n0 + row;
         gn = gn < N ? gn : N - 1;                  // only reachable by the unused slot of a short wave
         ld_ptr[i] = (is_a ? g.A + (size_t)gm * K + c * 8 : g.W + (size_t)gn * K + c * 8) + lg * BK;
     }
-    const bool wave_full = UNIFORM || wave < N_FULL;
+    const bool wave_full = UNIFORM || wave < G::N_FULL;
     [[maybe_unused]] const unsigned* sc_ptr = nullptr;
     if constexpr (MXA) {
         int gm = m0 + wave * 64 + lane;
@@ -1223,19 +1143,23 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     // 16 x 16 x 32 builds (S16): MB 16-row blocks x four 16-column blocks instead (acc is dead there)
-    constexpr int MB = S16 ? TM / 16 : 1;
     [[maybe_unused]] f32x4 acc16[MB][4];
 #pragma unroll
     for (int i = 0; i < MB; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // The stager.  THE issue site of the ring's LDS-DMA pieces: piece i of K-tile kt, from ld_ptr[i] to this wave's i-th wave-load slot of
+    // the stage at `sa`.  stage_in, the in-loop issues of the two 16-bit fragment loops and a ragged tile's extra piece all go through it,
+    // and wait_steady below counts what it puts into the vector-memory queue.
+    auto issue = [&](int i, int kt, char* sa) {
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ld_ptr[i] + kt * (BK * KG)),
+                                         (__attribute__((address_space(3))) void*)(sa + (KG == 2 ? grp * WLG + i * (WM * WN) + wv : i * NW + wave) * 1024), 16, 0, 0);
+    };
     auto stage_in = [&](int kt, int stage) {
         char* sa = smem + stage * STAGE_BYTES;
 #pragma unroll
         for (int i = 0; i < LPT; ++i)
-            if (UNIFORM || i + 1 < LPT || wave_full)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ld_ptr[i] + kt * (BK * KG)),
-                                                 (__attribute__((address_space(3))) void*)(sa + (KG == 2 ? grp * WLG + i * (WM * WN) + wv : i * NW + wave) * 1024), 16, 0, 0);
+            if (UNIFORM || i + 1 < LPT || wave_full) issue(i, kt, sa);
         if constexpr (MXA) {
             if (wave < SCALE_WAVES)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sc_ptr + kt),
@@ -1275,15 +1199,15 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
 #pragma unroll
                 for (int i = 0; i < MI; ++i) {
                     const int row = wm * TM + i * 32 + l31;
-                    u32x4 lo = *reinterpret_cast<const u32x4*>(sa + lds_off_bk<BK>(row, ks * 4 + half));
-                    u32x4 hi = *reinterpret_cast<const u32x4*>(sa + lds_off_bk<BK>(row, ks * 4 + 2 + half));
+                    u32x4 lo = *reinterpret_cast<const u32x4*>(sa + lds_tile_off(row, ks * 4 + half));
+                    u32x4 hi = *reinterpret_cast<const u32x4*>(sa + lds_tile_off(row, ks * 4 + 2 + half));
                     af[buf][i] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
                 }
 #pragma unroll
                 for (int j = 0; j < NI; ++j) {
                     const int row = wn * TN + j * 32 + l31;
-                    u32x4 lo = *reinterpret_cast<const u32x4*>(sb + lds_off_bk<BK>(row, ks * 4 + half));
-                    u32x4 hi = *reinterpret_cast<const u32x4*>(sb + lds_off_bk<BK>(row, ks * 4 + 2 + half));
+                    u32x4 lo = *reinterpret_cast<const u32x4*>(sb + lds_tile_off(row, ks * 4 + half));
+                    u32x4 hi = *reinterpret_cast<const u32x4*>(sb + lds_tile_off(row, ks * 4 + 2 + half));
                     bfr[buf][j] = i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
                 }
             };
@@ -1332,17 +1256,9 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
 #pragma unroll
                     for (int j = 0; j < NI; ++j)
                         acc[i][j] = mx(af[ks & 1][i], bfr[ks & 1][j], acc[i][j], ks, i);
-                if (ks + 1 < KS2) {
-                    constexpr int NR = 2 * (MI + NI), NM = MI * NI;
-#pragma unroll
-                    for (int r = 0; r < NM; ++r) {
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, NR / NM, 0);
-                    }
-                    if (NR % NM) __builtin_amdgcn_sched_group_barrier(0x100, NR % NM, 0);
-                } else {
-                    __builtin_amdgcn_sched_group_barrier(0x8, MI * NI, 0);
-                }
+                constexpr int NR = 2 * (MI + NI), NM = MI * NI;
+                if (ks + 1 < KS2) sched_reads_behind_mfmas<NR, NM, NR / NM>();
+                else sched_mfmas_only<NM>();
             }
             return;
         }
@@ -1353,10 +1269,10 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
             auto frag = [&](int ks, int buf) {
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
-                    af[buf][i] = *reinterpret_cast<const i64x2*>(sa + lds_off_bk<BK>(wm * TM + i * 32 + l31, ks * 2 + half));
+                    af[buf][i] = *reinterpret_cast<const i64x2*>(sa + lds_tile_off(wm * TM + i * 32 + l31, ks * 2 + half));
 #pragma unroll
                 for (int j = 0; j < NI; ++j)
-                    bfr[buf][j] = *reinterpret_cast<const i64x2*>(sb + lds_off_bk<BK>(wn * TN + j * 32 + l31, ks * 2 + half));
+                    bfr[buf][j] = *reinterpret_cast<const i64x2*>(sb + lds_tile_off(wn * TN + j * 32 + l31, ks * 2 + half));
             };
             frag(0, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, MI + NI, 0);
@@ -1371,16 +1287,8 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                         for (int j = 0; j < NI; ++j)
                             acc[i][j] = TRc ? __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(bfr[ks & 1][j][h2], af[ks & 1][i][h2], acc[i][j], 0, 0, 0)
                                             : __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(af[ks & 1][i][h2], bfr[ks & 1][j][h2], acc[i][j], 0, 0, 0);
-                if (ks + 1 < KS) {
-#pragma unroll
-                    for (int r = 0; r < MI + NI; ++r) {
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x8, 2 * MI * NI - (MI + NI), 0);
-                } else {
-                    __builtin_amdgcn_sched_group_barrier(0x8, 2 * MI * NI, 0);
-                }
+                if (ks + 1 < KS) sched_reads_behind_mfmas<MI + NI, 2 * MI * NI>();
+                else sched_mfmas_only<2 * MI * NI>();
             }
             return;
         }
@@ -1397,10 +1305,10 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
             auto frag = [&](int ks, int buf) {
 #pragma unroll
                 for (int i = 0; i < MB; ++i)
-                    af[buf][i] = *reinterpret_cast<const opx8*>(sa + lds_off_bk<BK>(wm * TM + i * 16 + l15, ks * 4 + q));
+                    af[buf][i] = *reinterpret_cast<const opx8*>(sa + lds_tile_off(wm * TM + i * 16 + l15, ks * 4 + q));
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    bfr[buf][j] = *reinterpret_cast<const opx8*>(sb + lds_off_bk<BK>(wn * TN + j * 16 + l15, ks * 4 + q));
+                    bfr[buf][j] = *reinterpret_cast<const opx8*>(sb + lds_tile_off(wn * TN + j * 16 + l15, ks * 4 + q));
             };
             frag(0, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
@@ -1411,9 +1319,7 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                     if (ks < DIL_STEPS && kt_issue >= 0) {
                         char* sdst = smem + st_issue * STAGE_BYTES;
 #pragma unroll
-                        for (int i = ks * DIL_PER; i < (ks + 1) * DIL_PER && i < NDIL; ++i)
-                            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ld_ptr[i] + kt_issue * (BK * KG)),
-                                                             (__attribute__((address_space(3))) void*)(sdst + (grp * WLG + i * (WM * WN) + wv) * 1024), 16, 0, 0);
+                        for (int i = ks * DIL_PER; i < (ks + 1) * DIL_PER && i < NDIL; ++i) issue(i, kt_issue, sdst);
                     }
                 }
 #pragma unroll
@@ -1429,43 +1335,25 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                         // pieces two at a time through the rest of the step, which is the half in front of the mid-iteration barrier
                         // (measured and not kept: one read behind each of the first eight MFMAs, 51.9 us against 50.7 on FF-out; reads
                         // and pieces together behind the first eight, 54.6)
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, NR / 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, NR - NR / 2, 0);
+                        sched_reads_behind_mfmas<NR, 2, NR / 2>();
                         if (DIL_PER == 8 && NM == 16) {
-                            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                                __builtin_amdgcn_sched_group_barrier(0x20, 2, 0);
-                                __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
-                            }
-                            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                            sched_mfmas_only<1>();
+                            sched_dma_pairs_behind_mfmas<4, 2>();
+                            sched_mfmas_only<1>();
                         } else {
-                            __builtin_amdgcn_sched_group_barrier(0x8, NM - 2, 0);
+                            sched_mfmas_only<NM - 2>();
                         }
                     } else {
-                        __builtin_amdgcn_sched_group_barrier(0x8, NM, 0);
+                        sched_mfmas_only<NM>();
                     }
-                    if (ks == KS2 / 2 - 1) {          // the OTHER group's iteration boundary (it runs half an iteration out of phase)
-                        __builtin_amdgcn_sched_barrier(0);
-                        __builtin_amdgcn_s_barrier();
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+                    if (ks == KS2 / 2 - 1) kgroup_mid_barrier();
                 } else if (ks + 1 < KS2) {
                     // one read of the next step's fragments behind each of the first MFMAs
                     // (measured on the 12-wave heads tile and not kept: two reads behind each of the first four MFMAs, 37.2 us against 36.3
                     // for to_qkv in fp16, 35.8 against 35.2 in bf16)
-#pragma unroll
-                    for (int r = 0; r < (NR < NM ? NR : NM); ++r) {
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    if (NM > NR) __builtin_amdgcn_sched_group_barrier(0x8, NM - NR, 0);
-                    if (NR > NM) __builtin_amdgcn_sched_group_barrier(0x100, NR - NM, 0);
+                    sched_reads_behind_mfmas<NR, NM>();
                 } else {
-                    __builtin_amdgcn_sched_group_barrier(0x8, NM, 0);
+                    sched_mfmas_only<NM>();
                 }
             }
             return;
@@ -1474,10 +1362,10 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
         auto frag = [&](int ks, int buf) {
 #pragma unroll
             for (int i = 0; i < MI; ++i)
-                af[buf][i] = *reinterpret_cast<const opx8*>(sa + lds_off_bk<BK>(wm * TM + i * 32 + l31, ks * 2 + half));
+                af[buf][i] = *reinterpret_cast<const opx8*>(sa + lds_tile_off(wm * TM + i * 32 + l31, ks * 2 + half));
 #pragma unroll
             for (int j = 0; j < NI; ++j)
-                bfr[buf][j] = *reinterpret_cast<const opx8*>(sb + lds_off_bk<BK>(wn * TN + j * 32 + l31, ks * 2 + half));
+                bfr[buf][j] = *reinterpret_cast<const opx8*>(sb + lds_tile_off(wn * TN + j * 32 + l31, ks * 2 + half));
         };
         frag(0, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, MI + NI, 0);        // the first fragments: DS reads only
@@ -1490,9 +1378,7 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                 if (ks < DIL_STEPS && kt_issue >= 0) {
                     char* sdst = smem + st_issue * STAGE_BYTES;
 #pragma unroll
-                    for (int i = ks * DIL_PER; i < (ks + 1) * DIL_PER && i < NDIL; ++i)
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ld_ptr[i] + kt_issue * (BK * KG)),
-                                                         (__attribute__((address_space(3))) void*)(sdst + (KG == 2 ? grp * WLG + i * (WM * WN) + wv : i * NW + wave) * 1024), 16, 0, 0);
+                    for (int i = ks * DIL_PER; i < (ks + 1) * DIL_PER && i < NDIL; ++i) issue(i, kt_issue, sdst);
                 }
             }
 #pragma unroll
@@ -1509,36 +1395,22 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                     // cover the trailing read, two do not)
                     // all of the next step's fragment reads behind the FIRST MFMA: they get three MFMAs (~100 cycles) of head start on the
                     // wait in front of the next step instead of one read trailing the last MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
+                    sched_reads_behind_mfmas<NR, 1, NR>();
                     if (ks < KS / 2 && DIL_PER == 4) {
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x20, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x20, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                        sched_dma_pairs_behind_mfmas<2, 0>();
+                        sched_mfmas_only<1>();
                     } else {
-                        __builtin_amdgcn_sched_group_barrier(0x8, NM - 1, 0);
+                        sched_mfmas_only<NM - 1>();
                     }
                 } else {
-#pragma unroll
-                    for (int r = 0; r < (NR < NM ? NR : NM); ++r) {
-                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    if (NM > NR) __builtin_amdgcn_sched_group_barrier(0x8, NM - NR, 0);
-                    if (NR > NM) __builtin_amdgcn_sched_group_barrier(0x100, NR - NM, 0);
+                    sched_reads_behind_mfmas<NR, NM>();
                     if (DIL_ON && ks < DIL_STEPS) __builtin_amdgcn_sched_group_barrier(0x20, DIL_PER, 0);          // this step's DMA pieces behind its MFMAs
                 }
             } else {
-                __builtin_amdgcn_sched_group_barrier(0x8, MI * NI, 0);
+                sched_mfmas_only<MI * NI>();
             }
             if constexpr (KG == 2) {
-                if (ks == KS / 2 - 1) {          // the OTHER group's iteration boundary (it runs half an iteration out of phase)
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                if (ks == KS / 2 - 1) kgroup_mid_barrier();
             }
         }
     };
@@ -1606,7 +1478,6 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
     // The orientation is fixed at compile time wherever it can be (ORI 0: un-swapped only -- fp32 output, MXFP8 A operand;
     // 1: transposed only -- SwiGLU; 2: per workgroup -- heads: q / k transposed, V^T un-swapped): one main loop instead of two keeps
     // the 128-VGPR kernels (16 waves, e4m3 fragments) out of scratch.
-    constexpr int ORI = (MXA || EPI == EPI_F32) ? 0 : (EPI == EPI_SWIGLU ? 1 : 2);
     bool tr = ORI != 0;
     if constexpr (EPI == EPI_HEADS) {
         const int hp = g.heads.heads * 64;
@@ -1623,9 +1494,7 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
             if constexpr (DIL_ON) {
                 if (wave_rows_valid) {
                     if constexpr (!UNIFORM) {          // the extra piece of the first waves of a ragged tile
-                        if (wave_full)
-                            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ld_ptr[LPT - 1] + (k + D) * (BK * KG)),
-                                                             (__attribute__((address_space(3))) void*)(smem + wr * STAGE_BYTES + ((LPT - 1) * NW + wave) * 1024), 16, 0, 0);
+                        if (wave_full) issue(LPT - 1, k + D, smem + wr * STAGE_BYTES);
                     }
                     compute(rd, trc, k + D, wr);
                 } else {
@@ -1785,7 +1654,7 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
                     for (int e = 0; e < 4; ++e) fin[rb][cb][e] = (grp ? acc16[2 + rb][cb][e] : acc16[rb][cb][e]) + t[e];
                 }
             if (epi_rows_valid)
-                gemm_epilogue_f32_staged<1, true>(g, fin, reinterpret_cast<float*>(smem + NW * 8192) + wave * 2048, epi_m, n0 + wn * TN, lane, resid);
+                gemm_epilogue_f32_staged<1, true>(g, fin, reinterpret_cast<float*>(smem + G::KG_STAGING_OFF) + wave * 2048, epi_m, n0 + wn * TN, lane, resid);
             return;
         }
         float* mine = reinterpret_cast<float*>(smem) + wave * 2048;
@@ -1800,9 +1669,8 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) fin[0][j][r] = (grp ? acc[1][j][r] : acc[0][j][r]) + theirs[(j * 16 + r) * 64 + lane];
-        static_assert(KG == 1 || NS * STAGE_BYTES >= 2 * NW * 8192, "exchange + staging areas");
         if (epi_rows_valid)
-            gemm_epilogue_f32_staged<1, true>(g, fin, reinterpret_cast<float*>(smem + NW * 8192) + wave * 2048, epi_m, n0 + wn * TN, lane, resid);
+            gemm_epilogue_f32_staged<1, true>(g, fin, reinterpret_cast<float*>(smem + G::KG_STAGING_OFF) + wave * 2048, epi_m, n0 + wn * TN, lane, resid);
         return;
     }
     if constexpr (EPI == EPI_F32) {
@@ -1830,32 +1698,24 @@ __global__ __launch_bounds__(KG * WM * WN * 64) void gemm_pipe_kernel(GemmArgs g
 
 template <int BM, int BN, int BK, int WM, int WN, int NS, int EPIX, int FP8 = 0, int KG = 1, bool DIL = false>
 int launch_pipe(const GemmArgs& a, hipStream_t stream) {
-    constexpr int EPI = EPIX == EPI_HEADS_QKN ? EPI_HEADS : EPIX == EPI_ACT16 ? EPI_SWIGLU : EPIX;
-    constexpr int NT = KG * WM * WN * 64;
-    constexpr bool LN_CONS = (EPI == EPI_SWIGLU || EPI == EPI_HEADS) && FP8 == 0;
-    constexpr int LDS = NS * KG * ((BM + BN) * BK * 2 + (FP8 == 3 ? BM * 4 : 0)) + (LN_CONS ? (BM + BN) * 8 : 0);     // + (mean, rstd) per row, (c1, c2) per column
-    static_assert(LDS <= 160 * 1024, "LDS ring exceeds 160 KiB");
-    SAT_CHECK_ARG(LN_CONS || !a.ln_part, SAT_E_UNSUPPORTED, "gemm: LayerNorm fold needs bf16 operands and a SwiGLU / heads epilogue");
-    SAT_CHECK_ARG((!a.xb && !a.ln_part_out) || (EPI == EPI_F32 && BN / WN == 64 && FP8 == 0 && a.xb && a.ln_part_out), SAT_E_UNSUPPORTED,
+    using G = RingGeom<BM, BN, BK, WM, WN, NS, EPIX, FP8, KG, DIL>;          // the launch's NT, LDS bytes and what the build supports
+    SAT_CHECK_ARG(G::LN_CONS || !a.ln_part, SAT_E_UNSUPPORTED, "gemm: LayerNorm fold needs bf16 operands and a SwiGLU / heads epilogue");
+    SAT_CHECK_ARG((!a.xb && !a.ln_part_out) || (G::EPI == EPI_F32 && FP8 == 0 && a.xb && a.ln_part_out), SAT_E_UNSUPPORTED,
                   "gemm: the bf16 image / row statistics come from the bf16 fp32-output tiles with 64-column wave tiles");
-    static_assert(EPI != EPI_F32 || BN / WN != 64 || LDS >= WM * WN * 8192, "the staged fp32 epilogue needs 8 KiB of LDS per wave");
     auto kern = gemm_pipe_kernel<BM, BN, BK, WM, WN, NS, EPIX, FP8, KG, DIL>;
-    // fused cross-attention (HeadsEpi::xa_k): three K / V^T tiles of 64 keys behind the ring and the LayerNorm constants
-    constexpr bool XA_OK = EPI == EPI_HEADS && BM == 128 && BN == 64 && BK == 64 && WM == 4 && WN == 1 && NS == 3 && FP8 == 0;
-    constexpr int XA_LDS = XA_OK ? ((NS * (BM + BN) * BK * 2 + (BM + BN) * 8 + 1023) & ~1023) + 3 * 16384 : LDS;
-    static_assert(XA_LDS <= 160 * 1024, "fused cross-attention: K / V^T tiles do not fit behind the ring");
+    // fused cross-attention (HeadsEpi::xa_k): three K / V^T tiles of 64 keys behind the ring and the LayerNorm constants (G::XA_LDS)
     bool xa = false;
-    if constexpr (EPI == EPI_HEADS) {
+    if constexpr (G::EPI == EPI_HEADS) {
         xa = a.heads.xa_k != nullptr;
         if (xa) {
             const HeadsEpi& he = a.heads;
-            SAT_CHECK_ARG(XA_OK, SAT_E_UNSUPPORTED, "gemm: the fused cross-attention epilogue lives in the 128 x 64 tile (variant 16)");
+            SAT_CHECK_ARG(G::XA_OK, SAT_E_UNSUPPORTED, "gemm: the fused cross-attention epilogue lives in the 128 x 64 tile (variant 16)");
             SAT_CHECK_ARG(he.parts == 1 && (he.kind[0] & ~16) == 8 && he.qscale == SAT_ATTN_QSCALE && he.xa_vt && he.xa_out && he.xa_kvh > 0 &&
                               he.heads % he.xa_kvh == 0 && he.xa_sk > 0 && he.xa_sk + 3 <= 192 && he.xa_sk_pad >= he.xa_sk + 3 && he.xa_sk_pad % 64 == 0,
                           SAT_E_UNSUPPORTED, "gemm: fused cross-attention needs one pre-scaled row-major part and at most 189 keys (got %d)", he.xa_sk);
         }
     }
-    SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), XA_LDS));
+    SAT_TRY(sat_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), G::XA_LDS));
     GemmArgs b = a;
     if (FP8) {
         SAT_CHECK_ARG(a.K % 128 == 0 && a.w_scale && (FP8 == 3 ? (const void*)a.a_bscale : (const void*)a.a_scale), SAT_E_UNSUPPORTED,
@@ -1865,7 +1725,7 @@ int launch_pipe(const GemmArgs& a, hipStream_t stream) {
     SAT_CHECK_ARG(b.N % BN == 0, SAT_E_UNSUPPORTED, "gemm: N=%d not a multiple of the %d-column tile", b.N, BN);
     SAT_CHECK_ARG(b.K % (BK * KG) == 0 && b.K / (BK * KG) >= NS, SAT_E_UNSUPPORTED, "gemm: K=%d too small for the %d-stage pipeline", a.K, NS);
     int tiles = cdiv(b.M, BM) * (b.N / BN);
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(NT), xa ? XA_LDS : LDS, stream, b);
+    hipLaunchKernelGGL(kern, dim3(tiles), dim3(G::NT), xa ? G::XA_LDS : G::LDS, stream, b);
     SAT_LAUNCH_CHECK();
     return 0;
 }

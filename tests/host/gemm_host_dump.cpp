@@ -2,12 +2,14 @@
 // kernel (csrc/ph8_sched.h) on the CPU.  Plain C++17, no HIP.
 //   gemm_host_dump routes [splits]   one case per stdin line -> the kernel template that would be launched, or the error
 //   gemm_host_dump sched          every schedule of a grid of shapes is walked workgroup by workgroup and checked to be an exact cover
+//   gemm_host_dump ring           the geometry (csrc/gemm_ring_geom.h: RingGeom) of every ring tile x epilogue x operand flavour that gemm_bf16.hip builds
 #include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
+#include "gemm_ring_geom.h"
 #include "gemm_tiles.h"
 
 // error codes of include/sat_hip.h (that header is C ABI + HIP-free, but the route function only names message ids)
@@ -172,9 +174,51 @@ static int sched() {
     return failures ? 1 : 0;
 }
 
+// ---- the ring tiles' geometry ---------------------------------------------------------------------------------------------------
+// One line per instantiation of gemm_pipe_kernel: the template arguments launch_tile (csrc/gemm_bf16.hip) hands launch_pipe, then every
+// member of RingGeom.  Instantiating the struct also runs its static_asserts.
+template <int ID, int EPIX, int F8>
+static void ring_one() {
+    constexpr SatTile t = sat_tile_geom(ID);
+    static_assert(t.family == SAT_GEMM_PIPE, "ring tiles only");
+    using G = RingGeom<t.bm, t.bn, t.bk, t.wm, t.wn, t.ns, EPIX, F8, t.kg, t.dil && F8 == 0>;
+    printf("tile=%d epix=%d f8=%d", ID, EPIX, F8);
+#define M(name) printf(" " #name "=%d", (int)G::name);
+    M(TILE_M) M(TILE_N) M(STAGES) M(KGROUPS) M(EPI) M(QKN) M(NT) M(TM) M(TN) M(MI) M(NI) M(S16) M(MB) M(CPR) M(NW) M(WL_A) M(WLG) M(WL) M(LPT) M(N_FULL) M(UNIFORM) M(ROWB) M(MXA) M(SCALE_WAVES)
+    M(GROUP_BYTES) M(STAGE_BYTES) M(D) M(DIL_ON) M(NDIL) M(DIL_STEPS) M(DIL_PER) M(LN_CONS) M(LN_OFF) M(PRE_RESID) M(ORI) M(XA_OK) M(XA_OFF) M(LDS) M(XA_LDS)
+    M(KG_STAGING_OFF)
+#undef M
+    printf("\n");
+}
+// launch_epi (csrc/gemm_bf16.hip) restated: the tiles built for (epilogue, operand flavour) -- change both together
+template <int EPIX, int F8>
+static void ring_epi() {
+    ring_one<SAT_TILE_128, EPIX, F8>();
+    ring_one<SAT_TILE_128x64, EPIX, F8>();
+    ring_one<SAT_TILE_256, EPIX, F8>();
+    ring_one<SAT_TILE_256x192, EPIX, F8>();
+    if constexpr (F8 == 0) {
+        if constexpr (EPIX == EPI_F32) {
+            ring_one<SAT_TILE_128_DEEP, EPIX, F8>();
+            ring_one<SAT_TILE_128_KGROUP, EPIX, F8>();
+        }
+        if constexpr (EPIX == EPI_HEADS || EPIX == EPI_HEADS_QKN) ring_one<SAT_TILE_128x64_XATTN, EPIX, F8>();
+    }
+}
+// launch_flavour and sat_launch_gemm restated: e4m3 flavours 1 and 2 of the three caller epilogues, 3 (MXFP8 A) of the fp32 output
+static int ring() {
+    ring_epi<EPI_F32, 0>(); ring_epi<EPI_F32, 1>(); ring_epi<EPI_F32, 2>(); ring_epi<EPI_F32, 3>();
+    ring_epi<EPI_SWIGLU, 0>(); ring_epi<EPI_SWIGLU, 1>(); ring_epi<EPI_SWIGLU, 2>();
+    ring_epi<EPI_HEADS, 0>(); ring_epi<EPI_HEADS, 1>(); ring_epi<EPI_HEADS, 2>();
+    ring_epi<EPI_HEADS_QKN, 0>();
+    ring_epi<EPI_ACT16, 0>();
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && !strcmp(argv[1], "routes")) return routes(argc >= 3 && !strcmp(argv[2], "splits"));
     if (argc >= 2 && !strcmp(argv[1], "sched")) return sched();
-    fprintf(stderr, "usage: gemm_host_dump routes | sched\n");
+    if (argc >= 2 && !strcmp(argv[1], "ring")) return ring();
+    fprintf(stderr, "usage: gemm_host_dump routes | sched | ring\n");
     return 2;
 }

@@ -132,8 +132,93 @@ def test_schedule_is_an_exact_cover(driver):
     assert cases == 72000 and split > 1000
 
 
+# ---- the ring tiles' geometry (csrc/gemm_ring_geom.h), which gemm_pipe_kernel and launch_pipe both read ----
+def _ring(exe):
+    rows = []
+    for line in subprocess.run([exe, "ring"], check=True, capture_output=True, text=True).stdout.strip().split("\n"):
+        rows.append({k: int(v) for k, v in (f.split("=") for f in line.split())})
+    return rows
+
+
+def _one(rows, tile, epix, f8=0):
+    got = [r for r in rows if (r["tile"], r["epix"], r["f8"]) == (tile, epix, f8)]
+    assert len(got) == 1, (tile, epix, f8)
+    return got[0]
+
+
+HEADS_QKN, ACT16 = 4, 5
+
+
 @needs_cxx
-@pytest.mark.parametrize("header", ["gemm_tiles.h", "ph8_sched.h"])
+def test_ring_geometry_of_every_built_tile(driver):
+    """RingGeom of every (ring tile, epilogue, operand flavour) that launch_epi / launch_flavour build.  The values are those of the
+    expressions gemm_pipe_kernel and launch_pipe each had of their own before the struct (commit 18f5687): the launch's dynamic LDS bytes,
+    the wave-load split, the in-loop DMA pieces, the offsets behind the ring."""
+    rows = _ring(driver)
+    # 4 tiles x (3 epilogues x 3 flavours + MXFP8 A + qk_norm + plain activation) + tiles 44, 49 (fp32) + tile 256 (heads, qk_norm)
+    assert len(rows) == 4 * 12 + 2 + 2 and len({(r["tile"], r["epix"], r["f8"]) for r in rows}) == len(rows)
+    for r in rows:
+        assert r["LDS"] <= 160 * 1024 and r["XA_LDS"] <= 160 * 1024, r
+        assert (r["D"] - 1) * r["LPT"] < 64, r          # the counted vmcnt waits fit the 6-bit immediate
+        f32, mxa = r["EPI"] == F32, r["f8"] == 3
+        assert r["ORI"] == (0 if f32 or mxa else 1 if r["EPI"] == SWIGLU else 2), r
+        assert r["EPI"] == {HEADS_QKN: HEADS, ACT16: SWIGLU}.get(r["epix"], r["epix"]) and r["QKN"] == (r["epix"] in (HEADS_QKN, ACT16)), r
+        # the launcher's LDS is the kernel's: NS stages, then the LayerNorm constants where the build has them; the cross-attention tiles behind both
+        bm, bn = r["TILE_M"], r["TILE_N"]
+        assert r["STAGE_BYTES"] == r["KGROUPS"] * ((bm + bn) * 128 + mxa * bm * 4) and r["LN_OFF"] == r["STAGES"] * r["STAGE_BYTES"], r
+        assert r["LDS"] == r["LN_OFF"] + r["LN_CONS"] * (bm + bn) * 8 and r["NT"] == 64 * r["NW"], r
+        assert r["XA_LDS"] == (r["XA_OFF"] + 3 * 16384 if r["XA_OK"] else r["LDS"]), r
+        assert r["XA_OFF"] % 1024 == 0 and r["XA_OFF"] >= r["LDS"], r
+        assert r["WL"] == r["WLG"] * (2 if r["tile"] == 49 else 1) and r["UNIFORM"] == (r["WL"] % r["NW"] == 0), r
+        assert r["N_FULL"] == r["WL"] - (r["LPT"] - 1) * r["NW"] and 0 < r["N_FULL"] <= r["NW"], r
+        # the fused cross-attention epilogue: the heads builds of the 128 x 64 geometry (tile 256, and tile 16 whose kernel carries it
+        # too -- both the kernel's and the launcher's expression said so) with 16-bit operands, and no other
+        assert r["XA_OK"] == (r["tile"] in (16, 256) and r["EPI"] == HEADS and r["f8"] == 0), r
+        assert r["S16"] == (r["f8"] == 0 and ((f32 and r["NT"] == 512) or (r["epix"] == HEADS and r["NT"] == 768))), r
+
+    t30 = _one(rows, 30, HEADS)          # 256 x 192 on 12 waves: the ragged tile
+    assert (t30["WL"], t30["LPT"], t30["N_FULL"], t30["UNIFORM"], t30["NW"]) == (56, 5, 8, 0, 12)
+    assert t30["LDS"] == 2 * 57344 + 448 * 8 == 118272 and t30["S16"] == 1 and _one(rows, 30, HEADS_QKN)["S16"] == 0
+
+    t49 = _one(rows, 49, F32)            # two K-groups: the exchange and staging areas fit the ring exactly
+    assert t49["STAGE_BYTES"] == 65536 and t49["LDS"] == 131072 == 2 * t49["NW"] * 8192 and t49["KG_STAGING_OFF"] == 65536
+    # (every wave issues LPT = 64 wave-loads / 8 waves = 8 pieces in the loop body, all of them in the one 32-k step in front of the
+    # mid-iteration barrier: `DIL_PER == 8 && NM == 16` in the 16 x 16 x 32 fragment loop.  4 is DIL_PER of the 32 x 32 x 16 build, below)
+    assert (t49["LPT"], t49["NDIL"], t49["DIL_STEPS"], t49["DIL_PER"], t49["S16"], t49["PRE_RESID"]) == (8, 8, 1, 8, 1, 1)
+
+    assert _one(rows, 44, F32)["LDS"] == 4 * 32768 == 131072
+    t15 = _one(rows, 15, F32)
+    assert t15["LDS"] == 3 * 32768 == 98304 and t15["S16"] == 1 and t15["PRE_RESID"] == 1
+    assert all(_one(rows, 15, F32, f8)["S16"] == 0 and _one(rows, 15, F32, f8)["LDS"] == 98304 + (f8 == 3) * 3 * 128 * 4 for f8 in (1, 2, 3))
+
+    t22 = _one(rows, 22, SWIGLU)
+    assert t22["LDS"] == 2 * 65536 + 512 * 8 == 135168 and t22["NT"] == 1024 and t22["PRE_RESID"] == 0
+    mx = _one(rows, 22, F32, 3)          # MXFP8 A operand: + one scale dword per A row per stage
+    assert (mx["STAGE_BYTES"], mx["LDS"], mx["SCALE_WAVES"], mx["MXA"]) == (66560, 133120, 4, 1)
+
+    xa = _one(rows, 256, HEADS)          # cross-attention: ring, LayerNorm constants, rounded up to 1 KiB, three 16-KiB K / V^T tiles
+    assert xa["XA_OFF"] == 75776 and xa["XA_LDS"] == 75776 + 3 * 16384 == 124928 and xa["LDS"] == 3 * 24576 + 192 * 8 and xa["DIL_ON"] == 0
+    t16 = _one(rows, 16, HEADS)          # the same geometry with the pieces in the MFMA stream (16-bit operands only)
+    assert (t16["DIL_ON"], t16["NDIL"], t16["DIL_STEPS"], t16["DIL_PER"]) == (1, 6, 3, 2) and _one(rows, 16, HEADS, 1)["DIL_ON"] == 0
+    # LayerNorm constants: 16-bit SwiGLU / heads builds only, (BM + BN) * 8 bytes behind the ring
+    for r in rows:
+        assert r["LN_CONS"] == (r["EPI"] in (SWIGLU, HEADS) and r["f8"] == 0), r
+    assert t30["LDS"] - t30["LN_OFF"] == 448 * 8 and t22["LDS"] - t22["LN_OFF"] == 512 * 8 and t15["LDS"] == t15["LN_OFF"]
+
+
+@needs_cxx
+def test_ring_geometry_of_the_32x32_build(tmp_path):
+    """-DSAT_RING_MFMA_32X32 (A/B builds): no tile on the 16 x 16 x 32 MFMA; the K-group tile spreads its pieces over two 16-k steps."""
+    exe = str(tmp_path / "gemm_host_dump_32")
+    subprocess.run(_host_cxx() + ["-O2", "-Wall", "-Wno-unknown-pragmas", "-DSAT_RING_MFMA_32X32", "-I", CSRC, DRIVER, "-o", exe], check=True, capture_output=True)
+    rows = _ring(exe)
+    assert not any(r["S16"] for r in rows) and all(r["MB"] == 1 for r in rows)
+    t49 = _one(rows, 49, F32)
+    assert (t49["NDIL"], t49["DIL_STEPS"], t49["DIL_PER"], t49["LDS"]) == (8, 2, 4, 131072)
+
+
+@needs_cxx
+@pytest.mark.parametrize("header", ["gemm_tiles.h", "ph8_sched.h", "gemm_ring_geom.h"])
 def test_headers_compile_alone_with_the_host_compiler(header, tmp_path):
     src = tmp_path / "alone.cpp"
     src.write_text(f'#include "{header}"\nint main() {{ return 0; }}\n')

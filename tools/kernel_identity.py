@@ -1,22 +1,35 @@
 """Are the kernels of one source file the same in two trees?  Compiles the file device-only to assembly in both (the Makefile's flags, each
-operand build) and compares kernel by kernel: the instruction stream with symbol names replaced by their demangled, namespace-free form, and
-the resource metadata.  A plain diff of two compilations; developer tool, no GPU.
+operand build the Makefile gives the file) and compares kernel by kernel: the instruction stream with symbol names replaced by their
+demangled, namespace-free form, and the resource metadata.  A plain diff of two compilations; developer tool, no GPU.
 
-usage: python tools/kernel_identity.py [--rename old=new]... <parent tree's csrc> [file.hip]      (default oobleck.hip; exit code 1 when a
-kernel differs; --rename: the parent's kernel `old`, named as the table prints it, is compared with the branch's kernel `new`)"""
+usage: python tools/kernel_identity.py [--rename old=new]... [--define NAME]... <parent tree's csrc> [file.hip]      (default oobleck.hip;
+exit code 1 when a kernel differs; --rename: the parent's kernel `old`, named as the table prints it, is compared with the branch's kernel
+`new`; --define: -DNAME on every compilation, e.g. SAT_GEMM_EXPERIMENTS for the `make exp` objects or SAT_RING_MFMA_32X32)"""
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "friendly-stable-audio-tools_amd", "csrc")
 HIPCC, FILT = "/opt/rocm/bin/hipcc", "c++filt"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "--cuda-device-only", "-S"]
-BUILDS = {"bf16": [], "fp16": ["-DSAT_OPERAND_F16"], "fp32": ["-DSAT_OPERAND_F32"]}
 META = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size",
         "kernarg_segment_size")
+
+
+def builds_of(src):
+    """the operand builds the Makefile compiles `src` in: bf16 always, fp16 for the files of DUAL, fp32 for those of TRIPLE"""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    listed = lambda var: src in re.search(r"^%s\s*=(.*)$" % var, mk, re.M).group(1).split()
+    res = {"bf16": []}
+    if listed("DUAL"):
+        res["fp16"] = ["-DSAT_OPERAND_F16"]
+    if listed("TRIPLE"):
+        res["fp32"] = ["-DSAT_OPERAND_F32"]
+    return res
 
 
 def plain(names):
@@ -53,16 +66,28 @@ def kernels(csrc, src, defs, workdir, rename={}):
 
 
 def main():
-    argv, rename = sys.argv[1:], {}
-    while argv and argv[0] == "--rename":
-        old, new = argv[1].split("=", 1)
-        rename[old] = new
+    argv, rename, defines = sys.argv[1:], {}, []
+    while argv and argv[0] in ("--rename", "--define"):
+        if argv[0] == "--rename":
+            old, new = argv[1].split("=", 1)
+            rename[old] = new
+        else:
+            defines.append("-D" + argv[1])
         argv = argv[2:]
     parent, src = argv[0], argv[1] if len(argv) > 1 else "oobleck.hip"
     bad = 0
-    for build, defs in BUILDS.items():
-        with tempfile.TemporaryDirectory() as d:
-            (old, cmd), (new, _) = kernels(parent, src, defs, d, rename), kernels(CSRC, src, defs, d)
+    builds = builds_of(src)
+    with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(2 * len(builds)) as pool:
+        # the compilations are independent of each other: all of them at once, each into a directory of its own
+        jobs = {}
+        for build, defs in builds.items():
+            for side, csrc, ren in (("old", parent, rename), ("new", CSRC, {})):
+                wd = os.path.join(d, build + side)
+                os.mkdir(wd)
+                jobs[build, side] = pool.submit(kernels, csrc, src, defs + defines, wd, ren)
+        done = {k: j.result() for k, j in jobs.items()}
+    for build in builds:
+        (old, cmd), (new, _) = done[build, "old"], done[build, "new"]
         print(f"== {build}: {cmd}")
         print(f"{'kernel':44s} {'instr':>6s} " + " ".join(f"{k.replace('_segment', '').replace('_fixed_size', '').replace('_count', ''):>10s}" for k in META) + "  stream  metadata")
         same = sorted(old) == sorted(new)
